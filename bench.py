@@ -31,13 +31,6 @@ import os
 import sys
 import time
 
-# The solve keeps up to four window groups in flight on separate HIP streams.  ROCm maps the streams of a process onto
-# GPU_MAX_HW_QUEUES hardware queues (default 4); once RCCL has created its own streams, several of ours share a queue and
-# serialise (measured: 4240 -> 3580 windows/s on one GPU with an initialised process group).  Must be set before HIP initialises.
-# 16, not 8: the `e2e` leg runs two more contexts (five streams each) next to the resident one; with 8 queues their uploads shared a
-# queue with another lane's group streams and a solve's turn took 70 ms instead of 55 (e2e 3550 -> 4150 windows/s, `value` unchanged).
-os.environ.setdefault("GPU_MAX_HW_QUEUES", "16")
-
 ROOT = os.path.dirname(os.path.abspath(__file__))
 for _p in (ROOT, os.path.join(ROOT, "oracle")):
     if _p not in sys.path:
@@ -485,6 +478,46 @@ def secondary_block(ctx, dev, repeats=5):
     return out
 
 
+# ================================================================================================== --dump-outputs
+DUMP_BYTES_MAX = 64 * 10 ** 6       # every file of one dump together, .npy headers included
+DUMP_SAMPLE_SEED = 0x0D0D
+
+
+def dump_outputs(path, batch):
+    """What the last solve handed its caller (lld_ba_batch_download_range over the batch) as DIR/<name>.npy: float64, the 0/1 outlier flags float32.
+    Poses and statistics of every window; landmarks, lines and outlier flags of a seeded sample of windows (sample_window_ids.npy), as many
+    as fit in DUMP_BYTES_MAX.  Per-window arrays are concatenated along their first axis in window order."""
+    import numpy as np
+    outs = batch.download_all()
+    stats = [o.stats for o in outs]
+    files = {"cam_qt": np.concatenate([o.cam_qt for o in outs])}
+    for k in stats[0]:
+        files["stats_" + k] = np.array([s[k] for s in stats], dtype=np.float64)
+
+    def window_arrays(o):
+        return {"pt_xyz": o.pt_xyz, "line_x0": o.line_x0, "line_dir": o.line_dir, "pt_obs_outlier": o.pt_obs_outlier.astype(np.float32),
+                "ln_edge_outlier": o.ln_edge_outlier.astype(np.float32), "line_removed": o.line_removed.astype(np.float32)}
+    header = 128
+    used = sum(a.nbytes + header for a in files.values()) + 7 * header + 8 * len(outs)     # + the sampled files' headers and the id list
+    ids = []
+    for i in np.random.default_rng(DUMP_SAMPLE_SEED).permutation(len(outs)):
+        nb = sum(a.nbytes for a in window_arrays(outs[i]).values())
+        if used + nb > DUMP_BYTES_MAX:
+            break
+        used += nb; ids.append(int(i))
+    if not ids:
+        raise SystemExit(f"--dump-outputs: not even one window's landmarks fit in {DUMP_BYTES_MAX} bytes")
+    ids.sort()
+    files["sample_window_ids"] = np.array(ids, dtype=np.float64)
+    per = [window_arrays(outs[i]) for i in ids]
+    for k in per[0]:
+        files[k] = np.concatenate([p[k] for p in per])
+    os.makedirs(path, exist_ok=True)
+    for k, a in files.items():
+        np.save(os.path.join(path, k + ".npy"), np.ascontiguousarray(a))
+    return {"dir": path, "files": len(files), "bytes": sum(os.path.getsize(os.path.join(path, k + ".npy")) for k in files), "windows": len(outs), "sampled_windows": len(ids)}
+
+
 # ================================================================================================== host buffers in -> results out
 def e2e_block(windows, device, lanes=3, batches_per_lane=16):
     """Steady-state rate at the C ABI with HOST buffers on both sides: `lanes` host threads, each with its own context, loop
@@ -563,7 +596,10 @@ def main():
     ap.add_argument("--groups", type=int, default=0, help="stream groups of the timed solves (0 = the library's choice; 1 under rocprofv3: per-kernel times of one stream)")
     ap.add_argument("--gen-workers", type=int, default=0, help="processes generating the synthetic windows (0 = auto; use 1 under rocprofv3)")
     ap.add_argument("--no-rccl-check", action="store_true", help="N = 1: skip the untimed step through a one-rank RCCL group (profiling runs: no RCCL kernels in the trace)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="after the timed steps, write what the last one computed (rank 0's windows) as DIR/<name>.npy")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        raise SystemExit("--steps must be >= 1 and --warmup >= 0")
 
     rank = int(os.environ.get("RANK", "0")); world = int(os.environ.get("WORLD_SIZE", "1"))
     local_rank = int(os.environ.get("LOCAL_RANK", "0"))
@@ -643,6 +679,7 @@ def main():
     gather.drain()                        # the last gather is inside the timed region
     D.barrier(use_dist, True)
     elapsed = time.perf_counter() - t0
+    dumped = dump_outputs(args.dump_outputs, batch) if args.dump_outputs and rank == 0 else None     # before any further solve overwrites them
     # Roofline pass (untimed): the timed steps keep several window groups in flight on separate streams, so their HIP-event
     # brackets overlap; one more step with a single group gives disjoint per-kernel-family event times on that stream.
     # Per-phase events are off in the timed steps, as in the product's default (lld_ba_batch_set_phase_timing: six event records per
@@ -857,6 +894,7 @@ def main():
             # one rank, measured: what the asynchronous RCCL gather of every step costs the solve it overlaps (null under a launcher: there the
             # gather IS inside `value`); DESIGN.md 5 states the policy that follows from it
             "rccl_overhead": rccl_overhead,
+            "dumped_outputs": dumped,
         }
     batch.close()
     if world > 1 and not args.no_secondary:

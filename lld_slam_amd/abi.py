@@ -196,11 +196,6 @@ PRODUCT_SYMBOLS = [
 ]
 
 
-# see bench.py: more hardware queues than the default 4, so that the library's group streams do not share a queue with the caller's
-# other streams (effective only if HIP has not been initialised yet)
-os.environ.setdefault("GPU_MAX_HW_QUEUES", "16")
-
-
 def product_library_path() -> str:
     if os.environ.get("LLD_AMD_LIB"):          # kernel experiments: an alternative build of the same ABI
         return os.environ["LLD_AMD_LIB"]

@@ -1,6 +1,6 @@
-import re, sys
+import os, re, sys
 from collections import Counter
-s=open('/root/repo/build/lld_ba.s').read()
+s=open(os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), 'build', 'lld_ba.s')).read()     # tools/kernel_regs.sh lld_ba writes it
 for name in ['ba_linearize_pt_kernel','ba_linearize_ln_kernel','ba_backsub_pt_kernel','ba_backsub_ln_kernel']:
     i=s.index('\n_ZN5lldba%d%s'%(len(name),name)+'E')
     i=s.index(':\n',i)
