@@ -970,6 +970,111 @@ int lld_compute_stereo_matches(lld_ctx* ctx, const lld_keypoints* left, const ll
  * launch: one workgroup per problem, all inputs moved in one host-to-device copy and all outputs in one copy back. */
 int lld_orb_search_batch(lld_ctx* ctx, int n, const lld_orb_search* problems, lld_orb_search_result* outs);
 
+
+/* ------------------------------------------------------------------ ORBextractor::operator(), whole routine
+ * src/ORBextractor.cc:1043-1105 with what it calls: ComputePyramid (:1107-1132), ComputeKeyPointsOctTree (:765-852),
+ * DistributeOctTree (:539-763, DivideNode :480-537), computeOrientation / IC_Angle (:77-104), the blur (:1085-1086) and
+ * computeOrbDescriptor (:108-148).  A handle holds the level tables, the device buffers (sized once from max_cols / max_rows /
+ * max_images) and the last pyramid, which lld_compute_stereo_matches can read in place (lld_orb_extractor_pyramids).
+ * Everything is integer or single-rounding float work: results are bit-exact against the CPU restatement
+ * (tests/orb_extract_ref.py).  OpenCV is restated as follows (parity with OpenCV itself unpinned):
+ *   Level tables (:411-470): mvScaleFactor[l] = cumulative float products, inverse = 1.0f / factor, sigma2 = factor^2;
+ *     nDesiredFeaturesPerScale = nfeatures*(1-f)/(1-(float)pow((double)f, n_levels)) in float (f = 1.0f/scale_factor),
+ *     mnFeaturesPerLevel[l] = cvRound of it (then *= f), the remainder (>= 0) to the last level; umax as the constructor.
+ *   Pyramid: level 0 is the image; level l = resize(level l-1) to cvRound((float)cols*inv[l]) x cvRound((float)rows*inv[l])
+ *     (cvRound = round half to even).  Bilinear, 8-bit fixed point: per axis scale = 1.0/((double)dsize/ssize),
+ *     f = (float)((d+0.5)*scale - 0.5) in double without contraction, s = floor(f), f -= s; s < 0 -> s = 0, f = 0;
+ *     s >= ssize-1 -> s = ssize-1, f = 0; c1 = cvRound(f*2048), c0 = 2048-c1 (11-bit coefficients); horizontal pass
+ *     h = c0*S[s] + c1*S[s+1] on the two source rows, vertical v = b0*h0 + b1*h1, pixel = (v + 2^21) >> 22.  The bordered copy
+ *     (copyMakeBorder) is never read by the extractor or the stereo SAD and is not kept.
+ *   FAST (:765-832): score(p) = (largest m such that 9 contiguous pixels of the 16-pixel Bresenham circle of radius 3 all differ
+ *     from p by >= m in the same direction) - 1; p is a corner at threshold t iff score >= t (strict > p+t / < p-t).  Per 30-px
+ *     cell (the reference's wCell / hCell, +6 overlap, asymmetric skips iniY >= maxBorderY-3 and iniX >= maxBorderX-6, clipping
+ *     to maxBorder) detection and non-maximum suppression run INSIDE the cell's sub-image: only pixels >= 3 from its edges are
+ *     tested, a neighbour outside that interior or not a corner at the cell's threshold counts as 0, a corner is kept iff its score
+ *     is > all 8 neighbours.  Row-major within a cell, cells row-major; a pixel in the overlap of two cells appears twice (both
+ *     kept).  min_th_fast is retried only in cells that found nothing at ini_th_fast.  response = (float)score.
+ *   DistributeOctTree: the reference's list semantics (push_front of n1..n4, erasure of split nodes, bNoMore at size 1, stop at
+ *     size >= N or unchanged size, sorted phase from the largest node down breaking at size >= N; each node keeps the first key of
+ *     strictly greatest response in candidate order).  DEVIATION (the reference is not deterministic here): its sort of
+ *     pair<size, ExtractorNode*> orders nodes of equal size by heap address; here a node created later counts as the larger, i.e.
+ *     equal sizes are split in reverse creation (push) order.  A level returns up to max(N+3, 4*nIni) keypoints (no trimming;
+ *     N+3 whenever 4*round(w/h) <= N+3, e.g. for every level of KITTI at nfeatures = 2000).
+ *   IC_Angle: integer moments over the umax disc of the unblurred level; fastAtan2 as OpenCV's float polynomial (degrees, [0,360)):
+ *     c = min/(max + (float)DBL_EPSILON), a = (((p7 c^2 + p5) c^2 + p3) c^2 + p1) c with p_k = (float)coef_k * (float)(180/pi),
+ *     90-a when |y| > |x|, 180-a for x < 0, 360-a for y < 0; every float operation rounded separately.
+ *   Blur: GaussianBlur(7x7, sigma 2, BORDER_REFLECT_101) restated as a documented integer filter (not OpenCV's own fixed point):
+ *     separable Q8 kernel {18, 34, 49, 54, 49, 34, 18} (round(256*g_i) of the normalised Gaussian, the centre lowered by one so the
+ *     taps sum to 256), horizontal then vertical in exact integers, pixel = (sum + 32768) >> 16, reflect-101 on the level's pixels.
+ *   Descriptor: a = cosf(angle*factorPI), b = sinf(...) as glibc >= 2.28 computes them (restated in csrc/lld_glibc_sincosf.h,
+ *     checked equal to this host's libm for every float angle in [0, 360): profiles/orb_sincosf_check.txt); offsets
+ *     cvRound(x*b + y*a), cvRound(x*a - y*b) with every float operation rounded separately (no FMA).
+ * Size limits: 62 <= each level's cols and rows (every level must give nCols, nRows and round(w/h) >= 1; checked on the host),
+ * cols, rows <= max_cols, max_rows <= 16383; 1 <= n_levels <= LLD_ORB_MAX_LEVELS; thresholds in [1, 255]; 1 < scale_factor;
+ * pattern coordinates |c| <= 13 (13*sqrt(2) rounds below EDGE_THRESHOLD = 19, so no descriptor read leaves the level).
+ * No limit on the candidate count: every per-level buffer is sized from the level's area at create time. */
+typedef struct lld_orb_extractor lld_orb_extractor;
+typedef struct {
+  int32_t nfeatures;
+  float   scale_factor;
+  int32_t n_levels;
+  int32_t ini_th_fast;
+  int32_t min_th_fast;
+  int32_t max_cols, max_rows;     /* largest level-0 image a call may pass            */
+  int32_t max_images;             /* images per lld_orb_extract call (e.g. 2: stereo) */
+  const int32_t* pattern;         /* [512][2] = ORBextractor::pattern (256 point pairs, x then y), copied at create */
+} lld_orb_extractor_params;
+typedef struct {
+  int32_t n_levels;
+  int32_t max_keypoints;          /* capacity an lld_orb_features must have for an image of max_cols x max_rows:
+                                     sum over levels of max(N_l + 3, 4*nIni_l); nfeatures + 3*n_levels for the usual sizes */
+  float   scale_factor[LLD_ORB_MAX_LEVELS];       /* mvScaleFactor    */
+  float   inv_scale_factor[LLD_ORB_MAX_LEVELS];   /* mvInvScaleFactor */
+  float   level_sigma2[LLD_ORB_MAX_LEVELS];       /* mvLevelSigma2    */
+  float   inv_level_sigma2[LLD_ORB_MAX_LEVELS];   /* mvInvLevelSigma2 */
+  int32_t features_per_level[LLD_ORB_MAX_LEVELS]; /* mnFeaturesPerLevel */
+  int32_t umax[16];                               /* HALF_PATCH_SIZE + 1 entries */
+} lld_orb_extractor_levels;
+typedef struct {
+  const uint8_t* data;            /* CV_8UC1 pixels, host or (on_device = 1) HBM */
+  int32_t cols, rows, step;       /* step: bytes per row                         */
+  int32_t on_device;
+} lld_orb_image;
+typedef struct {                  /* per (image, level), optional */
+  int32_t n_candidates;           /* FAST keypoints handed to DistributeOctTree  */
+  int32_t cells_min_th;           /* cells that found nothing at ini_th_fast     */
+  int32_t cells_empty;            /* cells that found nothing at min_th_fast too */
+  int32_t iterations;             /* passes of the outer loop (`iteration`)      */
+  int32_t sorted_rounds;          /* passes of the sorted-split loop (:673-738)  */
+  int32_t finish_unchanged;       /* 1: the loop ended because the size did not change (not size >= N) */
+  int32_t n_keypoints;            /* final node count = keypoints of the level   */
+  int32_t features_wanted;        /* N = mnFeaturesPerLevel[level]               */
+} lld_orb_level_stats;
+typedef struct {
+  int32_t  capacity;              /* in: entries the arrays hold (>= lld_orb_extractor_levels.max_keypoints)   */
+  int32_t  n;                     /* out: keypoints, level by level, within a level in the final lNodes order   */
+  float*   xy;                    /* [capacity][2] pt, scaled to level 0 by the float multiply of :1094-1101    */
+  int32_t* octave;                /* [capacity]                                                                 */
+  float*   angle;                 /* [capacity] degrees                                                         */
+  float*   response;              /* [capacity]                                                                 */
+  float*   size;                  /* [capacity] (float)(int)(PATCH_SIZE * mvScaleFactor[level])                 */
+  uint32_t* desc;                 /* [capacity][8] rBRIEF, byte order of mDescriptors.data                      */
+  lld_orb_level_stats* stats;     /* [n_levels] or NULL                                                         */
+} lld_orb_features;
+int  lld_orb_extractor_create(lld_ctx* ctx, const lld_orb_extractor_params* params, lld_orb_extractor** out);
+void lld_orb_extractor_destroy(lld_orb_extractor* ex);
+int  lld_orb_extractor_levels_get(const lld_orb_extractor* ex, lld_orb_extractor_levels* out);
+/* Extracts n_images (1 <= n_images <= max_images) images in one sequence of launches on the context's stream; returns after the
+ * results are on the host.  Invalid sizes, nulls, too many images or too small an output capacity return LLD_ERR_INVALID before
+ * anything is queued. */
+int  lld_orb_extract(lld_orb_extractor* ex, int n_images, const lld_orb_image* images, lld_orb_features* outs);
+/* The pyramid of image `image_index` of the last lld_orb_extract as device pointers: fills n_levels, cols, rows and steps and
+ * sets on_device = 1.  `left` or `right` (whichever is non-NULL) receives the level pointers, `step` the matching step array, so
+ * two calls (image 0 -> left, image 1 -> right) build the struct lld_compute_stereo_matches reads.  The arrays pointed to must
+ * hold n_levels entries.  Valid until the next lld_orb_extract on the handle or lld_orb_extractor_destroy. */
+int  lld_orb_extractor_pyramids(const lld_orb_extractor* ex, int image_index, const uint8_t** levels, int32_t* cols, int32_t* rows,
+                                int32_t* step);
+
 #if defined(__GNUC__)
 #pragma GCC visibility pop
 #endif

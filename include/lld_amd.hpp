@@ -421,5 +421,55 @@ class TrackedFrame {
   int nt_, nl_;
 };
 
+// Mirror of `class ORBextractor` (include/ORBextractor.h:45-110): the reference's constructor plus the caller's `pattern`
+// (512 cv::Point as x, y ints) and the largest image it will see; operator() on one image or a stereo pair.  The level tables
+// (mvScaleFactor ...) come from levels(); the pyramid of the last call stays on the device for lld_compute_stereo_matches.
+struct ORBFeatures {
+  std::vector<float> xy, angle, response, size;       // xy: [n][2]
+  std::vector<int32_t> octave;
+  std::vector<uint32_t> desc;                         // [n][8], the byte order of mDescriptors.data
+  std::vector<lld_orb_level_stats> stats;             // per level
+  int n() const { return (int)octave.size(); }
+};
+class ORBextractor {
+ public:
+  ORBextractor(Context& ctx, int nfeatures, float scaleFactor, int nlevels, int iniThFAST, int minThFAST, const int32_t* pattern,
+               int max_cols, int max_rows, int max_images = 2) {
+    lld_orb_extractor_params p{};
+    p.nfeatures = nfeatures; p.scale_factor = scaleFactor; p.n_levels = nlevels; p.ini_th_fast = iniThFAST; p.min_th_fast = minThFAST;
+    p.max_cols = max_cols; p.max_rows = max_rows; p.max_images = max_images; p.pattern = pattern;
+    check(lld_orb_extractor_create(ctx.get(), &p, &h_), "lld_orb_extractor_create");
+    check(lld_orb_extractor_levels_get(h_, &levels_), "lld_orb_extractor_levels_get");
+  }
+  ~ORBextractor() { lld_orb_extractor_destroy(h_); }
+  ORBextractor(const ORBextractor&) = delete;
+  ORBextractor& operator=(const ORBextractor&) = delete;
+  const lld_orb_extractor_levels& levels() const { return levels_; }
+  lld_orb_extractor* get() const { return h_; }
+  // images: host (on_device = 0) or HBM pixels; one ORBFeatures per image
+  std::vector<ORBFeatures> operator()(const std::vector<lld_orb_image>& images) {
+    const int cap = levels_.max_keypoints;
+    std::vector<ORBFeatures> out(images.size());
+    std::vector<lld_orb_features> f(images.size());
+    for (size_t i = 0; i < images.size(); i++) {
+      ORBFeatures& o = out[i];
+      o.xy.resize((size_t)cap * 2); o.angle.resize(cap); o.response.resize(cap); o.size.resize(cap); o.octave.resize(cap);
+      o.desc.resize((size_t)cap * 8); o.stats.resize(levels_.n_levels);
+      f[i] = lld_orb_features{cap, 0, o.xy.data(), o.octave.data(), o.angle.data(), o.response.data(), o.size.data(), o.desc.data(),
+                              o.stats.data()};
+    }
+    check(lld_orb_extract(h_, (int)images.size(), images.data(), f.data()), "lld_orb_extract");
+    for (size_t i = 0; i < images.size(); i++) {
+      const int n = f[i].n;
+      ORBFeatures& o = out[i];
+      o.xy.resize((size_t)n * 2); o.angle.resize(n); o.response.resize(n); o.size.resize(n); o.octave.resize(n); o.desc.resize((size_t)n * 8);
+    }
+    return out;
+  }
+ private:
+  lld_orb_extractor* h_ = nullptr;
+  lld_orb_extractor_levels levels_{};
+};
+
 }  // namespace lld_amd
 #endif
