@@ -1074,6 +1074,108 @@ int  lld_orb_extract(lld_orb_extractor* ex, int n_images, const lld_orb_image* i
  * hold n_levels entries.  Valid until the next lld_orb_extract on the handle or lld_orb_extractor_destroy. */
 int  lld_orb_extractor_pyramids(const lld_orb_extractor* ex, int image_index, const uint8_t** levels, int32_t* cols, int32_t* rows,
                                 int32_t* step);
+/* The rBRIEF descriptors of image `image_index` of the last lld_orb_extract as a device pointer: *desc = [n][8] u32 in HBM (the
+ * byte order of mDescriptors.data), *n = that image's keypoint count.  Valid under the same rule as lld_orb_extractor_pyramids;
+ * lld_bow_transform reads it with on_device = 1, so extract -> transform never leaves the device. */
+int  lld_orb_extractor_descriptors(const lld_orb_extractor* ex, int image_index, const uint32_t** desc, int32_t* n);
+
+
+/* ------------------------------------------------------------------ DBoW2 vocabulary: load, transform, L1 score
+ * Thirdparty/DBoW2/DBoW2/ of the reference, as ORB-SLAM2 uses it (ORBVocabulary = TemplatedVocabulary<FORB::TDescriptor, FORB>).
+ * Every value is bit-exact against the CPU restatement tests/bow_ref.py.  Restated rules:
+ *   Loader (TemplatedVocabulary.h:1338-1424, loadFromTextFile): line 1 is `k L scoring weighting`, refused unless 0 <= k <= 20,
+ *     1 <= L <= 10, 0 <= scoring <= 5, 0 <= weighting <= 3 (:1358).  Every following line is one node `parent isLeaf d0 .. d31
+ *     weight` and its node id is its line index (root = node 0, :1375-1381); the children of a node are its child lines in file
+ *     order (:1384); word ids number the lines with isLeaf > 0 in file order (:1402-1409); a descriptor byte is (unsigned char)
+ *     of the decimal int (FORB.cpp:120-135); weight is a double.  isLeaf() of a node means "has no children" (:328).
+ *   Descent (:1218-1256): from the root, each level's children in order, distance = FORB::distance (FORB.cpp:81-101, the 256-bit
+ *     Hamming distance), strict `<` (on equal distances the first child in order wins); the node reached at level m_L - levelsup
+ *     is nid (m_L - levelsup <= 0: the root, :1227); the descent stops at the first node without children and returns its
+ *     word_id and weight.
+ *   Transform (:1127-1194, levelsup = 4 at every call site of ORB-SLAM2): features in index order; weight w > 0 goes into both
+ *     vectors, anything else is a stop word and goes into neither.  TF / TF_IDF: BowVector::addWeight (BowVector.cpp:34-46), the
+ *     repeated hits of a word add w again and again in feature order (repeated addition, not count*w); IDF / BINARY:
+ *     addIfNotExist (:50-58).  FeatureVector::addFeature (FeatureVector.cpp:31-45): nodes ascending, feature indices ascending
+ *     within a node.  Then normalize (BowVector.cpp:62-84), L1: norm = sequential sum of fabs(v) in ascending word id, then
+ *     v /= norm for every word if norm > 0.  L1 scoring always normalises (ScoringObject.h:74), so the `/= nd` branch never runs.
+ *   Score (ScoringObject.cpp:23-66, L1Scoring::score(v1 = query, v2 = candidate)): the common words in ascending id,
+ *     score += fabs(vi - wi) - fabs(vi) - fabs(wi) left to right, then score = -score/2.0 (no common word: -0.0).
+ * DEVIATIONS (the reference is undefined here):
+ *   - nid is declared uninitialised per feature (:1151, :1179): a descent that reaches a leaf above level m_L - levelsup adds the
+ *     feature under an indeterminate node.  Here it goes under the leaf's own node id.
+ *   - A file ending in a newline makes the reference's `while(!f.eof())` parse one more, empty line: a childless non-word child of
+ *     the root with weight 0 and a descriptor FORB::fromString leaves uninitialised (features that land on it are dropped).  This
+ *     loader skips blank lines (whitespace only) and adds no such node.
+ * Limits: lld_bow_vocab_create refuses (LLD_ERR_INVALID, nothing allocated) a tree where node 0 is not the root or parent[i] >= i,
+ * a leaf flag that disagrees with "has no children", a node with more than LLD_BOW_MAX_CHILDREN children, a leaf deeper than
+ * LLD_BOW_MAX_DEPTH, fewer than 2 nodes, or weighting outside 0..3; scoring other than L1_NORM returns LLD_ERR_UNSUPPORTED.
+ * A vocabulary handle is driven by one host thread at a time (it runs on its context's stream). */
+#define LLD_BOW_MAX_FEATURES 8192        /* descriptors per set of one lld_bow_transform call */
+#define LLD_BOW_MAX_CHILDREN 64
+#define LLD_BOW_MAX_DEPTH 16
+#define LLD_BOW_L1_NORM 0                /* DBoW2::ScoringType: L1_NORM, L2_NORM, CHI_SQUARE, KL, BHATTACHARYYA, DOT_PRODUCT */
+#define LLD_BOW_TF_IDF 0                 /* DBoW2::WeightingType: TF_IDF, TF, IDF, BINARY */
+#define LLD_BOW_TF 1
+#define LLD_BOW_IDF 2
+#define LLD_BOW_BINARY 3
+typedef struct lld_bow_vocab lld_bow_vocab;
+typedef struct {
+  int32_t k, L, scoring, weighting;      /* the header line                                     */
+  int32_t n_nodes;                       /* root included                                       */
+  int32_t n_words;                       /* lines with isLeaf > 0                               */
+  int32_t* parent;                       /* [n_nodes]; parent[0] = -1 (the root has no line)    */
+  uint8_t* is_leaf;                      /* [n_nodes] the file flag (> 0 -> 1); is_leaf[0] = 0  */
+  uint32_t* desc;                        /* [n_nodes][8] u32, byte order of the text; root zero */
+  double* weight;                        /* [n_nodes]; weight[0] = 0                            */
+} lld_bow_vocab_desc;
+typedef struct {
+  int32_t k, L, scoring, weighting, n_nodes, n_words;
+  int32_t min_leaf_depth;                /* shallowest word (root = depth 0)                    */
+  int32_t max_depth;
+  int32_t max_sets, max_features;        /* as created                                          */
+} lld_bow_vocab_info;
+typedef struct {
+  const uint32_t* desc;                  /* [n][8] u32: host or (on_device = 1) HBM             */
+  int32_t n;                             /* 0 <= n <= the vocabulary's max_features             */
+  int32_t on_device;
+  int32_t levelsup;                      /* 4 at every ORB-SLAM2 call site                      */
+  int32_t reserved;
+} lld_bow_set;
+typedef struct {                         /* every array holds the set's n entries (node_start n + 1) */
+  int32_t n_words;                       /* out: BowVector size                                  */
+  int32_t* word;                         /* [n] ascending word ids                               */
+  double* value;                         /* [n] L1-normalised values                             */
+  int32_t n_nodes;                       /* out: FeatureVector size                              */
+  int32_t* node;                         /* [n] ascending node ids                               */
+  int32_t* node_start;                   /* [n + 1] CSR over `feature`                           */
+  int32_t* feature;                      /* [n] feature indices, ascending within a node         */
+  int32_t* feature_word;                 /* [n] or NULL: word id per feature, -1 = stop word     */
+  int32_t* feature_nid;                  /* [n] or NULL: nid per feature (also for stop words)   */
+} lld_bow_result;
+typedef struct {
+  int32_t n;                             /* words                                                */
+  const int32_t* word;                   /* [n] strictly ascending, each in [0, n_words)         */
+  const double* value;                   /* [n]                                                  */
+} lld_bow_vector;
+/* Host only (no context, no GPU): reads a DBoW2 text vocabulary in two calls.  With d->parent == NULL it fills k, L, scoring,
+ * weighting, n_nodes and n_words; with all four arrays set (n_nodes entries each) it fills them.  Returns LLD_ERR_INVALID for a
+ * missing file, a refused header, a malformed node line or a parent that is not an earlier node. */
+int  lld_bow_vocab_read_text(const char* path, lld_bow_vocab_desc* d);
+/* Validates the tree (see Limits) before anything is allocated, then uploads it into one device slab sized for max_sets sets of
+ * up to max_features (1 <= max_features <= LLD_BOW_MAX_FEATURES) descriptors. */
+int  lld_bow_vocab_create(lld_ctx* ctx, const lld_bow_vocab_desc* d, int max_sets, int max_features, lld_bow_vocab** out);
+void lld_bow_vocab_destroy(lld_bow_vocab* v);
+int  lld_bow_vocab_info_get(const lld_bow_vocab* v, lld_bow_vocab_info* out);
+/* TemplatedVocabulary::transform(features, BowVector, FeatureVector, levelsup) for n_sets (1..max_sets) sets in one sequence of
+ * launches; returns with the results on the host.  Nulls, n outside 0..max_features or too many sets return LLD_ERR_INVALID
+ * before anything is queued. */
+int  lld_bow_transform(lld_bow_vocab* v, int n_sets, const lld_bow_set* sets, lld_bow_result* results);
+/* L1Scoring::score(query, candidate c) for n_cand candidates given as CSR: candidate c holds the words
+ * cand_word[cand_start[c] .. cand_start[c+1]) (strictly ascending, each in [0, n_words)) with cand_value.  One upload, one
+ * launch, out[c] on return.  Malformed vectors return LLD_ERR_INVALID before anything is queued.  Staging uses the context's
+ * grow-only device scratch. */
+int  lld_bow_score(lld_bow_vocab* v, const lld_bow_vector* query, int n_cand, const int32_t* cand_start, const int32_t* cand_word,
+                   const double* cand_value, double* out);
 
 #if defined(__GNUC__)
 #pragma GCC visibility pop

@@ -8,6 +8,7 @@
 #define LLD_AMD_HPP
 
 #include <cstdint>
+#include <map>
 #include <stdexcept>
 #include <string>
 #include <vector>
@@ -469,6 +470,81 @@ class ORBextractor {
  private:
   lld_orb_extractor* h_ = nullptr;
   lld_orb_extractor_levels levels_{};
+};
+
+// Mirror of ORBVocabulary = DBoW2::TemplatedVocabulary<FORB::TDescriptor, FORB> (Thirdparty/DBoW2/DBoW2/TemplatedVocabulary.h):
+// loadFromTextFile, transform(features, BowVector&, FeatureVector&, levelsup) and score, with the L1 scoring ORB-SLAM2 uses.  The
+// vectors have DBoW2's shapes (BowVector.h, FeatureVector.h); features are [n][8] u32 rows (the bytes of mDescriptors.data), on the
+// host or (transform_device) in HBM, e.g. lld_orb_extractor_descriptors.  Results are those of include/lld_amd.h's restatement.
+class BowVector : public std::map<unsigned int, double> {};
+class FeatureVector : public std::map<unsigned int, std::vector<unsigned int> > {};
+class ORBVocabulary {
+ public:
+  explicit ORBVocabulary(Context& ctx, int max_sets = 2, int max_features = LLD_BOW_MAX_FEATURES)
+      : ctx_(ctx), max_sets_(max_sets), max_features_(max_features) {}
+  ~ORBVocabulary() { lld_bow_vocab_destroy(h_); }
+  ORBVocabulary(const ORBVocabulary&) = delete;
+  ORBVocabulary& operator=(const ORBVocabulary&) = delete;
+  // false where the file is refused (the reference's header checks, a malformed line) or the tree cannot be uploaded
+  bool loadFromTextFile(const std::string& filename) {
+    lld_bow_vocab_desc d{};
+    if (lld_bow_vocab_read_text(filename.c_str(), &d) != LLD_OK) return false;
+    std::vector<int32_t> parent(d.n_nodes);
+    std::vector<uint8_t> leaf(d.n_nodes);
+    std::vector<uint32_t> desc((size_t)d.n_nodes * 8);
+    std::vector<double> weight(d.n_nodes);
+    d.parent = parent.data(); d.is_leaf = leaf.data(); d.desc = desc.data(); d.weight = weight.data();
+    if (lld_bow_vocab_read_text(filename.c_str(), &d) != LLD_OK) return false;
+    lld_bow_vocab* h = nullptr;
+    if (lld_bow_vocab_create(ctx_.get(), &d, max_sets_, max_features_, &h) != LLD_OK) return false;
+    lld_bow_vocab_destroy(h_);
+    h_ = h;
+    check(lld_bow_vocab_info_get(h_, &info_), "lld_bow_vocab_info_get");
+    return true;
+  }
+  bool empty() const { return h_ == nullptr || info_.n_words == 0; }
+  unsigned int size() const { return (unsigned int)info_.n_words; }
+  int getBranchingFactor() const { return info_.k; }
+  int getDepthLevels() const { return info_.L; }
+  const lld_bow_vocab_info& info() const { return info_; }
+  lld_bow_vocab* get() const { return h_; }
+  void transform(const std::vector<uint32_t>& features, BowVector& v, FeatureVector& fv, int levelsup) const {
+    transform_set(features.data(), (int)(features.size() / 8), 0, levelsup, v, fv);
+  }
+  // features already in HBM (on_device = 1)
+  void transform_device(const uint32_t* d_features, int n, BowVector& v, FeatureVector& fv, int levelsup) const {
+    transform_set(d_features, n, 1, levelsup, v, fv);
+  }
+  double score(const BowVector& a, const BowVector& b) const {
+    std::vector<int32_t> qw, cw, start{0};
+    std::vector<double> qv, cv;
+    for (BowVector::const_iterator it = a.begin(); it != a.end(); ++it) { qw.push_back((int32_t)it->first); qv.push_back(it->second); }
+    for (BowVector::const_iterator it = b.begin(); it != b.end(); ++it) { cw.push_back((int32_t)it->first); cv.push_back(it->second); }
+    start.push_back((int32_t)cw.size());
+    lld_bow_vector q{(int32_t)qw.size(), qw.data(), qv.data()};
+    double out = 0.0;
+    check(lld_bow_score(h_, &q, 1, start.data(), cw.data(), cv.data(), &out), "lld_bow_score");
+    return out;
+  }
+ private:
+  void transform_set(const uint32_t* desc, int n, int on_device, int levelsup, BowVector& v, FeatureVector& fv) const {
+    v.clear(); fv.clear();
+    if (empty()) throw std::runtime_error("ORBVocabulary::transform: no vocabulary loaded");
+    const size_t m = (size_t)(n > 0 ? n : 1);
+    std::vector<int32_t> word(m), node(m), start(m + 1), feature(m);
+    std::vector<double> value(m);
+    lld_bow_set s{desc, n, on_device, levelsup, 0};
+    lld_bow_result r{0, word.data(), value.data(), 0, node.data(), start.data(), feature.data(), nullptr, nullptr};
+    check(lld_bow_transform(h_, 1, &s, &r), "lld_bow_transform");
+    for (int i = 0; i < r.n_words; i++) v.insert(v.end(), BowVector::value_type((unsigned int)word[i], value[i]));
+    for (int i = 0; i < r.n_nodes; i++)
+      fv.insert(fv.end(), FeatureVector::value_type((unsigned int)node[i],
+                                                     std::vector<unsigned int>(feature.begin() + start[i], feature.begin() + start[i + 1])));
+  }
+  Context& ctx_;
+  int max_sets_, max_features_;
+  lld_bow_vocab* h_ = nullptr;
+  lld_bow_vocab_info info_{};
 };
 
 }  // namespace lld_amd

@@ -194,6 +194,8 @@ PRODUCT_SYMBOLS = [
     "lld_sim3_params_default", "lld_optimize_sim3", "lld_optimize_sim3_batch",
     "lld_pose_graph_params_default", "lld_optimize_essential_graph",
     "lld_orb_extractor_create", "lld_orb_extractor_destroy", "lld_orb_extractor_levels_get", "lld_orb_extract", "lld_orb_extractor_pyramids",
+    "lld_orb_extractor_descriptors",
+    "lld_bow_vocab_read_text", "lld_bow_vocab_create", "lld_bow_vocab_destroy", "lld_bow_vocab_info_get", "lld_bow_transform", "lld_bow_score",
 ]
 
 

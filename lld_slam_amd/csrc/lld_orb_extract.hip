@@ -701,3 +701,11 @@ extern "C" int lld_orb_extractor_pyramids(const lld_orb_extractor* ex, int image
   }
   return LLD_OK;
 }
+
+extern "C" int lld_orb_extractor_descriptors(const lld_orb_extractor* ex, int image_index, const uint32_t** desc, int32_t* n) {
+  if (!ex || !desc || !n || image_index < 0 || image_index >= ex->last_n_images) return LLD_ERR_INVALID;
+  const size_t cap = (size_t)ex->cap_keys;
+  *desc = (const uint32_t*)(ex->d_out + ex->out_stride * image_index + cap * 24);
+  *n = *(const int32_t*)(ex->h_out + ex->out_stride * image_index + cap * 56);     // the count lld_orb_extract brought back
+  return LLD_OK;
+}
