@@ -1177,6 +1177,78 @@ int  lld_bow_transform(lld_bow_vocab* v, int n_sets, const lld_bow_set* sets, ll
 int  lld_bow_score(lld_bow_vocab* v, const lld_bow_vector* query, int n_cand, const int32_t* cand_start, const int32_t* cand_word,
                    const double* cand_value, double* out);
 
+/* ------------------------------------------------------------------ KeyFrameDatabase: resident inverted file, loop and reloc candidates
+ * src/KeyFrameDatabase.cc of the reference (ORB-SLAM2's), with the per-keyframe query registers of KeyFrame (mnLoopQuery,
+ * mnLoopWords, mLoopScore, mnRelocQuery, mnRelocWords, mRelocScore, include/KeyFrame.h) and the covisibility lists the queries read.
+ * Keyframes are the caller's mnId.  Ids, counters and candidates are bit-exact against the CPU restatement tests/kfdb_ref.py.
+ * Restated rules:
+ *   add (:40-45) appends the keyframe to the list of every word of its BowVector.  erase (:47-67) removes the first occurrence
+ *     from each of those lists: the other entries keep their order.  clear (:69-73) empties the lists and leaves every register
+ *     of every keyframe as it is.
+ *   Walk (:86-104 loop, :207-222 reloc): the query's words in ascending order, each word's list in list order.  Per encounter of a
+ *     keyframe: if its stamp (mnLoopQuery / mnRelocQuery) != the query id, words = 0 and (loop path: unless the keyframe is in the
+ *     connected set) it is stamped with the query id and appended to lKFsSharingWords; then words++.  Stamps start at 0
+ *     (KeyFrame.cc:38) and the loop and reloc registers are separate, so a keyframe whose stamp already equals the query id (query
+ *     id 0 on a fresh keyframe, a query id used again) is neither reset nor listed; a connected keyframe is never stamped, so its
+ *     words are reset at every encounter (it ends at 1).
+ *     List order = ascending (first query word the keyframe shares, add order): erase never reorders a list and the database
+ *     never holds a keyframe twice.
+ *   Thresholds (:111-138, :226-252): maxCommonWords = the largest words of the listed keyframes; minCommonWords =
+ *     (int)(maxCommonWords * 0.8f), a float product truncated.  A listed keyframe with words > minCommonWords (strict) is scored
+ *     (nscores++): si = (float)L1Scoring::score(query, keyframe), the double sum of lld_bow_score cast to float, stored in
+ *     mLoopScore / mRelocScore.  lScoreAndMatch holds the scored ones in list order; the loop path only those with si >= minScore.
+ *   Accumulation (:144-173, :258-287): per entry, over GetBestCovisibilityKeyFrames(10) (the first <= 10 of the ordered
+ *     covisibles), in order: accScore starts at si, float, summed left to right; bestScore starts at si and pBestKF at the entry,
+ *     replaced only on a strictly greater score (the first maximum wins).  A neighbour is admitted on the loop path when
+ *     mnLoopQuery == id && mnLoopWords > minCommonWords; on the reloc path when mnRelocQuery == id, with no words test, so a
+ *     neighbour listed but not scored in this query adds the mRelocScore of an earlier query.
+ *   Retain (:175-196, :289-308): bestAccScore = the largest accScore, starting at minScore (loop) or 0 (reloc); an entry is kept
+ *     when accScore > 0.75f*bestAccScore (strict, float); the output is its pBestKF, de-duplicated with the first occurrence kept,
+ *     in list order.  An empty lKFsSharingWords or lScoreAndMatch returns nothing (the registers the walk and the scoring changed
+ *     stay changed).
+ * DEVIATION (the reference is undefined here): mRelocScore is never initialised by the reference, and the reloc path reads it
+ *   for a keyframe it did not score.  Here every score register starts at 0.0f when the library first meets the keyframe; from
+ *   then on it persists across queries exactly like the reference field.
+ * Handles and limits: any id that is added or named by lld_kfdb_set_covisibles gets a slot with its own registers; slots are never
+ * released (ORB-SLAM2 never frees a keyframe) and max_keyframes (<= LLD_KFDB_MAX_KEYFRAMES) bounds them.  max_words bounds the words
+ * of the BowVectors in the database at one time; erase returns its space (an add that does not fit behind the last vector compacts
+ * the pool).  These return LLD_ERR_INVALID before anything is queued and leave the database unchanged: nulls; query or keyframe
+ * words not strictly ascending or outside [0, n_words); adding an id that is in the database (or twice in one call); more slots
+ * than max_keyframes or more words than max_words.  Erasing an id that is not in the database does nothing and returns LLD_OK.
+ * A query always runs to completion and updates the registers, even when capacity is smaller than the result.  A handle is driven
+ * by one host thread at a time, on its vocabulary's context stream. */
+#define LLD_KFDB_MAX_KEYFRAMES 8192      /* slots of one database                                */
+#define LLD_KFDB_MAX_COVISIBLES 10       /* GetBestCovisibilityKeyFrames(10)                     */
+typedef struct lld_kfdb lld_kfdb;
+typedef struct {
+  int32_t capacity;                      /* entries of kf_id / acc_score                          */
+  int32_t n_candidates;                  /* out: the full count; at most capacity ids are written */
+  uint64_t* kf_id;                       /* out: the reference's return order                    */
+  float* acc_score;                      /* out or NULL: accScore of the entry that produced each */
+  int32_t n_sharing;                     /* out: lKFsSharingWords.size()                          */
+  int32_t max_common_words;              /* out: maxCommonWords (0 when nothing is listed)        */
+  int32_t min_common_words;              /* out: minCommonWords                                   */
+  int32_t n_scored;                      /* out: nscores                                          */
+} lld_kfdb_result;
+/* KeyFrameDatabase(voc): an empty database on the vocabulary's context, for word ids in [0, voc's n_words). */
+int  lld_kfdb_create(lld_bow_vocab* voc, int32_t max_keyframes, int64_t max_words, lld_kfdb** out);
+void lld_kfdb_destroy(lld_kfdb* db);
+/* n add() calls, in order: keyframe kf_id[i] with BowVector vecs[i]. */
+int  lld_kfdb_add(lld_kfdb* db, int32_t n, const uint64_t* kf_id, const lld_bow_vector* vecs);
+/* n erase() calls (KeyFrame::SetBadFlag, src/KeyFrame.cc:567). */
+int  lld_kfdb_erase(lld_kfdb* db, int32_t n, const uint64_t* kf_id);
+int  lld_kfdb_clear(lld_kfdb* db);
+/* KeyFrame::UpdateBestCovisibles for n keyframes: the ordered covisibles of kf_id[i] are neighbour[start[i] .. start[i+1]) (start
+ * holds n + 1 entries); the first LLD_KFDB_MAX_COVISIBLES are kept.  Neighbours not yet in the database get a slot and count once
+ * they are added. */
+int  lld_kfdb_set_covisibles(lld_kfdb* db, int32_t n, const uint64_t* kf_id, const int32_t* start, const uint64_t* neighbour);
+/* DetectLoopCandidates(pKF, minScore) with pKF->mnId = query_id, pKF->mBowVec = q, GetConnectedKeyFrames() = connected (ids the
+ * database has never met are ignored).  Uploads the query, downloads the candidates. */
+int  lld_kfdb_detect_loop_candidates(lld_kfdb* db, uint64_t query_id, const lld_bow_vector* q, int32_t n_connected,
+                                     const uint64_t* connected, float min_score, lld_kfdb_result* out);
+/* DetectRelocalizationCandidates(F) with F->mnId = query_id, F->mBowVec = q. */
+int  lld_kfdb_detect_relocalization_candidates(lld_kfdb* db, uint64_t query_id, const lld_bow_vector* q, lld_kfdb_result* out);
+
 #if defined(__GNUC__)
 #pragma GCC visibility pop
 #endif

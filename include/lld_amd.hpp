@@ -9,6 +9,7 @@
 
 #include <cstdint>
 #include <map>
+#include <set>
 #include <stdexcept>
 #include <string>
 #include <vector>
@@ -545,6 +546,72 @@ class ORBVocabulary {
   int max_sets_, max_features_;
   lld_bow_vocab* h_ = nullptr;
   lld_bow_vocab_info info_{};
+};
+
+// Mirror of KeyFrameDatabase (src/KeyFrameDatabase.cc) over lld_kfdb_*: keyframes are the caller's mnId, BowVectors the std::map
+// of ORBVocabulary above.  The caller sends setCovisibles whenever KeyFrame::UpdateBestCovisibles runs.  The queries return the
+// candidate ids in the reference's order; lastStats() holds the counters of the last query.
+class KeyFrameDatabase {
+ public:
+  KeyFrameDatabase(const ORBVocabulary& voc, int max_keyframes = 4096, int64_t max_words = (int64_t)8 << 20) {
+    check(lld_kfdb_create(voc.get(), max_keyframes, max_words, &h_), "lld_kfdb_create");
+    max_keyframes_ = max_keyframes;
+  }
+  ~KeyFrameDatabase() { lld_kfdb_destroy(h_); }
+  KeyFrameDatabase(const KeyFrameDatabase&) = delete;
+  KeyFrameDatabase& operator=(const KeyFrameDatabase&) = delete;
+  void add(uint64_t kf_id, const BowVector& v) {
+    Flat f(v);
+    lld_bow_vector b = f.vec();
+    check(lld_kfdb_add(h_, 1, &kf_id, &b), "lld_kfdb_add");
+  }
+  void erase(uint64_t kf_id) { check(lld_kfdb_erase(h_, 1, &kf_id), "lld_kfdb_erase"); }
+  void clear() { check(lld_kfdb_clear(h_), "lld_kfdb_clear"); }
+  void setCovisibles(uint64_t kf_id, const std::vector<uint64_t>& ordered) {
+    int32_t start[2] = {0, (int32_t)ordered.size()};
+    check(lld_kfdb_set_covisibles(h_, 1, &kf_id, start, ordered.empty() ? nullptr : ordered.data()), "lld_kfdb_set_covisibles");
+  }
+  std::vector<uint64_t> DetectLoopCandidates(uint64_t kf_id, const BowVector& v, const std::set<uint64_t>& connected, float minScore) {
+    Flat f(v);
+    lld_bow_vector b = f.vec();
+    std::vector<uint64_t> conn(connected.begin(), connected.end());
+    return run([&](lld_kfdb_result* r) {
+      return lld_kfdb_detect_loop_candidates(h_, kf_id, &b, (int32_t)conn.size(), conn.empty() ? nullptr : conn.data(), minScore, r);
+    });
+  }
+  std::vector<uint64_t> DetectRelocalizationCandidates(uint64_t frame_id, const BowVector& v) {
+    Flat f(v);
+    lld_bow_vector b = f.vec();
+    return run([&](lld_kfdb_result* r) { return lld_kfdb_detect_relocalization_candidates(h_, frame_id, &b, r); });
+  }
+  const lld_kfdb_result& lastStats() const { return last_; }
+  const std::vector<float>& lastAccScores() const { return acc_; }
+  lld_kfdb* get() const { return h_; }
+ private:
+  struct Flat {
+    std::vector<int32_t> w;
+    std::vector<double> v;
+    explicit Flat(const BowVector& b) {
+      for (BowVector::const_iterator it = b.begin(); it != b.end(); ++it) { w.push_back((int32_t)it->first); v.push_back(it->second); }
+    }
+    lld_bow_vector vec() const { return lld_bow_vector{(int32_t)w.size(), w.data(), v.data()}; }
+  };
+  template <class F>
+  std::vector<uint64_t> run(F call) {
+    std::vector<uint64_t> ids((size_t)max_keyframes_);
+    acc_.assign((size_t)max_keyframes_, 0.0f);
+    last_ = lld_kfdb_result{};
+    last_.capacity = max_keyframes_; last_.kf_id = ids.data(); last_.acc_score = acc_.data();
+    check(call(&last_), "lld_kfdb_detect");
+    ids.resize((size_t)last_.n_candidates);
+    acc_.resize((size_t)last_.n_candidates);
+    last_.kf_id = nullptr; last_.acc_score = nullptr;
+    return ids;
+  }
+  lld_kfdb* h_ = nullptr;
+  int max_keyframes_ = 0;
+  lld_kfdb_result last_{};
+  std::vector<float> acc_;
 };
 
 }  // namespace lld_amd

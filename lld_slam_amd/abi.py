@@ -196,6 +196,8 @@ PRODUCT_SYMBOLS = [
     "lld_orb_extractor_create", "lld_orb_extractor_destroy", "lld_orb_extractor_levels_get", "lld_orb_extract", "lld_orb_extractor_pyramids",
     "lld_orb_extractor_descriptors",
     "lld_bow_vocab_read_text", "lld_bow_vocab_create", "lld_bow_vocab_destroy", "lld_bow_vocab_info_get", "lld_bow_transform", "lld_bow_score",
+    "lld_kfdb_create", "lld_kfdb_destroy", "lld_kfdb_add", "lld_kfdb_erase", "lld_kfdb_clear", "lld_kfdb_set_covisibles",
+    "lld_kfdb_detect_loop_candidates", "lld_kfdb_detect_relocalization_candidates",
 ]
 
 

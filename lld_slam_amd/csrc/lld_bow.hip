@@ -13,12 +13,14 @@
 //   bow_assemble  one 1024-thread workgroup per set: bitonic sort of (word, feature) and (nid, feature) keys in LDS, the word sums
 //                 by repeated addition, the L1 norm summed by one lane in ascending word order, the CSR of the FeatureVector
 //   bow_score     one wavefront per candidate: the terms of the common words in parallel (qpos lookup), summed in word order
+//                 (lld_bow_l1_score_wave of lld_bow_score.h, which the keyframe database runs too)
 #include <algorithm>
 #include <cerrno>
 #include <climits>
 #include <cmath>
 #include <string>
 
+#include "lld_bow_score.h"
 #include "lld_common.h"
 
 namespace {
@@ -249,39 +251,13 @@ __global__ void bow_qpos_set(int32_t* qpos, const int32_t* __restrict__ qword, i
   for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < nq; i += gridDim.x * blockDim.x) qpos[qword[i]] = mark ? i : -1;
 }
 
-__device__ inline double readlane_f64(double x, int lane) {
-  const int lo = __builtin_amdgcn_readlane(__double2loint(x), lane);
-  const int hi = __builtin_amdgcn_readlane(__double2hiint(x), lane);
-  return __hiloint2double(hi, lo);
-}
-
 __global__ __launch_bounds__(256) void bow_score(const int32_t* __restrict__ qpos, const double* __restrict__ qval, int n_cand,
                                                  const int32_t* __restrict__ cstart, const int32_t* __restrict__ cword,
                                                  const double* __restrict__ cval, double* __restrict__ out) {
   const int c = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
   if (c >= n_cand) return;
-  const int s = cstart[c], e = cstart[c + 1];
-  double score = 0.0;
-  for (int base = s; base < e; base += 64) {
-    const int j = base + lane;
-    bool common = false;
-    double term = 0.0;
-    if (j < e) {
-      const int p = qpos[cword[j]];
-      if (p >= 0) {
-        const double vi = qval[p], wi = cval[j];
-        term = fabs(vi - wi) - fabs(vi) - fabs(wi);
-        common = true;
-      }
-    }
-    unsigned long long m = __ballot(common);
-    while (m) {                                  // ascending candidate position = ascending word id
-      const int b = __builtin_ctzll(m);
-      m &= m - 1;
-      score += readlane_f64(term, b);
-    }
-  }
-  if (lane == 0) out[c] = -score / 2.0;
+  const double score = lld_bow_l1_score_wave(qpos, qval, cword, cval, cstart[c], cstart[c + 1], lane);
+  if (lane == 0) out[c] = score;
 }
 
 // ------------------------------------------------------------------------------------------------------------------ host
@@ -471,6 +447,8 @@ extern "C" void lld_bow_vocab_destroy(lld_bow_vocab* v) {
   if (v->h_out) (void)hipHostFree(v->h_out);
   delete v;
 }
+
+lld_ctx* lld_bow_vocab_context(const lld_bow_vocab* v) { return v->ctx; }
 
 extern "C" int lld_bow_vocab_info_get(const lld_bow_vocab* v, lld_bow_vocab_info* out) {
   if (!v || !out) return LLD_ERR_INVALID;

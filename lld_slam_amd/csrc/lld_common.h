@@ -82,6 +82,9 @@ static inline int lld_ctx_scratch(lld_ctx* ctx, size_t bytes, void** out) {
   return LLD_OK;
 }
 
+// The context a vocabulary was created on (lld_bow.hip; internal, not exported).
+lld_ctx* lld_bow_vocab_context(const lld_bow_vocab* v);
+
 // Simple bump allocator over one hipMalloc'd slab (all sub-buffers 256-B aligned).
 struct lld_slab {
   char* base = nullptr;

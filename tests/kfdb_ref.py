@@ -1,0 +1,418 @@
+"""Literal restatement of ORB-SLAM2's KeyFrameDatabase (src/KeyFrameDatabase.cc of the reference) in Python/numpy.  It shares no
+code with lld_slam_amd: the inverted file is a list per word, keyframes are objects holding the query registers of KeyFrame
+(mnLoopQuery, mnLoopWords, mLoopScore, mnRelocQuery, mnRelocWords, mRelocScore), and every float operation is np.float32.  The
+score is bow_ref.score.  Also: a seeded generator of keyframe trajectories with revisits (loops) and covisibility derived from
+the shared words.
+
+The one deviation of include/lld_amd.h is restated: the score registers start at 0.0f (the reference leaves mRelocScore
+uninitialised)."""
+from __future__ import annotations
+
+import numpy as np
+
+import bow_ref
+
+F32 = np.float32
+
+
+class Refused(ValueError):
+    """The library returns LLD_ERR_INVALID and leaves the database unchanged."""
+
+
+class KeyFrame:
+    def __init__(self, kf_id):
+        self.mnId = kf_id
+        self.mBowVec = None                     # (words, values) while in the database
+        self.mnLoopQuery = 0                    # KeyFrame.cc:38
+        self.mnLoopWords = 0
+        self.mLoopScore = F32(0.0)              # DEVIATION: the reference leaves the scores uninitialised
+        self.mnRelocQuery = 0
+        self.mnRelocWords = 0
+        self.mRelocScore = F32(0.0)
+        self.covisibles = []                    # mvpOrderedConnectedKeyFrames (only the first 10 are ever read)
+
+    def GetBestCovisibilityKeyFrames(self, n):
+        return self.covisibles[:n]
+
+
+class KeyFrameDatabase:
+    def __init__(self, n_words, max_keyframes=8192, max_words=1 << 40):
+        self.n_words = n_words
+        self.max_keyframes = max_keyframes
+        self.max_words = max_words
+        self.mvInvertedFile = [[] for _ in range(n_words)]
+        self.kfs = {}                           # id -> KeyFrame: every id the database has met (slots are never released)
+        self.in_db = set()
+        self.live_words = 0
+
+    # ---------------------------------------------------------------------------------------------------------- helpers
+    def kf(self, kf_id):
+        if kf_id not in self.kfs:
+            self.kfs[kf_id] = KeyFrame(kf_id)
+        return self.kfs[kf_id]
+
+    def _check_vec(self, v):
+        w = np.asarray(v[0])
+        if len(w) and (w.min() < 0 or w.max() >= self.n_words or np.any(np.diff(w) <= 0)):
+            raise Refused("words not strictly ascending or out of range")
+
+    def _check_slots(self, ids):
+        if len(self.kfs) + len({i for i in ids if i not in self.kfs}) > self.max_keyframes:
+            raise Refused("too many keyframes")
+
+    # ---------------------------------------------------------------------------------------------------------- :40-73
+    def add(self, kf_id, vec):
+        self.add_many([kf_id], [vec])
+
+    def add_many(self, ids, vecs):
+        ids = [int(i) for i in ids]
+        for i, v in zip(ids, vecs):
+            self._check_vec(v)
+        if len(set(ids)) != len(ids) or any(i in self.in_db for i in ids):
+            raise Refused("keyframe already in the database")
+        self._check_slots(ids)
+        if self.live_words + sum(len(v[0]) for v in vecs) > self.max_words:
+            raise Refused("too many words")
+        for i, v in zip(ids, vecs):
+            k = self.kf(i)
+            k.mBowVec = (np.asarray(v[0], np.int64), np.asarray(v[1], np.float64))
+            for w in k.mBowVec[0].tolist():
+                self.mvInvertedFile[w].append(k)
+            self.in_db.add(i)
+            self.live_words += len(v[0])
+
+    def erase(self, kf_id):
+        kf_id = int(kf_id)
+        if kf_id not in self.in_db:
+            return
+        k = self.kfs[kf_id]
+        for w in k.mBowVec[0].tolist():
+            lst = self.mvInvertedFile[w]
+            for j, x in enumerate(lst):
+                if x is k:
+                    del lst[j]
+                    break
+        self.in_db.discard(kf_id)
+        self.live_words -= len(k.mBowVec[0])
+        k.mBowVec = None
+
+    def clear(self):
+        self.mvInvertedFile = [[] for _ in range(self.n_words)]
+        for i in self.in_db:
+            self.kfs[i].mBowVec = None
+        self.in_db = set()
+        self.live_words = 0
+
+    def set_covisibles(self, kf_id, neighbours):
+        ids = [int(kf_id)] + [int(n) for n in list(neighbours)[:10]]
+        self._check_slots(ids)
+        self.kf(ids[0]).covisibles = [self.kf(n) for n in ids[1:]]
+
+    # ---------------------------------------------------------------------------------------------------------- :76-197
+    def detect_loop_candidates(self, query_id, q, connected, minScore):
+        """Returns (ids, accScores, stats) with stats = dict(n_sharing, max_common_words, min_common_words, n_scored)."""
+        self._check_vec(q)
+        minScore = F32(minScore)
+        spConnectedKeyFrames = {self.kfs[c] for c in connected if c in self.kfs}
+        lKFsSharingWords = []
+        for w in np.asarray(q[0]).tolist():
+            for pKFi in self.mvInvertedFile[w]:
+                if pKFi.mnLoopQuery != query_id:
+                    pKFi.mnLoopWords = 0
+                    if pKFi not in spConnectedKeyFrames:
+                        pKFi.mnLoopQuery = query_id
+                        lKFsSharingWords.append(pKFi)
+                pKFi.mnLoopWords += 1
+        stats = dict(n_sharing=len(lKFsSharingWords), max_common_words=0, min_common_words=0, n_scored=0)
+        if not lKFsSharingWords:
+            return [], [], stats
+        maxCommonWords = 0
+        for k in lKFsSharingWords:
+            if k.mnLoopWords > maxCommonWords:
+                maxCommonWords = k.mnLoopWords
+        minCommonWords = int(F32(maxCommonWords) * F32(0.8))
+        lScoreAndMatch = []
+        nscores = 0
+        for pKFi in lKFsSharingWords:
+            if pKFi.mnLoopWords > minCommonWords:
+                nscores += 1
+                si = F32(bow_ref.score(q, pKFi.mBowVec))
+                pKFi.mLoopScore = si
+                if si >= minScore:
+                    lScoreAndMatch.append((si, pKFi))
+        stats.update(max_common_words=maxCommonWords, min_common_words=minCommonWords, n_scored=nscores)
+        if not lScoreAndMatch:
+            return [], [], stats
+        lAccScoreAndMatch = []
+        bestAccScore = minScore
+        for si, pKFi in lScoreAndMatch:
+            bestScore = si
+            accScore = si
+            pBestKF = pKFi
+            for pKF2 in pKFi.GetBestCovisibilityKeyFrames(10):
+                if pKF2.mnLoopQuery == query_id and pKF2.mnLoopWords > minCommonWords:
+                    accScore = F32(accScore + pKF2.mLoopScore)
+                    if pKF2.mLoopScore > bestScore:
+                        pBestKF = pKF2
+                        bestScore = pKF2.mLoopScore
+            lAccScoreAndMatch.append((accScore, pBestKF))
+            if accScore > bestAccScore:
+                bestAccScore = accScore
+        return self._retain(lAccScoreAndMatch, bestAccScore, stats)
+
+    # ---------------------------------------------------------------------------------------------------------- :199-309
+    def detect_relocalization_candidates(self, query_id, q):
+        self._check_vec(q)
+        lKFsSharingWords = []
+        for w in np.asarray(q[0]).tolist():
+            for pKFi in self.mvInvertedFile[w]:
+                if pKFi.mnRelocQuery != query_id:
+                    pKFi.mnRelocWords = 0
+                    pKFi.mnRelocQuery = query_id
+                    lKFsSharingWords.append(pKFi)
+                pKFi.mnRelocWords += 1
+        stats = dict(n_sharing=len(lKFsSharingWords), max_common_words=0, min_common_words=0, n_scored=0)
+        if not lKFsSharingWords:
+            return [], [], stats
+        maxCommonWords = 0
+        for k in lKFsSharingWords:
+            if k.mnRelocWords > maxCommonWords:
+                maxCommonWords = k.mnRelocWords
+        minCommonWords = int(F32(maxCommonWords) * F32(0.8))
+        lScoreAndMatch = []
+        nscores = 0
+        for pKFi in lKFsSharingWords:
+            if pKFi.mnRelocWords > minCommonWords:
+                nscores += 1
+                si = F32(bow_ref.score(q, pKFi.mBowVec))
+                pKFi.mRelocScore = si
+                lScoreAndMatch.append((si, pKFi))
+        stats.update(max_common_words=maxCommonWords, min_common_words=minCommonWords, n_scored=nscores)
+        if not lScoreAndMatch:
+            return [], [], stats
+        lAccScoreAndMatch = []
+        bestAccScore = F32(0.0)
+        for si, pKFi in lScoreAndMatch:
+            bestScore = si
+            accScore = bestScore
+            pBestKF = pKFi
+            for pKF2 in pKFi.GetBestCovisibilityKeyFrames(10):
+                if pKF2.mnRelocQuery != query_id:
+                    continue
+                accScore = F32(accScore + pKF2.mRelocScore)
+                if pKF2.mRelocScore > bestScore:
+                    pBestKF = pKF2
+                    bestScore = pKF2.mRelocScore
+            lAccScoreAndMatch.append((accScore, pBestKF))
+            if accScore > bestAccScore:
+                bestAccScore = accScore
+        return self._retain(lAccScoreAndMatch, bestAccScore, stats)
+
+    @staticmethod
+    def _retain(lAccScoreAndMatch, bestAccScore, stats):
+        minScoreToRetain = F32(F32(0.75) * bestAccScore)
+        spAlreadyAddedKF = set()
+        ids, accs = [], []
+        for acc, pKFi in lAccScoreAndMatch:
+            if acc > minScoreToRetain and pKFi not in spAlreadyAddedKF:
+                ids.append(pKFi.mnId)
+                accs.append(F32(acc))
+                spAlreadyAddedKF.add(pKFi)
+        return ids, accs, stats
+
+
+# ------------------------------------------------------------------------------------------------------------------ generator
+
+def normalized(words, rng):
+    """A BowVector over the given words: positive values, L1-normalised (sequential sum in word order, as BowVector::normalize)."""
+    words = np.unique(np.asarray(words, np.int64))
+    v = rng.uniform(0.05, 3.0, len(words))
+    norm = 0.0
+    for x in v.tolist():
+        norm += abs(x)
+    return words.astype(np.int32), v / norm
+
+
+def zipf_words(rng, n_words, n, a=1.2, perm=None):
+    """n distinct words drawn with a Zipf-like skew (rank r has weight ~ r^-a), ranks mapped through perm."""
+    out = set()
+    while len(out) < n:
+        r = rng.zipf(a, 2 * n) - 1
+        r = r[r < n_words]
+        out.update((perm[r] if perm is not None else r).tolist())
+    return np.array(sorted(out)[:n] if len(out) > n else sorted(out), np.int64)
+
+
+def trajectory(seed, n_kf, n_words, words_per_kf=120, n_places=None, revisit_every=7, place_words=None, zipf_frac=0.3):
+    """Seeded keyframe trajectory.  The camera moves through places 0, 1, 2, ...; every revisit_every-th keyframe revisits an
+    earlier place (a loop).  Each place has its own word set; a keyframe draws most of its words from its place and the two
+    neighbouring places, the rest Zipf-skewed over the whole vocabulary.  Returns (ids, place, vectors) with ids = 1..n_kf."""
+    rng = np.random.default_rng(seed)
+    n_places = n_places or max(4, n_kf // 3)
+    place_words = place_words or 2 * words_per_kf
+    perm = rng.permutation(n_words)
+    places = [rng.choice(n_words, place_words, replace=False) for _ in range(n_places)]
+    place, cur = [], 0
+    for i in range(n_kf):
+        if i and i % revisit_every == 0 and cur > 3:
+            place.append(int(rng.integers(0, cur - 2)))
+        else:
+            cur = min(cur + (1 if rng.random() < 0.4 else 0), n_places - 1)
+            place.append(cur)
+    vecs = []
+    for i in range(n_kf):
+        p = place[i]
+        pool = np.concatenate([places[p], places[max(p - 1, 0)][:place_words // 4], places[min(p + 1, n_places - 1)][:place_words // 4]])
+        n_local = int(words_per_kf * (1 - zipf_frac))
+        local = rng.choice(pool, min(n_local, len(pool)), replace=False)
+        z = zipf_words(rng, n_words, words_per_kf - len(local), perm=perm)
+        vecs.append(normalized(np.concatenate([local, z]), rng))
+    return list(range(1, n_kf + 1)), place, vecs
+
+
+def covisibility(ids, vecs, window=12, min_shared=8):
+    """Ordered covisibles per keyframe from the shared words with the keyframes within `window` positions and those sharing its
+    place-like word sets: descending shared count, ties by id (UpdateBestCovisibles orders by weight)."""
+    sets = [set(v[0].tolist()) for v in vecs]
+    n = len(ids)
+    out = {}
+    for i in range(n):
+        cand = []
+        for j in range(max(0, i - window), min(n, i + window + 1)):
+            if j != i:
+                s = len(sets[i] & sets[j])
+                if s >= min_shared:
+                    cand.append((-s, ids[j]))
+        cand.sort()
+        out[ids[i]] = [c[1] for c in cand]
+    return out
+
+
+# ------------------------------------------------------------------------------------------------------------------ known answers
+# Each scenario is a list of operations and, per query, the expected (ids, accScores).  Values are dyadic, so every score is exact:
+# for L1-normalised positive vectors the score is the sum over the common words of min(v, w).
+#   ("add", id, (words, values))  ("erase", id)  ("clear",)  ("cov", id, [ordered covisibles])
+#   ("reloc", query_id, bow)  ("loop", query_id, bow, [connected], minScore)
+
+def _v(d):
+    w = sorted(d)
+    return np.array(w, np.int32), np.array([d[k] for k in w], np.float64)
+
+
+E25 = 2.0 ** -25
+
+SCENARIOS = {
+    # max = 10 -> minCommonWords = (int)(10*0.8f) = 8: 9 common words are scored, 8 are not
+    "truncation_boundary": ([
+        ("add", 1, _v({i: 0.0625 for i in range(10)} | {20: 0.375})),
+        ("add", 2, _v({i: 0.0625 for i in range(8)} | {21: 0.5})),
+        ("add", 3, _v({i: 0.0625 for i in range(9)} | {22: 0.4375})),
+        ("reloc", 1, _v({i: 0.1 for i in range(10)})),
+    ], [dict(n_sharing=3, max_common_words=10, min_common_words=8, n_scored=2)]),
+    # query 1 scores B at 1.0; query 2 lists B without scoring it, and A's neighbour B still adds that stale 1.0
+    "stale_reloc_score": ([
+        ("add", 1, _v({0: 0.25, 2: 0.25, 9: 0.5})),
+        ("add", 2, _v({0: 0.5, 1: 0.5})),
+        ("cov", 1, [2]),
+        ("reloc", 1, _v({0: 0.5, 1: 0.5})),
+        ("reloc", 2, _v({0: 0.5, 2: 0.25, 7: 0.25})),
+    ], [([2], [1.0]), ([2], [1.5])]),
+    "stale_reloc_score_fresh": ([
+        ("add", 1, _v({0: 0.25, 2: 0.25, 9: 0.5})),
+        ("add", 2, _v({0: 0.5, 1: 0.5})),
+        ("cov", 1, [2]),
+        ("reloc", 2, _v({0: 0.5, 2: 0.25, 7: 0.25})),
+    ], [([1], [0.5])]),
+    # query id 0 meets every keyframe already stamped 0; a query id used again meets them stamped with it
+    "query_id_zero_and_repeated": ([
+        ("add", 1, _v({0: 0.5, 1: 0.5})),
+        ("add", 2, _v({0: 0.25, 3: 0.75})),
+        ("reloc", 0, _v({0: 0.5, 1: 0.5})),
+        ("loop", 0, _v({0: 0.5, 1: 0.5}), [], 0.0),
+        ("reloc", 5, _v({0: 0.5, 1: 0.5})),
+        ("reloc", 5, _v({0: 0.5, 1: 0.5})),
+        ("loop", 9, _v({0: 0.5, 1: 0.5}), [], 0.0),
+        ("loop", 9, _v({0: 0.5, 1: 0.5}), [], 0.0),
+    ], [([], []), ([], []), ([1], [1.0]), ([], []), ([1], [1.0]), ([], [])]),
+    # keyframe 1 is connected to the query: never listed (its words end at 1), its neighbour role is gone too
+    "connected_left_out": ([
+        ("add", 1, _v({0: 0.5, 1: 0.5})),
+        ("add", 2, _v({0: 0.25, 1: 0.25, 3: 0.5})),
+        ("cov", 2, [1]),
+        ("loop", 3, _v({0: 0.5, 1: 0.5}), [1], 0.0),
+    ], [([2], [0.5])]),
+    # keyframes 1 and 2 both have 3 as their best covisible: one output
+    "same_best_once": ([
+        ("add", 1, _v({0: 0.25, 5: 0.75})),
+        ("add", 2, _v({0: 0.25, 6: 0.75})),
+        ("add", 3, _v({0: 0.5, 7: 0.5})),
+        ("cov", 1, [3]),
+        ("cov", 2, [3]),
+        ("reloc", 1, _v({0: 1.0})),
+    ], [([3], [0.75])]),
+    # neighbours 2 and 3 score the same, above 1's score: the first of them is pBestKF
+    "best_score_tie": ([
+        ("add", 1, _v({0: 0.25, 5: 0.75})),
+        ("add", 2, _v({0: 0.5, 6: 0.5})),
+        ("add", 3, _v({0: 0.5, 7: 0.5})),
+        ("cov", 1, [3, 2]),
+        ("reloc", 1, _v({0: 1.0})),
+    ], [([3], [1.25])]),
+    # si >= minScore keeps 2 (0.375 = minScore) in lScoreAndMatch; acc > 0.75f*0.5 drops it at retention
+    "min_score_vs_retain": ([
+        ("add", 1, _v({0: 0.5, 2: 0.5})),
+        ("add", 2, _v({0: 0.375, 3: 0.625})),
+        ("loop", 4, _v({0: 0.5, 1: 0.5}), [], 0.375),
+        ("loop", 5, _v({0: 0.5, 1: 0.5}), [], 0.4),
+        ("loop", 6, _v({0: 0.5, 1: 0.5}), [], 0.6),
+    ], [([1], [0.5]), ([1], [0.5]), ([], [])]),
+    # 0.75 + 2^-25 + 2^-25 left to right stays 0.75 (ties to even), not > 0.75f*1.0; summed the other way it would be kept
+    "summation_order": ([
+        ("add", 1, _v({0: 0.75, 5: 0.25})),
+        ("add", 2, _v({0: E25, 6: 1.0 - E25})),
+        ("add", 3, _v({0: E25, 7: 1.0 - E25})),
+        ("add", 4, _v({0: 1.0})),
+        ("cov", 1, [2, 3]),
+        ("reloc", 1, _v({0: 1.0})),
+    ], [([4], [1.0])]),
+    # erase keeps the order of the others; the re-added keyframe goes to the end of every list
+    "erase_then_readd": ([
+        ("add", 1, _v({0: 0.5, 5: 0.5})),
+        ("add", 2, _v({0: 0.5, 6: 0.5})),
+        ("reloc", 1, _v({0: 1.0})),
+        ("erase", 1),
+        ("erase", 77),
+        ("add", 1, _v({0: 0.5, 5: 0.5})),
+        ("reloc", 2, _v({0: 1.0})),
+    ], [([1, 2], [0.5, 0.5]), ([2, 1], [0.5, 0.5])]),
+    # clear empties the lists but keeps the registers: keyframe 1, re-added, still carries the stamp 7
+    "clear_keeps_registers": ([
+        ("add", 1, _v({0: 0.5, 5: 0.5})),
+        ("reloc", 7, _v({0: 1.0})),
+        ("clear",),
+        ("reloc", 8, _v({0: 1.0})),
+        ("add", 1, _v({0: 0.5, 5: 0.5})),
+        ("add", 2, _v({0: 0.25, 6: 0.75})),
+        ("reloc", 7, _v({0: 1.0})),
+    ], [([1], [0.5]), ([], []), ([2], [0.25])]),
+}
+
+
+def run_ops(db, ops):
+    """Runs a scenario on a restatement database; returns the (ids, accScores, stats) of every query."""
+    out = []
+    for op in ops:
+        k = op[0]
+        if k == "add":
+            db.add(op[1], op[2])
+        elif k == "erase":
+            db.erase(op[1])
+        elif k == "clear":
+            db.clear()
+        elif k == "cov":
+            db.set_covisibles(op[1], op[2])
+        elif k == "reloc":
+            out.append(db.detect_relocalization_candidates(op[1], op[2]))
+        elif k == "loop":
+            out.append(db.detect_loop_candidates(op[1], op[2], op[3], op[4]))
+    return out
