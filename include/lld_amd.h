@@ -1012,7 +1012,8 @@ int lld_orb_search_batch(lld_ctx* ctx, int n, const lld_orb_search* problems, ll
  * Size limits: 62 <= each level's cols and rows (every level must give nCols, nRows and round(w/h) >= 1; checked on the host),
  * cols, rows <= max_cols, max_rows <= 16383; 1 <= n_levels <= LLD_ORB_MAX_LEVELS; thresholds in [1, 255]; 1 < scale_factor;
  * pattern coordinates |c| <= 13 (13*sqrt(2) rounds below EDGE_THRESHOLD = 19, so no descriptor read leaves the level).
- * No limit on the candidate count: every per-level buffer is sized from the level's area at create time. */
+ * No limit on the candidate count: every per-level buffer is sized at create time from the level's area, with room for the
+ * cells' rounding (nCols * wCell may exceed the level's width). */
 typedef struct lld_orb_extractor lld_orb_extractor;
 typedef struct {
   int32_t nfeatures;
@@ -1066,7 +1067,8 @@ void lld_orb_extractor_destroy(lld_orb_extractor* ex);
 int  lld_orb_extractor_levels_get(const lld_orb_extractor* ex, lld_orb_extractor_levels* out);
 /* Extracts n_images (1 <= n_images <= max_images) images in one sequence of launches on the context's stream; returns after the
  * results are on the host.  Invalid sizes, nulls, too many images or too small an output capacity return LLD_ERR_INVALID before
- * anything is queued. */
+ * anything is queued.  A refused call leaves the handle as the last successful call left it: lld_orb_extractor_pyramids and
+ * lld_orb_extractor_descriptors still describe that call's images, with its sizes and counts. */
 int  lld_orb_extract(lld_orb_extractor* ex, int n_images, const lld_orb_image* images, lld_orb_features* outs);
 /* The pyramid of image `image_index` of the last lld_orb_extract as device pointers: fills n_levels, cols, rows and steps and
  * sets on_device = 1.  `left` or `right` (whichever is non-NULL) receives the level pointers, `step` the matching step array, so

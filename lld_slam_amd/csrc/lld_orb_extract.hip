@@ -9,6 +9,7 @@
 #include "lld_common.h"
 #include "lld_glibc_sincosf.h"
 
+#include <algorithm>
 #include <cmath>
 
 namespace {
@@ -540,7 +541,9 @@ extern "C" int lld_orb_extractor_create(lld_ctx* ctx, const lld_orb_extractor_pa
   for (int l = 0; l < nl; l++) {
     maxc[l] = l ? cv_round((float)P.max_cols * L.inv_scale_factor[l]) : P.max_cols;
     maxr[l] = l ? cv_round((float)P.max_rows * L.inv_scale_factor[l]) : P.max_rows;
-    keycap[l] = std::max(maxc[l] * maxr[l], 1);
+    // candidate slots: nCols cells of wCell = ceil(width / nCols) slots span < width + nCols <= maxc + maxc / 30 columns (more than
+    // maxc when width / nCols has a fraction, e.g. 4096 -> 135 cells of 31), likewise for rows
+    keycap[l] = std::max((maxc[l] + maxc[l] / 30) * (maxr[l] + maxr[l] / 30), 1);
     const int ini_max = std::max(maxc[l] / 30 + 2, 1);
     nodecap[l] = keycap[l] + ini_max + 8;
     rescap[l] = level_res_cap(L.features_per_level[l], ini_max);
@@ -605,7 +608,9 @@ extern "C" int lld_orb_extract(lld_orb_extractor* ex, int n_images, const lld_or
   if (!ex || !images || !outs || n_images < 1 || n_images > ex->p.max_images) return LLD_ERR_INVALID;
   const int nl = ex->p.n_levels;
   GeoTable* H = ex->h_geo;
-  // validate everything before anything is queued
+  // validate everything before anything is queued, into local storage: H still describes the last successful call's pyramid
+  // (lld_orb_extractor_pyramids) until every image has passed
+  std::vector<LevelGeo> geo((size_t)n_images * nl);
   for (int im = 0; im < n_images; im++) {
     const lld_orb_image& I = images[im];
     const lld_orb_features& O = outs[im];
@@ -617,7 +622,7 @@ extern "C" int lld_orb_extract(lld_orb_extractor* ex, int n_images, const lld_or
       const int c = l ? cv_round((float)I.cols * ex->lv.inv_scale_factor[l]) : I.cols;
       const int r = l ? cv_round((float)I.rows * ex->lv.inv_scale_factor[l]) : I.rows;
       if (!level_shape(c, r, &s)) return LLD_ERR_INVALID;
-      LevelGeo& g = H->g[im * nl + l];
+      LevelGeo& g = geo[im * nl + l];
       g = ex->slots[im * nl + l];
       g.cols = c; g.rows = r; g.step = c;
       g.n_cols = s.n_cols; g.n_rows = s.n_rows; g.w_cell = s.w_cell; g.h_cell = s.h_cell;
@@ -630,6 +635,7 @@ extern "C" int lld_orb_extract(lld_orb_extractor* ex, int n_images, const lld_or
     }
     if (O.capacity < need) return LLD_ERR_INVALID;
   }
+  std::copy(geo.begin(), geo.end(), H->g);
   H->n_images = n_images; H->n_levels = nl; H->min_th = ex->p.min_th_fast; H->ini_th = ex->p.ini_th_fast;
   hipStream_t st = ex->ctx->stream;
   LLD_HIP_TRY(hipSetDevice(ex->ctx->device));

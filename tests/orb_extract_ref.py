@@ -135,6 +135,23 @@ def level_grid(cols, rows):
     return max_bx, max_by, n_cols, n_rows, w_cell, h_cell
 
 
+def n_ini(cols, rows):
+    """DistributeOctTree's initial node count for a level: std::round((maxX - minX) / (maxY - minY)), halves away from zero."""
+    max_bx, max_by = cols - EDGE_THRESHOLD + 3, rows - EDGE_THRESHOLD + 3
+    return int(math.floor(float(f32(max_bx - MIN_BORDER) / f32(max_by - MIN_BORDER)) + 0.5))
+
+
+def level_ok(cols, rows):
+    """False where the reference divides by zero: no FAST cell (nCols or nRows = 0) or no initial octree node (round(w/h) = 0)."""
+    _, _, n_cols, n_rows, _, _ = level_grid(cols, rows)
+    return n_cols >= 1 and n_rows >= 1 and n_ini(cols, rows) >= 1
+
+
+def image_ok(cols, rows, tables):
+    """Every level of a cols x rows image passes level_ok: what extract() accepts."""
+    return all(level_ok(*(level_size(cols, rows, inv) if l else (cols, rows))) for l, inv in enumerate(tables["inv_scale"]))
+
+
 def cell_keypoints(score, max_bx, max_by, n_cols, n_rows, w_cell, h_cell, ini_th, min_th, stats):
     """ComputeKeyPointsOctTree's cell loop (:786-832): candidates (x, y relative to minBorder, score) in reference order."""
     out = []
@@ -357,7 +374,7 @@ def extract(image, nfeatures, scale_factor, nlevels, ini_th, min_th, pattern):
                   features_wanted=int(T["per_level"][l]))
         rows, cols = img.shape
         max_bx, max_by, n_cols, n_rows, w_cell, h_cell = level_grid(cols, rows)
-        if n_cols < 1 or n_rows < 1 or math.floor(float(f32(max_bx - MIN_BORDER) / f32(max_by - MIN_BORDER)) + 0.5) < 1:
+        if not level_ok(cols, rows):
             raise ValueError(f"level {l} ({cols}x{rows}): no FAST cell or no initial octree node (the reference divides by zero)")
         sc = fast_score_map(img)
         cands = cell_keypoints(sc, max_bx, max_by, n_cols, n_rows, w_cell, h_cell, ini_th, min_th, st)

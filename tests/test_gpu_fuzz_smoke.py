@@ -39,3 +39,16 @@ def test_the_scene_that_found_the_near_singular_line_gate(gpu_ctx, oracle, monke
     monkeypatch.setattr(FZ, "BIG", True)
     ok, nm = FZ.ROUTINES["line_stereo"](gpu_ctx, np.random.default_rng([9, 13712]), 519931807)
     assert ok and nm > 20
+
+
+def test_random_orb_extract_calls_bit_for_bit(gpu_ctx):
+    """A fixed-seed slice of tools/fuzz_orb_extract.py (the full log is profiles/fuzz_orb_extract_*.txt): 24 drawn lld_orb_extract
+    calls of 1-8 images (random parameters, sizes from the validity boundary to 1920x1080, host, strided and device input), every
+    output bit for bit against tests/orb_extract_ref.py."""
+    import fuzz_orb_extract as FO
+    with_kp = 0
+    for it in range(24):
+        ok, nk = FO.ROUTINES["extract"](gpu_ctx, np.random.default_rng([2026, 101, it]), it)
+        assert ok, it
+        with_kp += nk > 0
+    assert with_kp >= 12                                                # the draws are not degenerate: most calls produced keypoints

@@ -7,6 +7,7 @@ import pytest
 
 import orb_extract_ref as R
 import oracle_orbsearch as OS
+from orb_scenes import scene
 from lld_slam_amd import ORBmatcher, abi, synth
 from lld_slam_amd.orb_extractor import (OrbExtractorParams, OrbFeatures, OrbImage, ORBextractor, compute_stereo_matches_device)
 
@@ -26,31 +27,6 @@ def download(ptr, nbytes):
     hip.hipMemcpy.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int]
     assert hip.hipMemcpy(out.ctypes.data, C.cast(ptr, C.c_void_p), nbytes, 2) == 0      # hipMemcpyDeviceToHost
     return out
-
-
-def scene(kind, cols, rows, seed):
-    """Seeded test images: 'textured' (polygons on a smooth texture plus noise), 'flat' (a constant image with a few faint shapes),
-    'busy' (strong pixel noise: tens of thousands of level-0 candidates)."""
-    rng = np.random.default_rng(seed)
-    yy, xx = np.mgrid[0:rows, 0:cols]
-    if kind == "busy":
-        img = rng.integers(0, 256, (rows, cols)).astype(np.float64)
-    elif kind == "flat":
-        img = np.full((rows, cols), 118.0)
-        for _ in range(3):
-            cx, cy, r = rng.uniform(60, cols - 60), rng.uniform(40, rows - 40), rng.uniform(8, 25)
-            img[(xx - cx) ** 2 + (yy - cy) ** 2 < r * r] += rng.uniform(10, 30)
-        img += rng.integers(0, 2, (rows, cols))
-    else:
-        img = 90 + 40 * np.sin(xx / 37.0) * np.cos(yy / 23.0)
-        for _ in range(60):
-            cx, cy = rng.uniform(0, cols), rng.uniform(0, rows)
-            w, h = rng.uniform(5, 60, 2)
-            a = rng.uniform(0, np.pi)
-            u = (xx - cx) * np.cos(a) + (yy - cy) * np.sin(a); v = -(xx - cx) * np.sin(a) + (yy - cy) * np.cos(a)
-            img[(np.abs(u) < w) & (np.abs(v) < h)] = rng.uniform(0, 255)
-        img += rng.normal(0, 4, (rows, cols))
-    return np.clip(np.round(img), 0, 255).astype(np.uint8)
 
 
 def check_equal(got, exp, ex, image_index=None):

@@ -165,3 +165,61 @@ def test_glibc_sincosf_restatement_matches_libm_on_a_sample(tmp_path):
                            os.path.join(ROOT, "tools", "check_sincosf.c"), "-o", str(exe), "-lm"])
     out = subprocess.check_output([str(exe), "997"]).decode()
     assert "cos_diff 0 sin_diff 0" in out, out
+
+
+def test_level_tables_at_one_and_sixteen_levels_and_scale_2():
+    T = R.level_tables(1000, 1.2, 1)                                  # one level: nothing divided, every feature on level 0
+    assert T["scale"].tolist() == [1.0] and T["inv_scale"].tolist() == [1.0] and T["per_level"].tolist() == [1000]
+    T = R.level_tables(1000, 2.0, 4)                                  # powers of two are exact in float
+    assert T["scale"].tolist() == [1, 2, 4, 8] and T["inv_scale"].tolist() == [1, 0.5, 0.25, 0.125]
+    assert T["sigma2"].tolist() == [1, 4, 16, 64] and T["inv_sigma2"].tolist() == [1, 0.25, 0.0625, 0.015625]
+    # nDesired = 1000 (1 - 1/2) / (1 - 2^-4) = 533.3, then 266.7, 133.3: cvRound each, the remainder 67 to the last level
+    assert T["per_level"].tolist() == [533, 267, 133, 67]
+    T = R.level_tables(2000, 1.05, 16)
+    s = [1.0]
+    for _ in range(15):
+        s.append(float(np.float32(np.float32(s[-1]) * np.float32(1.05))))
+    assert T["scale"].tolist() == s and abs(s[-1] - 1.05 ** 15) < 1e-5
+    f = 1 / 1.05
+    nd = 2000 * (1 - f) / (1 - f ** 16)                               # 129.2, 123.1, ... in double: float rounding moves none of them
+    assert T["per_level"][:15].tolist() == [round(nd * f ** l) for l in range(15)]
+    assert T["per_level"].sum() == 2000 and T["per_level"][15] == 2000 - sum(round(nd * f ** l) for l in range(15))
+
+
+def test_level_size_rounds_ties_to_even():
+    """cvRound((float)cols * inv): an exact .5 goes to the even neighbour, down or up."""
+    assert R.level_size(701, 525, np.float32(0.5)) == (350, 262)       # 350.5, 262.5 -> down
+    assert R.level_size(703, 527, np.float32(0.5)) == (352, 264)       # 351.5, 263.5 -> up
+    assert R.level_size(701, 525, np.float32(0.125)) == (88, 66)       # 87.625, 65.625: no tie
+    assert R.level_size(6, 10, np.float32(0.25)) == (2, 2)             # 1.5 -> 2, 2.5 -> 2
+
+
+def test_size_limits_are_the_headers():
+    """62 px is the smallest level side with one FAST cell; round((cols - 32) / (rows - 32)) must be >= 1.  extract() accepts
+    exactly the images image_ok() accepts."""
+    assert R.level_ok(62, 62) and not R.level_ok(61, 62) and not R.level_ok(62, 61)
+    T = R.level_tables(1000, 1.2, 8)
+    inv = T["inv_scale"][-1]
+    c = next(c for c in range(62, 400) if R.level_size(c, c, inv)[0] >= 62)
+    assert R.level_size(c, c, inv) == (62, 62) and R.level_size(c - 1, c - 1, inv)[0] == 61
+    assert R.image_ok(c, c, T) and not R.image_ok(c - 1, c, T) and not R.image_ok(c, c - 1, T)
+    pat = R.seeded_pattern(0)
+    for cols, rows in [(c, c), (c - 1, c), (c, c - 1), (c + 1, 2 * c), (c, 2 * c + 200), (400, 120), (640, 200)]:
+        img = np.full((rows, cols), 9, np.uint8)
+        if R.image_ok(cols, rows, T):
+            R.extract(img, 1000, 1.2, 8, 20, 7, pat)
+        else:
+            try:
+                R.extract(img, 1000, 1.2, 8, 20, 7, pat)
+                raise AssertionError(f"{cols}x{rows} accepted")
+            except ValueError:
+                pass
+
+
+def test_n_ini_rounds_halves_away_from_zero():
+    """std::round in DistributeOctTree: (cols - 32) / (rows - 32) = k + 0.5 gives k + 1 (half-to-even would give k for even k)."""
+    assert [R.n_ini(32 + w, 132) for w in (50, 150, 250, 350, 49, 51)] == [1, 2, 3, 4, 0, 1]
+    assert R.level_ok(82, 132) and not R.level_ok(81, 132)
+    st = {}                                     # three initial nodes over 250 px keep 80 and 90 apart; two would share one child
+    out = R.distribute_oct_tree([(80, 5, 9), (90, 5, 9), (240, 5, 9)], 16, 266, 16, 116, 1, st)
+    assert len(out) == 3 and st["iterations"] == 1
