@@ -146,6 +146,17 @@ bool FrameOnDevice::TrackWithMotionModel(const TrackingMembers& tr, Frame& Cur, 
   Outputs out(nt_, nl_, 0);
   check(lld_frame_track_download(f_, &out.r, nullptr), "lld_frame_track_download");
   out.to(trace, nt_, nl_, 0);
+  if (out.r.n_search < 10) {
+    // :913-917: the reference returns before AddLinesFrom and PoseOptimization.  The frame holds the raw matches of the search used (the
+    // stage-1 record's ids), mvbOutlier stays false, no MapLine, the predicted pose; no MapPoint / MapLine is marked.  The chain has run
+    // on, so the device frame is handed this state back: it never holds what the object graph lacks.
+    for (int k = 0; k < nt_; k++) {
+      Cur.mvpMapPoints[k] = out.kp_id[k] >= 0 ? point_of[out.kp_id[k]] : static_cast<MapPoint*>(NULL);
+      Cur.mvbOutlier[k] = false;
+    }
+    SetFrameState(tr, Cur);
+    return false;
+  }
   // ---- write-back: matches, PoseOptimization's flags, the outlier discard (:940-975)
   for (int k = 0; k < nt_; k++) {
     Cur.mvpMapPoints[k] = static_cast<MapPoint*>(NULL); Cur.mvbOutlier[k] = false;
@@ -162,7 +173,6 @@ bool FrameOnDevice::TrackWithMotionModel(const TrackingMembers& tr, Frame& Cur, 
     Cur.mvpMapLines[i] = out.ln_out[i] ? static_cast<MapLine*>(NULL) : pML;
   }
   set_pose(Cur, out.r);
-  if (out.r.n_search < 10) return false;                                      // :913-917 (the chain has run on; the caller falls back to TrackReferenceKeyFrame)
   if (tr.mbOnlyTracking) { if (mbVO) *mbVO = out.r.n_points_map < 10; return out.r.n_points > 20; }
   return out.r.n_points_map >= 7;
 }

@@ -44,7 +44,9 @@ class FrameOnDevice {
   FrameOnDevice& operator=(const FrameOnDevice&) = delete;
 
   // bool Tracking::TrackWithMotionModel(): the caller has run UpdateLastFrame() and mCurrentFrame.SetPose(mVelocity*mLastFrame.mTcw), and
-  // cleared mCurrentFrame.mvpMapPoints (:897).  *mbVO as the reference sets it in localisation mode (:985).
+  // cleared mCurrentFrame.mvpMapPoints (:897).  *mbVO as the reference sets it in localisation mode (:985).  Below 10 matches (:913-917) the
+  // frame keeps only the raw matches of the search, with mvbOutlier false, no MapLines, the predicted pose and no marks on any MapPoint / MapLine;
+  // the device frame is set to that state, so TrackLocalMap may follow it on this object as after SetFrameState.
   bool TrackWithMotionModel(const TrackingMembers& tr, Frame& mCurrentFrame, const Frame& mLastFrame, bool* mbVO = nullptr, TrackTrace* trace = nullptr);
   // The frame's pose and matches came from another routine (Tracking::TrackReferenceKeyFrame, src/Tracking.cc:770-816, or Relocalization): hands the
   // device what mCurrentFrame holds now (mTcw, mvpMapPoints / mvbOutlier, mvpMapLines / mvbOutlierLines) so that TrackLocalMap can follow.

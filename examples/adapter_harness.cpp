@@ -694,7 +694,8 @@ int run_lastkf(const char* in, const char* out) {
 
 // Tracking::TrackWithMotionModel + Tracking::TrackLocalMap through adapters/lld_tracking_adapter.cc on a live object graph: the scene file of
 // `harness track` (lld_slam_amd/tracking.py write_harness_scene) plus a tail {Tlast[16] f32, mb f32, mbOnlyTracking i32, half_outliers i32,
-// via_set_state i32, 0}.  via_set_state: TrackLocalMap runs on a SECOND device frame that was handed the object graph's state (FrameOnDevice::SetFrameState),
+// via_set_state i32, 0}.  The dump ends with {TrackWithMotionModel's return value, mbVO, mnMatchesInliers, SetPose calls in all, SetPose calls
+// after TrackWithMotionModel}.  TrackLocalMap runs whatever TrackWithMotionModel returned.  via_set_state: TrackLocalMap runs on a SECOND device frame that was handed the object graph's state (FrameOnDevice::SetFrameState),
 // the way it follows TrackReferenceKeyFrame in the running system.
 // One MapPoint / MapLine object per id, shared by the last frame and the local map as in the running system.
 int run_track(const char* in, const char* out) {
@@ -804,6 +805,7 @@ int run_track(const char* in, const char* out) {
   };
   bool mbVO = false; int mnMatchesInliers = -1;
   const bool ok = dev.TrackWithMotionModel(tm, Cur, Last, &mbVO, &t1);
+  const int32_t set_pose_after_motion_model = Cur.n_set_pose;
   put_trace(t1); put_objects();
   if (tail[2]) {
     lld_adapter::FrameOnDevice dev2(ctx.get(), Cur);
@@ -814,8 +816,8 @@ int run_track(const char* in, const char* out) {
   }
   put_trace(t2); put_objects();
   w.put(t2.mp_in_view);
-  const int32_t fin[4] = {(int32_t)ok, (int32_t)mbVO, mnMatchesInliers, Cur.n_set_pose};
-  w.put(fin, 4);
+  const int32_t fin[5] = {(int32_t)ok, (int32_t)mbVO, mnMatchesInliers, Cur.n_set_pose, set_pose_after_motion_model};
+  w.put(fin, 5);
   std::printf("adapter-track: TrackWithMotionModel %s (%d points, %d lines), TrackLocalMap %d inliers (%d lines)\n", ok ? "ok" : "lost", t1.r.n_points, t1.r.n_lines, mnMatchesInliers, t2.r.n_lines);
   return 0;
 }

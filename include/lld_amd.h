@@ -793,7 +793,11 @@ typedef struct {
   double sx, sy;                                                       /* 1 / mnMaxX, 1 / mnMaxY (the Hough grid of lld_line_track_match)            */
 } lld_frame_lines;
 /* Uploads the frame's lines ONCE (and fills the 50 x 50 Hough grid cells on the device); NULL or n_left = 0: a frame without lines.  Resets the
- * tracking state of the frame.  Call it after lld_frame_create and before lld_frame_track_motion_model; synchronous. */
+ * tracking state of the frame.  Call it after lld_frame_create and before lld_frame_track_motion_model; synchronous.
+ * Line limit: LLD_ERR_UNSUPPORTED (the frame unchanged) above the most lines the chain can track next to the frame's nt keypoints.  TrackLocalMap's
+ * "already seen / tracked" test keeps two hash tables in 150 KB of LDS, pow2(4 max(nt, 1)) point slots and pow2(4 n_left + 32) line slots
+ * (pow2: the next power of two, at least 64), and PoseOptimization takes at most 16384 lines: n_left <= 4088 for every nt <= LLD_ORB_MAX_KEYPOINTS,
+ * n_left <= 8184 when nt <= 1024. */
 int  lld_frame_set_lines(lld_frame* frame, const lld_frame_lines* lines);
 typedef struct {
   int32_t n;
@@ -819,7 +823,7 @@ typedef struct {
   int32_t line_use_grid;            /* as lld_line_track_params.use_grid                                                                             */
   int32_t reserved;
 } lld_track_params;
-void lld_track_params_default(lld_track_params* p);
+void lld_track_params_default(lld_track_params* p);     /* cam is zeroed: the caller sets it (the track calls refuse fx, fy <= 0) */
 typedef struct {
   double  pose_qt[7];               /* mTcw after the stage's PoseOptimization (pFrame->SetPose, Optimizer.cc:918)                                   */
   double  chi2;
@@ -843,9 +847,14 @@ typedef struct {
   uint8_t* mp_in_view;              /* stage 2 only, [local_points->n] or NULL: Frame::isInFrustum of every local MapPoint that was not skipped (what the
                                        reference leaves in pMP->mbTrackInView and counts with IncreaseVisible, src/Tracking.cc:1645-1649)            */
 } lld_track_result;
+/* With n_search < 10 the stage-1 record describes a run the reference does not make: TrackWithMotionModel returns false there (src/Tracking.cc:913-917)
+ * before AddLinesFrom, PoseOptimization and the discard, while the chain runs on.  The frame then holds only the search's matches (kp_point_id >= 0,
+ * flags ignored) with the predicted pose; a caller hands the device that state with lld_frame_track_set_state before anything follows. */
 /* Stage 1.  `view`: Frame::UpdatePoseMatrices of the predicted pose mVelocity * mLastFrame.mTcw (as for lld_frame_search_last_frame);
  * `pose_qt`: Converter::toSE3Quat of the same matrix (lld_se3_from_tcw_f32).  last / last_point_id: LastFrame.mvpMapPoints as for
- * lld_frame_search_last_frame plus the id of every entry; last_lines: mLastFrame.mvpMapLines (NULL: none). */
+ * lld_frame_search_last_frame plus the id of every entry; last_lines: mLastFrame.mvpMapLines (NULL: none).
+ * LLD_ERR_INVALID before anything is queued when params->cam.fx or .fy is not > 0, or the frame was created without level_inv_sigma2
+ * (PoseOptimization's information per level); the same for lld_frame_track_set_state. */
 int  lld_frame_track_motion_model(lld_frame* frame, const lld_track_params* params, const lld_frame_view* view, const double* pose_qt,
                                   const lld_last_frame_points* last, const int32_t* last_point_id, const lld_map_lines* last_lines);
 /* Stage 1 ran elsewhere: Tracking::TrackReferenceKeyFrame (src/Tracking.cc:770-816) or Tracking::Relocalization end with the same

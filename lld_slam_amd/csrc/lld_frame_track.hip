@@ -231,6 +231,20 @@ __global__ __launch_bounds__(kSeenThreads) void track_mark_seen_kernel(TrackDev 
 
 inline size_t al(size_t b) { return (b + 255) & ~size_t(255); }
 
+// LDS of track_mark_seen_kernel for a frame: the point table holds the ids the frame holds or discarded (<= 2 nt), the line table the tracked
+// list (<= tracked_cap = 2 nl + 16), each at most half full.  Fixed per frame: sized once by state_build.
+constexpr size_t kSeenLdsMax = 150 * 1024;
+unsigned seen_pow2(unsigned n) { unsigned p = 64; while (p < n) p <<= 1; return p; }
+unsigned seen_point_slots(int nt) { return seen_pow2(4u * (unsigned)std::max(nt, 1)); }
+unsigned seen_line_slots(int nl) { return seen_pow2(2u * (unsigned)(2 * nl + 16)); }
+// The most frame lines the chain takes next to nt keypoints: the LDS above, and pose_track_launch's 16384 (its line scan keeps the edge flags in LDS).
+int track_max_lines(int nt) {
+  const size_t left = kSeenLdsMax / 4 - seen_point_slots(nt);
+  size_t lsize = 64;
+  while (2 * lsize <= left) lsize <<= 1;
+  return std::min((int)(lsize / 4) - 8, 16 * 1024);                       // seen_line_slots(nl) <= lsize  <=>  4 nl + 32 <= lsize
+}
+
 }  // namespace
 
 struct lld_frame_track_state {
@@ -249,6 +263,7 @@ struct lld_frame_track_state {
   ViewConsts consts{};
   bool stage1_queued = false;
   size_t in_view_off = 0; int n_in_view = 0;   // Frame::isInFrustum flags of stage 2's local MapPoints, inside d_work
+  unsigned seen_psize = 0, seen_lsize = 0; size_t seen_lds = 0;   // track_mark_seen_kernel's tables (state_build)
 };
 
 namespace lld_track {
@@ -280,6 +295,15 @@ int state_build(lld_frame* f, const lld_frame_lines* L) {
   const size_t o_has = take(nt), o_world = take((size_t)nt * 12), o_id = take((size_t)nt * 4), o_obs = take(nt), o_out = take(nt), o_disc = take((size_t)nt * 4 + 4);
   const size_t o_lhas = take(nl), o_lx0 = take((size_t)nl * 24), o_ldir = take((size_t)nl * 24), o_lid = take((size_t)nl * 4), o_lout = take(nl);
   const int tracked_cap = 2 * nl + 16;
+  S->seen_psize = seen_point_slots(nt); S->seen_lsize = seen_line_slots(nl);
+  S->seen_lds = ((size_t)S->seen_psize + S->seen_lsize) * 4;
+  if (S->seen_lds > kSeenLdsMax) { lld_track::state_free(f); return LLD_ERR_UNSUPPORTED; }      // (lld_frame_set_lines refuses such frames first)
+  if (S->seen_lds > 48 * 1024) {
+    // the attribute belongs to the kernel, not to the frame: raised to the budget, so that no frame's setting can shrink another's
+    if (hipFuncSetAttribute(reinterpret_cast<const void*>(&track_mark_seen_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)kSeenLdsMax) != hipSuccess) {
+      lld_track::state_free(f); return LLD_ERR_HIP;
+    }
+  }
   const size_t o_trk = take((size_t)tracked_cap * 4), o_cnt = take(64), o_pose = take(7 * 8), o_pout = take(12 * 8), o_view = take(sizeof(lld_frame_view)), o_lp = take(sizeof(LineTrackDevParams));
   const size_t o_ll = take((size_t)nl * 16), o_lo = take((size_t)nl * 4), o_lr = take((size_t)std::max(nr, 1) * 16), o_ro = take((size_t)std::max(nr, 1) * 4), o_lm = take((size_t)nl * 4);
   const size_t o_ld = take((size_t)nl * dim * 4), o_lc = take((size_t)nl * 4);
@@ -443,6 +467,7 @@ int lld_frame_set_lines(lld_frame* f, const lld_frame_lines* L) {
       if (L->left_octave[i] < 0 || L->left_octave[i] > 64 || L->line_matches[i] >= L->n_right) return LLD_ERR_INVALID;
     }
     for (int i = 0; i < L->n_right; i++) if (L->right_octave[i] < 0 || L->right_octave[i] > 64) return LLD_ERR_INVALID;
+    if (L->n_left > track_max_lines(f->nt)) return LLD_ERR_UNSUPPORTED;
   }
   LLD_HIP_TRY(hipSetDevice(f->ctx->device));
   LLD_HIP_TRY(hipStreamSynchronize(f->ctx->stream));
@@ -456,6 +481,7 @@ int lld_frame_track_motion_model(lld_frame* f, const lld_track_params* P, const 
   if (nq < 0 || (nq > 0 && (!last->world_pos || !last->valid || !last->octave || !last->desc || !last_point_id || (P->check_orientation && !last->angle)))) return LLD_ERR_INVALID;
   if (P->check_orientation && nt > 0 && !f->has_angle) return LLD_ERR_INVALID;
   if (view->n_levels != f->consts.n_levels) return LLD_ERR_INVALID;
+  if (!(P->cam.fx > 0) || !(P->cam.fy > 0) || !f->has_inv_sigma2) return LLD_ERR_INVALID;   // PoseOptimization's intrinsics and information
   for (int i = 0; i < nq; i++) if (last->octave[i] < 0 || last->octave[i] >= f->consts.n_levels) return LLD_ERR_INVALID;
   lld_ctx* ctx = f->ctx;
   LLD_HIP_TRY(hipSetDevice(ctx->device));
@@ -527,6 +553,7 @@ int lld_frame_track_set_state(lld_frame* f, const lld_track_params* P, const lld
   if (!f || !P || !view || !pose_qt || !held) return LLD_ERR_INVALID;
   const int nt = f->nt;
   if (view->n_levels != f->consts.n_levels) return LLD_ERR_INVALID;
+  if (!(P->cam.fx > 0) || !(P->cam.fy > 0) || !f->has_inv_sigma2) return LLD_ERR_INVALID;
   if (nt > 0 && (!held->kp_point_id || !held->kp_world_pos)) return LLD_ERR_INVALID;
   if (held->n_seen < 0 || held->n_seen > nt || (held->n_seen > 0 && !held->seen_point_id)) return LLD_ERR_INVALID;   // the outlier discard marks at most one MapPoint per keypoint
   lld_ctx* ctx = f->ctx;
@@ -596,8 +623,8 @@ int lld_frame_track_local_map(lld_frame* f, const lld_track_params* P, const lld
   const int n_map = (local_lines && S->nl > 0) ? local_lines->n : 0;
   size_t o = 0;
   auto take = [&](size_t bytes) { const size_t at = o; o += al(bytes); return at; };
-  // stage 1's kernels may still be reading their part of the work block: stage 2 lives behind the high-water mark of stage 1's
-  // layout (both stages are laid out from the frame's sizes and this call's, so the block is simply split in two halves here)
+  // stage 2 reuses the work block from its start: stage 1's kernels are queued before this upload on the same stream, and ensure_work
+  // synchronises the stream before it grows the block
   const size_t o_prob = take(orbs_problem_bytes());
   const size_t o_pos = take((size_t)nq * 12), o_nrm = take((size_t)nq * 12), o_maxd = take((size_t)nq * 4), o_mind = take((size_t)nq * 4), o_obs = take(nq), o_skip = take(nq);
   const size_t o_desc = take((size_t)nq * 32), o_id = take((size_t)nq * 4);
@@ -609,7 +636,6 @@ int lld_frame_track_local_map(lld_frame* f, const lld_track_params* P, const lld
   o_so[0] = take((size_t)nq * 4); o_so[1] = take((size_t)nq * 4); o_so[2] = take((size_t)nq * 4); o_so[3] = take(nq); o_so[4] = take((size_t)nt * 4); o_so[5] = take(16);
   const size_t o_qrec = take(orbs_qrec_bytes(nq)), o_cache = take(orbs_cache_bytes(nq));
   const size_t o_lwork = take(line_track_work_bytes(n_map, S->nl)), o_pwork = take(pose_track_work_bytes(nt, S->nl));
-  // (one work block serves both stages one after the other: the stream orders stage 2's upload behind stage 1's last kernel)
   s = ensure_work(S, ctx, o); if (s) return s;
   s = ensure_stage(S, 1, up_bytes); if (s) return s;
   char* h = S->h_stage[1]; char* d = S->d_work;
@@ -631,17 +657,10 @@ int lld_frame_track_local_map(lld_frame* f, const lld_track_params* P, const lld
   LLD_HIP_TRY(hipMemcpyAsync(d, h, up_bytes, hipMemcpyHostToDevice, st));
   LLD_HIP_TRY(hipEventRecord(S->uploaded[1], st)); S->upload_pending[1] = true;
   // ---- kernels
-  {
-    auto pow2 = [](unsigned n) { unsigned p = 64; while (p < n) p <<= 1; return p; };
-    const unsigned psize = pow2(4u * (unsigned)std::max(nt, 1)), lsize = pow2(2u * (unsigned)S->D.tracked_cap);     // held + discarded <= 2 nt ids: at most half full
-    const size_t lds = ((size_t)psize + lsize) * 4;
-    if (lds > 150 * 1024) return LLD_ERR_UNSUPPORTED;
-    if (lds > 48 * 1024) LLD_HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(&track_mark_seen_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    if (nq + n_map > 0)
-      hipLaunchKernelGGL(track_mark_seen_kernel, dim3(1), dim3(kSeenThreads), lds, st, S->D, nq, reinterpret_cast<const int32_t*>(d + o_id),
-                         reinterpret_cast<const uint8_t*>(d + o_skip), reinterpret_cast<uint8_t*>(d + o_skip2), n_map, reinterpret_cast<const int32_t*>(d + U.id),
-                         reinterpret_cast<const uint8_t*>(d + U.skip), reinterpret_cast<uint8_t*>(d + o_lskip2), psize - 1, lsize - 1);
-  }
+  if (nq + n_map > 0)                                                          // (tables sized by state_build)
+    hipLaunchKernelGGL(track_mark_seen_kernel, dim3(1), dim3(kSeenThreads), S->seen_lds, st, S->D, nq, reinterpret_cast<const int32_t*>(d + o_id),
+                       reinterpret_cast<const uint8_t*>(d + o_skip), reinterpret_cast<uint8_t*>(d + o_skip2), n_map, reinterpret_cast<const int32_t*>(d + U.id),
+                       reinterpret_cast<const uint8_t*>(d + U.skip), reinterpret_cast<uint8_t*>(d + o_lskip2), S->seen_psize - 1, S->seen_lsize - 1);
   S->in_view_off = o_inview; S->n_in_view = nq;
   s = orbs_project_local_points(st, f, nullptr, S->D.view, MP, P->viewing_cos_limit, P->th_local, d + o_qrec, reinterpret_cast<uint8_t*>(d + o_inview),
                                 S->D.rec_h[1]->i + RI_IN_VIEW); if (s) return s;

@@ -1248,7 +1248,7 @@ extern "C" int lld_frame_create(lld_ctx* ctx, const lld_orb_search* kp, lld_fram
   for (int k = 0; k < nt; k++) if (kp->t_octave[k] < 0 || kp->t_octave[k] >= LLD_ORB_MAX_LEVELS) return LLD_ERR_INVALID;
   LLD_HIP_TRY(hipSetDevice(ctx->device));
   lld_frame* f = new lld_frame();
-  f->ctx = ctx; f->nt = nt; f->has_uright = kp->t_uright != nullptr; f->has_angle = kp->t_angle != nullptr;
+  f->ctx = ctx; f->nt = nt; f->has_uright = kp->t_uright != nullptr; f->has_angle = kp->t_angle != nullptr; f->has_inv_sigma2 = kp->level_inv_sigma2 != nullptr;
   f->consts = *kp;
   f->consts.t_desc = nullptr; f->consts.t_xy = nullptr; f->consts.t_octave = nullptr; f->consts.t_uright = nullptr; f->consts.t_angle = nullptr; f->consts.t_occupied = nullptr;
   f->consts.nq = 0; f->consts.q_desc = nullptr;

@@ -15,7 +15,7 @@ struct lld_frame_track_state;
 // as device arrays, so that the whole sequence runs without a trip through the host (lld_frame_track.hip).
 struct lld_frame {
   lld_ctx* ctx = nullptr;
-  int nt = 0; bool has_uright = false, has_angle = false;
+  int nt = 0; bool has_uright = false, has_angle = false, has_inv_sigma2 = false;
   char* d = nullptr;                       // one device allocation: desc | xy | octave | uright | angle
   size_t o_td = 0, o_txy = 0, o_toct = 0, o_tur = 0, o_tang = 0;
   lld_orb_search consts;                   // grid constants, n_levels; the level tables are copied below

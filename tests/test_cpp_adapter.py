@@ -679,7 +679,7 @@ def _read_track_dump(path, nt, nl, n_mp):
             o["lines"] = np.fromfile(f, np.int32, 2 * n[1]).reshape(-1, 2)       # id, tracked_last_id
             stages.append((d, o))
         in_view = np.fromfile(f, np.uint8, n_mp)
-        fin = np.fromfile(f, np.int32, 4)
+        fin = np.fromfile(f, np.int32, 5)      # return value, mbVO, mnMatchesInliers, SetPose calls in all, SetPose calls after TrackWithMotionModel
     return stages[0], stages[1], in_view, fin
 
 
@@ -762,3 +762,116 @@ def test_tracking_chain_adapter_on_live_objects(harness, oracle, tmp_path, scene
     ok = e1["n_search"] >= 10 and ((e1["n_points"] > 20) if only_tracking else (e1["n_points_map"] >= 7))
     assert fin[0] == int(ok) and fin[1] == int(bool(only_tracking) and e1["n_points_map"] < 10)
     assert fin[2] == (e2["n_points"] if only_tracking else e2["n_points_map"]) and fin[3] == 3
+
+
+def _run_track_harness(harness, tmp_path, sc, only_tracking, via_set_state):
+    from lld_slam_amd import tracking
+    nl = tracking.write_harness_scene(tmp_path / "in.bin", sc)
+    Tlast = np.array(sc["Tcw_guess"], np.float32).reshape(4, 4)                 # tlc = 0: direction 0
+    mb = np.float32(sc["cam"][4]) / np.float32(sc["cam"][0])
+    with open(tmp_path / "in.bin", "ab") as f:
+        Tlast.tofile(f); np.array([mb], np.float32).tofile(f); np.array([only_tracking, 0, via_set_state, 0], np.int32).tofile(f)
+    p = subprocess.run([harness, "track", str(tmp_path / "in.bin"), str(tmp_path / "out.bin")], capture_output=True, text=True, timeout=300)
+    assert p.returncode == 0, p.stderr
+    return _read_track_dump(tmp_path / "out.bin", sc["frame"].n, nl, len(sc["map_ids"]))
+
+
+def _same_counters(g, e):
+    for k in ("kp_point_id", "kp_outlier", "ln_line_id", "ln_outlier"):
+        np.testing.assert_array_equal(g[k], e[k], err_msg=k)
+    for k in ("n_inliers", "n_edges", "n_search_first", "n_search", "used_wide", "n_points", "n_points_map", "n_lines_matched", "n_lines", "n_discarded"):
+        assert g[k] == e[k], (k, g[k], e[k])
+    np.testing.assert_allclose(g["pose_qt"], e["pose_qt"], rtol=1e-6, atol=1e-8)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("name,only_tracking,via_set_state", [
+    ("fail_0", 0, 0), ("fail_0", 1, 1), ("fail_9_wide", 0, 0), ("fail_9_wide", 1, 0), ("fail_9_wide", 0, 1), ("fail_9_wide", 1, 1),
+    ("fail_10_wide", 0, 0), ("fail_10_wide", 1, 0), ("fail_10_wide", 0, 1),
+    ("map_6", 0, 0), ("map_7", 0, 0), ("only_20", 1, 0), ("only_21", 1, 0), ("vo_9", 1, 0), ("vo_10", 1, 0)])
+def test_tracking_adapter_at_the_failure_exit_and_return_boundaries(harness, oracle, tmp_path, name, only_tracking, via_set_state):
+    """FrameOnDevice::TrackWithMotionModel where src/Tracking.cc:913-917 returns false (fewer than 10 matches after the search used) and on
+    every boundary of its return value (:985-993), lines present.  After a failure the frame holds the raw matches of that search and nothing
+    else: mvbOutlier all false, no MapLines, the predicted mTcw (SetPose once), no mnLastFrameSeen / mbTrackInView / tracked_last_id marks.
+    TrackLocalMap then runs from that state (on the same device frame, or on a second one handed the objects' state) and equals the oracle's
+    TrackLocalMap from motion_model_failure_state."""
+    import oracle_tracking as OT
+    import track_scenes as TS
+    sc, params = TS.scene(name)
+    assert not params
+    nt, n_mp, cur_id = sc["frame"].n, len(sc["map_ids"]), 42
+    nl = len(sc["lines"]["left_lines"])
+    (g1, o1), (g2, o2), in_view, fin = _run_track_harness(harness, tmp_path, sc, only_tracking, via_set_state)
+    e1 = TS.stage1(sc)                                                           # the device chain's stage 1 runs on past the exit
+    _same_counters(g1, e1)
+    failed = OT.motion_model_failure_state(sc)
+    assert (failed is not None) == (name in ("fail_0", "fail_9_wide"))
+    lib = oracle.lib()
+    ids = np.asarray(sc["map_ids"]); order = np.argsort(ids)
+    pts1, pts2 = o1["points"], o2["points"]
+    assert np.array_equal(pts1[:, 0], ids[order]) and np.array_equal(pts2[:, 0], ids[order])
+    # ---- the frame and the objects after TrackWithMotionModel
+    if failed is not None:
+        fr = failed["frame"]
+        np.testing.assert_array_equal(failed["kp_point_id"], g1["kp_point_id"])   # the raw matches ARE the stage-1 record's ids
+        np.testing.assert_array_equal(o1["mvpMapPoints"], failed["kp_point_id"])
+        np.testing.assert_array_equal(o1["mvbOutlier"], np.zeros(nt, np.uint8))
+        np.testing.assert_array_equal(o1["mvpMapLines"], np.full(nl, -1, np.int32))
+        np.testing.assert_array_equal(o1["mvbOutlierLines"], np.zeros(nl, np.uint8))
+        np.testing.assert_array_equal(o1["mTcw"], failed["Tcw"])
+        np.testing.assert_array_equal(failed["Tcw"], np.asarray(sc["Tcw_guess"], np.float32))
+        assert fin[4] == 1                                                       # the prediction's SetPose only
+        assert np.all(pts1[:, 4] == 0) and np.all(pts1[:, 3] == 0) and np.all(pts1[:, 1] == 1) and np.all(pts1[:, 2] == 1)
+        np.testing.assert_array_equal(o1["lines"][:, 1], np.full(len(o1["lines"]), -1))
+        assert fin[0] == 0 and fin[1] == 0                                       # return false; mbVO untouched
+        held0, seen0 = set(int(i) for i in failed["kp_point_id"] if i >= 0), set()
+        took = set()
+        flags_pt, flags_ln = np.zeros(nt, np.uint8), np.zeros(nl, np.uint8)
+    else:
+        fr = OT.new_frame(sc)
+        searched = OT.motion_model_search(sc, fr)
+        e1b = OT.motion_model_rest(sc, fr, searched)
+        keep = (e1b["kp_point_id"] >= 0) & (e1b["kp_outlier"] == 0)
+        np.testing.assert_array_equal(o1["mvpMapPoints"], np.where(keep, e1b["kp_point_id"], -1))
+        np.testing.assert_array_equal(o1["mvbOutlier"], np.zeros(nt, np.uint8))
+        lkeep = (e1b["ln_line_id"] >= 0) & (e1b["ln_outlier"] == 0)
+        np.testing.assert_array_equal(o1["mvpMapLines"], np.where(lkeep, e1b["ln_line_id"], -1))
+        flags_ln = np.where(e1b["ln_line_id"] >= 0, e1b["ln_outlier"], 0).astype(np.uint8)
+        np.testing.assert_array_equal(o1["mvbOutlierLines"], flags_ln)
+        np.testing.assert_allclose(o1["mTcw"], host.se3_to_tcw_f32(lib, e1b["pose_qt"]), rtol=0, atol=2e-6)
+        assert fin[4] == 2
+        thrown = set(int(i) for i in e1b["kp_point_id"][(e1b["kp_point_id"] >= 0) & (e1b["kp_outlier"] != 0)])
+        np.testing.assert_array_equal(pts1[:, 4], [cur_id if int(i) in thrown else 0 for i in pts1[:, 0]])
+        took = set(int(i) for i in e1b["ln_line_id"][e1b["ln_line_id"] >= 0])
+        np.testing.assert_array_equal(o1["lines"][:, 1], [cur_id if int(i) in took else -1 for i in o1["lines"][:, 0]])
+        ok = (e1b["n_points"] > 20) if only_tracking else (e1b["n_points_map"] >= 7)
+        assert fin[0] == int(ok) and fin[1] == int(bool(only_tracking) and e1b["n_points_map"] < 10)
+        want = dict(map_6=0, map_7=1, only_20=0, only_21=1).get(name)
+        if want is not None:
+            assert fin[0] == want
+        if name.startswith("vo_"):
+            assert fin[0] == 1 and fin[1] == int(name == "vo_9")
+        held0, seen0 = set(int(i) for i in e1b["kp_point_id"][keep]), thrown
+        flags_pt = np.zeros(nt, np.uint8)
+    # ---- TrackLocalMap from that state
+    e2 = OT.track_local_map(sc, fr)
+    _same_counters(g2, e2)
+    np.testing.assert_array_equal(in_view, e2["mp_in_view"])
+    keep2 = (e2["kp_point_id"] >= 0) & (e2["kp_outlier"] == 0)
+    np.testing.assert_array_equal(o2["mvpMapPoints"], np.where(keep2, e2["kp_point_id"], -1))
+    np.testing.assert_array_equal(o2["mvbOutlier"], np.where(e2["kp_point_id"] >= 0, e2["kp_outlier"], flags_pt))
+    lkeep2 = (e2["ln_line_id"] >= 0) & (e2["ln_outlier"] == 0)
+    np.testing.assert_array_equal(o2["mvpMapLines"], np.where(lkeep2, e2["ln_line_id"], -1))
+    np.testing.assert_array_equal(o2["mvbOutlierLines"], np.where(e2["ln_line_id"] >= 0, e2["ln_outlier"], flags_ln))
+    np.testing.assert_allclose(o2["mTcw"], host.se3_to_tcw_f32(lib, e2["pose_qt"]), rtol=0, atol=2e-6)
+    held2 = set(int(i) for i in e2["kp_point_id"][keep2])
+    vis = 1 + np.array([int(i) in held0 for i in ids]) + e2["mp_in_view"].astype(int)
+    found = 1 + np.array([int(i) in held2 for i in ids])
+    seen = np.array([cur_id if (int(i) in held0 or int(i) in seen0) else 0 for i in ids])
+    np.testing.assert_array_equal(pts2[:, 1], vis[order]); np.testing.assert_array_equal(pts2[:, 2], found[order])
+    np.testing.assert_array_equal(pts2[:, 3], e2["mp_in_view"][order]); np.testing.assert_array_equal(pts2[:, 4], seen[order])
+    took |= set(int(i) for i in e2["ln_line_id"][e2["ln_line_id"] >= 0])
+    np.testing.assert_array_equal(o2["lines"][:, 1], [cur_id if int(i) in took else -1 for i in o2["lines"][:, 0]])
+    assert fin[2] == (e2["n_points"] if only_tracking else e2["n_points_map"])
+    assert fin[3] == fin[4] + int(e2["n_point_edges"] >= 3)
+    assert e2["n_points"] > 20 and e2["n_lines_matched"] > 0                    # TrackLocalMap finds the frame again from the prediction

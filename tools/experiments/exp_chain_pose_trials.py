@@ -6,7 +6,7 @@ sys.path[:0] = [ROOT, os.path.join(ROOT, "oracle")]
 import numpy as np
 import oracle_tracking as OT
 import oracle_py as O
-from lld_slam_amd import Context, Optimizer, synth
+from lld_slam_amd import Context, Optimizer, host, synth
 from lld_slam_amd.tracking import DeviceTrackedFrame
 arg = sys.argv[1] if len(sys.argv) > 1 else "mono"
 if arg == "mono":
@@ -16,7 +16,7 @@ if arg == "mono":
 else:
     sc = synth.make_tracking_scene(int(arg))
 e1, e2 = OT.track_frame(sc)
-probs = OT.track_frame.last_problems
+probs = [host.PoseFrame(**vars(p)) for p in OT.track_frame.last_problems]      # the checker keeps plain arrays
 with Context(0) as ctx:
     for k, prob in enumerate(probs):
         o = O.pose_opt(prob, 0.5)

@@ -56,7 +56,8 @@ def main():
                 # chain's edge assembly or in the optimiser's path?
                 import oracle_py as O
                 from lld_slam_amd import Optimizer
-                for k, prob in enumerate(OT.track_frame.last_problems):
+                from lld_slam_amd import host as H
+                for k, prob in enumerate([H.PoseFrame(**vars(p)) for p in OT.track_frame.last_problems]):   # (the checker keeps plain arrays)
                     o = O.pose_opt(prob, 0.5); d = Optimizer(ctx).PoseOptimization(prob, 0.5)
                     print(f"  stage {k + 1} problem {prob.n_points}+{prob.n_lines}: oracle {o.lm_iterations}/{o.lm_trials} chi2 {o.chi2:.10g} | lld_pose_opt {d.lm_iterations}/{d.lm_trials} chi2 {d.chi2:.10g} "
                           f"| chain {g[k]['lm_iterations']}/{g[k]['lm_trials']} chi2 {g[k]['chi2']:.10g} | dpose(pose_opt, oracle) {np.max(np.abs(d.pose_qt - o.pose_qt)):.2e} dpose(chain, oracle) {np.max(np.abs(g[k]['pose_qt'] - o.pose_qt)):.2e}")
