@@ -1,7 +1,8 @@
 #!/usr/bin/env python3
 """bench.py — throughput of the batched local bundle adjustment (the metric of BASELINE.json) on N MI355X.
 
-  python bench.py --gpus 1 --steps 3 --warmup 1
+  python bench.py --gpus 1 --steps 3 --warmup 1            (the headline alone)
+  python bench.py --gpus 1 --steps 3 --warmup 1 --full     (the headline and every other figure below)
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P bench.py --gpus N ...
 
 One "step" = one pass of the hot path (Optimizer::LocalBundleAdjustment, both LM rounds, outlier protocol, read-back) over
@@ -11,12 +12,18 @@ are independent, so ranks shard the window list - weak scaling by default (--win
 splits the same --windows-per-gpu windows over the ranks - and the only collective is the gather of the fixed-stride result
 records to rank 0 (RCCL), inside the timed region (lld_slam_amd/dist.py, the module tests/test_distributed_cpu.py drives over gloo).
 
-Rank 0 prints ONE JSON line.
+Rank 0 prints ONE JSON line.  A plain run does what the headline needs and no more: it generates the windows, uploads them, ramps the
+clocks, runs the W warm-up and the K timed steps, writes --dump-outputs and prints `value`, `ms_per_step`, `config` and `lm`.  Everything
+else is measured with --full only (each block can be left out of a --full run by its --no-* option); without it these keys are null or absent:
+  config.gathered_records_ok  the gathered result records checked against the windows each rank was given (N = 1: one untimed step through
+                a one-rank RCCL group after the timed region)
+  rccl_overhead N = 1: the K steps again with the asynchronous one-rank RCCL gather behind every solve, against K plain steps
   roofline      the dominant kernel family of the step (by summed HIP-event time on the library's own stream) under two rulers:
                 model bytes (SURVEY.md §8d record sizes) against the nominal 8 TB/s, and the bytes the HBM-side
                 counters saw (profiles/roofline_traffic.json) against the 6.3 TB/s a streaming kernel reaches on this part; every
                 other family under both rulers in `families`
-  cpu_baseline  the single-threaded CPU oracle (a port of the reference algorithm, not the reference binary) on a bounded sample
+  cpu_baseline  the single-threaded CPU oracle (a port of the reference algorithm, not the reference binary) on a bounded sample;
+  parity        the same sample's results against the device's (matched chi2, identical outlier sets)
   e2e           host buffers in -> results out at the C ABI, steady state: three host threads, each create -> solve -> download on its
                 own context (NOT `value`, which times resident windows)
   secondary     the other BASELINE.json configs, untimed by `value`: PoseOptimization (4096 frames), ORB + LBD brute force (1024 frame
@@ -577,6 +584,140 @@ def e2e_block(windows, device, lanes=3, batches_per_lane=16):
             "note": "host buffers in, results out, at the C ABI; `value` times resident windows.  The Python mirror (BABatch(ctx, windows)) adds its ctypes marshalling on top."}
 
 
+# ================================================================================================== --full: roofline, CPU baseline
+def roofline_block(windows, stats, phase, launches, step_s, stream_gbs):
+    """Roofline of the dominant kernel family (HIP events of the single-stream roofline pass, recorded on the library's own stream) and
+    both rulers of every other family.  `step_s`: seconds per timed step; `stream_gbs`: copy_ceiling_gbs()."""
+    import numpy as np
+    wpg = len(windows)
+    per = {k: 0 for k in PHASES}
+    for w, s in zip(windows, stats):
+        ab = algorithmic_bytes(w, sum(s["lm_trials"]), sum(s["lm_iterations"]), s["pcg_iterations"])
+        for k in PHASES:
+            per[k] += ab[k]
+    kdom = int(np.argmax(phase[:5])); kname = PHASES[kdom]
+    traffic_tab = _traffic_table() if wpg == 256 else {}          # the committed counters were collected on 256-window launches
+    issue_tab = _issue_table() if wpg == 256 else {}
+    def rulers(k):
+        i = PHASES.index(k); ms_k = float(phase[i]); n = max(float(launches[i]), 1.0)
+        if ms_k <= 0:
+            return None
+        model = per[k] / (ms_k * 1e-3) / 1e9
+        r = {"avg_launch_ms": round(ms_k / n, 4), "model_bytes_per_launch": int(per[k] / n), "model_GBps": round(model, 1), "model_frac_of_8TBps": round(model / HBM_PEAK_GBS, 4)}
+        tb = traffic_tab.get(k)
+        if tb:
+            cnt = tb / (ms_k / n * 1e-3) / 1e9
+            r.update({"counter_bytes_per_launch": int(tb), "counter_GBps": round(cnt, 1), "counter_frac_of_8TBps": round(cnt / HBM_PEAK_GBS, 4),
+                      "counter_frac_of_6.3TBps_achievable": round(cnt / HBM_ACHIEVABLE_GBS, 4), "model_over_counter": round(per[k] / n / tb, 3)})
+        iq = issue_tab.get(k)
+        if iq:
+            # the compute ruler that exists for EVERY family (round 6): VALU instructions the counters saw per launch against the issue peak of
+            # one instruction per 4 clocks and SIMD, and how busy the LDS pipe was - next to the HBM ruler, the larger of the two names the
+            # resource the family is closest to
+            t_launch = ms_k / n * 1e-3
+            r["valu_issue_frac"] = round(iq["SQ_INSTS_VALU"] * 4.0 / (1024 * t_launch * 2.4e9), 4)
+            r["lds_pipe_busy_frac"] = round(iq["SQ_LDS_IDX_ACTIVE"] / (256 * t_launch * 2.4e9), 4)
+            r["lds_bank_conflict_of_lds_cycles"] = round(iq["SQ_LDS_BANK_CONFLICT"] / max(iq["SQ_LDS_IDX_ACTIVE"], 1.0), 4)
+            cand = {"valu_issue": r["valu_issue_frac"], "lds_pipe": r["lds_pipe_busy_frac"], "hbm": r.get("counter_frac_of_8TBps") or 0.0}
+            r["closest_ruler"] = max(cand, key=cand.get)
+        if tb and per[k] / n / tb > 1.5:
+            # the SURVEY model charges this family bytes its kernels do not move (point Hpl blocks are recomputed, not stored): the
+            # model ruler would print an impossible fraction of the peak - it is withdrawn here, the counter ruler stands
+            r["model_frac_of_8TBps"] = None
+            r["model_ruler"] = "invalid for this family (model bytes > 1.5 x the bytes the HBM counters saw); use the counter ruler"
+        return r
+    fam = {k: rulers(k) for k in PHASES if k != "ba_control"}
+    dom = fam[kname]
+    # HBM ruler of the dominant family: the bytes the counters SAW (per launch, committed passes) over this run's HIP-event time, against the
+    # 8 TB/s of the data sheet; the SURVEY model (which charges every point edge a 144 B block the kernels recompute) stays beside it
+    hbm = {"achieved": dom.get("counter_GBps"), "peak": HBM_PEAK_GBS, "unit": "GB/s",
+           "frac": None if "counter_GBps" not in dom else round(dom["counter_GBps"] / HBM_PEAK_GBS, 4), "source": "counters" if "counter_GBps" in dom else None,
+           "frac_of_6.3TBps_achievable": dom.get("counter_frac_of_6.3TBps_achievable"),
+           "model": {"achieved": dom["model_GBps"], "frac": round(dom["model_GBps"] / HBM_PEAK_GBS, 4), "algorithmic_bytes_per_launch": dom["model_bytes_per_launch"],
+                     "note": "SURVEY 8d bytes: W + V + S per launch; charges point Hpl blocks the kernel does not move"}}
+    if hbm["achieved"] is None:                      # no counters for this batch size: the model is all there is
+        hbm.update({"achieved": dom["model_GBps"], "frac": round(dom["model_GBps"] / HBM_PEAK_GBS, 4), "source": "model"})
+    # the whole step: counter bytes of every family x its launches in the single-stream step, over the TIMED step
+    step_ruler = None
+    if traffic_tab:
+        step_bytes = sum(float(traffic_tab.get(k, 0)) * float(launches[i]) for i, k in enumerate(PHASES)) + float(traffic_tab.get("_other_per_solve", 0))
+        step_gbs = step_bytes / step_s / 1e9
+        step_ruler = {"counter_bytes_per_step": int(step_bytes), "achieved_GBps": round(step_gbs, 1), "frac_of_8TBps": round(step_gbs / HBM_PEAK_GBS, 4),
+                      "note": "sum over the kernel families of (counter bytes per launch x launches of the single-stream step) / ms_per_step of the timed steps"}
+    roofline = {"kernel": kname, "traffic": dom.get("counter_bytes_per_launch"),
+                "traffic_source": None if not traffic_tab else "profiles/roofline_traffic.json (" + str(traffic_tab.get("_taken_on", "see its _note")) + "): TCC FETCH_SIZE (doubled on gfx950) + WRITE_SIZE of separate "
+                                  "rocprofv3 --pmc passes over `bench.py --windows-per-gpu 256` (tools/profile_pmc.sh + tools/make_roofline_traffic.py); NOT re-measured in this run "
+                                  "(a bench process cannot run under --pmc and time itself)",
+                "hbm": hbm, "step": step_ruler,
+                "measured_copy_ceiling_GBps": stream_gbs,
+                "launches_per_step": float(launches[kdom]), "avg_launch_ms": dom["avg_launch_ms"], "algorithmic_bytes_per_launch": dom["model_bytes_per_launch"],
+                "families": fam,
+                "rulers": "model = SURVEY §8d bytes (charges every point edge a 144 B Hpl block the kernels recompute instead of moving: where model_over_counter > 1 "
+                          "the model ruler overstates traffic and the counter ruler is the honest one); counter = FETCH_SIZE (doubled on gfx950) + WRITE_SIZE of separate rocprofv3 --pmc passes",
+                "phase_ms_single_stream_step": {k: round(float(phase[i]), 3) for i, k in enumerate(PHASES)},
+                "solve_ms_single_stream_step": round(float(phase[5]), 3)}
+    if kname == "ba_schur":
+        # The ruler that BINDS this family is arithmetic (fp64 vector FMA; the blocks are 6x6 / 6x3 / 6x4, no matrix cores): it goes first.
+        fma_total = sum(schur_fmas(w, sum(st_["lm_trials"])) for w, st_ in zip(windows, stats))
+        tf = fma_total / (float(phase[kdom]) * 1e-3) / 1e12
+        roofline.update({"bound": "fp64_fma", "achieved": round(2.0 * tf, 2), "peak": round(2.0 * FP64_FMA_PEAK_T, 1), "unit": "TFLOP/s", "frac": round(tf / FP64_FMA_PEAK_T, 4),
+                         "fp64_fma": {"achieved_TFMA_per_s": round(tf, 2), "peak_TFMA_per_s": FP64_FMA_PEAK_T, "frac": round(tf / FP64_FMA_PEAK_T, 4),
+                                      "note": "useful FMAs of the family (bench.schur_fmas) over its HIP-event time; vector fp64 peak = 256 CU x 4 SIMD x 16 lanes/clk x 2.4 GHz"}})
+    else:
+        roofline.update({"bound": "hbm", "achieved": hbm["achieved"], "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": hbm["frac"]})
+    return roofline
+
+
+def cpu_baseline_block(batch, windows, cpu_sample):
+    """CPU baseline + matched-chi2 check (N=1 only): the single-threaded oracle on a bounded sample spread over the batch, its results against
+    what the batch's last solve computed, then the same port with one window per host thread."""
+    import numpy as np
+    import oracle_py as O
+    wpg = len(windows)
+    O.lib()
+    ns = min(cpu_sample, wpg)
+    ids = sorted(set(int(round(i * (wpg - 1) / max(1, ns - 1))) for i in range(ns)))     # spread over the batch: every stream group is sampled
+    tc = time.perf_counter(); ores = [O.local_ba(windows[i]) for i in ids]; cpu_s = time.perf_counter() - tc
+    gres = [batch.download(i) for i in ids]
+    rel = max(abs(g.stats["chi2_final"] - o.stats["chi2_final"]) / max(o.stats["chi2_final"], 1e-300) for g, o in zip(gres, ores))
+    same = all(np.array_equal(g.pt_obs_outlier, o.pt_obs_outlier) and np.array_equal(g.ln_edge_outlier, o.ln_edge_outlier) and np.array_equal(g.line_removed, o.line_removed)
+               for g, o in zip(gres, ores))
+    # the same port with one window per host thread (the reference's g2o is single-threaded per window; ctypes drops the GIL)
+    from concurrent.futures import ThreadPoolExecutor
+    nthr = max(1, min(os.cpu_count() or 1, 32, wpg))
+    tp = time.perf_counter()
+    with ThreadPoolExecutor(nthr) as ex:
+        list(ex.map(lambda i: O.local_ba(windows[i]), range(nthr)))
+    par_s = time.perf_counter() - tp
+    cpu = {"value": round(len(ids) / cpu_s, 4), "unit": "windows/s", "cores": 1, "kind": "port",
+           "sample": f"{len(ids)} LBA-B windows (ids {ids}) through oracle/liblld_oracle.so, 1 thread, exact dense LDLT of the reduced system",
+           "all_cores": {"value": round(nthr / par_s, 4), "cores": nthr, "sample": f"{nthr} windows, one per thread, concurrently"}}
+    pose_err = max(float(np.max(np.abs(g.cam_qt - o.cam_qt)) / np.max(np.abs(o.cam_qt))) for g, o in zip(gres, ores))
+    pt_err = np.concatenate([np.linalg.norm(g.pt_xyz - o.pt_xyz, axis=1) / np.linalg.norm(o.pt_xyz, axis=1) for g, o in zip(gres, ores)])
+    parity = {"windows_checked": len(ids), "window_ids": ids, "max_rel_chi2_final": float(rel), "outlier_sets_identical": bool(same),
+              "max_rel_pose": pose_err, "median_rel_point": float(np.median(pt_err)), "points_within_1e-5": float(np.mean(pt_err <= 1e-5))}
+    return cpu, parity
+
+
+def copy_ceiling_gbs(dev):
+    """Measured stream ceiling of this GPU (SURVEY.md §8d asks for it next to the nominal 8 TB/s): a device-to-device copy of 2 GiB,
+    bytes read + bytes written over the HIP-event time, best of 5."""
+    import torch
+    try:
+        a = torch.empty(1 << 31, dtype=torch.uint8, device=dev); b = torch.empty_like(a)
+        b.copy_(a); torch.cuda.synchronize()
+        best = 1e30
+        for _ in range(5):
+            e0 = torch.cuda.Event(enable_timing=True); e1 = torch.cuda.Event(enable_timing=True)
+            e0.record(); b.copy_(a); e1.record(); torch.cuda.synchronize()
+            best = min(best, e0.elapsed_time(e1))
+        gbs = round(2.0 * a.numel() / (best * 1e-3) / 1e9, 1)
+        del a, b
+        return gbs
+    except Exception:
+        return None
+
+
 # ================================================================================================== main
 def main():
     ap = argparse.ArgumentParser()
@@ -587,15 +728,17 @@ def main():
     ap.add_argument("--ramp-steps-max", type=int, default=60)
     ap.add_argument("--windows-per-gpu", type=int, default=256, help="windows per GPU (weak scaling); with --strong: windows in total")
     ap.add_argument("--strong", action="store_true", help="strong scaling: the same --windows-per-gpu windows split over the ranks (SURVEY §8d: 256 windows, 32 per GPU at 8)")
-    ap.add_argument("--cpu-sample", type=int, default=40, help="LBA-B windows timed on the CPU oracle (rank 0, N=1 only)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-secondary", action="store_true", help="skip the PO / MATCH / LBA-A / single-call block (N=1 only anyway)")
-    ap.add_argument("--no-e2e", action="store_true", help="skip the host-buffers-in / results-out pipeline (N=1 only anyway)")
-    ap.add_argument("--e2e-lanes", type=int, default=3, help="host threads of the e2e leg (solves take turns on the device; a third lane keeps a batch ready: 4250 -> 4490 windows/s)")
+    ap.add_argument("--full", action="store_true", help="after the headline, measure and check everything else: roofline pass and copy ceiling, gathered-record check, "
+                    "rccl_overhead, CPU baseline and parity, e2e, secondary configs (a plain run does none of these)")
+    ap.add_argument("--cpu-sample", type=int, default=40, help="LBA-B windows timed on the CPU oracle (--full; rank 0, N=1 only)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU baseline and its parity block")
+    ap.add_argument("--no-secondary", action="store_true", help="--full without the PO / MATCH / LBA-A / single-call block")
+    ap.add_argument("--no-e2e", action="store_true", help="--full without the host-buffers-in / results-out pipeline (N=1 only anyway)")
+    ap.add_argument("--e2e-lanes", type=int, default=3, help="host threads of the e2e leg of --full (solves take turns on the device; a third lane keeps a batch ready: 4250 -> 4490 windows/s)")
     ap.add_argument("--shared-accumulators", action="store_true", help="run the timed leg with lld_ba_params.deterministic = 0 (not bit-reproducible; the default is)")
     ap.add_argument("--groups", type=int, default=0, help="stream groups of the timed solves (0 = the library's choice; 1 under rocprofv3: per-kernel times of one stream)")
     ap.add_argument("--gen-workers", type=int, default=0, help="processes generating the synthetic windows (0 = auto; use 1 under rocprofv3)")
-    ap.add_argument("--no-rccl-check", action="store_true", help="N = 1: skip the untimed step through a one-rank RCCL group (profiling runs: no RCCL kernels in the trace)")
+    ap.add_argument("--no-rccl-check", action="store_true", help="--full at N = 1 without the untimed step through a one-rank RCCL group and rccl_overhead")
     ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="after the timed steps, write what the last one computed (rank 0's windows) as DIR/<name>.npy")
     args = ap.parse_args()
     if args.steps < 1 or args.warmup < 0:
@@ -680,41 +823,29 @@ def main():
     D.barrier(use_dist, True)
     elapsed = time.perf_counter() - t0
     dumped = dump_outputs(args.dump_outputs, batch) if args.dump_outputs and rank == 0 else None     # before any further solve overwrites them
-    # Roofline pass (untimed): the timed steps keep several window groups in flight on separate streams, so their HIP-event
-    # brackets overlap; one more step with a single group gives disjoint per-kernel-family event times on that stream.
-    # Per-phase events are off in the timed steps, as in the product's default (lld_ba_batch_set_phase_timing: six event records per
-    # super-step cost 1.6 % of a 256-window solve and 10 - 15 % of a small batch's); this pass turns them on.
-    batch.set_groups(1); batch.set_phase_timing(True)
-    batch.solve()
-    phase = batch.phase_ms()
-    launches = np.array([batch.kernel_stats(k)[0] for k in range(5)], dtype=np.float64)
-    batch.set_phase_timing(False); batch.set_groups(args.groups)
-    # Measured stream ceiling of this GPU (SURVEY.md §8d asks for it next to the nominal 8 TB/s): a device-to-device copy of 2 GiB,
-    # bytes read + bytes written over the HIP-event time, best of 5.
-    stream_gbs = None
-    if rank == 0:
-        try:
-            a = torch.empty(1 << 31, dtype=torch.uint8, device=dev); b = torch.empty_like(a)
-            b.copy_(a); torch.cuda.synchronize()
-            best = 1e30
-            for _ in range(5):
-                e0 = torch.cuda.Event(enable_timing=True); e1 = torch.cuda.Event(enable_timing=True)
-                e0.record(); b.copy_(a); e1.record(); torch.cuda.synchronize()
-                best = min(best, e0.elapsed_time(e1))
-            stream_gbs = round(2.0 * a.numel() / (best * 1e-3) / 1e9, 1)
-            del a, b
-        except Exception:
-            stream_gbs = None
+    phase = launches = stream_gbs = None
+    if args.full:
+        # Roofline pass (untimed): the timed steps keep several window groups in flight on separate streams, so their HIP-event
+        # brackets overlap; one more step with a single group gives disjoint per-kernel-family event times on that stream.
+        # Per-phase events are off in the timed steps, as in the product's default (lld_ba_batch_set_phase_timing: six event records per
+        # super-step cost 1.6 % of a 256-window solve and 10 - 15 % of a small batch's); this pass turns them on.
+        batch.set_groups(1); batch.set_phase_timing(True)
+        batch.solve()
+        phase = batch.phase_ms()
+        launches = np.array([batch.kernel_stats(k)[0] for k in range(5)], dtype=np.float64)
+        batch.set_phase_timing(False); batch.set_groups(args.groups)
+        if rank == 0:
+            stream_gbs = copy_ceiling_gbs(dev)
     elapsed = D.max_over_ranks(elapsed, dev, use_dist)
 
     stats = batch.stats()
-    # One rank, no launcher: the timed steps above had no collective to run.  ONE untimed step now goes through a one-rank RCCL group - the
+    # --full, one rank, no launcher: the timed steps above had no collective to run.  ONE untimed step now goes through a one-rank RCCL group - the
     # same RecordGather the N > 1 line times, the same check of the gathered records - so that the driver's N = 1 line says whether the
     # collective path works on this box (`gathered_records_ok`), not null.  Failing to bring RCCL up must not cost the headline line.
     late_gather = None
     pg_inited = use_dist                                          # a process group we must destroy, whatever happens after its creation
     rccl_overhead = None
-    if world == 1 and not use_dist and not args.no_rccl_check:
+    if args.full and world == 1 and not use_dist and not args.no_rccl_check:
         try:
             sys.stdout.flush(); saved_stdout = os.dup(1); os.dup2(2, 1)          # (RCCL's banner goes to stderr)
             os.environ.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")
@@ -755,12 +886,12 @@ def main():
     if rank == 0:
         # every rank's records arrived AND are the windows shard() assigned: per rank, the first and the last record are checked against
         # the window id of their slot (index + edge count in the header, fixed cameras bit for bit against the generator), all headers
-        # for a finished protocol
+        # for a finished protocol (--full)
         gathered_ok = None
         if late_gather is not None:                        # N = 1: the untimed one-rank RCCL step above
             gather, counts_g, common_stride = late_gather[0], late_gather[1], late_gather[2]
             assert counts_g == counts
-        if use_dist or late_gather is not None:
+        if args.full and (use_dist or late_gather is not None):
             gathered_ok = True
             try:
                 D.verify_gathered_records(gather.rank_records, counts, common_stride, args.windows_per_gpu, world, args.strong, synth.make_lba_b)
@@ -773,110 +904,13 @@ def main():
                     gathered_ok = bool(gathered_ok and np.isfinite(h[1]) and h[1] > 0 and h[2] >= 1 and h[8] == k)
         total_windows = sum(counts) * args.steps
         value = total_windows / elapsed
-        # ---- roofline of the dominant kernel family (HIP events recorded on the library's own stream)
-        per = {k: 0 for k in PHASES}
-        for w, s in zip(windows, stats):
-            ab = algorithmic_bytes(w, sum(s["lm_trials"]), sum(s["lm_iterations"]), s["pcg_iterations"])
-            for k in PHASES:
-                per[k] += ab[k]
-        kdom = int(np.argmax(phase[:5])); kname = PHASES[kdom]
-        traffic_tab = _traffic_table() if wpg == 256 else {}          # the committed counters were collected on 256-window launches
-        issue_tab = _issue_table() if wpg == 256 else {}
-        def rulers(k):
-            i = PHASES.index(k); ms_k = float(phase[i]); n = max(float(launches[i]), 1.0)
-            if ms_k <= 0:
-                return None
-            model = per[k] / (ms_k * 1e-3) / 1e9
-            r = {"avg_launch_ms": round(ms_k / n, 4), "model_bytes_per_launch": int(per[k] / n), "model_GBps": round(model, 1), "model_frac_of_8TBps": round(model / HBM_PEAK_GBS, 4)}
-            tb = traffic_tab.get(k)
-            if tb:
-                cnt = tb / (ms_k / n * 1e-3) / 1e9
-                r.update({"counter_bytes_per_launch": int(tb), "counter_GBps": round(cnt, 1), "counter_frac_of_8TBps": round(cnt / HBM_PEAK_GBS, 4),
-                          "counter_frac_of_6.3TBps_achievable": round(cnt / HBM_ACHIEVABLE_GBS, 4), "model_over_counter": round(per[k] / n / tb, 3)})
-            iq = issue_tab.get(k)
-            if iq:
-                # the compute ruler that exists for EVERY family (round 6): VALU instructions the counters saw per launch against the issue peak of
-                # one instruction per 4 clocks and SIMD, and how busy the LDS pipe was - next to the HBM ruler, the larger of the two names the
-                # resource the family is closest to
-                t_launch = ms_k / n * 1e-3
-                r["valu_issue_frac"] = round(iq["SQ_INSTS_VALU"] * 4.0 / (1024 * t_launch * 2.4e9), 4)
-                r["lds_pipe_busy_frac"] = round(iq["SQ_LDS_IDX_ACTIVE"] / (256 * t_launch * 2.4e9), 4)
-                r["lds_bank_conflict_of_lds_cycles"] = round(iq["SQ_LDS_BANK_CONFLICT"] / max(iq["SQ_LDS_IDX_ACTIVE"], 1.0), 4)
-                cand = {"valu_issue": r["valu_issue_frac"], "lds_pipe": r["lds_pipe_busy_frac"], "hbm": r.get("counter_frac_of_8TBps") or 0.0}
-                r["closest_ruler"] = max(cand, key=cand.get)
-            if tb and per[k] / n / tb > 1.5:
-                # the SURVEY model charges this family bytes its kernels do not move (point Hpl blocks are recomputed, not stored): the
-                # model ruler would print an impossible fraction of the peak - it is withdrawn here, the counter ruler stands
-                r["model_frac_of_8TBps"] = None
-                r["model_ruler"] = "invalid for this family (model bytes > 1.5 x the bytes the HBM counters saw); use the counter ruler"
-            return r
-        fam = {k: rulers(k) for k in PHASES if k != "ba_control"}
-        dom = fam[kname]
-        # HBM ruler of the dominant family: the bytes the counters SAW (per launch, committed passes) over this run's HIP-event time, against the
-        # 8 TB/s of the data sheet; the SURVEY model (which charges every point edge a 144 B block the kernels recompute) stays beside it
-        hbm = {"achieved": dom.get("counter_GBps"), "peak": HBM_PEAK_GBS, "unit": "GB/s",
-               "frac": None if "counter_GBps" not in dom else round(dom["counter_GBps"] / HBM_PEAK_GBS, 4), "source": "counters" if "counter_GBps" in dom else None,
-               "frac_of_6.3TBps_achievable": dom.get("counter_frac_of_6.3TBps_achievable"),
-               "model": {"achieved": dom["model_GBps"], "frac": round(dom["model_GBps"] / HBM_PEAK_GBS, 4), "algorithmic_bytes_per_launch": dom["model_bytes_per_launch"],
-                         "note": "SURVEY 8d bytes: W + V + S per launch; charges point Hpl blocks the kernel does not move"}}
-        if hbm["achieved"] is None:                      # no counters for this batch size: the model is all there is
-            hbm.update({"achieved": dom["model_GBps"], "frac": round(dom["model_GBps"] / HBM_PEAK_GBS, 4), "source": "model"})
-        # the whole step: counter bytes of every family x its launches in the single-stream step, over the TIMED step
-        step_ruler = None
-        if traffic_tab:
-            step_bytes = sum(float(traffic_tab.get(k, 0)) * float(launches[i]) for i, k in enumerate(PHASES)) + float(traffic_tab.get("_other_per_solve", 0))
-            step_gbs = step_bytes / (elapsed / args.steps) / 1e9
-            step_ruler = {"counter_bytes_per_step": int(step_bytes), "achieved_GBps": round(step_gbs, 1), "frac_of_8TBps": round(step_gbs / HBM_PEAK_GBS, 4),
-                          "note": "sum over the kernel families of (counter bytes per launch x launches of the single-stream step) / ms_per_step of the timed steps"}
-        roofline = {"kernel": kname, "traffic": dom.get("counter_bytes_per_launch"),
-                    "traffic_source": None if not traffic_tab else "profiles/roofline_traffic.json (" + str(traffic_tab.get("_taken_on", "see its _note")) + "): TCC FETCH_SIZE (doubled on gfx950) + WRITE_SIZE of separate "
-                                      "rocprofv3 --pmc passes over `bench.py --windows-per-gpu 256` (tools/profile_pmc.sh + tools/make_roofline_traffic.py); NOT re-measured in this run "
-                                      "(a bench process cannot run under --pmc and time itself)",
-                    "hbm": hbm, "step": step_ruler,
-                    "measured_copy_ceiling_GBps": stream_gbs,
-                    "launches_per_step": float(launches[kdom]), "avg_launch_ms": dom["avg_launch_ms"], "algorithmic_bytes_per_launch": dom["model_bytes_per_launch"],
-                    "families": fam,
-                    "rulers": "model = SURVEY §8d bytes (charges every point edge a 144 B Hpl block the kernels recompute instead of moving: where model_over_counter > 1 "
-                              "the model ruler overstates traffic and the counter ruler is the honest one); counter = FETCH_SIZE (doubled on gfx950) + WRITE_SIZE of separate rocprofv3 --pmc passes",
-                    "phase_ms_single_stream_step": {k: round(float(phase[i]), 3) for i, k in enumerate(PHASES)},
-                    "solve_ms_single_stream_step": round(float(phase[5]), 3)}
-        if kname == "ba_schur":
-            # The ruler that BINDS this family is arithmetic (fp64 vector FMA; the blocks are 6x6 / 6x3 / 6x4, no matrix cores): it goes first.
-            fma_total = sum(schur_fmas(w, sum(st_["lm_trials"])) for w, st_ in zip(windows, stats))
-            tf = fma_total / (float(phase[kdom]) * 1e-3) / 1e12
-            roofline.update({"bound": "fp64_fma", "achieved": round(2.0 * tf, 2), "peak": round(2.0 * FP64_FMA_PEAK_T, 1), "unit": "TFLOP/s", "frac": round(tf / FP64_FMA_PEAK_T, 4),
-                             "fp64_fma": {"achieved_TFMA_per_s": round(tf, 2), "peak_TFMA_per_s": FP64_FMA_PEAK_T, "frac": round(tf / FP64_FMA_PEAK_T, 4),
-                                          "note": "useful FMAs of the family (bench.schur_fmas) over its HIP-event time; vector fp64 peak = 256 CU x 4 SIMD x 16 lanes/clk x 2.4 GHz"}})
-        else:
-            roofline.update({"bound": "hbm", "achieved": hbm["achieved"], "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": hbm["frac"]})
-        # ---- CPU baseline + matched-chi2 check on a bounded sample (N=1 only)
-        cpu = None; parity = None
-        if world == 1 and not args.no_cpu_baseline and args.cpu_sample > 0:
-            import oracle_py as O
-            O.lib()
-            ns = min(args.cpu_sample, wpg)
-            ids = sorted(set(int(round(i * (wpg - 1) / max(1, ns - 1))) for i in range(ns)))     # spread over the batch: every stream group is sampled
-            tc = time.perf_counter(); ores = [O.local_ba(windows[i]) for i in ids]; cpu_s = time.perf_counter() - tc
-            gres = [batch.download(i) for i in ids]
-            rel = max(abs(g.stats["chi2_final"] - o.stats["chi2_final"]) / max(o.stats["chi2_final"], 1e-300) for g, o in zip(gres, ores))
-            same = all(np.array_equal(g.pt_obs_outlier, o.pt_obs_outlier) and np.array_equal(g.ln_edge_outlier, o.ln_edge_outlier) and np.array_equal(g.line_removed, o.line_removed)
-                       for g, o in zip(gres, ores))
-            # the same port with one window per host thread (the reference's g2o is single-threaded per window; ctypes drops the GIL)
-            from concurrent.futures import ThreadPoolExecutor
-            nthr = max(1, min(os.cpu_count() or 1, 32, wpg))
-            tp = time.perf_counter()
-            with ThreadPoolExecutor(nthr) as ex:
-                list(ex.map(lambda i: O.local_ba(windows[i]), range(nthr)))
-            par_s = time.perf_counter() - tp
-            cpu = {"value": round(len(ids) / cpu_s, 4), "unit": "windows/s", "cores": 1, "kind": "port",
-                   "sample": f"{len(ids)} LBA-B windows (ids {ids}) through oracle/liblld_oracle.so, 1 thread, exact dense LDLT of the reduced system",
-                   "all_cores": {"value": round(nthr / par_s, 4), "cores": nthr, "sample": f"{nthr} windows, one per thread, concurrently"}}
-            pose_err = max(float(np.max(np.abs(g.cam_qt - o.cam_qt)) / np.max(np.abs(o.cam_qt))) for g, o in zip(gres, ores))
-            pt_err = np.concatenate([np.linalg.norm(g.pt_xyz - o.pt_xyz, axis=1) / np.linalg.norm(o.pt_xyz, axis=1) for g, o in zip(gres, ores)])
-            parity = {"windows_checked": len(ids), "window_ids": ids, "max_rel_chi2_final": float(rel), "outlier_sets_identical": bool(same),
-                      "max_rel_pose": pose_err, "median_rel_point": float(np.median(pt_err)), "points_within_1e-5": float(np.mean(pt_err <= 1e-5))}
+        roofline = cpu = parity = None
+        if args.full:
+            roofline = roofline_block(windows, stats, phase, launches, elapsed / args.steps, stream_gbs)
+            if world == 1 and not args.no_cpu_baseline and args.cpu_sample > 0:
+                cpu, parity = cpu_baseline_block(batch, windows, args.cpu_sample)
         result = {
-            "metric": METRIC, "value": round(value, 3), "unit": "windows/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
+            "metric": METRIC, "value": round(value, 3), "unit": "windows/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "full": args.full,
             "ms_per_step": round(1e3 * elapsed / args.steps, 3), "higher_is_better": True, "scaling": "strong" if args.strong else "weak", "vs_baseline": None,
             "dtype": "f64", "data": "synthetic",
             "config": {"workload": f"batched LocalBundleAdjustment, {'%d LBA-B windows in total' % sum(counts) if args.strong else '%d LBA-B windows per GPU' % wpg} "
@@ -897,7 +931,7 @@ def main():
             "dumped_outputs": dumped,
         }
     batch.close()
-    if world > 1 and not args.no_secondary:
+    if args.full and world > 1 and not args.no_secondary:
         # every rank takes part (collectives inside); rank 0 keeps the figures
         try:
             sec = sharded_secondary(ctx, dev, world, rank)
@@ -905,7 +939,7 @@ def main():
             sec = {"error": repr(ex)[:300]}
         if rank == 0:
             result["secondary"] = sec
-    if rank == 0 and world == 1 and not use_dist:
+    if args.full and rank == 0 and world == 1 and not use_dist:
         if not args.no_e2e:
             try:
                 result["e2e"] = e2e_block(windows, local_rank, lanes=max(1, args.e2e_lanes))

@@ -7,7 +7,7 @@ cd /tmp && export TMPDIR=/tmp
 for t in ${@:-1 8 32 64 256}; do
   export LLD_BA_SCHUR_TILE=$t
   for rep in 1 2; do
-  python3 $R/bench.py --windows-per-gpu 256 --steps 8 --warmup 2 --no-secondary --no-e2e --no-cpu-baseline --no-rccl-check 2>/dev/null | python3 -c "
+  python3 $R/bench.py --full --windows-per-gpu 256 --steps 8 --warmup 2 --no-secondary --no-e2e --no-cpu-baseline --no-rccl-check 2>/dev/null | python3 -c "
 import json,sys; d=json.loads(sys.stdin.readline()); print('tile %4d  %8.1f windows/s  %7.3f ms/solve  ba_schur %.3f ms' % ($t, d['value'], d['ms_per_step'], d['roofline']['phase_ms_single_stream_step']['ba_schur']))"
   done
   rocprofv3 --kernel-trace --pmc FETCH_SIZE -d $OUT/t$t -o f -- python3 $R/bench.py --steps 1 --warmup 1 --windows-per-gpu 256 --no-cpu-baseline --no-secondary --no-e2e --no-rccl-check --gen-workers 1 --groups 1 > $OUT/t$t.log 2>&1
