@@ -1260,6 +1260,112 @@ int  lld_kfdb_detect_loop_candidates(lld_kfdb* db, uint64_t query_id, const lld_
 /* DetectRelocalizationCandidates(F) with F->mnId = query_id, F->mBowVec = q. */
 int  lld_kfdb_detect_relocalization_candidates(lld_kfdb* db, uint64_t query_id, const lld_bow_vector* q, lld_kfdb_result* out);
 
+/* ================================================================== PnPsolver (src/PnPsolver.cc), Tracking::Relocalization's RANSAC
+ * A batch of independent PnPsolvers, one per relocalisation candidate, whose RANSAC state stays in HBM between iterate() calls.
+ * The interface is the reference's: the constructor (lld_pnp_problem), SetRansacParameters (lld_pnp_params), iterate(n, bNoMore,
+ * vbInliers, nInliers) (lld_pnp_batch_iterate + _download) and find() (lld_pnp_batch_find).  Restated literally:
+ *   PnPsolver(F, vpMapPointMatches) (:66-110): the caller skips NULL and isBad() points; correspondence i carries GetWorldPos()
+ *     (float xyz), mvKeysUn[kp].pt (float uv), mvLevelSigma2[octave] (float sigma2) and kp = mvKeyPointIndices[i]; fu, fv, uc, vc
+ *     = F.fx, fy, cx, cy.  adapters/lld_pnp_adapter.cc does this on live objects.
+ *   SetRansacParameters (:121-157), computed on the host by lld_pnp_batch_create: nMinInliers = N*epsilon (a float product,
+ *     truncated), raised to minInliers and to minSet; epsilon raised to (float)nMinInliers/N; nIterations = 1 when nMinInliers == N,
+ *     else ceil(log(1-p)/log(1-pow(epsilon,3))) (the exponent is 3, not minSet); mRansacMaxIts = max(1, min(nIterations,
+ *     maxIterations)); mvMaxError[i] = sigma2[i]*th2 in float.  Relocalization's values (Tracking.cc:1882) are the defaults.
+ *   iterate (:165-258): outputs reset; N < mRansacMinInliers -> bNoMore, no draws, no pose.  The loop runs while mnIterations <
+ *     mRansacMaxIts || nCurrentIterations < n (a call after the budget is spent still runs n iterations).  Each iteration draws
+ *     4 indices (RandomInt over the remaining vAvailableIndices, the back swapped into the taken place), runs EPnP and
+ *     CheckInliers; a hypothesis with mnInliersi >= mRansacMinInliers is eligible; an eligible one with a strictly greater count
+ *     than mnBestInliers becomes the best (mBestTcw = R|t converted to float); every eligible one calls Refine on the best set,
+ *     and a Refine that succeeds returns the refined pose at once.  When the budget is spent: bNoMore, and the best hypothesis
+ *     (not refined) when mnBestInliers >= mRansacMinInliers.  vbInliers has n_keypoints entries, set at mvKeyPointIndices.
+ *   Refine (:260-306): EPnP on every best inlier in ascending index order, CheckInliers; success only when the count is strictly
+ *     greater than mRansacMinInliers.  A best set of exactly 4 (min_inliers <= 4 with N <= 9) takes the minimal-set basis below.
+ *   CheckInliers (:308-340): Xc, Yc, invZc float, ue / ve double, distX, distY, error2 float; inlier when error2 < mvMaxError[i].
+ *     The kernels are compiled without FMA contraction, so every in/out decision is the reference's expression.
+ *   EPnP compute_pose (:477-525) in fp64: PCA control points (:375-409), barycentric coordinates (:411-434), M, L_6x10 and rho,
+ *     the three beta approximations (:667-758) each with 5 Gauss-Newton steps through the reference's own Householder qr_solve
+ *     (:840-952; where it returns early without writing X, X keeps its previous value, 0 at the start), compute_R_and_t with
+ *     solve_for_sign on the first point's z only (:636-665), estimate_R_and_t with its determinant flip of R's third row
+ *     (:569-627), and the lowest reprojection error with ties going to the lower index (:518-520).
+ * DEVIATION 1 (the sample stream): DUtils::Random::RandomInt (Thirdparty/DBoW2/DUtils/Random.cpp:47-50) draws from the
+ *   process-global rand(), which the stereo path never seeds and the LoopClosing thread shares.  Here every solver has its own
+ *   stream: glibc's rand() after srand(seed) (the TYPE_3 additive generator: r[i] = r[i-3] + r[i-31] mod 2^32, output r >> 1,
+ *   310 warm-up values discarded; seed 0 acts as 1), turned into indices by RandomInt's int(rand()/(RAND_MAX+1.0)*d).  With one
+ *   stream each the solvers are independent, so one batched round (iterate(5) on every live candidate) gives exactly what the
+ *   reference's sequential round robin (Tracking.cc:1894-1987) gives for every candidate it reaches.
+ * DEVIATION 2 (numerics left to OpenCV): with 4 correspondences M^T M has an exactly 4-dimensional null space and the basis
+ *   cvSVD returns (:491) is an artefact of its Jacobi sweeps, which the beta approximations (and so the result) depend on.  For a
+ *   minimal set the basis is columns 9..12 of Q of a Householder QR of M^T (12 x 8), as ut rows 11, 10, 9, 8.  Refine (N > 4)
+ *   takes the eigenvectors of the 4 smallest |eigenvalues| of M^T M from a cyclic Jacobi (at most 40 sweeps, stopping when the
+ *   squared off-diagonal sum is <= 1e-36 of the squared diagonal sum); the 3x3 PCA uses the same routine, and the SVD of ABt is
+ *   V from the Jacobi of ABt^T ABt with u_k = ABt v_k / s_k (a cut third column completed as u0 x u1).  Every eigenvector's sign
+ *   is canonical (its first largest-magnitude component positive).  cvInvert(CV_SVD) and cvSolve(CV_SVD) become (A^T A)^+ A^T
+ *   with eigenvalues of A^T A at or below 1e-14 of the largest dropped (singular values below about 1e-7 of the largest); this
+ *   cutoff is this library's choice, not OpenCV's.  Non-finite values follow IEEE with no special case (a NaN pose has 0 inliers).
+ * Limits: LLD_ERR_INVALID / LLD_ERR_UNSUPPORTED with nothing allocated: nulls; n < 1 or more than LLD_PNP_MAX_SOLVERS solvers;
+ *   more than LLD_PNP_MAX_CORRESPONDENCES correspondences or LLD_PNP_MAX_KEYPOINTS keypoints; a kp_index out of range or repeated;
+ *   fx or fy not > 0; min_set other than 4 (UNSUPPORTED); max_iterations outside 1..LLD_PNP_MAX_ITERATIONS, probability outside
+ *   (0, 1), epsilon outside (0, 1], th2 not > 0.  lld_pnp_batch_iterate: n_iterations < 1 (INVALID) or above
+ *   LLD_PNP_MAX_ITERATIONS (UNSUPPORTED).  A handle is driven by one host thread at a time, on its context's stream. */
+#define LLD_PNP_MAX_CORRESPONDENCES 8192  /* per solver                                        */
+#define LLD_PNP_MAX_KEYPOINTS 8192        /* per frame (length of vbInliers)                   */
+#define LLD_PNP_MAX_SOLVERS 256           /* per batch                                         */
+#define LLD_PNP_MAX_ITERATIONS 65536      /* mRansacMaxIts and iterate()'s n                   */
+typedef struct {
+  double probability;                    /* 0.99                                                  */
+  int32_t min_inliers;                   /* 10                                                    */
+  int32_t max_iterations;                /* 300                                                   */
+  int32_t min_set;                       /* 4 (the only one supported)                            */
+  float epsilon;                         /* 0.5                                                   */
+  float th2;                             /* 5.991                                                 */
+} lld_pnp_params;
+void lld_pnp_params_default(lld_pnp_params* p);    /* SetRansacParameters(0.99, 10, 300, 4, 0.5, 5.991) (Tracking.cc:1882) */
+typedef struct {
+  int32_t n;                             /* correspondences                                       */
+  const float* xyz;                      /* [3n] GetWorldPos()                                    */
+  const float* uv;                       /* [2n] mvKeysUn[kp].pt                                  */
+  const float* sigma2;                   /* [n]  mvLevelSigma2[octave]                            */
+  const int32_t* kp_index;               /* [n]  mvKeyPointIndices: distinct, in [0, n_keypoints) */
+  int32_t n_keypoints;                   /* vpMapPointMatches.size()                              */
+  float fx, fy, cx, cy;
+  uint32_t seed;                         /* srand(seed) of this solver's stream (DEVIATION 1)     */
+} lld_pnp_problem;
+typedef struct {
+  float Tcw[12];                         /* 3x4 row-major [R | t], float as the reference's cv::Mat */
+  int32_t has_pose;                      /* iterate() returned a non-empty Mat                    */
+  int32_t n_inliers;                     /* nInliers                                              */
+  int32_t no_more;                       /* bNoMore                                               */
+  int32_t iterations;                    /* mnIterations                                          */
+  int32_t best_inliers;                  /* mnBestInliers                                         */
+  int32_t n_keypoints;                   /* out: entries written to inlier                        */
+  uint8_t* inlier;                       /* [n_keypoints] vbInliers, caller-allocated, or NULL    */
+} lld_pnp_result;
+typedef struct {                          /* diagnostic: one hypothesis of the last iterate call   */
+  int32_t n_inliers;                     /* mnInliersi                                            */
+  int32_t record;                        /* 1: a new best                                         */
+  int32_t refine;                        /* -1 not eligible; else the Refine of its best-so-far set: 0 failed, 1 succeeded */
+  int32_t refined_inliers;               /* that Refine's count                                   */
+  double R[9], t[3];                     /* mRi, mti                                              */
+} lld_pnp_hypothesis;
+typedef struct lld_pnp_batch lld_pnp_batch;
+/* n PnPsolvers with SetRansacParameters(params): uploads one slab of all correspondences and the RANSAC constants. */
+int  lld_pnp_batch_create(lld_ctx* ctx, int32_t n, const lld_pnp_problem* problems, const lld_pnp_params* params, lld_pnp_batch** out);
+/* iterate(n_iterations) on every solver with active[s] != 0 (active NULL: all), on the device, with no host trip between the
+ * kernels; queued on the context's stream.  Inactive solvers keep their state and last results. */
+int  lld_pnp_batch_iterate(lld_pnp_batch* b, int32_t n_iterations, const uint8_t* active);
+/* find() (:159-163) on every active solver: iterate(mRansacMaxIts) of each, continuing its state like the reference's find(). */
+int  lld_pnp_batch_find(lld_pnp_batch* b, const uint8_t* active);
+/* The last iterate's outputs of every solver (outs[n]); waits for the stream. */
+int  lld_pnp_batch_download(lld_pnp_batch* b, lld_pnp_result* outs);
+/* Diagnostic (tests): the hypotheses drawn by the last iterate call of `solver`.  n_window: hypotheses evaluated (the window
+ * max(n, budget - mnIterations), speculative ones past a successful Refine included); n_run: the iterations iterate() made.
+ * The first min(capacity, n_window) are written.  An inactive solver reports 0 / 0. */
+int  lld_pnp_batch_hypotheses(lld_pnp_batch* b, int32_t solver, int32_t capacity, lld_pnp_hypothesis* out, int32_t* n_window,
+                              int32_t* n_run);
+void lld_pnp_batch_destroy(lld_pnp_batch* b);
+/* find() (:159-163) on one freshly constructed solver: create, lld_pnp_batch_find, download, destroy. */
+int  lld_pnp_find(lld_ctx* ctx, const lld_pnp_problem* problem, const lld_pnp_params* params, lld_pnp_result* out);
+
 #if defined(__GNUC__)
 #pragma GCC visibility pop
 #endif

@@ -614,5 +614,103 @@ class KeyFrameDatabase {
   std::vector<float> acc_;
 };
 
+// PnPsolver (src/PnPsolver.cc) on the device: one solver's correspondences as PnPsolver(F, vpMapPointMatches) gathers them
+// (NULL and isBad() points skipped by the caller).  Rules and deviations: include/lld_amd.h.
+struct PnPProblem {
+  std::vector<float> xyz;                // [3n] GetWorldPos()
+  std::vector<float> uv;                 // [2n] mvKeysUn[i].pt
+  std::vector<float> sigma2;             // [n]  mvLevelSigma2[octave]
+  std::vector<int32_t> kp_index;         // [n]  mvKeyPointIndices
+  int32_t n_keypoints = 0;               // vpMapPointMatches.size()
+  float fx = 0, fy = 0, cx = 0, cy = 0;
+  uint32_t seed = 0;                     // this solver's rand() stream
+  lld_pnp_problem c() const {
+    lld_pnp_problem p;
+    p.n = (int32_t)kp_index.size();
+    p.xyz = xyz.data(); p.uv = uv.data(); p.sigma2 = sigma2.data(); p.kp_index = kp_index.data();
+    p.n_keypoints = n_keypoints; p.fx = fx; p.fy = fy; p.cx = cx; p.cy = cy; p.seed = seed;
+    return p;
+  }
+};
+
+// iterate()'s outputs: an empty Tcw (has_pose false) where the reference returns an empty cv::Mat.
+struct PnPOutput {
+  bool has_pose = false;
+  float Tcw[12] = {};                    // 3x4 row-major [R | t]
+  bool bNoMore = false;
+  std::vector<bool> vbInliers;
+  int nInliers = 0;
+  int iterations = 0;                    // mnIterations after the call
+};
+
+// A batch of PnPsolvers resident in HBM, one per relocalisation candidate: iterate(n, active) runs iterate(n) on every active
+// solver in one device-resident sequence.
+class PnPsolverBatch {
+ public:
+  PnPsolverBatch(const Context& ctx, const std::vector<PnPProblem>& problems) : PnPsolverBatch(ctx, problems, defaults()) {}
+  PnPsolverBatch(const Context& ctx, const std::vector<PnPProblem>& problems, const lld_pnp_params& params) {
+    std::vector<lld_pnp_problem> c;
+    for (const PnPProblem& p : problems) { c.push_back(p.c()); n_kp_.push_back(p.n_keypoints); }
+    check(lld_pnp_batch_create(ctx.get(), (int32_t)c.size(), c.data(), &params, &h_), "lld_pnp_batch_create");
+  }
+  ~PnPsolverBatch() { lld_pnp_batch_destroy(h_); }
+  PnPsolverBatch(const PnPsolverBatch&) = delete;
+  PnPsolverBatch& operator=(const PnPsolverBatch&) = delete;
+  // SetRansacParameters(0.99, 10, 300, 4, 0.5, 5.991): Tracking::Relocalization's values (Tracking.cc:1882)
+  static lld_pnp_params defaults() { lld_pnp_params p; lld_pnp_params_default(&p); return p; }
+  std::vector<PnPOutput> iterate(int nIterations, const std::vector<uint8_t>& active = {}) {
+    check(lld_pnp_batch_iterate(h_, nIterations, active.empty() ? nullptr : active.data()), "lld_pnp_batch_iterate");
+    return download();
+  }
+  // find() on every active solver: iterate(mRansacMaxIts) of each, continuing its state
+  std::vector<PnPOutput> find(const std::vector<uint8_t>& active = {}) {
+    check(lld_pnp_batch_find(h_, active.empty() ? nullptr : active.data()), "lld_pnp_batch_find");
+    return download();
+  }
+  std::vector<PnPOutput> download() {
+    const size_t n = n_kp_.size();
+    std::vector<lld_pnp_result> r(n);
+    std::vector<std::vector<uint8_t>> fl(n);
+    for (size_t i = 0; i < n; ++i) { fl[i].assign(n_kp_[i] > 0 ? n_kp_[i] : 1, 0); r[i].inlier = fl[i].data(); }
+    check(lld_pnp_batch_download(h_, r.data()), "lld_pnp_batch_download");
+    std::vector<PnPOutput> out(n);
+    for (size_t i = 0; i < n; ++i) {
+      out[i].has_pose = r[i].has_pose != 0;
+      for (int q = 0; q < 12; ++q) out[i].Tcw[q] = r[i].Tcw[q];
+      out[i].bNoMore = r[i].no_more != 0;
+      out[i].vbInliers.assign(fl[i].begin(), fl[i].begin() + n_kp_[i]);
+      out[i].nInliers = r[i].n_inliers;
+      out[i].iterations = r[i].iterations;
+    }
+    return out;
+  }
+  lld_pnp_batch* get() const { return h_; }
+ private:
+  lld_pnp_batch* h_ = nullptr;
+  std::vector<int32_t> n_kp_;
+};
+
+// One PnPsolver: iterate(nIterations, bNoMore, vbInliers, nInliers) and find(vbInliers, nInliers) with the reference's names.
+class PnPsolver {
+ public:
+  PnPsolver(const Context& ctx, const PnPProblem& p, const lld_pnp_params& params = PnPsolverBatch::defaults())
+      : b_(ctx, std::vector<PnPProblem>{p}, params) {}
+  bool iterate(int nIterations, bool& bNoMore, std::vector<bool>& vbInliers, int& nInliers, float Tcw[12]) {
+    return take(b_.iterate(nIterations)[0], bNoMore, vbInliers, nInliers, Tcw);
+  }
+  // find() (:159-163) = iterate(mRansacMaxIts), continuing this solver's state
+  bool find(std::vector<bool>& vbInliers, int& nInliers, float Tcw[12]) {
+    bool bNoMore;
+    return take(b_.find()[0], bNoMore, vbInliers, nInliers, Tcw);
+  }
+ private:
+  static bool take(const PnPOutput& o, bool& bNoMore, std::vector<bool>& vbInliers, int& nInliers, float Tcw[12]) {
+    bNoMore = o.bNoMore; vbInliers = o.has_pose ? o.vbInliers : std::vector<bool>(); nInliers = o.nInliers;
+    for (int q = 0; q < 12; ++q) Tcw[q] = o.Tcw[q];
+    return o.has_pose;
+  }
+  PnPsolverBatch b_;
+};
+
 }  // namespace lld_amd
 #endif

@@ -158,6 +158,27 @@ class Sim3Result(C.Structure):
                 ("n_bad_first", C.c_int32), ("lm_iterations", C.c_int32 * 2), ("lm_trials", C.c_int32 * 2), ("chi2", C.c_double)]
 
 
+class PnPParams(C.Structure):
+    _fields_ = [("probability", C.c_double), ("min_inliers", C.c_int32), ("max_iterations", C.c_int32), ("min_set", C.c_int32),
+                ("epsilon", C.c_float), ("th2", C.c_float)]
+
+
+class PnPProblem(C.Structure):
+    _fields_ = [("n", C.c_int32), ("xyz", c_float_p), ("uv", c_float_p), ("sigma2", c_float_p), ("kp_index", c_int32_p),
+                ("n_keypoints", C.c_int32), ("fx", C.c_float), ("fy", C.c_float), ("cx", C.c_float), ("cy", C.c_float),
+                ("seed", C.c_uint32)]
+
+
+class PnPResult(C.Structure):
+    _fields_ = [("Tcw", C.c_float * 12), ("has_pose", C.c_int32), ("n_inliers", C.c_int32), ("no_more", C.c_int32),
+                ("iterations", C.c_int32), ("best_inliers", C.c_int32), ("n_keypoints", C.c_int32), ("inlier", c_uint8_p)]
+
+
+class PnPHypothesis(C.Structure):
+    _fields_ = [("n_inliers", C.c_int32), ("record", C.c_int32), ("refine", C.c_int32), ("refined_inliers", C.c_int32),
+                ("R", C.c_double * 9), ("t", C.c_double * 3)]
+
+
 class PoseGraph(C.Structure):
     _fields_ = [("n_vertices", C.c_int32), ("n_edges", C.c_int32), ("sim3", c_double_p), ("fixed", c_uint8_p), ("edge_i", c_int32_p),
                 ("edge_j", c_int32_p), ("edge_sji", c_double_p)]
@@ -198,6 +219,8 @@ PRODUCT_SYMBOLS = [
     "lld_bow_vocab_read_text", "lld_bow_vocab_create", "lld_bow_vocab_destroy", "lld_bow_vocab_info_get", "lld_bow_transform", "lld_bow_score",
     "lld_kfdb_create", "lld_kfdb_destroy", "lld_kfdb_add", "lld_kfdb_erase", "lld_kfdb_clear", "lld_kfdb_set_covisibles",
     "lld_kfdb_detect_loop_candidates", "lld_kfdb_detect_relocalization_candidates",
+    "lld_pnp_params_default", "lld_pnp_batch_create", "lld_pnp_batch_iterate", "lld_pnp_batch_download", "lld_pnp_batch_hypotheses",
+    "lld_pnp_batch_destroy", "lld_pnp_find", "lld_pnp_batch_find",
 ]
 
 
@@ -297,6 +320,17 @@ class Lib:
             f("match_hamming256_batch_dev").restype = C.c_int
             f("match_l2f32_batch_dev").argtypes = [vp, C.c_int, vp, C.c_int, vp, C.c_int, C.c_int, vp, vp, vp, vp]
             f("match_l2f32_batch_dev").restype = C.c_int
+            f("pnp_params_default").argtypes = [C.POINTER(PnPParams)]; f("pnp_params_default").restype = None
+            f("pnp_batch_create").argtypes = [vp, C.c_int32, C.POINTER(PnPProblem), C.POINTER(PnPParams), C.POINTER(vp)]
+            f("pnp_batch_create").restype = C.c_int
+            f("pnp_batch_iterate").argtypes = [vp, C.c_int32, c_uint8_p]; f("pnp_batch_iterate").restype = C.c_int
+            f("pnp_batch_find").argtypes = [vp, c_uint8_p]; f("pnp_batch_find").restype = C.c_int
+            f("pnp_batch_download").argtypes = [vp, C.POINTER(PnPResult)]; f("pnp_batch_download").restype = C.c_int
+            f("pnp_batch_hypotheses").argtypes = [vp, C.c_int32, C.c_int32, C.POINTER(PnPHypothesis), c_int32_p, c_int32_p]
+            f("pnp_batch_hypotheses").restype = C.c_int
+            f("pnp_batch_destroy").argtypes = [vp]; f("pnp_batch_destroy").restype = None
+            f("pnp_find").argtypes = [vp, C.POINTER(PnPProblem), C.POINTER(PnPParams), C.POINTER(PnPResult)]
+            f("pnp_find").restype = C.c_int
 
 
 _PRODUCT = None
