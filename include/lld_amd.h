@@ -1366,6 +1366,124 @@ void lld_pnp_batch_destroy(lld_pnp_batch* b);
 /* find() (:159-163) on one freshly constructed solver: create, lld_pnp_batch_find, download, destroy. */
 int  lld_pnp_find(lld_ctx* ctx, const lld_pnp_problem* problem, const lld_pnp_params* params, lld_pnp_result* out);
 
+/* ================================================================== Sim3Solver (src/Sim3Solver.cc), LoopClosing::ComputeSim3's RANSAC
+ * A batch of independent Sim3Solvers, one per loop candidate, whose RANSAC state stays in HBM between iterate() calls.  The prefix
+ * is lld_sim3solver_ (lld_sim3_ is OptimizeSim3 above).  The interface is the reference's: the constructor (lld_sim3solver_problem),
+ * SetRansacParameters (lld_sim3solver_params), iterate(n, bNoMore, vbInliers, nInliers) (lld_sim3solver_batch_iterate + _download),
+ * find() (lld_sim3solver_batch_find) and GetEstimatedRotation / Translation / Scale (the best hypothesis, in the result).
+ * Restated literally:
+ *   Sim3Solver(pKF1, pKF2, vpMatched12, bFixScale) (:37-112): the caller walks vpMatched12 (length mN1 = n1) and skips an entry
+ *     whose vpMatched12[i1] or pKF1->GetMapPointMatches()[i1] is NULL, either point isBad(), or either GetIndexInKeyFrame < 0;
+ *     correspondence i carries both GetWorldPos() (float xyz), mvLevelSigma2[kp.octave] of both keypoints and index1 = i1.
+ *     adapters/lld_sim3_adapter.cc does this on live objects.  lld_sim3solver_batch_create then computes, on the host:
+ *     mvX3Dc1/2 = Rcw*Xw + tcw (float), mvP1im1 / mvP2im2 by FromCameraToImage (float: invz = 1/z, x = X*invz, u = fx*x + cx),
+ *     mvnMaxError1/2 = 9.210*sigma2 in double TRUNCATED to an integer (std::vector<size_t>, include/Sim3Solver.h:78-79: sigma2
+ *     1 -> 9, 1.44 -> 13, 2.0736 -> 19, 2.986 -> 27), compared as err < (float)maxErr.
+ *   SetRansacParameters (:114-138): epsilon = (float)minInliers/N; nIterations = 1 when minInliers == N, else
+ *     ceil(log(1-p)/log(1-pow(epsilon,3))); mRansacMaxIts = max(1, min(nIterations, maxIterations)).  LoopClosing's values
+ *     (0.99, 20, 300, LoopClosing.cc:277) are the defaults here, not the header's minInliers = 6.
+ *   iterate (:140-207): outputs reset (vbInliers: n1 entries, false); N < mRansacMinInliers -> bNoMore, no draws, no pose.  The
+ *     loop runs while mnIterations < mRansacMaxIts AND nCurrentIterations < n (PnPsolver has OR: here a call after the budget is
+ *     spent draws nothing and returns bNoMore).  Each iteration draws 3 indices (RandomInt over a fresh copy of mvAllIndices, the
+ *     back swapped into the taken place), runs ComputeSim3 and CheckInliers.  A hypothesis with mnInliersi >= mnBestInliers
+ *     becomes the best (ties replace it; the first one becomes the best even with 0 inliers); a best with mnInliersi >
+ *     mRansacMinInliers returns T12 at once, before the bNoMore test (a success on the budget's last iteration has bNoMore false),
+ *     with vbInliers set at index1 of its inliers.  Otherwise bNoMore = mnIterations >= mRansacMaxIts and no pose.
+ *   find() (:209-213) is iterate(mRansacMaxIts), continuing the solver's state.
+ *   ComputeSim3 (:226-337), Horn's closed form on the 3 sampled points in float: centroids O1, O2 and Pr = P - O; M = Pr2*Pr1^T;
+ *     the 10 entries of N from M's floats (float sums, stored in double, then into a float 4x4); the eigenvector q of N's largest
+ *     eigenvalue; ang = atan2(||q.xyz||, q.w); vec = 2*ang*q.xyz/||q.xyz||; R12 = Rodrigues(vec); P3 = R12*Pr2; s = (float)(nom/den)
+ *     with nom = Pr1.dot(P3) and den = sum of P3's squares (floats) both in double, or 1 under fix_scale; t = O1 - (s*R)*O2;
+ *     T12 = [sR | t]; T21 = [(1/s)R^T | -((1/s)R^T) t].
+ *   CheckInliers (:340-364): X3Dc2 through T12 into K1 and X3Dc1 through T21 into K2 (Project: P3Dc = R*X + t, then as
+ *     FromCameraToImage); err = dist.dot(dist) as float; an inlier when both errors are below their thresholds.  No depth test.
+ *   Non-finite values follow IEEE with no special case: a sample whose rotation is exactly the identity has ||q.xyz|| = 0, so vec,
+ *   R, T12 and T21 are NaN and the hypothesis has 0 inliers (and becomes the best if it is the first).
+ * DEVIATION 1 (the sample stream): as lld_pnp's DEVIATION 1.  RandomInt draws from the process-global rand(), which the
+ *   LoopClosing thread shares with Tracking.  Here every solver owns a glibc TYPE_3 rand() stream after srand(seed), so one batched
+ *   round (iterate(5) on every live candidate, LoopClosing.cc:289-342) gives exactly what the sequential round robin gives for
+ *   every candidate it reaches.
+ * DEVIATION 2 (numerics left to OpenCV): these choices are this library's, restated identically in tests/sim3solver_ref.py.
+ *   Products and dot products of float matrices (Rcw*X, Pr2*Pr1^T, R*Pr2, (s*R)*O2, sRinv*t, Project's R*X, Mat::dot, cv::norm):
+ *   the float products summed in double in index order, starting from the first, rounded to float once, then the float + t.
+ *   Centroids: the float sum of the three columns in order, divided by 3.0f.  s*R: the float product; (1/s)*R^T: the double
+ *   quotient times the widened float, rounded.  vec: alpha = (2*ang)/||q.xyz|| in double, vec_i = (float)(q_i*alpha).
+ *   cv::eigen(N): lld_pnp's cyclic Jacobi in fp64 on the widened N (same sweeps and tolerance); the largest eigenvalue, the lowest
+ *   index on a tie; canonical sign (the first largest-magnitude component positive); rounded to float.  cv::Rodrigues: theta =
+ *   ||vec|| in double; theta < DBL_EPSILON gives the identity; else r = vec/theta and R_ij = (cos*d_ij + (1-cos)*(r_i*r_j)) +
+ *   sin*[r]x_ij in double, rounded to float.  Device atan2 / sin / cos may differ from glibc by an ulp of double; R, t and s
+ *   hold to the restatement within 1 float ulp.  The kernels are compiled without FMA contraction.
+ * Limits: LLD_ERR_INVALID / LLD_ERR_UNSUPPORTED with nothing allocated: nulls; n < 1 or more than LLD_SIM3S_MAX_SOLVERS solvers;
+ *   more than LLD_SIM3S_MAX_CORRESPONDENCES correspondences or LLD_SIM3S_MAX_KEYPOINTS keypoints (n1); an index1 out of range or
+ *   repeated; a sigma2 that is negative, not finite or 9.210*sigma2 >= 2^32; fx or fy of either keyframe not > 0; min_inliers < 3
+ *   (UNSUPPORTED: a draw needs 3 correspondences); max_iterations outside 1..LLD_SIM3S_MAX_ITERATIONS, probability outside (0, 1).
+ *   lld_sim3solver_batch_iterate: n_iterations < 1 (INVALID) or above LLD_SIM3S_MAX_ITERATIONS (UNSUPPORTED).  A handle is driven
+ *   by one host thread at a time, on its context's stream. */
+#define LLD_SIM3S_MAX_CORRESPONDENCES 8192  /* per solver                                      */
+#define LLD_SIM3S_MAX_KEYPOINTS 8192        /* mN1 (length of vbInliers)                       */
+#define LLD_SIM3S_MAX_SOLVERS 256           /* per batch                                       */
+#define LLD_SIM3S_MAX_ITERATIONS 65536      /* maxIterations and iterate()'s n                 */
+typedef struct {
+  double probability;                    /* 0.99                                                  */
+  int32_t min_inliers;                   /* 20                                                    */
+  int32_t max_iterations;                /* 300                                                   */
+} lld_sim3solver_params;
+void lld_sim3solver_params_default(lld_sim3solver_params* p);   /* SetRansacParameters(0.99, 20, 300) (LoopClosing.cc:277) */
+typedef struct {
+  int32_t n;                             /* correspondences                                       */
+  const float* xyz1;                     /* [3n] pMP1->GetWorldPos()                              */
+  const float* xyz2;                     /* [3n] pMP2->GetWorldPos()                              */
+  const float* sigma2_1;                 /* [n]  pKF1->mvLevelSigma2[kp1.octave]                  */
+  const float* sigma2_2;                 /* [n]  pKF2->mvLevelSigma2[kp2.octave]                  */
+  const int32_t* index1;                 /* [n]  mvnIndices1: distinct, in [0, n1)                */
+  int32_t n1;                            /* mN1 = vpMatched12.size()                              */
+  float Rcw1[9], tcw1[3];                /* pKF1->GetRotation() (row-major), GetTranslation()     */
+  float Rcw2[9], tcw2[3];
+  float fx1, fy1, cx1, cy1;              /* pKF1->mK                                              */
+  float fx2, fy2, cx2, cy2;              /* pKF2->mK                                              */
+  int32_t fix_scale;                     /* bFixScale                                             */
+  uint32_t seed;                         /* srand(seed) of this solver's stream (DEVIATION 1)     */
+} lld_sim3solver_problem;
+typedef struct {
+  float T12[12];                         /* 3x4 row-major [sR | t] iterate() returned, or zeros   */
+  float R[9], t[3], s;                   /* GetEstimatedRotation / Translation / Scale (the best; zeros before any hypothesis) */
+  int32_t has_pose;                      /* iterate() returned a non-empty Mat                    */
+  int32_t n_inliers;                     /* nInliers                                              */
+  int32_t no_more;                       /* bNoMore                                               */
+  int32_t iterations;                    /* mnIterations                                          */
+  int32_t best_inliers;                  /* mnBestInliers                                         */
+  int32_t n1;                            /* out: entries written to inlier                        */
+  uint8_t* inlier;                       /* [n1] vbInliers, caller-allocated, or NULL             */
+} lld_sim3solver_result;
+typedef struct {                          /* diagnostic: one hypothesis of the last iterate call   */
+  int32_t n_inliers;                     /* mnInliersi                                            */
+  int32_t record;                        /* 1: it became the best (>= mnBestInliers)              */
+  int32_t idx[3];                        /* the sampled correspondences                           */
+  float s;                               /* ms12i                                                 */
+  float R[9], t[3];                      /* mR12i, mt12i                                          */
+  float T12[12];                         /* mT12i rows 0..2                                       */
+} lld_sim3solver_hypothesis;
+typedef struct lld_sim3solver_batch lld_sim3solver_batch;
+/* n Sim3Solvers with SetRansacParameters(params): the constructor's camera points, projections and thresholds, then one upload. */
+int  lld_sim3solver_batch_create(lld_ctx* ctx, int32_t n, const lld_sim3solver_problem* problems, const lld_sim3solver_params* params,
+                                 lld_sim3solver_batch** out);
+/* iterate(n_iterations) on every solver with active[s] != 0 (active NULL: all), on the device, with no host trip between the
+ * kernels; queued on the context's stream.  Inactive solvers keep their state and last results. */
+int  lld_sim3solver_batch_iterate(lld_sim3solver_batch* b, int32_t n_iterations, const uint8_t* active);
+/* find() (:209-213) on every active solver: iterate(mRansacMaxIts) of each, continuing its state like the reference's find(). */
+int  lld_sim3solver_batch_find(lld_sim3solver_batch* b, const uint8_t* active);
+/* The last iterate's outputs of every solver (outs[n]); waits for the stream. */
+int  lld_sim3solver_batch_download(lld_sim3solver_batch* b, lld_sim3solver_result* outs);
+/* Diagnostic (tests): the hypotheses drawn by the last iterate call of `solver`.  n_window: hypotheses evaluated (min(n,
+ * mRansacMaxIts - mnIterations), speculative ones past a returned pose included); n_run: the iterations iterate() made.  The
+ * first min(capacity, n_window) are written.  An inactive solver reports 0 / 0. */
+int  lld_sim3solver_batch_hypotheses(lld_sim3solver_batch* b, int32_t solver, int32_t capacity, lld_sim3solver_hypothesis* out,
+                                     int32_t* n_window, int32_t* n_run);
+void lld_sim3solver_batch_destroy(lld_sim3solver_batch* b);
+/* find() on one freshly constructed solver: create, lld_sim3solver_batch_find, download, destroy. */
+int  lld_sim3solver_find(lld_ctx* ctx, const lld_sim3solver_problem* problem, const lld_sim3solver_params* params,
+                         lld_sim3solver_result* out);
+
 #if defined(__GNUC__)
 #pragma GCC visibility pop
 #endif

@@ -712,5 +712,121 @@ class PnPsolver {
   PnPsolverBatch b_;
 };
 
+// Sim3Solver (src/Sim3Solver.cc) on the device: one solver's correspondences as Sim3Solver(pKF1, pKF2, vpMatched12, bFixScale)
+// gathers them (the caller skips what the constructor skips).  Rules and deviations: include/lld_amd.h.
+struct Sim3Problem {
+  std::vector<float> xyz1, xyz2;         // [3n] pMP1 / pMP2->GetWorldPos()
+  std::vector<float> sigma2_1, sigma2_2; // [n]  mvLevelSigma2[octave] of both keypoints
+  std::vector<int32_t> index1;           // [n]  mvnIndices1
+  int32_t n1 = 0;                        // vpMatched12.size()
+  float Rcw1[9] = {}, tcw1[3] = {}, Rcw2[9] = {}, tcw2[3] = {};
+  float fx1 = 0, fy1 = 0, cx1 = 0, cy1 = 0, fx2 = 0, fy2 = 0, cx2 = 0, cy2 = 0;
+  bool bFixScale = true;
+  uint32_t seed = 0;                     // this solver's rand() stream
+  lld_sim3solver_problem c() const {
+    lld_sim3solver_problem p;
+    p.n = (int32_t)index1.size();
+    p.xyz1 = xyz1.data(); p.xyz2 = xyz2.data(); p.sigma2_1 = sigma2_1.data(); p.sigma2_2 = sigma2_2.data(); p.index1 = index1.data();
+    p.n1 = n1;
+    for (int q = 0; q < 9; ++q) { p.Rcw1[q] = Rcw1[q]; p.Rcw2[q] = Rcw2[q]; }
+    for (int q = 0; q < 3; ++q) { p.tcw1[q] = tcw1[q]; p.tcw2[q] = tcw2[q]; }
+    p.fx1 = fx1; p.fy1 = fy1; p.cx1 = cx1; p.cy1 = cy1; p.fx2 = fx2; p.fy2 = fy2; p.cx2 = cx2; p.cy2 = cy2;
+    p.fix_scale = bFixScale ? 1 : 0; p.seed = seed;
+    return p;
+  }
+};
+
+// iterate()'s outputs: an empty T12 (has_pose false) where the reference returns an empty cv::Mat; R / t / s are the best
+// hypothesis (GetEstimatedRotation / Translation / Scale).
+struct Sim3Output {
+  bool has_pose = false;
+  float T12[12] = {};                    // 3x4 row-major [sR | t]
+  bool bNoMore = false;
+  std::vector<bool> vbInliers;
+  int nInliers = 0;
+  int iterations = 0;                    // mnIterations after the call
+  float R[9] = {}, t[3] = {}, s = 0;
+};
+
+// A batch of Sim3Solvers resident in HBM, one per loop candidate: iterate(n, active) runs iterate(n) on every active solver in
+// one device-resident sequence.
+class Sim3SolverBatch {
+ public:
+  Sim3SolverBatch(const Context& ctx, const std::vector<Sim3Problem>& problems) : Sim3SolverBatch(ctx, problems, defaults()) {}
+  Sim3SolverBatch(const Context& ctx, const std::vector<Sim3Problem>& problems, const lld_sim3solver_params& params) {
+    std::vector<lld_sim3solver_problem> c;
+    for (const Sim3Problem& p : problems) { c.push_back(p.c()); n1_.push_back(p.n1); }
+    check(lld_sim3solver_batch_create(ctx.get(), (int32_t)c.size(), c.data(), &params, &h_), "lld_sim3solver_batch_create");
+  }
+  ~Sim3SolverBatch() { lld_sim3solver_batch_destroy(h_); }
+  Sim3SolverBatch(const Sim3SolverBatch&) = delete;
+  Sim3SolverBatch& operator=(const Sim3SolverBatch&) = delete;
+  // SetRansacParameters(0.99, 20, 300): LoopClosing::ComputeSim3's values (LoopClosing.cc:277)
+  static lld_sim3solver_params defaults() { lld_sim3solver_params p; lld_sim3solver_params_default(&p); return p; }
+  std::vector<Sim3Output> iterate(int nIterations, const std::vector<uint8_t>& active = {}) {
+    check(lld_sim3solver_batch_iterate(h_, nIterations, active.empty() ? nullptr : active.data()), "lld_sim3solver_batch_iterate");
+    return download();
+  }
+  // find() on every active solver: iterate(mRansacMaxIts) of each, continuing its state
+  std::vector<Sim3Output> find(const std::vector<uint8_t>& active = {}) {
+    check(lld_sim3solver_batch_find(h_, active.empty() ? nullptr : active.data()), "lld_sim3solver_batch_find");
+    return download();
+  }
+  std::vector<Sim3Output> download() {
+    const size_t n = n1_.size();
+    std::vector<lld_sim3solver_result> r(n);
+    std::vector<std::vector<uint8_t> > fl(n);
+    for (size_t i = 0; i < n; ++i) { fl[i].assign(n1_[i] > 0 ? n1_[i] : 1, 0); r[i].inlier = fl[i].data(); }
+    check(lld_sim3solver_batch_download(h_, r.data()), "lld_sim3solver_batch_download");
+    std::vector<Sim3Output> out(n);
+    for (size_t i = 0; i < n; ++i) {
+      out[i].has_pose = r[i].has_pose != 0;
+      for (int q = 0; q < 12; ++q) out[i].T12[q] = r[i].T12[q];
+      out[i].bNoMore = r[i].no_more != 0;
+      out[i].vbInliers.assign(fl[i].begin(), fl[i].begin() + n1_[i]);
+      out[i].nInliers = r[i].n_inliers;
+      out[i].iterations = r[i].iterations;
+      for (int q = 0; q < 9; ++q) out[i].R[q] = r[i].R[q];
+      for (int q = 0; q < 3; ++q) out[i].t[q] = r[i].t[q];
+      out[i].s = r[i].s;
+    }
+    return out;
+  }
+  lld_sim3solver_batch* get() const { return h_; }
+ private:
+  lld_sim3solver_batch* h_ = nullptr;
+  std::vector<int32_t> n1_;
+};
+
+// One Sim3Solver with the reference's method names: iterate(nIterations, bNoMore, vbInliers, nInliers), find(vbInliers12,
+// nInliers) and GetEstimatedRotation / Translation / Scale.
+class Sim3Solver {
+ public:
+  Sim3Solver(const Context& ctx, const Sim3Problem& p, const lld_sim3solver_params& params = Sim3SolverBatch::defaults())
+      : b_(ctx, std::vector<Sim3Problem>{p}, params) {}
+  bool iterate(int nIterations, bool& bNoMore, std::vector<bool>& vbInliers, int& nInliers, float T12[12]) {
+    last_ = b_.iterate(nIterations)[0];
+    return take(bNoMore, vbInliers, nInliers, T12);
+  }
+  // find() (:209-213) = iterate(mRansacMaxIts), continuing this solver's state
+  bool find(std::vector<bool>& vbInliers12, int& nInliers, float T12[12]) {
+    bool bNoMore;
+    last_ = b_.find()[0];
+    return take(bNoMore, vbInliers12, nInliers, T12);
+  }
+  // the best hypothesis so far (row-major 3x3, 3, scalar)
+  void GetEstimatedRotation(float R[9]) const { for (int q = 0; q < 9; ++q) R[q] = last_.R[q]; }
+  void GetEstimatedTranslation(float t[3]) const { for (int q = 0; q < 3; ++q) t[q] = last_.t[q]; }
+  float GetEstimatedScale() const { return last_.s; }
+ private:
+  bool take(bool& bNoMore, std::vector<bool>& vbInliers, int& nInliers, float T12[12]) const {
+    bNoMore = last_.bNoMore; vbInliers = last_.vbInliers; nInliers = last_.nInliers;
+    for (int q = 0; q < 12; ++q) T12[q] = last_.T12[q];
+    return last_.has_pose;
+  }
+  Sim3SolverBatch b_;
+  Sim3Output last_;
+};
+
 }  // namespace lld_amd
 #endif

@@ -179,6 +179,29 @@ class PnPHypothesis(C.Structure):
                 ("R", C.c_double * 9), ("t", C.c_double * 3)]
 
 
+class Sim3SolverParams(C.Structure):
+    _fields_ = [("probability", C.c_double), ("min_inliers", C.c_int32), ("max_iterations", C.c_int32)]
+
+
+class Sim3SolverProblem(C.Structure):
+    _fields_ = [("n", C.c_int32), ("xyz1", c_float_p), ("xyz2", c_float_p), ("sigma2_1", c_float_p), ("sigma2_2", c_float_p),
+                ("index1", c_int32_p), ("n1", C.c_int32), ("Rcw1", C.c_float * 9), ("tcw1", C.c_float * 3), ("Rcw2", C.c_float * 9),
+                ("tcw2", C.c_float * 3), ("fx1", C.c_float), ("fy1", C.c_float), ("cx1", C.c_float), ("cy1", C.c_float),
+                ("fx2", C.c_float), ("fy2", C.c_float), ("cx2", C.c_float), ("cy2", C.c_float), ("fix_scale", C.c_int32),
+                ("seed", C.c_uint32)]
+
+
+class Sim3SolverResult(C.Structure):
+    _fields_ = [("T12", C.c_float * 12), ("R", C.c_float * 9), ("t", C.c_float * 3), ("s", C.c_float), ("has_pose", C.c_int32),
+                ("n_inliers", C.c_int32), ("no_more", C.c_int32), ("iterations", C.c_int32), ("best_inliers", C.c_int32),
+                ("n1", C.c_int32), ("inlier", c_uint8_p)]
+
+
+class Sim3SolverHypothesis(C.Structure):
+    _fields_ = [("n_inliers", C.c_int32), ("record", C.c_int32), ("idx", C.c_int32 * 3), ("s", C.c_float), ("R", C.c_float * 9),
+                ("t", C.c_float * 3), ("T12", C.c_float * 12)]
+
+
 class PoseGraph(C.Structure):
     _fields_ = [("n_vertices", C.c_int32), ("n_edges", C.c_int32), ("sim3", c_double_p), ("fixed", c_uint8_p), ("edge_i", c_int32_p),
                 ("edge_j", c_int32_p), ("edge_sji", c_double_p)]
@@ -221,6 +244,8 @@ PRODUCT_SYMBOLS = [
     "lld_kfdb_detect_loop_candidates", "lld_kfdb_detect_relocalization_candidates",
     "lld_pnp_params_default", "lld_pnp_batch_create", "lld_pnp_batch_iterate", "lld_pnp_batch_download", "lld_pnp_batch_hypotheses",
     "lld_pnp_batch_destroy", "lld_pnp_find", "lld_pnp_batch_find",
+    "lld_sim3solver_params_default", "lld_sim3solver_batch_create", "lld_sim3solver_batch_iterate", "lld_sim3solver_batch_find",
+    "lld_sim3solver_batch_download", "lld_sim3solver_batch_hypotheses", "lld_sim3solver_batch_destroy", "lld_sim3solver_find",
 ]
 
 
@@ -331,6 +356,17 @@ class Lib:
             f("pnp_batch_destroy").argtypes = [vp]; f("pnp_batch_destroy").restype = None
             f("pnp_find").argtypes = [vp, C.POINTER(PnPProblem), C.POINTER(PnPParams), C.POINTER(PnPResult)]
             f("pnp_find").restype = C.c_int
+            f("sim3solver_params_default").argtypes = [C.POINTER(Sim3SolverParams)]; f("sim3solver_params_default").restype = None
+            f("sim3solver_batch_create").argtypes = [vp, C.c_int32, C.POINTER(Sim3SolverProblem), C.POINTER(Sim3SolverParams), C.POINTER(vp)]
+            f("sim3solver_batch_create").restype = C.c_int
+            f("sim3solver_batch_iterate").argtypes = [vp, C.c_int32, c_uint8_p]; f("sim3solver_batch_iterate").restype = C.c_int
+            f("sim3solver_batch_find").argtypes = [vp, c_uint8_p]; f("sim3solver_batch_find").restype = C.c_int
+            f("sim3solver_batch_download").argtypes = [vp, C.POINTER(Sim3SolverResult)]; f("sim3solver_batch_download").restype = C.c_int
+            f("sim3solver_batch_hypotheses").argtypes = [vp, C.c_int32, C.c_int32, C.POINTER(Sim3SolverHypothesis), c_int32_p, c_int32_p]
+            f("sim3solver_batch_hypotheses").restype = C.c_int
+            f("sim3solver_batch_destroy").argtypes = [vp]; f("sim3solver_batch_destroy").restype = None
+            f("sim3solver_find").argtypes = [vp, C.POINTER(Sim3SolverProblem), C.POINTER(Sim3SolverParams), C.POINTER(Sim3SolverResult)]
+            f("sim3solver_find").restype = C.c_int
 
 
 _PRODUCT = None
