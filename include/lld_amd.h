@@ -399,7 +399,8 @@ int lld_optimize_sim3_batch(lld_ctx* ctx, int n, const lld_sim3_problem* problem
  * (core/base_binary_edge.hpp:131-197), Levenberg-Marquardt with setUserLambdaInit(1e-16), optimize(15).  Nothing is marginalised:
  * H is the 7N x 7N system, solved by the block-Jacobi PCG spread over the GPU (g2o: sparse Cholesky).
  * Building the edge list from the map (:1447-1585) and the write-back (:1593-1653: SE3 recovery [R t/s], MapPoint correction through
- * the reference keyframe) stay with the adapter. */
+ * the reference keyframe) stay with the adapter.  LLD_ERR_INVALID for an edge whose end is out of range or whose two ends are the
+ * same vertex (edge_i == edge_j: the reference never builds one). */
 typedef struct {
   int32_t n_vertices;
   int32_t n_edges;

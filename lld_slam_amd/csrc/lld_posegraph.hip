@@ -449,7 +449,10 @@ extern "C" int lld_optimize_essential_graph(lld_ctx* ctx, const lld_pose_graph* 
   const int N = g->n_vertices, E = g->n_edges;
   if (N < 0 || E < 0 || (N > 0 && !g->sim3) || (E > 0 && (!g->edge_i || !g->edge_j || !g->edge_sji))) return LLD_ERR_INVALID;
   if (prm.iterations < 0 || prm.max_trials <= 0 || !(prm.pcg_rel_tol > 0) || prm.solver < 0 || prm.solver > 2) return LLD_ERR_INVALID;
-  for (int e = 0; e < E; e++) if (g->edge_i[e] < 0 || g->edge_i[e] >= N || g->edge_j[e] < 0 || g->edge_j[e] >= N) return LLD_ERR_INVALID;
+  // a self-edge (edge_i == edge_j) is refused: the reference never builds one, and the dense fill (J0^T J0 + J1^T J1) and the PCG
+  // matvec ((J0 + J1)^T (J0 + J1)) would solve different systems for it
+  for (int e = 0; e < E; e++)
+    if (g->edge_i[e] < 0 || g->edge_i[e] >= N || g->edge_j[e] < 0 || g->edge_j[e] >= N || g->edge_i[e] == g->edge_j[e]) return LLD_ERR_INVALID;
   out->chi2 = 0; out->lm_iterations = 0; out->lm_trials = 0; out->pcg_iterations = 0; out->solver_used = 0;
   if (N) std::memcpy(out->sim3, g->sim3, sizeof(double) * 8 * (size_t)N);
   // unknowns in vertex order (g2o: buildIndexMapping over the vertices sorted by id), vertex CSR in edge order

@@ -71,6 +71,10 @@ def test_essential_graph_degenerate_inputs(gpu_ctx, oracle):
     bad = dataclasses.replace(gr, edge_j=np.full_like(gr.edge_j, 99))
     with pytest.raises(RuntimeError):
         Optimizer(gpu_ctx).OptimizeEssentialGraph(bad)
+    selfedge = gr.edge_j.copy(); selfedge[5] = gr.edge_i[5]              # a self-edge: the dense fill and the PCG would differ on it
+    for solver in (0, 1, 2):
+        with pytest.raises(RuntimeError):
+            Optimizer(gpu_ctx).OptimizeEssentialGraph(dataclasses.replace(gr, edge_j=selfedge), solver=solver)
     consistent = synth.make_essential_graph(5, 40, drift=(0.0, 0.0))
     g, o = Optimizer(gpu_ctx).OptimizeEssentialGraph(consistent), oracle.optimize_essential_graph(consistent)
     assert g.chi2 < 1e-16 and o.chi2 < 1e-16 and (deviation(g, o)[:3] <= 1e-7).all()         # a fixed point: nothing moves

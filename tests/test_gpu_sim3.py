@@ -58,3 +58,112 @@ def test_optimize_sim3_batch_of_candidates(gpu_ctx, oracle):
     gs = Optimizer(gpu_ctx).OptimizeSim3(pairs, th2=10.0)
     for g, p in zip(gs, pairs):
         _check(g, oracle.optimize_sim3(p), oracle.optimize_sim3(p, fma=True))
+
+
+# ---------------------------------------------------------------- exact candidates (tests/sim3_scenes.py): every count known in advance
+
+def _exact(gpu_ctx, oracle, p, **kw):
+    g = Optimizer(gpu_ctx).OptimizeSim3(p, **kw)
+    _check(g, oracle.optimize_sim3(p, **kw), oracle.optimize_sim3(p, fma=True, **kw))
+    return g
+
+
+@pytest.mark.parametrize("survivors", [9, 10])
+def test_optimize_sim3_survivor_threshold(gpu_ctx, oracle, survivors):
+    """n - nBad < 10 after round 1: return 0 with g2oS12 unchanged; exactly 10: a full round 2."""
+    from sim3_scenes import make_exact_pair
+    p = make_exact_pair(1, survivors + 2, out12=1, out21=1)
+    g = _exact(gpu_ctx, oracle, p)
+    assert g.n_bad_first == 2 and np.array_equal(g.dropped.astype(bool), p.meta["bad"])
+    if survivors == 9:
+        assert g.n_inliers == 0 and g.lm_iterations[1] == 0
+        np.testing.assert_array_equal(g.s12_q, p.s12_q); np.testing.assert_array_equal(g.s12_t, p.s12_t); assert g.s12_s == p.s12_s
+    else:
+        assert g.n_inliers == 10 and g.lm_iterations[1] > 0
+
+
+@pytest.mark.parametrize("clean,bad", [(1, 3), (3, 1)])
+@pytest.mark.parametrize("nbad", [0, 1])
+def test_optimize_sim3_more_iterations_budget(gpu_ctx, oracle, nbad, clean, bad):
+    """nBad = 0 selects its_more_clean, nBad = 1 its_more_bad (the oracle uses the selected budget to the end on these scenes,
+    tests/test_oracle_sim3.py); LM may stop early, so the device's count is held to the oracle's and to the budget."""
+    from sim3_scenes import make_exact_pair
+    p = make_exact_pair(2 + nbad, 60, out12=nbad, noise=0.49)
+    kw = dict(its_first=1, its_more_clean=clean, its_more_bad=bad)
+    g = Optimizer(gpu_ctx).OptimizeSim3(p, **kw)
+    o = oracle.optimize_sim3(p, **kw)
+    _check(g, o, oracle.optimize_sim3(p, fma=True, **kw))
+    assert g.n_bad_first == nbad and g.lm_iterations[0] == 1
+    assert g.lm_iterations[1] <= (bad if nbad else clean) and abs(g.lm_iterations[1] - o.lm_iterations[1]) <= 2
+
+
+@pytest.mark.parametrize("kind", ["out12", "out21", "out_both"])
+def test_optimize_sim3_drop_rule(gpu_ctx, oracle, kind):
+    """chi2(e12) > th2 || chi2(e21) > th2: a correspondence wrong in one image only is dropped like one wrong in both."""
+    from sim3_scenes import make_exact_pair
+    p = make_exact_pair(4, 80, **{kind: 5})
+    g = _exact(gpu_ctx, oracle, p)
+    np.testing.assert_array_equal(np.nonzero(g.dropped)[0], p.meta[kind])
+    assert g.n_bad_first == 5 and g.n_inliers == 75
+
+
+def test_optimize_sim3_point_behind_the_cameras(gpu_ctx, oracle):
+    """Finite negative depth: OptimizeSim3 checks no depth, a consistent point behind both cameras projects (mirrored) onto its
+    observations and stays in."""
+    from sim3_scenes import make_exact_pair
+    p = make_exact_pair(7, 50, behind=2, out12=1)
+    assert (p.p2c[p.meta["behind"], 2] < 0).all() and (p.p1c[p.meta["behind"], 2] < 0).all()
+    g = _exact(gpu_ctx, oracle, p)
+    assert not g.dropped[p.meta["behind"]].any() and g.n_inliers == 49
+
+
+@pytest.mark.parametrize("n", [1, 2, 255, 256, 257, 8192])
+def test_optimize_sim3_sizes(gpu_ctx, oracle, n):
+    """Around the kernel's 256-lane stride and at the Sim3Solver's maximum of 8192 correspondences."""
+    from sim3_scenes import make_exact_pair
+    p = make_exact_pair(10 + n, n, out12=n // 20, out21=n // 40)
+    g = _exact(gpu_ctx, oracle, p)
+    np.testing.assert_array_equal(g.dropped.astype(bool), p.meta["bad"])
+    assert g.n_inliers == (0 if n < 10 else n - int(p.meta["bad"].sum()))
+
+
+@pytest.mark.parametrize("kw,n,out,inliers", [
+    (dict(min_inliers=3), 4, 1, 3), (dict(min_inliers=3), 3, 1, 0),
+    (dict(min_inliers=50), 60, 10, 50), (dict(min_inliers=50), 60, 11, 0),
+    (dict(th2=5.991), 100, 8, 92), (dict(th2=10.0), 100, 8, 92), (dict(th2=50.0), 100, 8, 92),
+    (dict(max_trials=1), 100, 3, 97),
+    (dict(its_more_bad=2, its_more_clean=7), 100, 3, 97),
+    (dict(bFixScale=False), 100, 3, 97), (dict(bFixScale=True), 100, 3, 97),
+])
+def test_optimize_sim3_parameters(gpu_ctx, oracle, kw, n, out, inliers):
+    """Non-default parameters; th2 also sets the Huber delta (float(sqrt(th2)))."""
+    from sim3_scenes import make_exact_pair
+    p = make_exact_pair(30 + n + out, n, out12=out - out // 2, out_both=out // 2, scale=1.0 if kw.get("bFixScale", True) else 1.3)
+    g = _exact(gpu_ctx, oracle, p, **kw)
+    assert g.n_bad_first == out and g.n_inliers == inliers
+    if inliers == 0:
+        np.testing.assert_array_equal(g.s12_t, p.s12_t)
+    if kw.get("bFixScale", True):
+        assert g.s12_s == p.s12_s
+
+
+def test_optimize_sim3_mixed_batch_is_the_single_calls(gpu_ctx, oracle):
+    """One launch with n = 0, an early exit, a clean candidate and n = 8192: each workgroup's result is its single call's, bit
+    for bit, and the oracle's at _check."""
+    import dataclasses
+    from sim3_scenes import make_exact_pair
+    clean = make_exact_pair(40, 120)
+    empty = dataclasses.replace(clean, p1c=np.zeros((0, 3)), p2c=np.zeros((0, 3)), obs1=np.zeros((0, 2)), obs2=np.zeros((0, 2)),
+                                inv_sigma2_1=np.zeros(0), inv_sigma2_2=np.zeros(0))
+    pairs = [empty, make_exact_pair(41, 11, out12=1, out21=1), clean, make_exact_pair(42, 8192, out12=300, out21=100, out_both=50)]
+    opt = Optimizer(gpu_ctx)
+    batch = opt.OptimizeSim3(pairs)
+    for p, b in zip(pairs, batch):
+        s = opt.OptimizeSim3(p)
+        for f in ("s12_q", "s12_t", "dropped"):
+            np.testing.assert_array_equal(getattr(b, f), getattr(s, f))
+        assert (b.s12_s, b.n_inliers, b.n_bad_first, list(b.lm_iterations), list(b.lm_trials), b.chi2) == \
+               (s.s12_s, s.n_inliers, s.n_bad_first, list(s.lm_iterations), list(s.lm_trials), s.chi2)
+        if p.n:
+            _check(b, oracle.optimize_sim3(p), oracle.optimize_sim3(p, fma=True))
+    assert batch[0].n_inliers == 0 and batch[1].n_inliers == 0 and batch[2].n_inliers == 120 and batch[3].n_inliers == 8192 - 450

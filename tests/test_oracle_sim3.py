@@ -53,3 +53,24 @@ def test_optimize_sim3_free_scale_and_protocol_branches(oracle):
     # deterministic
     r2 = oracle.optimize_sim3(p, bFixScale=False)
     np.testing.assert_array_equal(r.s12_t, r2.s12_t)
+
+
+def test_optimize_sim3_exact_exits_and_budgets(oracle):
+    """On tests/sim3_scenes.py's exact candidates every count is known in advance: 9 survivors return 0 and leave g2oS12 alone,
+    10 run round 2; nBad = 0 / 1 selects its_more_clean / its_more_bad, and the nBad = 1 scene needs more than the clean budget."""
+    from sim3_scenes import make_exact_pair
+    for surv in (9, 10):
+        p = make_exact_pair(1, surv + 2, out12=1, out21=1)
+        r = oracle.optimize_sim3(p)
+        assert r.n_bad_first == 2 and np.array_equal(r.dropped.astype(bool), p.meta["bad"])
+        if surv == 9:
+            assert r.n_inliers == 0 and r.lm_iterations[1] == 0
+            np.testing.assert_array_equal(r.s12_q, p.s12_q); np.testing.assert_array_equal(r.s12_t, p.s12_t)
+        else:
+            assert r.n_inliers == 10 and r.lm_iterations[1] > 0
+    for nbad in (0, 1):
+        p = make_exact_pair(2 + nbad, 60, out12=nbad, noise=0.49)
+        for clean, bad in ((1, 3), (3, 1)):
+            r = oracle.optimize_sim3(p, its_first=1, its_more_clean=clean, its_more_bad=bad)
+            assert r.n_bad_first == nbad and r.n_inliers == 60 - nbad
+            assert r.lm_iterations[1] == (bad if nbad else clean)       # the budget of the selected branch, used to the end

@@ -5,12 +5,15 @@ place (every vertex and measurement component times 1 - 2^-52, 1 or 1 + 2^-52 at
 draw of a heavy-tailed quantity: g2o differentiates EdgeSim3 numerically, and in the flat valley of a free-scale graph LM's accept /
 reject decisions hinge on chi2 differences at rounding level; re-ordering the edges turned out not to move the oracle at all (its
 normal equations are summed per block in a fixed order), the last-place jitter does.  FLOOR = within ten times that spread, iteration /
-trial counts inside the range the variants span (+- 2 / 12 as in the test).   python tools/fuzz_posegraph.py [n=200] [seed=0]"""
+trial counts inside the range the variants span (+- 2 / 12 as in the test).  Every other graph comes from tests/posegraph_scenes.py
+(pLoopKF in the middle, many-to-many LoopConnections, earlier loops, re-parented edges, extra fixed vertices).
+  python tools/fuzz_posegraph.py [n=200] [seed=0]"""
 import dataclasses, sys, numpy as np
 sys.path.insert(0, "."); sys.path.insert(0, "tests"); sys.path.insert(0, "oracle")
 from lld_slam_amd import Context, Optimizer, synth
 import oracle_py as O
 from test_gpu_posegraph import _check, deviation
+import posegraph_scenes as S
 
 
 def oracle_spread(gr, o, fix, iters, rng):
@@ -38,7 +41,15 @@ def main():
         kw = dict(drift=(float(rng.choice([0.0005, 0.002, 0.01])), float(rng.choice([0.01, 0.03, 0.1]))), covis=int(rng.choice([1, 3, 6])),
                   n_corrected=int(rng.integers(1, max(2, nk // 3))))
         fix = bool(rng.integers(0, 2)); solver = int(rng.choice([1, 2])); iters = int(rng.choice([15, 15, 2, 3]))
-        gr = synth.make_essential_graph(int(rng.integers(0, 1 << 30)), nk, **kw)
+        if it % 2:                                                     # half of them shaped like the reference's graphs
+            nk = int(rng.choice([16, 30, 60, 120]))
+            kw = dict(drift=kw["drift"], covis=int(rng.choice([1, 3])), laps=int(rng.integers(1, 4)), loop_kf=int(rng.integers(0, nk // 2)),
+                      cur_conn=int(rng.integers(1, 7)), loop_conn=int(rng.integers(1, 8)), earlier_loops=int(rng.integers(0, 4)),
+                      long_covis=int(rng.integers(0, 4)), reparent_frac=float(rng.choice([0.0, 0.3])),
+                      extra_fixed=tuple(int(v) for v in rng.choice(nk, int(rng.integers(0, 3)), replace=False)))
+            gr = S.make_loop_scene(int(rng.integers(0, 1 << 30)), nk, **kw)
+        else:
+            gr = synth.make_essential_graph(int(rng.integers(0, 1 << 30)), nk, **kw)
         try:
             g = Optimizer(ctx).OptimizeEssentialGraph(gr, bFixScale=fix, solver=solver, iterations=iters)
             o = O.optimize_essential_graph(gr, bFixScale=fix, iterations=iters)
