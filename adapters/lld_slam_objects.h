@@ -72,6 +72,7 @@ class MatU8 {
 };
 
 struct Point2f { float x, y; };
+struct Point3f { float x, y, z; Point3f() : x(0.f), y(0.f), z(0.f) {} Point3f(float a, float b, float c) : x(a), y(b), z(c) {} };   // cv::Point3f
 struct KeyPoint { Point2f pt; int octave; float angle; KeyPoint() : pt{0.f, 0.f}, octave(0), angle(0.f) {} };   // cv::KeyPoint: pt, octave, angle
 struct KeyLine {                                                   // cv::line_descriptor::KeyLine (LineMatching.h:27): end points and octave
   float startPointX, startPointY, endPointX, endPointY; int octave;

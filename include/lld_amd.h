@@ -1485,6 +1485,128 @@ void lld_sim3solver_batch_destroy(lld_sim3solver_batch* b);
 int  lld_sim3solver_find(lld_ctx* ctx, const lld_sim3solver_problem* problem, const lld_sim3solver_params* params,
                          lld_sim3solver_result* out);
 
+/* ================================================================== Initializer (src/Initializer.cc), the monocular bootstrap
+ * Tracking::MonocularInitialization (src/Tracking.cc:579-640) builds Initializer(mCurrentFrame, 1.0, 200) on the reference frame
+ * and calls Initialize(mCurrentFrame, mvIniMatches, Rcw, tcw, mvIniP3D, vbTriangulated) on every later frame until it succeeds;
+ * mvIniMatches comes from ORBmatcher::SearchForInitialization (lld_search_for_initialization above).  A handle lives as long as
+ * the reference's object: lld_initializer_create is the constructor (:33-42; mvKeys1 stays in HBM), lld_initializer_initialize
+ * is Initialize() (:44-121).  One call queues its whole sequence on the context's stream with no host trip between the kernels.
+ * Restated literally:
+ *   Match list (:51-63): mvMatches12 = (i, vMatches12[i]) for every vMatches12[i] >= 0, in index order; N = its length.
+ *   Sets (:78-97): all iterations x 8 draws come from one stream, in order; each draw is RandomInt(0, size-1) over a fresh copy
+ *     of 0..N-1 per iteration, the back swapped into the taken place.  Built on the host inside the call, before its one upload.
+ *   Normalize (:749-795) over ALL keypoints of a frame, not only the matched: float means summed in index order, mean = sum/N,
+ *     float mean absolute deviations summed in index order, sX = (float)(1.0/meanDevX); point = (x - meanX)*sX in float;
+ *     T = [sX 0 -meanX*sX; 0 sY -meanY*sY; 0 0 1].  On the host (create for frame 1, initialize for frame 2).
+ *   ComputeH21 (:226-266): rows 2i = (0 0 0 -u1 -v1 -1 v2*u1 v2*v1 v2), 2i+1 = (u1 v1 1 0 0 0 -u2*u1 -u2*v1 -u2), float entries;
+ *     Hn = the null vector of the 16x9 system.  ComputeF21 (:268-303): rows (u2*u1 u2*v1 u2 v2*u1 v2*v1 v2 u1 v1 1); Fpre = the
+ *     null vector of the 8x9 system; its full SVD with w[2] = 0; Fn = u*diag(w)*vt.
+ *   Composition (:159-161, :210-212): H21i = T2inv*Hn*T1, H12i = H21i.inv(); F21i = T2t*Fn*T1, products left to right.
+ *   CheckHomography (:305-388) / CheckFundamental (:390-468) in float, operation by operation as written there (1.0/x is the
+ *     double quotient rounded to float): th = 5.991; th = 3.841 with thScore = 5.991; the test is `>`; a one-sided score term is
+ *     added even when the other side fails; score is the sequential float sum in match order, bit for bit.
+ *   Best hypothesis (:165, :216): replaced on strict `>`, starting from score 0.  When every hypothesis scores 0 (or NaN) the
+ *     model has no winner: its matrix, inlier count and mask are zeros and win_H / win_F is -1.
+ *   Model (:112-118): RH = SH/(SH+SF) in float; RH > 0.40 selects ReconstructH, otherwise (a 0/0 NaN included) ReconstructF.
+ *     The chosen model having no winner (both scores 0) gives success = 0 with no motion hypothesis run; the reference would
+ *     pass an empty Mat on.
+ *   ReconstructF (:470-570): N = the winner's inliers; E21 = K.t()*F21*K; DecomposeE (:909-929): t = u.col(2)/norm, R1 = u*W*vt,
+ *     R2 = u*W.t()*vt, each negated when its determinant < 0; CheckRT on (R1,t) (R2,t) (R1,-t) (R2,-t) in this order;
+ *     nMinGood = max(int(0.9*N), minTriangulated); nsimilar counts nGood > 0.7*maxGood in double; maxGood < nMinGood or
+ *     nsimilar > 1 fails; then the if / else-if chain on maxGood == nGood_k: the first equal one is examined and its
+ *     parallax > minParallax decides, the next is not tried.
+ *   ReconstructH (:572-732): A = K.inv()*H21*K, its full SVD, s = det(U)*det(Vt); d1/d2 < 1.00001 || d2/d3 < 1.00001 fails with
+ *     no hypothesis run; aux1, aux3, aux_stheta, ctheta, aux_sphi, cphi in float; the eight hypotheses in the reference's order
+ *     and signs (x1 = {a,a,-a,-a}, x3 = {b,-b,b,-b}, stheta / sphi = {c,-c,-c,c}); R = s*U*Rp*Vt, t = U*tp over its norm.  vn is
+ *     computed by the reference (n flipped when n.z < 0) but never read, and is not computed here.  nGood > bestGood moves best to
+ *     second, else nGood > secondBestGood; success when secondBestGood < 0.75*bestGood && bestParallax >= minParallax &&
+ *     bestGood > minTriangulated && bestGood > 0.9*N.
+ *   CheckRT (:798-907): vbGood and vP3D have n1 entries indexed by match.first.  P1 = K[I|0], P2 = K*[R|t], O2 = -R.t()*t.  Per
+ *     inlier match: Triangulate (:734-747: rows x*P.row(2)-P.row(0), y*P.row(2)-P.row(1) of both cameras in float, the null
+ *     vector of the 4x4, x3D = xyz/w); a non-finite coordinate skips the match; cosParallax = normal1.dot(normal2)/(dist1*dist2)
+ *     as float; z1 <= 0 && cosParallax < 0.99998 skips; p3dC2 = R*p3dC1+t, z2 <= 0 && cosParallax < 0.99998 skips; the two
+ *     reprojection errors in float against th2 = 4*sigma^2 (`>` skips); then cosParallax is pushed, vP3D written and nGood
+ *     counted BEFORE vbGood is set only when cosParallax < 0.99998.  parallax = acos(sorted[min(50, size-1)])*180/pi, 0 when
+ *     nGood == 0.  The selection here is exact (equal to sort-then-index; a NaN cosine orders by its bit pattern, where
+ *     std::sort is undefined).
+ *   Non-finite values follow IEEE with no special case beyond the reference's own isfinite test.
+ * Outputs when success = 0: R21, t21, p3d and triangulated are zeros (the reference leaves its arguments untouched).
+ *   best_index is the motion hypothesis the final rule examined (F: the first with nGood == maxGood once the count tests passed;
+ *   H: bestSolutionIdx), -1 when there was none; n_good / parallax hold every hypothesis run (four for F), zeros otherwise.
+ * DEVIATION 1 (the sample stream): the reference draws from the process-global rand(), seeded once per process by
+ *   SeedRandOnce(0), so only a process's first Initialize is reproducible.  Here EVERY initialize call draws from a fresh glibc
+ *   TYPE_3 stream after srand(seed); seed 0 equals srand(1), as in lld_pnp / lld_sim3solver.
+ * DEVIATION 2 (numerics left to OpenCV): these choices are this library's, restated identically in tests/initializer_ref.py.
+ *   Matrix products (also Mat::dot, R*p3dC1): the float products summed in double in index order from the first, rounded to float
+ *   once; then the float + t.  A chain A*B*C is (A*B)*C.  u*diag(w) is the float product u_ik*w_k.  s*U is the float product.
+ *   cv::norm: the square root of that double sum, in double; v/norm(v): the double reciprocal times the widened float, rounded;
+ *   x3D/w likewise.  cv::determinant (3x3): (a0*(a4*a8-a5*a7) - a1*(a3*a8-a5*a6)) + a2*(a3*a7-a4*a6) in double on the widened
+ *   entries.  Mat::inv (3x3): the cofactors in double times 1/det, rounded; det == 0 gives the zero matrix.  sqrt of a float: the
+ *   double square root rounded to float.
+ *   Null vector of the 16x9 / 8x9 / 4x4 systems: A^T A in double from the widened floats (each entry summed over the rows in order
+ *   from 0.0), lld_pnp's cyclic Jacobi in fp64 (same sweeps and tolerance), the eigenvector of the smallest eigenvalue, the
+ *   HIGHEST index on a tie, canonical sign (the first largest-magnitude component positive), rounded to float.
+ *   Full 3x3 SVDs (rank-2 step of F, DecomposeE, ReconstructH): the same Jacobi on A^T A; eigenvalues ordered descending (the
+ *   largest: lowest index on a tie; the smallest of the other two: highest index on a tie); v_k canonical; w_k = ||A v_k|| in
+ *   double; u_k = A v_k / w_k.  U is completed when a singular value is (near) zero: u_0 = e_0 when w_0 = 0; u_1, when not
+ *   w_1 > 1e-9*w_0, is the axis along which |u_0| is smallest (lowest index on a tie) made orthogonal to u_0 and normalised;
+ *   u_2, when not w_2 > 1e-9*w_0, is u_0 x u_1.  So A = U*diag(w)*Vt holds to rounding, U's columns are orthonormal to 1e-7 or
+ *   better, and s*U*Rp*Vt is a proper rotation whenever det(U)*det(Vt) = +-1 is, as in the reference.  U, w, Vt are then floats.
+ *   Device acos may differ from glibc's by an ulp of double; nothing else differs.  No FMA contraction in the kernels.
+ * Limits: LLD_ERR_INVALID / LLD_ERR_UNSUPPORTED with nothing allocated: nulls; n1, n2 or n12 below 1 (INVALID) or above
+ *   LLD_INIT_MAX_KEYPOINTS (UNSUPPORTED); n12 != n1; a match value >= n2; fewer than 8 matches (the reference would draw from an
+ *   empty vector); iterations outside 1..LLD_INIT_MAX_ITERATIONS; sigma not > 0 or not finite; fx or fy not > 0 or K not finite;
+ *   non-finite keypoints.  A handle is driven by one host thread at a time, on its context's stream. */
+#define LLD_INIT_MAX_KEYPOINTS 8192         /* n1, n2 and the length of vMatches12             */
+#define LLD_INIT_MAX_ITERATIONS 4096        /* mMaxIterations                                  */
+typedef struct {
+  float sigma;                           /* 1.0 (Tracking.cc:596)                                 */
+  int32_t iterations;                    /* 200 (Tracking.cc:596)                                 */
+  float min_parallax;                    /* 1.0 (Initializer.cc:116-118)                          */
+  int32_t min_triangulated;              /* 50  (Initializer.cc:116-118)                          */
+  uint32_t seed;                         /* srand(seed) of every call's stream (DEVIATION 1)      */
+} lld_initializer_params;
+void lld_initializer_params_default(lld_initializer_params* p);   /* (1.0, 200, 1.0, 50, 0) */
+typedef struct {
+  int32_t success;                       /* Initialize()'s return                                 */
+  int32_t model;                         /* 0: ReconstructH ran (RH > 0.40), 1: ReconstructF      */
+  float SH, SF, RH;
+  float H21[9], F21[9];                  /* the winners, row-major; zeros without a winner        */
+  int32_t n_inliers_H, n_inliers_F;
+  float R21[9], t21[3];                  /* zeros unless success                                  */
+  int32_t n_good[8];                     /* nGood of every motion hypothesis (four for F)         */
+  float parallax[8];
+  int32_t best_index;                    /* the motion hypothesis examined, or -1                 */
+  int32_t n_matches;                     /* N = mvMatches12.size()                                */
+  int32_t win_H, win_F;                  /* the winning iteration of each model, or -1            */
+  uint8_t* inlier_H;                     /* [N]  vbMatchesInliersH (room for n1), or NULL         */
+  uint8_t* inlier_F;                     /* [N]  vbMatchesInliersF (room for n1), or NULL         */
+  float* p3d;                            /* [3*n1] vP3D, or NULL                                  */
+  uint8_t* triangulated;                 /* [n1] vbTriangulated, or NULL                          */
+} lld_initializer_result;
+typedef struct {                          /* diagnostic: one hypothesis of the last initialize call */
+  int32_t idx[8];                        /* mvSets[it]                                            */
+  float M[9];                            /* H21i or F21i                                          */
+  float score;                           /* currentScore                                          */
+  int32_t n_inliers;                     /* true entries of vbCurrentInliers                      */
+} lld_initializer_hypothesis;
+typedef struct lld_initializer lld_initializer;
+/* Initializer(ReferenceFrame, sigma, iterations) (:33-42): K row-major 3x3, keys1_xy = mvKeysUn[i].pt of the reference frame. */
+int  lld_initializer_create(lld_ctx* ctx, const float* K, int32_t n1, const float* keys1_xy, const lld_initializer_params* params,
+                            lld_initializer** out);
+/* Initialize(CurrentFrame, vMatches12, ...) (:44-121): keys2_xy = mvKeysUn of the current frame, matches12[n12 = n1] = the index
+ * in frame 2 matched to keypoint i of frame 1, or negative.  The caller sets the four pointers of `result` (each may be NULL)
+ * before the call.  Waits for the stream. */
+int  lld_initializer_initialize(lld_initializer* h, int32_t n2, const float* keys2_xy, int32_t n12, const int32_t* matches12,
+                                lld_initializer_result* result);
+/* Diagnostic (tests): the hypotheses of the last initialize call, model 0 = H, 1 = F, in iteration order.  *n: the iterations
+ * run (0 before any call); the first min(capacity, *n) are written. */
+int  lld_initializer_hypotheses(lld_initializer* h, int32_t model, int32_t capacity, lld_initializer_hypothesis* out, int32_t* n);
+void lld_initializer_destroy(lld_initializer* h);
+/* One shot: create, initialize, destroy. */
+int  lld_initializer_find(lld_ctx* ctx, const float* K, int32_t n1, const float* keys1_xy, int32_t n2, const float* keys2_xy,
+                          int32_t n12, const int32_t* matches12, const lld_initializer_params* params, lld_initializer_result* result);
+
 #if defined(__GNUC__)
 #pragma GCC visibility pop
 #endif

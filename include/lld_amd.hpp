@@ -828,5 +828,66 @@ class Sim3Solver {
   Sim3Output last_;
 };
 
+// ---- Initializer (src/Initializer.cc): the monocular bootstrap's H / F RANSAC and reconstruction, resident for the life of
+// the reference's object.  Initializer(K, mvKeysUn of the reference frame, sigma, iterations) as the reference's constructor;
+// Initialize(mvKeysUn of the current frame, vMatches12, R21, t21, vP3D, vbTriangulated) returns the reference's bool.
+struct InitializerOutput {
+  lld_initializer_result r;              // every field of the C record (its four pointers are NULL)
+  std::vector<uint8_t> inlier_H, inlier_F;   // [N]
+  std::vector<float> p3d;                // [3*n1]
+  std::vector<uint8_t> triangulated;     // [n1]
+};
+
+class Initializer {
+ public:
+  static lld_initializer_params defaults() { lld_initializer_params p; lld_initializer_params_default(&p); return p; }
+  // keys1_xy: [2*n1] mvKeysUn[i].pt of the reference frame; K: row-major 3x3
+  Initializer(const Context& ctx, const float K[9], const std::vector<float>& keys1_xy, float sigma = 1.0f, int iterations = 200,
+              uint32_t seed = 0) : n1_((int32_t)(keys1_xy.size() / 2)) {
+    lld_initializer_params p = defaults();
+    p.sigma = sigma; p.iterations = iterations; p.seed = seed;
+    check(lld_initializer_create(ctx.get(), K, n1_, keys1_xy.data(), &p, &h_), "lld_initializer_create");
+  }
+  Initializer(const Context& ctx, const float K[9], const std::vector<float>& keys1_xy, const lld_initializer_params& p)
+      : n1_((int32_t)(keys1_xy.size() / 2)) {
+    check(lld_initializer_create(ctx.get(), K, n1_, keys1_xy.data(), &p, &h_), "lld_initializer_create");
+  }
+  ~Initializer() { lld_initializer_destroy(h_); }
+  Initializer(const Initializer&) = delete;
+  Initializer& operator=(const Initializer&) = delete;
+  // Every output of one Initialize() call.
+  InitializerOutput Run(const std::vector<float>& keys2_xy, const std::vector<int>& vMatches12) {
+    InitializerOutput o;
+    o.inlier_H.assign(n1_, 0); o.inlier_F.assign(n1_, 0); o.p3d.assign(3 * (size_t)n1_, 0.f); o.triangulated.assign(n1_, 0);
+    o.r = lld_initializer_result();
+    o.r.inlier_H = o.inlier_H.data(); o.r.inlier_F = o.inlier_F.data(); o.r.p3d = o.p3d.data(); o.r.triangulated = o.triangulated.data();
+    std::vector<int32_t> m(vMatches12.begin(), vMatches12.end());
+    check(lld_initializer_initialize(h_, (int32_t)(keys2_xy.size() / 2), keys2_xy.data(), (int32_t)m.size(), m.data(), &o.r),
+          "lld_initializer_initialize");
+    o.inlier_H.resize(o.r.n_matches); o.inlier_F.resize(o.r.n_matches);
+    o.r.inlier_H = nullptr; o.r.inlier_F = nullptr; o.r.p3d = nullptr; o.r.triangulated = nullptr;
+    return o;
+  }
+  // Initialize (:44-121): on success R21 (row-major 3x3), t21, vP3D ([3*n1]) and vbTriangulated ([n1]) are filled; on failure
+  // they are left untouched, as the reference leaves them.
+  bool Initialize(const std::vector<float>& keys2_xy, const std::vector<int>& vMatches12, float R21[9], float t21[3],
+                  std::vector<float>& vP3D, std::vector<bool>& vbTriangulated) {
+    last_ = Run(keys2_xy, vMatches12);
+    if (!last_.r.success) return false;
+    for (int q = 0; q < 9; ++q) R21[q] = last_.r.R21[q];
+    for (int q = 0; q < 3; ++q) t21[q] = last_.r.t21[q];
+    vP3D = last_.p3d;
+    vbTriangulated.assign(last_.triangulated.begin(), last_.triangulated.end());
+    return true;
+  }
+  const InitializerOutput& last() const { return last_; }
+  int32_t n1() const { return n1_; }
+  lld_initializer* get() const { return h_; }
+ private:
+  lld_initializer* h_ = nullptr;
+  int32_t n1_;
+  InitializerOutput last_;
+};
+
 }  // namespace lld_amd
 #endif

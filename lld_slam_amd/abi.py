@@ -202,6 +202,23 @@ class Sim3SolverHypothesis(C.Structure):
                 ("t", C.c_float * 3), ("T12", C.c_float * 12)]
 
 
+class InitializerParams(C.Structure):
+    _fields_ = [("sigma", C.c_float), ("iterations", C.c_int32), ("min_parallax", C.c_float), ("min_triangulated", C.c_int32),
+                ("seed", C.c_uint32)]
+
+
+class InitializerResult(C.Structure):
+    _fields_ = [("success", C.c_int32), ("model", C.c_int32), ("SH", C.c_float), ("SF", C.c_float), ("RH", C.c_float),
+                ("H21", C.c_float * 9), ("F21", C.c_float * 9), ("n_inliers_H", C.c_int32), ("n_inliers_F", C.c_int32),
+                ("R21", C.c_float * 9), ("t21", C.c_float * 3), ("n_good", C.c_int32 * 8), ("parallax", C.c_float * 8),
+                ("best_index", C.c_int32), ("n_matches", C.c_int32), ("win_H", C.c_int32), ("win_F", C.c_int32),
+                ("inlier_H", c_uint8_p), ("inlier_F", c_uint8_p), ("p3d", c_float_p), ("triangulated", c_uint8_p)]
+
+
+class InitializerHypothesis(C.Structure):
+    _fields_ = [("idx", C.c_int32 * 8), ("M", C.c_float * 9), ("score", C.c_float), ("n_inliers", C.c_int32)]
+
+
 class PoseGraph(C.Structure):
     _fields_ = [("n_vertices", C.c_int32), ("n_edges", C.c_int32), ("sim3", c_double_p), ("fixed", c_uint8_p), ("edge_i", c_int32_p),
                 ("edge_j", c_int32_p), ("edge_sji", c_double_p)]
@@ -246,6 +263,8 @@ PRODUCT_SYMBOLS = [
     "lld_pnp_batch_destroy", "lld_pnp_find", "lld_pnp_batch_find",
     "lld_sim3solver_params_default", "lld_sim3solver_batch_create", "lld_sim3solver_batch_iterate", "lld_sim3solver_batch_find",
     "lld_sim3solver_batch_download", "lld_sim3solver_batch_hypotheses", "lld_sim3solver_batch_destroy", "lld_sim3solver_find",
+    "lld_initializer_params_default", "lld_initializer_create", "lld_initializer_initialize", "lld_initializer_hypotheses",
+    "lld_initializer_destroy", "lld_initializer_find",
 ]
 
 
@@ -367,6 +386,17 @@ class Lib:
             f("sim3solver_batch_destroy").argtypes = [vp]; f("sim3solver_batch_destroy").restype = None
             f("sim3solver_find").argtypes = [vp, C.POINTER(Sim3SolverProblem), C.POINTER(Sim3SolverParams), C.POINTER(Sim3SolverResult)]
             f("sim3solver_find").restype = C.c_int
+            f("initializer_params_default").argtypes = [C.POINTER(InitializerParams)]; f("initializer_params_default").restype = None
+            f("initializer_create").argtypes = [vp, c_float_p, C.c_int32, c_float_p, C.POINTER(InitializerParams), C.POINTER(vp)]
+            f("initializer_create").restype = C.c_int
+            f("initializer_initialize").argtypes = [vp, C.c_int32, c_float_p, C.c_int32, c_int32_p, C.POINTER(InitializerResult)]
+            f("initializer_initialize").restype = C.c_int
+            f("initializer_hypotheses").argtypes = [vp, C.c_int32, C.c_int32, C.POINTER(InitializerHypothesis), c_int32_p]
+            f("initializer_hypotheses").restype = C.c_int
+            f("initializer_destroy").argtypes = [vp]; f("initializer_destroy").restype = None
+            f("initializer_find").argtypes = [vp, c_float_p, C.c_int32, c_float_p, C.c_int32, c_float_p, C.c_int32, c_int32_p,
+                                              C.POINTER(InitializerParams), C.POINTER(InitializerResult)]
+            f("initializer_find").restype = C.c_int
 
 
 _PRODUCT = None

@@ -1,4 +1,4 @@
-// lld_ransac.h — device pieces shared by the RANSAC solvers (lld_pnp.hip, lld_sim3solver.hip): one glibc rand() stream per
+// lld_ransac.h — device pieces shared by the RANSAC solvers (lld_pnp.hip, lld_sim3solver.hip, lld_initializer.hip): one glibc rand() stream per
 // solver (DEVIATION 1 of both sections of include/lld_amd.h), the cyclic Jacobi eigensolver and the canonical eigenvector sign.
 // Everything is in an anonymous namespace (one copy per including file) and compiled without FMA contraction.
 #ifndef LLD_RANSAC_H
@@ -26,7 +26,7 @@ __device__ __host__ inline uint32_t rng_next(uint32_t* ring, int32_t& head) {
 }
 
 // RandomInt(0, d - 1) (Thirdparty/DBoW2/DUtils/Random.cpp:47-50): int((double)rand() / (RAND_MAX + 1.0) * d)
-__device__ inline int random_int(uint32_t* ring, int32_t& head, int d) {
+__device__ __host__ inline int random_int(uint32_t* ring, int32_t& head, int d) {
   uint32_t r = rng_next(ring, head) >> 1;
   return int(((double)r / ((double)2147483647 + 1.0)) * (double)d);
 }

@@ -1,0 +1,552 @@
+"""Independent restatement of ORB-SLAM2's Initializer (src/Initializer.cc) with the two deviations of include/lld_amd.h: a fresh
+glibc TYPE_3 rand() stream per Initialize call, and the numerics OpenCV would decide (products summed in double in index order,
+null vectors and 3x3 SVDs through a cyclic Jacobi on A^T A with canonical signs, cofactor inverse and determinant).  Written from
+Initializer.cc and the header text; imports nothing from lld_slam_amd.  The stream comes from tests/pnp_ref.py.
+
+Everything is numpy element-wise arithmetic, batched over hypotheses or matches: a float value lives in a float32 array, a float
+operation is one float32 operation, a double operation one float64 operation, in the order the header states (numpy never fuses
+a multiply and an add).  The Jacobi is the scalar one of pnp_ref.py run on a batch, each matrix following its own convergence.
+
+Also: a seeded two-view scene generator with the variants general / planar / rotation / exact / wrong / collapsed."""
+from __future__ import annotations
+
+import numpy as np
+
+from pnp_ref import GlibcRand, JACOBI_SWEEPS, JACOBI_TOL
+
+F32 = np.float32
+F64 = np.float64
+SVD_CUT = 1e-9
+DEFAULT_PARAMS = dict(sigma=1.0, iterations=200, min_parallax=1.0, min_triangulated=50, seed=0)
+
+
+def _quiet(fn):
+    def wrapped(*a, **k):
+        with np.errstate(all="ignore"):
+            return fn(*a, **k)
+    return wrapped
+
+
+# ------------------------------------------------------------------ batched small linear algebra
+@_quiet
+def jacobi_batch(A):
+    """Cyclic Jacobi on a batch (B, n, n) of symmetric float64 matrices, in place: (eigenvalues (B, n), V (B, n, n))."""
+    B, n, _ = A.shape
+    V = np.zeros((B, n, n)); V[:, np.arange(n), np.arange(n)] = 1.0
+    live = np.ones(B, bool)
+    for _ in range(JACOBI_SWEEPS):
+        off = np.zeros(B); dg = np.zeros(B)
+        for p in range(n):
+            dg = dg + A[:, p, p] * A[:, p, p]
+            for q in range(p + 1, n):
+                off = off + A[:, p, q] * A[:, p, q]
+        live = live & ~(off <= JACOBI_TOL * dg)
+        if not live.any():
+            break
+        for p in range(n - 1):
+            for q in range(p + 1, n):
+                apq = A[:, p, q].copy()
+                m = live & (apq != 0.0)
+                if not m.any():
+                    continue
+                theta = (A[:, q, q] - A[:, p, p]) / (2.0 * apq)
+                t = 1.0 / (np.abs(theta) + np.sqrt(theta * theta + 1.0))
+                t = np.where(theta < 0.0, -t, t)
+                c = 1.0 / np.sqrt(t * t + 1.0)
+                s = t * c
+                c1, s1, m1 = c[:, None], s[:, None], m[:, None]
+                akp = A[:, :, p].copy(); akq = A[:, :, q].copy()
+                A[:, :, p] = np.where(m1, c1 * akp - s1 * akq, akp)
+                A[:, :, q] = np.where(m1, s1 * akp + c1 * akq, akq)
+                apk = A[:, p, :].copy(); aqk = A[:, q, :].copy()
+                A[:, p, :] = np.where(m1, c1 * apk - s1 * aqk, apk)
+                A[:, q, :] = np.where(m1, s1 * apk + c1 * aqk, aqk)
+                A[:, p, q] = np.where(m, 0.0, A[:, p, q])
+                A[:, q, p] = np.where(m, 0.0, A[:, q, p])
+                vkp = V[:, :, p].copy(); vkq = V[:, :, q].copy()
+                V[:, :, p] = np.where(m1, c1 * vkp - s1 * vkq, vkp)
+                V[:, :, q] = np.where(m1, s1 * vkp + c1 * vkq, vkq)
+    return A[:, np.arange(n), np.arange(n)].copy(), V
+
+
+def canonical_batch(col):
+    """Sign of each vector (B, n) fixed: its first largest-magnitude component positive."""
+    B, n = col.shape
+    ar = np.arange(B)
+    m = np.zeros(B, np.int64)
+    for k in range(1, n):
+        m = np.where(np.abs(col[:, k]) > np.abs(col[ar, m]), k, m)
+    neg = col[ar, m] < 0.0
+    return np.where(neg[:, None], -col, col)
+
+
+@_quiet
+def ata_batch(A):
+    """A^T A of a batch (B, m, n) of float32 matrices, in double: each entry summed over the rows in order from 0.0."""
+    Ad = A.astype(F64)
+    B, m, n = Ad.shape
+    out = np.zeros((B, n, n))
+    for a in range(n):
+        for b in range(a, n):
+            s = np.zeros(B)
+            for k in range(m):
+                s = s + Ad[:, k, a] * Ad[:, k, b]
+            out[:, a, b] = s; out[:, b, a] = s
+    return out
+
+
+def null_vector_batch(A):
+    """The null vector of each (m x n) float32 system: eigenvector of A^T A's smallest eigenvalue (the highest index on a tie),
+    canonical sign, rounded to float.  (B, n) float32."""
+    lam, V = jacobi_batch(ata_batch(A))
+    B, n = lam.shape
+    ar = np.arange(B)
+    e = np.zeros(B, np.int64)
+    for k in range(1, n):
+        e = np.where(lam[:, k] <= lam[ar, e], k, e)
+    with np.errstate(all="ignore"):
+        return canonical_batch(V[ar, :, e]).astype(F32)
+
+
+@_quiet
+def mm(A, B):
+    """Float matrix product (batched over leading axes): the products summed in double in index order from the first, rounded to
+    float once.  A 1-D B is a column."""
+    A = np.asarray(A, F32).astype(F64); B = np.asarray(B, F32).astype(F64)
+    vec = B.ndim == 1
+    if vec:
+        B = B[:, None]
+    s = A[..., :, 0, None] * B[..., None, 0, :]
+    for k in range(1, A.shape[-1]):
+        s = s + A[..., :, k, None] * B[..., None, k, :]
+    s = s.astype(F32)
+    return s[..., 0] if vec else s
+
+
+@_quiet
+def det3(A):
+    a = np.asarray(A, F32).astype(F64)
+    a0, a1, a2, a3, a4, a5, a6, a7, a8 = (a[..., i, j] for i in range(3) for j in range(3))
+    return (a0 * (a4 * a8 - a5 * a7) - a1 * (a3 * a8 - a5 * a6)) + a2 * (a3 * a7 - a4 * a6)
+
+
+@_quiet
+def inv3(A):
+    """Mat::inv of float 3x3 matrices: cofactors times 1/det in double, rounded; det == 0 gives zeros."""
+    a = np.asarray(A, F32).astype(F64)
+    a0, a1, a2, a3, a4, a5, a6, a7, a8 = (a[..., i, j] for i in range(3) for j in range(3))
+    det = det3(A)
+    d = 1.0 / det
+    cof = [(a4 * a8 - a5 * a7), (a2 * a7 - a1 * a8), (a1 * a5 - a2 * a4), (a5 * a6 - a3 * a8), (a0 * a8 - a2 * a6),
+           (a2 * a3 - a0 * a5), (a3 * a7 - a4 * a6), (a1 * a6 - a0 * a7), (a0 * a4 - a1 * a3)]
+    out = np.stack([(c * d).astype(F32) for c in cof], -1)
+    out = np.where((det == 0.0)[..., None], F32(0.0), out)
+    return out.reshape(a.shape).astype(F32)
+
+
+@_quiet
+def norm3(v):
+    v = np.asarray(v, F32).astype(F64)
+    return np.sqrt((v[..., 0] * v[..., 0] + v[..., 1] * v[..., 1]) + v[..., 2] * v[..., 2])
+
+
+@_quiet
+def unit3(v):
+    r = 1.0 / norm3(v)
+    return (np.asarray(v, F32).astype(F64) * r[..., None]).astype(F32)
+
+
+@_quiet
+def svd3(A):
+    """Full SVD of a batch (B, 3, 3) of float matrices by the header's rule: (U, w, Vt) as float32, w descending."""
+    A = np.asarray(A, F32)
+    Ad = A.astype(F64)
+    B = len(A)
+    ar = np.arange(B)
+    lam, V = jacobi_batch(ata_batch(A))
+    o0 = np.zeros(B, np.int64)
+    for k in (1, 2):
+        o0 = np.where(lam[:, k] > lam[ar, o0], k, o0)
+    o2 = np.full(B, -1, np.int64)
+    for k in range(3):
+        cond = (o0 != k) & ((o2 < 0) | (lam[:, k] <= lam[ar, np.maximum(o2, 0)]))
+        o2 = np.where(cond, k, o2)
+    o1 = 3 - o0 - o2
+    v, u, wd = [], [], []
+    for c in (o0, o1, o2):
+        vk = canonical_batch(V[ar, :, c])
+        uk = np.stack([(Ad[:, i, 0] * vk[:, 0] + Ad[:, i, 1] * vk[:, 1]) + Ad[:, i, 2] * vk[:, 2] for i in range(3)], 1)
+        v.append(vk); u.append(uk)
+        wd.append(np.sqrt((uk[:, 0] * uk[:, 0] + uk[:, 1] * uk[:, 1]) + uk[:, 2] * uk[:, 2]))
+    e0 = np.zeros((B, 3)); e0[:, 0] = 1.0
+    u0 = np.where((wd[0] > 0.0)[:, None], u[0] / wd[0][:, None], e0)
+    b = np.abs(u0)
+    m = np.where(b[:, 1] < b[:, 0], np.where(b[:, 2] < b[:, 1], 2, 1), np.where(b[:, 2] < b[:, 0], 2, 0))
+    um = u0[ar, m]
+    p = (np.arange(3)[None, :] == m[:, None]).astype(F64) - um[:, None] * u0
+    pn = np.sqrt((p[:, 0] * p[:, 0] + p[:, 1] * p[:, 1]) + p[:, 2] * p[:, 2])
+    u1 = np.where((wd[1] > SVD_CUT * wd[0])[:, None], u[1] / wd[1][:, None], p / pn[:, None])
+    cr = np.stack([u0[:, 1] * u1[:, 2] - u0[:, 2] * u1[:, 1], u0[:, 2] * u1[:, 0] - u0[:, 0] * u1[:, 2],
+                   u0[:, 0] * u1[:, 1] - u0[:, 1] * u1[:, 0]], 1)
+    u2 = np.where((wd[2] > SVD_CUT * wd[0])[:, None], u[2] / wd[2][:, None], cr)
+    U = np.stack([u0, u1, u2], 2).astype(F32)                                   # columns
+    Vt = np.stack(v, 1).astype(F32)                                             # rows
+    return U, np.stack(wd, 1).astype(F32), Vt
+
+
+# ------------------------------------------------------------------ Initializer.cc
+def normalize(keys):
+    """Normalize (:749-795) over all keypoints: (normalized points, T).  Sequential float sums."""
+    keys = np.asarray(keys, F32)
+    n = len(keys)
+    acc = lambda x: np.add.accumulate(x, dtype=F32)[-1]
+    with np.errstate(all="ignore"):
+        meanX = acc(keys[:, 0]) / F32(n); meanY = acc(keys[:, 1]) / F32(n)
+        px = keys[:, 0] - meanX; py = keys[:, 1] - meanY
+        devX = acc(np.abs(px)) / F32(n); devY = acc(np.abs(py)) / F32(n)
+        sX = F32(1.0 / F64(devX)); sY = F32(1.0 / F64(devY))
+        pts = np.stack([px * sX, py * sY], 1).astype(F32)
+        T = np.array([[sX, 0, -meanX * sX], [0, sY, -meanY * sY], [0, 0, 1]], F32)
+    return pts, T
+
+
+def build_sets(N, iterations, seed):
+    """mvSets (:78-97) from a fresh stream after srand(seed)."""
+    rng = GlibcRand(seed)
+    sets = np.zeros((iterations, 8), np.int64)
+    for it in range(iterations):
+        avail = list(range(N))
+        for j in range(8):
+            r = rng.random_int(0, len(avail) - 1)
+            sets[it, j] = avail[r]
+            avail[r] = avail[-1]
+            avail.pop()
+    return sets
+
+
+@_quiet
+def compute_H21(P1, P2):
+    """ComputeH21 (:226-266) on a batch: P1, P2 (B, 8, 2) float32 -> Hn (B, 3, 3)."""
+    B = len(P1)
+    u1, v1, u2, v2 = P1[..., 0], P1[..., 1], P2[..., 0], P2[..., 1]
+    z = np.zeros_like(u1); one = np.ones_like(u1)
+    r0 = np.stack([z, z, z, -u1, -v1, -one, v2 * u1, v2 * v1, v2], -1)
+    r1 = np.stack([u1, v1, one, z, z, z, -u2 * u1, -u2 * v1, -u2], -1)
+    A = np.stack([r0, r1], 2).reshape(B, 16, 9).astype(F32)
+    return null_vector_batch(A).reshape(B, 3, 3)
+
+
+@_quiet
+def compute_F21(P1, P2):
+    """ComputeF21 (:268-303) on a batch -> Fn (B, 3, 3)."""
+    B = len(P1)
+    u1, v1, u2, v2 = P1[..., 0], P1[..., 1], P2[..., 0], P2[..., 1]
+    A = np.stack([u2 * u1, u2 * v1, u2, v2 * u1, v2 * v1, v2, u1, v1, np.ones_like(u1)], -1).astype(F32)
+    Fpre = null_vector_batch(A).reshape(B, 3, 3)
+    U, w, Vt = svd3(Fpre)
+    w[:, 2] = 0.0
+    return mm(U * w[:, None, :], Vt)
+
+
+@_quiet
+def inv_sigma2(sigma):
+    return F32(1.0 / F64(F32(sigma) * F32(sigma)))
+
+
+@_quiet
+def check_homography(H21, H12, k1, k2, sigma):
+    """CheckHomography (:305-388): (score, inlier mask, chi1, chi2)."""
+    h, hi = np.asarray(H21, F32).reshape(9), np.asarray(H12, F32).reshape(9)
+    u1, v1, u2, v2 = k1[:, 0], k1[:, 1], k2[:, 0], k2[:, 1]
+    th = F32(5.991); iS = inv_sigma2(sigma)
+    w = (1.0 / (hi[6] * u2 + hi[7] * v2 + hi[8]).astype(F64)).astype(F32)
+    a = (hi[0] * u2 + hi[1] * v2 + hi[2]) * w
+    b = (hi[3] * u2 + hi[4] * v2 + hi[5]) * w
+    chi1 = ((u1 - a) * (u1 - a) + (v1 - b) * (v1 - b)) * iS
+    w = (1.0 / (h[6] * u1 + h[7] * v1 + h[8]).astype(F64)).astype(F32)
+    a = (h[0] * u1 + h[1] * v1 + h[2]) * w
+    b = (h[3] * u1 + h[4] * v1 + h[5]) * w
+    chi2 = ((u2 - a) * (u2 - a) + (v2 - b) * (v2 - b)) * iS
+    return _score(chi1, chi2, th, th)
+
+
+@_quiet
+def check_fundamental(F21, k1, k2, sigma):
+    """CheckFundamental (:390-468): (score, inlier mask, chi1, chi2)."""
+    f = np.asarray(F21, F32).reshape(9)
+    u1, v1, u2, v2 = k1[:, 0], k1[:, 1], k2[:, 0], k2[:, 1]
+    iS = inv_sigma2(sigma)
+    a2 = f[0] * u1 + f[1] * v1 + f[2]; b2 = f[3] * u1 + f[4] * v1 + f[5]; c2 = f[6] * u1 + f[7] * v1 + f[8]
+    num2 = a2 * u2 + b2 * v2 + c2
+    chi1 = (num2 * num2 / (a2 * a2 + b2 * b2)) * iS
+    a1 = f[0] * u2 + f[3] * v2 + f[6]; b1 = f[1] * u2 + f[4] * v2 + f[7]; c1 = f[2] * u2 + f[5] * v2 + f[8]
+    num1 = a1 * u1 + b1 * v1 + c1
+    chi2 = (num1 * num1 / (a1 * a1 + b1 * b1)) * iS
+    return _score(chi1, chi2, F32(3.841), F32(5.991))
+
+
+def _score(chi1, chi2, th, th_score):
+    out1 = chi1 > th; out2 = chi2 > th
+    terms = np.empty(2 * len(chi1), F32)
+    terms[0::2] = np.where(out1, F32(0.0), th_score - chi1)                    # a failed side adds nothing (+0 here)
+    terms[1::2] = np.where(out2, F32(0.0), th_score - chi2)
+    score = np.add.accumulate(terms, dtype=F32)[-1] if len(terms) else F32(0.0)   # the sequential float sum in match order
+    return F32(score), ~out1 & ~out2, chi1.astype(F32), chi2.astype(F32)
+
+
+@_quiet
+def check_rt(R, t, K, k1, k2, inl, sigma):
+    """CheckRT (:798-907) over the matches: dict(n_good, parallax, counted, good, p3d, cos) with per-match arrays."""
+    K = np.asarray(K, F32).reshape(3, 3)
+    fx, fy, cx, cy = K[0, 0], K[1, 1], K[0, 2], K[1, 2]
+    N = len(k1)
+    P1 = np.concatenate([K, np.zeros((3, 1), F32)], 1)
+    P2 = mm(K, np.concatenate([np.asarray(R, F32), np.asarray(t, F32)[:, None]], 1))
+    O2 = -mm(np.asarray(R, F32).T, t)
+    x1, y1, x2, y2 = (c[:, None] for c in (k1[:, 0], k1[:, 1], k2[:, 0], k2[:, 1]))
+    A = np.stack([x1 * P1[2] - P1[0], y1 * P1[2] - P1[1], x2 * P2[2] - P2[0], y2 * P2[2] - P2[1]], 1).astype(F32)
+    x = null_vector_batch(A)
+    inv = 1.0 / x[:, 3].astype(F64)
+    p = (x[:, :3].astype(F64) * inv[:, None]).astype(F32)
+    ok = inl & np.isfinite(p).all(1)
+    dist1 = norm3(p).astype(F32)
+    n2 = (p - O2).astype(F32)
+    dist2 = norm3(n2).astype(F32)
+    pd, nd = p.astype(F64), n2.astype(F64)
+    dot = pd[:, 0] * nd[:, 0]
+    dot = dot + pd[:, 1] * nd[:, 1]
+    dot = dot + pd[:, 2] * nd[:, 2]
+    cosp = (dot / (dist1 * dist2).astype(F64)).astype(F32)
+    low = cosp.astype(F64) < 0.99998
+    ok &= ~((p[:, 2] <= 0) & low)
+    p2 = (mm(np.asarray(R, F32)[None], p[:, :, None])[:, :, 0] + np.asarray(t, F32)).astype(F32)
+    ok &= ~((p2[:, 2] <= 0) & low)
+    th2 = F32(4.0 * F64(F32(sigma) * F32(sigma)))
+    iz1 = (1.0 / p[:, 2].astype(F64)).astype(F32)
+    im1x = fx * p[:, 0] * iz1 + cx; im1y = fy * p[:, 1] * iz1 + cy
+    e1 = (im1x - k1[:, 0]) * (im1x - k1[:, 0]) + (im1y - k1[:, 1]) * (im1y - k1[:, 1])
+    ok &= ~(e1 > th2)
+    iz2 = (1.0 / p2[:, 2].astype(F64)).astype(F32)
+    im2x = fx * p2[:, 0] * iz2 + cx; im2y = fy * p2[:, 1] * iz2 + cy
+    e2 = (im2x - k2[:, 0]) * (im2x - k2[:, 0]) + (im2y - k2[:, 1]) * (im2y - k2[:, 1])
+    ok &= ~(e2 > th2)
+    n_good = int(ok.sum())
+    parallax = F32(0.0)
+    if n_good > 0:
+        srt = np.sort(cosp[ok])
+        parallax = F32(np.arccos(F64(srt[min(50, n_good - 1)])) * 180 / 3.1415926535897932384626433832795)
+    return dict(n_good=n_good, parallax=parallax, counted=ok, good=ok & low, p3d=p, cos=cosp, e1=e1, e2=e2, th2=th2)
+
+
+def decompose_E(E):
+    """DecomposeE (:909-929): (R1, R2, t)."""
+    U, w, Vt = svd3(np.asarray(E, F32)[None])
+    U, Vt = U[0], Vt[0]
+    t = unit3(U[:, 2])
+    W = np.array([[0, -1, 0], [1, 0, 0], [0, 0, 1]], F32)
+    R1 = mm(mm(U, W), Vt)
+    if det3(R1) < 0:
+        R1 = -R1
+    R2 = mm(mm(U, W.T), Vt)
+    if det3(R2) < 0:
+        R2 = -R2
+    return R1, R2, t
+
+
+@_quiet
+def motions_H(H21, K):
+    """The eight Faugeras hypotheses of ReconstructH (:584-686), or [] on the d1/d2, d2/d3 exit."""
+    K = np.asarray(K, F32).reshape(3, 3)
+    A = mm(mm(inv3(K), H21), K)
+    U, w, Vt = svd3(A[None])
+    U, w, Vt = U[0], w[0], Vt[0]
+    s = F32(det3(U) * det3(Vt))
+    d1, d2, d3 = w
+    if F64(d1 / d2) < 1.00001 or F64(d2 / d3) < 1.00001:
+        return []
+    sq = lambda x: F32(np.sqrt(F64(x)))
+    aux1 = sq((d1 * d1 - d2 * d2) / (d1 * d1 - d3 * d3))
+    aux3 = sq((d2 * d2 - d3 * d3) / (d1 * d1 - d3 * d3))
+    x1 = [aux1, aux1, -aux1, -aux1]
+    x3 = [aux3, -aux3, aux3, -aux3]
+    rad = sq((d1 * d1 - d2 * d2) * (d2 * d2 - d3 * d3))
+    aux_st = rad / ((d1 + d3) * d2)
+    ct = (d2 * d2 + d1 * d3) / ((d1 + d3) * d2)
+    st = [aux_st, -aux_st, -aux_st, aux_st]
+    aux_sp = rad / ((d1 - d3) * d2)
+    cp = (d1 * d3 - d2 * d2) / ((d1 - d3) * d2)
+    sp = [aux_sp, -aux_sp, -aux_sp, aux_sp]
+    sU = (s * U).astype(F32)
+    out = []
+    for i in range(4):
+        Rp = np.eye(3, dtype=F32)
+        Rp[0, 0] = ct; Rp[0, 2] = -st[i]; Rp[2, 0] = st[i]; Rp[2, 2] = ct
+        R = mm(mm(sU, Rp), Vt)
+        tp = np.array([x1[i], 0, -x3[i]], F32) * (d1 - d3)
+        out.append((R, unit3(mm(U, tp))))
+    for i in range(4):
+        Rp = np.eye(3, dtype=F32)
+        Rp[0, 0] = cp; Rp[0, 2] = sp[i]; Rp[1, 1] = -1; Rp[2, 0] = sp[i]; Rp[2, 2] = -cp
+        R = mm(mm(sU, Rp), Vt)
+        tp = np.array([x1[i], 0, x3[i]], F32) * (d1 + d3)
+        out.append((R, unit3(mm(U, tp))))
+    return out
+
+
+class InitializerRef:
+    """Initializer(ReferenceFrame, sigma, iterations).  initialize() returns a dict shaped like lld_initializer_result and keeps
+    the hypotheses of the call in hyps_H / hyps_F (dicts idx, M, score, n_inliers) and the CheckRT records in rt."""
+
+    def __init__(self, K, keys1, sigma=1.0, iterations=200, min_parallax=1.0, min_triangulated=50, seed=0):
+        self.K = np.asarray(K, F32).reshape(3, 3)
+        self.keys1 = np.asarray(keys1, F32).reshape(-1, 2)
+        self.sigma, self.iterations = sigma, iterations
+        self.min_parallax, self.min_triangulated, self.seed = F32(min_parallax), min_triangulated, seed
+
+    @_quiet
+    def initialize(self, keys2, matches12):
+        keys2 = np.asarray(keys2, F32).reshape(-1, 2)
+        matches12 = np.asarray(matches12)
+        first = np.flatnonzero(matches12 >= 0)                                  # mvMatches12, index order
+        second = matches12[first]
+        N = len(first)
+        n1 = len(self.keys1)
+        self.sets = build_sets(N, self.iterations, self.seed)
+        pn1, T1 = normalize(self.keys1)
+        pn2, T2 = normalize(keys2)
+        self.k1, self.k2 = self.keys1[first], keys2[second]
+        P1 = pn1[first[self.sets]]; P2 = pn2[second[self.sets]]
+        B = self.iterations
+        Hn = compute_H21(P1, P2)
+        H21 = mm(mm(np.broadcast_to(inv3(T2), (B, 3, 3)), Hn), np.broadcast_to(T1, (B, 3, 3)))
+        H12 = inv3(H21)
+        Fn = compute_F21(P1, P2)
+        F21 = mm(mm(np.broadcast_to(T2.T, (B, 3, 3)), Fn), np.broadcast_to(T1, (B, 3, 3)))
+        self.hyps_H, self.hyps_F = [], []
+        out = dict(success=False, model=1, H21=np.zeros((3, 3), F32), F21=np.zeros((3, 3), F32), n_inliers_H=0, n_inliers_F=0,
+                   R21=np.zeros((3, 3), F32), t21=np.zeros(3, F32), n_good=np.zeros(8, np.int32), parallax=np.zeros(8, F32),
+                   best_index=-1, n_matches=N, win_H=-1, win_F=-1, inlier_H=np.zeros(N, np.uint8), inlier_F=np.zeros(N, np.uint8),
+                   p3d=np.zeros((n1, 3), F32), triangulated=np.zeros(n1, np.uint8))
+        SH = F32(0.0); SF = F32(0.0)
+        for it in range(B):
+            s, mask, _, _ = check_homography(H21[it], H12[it], self.k1, self.k2, self.sigma)
+            self.hyps_H.append(dict(idx=list(self.sets[it]), M=H21[it], Minv=H12[it], score=s, n_inliers=int(mask.sum())))
+            if s > SH:
+                SH = s; out.update(win_H=it, H21=H21[it], n_inliers_H=int(mask.sum()), inlier_H=mask.astype(np.uint8))
+        for it in range(B):
+            s, mask, _, _ = check_fundamental(F21[it], self.k1, self.k2, self.sigma)
+            self.hyps_F.append(dict(idx=list(self.sets[it]), M=F21[it], score=s, n_inliers=int(mask.sum())))
+            if s > SF:
+                SF = s; out.update(win_F=it, F21=F21[it], n_inliers_F=int(mask.sum()), inlier_F=mask.astype(np.uint8))
+        RH = F32(SH / (SH + SF))
+        out.update(SH=SH, SF=SF, RH=RH, model=0 if F64(RH) > 0.40 else 1)
+        self.rt = []
+        if out["model"] == 0 and out["win_H"] >= 0:
+            motions = motions_H(out["H21"], self.K)
+            inl, Nin = out["inlier_H"].astype(bool), out["n_inliers_H"]
+        elif out["model"] == 1 and out["win_F"] >= 0:
+            R1, R2, t = decompose_E(mm(mm(self.K.T, out["F21"]), self.K))
+            motions = [(R1, t), (R2, t), (R1, -t), (R2, -t)]
+            inl, Nin = out["inlier_F"].astype(bool), out["n_inliers_F"]
+        else:
+            motions = []
+        self.motions = motions
+        if not motions:
+            return out
+        for h, (R, t) in enumerate(motions):
+            r = check_rt(R, t, self.K, self.k1, self.k2, inl, self.sigma)
+            self.rt.append(r)
+            out["n_good"][h] = r["n_good"]; out["parallax"][h] = r["parallax"]
+        g, par = [int(x) for x in out["n_good"]], out["parallax"]
+        ok, best = False, -1
+        if out["model"] == 1:                                                   # ReconstructF (:499-569)
+            maxGood = max(g[:4])
+            nMinGood = max(int(0.9 * Nin), self.min_triangulated)
+            nsimilar = sum(1 for x in g[:4] if x > 0.7 * maxGood)
+            if not (maxGood < nMinGood or nsimilar > 1):
+                best = g[:4].index(maxGood)
+                ok = bool(par[best] > self.min_parallax)
+        else:                                                                   # ReconstructH (:689-731)
+            bestGood = second = 0; bestPar = F32(-1.0)
+            for i in range(8):
+                if g[i] > bestGood:
+                    second = bestGood; bestGood = g[i]; best = i; bestPar = par[i]
+                elif g[i] > second:
+                    second = g[i]
+            ok = bool(second < 0.75 * bestGood and bestPar >= self.min_parallax and bestGood > self.min_triangulated
+                      and bestGood > 0.9 * Nin)
+        out.update(success=ok, best_index=best)
+        if ok:
+            r = self.rt[best]
+            out["R21"], out["t21"] = motions[best]
+            out["p3d"][first[r["counted"]]] = r["p3d"][r["counted"]]
+            out["triangulated"][first[r["good"]]] = 1
+        return out
+
+
+# ------------------------------------------------------------------ scenes
+CAM = dict(fx=718.856, fy=718.856, cx=607.1928, cy=185.2157, w=1241, h=376)
+
+
+def _rot(w):
+    th = np.linalg.norm(w)
+    if th == 0:
+        return np.eye(3)
+    k = w / th
+    Kx = np.array([[0, -k[2], k[1]], [k[2], 0, -k[0]], [-k[1], k[0], 0]])
+    return np.eye(3) + np.sin(th) * Kx + (1 - np.cos(th)) * Kx @ Kx
+
+
+def make_scene(seed, n, inlier_ratio=0.9, noise=0.2, variant="general", extra=0.25):
+    """Two monocular views with n matches.  Camera 1 at the origin, X2 = R21 X1 + t21.  Variants: 'general' (depths 4..30 m, F
+    wins), 'planar' (one slanted plane, H wins), 'rotation' (t21 = 0: no parallax), 'exact' (general, no noise, no outliers),
+    'wrong' (every match joins unrelated points), 'collapsed' (every keypoint of frame 2 at one pixel: Normalize's deviation is
+    0, its scale inf, every hypothesis and score NaN, so neither model has a winner).  `extra`: unmatched keypoints per frame as a fraction of n (they take part in
+    Normalize); keys2 is shuffled.  Returns K, keys1, keys2, matches12, the truth R21 / t21 / X1 and the outlier flags."""
+    rng = np.random.default_rng(seed)
+    c = CAM
+    K = np.array([[c["fx"], 0, c["cx"]], [0, c["fy"], c["cy"]], [0, 0, 1]])
+    u = rng.uniform(40, c["w"] - 40, n); v = rng.uniform(20, c["h"] - 20, n)
+    ray = np.stack([(u - c["cx"]) / c["fx"], (v - c["cy"]) / c["fy"], np.ones(n)], 1)
+    if variant == "planar":
+        nrm = np.array([0.8, 0.3, -1.0]); nrm /= np.linalg.norm(nrm)
+        depth = (-8.0 / (ray @ nrm))
+    else:
+        depth = rng.uniform(4.0, 30.0, n)
+    X1 = ray * depth[:, None]
+    R21 = _rot(np.array([0.01, 0.06, -0.015]) + rng.normal(0, 0.005, 3))
+    t21 = np.zeros(3) if variant == "rotation" else np.array([-1.2, 0.08, 0.25]) + rng.normal(0, 0.03, 3)
+    X2 = X1 @ R21.T + t21
+    p2 = (X2 / X2[:, 2:3]) @ K.T
+    k1 = np.stack([u, v], 1)
+    k2 = p2[:, :2].copy()
+    out = np.zeros(n, bool)
+    if variant == "wrong":
+        out[:] = True
+    elif variant != "exact":
+        k1 += rng.normal(0, noise, (n, 2)); k2 += rng.normal(0, noise, (n, 2))
+        out = rng.random(n) >= inlier_ratio
+    k2[out] = np.stack([rng.uniform(0, c["w"], out.sum()), rng.uniform(0, c["h"], out.sum())], 1)
+    if variant == "collapsed":
+        k2[:] = (320.5, 177.25)
+    ne = int(extra * n)
+    e1 = np.stack([rng.uniform(0, c["w"], ne), rng.uniform(0, c["h"], ne)], 1)
+    e2 = np.stack([rng.uniform(0, c["w"], ne), rng.uniform(0, c["h"], ne)], 1)
+    if variant == "collapsed":
+        e2[:] = (320.5, 177.25)
+    n1 = n + ne
+    pos1 = rng.permutation(n1)                                                 # where each of [matched | extra] lands in frame 1
+    pos2 = rng.permutation(n1)
+    keys1 = np.zeros((n1, 2)); keys1[pos1] = np.concatenate([k1, e1])
+    keys2 = np.zeros((n1, 2)); keys2[pos2] = np.concatenate([k2, e2])
+    matches = np.full(n1, -1, np.int32)
+    matches[pos1[:n]] = pos2[:n]
+    X1_by_key = np.zeros((n1, 3)); X1_by_key[pos1[:n]] = X1
+    out_by_key = np.ones(n1, bool); out_by_key[pos1[:n]] = out
+    return dict(K=K.astype(F32), keys1=keys1.astype(F32), keys2=keys2.astype(F32), matches12=matches, R21=R21, t21=t21,
+                X1=X1_by_key, outlier=out_by_key, seed=int(rng.integers(0, 1 << 31)))
+
+
+def ref_from_scene(sc, **kw):
+    p = dict(DEFAULT_PARAMS); p["seed"] = sc["seed"]; p.update(kw)
+    return InitializerRef(sc["K"], sc["keys1"], **p)
