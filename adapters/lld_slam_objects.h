@@ -107,6 +107,7 @@ class KeyFrame {
   // what the matchers read (include/KeyFrame.h): keypoint descriptors, the image bounds and grid constants, the scale pyramid, the
   // pose pieces; and what ORBmatcher::Fuse writes
   MatU8 mDescriptors;
+  Mat mDescriptorsLines;                                           // one LBD descriptor (CV_32F row) per left line (KeyFrame.h)
   DBoW2::FeatureVector mFeatVec;                                   // vocabulary node -> keypoint indices (KeyFrame::ComputeBoW)
   int mnMinX = 0, mnMinY = 0, mnMaxX = 0, mnMaxY = 0;               // KeyFrame.h:196-199 (const int there)
   float mfGridElementWidthInv = 0, mfGridElementHeightInv = 0;
@@ -183,6 +184,7 @@ class MapPoint {
   unsigned long mnLastFrameSeen = 0;
 
   Mat mWorldPos;                                                   // 3x1 CV_32F
+  KeyFrame* mpRefKF = nullptr;                                     // MapPoint.h: the reference keyframe UpdateNormalAndDepth reads
   std::map<KeyFrame*, size_t> mObservations;                       // pointer-ordered, as in the reference
   bool mbBad = false;
   int n_set_pos = 0, n_update_normal = 0;
@@ -211,6 +213,7 @@ class MapLine {
   bool isBad() const { return mbBad; }
 
   Vector3d mX0, mDir;
+  Mat mDescriptor;                                                 // 1 x dim CV_32F (MapLine.h), written by ComputeDistinctiveDescriptors
   std::map<KeyFrame*, size_t> mObservations;
   bool mbBad = false;
   int n_set_pos = 0;

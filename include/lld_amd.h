@@ -1607,6 +1607,108 @@ void lld_initializer_destroy(lld_initializer* h);
 int  lld_initializer_find(lld_ctx* ctx, const float* K, int32_t n1, const float* keys1_xy, int32_t n2, const float* keys2_xy,
                           int32_t n12, const int32_t* matches12, const lld_initializer_params* params, lld_initializer_result* result);
 
+/* ---- Landmark refresh: MapPoint::ComputeDistinctiveDescriptors (src/MapPoint.cc:242-307), MapPoint::UpdateNormalAndDepth
+ * (src/MapPoint.cc:330-371) and MapLine::ComputeDistinctiveDescriptors (src/MapLine.cc:133-201) for a batch of landmarks.
+ * The reference runs them one object at a time in LocalMapping::ProcessNewKeyFrame / SearchInNeighbors (src/LocalMapping.cc:
+ * 141-162, :518-531), CreateNewMapPoints, at the end of every Local / GlobalBundleAdjustment and in LoopClosing::CorrectLoop /
+ * SearchAndFuse; what they write (mDescriptor, mNormalVector, mfMinDistance, mfMaxDistance) is what lld_orb_search_local_points
+ * and lld_frame_track_local_map read.  Each call makes one upload, queues its kernels on the context's stream with no host trip
+ * between them, makes one download and waits for the stream.
+ * Input: the observations of landmark i are entries obs_start[i] .. obs_start[i+1]-1 (CSR), LISTED IN THE ORDER IN WHICH THE
+ *   REFERENCE'S std::map<KeyFrame*,size_t> ITERATES (pointer order): that order decides ties and the float sum.  obs_kf[o] indexes a
+ *   keyframe table of n_kf entries (kf_ow = GetCameraCenter(), kf_bad = isBad()); obs_desc[o] is the row the caller gathered from
+ *   pKF->mDescriptors (pKF->mDescriptorsLines for lines).
+ * Descriptor rule (MapPoint.cc):
+ *   :251-252 mbBad returns; :256-257 no observations returns; :261-267 vDescriptors = the rows of the keyframes that are not bad,
+ *     in order; :269-270 none left returns.  Such a point is left alone: desc[i] keeps what the caller passed in, best_obs[i] =
+ *     best_median[i] = -1, bit 0 of updated[i] is clear.
+ *   :273-285 Distances[i][j] = DescriptorDistance of every pair (the popcount of the XOR of the 256 bits), diagonal 0.
+ *   :290-294 per row: the row sorted, median = element (size_t)(0.5*(N-1)), the diagonal zero included.  N = 1 and N = 2 give
+ *     index 0, i.e. median 0 and winner 0.  Computed here without a sort (the smallest v with count(d <= v) > index): equal.
+ *   :296-300 `median < BestMedian` from INT_MAX in row order: the first row with the strictly smallest median wins.
+ *   :305 mDescriptor = the winner's row.  best_obs[i] is the winner's position in the point's OWN observation list, bad keyframes
+ *     counted (so obs_start[i] + best_obs[i] is its entry); best_median[i] its median.
+ * Normal / depth rule (MapPoint.cc):
+ *   :338-339 mbBad returns; :345-346 no observations returns (bit 1 of updated[i] clear, outputs kept).  Bad keyframes are NOT
+ *     skipped: the reference does not test isBad() here, and n counts every observation.
+ *   :348-357 normal = 0; per observation in order: normali = mWorldPos - Owi (float subtraction), normal = normal +
+ *     normali/cv::norm(normali) (float additions in observation order).
+ *   :359-363 PC = Pos - Ow[ref_kf]; dist = (float)cv::norm(PC); level = ref_level[i], which the caller reads as
+ *     pRefKF->mvKeysUn[observations[pRefKF]].octave - observations[pRefKF] is std::map::operator[], so a reference keyframe that is
+ *     absent from the map yields keypoint 0 (the adapter reproduces this).
+ *   :367-369 mfMaxDistance = dist*level_scale[level]; mfMinDistance = mfMaxDistance/level_scale[n_levels-1] (float product and
+ *     quotient); mNormalVector = normal/n.
+ *   Numerics, as lld_orb_search_local_points states them for isInFrustum: float subtraction; cv::norm sums the squares in double in
+ *     index order and takes the double square root.  The one new choice is Mat / double (normali/norm, normal/n): OpenCV turns it
+ *     into convertTo with alpha = 1/s, whose CV_32F -> CV_32F path works in float, so x/s here is x * (float)(1.0/s): the double
+ *     reciprocal rounded to float, then one float product.  (Its `+ 0` shift is not performed: it could only turn a -0 into +0, and
+ *     the sum starts from +0.)  The device's double division, double square root and float division are correctly rounded, so
+ *     every output is bit for bit the restatement's.
+ *   DEVIATION (scales): one level_scale table serves all keyframes; the reference reads pRefKF->mvScaleFactors and
+ *     pRefKF->mnScaleLevels of each point's own reference keyframe (all equal in the reference's configurations: one extractor).
+ * Line rule (MapLine.cc:133-201): the same selection with obs_desc[n_obs][dim] in float (dim = 72 for LBD).
+ *   :175-177 distij = cv::norm(a - b) in the form lld_match_l2f32 fixes (float difference, squares summed in double in ascending
+ *     index order, double square root), then STORED AS FLOAT in Distances.
+ *   :186-188 QUIRK (int median): the row is sorted as floats, but the element is assigned to `int median`, so it is truncated
+ *     toward zero BEFORE the `median<BestMedian` test.  With unit-norm LBD rows almost every median truncates to 0 or 1 and the
+ *     first kept row wins.  best_median[i] is that int.  The sorted element is found by rank count, equal to sort-then-index for
+ *     finite distances; non-finite descriptors or a distance of 2^31 or more are outside the contract (std::sort and the
+ *     conversion are undefined there).
+ *   There is no normal / depth part for lines.  updated[i] is 1 when the descriptor was written.
+ * flags: LLD_LANDMARK_DESCRIPTOR, LLD_LANDMARK_NORMAL_DEPTH or both (LocalBundleAdjustment's tail and CorrectLoop want only the
+ *   second).  Inputs and outputs of the part not selected are neither read nor written and may be NULL; updated[] is always written.
+ * Limits: the reference's stack table `float Distances[N][N]` bounds N in practice (8 MiB of stack: N < 1449).  A point with more
+ *   than LLD_LANDMARK_MAX_OBS observations, a line with more than LLD_LANDMARK_MAX_LINE_OBS, or dim above
+ *   LLD_LANDMARK_MAX_LINE_DIM returns LLD_ERR_UNSUPPORTED before anything is queued.  LLD_ERR_INVALID, also before anything is
+ *   queued: a NULL required pointer; negative sizes; flags zero or with unknown bits; obs_start[0] != 0, obs_start not
+ *   non-decreasing or obs_start[n] != n_obs; an obs_kf outside [0, n_kf); with the normal part, n_levels outside
+ *   [1, LLD_ORB_MAX_LEVELS], or ref_kf outside [0, n_kf) / ref_level outside [0, n_levels) for a point the rule does not skip; dim
+ *   below 1.  n_points = 0 (n_lines = 0) is LLD_OK and touches nothing. */
+#define LLD_LANDMARK_MAX_OBS 1024          /* observations of one MapPoint                          */
+#define LLD_LANDMARK_MAX_LINE_OBS 64       /* observations of one MapLine                           */
+#define LLD_LANDMARK_MAX_LINE_DIM 128      /* floats of one line descriptor                         */
+#define LLD_LANDMARK_DESCRIPTOR   1u       /* flags / updated bit 0: ComputeDistinctiveDescriptors  */
+#define LLD_LANDMARK_NORMAL_DEPTH 2u       /* flags / updated bit 1: UpdateNormalAndDepth           */
+typedef struct {
+  int32_t n_points, n_obs, n_kf, n_levels;
+  uint32_t flags;
+  const int32_t*  obs_start;             /* [n_points+1]                                          */
+  const int32_t*  obs_kf;                /* [n_obs] index into the keyframe table                 */
+  const uint32_t* obs_desc;              /* [n_obs][8] pKF->mDescriptors.row(mit->second)         */
+  const float*    kf_ow;                 /* [n_kf][3] GetCameraCenter()                           */
+  const uint8_t*  kf_bad;                /* [n_kf] isBad()                                        */
+  const float*    pos;                   /* [n_points][3] mWorldPos                               */
+  const uint8_t*  bad;                   /* [n_points] mbBad                                      */
+  const int32_t*  ref_kf;                /* [n_points] mpRefKF in the keyframe table              */
+  const int32_t*  ref_level;             /* [n_points] pRefKF->mvKeysUn[observations[pRefKF]].octave */
+  const float*    level_scale;           /* [n_levels] mvScaleFactors                             */
+} lld_mappoint_refresh_in;
+typedef struct {                          /* in / out: an entry the rule leaves alone keeps its value */
+  uint32_t* desc;                        /* [n_points][8] mDescriptor                             */
+  int32_t*  best_obs;                    /* [n_points] BestIdx in the point's own list, or -1     */
+  int32_t*  best_median;                 /* [n_points] BestMedian, or -1                          */
+  float*    normal;                      /* [n_points][3] mNormalVector                           */
+  float*    min_distance;                /* [n_points] mfMinDistance                              */
+  float*    max_distance;                /* [n_points] mfMaxDistance                              */
+  uint8_t*  updated;                     /* [n_points] bit 0 descriptor, bit 1 normal / depth     */
+} lld_mappoint_refresh_out;
+int lld_mappoint_refresh(lld_ctx* ctx, const lld_mappoint_refresh_in* in, lld_mappoint_refresh_out* out);
+typedef struct {
+  int32_t n_lines, n_obs, n_kf, dim;
+  const int32_t* obs_start;              /* [n_lines+1]                                           */
+  const int32_t* obs_kf;                 /* [n_obs]                                               */
+  const float*   obs_desc;               /* [n_obs][dim] pKF->mDescriptorsLines.row(mit->second)  */
+  const uint8_t* kf_bad;                 /* [n_kf]                                                */
+  const uint8_t* bad;                    /* [n_lines] mbBad                                       */
+} lld_mapline_distinctive_in;
+typedef struct {
+  float*   desc;                         /* [n_lines][dim] mDescriptor                            */
+  int32_t* best_obs;                     /* [n_lines] or -1                                       */
+  int32_t* best_median;                  /* [n_lines] the int of the QUIRK, or -1                 */
+  uint8_t* updated;                      /* [n_lines] 1 when the descriptor was written           */
+} lld_mapline_distinctive_out;
+int lld_mapline_distinctive(lld_ctx* ctx, const lld_mapline_distinctive_in* in, lld_mapline_distinctive_out* out);
+
 #if defined(__GNUC__)
 #pragma GCC visibility pop
 #endif

@@ -889,5 +889,64 @@ class Initializer {
   InitializerOutput last_;
 };
 
+// ---- Landmark refresh (src/MapPoint.cc:242-307, :330-371; src/MapLine.cc:133-201) for a batch of landmarks in one call.
+// Observations in CSR form, in the order in which the reference's std::map<KeyFrame*,size_t> iterates.
+struct MapPointBatch {
+  std::vector<int32_t> obs_start;        // [n+1]
+  std::vector<int32_t> obs_kf;           // [n_obs] index into the keyframe table
+  std::vector<uint32_t> obs_desc;        // [8*n_obs]
+  std::vector<float> kf_ow;              // [3*n_kf]
+  std::vector<uint8_t> kf_bad;           // [n_kf]
+  std::vector<float> pos;                // [3*n]
+  std::vector<uint8_t> bad;              // [n]
+  std::vector<int32_t> ref_kf, ref_level;   // [n]
+  std::vector<float> level_scale;        // [n_levels]
+};
+// In / out: entries of a landmark the reference would leave alone keep their values.  Vectors that are too short are grown with zeros.
+struct MapPointRefreshOutput {
+  std::vector<uint32_t> desc;            // [8*n]
+  std::vector<int32_t> best_obs, best_median;
+  std::vector<float> normal, min_distance, max_distance;   // [3*n], [n], [n]
+  std::vector<uint8_t> updated;          // bit 0 descriptor, bit 1 normal / depth
+};
+inline void MapPointRefresh(const Context& ctx, const MapPointBatch& b, uint32_t flags, MapPointRefreshOutput& io) {
+  const size_t n = b.bad.size();
+  lld_mappoint_refresh_in in = lld_mappoint_refresh_in();
+  in.n_points = (int32_t)n; in.n_obs = (int32_t)b.obs_kf.size(); in.n_kf = (int32_t)b.kf_bad.size();
+  in.n_levels = (int32_t)b.level_scale.size(); in.flags = flags;
+  in.obs_start = b.obs_start.data(); in.obs_kf = b.obs_kf.data(); in.obs_desc = b.obs_desc.data(); in.kf_ow = b.kf_ow.data();
+  in.kf_bad = b.kf_bad.data(); in.pos = b.pos.data(); in.bad = b.bad.data(); in.ref_kf = b.ref_kf.data();
+  in.ref_level = b.ref_level.data(); in.level_scale = b.level_scale.data();
+  io.desc.resize(8 * n); io.best_obs.resize(n); io.best_median.resize(n); io.normal.resize(3 * n); io.min_distance.resize(n);
+  io.max_distance.resize(n); io.updated.resize(n);
+  lld_mappoint_refresh_out out;
+  out.desc = io.desc.data(); out.best_obs = io.best_obs.data(); out.best_median = io.best_median.data(); out.normal = io.normal.data();
+  out.min_distance = io.min_distance.data(); out.max_distance = io.max_distance.data(); out.updated = io.updated.data();
+  check(lld_mappoint_refresh(ctx.get(), &in, &out), "lld_mappoint_refresh");
+}
+
+struct MapLineBatch {
+  int32_t dim = 72;
+  std::vector<int32_t> obs_start, obs_kf;
+  std::vector<float> obs_desc;           // [dim*n_obs]
+  std::vector<uint8_t> kf_bad, bad;
+};
+struct MapLineDistinctiveOutput {
+  std::vector<float> desc;               // [dim*n]
+  std::vector<int32_t> best_obs, best_median;
+  std::vector<uint8_t> updated;
+};
+inline void MapLineDistinctive(const Context& ctx, const MapLineBatch& b, MapLineDistinctiveOutput& io) {
+  const size_t n = b.bad.size();
+  lld_mapline_distinctive_in in = lld_mapline_distinctive_in();
+  in.n_lines = (int32_t)n; in.n_obs = (int32_t)b.obs_kf.size(); in.n_kf = (int32_t)b.kf_bad.size(); in.dim = b.dim;
+  in.obs_start = b.obs_start.data(); in.obs_kf = b.obs_kf.data(); in.obs_desc = b.obs_desc.data(); in.kf_bad = b.kf_bad.data();
+  in.bad = b.bad.data();
+  io.desc.resize((size_t)(b.dim > 0 ? b.dim : 0) * n); io.best_obs.resize(n); io.best_median.resize(n); io.updated.resize(n);
+  lld_mapline_distinctive_out out;
+  out.desc = io.desc.data(); out.best_obs = io.best_obs.data(); out.best_median = io.best_median.data(); out.updated = io.updated.data();
+  check(lld_mapline_distinctive(ctx.get(), &in, &out), "lld_mapline_distinctive");
+}
+
 }  // namespace lld_amd
 #endif

@@ -219,6 +219,26 @@ class InitializerHypothesis(C.Structure):
     _fields_ = [("idx", C.c_int32 * 8), ("M", C.c_float * 9), ("score", C.c_float), ("n_inliers", C.c_int32)]
 
 
+class MapPointRefreshIn(C.Structure):
+    _fields_ = [("n_points", C.c_int32), ("n_obs", C.c_int32), ("n_kf", C.c_int32), ("n_levels", C.c_int32), ("flags", C.c_uint32),
+                ("obs_start", c_int32_p), ("obs_kf", c_int32_p), ("obs_desc", c_uint32_p), ("kf_ow", c_float_p), ("kf_bad", c_uint8_p),
+                ("pos", c_float_p), ("bad", c_uint8_p), ("ref_kf", c_int32_p), ("ref_level", c_int32_p), ("level_scale", c_float_p)]
+
+
+class MapPointRefreshOut(C.Structure):
+    _fields_ = [("desc", c_uint32_p), ("best_obs", c_int32_p), ("best_median", c_int32_p), ("normal", c_float_p),
+                ("min_distance", c_float_p), ("max_distance", c_float_p), ("updated", c_uint8_p)]
+
+
+class MapLineDistinctiveIn(C.Structure):
+    _fields_ = [("n_lines", C.c_int32), ("n_obs", C.c_int32), ("n_kf", C.c_int32), ("dim", C.c_int32), ("obs_start", c_int32_p),
+                ("obs_kf", c_int32_p), ("obs_desc", c_float_p), ("kf_bad", c_uint8_p), ("bad", c_uint8_p)]
+
+
+class MapLineDistinctiveOut(C.Structure):
+    _fields_ = [("desc", c_float_p), ("best_obs", c_int32_p), ("best_median", c_int32_p), ("updated", c_uint8_p)]
+
+
 class PoseGraph(C.Structure):
     _fields_ = [("n_vertices", C.c_int32), ("n_edges", C.c_int32), ("sim3", c_double_p), ("fixed", c_uint8_p), ("edge_i", c_int32_p),
                 ("edge_j", c_int32_p), ("edge_sji", c_double_p)]
@@ -265,6 +285,7 @@ PRODUCT_SYMBOLS = [
     "lld_sim3solver_batch_download", "lld_sim3solver_batch_hypotheses", "lld_sim3solver_batch_destroy", "lld_sim3solver_find",
     "lld_initializer_params_default", "lld_initializer_create", "lld_initializer_initialize", "lld_initializer_hypotheses",
     "lld_initializer_destroy", "lld_initializer_find",
+    "lld_mappoint_refresh", "lld_mapline_distinctive",
 ]
 
 
@@ -397,6 +418,10 @@ class Lib:
             f("initializer_find").argtypes = [vp, c_float_p, C.c_int32, c_float_p, C.c_int32, c_float_p, C.c_int32, c_int32_p,
                                               C.POINTER(InitializerParams), C.POINTER(InitializerResult)]
             f("initializer_find").restype = C.c_int
+            f("mappoint_refresh").argtypes = [vp, C.POINTER(MapPointRefreshIn), C.POINTER(MapPointRefreshOut)]
+            f("mappoint_refresh").restype = C.c_int
+            f("mapline_distinctive").argtypes = [vp, C.POINTER(MapLineDistinctiveIn), C.POINTER(MapLineDistinctiveOut)]
+            f("mapline_distinctive").restype = C.c_int
 
 
 _PRODUCT = None
