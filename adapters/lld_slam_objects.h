@@ -14,6 +14,7 @@
 #ifndef LLD_SLAM_OBJECTS_H
 #define LLD_SLAM_OBJECTS_H
 
+#include <algorithm>
 #include <cstddef>
 #include <cstring>
 #include <map>
@@ -81,6 +82,7 @@ struct KeyLine {                                                   // cv::line_d
 
 class MapPoint;
 class MapLine;
+class Map;
 
 class KeyFrame {
  public:
@@ -123,6 +125,31 @@ class KeyFrame {
   std::set<MapPoint*> GetMapPoints() const { std::set<MapPoint*> s; for (size_t i = 0; i < mvpMapPoints.size(); i++) if (mvpMapPoints[i]) s.insert(mvpMapPoints[i]); return s; }   // KeyFrame.cc:277-291 (bad points are filtered there; the doubles of the tests hold none)
   void ReplaceMapPointMatch(const size_t& idx, MapPoint* pMP) { mvpMapPoints[idx] = pMP; }
   Mat Ow;                                                          // 3x1, set with the pose by the reference (KeyFrame::SetPose)
+  // what LocalMapping::CreateNewMapPoints reads on top (include/KeyFrame.h)
+  int N = 0;                                                       // number of keypoints
+  float mb = 0, invfx = 0, invfy = 0;
+  std::vector<KeyPoint> mvKeys;                                    // the raw keypoints UnprojectStereo reads (KeyFrame.cc:643)
+  std::vector<float> mvDepth;                                      // negative: no depth
+  std::vector<KeyFrame*> GetBestCovisibilityKeyFrames(const int& n) const {   // KeyFrame.cc:182-190
+    if ((int)mvpOrderedConnectedKeyFrames.size() < n) return mvpOrderedConnectedKeyFrames;
+    return std::vector<KeyFrame*>(mvpOrderedConnectedKeyFrames.begin(), mvpOrderedConnectedKeyFrames.begin() + n);
+  }
+  // KeyFrame.cc:638-654: Twc.rowRange(0,3).colRange(0,3)*x3Dc+Twc.rowRange(0,3).col(3) = Rwc*x3Dc (one gemm, double accumulation) + Ow
+  Mat UnprojectStereo(int i) const {
+    const float z = mvDepth[i];
+    if (!(z > 0)) return Mat();
+    const float u = mvKeys[i].pt.x, v = mvKeys[i].pt.y;
+    const float c[3] = {(u - cx) * z * invfx, (v - cy) * z * invfy, z};
+    Mat x3D(3, 1);
+    for (int r = 0; r < 3; r++) {
+      double acc = (double)Tcw.at<float>(0, r) * (double)c[0];
+      acc += (double)Tcw.at<float>(1, r) * (double)c[1];
+      acc += (double)Tcw.at<float>(2, r) * (double)c[2];
+      x3D.at<float>(r) = (float)acc + Ow.at<float>(r);
+    }
+    return x3D;
+  }
+  inline float ComputeSceneMedianDepth(const int q) const;          // KeyFrame.cc:656-686, defined below MapPoint
 
   // (test access)
   Mat Tcw;
@@ -135,6 +162,11 @@ class KeyFrame {
 
 class MapPoint {
  public:
+  MapPoint() {}
+  // MapPoint(const cv::Mat &Pos, KeyFrame *pRefKF, Map* pMap)   (MapPoint.cc:32-44)
+  MapPoint(const Mat& Pos, KeyFrame* pRefKF, Map* pMap) { mNormalVector = Mat(3, 1); mWorldPos = Pos.clone(); mpRefKF = pRefKF; mpMap = pMap; mnId = nNextId()++; }
+  static unsigned long& nNextId() { static unsigned long n = 0; return n; }
+  Map* mpMap = nullptr;
   unsigned long mnId = 0;
   unsigned long mnBALocalForKF = 0;
   static std::mutex mGlobalMutex;
@@ -190,7 +222,24 @@ class MapPoint {
   int n_set_pos = 0, n_update_normal = 0;
 };
 
-class Map;
+// KeyFrame.cc:656-686.  The reference indexes an empty vector when the keyframe holds no MapPoint; here that yields 0.
+inline float KeyFrame::ComputeSceneMedianDepth(const int q) const {
+  std::vector<float> vDepths;
+  vDepths.reserve(mvpMapPoints.size());
+  const float zcw = Tcw.at<float>(2, 3);
+  for (size_t i = 0; i < mvpMapPoints.size(); i++) {
+    if (!mvpMapPoints[i]) continue;
+    const Mat x3Dw = mvpMapPoints[i]->GetWorldPos();
+    double acc = (double)Tcw.at<float>(2, 0) * (double)x3Dw.at<float>(0);    // Rcw2.dot(x3Dw): the double sum
+    acc += (double)Tcw.at<float>(2, 1) * (double)x3Dw.at<float>(1);
+    acc += (double)Tcw.at<float>(2, 2) * (double)x3Dw.at<float>(2);
+    vDepths.push_back((float)(acc + (double)zcw));
+  }
+  if (vDepths.empty()) return 0.f;
+  std::sort(vDepths.begin(), vDepths.end());
+  return vDepths[(vDepths.size() - 1) / q];
+}
+
 class MapLine {
  public:
   MapLine() {}
@@ -266,6 +315,8 @@ class Map {
   std::mutex mMutexMapUpdate;
   void AddMapLine(MapLine* pML) { mspMapLines.insert(pML); }       // Map.cc
   std::set<MapLine*> mspMapLines;
+  void AddMapPoint(MapPoint* pMP) { mspMapPoints.insert(pMP); }    // Map.cc
+  std::set<MapPoint*> mspMapPoints;
 };
 
 }  // namespace lld_slam

@@ -1709,6 +1709,125 @@ typedef struct {
 } lld_mapline_distinctive_out;
 int lld_mapline_distinctive(lld_ctx* ctx, const lld_mapline_distinctive_in* in, lld_mapline_distinctive_out* out);
 
+/* ================================================================== LocalMapping::CreateNewMapPoints (src/LocalMapping.cc:208-453), the loop body
+ * For the current keyframe (keyframe 1) and n_pairs covisible neighbours (keyframe 2 of each pair), every epipolar match that
+ * ORBmatcher::SearchForTriangulation returned goes through the parallax test, the linear triangulation or the stereo
+ * un-projection, the two depth tests, the two reprojection gates and the scale-consistency gate.  One call makes one upload,
+ * queues its two kernels on the context's stream with no host trip between them, makes one download and waits for the stream.
+ * What stays with the caller: the neighbour loop, ComputeF12, the search, ComputeSceneMedianDepth(2) (median_depth) and the
+ * object bookkeeping (new MapPoint, AddObservation, AddMapPoint, lld_mappoint_refresh for the new points).
+ * Restated literally:
+ *   Derived per keyframe: Rwc = Rcw.t(); Ow = -Rwc*tcw (src/KeyFrame.cc:85); invfx = 1.0f/fx, invfy = 1.0f/fy (src/Frame.cc:150).
+ *   Baseline gate (:245-262): baseline = (float)cv::norm(Ow2-Ow1) of the float difference.  Stereo: baseline < pKF2->mb skips the
+ *     pair.  Mono: ratioBaselineDepth = baseline/median_depth (float quotient); ratioBaselineDepth < 0.01 (the double constant)
+ *     skips it.  A skipped pair has pair_status 1, n_new 0 and every match LLD_NEWPTS_PAIR_SKIPPED.
+ *   Per match (idx1, idx2) (:287-451): bStereo1 = ur1[idx1] >= 0, bStereo2 = ur2[idx2] >= 0 (:294, :298).
+ *   :301-306 xn = ((x-cx)*invfx, (y-cy)*invfy, 1) in float from mvKeysUn; ray = Rwc*xn;
+ *     cosParallaxRays = ray1.dot(ray2)/(cv::norm(ray1)*cv::norm(ray2)), a double expression stored in a float.
+ *   :308-317 cosParallaxStereo1 = cosParallaxStereo2 = cosParallaxRays+1 (float).  QUIRK: `if(bStereo1) .. else if(bStereo2)` -
+ *     with BOTH keypoints stereo only cosParallaxStereo1 is computed, the other stays cosParallaxRays+1.  cosParallaxStereo =
+ *     min(cosParallaxStereo1, cosParallaxStereo2) (std::min: the second when it is strictly smaller).
+ *   :320 cosParallaxRays<cosParallaxStereo && cosParallaxRays>0 && (bStereo1 || bStereo2 || cosParallaxRays<0.9998): two float
+ *     tests and one against the double constant, all strict.  Then (:323-338) A.row(0) = xn1.x*Tcw1.row(2)-Tcw1.row(0), row(1)
+ *     with xn1.y and Tcw1.row(1), rows 2 and 3 likewise from keyframe 2 (float product, float difference); x3D = the null vector
+ *     of A; x3D[3] == 0 is W_ZERO (:334); x3D = x3D[0..2]/x3D[3].  source 0.
+ *   :341 else if(bStereo1 && cosParallaxStereo1<cosParallaxStereo2): x3D = keyframe 1's UnprojectStereo(idx1), source 1.
+ *   :345 else if(bStereo2 && cosParallaxStereo2<cosParallaxStereo1): x3D = keyframe 2's UnprojectStereo(idx2), source 2.
+ *   :349-350 else LOW_PARALLAX.
+ *   UnprojectStereo (src/KeyFrame.cc:638-654): z = mvDepth[i]; u, v from mvKeys - the RAW keypoint, not mvKeysUn (:643) -
+ *     x = (u-cx)*z*invfx, y = (v-cy)*z*invfy in float, left to right; Rwc*(x,y,z)+Ow.  z > 0 failing returns an empty Mat, which
+ *     the reference would fault on: here it is NO_DEPTH.
+ *   :355-360 z1 = Rcw1.row(2).dot(x3D)+tcw1[2]; z1 <= 0 is Z1; z2 likewise, Z2.
+ *   :364-388 x1, y1 like z1; invz1 = 1.0/z1, the double quotient rounded to float; u1 = fx1*x1*invz1+cx1, v1 = fy1*y1*invz1+cy1,
+ *     errX1 = u1-kp1.x, errY1 = v1-kp1.y in float.  Mono keypoint: (errX1*errX1+errY1*errY1) > 5.991*sigmaSquare1; stereo:
+ *     u1_r = u1-mbf*invz1, errX1_r = u1_r-kp1_ur, (errX1*errX1+errY1*errY1+errX1_r*errX1_r) > 7.8*sigmaSquare1.  The float sum
+ *     is widened and compared with the DOUBLE product 5.991*sigma2 / 7.8*sigma2; the test is `>`.  REPROJ1.
+ *   :391-414 the same for keyframe 2 with its own intrinsics and sigma2.  QUIRK: u2_r = u2 - mpCurrentKeyFrame->mbf*invz2 (:407),
+ *     the CURRENT keyframe's mbf.  REPROJ2.
+ *   :417-423 dist1 = (float)cv::norm(x3D-Ow1), dist2 = (float)cv::norm(x3D-Ow2); dist1 == 0 || dist2 == 0 is DIST_ZERO.
+ *   :426-432 ratioDist = dist2/dist1; ratioOctave = mvScaleFactors1[octave1]/mvScaleFactors2[octave2]; ratioFactor =
+ *     1.5f*mfScaleFactor; ratioDist*ratioFactor<ratioOctave || ratioDist>ratioOctave*ratioFactor, all in float, is SCALE.
+ *   Otherwise the point is created: status NEW.  Non-finite values follow IEEE with no special case (a NaN fails every test,
+ *     so a NaN point can come out NEW, as in the reference).
+ * Numerics left to OpenCV and libm: DEVIATION 2 of the Initializer section, unchanged.  Rwc*xn, Rwc*tcw, Rwc*x3Dc: the float
+ *   products summed in double in index order, rounded to float once; then the float + Ow.  Mat::dot is that double sum, and the
+ *   C++ expression it stands in (dot/(norm*norm), dot+t) is evaluated in double and rounded where it is assigned to a float.
+ *   cv::norm: the double square root of the double sum.  The 4x4 null vector: A^T A in double from the widened floats, the shared
+ *   cyclic Jacobi, the eigenvector of the smallest eigenvalue (the highest index on a tie), canonical sign, rounded to float.
+ *   x3D/w: the double reciprocal times the widened float, rounded.  No FMA contraction.
+ * DEVIATION (stereo parallax): cos(2*atan2(mb/2, depth)) (:313, :315) is evaluated as (d*d-a*a)/(d*d+a*a) in double on the widened
+ *   floats d = depth and a = mb/2 (a float), rounded to float.  The reference's chain of float libm calls cannot be reproduced bit
+ *   for bit; the closed form is the exact value correctly rounded, the same on host and device.  It differs from the float chain
+ *   by a few ulp, which matters only where cosParallaxRays is that close to it.
+ * Outputs (each pointer may be NULL): status / source / x3d per match (x3d zeros unless NEW; source names the branch taken, 0
+ *   where none was: LOW_PARALLAX and PAIR_SKIPPED); pair_status / n_new per pair; new_match = the global match indices with status
+ *   NEW in the reference's creation order (pair-major, match order within a pair; room for the number of matches);
+ *   n_new_total is always written.
+ * Limits, refused before anything is allocated: LLD_ERR_INVALID for a NULL required pointer (ctx, in, out, kf2, key_start and
+ *   match_start always; with at least one match also matches, keys1_xy, ur1, depth1, octave1, keys2_xy, ur2, depth2 and octave2 -
+ *   without a match none of these is read and each may be NULL; keys*_raw_xy may always be NULL), n_pairs < 1, a negative count, a
+ *   *_start array that does not begin at 0 or decreases, an idx1 / idx2 outside its keyframe, an octave of a matched keypoint
+ *   outside its level table, n_levels outside 1..LLD_ORB_MAX_LEVELS, a non-finite pose / intrinsic / mb / mbf / scale_factor
+ *   (median_depth too when monocular), fx or fy not > 0; LLD_ERR_UNSUPPORTED for n_pairs > LLD_NEWPTS_MAX_PAIRS or more than
+ *   LLD_NEWPTS_MAX_MATCHES matches in all.  No match in a pair, or in the whole call, is valid. */
+#define LLD_NEWPTS_MAX_PAIRS 64
+#define LLD_NEWPTS_MAX_MATCHES 65536
+#define LLD_NEWPTS_NEW           0         /* the point is created                                  */
+#define LLD_NEWPTS_LOW_PARALLAX  1         /* :349-350                                              */
+#define LLD_NEWPTS_W_ZERO        2         /* :334                                                  */
+#define LLD_NEWPTS_Z1            3         /* :356                                                  */
+#define LLD_NEWPTS_Z2            4         /* :360                                                  */
+#define LLD_NEWPTS_REPROJ1       5         /* :375-376, :386-387                                    */
+#define LLD_NEWPTS_REPROJ2       6         /* :401-402, :412-413                                    */
+#define LLD_NEWPTS_DIST_ZERO     7         /* :423                                                  */
+#define LLD_NEWPTS_SCALE         8         /* :431                                                  */
+#define LLD_NEWPTS_NO_DEPTH      9         /* UnprojectStereo with depth <= 0                       */
+#define LLD_NEWPTS_PAIR_SKIPPED 10         /* the baseline gate skipped the pair                    */
+#define LLD_NEWPTS_SRC_TRIANGULATED 0
+#define LLD_NEWPTS_SRC_STEREO1      1
+#define LLD_NEWPTS_SRC_STEREO2      2
+typedef struct {
+  float Rcw[9], tcw[3];                  /* GetRotation() row-major, GetTranslation()             */
+  float fx, fy, cx, cy;
+  float mb, mbf;                         /* mbf is read from keyframe 1 only (:381, :407)         */
+  float scale_factor;                    /* mfScaleFactor, read from keyframe 1 only (:233)       */
+  float median_depth;                    /* ComputeSceneMedianDepth(2): neighbours, monocular only */
+  int32_t n_levels;
+  float scale_factors[LLD_ORB_MAX_LEVELS];   /* mvScaleFactors                                    */
+  float level_sigma2[LLD_ORB_MAX_LEVELS];    /* mvLevelSigma2                                     */
+} lld_new_points_kf;
+typedef struct {
+  lld_new_points_kf kf1;                 /* mpCurrentKeyFrame                                     */
+  int32_t monocular;                     /* mbMonocular (0 / 1)                                   */
+  int32_t n_keys1;
+  const float*   keys1_xy;               /* [n_keys1][2] mvKeysUn[i].pt                           */
+  const float*   keys1_raw_xy;           /* [n_keys1][2] mvKeys[i].pt, NULL: equal to keys1_xy    */
+  const float*   ur1;                    /* [n_keys1] mvuRight                                    */
+  const float*   depth1;                 /* [n_keys1] mvDepth                                     */
+  const int32_t* octave1;                /* [n_keys1] mvKeysUn[i].octave                          */
+  int32_t n_pairs;
+  int32_t reserved;
+  const lld_new_points_kf* kf2;          /* [n_pairs] the neighbours                              */
+  const int32_t* key_start;              /* [n_pairs+1] the neighbours' keypoints, concatenated   */
+  const float*   keys2_xy;
+  const float*   keys2_raw_xy;           /* NULL: equal to keys2_xy                               */
+  const float*   ur2;
+  const float*   depth2;
+  const int32_t* octave2;
+  const int32_t* match_start;            /* [n_pairs+1] vMatchedIndices of each pair, concatenated */
+  const int32_t* matches;                /* [n_matches][2] (idx1, idx2 within the pair's keyframe) */
+} lld_new_points_in;
+typedef struct {                          /* every pointer may be NULL                             */
+  uint8_t* status;                       /* [n_matches] LLD_NEWPTS_*                              */
+  uint8_t* source;                       /* [n_matches] LLD_NEWPTS_SRC_*                          */
+  float*   x3d;                          /* [n_matches][3] zeros unless NEW                       */
+  uint8_t* pair_status;                  /* [n_pairs] 0 run, 1 skipped by the baseline gate       */
+  int32_t* n_new;                        /* [n_pairs]                                             */
+  int32_t* new_match;                    /* [n_matches] the first n_new_total entries are written */
+  int32_t  n_new_total;
+} lld_new_points_out;
+int lld_new_points_triangulate(lld_ctx* ctx, const lld_new_points_in* in, lld_new_points_out* out);
+
 #if defined(__GNUC__)
 #pragma GCC visibility pop
 #endif

@@ -948,5 +948,49 @@ inline void MapLineDistinctive(const Context& ctx, const MapLineBatch& b, MapLin
   check(lld_mapline_distinctive(ctx.get(), &in, &out), "lld_mapline_distinctive");
 }
 
+// The loop body of LocalMapping::CreateNewMapPoints (lld_new_points_triangulate): one keyframe against n_pairs neighbours.
+struct NewPointsKeys {
+  std::vector<float> xy;                 // [2*n] mvKeysUn
+  std::vector<float> raw_xy;             // [2*n] mvKeys, or empty: equal to xy
+  std::vector<float> ur, depth;          // [n] mvuRight, mvDepth
+  std::vector<int32_t> octave;           // [n]
+};
+struct NewPointsBatch {
+  lld_new_points_kf kf1;
+  bool monocular = false;
+  NewPointsKeys keys1;
+  std::vector<lld_new_points_kf> kf2;    // [n_pairs]
+  std::vector<int32_t> key_start;        // [n_pairs+1]
+  NewPointsKeys keys2;                   // the neighbours' keypoints, concatenated
+  std::vector<int32_t> match_start;      // [n_pairs+1]
+  std::vector<int32_t> matches;          // [2*n_matches] (idx1, idx2 within the pair's keyframe)
+  NewPointsBatch() : kf1() {}
+};
+struct NewPointsOutput {
+  std::vector<uint8_t> status, source;   // [n_matches] LLD_NEWPTS_*, LLD_NEWPTS_SRC_*
+  std::vector<float> x3d;                // [3*n_matches] zeros unless NEW
+  std::vector<uint8_t> pair_status;      // [n_pairs]
+  std::vector<int32_t> n_new;            // [n_pairs]
+  std::vector<int32_t> new_match;        // [n_new_total] in the reference's creation order
+};
+inline void TriangulateNewPoints(const Context& ctx, const NewPointsBatch& b, NewPointsOutput& o) {
+  const size_t n = b.matches.size() / 2, np = b.kf2.size();
+  lld_new_points_in in = lld_new_points_in();
+  in.kf1 = b.kf1; in.monocular = b.monocular ? 1 : 0; in.n_keys1 = (int32_t)b.keys1.ur.size();
+  in.keys1_xy = b.keys1.xy.data(); in.keys1_raw_xy = b.keys1.raw_xy.empty() ? NULL : b.keys1.raw_xy.data();
+  in.ur1 = b.keys1.ur.data(); in.depth1 = b.keys1.depth.data(); in.octave1 = b.keys1.octave.data();
+  in.n_pairs = (int32_t)np; in.kf2 = b.kf2.data(); in.key_start = b.key_start.data();
+  in.keys2_xy = b.keys2.xy.data(); in.keys2_raw_xy = b.keys2.raw_xy.empty() ? NULL : b.keys2.raw_xy.data();
+  in.ur2 = b.keys2.ur.data(); in.depth2 = b.keys2.depth.data(); in.octave2 = b.keys2.octave.data();
+  in.match_start = b.match_start.data(); in.matches = b.matches.data();
+  o.status.assign(n, 0); o.source.assign(n, 0); o.x3d.assign(3 * n, 0.0f); o.pair_status.assign(np, 0); o.n_new.assign(np, 0);
+  o.new_match.assign(n, 0);
+  lld_new_points_out out = lld_new_points_out();
+  out.status = o.status.data(); out.source = o.source.data(); out.x3d = o.x3d.data(); out.pair_status = o.pair_status.data();
+  out.n_new = o.n_new.data(); out.new_match = o.new_match.data();
+  check(lld_new_points_triangulate(ctx.get(), &in, &out), "lld_new_points_triangulate");
+  o.new_match.resize((size_t)out.n_new_total);
+}
+
 }  // namespace lld_amd
 #endif

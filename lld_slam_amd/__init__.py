@@ -10,9 +10,11 @@ from .pnp import PnPsolver, PnPsolverBatch  # noqa: F401
 from .sim3solver import Sim3Solver, Sim3SolverBatch  # noqa: F401
 from .initializer import Initializer, InitializerError, problem_from_scene  # noqa: F401
 from .landmarks import LandmarkError, distinctive_line_descriptors, refresh_map_points  # noqa: F401
+from .new_points import NewPointsError, triangulate_new_points  # noqa: F401
 from .host import (BABatch, Context, Optimizer, ORBmatcher, PoseBatch, PoseFrame, Tracking, TwoFrameLineMatcher,  # noqa: F401
                    Window)
 
 __all__ = ["abi", "Context", "Optimizer", "ORBmatcher", "TwoFrameLineMatcher", "Tracking", "BABatch", "PoseBatch", "Window",
            "PoseFrame", "PnPsolver", "PnPsolverBatch", "Sim3Solver", "Sim3SolverBatch", "Initializer", "InitializerError",
-           "problem_from_scene", "refresh_map_points", "distinctive_line_descriptors", "LandmarkError"]
+           "problem_from_scene", "refresh_map_points", "distinctive_line_descriptors", "LandmarkError",
+           "triangulate_new_points", "NewPointsError"]

@@ -239,6 +239,24 @@ class MapLineDistinctiveOut(C.Structure):
     _fields_ = [("desc", c_float_p), ("best_obs", c_int32_p), ("best_median", c_int32_p), ("updated", c_uint8_p)]
 
 
+class NewPointsKf(C.Structure):
+    _fields_ = [("Rcw", C.c_float * 9), ("tcw", C.c_float * 3), ("fx", C.c_float), ("fy", C.c_float), ("cx", C.c_float), ("cy", C.c_float),
+                ("mb", C.c_float), ("mbf", C.c_float), ("scale_factor", C.c_float), ("median_depth", C.c_float), ("n_levels", C.c_int32),
+                ("scale_factors", C.c_float * 16), ("level_sigma2", C.c_float * 16)]
+
+
+class NewPointsIn(C.Structure):
+    _fields_ = [("kf1", NewPointsKf), ("monocular", C.c_int32), ("n_keys1", C.c_int32), ("keys1_xy", c_float_p), ("keys1_raw_xy", c_float_p),
+                ("ur1", c_float_p), ("depth1", c_float_p), ("octave1", c_int32_p), ("n_pairs", C.c_int32), ("reserved", C.c_int32),
+                ("kf2", C.POINTER(NewPointsKf)), ("key_start", c_int32_p), ("keys2_xy", c_float_p), ("keys2_raw_xy", c_float_p),
+                ("ur2", c_float_p), ("depth2", c_float_p), ("octave2", c_int32_p), ("match_start", c_int32_p), ("matches", c_int32_p)]
+
+
+class NewPointsOut(C.Structure):
+    _fields_ = [("status", c_uint8_p), ("source", c_uint8_p), ("x3d", c_float_p), ("pair_status", c_uint8_p), ("n_new", c_int32_p),
+                ("new_match", c_int32_p), ("n_new_total", C.c_int32)]
+
+
 class PoseGraph(C.Structure):
     _fields_ = [("n_vertices", C.c_int32), ("n_edges", C.c_int32), ("sim3", c_double_p), ("fixed", c_uint8_p), ("edge_i", c_int32_p),
                 ("edge_j", c_int32_p), ("edge_sji", c_double_p)]
@@ -286,6 +304,7 @@ PRODUCT_SYMBOLS = [
     "lld_initializer_params_default", "lld_initializer_create", "lld_initializer_initialize", "lld_initializer_hypotheses",
     "lld_initializer_destroy", "lld_initializer_find",
     "lld_mappoint_refresh", "lld_mapline_distinctive",
+    "lld_new_points_triangulate",
 ]
 
 
@@ -422,6 +441,8 @@ class Lib:
             f("mappoint_refresh").restype = C.c_int
             f("mapline_distinctive").argtypes = [vp, C.POINTER(MapLineDistinctiveIn), C.POINTER(MapLineDistinctiveOut)]
             f("mapline_distinctive").restype = C.c_int
+            f("new_points_triangulate").argtypes = [vp, C.POINTER(NewPointsIn), C.POINTER(NewPointsOut)]
+            f("new_points_triangulate").restype = C.c_int
 
 
 _PRODUCT = None
