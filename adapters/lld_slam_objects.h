@@ -20,6 +20,7 @@
 #include <map>
 #include <mutex>
 #include <set>
+#include <utility>
 #include <vector>
 
 // ---- DBoW2::FeatureVector stand-in (Thirdparty/DBoW2/DBoW2/FeatureVector.h: a std::map<NodeId, std::vector<unsigned int>>)
@@ -151,6 +152,34 @@ class KeyFrame {
   }
   inline float ComputeSceneMedianDepth(const int q) const;          // KeyFrame.cc:656-686, defined below MapPoint
 
+  // what KeyFrame::UpdateConnections and LocalMapping::KeyFrameCulling read and write on top (include/KeyFrame.h)
+  float mThDepth = 0;
+  std::map<KeyFrame*, int> mConnectedKeyFrameWeights;              // pointer-ordered, as in the reference
+  std::vector<int> mvOrderedWeights;
+  bool mbFirstConnection = true;
+  KeyFrame* mpParent = nullptr;
+  std::set<KeyFrame*> mspChildrens;
+  void AddChild(KeyFrame* pKF) { mspChildrens.insert(pKF); }
+  void UpdateBestCovisibles() {                                     // KeyFrame.cc:146-165: sort of (weight, pointer), then push_front
+    std::vector<std::pair<int, KeyFrame*> > vPairs;
+    vPairs.reserve(mConnectedKeyFrameWeights.size());
+    for (std::map<KeyFrame*, int>::iterator mit = mConnectedKeyFrameWeights.begin(), mend = mConnectedKeyFrameWeights.end(); mit != mend; mit++)
+      vPairs.push_back(std::make_pair(mit->second, mit->first));
+    std::sort(vPairs.begin(), vPairs.end());
+    mvpOrderedConnectedKeyFrames.clear(); mvOrderedWeights.clear();
+    for (size_t i = vPairs.size(); i-- > 0;) { mvpOrderedConnectedKeyFrames.push_back(vPairs[i].second); mvOrderedWeights.push_back(vPairs[i].first); }
+  }
+  void AddConnection(KeyFrame* pKF, const int& weight) {           // KeyFrame.cc:131-144
+    std::map<KeyFrame*, int>::iterator it = mConnectedKeyFrameWeights.find(pKF);
+    if (it != mConnectedKeyFrameWeights.end() && it->second == weight) return;
+    mConnectedKeyFrameWeights[pKF] = weight;
+    UpdateBestCovisibles();
+  }
+  void EraseConnection(KeyFrame* pKF) {                             // KeyFrame.cc: erase, then re-sort
+    if (mConnectedKeyFrameWeights.erase(pKF)) UpdateBestCovisibles();
+  }
+  inline void SetBadFlag();                                         // KeyFrame.cc:476-: defined below MapPoint
+
   // (test access)
   Mat Tcw;
   bool mbBad = false;
@@ -238,6 +267,27 @@ inline float KeyFrame::ComputeSceneMedianDepth(const int q) const {
   if (vDepths.empty()) return 0.f;
   std::sort(vDepths.begin(), vDepths.end());
   return vDepths[(vDepths.size() - 1) / q];
+}
+
+// KeyFrame.cc:476-565 without the spanning-tree repair: the connections are erased on both sides and the keyframe's observations
+// are erased from its map points as MapPoint::EraseObservation does it (nObs drops by 2 for a stereo keypoint, by 1 otherwise; a
+// point left with nObs <= 2 becomes bad).  That is what changes the counts of the keyframes KeyFrameCulling visits afterwards.
+inline void KeyFrame::SetBadFlag() {
+  if (mnId == 0) return;
+  for (std::map<KeyFrame*, int>::iterator mit = mConnectedKeyFrameWeights.begin(), mend = mConnectedKeyFrameWeights.end(); mit != mend; mit++)
+    mit->first->EraseConnection(this);
+  for (size_t i = 0; i < mvpMapPoints.size(); i++) {
+    MapPoint* pMP = mvpMapPoints[i];
+    if (!pMP) continue;
+    const int idx = pMP->GetIndexInKeyFrame(this);
+    if (idx < 0) continue;
+    pMP->nObs -= ((size_t)idx < mvuRight.size() && mvuRight[idx] >= 0) ? 2 : 1;
+    pMP->EraseObservation(this);
+    if (pMP->nObs <= 2) pMP->mbBad = true;
+  }
+  mConnectedKeyFrameWeights.clear();
+  mvpOrderedConnectedKeyFrames.clear();
+  mbBad = true;
 }
 
 class MapLine {

@@ -1828,6 +1828,103 @@ typedef struct {                          /* every pointer may be NULL          
 } lld_new_points_out;
 int lld_new_points_triangulate(lld_ctx* ctx, const lld_new_points_in* in, lld_new_points_out* out);
 
+/* ---- Covisibility counting: KeyFrame::UpdateConnections (src/KeyFrame.cc:312-402), the vote of Tracking::UpdateLocalKeyFrames and
+ * the redundancy count of LocalMapping::KeyFrameCulling (src/LocalMapping.cc:633-697) for a batch of keyframes ("queries") in one
+ * call.  The reference runs them one keyframe at a time over copies of MapPoint::mObservations: in LocalMapping::
+ * ProcessNewKeyFrame (:165) and SearchInNeighbors (:534), in Tracking (:696-697, :1358) and once per keyframe of the corrected
+ * neighbourhood in LoopClosing::CorrectLoop (:434, :517, :556).  What UpdateConnections writes is what lld_kfdb_set_covisibles,
+ * GetBestCovisibilityKeyFrames and the local-BA window builder consume.  Every result is an integer, so the call is exact and
+ * bit-reproducible.  Each call makes one upload, queues its kernels on the context's stream with no host trip between them,
+ * makes one download and waits for the stream once.
+ * Keyframe table: n_kf slots, no per-slot data.  THE CALLER NUMBERS THE KEYFRAMES IN THE ORDER IN WHICH THE REFERENCE'S
+ *   std::map<KeyFrame*, ...> ITERATES THEM (pointer order, std::less<KeyFrame*>): THAT ORDER DECIDES EVERY TIE BELOW.
+ * Map points: the observations of point p are entries obs_start[p] .. obs_start[p+1]-1 (the CSR layout of lld_mappoint_refresh);
+ *   obs_kf[o] is the observing keyframe's slot, obs_octave[o] = pKFi->mvKeysUn[mit->second].octave (culling only), point_bad[p] =
+ *   isBad(), point_nobs[p] = MapPoint::Observations(), i.e. the stereo-weighted nObs and not the list length (culling only).
+ * Queries: query_kf[q] is the slot of the keyframe itself, or -1 to exclude nobody (a Frame's vote in UpdateLocalKeyFrames,
+ *   Tracking.cc).  Entries q_start[q] .. q_start[q+1]-1 of q_point are the entries of mvpMapPoints that are not NULL, in keypoint
+ *   order; a point listed twice counts twice, as the reference's walk over the vector counts it.  For culling, q_octave[e] =
+ *   pKF->mvKeysUn[i].octave and q_depth[e] = pKF->mvDepth[i] per entry, q_th_depth[q] = pKF->mThDepth per query, and `monocular`.
+ * Connections rule (KeyFrame.cc):
+ *   :329-333 a NULL entry and a bad point are skipped (the caller lists no NULL entries).
+ *   :335-342 for every observation whose slot differs from query_kf[q]: counter[slot]++.
+ *   :346-347 an empty counter returns: updated[q] = 0, the query owns no entries of either list, n_max[q] = 0, kf_max[q] = -1.
+ *   :390     mConnectedKeyFrameWeights = KFcounter: entries conn_start[q] .. conn_start[q+1]-1 of conn_kf / conn_weight are every
+ *            non-zero counter in ascending slot order (map order).
+ *   :359-363 nmax / pKFmax: the first `>` in map order, so kf_max[q] is the LOWEST slot that holds the maximum; n_max[q] and
+ *            kf_max[q] are always written.
+ *   :364-368 the counters >= th are the pairs (weight, keyframe).
+ *   :371-375 if there is none, the single pair (nmax, pKFmax).
+ *   :377-384 sort of pair<int,KeyFrame*> ascending, then push_front: ordered_kf / ordered_weight (entries ordered_start[q] ..)
+ *            are by DESCENDING weight, equal weights by DESCENDING slot.
+ *   The AddConnection calls on the neighbours (:367, :374) and the first-connection parent (:394-399) belong to the caller
+ *   (adapters/lld_covisibility_adapter.cc applies them).
+ *   Capacities: conn_capacity / ordered_capacity are the entries the caller's conn_* / ordered_* arrays hold over all queries.
+ *   The totals needed are always written to n_conn / n_ordered.  If either capacity is short the call returns LLD_ERR_INVALID
+ *   with only those two totals written.  sum over q of min(n_kf, observations of q's entries) always suffices for both.
+ * Culling rule (LocalMapping.cc), per query:
+ *   :655-657 a bad point is skipped.
+ *   :659-663 unless `monocular`, an entry with q_depth > q_th_depth || q_depth < 0 is skipped (float compares, exactly these two:
+ *            depth == th_depth is kept).
+ *   :665     n_mps++.
+ *   :666     only if point_nobs > th_obs:
+ *   :668-684 count the point's observations with slot != query_kf[q] and obs_octave <= q_octave + 1.  The reference breaks at
+ *            th_obs, so its test is "count >= th_obs", which does not depend on the order of the observations.
+ *   :685-688 if it holds, n_redundant++.
+ *   :694     redundant[q] = (n_redundant > redundant_ratio * n_mps): the int against the double product, as written there.
+ *   The mnId==0 skip (:644-645) and SetBadFlag (:695) belong to the caller.  SetBadFlag erases observations, so the counts of the
+ *   keyframes after a culled one change: the adapter calls again for the rest.
+ * flags: LLD_COVIS_CONNECTIONS, LLD_COVIS_CULLING or both.  Arrays of the part not selected are neither read nor written and may
+ *   be NULL.  phase_ms may be NULL; otherwise it receives the HIP-event times of the upload, the kernels and the download.
+ * Limits: n_kf above LLD_COVIS_MAX_KF (64 KB of LDS counters) returns LLD_ERR_UNSUPPORTED before anything is queued.
+ *   LLD_ERR_INVALID, also before anything is queued: a NULL required pointer; a negative size or capacity; flags zero or with
+ *   unknown bits; obs_start / q_start not starting at 0, not non-decreasing or not ending at n_obs / n_entries; an obs_kf outside
+ *   [0, n_kf); a query_kf outside [-1, n_kf); a q_point outside [0, n_points).  n_queries = 0 is LLD_OK and touches nothing. */
+#define LLD_COVIS_MAX_KF 16384             /* keyframe slots of one call                            */
+#define LLD_COVIS_CONNECTIONS 1u           /* flags bit 0: UpdateConnections / the local-keyframe vote */
+#define LLD_COVIS_CULLING     2u           /* flags bit 1: KeyFrameCulling's redundancy count       */
+typedef struct {
+  int32_t th;                            /* 15  (KeyFrame.cc:353)                                 */
+  int32_t th_obs;                        /* 3   (LocalMapping.cc:648)                             */
+  double  redundant_ratio;               /* 0.9 (LocalMapping.cc:694)                             */
+} lld_covisibility_params;
+void lld_covisibility_params_default(lld_covisibility_params* p);
+typedef struct {
+  int32_t n_kf, n_points, n_obs, n_queries, n_entries;
+  int32_t monocular;                     /* mbMonocular: no depth test in the culling part        */
+  uint32_t flags;
+  lld_covisibility_params params;
+  const int32_t* obs_start;              /* [n_points+1]                                          */
+  const int32_t* obs_kf;                 /* [n_obs] slot of the observing keyframe                */
+  const int32_t* obs_octave;             /* [n_obs] culling only                                  */
+  const uint8_t* point_bad;              /* [n_points]                                            */
+  const int32_t* point_nobs;             /* [n_points] MapPoint::Observations(); culling only     */
+  const int32_t* query_kf;               /* [n_queries] own slot, or -1                           */
+  const int32_t* q_start;                /* [n_queries+1]                                         */
+  const int32_t* q_point;                /* [n_entries] the non-NULL mvpMapPoints in keypoint order */
+  const int32_t* q_octave;               /* [n_entries] culling only                              */
+  const float*   q_depth;                /* [n_entries] culling only                              */
+  const float*   q_th_depth;             /* [n_queries] culling only                              */
+} lld_covisibility_in;
+typedef struct {
+  int32_t  conn_capacity, ordered_capacity;   /* in: entries of conn_* / ordered_*               */
+  int32_t  n_conn, n_ordered;            /* out: entries needed, always written                   */
+  int32_t* conn_start;                   /* [n_queries+1]                                         */
+  int32_t* conn_kf;                      /* [conn_capacity] ascending slot per query              */
+  int32_t* conn_weight;                  /* [conn_capacity]                                       */
+  int32_t* ordered_start;                /* [n_queries+1]                                         */
+  int32_t* ordered_kf;                   /* [ordered_capacity] descending (weight, slot) per query */
+  int32_t* ordered_weight;               /* [ordered_capacity]                                    */
+  int32_t* n_max;                        /* [n_queries]                                           */
+  int32_t* kf_max;                       /* [n_queries] or -1                                     */
+  uint8_t* updated;                      /* [n_queries] 0: the early return of :346-347           */
+  int32_t* n_mps;                        /* [n_queries] culling                                   */
+  int32_t* n_redundant;                  /* [n_queries] culling                                   */
+  uint8_t* redundant;                    /* [n_queries] culling                                   */
+  float*   phase_ms;                     /* [3] upload, kernels, download; may be NULL            */
+} lld_covisibility_out;
+int lld_covisibility(lld_ctx* ctx, const lld_covisibility_in* in, lld_covisibility_out* out);
+
 #if defined(__GNUC__)
 #pragma GCC visibility pop
 #endif

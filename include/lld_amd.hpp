@@ -992,5 +992,75 @@ inline void TriangulateNewPoints(const Context& ctx, const NewPointsBatch& b, Ne
   o.new_match.resize((size_t)out.n_new_total);
 }
 
+// ---- Covisibility counting (src/KeyFrame.cc:312-402, src/LocalMapping.cc:633-697) for a batch of keyframes in one call.
+// Keyframes are slots NUMBERED IN THE ORDER IN WHICH THE REFERENCE'S std::map<KeyFrame*, ...> ITERATES; the map points' observations
+// are in the CSR layout of MapPointBatch; a query is one keyframe (or -1: a Frame, excluding nobody) with the entries of
+// mvpMapPoints that are not NULL, in keypoint order.
+struct CovisibilityBatch {
+  int32_t n_kf;
+  bool monocular;
+  lld_covisibility_params params;
+  std::vector<int32_t> obs_start, obs_kf, obs_octave;      // [n_points+1], [n_obs], [n_obs] (culling)
+  std::vector<uint8_t> point_bad;                          // [n_points]
+  std::vector<int32_t> point_nobs;                         // [n_points] MapPoint::Observations() (culling)
+  std::vector<int32_t> query_kf, q_start, q_point, q_octave;   // [n_queries], [n_queries+1], [n_entries], [n_entries] (culling)
+  std::vector<float> q_depth, q_th_depth;                  // [n_entries], [n_queries] (culling)
+  CovisibilityBatch() : n_kf(0), monocular(false) { lld_covisibility_params_default(&params); }
+};
+struct CovisibilityOutput {
+  std::vector<int32_t> conn_start, conn_kf, conn_weight;            // mConnectedKeyFrameWeights in map order
+  std::vector<int32_t> ordered_start, ordered_kf, ordered_weight;   // mvpOrderedConnectedKeyFrames / mvOrderedWeights
+  std::vector<int32_t> n_max, kf_max;
+  std::vector<uint8_t> updated;                                     // 0: UpdateConnections returns early
+  std::vector<int32_t> n_mps, n_redundant;
+  std::vector<uint8_t> redundant;
+  float phase_ms[3];                                                // upload, kernels, download when `timed`
+};
+inline void Covisibility(const Context& ctx, const CovisibilityBatch& b, uint32_t flags, CovisibilityOutput& o, bool timed = false) {
+  const size_t nq = b.query_kf.size(), np = b.point_bad.size();
+  lld_covisibility_in in = lld_covisibility_in();
+  in.n_kf = b.n_kf; in.n_points = (int32_t)np; in.n_obs = (int32_t)b.obs_kf.size(); in.n_queries = (int32_t)nq;
+  in.n_entries = (int32_t)b.q_point.size(); in.monocular = b.monocular ? 1 : 0; in.flags = flags; in.params = b.params;
+  in.obs_start = b.obs_start.data(); in.obs_kf = b.obs_kf.data(); in.point_bad = b.point_bad.data(); in.query_kf = b.query_kf.data();
+  in.q_start = b.q_start.data(); in.q_point = b.q_point.data();
+  const bool conn = (flags & LLD_COVIS_CONNECTIONS) != 0, cull = (flags & LLD_COVIS_CULLING) != 0;
+  if (cull) {
+    in.obs_octave = b.obs_octave.data(); in.point_nobs = b.point_nobs.data(); in.q_octave = b.q_octave.data();
+    in.q_depth = b.q_depth.data(); in.q_th_depth = b.q_th_depth.data();
+  }
+  lld_covisibility_out out = lld_covisibility_out();
+  if (conn) {
+    // entries that always suffice: per query min(n_kf, observations of its entries); malformed lists get 0 and are refused by the call
+    long long cap = 0;
+    if (b.obs_start.size() == np + 1 && b.q_start.size() == nq + 1)
+      for (size_t q = 0; q < nq; ++q) {
+        long long c = 0;
+        for (int32_t e = b.q_start[q]; e < b.q_start[q + 1] && e >= 0 && (size_t)e < b.q_point.size() && c < b.n_kf; ++e) {
+          const int32_t p = b.q_point[e];
+          if (p >= 0 && (size_t)p < np) c += b.obs_start[p + 1] - b.obs_start[p];
+        }
+        cap += c < b.n_kf ? c : b.n_kf;
+      }
+    if (cap > 0x7fffffffLL) cap = 0x7fffffffLL;
+    o.conn_start.assign(nq + 1, 0); o.ordered_start.assign(nq + 1, 0); o.n_max.assign(nq, 0); o.kf_max.assign(nq, -1); o.updated.assign(nq, 0);
+    o.conn_kf.assign((size_t)cap, 0); o.conn_weight.assign((size_t)cap, 0); o.ordered_kf.assign((size_t)cap, 0); o.ordered_weight.assign((size_t)cap, 0);
+    out.conn_capacity = out.ordered_capacity = (int32_t)cap;
+    out.conn_start = o.conn_start.data(); out.conn_kf = o.conn_kf.data(); out.conn_weight = o.conn_weight.data();
+    out.ordered_start = o.ordered_start.data(); out.ordered_kf = o.ordered_kf.data(); out.ordered_weight = o.ordered_weight.data();
+    out.n_max = o.n_max.data(); out.kf_max = o.kf_max.data(); out.updated = o.updated.data();
+  }
+  if (cull) {
+    o.n_mps.assign(nq, 0); o.n_redundant.assign(nq, 0); o.redundant.assign(nq, 0);
+    out.n_mps = o.n_mps.data(); out.n_redundant = o.n_redundant.data(); out.redundant = o.redundant.data();
+  }
+  o.phase_ms[0] = o.phase_ms[1] = o.phase_ms[2] = 0.f;
+  if (timed) out.phase_ms = o.phase_ms;
+  check(lld_covisibility(ctx.get(), &in, &out), "lld_covisibility");
+  if (conn && nq) {
+    o.conn_kf.resize((size_t)out.n_conn); o.conn_weight.resize((size_t)out.n_conn);
+    o.ordered_kf.resize((size_t)out.n_ordered); o.ordered_weight.resize((size_t)out.n_ordered);
+  }
+}
+
 }  // namespace lld_amd
 #endif

@@ -11,10 +11,11 @@ from .sim3solver import Sim3Solver, Sim3SolverBatch  # noqa: F401
 from .initializer import Initializer, InitializerError, problem_from_scene  # noqa: F401
 from .landmarks import LandmarkError, distinctive_line_descriptors, refresh_map_points  # noqa: F401
 from .new_points import NewPointsError, triangulate_new_points  # noqa: F401
+from .covisibility import CovisibilityError, keyframe_culling, update_connections  # noqa: F401
 from .host import (BABatch, Context, Optimizer, ORBmatcher, PoseBatch, PoseFrame, Tracking, TwoFrameLineMatcher,  # noqa: F401
                    Window)
 
 __all__ = ["abi", "Context", "Optimizer", "ORBmatcher", "TwoFrameLineMatcher", "Tracking", "BABatch", "PoseBatch", "Window",
            "PoseFrame", "PnPsolver", "PnPsolverBatch", "Sim3Solver", "Sim3SolverBatch", "Initializer", "InitializerError",
            "problem_from_scene", "refresh_map_points", "distinctive_line_descriptors", "LandmarkError",
-           "triangulate_new_points", "NewPointsError"]
+           "triangulate_new_points", "NewPointsError", "update_connections", "keyframe_culling", "CovisibilityError"]

@@ -257,6 +257,26 @@ class NewPointsOut(C.Structure):
                 ("new_match", c_int32_p), ("n_new_total", C.c_int32)]
 
 
+class CovisibilityParams(C.Structure):
+    _fields_ = [("th", C.c_int32), ("th_obs", C.c_int32), ("redundant_ratio", C.c_double)]
+
+
+class CovisibilityIn(C.Structure):
+    _fields_ = [("n_kf", C.c_int32), ("n_points", C.c_int32), ("n_obs", C.c_int32), ("n_queries", C.c_int32), ("n_entries", C.c_int32),
+                ("monocular", C.c_int32), ("flags", C.c_uint32), ("params", CovisibilityParams), ("obs_start", c_int32_p),
+                ("obs_kf", c_int32_p), ("obs_octave", c_int32_p), ("point_bad", c_uint8_p), ("point_nobs", c_int32_p),
+                ("query_kf", c_int32_p), ("q_start", c_int32_p), ("q_point", c_int32_p), ("q_octave", c_int32_p), ("q_depth", c_float_p),
+                ("q_th_depth", c_float_p)]
+
+
+class CovisibilityOut(C.Structure):
+    _fields_ = [("conn_capacity", C.c_int32), ("ordered_capacity", C.c_int32), ("n_conn", C.c_int32), ("n_ordered", C.c_int32),
+                ("conn_start", c_int32_p), ("conn_kf", c_int32_p), ("conn_weight", c_int32_p), ("ordered_start", c_int32_p),
+                ("ordered_kf", c_int32_p), ("ordered_weight", c_int32_p), ("n_max", c_int32_p), ("kf_max", c_int32_p),
+                ("updated", c_uint8_p), ("n_mps", c_int32_p), ("n_redundant", c_int32_p), ("redundant", c_uint8_p),
+                ("phase_ms", c_float_p)]
+
+
 class PoseGraph(C.Structure):
     _fields_ = [("n_vertices", C.c_int32), ("n_edges", C.c_int32), ("sim3", c_double_p), ("fixed", c_uint8_p), ("edge_i", c_int32_p),
                 ("edge_j", c_int32_p), ("edge_sji", c_double_p)]
@@ -305,6 +325,7 @@ PRODUCT_SYMBOLS = [
     "lld_initializer_destroy", "lld_initializer_find",
     "lld_mappoint_refresh", "lld_mapline_distinctive",
     "lld_new_points_triangulate",
+    "lld_covisibility_params_default", "lld_covisibility",
 ]
 
 
@@ -443,6 +464,10 @@ class Lib:
             f("mapline_distinctive").restype = C.c_int
             f("new_points_triangulate").argtypes = [vp, C.POINTER(NewPointsIn), C.POINTER(NewPointsOut)]
             f("new_points_triangulate").restype = C.c_int
+            f("covisibility_params_default").argtypes = [C.POINTER(CovisibilityParams)]
+            f("covisibility_params_default").restype = None
+            f("covisibility").argtypes = [vp, C.POINTER(CovisibilityIn), C.POINTER(CovisibilityOut)]
+            f("covisibility").restype = C.c_int
 
 
 _PRODUCT = None
