@@ -1092,6 +1092,63 @@ int  lld_orb_extractor_pyramids(const lld_orb_extractor* ex, int image_index, co
 int  lld_orb_extractor_descriptors(const lld_orb_extractor* ex, int image_index, const uint32_t** desc, int32_t* n);
 
 
+/* ------------------------------------------------------------------ the stereo Frame, built on the device
+ * Frame::Frame for a stereo pair (src/Frame.cc:77-170) runs, after the two ORBextractor calls (:101-106): UndistortKeyPoints (:111),
+ * ComputeStereoMatches (:113), the level tables and grid constants (:92-98, :140-157) and AssignFeaturesToGrid (:159).  These calls do
+ * that part on the device and hand back a resident lld_frame - the handle of lld_frame_create, on which lld_frame_search_last_frame,
+ * lld_frame_search_local_points, lld_frame_set_lines, lld_frame_track_* and lld_frame_destroy work unchanged - whose mvuRight and
+ * mvDepth were COMPUTED in HBM; the frame carries right coordinates, angles and mvInvLevelSigma2, so the whole chain may follow.
+ *   stage 1  the row-band Hamming search of ComputeStereoMatches (:536-613): one wavefront per left keypoint, a lane per right
+ *            keypoint; right keypoint iR is a candidate iff its octave is within +-1 of the left one, (int)vL lies in
+ *            [floor(yR - r), ceil(yR + r)] with r = 2 * scale[octave_R], and uR lies in [uL - mbf/mb, uL]; a left keypoint with uL < 0
+ *            is skipped; lowest distance, then lowest iR; accepted iff the distance is < (TH_HIGH + TH_LOW) / 2.  Bit-identical to
+ *            the LLD_ORB_CAND_ROWS problem lld_compute_stereo_matches runs (which needs one workgroup and a trip through the host).
+ *   stage 2, 3  the SAD refinement and the median cut of lld_compute_stereo_matches (same kernels), writing mvuRight / mvDepth into
+ *            the frame's own arrays.
+ * Scope: RECTIFIED stereo only - mvKeysUn = mvKeys, the `mDistCoef.at<float>(0)==0.0` branch of Frame::UndistortKeyPoints
+ * (:468-474); a caller with a distorted camera undistorts on the host and uses lld_frame_create.  Lines are added with
+ * lld_frame_set_lines as before (the reference's line extractor is external and host-side).
+ * Both build calls queue their kernels on the context's stream and return WITHOUT synchronising; every later call on the frame is
+ * ordered after them by that stream, and lld_frame_stereo_download is the one that waits.
+ * Refusals, before anything is queued: LLD_ERR_INVALID for null pointers, mb not > 0, a grid outside lld_frame_create's limits,
+ * n_levels outside [1, LLD_ORB_MAX_LEVELS] or different from pyr->n_levels, octaves outside [0, n_levels), an extractor without a
+ * successful lld_orb_extract, image indices outside that call's n_images or equal to each other; LLD_ERR_UNSUPPORTED above
+ * LLD_ORB_MAX_KEYPOINTS keypoints on either side.  A left image without keypoints gives an empty frame (nt = 0) and LLD_OK
+ * (Frame.cc:108-109). */
+typedef struct {
+  float grid_min_x, grid_min_y, grid_width_inv, grid_height_inv;   /* mnMinX, mnMinY, mfGridElementWidthInv, mfGridElementHeightInv  */
+  int32_t grid_cols, grid_rows;                                    /* 64, 48 (Frame.h:43-44); as lld_orb_search                       */
+  float mb, mbf;                                                   /* mb = mbf / fx (Frame.cc:156), mbf: minZ = mb, maxD = mbf / mb   */
+  const float* left_angle;      /* [left->n] mvKeysUn[k].angle, which searches with check_orientation read; required by
+                                   lld_frame_build_stereo_keypoints (host or device like the keypoints); lld_frame_build_stereo reads
+                                   the extractor's own                                                                               */
+  const float* right_angle;     /* [right->n] or NULL; no routine reads mvKeysRight[k].angle, the frame does not keep it             */
+  int32_t keypoints_on_device;  /* lld_frame_build_stereo_keypoints: 1 = xy, desc and the angles of both sides and right->octave are
+                                   HBM pointers, read in place.  left->octave stays a HOST array on both routes: it becomes the
+                                   frame's host copy of the octaves (query validation) and is the one array uploaded               */
+  int32_t n_levels;             /* mnScaleLevels; must equal pyr->n_levels                                                           */
+  const float* level_scale;       /* [n_levels] mvScaleFactors                                                                       */
+  const float* level_sigma2;      /* [n_levels] mvLevelSigma2, or NULL (all 1)                                                       */
+  const float* level_inv_sigma2;  /* [n_levels] mvInvLevelSigma2                                                                     */
+} lld_frame_stereo_params;
+/* The general form.  left / right: mvKeys / mvKeysRight with mDescriptors / mDescriptorsRight, on the host or (keypoints_on_device)
+ * in HBM; pyr: the two image pyramids as for lld_compute_stereo_matches, on the host or (pyr->on_device) in HBM.  Everything that
+ * starts on the host travels in ONE copy from a pinned buffer the frame owns; with device keypoints that copy is left->octave
+ * (plus host pyramids).  Device inputs must stay valid until the queued work has run (e.g. until lld_frame_stereo_download). */
+int  lld_frame_build_stereo_keypoints(lld_ctx* ctx, const lld_keypoints* left, const lld_keypoints* right, const lld_stereo_pyramids* pyr,
+                                      const lld_frame_stereo_params* params, lld_frame** out);
+/* The same build on images left_image / right_image of the handle's last lld_orb_extract, on the extractor's context: keypoints,
+ * angles, descriptors and pyramids are read where the extractor left them, the level tables are the extractor's (params->n_levels,
+ * level_*, left_angle, right_angle and keypoints_on_device are ignored), and nothing is uploaded.  The frame copies what it keeps
+ * into its own allocation (device to device, inside the search kernel), so it survives the next lld_orb_extract on the handle and
+ * the handle's destruction. */
+int  lld_frame_build_stereo(lld_orb_extractor* ex, int left_image, int right_image, const lld_frame_stereo_params* params, lld_frame** out);
+/* Waits for the frame's queued work and fetches mvuRight, mvDepth, optionally best_r / sad, and n_matches in one copy (the host
+ * needs them for Frame::UnprojectStereo and for keyframe creation).  out->u_right and out->depth must hold the frame's nt entries.
+ * LLD_ERR_INVALID on a frame made by lld_frame_create. */
+int  lld_frame_stereo_download(lld_frame* frame, lld_stereo_result* out);
+
+
 /* ------------------------------------------------------------------ DBoW2 vocabulary: load, transform, L1 score
  * Thirdparty/DBoW2/DBoW2/ of the reference, as ORB-SLAM2 uses it (ORBVocabulary = TemplatedVocabulary<FORB::TDescriptor, FORB>).
  * Every value is bit-exact against the CPU restatement tests/bow_ref.py.  Restated rules:

@@ -12,6 +12,7 @@
 #include <set>
 #include <stdexcept>
 #include <string>
+#include <memory>
 #include <vector>
 
 #include "lld_amd.h"
@@ -394,6 +395,12 @@ class TrackedFrame {
     if (st != LLD_OK) { lld_frame_destroy(f_); f_ = nullptr; check(st, "lld_frame_set_lines"); }
     lld_track_params_default(&params);
   }
+  // a frame the device built (StereoFrame below): takes ownership of `built`, whose nt keypoints are already resident
+  TrackedFrame(lld_frame* built, int nt, const lld_frame_lines* lines) : f_(built), nt_(nt), nl_(lines ? lines->n_left : 0) {
+    const int st = lld_frame_set_lines(f_, lines);
+    if (st != LLD_OK) { lld_frame_destroy(f_); f_ = nullptr; check(st, "lld_frame_set_lines"); }
+    lld_track_params_default(&params);
+  }
   ~TrackedFrame() { if (f_) lld_frame_destroy(f_); }
   TrackedFrame(const TrackedFrame&) = delete;
   TrackedFrame& operator=(const TrackedFrame&) = delete;
@@ -417,6 +424,15 @@ class TrackedFrame {
     if (stage1) stage1->bind(nt_, nl_);
     if (stage2) stage2->bind(nt_, nl_);
     check(lld_frame_track_download(f_, stage1 ? &stage1->r : nullptr, stage2 ? &stage2->r : nullptr), "lld_frame_track_download");
+  }
+  int N() const { return nt_; }
+  // mvuRight / mvDepth of a frame StereoFrame built (Frame::UnprojectStereo and keyframe creation read them on the host); waits for the build
+  int DownloadStereo(std::vector<float>& mvuRight, std::vector<float>& mvDepth) {
+    mvuRight.assign(nt_, -1.f); mvDepth.assign(nt_, -1.f);
+    lld_stereo_result r{};
+    r.u_right = mvuRight.data(); r.depth = mvDepth.data();
+    check(lld_frame_stereo_download(f_, &r), "lld_frame_stereo_download");
+    return r.n_matches;
   }
  private:
   lld_frame* f_ = nullptr;
@@ -472,6 +488,22 @@ class ORBextractor {
   lld_orb_extractor* h_ = nullptr;
   lld_orb_extractor_levels levels_{};
 };
+
+// Frame::Frame(imLeft, imRight, ...) (src/Frame.cc:77-170) after `ex` extracted the pair (images `left_image`, `right_image` of its last call):
+// ComputeStereoMatches and the resident frame on the device, nothing through the host (lld_frame_build_stereo).  mb, mbf as the Frame's;
+// the grid follows Frame.cc:140-150 for a rectified pair of cols x rows pixels (mnMinX = mnMinY = 0).  Returns the frame of the Tracking
+// chain; the build is queued, not waited for.
+inline std::unique_ptr<TrackedFrame> StereoFrame(ORBextractor& ex, int left_image, int right_image, int n_left, int cols, int rows, float mb, float mbf,
+                                                 const lld_frame_lines* lines) {
+  lld_frame_stereo_params p{};
+  p.grid_min_x = 0.f; p.grid_min_y = 0.f;
+  p.grid_cols = 64; p.grid_rows = 48;                                   // FRAME_GRID_COLS, FRAME_GRID_ROWS
+  p.grid_width_inv = (float)p.grid_cols / (float)cols; p.grid_height_inv = (float)p.grid_rows / (float)rows;
+  p.mb = mb; p.mbf = mbf;
+  lld_frame* f = nullptr;
+  check(lld_frame_build_stereo(ex.get(), left_image, right_image, &p, &f), "lld_frame_build_stereo");
+  return std::unique_ptr<TrackedFrame>(new TrackedFrame(f, n_left, lines));
+}
 
 // Mirror of ORBVocabulary = DBoW2::TemplatedVocabulary<FORB::TDescriptor, FORB> (Thirdparty/DBoW2/DBoW2/TemplatedVocabulary.h):
 // loadFromTextFile, transform(features, BowVector&, FeatureVector&, levelsup) and score, with the L1 scoring ORB-SLAM2 uses.  The

@@ -292,6 +292,14 @@ class PoseGraphResult(C.Structure):
                 ("solver_used", C.c_int32)]
 
 
+class FrameStereoParams(C.Structure):
+    """lld_frame_stereo_params (include/lld_amd.h): the constants of a stereo Frame built on the device."""
+    _fields_ = [("grid_min_x", C.c_float), ("grid_min_y", C.c_float), ("grid_width_inv", C.c_float), ("grid_height_inv", C.c_float),
+                ("grid_cols", C.c_int32), ("grid_rows", C.c_int32), ("mb", C.c_float), ("mbf", C.c_float),
+                ("left_angle", c_float_p), ("right_angle", c_float_p), ("keypoints_on_device", C.c_int32), ("n_levels", C.c_int32),
+                ("level_scale", c_float_p), ("level_sigma2", c_float_p), ("level_inv_sigma2", c_float_p)]
+
+
 PRODUCT_SYMBOLS = [
     "lld_status_string", "lld_ctx_create", "lld_ctx_destroy", "lld_ctx_stream", "lld_ctx_synchronize", "lld_ctx_release_cache",
     "lld_se3_from_tcw_f32", "lld_se3_to_tcw_f32", "lld_orb_inv_level_sigma2",
@@ -326,6 +334,7 @@ PRODUCT_SYMBOLS = [
     "lld_mappoint_refresh", "lld_mapline_distinctive",
     "lld_new_points_triangulate",
     "lld_covisibility_params_default", "lld_covisibility",
+    "lld_frame_build_stereo_keypoints", "lld_frame_build_stereo", "lld_frame_stereo_download",
 ]
 
 

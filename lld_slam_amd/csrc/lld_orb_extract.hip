@@ -6,7 +6,7 @@
 //   copy level 0 -> orbx_resize per level 1..L-1 -> orbx_score (FAST score map) + orbx_blur (one launch each, every level)
 //   -> orbx_cells (one wavefront per cell: thresholds, NMS, ordered output) -> orbx_octree (one workgroup per (image, level))
 //   -> orbx_emit (orientation, descriptor, scaled keypoint) -> one copy of every image's results to the host.
-#include "lld_common.h"
+#include "lld_stereo_internal.h"
 #include "lld_glibc_sincosf.h"
 
 #include <algorithm>
@@ -707,6 +707,26 @@ extern "C" int lld_orb_extractor_pyramids(const lld_orb_extractor* ex, int image
   }
   return LLD_OK;
 }
+
+// ---- what lld_frame_build.hip reads in place (lld_stereo_internal.h)
+int lld_stereo::extracted_image(const lld_orb_extractor* ex, int image, ExtractedImage* out) {
+  if (!ex || !out || image < 0 || image >= ex->last_n_images) return LLD_ERR_INVALID;
+  const size_t cap = (size_t)ex->cap_keys;
+  const char* d = ex->d_out + ex->out_stride * image; const char* h = ex->h_out + ex->out_stride * image;
+  std::memset(out, 0, sizeof(*out));
+  out->n = *(const int32_t*)(h + cap * 56);
+  out->d_xy = (const float*)d; out->d_octave = (const int32_t*)(d + cap * 8); out->d_angle = (const float*)(d + cap * 12);
+  out->d_desc = (const uint32_t*)(d + cap * 24);
+  out->h_octave = (const int32_t*)(h + cap * 8);
+  const int nl = ex->p.n_levels;
+  for (int l = 0; l < nl; l++) {
+    const LevelGeo& g = ex->h_geo->g[image * nl + l];
+    out->level[l] = g.img; out->cols[l] = g.cols; out->rows[l] = g.rows; out->step[l] = g.step;
+  }
+  return LLD_OK;
+}
+lld_ctx* lld_stereo::extractor_context(const lld_orb_extractor* ex) { return ex->ctx; }
+const lld_orb_extractor_levels* lld_stereo::extractor_levels(const lld_orb_extractor* ex) { return &ex->lv; }
 
 extern "C" int lld_orb_extractor_descriptors(const lld_orb_extractor* ex, int image_index, const uint32_t** desc, int32_t* n) {
   if (!ex || !desc || !n || image_index < 0 || image_index >= ex->last_n_images) return LLD_ERR_INVALID;

@@ -1284,6 +1284,7 @@ extern "C" void lld_frame_destroy(lld_frame* f) {
   (void)hipStreamSynchronize(f->ctx->stream);
   lld_track::state_free(f);
   if (f->d) (void)hipFree(f->d);
+  if (f->h_stage) (void)hipHostFree(f->h_stage);
   delete f;
 }
 

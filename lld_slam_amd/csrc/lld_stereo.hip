@@ -6,22 +6,14 @@
 //                                                  integers below 2^16), then one pass that clears the outliers
 // Integer sums and single-rounding float operations (explicit _rn intrinsics, nothing contracts), so the outputs are bit-exact
 // against the CPU restatement.  The two image pyramids travel in one pinned-staged copy unless the caller already has them in HBM.
-#include "lld_common.h"
+#include "lld_stereo_internal.h"
 
 namespace {
 
+using lld_stereo::RefineArgs;                       // (lld_stereo_internal.h: lld_frame_build.hip runs the same two kernels on a resident frame)
+
 constexpr int kW = 5, kL = 5;                       // w and L of Frame.cc:627,633
 constexpr int kMaxLevels = LLD_ORB_MAX_LEVELS;
-
-struct RefineArgs {
-  int n_left;
-  const float* left_xy; const int32_t* left_octave; const float* right_xy; const int32_t* best_r;
-  const uint8_t* left_img[kMaxLevels]; const uint8_t* right_img[kMaxLevels];
-  int cols[kMaxLevels], rows[kMaxLevels], lstep[kMaxLevels], rstep[kMaxLevels];
-  float scale[kMaxLevels], inv_scale[kMaxLevels];
-  float min_d, max_d, mbf;
-  float* u_right; float* depth; int32_t* sad;
-};
 
 __global__ __launch_bounds__(256) void stereo_refine_kernel(RefineArgs A) {
   const int gid = blockIdx.x * blockDim.x + threadIdx.x;
@@ -144,6 +136,13 @@ inline size_t al64(size_t b) { return (b + 63) & ~size_t(63); }
 
 }  // namespace
 
+int lld_stereo::refine_launch(hipStream_t st, const RefineArgs& A, int32_t* summary) {
+  hipLaunchKernelGGL(stereo_refine_kernel, dim3((A.n_left * 16 + 255) / 256), dim3(256), 0, st, A);
+  hipLaunchKernelGGL(stereo_median_kernel, dim3(1), dim3(1024), 0, st, A.n_left, A.u_right, A.depth, A.sad, summary);
+  LLD_HIP_TRY(hipGetLastError());
+  return LLD_OK;
+}
+
 extern "C" int lld_compute_stereo_matches(lld_ctx* ctx, const lld_keypoints* left, const lld_keypoints* right, const lld_stereo_pyramids* pyr,
                                           float mb, float mbf, lld_stereo_result* out) {
   if (!ctx || !left || !right || !pyr || !out) return LLD_ERR_INVALID;
@@ -214,9 +213,7 @@ extern "C" int lld_compute_stereo_matches(lld_ctx* ctx, const lld_keypoints* lef
   A.u_right = reinterpret_cast<float*>(d_out + r_ur); A.depth = reinterpret_cast<float*>(d_out + r_dep); A.sad = reinterpret_cast<int32_t*>(d_out + r_sad);
   hipStream_t sm = ctx->stream;
   LLD_HIP_TRY(hipMemcpyAsync(d, h, in, hipMemcpyHostToDevice, sm));
-  hipLaunchKernelGGL(stereo_refine_kernel, dim3((nl * 16 + 255) / 256), dim3(256), 0, sm, A);
-  hipLaunchKernelGGL(stereo_median_kernel, dim3(1), dim3(1024), 0, sm, nl, A.u_right, A.depth, A.sad, reinterpret_cast<int32_t*>(d_out + r_sum));
-  LLD_HIP_TRY(hipGetLastError());
+  st = lld_stereo::refine_launch(sm, A, reinterpret_cast<int32_t*>(d_out + r_sum)); if (st) return st;
   LLD_HIP_TRY(hipMemcpyAsync(h_out, d_out, outb, hipMemcpyDeviceToHost, sm));
   LLD_HIP_TRY(hipStreamSynchronize(sm));
   std::memcpy(out->u_right, h_out + r_ur, (size_t)nl * 4); std::memcpy(out->depth, h_out + r_dep, (size_t)nl * 4);

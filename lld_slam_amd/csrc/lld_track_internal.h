@@ -22,6 +22,12 @@ struct lld_frame {
   float scale[LLD_ORB_MAX_LEVELS], sigma2[LLD_ORB_MAX_LEVELS], inv_sigma2[LLD_ORB_MAX_LEVELS];
   std::vector<int32_t> octave;             // host copy (validation of queries needs none of the rest)
   lld_frame_track_state* track = nullptr;  // owned by lld_frame_track.hip (lld_track::state_free)
+  // A frame built by lld_frame_build_stereo* (lld_frame_build.hip): mvuRight / mvDepth were computed into `d` by kernels.  o_res is the start of
+  // the contiguous block u_right | depth | best_r | sad | summary that lld_frame_stereo_download fetches in one copy (u_right at o_tur); h_stage is
+  // the pinned staging of the build's one upload, owned by the frame because the build returns before that copy has run.
+  bool stereo_built = false;
+  size_t o_res = 0, o_depth = 0, o_bestr = 0, o_sad = 0, o_sum = 0, res_bytes = 0;
+  void* h_stage = nullptr;
 };
 
 namespace lld_track {

@@ -8,7 +8,7 @@ import numpy as np
 
 from . import abi
 from .abi import c_float_p, c_int32_p, c_uint32_p, c_uint8_p
-from .orb_search import Frame, StereoMatches, StereoPyramids, StereoResult, keypoints_struct
+from .orb_search import Frame, StereoBuiltFrame, StereoMatches, StereoPyramids, StereoResult, frame_stereo_params, keypoints_struct
 
 MAX_LEVELS = 16
 
@@ -159,6 +159,23 @@ class ORBextractor:
         P.scale_factors = keep["scale"].ctypes.data_as(c_float_p); P.inv_scale_factors = keep["inv"].ctypes.data_as(c_float_p)
         P.on_device = 1
         return P, keep
+
+    def build_stereo_frame_raw(self, left_index, right_index, params):
+        """lld_frame_build_stereo as it is: (status, handle)."""
+        h = C.c_void_p()
+        st = _fn(self.lib, "frame_build_stereo", [C.c_void_p, C.c_int, C.c_int, C.POINTER(abi.FrameStereoParams), C.POINTER(C.c_void_p)])(
+            self.handle, int(left_index), int(right_index), None if params is None else C.byref(params), C.byref(h))
+        return st, h
+
+    def build_stereo_frame(self, L: Frame, mb, mbf, left_index=0, right_index=1) -> StereoBuiltFrame:
+        """Frame::Frame's device part on images left_index / right_index of the last call (lld_frame_build_stereo): the stereo
+        search, the refinement and the resident frame, without the keypoints leaving HBM.  `L`: the Frame the last call returned
+        for the left image (image bounds for the grid; the host's view of the keypoints).  Queued, not waited for."""
+        prm, keep = frame_stereo_params(L, mb, mbf)
+        st, h = self.build_stereo_frame_raw(left_index, right_index, prm)
+        if st != abi.LLD_OK:
+            raise RuntimeError(f"lld_frame_build_stereo failed: {self.lib.fn('status_string')(st).decode()} (status {st})")
+        return StereoBuiltFrame(self.lib, self.ctx.handle, L, h)
 
     def close(self):
         if getattr(self, "handle", None):

@@ -614,6 +614,73 @@ class ResidentFrame:
         return out, fr
 
 
+class StereoBuiltFrame(ResidentFrame):
+    """A resident frame made by lld_frame_build_stereo / lld_frame_build_stereo_keypoints: mvuRight / mvDepth were computed on the
+    device.  Everything a ResidentFrame does works on it; `download()` waits and returns the StereoMatches, and fills `F.uright`.
+    `F` is the left Frame as the host knows it (its uright is -1 until download)."""
+
+    def __init__(self, lib, ctx, F: Frame, handle):
+        self.lib, self.ctx, self.F, self.handle = lib, ctx, F, handle
+
+    def download(self) -> StereoMatches:
+        n = self.F.n
+        out = StereoMatches(np.empty(n, np.float32), np.empty(n, np.float32), np.empty(n, np.int32), np.empty(n, np.int32), 0)
+        r = StereoResult(); r.u_right = _p(out.u_right, c_float_p); r.depth = _p(out.depth, c_float_p)
+        r.best_r = _p(out.best_r, c_int32_p); r.sad = _p(out.sad, c_int32_p)
+        fn = self.lib.fn("frame_stereo_download"); fn.argtypes = [C.c_void_p, C.POINTER(StereoResult)]; fn.restype = C.c_int
+        st = fn(self.handle, C.byref(r))
+        if st != abi.LLD_OK:
+            raise RuntimeError(f"lld_frame_stereo_download failed: {self.lib.fn('status_string')(st).decode()}")
+        out.n_matches = r.n_matches
+        self.F.uright = out.u_right.copy()
+        return out
+
+
+def frame_stereo_params(F: Frame, mb, mbf, angle=None, keypoints_on_device=False):
+    """lld_frame_stereo_params from the Frame's image bounds and level tables: (struct, arrays kept alive).  `angle`: the left
+    angles as a pointer value when they live on the device, else F.angle."""
+    F.normalise()
+    P = abi.FrameStereoParams()
+    P.grid_min_x, P.grid_min_y = float(np.float32(F.min_x)), float(np.float32(F.min_y))
+    P.grid_width_inv, P.grid_height_inv = float(F.width_inv), float(F.height_inv)
+    P.grid_cols, P.grid_rows = FRAME_GRID_COLS, FRAME_GRID_ROWS
+    P.mb, P.mbf = float(np.float32(mb)), float(np.float32(mbf))
+    P.left_angle = _p(F.angle, c_float_p) if angle is None else C.cast(C.c_void_p(angle), c_float_p)
+    P.keypoints_on_device = int(keypoints_on_device)
+    P.n_levels = int(F.scale.shape[0])
+    P.level_scale = _p(F.scale, c_float_p); P.level_sigma2 = _p(F.sigma2, c_float_p); P.level_inv_sigma2 = _p(F.inv_sigma2, c_float_p)
+    return P, dict(F=F)
+
+
+def build_stereo_frame_raw(lib, ctx, kl: Keypoints, kr: Keypoints, pyr: StereoPyramids, params):
+    """lld_frame_build_stereo_keypoints as it is: (status, handle)."""
+    fn = lib.fn("frame_build_stereo_keypoints")
+    fn.argtypes = [C.c_void_p, C.POINTER(Keypoints), C.POINTER(Keypoints), C.POINTER(StereoPyramids), C.POINTER(abi.FrameStereoParams),
+                   C.POINTER(C.c_void_p)]
+    fn.restype = C.c_int
+    h = C.c_void_p()
+    st = fn(ctx, None if kl is None else C.byref(kl), None if kr is None else C.byref(kr), None if pyr is None else C.byref(pyr),
+            None if params is None else C.byref(params), C.byref(h))
+    return st, h
+
+
+def build_stereo_frame_keypoints(lib, ctx, L: Frame, R: Frame, left_levels, right_levels, inv_scale, mb, mbf, device=None) -> StereoBuiltFrame:
+    """The stereo Frame from the caller's keypoints and host pyramids (lld_frame_build_stereo_keypoints); queued, not waited for.
+    `device`: dict of pointer values (lxy, ldesc, langle, rxy, roct, rdesc) when the keypoints already live in HBM - L.octave
+    stays on the host."""
+    kl, kr = keypoints_struct(L), keypoints_struct(R)
+    P, keep = pyramids_struct(left_levels, right_levels, L.scale, inv_scale)
+    if device is not None:
+        kl.xy = C.cast(C.c_void_p(device["lxy"]), c_float_p); kl.desc = C.cast(C.c_void_p(device["ldesc"]), c_uint32_p)
+        kr.xy = C.cast(C.c_void_p(device["rxy"]), c_float_p); kr.octave = C.cast(C.c_void_p(device["roct"]), c_int32_p)
+        kr.desc = C.cast(C.c_void_p(device["rdesc"]), c_uint32_p)
+    prm, keep2 = frame_stereo_params(L, mb, mbf, angle=None if device is None else device["langle"], keypoints_on_device=device is not None)
+    st, h = build_stereo_frame_raw(lib, ctx, kl, kr, P, prm)
+    if st != abi.LLD_OK:
+        raise RuntimeError(f"lld_frame_build_stereo_keypoints failed: {lib.fn('status_string')(st).decode()}")
+    return StereoBuiltFrame(lib, ctx, L, h)
+
+
 def fuse_search_points(lib, ctx, KF: Frame, view: FrameView, mp: dict, th=3.0):
     """ORBmatcher::Fuse(KeyFrame*, vpMapPoints, th) (src/ORBmatcher.cc:825-958) with the projection loop on the device too.
     Returns (SearchOutput, proj_uvr [n,3]); match[i] = bestIdx or -1, n_matches = nFused."""

@@ -175,7 +175,23 @@ class DeviceTrackedFrame:
     def __init__(self, ctx, F: orb_search.Frame, cam, lines: dict | None = None, gamma=0.5, **params):
         self.ctx, self.lib, self.F, self.cam = ctx, ctx.lib, F, cam
         self.res = orb_search.ResidentFrame(ctx.lib, ctx.handle, F)
-        lib = self.lib
+        self._setup(lines, gamma, params)
+
+    @classmethod
+    def from_stereo_build(cls, ctx, built: "orb_search.StereoBuiltFrame", cam, lines: dict | None = None, gamma=0.5, **params):
+        """The chain on a frame the device built (ORBextractor.build_stereo_frame / orb_search.build_stereo_frame_keypoints): the
+        handle is taken over (close() destroys it), nothing is uploaded again."""
+        h_ctx = getattr(built.ctx, "value", built.ctx)
+        if h_ctx != getattr(ctx.handle, "value", ctx.handle):
+            raise ValueError("the built frame belongs to another context")
+        self = cls.__new__(cls)
+        self.ctx, self.lib, self.F, self.cam = ctx, ctx.lib, built.F, cam
+        self.res = built
+        self._setup(lines, gamma, params)
+        return self
+
+    def _setup(self, lines, gamma, params):
+        lib, F = self.lib, self.F
         lib.fn("frame_set_lines").argtypes = [C.c_void_p, C.POINTER(FrameLines)]; lib.fn("frame_set_lines").restype = C.c_int
         lib.fn("track_params_default").argtypes = [C.POINTER(TrackParams)]; lib.fn("track_params_default").restype = None
         lib.fn("frame_track_motion_model").argtypes = [C.c_void_p, C.POINTER(TrackParams), C.POINTER(orb_search.FrameView), c_double_p,
@@ -198,7 +214,7 @@ class DeviceTrackedFrame:
             self.n_lines = int(L.n_left)
         self.params = TrackParams()
         lib.fn("track_params_default")(C.byref(self.params))
-        self.params.cam = abi.Camera(*[float(np.float32(c)) for c in cam])
+        self.params.cam = abi.Camera(*[float(np.float32(c)) for c in self.cam])
         self.params.pose.gamma = gamma
         for k_, v in params.items():
             setattr(self.params, k_, v)
