@@ -177,6 +177,84 @@ bool FrameOnDevice::TrackWithMotionModel(const TrackingMembers& tr, Frame& Cur, 
   return out.r.n_points_map >= 7;
 }
 
+bool FrameOnDevice::TrackReferenceKeyFrame(const TrackingMembers& tr, Frame& Cur, const Frame& Last, const KeyFrame* pKF, lld_bow_vocab* voc, int levelsup, TrackTrace* trace) {
+  params_.pose.gamma = tr.gamma; params_.line_md_thr = tr.mdThr;
+  // ---- mCurrentFrame.ComputeBoW() (:776): the FeatureVector stays on the device; the host copy goes into the Frame
+  {
+    const int m = nt_ + 1;
+    std::vector<int32_t> word(m), node(m), start(m + 1), feat(m); std::vector<double> value(m);
+    lld_bow_result R; std::memset(&R, 0, sizeof R);
+    R.word = word.data(); R.value = value.data(); R.node = node.data(); R.node_start = start.data(); R.feature = feat.data();
+    check(lld_frame_compute_bow(f_, voc, levelsup, &R), "lld_frame_compute_bow");
+    Cur.mFeatVec.clear();
+    for (int i = 0; i < R.n_nodes; i++) Cur.mFeatVec[(unsigned int)node[i]].assign(feat.begin() + start[i], feat.begin() + start[i + 1]);
+  }
+  // ---- gather mpReferenceKF (src/ORBmatcher.cc:161-199, :234)
+  const std::vector<MapPoint*> vpMapPointsKF = pKF->GetMapPointMatches();
+  const int n = (int)vpMapPointsKF.size();
+  std::vector<float> angle(n + 1, 0.f), pos(3 * (size_t)n + 3, 0.f); std::vector<int32_t> ids(n + 1, -1); std::vector<uint8_t> has_obs(n + 1, 0);
+  std::unordered_map<int32_t, MapPoint*> point_of;
+  for (int i = 0; i < n; i++) {
+    angle[i] = pKF->mvKeysUn[i].angle;
+    MapPoint* pMP = vpMapPointsKF[i];
+    if (!pMP || pMP->isBad()) continue;                                        // :193-197
+    ids[i] = (int32_t)pMP->mnId; point_of[ids[i]] = pMP;
+    const lld_slam::Mat P = pMP->GetWorldPos();
+    for (int k = 0; k < 3; k++) pos[3 * i + k] = P.at<float>(k);
+    has_obs[i] = pMP->Observations() > 0;
+  }
+  std::vector<int32_t> knode, kstart(1, 0), kfeat;
+  for (DBoW2::FeatureVector::const_iterator it = pKF->mFeatVec.begin(); it != pKF->mFeatVec.end(); ++it) {   // a std::map: ascending node ids
+    knode.push_back((int32_t)it->first);
+    for (size_t j = 0; j < it->second.size(); j++) kfeat.push_back((int32_t)it->second[j]);
+    kstart.push_back((int32_t)kfeat.size());
+  }
+  knode.push_back(0); kfeat.push_back(0);                                      // (never read: non-null pointers for empty lists)
+  lld_ref_keyframe kf; std::memset(&kf, 0, sizeof kf);
+  kf.n = n; kf.desc = pKF->mDescriptors.ptr<uint32_t>(); kf.angle = angle.data(); kf.point_id = ids.data(); kf.world_pos = pos.data(); kf.has_obs = has_obs.data();
+  kf.n_nodes = (int)kstart.size() - 1; kf.node = knode.data(); kf.node_start = kstart.data(); kf.feature = kfeat.data();
+  static const uint32_t no_desc[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+  if (n == 0) kf.desc = no_desc;
+  // ---- the stage, from mLastFrame.mTcw (:789): Frame::UpdatePoseMatrices of that matrix with this frame's constants
+  lld_frame_view view; std::memset(&view, 0, sizeof view);
+  for (int r = 0; r < 3; r++) {
+    for (int c = 0; c < 3; c++) view.Rcw[3 * r + c] = Last.mTcw.at<float>(r, c);
+    view.tcw[r] = Last.mTcw.at<float>(r, 3);
+  }
+  for (int r = 0; r < 3; r++) {
+    double acc = 0.0;                                                         // mOw = -mRcw.t()*mtcw: one gemm, double accumulation
+    for (int k = 0; k < 3; k++) acc += (double)view.Rcw[3 * k + r] * (double)view.tcw[k];
+    view.Ow[r] = (float)(-acc);
+  }
+  view.fx = Cur.fx; view.fy = Cur.fy; view.cx = Cur.cx; view.cy = Cur.cy; view.bf = Cur.mbf;
+  view.min_x = Cur.mnMinX; view.max_x = Cur.mnMaxX; view.min_y = Cur.mnMinY; view.max_y = Cur.mnMaxY;
+  view.log_scale_factor = Cur.mfLogScaleFactor; view.n_levels = Cur.mnScaleLevels;
+  double qt[7];
+  lld_se3_from_tcw_f32(Last.mTcw.ptr<float>(), qt);
+  check(lld_frame_track_reference_keyframe(f_, &params_, &view, qt, &kf), "lld_frame_track_reference_keyframe");
+  Outputs out(nt_, nl_, 0);
+  check(lld_frame_track_download(f_, &out.r, nullptr), "lld_frame_track_download");
+  out.to(trace, nt_, nl_, 0);
+  if (out.r.n_search < 15) {
+    // :785-786: the reference returns before it assigns the matches or sets the pose.  The chain has run on, so the device frame is handed
+    // back what the objects hold (possible only once the frame has a pose).
+    if (!Cur.mTcw.empty()) SetFrameState(tr, Cur);
+    return false;
+  }
+  // ---- write-back: mvpMapPoints = vpMapPointMatches (:788), SetPose (:789), PoseOptimization, the discard (:796-814)
+  Cur.SetPose(Last.mTcw);
+  for (int k = 0; k < nt_; k++) {
+    Cur.mvpMapPoints[k] = static_cast<MapPoint*>(NULL);
+    if (out.kp_id[k] < 0) continue;
+    MapPoint* pMP = point_of[out.kp_id[k]];
+    Cur.mvbOutlier[k] = false;                                                 // cleared by PoseOptimization for an inlier, by the discard for an outlier (:806)
+    if (out.kp_out[k]) { pMP->mbTrackInView = false; pMP->mnLastFrameSeen = Cur.mnId; }
+    else Cur.mvpMapPoints[k] = pMP;
+  }
+  set_pose(Cur, out.r);
+  return out.r.n_points_map >= 10;
+}
+
 void FrameOnDevice::SetFrameState(const TrackingMembers& tr, const Frame& Cur) {
   params_.pose.gamma = tr.gamma; params_.line_md_thr = tr.mdThr;
   std::vector<int32_t> kp_id(nt_ + 1, -1), ln_id(nl_ + 1, -1); std::vector<float> world(3 * (size_t)nt_ + 3, 0.f); std::vector<uint8_t> obs(nt_ + 1, 0), out(nt_ + 1, 0), lout(nl_ + 1, 0);

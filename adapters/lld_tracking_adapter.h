@@ -1,7 +1,8 @@
 // lld_tracking_adapter.h — host adapter for the Tracking thread's per-frame chain on live SLAM objects (round 6):
 //   bool Tracking::TrackWithMotionModel()   src/Tracking.cc:885-994   (from `mCurrentFrame.SetPose(mVelocity*mLastFrame.mTcw)` on)
 //   bool Tracking::TrackLocalMap()          src/Tracking.cc:1126-1220 (after UpdateLocalMap())
-// Both run as ONE device-resident sequence (lld_frame_track_*, include/lld_amd.h): the frame's keypoints and lines go to the device once
+//   bool Tracking::TrackReferenceKeyFrame() src/Tracking.cc:773-817   (the other common way into TrackLocalMap)
+// All run as ONE device-resident sequence (lld_frame_track_*, include/lld_amd.h): the frame's keypoints and lines go to the device once
 // (FrameOnDevice's constructor - the last step of the reference's Frame constructor), each routine gathers its map-side inputs, queues
 // its stage, fetches the stage's record and writes it back into the objects the way the reference's loops do (mvpMapPoints / mvbOutlier /
 // mvpMapLines / mvbOutlierLines / mTcw of the frame; mnLastFrameSeen, mbTrackInView, IncreaseVisible / IncreaseFound of the MapPoints;
@@ -22,6 +23,7 @@
 namespace lld_adapter {
 
 using lld_slam::Frame;
+using lld_slam::KeyFrame;
 using lld_slam::MapLine;
 using lld_slam::MapPoint;
 
@@ -48,6 +50,14 @@ class FrameOnDevice {
   // frame keeps only the raw matches of the search, with mvbOutlier false, no MapLines, the predicted pose and no marks on any MapPoint / MapLine;
   // the device frame is set to that state, so TrackLocalMap may follow it on this object as after SetFrameState.
   bool TrackWithMotionModel(const TrackingMembers& tr, Frame& mCurrentFrame, const Frame& mLastFrame, bool* mbVO = nullptr, TrackTrace* trace = nullptr);
+  // bool Tracking::TrackReferenceKeyFrame() (src/Tracking.cc:773-817) as one device sequence (lld_frame_compute_bow + lld_frame_track_reference_keyframe):
+  // mCurrentFrame.ComputeBoW() on the resident descriptors (mFeatVec is filled from the call's host result; `voc` belongs to this frame's
+  // context), the gather from mpReferenceKF (mDescriptors, mvKeysUn[k].angle, GetMapPointMatches() with NULL / isBad as -1, mFeatVec), the stage,
+  // then the write-back: mvpMapPoints, mvbOutlier, mTcw, and mbTrackInView / mnLastFrameSeen of the discarded.  Returns as :816.  Below 15 matches
+  // (:785-786) the objects stay untouched and false is returned; when mCurrentFrame has a pose the device frame is set back to what the objects
+  // hold, otherwise the caller does that (SetFrameState) before TrackLocalMap follows.
+  bool TrackReferenceKeyFrame(const TrackingMembers& tr, Frame& mCurrentFrame, const Frame& mLastFrame, const KeyFrame* mpReferenceKF, lld_bow_vocab* voc,
+                              int levelsup = 4, TrackTrace* trace = nullptr);
   // The frame's pose and matches came from another routine (Tracking::TrackReferenceKeyFrame, src/Tracking.cc:770-816, or Relocalization): hands the
   // device what mCurrentFrame holds now (mTcw, mvpMapPoints / mvbOutlier, mvpMapLines / mvbOutlierLines) so that TrackLocalMap can follow.
   void SetFrameState(const TrackingMembers& tr, const Frame& mCurrentFrame);

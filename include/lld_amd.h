@@ -858,6 +858,36 @@ typedef struct {
  * (PoseOptimization's information per level); the same for lld_frame_track_set_state. */
 int  lld_frame_track_motion_model(lld_frame* frame, const lld_track_params* params, const lld_frame_view* view, const double* pose_qt,
                                   const lld_last_frame_points* last, const int32_t* last_point_id, const lld_map_lines* last_lines);
+/* Stage 1 by Tracking::TrackReferenceKeyFrame (src/Tracking.cc:773-817): ORBmatcher(0.7, true).SearchByBoW(mpReferenceKF, mCurrentFrame)
+ * (src/ORBmatcher.cc:159-288) -> mvpMapPoints = the matches, SetPose(mLastFrame.mTcw) (:788-789) -> Optimizer::PoseOptimization (:792) ->
+ * outlier discard (:796-814), as a third entry into the chain next to lld_frame_track_motion_model: one upload of the keyframe side, no
+ * host trip, no synchronisation.  The frame's FeatureVector is the one lld_frame_compute_bow left in HBM; the keyframe's arrives as CSR
+ * and the node merge (:180-264) runs on the device: one wavefront per keyframe node looks its id up in the frame's node list, walks the
+ * node's keyframe features in list order and keeps the node's occupancy in registers, so one pass is exact.  The rotation histogram and
+ * ComputeThreeMaxima (:267-285, :1601-1642) follow in one small kernel that writes the kept matches into the frame's tables.
+ * mfNNratio = 0.7 and mbCheckOrientation = true are fixed (lld_track_params has no room for them); the frame needs its angles.
+ * The reference adds no lines here: the frame's line tables stay empty through stage 1, its lines stay uploaded for stage 2.
+ * The stage-1 record: n_search_first = n_search = SearchByBoW's return value, used_wide = 0, n_lines_matched = n_lines = 0, the rest as
+ * for lld_frame_track_motion_model.  With n_search < 15 the record describes a run the reference does not make: TrackReferenceKeyFrame
+ * returns false there (:785-786) before SetPose, PoseOptimization and the discard, while the chain runs on.  The frame then holds only the
+ * raw matches (kp_point_id >= 0, flags ignored) with the handed-in pose, as in the note on n_search < 10 above.
+ * LLD_ERR_INVALID before anything is queued, the frame unchanged: no lld_frame_compute_bow on this frame yet, a NULL argument, n outside
+ * [0, LLD_ORB_MAX_KEYPOINTS], n_nodes outside [0, n], node ids not strictly ascending, node_start not ascending from 0, feature
+ * indices outside [0, n), cam.fx or cam.fy not > 0, a frame without level_inv_sigma2 or (nt > 0) without angles. */
+typedef struct {
+  int32_t n;                        /* keypoints of mpReferenceKF                                                                                    */
+  const uint32_t* desc;             /* [n][8] pKF->mDescriptors                                                                                      */
+  const float*    angle;            /* [n] pKF->mvKeysUn[k].angle                                                                                    */
+  const int32_t*  point_id;         /* [n] id of GetMapPointMatches()[k], -1 = NULL or isBad (:193-197)                                              */
+  const float*    world_pos;        /* [n][3] GetWorldPos() of those (ignored where the id is -1)                                                    */
+  const uint8_t*  has_obs;          /* [n] Observations() > 0, or NULL: all                                                                          */
+  int32_t n_nodes;                  /* pKF->mFeatVec as lld_bow_result gives it: node ids strictly ascending, CSR node_start [n_nodes + 1], feature  */
+  const int32_t* node; const int32_t* node_start; const int32_t* feature;   /* a keyframe feature listed under two nodes is tolerated: it is tried in both, and the frame's
+                                                                               own FeatureVector keeps every frame feature under one node, which is what exactness needs */
+} lld_ref_keyframe;
+/* view / pose_qt: Frame::UpdatePoseMatrices and Converter::toSE3Quat of mLastFrame.mTcw (:789), formed as for lld_frame_track_motion_model. */
+int  lld_frame_track_reference_keyframe(lld_frame* frame, const lld_track_params* params, const lld_frame_view* view, const double* pose_qt,
+                                        const lld_ref_keyframe* kf);
 /* Stage 1 ran elsewhere: Tracking::TrackReferenceKeyFrame (src/Tracking.cc:770-816) or Tracking::Relocalization end with the same
  * PoseOptimization + outlier discard but find their matches by bag of words / PnP.  This call hands the device what such a routine left in
  * the frame, so that lld_frame_track_local_map can follow on the same handle (Tracking::Track runs TrackLocalMap after whichever routine
@@ -1239,6 +1269,16 @@ int  lld_bow_vocab_info_get(const lld_bow_vocab* v, lld_bow_vocab_info* out);
  * launches; returns with the results on the host.  Nulls, n outside 0..max_features or too many sets return LLD_ERR_INVALID
  * before anything is queued. */
 int  lld_bow_transform(lld_bow_vocab* v, int n_sets, const lld_bow_set* sets, lld_bow_result* results);
+/* Frame::ComputeBoW (src/Frame.cc) on a resident frame: the descent and the assembly of lld_bow_transform on the frame's own device
+ * descriptors (no upload), after which the FeatureVector (node, node_start, feature and their counts) is copied device to device, on the
+ * stream, into memory the frame owns: it survives every later lld_bow_transform / lld_frame_compute_bow on the vocabulary and is what
+ * lld_frame_track_reference_keyframe matches against.  out_or_null != NULL: waits and returns BowVector and FeatureVector on the host
+ * (arrays of nt entries, node_start nt + 1, as for lld_bow_transform; bit-identical to it on the same descriptors) - a frame that becomes a
+ * keyframe needs them for lld_kfdb_add.  NULL: queues the work and returns without synchronising (the frame's first call allocates).
+ * A frame without keypoints gives empty vectors and LLD_OK.  Works on frames of lld_frame_create and of lld_frame_build_stereo*.
+ * LLD_ERR_INVALID before anything is queued: a NULL frame or vocabulary, a vocabulary of another context than the frame's, more keypoints
+ * than the vocabulary's max_features, or out arrays missing as for lld_bow_transform. */
+int  lld_frame_compute_bow(lld_frame* frame, lld_bow_vocab* voc, int levelsup, lld_bow_result* out_or_null);
 /* L1Scoring::score(query, candidate c) for n_cand candidates given as CSR: candidate c holds the words
  * cand_word[cand_start[c] .. cand_start[c+1]) (strictly ascending, each in [0, n_words)) with cand_value.  One upload, one
  * launch, out[c] on return.  Malformed vectors return LLD_ERR_INVALID before anything is queued.  Staging uses the context's

@@ -411,6 +411,18 @@ class TrackedFrame {
     lld_se3_from_tcw_f32(Tcw, qt);                       // Converter::toSE3Quat(pFrame->mTcw)
     check(lld_frame_track_motion_model(f_, &params, &view, qt, &last, last_ids, last_lines), "lld_frame_track_motion_model");
   }
+  // Frame::ComputeBoW on the resident descriptors (voc: ORBVocabulary::get() of the frame's context).  out == NULL: queued, not waited for; else
+  // BowVector and FeatureVector arrive on the host as from lld_bow_transform (arrays of N() entries, node_start N() + 1).
+  void ComputeBoW(lld_bow_vocab* voc, int levelsup = 4, lld_bow_result* out = nullptr) {
+    check(lld_frame_compute_bow(f_, voc, levelsup, out), "lld_frame_compute_bow");
+  }
+  // Tracking::TrackReferenceKeyFrame (src/Tracking.cc:773-817) after ComputeBoW: SearchByBoW against mpReferenceKF, PoseOptimization from
+  // mLastFrame.mTcw (Tcw / view as for TrackWithMotionModel), the outlier discard.  Returns nothing: stage 1 of Download().
+  void TrackReferenceKeyFrame(const lld_frame_view& view, const float Tcw[16], const lld_ref_keyframe& kf) {
+    double qt[7];
+    lld_se3_from_tcw_f32(Tcw, qt);
+    check(lld_frame_track_reference_keyframe(f_, &params, &view, qt, &kf), "lld_frame_track_reference_keyframe");
+  }
   // stage 1 ran elsewhere (TrackReferenceKeyFrame / Relocalization): the frame's pose and what it holds, then TrackLocalMap as usual
   void SetState(const lld_frame_view& view, const float Tcw[16], const lld_frame_held& held) {
     double qt[7];

@@ -300,6 +300,12 @@ class FrameStereoParams(C.Structure):
                 ("level_scale", c_float_p), ("level_sigma2", c_float_p), ("level_inv_sigma2", c_float_p)]
 
 
+class RefKeyFrame(C.Structure):
+    """lld_ref_keyframe (include/lld_amd.h): mpReferenceKF as lld_frame_track_reference_keyframe reads it."""
+    _fields_ = [("n", C.c_int32), ("desc", c_uint32_p), ("angle", c_float_p), ("point_id", c_int32_p), ("world_pos", c_float_p),
+                ("has_obs", c_uint8_p), ("n_nodes", C.c_int32), ("node", c_int32_p), ("node_start", c_int32_p), ("feature", c_int32_p)]
+
+
 PRODUCT_SYMBOLS = [
     "lld_status_string", "lld_ctx_create", "lld_ctx_destroy", "lld_ctx_stream", "lld_ctx_synchronize", "lld_ctx_release_cache",
     "lld_se3_from_tcw_f32", "lld_se3_to_tcw_f32", "lld_orb_inv_level_sigma2",
@@ -318,6 +324,7 @@ PRODUCT_SYMBOLS = [
     "lld_compute_stereo_matches",
     "lld_frame_create", "lld_frame_search_last_frame", "lld_frame_search_local_points", "lld_frame_destroy",
     "lld_frame_set_lines", "lld_track_params_default", "lld_frame_track_motion_model", "lld_frame_track_local_map", "lld_frame_track_download", "lld_frame_track_set_state",
+    "lld_frame_compute_bow", "lld_frame_track_reference_keyframe",
     "lld_sim3_params_default", "lld_optimize_sim3", "lld_optimize_sim3_batch",
     "lld_pose_graph_params_default", "lld_optimize_essential_graph",
     "lld_orb_extractor_create", "lld_orb_extractor_destroy", "lld_orb_extractor_levels_get", "lld_orb_extract", "lld_orb_extractor_pyramids",
@@ -477,6 +484,11 @@ class Lib:
             f("covisibility_params_default").restype = None
             f("covisibility").argtypes = [vp, C.POINTER(CovisibilityIn), C.POINTER(CovisibilityOut)]
             f("covisibility").restype = C.c_int
+            # (frame, vocabulary, levelsup, lld_bow_result* or NULL); (frame, lld_track_params*, lld_frame_view*, pose_qt, lld_ref_keyframe*):
+            # the structs of vocabulary.py / tracking.py / orb_search.py pass by reference
+            f("frame_compute_bow").argtypes = [vp, vp, C.c_int, vp]; f("frame_compute_bow").restype = C.c_int
+            f("frame_track_reference_keyframe").argtypes = [vp, vp, vp, c_double_p, C.POINTER(RefKeyFrame)]
+            f("frame_track_reference_keyframe").restype = C.c_int
 
 
 _PRODUCT = None

@@ -22,6 +22,7 @@
 
 #include "lld_bow_score.h"
 #include "lld_common.h"
+#include "lld_track_internal.h"
 
 namespace {
 
@@ -260,9 +261,31 @@ __global__ __launch_bounds__(256) void bow_score(const int32_t* __restrict__ qpo
   if (lane == 0) out[c] = score;
 }
 
+// lld_frame_compute_bow's one-entry set table
+__global__ void bow_set_store(BowSetDev S, BowSetDev* dst) {
+  if (threadIdx.x == 0) *dst = S;
+}
+
 // ------------------------------------------------------------------------------------------------------------------ host
 
 namespace {
+
+// One set's output block (host copy) into the caller's arrays.
+int unpack_result(const char* o, int n, lld_bow_result& R) {
+  const int32_t* I = (const int32_t*)(o + (size_t)8 * n);
+  const int nw = I[0], nn = I[1];
+  if (nw < 0 || nw > n || nn < 0 || nn > n) return LLD_ERR_HIP;
+  R.n_words = nw; R.n_nodes = nn;
+  const int nv = I[2 + 2 * n + nn];              // node_start[n_nodes]
+  if (nv < 0 || nv > n) return LLD_ERR_HIP;
+  if (nw) { std::memcpy(R.value, o, (size_t)nw * 8); std::memcpy(R.word, I + 2, (size_t)nw * 4); }
+  if (nn) std::memcpy(R.node, I + 2 + n, (size_t)nn * 4);
+  std::memcpy(R.node_start, I + 2 + 2 * n, (size_t)(nn + 1) * 4);
+  if (nv) std::memcpy(R.feature, I + 3 + 3 * n, (size_t)nv * 4);
+  if (R.feature_word && n) std::memcpy(R.feature_word, I + 3 + 4 * n, (size_t)n * 4);
+  if (R.feature_nid && n) std::memcpy(R.feature_nid, I + 3 + 5 * n, (size_t)n * 4);
+  return LLD_OK;
+}
 
 // Whitespace-separated tokens of one line.
 void split(const std::string& s, std::vector<std::string>* out) {
@@ -500,23 +523,40 @@ extern "C" int lld_bow_transform(lld_bow_vocab* v, int n_sets, const lld_bow_set
   LLD_HIP_TRY(hipMemcpyAsync(v->h_out, v->d_out, out_used, hipMemcpyDeviceToHost, st));
   LLD_HIP_TRY(hipStreamSynchronize(st));
   for (int s = 0; s < n_sets; s++) {
-    const int n = sets[s].n;
-    lld_bow_result& R = results[s];
-    const char* o = v->h_out + T[s].out_off;
-    const int32_t* I = (const int32_t*)(o + (size_t)8 * n);
-    const int nw = I[0], nn = I[1];
-    if (nw < 0 || nw > n || nn < 0 || nn > n) return LLD_ERR_HIP;
-    R.n_words = nw; R.n_nodes = nn;
-    const int nv = I[2 + 2 * n + nn];            // node_start[n_nodes]
-    if (nv < 0 || nv > n) return LLD_ERR_HIP;
-    if (nw) { std::memcpy(R.value, o, (size_t)nw * 8); std::memcpy(R.word, I + 2, (size_t)nw * 4); }
-    if (nn) std::memcpy(R.node, I + 2 + n, (size_t)nn * 4);
-    std::memcpy(R.node_start, I + 2 + 2 * n, (size_t)(nn + 1) * 4);
-    if (nv) std::memcpy(R.feature, I + 3 + 3 * n, (size_t)nv * 4);
-    if (R.feature_word && n) std::memcpy(R.feature_word, I + 3 + 4 * n, (size_t)n * 4);
-    if (R.feature_nid && n) std::memcpy(R.feature_nid, I + 3 + 5 * n, (size_t)n * 4);
+    const int rc = unpack_result(v->h_out + T[s].out_off, sets[s].n, results[s]);
+    if (rc) return rc;
   }
   return LLD_OK;
+}
+
+// Frame::ComputeBoW on a resident frame (include/lld_amd.h).  The set table has one entry, written by a kernel from its arguments: the
+// vocabulary's pinned staging is not touched, so a call that returns without waiting leaves nothing a later lld_bow_transform could overwrite.
+extern "C" int lld_frame_compute_bow(lld_frame* f, lld_bow_vocab* v, int levelsup, lld_bow_result* R) {
+  if (!f || !v || f->ctx != v->ctx) return LLD_ERR_INVALID;
+  const int n = f->nt;
+  if (n < 0 || n > v->info.max_features) return LLD_ERR_INVALID;
+  if (R && (!R->node_start || (n > 0 && (!R->word || !R->value || !R->node || !R->feature)))) return LLD_ERR_INVALID;
+  LLD_HIP_TRY(hipSetDevice(v->ctx->device));
+  const size_t bytes = out_block_bytes(n);
+  if (!f->d_bow && hipMalloc(reinterpret_cast<void**>(&f->d_bow), bytes) != hipSuccess) { f->d_bow = nullptr; return LLD_ERR_ALLOC; }   // (nt is fixed for the frame's life)
+  BowSetDev S{};
+  S.desc = reinterpret_cast<const uint32_t*>(f->d + f->o_td); S.n = n;
+  S.nid_level = (int32_t)std::max<long long>(INT_MIN, std::min<long long>(INT_MAX, (long long)v->info.L - levelsup));
+  hipStream_t st = v->ctx->stream;
+  BowSetDev* dT = reinterpret_cast<BowSetDev*>(v->d_stage);
+  hipLaunchKernelGGL(bow_set_store, dim3(1), dim3(64), 0, st, S, dT);
+  if (n > 0)
+    hipLaunchKernelGGL(bow_descend, dim3((n + kDescPerBlock - 1) / kDescPerBlock, 1), dim3(256), 0, st, v->d_info, v->d_pdesc, v->d_pnode, v->d_word_of,
+                       v->d_weight, dT, v->d_fword, v->d_fnid, v->d_fw);
+  const int repeated_add = v->info.weighting == LLD_BOW_TF_IDF || v->info.weighting == LLD_BOW_TF;
+  hipLaunchKernelGGL(bow_assemble, dim3(1), dim3(kAsmThreads), 0, st, dT, v->d_fword, v->d_fnid, v->d_fw, v->d_out, repeated_add);
+  LLD_HIP_TRY(hipGetLastError());
+  LLD_HIP_TRY(hipMemcpyAsync(f->d_bow, v->d_out, bytes, hipMemcpyDeviceToDevice, st));
+  f->has_bow = true;
+  if (!R) return LLD_OK;
+  LLD_HIP_TRY(hipMemcpyAsync(v->h_out, v->d_out, bytes, hipMemcpyDeviceToHost, st));
+  LLD_HIP_TRY(hipStreamSynchronize(st));
+  return unpack_result(v->h_out, n, *R);
 }
 
 extern "C" int lld_bow_score(lld_bow_vocab* v, const lld_bow_vector* query, int n_cand, const int32_t* cand_start, const int32_t* cand_word,

@@ -549,6 +549,77 @@ int lld_frame_track_motion_model(lld_frame* f, const lld_track_params* P, const 
   return LLD_OK;
 }
 
+// Tracking::TrackReferenceKeyFrame (src/Tracking.cc:773-817) as stage 1: SearchByBoW against the FeatureVector lld_frame_compute_bow left in the
+// frame, mvpMapPoints = the matches, SetPose(mLastFrame.mTcw), PoseOptimization on the points alone, the discard of :796-814 (what
+// track_after_pose_kernel does for stage 0: the flagged leave, their flag is cleared, their id is marked seen, nmatchesMap is counted).
+int lld_frame_track_reference_keyframe(lld_frame* f, const lld_track_params* P, const lld_frame_view* view, const double* pose_qt, const lld_ref_keyframe* kf) {
+  if (!f || !P || !view || !pose_qt || !kf) return LLD_ERR_INVALID;
+  if (!f->has_bow) return LLD_ERR_INVALID;                                     // Frame::ComputeBoW comes first (:776)
+  const int n = kf->n, nn = kf->n_nodes, nt = f->nt;
+  if (n < 0 || n > LLD_ORB_MAX_KEYPOINTS || nn < 0 || nn > n) return LLD_ERR_INVALID;
+  if (n > 0 && (!kf->desc || !kf->angle || !kf->point_id || !kf->world_pos)) return LLD_ERR_INVALID;
+  if (nn > 0 && (!kf->node || !kf->node_start || !kf->feature)) return LLD_ERR_INVALID;
+  if (nt > 0 && !f->has_angle) return LLD_ERR_INVALID;                         // ORBmatcher(0.7, true): mbCheckOrientation
+  if (view->n_levels != f->consts.n_levels) return LLD_ERR_INVALID;
+  if (!(P->cam.fx > 0) || !(P->cam.fy > 0) || !f->has_inv_sigma2) return LLD_ERR_INVALID;
+  int nv = 0;
+  if (nn > 0) {
+    if (kf->node_start[0] != 0) return LLD_ERR_INVALID;
+    for (int i = 0; i < nn; i++) {
+      if (kf->node_start[i + 1] < kf->node_start[i] || kf->node_start[i + 1] > n) return LLD_ERR_INVALID;   // a feature sits under one node
+      if (i > 0 && kf->node[i] <= kf->node[i - 1]) return LLD_ERR_INVALID;
+    }
+    nv = kf->node_start[nn];
+    for (int i = 0; i < nv; i++) if (kf->feature[i] < 0 || kf->feature[i] >= n) return LLD_ERR_INVALID;
+  }
+  lld_ctx* ctx = f->ctx;
+  LLD_HIP_TRY(hipSetDevice(ctx->device));
+  int s = ensure_state(f); if (s) return s;
+  lld_frame_track_state* S = f->track;
+  fill_consts(S, f, P, view);
+  size_t o = 0;
+  auto take = [&](size_t bytes) { const size_t at = o; o += al(bytes); return at; };
+  const size_t o_pose = take(7 * 8), o_lp = take(sizeof(LineTrackDevParams)), o_view = take(sizeof(lld_frame_view));
+  const size_t o_desc = take((size_t)n * 32), o_ang = take((size_t)n * 4), o_id = take((size_t)n * 4), o_pos = take((size_t)n * 12), o_obs = take(n);
+  const size_t o_node = take((size_t)nn * 4), o_start = take((size_t)(nn + 1) * 4), o_feat = take((size_t)nv * 4);
+  const size_t up_bytes = o;
+  const size_t o_taken = take((size_t)nt * 4), o_pwork = take(pose_track_work_bytes(nt, S->nl));
+  s = ensure_work(S, ctx, o); if (s) return s;
+  s = ensure_stage(S, 0, up_bytes); if (s) return s;
+  char* h = S->h_stage[0]; char* d = S->d_work;
+  std::memcpy(h + o_pose, pose_qt, 7 * 8);
+  line_params_from_view(S->consts, *view, reinterpret_cast<LineTrackDevParams*>(h + o_lp));
+  std::memcpy(h + o_view, view, sizeof(lld_frame_view));
+  if (n) {
+    std::memcpy(h + o_desc, kf->desc, (size_t)n * 32); std::memcpy(h + o_ang, kf->angle, (size_t)n * 4); std::memcpy(h + o_id, kf->point_id, (size_t)n * 4);
+    std::memcpy(h + o_pos, kf->world_pos, (size_t)n * 12);
+    if (kf->has_obs) std::memcpy(h + o_obs, kf->has_obs, n); else std::memset(h + o_obs, 1, n);
+  }
+  if (nn) { std::memcpy(h + o_node, kf->node, (size_t)nn * 4); std::memcpy(h + o_start, kf->node_start, (size_t)(nn + 1) * 4); }
+  else std::memset(h + o_start, 0, 4);
+  if (nv) std::memcpy(h + o_feat, kf->feature, (size_t)nv * 4);
+  hipStream_t st = ctx->stream;
+  LLD_HIP_TRY(hipMemcpyAsync(d, h, up_bytes, hipMemcpyHostToDevice, st));
+  LLD_HIP_TRY(hipEventRecord(S->uploaded[0], st)); S->upload_pending[0] = true;
+  const int nmax = std::max(std::max(nt, S->nl), 64);
+  hipLaunchKernelGGL(track_reset_kernel, dim3((nmax + 255) / 256), dim3(256), 0, st, S->D, reinterpret_cast<const double*>(d + o_pose),
+                     reinterpret_cast<const lld_frame_view*>(d + o_view), reinterpret_cast<const LineTrackDevParams*>(d + o_lp));
+  BowSearchDev B{};
+  B.nt = nt; B.n_kf_nodes = nn;
+  B.f_desc = reinterpret_cast<const uint32_t*>(f->d + f->o_td); B.f_angle = reinterpret_cast<const float*>(f->d + f->o_tang);
+  B.f_n_nodes = f->bow_n_nodes(); B.f_node = f->bow_node(); B.f_node_start = f->bow_node_start(); B.f_feature = f->bow_feature();
+  B.kf_desc = reinterpret_cast<const uint32_t*>(d + o_desc); B.kf_angle = reinterpret_cast<const float*>(d + o_ang); B.kf_point_id = reinterpret_cast<const int32_t*>(d + o_id);
+  B.kf_node = reinterpret_cast<const int32_t*>(d + o_node); B.kf_node_start = reinterpret_cast<const int32_t*>(d + o_start); B.kf_feature = reinterpret_cast<const int32_t*>(d + o_feat);
+  B.nnratio = 0.7f; B.check_orientation = 1;                                   // ORBmatcher matcher(0.7,true) (:780)
+  B.taken = reinterpret_cast<int32_t*>(d + o_taken);
+  const ApplyDev ap{S->D.kp_has, S->D.kp_world, S->D.kp_id, S->D.kp_obs, reinterpret_cast<const float*>(d + o_pos), B.kf_point_id,
+                    reinterpret_cast<const uint8_t*>(d + o_obs), S->D.rec_h[0]->i + RI_SEARCH1, 0, 0};
+  s = bow_search_launch(st, B, ap); if (s) return s;
+  s = run_pose(f, st, P, d + o_pwork, 0); if (s) return s;                     // (no AddLinesFrom: track_reset_kernel left the line tables empty)
+  S->stage1_queued = true; S->n_in_view = 0;
+  return LLD_OK;
+}
+
 int lld_frame_track_set_state(lld_frame* f, const lld_track_params* P, const lld_frame_view* view, const double* pose_qt, const lld_frame_held* held) {
   if (!f || !P || !view || !pose_qt || !held) return LLD_ERR_INVALID;
   const int nt = f->nt;

@@ -1285,6 +1285,7 @@ extern "C" void lld_frame_destroy(lld_frame* f) {
   lld_track::state_free(f);
   if (f->d) (void)hipFree(f->d);
   if (f->h_stage) (void)hipHostFree(f->h_stage);
+  if (f->d_bow) (void)hipFree(f->d_bow);
   delete f;
 }
 

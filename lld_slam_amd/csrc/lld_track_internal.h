@@ -28,6 +28,14 @@ struct lld_frame {
   bool stereo_built = false;
   size_t o_res = 0, o_depth = 0, o_bestr = 0, o_sad = 0, o_sum = 0, res_bytes = 0;
   void* h_stage = nullptr;
+  // Frame::ComputeBoW (lld_frame_compute_bow, lld_bow.hip): the frame's copy of the vocabulary's output block for its nt descriptors -
+  // value[nt] f64 | int32 {n_words, n_nodes} | word[nt] | node[nt] | node_start[nt + 1] | feature[nt] | ... - so mFeatVec stays in HBM.
+  char* d_bow = nullptr; bool has_bow = false;
+  const int32_t* bow_ints() const { return reinterpret_cast<const int32_t*>(d_bow + (size_t)8 * nt); }
+  const int32_t* bow_n_nodes() const { return bow_ints() + 1; }
+  const int32_t* bow_node() const { return bow_ints() + 2 + nt; }
+  const int32_t* bow_node_start() const { return bow_ints() + 2 + 2 * (size_t)nt; }
+  const int32_t* bow_feature() const { return bow_ints() + 3 + 3 * (size_t)nt; }
 };
 
 namespace lld_track {
@@ -57,6 +65,21 @@ int orbs_project_last_frame(hipStream_t st, const lld_frame* f, const lld_frame_
 int orbs_project_local_points(hipStream_t st, const lld_frame* f, const lld_frame_view* view_h, const lld_frame_view* view_d, const MapPointsDev& mp, float cos_limit, float th,
                               void* d_qrec, uint8_t* d_in_view, int32_t* d_n_in_view);
 int orbs_launch(lld_ctx* ctx, hipStream_t st, const lld_frame* f, const void* problem_d);
+
+// ---------------------------------------------------------------- ORBmatcher::SearchByBoW(KeyFrame*, Frame&) on device arrays (lld_frame_track_bow.hip)
+// The frame's FeatureVector is the one in lld_frame::d_bow (its node count is read on the device), the keyframe's an uploaded CSR.  One
+// wavefront per keyframe node; `taken` [nt] is scratch (the keyframe feature that took frame feature k, or -1).  The accepted matches that
+// survive the rotation histogram go into the frame's tables through `ap` (q_* index keyframe features); ap.counts[0..2] = n, n, 0.
+struct BowSearchDev {
+  int nt, n_kf_nodes;
+  const uint32_t* f_desc; const float* f_angle;
+  const int32_t* f_n_nodes; const int32_t* f_node; const int32_t* f_node_start; const int32_t* f_feature;
+  const uint32_t* kf_desc; const float* kf_angle; const int32_t* kf_point_id;
+  const int32_t* kf_node; const int32_t* kf_node_start; const int32_t* kf_feature;
+  float nnratio; int check_orientation;
+  int32_t* taken;
+};
+int bow_search_launch(hipStream_t st, const BowSearchDev& in, const ApplyDev& ap);
 
 // ---------------------------------------------------------------- Tracking::AddLinesFrom on device arrays (lld_match.hip)
 struct LineTrackDevParams { double K[9]; double R[9]; double t[3]; double tr[3]; double thr_base, sx, sy; int monocular, use_grid; };   // = LineTrackParams of lld_match.hip

@@ -168,6 +168,25 @@ def map_lines_struct(ml: dict | None):
     return m, keep
 
 
+def ref_keyframe_struct(kf: dict):
+    """lld_ref_keyframe from a dict (see DeviceTrackedFrame.track_reference_keyframe); returns (struct, arrays kept alive)."""
+    from .abi import c_uint32_p
+    keep = dict(desc=np.ascontiguousarray(kf["desc"], np.uint32).reshape(-1, 8), angle=np.ascontiguousarray(kf["angle"], np.float32),
+                point_id=np.ascontiguousarray(kf["point_id"], np.int32), world_pos=np.ascontiguousarray(kf["world_pos"], np.float32).reshape(-1, 3),
+                has_obs=None if kf.get("has_obs") is None else np.ascontiguousarray(kf["has_obs"], np.uint8),
+                node=np.ascontiguousarray(kf["node"], np.int32), node_start=np.ascontiguousarray(kf["node_start"], np.int32),
+                feature=np.ascontiguousarray(kf["feature"], np.int32))
+    K = abi.RefKeyFrame()
+    K.n = keep["desc"].shape[0]
+    K.desc = keep["desc"].ctypes.data_as(c_uint32_p); K.angle = keep["angle"].ctypes.data_as(c_float_p)
+    K.point_id = keep["point_id"].ctypes.data_as(c_int32_p); K.world_pos = keep["world_pos"].ctypes.data_as(c_float_p)
+    K.has_obs = None if keep["has_obs"] is None else keep["has_obs"].ctypes.data_as(c_uint8_p)
+    K.n_nodes = keep["node"].shape[0]
+    K.node = keep["node"].ctypes.data_as(c_int32_p); K.node_start = keep["node_start"].ctypes.data_as(c_int32_p)
+    K.feature = keep["feature"].ctypes.data_as(c_int32_p)
+    return K, keep
+
+
 class DeviceTrackedFrame:
     """lld_frame_track_*: the whole per-frame sequence on the device (include/lld_amd.h).  `lines`: dict with left_lines [n,4], left_octave,
     right_lines, right_octave, line_matches, desc (the frame's mvLinesLeft / mvLinesRight / line_matches / mDescriptorsLines) or None."""
@@ -241,6 +260,37 @@ class DeviceTrackedFrame:
         ml, keep2 = map_lines_struct(last_lines)
         self._check(self.lib.fn("frame_track_motion_model")(self.res.handle, C.byref(self.params), C.byref(view), qt.ctypes.data_as(c_double_p), C.byref(m),
                                                              ids.ctypes.data_as(c_int32_p), C.byref(ml) if last_lines is not None else None), "lld_frame_track_motion_model")
+        return view, qt
+
+    def compute_bow(self, voc, levelsup=4, host=False):
+        """Frame::ComputeBoW on the resident descriptors (lld_frame_compute_bow): the FeatureVector stays in HBM with the frame.  host=True
+        waits and returns the vocabulary.BowTransform (what a new keyframe hands lld_kfdb_add); otherwise the work is only queued."""
+        from . import vocabulary as V
+        fn = self.lib.fn("frame_compute_bow")
+        if not host:
+            self._check(fn(self.res.handle, voc.handle, int(levelsup), None), "lld_frame_compute_bow")
+            return None
+        n = self.F.n; m = max(n, 1)
+        r = V.BowTransform(np.empty(m, np.int32), np.empty(m, np.float64), np.empty(m, np.int32), np.empty(m + 1, np.int32), np.empty(m, np.int32),
+                           np.empty(m, np.int32), np.empty(m, np.int32))
+        R = V.BowResult(0, r.word.ctypes.data_as(c_int32_p), r.value.ctypes.data_as(c_double_p), 0, r.node.ctypes.data_as(c_int32_p),
+                        r.node_start.ctypes.data_as(c_int32_p), r.feature.ctypes.data_as(c_int32_p), r.feature_word.ctypes.data_as(c_int32_p),
+                        r.feature_nid.ctypes.data_as(c_int32_p))
+        self._check(fn(self.res.handle, voc.handle, int(levelsup), C.byref(R)), "lld_frame_compute_bow")
+        nw, nn = R.n_words, R.n_nodes
+        return V.BowTransform(r.word[:nw], r.value[:nw], r.node[:nn], r.node_start[:nn + 1], r.feature[:int(r.node_start[nn])], r.feature_word[:n], r.feature_nid[:n])
+
+    def track_reference_keyframe(self, Tcw_last_f32, kf: dict):
+        """Queues stage 1 as Tracking::TrackReferenceKeyFrame runs it (lld_frame_track_reference_keyframe), after compute_bow.  Tcw_last_f32:
+        mLastFrame.mTcw.  kf: desc [n,8] u32, angle [n], point_id [n] (-1: no MapPoint or a bad one), world_pos [n,3], optionally has_obs
+        [n], and mpReferenceKF's FeatureVector as node / node_start / feature (a BowTransform's fields)."""
+        from .host import se3_from_tcw_f32
+        T = np.ascontiguousarray(Tcw_last_f32, np.float32).reshape(4, 4)
+        view = orb_search.frame_view(T, self.cam, self.F)
+        qt = np.ascontiguousarray(se3_from_tcw_f32(self.lib, T), np.float64)
+        K, keep = ref_keyframe_struct(kf)
+        self._check(self.lib.fn("frame_track_reference_keyframe")(self.res.handle, C.byref(self.params), C.byref(view), qt.ctypes.data_as(c_double_p), C.byref(K)),
+                    "lld_frame_track_reference_keyframe")
         return view, qt
 
     def set_state(self, Tcw_f32, kp_point_id, kp_world_pos, kp_has_obs=None, kp_outlier=None, seen_point_id=(), ln_line_id=None, ln_x0=None, ln_dir=None,
@@ -346,3 +396,45 @@ def read_harness_result(path, nt, nl, repeats):
             recs.append(d)
         ms = dict(total=np.fromfile(f, np.float64, repeats), queue_motion_model=np.fromfile(f, np.float64, repeats), queue_local_map=np.fromfile(f, np.float64, repeats))
     return recs[0], recs[1], ms
+
+
+# ------------------------------------------------------------------------------------------------ flat files of examples/refkf_harness.cpp
+def write_refkf_scene(path, sc: dict, kf: dict, Tcw_last, levelsup, gamma=0.5):
+    """A make_tracking_scene dict (its lines are not written), mpReferenceKF as DeviceTrackedFrame.track_reference_keyframe takes it and
+    mLastFrame.mTcw, as the flat binary `examples/refkf_harness` reads."""
+    F = sc["frame"]; mp = sc["map_points"]
+    T = np.ascontiguousarray(Tcw_last, np.float32).reshape(4, 4)
+    view = orb_search.frame_view(T, sc["cam"], F)
+    f32 = lambda a: np.ascontiguousarray(a, np.float32); i32 = lambda a: np.ascontiguousarray(a, np.int32); u8 = lambda a: np.ascontiguousarray(a, np.uint8)
+    n_kf, n_mp = len(kf["angle"]), len(sc["map_ids"])
+    with open(path, "wb") as f:
+        i32([F.n, F.scale.shape[0], n_kf, len(kf["node"]), len(kf["feature"]), n_mp, int(levelsup), 0]).tofile(f)
+        f32([F.min_x, F.min_y, F.max_x, F.max_y, F.width_inv, F.height_inv]).tofile(f)
+        f32(F.scale).tofile(f); f32(F.sigma2).tofile(f); f32(F.inv_sigma2).tofile(f)
+        np.array([float(np.float32(c)) for c in sc["cam"]] + [gamma], np.float64).tofile(f)
+        np.ascontiguousarray(F.desc, np.uint32).tofile(f); f32(F.xy).tofile(f); i32(F.octave).tofile(f); f32(F.uright).tofile(f); f32(F.angle).tofile(f)
+        f.write(bytes(view)); f32(T).tofile(f)
+        obs = kf.get("has_obs") if kf.get("has_obs") is not None else np.ones(n_kf, np.uint8)
+        np.ascontiguousarray(kf["desc"], np.uint32).tofile(f); f32(kf["angle"]).tofile(f); i32(kf["point_id"]).tofile(f); f32(kf["world_pos"]).tofile(f); u8(obs).tofile(f)
+        i32(kf["node"]).tofile(f); i32(kf["node_start"]).tofile(f); i32(kf["feature"]).tofile(f)
+        mobs = mp.get("has_obs") if mp.get("has_obs") is not None else np.ones(n_mp, np.uint8)
+        f32(mp["world_pos"]).tofile(f); f32(mp["normal"]).tofile(f); f32(mp["max_distance"]).tofile(f); f32(mp["min_distance"]).tofile(f)
+        np.ascontiguousarray(mp["desc"], np.uint32).tofile(f); u8(mobs).tofile(f); u8(mp["skip"]).tofile(f); i32(sc["map_ids"]).tofile(f)
+
+
+def read_refkf_result(path, nt, n_kf):
+    """What `examples/refkf_harness` wrote: dict(records=[stage 1, stage 2] of the lld_amd.hpp route, adapter=dict(...) of the object graph)."""
+    def state(f):
+        return dict(point_id=np.fromfile(f, np.int32, nt), outlier=np.fromfile(f, np.uint8, nt), Tcw=np.fromfile(f, np.float32, 16).reshape(4, 4))
+    with open(path, "rb") as f:
+        recs = []
+        for _ in range(2):
+            d = dict(pose_qt=np.fromfile(f, np.float64, 7), chi2=float(np.fromfile(f, np.float64, 1)[0]))
+            for k, v in zip(_COUNTERS, np.fromfile(f, np.int32, 14)): d[k] = int(v)
+            d["kp_point_id"] = np.fromfile(f, np.int32, nt); d["kp_outlier"] = np.fromfile(f, np.uint8, nt)
+            recs.append(d)
+        a = dict(returned=int(np.fromfile(f, np.int32, 1)[0]), after_stage1=state(f), seen=np.fromfile(f, np.uint8, n_kf), in_view=np.fromfile(f, np.uint8, n_kf))
+        nn, nv = np.fromfile(f, np.int32, 2)
+        a["feat_vec"] = dict(node=np.fromfile(f, np.int32, nn), node_start=np.fromfile(f, np.int32, nn + 1), feature=np.fromfile(f, np.int32, nv))
+        a["inliers"] = int(np.fromfile(f, np.int32, 1)[0]); a["after_stage2"] = state(f)
+    return dict(records=recs, adapter=a)
