@@ -604,7 +604,9 @@ int lld_line_hough_cells(const float* lines, int n, double sx, double sy, int32_
  *   LLD_ORB_CAND_ROWS  Frame::ComputeStereoMatches (src/Frame.cc:541-613): right keypoint iR is a
  *                      candidate of left keypoint iL iff (int)vL lies in [floor(yR-r), ceil(yR+r)],
  *                      r = 2*scale[octave_R]; index order; uR in [uL-disp_max, uL-disp_min];
- *                      a query with uL-disp_min < 0 is skipped (:577-578).
+ *                      a query with uL-disp_min < 0 is skipped (:577-578).  The reference indexes
+ *                      vRowIndices[vL] unchecked; with image_rows > 0 a query whose row (long long)vL is
+ *                      outside [0, image_rows) has no candidates (vL in (-1, 0) truncates to row 0).
  * Gates (lld_orb_search.gates, OR of LLD_ORB_GATE_*), each skips a candidate:
  *   LEVEL    octave < q_level_min || (q_level_max >= 0 && octave > q_level_max)
  *   STEREO   t_uright > 0 && fabs(q_uright - t_uright) > q_stereo_radius   (ORBmatcher.cc:90-95,1400-1406)
@@ -681,6 +683,7 @@ typedef struct {
   float   nnratio;                /* mfNNratio                                                   */
   int32_t sequential;             /* 0 | 1 occupancy by earlier queries | 2 SearchForInitialization's take-over rule        */
   int32_t check_orientation;
+  int32_t image_rows;             /* ROWS: rows of the image (vRowIndices.size(), Frame.cc:536); 0 = the query's row is not checked */
 } lld_orb_search;
 
 typedef struct {
@@ -976,7 +979,9 @@ int lld_orb_search_by_sim3(lld_ctx* ctx, const lld_orb_search* kf1, const lld_fr
  * (:690-703): median of the SAD distances, entries with dist >= 1.5f*1.4f*median are cleared.
  * All of it is integer / single-rounding float work: results are bit-exact against the CPU restatement.
  * Deviation: the reference slices cv::Mat ranges unchecked (OpenCV aborts when a patch leaves the image; ORB keeps keypoints
- * 19 px inside); here such a keypoint simply gets no stereo match. */
+ * 19 px inside); here such a keypoint simply gets no stereo match.  Likewise unchecked in the reference: vRowIndices[kp.pt.y] (:569)
+ * for a left keypoint whose row (long long)vL is not a row of level 0; here, on both routes (this call and lld_frame_build_stereo*),
+ * such a keypoint has no candidate row: best_r = -1, no match. */
 typedef struct {
   int32_t n;
   const float*    xy;           /* [n][2] mvKeys / mvKeysRight .pt */

@@ -31,6 +31,7 @@ struct RowsArgs {
   const float* right_xy; const int32_t* right_octave; const uint32_t* right_desc;
   float scale[kMaxLevels];
   float min_d, max_d;
+  int rows0;                                 // rows of level 0: a left keypoint whose row lies outside has no candidates
   int32_t* best_r;
 };
 
@@ -60,7 +61,7 @@ __global__ __launch_bounds__(kBlock) void stereo_rows_kernel(RowsArgs A) {
   const float minU = __fsub_rn(uL, A.max_d), maxU = __fsub_rn(uL, A.min_d);   // Frame.cc:574-575
   const long long row = (long long)vL;                                        // vRowIndices[vL], :569
   int best = 0x7fffffff;
-  if (!(maxU < 0.f)) {                                                        // :577-578
+  if (!(maxU < 0.f) && row >= 0 && row < A.rows0) {                           // :577-578; vRowIndices[vL] is indexed unchecked in the reference
     for (int iR = lane; iR < A.n_right; iR += kWave) {
       const int oR = A.right_octave[iR];
       if (oR < oL - 1 || oR > oL + 1) continue;                               // :589-590
@@ -161,6 +162,7 @@ int build(lld_ctx* ctx, const BuildIn& B, lld_frame** out) {
   R.right_desc = up_kp ? reinterpret_cast<const uint32_t*>(d + o_rdesc) : B.rdesc;
   for (int l = 0; l < kMaxLevels; l++) R.scale[l] = l < nlv ? B.pyr_scale[l] : 1.f;
   R.min_d = 0.0f; R.max_d = P.mbf / P.mb;                                     // minZ = mb; minD = 0; maxD = mbf / minZ (Frame.cc:558-560)
+  R.rows0 = B.rows[0];
   R.best_r = reinterpret_cast<int32_t*>(d + f->o_bestr);
 
   lld_stereo::RefineArgs A; std::memset(&A, 0, sizeof(A));

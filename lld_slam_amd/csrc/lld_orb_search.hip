@@ -46,7 +46,7 @@ struct Problem {
   const uint32_t* q_desc; const QRec* q; const int32_t* cand_idx;
   float min_x, min_y, winv, hinv; int cols, rows;
   int n_levels; float scale[LLD_ORB_MAX_LEVELS], sigma2[LLD_ORB_MAX_LEVELS], inv_sigma2[LLD_ORB_MAX_LEVELS];
-  float disp_min, disp_max, epi_x, epi_y; int only_stereo;
+  float disp_min, disp_max, epi_x, epi_y; int only_stereo; int image_rows;
   int candidates, gates, tie_last, accept_max, ratio_mode; float nnratio; int sequential, check_orientation;
   int32_t* match; int32_t* best_dist; int32_t* second_dist; uint8_t* removed; int32_t* owner; int32_t* summary;   // summary: n_matches, rounds
   int desc_in_lds, want_owner;
@@ -425,7 +425,7 @@ __global__ __launch_bounds__(kThreads) void orb_search_kernel(const Problem* __r
           // (src/Frame.cc:546-556).  Only the row buckets that can satisfy this are scanned; the exact test follows.
           const float minU = __fsub_rn(Q.u, P.disp_max), maxU = __fsub_rn(Q.u, P.disp_min);                       // Frame.cc:574-575
           const long long row = (long long)Q.v;                                                                    // vRowIndices[vL], :569
-          if (!(maxU < 0.f)) {                                                                                     // :577-578
+          if (!(maxU < 0.f) && (P.image_rows <= 0 || (row >= 0 && row < P.image_rows))) {                          // :577-578; a row outside the image has no candidates
             // buckets are (octave, row): only the octaves the level gate admits are scanned, each with its own row margin
             int o_lo = 0, o_hi = P.cols - 1;
             if (P.gates & LLD_ORB_GATE_LEVEL) { o_lo = min(max(Q.level_min, 0), P.cols - 1); if (Q.level_max >= 0) o_hi = min(Q.level_max, P.cols - 1); }
@@ -986,7 +986,7 @@ extern "C" int lld_orb_search_batch(lld_ctx* ctx, int n, const lld_orb_search* p
       P.sigma2[l] = (s.level_sigma2 && l < s.n_levels) ? s.level_sigma2[l] : 1.f;
       P.inv_sigma2[l] = (s.level_inv_sigma2 && l < s.n_levels) ? s.level_inv_sigma2[l] : 1.f;
     }
-    P.disp_min = s.disp_min; P.disp_max = s.disp_max; P.epi_x = s.epipole_x; P.epi_y = s.epipole_y; P.only_stereo = s.only_stereo;
+    P.disp_min = s.disp_min; P.disp_max = s.disp_max; P.epi_x = s.epipole_x; P.epi_y = s.epipole_y; P.only_stereo = s.only_stereo; P.image_rows = s.image_rows;
     P.candidates = s.candidates; P.gates = s.gates; P.tie_last = s.tie_last; P.accept_max = s.accept_max; P.ratio_mode = s.ratio_mode;
     P.nnratio = s.nnratio; P.sequential = s.sequential; P.check_orientation = s.check_orientation;
     P.match = reinterpret_cast<int32_t*>(d_out + L.match); P.best_dist = reinterpret_cast<int32_t*>(d_out + L.bd);

@@ -171,7 +171,7 @@ extern "C" int lld_compute_stereo_matches(lld_ctx* ctx, const lld_keypoints* lef
   S.nt = nr; S.t_desc = right->desc; S.t_xy = right->xy; S.t_octave = right->octave;
   S.nq = nl; S.q_desc = left->desc; S.q_uv = left->xy; S.q_level_min = lmin.data(); S.q_level_max = lmax.data();
   S.n_levels = nlv; S.level_scale = pyr->scale_factors;
-  S.disp_min = minD; S.disp_max = maxD;
+  S.disp_min = minD; S.disp_max = maxD; S.image_rows = pyr->rows[0];
   S.candidates = LLD_ORB_CAND_ROWS; S.gates = LLD_ORB_GATE_LEVEL; S.accept_max = (100 + 50) / 2 - 1;   // bestDist < thOrbDist
   lld_orb_search_result R; std::memset(&R, 0, sizeof(R));
   R.match = match.data(); R.best_dist = bd.data(); R.second_dist = sd.data(); R.removed = removed.data();

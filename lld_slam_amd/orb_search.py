@@ -38,6 +38,7 @@ class OrbSearch(C.Structure):
         ("only_stereo", C.c_int32),
         ("candidates", C.c_int32), ("gates", C.c_int32), ("tie_last", C.c_int32), ("accept_max", C.c_int32),
         ("ratio_mode", C.c_int32), ("nnratio", C.c_float), ("sequential", C.c_int32), ("check_orientation", C.c_int32),
+        ("image_rows", C.c_int32),
     ]
 
 

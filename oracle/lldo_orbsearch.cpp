@@ -591,10 +591,16 @@ void lldo_stereo_search(const lldo_frame* L, const lldo_frame* R, int n_rows, fl
 // Frame::ComputeStereoMatches, whole routine (src/Frame.cc:530-704), through the structs of include/lld_amd.h.  cv::Mat slicing and
 // cv::norm(IL,IR,NORM_L1) on CV_32F patches of 8-bit pixels are exact integer arithmetic; patches that would leave the image (where
 // OpenCV aborts) get no match, as in the product.  Returns the number of entries of vDistIdx that survive the median cut.
-int lldo_compute_stereo_matches(const lld_keypoints* left, const lld_keypoints* right, const lld_stereo_pyramids* pyr, float mb, float mbf,
-                                float* mvuRight, float* mvDepth, int32_t* best_r, int32_t* sad) {
+// exit_code [n_left] or NULL - a census, no part of the routine: where each left keypoint leaves it, in the routine's order
+//   1 row outside the image   2 empty row   3 maxU < 0   4 no candidate passed the octave and u gates   5 bestDist >= thOrbDist
+//   6 iniu < 0 || endu >= cols   7 patch leaves the image   8 bestincR == +-L   9 disparity outside [minD, maxD)
+//   10 matched with disparity == 0 (the 0.01 branch)   11 matched and kept   12 matched and removed by the median cut
+//   13 deltaR outside [-1, 1]: unreachable (dist2 is the first strict minimum, so |deltaR| <= 0.5), listed so that no path goes unnamed
+int lldo_compute_stereo_matches_exits(const lld_keypoints* left, const lld_keypoints* right, const lld_stereo_pyramids* pyr, float mb, float mbf,
+                                      float* mvuRight, float* mvDepth, int32_t* best_r, int32_t* sad, int32_t* exit_code) {
   const int N = left->n, Nr = right->n;
   for (int i = 0; i < N; i++) { mvuRight[i] = -1.0f; mvDepth[i] = -1.0f; if (best_r) best_r[i] = -1; if (sad) sad[i] = -1; }
+  auto leave = [&](int iL, int code) { if (exit_code) exit_code[iL] = code; };
   const int thOrbDist = (TH_HIGH + TH_LOW) / 2;
   const int nRows = pyr->rows[0];
   std::vector<std::vector<size_t>> vRowIndices(nRows);
@@ -614,19 +620,21 @@ int lldo_compute_stereo_matches(const lld_keypoints* left, const lld_keypoints* 
     const int levelL = left->octave[iL];
     const float vL = left->xy[2 * iL + 1];
     const float uL = left->xy[2 * iL];
-    if (!((long long)vL >= 0 && (long long)vL < nRows)) continue;                                       // unchecked in the reference
+    if (!((long long)vL >= 0 && (long long)vL < nRows)) { leave(iL, 1); continue; }                     // unchecked in the reference
     const std::vector<size_t>& vCandidates = vRowIndices[(size_t)vL];
-    if (vCandidates.empty()) continue;
+    if (vCandidates.empty()) { leave(iL, 2); continue; }
     const float minU = uL - maxD;
     const float maxU = uL - minD;
-    if (maxU < 0) continue;
+    if (maxU < 0) { leave(iL, 3); continue; }
     int bestDist = TH_HIGH;
     size_t bestIdxR = 0;
+    bool anyCandidate = false;                                                                          // census only
     for (size_t iC = 0; iC < vCandidates.size(); iC++) {
       const size_t iR = vCandidates[iC];
       if (right->octave[iR] < levelL - 1 || right->octave[iR] > levelL + 1) continue;
       const float uR = right->xy[2 * iR];
       if (uR >= minU && uR <= maxU) {
+        anyCandidate = true;
         const int dist = lldo_descriptor_distance(left->desc + 8 * iL, right->desc + 8 * iR);
         if (dist < bestDist) { bestDist = dist; bestIdxR = iR; }
       }
@@ -650,9 +658,9 @@ int lldo_compute_stereo_matches(const lld_keypoints* left, const lld_keypoints* 
       vDists.resize(2 * L + 1);
       const float iniu = scaleduR0 + L - w;
       const float endu = scaleduR0 + L + w + 1;
-      if (iniu < 0 || endu >= cols) continue;
+      if (iniu < 0 || endu >= cols) { leave(iL, 6); continue; }
       // rowRange / colRange outside the image: cv::Mat would abort; no match here
-      if (x0 - w < 0 || x0 + w >= cols || y0 - w < 0 || y0 + w >= rows || xr - L - w < 0 || xr + L + w >= cols) continue;
+      if (x0 - w < 0 || x0 + w >= cols || y0 - w < 0 || y0 + w >= rows || xr - L - w < 0 || xr + L + w >= cols) { leave(iL, 7); continue; }
       float IL[11][11];
       const float cL = (float)imL[(size_t)y0 * sL + x0];
       for (int r = 0; r < 2 * w + 1; r++) for (int c = 0; c < 2 * w + 1; c++) IL[r][c] = (float)imL[(size_t)(y0 - w + r) * sL + (x0 - w + c)] - cL;
@@ -668,22 +676,23 @@ int lldo_compute_stereo_matches(const lld_keypoints* left, const lld_keypoints* 
         if (dist < bestDist) { bestDist = dist; bestincR = incR; }
         vDists[L + incR] = dist;
       }
-      if (bestincR == -L || bestincR == L) continue;
+      if (bestincR == -L || bestincR == L) { leave(iL, 8); continue; }
       const float dist1 = vDists[L + bestincR - 1];
       const float dist2 = vDists[L + bestincR];
       const float dist3 = vDists[L + bestincR + 1];
       const float deltaR = (dist1 - dist3) / (2.0f * (dist1 + dist3 - 2.0f * dist2));
-      if (deltaR < -1 || deltaR > 1) continue;
+      if (deltaR < -1 || deltaR > 1) { leave(iL, 13); continue; }
       float bestuR = pyr->scale_factors[levelL] * ((float)scaleduR0 + (float)bestincR + deltaR);
       float disparity = (uL - bestuR);
       if (disparity >= minD && disparity < maxD) {
+        leave(iL, disparity <= 0 ? 10 : 11);
         if (disparity <= 0) { disparity = 0.01; bestuR = uL - 0.01; }
         mvDepth[iL] = mbf / disparity;
         mvuRight[iL] = bestuR;
         vDistIdx.push_back(std::pair<int, int>(bestDist, iL));
         if (sad) sad[iL] = bestDist;
-      }
-    }
+      } else leave(iL, 9);
+    } else leave(iL, anyCandidate ? 5 : 4);
   }
   if (vDistIdx.empty()) return 0;                                                                       // the reference reads vDistIdx[0] regardless
   std::sort(vDistIdx.begin(), vDistIdx.end());
@@ -694,9 +703,15 @@ int lldo_compute_stereo_matches(const lld_keypoints* left, const lld_keypoints* 
     if (vDistIdx[i].first < thDist) break;
     mvuRight[vDistIdx[i].second] = -1;
     mvDepth[vDistIdx[i].second] = -1;
+    leave(vDistIdx[i].second, 12);
     kept--;
   }
   return kept;
+}
+
+int lldo_compute_stereo_matches(const lld_keypoints* left, const lld_keypoints* right, const lld_stereo_pyramids* pyr, float mb, float mbf,
+                                float* mvuRight, float* mvDepth, int32_t* best_r, int32_t* sad) {
+  return lldo_compute_stereo_matches_exits(left, right, pyr, mb, mbf, mvuRight, mvDepth, best_r, sad, nullptr);
 }
 
 // Frame::isInFrustum for every MapPoint (src/Frame.cc:333-389) with the per-point part of Tracking::SearchLocalPoints
