@@ -82,6 +82,37 @@ static inline int lld_ctx_scratch(lld_ctx* ctx, size_t bytes, void** out) {
   return LLD_OK;
 }
 
+// Grow-only device buffer of exactly the size asked for (the per-call buffers of the RANSAC solvers).  LLD_ERR_ALLOC leaves *p null.
+static inline int lld_grow_device(void** p, size_t* bytes, size_t need) {
+  if (need > *bytes) {
+    if (*p) LLD_HIP_TRY(hipFree(*p));
+    *p = nullptr; *bytes = 0;
+    if (hipMalloc(p, need) != hipSuccess) { *p = nullptr; return LLD_ERR_ALLOC; }
+    *bytes = need;
+  }
+  return LLD_OK;
+}
+
+// hyp_off of one call of a batch of RANSAC solvers: solver s owns slots [off[s], off[s + 1]), bound_of_solver(s) of them when
+// it is active (active = null: all are) and none otherwise.
+template <class F>
+static inline std::vector<int32_t> ransac_call_offsets(int n, const uint8_t* active, F bound_of_solver) {
+  std::vector<int32_t> off(n + 1, 0);
+  for (int s = 0; s < n; ++s) off[s + 1] = off[s] + (!active || active[s] ? bound_of_solver(s) : 0);
+  return off;
+}
+
+// Every index[i], i < n, lies in [0, n_keypoints) and none occurs twice.
+static inline bool indices_unique_in_range(const int32_t* index, int n, int n_keypoints) {
+  std::vector<uint8_t> seen(n_keypoints, 0);
+  for (int i = 0; i < n; ++i) {
+    const int k = index[i];
+    if (k < 0 || k >= n_keypoints || seen[k]) return false;
+    seen[k] = 1;
+  }
+  return true;
+}
+
 // The context a vocabulary was created on (lld_bow.hip; internal, not exported).
 lld_ctx* lld_bow_vocab_context(const lld_bow_vocab* v);
 

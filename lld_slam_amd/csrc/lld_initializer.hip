@@ -850,28 +850,13 @@ extern "C" int lld_initializer_initialize(lld_initializer* h, int32_t n2, const 
   {                                           // mvSets (:78-97) from a fresh stream after srand(seed) (DEVIATION 1)
     uint32_t ring[31]; int32_t head;
     srand_state(h->params.seed, ring, &head);
-    std::vector<int32_t> avail(N);
-    for (int it = 0; it < its; ++it) {
-      for (int i = 0; i < N; ++i) avail[i] = i;
-      int size = N;
-      for (int j = 0; j < 8; ++j) {
-        const int r = random_int(ring, head, size);
-        sets[8 * it + j] = avail[r];
-        avail[r] = avail[size - 1];
-        --size;
-      }
-    }
+    for (int it = 0; it < its; ++it) draw_set<8>(ring, head, N, sets + 8 * it);
   }
   const size_t NN = (size_t)N;
   const size_t need = up + lld_slab::pad(sizeof(IHyp) * 2 * (size_t)its) + lld_slab::pad(sizeof(IRes)) + 2 * lld_slab::pad(NN) +
                       lld_slab::pad(sizeof(IMotion) * 8) + lld_slab::pad(8 * NN) + lld_slab::pad(sizeof(float) * 8 * NN) +
                       lld_slab::pad(sizeof(float) * 24 * NN) + lld_slab::pad(sizeof(float) * 3 * (size_t)n1) + lld_slab::pad((size_t)n1);
-  if (need > h->dcall_bytes) {
-    if (h->dcall) LLD_HIP_TRY(hipFree(h->dcall));
-    h->dcall = nullptr; h->dcall_bytes = 0;
-    if (hipMalloc(&h->dcall, need) != hipSuccess) { h->dcall = nullptr; return LLD_ERR_ALLOC; }
-    h->dcall_bytes = need;
-  }
+  if (int rc = lld_grow_device(&h->dcall, &h->dcall_bytes, need)) return rc;
   lld_slab sl; sl.base = (char*)h->dcall; sl.size = need;
   Dev d{};
   char* up_base = sl.take<char>(up);

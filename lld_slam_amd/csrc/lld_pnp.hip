@@ -27,7 +27,6 @@
 #pragma clang fp contract(off)
 
 #include <algorithm>
-#include <climits>
 #include <cmath>
 #include <vector>
 
@@ -47,8 +46,7 @@ struct PnpDesc {
 };
 
 struct PnpState {
-  uint32_t ring[31]; int32_t head;           // r[i-31 .. i-1] of glibc's TYPE_3 table, ring[head] = r[i-31]
-  uint32_t ring0[31]; int32_t head0;         // the stream at the start of the call's window
+  RansacStream rng;
   int32_t n_iter;                            // mnIterations
   int32_t best;                              // mnBestInliers
   int32_t window;                            // hypotheses drawn for this call (0: N < mRansacMinInliers)
@@ -435,15 +433,6 @@ __device__ inline bool is_inlier(const double* rt, float4 p, float2 uv, double f
   return error2 < p.w;
 }
 
-__device__ inline int solver_of(const int32_t* off, int n, int g) {
-  int lo = 0, hi = n;                        // off[lo] <= g < off[hi]
-  while (hi - lo > 1) {
-    int mid = (lo + hi) >> 1;
-    if (off[mid] <= g) lo = mid; else hi = mid;
-  }
-  return lo;
-}
-
 struct Dev {
   const float4* pt; const float2* uv; const int32_t* kp;
   const PnpDesc* desc; PnpState* st; PnpRes* res; uint8_t* flags;
@@ -471,29 +460,10 @@ __global__ void pnp_sample(Dev d) {
   int W = ds.n < ds.min_inliers ? 0 : max(n_it, ds.max_its - st.n_iter);
   if (W > bound) W = bound;                  // cannot happen: bound = max(n_it, mRansacMaxIts)
   st.window = W;
-  uint32_t* ring = st.ring;                  // advanced in place; pnp_resolve rewinds it to ring0 + the draws made
-  int32_t head = st.head;
-  for (int i = 0; i < 31; ++i) st.ring0[i] = ring[i];
-  st.head0 = head;
+  st.rng.save();                             // ring is advanced in place; pnp_resolve rewinds it to the saved one + the draws made
+  int32_t head = st.rng.head;
   int32_t* out = d.idx + 4 * d.hyp_off[s];
-  for (int k = 0; k < W; ++k) {
-    // vAvailableIndices = mvAllIndices, then 4 x (RandomInt over the remaining, take, swap the back into its place, pop): the
-    // positions overwritten so far are kept in (pos, val) pairs instead of a copy of the index list.
-    int pos[4], val[4];
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-      const int size = ds.n - i;
-      const int r = random_int(ring, head, size);
-      int v = r, back = size - 1;
-#pragma unroll
-      for (int j = 0; j < i; ++j) {            // oldest first: the newest write of a position wins
-        if (pos[j] == r) v = val[j];
-        if (pos[j] == size - 1) back = val[j];
-      }
-      out[4 * k + i] = v;
-      pos[i] = r; val[i] = back;               // vAvailableIndices[randi] = back(); pop_back()
-    }
-  }
+  for (int k = 0; k < W; ++k) draw_set<4>(st.rng.ring, head, ds.n, out + 4 * k);
 }
 
 // EPnP on the 4 correspondences of one hypothesis (compute_pose :477-525), scratch lane-interleaved in dynamic LDS.
@@ -586,7 +556,7 @@ __global__ __launch_bounds__(kHypLanes) void pnp_hyp(Dev d, int n_slots) {
 
 // One wavefront per hypothesis slot: CheckInliers' count.
 __global__ __launch_bounds__(256) void pnp_count(Dev d, int n_slots) {
-  const int g = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
+  const int g = blockIdx.x * 4 + (threadIdx.x >> 6);
   if (g >= n_slots) return;
   const int s = solver_of(d.hyp_off, d.n, g);
   if (g - d.hyp_off[s] >= d.st[s].window) return;
@@ -594,13 +564,10 @@ __global__ __launch_bounds__(256) void pnp_count(Dev d, int n_slots) {
   double rt[12];
 #pragma unroll
   for (int q = 0; q < 12; ++q) rt[q] = d.rt[12 * (size_t)g + q];
-  int cnt = 0;
-  for (int i0 = 0; i0 < ds.n; i0 += 64) {
-    const int i = i0 + lane;
-    const bool in = i < ds.n && is_inlier(rt, d.pt[ds.off + i], d.uv[ds.off + i], ds.fu, ds.fv, ds.uc, ds.vc);
-    cnt += __popcll(__ballot(in));
-  }
-  if (lane == 0) d.hyp[g] = HypRec{cnt, 0, -1, 0};
+  const int cnt = wave_count(ds.n, [&](int i) {
+    return is_inlier(rt, d.pt[ds.off + i], d.uv[ds.off + i], ds.fu, ds.fv, ds.uc, ds.vc);
+  });
+  if ((threadIdx.x & 63) == 0) d.hyp[g] = HypRec{cnt, 0, -1, 0};
 }
 
 // One lane per solver: records (strict increases of the count among eligible hypotheses) and the Refine each eligible
@@ -878,23 +845,14 @@ __global__ __launch_bounds__(kThreads) void pnp_resolve(Dev d) {
       res.tcw[q] = mode == 0 ? 0.0f : (mode == 1 ? (float)rt_sh[(q % 4) == 3 ? 9 + q / 4 : 3 * (q / 4) + q % 4]
                                                  : st.best_tcw[(q % 4) == 3 ? 9 + q / 4 : 3 * (q / 4) + q % 4]);
     mode_sh = mode;
-    // the stream after the draws made: 4 per iteration run
-    uint32_t ring[31];
-    int32_t head = st.head0;
-    for (int i = 0; i < 31; ++i) ring[i] = st.ring0[i];
-    for (int i = 0; i < 4 * run; ++i) rng_next(ring, head);
-    for (int i = 0; i < 31; ++i) st.ring[i] = ring[i];
-    st.head = head;
+    st.rng.rewind(4 * run);                  // the stream after the draws made: 4 per iteration run
   }
   __syncthreads();
-  uint8_t* fl = d.flags + ds.kp_off;
-  for (int i = tid; i < ds.n_kp; i += kThreads) fl[i] = 0;
-  __syncthreads();
-  if (mode_sh == 0) return;
-  double rt[12];
+  double rt[12];                             // read only when a pose is returned
   for (int q = 0; q < 12; ++q) rt[q] = rt_sh[q];
-  for (int i = tid; i < ds.n; i += kThreads)
-    if (is_inlier(rt, d.pt[ds.off + i], d.uv[ds.off + i], ds.fu, ds.fv, ds.uc, ds.vc)) fl[d.kp[ds.off + i]] = 1;
+  scatter_inliers<kThreads>(d.flags + ds.kp_off, ds.n_kp, mode_sh != 0, d.kp + ds.off, ds.n, [&](int i) {
+    return is_inlier(rt, d.pt[ds.off + i], d.uv[ds.off + i], ds.fu, ds.fv, ds.uc, ds.vc);
+  });
 }
 
 }  // namespace
@@ -924,13 +882,7 @@ static int pnp_check_problem(const lld_pnp_problem& q) {
   if (q.n > LLD_PNP_MAX_CORRESPONDENCES || q.n_keypoints > LLD_PNP_MAX_KEYPOINTS) return LLD_ERR_UNSUPPORTED;
   if (q.n > 0 && (!q.xyz || !q.uv || !q.sigma2 || !q.kp_index)) return LLD_ERR_INVALID;
   if (!(q.fx > 0.0f) || !(q.fy > 0.0f)) return LLD_ERR_INVALID;
-  std::vector<uint8_t> seen(q.n_keypoints, 0);
-  for (int i = 0; i < q.n; ++i) {
-    const int k = q.kp_index[i];
-    if (k < 0 || k >= q.n_keypoints || seen[k]) return LLD_ERR_INVALID;
-    seen[k] = 1;
-  }
-  return LLD_OK;
+  return indices_unique_in_range(q.kp_index, q.n, q.n_keypoints) ? LLD_OK : LLD_ERR_INVALID;
 }
 
 static int pnp_check_params(const lld_pnp_params& p) {
@@ -970,19 +922,11 @@ extern "C" int lld_pnp_batch_create(lld_ctx* ctx, int32_t n, const lld_pnp_probl
     if (nMinInliers < params->min_set) nMinInliers = params->min_set;
     float eps = eps0;
     if (N > 0 && eps < (float)nMinInliers / N) eps = (float)nMinInliers / N;
-    int nIterations;
-    if (nMinInliers == N) nIterations = 1;
-    else {
-      // N < minInliers gives epsilon > 1 and a NaN quotient; the reference's (int) of it is INT_MIN on x86-64 (budget 1), written
-      // out here instead of left to an undefined conversion.  iterate() never draws for such a solver.
-      const double q = std::ceil(std::log(1 - params->probability) / std::log(1 - std::pow(eps, 3)));
-      nIterations = std::isfinite(q) && q < 2147483647.0 ? (int)q : INT_MIN;
-    }
     ds.min_inliers = nMinInliers;
-    ds.max_its = std::max(1, std::min(nIterations, params->max_iterations));
+    ds.max_its = ransac_max_iterations(params->probability, eps, nMinInliers, N, params->max_iterations);
     ds.fu = q.fx; ds.fv = q.fy; ds.uc = q.cx; ds.vc = q.cy;
     std::memset(&st[s], 0, sizeof(PnpState));
-    srand_state(q.seed, st[s].ring, &st[s].head);
+    srand_state(q.seed, st[s].rng.ring, &st[s].rng.head);
     st[s].carried_job = -1;
     ntot += N;
     b->n_kp_total += q.n_keypoints;
@@ -1057,11 +1001,7 @@ extern "C" void lld_pnp_batch_destroy(lld_pnp_batch* b) {
 static int pnp_iterate(lld_pnp_batch* b, int32_t n_iterations, const uint8_t* active) {
   LLD_HIP_TRY(hipSetDevice(b->ctx->device));
   const int n = b->n;
-  std::vector<int32_t> off(n + 1, 0);
-  for (int s = 0; s < n; ++s) {
-    const bool on = !active || active[s];
-    off[s + 1] = off[s] + (on ? std::max(n_iterations, b->desc[s].max_its) : 0);
-  }
+  const std::vector<int32_t> off = ransac_call_offsets(n, active, [&](int s) { return std::max(n_iterations, b->desc[s].max_its); });
   const int slots = off[n];
   // the previous call's hypotheses stay readable only until this call touches the per-call buffers
   b->last_off.clear();
@@ -1072,11 +1012,9 @@ static int pnp_iterate(lld_pnp_batch* b, int32_t n_iterations, const uint8_t* ac
                 lld_slab::pad(sizeof(double) * 12 * (size_t)slots) + lld_slab::pad(sizeof(HypRec) * (size_t)slots) +
                 lld_slab::pad(sizeof(PnpJob) * ((size_t)slots + n)) + lld_slab::pad(sizeof(double) * 8 * (size_t)grid_refine * b->dev.max_n) +
                 lld_slab::pad(sizeof(int32_t) * (size_t)grid_refine * b->dev.max_n);
-  if (need > b->dcall_bytes) {
-    if (b->dcall) LLD_HIP_TRY(hipFree(b->dcall));
-    b->dcall = nullptr; b->dcall_bytes = 0;
-    if (hipMalloc(&b->dcall, need) != hipSuccess) { b->dcall = nullptr; b->dev.hyp_off = nullptr; return LLD_ERR_ALLOC; }
-    b->dcall_bytes = need;
+  if (int rc = lld_grow_device(&b->dcall, &b->dcall_bytes, need)) {
+    if (rc == LLD_ERR_ALLOC) b->dev.hyp_off = nullptr;
+    return rc;
   }
   lld_slab sl; sl.base = (char*)b->dcall; sl.size = need;
   Dev d = b->dev;

@@ -1,5 +1,6 @@
-// lld_ransac.h — device pieces shared by the RANSAC solvers (lld_pnp.hip, lld_sim3solver.hip, lld_initializer.hip): one glibc rand() stream per
-// solver (DEVIATION 1 of both sections of include/lld_amd.h), the cyclic Jacobi eigensolver and the canonical eigenvector sign.
+// lld_ransac.h — device pieces shared by the RANSAC solvers (lld_pnp.hip, lld_sim3solver.hip, lld_initializer.hip): the rand()
+// stream and minimal-set draw of lld_ransac_stream.h, the cyclic Jacobi eigensolver, the canonical eigenvector sign, and the
+// parts of a batch's count and resolve kernels that do not depend on the model.
 // Everything is in an anonymous namespace (one copy per including file) and compiled without FMA contraction.
 #ifndef LLD_RANSAC_H
 #define LLD_RANSAC_H
@@ -8,45 +9,14 @@
 
 #include <hip/hip_runtime.h>
 
+#include "lld_ransac_stream.h"
+
 #pragma clang fp contract(off)
 
 namespace {
 
 constexpr int kSweeps = 40;                  // most cyclic Jacobi sweeps
 constexpr double kJacTol = 1e-36;            // stop: sum of squared off-diagonals <= kJacTol * sum of squared diagonals
-
-// ------------------------------------------------------------------ glibc rand() on a lane
-__device__ __host__ inline uint32_t rng_next(uint32_t* ring, int32_t& head) {
-  int h = head;
-  int h3 = h + 28; if (h3 >= 31) h3 -= 31;
-  uint32_t x = ring[h] + ring[h3];
-  ring[h] = x;
-  head = h + 1 == 31 ? 0 : h + 1;
-  return x;
-}
-
-// RandomInt(0, d - 1) (Thirdparty/DBoW2/DUtils/Random.cpp:47-50): int((double)rand() / (RAND_MAX + 1.0) * d)
-__device__ __host__ inline int random_int(uint32_t* ring, int32_t& head, int d) {
-  uint32_t r = rng_next(ring, head) >> 1;
-  return int(((double)r / ((double)2147483647 + 1.0)) * (double)d);
-}
-
-static void srand_state(uint32_t seed, uint32_t* ring, int32_t* head) {
-  if (seed == 0) seed = 1;
-  int32_t r[34];
-  int32_t word = (int32_t)seed;
-  r[0] = word;
-  for (int i = 1; i < 31; ++i) {
-    int32_t hi = word / 127773, lo = word % 127773;
-    word = 16807 * lo - 2836 * hi;
-    if (word < 0) word += 2147483647;
-    r[i] = word;
-  }
-  for (int i = 31; i < 34; ++i) r[i] = r[i - 31];
-  for (int i = 0; i < 31; ++i) ring[i] = (uint32_t)r[3 + i];
-  *head = 0;
-  for (int i = 0; i < 310; ++i) rng_next(ring, *head);
-}
 
 // ------------------------------------------------------------------ strided scratch (LDS, lane-interleaved or not)
 struct SP {
@@ -102,6 +72,40 @@ __device__ void canonical_col(SP V, int n, int col, SP dst) {
     if (fabs(V[k * n + col]) > fabs(V[m * n + col])) m = k;
   bool neg = V[m * n + col] < 0.0;
   for (int k = 0; k < n; ++k) dst[k] = neg ? -V[k * n + col] : V[k * n + col];
+}
+
+// ------------------------------------------------------------------ a batch of solvers: hypothesis slots, counts, flags
+// The solver that owns hypothesis slot g of a call: off[n + 1] are the slot bounds, off[s] <= g < off[s + 1].
+__device__ inline int solver_of(const int32_t* off, int n, int g) {
+  int lo = 0, hi = n;                        // off[lo] <= g < off[hi]
+  while (hi - lo > 1) {
+    int mid = (lo + hi) >> 1;
+    if (off[mid] <= g) lo = mid; else hi = mid;
+  }
+  return lo;
+}
+
+// One wavefront: how many i < n satisfy pred(i), by ballot / popcount (the same count on every lane).
+template <class F>
+__device__ inline int wave_count(int n, F pred) {
+  const int lane = threadIdx.x & 63;
+  int cnt = 0;
+  for (int i0 = 0; i0 < n; i0 += 64) {
+    const int i = i0 + lane;
+    const bool in = i < n && pred(i);
+    cnt += __popcll(__ballot(in));
+  }
+  return cnt;
+}
+
+// The tail of a resolve workgroup of T lanes: vbInliers cleared, then, when a pose is returned, set at index[i] of every inlier.
+template <int T, class F>
+__device__ inline void scatter_inliers(uint8_t* flags, int n_flags, bool has_pose, const int32_t* index, int n, F pred) {
+  for (int i = threadIdx.x; i < n_flags; i += T) flags[i] = 0;
+  __syncthreads();
+  if (!has_pose) return;
+  for (int i = threadIdx.x; i < n; i += T)
+    if (pred(i)) flags[index[i]] = 1;
 }
 
 }  // namespace

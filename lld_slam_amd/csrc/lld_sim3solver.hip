@@ -23,7 +23,6 @@
 
 #include <algorithm>
 #include <cfloat>
-#include <climits>
 #include <cmath>
 #include <vector>
 
@@ -43,8 +42,7 @@ struct S3Desc {
 };
 
 struct S3State {
-  uint32_t ring[31]; int32_t head;           // r[i-31 .. i-1] of glibc's TYPE_3 table, ring[head] = r[i-31]
-  uint32_t ring0[31]; int32_t head0;         // the stream at the start of the call's window
+  RansacStream rng;
   int32_t n_iter;                            // mnIterations
   int32_t best;                              // mnBestInliers
   int32_t window;                            // hypotheses drawn for this call
@@ -215,15 +213,6 @@ __device__ void horn(const float P1[3][3], const float P2[3][3], bool fix_scale,
   h.s = s;
 }
 
-__device__ inline int solver_of(const int32_t* off, int n, int g) {
-  int lo = 0, hi = n;                        // off[lo] <= g < off[hi]
-  while (hi - lo > 1) {
-    int mid = (lo + hi) >> 1;
-    if (off[mid] <= g) lo = mid; else hi = mid;
-  }
-  return lo;
-}
-
 struct Dev {
   const float4* x1; const float4* x2; const float4* im; const int32_t* i1;
   const S3Desc* desc; S3State* st; S3Res* res; uint8_t* flags;
@@ -246,29 +235,10 @@ __global__ void s3_sample(Dev d) {
   int W = ds.n < ds.min_inliers ? 0 : max(0, min(n_it, ds.max_its - st.n_iter));
   if (W > bound) W = bound;                  // cannot happen: bound = min(n_it, mRansacMaxIts)
   st.window = W;
-  uint32_t* ring = st.ring;                  // advanced in place; s3_resolve rewinds it to ring0 + the draws made
-  int32_t head = st.head;
-  for (int i = 0; i < 31; ++i) st.ring0[i] = ring[i];
-  st.head0 = head;
+  st.rng.save();                             // ring is advanced in place; s3_resolve rewinds it to the saved one + the draws made
+  int32_t head = st.rng.head;
   S3Hyp* out = d.hyp + d.hyp_off[s];
-  for (int k = 0; k < W; ++k) {
-    // vAvailableIndices = mvAllIndices, then 3 x (RandomInt over the remaining, take, swap the back into its place, pop): the
-    // positions overwritten so far are kept in (pos, val) pairs instead of a copy of the index list.
-    int pos[3], val[3];
-#pragma unroll
-    for (int i = 0; i < 3; ++i) {
-      const int size = ds.n - i;
-      const int r = random_int(ring, head, size);
-      int v = r, back = size - 1;
-#pragma unroll
-      for (int j = 0; j < i; ++j) {            // oldest first: the newest write of a position wins
-        if (pos[j] == r) v = val[j];
-        if (pos[j] == size - 1) back = val[j];
-      }
-      out[k].idx[i] = v;
-      pos[i] = r; val[i] = back;               // vAvailableIndices[randi] = back(); pop_back()
-    }
-  }
+  for (int k = 0; k < W; ++k) draw_set<3>(st.rng.ring, head, ds.n, out[k].idx);
 }
 
 // ComputeSim3 on one hypothesis per lane.
@@ -293,7 +263,7 @@ __global__ __launch_bounds__(kHypLanes) void s3_hyp(Dev d, int n_slots) {
 }
 
 __global__ __launch_bounds__(256) void s3_count(Dev d, int n_slots) {
-  const int g = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
+  const int g = blockIdx.x * 4 + (threadIdx.x >> 6);
   if (g >= n_slots) return;
   const int s = solver_of(d.hyp_off, d.n, g);
   if (g - d.hyp_off[s] >= d.st[s].window) return;
@@ -301,13 +271,10 @@ __global__ __launch_bounds__(256) void s3_count(Dev d, int n_slots) {
   float T12[12], T21[12];
 #pragma unroll
   for (int q = 0; q < 12; ++q) { T12[q] = d.hyp[g].T12[q]; T21[q] = d.hyp[g].T21[q]; }
-  int cnt = 0;
-  for (int i0 = 0; i0 < ds.n; i0 += 64) {
-    const int i = i0 + lane;
-    const bool in = i < ds.n && is_inlier(T12, T21, d.x1[ds.off + i], d.x2[ds.off + i], d.im[ds.off + i], ds.k1, ds.k2);
-    cnt += __popcll(__ballot(in));
-  }
-  if (lane == 0) d.hyp[g].n_inliers = cnt;
+  const int cnt = wave_count(ds.n, [&](int i) {
+    return is_inlier(T12, T21, d.x1[ds.off + i], d.x2[ds.off + i], d.im[ds.off + i], ds.k1, ds.k2);
+  });
+  if ((threadIdx.x & 63) == 0) d.hyp[g].n_inliers = cnt;
 }
 
 __global__ __launch_bounds__(kThreads) void s3_resolve(Dev d) {
@@ -352,23 +319,14 @@ __global__ __launch_bounds__(kThreads) void s3_resolve(Dev d) {
     for (int q = 0; q < 3; ++q) res.t[q] = st.best_t[q];
     res.s = st.best_s;
     has_sh = has;
-    // the stream after the draws made: 3 per iteration run
-    uint32_t ring[31];
-    int32_t head = st.head0;
-    for (int i = 0; i < 31; ++i) ring[i] = st.ring0[i];
-    for (int i = 0; i < 3 * run; ++i) rng_next(ring, head);
-    for (int i = 0; i < 31; ++i) st.ring[i] = ring[i];
-    st.head = head;
+    st.rng.rewind(3 * run);                  // the stream after the draws made: 3 per iteration run
   }
   __syncthreads();
-  uint8_t* fl = d.flags + ds.fl_off;
-  for (int i = tid; i < ds.n1; i += kThreads) fl[i] = 0;
-  __syncthreads();
-  if (!has_sh) return;
-  float T12[12], T21[12];
+  float T12[12], T21[12];                    // read only when a pose is returned
   for (int q = 0; q < 12; ++q) { T12[q] = T_sh[q]; T21[q] = T_sh[12 + q]; }
-  for (int i = tid; i < ds.n; i += kThreads)
-    if (is_inlier(T12, T21, d.x1[ds.off + i], d.x2[ds.off + i], d.im[ds.off + i], ds.k1, ds.k2)) fl[d.i1[ds.off + i]] = 1;
+  scatter_inliers<kThreads>(d.flags + ds.fl_off, ds.n1, has_sh != 0, d.i1 + ds.off, ds.n, [&](int i) {
+    return is_inlier(T12, T21, d.x1[ds.off + i], d.x2[ds.off + i], d.im[ds.off + i], ds.k1, ds.k2);
+  });
 }
 
 }  // namespace
@@ -395,14 +353,10 @@ static int s3_check_problem(const lld_sim3solver_problem& q) {
   if (q.n > LLD_SIM3S_MAX_CORRESPONDENCES || q.n1 > LLD_SIM3S_MAX_KEYPOINTS) return LLD_ERR_UNSUPPORTED;
   if (q.n > 0 && (!q.xyz1 || !q.xyz2 || !q.sigma2_1 || !q.sigma2_2 || !q.index1)) return LLD_ERR_INVALID;
   if (!(q.fx1 > 0.0f) || !(q.fy1 > 0.0f) || !(q.fx2 > 0.0f) || !(q.fy2 > 0.0f)) return LLD_ERR_INVALID;
-  std::vector<uint8_t> seen(q.n1, 0);
-  for (int i = 0; i < q.n; ++i) {
-    const int k = q.index1[i];
-    if (k < 0 || k >= q.n1 || seen[k]) return LLD_ERR_INVALID;
-    seen[k] = 1;
+  if (!indices_unique_in_range(q.index1, q.n, q.n1)) return LLD_ERR_INVALID;
+  for (int i = 0; i < q.n; ++i)
     for (float s2 : {q.sigma2_1[i], q.sigma2_2[i]})
       if (!(s2 >= 0.0f) || !(9.210 * s2 < 4294967296.0)) return LLD_ERR_INVALID;   // NaN and inf fail too
-  }
   return LLD_OK;
 }
 
@@ -457,19 +411,11 @@ extern "C" int lld_sim3solver_batch_create(lld_ctx* ctx, int32_t n, const lld_si
     // SetRansacParameters (:114-138), literally
     const int N = q.n;
     const int minInliers = params->min_inliers;
-    const float epsilon = (float)minInliers / N;
-    int nIterations;
-    if (minInliers == N) nIterations = 1;
-    else {
-      // N < minInliers gives epsilon > 1 (N = 0: inf) and a NaN quotient; the reference's (int) of it is INT_MIN on x86-64
-      // (budget 1), written out here instead of left to an undefined conversion.  iterate() never draws for such a solver.
-      const double qt = std::ceil(std::log(1 - params->probability) / std::log(1 - std::pow(epsilon, 3)));
-      nIterations = std::isfinite(qt) && qt < 2147483647.0 ? (int)qt : INT_MIN;
-    }
+    const float epsilon = (float)minInliers / N;                  // N = 0: inf
     ds.min_inliers = minInliers;
-    ds.max_its = std::max(1, std::min(nIterations, params->max_iterations));
+    ds.max_its = ransac_max_iterations(params->probability, epsilon, minInliers, N, params->max_iterations);
     std::memset(&st[s], 0, sizeof(S3State));
-    srand_state(q.seed, st[s].ring, &st[s].head);
+    srand_state(q.seed, st[s].rng.ring, &st[s].rng.head);
     ntot += N;
     b->n1_total += q.n1;
   }
@@ -544,21 +490,17 @@ extern "C" void lld_sim3solver_batch_destroy(lld_sim3solver_batch* b) {
 static int s3_iterate(lld_sim3solver_batch* b, int32_t n_iterations, const uint8_t* active) {
   LLD_HIP_TRY(hipSetDevice(b->ctx->device));
   const int n = b->n;
-  std::vector<int32_t> off(n + 1, 0);
-  for (int s = 0; s < n; ++s) {
-    const bool on = !active || active[s];
+  const std::vector<int32_t> off = ransac_call_offsets(n, active, [&](int s) {
     const int its = b->desc[s].max_its;
-    off[s + 1] = off[s] + (on ? (n_iterations > 0 ? std::min(n_iterations, its) : its) : 0);
-  }
+    return n_iterations > 0 ? std::min(n_iterations, its) : its;
+  });
   const int slots = off[n];
   // the previous call's hypotheses stay readable only until this call touches the per-call buffers
   b->last_off.clear();
   size_t need = lld_slab::pad(sizeof(int32_t) * (n + 1)) + lld_slab::pad(sizeof(S3Hyp) * (size_t)std::max(slots, 1));
-  if (need > b->dcall_bytes) {
-    if (b->dcall) LLD_HIP_TRY(hipFree(b->dcall));
-    b->dcall = nullptr; b->dcall_bytes = 0;
-    if (hipMalloc(&b->dcall, need) != hipSuccess) { b->dcall = nullptr; b->dev.hyp_off = nullptr; return LLD_ERR_ALLOC; }
-    b->dcall_bytes = need;
+  if (int rc = lld_grow_device(&b->dcall, &b->dcall_bytes, need)) {
+    if (rc == LLD_ERR_ALLOC) b->dev.hyp_off = nullptr;
+    return rc;
   }
   lld_slab sl; sl.base = (char*)b->dcall; sl.size = need;
   Dev d = b->dev;

@@ -2,13 +2,12 @@
 RANSAC state stays in HBM between iterate() calls.  The rules and the two deviations are those of include/lld_amd.h."""
 from __future__ import annotations
 
-import ctypes as C
 from dataclasses import dataclass
 
 import numpy as np
 
-from . import abi
-from .abi import PnPHypothesis, PnPParams, PnPProblem, PnPResult, c_float_p, c_int32_p, c_uint8_p
+from ._ransac_batch import RansacBatch
+from .abi import PnPHypothesis, PnPParams, PnPProblem, PnPResult, c_float_p, c_int32_p
 
 MAX_CORRESPONDENCES = 8192   # LLD_PNP_MAX_CORRESPONDENCES
 MAX_KEYPOINTS = 8192         # LLD_PNP_MAX_KEYPOINTS
@@ -60,99 +59,31 @@ def problem_from_scene(sc):
     return _Problem(sc["xyz"], sc["uv"], sc["sigma2"], sc["kp_index"], sc["n_keypoints"], sc["fx"], sc["fy"], sc["cx"], sc["cy"], sc["seed"])
 
 
-class PnPsolverBatch:
+class PnPsolverBatch(RansacBatch):
     """n PnPsolvers (PnPsolver(F, vpMapPointMatches) + SetRansacParameters) resident on the device.  Each problem is a dict
     with xyz, uv, sigma2, kp_index, n_keypoints, fx, fy, cx, cy, seed."""
+    prefix, Error, max_iterations = "pnp", PnPError, MAX_ITERATIONS
+    Problem, ProblemC, ResultC, HypothesisC = _Problem, PnPProblem, PnPResult, PnPHypothesis
+    from_scene, make_params = staticmethod(problem_from_scene), staticmethod(_params)
 
     def __init__(self, ctx, problems, params=DEFAULT_PARAMS):
-        self.ctx = ctx
-        self.lib = ctx.lib
-        self._p = [p if isinstance(p, _Problem) else problem_from_scene(p) for p in problems]
-        arr = (PnPProblem * len(self._p))(*[p.c for p in self._p])
-        self._params = _params(params)
-        h = C.c_void_p()
-        st = self.lib.fn("pnp_batch_create")(ctx.handle, len(self._p), arr, C.byref(self._params), C.byref(h))
-        if st != abi.LLD_OK:
-            raise PnPError("lld_pnp_batch_create", st)
-        self.handle = h
-        self.n = len(self._p)
+        super().__init__(ctx, problems, params)
 
-    def iterate(self, nIterations=5, active=None):
-        """iterate(nIterations) on every active solver (one device-resident sequence); returns the outputs of all solvers
-        (inactive ones keep their previous outputs)."""
-        self.iterate_async(nIterations, active)
-        return self.download()
+    @staticmethod
+    def n_flags(p):
+        return p.n_keypoints
 
-    def iterate_async(self, nIterations=5, active=None):
-        act = None
-        if active is not None:
-            self._act = np.ascontiguousarray(np.asarray(active, bool).astype(np.uint8))
-            act = self._act.ctypes.data_as(c_uint8_p)
-        st = self.lib.fn("pnp_batch_iterate")(self.handle, int(nIterations), act)
-        if st != abi.LLD_OK:
-            raise PnPError("lld_pnp_batch_iterate", st)
-
-    def find(self, active=None):
-        """find() on every active solver: iterate(mRansacMaxIts) of each, continuing its state."""
-        act = None
-        if active is not None:
-            self._act = np.ascontiguousarray(np.asarray(active, bool).astype(np.uint8))
-            act = self._act.ctypes.data_as(c_uint8_p)
-        st = self.lib.fn("pnp_batch_find")(self.handle, act)
-        if st != abi.LLD_OK:
-            raise PnPError("lld_pnp_batch_find", st)
-        return self.download()
-
-    def download(self):
-        res = (PnPResult * self.n)()
-        bufs = []
-        for i, p in enumerate(self._p):
-            b = np.zeros(max(p.n_keypoints, 1), np.uint8)
-            bufs.append(b)
-            res[i].inlier = b.ctypes.data_as(c_uint8_p)
-        st = self.lib.fn("pnp_batch_download")(self.handle, res)
-        if st != abi.LLD_OK:
-            raise PnPError("lld_pnp_batch_download", st)
-        out = []
-        for i, p in enumerate(self._p):
-            r = res[i]
-            T = np.array(r.Tcw[:], np.float32).reshape(3, 4) if r.has_pose else None
-            out.append(PnPOutput(T, bool(r.no_more), bufs[i][:p.n_keypoints].copy(), r.n_inliers, r.iterations, r.best_inliers))
-        return out
+    @staticmethod
+    def output(r, inliers):
+        T = np.array(r.Tcw[:], np.float32).reshape(3, 4) if r.has_pose else None
+        return PnPOutput(T, bool(r.no_more), inliers, r.n_inliers, r.iterations, r.best_inliers)
 
     def hypotheses(self, solver, capacity=None):
         """Diagnostic: (n_window, n_run, records) of the last iterate call of one solver; records is a list of dicts with
         n_inliers, record, refine (-1 / 0 / 1), refined_inliers, R (3x3), t (3)."""
-        cap = capacity if capacity is not None else MAX_ITERATIONS
-        nw, nr = C.c_int32(), C.c_int32()
-        st = self.lib.fn("pnp_batch_hypotheses")(self.handle, solver, 0, None, C.byref(nw), C.byref(nr))
-        if st != abi.LLD_OK:
-            raise PnPError("lld_pnp_batch_hypotheses", st)
-        m = min(cap, nw.value)
-        buf = (PnPHypothesis * max(m, 1))()
-        st = self.lib.fn("pnp_batch_hypotheses")(self.handle, solver, m, buf, C.byref(nw), C.byref(nr))
-        if st != abi.LLD_OK:
-            raise PnPError("lld_pnp_batch_hypotheses", st)
-        recs = [dict(n_inliers=h.n_inliers, record=h.record, refine=h.refine, refined_inliers=h.refined_inliers,
-                     R=np.array(h.R[:]).reshape(3, 3), t=np.array(h.t[:])) for h in buf[:m]]
-        return nw.value, nr.value, recs
-
-    def close(self):
-        if getattr(self, "handle", None):
-            self.lib.fn("pnp_batch_destroy")(self.handle)
-            self.handle = None
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *a):
-        self.close()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
+        nw, nr, hyps = self._hypotheses(solver, capacity)
+        return nw, nr, [dict(n_inliers=h.n_inliers, record=h.record, refine=h.refine, refined_inliers=h.refined_inliers,
+                             R=np.array(h.R[:]).reshape(3, 3), t=np.array(h.t[:])) for h in hyps]
 
 
 class PnPsolver(PnPsolverBatch):

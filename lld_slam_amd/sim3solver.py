@@ -2,13 +2,12 @@
 state stays in HBM between iterate() calls.  The rules and the two deviations are those of include/lld_amd.h."""
 from __future__ import annotations
 
-import ctypes as C
 from dataclasses import dataclass
 
 import numpy as np
 
-from . import abi
-from .abi import Sim3SolverHypothesis, Sim3SolverParams, Sim3SolverProblem, Sim3SolverResult, c_float_p, c_int32_p, c_uint8_p
+from ._ransac_batch import RansacBatch
+from .abi import Sim3SolverHypothesis, Sim3SolverParams, Sim3SolverProblem, Sim3SolverResult, c_float_p, c_int32_p
 
 MAX_CORRESPONDENCES = 8192   # LLD_SIM3S_MAX_CORRESPONDENCES
 MAX_KEYPOINTS = 8192         # LLD_SIM3S_MAX_KEYPOINTS
@@ -74,101 +73,33 @@ def problem_from_scene(sc):
                     sc["Rcw2"], sc["tcw2"], sc["K1"], sc["K2"], sc["fix_scale"], sc["seed"])
 
 
-class Sim3SolverBatch:
+class Sim3SolverBatch(RansacBatch):
     """n Sim3Solvers (Sim3Solver(pKF1, pKF2, vpMatched12, bFixScale) + SetRansacParameters) resident on the device.  Each
     problem is a dict with xyz1, xyz2, sigma2_1, sigma2_2, index1, n1, Rcw1, tcw1, Rcw2, tcw2, K1, K2, fix_scale, seed."""
+    prefix, Error, max_iterations = "sim3solver", Sim3SolverError, MAX_ITERATIONS
+    Problem, ProblemC, ResultC, HypothesisC = _Problem, Sim3SolverProblem, Sim3SolverResult, Sim3SolverHypothesis
+    from_scene, make_params = staticmethod(problem_from_scene), staticmethod(_params)
 
     def __init__(self, ctx, problems, params=DEFAULT_PARAMS):
-        self.ctx = ctx
-        self.lib = ctx.lib
-        self._p = [p if isinstance(p, _Problem) else problem_from_scene(p) for p in problems]
-        arr = (Sim3SolverProblem * len(self._p))(*[p.c for p in self._p])
-        self._params = _params(params)
-        h = C.c_void_p()
-        st = self.lib.fn("sim3solver_batch_create")(ctx.handle, len(self._p), arr, C.byref(self._params), C.byref(h))
-        if st != abi.LLD_OK:
-            raise Sim3SolverError("lld_sim3solver_batch_create", st)
-        self.handle = h
-        self.n = len(self._p)
+        super().__init__(ctx, problems, params)
 
-    def _active(self, active):
-        if active is None:
-            return None
-        self._act = np.ascontiguousarray(np.asarray(active, bool).astype(np.uint8))
-        return self._act.ctypes.data_as(c_uint8_p)
+    @staticmethod
+    def n_flags(p):
+        return p.n1
 
-    def iterate(self, nIterations=5, active=None):
-        """iterate(nIterations) on every active solver (one device-resident sequence); returns the outputs of all solvers
-        (inactive ones keep their previous outputs)."""
-        self.iterate_async(nIterations, active)
-        return self.download()
-
-    def iterate_async(self, nIterations=5, active=None):
-        st = self.lib.fn("sim3solver_batch_iterate")(self.handle, int(nIterations), self._active(active))
-        if st != abi.LLD_OK:
-            raise Sim3SolverError("lld_sim3solver_batch_iterate", st)
-
-    def find(self, active=None):
-        """find() on every active solver: iterate(mRansacMaxIts) of each, continuing its state."""
-        st = self.lib.fn("sim3solver_batch_find")(self.handle, self._active(active))
-        if st != abi.LLD_OK:
-            raise Sim3SolverError("lld_sim3solver_batch_find", st)
-        return self.download()
-
-    def download(self):
-        res = (Sim3SolverResult * self.n)()
-        bufs = []
-        for i, p in enumerate(self._p):
-            b = np.zeros(max(p.n1, 1), np.uint8)
-            bufs.append(b)
-            res[i].inlier = b.ctypes.data_as(c_uint8_p)
-        st = self.lib.fn("sim3solver_batch_download")(self.handle, res)
-        if st != abi.LLD_OK:
-            raise Sim3SolverError("lld_sim3solver_batch_download", st)
-        out = []
-        for i, p in enumerate(self._p):
-            r = res[i]
-            T = np.array(r.T12[:], np.float32).reshape(3, 4) if r.has_pose else None
-            out.append(Sim3SolverOutput(T, bool(r.no_more), bufs[i][:p.n1].copy(), r.n_inliers, r.iterations, r.best_inliers,
-                                        np.array(r.R[:], np.float32).reshape(3, 3), np.array(r.t[:], np.float32),
-                                        np.float32(r.s)))
-        return out
+    @staticmethod
+    def output(r, inliers):
+        T = np.array(r.T12[:], np.float32).reshape(3, 4) if r.has_pose else None
+        return Sim3SolverOutput(T, bool(r.no_more), inliers, r.n_inliers, r.iterations, r.best_inliers,
+                                np.array(r.R[:], np.float32).reshape(3, 3), np.array(r.t[:], np.float32), np.float32(r.s))
 
     def hypotheses(self, solver, capacity=None):
         """Diagnostic: (n_window, n_run, records) of the last iterate call of one solver; records is a list of dicts with
         n_inliers, record, idx (3), s, R (3x3), t (3), T12 (3x4), all floats as float32."""
-        cap = capacity if capacity is not None else MAX_ITERATIONS
-        nw, nr = C.c_int32(), C.c_int32()
-        fn = self.lib.fn("sim3solver_batch_hypotheses")
-        st = fn(self.handle, solver, 0, None, C.byref(nw), C.byref(nr))
-        if st != abi.LLD_OK:
-            raise Sim3SolverError("lld_sim3solver_batch_hypotheses", st)
-        m = min(cap, nw.value)
-        buf = (Sim3SolverHypothesis * max(m, 1))()
-        st = fn(self.handle, solver, m, buf, C.byref(nw), C.byref(nr))
-        if st != abi.LLD_OK:
-            raise Sim3SolverError("lld_sim3solver_batch_hypotheses", st)
-        recs = [dict(n_inliers=h.n_inliers, record=h.record, idx=list(h.idx), s=np.float32(h.s),
-                     R=np.array(h.R[:], np.float32).reshape(3, 3), t=np.array(h.t[:], np.float32),
-                     T12=np.array(h.T12[:], np.float32).reshape(3, 4)) for h in buf[:m]]
-        return nw.value, nr.value, recs
-
-    def close(self):
-        if getattr(self, "handle", None):
-            self.lib.fn("sim3solver_batch_destroy")(self.handle)
-            self.handle = None
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *a):
-        self.close()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
+        nw, nr, hyps = self._hypotheses(solver, capacity)
+        return nw, nr, [dict(n_inliers=h.n_inliers, record=h.record, idx=list(h.idx), s=np.float32(h.s),
+                             R=np.array(h.R[:], np.float32).reshape(3, 3), t=np.array(h.t[:], np.float32),
+                             T12=np.array(h.T12[:], np.float32).reshape(3, 4)) for h in hyps]
 
 
 class Sim3Solver(Sim3SolverBatch):

@@ -12,7 +12,7 @@ from __future__ import annotations
 
 import numpy as np
 
-from pnp_ref import GlibcRand, JACOBI_SWEEPS, JACOBI_TOL
+from pnp_ref import GlibcRand, JACOBI_SWEEPS, JACOBI_TOL, draw_set
 
 F32 = np.float32
 F64 = np.float64
@@ -213,15 +213,7 @@ def normalize(keys):
 def build_sets(N, iterations, seed):
     """mvSets (:78-97) from a fresh stream after srand(seed)."""
     rng = GlibcRand(seed)
-    sets = np.zeros((iterations, 8), np.int64)
-    for it in range(iterations):
-        avail = list(range(N))
-        for j in range(8):
-            r = rng.random_int(0, len(avail) - 1)
-            sets[it, j] = avail[r]
-            avail[r] = avail[-1]
-            avail.pop()
-    return sets
+    return np.array([draw_set(rng, N, 8) for _ in range(iterations)], np.int64).reshape(iterations, 8)
 
 
 @_quiet

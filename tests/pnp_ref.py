@@ -63,6 +63,19 @@ class GlibcRand:
         return int((float(self.rand()) / (float(RAND_MAX) + 1.0)) * d) + lo
 
 
+def draw_set(rng: GlibcRand, N: int, K: int) -> list[int]:
+    """One minimal set: vAvailableIndices = mvAllIndices, then K x (RandomInt over the remaining, take, move the back into its
+    place, pop_back)."""
+    avail = list(range(N))
+    idx = []
+    for _ in range(K):
+        r = rng.random_int(0, len(avail) - 1)
+        idx.append(avail[r])
+        avail[r] = avail[-1]
+        avail.pop()
+    return idx
+
+
 def glibc_rand_sequence(seed: int, n: int) -> list[int]:
     g = GlibcRand(seed)
     return [g.rand() for _ in range(n)]
@@ -569,14 +582,7 @@ class PnPsolverRef:
         return check_inliers(R, t, self.xyz, self.uv, self.max_error, self.fu, self.fv, self.uc, self.vc)
 
     def sample(self):
-        avail = list(range(self.N))
-        idx = []
-        for _ in range(4):
-            r = self.rng.random_int(0, len(avail) - 1)
-            idx.append(avail[r])
-            avail[r] = avail[-1]
-            avail.pop()
-        return idx
+        return draw_set(self.rng, self.N, 4)
 
     def hypothesis(self, idx):
         return compute_pose(self.xyz[idx].astype(np.float64), self.uv[idx].astype(np.float64), self.fu, self.fv, self.uc, self.vc)

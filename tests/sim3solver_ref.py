@@ -16,7 +16,7 @@ import math
 
 import numpy as np
 
-from pnp_ref import GlibcRand, canonical, jacobi_eig
+from pnp_ref import GlibcRand, canonical, draw_set, jacobi_eig
 
 F32 = np.float32
 DBL_EPSILON = 2.220446049250313e-16
@@ -210,14 +210,7 @@ class Sim3SolverRef:
         return check_inliers(h["T12"], h["T21"], self.X1, self.X2, self.P1im1, self.P2im2, self.err1, self.err2, self.K1, self.K2)
 
     def sample(self):
-        avail = list(range(self.N))
-        idx = []
-        for _ in range(3):
-            r = self.rng.random_int(0, len(avail) - 1)
-            idx.append(avail[r])
-            avail[r] = avail[-1]
-            avail.pop()
-        return idx
+        return draw_set(self.rng, self.N, 3)
 
     def hypothesis(self, idx):
         return compute_sim3(self.X1[idx], self.X2[idx], self.fix_scale)
