@@ -2,6 +2,7 @@
 #include "lld_tracking_adapter.h"
 
 #include <cstring>
+#include <memory>
 #include <stdexcept>
 #include <string>
 #include <unordered_map>
@@ -81,6 +82,63 @@ void set_pose(Frame& F, const lld_track_result& r) {
   float T[16];
   lld_se3_to_tcw_f32(r.pose_qt, T);
   F.SetPose(lld_slam::Mat(4, 4, T));
+}
+
+// KeyFrame -> lld_ref_keyframe (src/ORBmatcher.cc:161-199, :234): mDescriptors, mvKeysUn[k].angle, GetMapPointMatches() with NULL / isBad as -1, mFeatVec
+struct KeyFrameSide {
+  std::vector<float> angle, pos, maxd, mind; std::vector<int32_t> ids, knode, kstart, kfeat; std::vector<uint8_t> has_obs; std::vector<uint32_t> pdesc;
+  std::unordered_map<int32_t, MapPoint*> point_of;
+  lld_ref_keyframe kf;
+  explicit KeyFrameSide(const KeyFrame* pKF, bool for_projection = false) : kstart(1, 0) {
+    const std::vector<MapPoint*> vpMapPointsKF = pKF->GetMapPointMatches();
+    const int n = (int)vpMapPointsKF.size();
+    angle.assign(n + 1, 0.f); pos.assign(3 * (size_t)n + 3, 0.f); ids.assign(n + 1, -1); has_obs.assign(n + 1, 0);
+    if (for_projection) { maxd.assign(n + 1, 0.f); mind.assign(n + 1, 0.f); pdesc.assign(8 * (size_t)n + 8, 0u); }
+    for (int i = 0; i < n; i++) {
+      angle[i] = pKF->mvKeysUn[i].angle;
+      MapPoint* pMP = vpMapPointsKF[i];
+      if (!pMP || pMP->isBad()) continue;                                      // :193-197
+      ids[i] = (int32_t)pMP->mnId; point_of[ids[i]] = pMP;
+      const lld_slam::Mat P = pMP->GetWorldPos();
+      for (int k = 0; k < 3; k++) pos[3 * i + k] = P.at<float>(k);
+      has_obs[i] = pMP->Observations() > 0;
+      if (for_projection) {                                                    // SearchByProjection(F, pKF, ..) reads these of the MapPoint (:1507-1530)
+        maxd[i] = pMP->GetMaxDistance(); mind[i] = pMP->GetMinDistance();
+        const lld_slam::MatU8 d = pMP->GetDescriptor();
+        std::memcpy(&pdesc[8 * (size_t)i], d.ptr<uint32_t>(), 32);
+      }
+    }
+    for (DBoW2::FeatureVector::const_iterator it = pKF->mFeatVec.begin(); it != pKF->mFeatVec.end(); ++it) {   // a std::map: ascending node ids
+      knode.push_back((int32_t)it->first);
+      for (size_t j = 0; j < it->second.size(); j++) kfeat.push_back((int32_t)it->second[j]);
+      kstart.push_back((int32_t)kfeat.size());
+    }
+    knode.push_back(0); kfeat.push_back(0);                                    // (never read: non-null pointers for empty lists)
+    std::memset(&kf, 0, sizeof kf);
+    kf.n = n; kf.desc = pKF->mDescriptors.ptr<uint32_t>(); kf.angle = angle.data(); kf.point_id = ids.data(); kf.world_pos = pos.data(); kf.has_obs = has_obs.data();
+    kf.n_nodes = (int)kstart.size() - 1; kf.node = knode.data(); kf.node_start = kstart.data(); kf.feature = kfeat.data();
+    static const uint32_t no_desc[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+    if (n == 0) kf.desc = no_desc;
+  }
+  KeyFrameSide(const KeyFrameSide&) = delete;
+};
+
+// Frame::UpdatePoseMatrices of a float matrix with the frame's constants
+lld_frame_view view_of_matrix(const Frame& Cur, const float* T) {
+  lld_frame_view view; std::memset(&view, 0, sizeof view);
+  for (int r = 0; r < 3; r++) {
+    for (int c = 0; c < 3; c++) view.Rcw[3 * r + c] = T[4 * r + c];
+    view.tcw[r] = T[4 * r + 3];
+  }
+  for (int r = 0; r < 3; r++) {
+    double acc = 0.0;                                                         // mOw = -mRcw.t()*mtcw: one gemm, double accumulation
+    for (int k = 0; k < 3; k++) acc += (double)view.Rcw[3 * k + r] * (double)view.tcw[k];
+    view.Ow[r] = (float)(-acc);
+  }
+  view.fx = Cur.fx; view.fy = Cur.fy; view.cx = Cur.cx; view.cy = Cur.cy; view.bf = Cur.mbf;
+  view.min_x = Cur.mnMinX; view.max_x = Cur.mnMaxX; view.min_y = Cur.mnMinY; view.max_y = Cur.mnMaxY;
+  view.log_scale_factor = Cur.mfLogScaleFactor; view.n_levels = Cur.mnScaleLevels;
+  return view;
 }
 
 }  // namespace
@@ -177,58 +235,69 @@ bool FrameOnDevice::TrackWithMotionModel(const TrackingMembers& tr, Frame& Cur, 
   return out.r.n_points_map >= 7;
 }
 
+// mCurrentFrame.ComputeBoW(): the FeatureVector stays on the device; the host copy goes into the Frame
+void FrameOnDevice::ComputeBoW(Frame& Cur, lld_bow_vocab* voc, int levelsup) {
+  const int m = nt_ + 1;
+  std::vector<int32_t> word(m), node(m), start(m + 1), feat(m); std::vector<double> value(m);
+  lld_bow_result R; std::memset(&R, 0, sizeof R);
+  R.word = word.data(); R.value = value.data(); R.node = node.data(); R.node_start = start.data(); R.feature = feat.data();
+  check(lld_frame_compute_bow(f_, voc, levelsup, &R), "lld_frame_compute_bow");
+  Cur.mFeatVec.clear();
+  for (int i = 0; i < R.n_nodes; i++) Cur.mFeatVec[(unsigned int)node[i]].assign(feat.begin() + start[i], feat.begin() + start[i + 1]);
+}
+
+bool FrameOnDevice::Relocalization(const TrackingMembers& tr, Frame& Cur, const std::vector<KeyFrame*>& vpCandidateKFs, lld_bow_vocab* voc, int levelsup,
+                                   const std::vector<uint32_t>* seeds, RelocTrace* trace) {
+  params_.pose.gamma = tr.gamma; params_.line_md_thr = tr.mdThr;
+  if (voc) ComputeBoW(Cur, voc, levelsup);                                     // :1840 (NULL: the caller ran ComputeBoW on this object to query the database)
+  const int K = (int)vpCandidateKFs.size();
+  if (K == 0) return false;                                                    // :1846-1847
+  if (seeds && (int)seeds->size() != K) check(LLD_ERR_INVALID, "FrameOnDevice::Relocalization: one seed per candidate");
+  std::vector<std::unique_ptr<KeyFrameSide>> sides;
+  std::vector<lld_ref_keyframe> kfs(K); std::vector<lld_reloc_candidate> ex(K);
+  for (int i = 0; i < K; i++) {
+    sides.emplace_back(new KeyFrameSide(vpCandidateKFs[i], true));
+    KeyFrameSide& s = *sides.back();
+    kfs[i] = s.kf;
+    std::memset(&ex[i], 0, sizeof ex[i]);
+    ex[i].max_distance = s.maxd.data(); ex[i].min_distance = s.mind.data(); ex[i].point_desc = s.pdesc.data();
+    ex[i].is_bad = vpCandidateKFs[i]->isBad(); ex[i].seed = seeds ? (*seeds)[i] : (uint32_t)i;
+  }
+  // the pose the frame keeps when nothing matches: what it holds now (a lost frame may hold none: identity)
+  float T0[16] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1};
+  if (!Cur.mTcw.empty()) std::memcpy(T0, Cur.mTcw.ptr<float>(), sizeof T0);
+  const lld_frame_view view = view_of_matrix(Cur, T0);
+  double qt[7];
+  lld_se3_from_tcw_f32(T0, qt);
+  lld_pnp_params prm; lld_pnp_params_default(&prm);                            // SetRansacParameters(0.99,10,300,4,0.5,5.991) (:1882)
+  RelocTrace local; RelocTrace& R = trace ? *trace : local;
+  R.n_bow.assign(K, 0); R.rounds.assign(K, 0); R.n_good_last.assign(K, -1); R.rungs.assign(K, 0); R.n_additional1.assign(K, 0); R.n_additional2.assign(K, 0);
+  R.discarded.assign(K, 0);
+  std::memset(&R.r, 0, sizeof R.r);
+  R.r.n_bow = R.n_bow.data(); R.r.rounds = R.rounds.data(); R.r.n_good_last = R.n_good_last.data(); R.r.rungs = R.rungs.data();
+  R.r.n_additional1 = R.n_additional1.data(); R.r.n_additional2 = R.n_additional2.data(); R.r.discarded = R.discarded.data();
+  check(lld_frame_relocalize(f_, &params_, &view, qt, K, kfs.data(), ex.data(), &prm, &R.r), "lld_frame_relocalize");
+  if (!R.r.matched) return false;                                              // the objects stay untouched (:1988-1991)
+  // ---- write-back: what the winning attempt left in the frame (:1919-1971): mTcw, mvpMapPoints, mvbOutlier of the held points
+  Outputs out(nt_, nl_, 0);
+  check(lld_frame_track_download(f_, &out.r, nullptr), "lld_frame_track_download");
+  KeyFrameSide& w = *sides[R.r.winner];
+  for (int k = 0; k < nt_; k++) {
+    Cur.mvpMapPoints[k] = out.kp_id[k] >= 0 ? w.point_of[out.kp_id[k]] : static_cast<MapPoint*>(NULL);
+    Cur.mvbOutlier[k] = out.kp_id[k] >= 0 && out.kp_out[k] != 0;
+  }
+  Cur.SetPose(lld_slam::Mat(4, 4, R.r.Tcw));
+  return true;                                                                 // the caller sets mnLastRelocFrameId (:1994)
+}
+
 bool FrameOnDevice::TrackReferenceKeyFrame(const TrackingMembers& tr, Frame& Cur, const Frame& Last, const KeyFrame* pKF, lld_bow_vocab* voc, int levelsup, TrackTrace* trace) {
   params_.pose.gamma = tr.gamma; params_.line_md_thr = tr.mdThr;
-  // ---- mCurrentFrame.ComputeBoW() (:776): the FeatureVector stays on the device; the host copy goes into the Frame
-  {
-    const int m = nt_ + 1;
-    std::vector<int32_t> word(m), node(m), start(m + 1), feat(m); std::vector<double> value(m);
-    lld_bow_result R; std::memset(&R, 0, sizeof R);
-    R.word = word.data(); R.value = value.data(); R.node = node.data(); R.node_start = start.data(); R.feature = feat.data();
-    check(lld_frame_compute_bow(f_, voc, levelsup, &R), "lld_frame_compute_bow");
-    Cur.mFeatVec.clear();
-    for (int i = 0; i < R.n_nodes; i++) Cur.mFeatVec[(unsigned int)node[i]].assign(feat.begin() + start[i], feat.begin() + start[i + 1]);
-  }
-  // ---- gather mpReferenceKF (src/ORBmatcher.cc:161-199, :234)
-  const std::vector<MapPoint*> vpMapPointsKF = pKF->GetMapPointMatches();
-  const int n = (int)vpMapPointsKF.size();
-  std::vector<float> angle(n + 1, 0.f), pos(3 * (size_t)n + 3, 0.f); std::vector<int32_t> ids(n + 1, -1); std::vector<uint8_t> has_obs(n + 1, 0);
-  std::unordered_map<int32_t, MapPoint*> point_of;
-  for (int i = 0; i < n; i++) {
-    angle[i] = pKF->mvKeysUn[i].angle;
-    MapPoint* pMP = vpMapPointsKF[i];
-    if (!pMP || pMP->isBad()) continue;                                        // :193-197
-    ids[i] = (int32_t)pMP->mnId; point_of[ids[i]] = pMP;
-    const lld_slam::Mat P = pMP->GetWorldPos();
-    for (int k = 0; k < 3; k++) pos[3 * i + k] = P.at<float>(k);
-    has_obs[i] = pMP->Observations() > 0;
-  }
-  std::vector<int32_t> knode, kstart(1, 0), kfeat;
-  for (DBoW2::FeatureVector::const_iterator it = pKF->mFeatVec.begin(); it != pKF->mFeatVec.end(); ++it) {   // a std::map: ascending node ids
-    knode.push_back((int32_t)it->first);
-    for (size_t j = 0; j < it->second.size(); j++) kfeat.push_back((int32_t)it->second[j]);
-    kstart.push_back((int32_t)kfeat.size());
-  }
-  knode.push_back(0); kfeat.push_back(0);                                      // (never read: non-null pointers for empty lists)
-  lld_ref_keyframe kf; std::memset(&kf, 0, sizeof kf);
-  kf.n = n; kf.desc = pKF->mDescriptors.ptr<uint32_t>(); kf.angle = angle.data(); kf.point_id = ids.data(); kf.world_pos = pos.data(); kf.has_obs = has_obs.data();
-  kf.n_nodes = (int)kstart.size() - 1; kf.node = knode.data(); kf.node_start = kstart.data(); kf.feature = kfeat.data();
-  static const uint32_t no_desc[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-  if (n == 0) kf.desc = no_desc;
-  // ---- the stage, from mLastFrame.mTcw (:789): Frame::UpdatePoseMatrices of that matrix with this frame's constants
-  lld_frame_view view; std::memset(&view, 0, sizeof view);
-  for (int r = 0; r < 3; r++) {
-    for (int c = 0; c < 3; c++) view.Rcw[3 * r + c] = Last.mTcw.at<float>(r, c);
-    view.tcw[r] = Last.mTcw.at<float>(r, 3);
-  }
-  for (int r = 0; r < 3; r++) {
-    double acc = 0.0;                                                         // mOw = -mRcw.t()*mtcw: one gemm, double accumulation
-    for (int k = 0; k < 3; k++) acc += (double)view.Rcw[3 * k + r] * (double)view.tcw[k];
-    view.Ow[r] = (float)(-acc);
-  }
-  view.fx = Cur.fx; view.fy = Cur.fy; view.cx = Cur.cx; view.cy = Cur.cy; view.bf = Cur.mbf;
-  view.min_x = Cur.mnMinX; view.max_x = Cur.mnMaxX; view.min_y = Cur.mnMinY; view.max_y = Cur.mnMaxY;
-  view.log_scale_factor = Cur.mfLogScaleFactor; view.n_levels = Cur.mnScaleLevels;
+  if (voc) ComputeBoW(Cur, voc, levelsup);                                     // mCurrentFrame.ComputeBoW() (:776); NULL: done on this object already
+  // ---- gather mpReferenceKF; the stage starts from mLastFrame.mTcw (:789): Frame::UpdatePoseMatrices of that matrix with this frame's constants
+  KeyFrameSide side(pKF);
+  const lld_ref_keyframe& kf = side.kf;
+  std::unordered_map<int32_t, MapPoint*>& point_of = side.point_of;
+  const lld_frame_view view = view_of_matrix(Cur, Last.mTcw.ptr<float>());
   double qt[7];
   lld_se3_from_tcw_f32(Last.mTcw.ptr<float>(), qt);
   check(lld_frame_track_reference_keyframe(f_, &params_, &view, qt, &kf), "lld_frame_track_reference_keyframe");

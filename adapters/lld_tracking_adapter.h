@@ -2,6 +2,7 @@
 //   bool Tracking::TrackWithMotionModel()   src/Tracking.cc:885-994   (from `mCurrentFrame.SetPose(mVelocity*mLastFrame.mTcw)` on)
 //   bool Tracking::TrackLocalMap()          src/Tracking.cc:1126-1220 (after UpdateLocalMap())
 //   bool Tracking::TrackReferenceKeyFrame() src/Tracking.cc:773-817   (the other common way into TrackLocalMap)
+//   bool Tracking::Relocalization()         src/Tracking.cc:1837-1998 (the third)
 // All run as ONE device-resident sequence (lld_frame_track_*, include/lld_amd.h): the frame's keypoints and lines go to the device once
 // (FrameOnDevice's constructor - the last step of the reference's Frame constructor), each routine gathers its map-side inputs, queues
 // its stage, fetches the stage's record and writes it back into the objects the way the reference's loops do (mvpMapPoints / mvbOutlier /
@@ -37,6 +38,9 @@ struct TrackingMembers {          // what the two routines read off `this` (incl
 // What one stage got back (optional; the tests read it, a live system passes nullptr).
 struct TrackTrace { lld_track_result r; std::vector<int32_t> kp_point_id, ln_line_id; std::vector<uint8_t> kp_outlier, ln_outlier, mp_in_view; };
 
+// What Relocalization got back (optional, as TrackTrace): lld_reloc_result with its per-candidate arrays owned here.
+struct RelocTrace { lld_reloc_result r; std::vector<int32_t> n_bow, rounds, n_good_last, rungs, n_additional1, n_additional2; std::vector<uint8_t> discarded; };
+
 class FrameOnDevice {
  public:
   // the frame's own data: mDescriptors, mvKeysUn, mvuRight, the grid and level tables, mvLinesLeft / mvLinesRight / line_matches / mDescriptorsLines
@@ -50,6 +54,11 @@ class FrameOnDevice {
   // frame keeps only the raw matches of the search, with mvbOutlier false, no MapLines, the predicted pose and no marks on any MapPoint / MapLine;
   // the device frame is set to that state, so TrackLocalMap may follow it on this object as after SetFrameState.
   bool TrackWithMotionModel(const TrackingMembers& tr, Frame& mCurrentFrame, const Frame& mLastFrame, bool* mbVO = nullptr, TrackTrace* trace = nullptr);
+  // mCurrentFrame.ComputeBoW() on the resident descriptors (lld_frame_compute_bow): the FeatureVector stays on the device with the frame, mFeatVec is
+  // filled from the call's host result; `voc` belongs to this frame's context.  The two routines below run it themselves unless they are handed
+  // voc = NULL, which says it has been run on this object - Relocalization's caller needs the frame's vectors for DetectRelocalizationCandidates
+  // (:1844) before it has any candidate to hand over.
+  void ComputeBoW(Frame& mCurrentFrame, lld_bow_vocab* voc, int levelsup = 4);
   // bool Tracking::TrackReferenceKeyFrame() (src/Tracking.cc:773-817) as one device sequence (lld_frame_compute_bow + lld_frame_track_reference_keyframe):
   // mCurrentFrame.ComputeBoW() on the resident descriptors (mFeatVec is filled from the call's host result; `voc` belongs to this frame's
   // context), the gather from mpReferenceKF (mDescriptors, mvKeysUn[k].angle, GetMapPointMatches() with NULL / isBad as -1, mFeatVec), the stage,
@@ -58,6 +67,13 @@ class FrameOnDevice {
   // hold, otherwise the caller does that (SetFrameState) before TrackLocalMap follows.
   bool TrackReferenceKeyFrame(const TrackingMembers& tr, Frame& mCurrentFrame, const Frame& mLastFrame, const KeyFrame* mpReferenceKF, lld_bow_vocab* voc,
                               int levelsup = 4, TrackTrace* trace = nullptr);
+  // bool Tracking::Relocalization() (src/Tracking.cc:1837-1998) in one call (lld_frame_compute_bow + lld_frame_relocalize), vpCandidateKFs being what
+  // DetectRelocalizationCandidates returned (:1844): ComputeBoW as above, the gather of every candidate (as for TrackReferenceKeyFrame, plus each
+  // MapPoint's distance band and descriptor and pKF->isBad()), the call, and on success the write-back of mTcw, mvpMapPoints and mvbOutlier.  Returns
+  // bMatch; on false the objects stay untouched (a frame nobody reads, include/lld_amd.h).  The caller sets mnLastRelocFrameId (:1994).
+  // seeds: one per candidate for its PnPsolver's rand() stream (default: its index; another length throws).  TrackLocalMap may follow on this object without SetFrameState.
+  bool Relocalization(const TrackingMembers& tr, Frame& mCurrentFrame, const std::vector<KeyFrame*>& vpCandidateKFs, lld_bow_vocab* voc, int levelsup = 4,
+                      const std::vector<uint32_t>* seeds = nullptr, RelocTrace* trace = nullptr);
   // The frame's pose and matches came from another routine (Tracking::TrackReferenceKeyFrame, src/Tracking.cc:770-816, or Relocalization): hands the
   // device what mCurrentFrame holds now (mTcw, mvpMapPoints / mvbOutlier, mvpMapLines / mvbOutlierLines) so that TrackLocalMap can follow.
   void SetFrameState(const TrackingMembers& tr, const Frame& mCurrentFrame);

@@ -891,10 +891,11 @@ typedef struct {
 /* view / pose_qt: Frame::UpdatePoseMatrices and Converter::toSE3Quat of mLastFrame.mTcw (:789), formed as for lld_frame_track_motion_model. */
 int  lld_frame_track_reference_keyframe(lld_frame* frame, const lld_track_params* params, const lld_frame_view* view, const double* pose_qt,
                                         const lld_ref_keyframe* kf);
-/* Stage 1 ran elsewhere: Tracking::TrackReferenceKeyFrame (src/Tracking.cc:770-816) or Tracking::Relocalization end with the same
- * PoseOptimization + outlier discard but find their matches by bag of words / PnP.  This call hands the device what such a routine left in
- * the frame, so that lld_frame_track_local_map can follow on the same handle (Tracking::Track runs TrackLocalMap after whichever routine
- * produced the pose, :401-407).  The record of stage 1 reads as empty afterwards. */
+/* Stage 1 by Tracking::Relocalization (src/Tracking.cc:1837-1998) is lld_frame_relocalize, declared after lld_pnp_params below.
+ * Stage 1 ran elsewhere: a caller that runs Tracking::TrackReferenceKeyFrame (src/Tracking.cc:770-816) or Tracking::Relocalization call by
+ * call - they end with the same PoseOptimization + outlier discard but find their matches by bag of words / PnP - hands the device what such a
+ * routine left in the frame, so that lld_frame_track_local_map can follow on the same handle (Tracking::Track runs TrackLocalMap after whichever
+ * routine produced the pose, :401-407).  The record of stage 1 reads as empty afterwards. */
 typedef struct {
   const int32_t* kp_point_id;       /* [nt] id of mvpMapPoints[k] or -1                                                                              */
   const float*   kp_world_pos;      /* [nt][3] GetWorldPos() of those (ignored where the id is -1)                                                   */
@@ -1468,6 +1469,76 @@ int  lld_pnp_batch_hypotheses(lld_pnp_batch* b, int32_t solver, int32_t capacity
 void lld_pnp_batch_destroy(lld_pnp_batch* b);
 /* find() (:159-163) on one freshly constructed solver: create, lld_pnp_batch_find, download, destroy. */
 int  lld_pnp_find(lld_ctx* ctx, const lld_pnp_problem* problem, const lld_pnp_params* params, lld_pnp_result* out);
+
+/* ------------------------------------------------------------------ Tracking::Relocalization as a stage of the frame chain
+ * Stage 1 by Tracking::Relocalization (src/Tracking.cc:1837-1998), the fourth entry into the chain of lld_frame_track_* (declared here
+ * because it takes lld_pnp_params): ONE call for ORBmatcher(0.75, true).SearchByBoW against every candidate (:1873), the PnPsolvers
+ * (:1881-1883), the rounds of iterate(5) (:1894-1915) and, for every candidate a round gives a pose, the ladder PoseOptimization ->
+ * discard -> SearchByProjection(F, pKF, sFound, 10, 100) -> PoseOptimization -> SearchByProjection(.., 3, 64) -> PoseOptimization -> discard
+ * (:1917-1976).  One upload of the candidates; the K match counts come back once (the host applies `nmatches < 15` and isBad and computes
+ * SetRansacParameters, whose log / ceil stay the host's fp64 expression); after that the host reads ONE status word per round and nothing
+ * else until `out` is fetched.
+ *   - SearchByBoW runs for all candidates in one launch: one wavefront per (candidate, keyframe node), the rotation histogram per candidate,
+ *     into a per-candidate match table instead of the frame's own (vvpMapPointMatches[i]).
+ *   - The PnPsolver constructor (:66-110) is a kernel: a candidate's matches in ascending keypoint order, xyz = the candidate's world
+ *     positions, uv / sigma2 from the resident keypoints and the frame's level table.
+ *   - Each solver owns its rand() stream (DEVIATION 1 above) and a candidate's ladder touches only its own copy of the frame's
+ *     mvpMapPoints / mvbOutlier / mTcw, so the reference's sequential round robin equals: evaluate every live candidate of a round side by
+ *     side, then take the first in candidate order whose ladder ends with nGood >= 50.  The ladder's rungs are predicated on device flags.
+ *   - sFound is a set of MapPoint ids: a candidate's MapPoint is skipped by the projected search when its id is among the ids the
+ *     candidate's copy of the frame holds (at :1930 the inliers, at :1958-1961 everything held).
+ * On success (out->matched = 1) the frame is left as the other stage-1 entries leave it - the pose (mTcw of the winning attempt), the
+ * MapPoints it holds with ids / world positions / Observations() > 0, mvbOutlier of those, no lines, nothing marked seen (Relocalization
+ * sets no mnLastFrameSeen) - so lld_frame_track_local_map can follow with no lld_frame_track_set_state.  The reference's quirk is kept:
+ * when the second PoseOptimization lifts nGood to >= 50, the points it flagged stay in mvpMapPoints with mvbOutlier set (:1952-1956
+ * discard nothing).  lld_frame_track_download's stage-1 record then carries that state: pose_qt and chi2 of the winner's last
+ * PoseOptimization, n_inliers = nGood, kp_point_id / kp_outlier, n_points / n_points_map of what the frame holds, n_search_first =
+ * n_search = the winner's SearchByBoW count, zeros elsewhere (on failure: all zeros, every id -1).
+ * DEVIATIONS: (a) on failure (matched = 0) the frame holds nothing and keeps the pose handed in; the reference leaves the residue of the
+ * last attempt in a frame nobody reads.  (b) mvbOutlier of a keypoint WITHOUT a MapPoint reads 0; the reference keeps there the flag of
+ * whichever earlier attempt last held a point on it, which nothing reads before PoseOptimization resets it.  (c) the candidates after the
+ * winner are iterated speculatively in the winning round; their records report the state before that round, as the reference leaves them.
+ * `view` / `pose_qt`: the image bounds, scale constants and intrinsics of the frame as for lld_frame_track_motion_model, and the pose the
+ * frame keeps when nothing matches.  candidates[i] = vpCandidateKFs[i] as lld_ref_keyframe describes a keyframe (ids distinct inside one
+ * keyframe); extra[i] what the projected search and the solver need beyond it.
+ * LLD_ERR_INVALID before anything is queued, the frame unchanged: no lld_frame_compute_bow on this frame yet, a NULL argument, n_candidates
+ * outside [1, LLD_PNP_MAX_SOLVERS], any per-candidate condition lld_frame_track_reference_keyframe refuses, a candidate with keypoints but
+ * no max_distance / min_distance, cam.fx or cam.fy not > 0, a frame without level_inv_sigma2 or (nt > 0) angles, pnp parameters
+ * lld_pnp_batch_create refuses (min_set other than 4: LLD_ERR_UNSUPPORTED).  All candidates discarded before PnP (isBad, or fewer than 15
+ * matches): matched = 0, no round queued (nCandidates == 0, :1894).  Synchronous: returns when the routine has ended.
+ * Any other error (LLD_ERR_ALLOC, LLD_ERR_HIP) may arrive after the frame was emptied for the routine: it then holds nothing, at the pose handed in. */
+#define LLD_RELOC_RUNG_POSE1   1         /* PoseOptimization on the PnP inliers (:1936)                                          */
+#define LLD_RELOC_RUNG_SEARCH1 2         /* nGood < 50: SearchByProjection(.., 10, 100) (:1948)                                  */
+#define LLD_RELOC_RUNG_POSE2   4         /* nadditional + nGood >= 50: PoseOptimization (:1952)                                  */
+#define LLD_RELOC_RUNG_SEARCH2 8         /* 30 < nGood < 50: SearchByProjection(.., 3, 64) (:1962)                               */
+#define LLD_RELOC_RUNG_POSE3   16        /* nGood + nadditional >= 50: PoseOptimization and discard (:1967-1971)                 */
+typedef struct {
+  const float*    max_distance;          /* [n] mfMaxDistance of GetMapPointMatches()[k] (ignored where point_id is -1)          */
+  const float*    min_distance;          /* [n] mfMinDistance                                                                    */
+  const uint32_t* point_desc;            /* [n][8] pMP->GetDescriptor() (ORBmatcher.cc:1530), or NULL: the keyframe's own desc   */
+  int32_t  is_bad;                       /* pKF->isBad() (:1869)                                                                 */
+  uint32_t seed;                         /* srand(seed) of this candidate's PnPsolver                                            */
+} lld_reloc_candidate;
+typedef struct {
+  int32_t matched;                       /* bMatch                                                                               */
+  int32_t winner;                        /* index into candidates, -1                                                            */
+  int32_t round;                         /* 1-based round of the while loop (:1894) in which it won, 0                           */
+  int32_t n_good;                        /* the winner's nGood, 0                                                                */
+  int32_t n_rounds;                      /* rounds run                                                                           */
+  int32_t n_kept;                        /* nCandidates after the BoW gate (:1884)                                               */
+  float   Tcw[16];                       /* mCurrentFrame.mTcw at return (matched = 0: the pose handed in)                       */
+  /* per candidate, caller-allocated [n_candidates], any may be NULL */
+  int32_t* n_bow;                        /* SearchByBoW's return value (0 for an isBad keyframe: the reference does not search)  */
+  uint8_t* discarded;                    /* vbDiscarded[i] at return                                                             */
+  int32_t* rounds;                       /* iterate(5) calls the candidate received                                              */
+  int32_t* n_good_last;                  /* nGood at the end of its last attempt (a round that gave it a pose), -1: none         */
+  int32_t* rungs;                        /* OR of LLD_RELOC_RUNG_* its last attempt took                                         */
+  int32_t* n_additional1;                /* nadditional of the (10, 100) search of that attempt, 0 when not run                  */
+  int32_t* n_additional2;                /* ... of the (3, 64) search                                                            */
+} lld_reloc_result;
+int  lld_frame_relocalize(lld_frame* frame, const lld_track_params* params, const lld_frame_view* view, const double* pose_qt,
+                          int32_t n_candidates, const lld_ref_keyframe* candidates, const lld_reloc_candidate* extra, const lld_pnp_params* pnp,
+                          lld_reloc_result* out);
 
 /* ================================================================== Sim3Solver (src/Sim3Solver.cc), LoopClosing::ComputeSim3's RANSAC
  * A batch of independent Sim3Solvers, one per loop candidate, whose RANSAC state stays in HBM between iterate() calls.  The prefix

@@ -423,7 +423,32 @@ class TrackedFrame {
     lld_se3_from_tcw_f32(Tcw, qt);
     check(lld_frame_track_reference_keyframe(f_, &params, &view, qt, &kf), "lld_frame_track_reference_keyframe");
   }
-  // stage 1 ran elsewhere (TrackReferenceKeyFrame / Relocalization): the frame's pose and what it holds, then TrackLocalMap as usual
+  // Tracking::Relocalization (src/Tracking.cc:1837-1998) after ComputeBoW, in one call: candidates[i] / extra[i] = vpCandidateKFs[i]; Tcw / view: the
+  // pose the frame keeps when nothing matches.  Returns bMatch; on true TrackLocalMap can follow.  `rec` binds its per-candidate arrays itself.
+  struct RelocRecord {
+    lld_reloc_result r{};
+    std::vector<int32_t> n_bow, rounds, n_good_last, rungs, n_additional1, n_additional2;
+    std::vector<uint8_t> discarded;
+    void bind(int k) {
+      n_bow.assign(k, 0); rounds.assign(k, 0); n_good_last.assign(k, -1); rungs.assign(k, 0); n_additional1.assign(k, 0); n_additional2.assign(k, 0); discarded.assign(k, 0);
+      r.n_bow = n_bow.data(); r.rounds = rounds.data(); r.n_good_last = n_good_last.data(); r.rungs = rungs.data(); r.n_additional1 = n_additional1.data();
+      r.n_additional2 = n_additional2.data(); r.discarded = discarded.data();
+    }
+  };
+  bool Relocalization(const lld_frame_view& view, const float Tcw[16], const std::vector<lld_ref_keyframe>& candidates, const std::vector<lld_reloc_candidate>& extra,
+                      RelocRecord* rec = nullptr, const lld_pnp_params* pnp = nullptr) {
+    double qt[7];
+    lld_se3_from_tcw_f32(Tcw, qt);
+    lld_pnp_params prm;
+    if (pnp) prm = *pnp; else lld_pnp_params_default(&prm);  // SetRansacParameters(0.99,10,300,4,0.5,5.991) (:1882)
+    RelocRecord local;
+    RelocRecord& R = rec ? *rec : local;
+    R.bind((int)candidates.size());
+    if (candidates.size() != extra.size()) check(LLD_ERR_INVALID, "lld_frame_relocalize");
+    check(lld_frame_relocalize(f_, &params, &view, qt, (int32_t)candidates.size(), candidates.data(), extra.data(), &prm, &R.r), "lld_frame_relocalize");
+    return R.r.matched != 0;
+  }
+  // stage 1 ran elsewhere (TrackReferenceKeyFrame / Relocalization call by call): the frame's pose and what it holds, then TrackLocalMap as usual
   void SetState(const lld_frame_view& view, const float Tcw[16], const lld_frame_held& held) {
     double qt[7];
     lld_se3_from_tcw_f32(Tcw, qt);

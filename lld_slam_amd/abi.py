@@ -306,6 +306,22 @@ class RefKeyFrame(C.Structure):
                 ("has_obs", c_uint8_p), ("n_nodes", C.c_int32), ("node", c_int32_p), ("node_start", c_int32_p), ("feature", c_int32_p)]
 
 
+class RelocCandidate(C.Structure):
+    """lld_reloc_candidate (include/lld_amd.h): what lld_frame_relocalize needs of a candidate keyframe beyond lld_ref_keyframe."""
+    _fields_ = [("max_distance", c_float_p), ("min_distance", c_float_p), ("point_desc", c_uint32_p), ("is_bad", C.c_int32), ("seed", C.c_uint32)]
+
+
+class RelocResult(C.Structure):
+    """lld_reloc_result (include/lld_amd.h)."""
+    _fields_ = [("matched", C.c_int32), ("winner", C.c_int32), ("round", C.c_int32), ("n_good", C.c_int32), ("n_rounds", C.c_int32), ("n_kept", C.c_int32),
+                ("Tcw", C.c_float * 16),
+                ("n_bow", c_int32_p), ("discarded", c_uint8_p), ("rounds", c_int32_p), ("n_good_last", c_int32_p), ("rungs", c_int32_p),
+                ("n_additional1", c_int32_p), ("n_additional2", c_int32_p)]
+
+
+RELOC_RUNG_POSE1, RELOC_RUNG_SEARCH1, RELOC_RUNG_POSE2, RELOC_RUNG_SEARCH2, RELOC_RUNG_POSE3 = 1, 2, 4, 8, 16
+
+
 PRODUCT_SYMBOLS = [
     "lld_status_string", "lld_ctx_create", "lld_ctx_destroy", "lld_ctx_stream", "lld_ctx_synchronize", "lld_ctx_release_cache",
     "lld_se3_from_tcw_f32", "lld_se3_to_tcw_f32", "lld_orb_inv_level_sigma2",
@@ -324,7 +340,7 @@ PRODUCT_SYMBOLS = [
     "lld_compute_stereo_matches",
     "lld_frame_create", "lld_frame_search_last_frame", "lld_frame_search_local_points", "lld_frame_destroy",
     "lld_frame_set_lines", "lld_track_params_default", "lld_frame_track_motion_model", "lld_frame_track_local_map", "lld_frame_track_download", "lld_frame_track_set_state",
-    "lld_frame_compute_bow", "lld_frame_track_reference_keyframe",
+    "lld_frame_compute_bow", "lld_frame_track_reference_keyframe", "lld_frame_relocalize",
     "lld_sim3_params_default", "lld_optimize_sim3", "lld_optimize_sim3_batch",
     "lld_pose_graph_params_default", "lld_optimize_essential_graph",
     "lld_orb_extractor_create", "lld_orb_extractor_destroy", "lld_orb_extractor_levels_get", "lld_orb_extract", "lld_orb_extractor_pyramids",
@@ -489,6 +505,10 @@ class Lib:
             f("frame_compute_bow").argtypes = [vp, vp, C.c_int, vp]; f("frame_compute_bow").restype = C.c_int
             f("frame_track_reference_keyframe").argtypes = [vp, vp, vp, c_double_p, C.POINTER(RefKeyFrame)]
             f("frame_track_reference_keyframe").restype = C.c_int
+            # (frame, lld_track_params*, lld_frame_view*, pose_qt, n_candidates, lld_ref_keyframe[], lld_reloc_candidate[], lld_pnp_params*, lld_reloc_result*)
+            f("frame_relocalize").argtypes = [vp, vp, vp, c_double_p, C.c_int32, C.POINTER(RefKeyFrame), C.POINTER(RelocCandidate), C.POINTER(PnPParams),
+                                              C.POINTER(RelocResult)]
+            f("frame_relocalize").restype = C.c_int
 
 
 _PRODUCT = None

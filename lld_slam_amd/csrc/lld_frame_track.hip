@@ -19,66 +19,12 @@
 // i.e. what the reference does in the few lines of C++ between its calls.
 #include "lld_common.h"
 #include "lld_device_math.h"
+#include "lld_frame_track_state.h"
 #include "lld_track_internal.h"
 
 namespace {
 
 using namespace lld_track;
-
-constexpr int kRecInts = 16;
-struct RecHeader { double pose_qt[7]; double chi2; int32_t i[kRecInts]; };
-// i[]: 0 n_inliers, 1 lm_iterations, 2 lm_trials, 3 n_edges, 4 n_search_first, 5 n_search, 6 used_wide, 7 n_points, 8 n_points_map,
-//      9 n_lines_matched, 10 n_lines, 11 n_discarded, 12 n_point_edges, 13 n_in_view
-enum { RI_INL = 0, RI_ITS, RI_TRIALS, RI_EDGES, RI_SEARCH1, RI_SEARCH, RI_WIDE, RI_POINTS, RI_POINTS_MAP, RI_LINES_MATCHED, RI_LINES, RI_DISCARDED, RI_POINT_EDGES, RI_IN_VIEW };
-
-struct TrackDev {                 // device pointers of the frame's tracking state (all inside lld_frame_track_state::d_state)
-  int nt, nl, nr, dim;
-  uint8_t* kp_has; float* kp_world; int32_t* kp_id; uint8_t* kp_obs; uint8_t* kp_outlier;
-  int32_t* discard; int32_t* n_discard;
-  uint8_t* ln_has; double* ln_x0; double* ln_dir; int32_t* ln_id; uint8_t* ln_outlier;
-  int32_t* tracked; int32_t* n_tracked; int tracked_cap;
-  double* pose_qt; double* pose_out; lld_frame_view* view; LineTrackDevParams* line_params;
-  // per-stage records
-  RecHeader* rec_h[2]; int32_t* rec_kp_id[2]; uint8_t* rec_kp_out[2]; int32_t* rec_ln_id[2]; uint8_t* rec_ln_out[2];
-};
-
-struct ViewConsts { float fx, fy, cx, cy, bf, min_x, max_x, min_y, max_y, log_scale_factor; int n_levels; double b, thr_base, sx, sy; int monocular, use_grid; };
-
-// Frame::SetPose + UpdatePoseMatrices (src/Frame.cc:318-331) from the optimised SE3Quat: Converter::toCvMat narrows to_homogeneous_matrix
-// to float (src/Converter.cc:49-70); mOw = -mRcw.t()*mtcw is one cv::gemm (double accumulation, one rounding).  No contraction: the same
-// operations, one rounding each, as lld_se3_to_tcw_f32 performs on the host.
-__device__ void view_from_pose(const double* qt, const ViewConsts& C, lld_frame_view* V, LineTrackDevParams* L, double* qt_of_float_matrix) {
-#pragma clang fp contract(off)
-  const lld::Pose p = lld::pose_load(qt);
-  const lld::Mat3 R = lld::quat_rotation(p.q);
-  float Rf[9], tf[3];
-  for (int i = 0; i < 3; i++) for (int j = 0; j < 3; j++) Rf[3 * i + j] = (float)R.m[i][j];
-  tf[0] = (float)p.t.x; tf[1] = (float)p.t.y; tf[2] = (float)p.t.z;
-  {
-    // The Frame keeps the FLOAT matrix only: the next PoseOptimization starts from Converter::toSE3Quat(pFrame->mTcw) (Optimizer.cc:823),
-    // i.e. from lld_se3_from_tcw_f32 of these floats, not from the double SE3Quat that was just optimised.
-    lld::Mat3 Rd;
-    for (int i = 0; i < 3; i++) for (int j = 0; j < 3; j++) Rd.m[i][j] = (double)Rf[3 * i + j];
-    lld::Pose pf; pf.q = lld::quat_from_rotation(Rd); pf.t = lld::vec3((double)tf[0], (double)tf[1], (double)tf[2]);
-    lld::pose_normalize(pf);
-    lld::pose_store(pf, qt_of_float_matrix);
-  }
-  for (int i = 0; i < 9; i++) V->Rcw[i] = Rf[i];
-  for (int i = 0; i < 3; i++) {
-    V->tcw[i] = tf[i];
-    const double acc = ((double)Rf[0 + i] * (double)tf[0] + (double)Rf[3 + i] * (double)tf[1]) + (double)Rf[6 + i] * (double)tf[2];
-    V->Ow[i] = (float)(-acc);
-  }
-  V->fx = C.fx; V->fy = C.fy; V->cx = C.cx; V->cy = C.cy; V->bf = C.bf;
-  V->min_x = C.min_x; V->max_x = C.max_x; V->min_y = C.min_y; V->max_y = C.max_y; V->log_scale_factor = C.log_scale_factor; V->n_levels = C.n_levels;
-  // AddLinesFrom's camera (src/Tracking.cc:920-923, :1136-1139): T_curr = mTcw.inv() widened to double.  The build takes the frame's own
-  // Rwc = Rcw^T and Ow for it (equal to OpenCV's float LU inverse up to float rounding: include/lld_amd.h); the right camera is GetTForRight.
-  for (int i = 0; i < 9; i++) L->K[i] = 0.0;
-  L->K[0] = (double)C.fx; L->K[2] = (double)C.cx; L->K[4] = (double)C.fy; L->K[5] = (double)C.cy; L->K[8] = 1.0;
-  for (int r = 0; r < 3; r++) { for (int c = 0; c < 3; c++) L->R[3 * r + c] = (double)Rf[3 * c + r]; L->t[r] = (double)V->Ow[r]; }
-  for (int r = 0; r < 3; r++) L->tr[r] = L->t[r] + L->R[3 * r] * C.b;
-  L->thr_base = C.thr_base; L->sx = C.sx; L->sy = C.sy; L->monocular = C.monocular; L->use_grid = C.use_grid;
-}
 
 // A new frame enters TrackWithMotionModel: no MapPoints (fill(..., NULL), :897), no outlier flags, nothing discarded or tracked yet.
 __global__ void track_reset_kernel(TrackDev D, const double* pose_guess, const lld_frame_view* view_up, const LineTrackDevParams* lp_up) {
@@ -193,24 +139,6 @@ __global__ __launch_bounds__(1024) void track_after_pose_kernel(TrackDev D, View
 // MapPoints the frame holds (:1629) and for those the outlier discard marked (:949).  Ids are the caller's (>= 0).  Lines: tracked_last_id ==
 // mnId (:1023) against the list of lines assigned so far.
 constexpr int kSeenThreads = 1024;
-__device__ __forceinline__ unsigned seen_hash(int32_t id, unsigned mask) { return ((unsigned)id * 2654435761u >> 7) & mask; }
-__device__ __forceinline__ void seen_insert(int32_t* tab, unsigned mask, int32_t id) {
-  unsigned h = seen_hash(id, mask);
-  for (;;) {
-    const int32_t old = atomicCAS(&tab[h], -1, id);
-    if (old == -1 || old == id) return;
-    h = (h + 1) & mask;
-  }
-}
-__device__ __forceinline__ bool seen_lookup(const int32_t* tab, unsigned mask, int32_t id) {
-  unsigned h = seen_hash(id, mask);
-  for (;;) {
-    const int32_t v = tab[h];
-    if (v == id) return true;
-    if (v == -1) return false;
-    h = (h + 1) & mask;
-  }
-}
 // One workgroup: the ids the frame holds or discarded (and the lines it tracked) go into two open-addressing hash sets in LDS (at most half
 // full: ids >= 0, -1 = empty), then every local MapPoint / MapLine probes its id.
 __global__ __launch_bounds__(kSeenThreads) void track_mark_seen_kernel(TrackDev D, int n_mp, const int32_t* mp_id, const uint8_t* mp_skip, uint8_t* mp_skip_out,
@@ -229,8 +157,6 @@ __global__ __launch_bounds__(kSeenThreads) void track_mark_seen_kernel(TrackDev 
   for (int j = tid; j < n_ml; j += kSeenThreads) ml_skip_out[j] = ((ml_skip && ml_skip[j]) || seen_lookup(ltab, lmask, ml_id[j])) ? 1 : 0;
 }
 
-inline size_t al(size_t b) { return (b + 255) & ~size_t(255); }
-
 // LDS of track_mark_seen_kernel for a frame: the point table holds the ids the frame holds or discarded (<= 2 nt), the line table the tracked
 // list (<= tracked_cap = 2 nl + 16), each at most half full.  Fixed per frame: sized once by state_build.
 constexpr size_t kSeenLdsMax = 150 * 1024;
@@ -247,25 +173,6 @@ int track_max_lines(int nt) {
 
 }  // namespace
 
-struct lld_frame_track_state {
-  TrackDev D{};
-  char* d_state = nullptr;                 // per-frame state + records (sized at lld_frame_set_lines / first track call)
-  size_t rec_off = 0, rec_bytes = 0;       // the two records, contiguous (one download)
-  // frame lines
-  int nl = 0, nr = 0, dim = 0; double sx = 0, sy = 0;
-  const float* ln_left = nullptr; const int32_t* ln_loct = nullptr; const float* ln_right = nullptr; const int32_t* ln_roct = nullptr;
-  const int32_t* ln_match = nullptr; const float* ln_desc = nullptr; int32_t* ln_cell = nullptr;
-  // per-call work: uploaded inputs + search / line / pose scratch (grow-only), one pinned staging region per stage
-  char* d_work = nullptr; size_t work_bytes = 0;
-  char* h_stage[2] = {nullptr, nullptr}; size_t h_stage_bytes[2] = {0, 0};
-  hipEvent_t uploaded[2] = {nullptr, nullptr}; bool upload_pending[2] = {false, false};
-  char* h_rec = nullptr; size_t h_rec_bytes = 0;
-  ViewConsts consts{};
-  bool stage1_queued = false;
-  size_t in_view_off = 0; int n_in_view = 0;   // Frame::isInFrustum flags of stage 2's local MapPoints, inside d_work
-  unsigned seen_psize = 0, seen_lsize = 0; size_t seen_lds = 0;   // track_mark_seen_kernel's tables (state_build)
-};
-
 namespace lld_track {
 void state_free(lld_frame* f) {
   lld_frame_track_state* S = f->track;
@@ -277,6 +184,46 @@ void state_free(lld_frame* f) {
   delete S;
   f->track = nullptr;
 }
+
+int ensure_work(lld_frame_track_state* S, lld_ctx* ctx, size_t bytes) {
+  if (bytes <= S->work_bytes) return LLD_OK;
+  LLD_HIP_TRY(hipStreamSynchronize(ctx->stream));                // kernels of an earlier stage may still read the old block
+  if (S->d_work) LLD_HIP_TRY(hipFree(S->d_work));
+  S->d_work = nullptr; S->work_bytes = 0;
+  const size_t want = bytes + (bytes >> 2) + 4096;
+  if (hipMalloc(reinterpret_cast<void**>(&S->d_work), want) != hipSuccess) return LLD_ERR_ALLOC;
+  S->work_bytes = want;
+  return LLD_OK;
+}
+int ensure_stage(lld_frame_track_state* S, int s, size_t bytes) {
+  if (S->upload_pending[s]) { LLD_HIP_TRY(hipEventSynchronize(S->uploaded[s])); S->upload_pending[s] = false; }   // (long complete: the previous frame's copy)
+  if (bytes <= S->h_stage_bytes[s]) return LLD_OK;
+  if (S->h_stage[s]) LLD_HIP_TRY(hipHostFree(S->h_stage[s]));
+  S->h_stage[s] = nullptr; S->h_stage_bytes[s] = 0;
+  const size_t want = bytes + (bytes >> 2) + 4096;
+  LLD_HIP_TRY(hipHostMalloc(reinterpret_cast<void**>(&S->h_stage[s]), want, hipHostMallocDefault));
+  S->h_stage_bytes[s] = want;
+  return LLD_OK;
+}
+
+void fill_consts(lld_frame_track_state* S, const lld_frame* f, const lld_track_params* P, const lld_frame_view* view) {
+  ViewConsts& C = S->consts;
+  C.fx = view->fx; C.fy = view->fy; C.cx = view->cx; C.cy = view->cy; C.bf = view->bf;
+  C.min_x = view->min_x; C.max_x = view->max_x; C.min_y = view->min_y; C.max_y = view->max_y; C.log_scale_factor = view->log_scale_factor; C.n_levels = view->n_levels;
+  C.b = (double)(view->bf / view->fx);                                      // mb = mbf / fx, floats (src/Frame.cc:97)
+  C.thr_base = P->line_thr_reproj_base; C.sx = S->sx; C.sy = S->sy; C.monocular = P->monocular; C.use_grid = P->line_use_grid;
+  (void)f;
+}
+
+// the host-side twin of view_from_pose's line camera for stage 1, where the view is the caller's (mVelocity * mLastFrame.mTcw is a float product)
+void line_params_from_view(const ViewConsts& C, const lld_frame_view& V, LineTrackDevParams* L) {
+  std::memset(L, 0, sizeof *L);
+  L->K[0] = (double)C.fx; L->K[2] = (double)C.cx; L->K[4] = (double)C.fy; L->K[5] = (double)C.cy; L->K[8] = 1.0;
+  for (int r = 0; r < 3; r++) { for (int c = 0; c < 3; c++) L->R[3 * r + c] = (double)V.Rcw[3 * c + r]; L->t[r] = (double)V.Ow[r]; }
+  for (int r = 0; r < 3; r++) L->tr[r] = L->t[r] + L->R[3 * r] * C.b;
+  L->thr_base = C.thr_base; L->sx = C.sx; L->sy = C.sy; L->monocular = C.monocular; L->use_grid = C.use_grid;
+}
+
 }  // namespace lld_track
 
 namespace {
@@ -348,47 +295,6 @@ int state_build(lld_frame* f, const lld_frame_lines* L) {
   return LLD_OK;
 }
 
-int ensure_state(lld_frame* f) { return f->track ? LLD_OK : state_build(f, nullptr); }
-
-int ensure_work(lld_frame_track_state* S, lld_ctx* ctx, size_t bytes) {
-  if (bytes <= S->work_bytes) return LLD_OK;
-  LLD_HIP_TRY(hipStreamSynchronize(ctx->stream));                // kernels of an earlier stage may still read the old block
-  if (S->d_work) LLD_HIP_TRY(hipFree(S->d_work));
-  S->d_work = nullptr; S->work_bytes = 0;
-  const size_t want = bytes + (bytes >> 2) + 4096;
-  if (hipMalloc(reinterpret_cast<void**>(&S->d_work), want) != hipSuccess) return LLD_ERR_ALLOC;
-  S->work_bytes = want;
-  return LLD_OK;
-}
-int ensure_stage(lld_frame_track_state* S, int s, size_t bytes) {
-  if (S->upload_pending[s]) { LLD_HIP_TRY(hipEventSynchronize(S->uploaded[s])); S->upload_pending[s] = false; }   // (long complete: the previous frame's copy)
-  if (bytes <= S->h_stage_bytes[s]) return LLD_OK;
-  if (S->h_stage[s]) LLD_HIP_TRY(hipHostFree(S->h_stage[s]));
-  S->h_stage[s] = nullptr; S->h_stage_bytes[s] = 0;
-  const size_t want = bytes + (bytes >> 2) + 4096;
-  LLD_HIP_TRY(hipHostMalloc(reinterpret_cast<void**>(&S->h_stage[s]), want, hipHostMallocDefault));
-  S->h_stage_bytes[s] = want;
-  return LLD_OK;
-}
-
-void fill_consts(lld_frame_track_state* S, const lld_frame* f, const lld_track_params* P, const lld_frame_view* view) {
-  ViewConsts& C = S->consts;
-  C.fx = view->fx; C.fy = view->fy; C.cx = view->cx; C.cy = view->cy; C.bf = view->bf;
-  C.min_x = view->min_x; C.max_x = view->max_x; C.min_y = view->min_y; C.max_y = view->max_y; C.log_scale_factor = view->log_scale_factor; C.n_levels = view->n_levels;
-  C.b = (double)(view->bf / view->fx);                                      // mb = mbf / fx, floats (src/Frame.cc:97)
-  C.thr_base = P->line_thr_reproj_base; C.sx = S->sx; C.sy = S->sy; C.monocular = P->monocular; C.use_grid = P->line_use_grid;
-  (void)f;
-}
-
-// the host-side twin of view_from_pose's line camera for stage 1, where the view is the caller's (mVelocity * mLastFrame.mTcw is a float product)
-void line_params_from_view(const ViewConsts& C, const lld_frame_view& V, LineTrackDevParams* L) {
-  std::memset(L, 0, sizeof *L);
-  L->K[0] = (double)C.fx; L->K[2] = (double)C.cx; L->K[4] = (double)C.fy; L->K[5] = (double)C.cy; L->K[8] = 1.0;
-  for (int r = 0; r < 3; r++) { for (int c = 0; c < 3; c++) L->R[3 * r + c] = (double)V.Rcw[3 * c + r]; L->t[r] = (double)V.Ow[r]; }
-  for (int r = 0; r < 3; r++) L->tr[r] = L->t[r] + L->R[3 * r] * C.b;
-  L->thr_base = C.thr_base; L->sx = C.sx; L->sy = C.sy; L->monocular = C.monocular; L->use_grid = C.use_grid;
-}
-
 struct LinesUp { size_t x0, dir, x1, x2, skip, desc, id, skip2, matches; };
 
 // lines half of a stage: AddLinesFrom on the uploaded map lines (skip bytes at `d_skip`), then the assignment into the frame
@@ -445,6 +351,34 @@ void pack_lines(char* h, const LinesUp& U, const lld_map_lines* ML, int dim) {
 }
 
 }  // namespace
+
+namespace lld_track {
+int ensure_state(lld_frame* f) { return f->track ? LLD_OK : state_build(f, nullptr); }
+int ref_keyframe_check(const lld_ref_keyframe* kf, int* n_features) {
+  const int n = kf->n, nn = kf->n_nodes;
+  *n_features = 0;
+  if (n < 0 || n > LLD_ORB_MAX_KEYPOINTS || nn < 0 || nn > n) return LLD_ERR_INVALID;
+  if (n > 0 && (!kf->desc || !kf->angle || !kf->point_id || !kf->world_pos)) return LLD_ERR_INVALID;
+  if (nn > 0 && (!kf->node || !kf->node_start || !kf->feature)) return LLD_ERR_INVALID;
+  if (nn > 0) {
+    if (kf->node_start[0] != 0) return LLD_ERR_INVALID;
+    for (int i = 0; i < nn; i++) {
+      if (kf->node_start[i + 1] < kf->node_start[i] || kf->node_start[i + 1] > n) return LLD_ERR_INVALID;   // a feature sits under one node
+      if (i > 0 && kf->node[i] <= kf->node[i - 1]) return LLD_ERR_INVALID;
+    }
+    const int nv = kf->node_start[nn];
+    for (int i = 0; i < nv; i++) if (kf->feature[i] < 0 || kf->feature[i] >= n) return LLD_ERR_INVALID;
+    *n_features = nv;
+  }
+  return LLD_OK;
+}
+int track_reset_launch(hipStream_t st, lld_frame_track_state* S, const double* pose_d, const lld_frame_view* view_d, const LineTrackDevParams* lp_d) {
+  const int nmax = std::max(std::max(S->D.nt, S->nl), 64);
+  hipLaunchKernelGGL(track_reset_kernel, dim3((nmax + 255) / 256), dim3(256), 0, st, S->D, pose_d, view_d, lp_d);
+  LLD_HIP_TRY(hipGetLastError());
+  return LLD_OK;
+}
+}  // namespace lld_track
 
 extern "C" {
 
@@ -556,22 +490,11 @@ int lld_frame_track_reference_keyframe(lld_frame* f, const lld_track_params* P, 
   if (!f || !P || !view || !pose_qt || !kf) return LLD_ERR_INVALID;
   if (!f->has_bow) return LLD_ERR_INVALID;                                     // Frame::ComputeBoW comes first (:776)
   const int n = kf->n, nn = kf->n_nodes, nt = f->nt;
-  if (n < 0 || n > LLD_ORB_MAX_KEYPOINTS || nn < 0 || nn > n) return LLD_ERR_INVALID;
-  if (n > 0 && (!kf->desc || !kf->angle || !kf->point_id || !kf->world_pos)) return LLD_ERR_INVALID;
-  if (nn > 0 && (!kf->node || !kf->node_start || !kf->feature)) return LLD_ERR_INVALID;
+  int nv = 0;
+  if (int st = ref_keyframe_check(kf, &nv)) return st;
   if (nt > 0 && !f->has_angle) return LLD_ERR_INVALID;                         // ORBmatcher(0.7, true): mbCheckOrientation
   if (view->n_levels != f->consts.n_levels) return LLD_ERR_INVALID;
   if (!(P->cam.fx > 0) || !(P->cam.fy > 0) || !f->has_inv_sigma2) return LLD_ERR_INVALID;
-  int nv = 0;
-  if (nn > 0) {
-    if (kf->node_start[0] != 0) return LLD_ERR_INVALID;
-    for (int i = 0; i < nn; i++) {
-      if (kf->node_start[i + 1] < kf->node_start[i] || kf->node_start[i + 1] > n) return LLD_ERR_INVALID;   // a feature sits under one node
-      if (i > 0 && kf->node[i] <= kf->node[i - 1]) return LLD_ERR_INVALID;
-    }
-    nv = kf->node_start[nn];
-    for (int i = 0; i < nv; i++) if (kf->feature[i] < 0 || kf->feature[i] >= n) return LLD_ERR_INVALID;
-  }
   lld_ctx* ctx = f->ctx;
   LLD_HIP_TRY(hipSetDevice(ctx->device));
   int s = ensure_state(f); if (s) return s;

@@ -1,0 +1,135 @@
+// lld_frame_track_state.h — the device-resident tracking state of one lld_frame (what the reference keeps IN the Frame between the calls of
+// the Tracking thread) as the translation units that run stages on it see it: lld_frame_track.hip (TrackWithMotionModel, TrackReferenceKeyFrame,
+// TrackLocalMap, set_state, download) and lld_frame_reloc.hip (Relocalization).  Nothing here is exported.
+#ifndef LLD_FRAME_TRACK_STATE_H
+#define LLD_FRAME_TRACK_STATE_H
+
+#include "lld_common.h"
+#include "lld_device_math.h"
+#include "lld_track_internal.h"
+
+namespace lld_track {
+
+constexpr int kRecInts = 16;
+struct RecHeader { double pose_qt[7]; double chi2; int32_t i[kRecInts]; };
+// i[]: 0 n_inliers, 1 lm_iterations, 2 lm_trials, 3 n_edges, 4 n_search_first, 5 n_search, 6 used_wide, 7 n_points, 8 n_points_map,
+//      9 n_lines_matched, 10 n_lines, 11 n_discarded, 12 n_point_edges, 13 n_in_view
+enum { RI_INL = 0, RI_ITS, RI_TRIALS, RI_EDGES, RI_SEARCH1, RI_SEARCH, RI_WIDE, RI_POINTS, RI_POINTS_MAP, RI_LINES_MATCHED, RI_LINES, RI_DISCARDED, RI_POINT_EDGES, RI_IN_VIEW };
+
+struct TrackDev {                 // device pointers of the frame's tracking state (all inside lld_frame_track_state::d_state)
+  int nt, nl, nr, dim;
+  uint8_t* kp_has; float* kp_world; int32_t* kp_id; uint8_t* kp_obs; uint8_t* kp_outlier;
+  int32_t* discard; int32_t* n_discard;
+  uint8_t* ln_has; double* ln_x0; double* ln_dir; int32_t* ln_id; uint8_t* ln_outlier;
+  int32_t* tracked; int32_t* n_tracked; int tracked_cap;
+  double* pose_qt; double* pose_out; lld_frame_view* view; LineTrackDevParams* line_params;
+  // per-stage records
+  RecHeader* rec_h[2]; int32_t* rec_kp_id[2]; uint8_t* rec_kp_out[2]; int32_t* rec_ln_id[2]; uint8_t* rec_ln_out[2];
+};
+
+struct ViewConsts { float fx, fy, cx, cy, bf, min_x, max_x, min_y, max_y, log_scale_factor; int n_levels; double b, thr_base, sx, sy; int monocular, use_grid; };
+
+// Frame::UpdatePoseMatrices (src/Frame.cc:325-331) of a FLOAT mTcw, and Converter::toSE3Quat of it: mOw = -mRcw.t()*mtcw is one cv::gemm
+// (double accumulation, one rounding).  The Frame keeps the FLOAT matrix only: the next PoseOptimization starts from
+// Converter::toSE3Quat(pFrame->mTcw) (Optimizer.cc:823), i.e. from lld_se3_from_tcw_f32 of these floats.  No contraction: the same
+// operations, one rounding each, as the host's conversions perform.
+__device__ inline void view_from_matrix(const float* Rf, const float* tf, const ViewConsts& C, lld_frame_view* V, double* qt_of_float_matrix) {
+#pragma clang fp contract(off)
+  {
+    lld::Mat3 Rd;
+    for (int i = 0; i < 3; i++) for (int j = 0; j < 3; j++) Rd.m[i][j] = (double)Rf[3 * i + j];
+    lld::Pose pf; pf.q = lld::quat_from_rotation(Rd); pf.t = lld::vec3((double)tf[0], (double)tf[1], (double)tf[2]);
+    lld::pose_normalize(pf);
+    lld::pose_store(pf, qt_of_float_matrix);
+  }
+  for (int i = 0; i < 9; i++) V->Rcw[i] = Rf[i];
+  for (int i = 0; i < 3; i++) {
+    V->tcw[i] = tf[i];
+    const double acc = ((double)Rf[0 + i] * (double)tf[0] + (double)Rf[3 + i] * (double)tf[1]) + (double)Rf[6 + i] * (double)tf[2];
+    V->Ow[i] = (float)(-acc);
+  }
+  V->fx = C.fx; V->fy = C.fy; V->cx = C.cx; V->cy = C.cy; V->bf = C.bf;
+  V->min_x = C.min_x; V->max_x = C.max_x; V->min_y = C.min_y; V->max_y = C.max_y; V->log_scale_factor = C.log_scale_factor; V->n_levels = C.n_levels;
+}
+
+// AddLinesFrom's camera (src/Tracking.cc:920-923, :1136-1139): T_curr = mTcw.inv() widened to double.  The build takes the frame's own
+// Rwc = Rcw^T and Ow for it (equal to OpenCV's float LU inverse up to float rounding: include/lld_amd.h); the right camera is GetTForRight.
+__device__ inline void line_camera_from_view(const ViewConsts& C, const lld_frame_view& V, LineTrackDevParams* L) {
+#pragma clang fp contract(off)
+  for (int i = 0; i < 9; i++) L->K[i] = 0.0;
+  L->K[0] = (double)C.fx; L->K[2] = (double)C.cx; L->K[4] = (double)C.fy; L->K[5] = (double)C.cy; L->K[8] = 1.0;
+  for (int r = 0; r < 3; r++) { for (int c = 0; c < 3; c++) L->R[3 * r + c] = (double)V.Rcw[3 * c + r]; L->t[r] = (double)V.Ow[r]; }
+  for (int r = 0; r < 3; r++) L->tr[r] = L->t[r] + L->R[3 * r] * C.b;
+  L->thr_base = C.thr_base; L->sx = C.sx; L->sy = C.sy; L->monocular = C.monocular; L->use_grid = C.use_grid;
+}
+
+// Frame::SetPose + UpdatePoseMatrices (src/Frame.cc:318-331) from the optimised SE3Quat: Converter::toCvMat narrows to_homogeneous_matrix
+// to float (src/Converter.cc:49-70), as lld_se3_to_tcw_f32 does on the host.  L (may be null): AddLinesFrom's camera.
+__device__ inline void view_from_pose(const double* qt, const ViewConsts& C, lld_frame_view* V, LineTrackDevParams* L, double* qt_of_float_matrix) {
+#pragma clang fp contract(off)
+  const lld::Pose p = lld::pose_load(qt);
+  const lld::Mat3 R = lld::quat_rotation(p.q);
+  float Rf[9], tf[3];
+  for (int i = 0; i < 3; i++) for (int j = 0; j < 3; j++) Rf[3 * i + j] = (float)R.m[i][j];
+  tf[0] = (float)p.t.x; tf[1] = (float)p.t.y; tf[2] = (float)p.t.z;
+  view_from_matrix(Rf, tf, C, V, qt_of_float_matrix);
+  if (L) line_camera_from_view(C, *V, L);
+}
+
+// Open-addressing sets of MapPoint / MapLine ids (>= 0; -1 = empty) in LDS, at most half full: "is this id among those the frame holds".
+__device__ __forceinline__ unsigned seen_hash(int32_t id, unsigned mask) { return ((unsigned)id * 2654435761u >> 7) & mask; }
+__device__ __forceinline__ void seen_insert(int32_t* tab, unsigned mask, int32_t id) {
+  unsigned h = seen_hash(id, mask);
+  for (;;) {
+    const int32_t old = atomicCAS(&tab[h], -1, id);
+    if (old == -1 || old == id) return;
+    h = (h + 1) & mask;
+  }
+}
+__device__ __forceinline__ bool seen_lookup(const int32_t* tab, unsigned mask, int32_t id) {
+  unsigned h = seen_hash(id, mask);
+  for (;;) {
+    const int32_t v = tab[h];
+    if (v == id) return true;
+    if (v == -1) return false;
+    h = (h + 1) & mask;
+  }
+}
+
+inline size_t al(size_t b) { return (b + 255) & ~size_t(255); }
+
+}  // namespace lld_track
+
+struct lld_frame_track_state {
+  lld_track::TrackDev D{};
+  char* d_state = nullptr;                 // per-frame state + records (sized at lld_frame_set_lines / first track call)
+  size_t rec_off = 0, rec_bytes = 0;       // the two records, contiguous (one download)
+  // frame lines
+  int nl = 0, nr = 0, dim = 0; double sx = 0, sy = 0;
+  const float* ln_left = nullptr; const int32_t* ln_loct = nullptr; const float* ln_right = nullptr; const int32_t* ln_roct = nullptr;
+  const int32_t* ln_match = nullptr; const float* ln_desc = nullptr; int32_t* ln_cell = nullptr;
+  // per-call work: uploaded inputs + search / line / pose scratch (grow-only), one pinned staging region per stage
+  char* d_work = nullptr; size_t work_bytes = 0;
+  char* h_stage[2] = {nullptr, nullptr}; size_t h_stage_bytes[2] = {0, 0};
+  hipEvent_t uploaded[2] = {nullptr, nullptr}; bool upload_pending[2] = {false, false};
+  char* h_rec = nullptr; size_t h_rec_bytes = 0;
+  lld_track::ViewConsts consts{};
+  bool stage1_queued = false;
+  size_t in_view_off = 0; int n_in_view = 0;   // Frame::isInFrustum flags of stage 2's local MapPoints, inside d_work
+  unsigned seen_psize = 0, seen_lsize = 0; size_t seen_lds = 0;   // track_mark_seen_kernel's tables (state_build)
+};
+
+namespace lld_track {
+// host plumbing of a stage (lld_frame_track.hip)
+int ensure_state(lld_frame* f);                                            // the state exists (a frame without lines unless lld_frame_set_lines ran)
+int ensure_work(lld_frame_track_state* S, lld_ctx* ctx, size_t bytes);     // grow-only d_work; synchronises the stream before it reallocates
+int ensure_stage(lld_frame_track_state* S, int s, size_t bytes);           // grow-only pinned staging of stage s, free of its previous upload
+// a new frame enters stage 1: no MapPoints, no flags, nothing discarded or tracked, both record headers zero, the pose / view / line camera uploaded at *_d
+int track_reset_launch(hipStream_t st, lld_frame_track_state* S, const double* pose_d, const lld_frame_view* view_d, const LineTrackDevParams* lp_d);
+// what lld_frame_track_reference_keyframe refuses about a keyframe (LLD_ERR_INVALID); n_features: entries of its feature list
+int ref_keyframe_check(const lld_ref_keyframe* kf, int* n_features);
+void fill_consts(lld_frame_track_state* S, const lld_frame* f, const lld_track_params* P, const lld_frame_view* view);
+void line_params_from_view(const ViewConsts& C, const lld_frame_view& V, LineTrackDevParams* L);
+}  // namespace lld_track
+
+#endif

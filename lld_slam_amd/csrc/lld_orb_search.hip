@@ -794,9 +794,8 @@ struct ProjGenArgs {
   QRec* q; float* uv; int32_t* level;
 };
 
-__global__ __launch_bounds__(256) void project_general_kernel(ProjGenArgs F) {
-  const int i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= F.n) return;
+// (scale: the level table, F.scale for a kernel whose argument F is)
+__device__ __forceinline__ void project_general_one(const ProjGenArgs& F, const float* scale, int i) {
   QRec Q; memset(&Q, 0, sizeof(Q));
   Q.level_min = -1; Q.level_max = -1;
   Q.angle = F.angle ? F.angle[i] : 0.f;
@@ -839,13 +838,32 @@ __global__ __launch_bounds__(256) void project_general_kernel(ProjGenArgs F) {
     }
     if (dist < minDistance || dist > maxDistance) break;
     lvl = predict_scale(F.maxd[i], dist, F.V);
-    Q.u = u; Q.v = v; Q.radius = __fmul_rn(F.th, F.scale[lvl]);
+    Q.u = u; Q.v = v; Q.radius = __fmul_rn(F.th, scale[lvl]);
     Q.level_min = lvl - 1; Q.level_max = F.routine == LLD_ORB_PROJ_RELOC ? lvl + 1 : lvl;
     Q.flags = 1 | 2;                                                              // valid; a match blocks the keypoint for later points (routines with occupancy)
   } while (false);
   F.q[i] = Q;
   if (F.uv) { F.uv[2 * i] = u; F.uv[2 * i + 1] = v; }
   if (F.level) F.level[i] = lvl;
+}
+__global__ __launch_bounds__(256) void project_general_kernel(ProjGenArgs F) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= F.n) return;
+  project_general_one(F, F.scale, i);
+}
+
+// LLD_ORB_PROJ_RELOC for slot blockIdx.y of Tracking::Relocalization's side-by-side candidates (lld_frame_reloc.hip): the slot's own MapPoints,
+// skip bytes (bad or already found), view (device memory: the pose was optimised on the device) and predicate.
+struct ProjRelocSlotsArgs { const lld_track::RelocProjSlot* slots; float scale[LLD_ORB_MAX_LEVELS]; float th; };
+__global__ __launch_bounds__(256) void project_reloc_slots_kernel(ProjRelocSlotsArgs A) {
+  const lld_track::RelocProjSlot S = A.slots[blockIdx.y];
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= S.n || *S.run == 0) return;
+  ProjGenArgs F;
+  F.V = *S.view; F.n = S.n; F.routine = LLD_ORB_PROJ_RELOC;
+  F.pos = S.pos; F.nrm = nullptr; F.maxd = S.maxd; F.mind = S.mind; F.skip = S.skip; F.angle = S.angle;
+  F.th = A.th; F.q = static_cast<QRec*>(S.qrec); F.uv = nullptr; F.level = nullptr;
+  project_general_one(F, A.scale, i);
 }
 
 constexpr size_t kLdsLimit = 160 * 1024 - 512;
@@ -1500,6 +1518,36 @@ int orbs_project_local_points(hipStream_t st, const lld_frame* f, const lld_fram
   for (int l = 0; l < LLD_ORB_MAX_LEVELS; l++) F.scale[l] = l < f->consts.n_levels ? f->scale[l] : 1.f;
   F.cos_limit = cos_limit; F.th = th; F.q = static_cast<QRec*>(d_qrec); F.in_view = d_in_view; F.n_in_view = d_n_in_view;
   hipLaunchKernelGGL(frustum_kernel, dim3((mp.n + 255) / 256), dim3(256), 0, st, F);
+  LLD_HIP_TRY(hipGetLastError());
+  return LLD_OK;
+}
+
+size_t orbs_problem_stride() { return sizeof(Problem); }
+void orbs_fill_problem_reloc(const lld_frame* f, int nq, const uint8_t* d_occupied, const void* d_qrec, const uint32_t* d_qdesc, const SearchOut& out, void* d_cache,
+                             int accept_max, RunIf run_if, const ApplyDev& ap, void* problem_h) {
+  orbs_fill_problem(f, 0, nq, d_occupied, d_qrec, d_qdesc, out, d_cache, 0.f, 1, run_if, ap, problem_h);
+  Problem& P = *static_cast<Problem*>(problem_h);
+  P.gates = LLD_ORB_GATE_LEVEL; P.accept_max = accept_max;                      // ORBdist (:1555); no stereo gate in this routine
+  P.t_occ_obs = nullptr;                                                        // if(CurrentFrame.mvpMapPoints[i2]) continue;  (:1528)
+}
+
+int orbs_project_reloc_slots(hipStream_t st, const lld_frame* f, int n_slots, int n_max, const RelocProjSlot* slots_d, float th) {
+  if (n_slots <= 0 || n_max <= 0) return LLD_OK;
+  ProjRelocSlotsArgs A; std::memset(&A, 0, sizeof(A));
+  A.slots = slots_d; A.th = th;
+  for (int l = 0; l < LLD_ORB_MAX_LEVELS; l++) A.scale[l] = l < f->consts.n_levels ? f->scale[l] : 1.f;
+  hipLaunchKernelGGL(project_reloc_slots_kernel, dim3((n_max + 255) / 256, n_slots), dim3(256), 0, st, A);
+  LLD_HIP_TRY(hipGetLastError());
+  return LLD_OK;
+}
+
+int orbs_launch_n(lld_ctx* ctx, hipStream_t st, const lld_frame* f, const void* problems_d, int n) {
+  if (n <= 0) return LLD_OK;
+  const lld_orb_search& c = f->consts;
+  const bool desc_in_lds = lds_bytes(f->nt, c.grid_cols * c.grid_rows, true, true) <= kLdsLimit;
+  const size_t lds = lds_bytes(f->nt, c.grid_cols * c.grid_rows, true, desc_in_lds);
+  if (!ctx->orb_lds_raised) { LLD_HIP_TRY(hipFuncSetAttribute((const void*)orb_search_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kLdsLimit)); ctx->orb_lds_raised = true; }
+  hipLaunchKernelGGL(orb_search_kernel, dim3(n), dim3(kThreads), lds, st, static_cast<const Problem*>(problems_d));
   LLD_HIP_TRY(hipGetLastError());
   return LLD_OK;
 }

@@ -31,6 +31,7 @@
 #include <vector>
 
 #include "lld_common.h"
+#include "lld_pnp_internal.h"
 #include "lld_ransac.h"
 
 namespace {
@@ -57,10 +58,7 @@ struct PnpState {
   float best_tcw[12];                        // mBestTcw (float)
 };
 
-struct PnpRes {
-  float tcw[12];
-  int32_t has_pose, n_inliers, no_more, iterations, best_inliers, pad[3];
-};
+using lld_pnp::PnpRes;                       // the last iterate()'s outputs (lld_pnp_internal.h)
 
 struct PnpJob {                              // one Refine
   int32_t solver, hyp;                       // hyp: global hypothesis slot, -1 = the carried-in best set
@@ -444,6 +442,7 @@ struct Dev {
   double* scratch;                           // refine workgroups: [grid][8 * max_n]
   int32_t* scratch_idx;                      // [grid][max_n]
   int n, n_iterations, max_n;
+  const uint8_t* live;                       // [n] device, or null: all.  A solver with live = 0 keeps its state and last results (lld_pnp_internal.h)
 };
 
 // ------------------------------------------------------------------ kernels
@@ -454,6 +453,7 @@ __global__ void pnp_sample(Dev d) {
   if (bound == 0) return;                    // not active in this call
   const PnpDesc ds = d.desc[s];
   PnpState& st = d.st[s];
+  if (d.live && !d.live[s]) { st.window = 0; return; }   // no hypothesis of its slots is evaluated
   // iterate (:165-258): N < mRansacMinInliers -> bNoMore with no draws; else the loop runs while mnIterations < budget or
   // fewer than n this call, i.e. max(n, budget - mnIterations) iterations unless a Refine succeeds first.
   const int n_it = d.n_iterations > 0 ? d.n_iterations : ds.max_its;   // 0: find(), iterate(mRansacMaxIts)
@@ -578,6 +578,10 @@ __global__ void pnp_records(Dev d) {
   const int h0 = d.hyp_off[s];
   if (d.hyp_off[s + 1] == h0) {              // not active: its one job slot is empty
     d.job[h0 + s].solver = -1;
+    return;
+  }
+  if (d.live && !d.live[s]) {                // its slots were laid out, none of its jobs exists
+    for (int q = 0; q < d.hyp_off[s + 1] - h0 + 1; ++q) d.job[h0 + s + q].solver = -1;
     return;
   }
   PnpState& st = d.st[s];
@@ -801,6 +805,7 @@ __global__ __launch_bounds__(kThreads) void pnp_resolve(Dev d) {
   const int s = blockIdx.x;
   const int h0 = d.hyp_off[s];
   if (d.hyp_off[s + 1] == h0) return;        // not active
+  if (d.live && !d.live[s]) return;
   __shared__ double rt_sh[12];
   __shared__ int mode_sh;                    // 0: no pose, 1: refined (job rt), 2: best
   const PnpDesc ds = d.desc[s];
@@ -894,6 +899,32 @@ static int pnp_check_params(const lld_pnp_params& p) {
 
 static int pnp_upload(lld_pnp_batch* b, const lld_pnp_problem* problems, const lld_pnp_params* params, std::vector<PnpState>& st,
                       int64_t ntot);
+static int pnp_alloc(lld_pnp_batch* b, std::vector<PnpState>& st, int64_t ntot);
+
+// SetRansacParameters (:121-157), literally, and the solver's stream: what the constructor and SetRansacParameters leave besides the correspondences
+static void pnp_describe(lld_pnp_batch* b, int s, int N, int n_keypoints, float fx, float fy, float cx, float cy, uint32_t seed, const lld_pnp_params* params,
+                         int64_t* ntot, PnpState* st) {
+  PnpDesc& ds = b->desc[s];
+  std::memset(&ds, 0, sizeof(ds));
+  ds.off = (int32_t)*ntot; ds.n = N; ds.n_kp = n_keypoints; ds.kp_off = (int32_t)b->n_kp_total;
+  b->kp_off[s] = ds.kp_off;
+  const float eps0 = params->epsilon;
+  int nMinInliers = N * eps0;                                   // float product, truncated
+  if (nMinInliers < params->min_inliers) nMinInliers = params->min_inliers;
+  if (nMinInliers < params->min_set) nMinInliers = params->min_set;
+  float eps = eps0;
+  if (N > 0 && eps < (float)nMinInliers / N) eps = (float)nMinInliers / N;
+  ds.min_inliers = nMinInliers;
+  ds.max_its = ransac_max_iterations(params->probability, eps, nMinInliers, N, params->max_iterations);
+  ds.fu = fx; ds.fv = fy; ds.uc = cx; ds.vc = cy;
+  std::memset(st, 0, sizeof(PnpState));
+  srand_state(seed, st->rng.ring, &st->rng.head);
+  st->carried_job = -1;
+  *ntot += N;
+  b->n_kp_total += n_keypoints;
+  b->max_n = std::max(b->max_n, N);
+  b->max_its_all = std::max(b->max_its_all, ds.max_its);
+}
 
 extern "C" int lld_pnp_batch_create(lld_ctx* ctx, int32_t n, const lld_pnp_problem* problems, const lld_pnp_params* params,
                                     lld_pnp_batch** out) {
@@ -910,28 +941,7 @@ extern "C" int lld_pnp_batch_create(lld_ctx* ctx, int32_t n, const lld_pnp_probl
   std::vector<PnpState> st(n);
   for (int s = 0; s < n; ++s) {
     const lld_pnp_problem& q = problems[s];
-    PnpDesc& ds = b->desc[s];
-    std::memset(&ds, 0, sizeof(ds));
-    ds.off = (int32_t)ntot; ds.n = q.n; ds.n_kp = q.n_keypoints; ds.kp_off = (int32_t)b->n_kp_total;
-    b->kp_off[s] = ds.kp_off;
-    // SetRansacParameters (:121-157), literally
-    const int N = q.n;
-    const float eps0 = params->epsilon;
-    int nMinInliers = N * eps0;                                   // float product, truncated
-    if (nMinInliers < params->min_inliers) nMinInliers = params->min_inliers;
-    if (nMinInliers < params->min_set) nMinInliers = params->min_set;
-    float eps = eps0;
-    if (N > 0 && eps < (float)nMinInliers / N) eps = (float)nMinInliers / N;
-    ds.min_inliers = nMinInliers;
-    ds.max_its = ransac_max_iterations(params->probability, eps, nMinInliers, N, params->max_iterations);
-    ds.fu = q.fx; ds.fv = q.fy; ds.uc = q.cx; ds.vc = q.cy;
-    std::memset(&st[s], 0, sizeof(PnpState));
-    srand_state(q.seed, st[s].rng.ring, &st[s].rng.head);
-    st[s].carried_job = -1;
-    ntot += N;
-    b->n_kp_total += q.n_keypoints;
-    b->max_n = std::max(b->max_n, N);
-    b->max_its_all = std::max(b->max_its_all, ds.max_its);
+    pnp_describe(b, s, q.n, q.n_keypoints, q.fx, q.fy, q.cx, q.cy, q.seed, params, &ntot, &st[s]);
   }
   if (int rc = pnp_upload(b, problems, params, st, ntot)) {   // nothing half-built survives a failure
     lld_pnp_batch_destroy(b);
@@ -957,6 +967,22 @@ static int pnp_upload(lld_pnp_batch* b, const lld_pnp_problem* problems, const l
       kp[o + i] = q.kp_index[i];
     }
   }
+  if (int rc = pnp_alloc(b, st, ntot)) return rc;
+  hipStream_t stream = ctx->stream;
+  const Dev& d = b->dev;
+  if (ntot) {
+    LLD_HIP_TRY(hipMemcpyAsync((void*)d.pt, pt.data(), sizeof(float4) * ntot, hipMemcpyHostToDevice, stream));
+    LLD_HIP_TRY(hipMemcpyAsync((void*)d.uv, uv.data(), sizeof(float2) * ntot, hipMemcpyHostToDevice, stream));
+    LLD_HIP_TRY(hipMemcpyAsync((void*)d.kp, kp.data(), sizeof(int32_t) * ntot, hipMemcpyHostToDevice, stream));
+    LLD_HIP_TRY(hipStreamSynchronize(stream));                  // (the staging vectors are this function's)
+  }
+  return LLD_OK;
+}
+
+// The batch's slab and everything in it but the correspondences: descriptors, streams, zeroed results and flags.
+static int pnp_alloc(lld_pnp_batch* b, std::vector<PnpState>& st, int64_t ntot) {
+  lld_ctx* ctx = b->ctx;
+  const int n = b->n;
   size_t bytes = lld_slab::pad(sizeof(float4) * std::max<int64_t>(ntot, 1)) + lld_slab::pad(sizeof(float2) * std::max<int64_t>(ntot, 1)) +
                  lld_slab::pad(sizeof(int32_t) * std::max<int64_t>(ntot, 1)) + lld_slab::pad(sizeof(PnpDesc) * n) +
                  lld_slab::pad(sizeof(PnpState) * n) + lld_slab::pad(sizeof(PnpRes) * n) + lld_slab::pad(std::max<int64_t>(b->n_kp_total, 1));
@@ -974,11 +1000,6 @@ static int pnp_upload(lld_pnp_batch* b, const lld_pnp_problem* problems, const l
   hipStream_t stream = ctx->stream;
   std::vector<PnpRes> res(n);
   std::memset(res.data(), 0, sizeof(PnpRes) * n);
-  if (ntot) {
-    LLD_HIP_TRY(hipMemcpyAsync((void*)d.pt, pt.data(), sizeof(float4) * ntot, hipMemcpyHostToDevice, stream));
-    LLD_HIP_TRY(hipMemcpyAsync((void*)d.uv, uv.data(), sizeof(float2) * ntot, hipMemcpyHostToDevice, stream));
-    LLD_HIP_TRY(hipMemcpyAsync((void*)d.kp, kp.data(), sizeof(int32_t) * ntot, hipMemcpyHostToDevice, stream));
-  }
   LLD_HIP_TRY(hipMemcpyAsync((void*)d.desc, b->desc.data(), sizeof(PnpDesc) * n, hipMemcpyHostToDevice, stream));
   LLD_HIP_TRY(hipMemcpyAsync(d.st, st.data(), sizeof(PnpState) * n, hipMemcpyHostToDevice, stream));
   LLD_HIP_TRY(hipMemcpyAsync(d.res, res.data(), sizeof(PnpRes) * n, hipMemcpyHostToDevice, stream));
@@ -998,7 +1019,7 @@ extern "C" void lld_pnp_batch_destroy(lld_pnp_batch* b) {
 }
 
 // iterate(n_iterations) on the active solvers; n_iterations = 0: each solver's own mRansacMaxIts (find()).
-static int pnp_iterate(lld_pnp_batch* b, int32_t n_iterations, const uint8_t* active) {
+static int pnp_iterate(lld_pnp_batch* b, int32_t n_iterations, const uint8_t* active, const uint8_t* live_d = nullptr) {
   LLD_HIP_TRY(hipSetDevice(b->ctx->device));
   const int n = b->n;
   const std::vector<int32_t> off = ransac_call_offsets(n, active, [&](int s) { return std::max(n_iterations, b->desc[s].max_its); });
@@ -1027,6 +1048,7 @@ static int pnp_iterate(lld_pnp_batch* b, int32_t n_iterations, const uint8_t* ac
   d.scratch = sl.take<double>(8 * (size_t)grid_refine * d.max_n);
   d.scratch_idx = sl.take<int32_t>((size_t)grid_refine * d.max_n);
   d.n_iterations = n_iterations;
+  d.live = live_d;
   b->dev = d;
   b->grid_refine = grid_refine;
   hipStream_t stream = b->ctx->stream;
@@ -1049,6 +1071,40 @@ extern "C" int lld_pnp_batch_iterate(lld_pnp_batch* b, int32_t n_iterations, con
   if (n_iterations > LLD_PNP_MAX_ITERATIONS) return LLD_ERR_UNSUPPORTED;
   return pnp_iterate(b, n_iterations, active);
 }
+
+namespace lld_pnp {
+
+int batch_create_dev(lld_ctx* ctx, int32_t n, const int32_t* n_corr, int32_t n_keypoints, float fx, float fy, float cx, float cy, const uint32_t* seed,
+                     const lld_pnp_params* params, lld_pnp_batch** out, SlabDev* slab, int32_t* off) {
+  if (!ctx || !n_corr || !seed || !params || !out || !slab || !off || n < 1) return LLD_ERR_INVALID;
+  *out = nullptr;
+  if (n > LLD_PNP_MAX_SOLVERS || n_keypoints > LLD_PNP_MAX_KEYPOINTS) return LLD_ERR_UNSUPPORTED;
+  if (int st = pnp_check_params(*params)) return st;
+  if (n_keypoints < 0 || !(fx > 0.0f) || !(fy > 0.0f)) return LLD_ERR_INVALID;
+  for (int s = 0; s < n; ++s) if (n_corr[s] < 0 || n_corr[s] > n_keypoints) return LLD_ERR_INVALID;
+  auto* b = new lld_pnp_batch();
+  b->ctx = ctx; b->n = n;
+  b->desc.resize(n); b->kp_off.resize(n);
+  int64_t ntot = 0;
+  std::vector<PnpState> st(n);
+  for (int s = 0; s < n; ++s) pnp_describe(b, s, n_corr[s], n_keypoints, fx, fy, cx, cy, seed[s], params, &ntot, &st[s]);
+  if (int rc = pnp_alloc(b, st, ntot)) { lld_pnp_batch_destroy(b); return rc; }
+  for (int s = 0; s < n; ++s) off[s] = b->desc[s].off;
+  slab->pt = const_cast<float4*>(b->dev.pt); slab->uv = const_cast<float2*>(b->dev.uv); slab->kp = const_cast<int32_t*>(b->dev.kp);
+  *out = b;
+  return LLD_OK;
+}
+
+int batch_iterate_live(lld_pnp_batch* b, int32_t n_iterations, const uint8_t* live_d) {
+  if (!b || n_iterations < 1) return LLD_ERR_INVALID;
+  if (n_iterations > LLD_PNP_MAX_ITERATIONS) return LLD_ERR_UNSUPPORTED;
+  return pnp_iterate(b, n_iterations, nullptr, live_d);
+}
+
+const PnpRes* batch_results_dev(const lld_pnp_batch* b) { return b->dev.res; }
+const uint8_t* batch_flags_dev(const lld_pnp_batch* b, int32_t solver) { return b->dev.flags + b->kp_off[solver]; }
+
+}  // namespace lld_pnp
 
 extern "C" int lld_pnp_batch_find(lld_pnp_batch* b, const uint8_t* active) {
   if (!b) return LLD_ERR_INVALID;

@@ -891,6 +891,60 @@ __global__ __launch_bounds__(kAsmThreads) void pose_assemble_kernel(lld_track::P
     *reinterpret_cast<PoseFrameDev*>(img + Y.frames) = F;
   }
 }
+
+// The point half of pose_assemble_kernel for slot blockIdx.x of n_slots copies of the frame's state: slot s owns points [s nt, s nt + n_pt)
+// of the image.  A slot that does not run gets no edges: pose_opt_kernel leaves such a frame at once (fewer than three points).
+__global__ __launch_bounds__(kAsmThreads) void pose_slots_assemble_kernel(lld_track::PoseSlotsDev in, PoseAsmConsts dc, char* img, PoseLayout Y, int* pt_kp) {
+  __shared__ int scan_lds[kAsmThreads / 64 + 1];
+  const int tid = threadIdx.x, s = blockIdx.x;
+  const bool run = in.run[s] != 0;
+  const uint8_t* kp_has = in.kp_has + (size_t)s * in.nt;
+  const float* kp_world = in.kp_world + 3 * (size_t)s * in.nt;
+  double* pt = reinterpret_cast<double*>(img + Y.pt);
+  const int per = (in.nt + kAsmThreads - 1) / kAsmThreads, k0 = min(tid * per, in.nt), k1 = min(k0 + per, in.nt);
+  int cnt = 0;
+  if (run) for (int k = k0; k < k1; k++) cnt += kp_has[k] ? 1 : 0;
+  int n_pt;
+  int e = block_excl_scan(cnt, scan_lds, n_pt);
+  const size_t base = (size_t)s * in.nt;
+  for (int k = k0; k < k1 && run; k++) {
+    if (!kp_has[k]) continue;
+    const float ur = in.t_uright ? in.t_uright[k] : -1.f;
+    const size_t at = base + e;
+    pt[0 * Y.NP + at] = (double)kp_world[3 * k]; pt[1 * Y.NP + at] = (double)kp_world[3 * k + 1]; pt[2 * Y.NP + at] = (double)kp_world[3 * k + 2];
+    pt[3 * Y.NP + at] = (double)in.t_xy[2 * k]; pt[4 * Y.NP + at] = (double)in.t_xy[2 * k + 1];
+    pt[5 * Y.NP + at] = ur < 0.f ? -1.0 : (double)ur;
+    pt[6 * Y.NP + at] = (double)in.inv_sigma2[in.t_octave[k]];
+    pt_kp[at] = k;
+    e++;
+  }
+  if (tid == 0) {
+    PoseFrameDev F;
+    F.cam = lld::make_camk(in.cam);
+    for (int k = 0; k < 7; k++) F.T0[k] = in.pose_qt[7 * s + k];
+    F.pt_off = (int)base; F.n_pt = n_pt; F.le_off = 0; F.n_le = 0; F.ln_off = 0; F.n_ln = 0;
+    F.delta_mono = dc.delta_mono; F.delta_stereo = dc.delta_stereo; F.delta_ln_stereo = dc.delta_ln_stereo; F.delta_ln_mono = dc.delta_ln_mono;
+    F.thr_ln_stereo = dc.thr_ln_stereo; F.thr_ln_mono = dc.thr_ln_mono;
+    reinterpret_cast<PoseFrameDev*>(img + Y.frames)[s] = F;
+  }
+}
+
+// ... and what pose_opt_kernel writes through pt_kp / kp_outlier / track_out for one resident frame, per slot that ran.
+__global__ __launch_bounds__(256) void pose_slots_scatter_kernel(lld_track::PoseSlotsDev in, const char* img, PoseLayout Y, const int* pt_kp) {
+  const int s = blockIdx.x;
+  if (!in.run[s]) return;
+  const PoseFrameDev& F = reinterpret_cast<const PoseFrameDev*>(img + Y.frames)[s];
+  const uint8_t* pt_outlier = reinterpret_cast<const uint8_t*>(img + Y.pt_outlier);
+  for (int i = threadIdx.x; i < F.n_pt; i += 256) in.kp_outlier[(size_t)s * in.nt + pt_kp[F.pt_off + i]] = pt_outlier[F.pt_off + i];
+  if (threadIdx.x == 0) {
+    const PoseOut& o = reinterpret_cast<const PoseOut*>(img + Y.out)[s];
+    double* to = in.pose_out + 12 * (size_t)s;
+    for (int k = 0; k < 7; k++) to[k] = o.qt[k];
+    to[7] = o.chi2;
+    int* ti = reinterpret_cast<int*>(to + 8);
+    ti[0] = o.n_inliers; ti[1] = o.lm_iterations; ti[2] = o.lm_trials; ti[3] = F.n_pt; ti[4] = F.n_pt; ti[5] = 0;
+  }
+}
 }  // namespace
 
 namespace lld_track {
@@ -921,6 +975,33 @@ int pose_track_launch(lld_ctx* ctx, hipStream_t st, const PoseTrackDev& in, cons
   if (lds <= kPoseLdsBudget) s = pose_launch_as<true, float, kPoseThreadsMax>(ctx, st, 1, lds, fr, A, po, prm);
   else s = pose_launch_as<false, double, kPoseThreadsMax>(ctx, st, 1, 0, fr, A, po, prm);
   return s;
+}
+
+static PoseLayout slots_layout(int n_slots, int nt) { return pose_layout(n_slots, (size_t)n_slots * nt, 0, 0, true); }
+size_t pose_slots_work_bytes(int n_slots, int nt) {
+  return slots_layout(n_slots, nt).total + lld_slab::pad(4 * ((size_t)n_slots * nt + 1)) + 256;
+}
+int pose_slots_launch(lld_ctx* ctx, hipStream_t st, const PoseSlotsDev& in, const lld_pose_params& prm, void* d_work) {
+  if (in.n_slots <= 0) return LLD_OK;
+  char* d_img = static_cast<char*>(d_work);
+  const PoseLayout Y = slots_layout(in.n_slots, in.nt);
+  int* pt_kp = reinterpret_cast<int*>(d_img + Y.total);
+  const float dMono = (float)std::sqrt(5.991), dStereo = (float)std::sqrt(7.815);
+  float dLnS = dStereo, dLnM = dMono;
+  dLnS *= prm.gamma; dLnM *= prm.gamma;
+  PoseAsmConsts dc{(double)dMono, (double)dStereo, (double)dLnS, (double)dLnM, (double)(dLnS * dLnS), (double)(dLnM * dLnM)};
+  hipLaunchKernelGGL(pose_slots_assemble_kernel, dim3(in.n_slots), dim3(kAsmThreads), 0, st, in, dc, d_img, Y, pt_kp);
+  const PoseArrays A = pose_arrays(d_img, Y);                  // (no pt_kp / track_out: pose_slots_scatter_kernel hands the slots their results)
+  const size_t lds = pose_lds_bytes(in.nt, 0, 0, true);
+  const PoseFrameDev* fr = reinterpret_cast<const PoseFrameDev*>(d_img + Y.frames);
+  PoseOut* po = reinterpret_cast<PoseOut*>(d_img + Y.out);
+  int s;
+  if (lds <= kPoseLdsBudget) s = pose_launch_as<true, float, kPoseThreadsMax>(ctx, st, in.n_slots, lds, fr, A, po, prm);
+  else s = pose_launch_as<false, double, kPoseThreadsMax>(ctx, st, in.n_slots, 0, fr, A, po, prm);
+  if (s) return s;
+  hipLaunchKernelGGL(pose_slots_scatter_kernel, dim3(in.n_slots), dim3(256), 0, st, in, static_cast<const char*>(d_img), Y, static_cast<const int*>(pt_kp));
+  LLD_HIP_TRY(hipGetLastError());
+  return LLD_OK;
 }
 }  // namespace lld_track
 

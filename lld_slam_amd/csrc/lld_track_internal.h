@@ -65,6 +65,17 @@ int orbs_project_last_frame(hipStream_t st, const lld_frame* f, const lld_frame_
 int orbs_project_local_points(hipStream_t st, const lld_frame* f, const lld_frame_view* view_h, const lld_frame_view* view_d, const MapPointsDev& mp, float cos_limit, float th,
                               void* d_qrec, uint8_t* d_in_view, int32_t* d_n_in_view);
 int orbs_launch(lld_ctx* ctx, hipStream_t st, const lld_frame* f, const void* problem_d);
+// ORBmatcher::SearchByProjection(Frame&, KeyFrame*, sAlreadyFound, th, ORBdist) (src/ORBmatcher.cc:1472-1599, LLD_ORB_PROJ_RELOC) on n_slots copies
+// of the frame's mvpMapPoints at once, each against its own keyframe: slot s projects its candidate's MapPoints through ITS view (device
+// memory) and searches with ITS occupancy.  A slot runs iff *run != 0 (projection) / its Problem's run_if holds (search).
+struct RelocProjSlot { int32_t n; int32_t pad; const float* pos; const float* maxd; const float* mind; const uint8_t* skip; const float* angle; void* qrec;
+                       const lld_frame_view* view; const int32_t* run; };
+int orbs_project_reloc_slots(hipStream_t st, const lld_frame* f, int n_slots, int n_max, const RelocProjSlot* slots_d, float th);
+// orbs_fill_problem for that search: occupancy = any MapPoint on the keypoint (:1528), bestDist <= accept_max, the rotation histogram, no ratio test
+void orbs_fill_problem_reloc(const lld_frame* f, int nq, const uint8_t* d_occupied, const void* d_qrec, const uint32_t* d_qdesc, const SearchOut& out, void* d_cache,
+                             int accept_max, RunIf run_if, const ApplyDev& ap, void* problem_h);
+size_t orbs_problem_stride();                                              // of an array of problems (orbs_launch_n)
+int orbs_launch_n(lld_ctx* ctx, hipStream_t st, const lld_frame* f, const void* problems_d, int n);   // one workgroup per problem
 
 // ---------------------------------------------------------------- ORBmatcher::SearchByBoW(KeyFrame*, Frame&) on device arrays (lld_frame_track_bow.hip)
 // The frame's FeatureVector is the one in lld_frame::d_bow (its node count is read on the device), the keyframe's an uploaded CSR.  One
@@ -109,6 +120,21 @@ struct PoseTrackDev {
 };
 size_t pose_track_work_bytes(int nt, int nl);
 int pose_track_launch(lld_ctx* ctx, hipStream_t st, const PoseTrackDev& in, const lld_pose_params& prm, void* d_work);
+// The same PoseOptimization on n_slots COPIES of one frame's mvpMapPoints / mvbOutlier / mTcw at once (Tracking::Relocalization evaluates its
+// candidates side by side, lld_frame_reloc.hip): points only, one workgroup of pose_opt_kernel per slot.  Slot s runs iff run[s] != 0 - a
+// slot that does not run keeps its flags and its pose_out.
+struct PoseSlotsDev {
+  int n_slots, nt;
+  const float* t_xy; const float* t_uright; const int32_t* t_octave;       // the frame's keypoints (shared by the slots)
+  const uint8_t* kp_has; const float* kp_world;                            // [n_slots][nt], [n_slots][nt][3]
+  const double* pose_qt;                                                   // [n_slots][7]
+  const int32_t* run;                                                      // [n_slots]
+  lld_camera cam; float inv_sigma2[LLD_ORB_MAX_LEVELS];
+  uint8_t* kp_outlier;                                                     // [n_slots][nt]
+  double* pose_out;                                                        // [n_slots][12], each as PoseTrackDev::pose_out
+};
+size_t pose_slots_work_bytes(int n_slots, int nt);
+int pose_slots_launch(lld_ctx* ctx, hipStream_t st, const PoseSlotsDev& in, const lld_pose_params& prm, void* d_work);
 
 }  // namespace lld_track
 

@@ -293,6 +293,47 @@ class DeviceTrackedFrame:
                     "lld_frame_track_reference_keyframe")
         return view, qt
 
+    def relocalize(self, candidates, seeds=None, Tcw_f32=None, pnp_params=None):
+        """Tracking::Relocalization as stage 1 (lld_frame_relocalize), after compute_bow: one call, synchronous.  candidates: vpCandidateKFs,
+        each a dict as track_reference_keyframe takes it plus max_distance / min_distance [n] of its MapPoints, optionally point_desc [n,8]
+        (pMP->GetDescriptor(); default: the keyframe's desc) and is_bad.  seeds: one per candidate (default: its index).  Tcw_f32: the
+        pose the frame keeps when nothing matches (default: identity).  Returns the record as a dict; on matched, track_local_map can follow."""
+        from .host import se3_from_tcw_f32
+        from .abi import c_uint32_p
+        K = len(candidates)
+        T = np.eye(4, dtype=np.float32) if Tcw_f32 is None else np.ascontiguousarray(Tcw_f32, np.float32).reshape(4, 4)
+        view = orb_search.frame_view(T, self.cam, self.F)
+        qt = np.ascontiguousarray(se3_from_tcw_f32(self.lib, T), np.float64)
+        kfs = (abi.RefKeyFrame * max(K, 1))(); ex = (abi.RelocCandidate * max(K, 1))(); keep = []
+        for i, c in enumerate(candidates):
+            k, kept = ref_keyframe_struct(c)
+            kfs[i] = k
+            maxd = None if c.get("max_distance") is None else np.ascontiguousarray(c["max_distance"], np.float32)
+            mind = None if c.get("min_distance") is None else np.ascontiguousarray(c["min_distance"], np.float32)
+            pd = None if c.get("point_desc") is None else np.ascontiguousarray(c["point_desc"], np.uint32).reshape(-1, 8)
+            keep.append((kept, maxd, mind, pd))
+            ex[i].max_distance = None if maxd is None else maxd.ctypes.data_as(c_float_p)
+            ex[i].min_distance = None if mind is None else mind.ctypes.data_as(c_float_p)
+            ex[i].point_desc = None if pd is None else pd.ctypes.data_as(c_uint32_p)
+            ex[i].is_bad = int(bool(c.get("is_bad", False)))
+            ex[i].seed = int(i if seeds is None else seeds[i]) & 0xFFFFFFFF
+        prm = abi.PnPParams()
+        self.lib.fn("pnp_params_default")(C.byref(prm))
+        for k_, v in (pnp_params or {}).items():
+            setattr(prm, k_, v)
+        m = max(K, 1)
+        a = dict(n_bow=np.zeros(m, np.int32), discarded=np.zeros(m, np.uint8), rounds=np.zeros(m, np.int32), n_good_last=np.zeros(m, np.int32),
+                 rungs=np.zeros(m, np.int32), n_additional1=np.zeros(m, np.int32), n_additional2=np.zeros(m, np.int32))
+        r = abi.RelocResult()
+        for k_, v in a.items():
+            setattr(r, k_, v.ctypes.data_as(c_uint8_p if v.dtype == np.uint8 else c_int32_p))
+        self._check(self.lib.fn("frame_relocalize")(self.res.handle, C.byref(self.params), C.byref(view), qt.ctypes.data_as(c_double_p), K, kfs, ex, C.byref(prm),
+                                                    C.byref(r)), "lld_frame_relocalize")
+        out = {k_: v[:K].copy() for k_, v in a.items()}
+        out.update(matched=int(r.matched), winner=int(r.winner), round=int(r.round), n_good=int(r.n_good), n_rounds=int(r.n_rounds), n_kept=int(r.n_kept),
+                   Tcw=np.array(list(r.Tcw), np.float32).reshape(4, 4))
+        return out
+
     def set_state(self, Tcw_f32, kp_point_id, kp_world_pos, kp_has_obs=None, kp_outlier=None, seen_point_id=(), ln_line_id=None, ln_x0=None, ln_dir=None,
                   ln_outlier=None, tracked_line_id=()):
         """lld_frame_track_set_state: stage 1 ran elsewhere (TrackReferenceKeyFrame / Relocalization); the frame's float pose and what it holds."""
@@ -344,6 +385,124 @@ class DeviceTrackedFrame:
             for c in _COUNTERS: d[c] = int(getattr(r, c))
             res.append(d)
         return res
+
+
+# ------------------------------------------------------------------------------------------------ Relocalization, call by call
+def relocalize_call_by_call(ctx, voc, levelsup, F: orb_search.Frame, cam, candidates, seeds=None, pnp_params=None, gamma=0.5, max_rounds=400):
+    """Tracking::Relocalization (src/Tracking.cc:1837-1998) driven from the host one library call at a time - the alternative recipe of
+    INTEGRATION.md section 11 - with the same arguments and the same record as DeviceTrackedFrame.relocalize: lld_bow_transform for the
+    frame's FeatureVector (the candidates bring theirs), lld_orb_search_run's SearchByBoW per candidate, lld_pnp_batch_* with a download per round, lld_pose_opt and
+    lld_orb_search_projected (LLD_ORB_PROJ_RELOC) per rung.  Returns the record plus what the frame holds at the end (kp_point_id,
+    kp_outlier, kp_world_pos, kp_has_obs, Tcw) for lld_frame_track_set_state."""
+    from types import SimpleNamespace
+    from .host import ORBmatcher
+    from .pnp import DEFAULT_PARAMS, PnPsolverBatch
+    from .vocabulary import common_nodes
+    K = len(candidates); nt = F.n
+    seeds = list(range(K)) if seeds is None else list(seeds)
+    names = ("probability", "min_inliers", "max_iterations", "min_set", "epsilon", "th2")
+    prm = tuple((pnp_params or {}).get(k, d) for k, d in zip(names, DEFAULT_PARAMS))
+    fvF = voc.transform(F.desc, levelsup)
+    m1, m2 = ORBmatcher(ctx, 0.75, True), ORBmatcher(ctx, 0.9, True)
+    n_bow = np.zeros(K, np.int32); discarded = np.zeros(K, np.uint8); slot = [None] * K; problems = []; which = []
+    fx, fy, cx, cy = [float(np.float32(c)) for c in cam[:4]]
+    for i, kf in enumerate(candidates):
+        if kf.get("is_bad"):
+            discarded[i] = 1; continue
+        n = len(kf["angle"])
+        KF = orb_search.Frame(desc=np.asarray(kf["desc"], np.uint32).reshape(-1, 8), xy=np.zeros((n, 2), np.float32), octave=np.zeros(n, np.int32),
+                              uright=np.full(n, -1.0, np.float32), angle=np.asarray(kf["angle"], np.float32)).normalise()
+        # pKF->mFeatVec exists since the keyframe was made (KeyFrame::ComputeBoW): the candidate's own CSR, as lld_frame_relocalize takes it
+        fvK = SimpleNamespace(node=np.asarray(kf["node"], np.int32), node_start=np.asarray(kf["node_start"], np.int32), feature=np.asarray(kf["feature"], np.int32))
+        out = m1.SearchByBoWFrame(KF, F, common_nodes(fvK, fvF), (np.asarray(kf["point_id"]) >= 0).astype(np.uint8))
+        qk = out.query_kp if len(out.query_kp) else np.zeros(1, np.int64)
+        slot[i] = np.where(out.owner >= 0, qk[np.maximum(out.owner, 0)], -1)
+        n_bow[i] = out.n_matches
+        if out.n_matches < 15:
+            discarded[i] = 1; continue
+        k = np.nonzero(slot[i] >= 0)[0]
+        problems.append(dict(xyz=np.asarray(kf["world_pos"], np.float32)[slot[i][k]], uv=F.xy[k], sigma2=F.sigma2[F.octave[k]], kp_index=k, n_keypoints=nt,
+                             fx=fx, fy=fy, cx=cx, cy=cy, seed=seeds[i]))
+        which.append(i)
+    n_kept = len(which)
+    rounds = np.zeros(K, np.int32); good_last = np.full(K, -1, np.int32); rungs = np.zeros(K, np.int32); add1 = np.zeros(K, np.int32); add2 = np.zeros(K, np.int32)
+    kp_has = np.zeros(nt, bool); kp_id = np.full(nt, -1, np.int64); kp_world = np.zeros((nt, 3), np.float32); kp_obs = np.zeros(nt, np.uint8); kp_out = np.zeros(nt, np.uint8)
+    state = dict(T=None)
+    opt = Optimizer(ctx)
+
+    def optimise():
+        prob, idx = pose_frame_from_matches(F, cam, state["qt"], kp_world, kp_has)
+        o = opt.PoseOptimization(prob, gamma)
+        kp_out[idx] = o.pt_outlier
+        if len(idx) >= 3:
+            state["T"] = qt_to_tcw_f32(ctx.lib, o.pose_qt)
+            state["qt"] = se3_from_tcw(state["T"])
+        return int(o.n_inliers)
+
+    def se3_from_tcw(T):
+        from .host import se3_from_tcw_f32
+        return np.ascontiguousarray(se3_from_tcw_f32(ctx.lib, T), np.float64)
+
+    def project(kf, found, th, dist):
+        pid = np.asarray(kf["point_id"])
+        desc = kf["point_desc"] if kf.get("point_desc") is not None else kf["desc"]
+        mp = dict(world_pos=kf["world_pos"], max_distance=kf["max_distance"], min_distance=kf["min_distance"], desc=desc,
+                  skip=((pid < 0) | np.isin(pid, list(found))).astype(np.uint8))
+        out, _, _ = m2.SearchByProjectionRelocPoints(F, orb_search.frame_view(state["T"], cam, F), mp, kf["angle"], kp_has.astype(np.uint8), th, dist)
+        obs = kf.get("has_obs") if kf.get("has_obs") is not None else np.ones(len(pid), np.uint8)
+        for k in np.nonzero(out.owner >= 0)[0]:
+            q = int(out.owner[k])
+            kp_has[k] = True; kp_world[k] = np.asarray(kf["world_pos"], np.float32)[q]; kp_id[k] = int(pid[q]); kp_obs[k] = int(obs[q])
+        return int(out.n_matches)
+
+    def discard():
+        bad = kp_has & (kp_out != 0)
+        kp_has[bad] = False; kp_id[bad] = -1
+    matched, winner, win_round, n_good, n_round = 0, -1, 0, 0, 0
+    batch = PnPsolverBatch(ctx, problems, prm) if n_kept else None
+    try:
+        live = np.ones(n_kept, bool)
+        while live.any() and not matched and n_round < max_rounds:
+            n_round += 1
+            res = batch.iterate(5, live)
+            for s in range(n_kept):
+                if not live[s]: continue
+                i = which[s]; kf = candidates[i]; o = res[s]
+                rounds[i] += 1
+                if o.no_more: live[s] = False; discarded[i] = 1
+                if o.Tcw is None: continue
+                T = np.eye(4, dtype=np.float32); T[:3, :] = o.Tcw
+                state["T"] = T; state["qt"] = se3_from_tcw(T)
+                inl = o.inliers != 0
+                pid = np.asarray(kf["point_id"]); q = np.maximum(slot[i], 0)
+                obs = kf.get("has_obs") if kf.get("has_obs") is not None else np.ones(len(pid), np.uint8)
+                kp_has[:] = inl; kp_id[:] = np.where(inl, pid[q], -1); kp_world[:] = np.where(inl[:, None], np.asarray(kf["world_pos"], np.float32)[q], 0)
+                kp_obs[:] = np.where(inl, np.asarray(obs)[q], 0)
+                found = set(int(x) for x in kp_id[inl])
+                g = optimise(); mask = abi.RELOC_RUNG_POSE1; a1 = a2 = 0
+                if g >= 10:
+                    discard()
+                    if g < 50:
+                        a1 = project(kf, found, 10.0, 100); mask |= abi.RELOC_RUNG_SEARCH1
+                        if a1 + g >= 50:
+                            g = optimise(); mask |= abi.RELOC_RUNG_POSE2
+                            if 30 < g < 50:
+                                a2 = project(kf, set(int(x) for x in kp_id[kp_has]), 3.0, 64); mask |= abi.RELOC_RUNG_SEARCH2
+                                if g + a2 >= 50:
+                                    g = optimise(); mask |= abi.RELOC_RUNG_POSE3
+                                    discard()
+                good_last[i], rungs[i], add1[i], add2[i] = g, mask, a1, a2
+                if g >= 50:
+                    matched, winner, win_round, n_good = 1, i, n_round, g
+                    break
+    finally:
+        if batch is not None and hasattr(batch, "close"): batch.close()
+    if not matched:
+        kp_has[:] = False; kp_id[:] = -1
+    return dict(matched=matched, winner=winner, round=win_round, n_good=n_good, n_rounds=n_round, n_kept=n_kept, n_bow=n_bow, discarded=discarded, rounds=rounds,
+                n_good_last=good_last, rungs=rungs, n_additional1=add1, n_additional2=add2, kp_point_id=np.where(kp_has, kp_id, -1).astype(np.int32),
+                kp_outlier=np.where(kp_has, kp_out, 0).astype(np.uint8), kp_world_pos=np.where(kp_has[:, None], kp_world, 0).astype(np.float32),
+                kp_has_obs=np.where(kp_has, kp_obs, 0).astype(np.uint8), Tcw=state["T"] if matched else None)
 
 
 # ------------------------------------------------------------------------------------------------ flat files of examples/harness.cpp `track`
@@ -438,3 +597,44 @@ def read_refkf_result(path, nt, n_kf):
         a["feat_vec"] = dict(node=np.fromfile(f, np.int32, nn), node_start=np.fromfile(f, np.int32, nn + 1), feature=np.fromfile(f, np.int32, nv))
         a["inliers"] = int(np.fromfile(f, np.int32, 1)[0]); a["after_stage2"] = state(f)
     return dict(records=recs, adapter=a)
+
+
+# ------------------------------------------------------------------------------------------------ flat files of examples/reloc_harness.cpp
+def write_reloc_scene(path, F: orb_search.Frame, cam, candidates, seeds, Tcw0, levelsup, gamma=0.5):
+    """A frame, the pose it carries and the candidates DeviceTrackedFrame.relocalize takes, as the flat binary `examples/reloc_harness` reads."""
+    T = np.ascontiguousarray(Tcw0, np.float32).reshape(4, 4)
+    view = orb_search.frame_view(T, cam, F)
+    f32 = lambda a: np.ascontiguousarray(a, np.float32); i32 = lambda a: np.ascontiguousarray(a, np.int32); u8 = lambda a: np.ascontiguousarray(a, np.uint8)
+    with open(path, "wb") as f:
+        i32([F.n, F.scale.shape[0], len(candidates), int(levelsup)]).tofile(f)
+        f32([F.min_x, F.min_y, F.max_x, F.max_y, F.width_inv, F.height_inv]).tofile(f)
+        f32(F.scale).tofile(f); f32(F.sigma2).tofile(f); f32(F.inv_sigma2).tofile(f)
+        np.array([float(np.float32(c)) for c in cam] + [gamma], np.float64).tofile(f)
+        np.ascontiguousarray(F.desc, np.uint32).tofile(f); f32(F.xy).tofile(f); i32(F.octave).tofile(f); f32(F.uright).tofile(f); f32(F.angle).tofile(f)
+        f.write(bytes(view)); f32(T).tofile(f)
+        for kf, seed in zip(candidates, seeds):
+            n = len(kf["angle"])
+            obs = kf.get("has_obs") if kf.get("has_obs") is not None else np.ones(n, np.uint8)
+            pdesc = kf["point_desc"] if kf.get("point_desc") is not None else kf["desc"]
+            i32([n, len(kf["node"]), len(kf["feature"]), int(bool(kf.get("is_bad", False))), int(seed)]).tofile(f)
+            np.ascontiguousarray(kf["desc"], np.uint32).tofile(f); np.ascontiguousarray(pdesc, np.uint32).tofile(f); f32(kf["angle"]).tofile(f); i32(kf["point_id"]).tofile(f)
+            f32(kf["world_pos"]).tofile(f); u8(obs).tofile(f); f32(kf["max_distance"]).tofile(f); f32(kf["min_distance"]).tofile(f)
+            i32(kf["node"]).tofile(f); i32(kf["node_start"]).tofile(f); i32(kf["feature"]).tofile(f)
+
+
+def read_reloc_result(path, nt, K):
+    """What `examples/reloc_harness` wrote: dict(returned, record, kp_point_id, kp_outlier) of the lld_amd.hpp route and adapter=dict(returned,
+    point_id, outlier, Tcw) of the object graph."""
+    with open(path, "rb") as f:
+        out = dict(returned=int(np.fromfile(f, np.int32, 1)[0]))
+        h = np.fromfile(f, np.int32, 6)
+        rec = dict(zip(("matched", "winner", "round", "n_good", "n_rounds", "n_kept"), (int(x) for x in h)))
+        rec["Tcw"] = np.fromfile(f, np.float32, 16).reshape(4, 4)
+        for k, dt in (("n_bow", np.int32), ("discarded", np.uint8), ("rounds", np.int32), ("n_good_last", np.int32), ("rungs", np.int32), ("n_additional1", np.int32),
+                      ("n_additional2", np.int32)):
+            rec[k] = np.fromfile(f, dt, K)
+        out["record"] = rec
+        out["kp_point_id"] = np.fromfile(f, np.int32, nt); out["kp_outlier"] = np.fromfile(f, np.uint8, nt)
+        out["adapter"] = dict(returned=int(np.fromfile(f, np.int32, 1)[0]), point_id=np.fromfile(f, np.int32, nt), outlier=np.fromfile(f, np.uint8, nt),
+                              Tcw=np.fromfile(f, np.float32, 16).reshape(4, 4))
+    return out
