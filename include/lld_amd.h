@@ -472,7 +472,23 @@ int lld_match_l2f32_batch_dev(lld_ctx* ctx, int batch, const float* q_dev, int n
  * assignment.  For left line j = 0..nq-1 in order: over right lines oi not yet taken and
  * with gate[j][oi] != 0 (CheckLinePair's geometric gates, :81-109, computed by the caller),
  * pick the strict running minimum of the descriptor distance below `tau`; the winner is
- * masked for all later j.  matches[j] = oi or -1. */
+ * masked for all later j.  matches[j] = oi or -1.
+ *
+ * Limits of the line matchers (lld_line_match_greedy, lld_line_match_stereo, lld_line_track_match; rows = nq or
+ * n_map, columns = nt or n_cur).  Each is decided on the host from the arguments alone and refused BEFORE anything is
+ * allocated, copied or queued; the context stays usable and the next valid call is unaffected:
+ *   LLD_ERR_INVALID      a required pointer is NULL, a count is negative, dim <= 0, sx / sy not > 0, an octave outside
+ *                        0..64, a stereo partner index >= the count of right lines;
+ *   LLD_ERR_UNSUPPORTED  dim > LLD_LINE_DIM_MAX (128) - lld_line_match_last_frame alone takes up to
+ *                        LLD_LINE_LASTKF_DIM_MAX (4096);
+ *   LLD_ERR_UNSUPPORTED  columns * 8 + dim * 4 > LLD_LINE_LDS_CEILING (150 KiB): one row of distances and the row's
+ *                        descriptor live in LDS (19 164 columns at dim 72);
+ *   LLD_ERR_UNSUPPORTED  (rows + columns) * 4 + 16 > LLD_LINE_LDS_CEILING: the greedy resolve keeps one word per row
+ *                        and per column in LDS (38 396 rows and columns together).
+ * lld_line_match_last_frame has no size ceiling of this kind (its LDS holds one descriptor: dim * 4 + 16 bytes). */
+#define LLD_LINE_DIM_MAX 128
+#define LLD_LINE_LASTKF_DIM_MAX 4096
+#define LLD_LINE_LDS_CEILING (150 * 1024)
 int lld_line_match_greedy(lld_ctx* ctx, const float* desc_left, int nq, const float* desc_right,
                           int nt, int dim, const uint8_t* gate /*[nq][nt]*/, double tau,
                           int32_t* matches /*[nq]*/, double* match_dist /*[nq] or NULL*/);
@@ -490,7 +506,8 @@ int lld_line_match_greedy(lld_ctx* ctx, const float* desc_left, int nq, const fl
  *      have z >= 0 (:104-109);
  * then the greedy, order-dependent descriptor assignment of lld_line_match_greedy.
  * lines: [n][4] float startPointX, startPointY, endPointX, endPointY of the KeyLines.
- * K: row-major 3x3 (Frame.cc:118-120).  b: mbf / fx.  gate_out: [nq][nt] bytes or NULL. */
+ * K: row-major 3x3 (Frame.cc:118-120).  b: mbf / fx.  gate_out: [nq][nt] bytes or NULL.
+ * Refusals and size ceilings: see lld_line_match_greedy (LLD_ERR_INVALID / LLD_ERR_UNSUPPORTED, nothing is queued). */
 typedef struct {
   double K[9];
   double b;
@@ -525,7 +542,9 @@ int lld_line_match_stereo(lld_ctx* ctx, const lld_line_stereo_params* params,
  * map_x0 / map_dir: MapLine::GetMinimalPos; map_x1 / map_x2: GetMainPoints3D.  lines: [n][4] float startPointX,
  * startPointY, endPointX, endPointY.  line_matches[si]: index of the right line matched to left line si or -1.
  * matches[i] = frame line or -1; gate_out [n_map][n_cur] (optional): 1 where a pair passed every test but the
- * descriptor threshold. */
+ * descriptor threshold.
+ * Refusals and size ceilings (rows = n_map, columns = n_cur): see lld_line_match_greedy; LLD_ERR_INVALID or
+ * LLD_ERR_UNSUPPORTED is returned before anything is allocated or queued. */
 typedef struct {
   double K[9];
   double T_curr[16];
@@ -558,7 +577,10 @@ int lld_line_track_match(lld_ctx* ctx, const lld_line_track_params* params,
  * (:1580-1592).  No step depends on another line: rows run in parallel.
  * match_last[i]: the accepted line of the last frame or -1; created[i]: 1 if the reference would construct the
  * MapLine (x0 / dir [n_cur][3] valid).  The sign of dir is the build's (largest component positive): Eigen's JacobiSVD
- * is not restated and a 3D line has no orientation.  T_curr, T_last: camera-to-world, row-major 4x4. */
+ * is not restated and a 3D line has no orientation.  T_curr, T_last: camera-to-world, row-major 4x4.
+ * Refused before anything is queued: LLD_ERR_INVALID for a NULL required pointer, a negative count, dim <= 0, sx / sy
+ * not > 0, an octave of the last frame outside 0..64 or a partner index >= its right count; LLD_ERR_UNSUPPORTED for
+ * dim > LLD_LINE_LASTKF_DIM_MAX (4096). */
 typedef struct {
   double K[9];
   double T_curr[16], T_last[16];

@@ -936,6 +936,7 @@ static int line_match_core(lld_ctx* ctx, const lld_line_stereo_params* geom, con
   if (nq == 0) return LLD_OK;
   if (nt == 0) { for (int i = 0; i < nq; i++) { matches[i] = -1; if (match_dist) match_dist[i] = 1.7976931348623157e308; } return LLD_OK; }
   if ((size_t)nt * 8 + (size_t)dim * 4 > 150 * 1024) return LLD_ERR_UNSUPPORTED;         // one row of distances lives in LDS (nt <= ~19 000)
+  if (line_resolve_lds(nq, nt) > 150 * 1024) return LLD_ERR_UNSUPPORTED;                  // blk + pick of the resolve: refused before anything is allocated or queued
   LLD_HIP_TRY(hipSetDevice(ctx->device));
   const size_t pairs = (size_t)nq * nt;
   auto pad = [](size_t b) { return (b + 255) & ~size_t(255); };
@@ -1042,6 +1043,7 @@ int lld_line_track_match(lld_ctx* ctx, const lld_line_track_params* prm, int n_m
   if (n_map == 0) return LLD_OK;
   if (n_cur == 0) { for (int i = 0; i < n_map; i++) { matches[i] = -1; if (match_dist) match_dist[i] = 1.7976931348623157e308; } return LLD_OK; }
   if ((size_t)n_cur * 8 + (size_t)dim * 4 > 150 * 1024) return LLD_ERR_UNSUPPORTED;
+  if (line_resolve_lds(n_map, n_cur) > 150 * 1024) return LLD_ERR_UNSUPPORTED;            // (as in line_match_core: before the allocation and the first launch)
   LLD_HIP_TRY(hipSetDevice(ctx->device));
   const size_t pairs = (size_t)n_map * n_cur;
   auto pad = [](size_t b) { return (b + 255) & ~size_t(255); };

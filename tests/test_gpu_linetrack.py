@@ -4,6 +4,8 @@ import pytest
 
 from lld_slam_amd import Tracking, synth
 
+from line_ref import track_naive
+
 pytestmark = pytest.mark.gpu
 
 
@@ -26,6 +28,10 @@ def test_add_lines_from_matches_oracle(gpu_ctx, oracle, scene, kw):
     assert np.all(gg[og.astype(bool)] == 1)
     assert not np.any(gg[L["skip"].astype(bool)])
     assert not np.any(gg[:, F["occupied"].astype(bool)])
+    # and it EQUALS the order-independent gate of the plain numpy restatement: an extra one from a missing or loosened gate fails here
+    nm, ng = track_naive(P, L, F, want_gate=True, **kw)
+    np.testing.assert_array_equal(gg, ng)
+    np.testing.assert_array_equal(gm, nm)
     assert (gm >= 0).sum() > 10
 
 
