@@ -6,72 +6,10 @@ import pytest
 
 import oracle_orbsearch as OS
 from lld_slam_amd import orb_search, synth
-from lld_slam_amd.orb_search import FRAME_GRID_COLS, FRAME_GRID_ROWS, Frame, orb_levels
+from lld_slam_amd.orb_search import Frame, orb_levels
+from orbsearch_ref import popcount, py_features_in_area, py_grid, py_rot_bin, py_search_for_initialization, py_search_map, py_three_maxima
 
 f32 = np.float32
-
-
-def popcount(a, b):
-    return int(np.unpackbits((a ^ b).view(np.uint8)).sum())
-
-
-def c_round(x):
-    """C round(): half away from zero."""
-    return int(np.floor(abs(float(x)) + 0.5) * (1 if x >= 0 else -1))
-
-
-def py_grid(F):
-    """Frame::AssignFeaturesToGrid + PosInGrid (src/Frame.cc:294-313, 446-456)."""
-    cells = {}
-    for i in range(F.n):
-        px = c_round(f32(f32(F.xy[i, 0] - f32(F.min_x)) * F.width_inv)); py = c_round(f32(f32(F.xy[i, 1] - f32(F.min_y)) * F.height_inv))
-        if px < 0 or px >= FRAME_GRID_COLS or py < 0 or py >= FRAME_GRID_ROWS:
-            continue
-        cells.setdefault((px, py), []).append(i)
-    return cells
-
-
-def py_features_in_area(F, cells, x, y, r, min_level=-1, max_level=-1):
-    """Frame::GetFeaturesInArea (src/Frame.cc:391-444), all arithmetic in float32."""
-    x, y, r = f32(x), f32(y), f32(r)
-    out = []
-    nMinCellX = max(0, int(np.floor(f32(f32(f32(x - f32(F.min_x)) - r) * F.width_inv))))
-    if nMinCellX >= FRAME_GRID_COLS: return out
-    nMaxCellX = min(FRAME_GRID_COLS - 1, int(np.ceil(f32(f32(f32(x - f32(F.min_x)) + r) * F.width_inv))))
-    if nMaxCellX < 0: return out
-    nMinCellY = max(0, int(np.floor(f32(f32(f32(y - f32(F.min_y)) - r) * F.height_inv))))
-    if nMinCellY >= FRAME_GRID_ROWS: return out
-    nMaxCellY = min(FRAME_GRID_ROWS - 1, int(np.ceil(f32(f32(f32(y - f32(F.min_y)) + r) * F.height_inv))))
-    if nMaxCellY < 0: return out
-    check = (min_level > 0) or (max_level >= 0)
-    for ix in range(nMinCellX, nMaxCellX + 1):
-        for iy in range(nMinCellY, nMaxCellY + 1):
-            for k in cells.get((ix, iy), []):
-                if check:
-                    if F.octave[k] < min_level: continue
-                    if max_level >= 0 and F.octave[k] > max_level: continue
-                if abs(f32(F.xy[k, 0] - x)) < r and abs(f32(F.xy[k, 1] - y)) < r:
-                    out.append(k)
-    return out
-
-
-def py_three_maxima(counts):
-    """ORBmatcher::ComputeThreeMaxima (src/ORBmatcher.cc:1601-1642)."""
-    max1 = max2 = max3 = 0; ind1 = ind2 = ind3 = -1
-    for i, s in enumerate(counts):
-        if s > max1: max3, max2, max1, ind3, ind2, ind1 = max2, max1, s, ind2, ind1, i
-        elif s > max2: max3, max2, ind3, ind2 = max2, s, ind2, i
-        elif s > max3: max3, ind3 = s, i
-    if max2 < f32(0.1) * f32(max1): ind2 = ind3 = -1
-    elif max3 < f32(0.1) * f32(max1): ind3 = -1
-    return [ind1, ind2, ind3]
-
-
-def py_rot_bin(a1, a2):
-    rot = f32(f32(a1) - f32(a2))
-    if rot < 0: rot = f32(rot + f32(360.0))
-    b = c_round(f32(rot * f32(f32(1.0) / f32(30))))
-    return 0 if b == 30 else b
 
 
 # --------------------------------------------------------------------------------------------------------------------
@@ -119,30 +57,6 @@ def test_three_maxima_known_answers():
     for _ in range(200):
         c = rng.integers(0, 40, 30).tolist()
         assert run(c) == py_three_maxima(c)
-
-
-def py_search_map(F, q, th, nn):
-    """ORBmatcher::SearchByProjection(Frame&, vpMapPoints, th) (src/ORBmatcher.cc:45-129), naive."""
-    cells = py_grid(F)
-    slot = np.where(q["occupied"] != 0, 1 << 20, -1).astype(np.int64); slot_obs = q["occupied"].copy()
-    n = 0
-    for i in range(q["desc"].shape[0]):
-        if not q["valid"][i]: continue
-        lvl = int(q["level"][i])
-        r = f32(2.5) if float(q["view_cos"][i]) > 0.998 else f32(4.0)
-        if f32(th) != f32(1.0): r = f32(r * f32(th))
-        rad = f32(r * F.scale[lvl])
-        best = best2 = 256; bl = bl2 = -1; bi = -1
-        for k in py_features_in_area(F, cells, q["uv"][i, 0], q["uv"][i, 1], rad, lvl - 1, lvl):
-            if slot[k] >= 0 and slot_obs[k]: continue
-            if F.uright[k] > 0 and abs(f32(q["ur"][i] - F.uright[k])) > rad: continue
-            d = popcount(q["desc"][i], F.desc[k])
-            if d < best: best2, best, bl2, bl, bi = best, d, bl, int(F.octave[k]), k
-            elif d < best2: bl2, best2 = int(F.octave[k]), d
-        if best <= 100:
-            if bl == bl2 and f32(best) > f32(f32(nn) * f32(best2)): continue
-            slot[bi] = i; slot_obs[bi] = q["obs"][i]; n += 1
-    return n, slot
 
 
 @pytest.mark.parametrize("seed,th", [(0, 1.0), (1, 3.0)])
@@ -359,37 +273,6 @@ def test_compute_stereo_matches_degenerate_inputs():
               angle=np.zeros(0, np.float32))
     n, ur, dep, br, sad = OS.compute_stereo_matches(L, E, sc["left"], sc["right"], sc["inv_scale"], sc["mb"], sc["mbf"])
     assert n == 0 and (ur < 0).all() and (br < 0).all()
-
-
-def py_search_for_initialization(F1, F2, prev, window, nn, check_ori):
-    """ORBmatcher::SearchForInitialization (src/ORBmatcher.cc:405-520) line by line; also counts the matches taken away from a holder."""
-    cells = py_grid(F2)
-    m12 = [-1] * F1.n; m21 = [-1] * F2.n; md = [2 ** 31 - 1] * F2.n
-    hist = [[] for _ in range(30)]; n = 0; steals = 0
-    for i1 in range(F1.n):
-        if F1.octave[i1] > 0: continue
-        cand = py_features_in_area(F2, cells, prev[i1, 0], prev[i1, 1], window, 0, 0)
-        if not cand: continue
-        best = best2 = 2 ** 31 - 1; bi = -1
-        for i2 in cand:
-            d = popcount(F1.desc[i1], F2.desc[i2])
-            if md[i2] <= d: continue
-            if d < best: best2 = best; best = d; bi = i2
-            elif d < best2: best2 = d
-        if best <= 50 and f32(best) < f32(f32(best2) * f32(nn)):
-            if m21[bi] >= 0: m12[m21[bi]] = -1; n -= 1; steals += 1
-            m12[i1] = bi; m21[bi] = i1; md[bi] = best; n += 1
-            if check_ori: hist[py_rot_bin(F1.angle[i1], F2.angle[bi])].append(i1)
-    if check_ori:
-        keep = py_three_maxima([len(h) for h in hist])
-        for b in range(30):
-            if b in keep: continue
-            for i1 in hist[b]:
-                if m12[i1] >= 0: m12[i1] = -1; n -= 1
-    prev = prev.copy()
-    for i1 in range(F1.n):
-        if m12[i1] >= 0: prev[i1] = F2.xy[m12[i1]]
-    return n, np.array(m12, np.int32), prev, steals
 
 
 @pytest.mark.parametrize("pid,window,nn,ori", [(0, 30, 0.9, True), (1, 100, 0.9, True), (2, 60, 0.7, False)])
