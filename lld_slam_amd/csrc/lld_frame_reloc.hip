@@ -286,7 +286,7 @@ extern "C" int lld_frame_relocalize(lld_frame* f, const lld_track_params* P, con
   const size_t o_pose = take(7 * 8), o_lp = take(sizeof(LineTrackDevParams)), o_view = take(sizeof(lld_frame_view));
   const size_t o_bows = take(sizeof(BowSearchDev) * K), o_aps = take(sizeof(ApplyDev) * K), o_cand = take(sizeof(CandDev) * K);
   const size_t o_proj1 = take(sizeof(RelocProjSlot) * K), o_proj2 = take(sizeof(RelocProjSlot) * K);
-  const size_t pstride = orbs_problem_stride();
+  const size_t pstride = orbs_problem_bytes();
   const size_t o_prob = take(pstride * 2 * K);
   struct CandUp { size_t desc, ang, id, pos, obs, node, start, feat, maxd, mind, pdesc; };
   std::vector<CandUp> U(K);

@@ -471,11 +471,11 @@ int lld_frame_track_motion_model(lld_frame* f, const lld_track_params* P, const 
   const int nmax = std::max(std::max(nt, S->nl), 64);
   hipLaunchKernelGGL(track_reset_kernel, dim3((nmax + 255) / 256), dim3(256), 0, st, S->D, reinterpret_cast<const double*>(d + o_pose),
                      reinterpret_cast<const lld_frame_view*>(d + o_view), reinterpret_cast<const LineTrackDevParams*>(d + o_lp));
-  s = orbs_project_last_frame(st, f, view, nullptr, LF, P->direction, P->th_motion, d + o_qrec, RunIf{}); if (s) return s;
-  s = orbs_launch(ctx, st, f, d + o_prob1); if (s) return s;
+  s = orbs_project_last_frame(st, f->consts, view, nullptr, LF, P->direction, P->th_motion, d + o_qrec, nullptr, RunIf{}); if (s) return s;
+  s = orbs_launch_n(ctx, st, f, d + o_prob1, 1); if (s) return s;
   if (wide) {
-    s = orbs_project_last_frame(st, f, view, nullptr, LF, P->direction, 2.f * P->th_motion, d + o_qrec, gate); if (s) return s;
-    s = orbs_launch(ctx, st, f, d + o_prob2); if (s) return s;
+    s = orbs_project_last_frame(st, f->consts, view, nullptr, LF, P->direction, 2.f * P->th_motion, d + o_qrec, nullptr, gate); if (s) return s;
+    s = orbs_launch_n(ctx, st, f, d + o_prob2, 1); if (s) return s;
   }
   s = run_lines(f, st, P, n_map ? last_lines : nullptr, d, U, reinterpret_cast<const uint8_t*>(d + U.skip), d + o_lwork, 0); if (s) return s;
   s = run_pose(f, st, P, d + o_pwork, 0); if (s) return s;
@@ -656,9 +656,9 @@ int lld_frame_track_local_map(lld_frame* f, const lld_track_params* P, const lld
                        reinterpret_cast<const uint8_t*>(d + o_skip), reinterpret_cast<uint8_t*>(d + o_skip2), n_map, reinterpret_cast<const int32_t*>(d + U.id),
                        reinterpret_cast<const uint8_t*>(d + U.skip), reinterpret_cast<uint8_t*>(d + o_lskip2), S->seen_psize - 1, S->seen_lsize - 1);
   S->in_view_off = o_inview; S->n_in_view = nq;
-  s = orbs_project_local_points(st, f, nullptr, S->D.view, MP, P->viewing_cos_limit, P->th_local, d + o_qrec, reinterpret_cast<uint8_t*>(d + o_inview),
-                                S->D.rec_h[1]->i + RI_IN_VIEW); if (s) return s;
-  s = orbs_launch(ctx, st, f, d + o_prob); if (s) return s;
+  s = orbs_project_local_points(st, f->consts, nullptr, S->D.view, MP, P->viewing_cos_limit, P->th_local, d + o_qrec,
+                                FrustumOut{reinterpret_cast<uint8_t*>(d + o_inview), nullptr, nullptr, nullptr, S->D.rec_h[1]->i + RI_IN_VIEW}); if (s) return s;
+  s = orbs_launch_n(ctx, st, f, d + o_prob, 1); if (s) return s;
   s = run_lines(f, st, P, n_map ? local_lines : nullptr, d, U, reinterpret_cast<const uint8_t*>(d + o_lskip2), d + o_lwork, 1); if (s) return s;
   s = run_pose(f, st, P, d + o_pwork, 1); if (s) return s;
   return LLD_OK;

@@ -261,11 +261,6 @@ struct LastFrameArgs {
   QRec* q; float* uvr;
   const lld_frame_view* view_d;
   const int32_t* run_if; int run_if_below, run_if_want;
-  // ... and hands the frame what it matched: CurrentFrame.mvpMapPoints[bestIdx] = pMP (src/ORBmatcher.cc:124, :1427) for every keypoint the search
-  // leaves with an owner, if it accepted at least ap_min_matches (Tracking.cc:907: a first search below 20 is thrown away and repeated wider)
-  uint8_t* ap_has; float* ap_world; int32_t* ap_id; uint8_t* ap_obs;
-  const float* ap_q_pos; const int32_t* ap_q_id; const uint8_t* ap_q_obs;
-  int32_t* ap_counts; int ap_min_matches, ap_is_retry;      // ap_counts: [0] n of the first search, [1] n of the search whose matches were taken, [2] retry used
 };
 
 __device__ __forceinline__ void project_last_one(const LastFrameArgs& F, int i) {
@@ -907,11 +902,115 @@ int validate(const lld_orb_search* s, const lld_orb_search_result* out) {
 
 inline size_t al(size_t b) { return (b + 63) & ~size_t(63); }
 
-// Byte layout of one problem inside the packed input / output regions (identical in pinned host memory and in HBM).
-struct Layout {
-  size_t q, q_desc, t_desc, t_xy, t_oct, t_ur, t_ang, t_occ, cand, in_end;      // offsets from the start of the input region
-  size_t match, bd, sd, owner, sum, rem, out_end;                               // offsets from the start of the output region
+using lld_track::FrustumOut;
+using lld_track::LastFrameDev;
+using lld_track::MapPointsDev;
+using lld_track::SearchOut;
+
+// ---------------------------------------------------------------- the launch of orb_search_kernel
+// The descriptors join the keypoint records in LDS when everything still fits.
+struct LdsPlan { bool desc_in_lds; size_t bytes; };
+LdsPlan lds_plan(int nt, int n_cells, bool bucketed) {
+  const bool desc = lds_bytes(nt, n_cells, bucketed, true) <= kLdsLimit;
+  return {desc, lds_bytes(nt, n_cells, bucketed, desc)};
+}
+
+// One workgroup per problem of problems_d[n]; `lds` is the largest LdsPlan::bytes among them.
+int launch_search(lld_ctx* ctx, hipStream_t st, const void* problems_d, int n, size_t lds) {
+  if (!ctx->orb_lds_raised) { LLD_HIP_TRY(hipFuncSetAttribute((const void*)orb_search_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kLdsLimit)); ctx->orb_lds_raised = true; }
+  hipLaunchKernelGGL(orb_search_kernel, dim3(n), dim3(kThreads), lds, st, static_cast<const Problem*>(problems_d));
+  LLD_HIP_TRY(hipGetLastError());
+  return LLD_OK;
+}
+
+// ---------------------------------------------------------------- the searched frame
+// A level table as the kernels index it: the caller's first n_levels entries, 1 above them and for a table that was not given.
+void copy_levels(float (&dst)[LLD_ORB_MAX_LEVELS], const float* src, int n_levels) {
+  for (int l = 0; l < LLD_ORB_MAX_LEVELS; l++) dst[l] = (src && l < n_levels) ? src[l] : 1.f;
+}
+
+// What the entry points that take a frame by its keypoints (and lld_frame_create, which keeps them) refuse.  host_arrays: the keypoint
+// arrays of `s` are the caller's and get read; false when they are resident on the device and `s` carries only the constants.
+int check_keypoints(const lld_orb_search* s, bool host_arrays, bool need_angle) {
+  const int nt = s->nt;
+  if (nt < 0) return LLD_ERR_INVALID;
+  if (nt > LLD_ORB_MAX_KEYPOINTS) return LLD_ERR_UNSUPPORTED;
+  if (host_arrays && nt > 0 && (!s->t_desc || !s->t_xy || !s->t_octave || (need_angle && !s->t_angle))) return LLD_ERR_INVALID;
+  if (!s->level_scale || s->n_levels <= 0 || s->n_levels > LLD_ORB_MAX_LEVELS) return LLD_ERR_INVALID;
+  if (s->grid_cols <= 0 || s->grid_rows <= 0 || s->grid_cols * s->grid_rows > 8191) return LLD_ERR_INVALID;
+  if (host_arrays) for (int k = 0; k < nt; k++) if (s->t_octave[k] < 0 || s->t_octave[k] >= LLD_ORB_MAX_LEVELS) return LLD_ERR_INVALID;
+  return LLD_OK;
+}
+
+// The keypoint side of a search as DEVICE pointers: into the upload region of the call, or into a resident lld_frame.
+struct KeypointsDev { int nt; const uint32_t* desc; const float* xy; const int32_t* octave; const float* uright; const float* angle; };
+
+KeypointsDev resident_keypoints(const lld_frame* f, bool want_angle) {
+  return {f->nt, reinterpret_cast<const uint32_t*>(f->d + f->o_td), reinterpret_cast<const float*>(f->d + f->o_txy), reinterpret_cast<const int32_t*>(f->d + f->o_toct),
+          f->has_uright ? reinterpret_cast<const float*>(f->d + f->o_tur) : nullptr,
+          (want_angle && f->has_angle) ? reinterpret_cast<const float*>(f->d + f->o_tang) : nullptr};
+}
+
+// Where a caller's keypoint arrays travel in an upload region: desc | xy | octave | uright | angle, the last two only when wanted.
+struct KeypointsUp {
+  size_t desc, xy, octave, uright, angle; bool has_uright, has_angle;
+  void reserve(size_t& off, size_t nt, bool with_uright, bool with_angle) {
+    auto add = [&](size_t b) { const size_t o = off; off += al(b); return o; };
+    has_uright = with_uright; has_angle = with_angle;
+    desc = add(nt * 32); xy = add(nt * 8); octave = add(nt * 4); uright = has_uright ? add(nt * 4) : 0; angle = has_angle ? add(nt * 4) : 0;
+  }
+  void stage(char* h, const lld_orb_search& s) const {
+    const size_t nt = s.nt;
+    if (!nt) return;
+    std::memcpy(h + desc, s.t_desc, nt * 32); std::memcpy(h + xy, s.t_xy, nt * 8); std::memcpy(h + octave, s.t_octave, nt * 4);
+    if (has_uright) std::memcpy(h + uright, s.t_uright, nt * 4);
+    if (has_angle) std::memcpy(h + angle, s.t_angle, nt * 4);
+  }
+  KeypointsDev dev(const char* d, int nt) const {
+    return {nt, reinterpret_cast<const uint32_t*>(d + desc), reinterpret_cast<const float*>(d + xy), reinterpret_cast<const int32_t*>(d + octave),
+            has_uright ? reinterpret_cast<const float*>(d + uright) : nullptr, has_angle ? reinterpret_cast<const float*>(d + angle) : nullptr};
+  }
 };
+
+// Everything of a Problem that describes the searched frame: its keypoints, its cols x rows buckets with the grid constants of `s`, its level tables.
+void set_frame(Problem& P, const KeypointsDev& K, const lld_orb_search& s, int cols, int rows, const float* sigma2, const float* inv_sigma2) {
+  P.nt = K.nt; P.t_desc = K.desc; P.t_xy = K.xy; P.t_octave = K.octave; P.t_uright = K.uright; P.t_angle = K.angle;
+  P.min_x = s.grid_min_x; P.min_y = s.grid_min_y; P.winv = s.grid_width_inv; P.hinv = s.grid_height_inv;
+  P.cols = cols; P.rows = rows; P.n_levels = s.n_levels;
+  copy_levels(P.scale, s.level_scale, s.n_levels); copy_levels(P.sigma2, sigma2, s.n_levels); copy_levels(P.inv_sigma2, inv_sigma2, s.n_levels);
+}
+
+// ---------------------------------------------------------------- the results
+void set_outputs(Problem& P, const SearchOut& o, bool want_owner, void* cache, bool desc_in_lds) {
+  P.match = o.match; P.best_dist = o.best_dist; P.second_dist = o.second_dist; P.removed = o.removed; P.owner = o.owner; P.summary = o.summary;
+  P.want_owner = want_owner; P.cache = static_cast<unsigned long long*>(cache); P.desc_in_lds = desc_in_lds;
+}
+
+// The block match | best_dist | second_dist | owner | summary | removed of one (nq, nt) search, laid out alike in pinned host memory and in HBM.
+struct ResultRegion {
+  size_t nq, nt, match, bd, sd, owner, sum, rem;
+  void reserve(size_t& off, size_t nq_, size_t nt_) {
+    auto add = [&](size_t b) { const size_t o = off; off += al(b); return o; };
+    nq = nq_; nt = nt_;
+    match = add(nq * 4); bd = add(nq * 4); sd = add(nq * 4); owner = add(nt * 4); sum = add(16); rem = add(nq);
+  }
+  SearchOut dev(char* d_out) const {
+    return {reinterpret_cast<int32_t*>(d_out + match), reinterpret_cast<int32_t*>(d_out + bd), reinterpret_cast<int32_t*>(d_out + sd),
+            reinterpret_cast<uint8_t*>(d_out + rem), reinterpret_cast<int32_t*>(d_out + owner), reinterpret_cast<int32_t*>(d_out + sum)};
+  }
+  void fetch(const char* h_out, lld_orb_search_result& o) const {
+    if (nq) {
+      std::memcpy(o.match, h_out + match, nq * 4); std::memcpy(o.best_dist, h_out + bd, nq * 4);
+      std::memcpy(o.second_dist, h_out + sd, nq * 4); std::memcpy(o.removed, h_out + rem, nq);
+    }
+    if (o.owner && nt) std::memcpy(o.owner, h_out + owner, nt * 4);
+    const int32_t* s = reinterpret_cast<const int32_t*>(h_out + sum);
+    o.n_matches = s[0]; o.rounds = s[1];
+  }
+};
+
+// Byte layout of one problem of a batch inside the packed input / output regions.
+struct Layout { size_t q, q_desc, t_occ, cand; KeypointsUp kp; ResultRegion res; };
 
 }  // namespace
 
@@ -924,26 +1023,15 @@ extern "C" int lld_orb_search_batch(lld_ctx* ctx, int n, const lld_orb_search* p
   // ---- lay the batch out: [Problem x n | per-problem inputs ...] and [per-problem outputs ...]
   std::vector<Layout> lay((size_t)n);
   size_t in_off = al(sizeof(Problem) * (size_t)n), out_off = 0, lds_max = 0;
+  auto add_in = [&](size_t b) { const size_t o = in_off; in_off += al(b); return o; };
   for (int i = 0; i < n; i++) {
     const lld_orb_search& s = problems[i]; Layout& L = lay[i];
-    const size_t nt = s.nt, nq = s.nq, nc = (s.candidates == LLD_ORB_CAND_CSR) ? s.n_cand : 0;
-    L.q = in_off; in_off += al(nq * sizeof(QRec));
-    L.q_desc = in_off; in_off += al(nq * 32);
-    L.t_desc = in_off; in_off += al(nt * 32);
-    L.t_xy = in_off; in_off += al(nt * 8);
-    L.t_oct = in_off; in_off += al(nt * 4);
-    L.t_ur = in_off; in_off += s.t_uright ? al(nt * 4) : 0;
-    L.t_ang = in_off; in_off += s.t_angle ? al(nt * 4) : 0;
-    L.t_occ = in_off; in_off += s.t_occupied ? al(nt) : 0;
-    L.cand = in_off; in_off += al(nc * 4);
-    L.in_end = in_off;
-    L.match = out_off; out_off += al(nq * 4);
-    L.bd = out_off; out_off += al(nq * 4);
-    L.sd = out_off; out_off += al(nq * 4);
-    L.owner = out_off; out_off += al(nt * 4);
-    L.sum = out_off; out_off += al(16);
-    L.rem = out_off; out_off += al(nq);
-    L.out_end = out_off;
+    const size_t nt = s.nt, nq = s.nq;
+    L.q = add_in(nq * sizeof(QRec)); L.q_desc = add_in(nq * 32);
+    L.kp.reserve(in_off, nt, s.t_uright != nullptr, s.t_angle != nullptr);
+    L.t_occ = add_in(s.t_occupied ? nt : 0);
+    L.cand = add_in(s.candidates == LLD_ORB_CAND_CSR ? (size_t)s.n_cand * 4 : 0);
+    L.res.reserve(out_off, nq, nt);
   }
   const size_t in_bytes = in_off, out_bytes = out_off;
   // device-only scratch behind the output region: the round-1 candidate cache of the sequential problems
@@ -959,7 +1047,7 @@ extern "C" int lld_orb_search_batch(lld_ctx* ctx, int n, const lld_orb_search* p
   for (int i = 0; i < n; i++) {
     const lld_orb_search& s = problems[i]; const Layout& L = lay[i];
     const int nt = s.nt, nq = s.nq;
-    const bool grid = s.candidates == LLD_ORB_CAND_GRID;
+    const bool grid = s.candidates == LLD_ORB_CAND_GRID, by_rows = s.candidates == LLD_ORB_CAND_ROWS;
     QRec* qr = reinterpret_cast<QRec*>(h + L.q);
     for (int q = 0; q < nq; q++) {
       QRec& Q = qr[q]; std::memset(&Q, 0, sizeof(Q));
@@ -975,67 +1063,33 @@ extern "C" int lld_orb_search_batch(lld_ctx* ctx, int n, const lld_orb_search* p
       if (s.candidates == LLD_ORB_CAND_CSR) { Q.cs = s.cand_range[2 * q]; Q.ce = s.cand_range[2 * q + 1]; }
     }
     if (nq) std::memcpy(h + L.q_desc, s.q_desc, (size_t)nq * 32);
-    if (nt) {
-      std::memcpy(h + L.t_desc, s.t_desc, (size_t)nt * 32);
-      std::memcpy(h + L.t_xy, s.t_xy, (size_t)nt * 8);
-      std::memcpy(h + L.t_oct, s.t_octave, (size_t)nt * 4);
-      if (s.t_uright) std::memcpy(h + L.t_ur, s.t_uright, (size_t)nt * 4);
-      if (s.t_angle) std::memcpy(h + L.t_ang, s.t_angle, (size_t)nt * 4);
-      if (s.t_occupied) std::memcpy(h + L.t_occ, s.t_occupied, (size_t)nt);
-    }
+    L.kp.stage(h, s);
+    if (nt && s.t_occupied) std::memcpy(h + L.t_occ, s.t_occupied, (size_t)nt);
     if (s.candidates == LLD_ORB_CAND_CSR && s.n_cand) std::memcpy(h + L.cand, s.cand_idx, (size_t)s.n_cand * 4);
 
     Problem& P = reinterpret_cast<Problem*>(h)[i]; std::memset(&P, 0, sizeof(P));
-    P.nt = nt; P.nq = nq;
-    P.t_desc = reinterpret_cast<const uint32_t*>(d + L.t_desc); P.t_xy = reinterpret_cast<const float*>(d + L.t_xy);
-    P.t_octave = reinterpret_cast<const int32_t*>(d + L.t_oct);
-    P.t_uright = s.t_uright ? reinterpret_cast<const float*>(d + L.t_ur) : nullptr;
-    P.t_angle = s.t_angle ? reinterpret_cast<const float*>(d + L.t_ang) : nullptr;
+    P.nq = nq;
+    // the buckets of the counting sort: the caller's grid, or one per (octave, image row), or a single one
+    const int n_lv = std::max(1, s.n_levels);
+    const int cols = grid ? s.grid_cols : (by_rows ? n_lv : 1), rows = grid ? s.grid_rows : (by_rows ? std::min(kRowBuckets, 8190 / n_lv) : 1);
+    set_frame(P, L.kp.dev(d, nt), s, cols, rows, s.level_sigma2, s.level_inv_sigma2);
     P.t_occupied = s.t_occupied ? reinterpret_cast<const uint8_t*>(d + L.t_occ) : nullptr;
     P.q_desc = reinterpret_cast<const uint32_t*>(d + L.q_desc); P.q = reinterpret_cast<const QRec*>(d + L.q);
     P.cand_idx = reinterpret_cast<const int32_t*>(d + L.cand);
-    P.min_x = s.grid_min_x; P.min_y = s.grid_min_y; P.winv = s.grid_width_inv; P.hinv = s.grid_height_inv;
-    const int n_lv = std::max(1, s.n_levels);
-    P.cols = grid ? s.grid_cols : (s.candidates == LLD_ORB_CAND_ROWS ? n_lv : 1);
-    P.rows = grid ? s.grid_rows : (s.candidates == LLD_ORB_CAND_ROWS ? std::min(kRowBuckets, 8190 / n_lv) : 1);
-    P.n_levels = s.n_levels;
-    for (int l = 0; l < LLD_ORB_MAX_LEVELS; l++) {
-      P.scale[l] = (s.level_scale && l < s.n_levels) ? s.level_scale[l] : 1.f;
-      P.sigma2[l] = (s.level_sigma2 && l < s.n_levels) ? s.level_sigma2[l] : 1.f;
-      P.inv_sigma2[l] = (s.level_inv_sigma2 && l < s.n_levels) ? s.level_inv_sigma2[l] : 1.f;
-    }
     P.disp_min = s.disp_min; P.disp_max = s.disp_max; P.epi_x = s.epipole_x; P.epi_y = s.epipole_y; P.only_stereo = s.only_stereo; P.image_rows = s.image_rows;
     P.candidates = s.candidates; P.gates = s.gates; P.tie_last = s.tie_last; P.accept_max = s.accept_max; P.ratio_mode = s.ratio_mode;
     P.nnratio = s.nnratio; P.sequential = s.sequential; P.check_orientation = s.check_orientation;
-    P.match = reinterpret_cast<int32_t*>(d_out + L.match); P.best_dist = reinterpret_cast<int32_t*>(d_out + L.bd);
-    P.second_dist = reinterpret_cast<int32_t*>(d_out + L.sd); P.removed = reinterpret_cast<uint8_t*>(d_out + L.rem);
-    P.owner = reinterpret_cast<int32_t*>(d_out + L.owner); P.summary = reinterpret_cast<int32_t*>(d_out + L.sum);
-    P.want_owner = outs[i].owner != nullptr;
-    P.cache = reinterpret_cast<unsigned long long*>(d_cache + cache_at[i]);
-    const bool bucketed = grid || s.candidates == LLD_ORB_CAND_ROWS;
-    P.desc_in_lds = lds_bytes(nt, P.cols * P.rows, bucketed, true) <= kLdsLimit;
-    lds_max = std::max(lds_max, lds_bytes(nt, P.cols * P.rows, bucketed, P.desc_in_lds != 0));
+    const LdsPlan lds = lds_plan(nt, cols * rows, grid || by_rows);
+    set_outputs(P, L.res.dev(d_out), outs[i].owner != nullptr, d_cache + cache_at[i], lds.desc_in_lds);
+    lds_max = std::max(lds_max, lds.bytes);
   }
 
   hipStream_t sm = ctx->stream;
   LLD_HIP_TRY(hipMemcpyAsync(d, h, in_bytes, hipMemcpyHostToDevice, sm));
-  if (!ctx->orb_lds_raised) { LLD_HIP_TRY(hipFuncSetAttribute((const void*)orb_search_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kLdsLimit)); ctx->orb_lds_raised = true; }
-  hipLaunchKernelGGL(orb_search_kernel, dim3(n), dim3(kThreads), lds_max, sm, reinterpret_cast<const Problem*>(d));
-  LLD_HIP_TRY(hipGetLastError());
+  st = launch_search(ctx, sm, d, n, lds_max); if (st) return st;
   LLD_HIP_TRY(hipMemcpyAsync(h_out, d_out, out_bytes, hipMemcpyDeviceToHost, sm));
   LLD_HIP_TRY(hipStreamSynchronize(sm));
-
-  for (int i = 0; i < n; i++) {
-    const Layout& L = lay[i]; lld_orb_search_result& o = outs[i];
-    const size_t nt = problems[i].nt, nq = problems[i].nq;
-    if (nq) {
-      std::memcpy(o.match, h_out + L.match, nq * 4); std::memcpy(o.best_dist, h_out + L.bd, nq * 4);
-      std::memcpy(o.second_dist, h_out + L.sd, nq * 4); std::memcpy(o.removed, h_out + L.rem, nq);
-    }
-    if (o.owner && nt) std::memcpy(o.owner, h_out + L.owner, nt * 4);
-    const int32_t* sum = reinterpret_cast<const int32_t*>(h_out + L.sum);
-    o.n_matches = sum[0]; o.rounds = sum[1];
-  }
+  for (int i = 0; i < n; i++) lay[i].res.fetch(h_out, outs[i]);
   return LLD_OK;
 }
 
@@ -1045,45 +1099,30 @@ extern "C" int lld_orb_search_run(lld_ctx* ctx, const lld_orb_search* s, lld_orb
 
 namespace {
 
-}  // namespace
-
-// (struct lld_frame: lld_track_internal.h)
-
-namespace {
-
 // Shared plumbing of the "project on the device, then search" entry points: one packed input region
 // [Problem | QRec[nq] (written by the projection kernel) | q_desc | frame keypoints | caller inputs] and one output region.
 struct ProjSearch {
   lld_ctx* ctx; const lld_orb_search* frame; int nt, nq; bool need_angle;
   const lld_frame* resident = nullptr;     // the keypoint side is already on the device (lld_frame_*): only t_occupied travels
-  size_t in = 0, out = 0;
-  size_t o_q = 0, o_qd = 0, o_td = 0, o_txy = 0, o_toct = 0, o_tur = 0, o_tang = 0, o_tocc = 0;
-  size_t r_match = 0, r_bd = 0, r_sd = 0, r_owner = 0, r_sum = 0, r_rem = 0;
+  size_t in = 0, out = 0, o_q = 0, o_qd = 0, o_tocc = 0;
+  KeypointsUp kp{}; ResultRegion res{}; LdsPlan lds{};
   char *h = nullptr, *d = nullptr, *h_out = nullptr, *d_out = nullptr;
   size_t add_in(size_t bytes) { const size_t o = in; in += al(bytes); return o; }
   size_t add_out(size_t bytes) { const size_t o = out; out += al(bytes); return o; }
 
-  int check(const lld_orb_search_result* res) const {
-    if (nt < 0 || nq < 0) return LLD_ERR_INVALID;
-    if (nt > LLD_ORB_MAX_KEYPOINTS) return LLD_ERR_UNSUPPORTED;
-    if (!res->match || !res->best_dist || !res->second_dist || !res->removed) return LLD_ERR_INVALID;
-    if (resident) { if (need_angle && nt > 0 && !resident->has_angle) return LLD_ERR_INVALID; }
-    else if (nt > 0 && (!frame->t_desc || !frame->t_xy || !frame->t_octave || (need_angle && !frame->t_angle))) return LLD_ERR_INVALID;
-    if (!frame->level_scale || frame->n_levels <= 0 || frame->n_levels > LLD_ORB_MAX_LEVELS) return LLD_ERR_INVALID;
-    if (frame->grid_cols <= 0 || frame->grid_rows <= 0 || frame->grid_cols * frame->grid_rows > 8191) return LLD_ERR_INVALID;
-    if (!resident) for (int k = 0; k < nt; k++) if (frame->t_octave[k] < 0 || frame->t_octave[k] >= LLD_ORB_MAX_LEVELS) return LLD_ERR_INVALID;
+  int check(const lld_orb_search_result* r) const {
+    if (nq < 0) return LLD_ERR_INVALID;
+    const int st = check_keypoints(frame, !resident, need_angle); if (st) return st;
+    if (!r->match || !r->best_dist || !r->second_dist || !r->removed) return LLD_ERR_INVALID;
+    if (resident && need_angle && nt > 0 && !resident->has_angle) return LLD_ERR_INVALID;
     return LLD_OK;
   }
   void layout() {
     in = al(sizeof(Problem));
     o_q = add_in((size_t)nq * sizeof(QRec)); o_qd = add_in((size_t)nq * 32);
-    if (!resident) {
-      o_td = add_in((size_t)nt * 32); o_txy = add_in((size_t)nt * 8); o_toct = add_in((size_t)nt * 4);
-      o_tur = frame->t_uright ? add_in((size_t)nt * 4) : 0; o_tang = need_angle ? add_in((size_t)nt * 4) : 0;
-    }
+    if (!resident) kp.reserve(in, (size_t)nt, frame->t_uright != nullptr, need_angle);
     o_tocc = frame->t_occupied ? add_in((size_t)nt) : 0;
-    r_match = add_out((size_t)nq * 4); r_bd = add_out((size_t)nq * 4); r_sd = add_out((size_t)nq * 4); r_owner = add_out((size_t)nt * 4);
-    r_sum = add_out(16); r_rem = add_out((size_t)nq);
+    res.reserve(out, (size_t)nq, (size_t)nt);
   }
   int alloc() {
     void* hb; int st = lld_ctx_pinned(ctx, in + out, &hb); if (st) return st;
@@ -1094,57 +1133,50 @@ struct ProjSearch {
   // frame keypoints + query descriptors into the staging buffer, Problem with everything but the matching rules
   Problem& pack(const uint32_t* q_desc, bool want_owner) {
     if (nq) std::memcpy(h + o_qd, q_desc, (size_t)nq * 32);
-    if (nt && !resident) {
-      std::memcpy(h + o_td, frame->t_desc, (size_t)nt * 32); std::memcpy(h + o_txy, frame->t_xy, (size_t)nt * 8);
-      std::memcpy(h + o_toct, frame->t_octave, (size_t)nt * 4);
-      if (frame->t_uright) std::memcpy(h + o_tur, frame->t_uright, (size_t)nt * 4);
-      if (need_angle) std::memcpy(h + o_tang, frame->t_angle, (size_t)nt * 4);
-    }
+    if (!resident) kp.stage(h, *frame);
     if (nt && frame->t_occupied) std::memcpy(h + o_tocc, frame->t_occupied, (size_t)nt);
     Problem& P = *reinterpret_cast<Problem*>(h); std::memset(&P, 0, sizeof(P));
-    P.nt = nt; P.nq = nq;
-    if (resident) {
-      P.t_desc = reinterpret_cast<const uint32_t*>(resident->d + resident->o_td); P.t_xy = reinterpret_cast<const float*>(resident->d + resident->o_txy);
-      P.t_octave = reinterpret_cast<const int32_t*>(resident->d + resident->o_toct);
-      P.t_uright = resident->has_uright ? reinterpret_cast<const float*>(resident->d + resident->o_tur) : nullptr;
-      P.t_angle = (need_angle && resident->has_angle) ? reinterpret_cast<const float*>(resident->d + resident->o_tang) : nullptr;
-    } else {
-      P.t_desc = reinterpret_cast<const uint32_t*>(d + o_td); P.t_xy = reinterpret_cast<const float*>(d + o_txy);
-      P.t_octave = reinterpret_cast<const int32_t*>(d + o_toct);
-      P.t_uright = frame->t_uright ? reinterpret_cast<const float*>(d + o_tur) : nullptr;
-      P.t_angle = need_angle ? reinterpret_cast<const float*>(d + o_tang) : nullptr;
-    }
+    P.nq = nq;
+    set_frame(P, resident ? resident_keypoints(resident, need_angle) : kp.dev(d, nt), *frame, frame->grid_cols, frame->grid_rows, nullptr, nullptr);
     P.t_occupied = frame->t_occupied ? reinterpret_cast<const uint8_t*>(d + o_tocc) : nullptr;
     P.q_desc = reinterpret_cast<const uint32_t*>(d + o_qd); P.q = reinterpret_cast<const QRec*>(d + o_q);
-    P.min_x = frame->grid_min_x; P.min_y = frame->grid_min_y; P.winv = frame->grid_width_inv; P.hinv = frame->grid_height_inv;
-    P.cols = frame->grid_cols; P.rows = frame->grid_rows; P.n_levels = frame->n_levels;
-    for (int l = 0; l < LLD_ORB_MAX_LEVELS; l++) { P.scale[l] = l < frame->n_levels ? frame->level_scale[l] : 1.f; P.sigma2[l] = 1.f; P.inv_sigma2[l] = 1.f; }
     P.candidates = LLD_ORB_CAND_GRID;
-    P.match = reinterpret_cast<int32_t*>(d_out + r_match); P.best_dist = reinterpret_cast<int32_t*>(d_out + r_bd);
-    P.second_dist = reinterpret_cast<int32_t*>(d_out + r_sd); P.removed = reinterpret_cast<uint8_t*>(d_out + r_rem);
-    P.owner = reinterpret_cast<int32_t*>(d_out + r_owner); P.summary = reinterpret_cast<int32_t*>(d_out + r_sum);
-    P.want_owner = want_owner;
-    P.cache = reinterpret_cast<unsigned long long*>(d_out + out);
-    P.desc_in_lds = lds_bytes(nt, P.cols * P.rows, true, true) <= kLdsLimit;
+    lds = lds_plan(nt, P.cols * P.rows, true);
+    set_outputs(P, res.dev(d_out), want_owner, d_out + out, lds.desc_in_lds);
     return P;
   }
   int upload() { LLD_HIP_TRY(hipMemcpyAsync(d, h, in, hipMemcpyHostToDevice, ctx->stream)); return LLD_OK; }
-  int search_and_fetch(lld_orb_search_result* res) {
-    const Problem& P = *reinterpret_cast<const Problem*>(h);
-    const size_t lds = lds_bytes(nt, P.cols * P.rows, true, P.desc_in_lds != 0);
-    if (!ctx->orb_lds_raised) { LLD_HIP_TRY(hipFuncSetAttribute((const void*)orb_search_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kLdsLimit)); ctx->orb_lds_raised = true; }
-    hipLaunchKernelGGL(orb_search_kernel, dim3(1), dim3(kThreads), lds, ctx->stream, reinterpret_cast<const Problem*>(d));
-    LLD_HIP_TRY(hipGetLastError());
+  int search_and_fetch(lld_orb_search_result* r) {
+    const int st = launch_search(ctx, ctx->stream, d, 1, lds.bytes); if (st) return st;
     LLD_HIP_TRY(hipMemcpyAsync(h_out, d_out, out, hipMemcpyDeviceToHost, ctx->stream));
     LLD_HIP_TRY(hipStreamSynchronize(ctx->stream));
-    if (nq) {
-      std::memcpy(res->match, h_out + r_match, (size_t)nq * 4); std::memcpy(res->best_dist, h_out + r_bd, (size_t)nq * 4);
-      std::memcpy(res->second_dist, h_out + r_sd, (size_t)nq * 4); std::memcpy(res->removed, h_out + r_rem, (size_t)nq);
-    }
-    if (res->owner && nt) std::memcpy(res->owner, h_out + r_owner, (size_t)nt * 4);
-    const int32_t* sum = reinterpret_cast<const int32_t*>(h_out + r_sum);
-    res->n_matches = sum[0]; res->rounds = sum[1];
+    res.fetch(h_out, *r);
     return LLD_OK;
+  }
+};
+
+// A caller's lld_map_points in the upload region of a ProjSearch: pos | normal | max_distance | min_distance | has_obs | skip.  The normals
+// and has_obs travel only for a routine that reads them, skip whenever the caller gave it.
+struct MapPointsUp {
+  size_t pos, nrm, maxd, mind, obs, skip; bool has_nrm, has_obs, has_skip;
+  void reserve(ProjSearch& S, const lld_map_points* mp, bool with_normal, bool with_obs) {
+    const size_t n = S.nq;
+    has_nrm = with_normal; has_obs = with_obs && mp->has_obs; has_skip = mp->skip != nullptr;
+    pos = S.add_in(n * 12); nrm = has_nrm ? S.add_in(n * 12) : 0; maxd = S.add_in(n * 4); mind = S.add_in(n * 4);
+    obs = has_obs ? S.add_in(n) : 0; skip = has_skip ? S.add_in(n) : 0;
+  }
+  MapPointsDev stage(const ProjSearch& S, const lld_map_points* mp) const {
+    const size_t n = S.nq;
+    if (n) {
+      std::memcpy(S.h + pos, mp->world_pos, n * 12);
+      if (has_nrm) std::memcpy(S.h + nrm, mp->normal, n * 12);
+      std::memcpy(S.h + maxd, mp->max_distance, n * 4); std::memcpy(S.h + mind, mp->min_distance, n * 4);
+      if (has_obs) std::memcpy(S.h + obs, mp->has_obs, n);
+      if (has_skip) std::memcpy(S.h + skip, mp->skip, n);
+    }
+    return {S.nq, reinterpret_cast<const float*>(S.d + pos), has_nrm ? reinterpret_cast<const float*>(S.d + nrm) : nullptr,
+            reinterpret_cast<const float*>(S.d + maxd), reinterpret_cast<const float*>(S.d + mind),
+            has_obs ? reinterpret_cast<const uint8_t*>(S.d + obs) : nullptr, has_skip ? reinterpret_cast<const uint8_t*>(S.d + skip) : nullptr};
   }
 };
 
@@ -1161,35 +1193,18 @@ static int local_points_impl(lld_ctx* ctx, const lld_orb_search* frame, const ll
   out->n_matches = 0; out->rounds = 0;
   LLD_HIP_TRY(hipSetDevice(ctx->device));
   S.layout();
-  const size_t o_pos = S.add_in((size_t)nq * 12), o_nrm = S.add_in((size_t)nq * 12), o_maxd = S.add_in((size_t)nq * 4), o_mind = S.add_in((size_t)nq * 4);
-  const size_t o_obs = mp->has_obs ? S.add_in((size_t)nq) : 0, o_skip = mp->skip ? S.add_in((size_t)nq) : 0;
+  MapPointsUp U; U.reserve(S, mp, true, true);
   const size_t r_inv = S.add_out((size_t)nq), r_uvr = S.add_out((size_t)nq * 12), r_lvl = S.add_out((size_t)nq * 4), r_vc = S.add_out((size_t)nq * 4);
   st = S.alloc(); if (st) return st;
-  if (nq) {
-    std::memcpy(S.h + o_pos, mp->world_pos, (size_t)nq * 12); std::memcpy(S.h + o_nrm, mp->normal, (size_t)nq * 12);
-    std::memcpy(S.h + o_maxd, mp->max_distance, (size_t)nq * 4); std::memcpy(S.h + o_mind, mp->min_distance, (size_t)nq * 4);
-    if (mp->has_obs) std::memcpy(S.h + o_obs, mp->has_obs, (size_t)nq);
-    if (mp->skip) std::memcpy(S.h + o_skip, mp->skip, (size_t)nq);
-  }
+  const MapPointsDev M = U.stage(S, mp);
   Problem& P = S.pack(mp->desc, out->owner != nullptr);
   P.gates = LLD_ORB_GATE_LEVEL | LLD_ORB_GATE_STEREO; P.accept_max = 100;       // TH_HIGH, src/ORBmatcher.cc:37,117
   P.ratio_mode = 2; P.nnratio = nnratio; P.sequential = 1;
   st = S.upload(); if (st) return st;
-  if (nq) {
-    FrustumArgs F; std::memset(&F, 0, sizeof(F));
-    F.V = *view; F.n = nq;
-    F.pos = reinterpret_cast<const float*>(S.d + o_pos); F.nrm = reinterpret_cast<const float*>(S.d + o_nrm);
-    F.maxd = reinterpret_cast<const float*>(S.d + o_maxd); F.mind = reinterpret_cast<const float*>(S.d + o_mind);
-    F.has_obs = mp->has_obs ? reinterpret_cast<const uint8_t*>(S.d + o_obs) : nullptr;
-    F.skip = mp->skip ? reinterpret_cast<const uint8_t*>(S.d + o_skip) : nullptr;
-    for (int l = 0; l < LLD_ORB_MAX_LEVELS; l++) F.scale[l] = P.scale[l];
-    F.cos_limit = viewing_cos_limit; F.th = th;
-    F.q = reinterpret_cast<QRec*>(S.d + S.o_q);
-    F.in_view = reinterpret_cast<uint8_t*>(S.d_out + r_inv); F.uvr = reinterpret_cast<float*>(S.d_out + r_uvr);
-    F.level = reinterpret_cast<int32_t*>(S.d_out + r_lvl); F.view_cos = reinterpret_cast<float*>(S.d_out + r_vc);
-    hipLaunchKernelGGL(frustum_kernel, dim3((nq + 255) / 256), dim3(256), 0, ctx->stream, F);
-    LLD_HIP_TRY(hipGetLastError());
-  }
+  st = lld_track::orbs_project_local_points(ctx->stream, *frame, view, nullptr, M, viewing_cos_limit, th, S.d + S.o_q,
+                                            FrustumOut{reinterpret_cast<uint8_t*>(S.d_out + r_inv), reinterpret_cast<float*>(S.d_out + r_uvr),
+                                                       reinterpret_cast<int32_t*>(S.d_out + r_lvl), reinterpret_cast<float*>(S.d_out + r_vc), nullptr});
+  if (st) return st;
   st = S.search_and_fetch(out); if (st) return st;
   if (nq && fr) {
     if (fr->in_view) std::memcpy(fr->in_view, S.h_out + r_inv, (size_t)nq);
@@ -1212,6 +1227,7 @@ static int last_frame_impl(lld_ctx* ctx, const lld_orb_search* frame, const lld_
   int st = S.check(out); if (st) return st;
   const int nq = S.nq;
   if (nq > 0 && (!last->world_pos || !last->valid || !last->octave || !last->desc || (check_orientation && !last->angle))) return LLD_ERR_INVALID;
+  if (view->n_levels != frame->n_levels) return LLD_ERR_INVALID;                // (as the other projecting searches and lld_frame_track_motion_model)
   for (int i = 0; i < nq; i++) if (last->octave[i] < 0 || last->octave[i] >= frame->n_levels) return LLD_ERR_INVALID;
   out->n_matches = 0; out->rounds = 0;
   LLD_HIP_TRY(hipSetDevice(ctx->device));
@@ -1226,23 +1242,14 @@ static int last_frame_impl(lld_ctx* ctx, const lld_orb_search* frame, const lld_
     if (last->angle) std::memcpy(S.h + o_ang, last->angle, (size_t)nq * 4);
     if (last->has_obs) std::memcpy(S.h + o_obs, last->has_obs, (size_t)nq);
   }
+  const LastFrameDev L{nq, reinterpret_cast<const float*>(S.d + o_pos), reinterpret_cast<const uint8_t*>(S.d + o_val), reinterpret_cast<const int32_t*>(S.d + o_oct),
+                       last->angle ? reinterpret_cast<const float*>(S.d + o_ang) : nullptr, last->has_obs ? reinterpret_cast<const uint8_t*>(S.d + o_obs) : nullptr};
   Problem& P = S.pack(last->desc, out->owner != nullptr);
   P.gates = LLD_ORB_GATE_LEVEL | LLD_ORB_GATE_STEREO; P.accept_max = 100;       // TH_HIGH, src/ORBmatcher.cc:1418
   P.ratio_mode = 0; P.sequential = 1; P.check_orientation = check_orientation != 0;
   st = S.upload(); if (st) return st;
-  if (nq) {
-    LastFrameArgs F; std::memset(&F, 0, sizeof(F));
-    F.V = *view; F.n = nq; F.direction = direction;
-    F.pos = reinterpret_cast<const float*>(S.d + o_pos); F.valid = reinterpret_cast<const uint8_t*>(S.d + o_val);
-    F.octave = reinterpret_cast<const int32_t*>(S.d + o_oct);
-    F.angle = last->angle ? reinterpret_cast<const float*>(S.d + o_ang) : nullptr;
-    F.has_obs = last->has_obs ? reinterpret_cast<const uint8_t*>(S.d + o_obs) : nullptr;
-    for (int l = 0; l < LLD_ORB_MAX_LEVELS; l++) F.scale[l] = P.scale[l];
-    F.th = th;
-    F.q = reinterpret_cast<QRec*>(S.d + S.o_q); F.uvr = reinterpret_cast<float*>(S.d_out + r_uvr);
-    hipLaunchKernelGGL(project_last_frame_kernel, dim3((nq + 255) / 256), dim3(256), 0, ctx->stream, F);
-    LLD_HIP_TRY(hipGetLastError());
-  }
+  st = lld_track::orbs_project_last_frame(ctx->stream, *frame, view, nullptr, L, direction, th, S.d + S.o_q, reinterpret_cast<float*>(S.d_out + r_uvr), lld_track::RunIf{});
+  if (st) return st;
   st = S.search_and_fetch(out); if (st) return st;
   if (nq && proj_uvr) std::memcpy(proj_uvr, S.h_out + r_uvr, (size_t)nq * 12);
   return LLD_OK;
@@ -1257,39 +1264,25 @@ extern "C" int lld_orb_search_last_frame(lld_ctx* ctx, const lld_orb_search* fra
 extern "C" int lld_frame_create(lld_ctx* ctx, const lld_orb_search* kp, lld_frame** out) {
   if (!ctx || !kp || !out) return LLD_ERR_INVALID;
   *out = nullptr;
+  int st = check_keypoints(kp, true, false); if (st) return st;
   const int nt = kp->nt;
-  if (nt < 0) return LLD_ERR_INVALID;
-  if (nt > LLD_ORB_MAX_KEYPOINTS) return LLD_ERR_UNSUPPORTED;
-  if (nt > 0 && (!kp->t_desc || !kp->t_xy || !kp->t_octave)) return LLD_ERR_INVALID;
-  if (!kp->level_scale || kp->n_levels <= 0 || kp->n_levels > LLD_ORB_MAX_LEVELS) return LLD_ERR_INVALID;
-  if (kp->grid_cols <= 0 || kp->grid_rows <= 0 || kp->grid_cols * kp->grid_rows > 8191) return LLD_ERR_INVALID;
-  for (int k = 0; k < nt; k++) if (kp->t_octave[k] < 0 || kp->t_octave[k] >= LLD_ORB_MAX_LEVELS) return LLD_ERR_INVALID;
   LLD_HIP_TRY(hipSetDevice(ctx->device));
   lld_frame* f = new lld_frame();
   f->ctx = ctx; f->nt = nt; f->has_uright = kp->t_uright != nullptr; f->has_angle = kp->t_angle != nullptr; f->has_inv_sigma2 = kp->level_inv_sigma2 != nullptr;
   f->consts = *kp;
   f->consts.t_desc = nullptr; f->consts.t_xy = nullptr; f->consts.t_octave = nullptr; f->consts.t_uright = nullptr; f->consts.t_angle = nullptr; f->consts.t_occupied = nullptr;
   f->consts.nq = 0; f->consts.q_desc = nullptr;
-  for (int l = 0; l < LLD_ORB_MAX_LEVELS; l++) {
-    f->scale[l] = l < kp->n_levels ? kp->level_scale[l] : 1.f;
-    f->sigma2[l] = (l < kp->n_levels && kp->level_sigma2) ? kp->level_sigma2[l] : 1.f;
-    f->inv_sigma2[l] = (l < kp->n_levels && kp->level_inv_sigma2) ? kp->level_inv_sigma2[l] : 1.f;
-  }
+  copy_levels(f->scale, kp->level_scale, kp->n_levels); copy_levels(f->sigma2, kp->level_sigma2, kp->n_levels); copy_levels(f->inv_sigma2, kp->level_inv_sigma2, kp->n_levels);
   f->consts.level_scale = f->scale; f->consts.level_sigma2 = f->sigma2; f->consts.level_inv_sigma2 = f->inv_sigma2;
   size_t bytes = 0;
-  auto add = [&](size_t b) { const size_t o = bytes; bytes += al(b); return o; };
-  f->o_td = add((size_t)nt * 32); f->o_txy = add((size_t)nt * 8); f->o_toct = add((size_t)nt * 4);
-  f->o_tur = f->has_uright ? add((size_t)nt * 4) : 0; f->o_tang = f->has_angle ? add((size_t)nt * 4) : 0;
+  KeypointsUp U; U.reserve(bytes, (size_t)nt, f->has_uright, f->has_angle);
+  f->o_td = U.desc; f->o_txy = U.xy; f->o_toct = U.octave; f->o_tur = U.uright; f->o_tang = U.angle;
   if (hipMalloc(reinterpret_cast<void**>(&f->d), bytes + 256) != hipSuccess) { delete f; return LLD_ERR_ALLOC; }
   void* hb = nullptr;
-  int st = lld_ctx_pinned(ctx, bytes + 256, &hb);
+  st = lld_ctx_pinned(ctx, bytes + 256, &hb);
   if (st) { (void)hipFree(f->d); delete f; return st; }
   char* h = static_cast<char*>(hb);
-  if (nt) {
-    std::memcpy(h + f->o_td, kp->t_desc, (size_t)nt * 32); std::memcpy(h + f->o_txy, kp->t_xy, (size_t)nt * 8); std::memcpy(h + f->o_toct, kp->t_octave, (size_t)nt * 4);
-    if (f->has_uright) std::memcpy(h + f->o_tur, kp->t_uright, (size_t)nt * 4);
-    if (f->has_angle) std::memcpy(h + f->o_tang, kp->t_angle, (size_t)nt * 4);
-  }
+  U.stage(h, *kp);
   // (the context's pinned staging is reused by the next call on this context: the copy must have left it before this one returns)
   if (hipMemcpyAsync(f->d, h, bytes, hipMemcpyHostToDevice, ctx->stream) != hipSuccess || hipStreamSynchronize(ctx->stream) != hipSuccess) { (void)hipFree(f->d); delete f; return LLD_ERR_HIP; }
   *out = f;
@@ -1332,26 +1325,19 @@ extern "C" int lld_orb_fuse_search(lld_ctx* ctx, const lld_orb_search* keyframe,
   out->n_matches = 0; out->rounds = 0;
   LLD_HIP_TRY(hipSetDevice(ctx->device));
   S.layout();
-  const size_t o_pos = S.add_in((size_t)nq * 12), o_nrm = S.add_in((size_t)nq * 12), o_maxd = S.add_in((size_t)nq * 4), o_mind = S.add_in((size_t)nq * 4);
-  const size_t o_skip = mp->skip ? S.add_in((size_t)nq) : 0;
+  MapPointsUp U; U.reserve(S, mp, true, false);
   const size_t r_uvr = S.add_out((size_t)nq * 12);
   st = S.alloc(); if (st) return st;
-  if (nq) {
-    std::memcpy(S.h + o_pos, mp->world_pos, (size_t)nq * 12); std::memcpy(S.h + o_nrm, mp->normal, (size_t)nq * 12);
-    std::memcpy(S.h + o_maxd, mp->max_distance, (size_t)nq * 4); std::memcpy(S.h + o_mind, mp->min_distance, (size_t)nq * 4);
-    if (mp->skip) std::memcpy(S.h + o_skip, mp->skip, (size_t)nq);
-  }
+  const MapPointsDev M = U.stage(S, mp);
   Problem& P = S.pack(mp->desc, out->owner != nullptr);
-  for (int l = 0; l < keyframe->n_levels; l++) P.inv_sigma2[l] = keyframe->level_inv_sigma2[l];
+  copy_levels(P.inv_sigma2, keyframe->level_inv_sigma2, keyframe->n_levels);
   P.gates = LLD_ORB_GATE_LEVEL | LLD_ORB_GATE_CHI2; P.accept_max = 50;          // TH_LOW, src/ORBmatcher.cc:38,934
   st = S.upload(); if (st) return st;
   if (nq) {
     FuseArgs F; std::memset(&F, 0, sizeof(F));
     F.V = *view; F.n = nq;
-    F.pos = reinterpret_cast<const float*>(S.d + o_pos); F.nrm = reinterpret_cast<const float*>(S.d + o_nrm);
-    F.maxd = reinterpret_cast<const float*>(S.d + o_maxd); F.mind = reinterpret_cast<const float*>(S.d + o_mind);
-    F.skip = mp->skip ? reinterpret_cast<const uint8_t*>(S.d + o_skip) : nullptr;
-    for (int l = 0; l < LLD_ORB_MAX_LEVELS; l++) F.scale[l] = P.scale[l];
+    F.pos = M.pos; F.nrm = M.normal; F.maxd = M.maxd; F.mind = M.mind; F.skip = M.skip;
+    copy_levels(F.scale, keyframe->level_scale, keyframe->n_levels);
     F.th = th;
     F.q = reinterpret_cast<QRec*>(S.d + S.o_q); F.uvr = reinterpret_cast<float*>(S.d_out + r_uvr);
     hipLaunchKernelGGL(project_fuse_kernel, dim3((nq + 255) / 256), dim3(256), 0, ctx->stream, F);
@@ -1377,17 +1363,12 @@ extern "C" int lld_orb_search_projected(lld_ctx* ctx, const lld_orb_search* fram
   out->n_matches = 0; out->rounds = 0;
   LLD_HIP_TRY(hipSetDevice(ctx->device));
   S.layout();
-  const size_t o_pos = S.add_in((size_t)nq * 12), o_nrm = need_normal ? S.add_in((size_t)nq * 12) : 0, o_maxd = S.add_in((size_t)nq * 4), o_mind = S.add_in((size_t)nq * 4);
-  const size_t o_skip = mp->skip ? S.add_in((size_t)nq) : 0, o_ang = angle ? S.add_in((size_t)nq * 4) : 0;
+  MapPointsUp U; U.reserve(S, mp, need_normal, false);
+  const size_t o_ang = angle ? S.add_in((size_t)nq * 4) : 0;
   const size_t r_uv = S.add_out((size_t)nq * 8), r_lvl = S.add_out((size_t)nq * 4);
   st = S.alloc(); if (st) return st;
-  if (nq) {
-    std::memcpy(S.h + o_pos, mp->world_pos, (size_t)nq * 12);
-    if (need_normal) std::memcpy(S.h + o_nrm, mp->normal, (size_t)nq * 12);
-    std::memcpy(S.h + o_maxd, mp->max_distance, (size_t)nq * 4); std::memcpy(S.h + o_mind, mp->min_distance, (size_t)nq * 4);
-    if (mp->skip) std::memcpy(S.h + o_skip, mp->skip, (size_t)nq);
-    if (angle) std::memcpy(S.h + o_ang, angle, (size_t)nq * 4);
-  }
+  const MapPointsDev M = U.stage(S, mp);
+  if (nq && angle) std::memcpy(S.h + o_ang, angle, (size_t)nq * 4);
   Problem& P = S.pack(mp->desc, out->owner != nullptr);
   P.gates = LLD_ORB_GATE_LEVEL;
   switch (routine) {
@@ -1402,11 +1383,9 @@ extern "C" int lld_orb_search_projected(lld_ctx* ctx, const lld_orb_search* fram
     F.V = *view; F.n = nq; F.routine = routine;
     for (int k = 0; k < 9; k++) F.sR[k] = proj->sR[k];
     for (int k = 0; k < 3; k++) F.t2[k] = proj->t[k];
-    F.pos = reinterpret_cast<const float*>(S.d + o_pos); F.nrm = need_normal ? reinterpret_cast<const float*>(S.d + o_nrm) : nullptr;
-    F.maxd = reinterpret_cast<const float*>(S.d + o_maxd); F.mind = reinterpret_cast<const float*>(S.d + o_mind);
-    F.skip = mp->skip ? reinterpret_cast<const uint8_t*>(S.d + o_skip) : nullptr;
+    F.pos = M.pos; F.nrm = M.normal; F.maxd = M.maxd; F.mind = M.mind; F.skip = M.skip;
     F.angle = angle ? reinterpret_cast<const float*>(S.d + o_ang) : nullptr;
-    for (int l = 0; l < LLD_ORB_MAX_LEVELS; l++) F.scale[l] = P.scale[l];
+    copy_levels(F.scale, frame->level_scale, frame->n_levels);
     F.th = proj->th;
     F.q = reinterpret_cast<QRec*>(S.d + S.o_q); F.uv = reinterpret_cast<float*>(S.d_out + r_uv); F.level = reinterpret_cast<int32_t*>(S.d_out + r_lvl);
     hipLaunchKernelGGL(project_general_kernel, dim3((nq + 255) / 256), dim3(256), 0, ctx->stream, F);
@@ -1459,70 +1438,61 @@ extern "C" int lld_orb_search_by_sim3(lld_ctx* ctx, const lld_orb_search* kf1, c
 // ================================================================ launchers for the device-resident Tracking chain (lld_track_internal.h)
 namespace lld_track {
 
-size_t orbs_problem_bytes() { return al(sizeof(Problem)); }
+size_t orbs_problem_bytes() { return sizeof(Problem); }
 size_t orbs_qrec_bytes(int nq) { return al((size_t)nq * sizeof(QRec)); }
 size_t orbs_cache_bytes(int nq) { return al((size_t)nq * 8 * kTopK); }
 void orbs_fill_problem(const lld_frame* f, int mode, int nq, const uint8_t* d_occupied, const void* d_qrec, const uint32_t* d_qdesc, const SearchOut& out,
                        void* d_cache, float nnratio, int check_orientation, RunIf run_if, const ApplyDev& ap, void* problem_h) {
   Problem& P = *static_cast<Problem*>(problem_h); std::memset(&P, 0, sizeof(P));
   const lld_orb_search& c = f->consts;
-  P.nt = f->nt; P.nq = nq;
-  P.t_desc = reinterpret_cast<const uint32_t*>(f->d + f->o_td); P.t_xy = reinterpret_cast<const float*>(f->d + f->o_txy);
-  P.t_octave = reinterpret_cast<const int32_t*>(f->d + f->o_toct);
-  P.t_uright = f->has_uright ? reinterpret_cast<const float*>(f->d + f->o_tur) : nullptr;
-  P.t_angle = (check_orientation && f->has_angle) ? reinterpret_cast<const float*>(f->d + f->o_tang) : nullptr;
+  P.nq = nq;
+  set_frame(P, resident_keypoints(f, check_orientation != 0), c, c.grid_cols, c.grid_rows, nullptr, nullptr);
   P.t_occupied = d_occupied;
   P.q_desc = d_qdesc; P.q = static_cast<const QRec*>(d_qrec);
-  P.min_x = c.grid_min_x; P.min_y = c.grid_min_y; P.winv = c.grid_width_inv; P.hinv = c.grid_height_inv;
-  P.cols = c.grid_cols; P.rows = c.grid_rows; P.n_levels = c.n_levels;
-  for (int l = 0; l < LLD_ORB_MAX_LEVELS; l++) { P.scale[l] = l < c.n_levels ? f->scale[l] : 1.f; P.sigma2[l] = 1.f; P.inv_sigma2[l] = 1.f; }
   P.candidates = LLD_ORB_CAND_GRID;
   P.gates = LLD_ORB_GATE_LEVEL | LLD_ORB_GATE_STEREO; P.accept_max = 100;       // TH_HIGH (src/ORBmatcher.cc:117, :1418)
   if (mode == 0) { P.ratio_mode = 0; P.check_orientation = check_orientation != 0; }
   else { P.ratio_mode = 2; P.nnratio = nnratio; }
   P.sequential = 1;
-  P.match = out.match; P.best_dist = out.best_dist; P.second_dist = out.second_dist; P.removed = out.removed; P.owner = out.owner; P.summary = out.summary;
-  P.want_owner = 1;
-  P.cache = static_cast<unsigned long long*>(d_cache);
-  P.desc_in_lds = lds_bytes(P.nt, P.cols * P.rows, true, true) <= kLdsLimit;
+  set_outputs(P, out, true, d_cache, lds_plan(f->nt, c.grid_cols * c.grid_rows, true).desc_in_lds);
   P.run_if = run_if.flag; P.run_if_below = run_if.below; P.run_if_want = run_if.want;
   P.t_occ_obs = ap.kp_obs;                                                      // (the frame's own flags: only a MapPoint with observations blocks its keypoint)
   P.ap_has = ap.kp_has; P.ap_world = ap.kp_world; P.ap_id = ap.kp_id; P.ap_obs = ap.kp_obs; P.ap_q_pos = ap.q_pos; P.ap_q_id = ap.q_id; P.ap_q_obs = ap.q_obs;
   P.ap_counts = ap.counts; P.ap_min_matches = ap.min_matches; P.ap_is_retry = ap.is_retry;
 }
 
-// (Round 6 also tried the projection loops as a prologue of the search kernel: one launch less, but 2500 frustum tests on ONE compute unit take
-// 38 us where ten workgroups of frustum_kernel take 11 - the chain got 30 us slower.  The projections keep their own launches.)
-int orbs_project_last_frame(hipStream_t st, const lld_frame* f, const lld_frame_view* view_h, const lld_frame_view* view_d, const LastFrameDev& last, int direction, float th,
-                            void* d_qrec, RunIf run_if) {
+// (The projections keep launches of their own: as a prologue of the search kernel, 2500 frustum tests on ONE compute unit take 38 us where ten
+// workgroups of frustum_kernel take 11.)
+int orbs_project_last_frame(hipStream_t st, const lld_orb_search& c, const lld_frame_view* view_h, const lld_frame_view* view_d, const LastFrameDev& last, int direction, float th,
+                            void* d_qrec, float* d_uvr, RunIf run_if) {
   if (last.n <= 0) return LLD_OK;
   LastFrameArgs F; std::memset(&F, 0, sizeof(F));
   if (view_h) F.V = *view_h;
   F.view_d = view_d; F.n = last.n; F.direction = direction;
   F.pos = last.pos; F.valid = last.valid; F.octave = last.octave; F.angle = last.angle; F.has_obs = last.has_obs;
-  for (int l = 0; l < LLD_ORB_MAX_LEVELS; l++) F.scale[l] = l < f->consts.n_levels ? f->scale[l] : 1.f;
-  F.th = th; F.q = static_cast<QRec*>(d_qrec); F.uvr = nullptr;
+  copy_levels(F.scale, c.level_scale, c.n_levels);
+  F.th = th; F.q = static_cast<QRec*>(d_qrec); F.uvr = d_uvr;
   F.run_if = run_if.flag; F.run_if_below = run_if.below; F.run_if_want = run_if.want;
   hipLaunchKernelGGL(project_last_frame_kernel, dim3((last.n + 255) / 256), dim3(256), 0, st, F);
   LLD_HIP_TRY(hipGetLastError());
   return LLD_OK;
 }
 
-int orbs_project_local_points(hipStream_t st, const lld_frame* f, const lld_frame_view* view_h, const lld_frame_view* view_d, const MapPointsDev& mp, float cos_limit, float th,
-                              void* d_qrec, uint8_t* d_in_view, int32_t* d_n_in_view) {
+int orbs_project_local_points(hipStream_t st, const lld_orb_search& c, const lld_frame_view* view_h, const lld_frame_view* view_d, const MapPointsDev& mp, float cos_limit, float th,
+                              void* d_qrec, const FrustumOut& out) {
   if (mp.n <= 0) return LLD_OK;
   FrustumArgs F; std::memset(&F, 0, sizeof(F));
   if (view_h) F.V = *view_h;
   F.view_d = view_d; F.n = mp.n;
   F.pos = mp.pos; F.nrm = mp.normal; F.maxd = mp.maxd; F.mind = mp.mind; F.has_obs = mp.has_obs; F.skip = mp.skip;
-  for (int l = 0; l < LLD_ORB_MAX_LEVELS; l++) F.scale[l] = l < f->consts.n_levels ? f->scale[l] : 1.f;
-  F.cos_limit = cos_limit; F.th = th; F.q = static_cast<QRec*>(d_qrec); F.in_view = d_in_view; F.n_in_view = d_n_in_view;
+  copy_levels(F.scale, c.level_scale, c.n_levels);
+  F.cos_limit = cos_limit; F.th = th; F.q = static_cast<QRec*>(d_qrec);
+  F.in_view = out.in_view; F.uvr = out.uvr; F.level = out.level; F.view_cos = out.view_cos; F.n_in_view = out.n_in_view;
   hipLaunchKernelGGL(frustum_kernel, dim3((mp.n + 255) / 256), dim3(256), 0, st, F);
   LLD_HIP_TRY(hipGetLastError());
   return LLD_OK;
 }
 
-size_t orbs_problem_stride() { return sizeof(Problem); }
 void orbs_fill_problem_reloc(const lld_frame* f, int nq, const uint8_t* d_occupied, const void* d_qrec, const uint32_t* d_qdesc, const SearchOut& out, void* d_cache,
                              int accept_max, RunIf run_if, const ApplyDev& ap, void* problem_h) {
   orbs_fill_problem(f, 0, nq, d_occupied, d_qrec, d_qdesc, out, d_cache, 0.f, 1, run_if, ap, problem_h);
@@ -1535,7 +1505,7 @@ int orbs_project_reloc_slots(hipStream_t st, const lld_frame* f, int n_slots, in
   if (n_slots <= 0 || n_max <= 0) return LLD_OK;
   ProjRelocSlotsArgs A; std::memset(&A, 0, sizeof(A));
   A.slots = slots_d; A.th = th;
-  for (int l = 0; l < LLD_ORB_MAX_LEVELS; l++) A.scale[l] = l < f->consts.n_levels ? f->scale[l] : 1.f;
+  copy_levels(A.scale, f->consts.level_scale, f->consts.n_levels);
   hipLaunchKernelGGL(project_reloc_slots_kernel, dim3((n_max + 255) / 256, n_slots), dim3(256), 0, st, A);
   LLD_HIP_TRY(hipGetLastError());
   return LLD_OK;
@@ -1543,23 +1513,7 @@ int orbs_project_reloc_slots(hipStream_t st, const lld_frame* f, int n_slots, in
 
 int orbs_launch_n(lld_ctx* ctx, hipStream_t st, const lld_frame* f, const void* problems_d, int n) {
   if (n <= 0) return LLD_OK;
-  const lld_orb_search& c = f->consts;
-  const bool desc_in_lds = lds_bytes(f->nt, c.grid_cols * c.grid_rows, true, true) <= kLdsLimit;
-  const size_t lds = lds_bytes(f->nt, c.grid_cols * c.grid_rows, true, desc_in_lds);
-  if (!ctx->orb_lds_raised) { LLD_HIP_TRY(hipFuncSetAttribute((const void*)orb_search_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kLdsLimit)); ctx->orb_lds_raised = true; }
-  hipLaunchKernelGGL(orb_search_kernel, dim3(n), dim3(kThreads), lds, st, static_cast<const Problem*>(problems_d));
-  LLD_HIP_TRY(hipGetLastError());
-  return LLD_OK;
-}
-
-int orbs_launch(lld_ctx* ctx, hipStream_t st, const lld_frame* f, const void* problem_d) {
-  const lld_orb_search& c = f->consts;
-  const bool desc_in_lds = lds_bytes(f->nt, c.grid_cols * c.grid_rows, true, true) <= kLdsLimit;
-  const size_t lds = lds_bytes(f->nt, c.grid_cols * c.grid_rows, true, desc_in_lds);
-  if (!ctx->orb_lds_raised) { LLD_HIP_TRY(hipFuncSetAttribute((const void*)orb_search_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kLdsLimit)); ctx->orb_lds_raised = true; }
-  hipLaunchKernelGGL(orb_search_kernel, dim3(1), dim3(kThreads), lds, st, static_cast<const Problem*>(problem_d));
-  LLD_HIP_TRY(hipGetLastError());
-  return LLD_OK;
+  return launch_search(ctx, st, problems_d, n, lds_plan(f->nt, f->consts.grid_cols * f->consts.grid_rows, true).bytes);
 }
 
 }  // namespace lld_track

@@ -47,6 +47,8 @@ void state_free(lld_frame* f);             // lld_frame_destroy calls it before 
 // matched (mvpMapPoints[bestIdx] = pMP as an epilogue).  Everything the kernels read or write is a device pointer; the problem is filled on the
 // host into pinned memory the caller uploads before the launch.  run_if: when non-null the kernels return at once unless
 // (*flag < below) == (want != 0) - the reference's "if(nmatches<20) search again with 2*th" (src/Tracking.cc:907-911) without a host decision.
+// sizeof the search kernel's problem record.  It is also the stride of the arrays of problems the kernel indexes (orbs_launch_n), so it
+// is not rounded up: a caller that places a lone problem in a work buffer aligns the offset like every other region of that buffer.
 size_t orbs_problem_bytes();
 size_t orbs_qrec_bytes(int nq);
 size_t orbs_cache_bytes(int nq);
@@ -60,11 +62,14 @@ struct MapPointsDev { int n; const float* pos; const float* normal; const float*
 // mode 0: SearchByProjection(Current, Last) rules (TH_HIGH, no ratio, rotation histogram optional); mode 1: SearchByProjection(F, MapPoints) rules
 void orbs_fill_problem(const lld_frame* f, int mode, int nq, const uint8_t* d_occupied, const void* d_qrec, const uint32_t* d_qdesc, const SearchOut& out,
                        void* d_cache, float nnratio, int check_orientation, RunIf run_if, const ApplyDev& ap, void* problem_h);
-int orbs_project_last_frame(hipStream_t st, const lld_frame* f, const lld_frame_view* view_h, const lld_frame_view* view_d, const LastFrameDev& last, int direction, float th,
-                            void* d_qrec, RunIf run_if);
-int orbs_project_local_points(hipStream_t st, const lld_frame* f, const lld_frame_view* view_h, const lld_frame_view* view_d, const MapPointsDev& mp, float cos_limit, float th,
-                              void* d_qrec, uint8_t* d_in_view, int32_t* d_n_in_view);
-int orbs_launch(lld_ctx* ctx, hipStream_t st, const lld_frame* f, const void* problem_d);
+// The projection loops, shared with the single-call entry points.  c: the searched frame's level_scale / n_levels; the view is read from
+// view_d (device memory) when that is non-null, else passed by value from view_h.  d_uvr and every member of FrustumOut are optional
+// device outputs: in_view[n] u8, uvr[n][3], level[n], view_cos[n]; *n_in_view += the number of points inside the frustum.
+struct FrustumOut { uint8_t* in_view; float* uvr; int32_t* level; float* view_cos; int32_t* n_in_view; };
+int orbs_project_last_frame(hipStream_t st, const lld_orb_search& c, const lld_frame_view* view_h, const lld_frame_view* view_d, const LastFrameDev& last, int direction, float th,
+                            void* d_qrec, float* d_uvr, RunIf run_if);
+int orbs_project_local_points(hipStream_t st, const lld_orb_search& c, const lld_frame_view* view_h, const lld_frame_view* view_d, const MapPointsDev& mp, float cos_limit, float th,
+                              void* d_qrec, const FrustumOut& out);
 // ORBmatcher::SearchByProjection(Frame&, KeyFrame*, sAlreadyFound, th, ORBdist) (src/ORBmatcher.cc:1472-1599, LLD_ORB_PROJ_RELOC) on n_slots copies
 // of the frame's mvpMapPoints at once, each against its own keyframe: slot s projects its candidate's MapPoints through ITS view (device
 // memory) and searches with ITS occupancy.  A slot runs iff *run != 0 (projection) / its Problem's run_if holds (search).
@@ -74,8 +79,7 @@ int orbs_project_reloc_slots(hipStream_t st, const lld_frame* f, int n_slots, in
 // orbs_fill_problem for that search: occupancy = any MapPoint on the keypoint (:1528), bestDist <= accept_max, the rotation histogram, no ratio test
 void orbs_fill_problem_reloc(const lld_frame* f, int nq, const uint8_t* d_occupied, const void* d_qrec, const uint32_t* d_qdesc, const SearchOut& out, void* d_cache,
                              int accept_max, RunIf run_if, const ApplyDev& ap, void* problem_h);
-size_t orbs_problem_stride();                                              // of an array of problems (orbs_launch_n)
-int orbs_launch_n(lld_ctx* ctx, hipStream_t st, const lld_frame* f, const void* problems_d, int n);   // one workgroup per problem
+int orbs_launch_n(lld_ctx* ctx, hipStream_t st, const lld_frame* f, const void* problems_d, int n);   // problems_d[n], one workgroup per problem
 
 // ---------------------------------------------------------------- ORBmatcher::SearchByBoW(KeyFrame*, Frame&) on device arrays (lld_frame_track_bow.hip)
 // The frame's FeatureVector is the one in lld_frame::d_bow (its node count is read on the device), the keyframe's an uploaded CSR.  One
