@@ -1164,7 +1164,8 @@ int  lld_orb_extractor_descriptors(const lld_orb_extractor* ex, int image_index,
  *   stage 2, 3  the SAD refinement and the median cut of lld_compute_stereo_matches (same kernels), writing mvuRight / mvDepth into
  *            the frame's own arrays.
  * Scope: RECTIFIED stereo only - mvKeysUn = mvKeys, the `mDistCoef.at<float>(0)==0.0` branch of Frame::UndistortKeyPoints
- * (:468-474); a caller with a distorted camera undistorts on the host and uses lld_frame_create.  Lines are added with
+ * (:468-474); the distorted branch, for the RGB-D and the monocular Frame, is lld_frame_build_mono* below (the reference rectifies a
+ * stereo pair before it reaches the Frame).  Lines are added with
  * lld_frame_set_lines as before (the reference's line extractor is external and host-side).
  * Both build calls queue their kernels on the context's stream and return WITHOUT synchronising; every later call on the frame is
  * ordered after them by that stream, and lld_frame_stereo_download is the one that waits.
@@ -1205,6 +1206,93 @@ int  lld_frame_build_stereo(lld_orb_extractor* ex, int left_image, int right_ima
  * needs them for Frame::UnprojectStereo and for keyframe creation).  out->u_right and out->depth must hold the frame's nt entries.
  * LLD_ERR_INVALID on a frame made by lld_frame_create. */
 int  lld_frame_stereo_download(lld_frame* frame, lld_stereo_result* out);
+
+
+/* ------------------------------------------------------------------ the RGB-D and the monocular Frame, built on the device
+ * The other two constructors of the reference: Frame::Frame(imGray, imDepth, ...) (src/Frame.cc:163-215) runs, after ExtractORB (:180),
+ * UndistortKeyPoints (:187, :468-498) and ComputeStereoFromRGBD (:189, :707-728); Frame::Frame(imGray, ...) (:220-292) runs
+ * UndistortKeyPoints (:248) and sets mvuRight = mvDepth = -1 (:255-256).  These calls do that on the device, in ONE launch with a lane
+ * per keypoint (no atomics, no LDS), and hand back a resident lld_frame as lld_frame_build_stereo* does: its keypoints are mvKeysUn, it
+ * carries mvuRight, angles and mvInvLevelSigma2, and lld_frame_search_*, lld_frame_compute_bow, lld_frame_set_lines and every
+ * lld_frame_track_* call work on it unchanged (th_motion = 15 and th_local = 3 are the reference's thresholds for these sensors,
+ * Tracking.cc:901, :1657).  The calls queue on the context's stream and return WITHOUT synchronising;
+ * lld_frame_keypoints_download is the one that waits.
+ *   undistortion  mvKeysUn[i].pt.  dist[0] == 0.0f: the distorted point, bit for bit, whatever the other coefficients hold (the
+ *            reference's test, :470).  Otherwise the RESTATED cv::undistortPoints(mat, mat, mK, mDistCoef, cv::Mat(), mK) (:486) -
+ *            OpenCV 3's cvUndistortPoints with R = I and P = K - in double, every operation rounded separately (no fused multiply-add):
+ *              fx, fy, cx, cy, k1 = dist[0], k2 = dist[1], p1 = dist[2], p2 = dist[3], k3 = dist[4] (0 when n_dist = 4) widened to double
+ *              ifx = 1.0/fx; ify = 1.0/fy;  x0 = x = ((double)u - cx)*ifx;  y0 = y = ((double)v - cy)*ify
+ *              5 times:  r2 = x*x + y*y;  icdist = 1.0/(1.0 + ((k3*r2 + k2)*r2 + k1)*r2)
+ *                        dx = ((2.0*p1)*x)*y + p2*(r2 + (2.0*x)*x);  dy = p1*(r2 + (2.0*y)*y) + ((2.0*p2)*x)*y
+ *                        x = (x0 - dx)*icdist;  y = (y0 - dy)*icdist
+ *              u_un = (float)(fx*x + cx);  v_un = (float)(fy*y + cy)
+ *            The five iterations are fixed, not run to convergence (up to 0.11 px is left at the corners of the TUM1 camera); that is
+ *            the reference's behaviour.  Parity with OpenCV's own binary is unpinned, as everywhere in this project; every value is
+ *            bit-exact against the numpy restatement tests/frame_mono_ref.py.  An undistorted keypoint may leave the grid; the searches
+ *            drop such a keypoint as Frame::PosInGrid does (:446-456).
+ *   depth    ComputeStereoFromRGBD: d = imDepth.at<float>(v, u) at the DISTORTED keypoint, row = (int)v, col = (int)u (truncation
+ *            toward zero).  The reference indexes unchecked; here a keypoint whose u or v is not finite or lies outside (-1, cols) x
+ *            (-1, rows) (compared in float, before the conversion) has no depth, so that no read leaves the image.  The depth image is
+ *            the one GrabImageRGBD receives (Tracking.cc:252-253, imDepth.convertTo(imDepth, CV_32F, mDepthMapFactor)) and only the
+ *            sampled pixels are converted: LLD_DEPTH_U16 gives d = (float)raw * factor, always; LLD_DEPTH_F32 gives d = raw * factor
+ *            when fabsf(factor - 1.0f) > 1e-5f and the raw value otherwise (one float multiply).  d > 0: mvDepth = d and
+ *            mvuRight = u_un - mbf/d (a float division, then a float subtraction); +inf passes (depth inf, mvuRight = u_un); zero,
+ *            negative and NaN leave both at -1.  factor is mDepthMapFactor as Tracking holds it, i.e. 1/DepthMapFactor of the
+ *            settings file (Tracking.cc:155-159).
+ *   no depth image (NULL): the monocular frame, mvuRight = mvDepth = -1 for every keypoint.
+ * Refusals, before anything is allocated or queued: LLD_ERR_INVALID for null pointers, fx or fy not > 0, cx or cy not finite, n_dist
+ * outside {4, 5}, a non-finite coefficient or mbf, a grid outside lld_frame_create's limits, n_levels outside [1, LLD_ORB_MAX_LEVELS], a host
+ * octave outside [0, n_levels), a depth image with cols or rows outside [1, 16383], a step below the row's bytes or not a multiple of
+ * the element size, an unknown type or a non-finite factor, an extractor without a successful lld_orb_extract, an image index outside
+ * that call's n_images; LLD_ERR_UNSUPPORTED above LLD_ORB_MAX_KEYPOINTS.  No keypoints give an empty frame and LLD_OK (:184-185). */
+#define LLD_DEPTH_F32 0        /* CV_32F  */
+#define LLD_DEPTH_U16 1        /* CV_16U  */
+typedef struct {
+  float grid_min_x, grid_min_y, grid_width_inv, grid_height_inv;   /* mnMinX, mnMinY, mfGridElementWidthInv, mfGridElementHeightInv:
+                                                                      from lld_frame_image_bounds (Frame.cc:197-200)                */
+  int32_t grid_cols, grid_rows;                                    /* 64, 48 (Frame.h:43-44); as lld_orb_search                       */
+  float fx, fy, cx, cy;                                            /* mK                                                              */
+  float dist[5];                                                   /* mDistCoef: k1, k2, p1, p2, k3; dist[4] is ignored when n_dist = 4 */
+  int32_t n_dist;                                                  /* 4 or 5 (mDistCoef.rows, Tracking.cc:85-87)                      */
+  float mbf;                                                       /* mvuRight = u_un - mbf / depth                                   */
+  int32_t keypoints_on_device;  /* lld_frame_build_mono_keypoints: 1 = kp->xy, kp->desc and left_angle are HBM pointers, read in place.
+                                   kp->octave stays a HOST array (the frame's host copy of the octaves, and the one array uploaded)    */
+  int32_t n_levels;             /* mnScaleLevels                                                                                       */
+  int32_t reserved;
+  const float* left_angle;      /* [kp->n] mvKeysUn[k].angle; required by lld_frame_build_mono_keypoints (host or device like the
+                                   keypoints); lld_frame_build_mono reads the extractor's own                                          */
+  const float* level_scale;       /* [n_levels] mvScaleFactors                                                                       */
+  const float* level_sigma2;      /* [n_levels] mvLevelSigma2, or NULL (all 1)                                                       */
+  const float* level_inv_sigma2;  /* [n_levels] mvInvLevelSigma2                                                                     */
+} lld_frame_mono_params;
+typedef struct {
+  const void* data;             /* imDepth.data as the caller holds it BEFORE convertTo: float or uint16_t pixels                      */
+  int32_t cols, rows;
+  int32_t step;                 /* bytes per image row (cv::Mat::step)                                                                 */
+  int32_t type;                 /* LLD_DEPTH_F32 or LLD_DEPTH_U16                                                                      */
+  float   factor;               /* mDepthMapFactor                                                                                     */
+  int32_t on_device;            /* 1: data is an HBM pointer, read in place; it must stay valid until the queued work has run          */
+} lld_depth_image;
+/* The general form.  kp: mvKeys with mDescriptors, on the host or (keypoints_on_device) in HBM; depth_or_null: the depth image on the
+ * host or (on_device) in HBM, or NULL for a monocular frame.  Everything that starts on the host, the depth image included (rows
+ * packed), travels in ONE copy from a pinned buffer the frame owns. */
+int  lld_frame_build_mono_keypoints(lld_ctx* ctx, const lld_keypoints* kp, const lld_depth_image* depth_or_null,
+                                    const lld_frame_mono_params* params, lld_frame** out);
+/* The same build on image `image` of the handle's last lld_orb_extract, on the extractor's context: keypoints, angles, descriptors and
+ * level tables are read where the extractor left them (params->n_levels, level_*, left_angle and keypoints_on_device are ignored);
+ * only a host depth image is uploaded.  The frame copies what it keeps into its own allocation inside the kernel, so it survives the
+ * next lld_orb_extract on the handle and the handle's destruction. */
+int  lld_frame_build_mono(lld_orb_extractor* ex, int image, const lld_depth_image* depth_or_null, const lld_frame_mono_params* params,
+                          lld_frame** out);
+/* Waits for the frame's queued work and fetches mvKeysUn[i].pt (xy_un [nt][2]), mvuRight and mvDepth ([nt] each) in one copy; any of
+ * the three may be NULL.  The host needs them for Frame::UnprojectStereo, the Initializer and keyframe creation.  LLD_ERR_INVALID on a
+ * frame made by lld_frame_create or lld_frame_build_stereo* (and lld_frame_stereo_download stays LLD_ERR_INVALID on a frame made here). */
+int  lld_frame_keypoints_download(lld_frame* frame, float* xy_un, float* u_right, float* depth);
+/* Frame::ComputeImageBounds (Frame.cc:500-528), host only: bounds = mnMinX, mnMaxX, mnMinY, mnMaxY.  dist[0] == 0.0f gives 0, cols, 0,
+ * rows; otherwise the undistortion above of the corners (0,0), (cols,0), (0,rows), (cols,rows) and the reference's min / max of them.
+ * LLD_ERR_INVALID as the build calls refuse the camera, or cols / rows not > 0. */
+int  lld_frame_image_bounds(int32_t cols, int32_t rows, float fx, float fy, float cx, float cy, const float* dist, int32_t n_dist,
+                            float bounds[4]);
 
 
 /* ------------------------------------------------------------------ DBoW2 vocabulary: load, transform, L1 score

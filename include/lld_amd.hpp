@@ -471,6 +471,12 @@ class TrackedFrame {
     check(lld_frame_stereo_download(f_, &r), "lld_frame_stereo_download");
     return r.n_matches;
   }
+  // mvKeysUn[i].pt ([N][2]), mvuRight and mvDepth of a frame MonoFrame built (Frame::UnprojectStereo, the Initializer and keyframe creation
+  // read them on the host); waits for the build
+  void DownloadKeypoints(std::vector<float>& mvKeysUn_xy, std::vector<float>& mvuRight, std::vector<float>& mvDepth) {
+    mvKeysUn_xy.assign((size_t)nt_ * 2, 0.f); mvuRight.assign(nt_, -1.f); mvDepth.assign(nt_, -1.f);
+    check(lld_frame_keypoints_download(f_, mvKeysUn_xy.data(), mvuRight.data(), mvDepth.data()), "lld_frame_keypoints_download");
+  }
  private:
   lld_frame* f_ = nullptr;
   int nt_, nl_;
@@ -540,6 +546,33 @@ inline std::unique_ptr<TrackedFrame> StereoFrame(ORBextractor& ex, int left_imag
   lld_frame* f = nullptr;
   check(lld_frame_build_stereo(ex.get(), left_image, right_image, &p, &f), "lld_frame_build_stereo");
   return std::unique_ptr<TrackedFrame>(new TrackedFrame(f, n_left, lines));
+}
+
+// Frame::ComputeImageBounds (src/Frame.cc:500-528) on the library's restated cv::undistortPoints: bounds = mnMinX, mnMaxX, mnMinY, mnMaxY.
+// K: fx, fy, cx, cy; dist: mDistCoef with n_dist = 4 or 5 entries.  Host only.
+inline void ImageBounds(int cols, int rows, const float K[4], const float* dist, int n_dist, float bounds[4]) {
+  check(lld_frame_image_bounds(cols, rows, K[0], K[1], K[2], K[3], dist, n_dist, bounds), "lld_frame_image_bounds");
+}
+
+// Frame::Frame(imGray, imDepth, ...) (src/Frame.cc:163-215) and Frame::Frame(imGray, ...) (:220-292) after `ex` extracted the image (`image` of
+// its last call, n keypoints, cols x rows pixels): UndistortKeyPoints and ComputeStereoFromRGBD on the device, nothing through the host
+// (lld_frame_build_mono).  depth: imDepth as GrabImageRGBD receives it with factor = mDepthMapFactor, or NULL for a monocular frame.  The grid
+// follows :197-200 on ImageBounds.  Returns the frame of the Tracking chain (set params.th_motion = 15, params.th_local = 3 for RGB-D and
+// params.monocular for a monocular frame, as Tracking does); the build is queued, not waited for.
+inline std::unique_ptr<TrackedFrame> MonoFrame(ORBextractor& ex, int image, int n, int cols, int rows, const float K[4], const float* dist, int n_dist,
+                                               float mbf, const lld_depth_image* depth, const lld_frame_lines* lines) {
+  float b[4];
+  ImageBounds(cols, rows, K, dist, n_dist, b);
+  lld_frame_mono_params p{};
+  p.grid_min_x = b[0]; p.grid_min_y = b[2];
+  p.grid_cols = 64; p.grid_rows = 48;                                   // FRAME_GRID_COLS, FRAME_GRID_ROWS
+  p.grid_width_inv = (float)p.grid_cols / (b[1] - b[0]); p.grid_height_inv = (float)p.grid_rows / (b[3] - b[2]);
+  p.fx = K[0]; p.fy = K[1]; p.cx = K[2]; p.cy = K[3];
+  for (int i = 0; i < 5; i++) p.dist[i] = (dist && i < n_dist) ? dist[i] : 0.f;
+  p.n_dist = n_dist; p.mbf = mbf;
+  lld_frame* f = nullptr;
+  check(lld_frame_build_mono(ex.get(), image, depth, &p, &f), "lld_frame_build_mono");
+  return std::unique_ptr<TrackedFrame>(new TrackedFrame(f, n, lines));
 }
 
 // Mirror of ORBVocabulary = DBoW2::TemplatedVocabulary<FORB::TDescriptor, FORB> (Thirdparty/DBoW2/DBoW2/TemplatedVocabulary.h):

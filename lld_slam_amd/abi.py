@@ -300,6 +300,24 @@ class FrameStereoParams(C.Structure):
                 ("level_scale", c_float_p), ("level_sigma2", c_float_p), ("level_inv_sigma2", c_float_p)]
 
 
+class FrameMonoParams(C.Structure):
+    """lld_frame_mono_params (include/lld_amd.h): the constants of an RGB-D or monocular Frame built on the device."""
+    _fields_ = [("grid_min_x", C.c_float), ("grid_min_y", C.c_float), ("grid_width_inv", C.c_float), ("grid_height_inv", C.c_float),
+                ("grid_cols", C.c_int32), ("grid_rows", C.c_int32), ("fx", C.c_float), ("fy", C.c_float), ("cx", C.c_float), ("cy", C.c_float),
+                ("dist", C.c_float * 5), ("n_dist", C.c_int32), ("mbf", C.c_float), ("keypoints_on_device", C.c_int32), ("n_levels", C.c_int32),
+                ("reserved", C.c_int32), ("left_angle", c_float_p), ("level_scale", c_float_p), ("level_sigma2", c_float_p),
+                ("level_inv_sigma2", c_float_p)]
+
+
+class DepthImage(C.Structure):
+    """lld_depth_image (include/lld_amd.h): imDepth as GrabImageRGBD receives it, before convertTo."""
+    _fields_ = [("data", C.c_void_p), ("cols", C.c_int32), ("rows", C.c_int32), ("step", C.c_int32), ("type", C.c_int32), ("factor", C.c_float),
+                ("on_device", C.c_int32)]
+
+
+DEPTH_F32, DEPTH_U16 = 0, 1
+
+
 class RefKeyFrame(C.Structure):
     """lld_ref_keyframe (include/lld_amd.h): mpReferenceKF as lld_frame_track_reference_keyframe reads it."""
     _fields_ = [("n", C.c_int32), ("desc", c_uint32_p), ("angle", c_float_p), ("point_id", c_int32_p), ("world_pos", c_float_p),
@@ -358,6 +376,7 @@ PRODUCT_SYMBOLS = [
     "lld_new_points_triangulate",
     "lld_covisibility_params_default", "lld_covisibility",
     "lld_frame_build_stereo_keypoints", "lld_frame_build_stereo", "lld_frame_stereo_download",
+    "lld_frame_build_mono_keypoints", "lld_frame_build_mono", "lld_frame_keypoints_download", "lld_frame_image_bounds",
 ]
 
 

@@ -28,6 +28,9 @@ struct lld_frame {
   bool stereo_built = false;
   size_t o_res = 0, o_depth = 0, o_bestr = 0, o_sad = 0, o_sum = 0, res_bytes = 0;
   void* h_stage = nullptr;
+  // A frame built by lld_frame_build_mono* (lld_frame_mono.hip): the kernel wrote mvKeysUn, mvuRight and mvDepth into `d`; o_res is the start of
+  // the contiguous block u_right | depth | xy that lld_frame_keypoints_download fetches in one copy.  h_stage as above.
+  bool mono_built = false;
   // Frame::ComputeBoW (lld_frame_compute_bow, lld_bow.hip): the frame's copy of the vocabulary's output block for its nt descriptors -
   // value[nt] f64 | int32 {n_words, n_nodes} | word[nt] | node[nt] | node_start[nt + 1] | feature[nt] | ... - so mFeatVec stays in HBM.
   char* d_bow = nullptr; bool has_bow = false;

@@ -8,7 +8,7 @@ import numpy as np
 
 from . import abi
 from .abi import c_float_p, c_int32_p, c_uint32_p, c_uint8_p
-from .orb_search import Frame, StereoBuiltFrame, StereoMatches, StereoPyramids, StereoResult, frame_stereo_params, keypoints_struct
+from .orb_search import Frame, MonoBuiltFrame, StereoBuiltFrame, StereoMatches, StereoPyramids, StereoResult, frame_stereo_params, keypoints_struct
 
 MAX_LEVELS = 16
 
@@ -176,6 +176,27 @@ class ORBextractor:
         if st != abi.LLD_OK:
             raise RuntimeError(f"lld_frame_build_stereo failed: {self.lib.fn('status_string')(st).decode()} (status {st})")
         return StereoBuiltFrame(self.lib, self.ctx.handle, L, h)
+
+    def build_mono_frame_raw(self, image_index, depth, params):
+        """lld_frame_build_mono as it is: (status, handle).  depth: an abi.DepthImage or None."""
+        h = C.c_void_p()
+        st = _fn(self.lib, "frame_build_mono", [C.c_void_p, C.c_int, C.POINTER(abi.DepthImage), C.POINTER(abi.FrameMonoParams), C.POINTER(C.c_void_p)])(
+            self.handle, int(image_index), None if depth is None else C.byref(depth), None if params is None else C.byref(params), C.byref(h))
+        return st, h
+
+    def build_mono_frame(self, L: Frame, cam, dist, mbf, depth=None, depth_factor=1.0, image_index=0) -> MonoBuiltFrame:
+        """Frame::Frame's device part for an RGB-D (depth given) or monocular image of the last call (lld_frame_build_mono):
+        UndistortKeyPoints and ComputeStereoFromRGBD without the keypoints leaving HBM.  `L`: the Frame the last call returned for that
+        image; cam: (fx, fy, cx, cy, ...); dist: mDistCoef (4 or 5 floats); depth: a float32 / uint16 image as GrabImageRGBD receives
+        it (or a device tuple, orb_search.depth_image_struct) with depth_factor = mDepthMapFactor.  Queued, not waited for."""
+        from .orb_search import depth_image_struct, frame_mono_params, mono_host_frame
+        H = mono_host_frame(self.lib, L, cam, dist)
+        prm, keep = frame_mono_params(H, cam, dist, mbf)
+        D, keep2 = depth_image_struct(depth, depth_factor)
+        st, h = self.build_mono_frame_raw(image_index, D, prm)
+        if st != abi.LLD_OK:
+            raise RuntimeError(f"lld_frame_build_mono failed: {self.lib.fn('status_string')(st).decode()} (status {st})")
+        return MonoBuiltFrame(self.lib, self.ctx.handle, H, h)
 
     def close(self):
         if getattr(self, "handle", None):

@@ -682,6 +682,132 @@ def build_stereo_frame_keypoints(lib, ctx, L: Frame, R: Frame, left_levels, righ
     return StereoBuiltFrame(lib, ctx, L, h)
 
 
+# ---------------------------------------------------------------------- the RGB-D / monocular Frame built on the device
+@dataclass
+class MonoKeypoints:
+    xy_un: np.ndarray        # [n,2] mvKeysUn[i].pt
+    u_right: np.ndarray      # mvuRight
+    depth: np.ndarray        # mvDepth
+
+
+class MonoBuiltFrame(ResidentFrame):
+    """A resident frame made by lld_frame_build_mono / lld_frame_build_mono_keypoints: mvKeysUn, mvuRight and mvDepth were computed on
+    the device.  Everything a ResidentFrame does works on it; `download()` waits, returns them and fills `F.xy` / `F.uright`.  `F` is
+    the Frame as the host knows it: the undistorted image bounds, and until download the DISTORTED keypoints with uright = -1."""
+
+    def __init__(self, lib, ctx, F: Frame, handle):
+        self.lib, self.ctx, self.F, self.handle = lib, ctx, F, handle
+
+    def download(self) -> MonoKeypoints:
+        n = self.F.n
+        out = MonoKeypoints(np.empty((n, 2), np.float32), np.empty(n, np.float32), np.empty(n, np.float32))
+        fn = self.lib.fn("frame_keypoints_download"); fn.argtypes = [C.c_void_p, c_float_p, c_float_p, c_float_p]; fn.restype = C.c_int
+        st = fn(self.handle, _p(out.xy_un, c_float_p), _p(out.u_right, c_float_p), _p(out.depth, c_float_p))
+        if st != abi.LLD_OK:
+            raise RuntimeError(f"lld_frame_keypoints_download failed: {self.lib.fn('status_string')(st).decode()}")
+        self.F.xy = out.xy_un.copy(); self.F.uright = out.u_right.copy()
+        return out
+
+
+def _dist_array(dist):
+    d = np.ascontiguousarray(dist, np.float32).reshape(-1)
+    return d, int(d.shape[0])
+
+
+def image_bounds_raw(lib, cols, rows, cam, dist, n_dist=None):
+    """lld_frame_image_bounds as it is: (status, [mnMinX, mnMaxX, mnMinY, mnMaxY]).  cam: (fx, fy, cx, cy, ...)."""
+    d, nd = _dist_array(dist) if dist is not None else (None, 0)
+    b = np.zeros(4, np.float32)
+    fn = lib.fn("frame_image_bounds")
+    fn.argtypes = [C.c_int32, C.c_int32, C.c_float, C.c_float, C.c_float, C.c_float, c_float_p, C.c_int32, c_float_p]; fn.restype = C.c_int
+    st = fn(int(cols), int(rows), *[float(np.float32(c)) for c in cam[:4]], _p(d, c_float_p), nd if n_dist is None else int(n_dist), _p(b, c_float_p))
+    return st, b
+
+
+def image_bounds(lib, cols, rows, cam, dist):
+    """Frame::ComputeImageBounds (src/Frame.cc:500-528) on the library's undistortion: float32 [mnMinX, mnMaxX, mnMinY, mnMaxY].  Host only."""
+    st, b = image_bounds_raw(lib, cols, rows, cam, dist)
+    if st != abi.LLD_OK:
+        raise ValueError(f"lld_frame_image_bounds failed: {lib.fn('status_string')(st).decode()}")
+    return b
+
+
+def frame_mono_params(F: Frame, cam, dist, mbf, angle=None, keypoints_on_device=False):
+    """lld_frame_mono_params from the Frame's (undistorted) image bounds and level tables: (struct, arrays kept alive).  `angle`: the
+    angles as a pointer value when they live on the device, else F.angle."""
+    F.normalise()
+    P = abi.FrameMonoParams()
+    P.grid_min_x, P.grid_min_y = float(np.float32(F.min_x)), float(np.float32(F.min_y))
+    P.grid_width_inv, P.grid_height_inv = float(F.width_inv), float(F.height_inv)
+    P.grid_cols, P.grid_rows = FRAME_GRID_COLS, FRAME_GRID_ROWS
+    P.fx, P.fy, P.cx, P.cy = [float(np.float32(c)) for c in cam[:4]]
+    d, nd = _dist_array(dist)
+    for i in range(min(nd, 5)): P.dist[i] = float(d[i])
+    P.n_dist = nd
+    P.mbf = float(np.float32(mbf))
+    P.left_angle = _p(F.angle, c_float_p) if angle is None else C.cast(C.c_void_p(angle), c_float_p)
+    P.keypoints_on_device = int(keypoints_on_device)
+    P.n_levels = int(F.scale.shape[0])
+    P.level_scale = _p(F.scale, c_float_p); P.level_sigma2 = _p(F.sigma2, c_float_p); P.level_inv_sigma2 = _p(F.inv_sigma2, c_float_p)
+    return P, dict(F=F)
+
+
+def depth_image_struct(depth, factor=1.0):
+    """lld_depth_image from a 2-D float32 / uint16 array (rows may be strided), or from a (device pointer, cols, rows, step in bytes,
+    type) tuple: (struct, array kept alive); (None, None) for depth = None."""
+    if depth is None:
+        return None, None
+    D = abi.DepthImage(); D.factor = float(np.float32(factor))
+    if isinstance(depth, tuple):
+        ptr, cols, rows, step, typ = depth
+        D.data, D.cols, D.rows, D.step, D.type, D.on_device = int(ptr), int(cols), int(rows), int(step), int(typ), 1
+        return D, None
+    a = np.asarray(depth)
+    if a.dtype not in (np.float32, np.uint16):
+        raise ValueError("a depth image is float32 (CV_32F) or uint16 (CV_16U)")
+    if a.ndim != 2 or a.strides[1] != a.itemsize:
+        a = np.ascontiguousarray(a).reshape(a.shape[0], -1)
+    D.data, D.cols, D.rows, D.step = a.ctypes.data, a.shape[1], a.shape[0], a.strides[0]
+    D.type = abi.DEPTH_F32 if a.dtype == np.float32 else abi.DEPTH_U16
+    D.on_device = 0
+    return D, a
+
+
+def mono_host_frame(lib, F: Frame, cam, dist, image_size=None) -> Frame:
+    """The Frame the host keeps next to a device-built one: F's arrays with the undistorted image bounds (lld_frame_image_bounds) of the
+    cols x rows image (default: F.max_x x F.max_y, what ORBextractor sets)."""
+    cols, rows = image_size if image_size is not None else (int(F.max_x), int(F.max_y))
+    b = image_bounds(lib, cols, rows, cam, dist)
+    import dataclasses
+    return dataclasses.replace(F, xy=F.xy.copy(), uright=np.full(F.n, -1, np.float32), min_x=float(b[0]), max_x=float(b[1]), min_y=float(b[2]),
+                               max_y=float(b[3])).normalise()
+
+
+def build_mono_frame_raw(lib, ctx, kp: Keypoints, depth, params):
+    """lld_frame_build_mono_keypoints as it is: (status, handle)."""
+    fn = lib.fn("frame_build_mono_keypoints")
+    fn.argtypes = [C.c_void_p, C.POINTER(Keypoints), C.POINTER(abi.DepthImage), C.POINTER(abi.FrameMonoParams), C.POINTER(C.c_void_p)]
+    fn.restype = C.c_int
+    h = C.c_void_p()
+    st = fn(ctx, None if kp is None else C.byref(kp), None if depth is None else C.byref(depth), None if params is None else C.byref(params), C.byref(h))
+    return st, h
+
+
+def build_mono_frame_keypoints(lib, ctx, F: Frame, cam, dist, mbf, depth=None, depth_factor=1.0, device=None, image_size=None) -> MonoBuiltFrame:
+    """The RGB-D (depth given) or monocular Frame from the caller's DISTORTED keypoints (lld_frame_build_mono_keypoints); queued, not
+    waited for.  `device`: dict of pointer values (xy, desc, angle) when the keypoints already live in HBM - F.octave stays on the host."""
+    H = mono_host_frame(lib, F, cam, dist, image_size)
+    kp = keypoints_struct(F)
+    if device is not None:
+        kp.xy = C.cast(C.c_void_p(device["xy"]), c_float_p); kp.desc = C.cast(C.c_void_p(device["desc"]), c_uint32_p)
+    prm, keep = frame_mono_params(H, cam, dist, mbf, angle=None if device is None else device["angle"], keypoints_on_device=device is not None)
+    D, keep2 = depth_image_struct(depth, depth_factor)
+    st, h = build_mono_frame_raw(lib, ctx, kp, D, prm)
+    if st != abi.LLD_OK:
+        raise RuntimeError(f"lld_frame_build_mono_keypoints failed: {lib.fn('status_string')(st).decode()}")
+    return MonoBuiltFrame(lib, ctx, H, h)
+
+
 def fuse_search_points(lib, ctx, KF: Frame, view: FrameView, mp: dict, th=3.0):
     """ORBmatcher::Fuse(KeyFrame*, vpMapPoints, th) (src/ORBmatcher.cc:825-958) with the projection loop on the device too.
     Returns (SearchOutput, proj_uvr [n,3]); match[i] = bestIdx or -1, n_matches = nFused."""

@@ -197,9 +197,10 @@ class DeviceTrackedFrame:
         self._setup(lines, gamma, params)
 
     @classmethod
-    def from_stereo_build(cls, ctx, built: "orb_search.StereoBuiltFrame", cam, lines: dict | None = None, gamma=0.5, **params):
-        """The chain on a frame the device built (ORBextractor.build_stereo_frame / orb_search.build_stereo_frame_keypoints): the
-        handle is taken over (close() destroys it), nothing is uploaded again."""
+    def from_built(cls, ctx, built: "orb_search.ResidentFrame", cam, lines: dict | None = None, gamma=0.5, **params):
+        """The chain on a frame the device built (orb_search.StereoBuiltFrame, or MonoBuiltFrame from ORBextractor.build_mono_frame /
+        orb_search.build_mono_frame_keypoints): the handle is taken over (close() destroys it), nothing is uploaded again.  For an
+        RGB-D frame pass th_motion=15, th_local=3 (Tracking.cc:901, :1657); for a monocular one th_motion=15 and monocular=1."""
         h_ctx = getattr(built.ctx, "value", built.ctx)
         if h_ctx != getattr(ctx.handle, "value", ctx.handle):
             raise ValueError("the built frame belongs to another context")
@@ -208,6 +209,11 @@ class DeviceTrackedFrame:
         self.res = built
         self._setup(lines, gamma, params)
         return self
+
+    @classmethod
+    def from_stereo_build(cls, ctx, built: "orb_search.StereoBuiltFrame", cam, lines: dict | None = None, gamma=0.5, **params):
+        """from_built on a stereo frame (ORBextractor.build_stereo_frame / orb_search.build_stereo_frame_keypoints)."""
+        return cls.from_built(ctx, built, cam, lines, gamma, **params)
 
     def _setup(self, lines, gamma, params):
         lib, F = self.lib, self.F
