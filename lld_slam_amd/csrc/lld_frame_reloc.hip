@@ -234,12 +234,8 @@ __global__ __launch_bounds__(kSlotThreads) void reloc_pick_kernel(RelocDev R, Tr
     for (int i = 0; i < 7; i++) D.pose_qt[i] = R.s_pose_qt[7 * w + i];
     *D.view = R.s_view[w];
     line_camera_from_view(C, *D.view, D.line_params);
-    const double* po = R.s_pose_out + 12 * (size_t)w;
-    const int* pi = reinterpret_cast<const int*>(po + 8);
     RecHeader& H = *D.rec_h[0];
-    for (int i = 0; i < 7; i++) H.pose_qt[i] = po[i];
-    H.chi2 = po[7];
-    H.i[RI_INL] = pi[0]; H.i[RI_ITS] = pi[1]; H.i[RI_TRIALS] = pi[2]; H.i[RI_EDGES] = pi[3]; H.i[RI_POINT_EDGES] = pi[4];
+    rec_header_from_pose(H, R.s_pose_out + 12 * (size_t)w);
     H.i[RI_SEARCH1] = R.m_cnt[4 * w]; H.i[RI_SEARCH] = R.m_cnt[4 * w];
     H.i[RI_POINTS] = cnt_sh[0]; H.i[RI_POINTS_MAP] = cnt_sh[1];
   }
@@ -277,136 +273,93 @@ extern "C" int lld_frame_relocalize(lld_frame* f, const lld_track_params* P, con
   LLD_HIP_TRY(hipSetDevice(ctx->device));
   int s = ensure_state(f); if (s) return s;
   lld_frame_track_state* S = f->track;
-  fill_consts(S, f, P, view);
+  fill_consts(S, P, view);
   const ViewConsts C = S->consts;
 
   // ---- layout: the uploaded block, then device-only state
-  size_t o = 0;
-  auto take = [&](size_t bytes) { const size_t at = o; o += al(bytes); return at; };
-  const size_t o_pose = take(7 * 8), o_lp = take(sizeof(LineTrackDevParams)), o_view = take(sizeof(lld_frame_view));
-  const size_t o_bows = take(sizeof(BowSearchDev) * K), o_aps = take(sizeof(ApplyDev) * K), o_cand = take(sizeof(CandDev) * K);
-  const size_t o_proj1 = take(sizeof(RelocProjSlot) * K), o_proj2 = take(sizeof(RelocProjSlot) * K);
-  const size_t pstride = orbs_problem_bytes();
-  const size_t o_prob = take(pstride * 2 * K);
-  struct CandUp { size_t desc, ang, id, pos, obs, node, start, feat, maxd, mind, pdesc; };
-  std::vector<CandUp> U(K);
-  for (int c = 0; c < K; c++) {
-    const int n = cands[c].n, nn = cands[c].n_nodes;
-    U[c].desc = take((size_t)n * 32); U[c].ang = take((size_t)n * 4); U[c].id = take((size_t)n * 4); U[c].pos = take((size_t)n * 12); U[c].obs = take(n);
-    U[c].node = take((size_t)nn * 4); U[c].start = take((size_t)(nn + 1) * 4); U[c].feat = take((size_t)nv[c] * 4);
-    U[c].maxd = take((size_t)n * 4); U[c].mind = take((size_t)n * 4);
-    U[c].pdesc = extra[c].point_desc ? take((size_t)n * 32) : U[c].desc;
-  }
-  const size_t up_bytes = o;
+  UploadBlock B; StageHeader H; H.reserve(B);
+  const auto bows = B.take<BowSearchDev>(K); const auto aps = B.take<ApplyDev>(K); const auto cand = B.take<CandDev>(K);
+  const Span<RelocProjSlot> proj[2] = {B.take<RelocProjSlot>(K), B.take<RelocProjSlot>(K)};
+  const size_t pstride = orbs_problem_bytes(); const auto prob = B.take<char>(pstride * 2 * K);
+  std::vector<RefKeyframeUp> U(K);
+  for (int c = 0; c < K; c++) U[c].reserve(B, cands[c], nv[c], &extra[c]);
+  B.end_upload();
   const size_t kn = (size_t)K * nt;
   // zeroed at the start of the call: match tables, counts, slots' flags and records
-  const size_t o_zero = o;
-  const size_t o_mhas = take(kn), o_mid = take(kn * 4), o_mobs = take(kn), o_mworld = take(kn * 12), o_mcnt = take((size_t)K * 16);
-  const size_t o_run = take((size_t)N_RUN * K * 4), o_cnt1 = take((size_t)K * 16), o_cnt2 = take((size_t)K * 16), o_cur = take((size_t)K * 16);
-  const size_t o_rec = take((size_t)K * REC_INTS * 4), o_status = take(ST_INTS * 4);
-  const size_t zero_bytes = o - o_zero;
-  const size_t o_taken = take(kn * 4);
-  const size_t o_shas = take(kn), o_sid = take(kn * 4), o_sobs = take(kn), o_sworld = take(kn * 12), o_sout = take(kn);
-  const size_t o_sqt = take((size_t)K * 7 * 8), o_spo = take((size_t)K * 12 * 8), o_sview = take(sizeof(lld_frame_view) * K);
-  const size_t o_live = take(K), o_keep = take(K), o_off = take((size_t)K * 4);
-  std::vector<size_t> o_skip(K), o_qrec(K), o_cache(K), o_so0(K), o_so1(K), o_so2(K), o_so3(K), o_so4(K), o_so5(K);
-  for (int c = 0; c < K; c++) {
-    const int n = cands[c].n;
-    o_skip[c] = take(n); o_qrec[c] = take(orbs_qrec_bytes(n)); o_cache[c] = take(orbs_cache_bytes(n));
-    o_so0[c] = take((size_t)n * 4); o_so1[c] = take((size_t)n * 4); o_so2[c] = take((size_t)n * 4); o_so3[c] = take(n); o_so4[c] = take((size_t)nt * 4); o_so5[c] = take(16);
-  }
-  const size_t o_pwork = take(pose_slots_work_bytes(K, nt));
-  s = ensure_work(S, ctx, o); if (s) return s;
-  s = ensure_stage(S, 0, up_bytes); if (s) return s;
+  const size_t o_zero = B.size;
+  const auto mhas = B.take<uint8_t>(kn); const auto mid = B.take<int32_t>(kn); const auto mobs = B.take<uint8_t>(kn); const auto mworld = B.take<float>(kn, 3);
+  const auto mcnt = B.take<int32_t>(K, 4), run = B.take<int32_t>(K, N_RUN), cnt1 = B.take<int32_t>(K, 4), cnt2 = B.take<int32_t>(K, 4), cur = B.take<int32_t>(K, 4);
+  const auto rec = B.take<int32_t>(K, REC_INTS), status = B.take<int32_t>(ST_INTS);
+  const size_t zero_bytes = B.size - o_zero;
+  const auto taken = B.take<int32_t>(kn);
+  const auto shas = B.take<uint8_t>(kn); const auto sid = B.take<int32_t>(kn); const auto sobs = B.take<uint8_t>(kn); const auto sworld = B.take<float>(kn, 3);
+  const auto sout = B.take<uint8_t>(kn); const auto sqt = B.take<double>(K, 7); const auto spo = B.take<double>(K, 12); const auto sview = B.take<lld_frame_view>(K);
+  const auto live = B.take<uint8_t>(K), keep = B.take<uint8_t>(K); const auto off_d = B.take<int32_t>(K);
+  struct SlotScratch { Span<uint8_t> skip; SearchScratch search; };          // sFound as skip bytes and the projected searches' scratch, per candidate
+  std::vector<SlotScratch> W(K);
+  for (int c = 0; c < K; c++) { W[c].skip = B.take<uint8_t>(cands[c].n); W[c].search.reserve(B, cands[c].n, nt); }
+  const auto pwork = B.take<char>(pose_slots_work_bytes(K, nt));
+  s = stage_begin(S, ctx, 0, B); if (s) return s;
   // the second pinned region: the small uploads after the counts are known, the status word, the final records
-  const size_t h2_keep = 0, h2_off = al(K), h2_status = h2_off + al((size_t)K * 4), h2_cnt = h2_status + al(ST_INTS * 4), h2_rec = h2_cnt + al((size_t)K * 4),
-               h2_view = h2_rec + al((size_t)K * REC_INTS * 4), h2_bytes = h2_view + al(sizeof(lld_frame_view));
-  s = ensure_stage(S, 1, h2_bytes); if (s) return s;
-  char* h = S->h_stage[0]; char* h2 = S->h_stage[1]; char* d = S->d_work;
+  UploadBlock B2; const auto h2_keep = B2.take<uint8_t>(K);
+  const auto h2_off = B2.take<int32_t>(K), h2_status = B2.take<int32_t>(ST_INTS), h2_cnt = B2.take<int32_t>(K), h2_rec = B2.take<int32_t>(K, REC_INTS); const auto h2_view = B2.take<lld_frame_view>(1);
+  s = ensure_stage(S, 1, B2.size); if (s) return s;
+  B2.bind(S->h_stage[1], nullptr);
 
   // ---- the device's view of everything
   RelocDev R{};
-  R.K = K; R.nt = nt; R.cand = reinterpret_cast<const CandDev*>(d + o_cand);
-  R.m_has = reinterpret_cast<uint8_t*>(d + o_mhas); R.m_id = reinterpret_cast<int32_t*>(d + o_mid); R.m_obs = reinterpret_cast<uint8_t*>(d + o_mobs);
-  R.m_world = reinterpret_cast<float*>(d + o_mworld); R.m_cnt = reinterpret_cast<int32_t*>(d + o_mcnt);
-  R.s_has = reinterpret_cast<uint8_t*>(d + o_shas); R.s_id = reinterpret_cast<int32_t*>(d + o_sid); R.s_obs = reinterpret_cast<uint8_t*>(d + o_sobs);
-  R.s_world = reinterpret_cast<float*>(d + o_sworld); R.s_out = reinterpret_cast<uint8_t*>(d + o_sout);
-  R.s_pose_qt = reinterpret_cast<double*>(d + o_sqt); R.s_pose_out = reinterpret_cast<double*>(d + o_spo); R.s_view = reinterpret_cast<lld_frame_view*>(d + o_sview);
-  R.run = reinterpret_cast<int32_t*>(d + o_run); R.cnt1 = reinterpret_cast<int32_t*>(d + o_cnt1); R.cnt2 = reinterpret_cast<int32_t*>(d + o_cnt2);
-  R.live = reinterpret_cast<uint8_t*>(d + o_live); R.cur = reinterpret_cast<int32_t*>(d + o_cur); R.rec = reinterpret_cast<int32_t*>(d + o_rec);
-  R.status = reinterpret_cast<int32_t*>(d + o_status);
+  R.K = K; R.nt = nt; R.cand = B.dev(cand);
+  R.m_has = B.dev(mhas); R.m_id = B.dev(mid); R.m_obs = B.dev(mobs); R.m_world = B.dev(mworld); R.m_cnt = B.dev(mcnt);
+  R.s_has = B.dev(shas); R.s_id = B.dev(sid); R.s_obs = B.dev(sobs); R.s_world = B.dev(sworld); R.s_out = B.dev(sout);
+  R.s_pose_qt = B.dev(sqt); R.s_pose_out = B.dev(spo); R.s_view = B.dev(sview);
+  R.run = B.dev(run); R.cnt1 = B.dev(cnt1); R.cnt2 = B.dev(cnt2); R.live = B.dev(live); R.cur = B.dev(cur); R.rec = B.dev(rec); R.status = B.dev(status);
 
   // ---- pack
-  std::memcpy(h + o_pose, pose_qt, 7 * 8);
-  line_params_from_view(C, *view, reinterpret_cast<LineTrackDevParams*>(h + o_lp));
-  std::memcpy(h + o_view, view, sizeof(lld_frame_view));
-  const uint32_t* f_desc = reinterpret_cast<const uint32_t*>(f->d + f->o_td);
-  const float* f_angle = reinterpret_cast<const float*>(f->d + f->o_tang);
+  H.stage(B, C, view, pose_qt);
   for (int c = 0; c < K; c++) {
-    const lld_ref_keyframe& kf = cands[c];
-    const int n = kf.n, nn = kf.n_nodes;
-    if (n) {
-      std::memcpy(h + U[c].desc, kf.desc, (size_t)n * 32); std::memcpy(h + U[c].ang, kf.angle, (size_t)n * 4); std::memcpy(h + U[c].id, kf.point_id, (size_t)n * 4);
-      std::memcpy(h + U[c].pos, kf.world_pos, (size_t)n * 12);
-      if (kf.has_obs) std::memcpy(h + U[c].obs, kf.has_obs, n); else std::memset(h + U[c].obs, 1, n);
-      std::memcpy(h + U[c].maxd, extra[c].max_distance, (size_t)n * 4); std::memcpy(h + U[c].mind, extra[c].min_distance, (size_t)n * 4);
-      if (extra[c].point_desc) std::memcpy(h + U[c].pdesc, extra[c].point_desc, (size_t)n * 32);
-    }
-    if (nn) { std::memcpy(h + U[c].node, kf.node, (size_t)nn * 4); std::memcpy(h + U[c].start, kf.node_start, (size_t)(nn + 1) * 4); }
-    else std::memset(h + U[c].start, 0, 4);
-    if (nv[c]) std::memcpy(h + U[c].feat, kf.feature, (size_t)nv[c] * 4);
-    const int32_t* d_id = reinterpret_cast<const int32_t*>(d + U[c].id);
-    const float* d_pos = reinterpret_cast<const float*>(d + U[c].pos);
-    const uint8_t* d_obs = reinterpret_cast<const uint8_t*>(d + U[c].obs);
-    BowSearchDev& B = reinterpret_cast<BowSearchDev*>(h + o_bows)[c];
-    std::memset(&B, 0, sizeof(B));
-    B.nt = nt; B.n_kf_nodes = extra[c].is_bad ? 0 : nn;                      // if(pKF->isBad()) vbDiscarded[i] = true: no search (:1869-1870)
-    B.f_desc = f_desc; B.f_angle = f_angle;
-    B.f_n_nodes = f->bow_n_nodes(); B.f_node = f->bow_node(); B.f_node_start = f->bow_node_start(); B.f_feature = f->bow_feature();
-    B.kf_desc = reinterpret_cast<const uint32_t*>(d + U[c].desc); B.kf_angle = reinterpret_cast<const float*>(d + U[c].ang); B.kf_point_id = d_id;
-    B.kf_node = reinterpret_cast<const int32_t*>(d + U[c].node); B.kf_node_start = reinterpret_cast<const int32_t*>(d + U[c].start);
-    B.kf_feature = reinterpret_cast<const int32_t*>(d + U[c].feat);
-    B.nnratio = 0.75f; B.check_orientation = 1;                              // ORBmatcher matcher(0.75,true) (:1853)
-    B.taken = reinterpret_cast<int32_t*>(d + o_taken) + (size_t)c * nt;
+    const int n = cands[c].n;
+    U[c].stage(B, cands[c], &extra[c]);
+    BowSearchDev& Bs = B.host(bows)[c];
+    std::memset(&Bs, 0, sizeof(Bs));
+    bow_frame_side(f, Bs);
+    Bs.n_kf_nodes = extra[c].is_bad ? 0 : cands[c].n_nodes;                  // if(pKF->isBad()) vbDiscarded[i] = true: no search (:1869-1870)
+    const RefKeyframeUp::Query q = U[c].dev(B, Bs);
+    Bs.nnratio = 0.75f; Bs.check_orientation = 1;                            // ORBmatcher matcher(0.75,true) (:1853)
+    Bs.taken = B.dev(taken) + (size_t)c * nt;
     const size_t ck = (size_t)c * nt;
-    reinterpret_cast<ApplyDev*>(h + o_aps)[c] = ApplyDev{R.m_has + ck, R.m_world + 3 * ck, R.m_id + ck, R.m_obs + ck, d_pos, d_id, d_obs, R.m_cnt + 4 * c, 0, 0};
-    reinterpret_cast<CandDev*>(h + o_cand)[c] = CandDev{n, 0, d_id, reinterpret_cast<uint8_t*>(d + o_skip[c])};
+    B.host(aps)[c] = ApplyDev{R.m_has + ck, R.m_world + 3 * ck, R.m_id + ck, R.m_obs + ck, q.pos, q.id, q.obs, R.m_cnt + 4 * c, 0, 0};
+    B.host(cand)[c] = CandDev{n, 0, q.id, B.dev(W[c].skip)};
     // the two projected searches of the slot: matcher2(0.9,true).SearchByProjection(F, pKF, sFound, 10, 100) and (.., 3, 64)
-    const SearchOut so{reinterpret_cast<int32_t*>(d + o_so0[c]), reinterpret_cast<int32_t*>(d + o_so1[c]), reinterpret_cast<int32_t*>(d + o_so2[c]),
-                       reinterpret_cast<uint8_t*>(d + o_so3[c]), reinterpret_cast<int32_t*>(d + o_so4[c]), reinterpret_cast<int32_t*>(d + o_so5[c])};
+    const SearchScratch& ss = W[c].search;
     for (int k = 0; k < 2; k++) {
-      const int32_t* run = R.run + (k == 0 ? RUN_S1 : RUN_S2) * K + c;
-      RelocProjSlot& ps = reinterpret_cast<RelocProjSlot*>(h + (k == 0 ? o_proj1 : o_proj2))[c];
-      ps = RelocProjSlot{n, 0, d_pos, reinterpret_cast<const float*>(d + U[c].maxd), reinterpret_cast<const float*>(d + U[c].mind), reinterpret_cast<const uint8_t*>(d + o_skip[c]),
-                         reinterpret_cast<const float*>(d + U[c].ang), d + o_qrec[c], R.s_view + c, run};
-      const ApplyDev ap{R.s_has + ck, R.s_world + 3 * ck, R.s_id + ck, R.s_obs + ck, d_pos, d_id, d_obs, (k == 0 ? R.cnt1 : R.cnt2) + 4 * c, 0, 0};
-      orbs_fill_problem_reloc(f, n, R.s_has + ck, d + o_qrec[c], reinterpret_cast<const uint32_t*>(d + U[c].pdesc), so, d + o_cache[c], k == 0 ? 100 : 64,
-                              RunIf{run, 1, 0}, ap, h + o_prob + pstride * (size_t)(k * K + c));
+      const int32_t* run_k = R.run + (k == 0 ? RUN_S1 : RUN_S2) * K + c;
+      B.host(proj[k])[c] = RelocProjSlot{n, 0, q.pos, B.dev(U[c].maxd), B.dev(U[c].mind), B.dev(W[c].skip), B.dev(U[c].ang), B.dev(ss.qrec), R.s_view + c, run_k};
+      const ApplyDev ap{R.s_has + ck, R.s_world + 3 * ck, R.s_id + ck, R.s_obs + ck, q.pos, q.id, q.obs, (k == 0 ? R.cnt1 : R.cnt2) + 4 * c, 0, 0};
+      orbs_fill_problem_reloc(f, n, R.s_has + ck, B.dev(ss.qrec), B.dev(U[c].pdesc), ss.out(B), B.dev(ss.cache), k == 0 ? 100 : 64,
+                              RunIf{run_k, 1, 0}, ap, B.host(prob) + pstride * (size_t)(k * K + c));
     }
   }
   hipStream_t st = ctx->stream;
-  LLD_HIP_TRY(hipMemcpyAsync(d, h, up_bytes, hipMemcpyHostToDevice, st));
-  LLD_HIP_TRY(hipEventRecord(S->uploaded[0], st)); S->upload_pending[0] = true;
+  s = stage_submit(S, st, 0, B); if (s) return s;
 
   // ---- the frame enters the routine holding nothing; SearchByBoW against every candidate
-  s = track_reset_launch(st, S, reinterpret_cast<const double*>(d + o_pose), reinterpret_cast<const lld_frame_view*>(d + o_view),
-                         reinterpret_cast<const LineTrackDevParams*>(d + o_lp)); if (s) return s;
+  s = track_reset_launch(st, S, B, H); if (s) return s;
   { const int nmax = std::max(std::max(nt, S->nl), 1); hipLaunchKernelGGL(reloc_record_clear_kernel, dim3((nmax + 255) / 256), dim3(256), 0, st, S->D); }
   S->stage1_queued = true; S->n_in_view = 0;
-  LLD_HIP_TRY(hipMemsetAsync(d + o_zero, 0, zero_bytes, st));
-  if (kn) LLD_HIP_TRY(hipMemsetAsync(d + o_taken, 0xff, kn * 4, st));
+  LLD_HIP_TRY(hipMemsetAsync(B.d + o_zero, 0, zero_bytes, st));
+  if (kn) LLD_HIP_TRY(hipMemsetAsync(B.dev(taken), 0xff, kn * 4, st));
   if (nt > 0 && nn_max > 0)
-    hipLaunchKernelGGL(reloc_bow_match_kernel, dim3((nn_max + kMatchWaves - 1) / kMatchWaves, K), dim3(kMatchWaves * 64), 0, st, reinterpret_cast<const BowSearchDev*>(d + o_bows));
-  hipLaunchKernelGGL(reloc_bow_finish_kernel, dim3(K), dim3(kFinishThreads), 0, st, reinterpret_cast<const BowSearchDev*>(d + o_bows), reinterpret_cast<const ApplyDev*>(d + o_aps));
+    hipLaunchKernelGGL(reloc_bow_match_kernel, dim3((nn_max + kMatchWaves - 1) / kMatchWaves, K), dim3(kMatchWaves * 64), 0, st, B.dev(bows));
+  hipLaunchKernelGGL(reloc_bow_finish_kernel, dim3(K), dim3(kFinishThreads), 0, st, B.dev(bows), B.dev(aps));
   LLD_HIP_TRY(hipGetLastError());
   // ---- the counts (4 K bytes: word 0 of every candidate's ap_counts): the only transfer before the rounds
-  int32_t* h_cnt = reinterpret_cast<int32_t*>(h2 + h2_cnt);
-  LLD_HIP_TRY(hipMemcpy2DAsync(h_cnt, 4, d + o_mcnt, 16, 4, K, hipMemcpyDeviceToHost, st));
+  int32_t* h_cnt = B2.host(h2_cnt);
+  LLD_HIP_TRY(hipMemcpy2DAsync(h_cnt, 4, R.m_cnt, 16, 4, K, hipMemcpyDeviceToHost, st));
   LLD_HIP_TRY(hipStreamSynchronize(st));
   S->upload_pending[0] = false;
   std::vector<int32_t> n_corr(K, 0), off(K, 0);
   std::vector<uint32_t> seeds(K, 0);
-  uint8_t* h_keep = reinterpret_cast<uint8_t*>(h2 + h2_keep);
+  uint8_t* h_keep = B2.host(h2_keep);
   int n_kept = 0;
   for (int c = 0; c < K; c++) {
     const int nb = h_cnt[c];
@@ -440,35 +393,34 @@ extern "C" int lld_frame_relocalize(lld_frame* f, const lld_track_params* P, con
   if (s) return s;
   auto fail = [&](int status) { (void)hipStreamSynchronize(st); lld_pnp_batch_destroy(batch); return status; };
   R.pnp_res = lld_pnp::batch_results_dev(batch); R.pnp_flags = lld_pnp::batch_flags_dev(batch, 0);
-  std::memcpy(h2 + h2_off, off.data(), (size_t)K * 4);
-  if (hipMemcpyAsync(d + o_keep, h2 + h2_keep, K, hipMemcpyHostToDevice, st) != hipSuccess || hipMemcpyAsync(d + o_live, h2 + h2_keep, K, hipMemcpyHostToDevice, st) != hipSuccess ||
-      hipMemcpyAsync(d + o_off, h2 + h2_off, (size_t)K * 4, hipMemcpyHostToDevice, st) != hipSuccess) return fail(LLD_ERR_HIP);
+  B2.stage(h2_off, off.data());
+  if (hipMemcpyAsync(B.dev(keep), h_keep, K, hipMemcpyHostToDevice, st) != hipSuccess || hipMemcpyAsync(R.live, h_keep, K, hipMemcpyHostToDevice, st) != hipSuccess ||
+      hipMemcpyAsync(B.dev(off_d), B2.host(h2_off), (size_t)K * 4, hipMemcpyHostToDevice, st) != hipSuccess) return fail(LLD_ERR_HIP);
   LevelTable sig2;
   for (int l = 0; l < LLD_ORB_MAX_LEVELS; l++) sig2.v[l] = f->sigma2[l];
-  hipLaunchKernelGGL(reloc_pnp_assemble_kernel, dim3(K), dim3(kAsmThreads), 0, st, R, reinterpret_cast<const int32_t*>(d + o_off), reinterpret_cast<const uint8_t*>(d + o_keep), slab,
-                     reinterpret_cast<const float*>(f->d + f->o_txy), reinterpret_cast<const int32_t*>(f->d + f->o_toct), sig2, pnp->th2);
+  const KeypointsDev kp = resident_keypoints(f, false);
+  hipLaunchKernelGGL(reloc_pnp_assemble_kernel, dim3(K), dim3(kAsmThreads), 0, st, R, B.dev(off_d), B.dev(keep), slab, kp.xy, kp.octave, sig2, pnp->th2);
 
   // ---- the rounds: iterate(5) on the live solvers, the gate, the ladder over the slots, the pick; one status word back
   PoseSlotsDev ps{};
   ps.n_slots = K; ps.nt = nt;
-  ps.t_xy = reinterpret_cast<const float*>(f->d + f->o_txy); ps.t_uright = f->has_uright ? reinterpret_cast<const float*>(f->d + f->o_tur) : nullptr;
-  ps.t_octave = reinterpret_cast<const int32_t*>(f->d + f->o_toct);
+  ps.t_xy = kp.xy; ps.t_uright = kp.uright; ps.t_octave = kp.octave;
   ps.kp_has = R.s_has; ps.kp_world = R.s_world; ps.pose_qt = R.s_pose_qt; ps.cam = P->cam;
   for (int l = 0; l < LLD_ORB_MAX_LEVELS; l++) ps.inv_sigma2[l] = f->inv_sigma2[l];
   ps.kp_outlier = R.s_out; ps.pose_out = R.s_pose_out;
   auto pose_rung = [&](int run_index, int stage) {
     PoseSlotsDev q = ps; q.run = R.run + run_index * K;
-    int r = pose_slots_launch(ctx, st, q, P->pose, d + o_pwork); if (r) return r;
+    int r = pose_slots_launch(ctx, st, q, P->pose, B.dev(pwork)); if (r) return r;
     hipLaunchKernelGGL(reloc_after_pose_kernel, dim3(K), dim3(kSlotThreads), 0, st, R, C, stage);
     return LLD_OK;
   };
   auto search_rung = [&](int k, float th) {
-    int r = orbs_project_reloc_slots(st, f, K, n_max, reinterpret_cast<const RelocProjSlot*>(d + (k == 0 ? o_proj1 : o_proj2)), th); if (r) return r;
-    r = orbs_launch_n(ctx, st, f, d + o_prob + pstride * (size_t)(k * K), K); if (r) return r;
+    int r = orbs_project_reloc_slots(st, f, K, n_max, B.dev(proj[k]), th); if (r) return r;
+    r = orbs_launch_n(ctx, st, f, B.dev(prob) + pstride * (size_t)(k * K), K); if (r) return r;
     hipLaunchKernelGGL(reloc_between_kernel, dim3((K + 63) / 64), dim3(64), 0, st, R, k + 1);
     return LLD_OK;
   };
-  volatile int32_t* h_word = reinterpret_cast<volatile int32_t*>(h2 + h2_status);
+  volatile int32_t* h_word = B2.host(h2_status);
   // every round a live solver either ends (bNoMore) or returned a pose after at least 5 more iterations; a stream of poses that never reach 50
   // inliers has no end in the reference either: the loop stops after max_iterations rounds
   const int max_rounds = pnp->max_iterations + kMaxRoundsSlack;
@@ -483,10 +435,10 @@ extern "C" int lld_frame_relocalize(lld_frame* f, const lld_track_params* P, con
     if (word < 0 || word == 0) break;                                        // bMatch, or nCandidates == 0
   }
   // ---- `out`
-  if (hipMemcpyAsync(h2 + h2_status, R.status, ST_INTS * 4, hipMemcpyDeviceToHost, st) != hipSuccess ||
-      hipMemcpyAsync(h2 + h2_rec, R.rec, (size_t)K * REC_INTS * 4, hipMemcpyDeviceToHost, st) != hipSuccess ||
-      hipMemcpyAsync(h2 + h2_view, S->D.view, sizeof(lld_frame_view), hipMemcpyDeviceToHost, st) != hipSuccess || hipStreamSynchronize(st) != hipSuccess) return fail(LLD_ERR_HIP);
-  fill_out(reinterpret_cast<const int32_t*>(h2 + h2_status), reinterpret_cast<const int32_t*>(h2 + h2_rec), reinterpret_cast<const lld_frame_view*>(h2 + h2_view));
+  if (hipMemcpyAsync(B2.host(h2_status), R.status, ST_INTS * 4, hipMemcpyDeviceToHost, st) != hipSuccess ||
+      hipMemcpyAsync(B2.host(h2_rec), R.rec, (size_t)K * REC_INTS * 4, hipMemcpyDeviceToHost, st) != hipSuccess ||
+      hipMemcpyAsync(B2.host(h2_view), S->D.view, sizeof(lld_frame_view), hipMemcpyDeviceToHost, st) != hipSuccess || hipStreamSynchronize(st) != hipSuccess) return fail(LLD_ERR_HIP);
+  fill_out(B2.host(h2_status), B2.host(h2_rec), B2.host(h2_view));
   lld_pnp_batch_destroy(batch);
   return LLD_OK;
 }

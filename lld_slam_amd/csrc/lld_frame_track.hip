@@ -16,7 +16,9 @@
 //                tracked (tracked_last_id = mnId, :1117): SearchLocalPoints / AddLinesFrom skip them by id.
 //
 // Kernels of this file: the bookkeeping between the library's search / line / pose kernels (lld_orb_search.hip, lld_match.hip, lld_pose.hip),
-// i.e. what the reference does in the few lines of C++ between its calls.
+// i.e. what the reference does in the few lines of C++ between its calls.  Host half of a stage: one UploadBlock (lld_upload_block.h) declares the
+// uploaded arrays and the scratch behind them once, region structs (here and in lld_frame_track_state.h) lay out, pack and bind each group of
+// arrays, stage_begin / stage_submit size the buffers and queue the one copy.
 #include "lld_common.h"
 #include "lld_device_math.h"
 #include "lld_frame_track_state.h"
@@ -34,16 +36,13 @@ __global__ void track_reset_kernel(TrackDev D, const double* pose_guess, const l
   if (i < D.nl) { D.ln_has[i] = 0; D.ln_id[i] = -1; D.ln_outlier[i] = 0; }
   if (i < 7) D.pose_qt[i] = pose_guess[i];
   if (i == 0) { *D.n_discard = 0; *D.n_tracked = 0; }
-  if (i < 2 * (int)(sizeof(RecHeader) / 4)) {
-    int32_t* h = reinterpret_cast<int32_t*>(i < (int)(sizeof(RecHeader) / 4) ? D.rec_h[0] : D.rec_h[1]);
-    h[i % (int)(sizeof(RecHeader) / 4)] = 0;
-  }
+  rec_headers_zero(D, i);
 }
 
 // The frame enters TrackLocalMap from a stage 1 that ran elsewhere (lld_frame_track_set_state): what that routine left in the frame.
-struct HeldUp { const int32_t* kp_id; const float* kp_world; const uint8_t* kp_obs; const uint8_t* kp_out; const int32_t* seen; int n_seen;
+struct HeldDev { const int32_t* kp_id; const float* kp_world; const uint8_t* kp_obs; const uint8_t* kp_out; const int32_t* seen; int n_seen;
                 const int32_t* ln_id; const double* ln_x0; const double* ln_dir; const uint8_t* ln_out; const int32_t* tracked; int n_tracked; };
-__global__ void track_load_kernel(TrackDev D, HeldUp U, const double* pose_qt, const lld_frame_view* view_up, const LineTrackDevParams* lp_up) {
+__global__ void track_load_kernel(TrackDev D, HeldDev U, const double* pose_qt, const lld_frame_view* view_up, const LineTrackDevParams* lp_up) {
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i == 0) { *D.view = *view_up; *D.line_params = *lp_up; *D.n_discard = U.n_seen; }
   if (i < D.nt) {
@@ -62,10 +61,7 @@ __global__ void track_load_kernel(TrackDev D, HeldUp U, const double* pose_qt, c
   if (i < U.n_tracked) D.tracked[i] = U.tracked[i];
   if (i == 0) *D.n_tracked = U.n_tracked;
   if (i < 7) D.pose_qt[i] = pose_qt[i];
-  if (i < 2 * (int)(sizeof(RecHeader) / 4)) {
-    int32_t* h = reinterpret_cast<int32_t*>(i < (int)(sizeof(RecHeader) / 4) ? D.rec_h[0] : D.rec_h[1]);
-    h[i % (int)(sizeof(RecHeader) / 4)] = 0;
-  }
+  rec_headers_zero(D, i);
   if (i < D.nt) { D.rec_kp_id[0][i] = -1; D.rec_kp_out[0][i] = 0; }
   if (i < D.nl) { D.rec_ln_id[0][i] = -1; D.rec_ln_out[0][i] = 0; }
 }
@@ -84,10 +80,7 @@ __global__ __launch_bounds__(1024) void track_after_pose_kernel(TrackDev D, View
   constexpr int kWalk = 960;
   if (tid == kWalk) {
     const int* pi = reinterpret_cast<const int*>(D.pose_out + 8);
-    RecHeader& H = *D.rec_h[stage];
-    for (int c = 0; c < 7; c++) H.pose_qt[c] = D.pose_out[c];
-    H.chi2 = D.pose_out[7];
-    H.i[RI_INL] = pi[0]; H.i[RI_ITS] = pi[1]; H.i[RI_TRIALS] = pi[2]; H.i[RI_EDGES] = pi[3]; H.i[RI_POINT_EDGES] = pi[4];
+    rec_header_from_pose(*D.rec_h[stage], D.pose_out);
     // pFrame->SetPose(pose) - unless PoseOptimization returned before it optimised (fewer than three points, Optimizer.cc:809-810)
     if (pi[4] >= 3) view_from_pose(D.pose_out, C, D.view, D.line_params, D.pose_qt);
   }
@@ -185,16 +178,6 @@ void state_free(lld_frame* f) {
   f->track = nullptr;
 }
 
-int ensure_work(lld_frame_track_state* S, lld_ctx* ctx, size_t bytes) {
-  if (bytes <= S->work_bytes) return LLD_OK;
-  LLD_HIP_TRY(hipStreamSynchronize(ctx->stream));                // kernels of an earlier stage may still read the old block
-  if (S->d_work) LLD_HIP_TRY(hipFree(S->d_work));
-  S->d_work = nullptr; S->work_bytes = 0;
-  const size_t want = bytes + (bytes >> 2) + 4096;
-  if (hipMalloc(reinterpret_cast<void**>(&S->d_work), want) != hipSuccess) return LLD_ERR_ALLOC;
-  S->work_bytes = want;
-  return LLD_OK;
-}
 int ensure_stage(lld_frame_track_state* S, int s, size_t bytes) {
   if (S->upload_pending[s]) { LLD_HIP_TRY(hipEventSynchronize(S->uploaded[s])); S->upload_pending[s] = false; }   // (long complete: the previous frame's copy)
   if (bytes <= S->h_stage_bytes[s]) return LLD_OK;
@@ -206,117 +189,182 @@ int ensure_stage(lld_frame_track_state* S, int s, size_t bytes) {
   return LLD_OK;
 }
 
-void fill_consts(lld_frame_track_state* S, const lld_frame* f, const lld_track_params* P, const lld_frame_view* view) {
+int stage_begin(lld_frame_track_state* S, lld_ctx* ctx, int s, UploadBlock& B) {
+  if (B.size > S->work_bytes) {                                  // grow-only d_work
+    LLD_HIP_TRY(hipStreamSynchronize(ctx->stream));                // kernels of an earlier stage may still read the old block
+    if (S->d_work) LLD_HIP_TRY(hipFree(S->d_work));
+    S->d_work = nullptr; S->work_bytes = 0;
+    const size_t want = B.size + (B.size >> 2) + 4096;
+    if (hipMalloc(reinterpret_cast<void**>(&S->d_work), want) != hipSuccess) return LLD_ERR_ALLOC;
+    S->work_bytes = want;
+  }
+  const int st = ensure_stage(S, s, B.up_bytes); if (st) return st;
+  B.bind(S->h_stage[s], S->d_work);
+  return LLD_OK;
+}
+int stage_submit(lld_frame_track_state* S, hipStream_t st, int s, const UploadBlock& B) {
+  LLD_HIP_TRY(hipMemcpyAsync(B.d, B.h, B.up_bytes, hipMemcpyHostToDevice, st));
+  LLD_HIP_TRY(hipEventRecord(S->uploaded[s], st)); S->upload_pending[s] = true;
+  return LLD_OK;
+}
+
+void fill_consts(lld_frame_track_state* S, const lld_track_params* P, const lld_frame_view* view) {
   ViewConsts& C = S->consts;
   C.fx = view->fx; C.fy = view->fy; C.cx = view->cx; C.cy = view->cy; C.bf = view->bf;
   C.min_x = view->min_x; C.max_x = view->max_x; C.min_y = view->min_y; C.max_y = view->max_y; C.log_scale_factor = view->log_scale_factor; C.n_levels = view->n_levels;
   C.b = (double)(view->bf / view->fx);                                      // mb = mbf / fx, floats (src/Frame.cc:97)
   C.thr_base = P->line_thr_reproj_base; C.sx = S->sx; C.sy = S->sy; C.monocular = P->monocular; C.use_grid = P->line_use_grid;
-  (void)f;
-}
-
-// the host-side twin of view_from_pose's line camera for stage 1, where the view is the caller's (mVelocity * mLastFrame.mTcw is a float product)
-void line_params_from_view(const ViewConsts& C, const lld_frame_view& V, LineTrackDevParams* L) {
-  std::memset(L, 0, sizeof *L);
-  L->K[0] = (double)C.fx; L->K[2] = (double)C.cx; L->K[4] = (double)C.fy; L->K[5] = (double)C.cy; L->K[8] = 1.0;
-  for (int r = 0; r < 3; r++) { for (int c = 0; c < 3; c++) L->R[3 * r + c] = (double)V.Rcw[3 * c + r]; L->t[r] = (double)V.Ow[r]; }
-  for (int r = 0; r < 3; r++) L->tr[r] = L->t[r] + L->R[3 * r] * C.b;
-  L->thr_base = C.thr_base; L->sx = C.sx; L->sy = C.sy; L->monocular = C.monocular; L->use_grid = C.use_grid;
 }
 
 }  // namespace lld_track
 
 namespace {
 
-// (Re)builds the device state of a frame: keypoint-side arrays, the frame's lines (copied from `L`, may be null: a frame without lines),
-// the records.  Synchronous (it is part of uploading a new frame, like lld_frame_create).
-int state_build(lld_frame* f, const lld_frame_lines* L) {
+// The fresh state f->track points at: keypoint-side arrays, the frame's lines (copied from `L`, may be null: a frame without lines), the records.
+// Synchronous (it is part of uploading a new frame, like lld_frame_create).  An error return leaves it half built: state_build takes it apart.
+int state_fill(lld_frame* f, const lld_frame_lines* L) {
   lld_ctx* ctx = f->ctx;
-  lld_track::state_free(f);
-  lld_frame_track_state* S = new lld_frame_track_state();
-  f->track = S;
+  lld_frame_track_state* S = f->track;
   const int nt = f->nt, nl = L ? L->n_left : 0, nr = L ? L->n_right : 0, dim = L ? L->dim : 1;
   S->nl = nl; S->nr = nr; S->dim = dim; S->sx = L ? L->sx : 1.0; S->sy = L ? L->sy : 1.0;
-  size_t o = 0;
-  auto take = [&](size_t bytes) { const size_t at = o; o += al(bytes); return at; };
-  const size_t o_has = take(nt), o_world = take((size_t)nt * 12), o_id = take((size_t)nt * 4), o_obs = take(nt), o_out = take(nt), o_disc = take((size_t)nt * 4 + 4);
-  const size_t o_lhas = take(nl), o_lx0 = take((size_t)nl * 24), o_ldir = take((size_t)nl * 24), o_lid = take((size_t)nl * 4), o_lout = take(nl);
   const int tracked_cap = 2 * nl + 16;
   S->seen_psize = seen_point_slots(nt); S->seen_lsize = seen_line_slots(nl);
   S->seen_lds = ((size_t)S->seen_psize + S->seen_lsize) * 4;
-  if (S->seen_lds > kSeenLdsMax) { lld_track::state_free(f); return LLD_ERR_UNSUPPORTED; }      // (lld_frame_set_lines refuses such frames first)
-  if (S->seen_lds > 48 * 1024) {
-    // the attribute belongs to the kernel, not to the frame: raised to the budget, so that no frame's setting can shrink another's
-    if (hipFuncSetAttribute(reinterpret_cast<const void*>(&track_mark_seen_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)kSeenLdsMax) != hipSuccess) {
-      lld_track::state_free(f); return LLD_ERR_HIP;
-    }
-  }
-  const size_t o_trk = take((size_t)tracked_cap * 4), o_cnt = take(64), o_pose = take(7 * 8), o_pout = take(12 * 8), o_view = take(sizeof(lld_frame_view)), o_lp = take(sizeof(LineTrackDevParams));
-  const size_t o_ll = take((size_t)nl * 16), o_lo = take((size_t)nl * 4), o_lr = take((size_t)std::max(nr, 1) * 16), o_ro = take((size_t)std::max(nr, 1) * 4), o_lm = take((size_t)nl * 4);
-  const size_t o_ld = take((size_t)nl * dim * 4), o_lc = take((size_t)nl * 4);
-  S->rec_off = o;
-  size_t o_rh[2], o_rk[2], o_rko[2], o_rl[2], o_rlo[2];
-  for (int s = 0; s < 2; s++) { o_rh[s] = take(sizeof(RecHeader)); o_rk[s] = take((size_t)nt * 4); o_rko[s] = take(nt); o_rl[s] = take((size_t)nl * 4); o_rlo[s] = take(nl); }
-  S->rec_bytes = o - S->rec_off;
-  if (hipMalloc(reinterpret_cast<void**>(&S->d_state), o + 256) != hipSuccess) { lld_track::state_free(f); return LLD_ERR_ALLOC; }
-  char* d = S->d_state;
+  if (S->seen_lds > kSeenLdsMax) return LLD_ERR_UNSUPPORTED;                                     // (lld_frame_set_lines refuses such frames first)
+  // the attribute belongs to the kernel, not to the frame: raised to the budget, so that no frame's setting can shrink another's
+  if (S->seen_lds > 48 * 1024 &&
+      hipFuncSetAttribute(reinterpret_cast<const void*>(&track_mark_seen_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)kSeenLdsMax) != hipSuccess) return LLD_ERR_HIP;
+  UploadBlock B;                                     // device only
+  const auto has = B.take<uint8_t>(nt); const auto world = B.take<float>(nt, 3); const auto id = B.take<int32_t>(nt); const auto obs = B.take<uint8_t>(nt), out = B.take<uint8_t>(nt);
+  const auto disc = B.take<int32_t>((size_t)nt + 1); const auto lhas = B.take<uint8_t>(nl); const auto lx0 = B.take<double>(nl, 3), ldir = B.take<double>(nl, 3);
+  const auto lid = B.take<int32_t>(nl); const auto lout = B.take<uint8_t>(nl); const auto trk = B.take<int32_t>(tracked_cap), cnt = B.take<int32_t>(16);   // cnt: n_discard, n_tracked
+  const auto pose = B.take<double>(7), pout = B.take<double>(12); const auto view = B.take<lld_frame_view>(1); const auto lp = B.take<LineTrackDevParams>(1);
+  UploadBlock LB;                                    // the frame's lines, a block of their own inside the state: they arrive in one copy
+  const auto ll = LB.take<float>(nl, 4); const auto lo = LB.take<int32_t>(nl); const auto lr = LB.take<float>(std::max(nr, 1), 4); const auto ro = LB.take<int32_t>(std::max(nr, 1));
+  const auto lm = LB.take<int32_t>(nl); const auto ld = LB.take<float>(nl, dim);
+  LB.end_upload();
+  const auto lc = LB.take<int32_t>(nl); const auto lines = B.take<char>(LB.size);
+  S->rec_off = B.size;
+  Span<RecHeader> rh[2]; Span<int32_t> rk[2], rl[2]; Span<uint8_t> rko[2], rlo[2];
+  for (int s = 0; s < 2; s++) { rh[s] = B.take<RecHeader>(1); rk[s] = B.take<int32_t>(nt); rko[s] = B.take<uint8_t>(nt); rl[s] = B.take<int32_t>(nl); rlo[s] = B.take<uint8_t>(nl); }
+  S->rec_bytes = B.size - S->rec_off;
+  if (hipMalloc(reinterpret_cast<void**>(&S->d_state), B.size + 256) != hipSuccess) { S->d_state = nullptr; return LLD_ERR_ALLOC; }
+  B.bind(nullptr, S->d_state);
   TrackDev& D = S->D;
   D.nt = nt; D.nl = nl; D.nr = nr; D.dim = dim;
-  D.kp_has = reinterpret_cast<uint8_t*>(d + o_has); D.kp_world = reinterpret_cast<float*>(d + o_world); D.kp_id = reinterpret_cast<int32_t*>(d + o_id);
-  D.kp_obs = reinterpret_cast<uint8_t*>(d + o_obs); D.kp_outlier = reinterpret_cast<uint8_t*>(d + o_out);
-  D.discard = reinterpret_cast<int32_t*>(d + o_disc); D.n_discard = reinterpret_cast<int32_t*>(d + o_cnt);
-  D.ln_has = reinterpret_cast<uint8_t*>(d + o_lhas); D.ln_x0 = reinterpret_cast<double*>(d + o_lx0); D.ln_dir = reinterpret_cast<double*>(d + o_ldir);
-  D.ln_id = reinterpret_cast<int32_t*>(d + o_lid); D.ln_outlier = reinterpret_cast<uint8_t*>(d + o_lout);
-  D.tracked = reinterpret_cast<int32_t*>(d + o_trk); D.n_tracked = reinterpret_cast<int32_t*>(d + o_cnt) + 1; D.tracked_cap = tracked_cap;
-  D.pose_qt = reinterpret_cast<double*>(d + o_pose); D.pose_out = reinterpret_cast<double*>(d + o_pout);
-  D.view = reinterpret_cast<lld_frame_view*>(d + o_view); D.line_params = reinterpret_cast<LineTrackDevParams*>(d + o_lp);
-  for (int s = 0; s < 2; s++) {
-    D.rec_h[s] = reinterpret_cast<RecHeader*>(d + o_rh[s]); D.rec_kp_id[s] = reinterpret_cast<int32_t*>(d + o_rk[s]); D.rec_kp_out[s] = reinterpret_cast<uint8_t*>(d + o_rko[s]);
-    D.rec_ln_id[s] = reinterpret_cast<int32_t*>(d + o_rl[s]); D.rec_ln_out[s] = reinterpret_cast<uint8_t*>(d + o_rlo[s]);
-  }
-  S->ln_left = reinterpret_cast<const float*>(d + o_ll); S->ln_loct = reinterpret_cast<const int32_t*>(d + o_lo); S->ln_right = reinterpret_cast<const float*>(d + o_lr);
-  S->ln_roct = reinterpret_cast<const int32_t*>(d + o_ro); S->ln_match = reinterpret_cast<const int32_t*>(d + o_lm); S->ln_desc = reinterpret_cast<const float*>(d + o_ld);
-  S->ln_cell = reinterpret_cast<int32_t*>(d + o_lc);
-  LLD_HIP_TRY(hipMemsetAsync(d, 0, o, ctx->stream));
+  D.kp_has = B.dev(has); D.kp_world = B.dev(world); D.kp_id = B.dev(id); D.kp_obs = B.dev(obs); D.kp_outlier = B.dev(out);
+  D.discard = B.dev(disc); D.n_discard = B.dev(cnt);
+  D.ln_has = B.dev(lhas); D.ln_x0 = B.dev(lx0); D.ln_dir = B.dev(ldir); D.ln_id = B.dev(lid); D.ln_outlier = B.dev(lout);
+  D.tracked = B.dev(trk); D.n_tracked = B.dev(cnt) + 1; D.tracked_cap = tracked_cap;
+  D.pose_qt = B.dev(pose); D.pose_out = B.dev(pout); D.view = B.dev(view); D.line_params = B.dev(lp);
+  for (int s = 0; s < 2; s++) { D.rec_h[s] = B.dev(rh[s]); D.rec_kp_id[s] = B.dev(rk[s]); D.rec_kp_out[s] = B.dev(rko[s]); D.rec_ln_id[s] = B.dev(rl[s]); D.rec_ln_out[s] = B.dev(rlo[s]); }
+  LB.bind(nullptr, B.dev(lines));
+  S->ln_left = LB.dev(ll); S->ln_loct = LB.dev(lo); S->ln_right = LB.dev(lr); S->ln_roct = LB.dev(ro); S->ln_match = LB.dev(lm); S->ln_desc = LB.dev(ld); S->ln_cell = LB.dev(lc);
+  LLD_HIP_TRY(hipMemsetAsync(B.d, 0, B.size, ctx->stream));
   if (nl > 0) {
-    // the lines travel through the context's pinned staging in one copy (synchronous: the staging is the context's)
-    const size_t span = (o_lc) - o_ll;
-    void* hb; int st = lld_ctx_pinned(ctx, span, &hb); if (st) return st;
-    char* h = static_cast<char*>(hb);
-    std::memset(h, 0, span);
-    std::memcpy(h + (o_ll - o_ll), L->left, (size_t)nl * 16); std::memcpy(h + (o_lo - o_ll), L->left_octave, (size_t)nl * 4);
-    if (nr > 0) { std::memcpy(h + (o_lr - o_ll), L->right, (size_t)nr * 16); std::memcpy(h + (o_ro - o_ll), L->right_octave, (size_t)nr * 4); }
-    std::memcpy(h + (o_lm - o_ll), L->line_matches, (size_t)nl * 4); std::memcpy(h + (o_ld - o_ll), L->desc, (size_t)nl * dim * 4);
-    LLD_HIP_TRY(hipMemcpyAsync(d + o_ll, h, span, hipMemcpyHostToDevice, ctx->stream));
-    int st2 = line_cells_dev(ctx->stream, S->ln_left, nl, S->sx, S->sy, S->ln_cell); if (st2) return st2;
+    // the lines travel through the context's pinned staging (synchronous: the staging is the context's)
+    void* hb; int st = lld_ctx_pinned(ctx, LB.up_bytes, &hb); if (st) return st;
+    LB.bind(static_cast<char*>(hb), LB.d);
+    std::memset(LB.h, 0, LB.up_bytes);
+    LB.stage(ll, L->left); LB.stage(lo, L->left_octave);
+    if (nr > 0) { LB.stage(lr, L->right); LB.stage(ro, L->right_octave); }
+    LB.stage(lm, L->line_matches); LB.stage(ld, L->desc);
+    LLD_HIP_TRY(hipMemcpyAsync(LB.d, LB.h, LB.up_bytes, hipMemcpyHostToDevice, ctx->stream));
+    st = line_cells_dev(ctx->stream, S->ln_left, nl, S->sx, S->sy, S->ln_cell); if (st) return st;
   }
   LLD_HIP_TRY(hipStreamSynchronize(ctx->stream));
   for (int s = 0; s < 2; s++) LLD_HIP_TRY(hipEventCreateWithFlags(&S->uploaded[s], hipEventDisableTiming));
   return LLD_OK;
 }
 
-struct LinesUp { size_t x0, dir, x1, x2, skip, desc, id, skip2, matches; };
-
-// lines half of a stage: AddLinesFrom on the uploaded map lines (skip bytes at `d_skip`), then the assignment into the frame
-int run_lines(lld_frame* f, hipStream_t st, const lld_track_params* P, const lld_map_lines* ML, char* d_in, const LinesUp& U, const uint8_t* d_skip, char* d_line_work, int stage) {
-  lld_frame_track_state* S = f->track;
-  const int n_map = ML ? ML->n : 0;
-  if (n_map <= 0 || S->nl <= 0) return LLD_OK;
-  int32_t* d_matches = reinterpret_cast<int32_t*>(d_in + U.matches);
-  LineMapDev M{n_map, reinterpret_cast<const double*>(d_in + U.x0), reinterpret_cast<const double*>(d_in + U.dir), reinterpret_cast<const double*>(d_in + U.x1),
-               reinterpret_cast<const double*>(d_in + U.x2), d_skip, reinterpret_cast<const float*>(d_in + U.desc)};
-  LineFrameDev Cur{S->nl, S->ln_left, S->ln_loct, S->ln_right, S->ln_match, S->D.ln_has, S->ln_cell, S->ln_desc, S->dim};
-  const LineApplyDev ap{S->D.ln_has, S->D.ln_x0, S->D.ln_dir, S->D.ln_id, S->D.tracked, S->D.n_tracked, S->D.tracked_cap, reinterpret_cast<const int32_t*>(d_in + U.id)};
-  (void)stage;
-  return line_track_launch_dev(f->ctx, st, S->D.line_params, M, Cur, P->line_md_thr, d_line_work, d_matches, ap);
+// (Re)builds the device state of a frame.  Every failure leaves the frame without one (hipFree waits for what state_fill queued on the block).
+int state_build(lld_frame* f, const lld_frame_lines* L) {
+  lld_track::state_free(f);
+  f->track = new lld_frame_track_state();
+  const int st = state_fill(f, L);
+  if (st) lld_track::state_free(f);
+  return st;
 }
 
-int run_pose(lld_frame* f, hipStream_t st, const lld_track_params* P, char* d_pose_work, int stage) {
+// The map lines of a stage (the last frame's, the local map's), then AddLinesFrom's matches behind the uploaded prefix.
+struct LinesUp {
+  int n = 0; Span<double> x0, dir, x1, x2; Span<uint8_t> skip; Span<float> desc; Span<int32_t> id, matches;
+  void reserve(UploadBlock& B, int n_map, int dim) {
+    n = n_map; x0 = B.take<double>(n, 3); dir = B.take<double>(n, 3); x1 = B.take<double>(n, 3); x2 = B.take<double>(n, 3);
+    skip = B.take<uint8_t>(n); desc = B.take<float>(n, dim); id = B.take<int32_t>(n);
+  }
+  void reserve_scratch(UploadBlock& B) { matches = B.take<int32_t>(std::max(n, 1)); }
+  void stage(const UploadBlock& B, const lld_map_lines* ML) const {
+    if (!n) return;
+    B.stage(x0, ML->x0); B.stage(dir, ML->dir); B.stage(x1, ML->x1); B.stage(x2, ML->x2); B.stage(skip, ML->skip, 0); B.stage(desc, ML->desc); B.stage(id, ML->id);
+  }
+  LineMapDev dev(const UploadBlock& B, const uint8_t* d_skip) const { return {n, B.dev(x0), B.dev(dir), B.dev(x1), B.dev(x2), d_skip, B.dev(desc)}; }
+};
+
+// mLastFrame's MapPoints as TrackWithMotionModel's SearchByProjection reads them, their descriptors and the caller's ids.
+struct LastPointsUp {
+  Span<float> pos, ang; Span<uint8_t> val, obs; Span<int32_t> oct, id; Span<uint32_t> desc;
+  void reserve(UploadBlock& B, int nq) {
+    pos = B.take<float>(nq, 3); val = B.take<uint8_t>(nq); oct = B.take<int32_t>(nq); ang = B.take<float>(nq); obs = B.take<uint8_t>(nq);
+    desc = B.take<uint32_t>(nq, 8); id = B.take<int32_t>(nq);
+  }
+  void stage(const UploadBlock& B, const lld_last_frame_points* last, const int32_t* ids) const {
+    B.stage(pos, last->world_pos); B.stage(val, last->valid); B.stage(oct, last->octave); B.stage(ang, last->angle, 0); B.stage(obs, last->has_obs, 1); B.stage(desc, last->desc); B.stage(id, ids);
+  }
+  LastFrameDev dev(const UploadBlock& B) const { return {(int)val.n, B.dev(pos), B.dev(val), B.dev(oct), B.dev(ang), B.dev(obs)}; }
+};
+
+// The local map's MapPoints as SearchLocalPoints reads them; skip2 (device only) = the caller's skip bytes or "already seen in this frame".
+struct LocalPointsUp {
+  Span<float> pos, nrm, maxd, mind; Span<uint8_t> obs, skip, skip2; Span<uint32_t> desc; Span<int32_t> id;
+  void reserve(UploadBlock& B, int nq) {
+    pos = B.take<float>(nq, 3); nrm = B.take<float>(nq, 3); maxd = B.take<float>(nq); mind = B.take<float>(nq); obs = B.take<uint8_t>(nq); skip = B.take<uint8_t>(nq);
+    desc = B.take<uint32_t>(nq, 8); id = B.take<int32_t>(nq);
+  }
+  void reserve_scratch(UploadBlock& B) { skip2 = B.take<uint8_t>(skip.n); }
+  void stage(const UploadBlock& B, const lld_map_points* mp, const int32_t* ids) const {
+    B.stage(pos, mp->world_pos); B.stage(nrm, mp->normal); B.stage(maxd, mp->max_distance); B.stage(mind, mp->min_distance);
+    B.stage(obs, mp->has_obs, 1); B.stage(skip, mp->skip, 0); B.stage(desc, mp->desc); B.stage(id, ids);
+  }
+  MapPointsDev dev(const UploadBlock& B) const { return {(int)skip.n, B.dev(pos), B.dev(nrm), B.dev(maxd), B.dev(mind), B.dev(obs), B.dev(skip2)}; }
+};
+
+// What a stage 1 that ran elsewhere left in the frame (lld_frame_held); trk: the held lines' ids, then the caller's further tracked ones.
+struct HeldUp {
+  int nl = 0, n_seen = 0, n_trk = 0; Span<int32_t> id, seen, lid, trk; Span<float> w; Span<uint8_t> obs, out, lout; Span<double> lx0, ldir;
+  void reserve(UploadBlock& B, int nt, int nl_, int n_seen_, int n_trk_) {
+    nl = nl_; n_seen = n_seen_; n_trk = n_trk_;
+    id = B.take<int32_t>(nt); w = B.take<float>(nt, 3); obs = B.take<uint8_t>(nt); out = B.take<uint8_t>(nt); seen = B.take<int32_t>(std::max(n_seen, 1));
+    lid = B.take<int32_t>(nl); lx0 = B.take<double>(nl, 3); ldir = B.take<double>(nl, 3); lout = B.take<uint8_t>(nl); trk = B.take<int32_t>(std::max(n_trk, 1));
+  }
+  void stage(const UploadBlock& B, const lld_frame_held* held) const {
+    B.stage(id, held->kp_point_id); B.stage(w, held->kp_world_pos); B.stage(obs, held->kp_has_obs, 1); B.stage(out, held->kp_outlier, 0);
+    if (n_seen) B.stage(seen, held->seen_point_id);
+    if (!nl) return;
+    const int32_t* lines = held->ln_line_id;                                  // null: the frame holds no lines (every id -1)
+    B.stage(lid, lines, 0xff); B.stage(lx0, lines ? held->ln_x0 : nullptr, 0); B.stage(ldir, lines ? held->ln_dir : nullptr, 0); B.stage(lout, held->ln_outlier, 0);
+    int32_t* t = B.host(trk); int at = 0;
+    if (lines) for (int i = 0; i < nl; i++) if (lines[i] >= 0) t[at++] = lines[i];                     // a line the frame holds was tracked by it (tracked_last_id, :1117)
+    for (int k = 0; k < held->n_tracked; k++) t[at++] = held->tracked_line_id[k];
+  }
+  HeldDev dev(const UploadBlock& B) const { return {B.dev(id), B.dev(w), B.dev(obs), B.dev(out), B.dev(seen), n_seen, B.dev(lid), B.dev(lx0), B.dev(ldir), B.dev(lout), B.dev(trk), nl ? n_trk : 0}; }
+};
+
+// lines half of a stage: AddLinesFrom on the uploaded map lines (skip bytes at `d_skip`), then the assignment into the frame
+int run_lines(lld_frame* f, hipStream_t st, const lld_track_params* P, const UploadBlock& B, const LinesUp& U, const uint8_t* d_skip, void* d_line_work) {
   lld_frame_track_state* S = f->track;
+  if (U.n <= 0 || S->nl <= 0) return LLD_OK;
+  LineFrameDev Cur{S->nl, S->ln_left, S->ln_loct, S->ln_right, S->ln_match, S->D.ln_has, S->ln_cell, S->ln_desc, S->dim};
+  const LineApplyDev ap{S->D.ln_has, S->D.ln_x0, S->D.ln_dir, S->D.ln_id, S->D.tracked, S->D.n_tracked, S->D.tracked_cap, B.dev(U.id)};
+  return line_track_launch_dev(f->ctx, st, S->D.line_params, U.dev(B, d_skip), Cur, P->line_md_thr, d_line_work, B.dev(U.matches), ap);
+}
+
+int run_pose(lld_frame* f, hipStream_t st, const lld_track_params* P, void* d_pose_work, int stage) {
+  lld_frame_track_state* S = f->track;
+  const KeypointsDev K = resident_keypoints(f, false);
   PoseTrackDev in{};
   in.nt = f->nt; in.nl = S->nl;
-  in.t_xy = reinterpret_cast<const float*>(f->d + f->o_txy); in.t_uright = f->has_uright ? reinterpret_cast<const float*>(f->d + f->o_tur) : nullptr;
-  in.t_octave = reinterpret_cast<const int32_t*>(f->d + f->o_toct);
+  in.t_xy = K.xy; in.t_uright = K.uright; in.t_octave = K.octave;
   in.kp_has = S->D.kp_has; in.kp_world = S->D.kp_world;
   in.ln_left = S->ln_left; in.ln_loct = S->ln_loct; in.ln_right = S->ln_right; in.ln_roct = S->ln_roct; in.ln_match = S->ln_match;
   in.ln_has = S->D.ln_has; in.ln_x0 = S->D.ln_x0; in.ln_dir = S->D.ln_dir;
@@ -329,25 +377,9 @@ int run_pose(lld_frame* f, hipStream_t st, const lld_track_params* P, char* d_po
   return LLD_OK;
 }
 
-int check_lines(const lld_frame_track_state* S, const lld_map_lines* ML) {
+int check_lines(const lld_map_lines* ML) {
   if (!ML || ML->n == 0) return LLD_OK;
-  if (ML->n < 0 || !ML->x0 || !ML->dir || !ML->x1 || !ML->x2 || !ML->desc || !ML->id) return LLD_ERR_INVALID;
-  (void)S;
-  return LLD_OK;
-}
-
-size_t lay_lines(size_t& o, int n_map, int dim, LinesUp* U, size_t* dev_only) {
-  auto take = [&](size_t bytes) { const size_t at = o; o += al(bytes); return at; };
-  U->x0 = take((size_t)n_map * 24); U->dir = take((size_t)n_map * 24); U->x1 = take((size_t)n_map * 24); U->x2 = take((size_t)n_map * 24);
-  U->skip = take(n_map); U->desc = take((size_t)n_map * dim * 4); U->id = take((size_t)n_map * 4);
-  (void)dev_only;
-  return o;
-}
-void pack_lines(char* h, const LinesUp& U, const lld_map_lines* ML, int dim) {
-  const size_t n = ML->n;
-  std::memcpy(h + U.x0, ML->x0, n * 24); std::memcpy(h + U.dir, ML->dir, n * 24); std::memcpy(h + U.x1, ML->x1, n * 24); std::memcpy(h + U.x2, ML->x2, n * 24);
-  if (ML->skip) std::memcpy(h + U.skip, ML->skip, n); else std::memset(h + U.skip, 0, n);
-  std::memcpy(h + U.desc, ML->desc, n * dim * 4); std::memcpy(h + U.id, ML->id, n * 4);
+  return (ML->n < 0 || !ML->x0 || !ML->dir || !ML->x1 || !ML->x2 || !ML->desc || !ML->id) ? LLD_ERR_INVALID : LLD_OK;
 }
 
 }  // namespace
@@ -372,9 +404,9 @@ int ref_keyframe_check(const lld_ref_keyframe* kf, int* n_features) {
   }
   return LLD_OK;
 }
-int track_reset_launch(hipStream_t st, lld_frame_track_state* S, const double* pose_d, const lld_frame_view* view_d, const LineTrackDevParams* lp_d) {
+int track_reset_launch(hipStream_t st, lld_frame_track_state* S, const UploadBlock& B, const StageHeader& H) {
   const int nmax = std::max(std::max(S->D.nt, S->nl), 64);
-  hipLaunchKernelGGL(track_reset_kernel, dim3((nmax + 255) / 256), dim3(256), 0, st, S->D, pose_d, view_d, lp_d);
+  hipLaunchKernelGGL(track_reset_kernel, dim3((nmax + 255) / 256), dim3(256), 0, st, S->D, B.dev(H.pose), B.dev(H.view), B.dev(H.lp));
   LLD_HIP_TRY(hipGetLastError());
   return LLD_OK;
 }
@@ -421,64 +453,42 @@ int lld_frame_track_motion_model(lld_frame* f, const lld_track_params* P, const 
   LLD_HIP_TRY(hipSetDevice(ctx->device));
   int s = ensure_state(f); if (s) return s;
   lld_frame_track_state* S = f->track;
-  s = check_lines(S, last_lines); if (s) return s;
+  s = check_lines(last_lines); if (s) return s;
   const int n_map = (last_lines && S->nl > 0) ? last_lines->n : 0;
-  fill_consts(S, f, P, view);
+  fill_consts(S, P, view);
   // ---- layout of the uploaded block, then the device-only scratch behind it
-  size_t o = 0;
-  auto take = [&](size_t bytes) { const size_t at = o; o += al(bytes); return at; };
-  const size_t o_prob1 = take(orbs_problem_bytes()), o_prob2 = take(orbs_problem_bytes());
-  const size_t o_pose = take(7 * 8), o_lp = take(sizeof(LineTrackDevParams)), o_view = take(sizeof(lld_frame_view));
-  const size_t o_pos = take((size_t)nq * 12), o_val = take(nq), o_oct = take((size_t)nq * 4), o_ang = take((size_t)nq * 4), o_obs = take(nq), o_desc = take((size_t)nq * 32), o_id = take((size_t)nq * 4);
-  LinesUp U{}; lay_lines(o, n_map, S->dim, &U, nullptr);
-  const size_t up_bytes = o;
-  U.matches = take((size_t)std::max(n_map, 1) * 4);
-  size_t o_so[2][6];
-  for (int k = 0; k < 2; k++) { o_so[k][0] = take((size_t)nq * 4); o_so[k][1] = take((size_t)nq * 4); o_so[k][2] = take((size_t)nq * 4); o_so[k][3] = take(nq); o_so[k][4] = take((size_t)nt * 4); o_so[k][5] = take(16); }
-  const size_t o_qrec = take(orbs_qrec_bytes(nq)), o_cache = take(orbs_cache_bytes(nq));
-  const size_t o_lwork = take(line_track_work_bytes(n_map, S->nl)), o_pwork = take(pose_track_work_bytes(nt, S->nl));
-  s = ensure_work(S, ctx, o); if (s) return s;
-  s = ensure_stage(S, 0, up_bytes); if (s) return s;
-  char* h = S->h_stage[0]; char* d = S->d_work;
+  UploadBlock B; StageHeader H; LastPointsUp LP; LinesUp U; SearchScratch sc[2];
+  const auto prob1 = B.take<char>(orbs_problem_bytes()), prob2 = B.take<char>(orbs_problem_bytes());
+  H.reserve(B); LP.reserve(B, nq); U.reserve(B, n_map, S->dim);
+  B.end_upload();
+  U.reserve_scratch(B);
+  sc[0].reserve(B, nq, nt); sc[1].reserve(B, nq, nt, &sc[0]);
+  const auto lwork = B.take<char>(line_track_work_bytes(n_map, S->nl)), pwork = B.take<char>(pose_track_work_bytes(nt, S->nl));
+  s = stage_begin(S, ctx, 0, B); if (s) return s;
   // ---- pack
-  if (nq) {
-    std::memcpy(h + o_pos, last->world_pos, (size_t)nq * 12); std::memcpy(h + o_val, last->valid, nq); std::memcpy(h + o_oct, last->octave, (size_t)nq * 4);
-    if (last->angle) std::memcpy(h + o_ang, last->angle, (size_t)nq * 4); else std::memset(h + o_ang, 0, (size_t)nq * 4);
-    if (last->has_obs) std::memcpy(h + o_obs, last->has_obs, nq); else std::memset(h + o_obs, 1, nq);
-    std::memcpy(h + o_desc, last->desc, (size_t)nq * 32); std::memcpy(h + o_id, last_point_id, (size_t)nq * 4);
-  }
-  if (n_map) pack_lines(h, U, last_lines, S->dim);
-  std::memcpy(h + o_pose, pose_qt, 7 * 8);
-  line_params_from_view(S->consts, *view, reinterpret_cast<LineTrackDevParams*>(h + o_lp));
-  std::memcpy(h + o_view, view, sizeof(lld_frame_view));
-  SearchOut so[2];
-  for (int k = 0; k < 2; k++)
-    so[k] = SearchOut{reinterpret_cast<int32_t*>(d + o_so[k][0]), reinterpret_cast<int32_t*>(d + o_so[k][1]), reinterpret_cast<int32_t*>(d + o_so[k][2]),
-                      reinterpret_cast<uint8_t*>(d + o_so[k][3]), reinterpret_cast<int32_t*>(d + o_so[k][4]), reinterpret_cast<int32_t*>(d + o_so[k][5])};
+  LP.stage(B, last, last_point_id); U.stage(B, last_lines); H.stage(B, S->consts, view, pose_qt);
+  const SearchOut so[2] = {sc[0].out(B), sc[1].out(B)};
   const bool wide = P->wide_retry != 0;
   const RunIf gate{so[0].summary, 20, 1};                                     // if(nmatches<20) (src/Tracking.cc:907)
-  const LastFrameDev LF{nq, reinterpret_cast<const float*>(d + o_pos), reinterpret_cast<const uint8_t*>(d + o_val), reinterpret_cast<const int32_t*>(d + o_oct),
-                        reinterpret_cast<const float*>(d + o_ang), reinterpret_cast<const uint8_t*>(d + o_obs)};
+  const LastFrameDev LF = LP.dev(B);
   int32_t* counts = S->D.rec_h[0]->i + RI_SEARCH1;                            // RI_SEARCH1, RI_SEARCH, RI_WIDE are consecutive
-  ApplyDev ap{S->D.kp_has, S->D.kp_world, S->D.kp_id, S->D.kp_obs, LF.pos, reinterpret_cast<const int32_t*>(d + o_id), LF.has_obs, counts, wide ? 20 : 0, 0};
-  orbs_fill_problem(f, 0, nq, S->D.kp_has, d + o_qrec, reinterpret_cast<const uint32_t*>(d + o_desc), so[0], d + o_cache, 0.f, P->check_orientation, RunIf{}, ap, h + o_prob1);
+  ApplyDev ap{S->D.kp_has, S->D.kp_world, S->D.kp_id, S->D.kp_obs, LF.pos, B.dev(LP.id), LF.has_obs, counts, wide ? 20 : 0, 0};
+  char* qrec = B.dev(sc[0].qrec);
+  orbs_fill_problem(f, 0, nq, S->D.kp_has, qrec, B.dev(LP.desc), so[0], B.dev(sc[0].cache), 0.f, P->check_orientation, RunIf{}, ap, B.host(prob1));
   ap.min_matches = 0; ap.is_retry = 1;
-  orbs_fill_problem(f, 0, nq, S->D.kp_has, d + o_qrec, reinterpret_cast<const uint32_t*>(d + o_desc), so[1], d + o_cache, 0.f, P->check_orientation, gate, ap, h + o_prob2);
+  orbs_fill_problem(f, 0, nq, S->D.kp_has, qrec, B.dev(LP.desc), so[1], B.dev(sc[0].cache), 0.f, P->check_orientation, gate, ap, B.host(prob2));
   hipStream_t st = ctx->stream;
-  LLD_HIP_TRY(hipMemcpyAsync(d, h, up_bytes, hipMemcpyHostToDevice, st));
-  LLD_HIP_TRY(hipEventRecord(S->uploaded[0], st)); S->upload_pending[0] = true;
+  s = stage_submit(S, st, 0, B); if (s) return s;
   // ---- kernels
-  const int nmax = std::max(std::max(nt, S->nl), 64);
-  hipLaunchKernelGGL(track_reset_kernel, dim3((nmax + 255) / 256), dim3(256), 0, st, S->D, reinterpret_cast<const double*>(d + o_pose),
-                     reinterpret_cast<const lld_frame_view*>(d + o_view), reinterpret_cast<const LineTrackDevParams*>(d + o_lp));
-  s = orbs_project_last_frame(st, f->consts, view, nullptr, LF, P->direction, P->th_motion, d + o_qrec, nullptr, RunIf{}); if (s) return s;
-  s = orbs_launch_n(ctx, st, f, d + o_prob1, 1); if (s) return s;
+  s = track_reset_launch(st, S, B, H); if (s) return s;
+  s = orbs_project_last_frame(st, f->consts, view, nullptr, LF, P->direction, P->th_motion, qrec, nullptr, RunIf{}); if (s) return s;
+  s = orbs_launch_n(ctx, st, f, B.dev(prob1), 1); if (s) return s;
   if (wide) {
-    s = orbs_project_last_frame(st, f->consts, view, nullptr, LF, P->direction, 2.f * P->th_motion, d + o_qrec, nullptr, gate); if (s) return s;
-    s = orbs_launch_n(ctx, st, f, d + o_prob2, 1); if (s) return s;
+    s = orbs_project_last_frame(st, f->consts, view, nullptr, LF, P->direction, 2.f * P->th_motion, qrec, nullptr, gate); if (s) return s;
+    s = orbs_launch_n(ctx, st, f, B.dev(prob2), 1); if (s) return s;
   }
-  s = run_lines(f, st, P, n_map ? last_lines : nullptr, d, U, reinterpret_cast<const uint8_t*>(d + U.skip), d + o_lwork, 0); if (s) return s;
-  s = run_pose(f, st, P, d + o_pwork, 0); if (s) return s;
+  s = run_lines(f, st, P, B, U, B.dev(U.skip), B.dev(lwork)); if (s) return s;
+  s = run_pose(f, st, P, B.dev(pwork), 0); if (s) return s;
   S->stage1_queued = true; S->n_in_view = 0;
   return LLD_OK;
 }
@@ -489,7 +499,7 @@ int lld_frame_track_motion_model(lld_frame* f, const lld_track_params* P, const 
 int lld_frame_track_reference_keyframe(lld_frame* f, const lld_track_params* P, const lld_frame_view* view, const double* pose_qt, const lld_ref_keyframe* kf) {
   if (!f || !P || !view || !pose_qt || !kf) return LLD_ERR_INVALID;
   if (!f->has_bow) return LLD_ERR_INVALID;                                     // Frame::ComputeBoW comes first (:776)
-  const int n = kf->n, nn = kf->n_nodes, nt = f->nt;
+  const int nt = f->nt;
   int nv = 0;
   if (int st = ref_keyframe_check(kf, &nv)) return st;
   if (nt > 0 && !f->has_angle) return LLD_ERR_INVALID;                         // ORBmatcher(0.7, true): mbCheckOrientation
@@ -499,46 +509,25 @@ int lld_frame_track_reference_keyframe(lld_frame* f, const lld_track_params* P, 
   LLD_HIP_TRY(hipSetDevice(ctx->device));
   int s = ensure_state(f); if (s) return s;
   lld_frame_track_state* S = f->track;
-  fill_consts(S, f, P, view);
-  size_t o = 0;
-  auto take = [&](size_t bytes) { const size_t at = o; o += al(bytes); return at; };
-  const size_t o_pose = take(7 * 8), o_lp = take(sizeof(LineTrackDevParams)), o_view = take(sizeof(lld_frame_view));
-  const size_t o_desc = take((size_t)n * 32), o_ang = take((size_t)n * 4), o_id = take((size_t)n * 4), o_pos = take((size_t)n * 12), o_obs = take(n);
-  const size_t o_node = take((size_t)nn * 4), o_start = take((size_t)(nn + 1) * 4), o_feat = take((size_t)nv * 4);
-  const size_t up_bytes = o;
-  const size_t o_taken = take((size_t)nt * 4), o_pwork = take(pose_track_work_bytes(nt, S->nl));
-  s = ensure_work(S, ctx, o); if (s) return s;
-  s = ensure_stage(S, 0, up_bytes); if (s) return s;
-  char* h = S->h_stage[0]; char* d = S->d_work;
-  std::memcpy(h + o_pose, pose_qt, 7 * 8);
-  line_params_from_view(S->consts, *view, reinterpret_cast<LineTrackDevParams*>(h + o_lp));
-  std::memcpy(h + o_view, view, sizeof(lld_frame_view));
-  if (n) {
-    std::memcpy(h + o_desc, kf->desc, (size_t)n * 32); std::memcpy(h + o_ang, kf->angle, (size_t)n * 4); std::memcpy(h + o_id, kf->point_id, (size_t)n * 4);
-    std::memcpy(h + o_pos, kf->world_pos, (size_t)n * 12);
-    if (kf->has_obs) std::memcpy(h + o_obs, kf->has_obs, n); else std::memset(h + o_obs, 1, n);
-  }
-  if (nn) { std::memcpy(h + o_node, kf->node, (size_t)nn * 4); std::memcpy(h + o_start, kf->node_start, (size_t)(nn + 1) * 4); }
-  else std::memset(h + o_start, 0, 4);
-  if (nv) std::memcpy(h + o_feat, kf->feature, (size_t)nv * 4);
+  fill_consts(S, P, view);
+  UploadBlock B; StageHeader H; RefKeyframeUp KF;
+  H.reserve(B); KF.reserve(B, *kf, nv);
+  B.end_upload();
+  const auto taken = B.take<int32_t>(nt); const auto pwork = B.take<char>(pose_track_work_bytes(nt, S->nl));
+  s = stage_begin(S, ctx, 0, B); if (s) return s;
+  H.stage(B, S->consts, view, pose_qt); KF.stage(B, *kf);
   hipStream_t st = ctx->stream;
-  LLD_HIP_TRY(hipMemcpyAsync(d, h, up_bytes, hipMemcpyHostToDevice, st));
-  LLD_HIP_TRY(hipEventRecord(S->uploaded[0], st)); S->upload_pending[0] = true;
-  const int nmax = std::max(std::max(nt, S->nl), 64);
-  hipLaunchKernelGGL(track_reset_kernel, dim3((nmax + 255) / 256), dim3(256), 0, st, S->D, reinterpret_cast<const double*>(d + o_pose),
-                     reinterpret_cast<const lld_frame_view*>(d + o_view), reinterpret_cast<const LineTrackDevParams*>(d + o_lp));
-  BowSearchDev B{};
-  B.nt = nt; B.n_kf_nodes = nn;
-  B.f_desc = reinterpret_cast<const uint32_t*>(f->d + f->o_td); B.f_angle = reinterpret_cast<const float*>(f->d + f->o_tang);
-  B.f_n_nodes = f->bow_n_nodes(); B.f_node = f->bow_node(); B.f_node_start = f->bow_node_start(); B.f_feature = f->bow_feature();
-  B.kf_desc = reinterpret_cast<const uint32_t*>(d + o_desc); B.kf_angle = reinterpret_cast<const float*>(d + o_ang); B.kf_point_id = reinterpret_cast<const int32_t*>(d + o_id);
-  B.kf_node = reinterpret_cast<const int32_t*>(d + o_node); B.kf_node_start = reinterpret_cast<const int32_t*>(d + o_start); B.kf_feature = reinterpret_cast<const int32_t*>(d + o_feat);
-  B.nnratio = 0.7f; B.check_orientation = 1;                                   // ORBmatcher matcher(0.7,true) (:780)
-  B.taken = reinterpret_cast<int32_t*>(d + o_taken);
-  const ApplyDev ap{S->D.kp_has, S->D.kp_world, S->D.kp_id, S->D.kp_obs, reinterpret_cast<const float*>(d + o_pos), B.kf_point_id,
-                    reinterpret_cast<const uint8_t*>(d + o_obs), S->D.rec_h[0]->i + RI_SEARCH1, 0, 0};
-  s = bow_search_launch(st, B, ap); if (s) return s;
-  s = run_pose(f, st, P, d + o_pwork, 0); if (s) return s;                     // (no AddLinesFrom: track_reset_kernel left the line tables empty)
+  s = stage_submit(S, st, 0, B); if (s) return s;
+  s = track_reset_launch(st, S, B, H); if (s) return s;
+  BowSearchDev Bs{};
+  bow_frame_side(f, Bs);
+  Bs.n_kf_nodes = kf->n_nodes;
+  const RefKeyframeUp::Query q = KF.dev(B, Bs);
+  Bs.nnratio = 0.7f; Bs.check_orientation = 1;                                 // ORBmatcher matcher(0.7,true) (:780)
+  Bs.taken = B.dev(taken);
+  const ApplyDev ap{S->D.kp_has, S->D.kp_world, S->D.kp_id, S->D.kp_obs, q.pos, q.id, q.obs, S->D.rec_h[0]->i + RI_SEARCH1, 0, 0};
+  s = bow_search_launch(st, Bs, ap); if (s) return s;
+  s = run_pose(f, st, P, B.dev(pwork), 0); if (s) return s;                    // (no AddLinesFrom: track_reset_launch left the line tables empty)
   S->stage1_queued = true; S->n_in_view = 0;
   return LLD_OK;
 }
@@ -561,45 +550,17 @@ int lld_frame_track_set_state(lld_frame* f, const lld_track_params* P, const lld
   if (held->n_tracked < 0 || (held->n_tracked > 0 && !held->tracked_line_id) || n_held_lines + held->n_tracked > S->D.tracked_cap - nl) return LLD_ERR_INVALID;
   for (int k = 0; k < held->n_seen; k++) if (held->seen_point_id[k] < 0) return LLD_ERR_INVALID;
   for (int k = 0; k < held->n_tracked; k++) if (held->tracked_line_id[k] < 0) return LLD_ERR_INVALID;
-  fill_consts(S, f, P, view);
-  size_t o = 0;
-  auto take = [&](size_t bytes) { const size_t at = o; o += al(bytes); return at; };
+  fill_consts(S, P, view);
   const int n_trk = n_held_lines + held->n_tracked;
-  const size_t o_pose = take(7 * 8), o_lp = take(sizeof(LineTrackDevParams)), o_view = take(sizeof(lld_frame_view));
-  const size_t o_id = take((size_t)nt * 4), o_w = take((size_t)nt * 12), o_obs = take(nt), o_out = take(nt), o_seen = take((size_t)std::max(held->n_seen, 1) * 4);
-  const size_t o_lid = take((size_t)nl * 4), o_lx0 = take((size_t)nl * 24), o_ldir = take((size_t)nl * 24), o_lout = take(nl), o_trk = take((size_t)std::max(n_trk, 1) * 4);
-  s = ensure_work(S, ctx, o); if (s) return s;
-  s = ensure_stage(S, 0, o); if (s) return s;
-  char* h = S->h_stage[0]; char* d = S->d_work;
-  std::memcpy(h + o_pose, pose_qt, 7 * 8);
-  line_params_from_view(S->consts, *view, reinterpret_cast<LineTrackDevParams*>(h + o_lp));
-  std::memcpy(h + o_view, view, sizeof(lld_frame_view));
-  if (nt) {
-    std::memcpy(h + o_id, held->kp_point_id, (size_t)nt * 4); std::memcpy(h + o_w, held->kp_world_pos, (size_t)nt * 12);
-    if (held->kp_has_obs) std::memcpy(h + o_obs, held->kp_has_obs, nt); else std::memset(h + o_obs, 1, nt);
-    if (held->kp_outlier) std::memcpy(h + o_out, held->kp_outlier, nt); else std::memset(h + o_out, 0, nt);
-  }
-  if (held->n_seen) std::memcpy(h + o_seen, held->seen_point_id, (size_t)held->n_seen * 4);
-  if (nl) {
-    int32_t* trk = reinterpret_cast<int32_t*>(h + o_trk); int at = 0;
-    if (held->ln_line_id) {
-      std::memcpy(h + o_lid, held->ln_line_id, (size_t)nl * 4); std::memcpy(h + o_lx0, held->ln_x0, (size_t)nl * 24); std::memcpy(h + o_ldir, held->ln_dir, (size_t)nl * 24);
-      for (int i = 0; i < nl; i++) if (held->ln_line_id[i] >= 0) trk[at++] = held->ln_line_id[i];      // a line the frame holds was tracked by it (tracked_last_id, :1117)
-    } else {
-      std::memset(h + o_lid, 0xff, (size_t)nl * 4); std::memset(h + o_lx0, 0, (size_t)nl * 24); std::memset(h + o_ldir, 0, (size_t)nl * 24);
-    }
-    if (held->ln_outlier) std::memcpy(h + o_lout, held->ln_outlier, nl); else std::memset(h + o_lout, 0, nl);
-    for (int k = 0; k < held->n_tracked; k++) trk[at++] = held->tracked_line_id[k];
-  }
+  UploadBlock B; StageHeader H; HeldUp U;
+  H.reserve(B); U.reserve(B, nt, nl, held->n_seen, n_trk);
+  B.end_upload();                                                              // everything travels
+  s = stage_begin(S, ctx, 0, B); if (s) return s;
+  H.stage(B, S->consts, view, pose_qt); U.stage(B, held);
   hipStream_t st = ctx->stream;
-  LLD_HIP_TRY(hipMemcpyAsync(d, h, o, hipMemcpyHostToDevice, st));
-  LLD_HIP_TRY(hipEventRecord(S->uploaded[0], st)); S->upload_pending[0] = true;
-  const HeldUp U{reinterpret_cast<const int32_t*>(d + o_id), reinterpret_cast<const float*>(d + o_w), reinterpret_cast<const uint8_t*>(d + o_obs), reinterpret_cast<const uint8_t*>(d + o_out),
-                 reinterpret_cast<const int32_t*>(d + o_seen), held->n_seen, reinterpret_cast<const int32_t*>(d + o_lid), reinterpret_cast<const double*>(d + o_lx0),
-                 reinterpret_cast<const double*>(d + o_ldir), reinterpret_cast<const uint8_t*>(d + o_lout), reinterpret_cast<const int32_t*>(d + o_trk), nl ? n_trk : 0};
+  s = stage_submit(S, st, 0, B); if (s) return s;
   const int nmax = std::max(std::max(std::max(nt, nl), n_trk), 64);
-  hipLaunchKernelGGL(track_load_kernel, dim3((nmax + 255) / 256), dim3(256), 0, st, S->D, U, reinterpret_cast<const double*>(d + o_pose),
-                     reinterpret_cast<const lld_frame_view*>(d + o_view), reinterpret_cast<const LineTrackDevParams*>(d + o_lp));
+  hipLaunchKernelGGL(track_load_kernel, dim3((nmax + 255) / 256), dim3(256), 0, st, S->D, U.dev(B), B.dev(H.pose), B.dev(H.view), B.dev(H.lp));
   LLD_HIP_TRY(hipGetLastError());
   S->stage1_queued = true; S->n_in_view = 0;
   return LLD_OK;
@@ -613,54 +574,35 @@ int lld_frame_track_local_map(lld_frame* f, const lld_track_params* P, const lld
   if (nq < 0 || (nq > 0 && (!mp->world_pos || !mp->normal || !mp->max_distance || !mp->min_distance || !mp->desc || !point_id))) return LLD_ERR_INVALID;
   lld_ctx* ctx = f->ctx;
   LLD_HIP_TRY(hipSetDevice(ctx->device));
-  int s = check_lines(S, local_lines); if (s) return s;
+  int s = check_lines(local_lines); if (s) return s;
   const int n_map = (local_lines && S->nl > 0) ? local_lines->n : 0;
-  size_t o = 0;
-  auto take = [&](size_t bytes) { const size_t at = o; o += al(bytes); return at; };
-  // stage 2 reuses the work block from its start: stage 1's kernels are queued before this upload on the same stream, and ensure_work
+  // stage 2 reuses the work block from its start: stage 1's kernels are queued before this upload on the same stream, and stage_begin
   // synchronises the stream before it grows the block
-  const size_t o_prob = take(orbs_problem_bytes());
-  const size_t o_pos = take((size_t)nq * 12), o_nrm = take((size_t)nq * 12), o_maxd = take((size_t)nq * 4), o_mind = take((size_t)nq * 4), o_obs = take(nq), o_skip = take(nq);
-  const size_t o_desc = take((size_t)nq * 32), o_id = take((size_t)nq * 4);
-  LinesUp U{}; lay_lines(o, n_map, S->dim, &U, nullptr);
-  const size_t up_bytes = o;
-  U.matches = take((size_t)std::max(n_map, 1) * 4);
-  const size_t o_skip2 = take(nq), o_lskip2 = take(std::max(n_map, 1)), o_inview = take(std::max(nq, 1));
-  size_t o_so[6];
-  o_so[0] = take((size_t)nq * 4); o_so[1] = take((size_t)nq * 4); o_so[2] = take((size_t)nq * 4); o_so[3] = take(nq); o_so[4] = take((size_t)nt * 4); o_so[5] = take(16);
-  const size_t o_qrec = take(orbs_qrec_bytes(nq)), o_cache = take(orbs_cache_bytes(nq));
-  const size_t o_lwork = take(line_track_work_bytes(n_map, S->nl)), o_pwork = take(pose_track_work_bytes(nt, S->nl));
-  s = ensure_work(S, ctx, o); if (s) return s;
-  s = ensure_stage(S, 1, up_bytes); if (s) return s;
-  char* h = S->h_stage[1]; char* d = S->d_work;
-  if (nq) {
-    std::memcpy(h + o_pos, mp->world_pos, (size_t)nq * 12); std::memcpy(h + o_nrm, mp->normal, (size_t)nq * 12);
-    std::memcpy(h + o_maxd, mp->max_distance, (size_t)nq * 4); std::memcpy(h + o_mind, mp->min_distance, (size_t)nq * 4);
-    if (mp->has_obs) std::memcpy(h + o_obs, mp->has_obs, nq); else std::memset(h + o_obs, 1, nq);
-    if (mp->skip) std::memcpy(h + o_skip, mp->skip, nq); else std::memset(h + o_skip, 0, nq);
-    std::memcpy(h + o_desc, mp->desc, (size_t)nq * 32); std::memcpy(h + o_id, point_id, (size_t)nq * 4);
-  }
-  if (n_map) pack_lines(h, U, local_lines, S->dim);
-  const SearchOut so{reinterpret_cast<int32_t*>(d + o_so[0]), reinterpret_cast<int32_t*>(d + o_so[1]), reinterpret_cast<int32_t*>(d + o_so[2]),
-                     reinterpret_cast<uint8_t*>(d + o_so[3]), reinterpret_cast<int32_t*>(d + o_so[4]), reinterpret_cast<int32_t*>(d + o_so[5])};
-  const MapPointsDev MP{nq, reinterpret_cast<const float*>(d + o_pos), reinterpret_cast<const float*>(d + o_nrm), reinterpret_cast<const float*>(d + o_maxd),
-                        reinterpret_cast<const float*>(d + o_mind), reinterpret_cast<const uint8_t*>(d + o_obs), reinterpret_cast<const uint8_t*>(d + o_skip2)};
-  const ApplyDev ap{S->D.kp_has, S->D.kp_world, S->D.kp_id, S->D.kp_obs, MP.pos, reinterpret_cast<const int32_t*>(d + o_id), MP.has_obs, S->D.rec_h[1]->i + RI_SEARCH1, 0, 0};
-  orbs_fill_problem(f, 1, nq, S->D.kp_has, d + o_qrec, reinterpret_cast<const uint32_t*>(d + o_desc), so, d + o_cache, P->nnratio_local, 0, RunIf{}, ap, h + o_prob);
+  UploadBlock B; LocalPointsUp MPU; LinesUp U; SearchScratch sc;
+  const auto prob = B.take<char>(orbs_problem_bytes());
+  MPU.reserve(B, nq); U.reserve(B, n_map, S->dim);
+  B.end_upload();
+  U.reserve_scratch(B); MPU.reserve_scratch(B);
+  const auto lskip2 = B.take<uint8_t>(std::max(n_map, 1)), inview = B.take<uint8_t>(std::max(nq, 1));
+  sc.reserve(B, nq, nt);
+  const auto lwork = B.take<char>(line_track_work_bytes(n_map, S->nl)), pwork = B.take<char>(pose_track_work_bytes(nt, S->nl));
+  s = stage_begin(S, ctx, 1, B); if (s) return s;
+  MPU.stage(B, mp, point_id); U.stage(B, local_lines);
+  const MapPointsDev MP = MPU.dev(B);
+  const ApplyDev ap{S->D.kp_has, S->D.kp_world, S->D.kp_id, S->D.kp_obs, MP.pos, B.dev(MPU.id), MP.has_obs, S->D.rec_h[1]->i + RI_SEARCH1, 0, 0};
+  orbs_fill_problem(f, 1, nq, S->D.kp_has, B.dev(sc.qrec), B.dev(MPU.desc), sc.out(B), B.dev(sc.cache), P->nnratio_local, 0, RunIf{}, ap, B.host(prob));
   hipStream_t st = ctx->stream;
-  LLD_HIP_TRY(hipMemcpyAsync(d, h, up_bytes, hipMemcpyHostToDevice, st));
-  LLD_HIP_TRY(hipEventRecord(S->uploaded[1], st)); S->upload_pending[1] = true;
+  s = stage_submit(S, st, 1, B); if (s) return s;
   // ---- kernels
   if (nq + n_map > 0)                                                          // (tables sized by state_build)
-    hipLaunchKernelGGL(track_mark_seen_kernel, dim3(1), dim3(kSeenThreads), S->seen_lds, st, S->D, nq, reinterpret_cast<const int32_t*>(d + o_id),
-                       reinterpret_cast<const uint8_t*>(d + o_skip), reinterpret_cast<uint8_t*>(d + o_skip2), n_map, reinterpret_cast<const int32_t*>(d + U.id),
-                       reinterpret_cast<const uint8_t*>(d + U.skip), reinterpret_cast<uint8_t*>(d + o_lskip2), S->seen_psize - 1, S->seen_lsize - 1);
-  S->in_view_off = o_inview; S->n_in_view = nq;
-  s = orbs_project_local_points(st, f->consts, nullptr, S->D.view, MP, P->viewing_cos_limit, P->th_local, d + o_qrec,
-                                FrustumOut{reinterpret_cast<uint8_t*>(d + o_inview), nullptr, nullptr, nullptr, S->D.rec_h[1]->i + RI_IN_VIEW}); if (s) return s;
-  s = orbs_launch_n(ctx, st, f, d + o_prob, 1); if (s) return s;
-  s = run_lines(f, st, P, n_map ? local_lines : nullptr, d, U, reinterpret_cast<const uint8_t*>(d + o_lskip2), d + o_lwork, 1); if (s) return s;
-  s = run_pose(f, st, P, d + o_pwork, 1); if (s) return s;
+    hipLaunchKernelGGL(track_mark_seen_kernel, dim3(1), dim3(kSeenThreads), S->seen_lds, st, S->D, nq, B.dev(MPU.id), B.dev(MPU.skip), B.dev(MPU.skip2), n_map, B.dev(U.id),
+                       B.dev(U.skip), B.dev(lskip2), S->seen_psize - 1, S->seen_lsize - 1);
+  S->in_view_off = inview.off; S->n_in_view = nq;
+  s = orbs_project_local_points(st, f->consts, nullptr, S->D.view, MP, P->viewing_cos_limit, P->th_local, B.dev(sc.qrec),
+                                FrustumOut{B.dev(inview), nullptr, nullptr, nullptr, S->D.rec_h[1]->i + RI_IN_VIEW}); if (s) return s;
+  s = orbs_launch_n(ctx, st, f, B.dev(prob), 1); if (s) return s;
+  s = run_lines(f, st, P, B, U, B.dev(lskip2), B.dev(lwork)); if (s) return s;
+  s = run_pose(f, st, P, B.dev(pwork), 1); if (s) return s;
   return LLD_OK;
 }
 

@@ -1,12 +1,14 @@
 // lld_frame_track_state.h — the device-resident tracking state of one lld_frame (what the reference keeps IN the Frame between the calls of
 // the Tracking thread) as the translation units that run stages on it see it: lld_frame_track.hip (TrackWithMotionModel, TrackReferenceKeyFrame,
-// TrackLocalMap, set_state, download) and lld_frame_reloc.hip (Relocalization).  Nothing here is exported.
+// TrackLocalMap, set_state, download) and lld_frame_reloc.hip (Relocalization), the device functions their kernels share, and the host half of a
+// stage that both use: begin / submit and the region structs of the arrays both upload.  Nothing here is exported.
 #ifndef LLD_FRAME_TRACK_STATE_H
 #define LLD_FRAME_TRACK_STATE_H
 
 #include "lld_common.h"
 #include "lld_device_math.h"
 #include "lld_track_internal.h"
+#include "lld_upload_block.h"
 
 namespace lld_track {
 
@@ -26,6 +28,21 @@ struct TrackDev {                 // device pointers of the frame's tracking sta
   // per-stage records
   RecHeader* rec_h[2]; int32_t* rec_kp_id[2]; uint8_t* rec_kp_out[2]; int32_t* rec_ln_id[2]; uint8_t* rec_ln_out[2];
 };
+
+// Both record headers to zero, one word per thread, when a frame enters stage 1.
+__device__ inline void rec_headers_zero(const TrackDev& D, int i) {
+  if (i < 2 * (int)(sizeof(RecHeader) / 4)) {
+    int32_t* h = reinterpret_cast<int32_t*>(i < (int)(sizeof(RecHeader) / 4) ? D.rec_h[0] : D.rec_h[1]);
+    h[i % (int)(sizeof(RecHeader) / 4)] = 0;
+  }
+}
+// What PoseOptimization left in pose_out (PoseTrackDev::pose_out) as the head of a stage's record.
+__device__ inline void rec_header_from_pose(RecHeader& H, const double* pose_out) {
+  const int* pi = reinterpret_cast<const int*>(pose_out + 8);
+  for (int c = 0; c < 7; c++) H.pose_qt[c] = pose_out[c];
+  H.chi2 = pose_out[7];
+  H.i[RI_INL] = pi[0]; H.i[RI_ITS] = pi[1]; H.i[RI_TRIALS] = pi[2]; H.i[RI_EDGES] = pi[3]; H.i[RI_POINT_EDGES] = pi[4];
+}
 
 struct ViewConsts { float fx, fy, cx, cy, bf, min_x, max_x, min_y, max_y, log_scale_factor; int n_levels; double b, thr_base, sx, sy; int monocular, use_grid; };
 
@@ -54,7 +71,8 @@ __device__ inline void view_from_matrix(const float* Rf, const float* tf, const 
 
 // AddLinesFrom's camera (src/Tracking.cc:920-923, :1136-1139): T_curr = mTcw.inv() widened to double.  The build takes the frame's own
 // Rwc = Rcw^T and Ow for it (equal to OpenCV's float LU inverse up to float rounding: include/lld_amd.h); the right camera is GetTForRight.
-__device__ inline void line_camera_from_view(const ViewConsts& C, const lld_frame_view& V, LineTrackDevParams* L) {
+// On the host for stage 1, where the view is the caller's (mVelocity * mLastFrame.mTcw is a float product).
+__host__ __device__ inline void line_camera_from_view(const ViewConsts& C, const lld_frame_view& V, LineTrackDevParams* L) {
 #pragma clang fp contract(off)
   for (int i = 0; i < 9; i++) L->K[i] = 0.0;
   L->K[0] = (double)C.fx; L->K[2] = (double)C.cx; L->K[4] = (double)C.fy; L->K[5] = (double)C.cy; L->K[8] = 1.0;
@@ -96,8 +114,6 @@ __device__ __forceinline__ bool seen_lookup(const int32_t* tab, unsigned mask, i
   }
 }
 
-inline size_t al(size_t b) { return (b + 255) & ~size_t(255); }
-
 }  // namespace lld_track
 
 struct lld_frame_track_state {
@@ -122,14 +138,64 @@ struct lld_frame_track_state {
 namespace lld_track {
 // host plumbing of a stage (lld_frame_track.hip)
 int ensure_state(lld_frame* f);                                            // the state exists (a frame without lines unless lld_frame_set_lines ran)
-int ensure_work(lld_frame_track_state* S, lld_ctx* ctx, size_t bytes);     // grow-only d_work; synchronises the stream before it reallocates
 int ensure_stage(lld_frame_track_state* S, int s, size_t bytes);           // grow-only pinned staging of stage s, free of its previous upload
-// a new frame enters stage 1: no MapPoints, no flags, nothing discarded or tracked, both record headers zero, the pose / view / line camera uploaded at *_d
-int track_reset_launch(hipStream_t st, lld_frame_track_state* S, const double* pose_d, const lld_frame_view* view_d, const LineTrackDevParams* lp_d);
+// begin: the grow-only d_work holds everything B declared (the stream is synchronised before it is reallocated), the pinned staging of stage s the uploaded prefix,
+// and B is bound to the two; submit: the one copy of that prefix is queued
+int stage_begin(lld_frame_track_state* S, lld_ctx* ctx, int s, UploadBlock& B);
+int stage_submit(lld_frame_track_state* S, hipStream_t st, int s, const UploadBlock& B);
 // what lld_frame_track_reference_keyframe refuses about a keyframe (LLD_ERR_INVALID); n_features: entries of its feature list
 int ref_keyframe_check(const lld_ref_keyframe* kf, int* n_features);
-void fill_consts(lld_frame_track_state* S, const lld_frame* f, const lld_track_params* P, const lld_frame_view* view);
-void line_params_from_view(const ViewConsts& C, const lld_frame_view& V, LineTrackDevParams* L);
+void fill_consts(lld_frame_track_state* S, const lld_track_params* P, const lld_frame_view* view);
+
+// ---- The groups of arrays a stage moves, each laid out (reserve), packed (stage) and bound to the kernels' structs (dev / out) in one place.
+// pose | line camera | view: what a frame enters a stage-1 routine with
+struct StageHeader {
+  Span<double> pose; Span<LineTrackDevParams> lp; Span<lld_frame_view> view;
+  void reserve(UploadBlock& B) { pose = B.take<double>(7); lp = B.take<LineTrackDevParams>(1); view = B.take<lld_frame_view>(1); }
+  void stage(const UploadBlock& B, const ViewConsts& C, const lld_frame_view* v, const double* pose_qt) const {
+    B.stage(pose, pose_qt); line_camera_from_view(C, *v, B.host(lp)); B.stage(view, v);
+  }
+};
+// a new frame enters stage 1: no MapPoints, no flags, nothing discarded or tracked, both record headers zero, the uploaded header taken over
+int track_reset_launch(hipStream_t st, lld_frame_track_state* S, const UploadBlock& B, const StageHeader& H);
+
+// A reference keyframe: descriptors, angles, MapPoints, the FeatureVector as CSR; of a relocalisation candidate (x) also the MapPoints' distances and own descriptors.
+struct RefKeyframeUp {
+  Span<uint32_t> desc, pdesc; Span<float> ang, pos, maxd, mind; Span<int32_t> id, node, start, feat; Span<uint8_t> obs;
+  struct Query { const float* pos; const int32_t* id; const uint8_t* obs; };                 // the q_* of an ApplyDev
+  void reserve(UploadBlock& B, const lld_ref_keyframe& kf, int nv, const lld_reloc_candidate* x = nullptr) {
+    const size_t n = kf.n, nn = kf.n_nodes;
+    desc = B.take<uint32_t>(n, 8); ang = B.take<float>(n); id = B.take<int32_t>(n); pos = B.take<float>(n, 3); obs = B.take<uint8_t>(n);
+    node = B.take<int32_t>(nn); start = B.take<int32_t>(nn + 1); feat = B.take<int32_t>(nv);
+    maxd = B.take<float>(x ? n : 0); mind = B.take<float>(x ? n : 0); pdesc = (x && x->point_desc) ? B.take<uint32_t>(n, 8) : desc;   // no own descriptors: the keyframe's
+  }
+  void stage(const UploadBlock& B, const lld_ref_keyframe& kf, const lld_reloc_candidate* x = nullptr) const {
+    B.stage(desc, kf.desc); B.stage(ang, kf.angle); B.stage(id, kf.point_id); B.stage(pos, kf.world_pos); B.stage(obs, kf.has_obs, 1);
+    B.stage(node, kf.node); B.stage(start, kf.n_nodes ? kf.node_start : nullptr, 0); B.stage(feat, kf.feature);   // no nodes: node_start = {0}
+    if (x) { B.stage(maxd, x->max_distance); B.stage(mind, x->min_distance); if (x->point_desc) B.stage(pdesc, x->point_desc); }
+  }
+  Query dev(const UploadBlock& B, BowSearchDev& S) const {
+    S.kf_desc = B.dev(desc); S.kf_angle = B.dev(ang); S.kf_point_id = B.dev(id); S.kf_node = B.dev(node); S.kf_node_start = B.dev(start); S.kf_feature = B.dev(feat);
+    return {B.dev(pos), B.dev(id), B.dev(obs)};
+  }
+};
+// the searched side of a SearchByBoW: the resident frame's descriptors, angles and FeatureVector
+inline void bow_frame_side(const lld_frame* f, BowSearchDev& S) {
+  const KeypointsDev K = resident_keypoints(f, true);
+  S.nt = K.nt; S.f_desc = K.desc; S.f_angle = K.angle;
+  S.f_n_nodes = f->bow_n_nodes(); S.f_node = f->bow_node(); S.f_node_start = f->bow_node_start(); S.f_feature = f->bow_feature();
+}
+
+// Device-only scratch of one (nq, nt) guided search: SearchOut, query records, candidate cache (a retry of the same queries shares the last two).
+// (ResultRegion of lld_orb_search.hip holds the same six arrays, but 64-byte aligned in the order its download fetches: it stays where it is.)
+struct SearchScratch {
+  Span<int32_t> match, bd, sd, owner, sum; Span<uint8_t> rem; Span<char> qrec, cache;
+  void reserve(UploadBlock& B, int nq, int nt, const SearchScratch* query_of = nullptr) {
+    match = B.take<int32_t>(nq); bd = B.take<int32_t>(nq); sd = B.take<int32_t>(nq); rem = B.take<uint8_t>(nq); owner = B.take<int32_t>(nt); sum = B.take<int32_t>(4);
+    qrec = query_of ? query_of->qrec : B.take<char>(orbs_qrec_bytes(nq)); cache = query_of ? query_of->cache : B.take<char>(orbs_cache_bytes(nq));
+  }
+  SearchOut out(const UploadBlock& B) const { return {B.dev(match), B.dev(bd), B.dev(sd), B.dev(rem), B.dev(owner), B.dev(sum)}; }
+};
 }  // namespace lld_track
 
 #endif

@@ -942,14 +942,8 @@ int check_keypoints(const lld_orb_search* s, bool host_arrays, bool need_angle) 
   return LLD_OK;
 }
 
-// The keypoint side of a search as DEVICE pointers: into the upload region of the call, or into a resident lld_frame.
-struct KeypointsDev { int nt; const uint32_t* desc; const float* xy; const int32_t* octave; const float* uright; const float* angle; };
-
-KeypointsDev resident_keypoints(const lld_frame* f, bool want_angle) {
-  return {f->nt, reinterpret_cast<const uint32_t*>(f->d + f->o_td), reinterpret_cast<const float*>(f->d + f->o_txy), reinterpret_cast<const int32_t*>(f->d + f->o_toct),
-          f->has_uright ? reinterpret_cast<const float*>(f->d + f->o_tur) : nullptr,
-          (want_angle && f->has_angle) ? reinterpret_cast<const float*>(f->d + f->o_tang) : nullptr};
-}
+using lld_track::KeypointsDev;             // the keypoint side of a search: into the upload region of the call, or into a resident lld_frame
+using lld_track::resident_keypoints;
 
 // Where a caller's keypoint arrays travel in an upload region: desc | xy | octave | uright | angle, the last two only when wanted.
 struct KeypointsUp {
@@ -1437,6 +1431,12 @@ extern "C" int lld_orb_search_by_sim3(lld_ctx* ctx, const lld_orb_search* kf1, c
 
 // ================================================================ launchers for the device-resident Tracking chain (lld_track_internal.h)
 namespace lld_track {
+
+KeypointsDev resident_keypoints(const lld_frame* f, bool want_angle) {
+  return {f->nt, reinterpret_cast<const uint32_t*>(f->d + f->o_td), reinterpret_cast<const float*>(f->d + f->o_txy), reinterpret_cast<const int32_t*>(f->d + f->o_toct),
+          f->has_uright ? reinterpret_cast<const float*>(f->d + f->o_tur) : nullptr,
+          (want_angle && f->has_angle) ? reinterpret_cast<const float*>(f->d + f->o_tang) : nullptr};
+}
 
 size_t orbs_problem_bytes() { return sizeof(Problem); }
 size_t orbs_qrec_bytes(int nq) { return al((size_t)nq * sizeof(QRec)); }

@@ -44,6 +44,9 @@ struct lld_frame {
 namespace lld_track {
 
 void state_free(lld_frame* f);             // lld_frame_destroy calls it before the keypoints go
+// The keypoint side of a search or a pose problem as DEVICE pointers; of a resident frame (lld_orb_search.hip): uright / angle null when it has none.
+struct KeypointsDev { int nt; const uint32_t* desc; const float* xy; const int32_t* octave; const float* uright; const float* angle; };
+KeypointsDev resident_keypoints(const lld_frame* f, bool want_angle);
 
 // ---------------------------------------------------------------- guided ORB search on device arrays (lld_orb_search.hip)
 // One search = a projection kernel that writes the query records + orb_search_kernel on one workgroup, which also hands the frame what it
