@@ -333,6 +333,7 @@ class Frame {                                                      // what PoseO
   std::vector<MapLine*> mvpMapLines;
   std::vector<bool> mvbOutlierLines;
   Mat mDescriptorsLines;                                           // one LBD descriptor (CV_32F row) per left line
+  Mat mDescriptorsLinesRight;                                      // ... per right line (Frame.h; read by the Frame constructor's MatchLines, src/Frame.cc:122)
   void SetPose(const Mat& T) { mTcw = T.clone(); n_set_pose++; UpdatePoseMatrices(); }
   int n_set_pose = 0;
   // what the matchers read (include/Frame.h).  The image bounds and grid constants are static members of the reference's Frame;

@@ -143,7 +143,8 @@ lld_frame_view view_of_matrix(const Frame& Cur, const float* T) {
 
 }  // namespace
 
-FrameOnDevice::FrameOnDevice(lld_ctx* ctx, const Frame& F) : ctx_(ctx), nt_(F.N), nl_((int)F.mvLinesLeft.size()) {
+void FrameOnDevice::create(const Frame& F) {
+  lld_ctx* ctx = ctx_;
   std::vector<float> xy(2 * (size_t)F.N + 2), angle(F.N + 1); std::vector<int32_t> octave(F.N + 1);
   for (int k = 0; k < F.N; k++) { xy[2 * k] = F.mvKeysUn[k].pt.x; xy[2 * k + 1] = F.mvKeysUn[k].pt.y; octave[k] = F.mvKeysUn[k].octave; angle[k] = F.mvKeysUn[k].angle; }
   lld_orb_search kp; std::memset(&kp, 0, sizeof kp);
@@ -152,6 +153,12 @@ FrameOnDevice::FrameOnDevice(lld_ctx* ctx, const Frame& F) : ctx_(ctx), nt_(F.N)
   kp.grid_cols = 64; kp.grid_rows = 48;
   kp.n_levels = F.mnScaleLevels; kp.level_scale = F.mvScaleFactors.data(); kp.level_sigma2 = F.mvLevelSigma2.data(); kp.level_inv_sigma2 = F.mvInvLevelSigma2.data();
   check(lld_frame_create(ctx, &kp, &f_), "lld_frame_create");
+  lld_track_params_default(&params_);
+  params_.cam = lld_camera{F.fx, F.fy, F.cx, F.cy, F.mbf};
+}
+
+FrameOnDevice::FrameOnDevice(lld_ctx* ctx, const Frame& F) : ctx_(ctx), nt_(F.N), nl_((int)F.mvLinesLeft.size()) {
+  create(F);
   std::vector<float> left, right; std::vector<int32_t> lo, ro, lm(F.line_matches.begin(), F.line_matches.end());
   key_lines(F.mvLinesLeft, left, lo); key_lines(F.mvLinesRight, right, ro);
   dim_ = nl_ > 0 ? F.mDescriptorsLines.cols : 1;
@@ -161,8 +168,58 @@ FrameOnDevice::FrameOnDevice(lld_ctx* ctx, const Frame& F) : ctx_(ctx), nt_(F.N)
   fl.sx = 1.0 / F.mnMaxX; fl.sy = 1.0 / F.mnMaxY;
   const int st = lld_frame_set_lines(f_, nl_ > 0 ? &fl : nullptr);
   if (st != LLD_OK) { lld_frame_destroy(f_); f_ = nullptr; check(st, "lld_frame_set_lines"); }
-  lld_track_params_default(&params_);
-  params_.cam = lld_camera{F.fx, F.fy, F.cx, F.cy, F.mbf};
+}
+
+// The Frame constructor's line half on the device (src/Frame.cc:118-122): lineMatcher.MatchLines(mvLinesLeft, mvLinesRight, mDescriptorsLines,
+// mDescriptorsLinesRight, &line_matches) and the upload in one queued call; line_matches comes back for the host's readers (KeyFrame::line_matches,
+// the counts of src/Tracking.cc:978).
+FrameOnDevice::FrameOnDevice(lld_ctx* ctx, Frame& F, const StereoLineParams& matcher) : ctx_(ctx), nt_(F.N), nl_((int)F.mvLinesLeft.size()) {
+  create(F);
+  std::vector<float> left, right; std::vector<int32_t> lo, ro;
+  key_lines(F.mvLinesLeft, left, lo); key_lines(F.mvLinesRight, right, ro);
+  dim_ = nl_ > 0 ? F.mDescriptorsLines.cols : 1;
+  const int nr = (int)F.mvLinesRight.size();
+  lld_frame_lines_build fl; std::memset(&fl, 0, sizeof fl);
+  fl.n_left = nl_; fl.left = left.data(); fl.left_octave = lo.data(); fl.desc_left = nl_ > 0 ? F.mDescriptorsLines.ptr<float>() : nullptr;
+  fl.n_right = nr; fl.right = right.data(); fl.right_octave = ro.data(); fl.desc_right = nr > 0 ? F.mDescriptorsLinesRight.ptr<float>() : nullptr;
+  fl.dim = dim_; fl.sx = 1.0 / F.mnMaxX; fl.sy = 1.0 / F.mnMaxY;
+  for (int i = 0; i < 9; i++) fl.stereo.K[i] = matcher.K[i];
+  fl.stereo.b = matcher.b; fl.stereo.tau = matcher.tau; fl.stereo.min_line_length = matcher.minLineLength; fl.stereo.is_stereo = 1;
+  int st = lld_frame_build_lines(f_, nl_ > 0 ? &fl : nullptr);
+  std::vector<int32_t> lm(nl_ + 1, -1);
+  if (st == LLD_OK) st = lld_frame_lines_download(f_, lm.data(), nullptr);
+  if (st != LLD_OK) { lld_frame_destroy(f_); f_ = nullptr; check(st, "lld_frame_build_lines"); }
+  F.line_matches.assign(lm.begin(), lm.begin() + nl_);
+}
+
+// Tracking::MatchLinesLastKF between two frames that are on the device: the call's result drives the object bookkeeping of :1597-1604; nothing is
+// gathered.  The device numbers the new lines from MapLine::nNextId in creation order, which is the order the constructors below run in.
+int FrameOnDevice::MatchLinesLastKF(const TrackingMembers& tr, Frame& Cur, FrameOnDevice& lastOnDevice, KeyFrame* pKF, lld_slam::Map* mpMap,
+                                    std::vector<MapLine*>* created, std::vector<int>* match_trace) {
+  const int n = nl_;
+  std::vector<int32_t> match_last(n + 1, -1), new_id(n + 1, -1); std::vector<uint8_t> made(n + 1, 0); std::vector<double> X0(3 * (size_t)n + 3, 0.0), dir(3 * (size_t)n + 3, 0.0);
+  lld_frame_new_lines_params p; std::memset(&p, 0, sizeof p);
+  p.thr_reproj_base = 6; p.md_thr = tr.mdThr; p.use_grid = 1;                // thrReprojLineBase = 6 pixels (:1451)
+  p.first_new_id = (int32_t)MapLine::nNextId();
+  lld_frame_new_lines_result r; std::memset(&r, 0, sizeof r);
+  r.match_last = match_last.data(); r.new_id = new_id.data(); r.created = made.data(); r.x0 = X0.data(); r.dir = dir.data();
+  check(lld_frame_new_map_lines(f_, lastOnDevice.f_, &p, &r), "lld_frame_new_map_lines");
+  if (created) created->assign(n, static_cast<MapLine*>(NULL));
+  for (int i = 0; i < n; i++) {
+    if (!made[i]) continue;
+    const lld_slam::Vector3d x0(X0[3 * i], X0[3 * i + 1], X0[3 * i + 2]), line_dir(dir[3 * i], dir[3 * i + 1], dir[3 * i + 2]);
+    MapLine* ml = new MapLine(x0, line_dir, pKF, mpMap, i);                   // :1597-1604
+    if ((int32_t)ml->mnId != new_id[i]) throw std::runtime_error("lld_frame_new_map_lines: MapLine ids left the device's numbering");
+    ml->AddObservation(pKF, i);
+    pKF->AddMapLine(ml, i);
+    ml->ComputeDistinctiveDescriptors();
+    Cur.mvpMapLines[i] = ml;
+    ml->tracked_last_id = Cur.mnId;
+    mpMap->AddMapLine(ml);
+    if (created) (*created)[i] = ml;
+  }
+  if (match_trace) match_trace->assign(match_last.begin(), match_last.begin() + n);
+  return r.n_created + r.n_held;                                              // :1610
 }
 
 FrameOnDevice::~FrameOnDevice() { if (f_) lld_frame_destroy(f_); }

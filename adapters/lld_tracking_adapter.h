@@ -41,10 +41,16 @@ struct TrackTrace { lld_track_result r; std::vector<int32_t> kp_point_id, ln_lin
 // What Relocalization got back (optional, as TrackTrace): lld_reloc_result with its per-candidate arrays owned here.
 struct RelocTrace { lld_reloc_result r; std::vector<int32_t> n_bow, rounds, n_good_last, rungs, n_additional1, n_additional2; std::vector<uint8_t> discarded; };
 
+// TwoFrameLineMatcher's constructor arguments (include/TwoFrameLineMatcher.h:31-38) as the Frame constructor passes them (src/Frame.cc:118-121)
+struct StereoLineParams { double K[9]; double b; double tau; int minLineLength; };
+
 class FrameOnDevice {
  public:
   // the frame's own data: mDescriptors, mvKeysUn, mvuRight, the grid and level tables, mvLinesLeft / mvLinesRight / line_matches / mDescriptorsLines
   FrameOnDevice(lld_ctx* ctx, const Frame& mCurrentFrame);
+  // the same, with the lines matched on the device (lld_frame_build_lines): mCurrentFrame brings mDescriptorsLinesRight instead of line_matches,
+  // which this constructor fills from the call's download - lineMatcher.MatchLines(...) of src/Frame.cc:121-122 is not run on the host
+  FrameOnDevice(lld_ctx* ctx, Frame& mCurrentFrame, const StereoLineParams& matcher);
   ~FrameOnDevice();
   FrameOnDevice(const FrameOnDevice&) = delete;
   FrameOnDevice& operator=(const FrameOnDevice&) = delete;
@@ -81,8 +87,16 @@ class FrameOnDevice {
   // Returns mnMatchesInliers through the pointer; the two final tests of the reference (:1212-1219) stay with the caller.
   void TrackLocalMap(const TrackingMembers& tr, Frame& mCurrentFrame, const std::vector<MapPoint*>& mvpLocalMapPoints, const std::vector<MapLine*>& local_lines,
                      const std::vector<lld_slam::Mat>& local_line_descs, int* mnMatchesInliers, TrackTrace* trace = nullptr);
+  // int Tracking::MatchLinesLastKF(bool do_skip_addnew, KeyFrame* pKF) (src/Tracking.cc:1449-1611) with mLastFrame on the device too (lld_frame_new_map_lines):
+  // no gather - lines, partners, descriptors, poses, what the frames hold and what this frame tracked are read where the chain left them - then the
+  // object bookkeeping of :1597-1604 from the call's result, as lld_line_adapter's MatchLinesLastKF does it from host arrays.  New MapLines take
+  // their mnId from MapLine::nNextId in creation order; the device gave the same ids (a mismatch throws).  "Tracked by this frame" (:1518) is what
+  // the device recorded: the lines its stages assigned, or the held lines after SetFrameState.  Returns mapline_cnt + cnt0.
+  int MatchLinesLastKF(const TrackingMembers& tr, Frame& mCurrentFrame, FrameOnDevice& lastOnDevice, KeyFrame* pKF, lld_slam::Map* mpMap,
+                       std::vector<MapLine*>* created = nullptr, std::vector<int>* match_trace = nullptr);
 
  private:
+  void create(const Frame& F);       // lld_frame_create of the keypoint side, the stage parameters
   lld_ctx* ctx_;
   lld_frame* f_ = nullptr;
   int nt_ = 0, nl_ = 0, dim_ = 1;

@@ -940,6 +940,65 @@ int  lld_frame_track_local_map(lld_frame* frame, const lld_track_params* params,
                                const lld_map_lines* local_lines);
 /* Waits for the queued stages and fetches their records (either may be NULL; stage2 is meaningful only after lld_frame_track_local_map). */
 int  lld_frame_track_download(lld_frame* frame, lld_track_result* stage1, lld_track_result* stage2);
+/* ------------------------------------------------------------------ the frame's lines, matched and turned into map lines on the device
+ * lld_frame_build_lines: what the Frame constructor does with its two line sets (src/Frame.cc:121-122: TwoFrameLineMatcher::MatchLines with
+ * T = identity, T_right = GetTForRight) and what lld_frame_set_lines does with the result, in one call that leaves Frame::line_matches in HBM
+ * where the chain reads it.  Both line sets, both octave arrays and both descriptor sets travel in ONE copy from a pinned buffer the frame
+ * owns; the Hough-cell fill, CheckLinePair's gates and distances (the kernels of lld_line_match_stereo) and the in-order greedy assignment
+ * are queued on the context's stream and the call returns: lld_frame_track_* follow on the same stream, nothing goes through the host.  The
+ * call waits for the stream first only when the frame already has a tracking state (which it replaces, as lld_frame_set_lines does).
+ * The result is bit-identical to lld_line_match_stereo followed by lld_frame_set_lines on the same arrays: same matches, same cells, same
+ * reset of the tracking state.  n_right = 0: every left line gets -1 and no matching kernel is launched.  lines = NULL or n_left = 0: a
+ * frame without lines.  The right descriptors are read by the match only; they stay allocated with the frame's line block (n_right * dim
+ * floats) but nothing reads them afterwards.
+ * Refused before anything is queued, the frame unchanged: LLD_ERR_INVALID for a NULL frame or required array, a negative count, dim <= 0,
+ * sx or sy not > 0, an octave outside 0..64; LLD_ERR_UNSUPPORTED for n_left above lld_frame_set_lines' line limit, dim > LLD_LINE_DIM_MAX,
+ * n_right * 8 + dim * 4 > LLD_LINE_LDS_CEILING or (n_left + n_right) * 4 + 16 > LLD_LINE_LDS_CEILING (see lld_line_match_greedy). */
+typedef struct {
+  int32_t n_left;  const float* left;  const int32_t* left_octave;  const float* desc_left;    /* mvLinesLeft, mDescriptorsLines [n_left][dim]  */
+  int32_t n_right; const float* right; const int32_t* right_octave; const float* desc_right;   /* mvLinesRight, mDescriptorsLinesRight           */
+  int32_t dim, reserved;
+  double  sx, sy;                    /* as lld_frame_lines */
+  lld_line_stereo_params stereo;     /* K, b, tau, min_line_length, is_stereo: as lld_line_match_stereo */
+} lld_frame_lines_build;
+int  lld_frame_build_lines(lld_frame* frame, const lld_frame_lines_build* lines);
+/* Waits for the frame's queued work and fetches Frame::line_matches (and, when match_dist is not NULL, the accepted descriptor distances) in
+ * one copy: the host needs them for KeyFrame::line_matches and the counts at src/Tracking.cc:978.  On a frame whose lines came from
+ * lld_frame_set_lines: the uploaded line_matches, and match_dist filled with lld_line_match_stereo's "no distance" value (DBL_MAX).  A frame
+ * without lines: LLD_OK, nothing is written. */
+int  lld_frame_lines_download(lld_frame* frame, int32_t* line_matches /*[n_left]*/, double* match_dist /*[n_left] or NULL*/);
+/* Tracking::MatchLinesLastKF (src/Tracking.cc:1449-1611, called from CreateNewKeyFrame :1433) between two RESIDENT frames: the kernel of
+ * lld_line_match_last_frame on what the two handles already hold - both frames' lines, line_matches, Hough cells, octaves and descriptors -
+ * with nothing uploaded but this parameter struct.
+ *   cameras       each frame's camera-to-world R, t and right-camera centre as its chain left them in device memory after its last stage
+ *                 (or lld_frame_track_set_state): [Rwc | Ow] widened to double instead of mTcw.inv(), the deviation AddLinesFrom documents
+ *                 above; K, b, sx, sy are the current frame's;
+ *   cur_occupied  mCurrentFrame.mvpMapLines[i] != NULL (:1477): the lines the current frame holds now;
+ *   last_skip     mLastFrame.mvpMapLines[li] && ...->tracked_last_id == mCurrentFrame.mnId (:1518): the last frame holds a line on li whose id
+ *                 is among the lines the current frame tracked (by id, on the device, against the table TrackLocalMap's skip test uses).
+ * A second kernel numbers the created lines in ascending i - the reference's creation order - first_new_id + rank (the caller passes
+ * MapLine::nNextId), and writes them into the current frame's state (held, id, X0, direction; mvbOutlierLines as it is): the handle then
+ * holds what mCurrentFrame.mvpMapLines holds after :1602, and when this frame is the next call's `last`, that call sees them.
+ * ml->tracked_last_id = mnId (:1603) has no reader left in this frame's life (no AddLinesFrom follows CreateNewKeyFrame on it), so the
+ * frame's tracked table is left alone: its capacity and the hash budget of TrackLocalMap's skip test do not change.
+ * One download, one wait.  Stereo only, like lld_line_match_last_frame.  The stage records of lld_frame_track_download predate this call.
+ * LLD_ERR_INVALID, both frames unchanged: a NULL argument, cur == last, frames of different contexts or different dim, a frame without
+ * lines or without a pose (no lld_frame_track_* stage and no lld_frame_track_set_state has run on it), first_new_id < 0 or
+ * first_new_id + n_left > INT32_MAX. */
+typedef struct {
+  double  thr_reproj_base;          /* 6 px (Tracking.cc:1451) */
+  double  md_thr;                   /* mdThr */
+  int32_t use_grid;                 /* as lld_line_lastkf_params.use_grid */
+  int32_t first_new_id;             /* MapLine::nNextId */
+} lld_frame_new_lines_params;
+typedef struct {
+  int32_t n_created;                /* mapline_cnt */
+  int32_t n_held;                   /* cnt0: lines the frame held on entry; the reference returns n_created + n_held (:1610) */
+  /* caller-allocated [n_left] / [n_left][3] of the current frame, as lld_line_match_last_frame; any may be NULL */
+  int32_t* match_last; uint8_t* created; double* x0; double* dir;
+  int32_t* new_id;                  /* [n_left] id given to a created line, else -1; may be NULL */
+} lld_frame_new_lines_result;
+int  lld_frame_new_map_lines(lld_frame* cur, lld_frame* last, const lld_frame_new_lines_params* params, lld_frame_new_lines_result* out);
 /* ORBmatcher::Fuse(KeyFrame*, vpMapPoints, th) (src/ORBmatcher.cc:825-958; the loop of LocalMapping::SearchInNeighbors) with the
  * projection loop (:841-890) on the device: cv::gemm transform, z >= 0, invz = 1/z, u = fx*(x*invz)+cx, KeyFrame::IsInImage
  * (upper bounds strict, src/KeyFrame.cc:633-636), ur = u - bf*invz, scale-invariance band, PO.dot(Pn) >= 0.5*dist3D, PredictScale;
@@ -1166,7 +1225,8 @@ int  lld_orb_extractor_descriptors(const lld_orb_extractor* ex, int image_index,
  * Scope: RECTIFIED stereo only - mvKeysUn = mvKeys, the `mDistCoef.at<float>(0)==0.0` branch of Frame::UndistortKeyPoints
  * (:468-474); the distorted branch, for the RGB-D and the monocular Frame, is lld_frame_build_mono* below (the reference rectifies a
  * stereo pair before it reaches the Frame).  Lines are added with
- * lld_frame_set_lines as before (the reference's line extractor is external and host-side).
+ * lld_frame_build_lines, which matches them on the device, or with lld_frame_set_lines when the caller has line_matches already (the
+ * reference's line extractor is external and host-side: the KeyLines and descriptors themselves come from the host either way).
  * Both build calls queue their kernels on the context's stream and return WITHOUT synchronising; every later call on the frame is
  * ordered after them by that stream, and lld_frame_stereo_download is the one that waits.
  * Refusals, before anything is queued: LLD_ERR_INVALID for null pointers, mb not > 0, a grid outside lld_frame_create's limits,

@@ -463,6 +463,43 @@ class TrackedFrame {
     check(lld_frame_track_download(f_, stage1 ? &stage1->r : nullptr, stage2 ? &stage2->r : nullptr), "lld_frame_track_download");
   }
   int N() const { return nt_; }
+  lld_frame* get() const { return f_; }
+  // The frame's lines matched ON the frame (lld_frame_build_lines): what Frame::Frame does with TwoFrameLineMatcher::MatchLines (src/Frame.cc:121-122)
+  // and the upload of lld_frame_set_lines in one queued call; replaces the lines the constructor was given (pass it NULL).  The chain follows on
+  // the stream; DownloadLines fetches Frame::line_matches when the host needs it.
+  void BuildLines(const lld_frame_lines_build* lines) {
+    check(lld_frame_build_lines(f_, lines), "lld_frame_build_lines");
+    nl_ = lines ? lines->n_left : 0;
+  }
+  int NLines() const { return nl_; }
+  // Frame::line_matches (and the accepted descriptor distances, DBL_MAX where none); waits for the frame's queued work
+  void DownloadLines(std::vector<int>* line_matches, std::vector<double>* match_dist = nullptr) {
+    std::vector<int32_t> m(nl_ + 1, -1);
+    if (match_dist) match_dist->assign(nl_, 0.0);
+    check(lld_frame_lines_download(f_, m.data(), match_dist && nl_ ? match_dist->data() : nullptr), "lld_frame_lines_download");
+    line_matches->assign(m.begin(), m.begin() + nl_);
+  }
+  // Tracking::MatchLinesLastKF (src/Tracking.cc:1449-1611) between this frame and `last`, both resident (lld_frame_new_map_lines): created[i] != 0 ->
+  // the reference constructs MapLine(X0[i], dir[i]) for line i; new_id[i] = first_new_id + its rank in creation order (pass MapLine::nNextId).
+  // The created lines have entered this frame's state.  Returns mapline_cnt + cnt0 like the reference.
+  struct NewMapLines {
+    lld_frame_new_lines_result r{};
+    std::vector<int32_t> match_last, new_id; std::vector<uint8_t> created; std::vector<double> X0, dir;
+    void bind(int n) {
+      match_last.assign(n + 1, -1); new_id.assign(n + 1, -1); created.assign(n + 1, 0); X0.assign(3 * (size_t)n + 3, 0.0); dir.assign(3 * (size_t)n + 3, 0.0);
+      r.match_last = match_last.data(); r.new_id = new_id.data(); r.created = created.data(); r.x0 = X0.data(); r.dir = dir.data();
+    }
+  };
+  int MatchLinesLastKF(TrackedFrame& last, int32_t first_new_id, NewMapLines* out, double thrReprojLineBase = 6.0, bool use_grid = true) {
+    NewMapLines local;
+    NewMapLines& R = out ? *out : local;
+    R.bind(nl_);
+    lld_frame_new_lines_params p{};
+    p.thr_reproj_base = thrReprojLineBase; p.md_thr = params.line_md_thr; p.use_grid = use_grid; p.first_new_id = first_new_id;
+    check(lld_frame_new_map_lines(f_, last.f_, &p, &R.r), "lld_frame_new_map_lines");
+    R.match_last.resize(nl_); R.new_id.resize(nl_); R.created.resize(nl_); R.X0.resize(3 * (size_t)nl_); R.dir.resize(3 * (size_t)nl_);
+    return R.r.n_created + R.r.n_held;
+  }
   // mvuRight / mvDepth of a frame StereoFrame built (Frame::UnprojectStereo and keyframe creation read them on the host); waits for the build
   int DownloadStereo(std::vector<float>& mvuRight, std::vector<float>& mvDepth) {
     mvuRight.assign(nt_, -1.f); mvDepth.assign(nt_, -1.f);

@@ -337,6 +337,24 @@ class RelocResult(C.Structure):
                 ("n_additional1", c_int32_p), ("n_additional2", c_int32_p)]
 
 
+class FrameLinesBuild(C.Structure):
+    """lld_frame_lines_build (include/lld_amd.h): both line sets with both descriptor sets, and TwoFrameLineMatcher's parameters."""
+    _fields_ = [("n_left", C.c_int32), ("left", c_float_p), ("left_octave", c_int32_p), ("desc_left", c_float_p),
+                ("n_right", C.c_int32), ("right", c_float_p), ("right_octave", c_int32_p), ("desc_right", c_float_p),
+                ("dim", C.c_int32), ("reserved", C.c_int32), ("sx", C.c_double), ("sy", C.c_double), ("stereo", LineStereoParams)]
+
+
+class FrameNewLinesParams(C.Structure):
+    """lld_frame_new_lines_params."""
+    _fields_ = [("thr_reproj_base", C.c_double), ("md_thr", C.c_double), ("use_grid", C.c_int32), ("first_new_id", C.c_int32)]
+
+
+class FrameNewLinesResult(C.Structure):
+    """lld_frame_new_lines_result."""
+    _fields_ = [("n_created", C.c_int32), ("n_held", C.c_int32), ("match_last", c_int32_p), ("created", c_uint8_p), ("x0", c_double_p),
+                ("dir", c_double_p), ("new_id", c_int32_p)]
+
+
 RELOC_RUNG_POSE1, RELOC_RUNG_SEARCH1, RELOC_RUNG_POSE2, RELOC_RUNG_SEARCH2, RELOC_RUNG_POSE3 = 1, 2, 4, 8, 16
 
 
@@ -359,6 +377,7 @@ PRODUCT_SYMBOLS = [
     "lld_frame_create", "lld_frame_search_last_frame", "lld_frame_search_local_points", "lld_frame_destroy",
     "lld_frame_set_lines", "lld_track_params_default", "lld_frame_track_motion_model", "lld_frame_track_local_map", "lld_frame_track_download", "lld_frame_track_set_state",
     "lld_frame_compute_bow", "lld_frame_track_reference_keyframe", "lld_frame_relocalize",
+    "lld_frame_build_lines", "lld_frame_lines_download", "lld_frame_new_map_lines",
     "lld_sim3_params_default", "lld_optimize_sim3", "lld_optimize_sim3_batch",
     "lld_pose_graph_params_default", "lld_optimize_essential_graph",
     "lld_orb_extractor_create", "lld_orb_extractor_destroy", "lld_orb_extractor_levels_get", "lld_orb_extract", "lld_orb_extractor_pyramids",
@@ -522,6 +541,10 @@ class Lib:
             # (frame, vocabulary, levelsup, lld_bow_result* or NULL); (frame, lld_track_params*, lld_frame_view*, pose_qt, lld_ref_keyframe*):
             # the structs of vocabulary.py / tracking.py / orb_search.py pass by reference
             f("frame_compute_bow").argtypes = [vp, vp, C.c_int, vp]; f("frame_compute_bow").restype = C.c_int
+            f("frame_build_lines").argtypes = [vp, C.POINTER(FrameLinesBuild)]; f("frame_build_lines").restype = C.c_int
+            f("frame_lines_download").argtypes = [vp, c_int32_p, c_double_p]; f("frame_lines_download").restype = C.c_int
+            f("frame_new_map_lines").argtypes = [vp, vp, C.POINTER(FrameNewLinesParams), C.POINTER(FrameNewLinesResult)]
+            f("frame_new_map_lines").restype = C.c_int
             f("frame_track_reference_keyframe").argtypes = [vp, vp, vp, c_double_p, C.POINTER(RefKeyFrame)]
             f("frame_track_reference_keyframe").restype = C.c_int
             # (frame, lld_track_params*, lld_frame_view*, pose_qt, n_candidates, lld_ref_keyframe[], lld_reloc_candidate[], lld_pnp_params*, lld_reloc_result*)

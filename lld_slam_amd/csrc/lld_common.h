@@ -9,6 +9,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <utility>
 #include <vector>
 
 #include "../../include/lld_amd.h"
@@ -33,6 +34,11 @@ struct lld_ctx {
   // pinned host staging for entry points that move many small arrays in one copy
   void* pinned = nullptr;
   size_t pinned_bytes = 0;
+  // pinned staging buffers of lld_frame_build_lines that destroyed frames handed back (at most kLineStagingKept): a frame owns its buffer
+  // while it lives, because its build returns before the copy has run, but a caller makes one frame per image and hipHostMalloc per image
+  // costs more than the match
+  static constexpr size_t kLineStagingKept = 4;
+  std::vector<std::pair<void*, size_t>> line_staging;
   // small pinned block the single-window BA polls its progress counters through
   void* poll = nullptr;
   // kernel attributes are per device: remembered per context, not in a process-wide static (a process may hold contexts on several GPUs)

@@ -39,6 +39,7 @@ void lld_ctx_destroy(lld_ctx* ctx) {
   if (ctx->scratch) (void)hipFree(ctx->scratch);
   if (ctx->pinned) (void)hipHostFree(ctx->pinned);
   if (ctx->poll) (void)hipHostFree(ctx->poll);
+  for (auto& b : ctx->line_staging) (void)hipHostFree(b.first);
   if (ctx->ba.stage_free) { (void)hipEventSynchronize(ctx->ba.stage_free); (void)hipEventDestroy(ctx->ba.stage_free); }
   if (ctx->ba.slab) (void)hipFree(ctx->ba.slab);
   for (void* p : ctx->ba.stage) if (p) (void)hipHostFree(p);

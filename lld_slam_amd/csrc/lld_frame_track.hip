@@ -220,13 +220,21 @@ void fill_consts(lld_frame_track_state* S, const lld_track_params* P, const lld_
 
 namespace {
 
+// lld_frame_build_lines with no right lines: every left line is unmatched (-1, "no distance").
+__global__ void lines_unmatched_kernel(int n, int32_t* __restrict__ match, double* __restrict__ dist) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i < n) { match[i] = -1; dist[i] = 1.7976931348623157e308; }
+}
+
 // The fresh state f->track points at: keypoint-side arrays, the frame's lines (copied from `L`, may be null: a frame without lines), the records.
 // Synchronous (it is part of uploading a new frame, like lld_frame_create).  An error return leaves it half built: state_build takes it apart.
-int state_fill(lld_frame* f, const lld_frame_lines* L) {
+// With `Bd` (lld_frame_build_lines; L is then null) the lines come with BOTH descriptor sets in one copy from the frame's own pinned staging,
+// line_matches is what the stereo matcher's kernels write, and nothing waits: the chain follows on the stream.
+int state_fill(lld_frame* f, const lld_frame_lines* L, const lld_frame_lines_build* Bd) {
   lld_ctx* ctx = f->ctx;
   lld_frame_track_state* S = f->track;
-  const int nt = f->nt, nl = L ? L->n_left : 0, nr = L ? L->n_right : 0, dim = L ? L->dim : 1;
-  S->nl = nl; S->nr = nr; S->dim = dim; S->sx = L ? L->sx : 1.0; S->sy = L ? L->sy : 1.0;
+  const int nt = f->nt, nl = Bd ? Bd->n_left : L ? L->n_left : 0, nr = Bd ? Bd->n_right : L ? L->n_right : 0, dim = Bd ? Bd->dim : L ? L->dim : 1;
+  S->nl = nl; S->nr = nr; S->dim = dim; S->sx = Bd ? Bd->sx : L ? L->sx : 1.0; S->sy = Bd ? Bd->sy : L ? L->sy : 1.0;
   const int tracked_cap = 2 * nl + 16;
   S->seen_psize = seen_point_slots(nt); S->seen_lsize = seen_line_slots(nl);
   S->seen_lds = ((size_t)S->seen_psize + S->seen_lsize) * 4;
@@ -241,8 +249,14 @@ int state_fill(lld_frame* f, const lld_frame_lines* L) {
   const auto pose = B.take<double>(7), pout = B.take<double>(12); const auto view = B.take<lld_frame_view>(1); const auto lp = B.take<LineTrackDevParams>(1);
   UploadBlock LB;                                    // the frame's lines, a block of their own inside the state: they arrive in one copy
   const auto ll = LB.take<float>(nl, 4); const auto lo = LB.take<int32_t>(nl); const auto lr = LB.take<float>(std::max(nr, 1), 4); const auto ro = LB.take<int32_t>(std::max(nr, 1));
-  const auto lm = LB.take<int32_t>(nl); const auto ld = LB.take<float>(nl, dim);
-  LB.end_upload();
+  Span<int32_t> lm; Span<float> ld, rd; Span<double> md;
+  if (!Bd) { lm = LB.take<int32_t>(nl); ld = LB.take<float>(nl, dim); LB.end_upload(); }
+  else {
+    // the right descriptors ride in the same copy and are dead once the match is made (the state keeps their nr * dim * 4 bytes allocated);
+    // line_matches | match_dist behind the upload, contiguous: lld_frame_lines_download fetches both in one copy
+    ld = LB.take<float>(nl, dim); rd = LB.take<float>(nr, dim); LB.end_upload();
+    lm = LB.take<int32_t>(nl); md = LB.take<double>(nl);
+  }
   const auto lc = LB.take<int32_t>(nl); const auto lines = B.take<char>(LB.size);
   S->rec_off = B.size;
   Span<RecHeader> rh[2]; Span<int32_t> rk[2], rl[2]; Span<uint8_t> rko[2], rlo[2];
@@ -260,8 +274,38 @@ int state_fill(lld_frame* f, const lld_frame_lines* L) {
   for (int s = 0; s < 2; s++) { D.rec_h[s] = B.dev(rh[s]); D.rec_kp_id[s] = B.dev(rk[s]); D.rec_kp_out[s] = B.dev(rko[s]); D.rec_ln_id[s] = B.dev(rl[s]); D.rec_ln_out[s] = B.dev(rlo[s]); }
   LB.bind(nullptr, B.dev(lines));
   S->ln_left = LB.dev(ll); S->ln_loct = LB.dev(lo); S->ln_right = LB.dev(lr); S->ln_roct = LB.dev(ro); S->ln_match = LB.dev(lm); S->ln_desc = LB.dev(ld); S->ln_cell = LB.dev(lc);
+  S->ln_mdist = Bd ? LB.dev(md) : nullptr; S->match_bytes = Bd ? (md.off - lm.off) + (size_t)nl * 8 : (size_t)nl * 4;
   LLD_HIP_TRY(hipMemsetAsync(B.d, 0, B.size, ctx->stream));
-  if (nl > 0) {
+  if (Bd && nl > 0) {
+    if (LB.up_bytes > f->h_lines_bytes) {
+      // (no copy can be reading the old staging: a frame that had lines had a state, and replacing a state waits for the stream first)
+      if (f->h_lines) LLD_HIP_TRY(hipHostFree(f->h_lines));
+      f->h_lines = nullptr; f->h_lines_bytes = 0;
+      auto& kept = ctx->line_staging;                                          // a buffer a destroyed frame handed back, if one is large enough
+      for (size_t k = 0; k < kept.size() && !f->h_lines; k++)
+        if (kept[k].second >= LB.up_bytes) { f->h_lines = kept[k].first; f->h_lines_bytes = kept[k].second; kept.erase(kept.begin() + k); }
+      if (!f->h_lines) {
+        const size_t want = LB.up_bytes + (LB.up_bytes >> 2) + 4096;
+        if (hipHostMalloc(&f->h_lines, want, hipHostMallocDefault) != hipSuccess) { f->h_lines = nullptr; return LLD_ERR_ALLOC; }
+        f->h_lines_bytes = want;
+      }
+    }
+    void* d_match_work = nullptr;
+    if (nr > 0) { const int st = lld_ctx_scratch(ctx, line_stereo_work_bytes(nl, nr), &d_match_work); if (st) return st; }   // device scratch: ordered by the stream
+    LB.bind(static_cast<char*>(f->h_lines), LB.d);
+    std::memset(LB.h, 0, LB.up_bytes);
+    LB.stage(ll, Bd->left); LB.stage(lo, Bd->left_octave); LB.stage(ld, Bd->desc_left);
+    if (nr > 0) { LB.stage(lr, Bd->right); LB.stage(ro, Bd->right_octave); LB.stage(rd, Bd->desc_right); }
+    LLD_HIP_TRY(hipMemcpyAsync(LB.d, LB.h, LB.up_bytes, hipMemcpyHostToDevice, ctx->stream));
+    int st = line_cells_dev(ctx->stream, S->ln_left, nl, S->sx, S->sy, S->ln_cell); if (st) return st;
+    if (nr > 0) {
+      const LineStereoDev in{nl, nr, dim, S->ln_left, S->ln_loct, S->ln_right, S->ln_roct, S->ln_desc, LB.dev(rd)};
+      st = line_stereo_launch_dev(ctx->stream, Bd->stereo, in, d_match_work, LB.dev(lm), LB.dev(md)); if (st) return st;
+    } else {
+      hipLaunchKernelGGL(lines_unmatched_kernel, dim3((nl + 255) / 256), dim3(256), 0, ctx->stream, nl, LB.dev(lm), LB.dev(md));
+      LLD_HIP_TRY(hipGetLastError());
+    }
+  } else if (nl > 0) {
     // the lines travel through the context's pinned staging (synchronous: the staging is the context's)
     void* hb; int st = lld_ctx_pinned(ctx, LB.up_bytes, &hb); if (st) return st;
     LB.bind(static_cast<char*>(hb), LB.d);
@@ -272,17 +316,20 @@ int state_fill(lld_frame* f, const lld_frame_lines* L) {
     LLD_HIP_TRY(hipMemcpyAsync(LB.d, LB.h, LB.up_bytes, hipMemcpyHostToDevice, ctx->stream));
     st = line_cells_dev(ctx->stream, S->ln_left, nl, S->sx, S->sy, S->ln_cell); if (st) return st;
   }
-  LLD_HIP_TRY(hipStreamSynchronize(ctx->stream));
+  if (!Bd) LLD_HIP_TRY(hipStreamSynchronize(ctx->stream));
   for (int s = 0; s < 2; s++) LLD_HIP_TRY(hipEventCreateWithFlags(&S->uploaded[s], hipEventDisableTiming));
   return LLD_OK;
 }
 
 // (Re)builds the device state of a frame.  Every failure leaves the frame without one (hipFree waits for what state_fill queued on the block).
-int state_build(lld_frame* f, const lld_frame_lines* L) {
+int state_build(lld_frame* f, const lld_frame_lines* L, const lld_frame_lines_build* Bd = nullptr) {
   lld_track::state_free(f);
   f->track = new lld_frame_track_state();
-  const int st = state_fill(f, L);
-  if (st) lld_track::state_free(f);
+  const int st = state_fill(f, L, Bd);
+  if (st) {
+    if (Bd) (void)hipStreamSynchronize(f->ctx->stream);                      // the queued copy must have left the frame's staging before a next call packs it
+    lld_track::state_free(f);
+  }
   return st;
 }
 
@@ -386,6 +433,8 @@ int check_lines(const lld_map_lines* ML) {
 
 namespace lld_track {
 int ensure_state(lld_frame* f) { return f->track ? LLD_OK : state_build(f, nullptr); }
+int frame_max_lines(int nt) { return track_max_lines(nt); }
+int frame_state_build_lines(lld_frame* f, const lld_frame_lines_build* Bd) { return state_build(f, nullptr, Bd); }
 int ref_keyframe_check(const lld_ref_keyframe* kf, int* n_features) {
   const int n = kf->n, nn = kf->n_nodes;
   *n_features = 0;

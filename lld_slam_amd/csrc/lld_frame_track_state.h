@@ -124,6 +124,9 @@ struct lld_frame_track_state {
   int nl = 0, nr = 0, dim = 0; double sx = 0, sy = 0;
   const float* ln_left = nullptr; const int32_t* ln_loct = nullptr; const float* ln_right = nullptr; const int32_t* ln_roct = nullptr;
   const int32_t* ln_match = nullptr; const float* ln_desc = nullptr; int32_t* ln_cell = nullptr;
+  // lld_frame_build_lines: the accepted stereo distances behind ln_match (null on a frame of lld_frame_set_lines); bytes of the span
+  // ln_match [| ln_mdist] that lld_frame_lines_download fetches
+  const double* ln_mdist = nullptr; size_t match_bytes = 0;
   // per-call work: uploaded inputs + search / line / pose scratch (grow-only), one pinned staging region per stage
   char* d_work = nullptr; size_t work_bytes = 0;
   char* h_stage[2] = {nullptr, nullptr}; size_t h_stage_bytes[2] = {0, 0};
@@ -138,6 +141,10 @@ struct lld_frame_track_state {
 namespace lld_track {
 // host plumbing of a stage (lld_frame_track.hip)
 int ensure_state(lld_frame* f);                                            // the state exists (a frame without lines unless lld_frame_set_lines ran)
+int frame_max_lines(int nt);                                               // the most lines the chain tracks next to nt keypoints (lld_frame_set_lines' limit)
+// (re)builds the state with the lines of lld_frame_build_lines (null or n_left = 0: without lines); queues the upload, the cells and the
+// stereo match on the context's stream and does not wait.  The caller has validated `Bd` and waited if a state existed.
+int frame_state_build_lines(lld_frame* f, const lld_frame_lines_build* Bd);
 int ensure_stage(lld_frame_track_state* S, int s, size_t bytes);           // grow-only pinned staging of stage s, free of its previous upload
 // begin: the grow-only d_work holds everything B declared (the stream is synchronised before it is reallocated), the pinned staging of stage s the uploaded prefix,
 // and B is bound to the two; submit: the one copy of that prefix is queued

@@ -721,15 +721,24 @@ __device__ __forceinline__ void image_line_of(const double* K, const double* R, 
 }
 
 // grid n_cur, block 64; dynamic LDS: dim floats (the current line's descriptor)
+// kDev: both frames are resident (lld_frame_new_map_lines): the two cameras are the LineTrackParams their chains left in device memory
+// (cur_cam also brings K, sx, sy); P then carries thr_base, md_thr and use_grid only.
+template <bool kDev>
 __global__ __launch_bounds__(64) void line_lastkf_kernel(LastKfParams P, int n_cur, const float* __restrict__ cur_left, const float* __restrict__ cur_right,
                                                         const int* __restrict__ cur_lm, const uint8_t* __restrict__ cur_occ, const float* __restrict__ cur_desc,
                                                         int n_last, const float* __restrict__ last_left, const int* __restrict__ last_oct,
                                                         const float* __restrict__ last_right, const int* __restrict__ last_lm,
                                                         const uint8_t* __restrict__ last_skip, const float* __restrict__ last_desc, const int* __restrict__ last_cell,
                                                         int dim, int* __restrict__ match_last, uint8_t* __restrict__ created, double* __restrict__ x0_out,
-                                                        double* __restrict__ dir_out) {
+                                                        double* __restrict__ dir_out, const LineTrackParams* __restrict__ cur_cam,
+                                                        const LineTrackParams* __restrict__ last_cam) {
   extern __shared__ __attribute__((aligned(16))) float qrow[];
   const int i = blockIdx.x, lane = threadIdx.x;
+  if (kDev) {
+    for (int k = 0; k < 9; k++) { P.K[k] = cur_cam->K[k]; P.R[k] = cur_cam->R[k]; P.Rl[k] = last_cam->R[k]; }
+    for (int k = 0; k < 3; k++) { P.t[k] = cur_cam->t[k]; P.tr[k] = cur_cam->tr[k]; P.tl[k] = last_cam->t[k]; P.tlr[k] = last_cam->tr[k]; }
+    P.sx = cur_cam->sx; P.sy = cur_cam->sy;
+  }
   if (lane == 0) { match_last[i] = -1; created[i] = 0; for (int k = 0; k < 3; k++) { x0_out[3 * i + k] = 0.0; dir_out[3 * i + k] = 0.0; } }
   if (cur_occ && cur_occ[i]) return;
   const int ri = cur_lm[i];
@@ -1160,12 +1169,12 @@ int lld_line_match_last_frame(lld_ctx* ctx, const lld_line_lastkf_params* prm, i
   P.thr_base = prm->thr_reproj_base; P.md_thr = prm->md_thr; P.sx = prm->sx; P.sy = prm->sy; P.use_grid = prm->use_grid;
   int* dcell = reinterpret_cast<int*>(d_dev);
   if (n_last > 0) hipLaunchKernelGGL(line_cells_kernel, dim3((n_last + 255) / 256), dim3(256), 0, sm, reinterpret_cast<const float*>(d + o_ll), n_last, P.sx, P.sy, dcell);
-  hipLaunchKernelGGL(line_lastkf_kernel, dim3(n_cur), dim3(64), (size_t)dim * 4 + 16, sm, P, n_cur, reinterpret_cast<const float*>(d + o_cl),
+  hipLaunchKernelGGL(line_lastkf_kernel<false>, dim3(n_cur), dim3(64), (size_t)dim * 4 + 16, sm, P, n_cur, reinterpret_cast<const float*>(d + o_cl),
                      reinterpret_cast<const float*>(d + o_cr), reinterpret_cast<const int*>(d + o_clm), reinterpret_cast<const uint8_t*>(d + o_co),
                      reinterpret_cast<const float*>(d + o_cd), n_last, reinterpret_cast<const float*>(d + o_ll), reinterpret_cast<const int*>(d + o_lo),
                      reinterpret_cast<const float*>(d + o_lr), reinterpret_cast<const int*>(d + o_llm), reinterpret_cast<const uint8_t*>(d + o_ls),
                      reinterpret_cast<const float*>(d + o_ld), dcell, dim, reinterpret_cast<int*>(d_out + r_m), reinterpret_cast<uint8_t*>(d_out + r_c),
-                     reinterpret_cast<double*>(d_out + r_x), reinterpret_cast<double*>(d_out + r_d));
+                     reinterpret_cast<double*>(d_out + r_x), reinterpret_cast<double*>(d_out + r_d), nullptr, nullptr);
   LLD_HIP_TRY(hipGetLastError());
   LLD_HIP_TRY(hipMemcpyAsync(h_out, d_out, out, hipMemcpyDeviceToHost, sm));
   LLD_HIP_TRY(hipStreamSynchronize(sm));
@@ -1213,6 +1222,52 @@ int line_track_launch_dev(lld_ctx* ctx, hipStream_t st, const LineTrackDevParams
                      nullptr, dmat, dc);
   { const int rs = line_resolve_prepare(n_map, n_cur); if (rs) return rs; }
   hipLaunchKernelGGL(line_resolve_kernel, dim3(1), dim3(kResolveThreads), line_resolve_lds(n_map, n_cur), st, dc, dmat, dgate, n_map, n_cur, tau, matches_d, nullptr, apply, map.x0, map.dir);
+  LLD_HIP_TRY(hipGetLastError());
+  return LLD_OK;
+}
+
+// TwoFrameLineMatcher::MatchLines of a frame's own stereo pair (lld_line_match_stereo's two kernels) on device arrays: the resolve writes the
+// frame's line_matches where the chain reads them.
+int line_stereo_check(int nl, int nr, int dim) {
+  if (dim > LLD_LINE_DIM_MAX) return LLD_ERR_UNSUPPORTED;
+  if (nl <= 0 || nr <= 0) return LLD_OK;
+  if ((size_t)nr * 8 + (size_t)dim * 4 > LLD_LINE_LDS_CEILING || line_resolve_lds(nl, nr) > LLD_LINE_LDS_CEILING) return LLD_ERR_UNSUPPORTED;
+  return LLD_OK;
+}
+size_t line_stereo_work_bytes(int nl, int nr) {
+  const size_t pairs = (size_t)nl * (size_t)nr;
+  return lt_pad(pairs) + lt_pad(pairs * 8) + lt_pad((size_t)nl * sizeof(LineCand)) + 256;
+}
+int line_stereo_launch_dev(hipStream_t st, const lld_line_stereo_params& prm, const LineStereoDev& in, void* d_work, int32_t* matches_d, double* match_dist_d) {
+  const int nl = in.nl, nr = in.nr, dim = in.dim;
+  if (nl <= 0 || nr <= 0) return LLD_OK;
+  { const int cs = line_stereo_check(nl, nr, dim); if (cs) return cs; }
+  const size_t pairs = (size_t)nl * (size_t)nr;
+  char* w = static_cast<char*>(d_work);
+  uint8_t* dgate = reinterpret_cast<uint8_t*>(w);
+  double* dmat = reinterpret_cast<double*>(w + lt_pad(pairs));
+  LineCand* dc = reinterpret_cast<LineCand*>(w + lt_pad(pairs) + lt_pad(pairs * 8));
+  LineGateParams P; std::memset(&P, 0, sizeof P);
+  for (int i = 0; i < 9; i++) P.K[i] = prm.K[i];
+  P.b = prm.b; P.min_len = (double)prm.min_line_length; P.is_stereo = prm.is_stereo;
+  const size_t lds = (size_t)nr * 8 + (size_t)dim * 4 + 16;
+  if (lds > 48 * 1024) LLD_HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(&line_candidates_kernel<true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+  hipLaunchKernelGGL(line_candidates_kernel<true>, dim3(nl), dim3(64), lds, st, P, in.left, in.loct, in.right, in.roct, in.dl, in.dr, dim, nr, nullptr, prm.tau, dgate, dmat, dc);
+  { const int rs = line_resolve_prepare(nl, nr); if (rs) return rs; }
+  hipLaunchKernelGGL(line_resolve_kernel, dim3(1), dim3(kResolveThreads), line_resolve_lds(nl, nr), st, dc, dmat, dgate, nl, nr, prm.tau, matches_d, match_dist_d,
+                     LineApplyDev{}, nullptr, nullptr);
+  LLD_HIP_TRY(hipGetLastError());
+  return LLD_OK;
+}
+
+// Tracking::MatchLinesLastKF on two resident frames: lld_line_match_last_frame's kernel with every operand in HBM.
+int line_lastkf_launch_dev(hipStream_t st, const LastKfDev& in, double thr_base, double md_thr, int use_grid, int32_t* match_last, uint8_t* created, double* x0, double* dir) {
+  if (in.cur.n_cur <= 0) return LLD_OK;
+  LastKfParams P; std::memset(&P, 0, sizeof P);
+  P.thr_base = thr_base; P.md_thr = md_thr; P.use_grid = use_grid;
+  hipLaunchKernelGGL(line_lastkf_kernel<true>, dim3(in.cur.n_cur), dim3(64), (size_t)in.cur.dim * 4 + 16, st, P, in.cur.n_cur, in.cur.left, in.cur.right, in.cur.lmatch,
+                     in.cur.occupied, in.cur.desc, in.last.n_cur, in.last.left, in.last.loct, in.last.right, in.last.lmatch, in.last_skip, in.last.desc, in.last.cell,
+                     in.cur.dim, match_last, created, x0, dir, reinterpret_cast<const LineTrackParams*>(in.cur_cam), reinterpret_cast<const LineTrackParams*>(in.last_cam));
   LLD_HIP_TRY(hipGetLastError());
   return LLD_OK;
 }

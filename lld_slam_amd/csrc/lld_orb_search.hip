@@ -1290,6 +1290,10 @@ extern "C" void lld_frame_destroy(lld_frame* f) {
   lld_track::state_free(f);
   if (f->d) (void)hipFree(f->d);
   if (f->h_stage) (void)hipHostFree(f->h_stage);
+  if (f->h_lines) {                                                           // (the stream was waited for above: no copy reads it)
+    if (f->ctx->line_staging.size() < lld_ctx::kLineStagingKept) f->ctx->line_staging.emplace_back(f->h_lines, f->h_lines_bytes);
+    else (void)hipHostFree(f->h_lines);
+  }
   if (f->d_bow) (void)hipFree(f->d_bow);
   delete f;
 }

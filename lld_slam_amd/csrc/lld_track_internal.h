@@ -28,6 +28,8 @@ struct lld_frame {
   bool stereo_built = false;
   size_t o_res = 0, o_depth = 0, o_bestr = 0, o_sad = 0, o_sum = 0, res_bytes = 0;
   void* h_stage = nullptr;
+  // lld_frame_build_lines (lld_frame_lines.hip): the pinned staging of its one upload, grow-only and the frame's own for the same reason.
+  void* h_lines = nullptr; size_t h_lines_bytes = 0;
   // A frame built by lld_frame_build_mono* (lld_frame_mono.hip): the kernel wrote mvKeysUn, mvuRight and mvDepth into `d`; o_res is the start of
   // the contiguous block u_right | depth | xy that lld_frame_keypoints_download fetches in one copy.  h_stage as above.
   bool mono_built = false;
@@ -114,6 +116,18 @@ int line_cells_dev(hipStream_t st, const float* d_left, int n, double sx, double
 // params_d: LineTrackDevParams in device memory (written by the tracker's pose kernel); matches_d [n_map]
 int line_track_launch_dev(lld_ctx* ctx, hipStream_t st, const LineTrackDevParams* params_d, const LineMapDev& map, const LineFrameDev& cur, double md_thr,
                           void* d_work, int32_t* matches_d, const LineApplyDev& apply);
+
+// TwoFrameLineMatcher::MatchLines of the frame's stereo pair (the kernels of lld_line_match_stereo) on device arrays: matches_d [nl] is the
+// frame's line_matches, match_dist_d [nl] the accepted distances (DBL_MAX where none).  check: the limits of lld_line_match_stereo
+// (LLD_ERR_UNSUPPORTED), decided from the counts alone; nothing is launched when either side is empty.
+struct LineStereoDev { int nl, nr, dim; const float* left; const int32_t* loct; const float* right; const int32_t* roct; const float* dl; const float* dr; };
+int line_stereo_check(int nl, int nr, int dim);
+size_t line_stereo_work_bytes(int nl, int nr);
+int line_stereo_launch_dev(hipStream_t st, const lld_line_stereo_params& prm, const LineStereoDev& in, void* d_work, int32_t* matches_d, double* match_dist_d);
+// Tracking::MatchLinesLastKF (the kernel of lld_line_match_last_frame) between two resident frames: `last` is a LineFrameDev whose n_cur counts
+// the last frame's lines; the cameras are the frames' own LineTrackDevParams in device memory (K, sx, sy from cur_cam).
+struct LastKfDev { LineFrameDev cur, last; const uint8_t* last_skip; const LineTrackDevParams* cur_cam; const LineTrackDevParams* last_cam; };
+int line_lastkf_launch_dev(hipStream_t st, const LastKfDev& in, double thr_base, double md_thr, int use_grid, int32_t* match_last, uint8_t* created, double* x0, double* dir);
 
 // ---------------------------------------------------------------- Optimizer::PoseOptimization on the frame's device state (lld_pose.hip)
 struct PoseTrackDev {

@@ -839,11 +839,14 @@ def make_local_map(F, scene_id=0, n=2000, related_frac=0.8, flip_p=0.06, pos_noi
                    skip=(rng.random(n) < 0.1).astype(np.uint8), occupied=(rng.random(F.n) < 0.05).astype(np.uint8), src=src.astype(np.int32))
 
 
-def make_tracking_scene(scene_id=0, n_kp=2000, n_map=2500, n_last=1200, rot_deg=0.25, trans=0.04, n_lines=300, n_map_lines=260, n_last_lines=140):
+def make_tracking_scene(scene_id=0, n_kp=2000, n_map=2500, n_last=1200, rot_deg=0.25, trans=0.04, n_lines=300, n_map_lines=260, n_last_lines=140,
+                        line_depth=(3.0, 40.0), line_length=(0.3, 2.5)):
     """One consistent little world for the Tracking thread's per-frame sequence (lld_slam_amd/tracking.py): a frame with `n_kp` keypoints,
     its true pose, `n_map` local MapPoints most of which are back-projections of the keypoints (make_local_map), the first `n_last` of them
     also being the last frame's tracked points (with that frame's octaves / angles), and the motion model's prediction of the pose - the
-    true pose moved by `rot_deg` degrees and `trans` metres.  Returns a dict."""
+    true pose moved by `rot_deg` degrees and `trans` metres.  `line_depth`, `line_length`: the depth and length ranges of the 3D lines in metres (TwoFrameLineMatcher's
+    triangulation-angle gate passes a stereo pair of this rig only within 2.4 m: a scene whose line_matches are to come from that matcher
+    wants near lines, and short ones to keep them inside the image).  Returns a dict."""
     rng = np.random.default_rng(SEED_SEARCH + 0x7000 + scene_id)
     F = make_orb_frame(200 + scene_id, n_kp)
     T, mp = make_local_map(F, 200 + scene_id, n_map, pos_noise=0.0004)          # MapPoints that re-project within a pixel: PoseOptimization keeps them
@@ -859,12 +862,12 @@ def make_tracking_scene(scene_id=0, n_kp=2000, n_map=2500, n_last=1200, rot_deg=
     sc = dict(frame=F, cam=KITTI_CAM, Tcw_true=T, Tcw_guess=Tg, pose_true=_tcw_to_qt(T.astype(np.float64)), pose_guess=_tcw_to_qt(Tg.astype(np.float64)),
               last=last, last_ids=np.arange(n_last), map_points=mp, map_ids=np.arange(n_map))
     if n_lines > 0:
-        sc.update(make_tracking_lines(scene_id, T.astype(np.float64), n_map_lines, n_lines, n_last_lines, Tcw_guess=Tg.astype(np.float64)))
+        sc.update(make_tracking_lines(scene_id, T.astype(np.float64), n_map_lines, n_lines, n_last_lines, Tcw_guess=Tg.astype(np.float64), depth=line_depth, length=line_length))
     return sc
 
 
 def make_tracking_lines(scene_id, Tcw, n_map=260, n_cur=300, n_last=140, dim=72, related_frac=0.75, pixel_noise=0.4, desc_noise=0.05, no_partner_frac=0.1,
-                        outlier_frac=0.12, Tcw_guess=None, trap_frac=0.12):
+                        outlier_frac=0.12, Tcw_guess=None, trap_frac=0.12, depth=(3.0, 40.0), length=(0.3, 2.5)):
     """The line half of make_tracking_scene: `n_cur` stereo lines of the frame at the true pose Tcw (world -> camera), `n_map` MapLines of which
     the first `related_frac * min(n_map, n_cur)` project onto frame lines (a few with a pose-inconsistent 3D position that passes the 2-pixel
     association gate of the predicted pose only sometimes, and PoseOptimization must then throw out), the rest elsewhere or behind the camera.
@@ -874,12 +877,12 @@ def make_tracking_lines(scene_id, Tcw, n_map=260, n_cur=300, n_last=140, dim=72,
     fx, fy, cx, cy, bf = [float(np.float32(c)) for c in KITTI_CAM]
     b = float(np.float32(np.float32(bf) / np.float32(fx)))
     Rcw = Tcw[:3, :3]; tcw = Tcw[:3, 3]
-    z = rng.uniform(3.0, 40.0, n_map)
+    z = rng.uniform(depth[0], depth[1], n_map)
     c = np.stack([(rng.uniform(60, 1180, n_map) - cx) * z / fx, (rng.uniform(30, 340, n_map) - cy) * z / fy, z], 1)
     behind = rng.random(n_map) < 0.04
     c[behind, 2] = -rng.uniform(1.0, 10.0, int(behind.sum()))
     d = rng.normal(size=(n_map, 3)); d[:, 2] *= 0.3; d /= np.linalg.norm(d, axis=1, keepdims=True)
-    half = rng.uniform(0.3, 2.5, n_map)[:, None] * 0.5
+    half = rng.uniform(length[0], length[1], n_map)[:, None] * 0.5
     A, B = c - half * d, c + half * d                                        # camera frame of the TRUE pose
 
     def proj(X, shift):

@@ -189,7 +189,9 @@ def ref_keyframe_struct(kf: dict):
 
 class DeviceTrackedFrame:
     """lld_frame_track_*: the whole per-frame sequence on the device (include/lld_amd.h).  `lines`: dict with left_lines [n,4], left_octave,
-    right_lines, right_octave, line_matches, desc (the frame's mvLinesLeft / mvLinesRight / line_matches / mDescriptorsLines) or None."""
+    right_lines, right_octave, line_matches, desc (the frame's mvLinesLeft / mvLinesRight / line_matches / mDescriptorsLines) or None.  A dict
+    that carries desc_right and stereo (TwoFrameLineMatcher's parameters) instead of line_matches has its lines matched on the device
+    (lld_frame_build_lines, see _build_lines)."""
 
     def __init__(self, ctx, F: orb_search.Frame, cam, lines: dict | None = None, gamma=0.5, **params):
         self.ctx, self.lib, self.F, self.cam = ctx, ctx.lib, F, cam
@@ -226,7 +228,9 @@ class DeviceTrackedFrame:
         lib.fn("frame_track_local_map").restype = C.c_int
         lib.fn("frame_track_download").argtypes = [C.c_void_p, C.POINTER(TrackResult), C.POINTER(TrackResult)]; lib.fn("frame_track_download").restype = C.c_int
         self.n_lines = 0; self.n_local_points = 0
-        if lines is not None:
+        if lines is not None and lines.get("desc_right") is not None:
+            self._build_lines(lines)
+        elif lines is not None:
             k = dict(left=np.ascontiguousarray(lines["left_lines"], np.float32).reshape(-1, 4), lo=np.ascontiguousarray(lines["left_octave"], np.int32),
                      right=np.ascontiguousarray(lines["right_lines"], np.float32).reshape(-1, 4), ro=np.ascontiguousarray(lines["right_octave"], np.int32),
                      lm=np.ascontiguousarray(lines["line_matches"], np.int32), desc=np.ascontiguousarray(lines["desc"], np.float32))
@@ -244,9 +248,48 @@ class DeviceTrackedFrame:
         for k_, v in params.items():
             setattr(self.params, k_, v)
 
+    def _build_lines(self, lines):
+        """lld_frame_build_lines: `lines` carries desc_right [n_right, dim] and stereo = dict(K [3,3], b, tau, min_line_length, is_stereo)
+        instead of line_matches; the stereo association is made on the device and stays there (lines_download() fetches it)."""
+        F = self.F
+        k = dict(left=np.ascontiguousarray(lines["left_lines"], np.float32).reshape(-1, 4), lo=np.ascontiguousarray(lines["left_octave"], np.int32),
+                 right=np.ascontiguousarray(lines["right_lines"], np.float32).reshape(-1, 4), ro=np.ascontiguousarray(lines["right_octave"], np.int32),
+                 dl=np.ascontiguousarray(lines["desc"], np.float32), dr=np.ascontiguousarray(lines["desc_right"], np.float32))
+        sp = lines["stereo"]
+        L = abi.FrameLinesBuild()
+        L.n_left = k["left"].shape[0]; L.left = k["left"].ctypes.data_as(c_float_p); L.left_octave = k["lo"].ctypes.data_as(c_int32_p)
+        L.desc_left = k["dl"].ctypes.data_as(c_float_p)
+        L.n_right = k["right"].shape[0]; L.right = k["right"].ctypes.data_as(c_float_p); L.right_octave = k["ro"].ctypes.data_as(c_int32_p)
+        L.desc_right = k["dr"].ctypes.data_as(c_float_p)
+        L.dim = k["dl"].shape[1] if k["dl"].ndim == 2 else int(lines["dim"])
+        L.sx = 1.0 / float(F.max_x); L.sy = 1.0 / float(F.max_y)
+        L.stereo = abi.LineStereoParams((C.c_double * 9)(*np.asarray(sp["K"], np.float64).ravel()), float(sp["b"]), float(sp["tau"]),
+                                        int(sp["min_line_length"]), int(sp.get("is_stereo", 1)))
+        self._check(self.lib.fn("frame_build_lines")(self.res.handle, C.byref(L)), "lld_frame_build_lines")
+        self.n_lines = int(L.n_left)
+
+    def lines_download(self):
+        """lld_frame_lines_download: waits for the frame's queued work; (line_matches [n_left] i32, match_dist [n_left] f64)."""
+        lm = np.full(self.n_lines, -1, np.int32); md = np.zeros(self.n_lines, np.float64)
+        self._check(self.lib.fn("frame_lines_download")(self.res.handle, lm.ctypes.data_as(c_int32_p), md.ctypes.data_as(c_double_p)), "lld_frame_lines_download")
+        return lm, md
+
+    def new_map_lines(self, last_frame: "DeviceTrackedFrame", first_new_id: int, thr_reproj_base=6.0, md_thr=None, use_grid=1):
+        """lld_frame_new_map_lines: Tracking::MatchLinesLastKF between this frame and `last_frame`, both resident.  Returns a dict with
+        n_created, n_held, match_last, created, x0, dir, new_id; the created lines have entered this frame's state."""
+        n = self.n_lines
+        a = dict(match_last=np.full(n, -1, np.int32), created=np.zeros(n, np.uint8), x0=np.zeros((n, 3)), dir=np.zeros((n, 3)), new_id=np.full(n, -1, np.int32))
+        P = abi.FrameNewLinesParams(float(thr_reproj_base), float(self.params.line_md_thr if md_thr is None else md_thr), int(use_grid), int(first_new_id))
+        R = abi.FrameNewLinesResult(0, 0, a["match_last"].ctypes.data_as(c_int32_p), a["created"].ctypes.data_as(c_uint8_p), a["x0"].ctypes.data_as(c_double_p),
+                                    a["dir"].ctypes.data_as(c_double_p), a["new_id"].ctypes.data_as(c_int32_p))
+        self._check(self.lib.fn("frame_new_map_lines")(self.res.handle, last_frame.res.handle, C.byref(P), C.byref(R)), "lld_frame_new_map_lines")
+        return dict(a, n_created=int(R.n_created), n_held=int(R.n_held))
+
     def _check(self, st, what):
         if st != abi.LLD_OK:
-            raise RuntimeError(f"{what} failed: {self.lib.fn('status_string')(st).decode()}")
+            err = RuntimeError(f"{what} failed: {self.lib.fn('status_string')(st).decode()}")
+            err.status = st
+            raise err
 
     def close(self):
         if self.res is not None:
