@@ -222,6 +222,90 @@ int FrameOnDevice::MatchLinesLastKF(const TrackingMembers& tr, Frame& Cur, Frame
   return r.n_created + r.n_held;                                              // :1610
 }
 
+namespace {
+void bind(FinishTrace& T, int n) {
+  T.created.assign(n + 1, 0); T.new_id.assign(n + 1, -1); T.kp_point_id.assign(n + 1, -1); T.order.assign(n + 1, -1); T.x3d.assign(3 * (size_t)n + 3, 0.f);
+  std::memset(&T.r, 0, sizeof T.r);
+  T.r.created = T.created.data(); T.r.new_id = T.new_id.data(); T.r.kp_point_id = T.kp_point_id.data(); T.r.order = T.order.data(); T.r.x3d = T.x3d.data();
+}
+// the created keypoints in visiting order: the order the reference's loop runs its constructors in
+std::vector<int> creation_order(const FinishTrace& T, int n) {
+  std::vector<int> at(n + 1, -1);                                             // at[rank] = keypoint
+  for (int i = 0; i < n; i++) if (T.order[i] >= 0) at[T.order[i]] = i;
+  std::vector<int> made;
+  for (int j = 0; j < n; j++) if (at[j] >= 0 && T.created[at[j]]) made.push_back(at[j]);
+  return made;
+}
+lld_slam::Mat point_of_result(const FinishTrace& T, int i) { return lld_slam::Mat(3, 1, &T.x3d[3 * (size_t)i]); }
+}  // namespace
+
+// The frame was made by lld_frame_create, which keeps no depth: mvDepth travels with the call.
+bool FrameOnDevice::NeedNewKeyFrame(const TrackingMembers& tr, const KeyFrameDecision& d, Frame& Cur, bool* interruptBA, FinishTrace* trace) {
+  for (int i = 0; i < nt_; i++) {                                             // Clean VO matches (:446-453)
+    MapPoint* pMP = Cur.mvpMapPoints[i];
+    if (pMP && pMP->Observations() < 1) { Cur.mvbOutlier[i] = false; Cur.mvpMapPoints[i] = static_cast<MapPoint*>(NULL); }
+  }
+  lld_frame_finish_params p; std::memset(&p, 0, sizeof p);
+  p.th_depth = d.mThDepth; p.first_new_id = (int32_t)MapPoint::nNextId(); p.force = -1;
+  p.only_tracking = tr.mbOnlyTracking; p.mapper_stopped = d.mapperStopped; p.mapper_idle = d.bLocalMappingIdle; p.keyframes_in_queue = d.KeyframesInQueue;
+  p.set_not_stop_ok = d.setNotStopOk; p.monocular = d.monocular; p.sensor_rgbd = d.rgbd; p.max_frames = d.mMaxFrames; p.min_frames = d.mMinFrames;
+  p.n_keyframes = d.nKFs; p.n_ref_matches = d.nRefMatches; p.n_matches_inliers = d.mnMatchesInliers;
+  p.frame_id = (int64_t)Cur.mnId; p.last_reloc_frame_id = (int64_t)d.mnLastRelocFrameId; p.last_keyframe_id = (int64_t)d.mnLastKeyFrameId;
+  p.depth = Cur.mvDepth.data();
+  bind(finish_, nt_);
+  check(lld_frame_track_finish(f_, &p, &finish_.r), "lld_frame_track_finish");
+  finish_made_ = finish_.r.made != 0;
+  if (interruptBA) *interruptBA = finish_.r.interrupt_ba != 0;
+  if (trace) {                                                                // a copy whose pointers name its own arrays
+    *trace = finish_;
+    trace->r.created = trace->created.data(); trace->r.new_id = trace->new_id.data(); trace->r.kp_point_id = trace->kp_point_id.data();
+    trace->r.order = trace->order.data(); trace->r.x3d = trace->x3d.data();
+  }
+  return finish_.r.need != 0;
+}
+
+void FrameOnDevice::CreateNewKeyFrame(const TrackingMembers& tr, Frame& Cur, KeyFrame* pKF, lld_slam::Map* mpMap, FrameOnDevice* lastOnDevice, std::vector<MapPoint*>* created) {
+  if (created) created->assign(nt_, static_cast<MapPoint*>(NULL));
+  if (!finish_made_) return;                                                  // :1369
+  const std::vector<int> made = creation_order(finish_, nt_);
+  for (size_t k = 0; k < made.size(); k++) {                                  // :1399-1429, the entries with bCreateNew
+    const int i = made[k];
+    MapPoint* pNewMP = new MapPoint(point_of_result(finish_, i), pKF, mpMap);
+    if ((int32_t)pNewMP->mnId != finish_.new_id[i]) throw std::runtime_error("lld_frame_track_finish: MapPoint ids left the device's numbering");
+    pNewMP->AddObservation(pKF, i);
+    pKF->AddMapPoint(pNewMP, i);
+    mpMap->AddMapPoint(pNewMP);
+    Cur.mvpMapPoints[i] = pNewMP;
+    if (created) (*created)[i] = pNewMP;
+  }
+  if (lastOnDevice && nl_ > 0) MatchLinesLastKF(tr, Cur, *lastOnDevice, pKF, mpMap);   // :1432-1434
+}
+
+void FrameOnDevice::DropOutliers(Frame& Cur) const {
+  for (int i = 0; i < nt_; i++)                                               // :472-476
+    if (Cur.mvpMapPoints[i] && Cur.mvbOutlier[i]) Cur.mvpMapPoints[i] = static_cast<MapPoint*>(NULL);
+}
+
+void FrameOnDevice::UpdateLastFrame(const TrackingMembers& tr, float mThDepth, Frame& Last, lld_slam::Map* mpMap, std::vector<MapPoint*>* mlpTemporalPoints) {
+  params_.pose.gamma = tr.gamma; params_.line_md_thr = tr.mdThr;
+  const lld_frame_view view = view_of(Last);                                  // mLastFrame.SetPose(Tlr*pRef->GetPose()) ran (:825)
+  double qt[7];
+  lld_se3_from_tcw_f32(Last.mTcw.ptr<float>(), qt);
+  lld_frame_points_params p; std::memset(&p, 0, sizeof p);
+  p.mode = LLD_POINTS_LAST_FRAME; p.th_depth = mThDepth; p.first_new_id = (int32_t)MapPoint::nNextId(); p.params = &params_; p.view = &view; p.pose_qt = qt;
+  p.depth = Last.mvDepth.data();
+  FinishTrace T; bind(T, nt_);
+  check(lld_frame_create_stereo_points(f_, &p, &T.r), "lld_frame_create_stereo_points");
+  const std::vector<int> made = creation_order(T, nt_);
+  for (size_t k = 0; k < made.size(); k++) {                                  // :865-874
+    const int i = made[k];
+    MapPoint* pNewMP = new MapPoint(point_of_result(T, i), static_cast<KeyFrame*>(NULL), mpMap);
+    if ((int32_t)pNewMP->mnId != T.new_id[i]) throw std::runtime_error("lld_frame_create_stereo_points: MapPoint ids left the device's numbering");
+    Last.mvpMapPoints[i] = pNewMP;
+    if (mlpTemporalPoints) mlpTemporalPoints->push_back(pNewMP);
+  }
+}
+
 FrameOnDevice::~FrameOnDevice() { if (f_) lld_frame_destroy(f_); }
 
 bool FrameOnDevice::TrackWithMotionModel(const TrackingMembers& tr, Frame& Cur, const Frame& Last, bool* mbVO, TrackTrace* trace) {

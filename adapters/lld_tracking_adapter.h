@@ -41,6 +41,24 @@ struct TrackTrace { lld_track_result r; std::vector<int32_t> kp_point_id, ln_lin
 // What Relocalization got back (optional, as TrackTrace): lld_reloc_result with its per-candidate arrays owned here.
 struct RelocTrace { lld_reloc_result r; std::vector<int32_t> n_bow, rounds, n_good_last, rungs, n_additional1, n_additional2; std::vector<uint8_t> discarded; };
 
+// What Tracking::NeedNewKeyFrame and CreateNewKeyFrame read off `this`, mpLocalMapper and mpMap (src/Tracking.cc:1227-1309, :1369), gathered by the
+// caller before the one device call that decides and creates.
+struct KeyFrameDecision {
+  float mThDepth = 0;
+  bool mapperStopped = false;          // mpLocalMapper->isStopped() || mpLocalMapper->stopRequested() (:1231)
+  bool bLocalMappingIdle = true;       // mpLocalMapper->AcceptKeyFrames() (:1247)
+  int KeyframesInQueue = 0;            // mpLocalMapper->KeyframesInQueue() (:1299)
+  bool setNotStopOk = true;            // mpLocalMapper->SetNotStop(true) (:1369): taken before the call; the caller undoes it (SetNotStop(false)) when no keyframe is made
+  int nKFs = 0;                        // mpMap->KeyFramesInMap()
+  int nRefMatches = 0;                 // mpReferenceKF->TrackedMapPoints(nKFs <= 2 ? 2 : 3)
+  int mnMatchesInliers = 0;
+  int mMaxFrames = 0, mMinFrames = 0;
+  unsigned long mnLastRelocFrameId = 0, mnLastKeyFrameId = 0;
+  bool monocular = false, rgbd = false;   // mSensor
+};
+// What the tail of Track() got back (optional, as TrackTrace): lld_frame_finish_result with its arrays owned here.
+struct FinishTrace { lld_frame_finish_result r; std::vector<uint8_t> created; std::vector<int32_t> new_id, kp_point_id, order; std::vector<float> x3d; };
+
 // TwoFrameLineMatcher's constructor arguments (include/TwoFrameLineMatcher.h:31-38) as the Frame constructor passes them (src/Frame.cc:118-121)
 struct StereoLineParams { double K[9]; double b; double tau; int minLineLength; };
 
@@ -94,9 +112,31 @@ class FrameOnDevice {
   // the device recorded: the lines its stages assigned, or the held lines after SetFrameState.  Returns mapline_cnt + cnt0.
   int MatchLinesLastKF(const TrackingMembers& tr, Frame& mCurrentFrame, FrameOnDevice& lastOnDevice, KeyFrame* pKF, lld_slam::Map* mpMap,
                        std::vector<MapLine*>* created = nullptr, std::vector<int>* match_trace = nullptr);
+  // The tail of Tracking::Track after a successful TrackLocalMap on this object (src/Tracking.cc:446-476) as ONE device call (lld_frame_track_finish),
+  // split where the reference's caller acts in between:
+  //   NeedNewKeyFrame    the cleaning of VO matches on the objects (:446-453), then the call: counts, decision, the new stereo points and the outlier
+  //                      drop happen on the device, on the state TrackLocalMap left there.  Returns NeedNewKeyFrame()'s value; *interruptBA: the
+  //                      caller calls mpLocalMapper->InterruptBA() (:1296).  KeyFrameMade(): need && d.setNotStopOk.
+  //   CreateNewKeyFrame  when KeyFrameMade(): pKF = new KeyFrame(mCurrentFrame, ..) is the caller's (:1375); the loop of :1399-1429 from the call's
+  //                      result - `new MapPoint(x3D, pKF, mpMap)` per created entry in visiting order, so that mnId is the id the device gave (a mismatch
+  //                      throws), AddObservation, pKF->AddMapPoint, mpMap->AddMapPoint, mvpMapPoints (ComputeDistinctiveDescriptors / UpdateNormalAndDepth
+  //                      of the new points: the caller's, as lld_landmark_adapter's RefreshMapPoints) - then MatchLinesLastKF (:1433) when lastOnDevice.
+  //   DropOutliers       :472-476 on the objects (the device has dropped them already).
+  bool NeedNewKeyFrame(const TrackingMembers& tr, const KeyFrameDecision& d, Frame& mCurrentFrame, bool* interruptBA, FinishTrace* trace = nullptr);
+  bool KeyFrameMade() const { return finish_made_; }
+  void CreateNewKeyFrame(const TrackingMembers& tr, Frame& mCurrentFrame, KeyFrame* pKF, lld_slam::Map* mpMap, FrameOnDevice* lastOnDevice,
+                         std::vector<MapPoint*>* created = nullptr);
+  void DropOutliers(Frame& mCurrentFrame) const;
+  // void Tracking::UpdateLastFrame() from :830 on, on the object that was the current frame of the last Track() (lld_frame_create_stereo_points,
+  // LLD_POINTS_LAST_FRAME): mLastFrame.SetPose(Tlr*pRef->GetPose()) is the caller's (:825) and travels with the call; the temporal MapPoints are
+  // news'd here in visiting order (MapPoint(x3D, mpMap, &mLastFrame, i) has no double: the three-argument constructor with a NULL keyframe stands
+  // in), entered into mLastFrame.mvpMapPoints and appended to mlpTemporalPoints.
+  void UpdateLastFrame(const TrackingMembers& tr, float mThDepth, Frame& mLastFrame, lld_slam::Map* mpMap, std::vector<MapPoint*>* mlpTemporalPoints);
 
  private:
-  void create(const Frame& F);       // lld_frame_create of the keypoint side, the stage parameters
+  void create(const Frame& F);
+  FinishTrace finish_;               // the result NeedNewKeyFrame fetched, for CreateNewKeyFrame
+  bool finish_made_ = false;       // lld_frame_create of the keypoint side, the stage parameters
   lld_ctx* ctx_;
   lld_frame* f_ = nullptr;
   int nt_ = 0, nl_ = 0, dim_ = 1;

@@ -999,6 +999,107 @@ typedef struct {
   int32_t* new_id;                  /* [n_left] id given to a created line, else -1; may be NULL */
 } lld_frame_new_lines_result;
 int  lld_frame_new_map_lines(lld_frame* cur, lld_frame* last, const lld_frame_new_lines_params* params, lld_frame_new_lines_result* out);
+/* ------------------------------------------------------------------ the tail of Tracking::Track on the resident frame: keyframe decision, new stereo points
+ * lld_frame_track_finish: what Tracking::Track does with mCurrentFrame after TrackLocalMap succeeded (src/Tracking.cc:429-476), in ONE kernel
+ * on the arrays the chain left in HBM - mvDepth and mvKeysUn of the built frame, kp_has / kp_id / kp_obs / kp_outlier, the view and stage 2's
+ * record of the tracking state - queued on the context's stream like the stages; the only wait is the fetch of the result (one copy).
+ * In the reference's order:
+ *   1. Clean VO matches (:446-453): a keypoint whose MapPoint has no observations loses it, and its mvbOutlier flag is cleared.
+ *   2. NeedNewKeyFrame's counts (:1250-1264): a keypoint is close when depth > 0 && depth < th_depth (strict); a close keypoint that holds a
+ *      MapPoint and is no outlier counts as n_tracked_close, every other close keypoint as n_non_tracked_close.  (monocular != 0: both stay 0, :1252.)
+ *   3. NeedNewKeyFrame's decision (:1227-1309) from the scalars below, in the reference's types: frame ids summed in 64 bits,
+ *      mnMatchesInliers < nRefMatches*0.25 in double, mnMatchesInliers < nRefMatches*thRefRatio in float with thRefRatio 0.75f, 0.4f when
+ *      n_keyframes < 2, 0.9f when monocular.  need = its return value; interrupt_ba = 1 when the reference calls mpLocalMapper->InterruptBA() (:1296) -
+ *      the caller must then call it; made = need && set_not_stop_ok (CreateNewKeyFrame returns at once when SetNotStop(true) fails, :1369).
+ *      force = 0 / 1 replaces `made` for a caller that decides elsewhere (-1: the decision above); need and interrupt_ba are reported either way.
+ *   4. If made, CreateNewKeyFrame's points (:1386-1430).  The candidates are the keypoints with depth > 0 in the order std::sort gives
+ *      pair<float,int>: by depth, equal depths by index (+inf sorts last, NaN and depth <= 0 never enter).  Every visited entry increments nPoints
+ *      whether or not a point is made, so entry j (from 0) is visited iff j <= J, J the first j >= 100 with depth_j > th_depth (strict, and NOT the
+ *      count's inequality: a depth equal to th_depth is neither close nor a reason to stop); the entry that stops the loop is itself processed.
+ *      A visited keypoint gets a new MapPoint when it holds none or one without observations.  Its position is Frame::UnprojectStereo
+ *      (src/Frame.cc:730-744): x = (u-cx)*z*invfx, y = (v-cy)*z*invfy in float with invfx = 1.0f/fx, (u, v) = mvKeysUn, then mRwc*x3Dc + mOw with
+ *      the frame's own view as stage 2 left it (Rwc = Rcw^T).  The matrix step is the library's un-projection of lld_new_points_triangulate: float
+ *      products summed in double in index order, one rounding, then the float addition of mOw; bit parity with OpenCV's gemm is not pinned, as
+ *      for every cv::Mat product restated in this header.  New ids are first_new_id + k, k the rank among the created points in visiting order
+ *      (the caller passes MapPoint::nNextId and news its MapPoints in that order).  The state takes kp_has = 1, kp_id, kp_world, kp_obs = 1
+ *      (AddObservation(pKF, i), :1415); kp_outlier stays as it is.
+ *   5. Drop outliers (:472-476), whenever the call runs: a keypoint that holds a MapPoint and is flagged loses it.
+ * RGB-D: TrackLocalMap takes its outlier MapPoints out of the frame for mSensor == System::STEREO only (:1171-1172), and stage 2 of the chain
+ * always does.  With sensor_rgbd != 0 the call first puts back what stage 2 took out (the ids and flags of its record; positions and
+ * observation flags never left the state), so that steps 1-5 see the frame the reference's RGB-D system sees: such a keypoint counts as not
+ * tracked, gets no new point while its MapPoint has observations, and loses it in step 5.  After lld_frame_track_set_state there is no
+ * stage-2 record and the state is taken as handed in.
+ * The handle then holds what mCurrentFrame holds when Track() returns: lld_frame_new_map_lines may follow on it with nothing in between, and
+ * the frame can serve as the next frame's `last`.  The stage records of lld_frame_track_download predate this call.
+ *
+ * lld_frame_create_stereo_points: the same depth-ordered creation, by the same kernel, where the reference runs it outside Track()'s tail:
+ *   LLD_POINTS_LAST_FRAME       Tracking::UpdateLastFrame's "visual odometry" points (:830-882): view / pose_qt (both or neither; formed as for
+ *                               lld_frame_track_motion_model) first replace the frame's pose (mLastFrame.SetPose, :825); the visiting rule is 4.; the
+ *                               new points are temporal: kp_obs = 0 (MapPoint(x3D, mpMap, &mLastFrame, i) adds no observation).  No cleaning, no
+ *                               decision, no outlier drop.  The frame needs a pose (a stage, or lld_frame_track_set_state, or view here).
+ *   LLD_POINTS_INITIALIZATION   Tracking::StereoInitialization (:535-550): every keypoint with depth > 0 gets a point, in index order, ids in index
+ *                               order, kp_obs = 1.  view / pose_qt are required (SetPose(eye), :526: the identity); the tracking state is reset
+ *                               to that of a new frame first, and a frame without a tracking state gets one.  th_depth is not read.
+ * Wherever view is given, `params` is required as for lld_frame_track_set_state (the line camera of the new pose is formed from it).
+ * n_tracked_close, n_non_tracked_close, need and interrupt_ba read 0; made reads 1.
+ *
+ * Depth: the frame's own mvDepth when a device build made it (lld_frame_build_stereo*, lld_frame_build_mono* - without a depth image every
+ * depth is -1 and nothing is close or created); for a frame of lld_frame_create, which keeps no depth, the host array depth[nt] (uploaded with
+ * the call; ignored on a built frame).
+ * LLD_ERR_INVALID before anything is queued, the frame unchanged: a NULL frame, params or out; no depth from either source;
+ * lld_frame_track_finish on a frame whose last chain call was neither lld_frame_track_local_map nor lld_frame_track_set_state; th_depth not > 0
+ * (finish and LLD_POINTS_LAST_FRAME); first_new_id < 0 or first_new_id + nt > INT32_MAX; force outside -1..1; an unknown mode; one of view / pose_qt
+ * without the other, or view without params (or with params lld_frame_track_set_state refuses); LLD_POINTS_LAST_FRAME on a frame without a
+ * pose; LLD_POINTS_INITIALIZATION without view.
+ * nt = 0 or no positive depth: LLD_OK with zeros. */
+typedef struct {
+  float   th_depth;                 /* mThDepth                                                                                                      */
+  int32_t first_new_id;             /* MapPoint::nNextId                                                                                             */
+  int32_t force;                    /* -1: made = need && set_not_stop_ok; 0 / 1: made = force                                                       */
+  int32_t only_tracking;            /* mbOnlyTracking (:1227)                                                                                        */
+  int32_t mapper_stopped;           /* mpLocalMapper->isStopped() || stopRequested() (:1231)                                                         */
+  int32_t mapper_idle;              /* mpLocalMapper->AcceptKeyFrames() (:1247)                                                                      */
+  int32_t keyframes_in_queue;       /* mpLocalMapper->KeyframesInQueue() (:1299)                                                                     */
+  int32_t set_not_stop_ok;          /* mpLocalMapper->SetNotStop(true) (:1369); the caller evaluates it only when need is possible, or undoes it    */
+  int32_t monocular;                /* mSensor == System::MONOCULAR                                                                                  */
+  int32_t max_frames, min_frames;   /* mMaxFrames, mMinFrames                                                                                        */
+  int32_t n_keyframes;              /* mpMap->KeyFramesInMap() (:1234)                                                                               */
+  int32_t n_ref_matches;            /* mpReferenceKF->TrackedMapPoints(nMinObs), nMinObs = n_keyframes <= 2 ? 2 : 3 (:1241-1244)                     */
+  int32_t n_matches_inliers;        /* mnMatchesInliers; -1: n_points_map of the frame's own stage-2 record                                          */
+  int32_t sensor_rgbd;              /* mSensor == System::RGBD: see "RGB-D" above                                                                     */
+  int32_t reserved;
+  int64_t frame_id;                 /* mCurrentFrame.mnId                                                                                            */
+  int64_t last_reloc_frame_id;      /* mnLastRelocFrameId                                                                                            */
+  int64_t last_keyframe_id;         /* mnLastKeyFrameId                                                                                              */
+  const float* depth;               /* [nt] mvDepth for a frame of lld_frame_create, else NULL                                                       */
+} lld_frame_finish_params;
+typedef struct {
+  int32_t n_tracked_close, n_non_tracked_close;   /* nTrackedClose, nNonTrackedClose                                                                 */
+  int32_t need, interrupt_ba, made;
+  int32_t n_visited;                /* entries of the sorted list the creation loop processed (0 when made = 0)                                      */
+  int32_t n_created;
+  int32_t reserved;
+  /* caller-allocated, any may be NULL */
+  uint8_t* created;                 /* [nt] 1 where a MapPoint was made                                                                              */
+  int32_t* new_id;                  /* [nt] its id, -1 where none                                                                                    */
+  float*   x3d;                     /* [nt][3] its position, 0 where none                                                                            */
+  int32_t* kp_point_id;             /* [nt] what the frame holds on exit: id of mvpMapPoints[k] or -1                                                */
+  int32_t* order;                   /* [nt] rank of the keypoint in the visiting order, -1 when it was not visited                                   */
+} lld_frame_finish_result;
+int  lld_frame_track_finish(lld_frame* frame, const lld_frame_finish_params* params, lld_frame_finish_result* out);
+#define LLD_POINTS_LAST_FRAME     0
+#define LLD_POINTS_INITIALIZATION 1
+typedef struct {
+  int32_t mode;                     /* LLD_POINTS_LAST_FRAME / LLD_POINTS_INITIALIZATION                                                             */
+  float   th_depth;                 /* mThDepth                                                                                                      */
+  int32_t first_new_id;             /* MapPoint::nNextId                                                                                             */
+  int32_t reserved;
+  const lld_track_params* params;   /* required with view, else may be NULL                                                                          */
+  const lld_frame_view* view;       /* NULL: the frame's pose stays (LLD_POINTS_LAST_FRAME only)                                                     */
+  const double* pose_qt;            /* [7] with view                                                                                                 */
+  const float* depth;               /* as lld_frame_finish_params.depth                                                                              */
+} lld_frame_points_params;
+int  lld_frame_create_stereo_points(lld_frame* frame, const lld_frame_points_params* params, lld_frame_finish_result* out);
 /* ORBmatcher::Fuse(KeyFrame*, vpMapPoints, th) (src/ORBmatcher.cc:825-958; the loop of LocalMapping::SearchInNeighbors) with the
  * projection loop (:841-890) on the device: cv::gemm transform, z >= 0, invz = 1/z, u = fx*(x*invz)+cx, KeyFrame::IsInImage
  * (upper bounds strict, src/KeyFrame.cc:633-636), ur = u - bf*invz, scale-invariance band, PO.dot(Pn) >= 0.5*dist3D, PredictScale;

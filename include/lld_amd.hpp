@@ -500,6 +500,43 @@ class TrackedFrame {
     R.match_last.resize(nl_); R.new_id.resize(nl_); R.created.resize(nl_); R.X0.resize(3 * (size_t)nl_); R.dir.resize(3 * (size_t)nl_);
     return R.r.n_created + R.r.n_held;
   }
+  // The tail of Tracking::Track (src/Tracking.cc:429-476) on the frame TrackLocalMap (or SetState) left on the device (lld_frame_track_finish):
+  // clean VO matches, NeedNewKeyFrame's counts and decision from the scalars of `p` (p.depth: mvDepth of a frame lld_frame_create made, else
+  // NULL), CreateNewKeyFrame's stereo points when a keyframe is made - created[i] != 0 -> the reference constructs MapPoint(x3D[i], pKF, mpMap)
+  // for keypoint i, in ascending order[i], with new_id[i] = p.first_new_id + its rank (pass MapPoint::nNextId) - and the outlier drop.
+  // kp_point_id: what the frame holds on exit.  Returns `need`; when r.interrupt_ba is set the caller calls mpLocalMapper->InterruptBA().
+  struct NewStereoPoints {
+    lld_frame_finish_result r{};
+    std::vector<uint8_t> created; std::vector<int32_t> new_id, kp_point_id, order; std::vector<float> x3D;
+    void bind(int n) {
+      created.assign(n + 1, 0); new_id.assign(n + 1, -1); kp_point_id.assign(n + 1, -1); order.assign(n + 1, -1); x3D.assign(3 * (size_t)n + 3, 0.f);
+      r.created = created.data(); r.new_id = new_id.data(); r.kp_point_id = kp_point_id.data(); r.order = order.data(); r.x3d = x3D.data();
+    }
+    void trim(int n) { created.resize(n); new_id.resize(n); kp_point_id.resize(n); order.resize(n); x3D.resize(3 * (size_t)n); }
+  };
+  bool Finish(const lld_frame_finish_params& p, NewStereoPoints* out) {
+    NewStereoPoints local;
+    NewStereoPoints& R = out ? *out : local;
+    R.bind(nt_);
+    check(lld_frame_track_finish(f_, &p, &R.r), "lld_frame_track_finish");
+    R.trim(nt_);
+    return R.r.need != 0;
+  }
+  // Tracking::UpdateLastFrame's temporal points (:830-882, mode LLD_POINTS_LAST_FRAME; Tcw / view: the pose mLastFrame.SetPose receives at :825,
+  // or NULL for both) and Tracking::StereoInitialization's points (:535-550, mode LLD_POINTS_INITIALIZATION; Tcw / view: the first pose).
+  // Returns the number of points made.
+  int CreateStereoPoints(int mode, float thDepth, int32_t first_new_id, const lld_frame_view* view, const float* Tcw, NewStereoPoints* out, const float* depth = nullptr) {
+    NewStereoPoints local;
+    NewStereoPoints& R = out ? *out : local;
+    R.bind(nt_);
+    double qt[7];
+    if (Tcw) lld_se3_from_tcw_f32(Tcw, qt);
+    lld_frame_points_params p{};
+    p.mode = mode; p.th_depth = thDepth; p.first_new_id = first_new_id; p.params = &params; p.view = view; p.pose_qt = Tcw ? qt : nullptr; p.depth = depth;
+    check(lld_frame_create_stereo_points(f_, &p, &R.r), "lld_frame_create_stereo_points");
+    R.trim(nt_);
+    return R.r.n_created;
+  }
   // mvuRight / mvDepth of a frame StereoFrame built (Frame::UnprojectStereo and keyframe creation read them on the host); waits for the build
   int DownloadStereo(std::vector<float>& mvuRight, std::vector<float>& mvDepth) {
     mvuRight.assign(nt_, -1.f); mvDepth.assign(nt_, -1.f);

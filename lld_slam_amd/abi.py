@@ -355,6 +355,29 @@ class FrameNewLinesResult(C.Structure):
                 ("dir", c_double_p), ("new_id", c_int32_p)]
 
 
+class FrameFinishParams(C.Structure):
+    """lld_frame_finish_params (include/lld_amd.h): mThDepth, MapPoint::nNextId and NeedNewKeyFrame's scalars."""
+    _fields_ = [("th_depth", C.c_float), ("first_new_id", C.c_int32), ("force", C.c_int32), ("only_tracking", C.c_int32), ("mapper_stopped", C.c_int32),
+                ("mapper_idle", C.c_int32), ("keyframes_in_queue", C.c_int32), ("set_not_stop_ok", C.c_int32), ("monocular", C.c_int32),
+                ("max_frames", C.c_int32), ("min_frames", C.c_int32), ("n_keyframes", C.c_int32), ("n_ref_matches", C.c_int32),
+                ("n_matches_inliers", C.c_int32), ("sensor_rgbd", C.c_int32), ("reserved", C.c_int32), ("frame_id", C.c_int64), ("last_reloc_frame_id", C.c_int64), ("last_keyframe_id", C.c_int64),
+                ("depth", c_float_p)]
+
+
+class FrameFinishResult(C.Structure):
+    """lld_frame_finish_result."""
+    _fields_ = [("n_tracked_close", C.c_int32), ("n_non_tracked_close", C.c_int32), ("need", C.c_int32), ("interrupt_ba", C.c_int32), ("made", C.c_int32),
+                ("n_visited", C.c_int32), ("n_created", C.c_int32), ("reserved", C.c_int32), ("created", c_uint8_p), ("new_id", c_int32_p),
+                ("x3d", c_float_p), ("kp_point_id", c_int32_p), ("order", c_int32_p)]
+
+
+class FramePointsParams(C.Structure):
+    """lld_frame_points_params: params / view are lld_track_params* / lld_frame_view* (the structs of tracking.py / orb_search.py by reference)."""
+    _fields_ = [("mode", C.c_int32), ("th_depth", C.c_float), ("first_new_id", C.c_int32), ("reserved", C.c_int32), ("params", C.c_void_p),
+                ("view", C.c_void_p), ("pose_qt", c_double_p), ("depth", c_float_p)]
+
+
+POINTS_LAST_FRAME, POINTS_INITIALIZATION = 0, 1
 RELOC_RUNG_POSE1, RELOC_RUNG_SEARCH1, RELOC_RUNG_POSE2, RELOC_RUNG_SEARCH2, RELOC_RUNG_POSE3 = 1, 2, 4, 8, 16
 
 
@@ -378,6 +401,7 @@ PRODUCT_SYMBOLS = [
     "lld_frame_set_lines", "lld_track_params_default", "lld_frame_track_motion_model", "lld_frame_track_local_map", "lld_frame_track_download", "lld_frame_track_set_state",
     "lld_frame_compute_bow", "lld_frame_track_reference_keyframe", "lld_frame_relocalize",
     "lld_frame_build_lines", "lld_frame_lines_download", "lld_frame_new_map_lines",
+    "lld_frame_track_finish", "lld_frame_create_stereo_points",
     "lld_sim3_params_default", "lld_optimize_sim3", "lld_optimize_sim3_batch",
     "lld_pose_graph_params_default", "lld_optimize_essential_graph",
     "lld_orb_extractor_create", "lld_orb_extractor_destroy", "lld_orb_extractor_levels_get", "lld_orb_extract", "lld_orb_extractor_pyramids",
@@ -545,6 +569,9 @@ class Lib:
             f("frame_lines_download").argtypes = [vp, c_int32_p, c_double_p]; f("frame_lines_download").restype = C.c_int
             f("frame_new_map_lines").argtypes = [vp, vp, C.POINTER(FrameNewLinesParams), C.POINTER(FrameNewLinesResult)]
             f("frame_new_map_lines").restype = C.c_int
+            f("frame_track_finish").argtypes = [vp, C.POINTER(FrameFinishParams), C.POINTER(FrameFinishResult)]; f("frame_track_finish").restype = C.c_int
+            f("frame_create_stereo_points").argtypes = [vp, C.POINTER(FramePointsParams), C.POINTER(FrameFinishResult)]
+            f("frame_create_stereo_points").restype = C.c_int
             f("frame_track_reference_keyframe").argtypes = [vp, vp, vp, c_double_p, C.POINTER(RefKeyFrame)]
             f("frame_track_reference_keyframe").restype = C.c_int
             # (frame, lld_track_params*, lld_frame_view*, pose_qt, n_candidates, lld_ref_keyframe[], lld_reloc_candidate[], lld_pnp_params*, lld_reloc_result*)

@@ -538,7 +538,7 @@ int lld_frame_track_motion_model(lld_frame* f, const lld_track_params* P, const 
   }
   s = run_lines(f, st, P, B, U, B.dev(U.skip), B.dev(lwork)); if (s) return s;
   s = run_pose(f, st, P, B.dev(pwork), 0); if (s) return s;
-  S->stage1_queued = true; S->n_in_view = 0;
+  S->stage1_queued = true; S->n_in_view = 0; S->finish_ready = false; S->stage2_queued = false;
   return LLD_OK;
 }
 
@@ -577,7 +577,7 @@ int lld_frame_track_reference_keyframe(lld_frame* f, const lld_track_params* P, 
   const ApplyDev ap{S->D.kp_has, S->D.kp_world, S->D.kp_id, S->D.kp_obs, q.pos, q.id, q.obs, S->D.rec_h[0]->i + RI_SEARCH1, 0, 0};
   s = bow_search_launch(st, Bs, ap); if (s) return s;
   s = run_pose(f, st, P, B.dev(pwork), 0); if (s) return s;                    // (no AddLinesFrom: track_reset_launch left the line tables empty)
-  S->stage1_queued = true; S->n_in_view = 0;
+  S->stage1_queued = true; S->n_in_view = 0; S->finish_ready = false; S->stage2_queued = false;
   return LLD_OK;
 }
 
@@ -611,7 +611,7 @@ int lld_frame_track_set_state(lld_frame* f, const lld_track_params* P, const lld
   const int nmax = std::max(std::max(std::max(nt, nl), n_trk), 64);
   hipLaunchKernelGGL(track_load_kernel, dim3((nmax + 255) / 256), dim3(256), 0, st, S->D, U.dev(B), B.dev(H.pose), B.dev(H.view), B.dev(H.lp));
   LLD_HIP_TRY(hipGetLastError());
-  S->stage1_queued = true; S->n_in_view = 0;
+  S->stage1_queued = true; S->n_in_view = 0; S->finish_ready = true; S->stage2_queued = false;
   return LLD_OK;
 }
 
@@ -652,6 +652,7 @@ int lld_frame_track_local_map(lld_frame* f, const lld_track_params* P, const lld
   s = orbs_launch_n(ctx, st, f, B.dev(prob), 1); if (s) return s;
   s = run_lines(f, st, P, B, U, B.dev(lskip2), B.dev(lwork)); if (s) return s;
   s = run_pose(f, st, P, B.dev(pwork), 1); if (s) return s;
+  S->finish_ready = true; S->stage2_queued = true;
   return LLD_OK;
 }
 

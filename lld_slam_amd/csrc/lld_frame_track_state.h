@@ -134,6 +134,8 @@ struct lld_frame_track_state {
   char* h_rec = nullptr; size_t h_rec_bytes = 0;
   lld_track::ViewConsts consts{};
   bool stage1_queued = false;
+  bool stage2_queued = false;                  // lld_frame_track_local_map ran after the last stage 1: the stage-2 record is this frame's
+  bool finish_ready = false;                   // the last chain call was lld_frame_track_local_map or lld_frame_track_set_state (lld_frame_track_finish)
   size_t in_view_off = 0; int n_in_view = 0;   // Frame::isInFrustum flags of stage 2's local MapPoints, inside d_work
   unsigned seen_psize = 0, seen_lsize = 0; size_t seen_lds = 0;   // track_mark_seen_kernel's tables (state_build)
 };

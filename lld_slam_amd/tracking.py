@@ -285,6 +285,61 @@ class DeviceTrackedFrame:
         self._check(self.lib.fn("frame_new_map_lines")(self.res.handle, last_frame.res.handle, C.byref(P), C.byref(R)), "lld_frame_new_map_lines")
         return dict(a, n_created=int(R.n_created), n_held=int(R.n_held))
 
+    def _finish_result(self):
+        nt = self.F.n
+        a = dict(created=np.zeros(nt, np.uint8), new_id=np.full(nt, -1, np.int32), x3d=np.zeros((nt, 3), np.float32), kp_point_id=np.full(nt, -1, np.int32),
+                 order=np.full(nt, -1, np.int32))
+        R = abi.FrameFinishResult()
+        R.created = a["created"].ctypes.data_as(c_uint8_p); R.new_id = a["new_id"].ctypes.data_as(c_int32_p); R.x3d = a["x3d"].ctypes.data_as(c_float_p)
+        R.kp_point_id = a["kp_point_id"].ctypes.data_as(c_int32_p); R.order = a["order"].ctypes.data_as(c_int32_p)
+        return R, a
+
+    @staticmethod
+    def _finish_dict(R, a):
+        return dict(a, n_tracked_close=int(R.n_tracked_close), n_non_tracked_close=int(R.n_non_tracked_close), need=int(R.need), interrupt_ba=int(R.interrupt_ba),
+                    made=int(R.made), n_visited=int(R.n_visited), n_created=int(R.n_created))
+
+    def finish(self, th_depth, first_new_id, depth=None, force=-1, **decision):
+        """lld_frame_track_finish: the tail of Tracking::Track (src/Tracking.cc:429-476) on the frame stage 2 (or set_state) left on the device:
+        clean VO matches, NeedNewKeyFrame's counts and decision, CreateNewKeyFrame's stereo points when a keyframe is made, the outlier drop.
+        decision: the scalars of lld_frame_finish_params by name (only_tracking, mapper_stopped, mapper_idle, keyframes_in_queue, set_not_stop_ok,
+        monocular, max_frames, min_frames, n_keyframes, n_ref_matches, n_matches_inliers [-1: the frame's own stage-2 record], frame_id,
+        last_reloc_frame_id, last_keyframe_id).  depth: mvDepth [nt] for a frame lld_frame_create made.  Returns a dict: the scalars of
+        lld_frame_finish_result and created, new_id, x3d, kp_point_id, order."""
+        P = abi.FrameFinishParams()
+        P.th_depth = float(th_depth); P.first_new_id = int(first_new_id); P.force = int(force); P.n_matches_inliers = -1
+        for k_, v in decision.items():
+            if k_ not in {n for n, _ in abi.FrameFinishParams._fields_}:
+                raise TypeError(f"finish() got an unknown scalar {k_!r}")
+            setattr(P, k_, int(v))
+        d = None if depth is None else np.ascontiguousarray(depth, np.float32)
+        P.depth = None if d is None else d.ctypes.data_as(c_float_p)
+        R, a = self._finish_result()
+        self._check(self.lib.fn("frame_track_finish")(self.res.handle, C.byref(P), C.byref(R)), "lld_frame_track_finish")
+        return self._finish_dict(R, a)
+
+    def create_stereo_points(self, mode, first_new_id, th_depth=0.0, Tcw_f32=None, depth=None):
+        """lld_frame_create_stereo_points: mode abi.POINTS_LAST_FRAME - Tracking::UpdateLastFrame's temporal points (:830-882), Tcw_f32 (optional)
+        the pose mLastFrame.SetPose receives (:825); mode abi.POINTS_INITIALIZATION - Tracking::StereoInitialization's points (:535-550), Tcw_f32
+        the pose of the first frame (default: the identity).  Returns the dict of finish()."""
+        from .host import se3_from_tcw_f32
+        P = abi.FramePointsParams()
+        P.mode = int(mode); P.th_depth = float(th_depth); P.first_new_id = int(first_new_id)
+        if Tcw_f32 is None and mode == abi.POINTS_INITIALIZATION:
+            Tcw_f32 = np.eye(4, dtype=np.float32)
+        keep = []
+        if Tcw_f32 is not None:
+            T = np.ascontiguousarray(Tcw_f32, np.float32).reshape(4, 4)
+            view = orb_search.frame_view(T, self.cam, self.F)
+            qt = np.ascontiguousarray(se3_from_tcw_f32(self.lib, T), np.float64)
+            keep += [view, qt]
+            P.params = C.addressof(self.params); P.view = C.addressof(view); P.pose_qt = qt.ctypes.data_as(c_double_p)
+        d = None if depth is None else np.ascontiguousarray(depth, np.float32)
+        P.depth = None if d is None else d.ctypes.data_as(c_float_p)
+        R, a = self._finish_result()
+        self._check(self.lib.fn("frame_create_stereo_points")(self.res.handle, C.byref(P), C.byref(R)), "lld_frame_create_stereo_points")
+        return self._finish_dict(R, a)
+
     def _check(self, st, what):
         if st != abi.LLD_OK:
             err = RuntimeError(f"{what} failed: {self.lib.fn('status_string')(st).decode()}")
