@@ -20,7 +20,7 @@ __device__ __forceinline__ void ba_control_body(const BAArrays& A, const BAWin& 
   if (S.phase == PH_RUN) {                           // interleaved partial sums + fixed shuffle tree (deterministic)
     const int nb = W.nt_pt + W.nt_ln;
     for (int i = lane; i < nb; i += 64) { tempChi += xwg_load(&A.chi_part2[W.part_off + i]); scale_l += xwg_load(&A.scale_part[W.part_off + i]); }
-    tempChi = wave_sum(tempChi); scale_l = wave_sum(scale_l);
+    tempChi = lld_wave::sum(tempChi); scale_l = lld_wave::sum(scale_l);
   }
   if (lane == 0 && S.phase == PH_RUN) {
     double scale = S.scale_cam + scale_l;

@@ -29,6 +29,7 @@
 
 #include "lld_common.h"
 #include "lld_device_math.h"
+#include "lld_wave.h"
 #include "lld_ba_chol_plan.h"
 
 namespace lldba {
@@ -223,37 +224,9 @@ __device__ __forceinline__ void xwg_store_i32(int* p, int v) { __hip_atomic_stor
 __device__ __forceinline__ int xwg_load_i32(const int* p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
 // The window grid row `y` of a per-super-step kernel works on (see BAArrays::slot_map); < 0: none, the workgroup leaves.
 #define LLD_ROW_WINDOW(A, st, y) ((A).slot_rd ? (A).slot_rd[(y)] : (int)(y))
-__device__ __forceinline__ double wave_sum(double x) {
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) x += __shfl_xor(x, off);
-  return x;
-}
-__device__ __forceinline__ double wave_max(double x) {
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) x = fmax(x, __shfl_xor(x, off));
-  return x;
-}
-// Fixed-tree block sum; result valid in every lane.  `scratch` holds blockDim/64 doubles.
-__device__ __forceinline__ double block_sum(double x, double* scratch) {
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, nw = blockDim.x >> 6;
-  x = wave_sum(x);
-  __syncthreads();
-  if (lane == 0) scratch[wave] = x;
-  __syncthreads();
-  double t = 0.0;
-  for (int i = 0; i < nw; i++) t += scratch[i];
-  return t;
-}
-__device__ __forceinline__ double block_max(double x, double* scratch) {
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, nw = blockDim.x >> 6;
-  x = wave_max(x);
-  __syncthreads();
-  if (lane == 0) scratch[wave] = x;
-  __syncthreads();
-  double t = 0.0;
-  for (int i = 0; i < nw; i++) t = fmax(t, scratch[i]);
-  return t;
-}
+// Wavefront and workgroup reductions: lld_wave.h (fixed addition order).  block_sum / block_max: `scratch` holds blockDim/64 doubles.
+using lld_wave::block_max;
+using lld_wave::block_sum;
 
 // Inverse of a symmetric positive definite D x D matrix (full row-major in/out) through Cholesky; false if not SPD.
 template <int D>

@@ -360,7 +360,7 @@ __device__ __forceinline__ void ba_begin_body(const BAArrays& A, const BAWin& W,
   double chi = 0.0;
   const int nb = W.nl_pt + W.nl_ln;
   for (int i = lane; i < nb; i += 64) chi += A.chi_part[W.part_off + i];
-  chi = wave_sum(chi);
+  chi = lld_wave::sum(chi);
   double md = 0.0;
   if (S.it == 0) {
     // computeLambdaInit: tau * max |H_kk| over cameras and landmarks (optimization_algorithm_levenberg.cpp:166-180)
@@ -369,7 +369,7 @@ __device__ __forceinline__ void ba_begin_body(const BAArrays& A, const BAWin& W,
       const double* h = H + c * 21;
       md = fmax(md, fmax(fmax(fabs(xwg_load(h)), fabs(xwg_load(h + 6))), fmax(fmax(fabs(xwg_load(h + 11)), fabs(xwg_load(h + 15))), fmax(fabs(xwg_load(h + 18)), fabs(xwg_load(h + 20))))));
     }
-    md = wave_max(md);
+    md = lld_wave::max(md);
   }
   if (lane == 0) {
     S.currentChi = chi; S.iniChi = chi;

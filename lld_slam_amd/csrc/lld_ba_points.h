@@ -57,7 +57,7 @@ __device__ __forceinline__ void seg_sum(double* v, int seg, int lane, int max_le
 template <int N>
 __device__ __forceinline__ void wave_sum_n(double* v) {
 #pragma unroll
-  for (int i = 0; i < N; i++) v[i] = wave_sum(v[i]);
+  for (int i = 0; i < N; i++) v[i] = lld_wave::sum(v[i]);
 }
 
 struct PtEdgeLin { double r[3], Jp[9], Jc[18], ws, rho0; bool stereo; };

@@ -67,7 +67,7 @@ __global__ __launch_bounds__(256) void ba_pcgm_matvec_kernel(BAArrays A, const B
   const double* p = A.pcg_vec + 2 * A.x_total + W.x_off;
   double acc = 0.0;
   for (int c = lane; c < n; c += 64) acc = fma(Sr[c], p[c], acc);
-  acc = wave_sum(acc);
+  acc = lld_wave::sum(acc);
   if (lane == 0) A.pcg_vec[3 * A.x_total + W.x_off + row] = acc;
 }
 

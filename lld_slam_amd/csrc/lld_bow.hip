@@ -23,6 +23,7 @@
 #include "lld_bow_score.h"
 #include "lld_common.h"
 #include "lld_track_internal.h"
+#include "lld_wave.h"
 
 namespace {
 
@@ -88,14 +89,11 @@ __global__ __launch_bounds__(256) void bow_descend(const int2* __restrict__ info
       const int c = c0 + lane;
       if (c < nf.y) {
         const uint4* p = pdesc + (size_t)(nf.x + c) * 2;
-        const uint4 a = p[0], b = p[1];
-        const unsigned dist = __popc(a.x ^ d[0]) + __popc(a.y ^ d[1]) + __popc(a.z ^ d[2]) + __popc(a.w ^ d[3]) +
-                              __popc(b.x ^ d[4]) + __popc(b.y ^ d[5]) + __popc(b.z ^ d[6]) + __popc(b.w ^ d[7]);
+        const unsigned dist = lld_wave::hamming256(d, p[0], p[1]);
         best = min(best, (dist << 6) | (unsigned)c);
       }
     }
-#pragma unroll
-    for (int o = kGroup / 2; o; o >>= 1) best = min(best, (unsigned)__shfl_xor((int)best, o, kGroup));
+    best = lld_wave::min<kGroup>(best);
     cur = pnode[nf.x + (int)(best & 63u)];
     if (level == S.nid_level) nid = cur;
     nf = info[cur];
@@ -110,48 +108,11 @@ __global__ __launch_bounds__(256) void bow_descend(const int2* __restrict__ info
   }
 }
 
-// Exclusive scan of one int per thread over the workgroup; *total = the sum.  tmp holds blockDim/64 + 1 ints.
-__device__ int block_excl_scan(int x, int* tmp, int* total) {
-  const int t = threadIdx.x, lane = t & 63, w = t >> 6, nw = blockDim.x >> 6;
-  int incl = x;
-#pragma unroll
-  for (int o = 1; o < 64; o <<= 1) {
-    const int y = __shfl_up(incl, o);
-    if (lane >= o) incl += y;
-  }
-  if (lane == 63) tmp[w] = incl;
-  __syncthreads();
-  if (t == 0) {
-    int s = 0;
-    for (int k = 0; k < nw; k++) { const int a = tmp[k]; tmp[k] = s; s += a; }
-    tmp[nw] = s;
-  }
-  __syncthreads();
-  const int r = tmp[w] + incl - x;
-  *total = tmp[nw];
-  __syncthreads();
-  return r;
-}
-
-__device__ void bitonic_sort(unsigned long long* keys, int npad) {
-  for (int k = 2; k <= npad; k <<= 1)
-    for (int j = k >> 1; j > 0; j >>= 1) {
-      for (int i = threadIdx.x; i < npad; i += blockDim.x) {
-        const int ixj = i ^ j;
-        if (ixj > i) {
-          const unsigned long long a = keys[i], b = keys[ixj];
-          if ((a > b) == ((i & k) == 0)) { keys[i] = b; keys[ixj] = a; }
-        }
-      }
-      __syncthreads();
-    }
-}
-
 __global__ __launch_bounds__(kAsmThreads) void bow_assemble(const BowSetDev* __restrict__ sets, const int32_t* __restrict__ fword,
                                                             const int32_t* __restrict__ fnid, const double* __restrict__ fw, char* out,
                                                             int repeated_add) {
   __shared__ unsigned long long keys[LLD_BOW_MAX_FEATURES];
-  __shared__ int tmp[kAsmThreads / 64 + 1];
+  __shared__ int tmp[kAsmThreads / 64];
   __shared__ int s_nvalid;
   __shared__ double s_norm;
   const BowSetDev S = sets[blockIdx.x];
@@ -181,7 +142,7 @@ __global__ __launch_bounds__(kAsmThreads) void bow_assemble(const BowSetDev* __r
   if (cnt) atomicAdd(&s_nvalid, cnt);
   __syncthreads();
   const int nv = s_nvalid;
-  bitonic_sort(keys, npad);
+  lld_wave::bitonic_sort<kAsmThreads>(keys, npad);
 
   // BowVector: one run per word; thread t owns sorted positions [t*8, t*8+8)
   double v[kAsmPerThread];
@@ -204,7 +165,7 @@ __global__ __launch_bounds__(kAsmThreads) void bow_assemble(const BowSetDev* __r
     }
   }
   int nw;
-  int r = block_excl_scan(cnt, tmp, &nw);        // ends with a barrier: keys may be overwritten now
+  int r = lld_wave::block_excl_scan<kAsmThreads>(cnt, tmp, nw);   // every lane is past its reads of keys: they may be overwritten now
   double* vals = (double*)keys;
 #pragma unroll
   for (int e = 0; e < kAsmPerThread; e++)
@@ -227,7 +188,7 @@ __global__ __launch_bounds__(kAsmThreads) void bow_assemble(const BowSetDev* __r
     keys[i] = k;
   }
   __syncthreads();
-  bitonic_sort(keys, npad);
+  lld_wave::bitonic_sort<kAsmThreads>(keys, npad);
   flags = 0; cnt = 0;
 #pragma unroll
   for (int e = 0; e < kAsmPerThread; e++) {
@@ -238,7 +199,7 @@ __global__ __launch_bounds__(kAsmThreads) void bow_assemble(const BowSetDev* __r
     }
   }
   int nn;
-  r = block_excl_scan(cnt, tmp, &nn);
+  r = lld_wave::block_excl_scan<kAsmThreads>(cnt, tmp, nn);
 #pragma unroll
   for (int e = 0; e < kAsmPerThread; e++)
     if (flags & (1u << e)) {

@@ -19,6 +19,7 @@
 
 #include "lld_common.h"
 #include "lld_track_internal.h"
+#include "lld_wave.h"
 
 namespace lld_bow_merge {
 
@@ -34,11 +35,6 @@ constexpr int kFinishThreads = 1024;
 constexpr int kFinishPerThread = LLD_ORB_MAX_KEYPOINTS / kFinishThreads;
 static_assert((1 << kPosBits) >= LLD_ORB_MAX_KEYPOINTS, "position bits");
 static_assert(LLD_ORB_MAX_KEYPOINTS <= 64 * 64, "one occupancy bit per chunk of 64 frame features in a 64-bit lane register");
-
-__device__ __forceinline__ unsigned hamming256(const uint4& a, const uint4& b, const uint4& c, const uint4& d) {
-  return __popc(a.x ^ c.x) + __popc(a.y ^ c.y) + __popc(a.z ^ c.z) + __popc(a.w ^ c.w) + __popc(b.x ^ d.x) + __popc(b.y ^ d.y) + __popc(b.z ^ d.z) +
-         __popc(b.w ^ d.w);
-}
 
 __device__ __forceinline__ uint4 bcast(const uint4& v, int src) {
   return make_uint4((unsigned)__shfl((int)v.x, src), (unsigned)__shfl((int)v.y, src), (unsigned)__shfl((int)v.z, src), (unsigned)__shfl((int)v.w, src));
@@ -85,10 +81,10 @@ __device__ __forceinline__ void bow_match_node(const BowSearchDev& B, int w, int
         const int p = (c << 6) + lane;
         if (p >= nf || ((occ >> c) & 1ull)) continue;
         unsigned dist;
-        if (c == 0) dist = hamming256(a0, b0, da, db);
+        if (c == 0) dist = lld_wave::hamming256(a0, b0, da, db);
         else {
           const int idx = B.f_feature[fs + p];
-          dist = hamming256(fdesc[2 * (size_t)idx], fdesc[2 * (size_t)idx + 1], da, db);
+          dist = lld_wave::hamming256(fdesc[2 * (size_t)idx], fdesc[2 * (size_t)idx + 1], da, db);
         }
         // strict < for both, ascending position inside the lane (:216-225); dist = 256 can pass neither test
         if (dist < (b1 >> kPosBits)) { b2 = b1 >> kPosBits; b1 = (dist << kPosBits) | (unsigned)p; }
@@ -162,7 +158,7 @@ __device__ __forceinline__ void bow_finish_block(const BowSearchDev& B, const Ap
     A.kp_world[3 * k] = A.q_pos[3 * q]; A.kp_world[3 * k + 1] = A.q_pos[3 * q + 1]; A.kp_world[3 * k + 2] = A.q_pos[3 * q + 2];
     kept++;
   }
-  for (int o = 32; o > 0; o >>= 1) kept += __shfl_xor(kept, o);
+  kept = lld_wave::sum(kept);
   if ((tid & 63) == 0 && kept) atomicAdd(&ctl[0], kept);
   __syncthreads();
   if (tid == 0) { A.counts[0] = ctl[0]; A.counts[1] = ctl[0]; A.counts[2] = 0; }

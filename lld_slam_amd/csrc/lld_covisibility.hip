@@ -18,6 +18,7 @@
 #include <vector>
 
 #include "lld_common.h"
+#include "lld_wave.h"
 
 namespace {
 
@@ -42,20 +43,6 @@ struct CovisArgs {
   int32_t* conn_start; int32_t* ord_start; int32_t* totals;                 // packed outputs
   int32_t* conn_kf; int32_t* conn_w; int32_t* ord_kf; int32_t* ord_w;
 };
-
-__device__ void bitonic_sort(u64* keys, int npad) {                         // ascending, npad a power of two
-  for (int k = 2; k <= npad; k <<= 1)
-    for (int j = k >> 1; j > 0; j >>= 1) {
-      for (int i = threadIdx.x; i < npad; i += kThreads) {
-        const int ixj = i ^ j;
-        if (ixj > i) {
-          const u64 a = keys[i], b = keys[ixj];
-          if ((a > b) == ((i & k) == 0)) { keys[i] = b; keys[ixj] = a; }
-        }
-      }
-      __syncthreads();
-    }
-}
 
 __global__ __launch_bounds__(kThreads) void covis_query(CovisArgs A) {
   extern __shared__ u64 dyn[];               // int counter[n_kf] while counting, the sort keys afterwards
@@ -99,14 +86,12 @@ __global__ __launch_bounds__(kThreads) void covis_query(CovisArgs A) {
       if (count_cull && A.obs_octave[o] <= lvl) c++;
     }
     if (cull) {
-#pragma unroll
-      for (int off = kGroup / 2; off > 0; off >>= 1) c += __shfl_xor(c, off);
+      c = lld_wave::sum<kGroup>(c);
       if (gl == 0 && count_cull && c >= A.th_obs) my_red++;
     }
   }
   if (cull) {
-#pragma unroll
-    for (int off = kWave / 2; off > 0; off >>= 1) { my_mps += __shfl_xor(my_mps, off); my_red += __shfl_xor(my_red, off); }
+    lld_wave::sum_each(my_mps, my_red);
     if (lane == 0) { atomicAdd(&s_cull[0], my_mps); atomicAdd(&s_cull[1], my_red); }
     __syncthreads();
     if (t == 0) {
@@ -147,8 +132,7 @@ __global__ __launch_bounds__(kThreads) void covis_query(CovisArgs A) {
     n_conn += tz; n_sel += ts;
     __syncthreads();
   }
-#pragma unroll
-  for (int o = kWave / 2; o > 0; o >>= 1) { const u64 other = __shfl_xor(best, o); if (other > best) best = other; }
+  best = lld_wave::max(best);
   if (lane == 0) s_best[wv] = best;
   __syncthreads();
   best = s_best[0];
@@ -167,7 +151,7 @@ __global__ __launch_bounds__(kThreads) void covis_query(CovisArgs A) {
   while (npad < n_sel) npad <<= 1;
   for (int i = t; i < npad; i += kThreads) dyn[i] = i < n_sel ? A.st_key[off + i] : 0ull;   // a real key is above 0: its weight is >= 1
   __syncthreads();
-  bitonic_sort(dyn, npad);
+  lld_wave::bitonic_sort<kThreads>(dyn, npad);
   for (int i = t; i < n_sel; i += kThreads) A.st_key[off + i] = dyn[npad - 1 - i];
 }
 
@@ -180,12 +164,8 @@ __global__ __launch_bounds__(kThreads) void covis_pack(CovisArgs A) {
     if (j < q) { v[0] += a; v[1] += b; }
     v[2] += a; v[3] += b;
   }
-#pragma unroll
-  for (int k = 0; k < 4; ++k) {
-#pragma unroll
-    for (int o = kWave / 2; o > 0; o >>= 1) v[k] += __shfl_xor(v[k], o);
-    if (lane == 0) s_sum[k][wv] = v[k];
-  }
+  lld_wave::sum_each(v[0], v[1], v[2], v[3]);
+  if (lane == 0) for (int k = 0; k < 4; ++k) s_sum[k][wv] = v[k];
   __syncthreads();
 #pragma unroll
   for (int k = 0; k < 4; ++k) { v[k] = 0; for (int w = 0; w < kWaves; ++w) v[k] += s_sum[k][w]; }

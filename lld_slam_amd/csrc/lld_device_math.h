@@ -26,6 +26,17 @@ LLD_HD Vec3 cross(const Vec3& a, const Vec3& b) {
   return vec3(a.y * b.z - a.z * b.y, a.z * b.x - a.x * b.z, a.x * b.y - a.y * b.x);
 }
 
+// Rwc * v for Rwc = Rcw.t(), all float (cv::Mat CV_32F): the float products summed in double in index order from the first, rounded to float once.
+LLD_HD void rwc_mul(const float* Rcw, const float* v, float* o) {
+#pragma unroll
+  for (int i = 0; i < 3; ++i) {
+    double s = (double)Rcw[i] * (double)v[0];
+    s += (double)Rcw[3 + i] * (double)v[1];
+    s += (double)Rcw[6 + i] * (double)v[2];
+    o[i] = (float)s;
+  }
+}
+
 // Eigen::Quaterniond(Matrix3d) — trace branch / largest-diagonal branch (Eigen Quaternion.h).
 LLD_HD Quat quat_from_rotation(const Mat3& R) {
   Quat q;

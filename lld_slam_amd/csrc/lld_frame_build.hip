@@ -14,6 +14,7 @@
 // the pyramids of an extractor, which the stream orders before that extractor's next call.
 #include "lld_stereo_internal.h"
 #include "lld_track_internal.h"
+#include "lld_wave.h"
 
 namespace {
 
@@ -70,14 +71,11 @@ __global__ __launch_bounds__(kBlock) void stereo_rows_kernel(RowsArgs A) {
       const long long maxr = (long long)ceilf(__fadd_rn(yR, r)), minr = (long long)floorf(__fsub_rn(yR, r));   // :546-556
       if (row < minr || row > maxr) continue;
       if (!(uR >= minU && uR <= maxU)) continue;                              // :594-596
-      int dist = 0;
-#pragma unroll
-      for (int w = 0; w < 8; w++) dist += __popc(dl[w] ^ A.right_desc[8 * iR + w]);
+      const int dist = lld_wave::hamming256(dl, A.right_desc + 8 * iR);
       best = min(best, (dist << kIdxBits) | iR);
     }
   }
-#pragma unroll
-  for (int m = kWave / 2; m >= 1; m >>= 1) best = min(best, __shfl_xor(best, m, kWave));
+  best = lld_wave::min(best);
   if (lane == 0) A.best_r[iL] = (best >> kIdxBits) < kThOrbDist ? (best & ((1 << kIdxBits) - 1)) : -1;       // bestDist < thOrbDist, :604
 }
 

@@ -16,8 +16,10 @@
 #include <climits>
 
 #include "lld_common.h"
+#include "lld_device_math.h"
 #include "lld_frame_track_state.h"
 #include "lld_track_internal.h"
+#include "lld_wave.h"
 
 namespace {
 
@@ -69,17 +71,6 @@ __device__ bool need_new_keyframe(const DecisionIn& p, int n_tracked_close, int 
   return !mono && p.keyframes_in_queue < 3;                                                                       // :1297-1305
 }
 
-// mRwc * x3Dc (Rwc = Rcw^T): the arithmetic of rwc_mul in lld_new_points.hip - float products summed in double in index order, one rounding.
-__device__ __forceinline__ void rwc_mul(const float* Rcw, const float* v, float* o) {
-#pragma unroll
-  for (int i = 0; i < 3; ++i) {
-    double s = (double)Rcw[i] * (double)v[0];
-    s += (double)Rcw[3 + i] * (double)v[1];
-    s += (double)Rcw[6 + i] * (double)v[2];
-    o[i] = (float)s;
-  }
-}
-
 __global__ __launch_bounds__(kFinThreads) void frame_finish_kernel(TrackDev D, FinishDev A, DecisionIn P) {
   __shared__ unsigned long long key[kFinMaxKeys];
   __shared__ int cnt[4];                                               // tracked close, non-tracked close, candidates
@@ -123,7 +114,7 @@ __global__ __launch_bounds__(kFinThreads) void frame_finish_kernel(TrackDev D, F
     }
     key[k] = kk;
   }
-  for (int off = 32; off > 0; off >>= 1) { n_tc += __shfl_xor(n_tc, off); n_ntc += __shfl_xor(n_ntc, off); n_cand += __shfl_xor(n_cand, off); }
+  lld_wave::sum_each(n_tc, n_ntc, n_cand);
   if (lane == 0) { atomicAdd(&cnt[0], n_tc); atomicAdd(&cnt[1], n_ntc); atomicAdd(&cnt[2], n_cand); }
   __syncthreads();
   // ---- 3. the decision
@@ -142,24 +133,13 @@ __global__ __launch_bounds__(kFinThreads) void frame_finish_kernel(TrackDev D, F
   const int m = cnt[2];                                                // vDepthIdx.size()
   // ---- 4. the creation (the whole workgroup takes the same branch)
   if (s_made && m > 0) {
-    // sort(vDepthIdx): a bitonic network on n_keys keys, the empty slots (all ones) last
-    for (int k = 2; k <= A.n_keys; k <<= 1) {
-      for (int j = k >> 1; j > 0; j >>= 1) {
-        for (int t = tid; t < (A.n_keys >> 1); t += kFinThreads) {
-          const int lo = ((t & ~(j - 1)) << 1) | (t & (j - 1)), hi = lo | j;
-          const unsigned long long a = key[lo], b = key[hi];
-          const bool up = (lo & k) == 0;
-          if ((a > b) == up) { key[lo] = b; key[hi] = a; }
-        }
-        __syncthreads();
-      }
-    }
+    lld_wave::bitonic_sort<kFinThreads>(key, A.n_keys);                // sort(vDepthIdx): the empty slots (all ones) last
     // the walk ends behind the first entry j with nPoints = j + 1 > 100 and depth > mThDepth (:1427); it is itself processed
     if (mode != FIN_INITIALIZATION) {
       int first = INT_MAX;
       for (int j = 100 + tid; j < m; j += kFinThreads)
         if (__uint_as_float((unsigned)(key[j] >> 32)) > A.th_depth) { first = j; break; }
-      for (int off = 32; off > 0; off >>= 1) first = min(first, __shfl_xor(first, off));
+      first = lld_wave::min(first);
       if (lane == 0 && first != INT_MAX) atomicMin(&s_first_far, first);
     }
     __syncthreads();
@@ -183,7 +163,7 @@ __global__ __launch_bounds__(kFinThreads) void frame_finish_kernel(TrackDev D, F
         const float z = A.depth[i], u = A.xy[2 * i], v = A.xy[2 * i + 1];
         const float xc[3] = {(u - A.cx) * z * A.invfx, (v - A.cy) * z * A.invfy, z};                      // Frame.cc:737-739
         float x[3];
-        rwc_mul(V.Rcw, xc, x);
+        lld::rwc_mul(V.Rcw, xc, x);
         for (int q = 0; q < 3; q++) { x[q] = x[q] + V.Ow[q]; A.x3d[3 * i + q] = x[q]; D.kp_world[3 * i + q] = x[q]; }   // :740
         A.created[i] = 1; A.new_id[i] = id;
         D.kp_has[i] = 1; D.kp_id[i] = id; D.kp_obs[i] = mode == FIN_LAST_FRAME ? 0 : 1;                    // a temporal point has no observation

@@ -23,6 +23,7 @@
 #include "lld_frame_track_state.h"
 #include "lld_pnp_internal.h"
 #include "lld_track_internal.h"
+#include "lld_wave.h"
 
 namespace {
 
@@ -78,21 +79,15 @@ struct LevelTable { float v[LLD_ORB_MAX_LEVELS]; };
 __global__ __launch_bounds__(kAsmThreads) void reloc_pnp_assemble_kernel(RelocDev R, const int32_t* __restrict__ off, const uint8_t* __restrict__ keep, lld_pnp::SlabDev slab,
                                                                          const float* __restrict__ t_xy, const int32_t* __restrict__ t_octave, LevelTable sigma2, float th2) {
   __shared__ int wsum[kAsmThreads / 64];
-  const int c = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  if (!keep[c]) return;
+  const int c = blockIdx.x, tid = threadIdx.x;
+  if (!keep[c]) return;                            // uniform over the workgroup
   const uint8_t* has = R.m_has + (size_t)c * R.nt;
   const float* world = R.m_world + 3 * (size_t)c * R.nt;
   const int per = (R.nt + kAsmThreads - 1) / kAsmThreads, k0 = min(tid * per, R.nt), k1 = min(k0 + per, R.nt);
   int cnt = 0;
   for (int k = k0; k < k1; k++) cnt += has[k] ? 1 : 0;
-  int incl = cnt;
-#pragma unroll
-  for (int o = 1; o < 64; o <<= 1) { const int t = __shfl_up(incl, o); if (lane >= o) incl += t; }
-  if (lane == 63) wsum[wave] = incl;
-  __syncthreads();
-  int base = 0;
-  for (int w = 0; w < wave; w++) base += wsum[w];
-  int e = off[c] + base + incl - cnt;
+  int n_has;
+  int e = off[c] + lld_wave::block_excl_scan<kAsmThreads>(cnt, wsum, n_has);
   const int end = off[c] + R.m_cnt[4 * c];         // (the count the host sized the slab by)
   for (int k = k0; k < k1; k++) {
     if (!has[k] || e >= end) continue;
@@ -227,7 +222,7 @@ __global__ __launch_bounds__(kSlotThreads) void reloc_pick_kernel(RelocDev R, Tr
     D.rec_kp_id[0][k] = has ? R.s_id[o + k] : -1; D.rec_kp_out[0][k] = bad;
     if (has) { n_pts++; if (R.s_obs[o + k]) n_map++; }
   }
-  for (int off = 32; off > 0; off >>= 1) { n_pts += __shfl_xor(n_pts, off); n_map += __shfl_xor(n_map, off); }
+  lld_wave::sum_each(n_pts, n_map);
   if ((tid & 63) == 0) { atomicAdd(&cnt_sh[0], n_pts); atomicAdd(&cnt_sh[1], n_map); }
   __syncthreads();
   if (tid == 0) {

@@ -23,6 +23,7 @@
 #include "lld_device_math.h"
 #include "lld_frame_track_state.h"
 #include "lld_track_internal.h"
+#include "lld_wave.h"
 
 namespace {
 
@@ -117,9 +118,7 @@ __global__ __launch_bounds__(1024) void track_after_pose_kernel(TrackDev D, View
     if (out_) { D.ln_has[i] = 0; D.ln_id[i] = -1; } else n_ln++;
   }
   // wavefront sums first: five LDS atomics per wavefront instead of per lane
-  for (int off = 32; off > 0; off >>= 1) {
-    n_pts += __shfl_xor(n_pts, off); n_map += __shfl_xor(n_map, off); n_disc += __shfl_xor(n_disc, off); n_lm += __shfl_xor(n_lm, off); n_ln += __shfl_xor(n_ln, off);
-  }
+  lld_wave::sum_each(n_pts, n_map, n_disc, n_lm, n_ln);
   if ((tid & 63) == 0) { atomicAdd(&cnt[0], n_pts); atomicAdd(&cnt[1], n_map); atomicAdd(&cnt[2], n_disc); atomicAdd(&cnt[3], n_lm); atomicAdd(&cnt[4], n_ln); }
   __syncthreads();
   if (tid == 0) {

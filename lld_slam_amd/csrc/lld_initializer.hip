@@ -27,6 +27,7 @@
 
 #include "lld_common.h"
 #include "lld_ransac.h"
+#include "lld_wave.h"
 
 namespace {
 
@@ -668,15 +669,6 @@ __global__ __launch_bounds__(kRtLanes) void ini_checkrt(Dev d) {
   d.rt_p3d[3 * o] = p[0]; d.rt_p3d[3 * o + 1] = p[1]; d.rt_p3d[3 * o + 2] = p[2];
 }
 
-__device__ inline int block_sum(int v, int* sh) {
-#pragma unroll
-  for (int s = 32; s > 0; s >>= 1) v += __shfl_xor(v, s);
-  __syncthreads();
-  if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = v;
-  __syncthreads();
-  return sh[0] + sh[1] + sh[2] + sh[3];
-}
-
 __global__ __launch_bounds__(kThreads) void ini_select(Dev d) {
   __shared__ int sh[4];
   const int h = blockIdx.x, tid = threadIdx.x;
@@ -685,7 +677,7 @@ __global__ __launch_bounds__(kThreads) void ini_select(Dev d) {
   const float* cs = d.rt_cos + (size_t)h * d.N;
   int c = 0;
   for (int i = tid; i < d.N; i += kThreads) c += fl[i] & 1;
-  const int nGood = block_sum(c, sh);
+  const int nGood = lld_wave::block_sum(c, sh);
   float par = 0.0f;
   if (nGood > 0) {
     // sorted[idx], idx = min(50, nGood-1): the largest key with at most idx counted keys below it, built bit by bit
@@ -695,7 +687,7 @@ __global__ __launch_bounds__(kThreads) void ini_select(Dev d) {
       const uint32_t trial = key | (1u << bit);
       int below = 0;
       for (int i = tid; i < d.N; i += kThreads) below += ((fl[i] & 1) && float_key(cs[i]) < trial) ? 1 : 0;
-      if (block_sum(below, sh) <= idx) key = trial;
+      if (lld_wave::block_sum(below, sh) <= idx) key = trial;
     }
     par = parallax_deg(key_float(key));
   }

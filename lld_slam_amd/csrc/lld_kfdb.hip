@@ -28,6 +28,7 @@
 
 #include "lld_bow_score.h"
 #include "lld_common.h"
+#include "lld_wave.h"
 
 namespace {
 
@@ -68,18 +69,6 @@ struct KfOut {
 struct Move {
   int32_t from, to, n;
 };
-
-__device__ inline int wave_sum(int x) {
-#pragma unroll
-  for (int o = 32; o; o >>= 1) x += __shfl_xor(x, o);
-  return x;
-}
-
-__device__ inline int wave_min(int x) {
-#pragma unroll
-  for (int o = 32; o; o >>= 1) x = min(x, __shfl_xor(x, o));
-  return x;
-}
 
 // bestAccScore's `if(accScore>bestAccScore)`: the later value replaces only when strictly greater, so every partial starting
 // from the initial value and combined this way gives the sequential result.
@@ -126,8 +115,8 @@ __global__ __launch_bounds__(256) void kfdb_walk(const KfSlot* __restrict__ slot
     const int p = qpos[pword[off + j]];
     if (p >= 0) { cnt++; mn = min(mn, p); }
   }
-  cnt = wave_sum(cnt);
-  mn = wave_min(mn);
+  cnt = lld_wave::sum(cnt);
+  mn = lld_wave::min(mn);
   if (lane || cnt == 0) return;
   // The walk meets this keyframe cnt times.  Per encounter: a stamp != id resets words to 0 and (unless connected) stamps and
   // lists it; then words++.
@@ -208,7 +197,7 @@ __global__ __launch_bounds__(kFinishThreads) void kfdb_finish(const KfSlot* __re
     best_acc = keep_greater(best_acc, acc);
   }
   // bestAccScore over the workgroup (keys[] doubles as the exchange area before it holds keys)
-  for (int o = 32; o; o >>= 1) best_acc = keep_greater(best_acc, __shfl_xor(best_acc, o));
+  best_acc = lld_wave::max(best_acc);            // (keep_greater's rule lane against lane)
   float* red = (float*)keys;
   if ((t & 63) == 0) red[t >> 6] = best_acc;
   __syncthreads();

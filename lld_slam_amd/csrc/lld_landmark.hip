@@ -24,6 +24,7 @@
 #include <vector>
 
 #include "lld_common.h"
+#include "lld_wave.h"
 
 namespace {
 
@@ -68,17 +69,6 @@ __device__ __forceinline__ int compact_kept(const int32_t* __restrict__ obs_kf, 
   return n;
 }
 
-__device__ __forceinline__ int wave_min(int key) {
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) { const int o = __shfl_xor(key, off); key = o < key ? o : key; }
-  return key;
-}
-
-__device__ __forceinline__ int hamming(const uint4& a0, const uint4& a1, const uint4& b0, const uint4& b1) {
-  return __popc(a0.x ^ b0.x) + __popc(a0.y ^ b0.y) + __popc(a0.z ^ b0.z) + __popc(a0.w ^ b0.w) +
-         __popc(a1.x ^ b1.x) + __popc(a1.y ^ b1.y) + __popc(a1.z ^ b1.z) + __popc(a1.w ^ b1.w);
-}
-
 // grid: the list, block 64
 __global__ __launch_bounds__(kWave) void lm_point_wave(PointArgs A) {
   __shared__ int kept[kWave];
@@ -102,7 +92,7 @@ __global__ __launch_bounds__(kWave) void lm_point_wave(PointArgs A) {
   for (int j = 0; j < N; ++j) {
     const uint4 b0 = make_uint4(bcast(d0.x, j), bcast(d0.y, j), bcast(d0.z, j), bcast(d0.w, j));
     const uint4 b1 = make_uint4(bcast(d1.x, j), bcast(d1.y, j), bcast(d1.z, j), bcast(d1.w, j));
-    dist[j * kWave + lane] = (uint16_t)hamming(d0, d1, b0, b1);
+    dist[j * kWave + lane] = (uint16_t)lld_wave::hamming256(d0, d1, b0, b1);
   }
   const int idx = (int)(0.5 * (N - 1));      // vDists[0.5*(N-1)] (:294)
   int lo = 0, hi = 256;                      // sorted[idx] = the smallest v with count(d <= v) >= idx + 1
@@ -112,7 +102,7 @@ __global__ __launch_bounds__(kWave) void lm_point_wave(PointArgs A) {
     for (int j = 0; j < N; ++j) cnt += dist[j * kWave + lane] <= mid ? 1 : 0;
     if (cnt > idx) hi = mid; else lo = mid + 1;
   }
-  const int key = wave_min(lane < N ? ((lo << 16) | lane) : 0x7fffffff);   // median < BestMedian in row order (:296-300)
+  const int key = lld_wave::min(lane < N ? ((lo << 16) | lane) : 0x7fffffff);   // median < BestMedian in row order (:296-300)
   const int w = kept[key & 0xffff];
   if (lane < 8) A.desc[(size_t)p * 8 + lane] = A.obs_desc[(size_t)(s + w) * 8 + lane];
   if (lane == 0) { A.best_obs[p] = w; A.best_median[p] = key >> 16; A.upd[p] = 1; }
@@ -149,13 +139,13 @@ __global__ __launch_bounds__(kBlock) void lm_point_block(PointArgs A) {
     while (lo < hi) {
       const int mid = (lo + hi) >> 1;
       int cnt = 0;
-      for (int j = 0; j < N; ++j) cnt += hamming(a0, a1, rows[2 * j], rows[2 * j + 1]) <= mid ? 1 : 0;
+      for (int j = 0; j < N; ++j) cnt += lld_wave::hamming256(a0, a1, rows[2 * j], rows[2 * j + 1]) <= mid ? 1 : 0;
       if (cnt > idx) hi = mid; else lo = mid + 1;
     }
     const int k = (lo << 16) | i;
     key = k < key ? k : key;
   }
-  key = wave_min(key);
+  key = lld_wave::min(key);
   if ((tid & (kWave - 1)) == 0) red[tid / kWave] = key;
   __syncthreads();
 #pragma unroll

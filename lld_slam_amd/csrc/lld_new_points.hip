@@ -21,6 +21,7 @@
 #include <vector>
 
 #include "lld_common.h"
+#include "lld_device_math.h"
 #include "lld_ransac.h"
 
 namespace {
@@ -41,17 +42,6 @@ struct Dev {
   int32_t* rank;
   int32_t N, n_pairs, monocular;
 };
-
-// Rwc*v for Rwc = Rcw.t(): the float products summed in double in index order from the first, rounded to float once.
-__host__ __device__ __forceinline__ void rwc_mul(const float* Rcw, const float* v, float* o) {
-#pragma unroll
-  for (int i = 0; i < 3; ++i) {
-    double s = (double)Rcw[i] * (double)v[0];
-    s += (double)Rcw[3 + i] * (double)v[1];
-    s += (double)Rcw[6 + i] * (double)v[2];
-    o[i] = (float)s;
-  }
-}
 
 // Mat::dot of row r of Rcw with x: the double sum.
 __device__ __forceinline__ double row_dot(const float* Rcw, int r, const float* x) {
@@ -74,7 +64,7 @@ __host__ __device__ __forceinline__ double norm3(const float* v) {
 
 // Ow = -Rwc*tcw (src/KeyFrame.cc:85)
 __host__ __device__ __forceinline__ void camera_center(const lld_new_points_kf* k, float* ow) {
-  rwc_mul(k->Rcw, k->tcw, ow);
+  lld::rwc_mul(k->Rcw, k->tcw, ow);
 #pragma unroll
   for (int i = 0; i < 3; ++i) ow[i] = -ow[i];
 }
@@ -104,7 +94,7 @@ __device__ __forceinline__ bool unproject_stereo(const lld_new_points_kf* k, con
                                                  float z, float* x3d) {
   if (!(z > 0.0f)) return false;
   const float c[3] = {(u - k->cx) * z * invfx, (v - k->cy) * z * invfy, z};
-  rwc_mul(k->Rcw, c, x3d);
+  lld::rwc_mul(k->Rcw, c, x3d);
 #pragma unroll
   for (int i = 0; i < 3; ++i) x3d[i] = x3d[i] + ow[i];
   return true;
@@ -162,8 +152,8 @@ __global__ __launch_bounds__(kLanes) void np_match(Dev d) {
     const float xn1[3] = {(kx1 - k1->cx) * invfx1, (ky1 - k1->cy) * invfy1, 1.0f};   // :301-302
     const float xn2[3] = {(kx2 - k2->cx) * invfx2, (ky2 - k2->cy) * invfy2, 1.0f};
     float ray1[3], ray2[3];
-    rwc_mul(k1->Rcw, xn1, ray1);                                               // :304-305
-    rwc_mul(k2->Rcw, xn2, ray2);
+    lld::rwc_mul(k1->Rcw, xn1, ray1);                                               // :304-305
+    lld::rwc_mul(k2->Rcw, xn2, ray2);
     double dot = (double)ray1[0] * (double)ray2[0];
     dot += (double)ray1[1] * (double)ray2[1];
     dot += (double)ray1[2] * (double)ray2[2];

@@ -15,6 +15,7 @@
 //   * float gates use explicit round-to-nearest intrinsics so no FMA contraction can change a comparison.
 #include "lld_common.h"
 #include "lld_track_internal.h"
+#include "lld_wave.h"
 
 namespace {
 
@@ -61,12 +62,8 @@ struct Problem {
   int32_t* ap_counts; int ap_min_matches, ap_is_retry;      // ap_counts: [0] n of the first search, [1] n of the search whose matches were taken, [2] retry used
 };
 
-template <class Ptr>
-__device__ __forceinline__ int hamming256(const uint32_t (&a)[8], Ptr b) {
-  const uint4 b0 = *reinterpret_cast<const uint4*>(b), b1 = *reinterpret_cast<const uint4*>(b + 4);
-  return __popc(a[0] ^ b0.x) + __popc(a[1] ^ b0.y) + __popc(a[2] ^ b0.z) + __popc(a[3] ^ b0.w) +
-         __popc(a[4] ^ b1.x) + __popc(a[5] ^ b1.y) + __popc(a[6] ^ b1.z) + __popc(a[7] ^ b1.w);
-}
+// a descriptor (eight words, 16-byte aligned: the frame's array and its copy in LDS) as the two uint4 it is read as
+__device__ __forceinline__ const uint4* as_uint4(const uint32_t* desc) { return reinterpret_cast<const uint4*>(desc); }
 
 __device__ __forceinline__ void top2_insert(unsigned long long c, unsigned long long& b1, unsigned long long& b2) {
   if (c < b1) { b2 = b1; b1 = c; } else if (c < b2) { b2 = c; }
@@ -389,7 +386,7 @@ __global__ __launch_bounds__(kThreads) void orb_search_kernel(const Problem* __r
         }
         auto visit = [&](int pos, const TKey& T, unsigned key) {
           if (!gates_pass(P, Q, T, q, blk, use_blk, lvl)) return;
-          const int d = P.desc_in_lds ? hamming256(qd, dsc + 8 * (size_t)pos) : hamming256(qd, P.t_desc + 8 * (size_t)tk_idx(T.meta));
+          const int d = P.desc_in_lds ? lld_wave::hamming256(qd, as_uint4(dsc + 8 * (size_t)pos)) : lld_wave::hamming256(qd, as_uint4(P.t_desc + 8 * (size_t)tk_idx(T.meta)));
           if (steal && blk[tk_idx(T.meta)] <= d) return;                                                           // ORBmatcher.cc:443-444
           if (P.tie_last) key = ~key;
           topk_insert(((unsigned long long)d << 32) | key, c);
@@ -545,7 +542,7 @@ __global__ __launch_bounds__(kThreads) void orb_search_kernel(const Problem* __r
           unsigned long long t1 = kNone, t2 = kNone;
           auto visit = [&](int pos, const TKey& T, unsigned key) {
             if (!gates_pass(P, Q, T, q, blk, false, lvl)) return;
-            const int d = P.desc_in_lds ? hamming256(qd, dsc + 8 * (size_t)pos) : hamming256(qd, P.t_desc + 8 * (size_t)tk_idx(T.meta));
+            const int d = P.desc_in_lds ? lld_wave::hamming256(qd, as_uint4(dsc + 8 * (size_t)pos)) : lld_wave::hamming256(qd, as_uint4(P.t_desc + 8 * (size_t)tk_idx(T.meta)));
             if (blk[tk_idx(T.meta)] <= d) return;                                                                  // ORBmatcher.cc:443-444
             top2_insert(((unsigned long long)d << 32) | key, t1, t2);
           };

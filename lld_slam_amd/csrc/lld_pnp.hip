@@ -33,6 +33,7 @@
 #include "lld_common.h"
 #include "lld_pnp_internal.h"
 #include "lld_ransac.h"
+#include "lld_wave.h"
 
 namespace {
 
@@ -785,7 +786,7 @@ __global__ __launch_bounds__(kThreads) void pnp_refine(Dev d, int n_jobs) {
       for (int q = 0; q < 12; ++q) rt[q] = rt_sh[q];
       int c = 0;
       for (int i = tid; i < ds.n; i += kThreads) c += is_inlier(rt, d.pt[ds.off + i], d.uv[ds.off + i], ds.fu, ds.fv, ds.uc, ds.vc);
-      for (int o = 32; o; o >>= 1) c += __shfl_xor(c, o);
+      c = lld_wave::sum(c);
       if ((tid & 63) == 0) cnt_sh[tid >> 6] = c;
       __syncthreads();
       if (tid == 0) {

@@ -16,6 +16,7 @@
 #include "lld_common.h"
 #include "lld_device_math.h"
 #include "lld_track_internal.h"
+#include "lld_wave.h"
 
 namespace {
 
@@ -807,22 +808,8 @@ namespace {
 constexpr int kAsmThreads = 1024;
 struct PoseAsmConsts { double delta_mono, delta_stereo, delta_ln_stereo, delta_ln_mono, thr_ln_stereo, thr_ln_mono; };
 
-__device__ __forceinline__ int block_excl_scan(int v, int* lds /*[kAsmThreads/64 + 1]*/, int& total) {
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  int incl = v;
-#pragma unroll
-  for (int off = 1; off < 64; off <<= 1) { const int t = __shfl_up(incl, off); if (lane >= off) incl += t; }
-  __syncthreads();                                             // (lds may still be read by the previous scan)
-  if (lane == 63) lds[wave] = incl;
-  __syncthreads();
-  int base = 0, tot = 0;
-  for (int w = 0; w < kAsmThreads / 64; w++) { const int t = lds[w]; if (w < wave) base += t; tot += t; }
-  total = tot;
-  return base + incl - v;
-}
-
 __global__ __launch_bounds__(kAsmThreads) void pose_assemble_kernel(lld_track::PoseTrackDev in, PoseAsmConsts dc, char* img, PoseLayout Y, int* pt_kp, int* ln_fi) {
-  __shared__ int scan_lds[kAsmThreads / 64 + 1];
+  __shared__ int scan_lds[kAsmThreads / 64];
   extern __shared__ unsigned char edge_stereo[];               // vnStereoLines: one entry per line EDGE, in the order they are added
   const int tid = threadIdx.x;
   const CamK cam = lld::make_camk(in.cam);
@@ -835,7 +822,7 @@ __global__ __launch_bounds__(kAsmThreads) void pose_assemble_kernel(lld_track::P
   int cnt = 0;
   for (int k = k0; k < k1; k++) cnt += in.kp_has[k] ? 1 : 0;
   int n_pt;
-  int e = block_excl_scan(cnt, scan_lds, n_pt);
+  int e = lld_wave::block_excl_scan<kAsmThreads>(cnt, scan_lds, n_pt);
   for (int k = k0; k < k1; k++) {
     if (!in.kp_has[k]) continue;
     const float ur = in.t_uright ? in.t_uright[k] : -1.f;
@@ -851,8 +838,8 @@ __global__ __launch_bounds__(kAsmThreads) void pose_assemble_kernel(lld_track::P
   int lc = 0, ec = 0;
   for (int i = l0; i < l1; i++) if (in.ln_has[i]) { lc++; ec += in.ln_match[i] >= 0 ? 2 : 1; }
   int n_ln, n_le;
-  int l = block_excl_scan(lc, scan_lds, n_ln);
-  int ie = block_excl_scan(ec, scan_lds, n_le);
+  int l = lld_wave::block_excl_scan<kAsmThreads>(lc, scan_lds, n_ln);
+  int ie = lld_wave::block_excl_scan<kAsmThreads>(ec, scan_lds, n_le);
   {
     int ie2 = ie;
     for (int i = l0; i < l1; i++) if (in.ln_has[i]) { const bool hr = in.ln_match[i] >= 0; edge_stereo[ie2++] = hr; if (hr) edge_stereo[ie2++] = 1; }
@@ -895,7 +882,7 @@ __global__ __launch_bounds__(kAsmThreads) void pose_assemble_kernel(lld_track::P
 // The point half of pose_assemble_kernel for slot blockIdx.x of n_slots copies of the frame's state: slot s owns points [s nt, s nt + n_pt)
 // of the image.  A slot that does not run gets no edges: pose_opt_kernel leaves such a frame at once (fewer than three points).
 __global__ __launch_bounds__(kAsmThreads) void pose_slots_assemble_kernel(lld_track::PoseSlotsDev in, PoseAsmConsts dc, char* img, PoseLayout Y, int* pt_kp) {
-  __shared__ int scan_lds[kAsmThreads / 64 + 1];
+  __shared__ int scan_lds[kAsmThreads / 64];
   const int tid = threadIdx.x, s = blockIdx.x;
   const bool run = in.run[s] != 0;
   const uint8_t* kp_has = in.kp_has + (size_t)s * in.nt;
@@ -905,7 +892,7 @@ __global__ __launch_bounds__(kAsmThreads) void pose_slots_assemble_kernel(lld_tr
   int cnt = 0;
   if (run) for (int k = k0; k < k1; k++) cnt += kp_has[k] ? 1 : 0;
   int n_pt;
-  int e = block_excl_scan(cnt, scan_lds, n_pt);
+  int e = lld_wave::block_excl_scan<kAsmThreads>(cnt, scan_lds, n_pt);
   const size_t base = (size_t)s * in.nt;
   for (int k = k0; k < k1 && run; k++) {
     if (!kp_has[k]) continue;
@@ -1149,6 +1136,117 @@ extern "C" __attribute__((visibility("default"))) int lld_exp_pose_wave_sums(lld
   LLD_HIP_TRY(hipGetLastError());
   LLD_HIP_TRY(hipMemcpyAsync(out28, d + 64 * 28, 28 * sizeof(double), hipMemcpyDeviceToHost, s));
   LLD_HIP_TRY(hipMemcpyAsync(out1, d + 64 * 28 + 28, 64 * sizeof(double), hipMemcpyDeviceToHost, s));
+  LLD_HIP_TRY(hipStreamSynchronize(s));
+  return LLD_OK;
+}
+#endif
+
+#ifdef LLD_EXPERIMENTS
+// experiments build only: the primitives of lld_wave.h on their own, one workgroup over caller data (tests/test_gpu_wave_prims.py).
+//   WP_SCAN   threads 256 | 1024.  in: int a[threads], b[threads].  out: int [2][threads + 1] - block_excl_scan of a, then of b through the
+//             same LDS array with nothing in between; entry [threads] of each row is the total as the LAST lane saw it.
+//   WP_SORT   256 threads, n = npad (a power of two in [2, 4096]).  in / out: u64 [n].
+//   WP_INT    64 threads.  in: int [64].  out: int [4][3][64] - widths 64, 16, 8, 4; sum, min, max; as every lane sees them.
+//   WP_F64    64 threads.  in: double a[64], b[64], c[64].  out: double [4][64] - sum(a), then a, b, c through one sum_each.
+//   WP_BLOCK  threads 256 | 768.  in: double x[threads], int k[threads].  out: double block_sum(x)[threads], double block_max(|x|)[threads],
+//             int block_sum(k)[threads] (stored as the doubles' and ints' byte images, in this order).
+//   WP_HAMMING  64 threads, n pairs.  in: uint32 [n][16] (a, then b; 16-byte aligned rows).  out: int [3][n] - the uint4 form, the
+//             (words, uint4*) form and the (words, uint32*) form.
+namespace {
+enum { WP_SCAN, WP_SORT, WP_INT, WP_F64, WP_BLOCK, WP_HAMMING };
+constexpr int kWpSortThreads = 256, kWpSortMax = 4096;
+
+template <int kThreads>
+__global__ __launch_bounds__(kThreads) void wp_scan_kernel(const int* in, int* out) {
+  __shared__ int lds[kThreads / 64];
+  const int t = threadIdx.x;
+  int ta, tb;
+  const int ra = lld_wave::block_excl_scan<kThreads>(in[t], lds, ta);
+  const int rb = lld_wave::block_excl_scan<kThreads>(in[kThreads + t], lds, tb);
+  out[t] = ra; out[kThreads + 1 + t] = rb;
+  if (t == kThreads - 1) { out[kThreads] = ta; out[2 * kThreads + 1] = tb; }
+}
+
+__global__ __launch_bounds__(kWpSortThreads) void wp_sort_kernel(const unsigned long long* in, unsigned long long* out, int npad) {
+  __shared__ unsigned long long keys[kWpSortMax];
+  for (int i = threadIdx.x; i < npad; i += kWpSortThreads) keys[i] = in[i];
+  __syncthreads();
+  lld_wave::bitonic_sort<kWpSortThreads>(keys, npad);
+  for (int i = threadIdx.x; i < npad; i += kWpSortThreads) out[i] = keys[i];
+}
+
+template <int W>
+__device__ void wp_int_width(int x, int* out) {
+  out[threadIdx.x] = lld_wave::sum<W>(x); out[64 + threadIdx.x] = lld_wave::min<W>(x); out[128 + threadIdx.x] = lld_wave::max<W>(x);
+}
+__global__ __launch_bounds__(64) void wp_int_kernel(const int* in, int* out) {
+  const int x = in[threadIdx.x];
+  wp_int_width<64>(x, out); wp_int_width<16>(x, out + 192); wp_int_width<8>(x, out + 384); wp_int_width<4>(x, out + 576);
+}
+
+__global__ __launch_bounds__(64) void wp_f64_kernel(const double* in, double* out) {
+  const int t = threadIdx.x;
+  double a = in[t], b = in[64 + t], c = in[128 + t];
+  out[t] = lld_wave::sum(a);
+  lld_wave::sum_each(a, b, c);
+  out[64 + t] = a; out[128 + t] = b; out[192 + t] = c;
+}
+
+__global__ __launch_bounds__(1024) void wp_block_kernel(const double* x, const int* k, double* sum, double* mx, int* isum) {
+  __shared__ double lds[16];
+  __shared__ int ilds[16];
+  const int t = threadIdx.x;
+  sum[t] = lld_wave::block_sum(x[t], lds);
+  mx[t] = lld_wave::block_max(fabs(x[t]), lds);
+  isum[t] = lld_wave::block_sum(k[t], ilds);
+}
+
+__global__ __launch_bounds__(64) void wp_hamming_kernel(const uint32_t* in, int* out, int n) {
+  for (int i = threadIdx.x; i < n; i += 64) {
+    const uint32_t* a = in + 16 * (size_t)i; const uint32_t* b = a + 8;
+    const uint4* a4 = reinterpret_cast<const uint4*>(a); const uint4* b4 = reinterpret_cast<const uint4*>(b);
+    uint32_t w[8];
+    for (int q = 0; q < 8; q++) w[q] = a[q];
+    out[i] = lld_wave::hamming256(a4[0], a4[1], b4[0], b4[1]);
+    out[n + i] = lld_wave::hamming256(w, b4);
+    out[2 * n + i] = lld_wave::hamming256(w, b);
+  }
+}
+}  // namespace
+extern "C" __attribute__((visibility("default"))) int lld_exp_wave_prims(lld_ctx* ctx, int what, int threads, int n, const void* in, void* out) {
+  if (!ctx || !in || !out) return LLD_ERR_INVALID;
+  size_t nin = 0, nout = 0;
+  switch (what) {
+    case WP_SCAN: if (threads != 256 && threads != 1024) return LLD_ERR_INVALID; nin = 8 * (size_t)threads; nout = 8 * ((size_t)threads + 1); break;
+    case WP_SORT: if (n < 2 || n > kWpSortMax || (n & (n - 1))) return LLD_ERR_INVALID; nin = nout = 8 * (size_t)n; break;
+    case WP_INT: nin = 4 * 64; nout = 4 * 4 * 3 * 64; break;
+    case WP_F64: nin = 8 * 3 * 64; nout = 8 * 4 * 64; break;
+    case WP_BLOCK: if (threads != 256 && threads != 768) return LLD_ERR_INVALID; nin = 12 * (size_t)threads; nout = 20 * (size_t)threads; break;
+    case WP_HAMMING: if (n < 1 || n > 4096) return LLD_ERR_INVALID; nin = 64 * (size_t)n; nout = 12 * (size_t)n; break;
+    default: return LLD_ERR_INVALID;
+  }
+  LLD_HIP_TRY(hipSetDevice(ctx->device));
+  const size_t o_out = lld_slab::pad(nin);
+  void* db; int st = lld_ctx_scratch(ctx, o_out + nout, &db); if (st) return st;
+  char* d = static_cast<char*>(db); char* e = d + o_out;
+  hipStream_t s = ctx->stream;
+  LLD_HIP_TRY(hipMemcpyAsync(d, in, nin, hipMemcpyHostToDevice, s));
+  switch (what) {
+    case WP_SCAN:
+      if (threads == 256) hipLaunchKernelGGL(wp_scan_kernel<256>, dim3(1), dim3(256), 0, s, (const int*)d, (int*)e);
+      else hipLaunchKernelGGL(wp_scan_kernel<1024>, dim3(1), dim3(1024), 0, s, (const int*)d, (int*)e);
+      break;
+    case WP_SORT: hipLaunchKernelGGL(wp_sort_kernel, dim3(1), dim3(kWpSortThreads), 0, s, (const unsigned long long*)d, (unsigned long long*)e, n); break;
+    case WP_INT: hipLaunchKernelGGL(wp_int_kernel, dim3(1), dim3(64), 0, s, (const int*)d, (int*)e); break;
+    case WP_F64: hipLaunchKernelGGL(wp_f64_kernel, dim3(1), dim3(64), 0, s, (const double*)d, (double*)e); break;
+    case WP_BLOCK:
+      hipLaunchKernelGGL(wp_block_kernel, dim3(1), dim3(threads), 0, s, (const double*)d, (const int*)(d + 8 * (size_t)threads), (double*)e,
+                         (double*)(e + 8 * (size_t)threads), (int*)(e + 16 * (size_t)threads));
+      break;
+    default: hipLaunchKernelGGL(wp_hamming_kernel, dim3(1), dim3(64), 0, s, (const uint32_t*)d, (int*)e, n); break;
+  }
+  LLD_HIP_TRY(hipGetLastError());
+  LLD_HIP_TRY(hipMemcpyAsync(out, e, nout, hipMemcpyDeviceToHost, s));
   LLD_HIP_TRY(hipStreamSynchronize(s));
   return LLD_OK;
 }

@@ -24,6 +24,7 @@
 #include "lld_common.h"
 #include "lld_device_math.h"
 #include "lld_sim3_math.h"
+#include "lld_wave.h"
 
 namespace {
 
@@ -71,11 +72,8 @@ __global__ __launch_bounds__(1024) void pg_errors_kernel(PgArrays A) {
     for (int k = 0; k < 7; k++) { A.err[7 * (size_t)e + k] = er[k]; c += er[k] * er[k]; }
     part += c;
   }
-  for (int off = 32; off > 0; off >>= 1) part += __shfl_xor(part, off);
-  __syncthreads();
-  if ((tid & 63) == 0) scratch[tid >> 6] = part;
-  __syncthreads();
-  if (tid == 0) { double s = 0.0; for (int w = 0; w < 16; w++) s += scratch[w]; A.sc[5] = s; }
+  const double s = lld_wave::block_sum(part, scratch);
+  if (tid == 0) A.sc[5] = s;
 }
 
 // lane <-> (edge, vertex role, dof)
@@ -167,12 +165,8 @@ __global__ __launch_bounds__(1024) void pg_pcg_init_kernel(PgArrays A, double la
     A.z[i] = zv; A.p[i] = zv;
     part += A.r[i] * zv;
   }
-  for (int off = 32; off > 0; off >>= 1) part += __shfl_xor(part, off);
-  __syncthreads();
-  if ((tid & 63) == 0) scratch[tid >> 6] = part;
-  __syncthreads();
+  const double rz0 = lld_wave::block_sum(part, scratch);
   if (tid == 0) {
-    double rz0 = 0.0; for (int w = 0; w < 16; w++) rz0 += scratch[w];
     const bool ok = ok_s != 0 && isfinite(rz0);
     A.sc[0] = rz0; A.sc[1] = tol * tol * rz0; A.sc[2] = 0.0; A.sc[3] = (ok && rz0 > 0.0) ? 0.0 : 1.0; A.sc[4] = ok ? 1.0 : 0.0;
   }
@@ -208,17 +202,9 @@ __global__ __launch_bounds__(1024) void pg_pcg_update_kernel(PgArrays A, int max
   if (A.sc[3] != 0.0) return;
   const int tid = threadIdx.x, n = 7 * A.nu;
   const double rz = A.sc[0], stop = A.sc[1];
-  auto bsum = [&](double part) {
-    for (int off = 32; off > 0; off >>= 1) part += __shfl_xor(part, off);
-    __syncthreads();
-    if ((tid & 63) == 0) scratch[tid >> 6] = part;
-    __syncthreads();
-    double s = 0.0; for (int w = 0; w < 16; w++) s += scratch[w];
-    return s;
-  };
   double part = 0.0;
   for (int i = tid; i < n; i += 1024) part += A.p[i] * A.ap[i];
-  const double pAp = bsum(part);
+  const double pAp = lld_wave::block_sum(part, scratch);
   if (!(pAp > 0.0) || !isfinite(pAp)) { if (tid == 0) { A.sc[3] = 1.0; A.sc[4] = 0.0; } return; }
   const double alpha = rz / pAp;
   for (int i = tid; i < n; i += 1024) { A.x[i] += alpha * A.p[i]; A.r[i] -= alpha * A.ap[i]; }
@@ -232,7 +218,7 @@ __global__ __launch_bounds__(1024) void pg_pcg_update_kernel(PgArrays A, int max
     A.z[i] = zv;
     part += A.r[i] * zv;
   }
-  const double rz_new = bsum(part);
+  const double rz_new = lld_wave::block_sum(part, scratch);
   const double iters = A.sc[2] + 1.0;
   bool done = false, ok = true;
   if (!isfinite(rz_new)) { done = true; ok = false; }
@@ -255,11 +241,8 @@ __global__ __launch_bounds__(1024) void pg_update_kernel(PgArrays A, double lamb
 #pragma unroll
     for (int k = 0; k < 7; k++) part += xu[k] * (lambda * xu[k] + A.b[(size_t)u * 7 + k]);
   }
-  for (int off = 32; off > 0; off >>= 1) part += __shfl_xor(part, off);
-  __syncthreads();
-  if ((tid & 63) == 0) scratch[tid >> 6] = part;
-  __syncthreads();
-  if (tid == 0) { double s = 0.0; for (int w = 0; w < 16; w++) s += scratch[w]; A.sc[6] = s; }
+  const double s = lld_wave::block_sum(part, scratch);
+  if (tid == 0) A.sc[6] = s;
 }
 
 

@@ -7,6 +7,7 @@
 #include "lld_common.h"
 #include "lld_device_math.h"
 #include "lld_sim3_math.h"
+#include "lld_wave.h"
 
 namespace {
 
@@ -59,12 +60,7 @@ template <int N>
 __device__ __forceinline__ void block_sum_n(double* v, double* lds /* [kSimWaves][N] */) {
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
 #pragma unroll
-  for (int i = 0; i < N; i++) {
-    double x = v[i];
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) x += __shfl_xor(x, off);
-    v[i] = x;
-  }
+  for (int i = 0; i < N; i++) v[i] = lld_wave::sum(v[i]);
   __syncthreads();
   if (lane == 0) {
 #pragma unroll
