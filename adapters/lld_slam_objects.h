@@ -73,6 +73,12 @@ class MatU8 {
   std::vector<unsigned int> d_;                                    // 4-byte aligned like cv::Mat's rows of 32
 };
 
+// ---- g2o::Sim3 stand-in (Thirdparty/g2o/g2o/types/sim3.h): rotation quaternion (x, y, z, w), translation, scale.  The adapters only carry it
+struct Sim3 {
+  double q[4], t[3], s;
+  Sim3() : q{0, 0, 0, 1}, t{0, 0, 0}, s(1.0) {}
+};
+
 struct Point2f { float x, y; };
 struct Point3f { float x, y, z; Point3f() : x(0.f), y(0.f), z(0.f) {} Point3f(float a, float b, float c) : x(a), y(b), z(c) {} };   // cv::Point3f
 struct KeyPoint { Point2f pt; int octave; float angle; KeyPoint() : pt{0.f, 0.f}, octave(0), angle(0.f) {} };   // cv::KeyPoint: pt, octave, angle
@@ -180,6 +186,12 @@ class KeyFrame {
   }
   inline void SetBadFlag();                                         // KeyFrame.cc:476-: defined below MapPoint
 
+  // what LoopClosing::RunGlobalBundleAdjustment reads and writes on top (include/KeyFrame.h:145-148, :90-92)
+  Mat mTcwGBA, mTcwBefGBA;
+  unsigned long mnBAGlobalForKF = 0;
+  std::set<KeyFrame*> GetChilds() const { return mspChildrens; }
+  KeyFrame* GetParent() const { return mpParent; }
+
   // (test access)
   Mat Tcw;
   bool mbBad = false;
@@ -243,6 +255,12 @@ class MapPoint {
   bool mbTrackInView = false;
   int mnTrackScaleLevel = 0;
   unsigned long mnLastFrameSeen = 0;
+
+  // variables used by loop closing (MapPoint.h:103-107)
+  unsigned long mnCorrectedByKF = 0, mnCorrectedReference = 0;
+  Mat mPosGBA;
+  unsigned long mnBAGlobalForKF = 0;
+  KeyFrame* GetReferenceKeyFrame() const { return mpRefKF; }
 
   Mat mWorldPos;                                                   // 3x1 CV_32F
   KeyFrame* mpRefKF = nullptr;                                     // MapPoint.h: the reference keyframe UpdateNormalAndDepth reads
@@ -368,6 +386,12 @@ class Map {
   std::set<MapLine*> mspMapLines;
   void AddMapPoint(MapPoint* pMP) { mspMapPoints.insert(pMP); }    // Map.cc
   std::set<MapPoint*> mspMapPoints;
+  // what the loop-closing thread reads on top (include/Map.h)
+  void AddKeyFrame(KeyFrame* pKF) { mspKeyFrames.insert(pKF); }
+  std::set<KeyFrame*> mspKeyFrames;
+  std::vector<KeyFrame*> GetAllKeyFrames() const { return std::vector<KeyFrame*>(mspKeyFrames.begin(), mspKeyFrames.end()); }
+  std::vector<MapPoint*> GetAllMapPoints() const { return std::vector<MapPoint*>(mspMapPoints.begin(), mspMapPoints.end()); }
+  std::vector<KeyFrame*> mvpKeyFrameOrigins;
 };
 
 }  // namespace lld_slam

@@ -398,8 +398,8 @@ int lld_optimize_sim3_batch(lld_ctx* ctx, int n, const lld_sim3_problem* problem
  * (types_seven_dof_expmap.h:99-127), identity information, no robust kernel, NUMERIC Jacobians for both vertices like g2o
  * (core/base_binary_edge.hpp:131-197), Levenberg-Marquardt with setUserLambdaInit(1e-16), optimize(15).  Nothing is marginalised:
  * H is the 7N x 7N system, solved by the block-Jacobi PCG spread over the GPU (g2o: sparse Cholesky).
- * Building the edge list from the map (:1447-1585) and the write-back (:1593-1653: SE3 recovery [R t/s], MapPoint correction through
- * the reference keyframe) stay with the adapter.  LLD_ERR_INVALID for an edge whose end is out of range or whose two ends are the
+ * Building the edge list from the map (:1447-1585) stays with the adapter; the write-back (:1601-1653: SE3 recovery [R t/s],
+ * MapPoint correction through the reference keyframe) is lld_essential_graph_apply.  LLD_ERR_INVALID for an edge whose end is out of range or whose two ends are the
  * same vertex (edge_i == edge_j: the reference never builds one). */
 typedef struct {
   int32_t n_vertices;
@@ -2368,6 +2368,141 @@ typedef struct {
   float*   phase_ms;                     /* [3] upload, kernels, download; may be NULL            */
 } lld_covisibility_out;
 int lld_covisibility(lld_ctx* ctx, const lld_covisibility_in* in, lld_covisibility_out* out);
+
+/* ================================================================== the loop-closing thread moves the map (lld_map_correct.hip)
+ * Three entry points for the three host loops that run with Map::mMutexMapUpdate held: LoopClosing::CorrectLoop
+ * (src/LoopClosing.cc:440-518), the write-back of Optimizer::OptimizeEssentialGraph (src/Optimizer.cc:1601-1653) and the map update
+ * of LoopClosing::RunGlobalBundleAdjustment (src/LoopClosing.cc:678-739).  Each call makes one upload, queues its kernels on the
+ * context's stream with no host trip between them, makes one download and waits for the stream.  Every index and every parent link
+ * is range-checked on the host first: LLD_ERR_INVALID / LLD_ERR_UNSUPPORTED are returned before anything is queued and leave the
+ * outputs untouched.
+ * Conventions: keyframe tables are numbered by the caller in std::less<KeyFrame*> order; the observations of a point are a CSR in
+ * std::map iteration order (as in lld_mappoint_refresh); a Sim3 is 8 doubles (rotation x, y, z, w, translation, scale); a float pose is
+ * Tcw[12], the rows of [R|t].  Float matrix products are cv::gemm products as this header fixes them everywhere: every entry the
+ * double sum of its terms in index order, rounded to float once.
+ * SetPose rule (src/KeyFrame.cc:82-89): Rwc = Rcw^T, Ow = -Rwc*tcw (one product), Twc = [Rwc | Ow].
+ * UpdateNormalAndDepth (src/MapPoint.cc:330-371) has the numerics of lld_mappoint_refresh, bit for bit; level_scale is one table for
+ * all keyframes (the DEVIATION stated there).  It runs in kernels sized for whole maps: eight points with at most 8 observations share
+ * a wavefront, longer lists take a wavefront each.
+ *
+ * (a) lld_loop_correct, CorrectLoop :440-518.
+ *   conn[n_conn]: the keyframe slots of mvpCurrentConnectedKFs plus mpCurrentKF IN THE ITERATION ORDER OF CorrectedSim3 (a
+ *   std::map<KeyFrame*, ...>, so ascending slot when the table is in pointer order); cur = the position of mpCurrentKF in it.  Per
+ *   connected keyframe r, kf_point[kf_start[r] .. kf_start[r+1]) = the point slots of the non-NULL GetMapPointMatches() in keypoint
+ *   order (a slot may repeat).  The keyframe table holds every keyframe that observes a listed point.
+ *   :442      Twc = mpCurrentKF->GetPoseInverse() by the SetPose rule.
+ *   :457-463  Tic = Tiw*Twc, a full 4x4 float product (the translation column is the four-term sum too); g2oSic = Sim3(Ric, tic, 1.0);
+ *             CorrectedSiw = g2oSic*mg2oScw (Eigen's Quaterniond(Matrix3d) and Sim3::operator*, no normalisation: sim3.h:64-67, :266-272);
+ *             for cur it is mg2oScw itself.  :466-470 NonCorrectedSiw = Sim3(Riw, tiw, 1.0).
+ *   :474-503  Owner of a point = the first rank in conn whose list holds it, points that are bad or `already` (mnCorrectedByKF ==
+ *             mpCurrentKF->mnId on entry) skipped.  Corrected position = CorrectedSwi.map(Siw.map(P)) of the owner: P widened to double,
+ *             Sim3::inverse and Sim3::map, rounded to float once (Converter::toCvMat).  corrected_by = the owner's rank, or -1.
+ *   :506-514  Corrected pose = toCvSE3(R(q), t*(1./s)) (a reciprocal, then a product), Ow by the SetPose rule.
+ *   :502      UpdateNormalAndDepth of a point owned by rank k reads, for an observing keyframe and for the reference keyframe alike, the
+ *             CORRECTED centre when that keyframe is in conn at a rank strictly below k, and the centre on entry otherwise (rank k itself:
+ *             its SetPose follows its points; keyframes outside conn never move).  This is what the interleaved loop computes.  A point
+ *             with no observations is moved, and its normal and depth are left alone (bit 1 of updated clear).
+ *   scw_f32 = Converter::toCvMat(Sim3) = [sR | t] in float (Converter.cc:55-61), what SearchAndFuse takes.  MapLines are not touched:
+ *   the reference does not touch them.  UpdateConnections (:517) stays the batched lld_covisibility call after this one.
+ * (b) lld_essential_graph_apply, Optimizer.cc:1601-1653.  sim3_before = vScw and sim3_after = the optimised CorrectedSiw: the sim3 array
+ *   lld_optimize_essential_graph takes and the one it returns.  corr_kf[p] = the slot the caller chose at :1631-1639
+ *   (mnCorrectedReference or pRefKF).  :1611-1619 every keyframe gets Tiw = toCvSE3(R, t*(1./s)) and its Ow; :1645-1650 every point that
+ *   is not bad gets after[r]^-1.map(before[r].map(P)), rounded once; :1652 UpdateNormalAndDepth with ALL centres new.
+ * (c) lld_global_ba_apply, LoopClosing.cc:678-739, all float cv::Mat arithmetic.  parent[k] = the slot of GetParent(), -1 for none.
+ *   :679-702  the walk from origins[] over the children: a child that is not kf_in_gba (mnBAGlobalForKF != nLoopKF on entry) gets
+ *             mTcwGBA = (Tchild*Twc_parent)*mTcwGBA_parent - two 4x4 products, Twc_parent the parent's [Rcw^T | Ow] BEFORE its update,
+ *             Tchild the child's pose before its update - and counts as visited.  Every visited keyframe reports tcw_before (its pose
+ *             on entry) and takes tcw_new = mTcwGBA with the SetPose-rule Ow.  A child reads only its parent, so the order among
+ *             siblings does not matter; chains of keyframes that are not kf_in_gba are composed top-down.
+ *   :705-739  a point that is not bad: in_gba takes pos_gba (moved 1); otherwise, when its reference keyframe was visited,
+ *             Xc = Rcw_before*P + tcw_before (the product rounded, then the float sum), P' = Rwc_new*Xc + Ow_new (moved 2); otherwise
+ *             it is untouched (moved 0).  There is no UpdateNormalAndDepth here: the reference has none.
+ *   LLD_ERR_INVALID besides the common cases: a parent out of range, its own parent or on a cycle; an origin out of range, repeated,
+ *   with a parent, or not kf_in_gba (the walk would read an mTcwGBA that was never set); a kf_in_gba keyframe the walk does not reach
+ *   (its points would read an unset mTcwBefGBA); a point that is neither bad nor in_gba with ref_kf out of range.
+ * Limits: n_kf above LLD_MAPCORR_MAX_KF, n_points above LLD_MAPCORR_MAX_POINTS, n_entries above LLD_MAPCORR_MAX_ENTRIES or a point with more than LLD_LANDMARK_MAX_OBS
+ *   observations returns LLD_ERR_UNSUPPORTED.  n_points = 0 and n_conn = 1 are valid; n_kf is at least 1.  LLD_ERR_INVALID: a NULL
+ *   required pointer; negative sizes; a CSR (kf_start, obs_start) that does not start at 0, decreases or does not end at its count;
+ *   a keyframe or point slot out of range; cur outside conn; a slot repeated in conn; n_levels outside [1, LLD_ORB_MAX_LEVELS]; ref_kf
+ *   or ref_level outside its table for a point the rule does not skip; a non-finite pose or Sim3, or a scale that is not > 0.
+ * Outputs are in / out: an entry the rule leaves alone keeps the value the caller passed in. */
+#define LLD_MAPCORR_MAX_KF 65536           /* keyframes of one call                                 */
+#define LLD_MAPCORR_MAX_POINTS (1 << 23)   /* map points of one call                                */
+#define LLD_MAPCORR_MAX_ENTRIES (1 << 24)  /* (connected keyframe, point) entries of lld_loop_correct */
+#define LLD_MAPCORR_MOVED 1u               /* updated bit 0: the position was corrected; bit 1 is LLD_LANDMARK_NORMAL_DEPTH */
+typedef struct {                          /* the point table of (a) and (b)                        */
+  int32_t n_points, n_obs, n_levels, reserved;
+  const float*    pos;                   /* [n_points][3] mWorldPos                               */
+  const uint8_t*  bad;                   /* [n_points] isBad()                                    */
+  const int32_t*  obs_start;             /* [n_points+1]                                          */
+  const int32_t*  obs_kf;                /* [n_obs] slot of the observing keyframe                */
+  const int32_t*  ref_kf;                /* [n_points] mpRefKF                                    */
+  const int32_t*  ref_level;             /* [n_points] as in lld_mappoint_refresh_in              */
+  const float*    level_scale;           /* [n_levels] mvScaleFactors                             */
+} lld_mapcorr_points;
+typedef struct {
+  int32_t n_kf, n_conn, cur, n_entries;
+  const float*    kf_tcw;                /* [n_kf][12] GetPose()                                  */
+  const int32_t*  conn;                  /* [n_conn] keyframe slots in CorrectedSim3's order      */
+  const double*   scw;                   /* [8] mg2oScw                                           */
+  const int32_t*  kf_start;              /* [n_conn+1]                                            */
+  const int32_t*  kf_point;              /* [n_entries] point slots per connected keyframe        */
+  const uint8_t*  already;               /* [n_points] mnCorrectedByKF == mpCurrentKF->mnId       */
+  lld_mapcorr_points  points;
+} lld_loop_correct_in;
+typedef struct {
+  double*  corrected_sim3;               /* [n_conn][8] CorrectedSim3                             */
+  double*  non_corrected_sim3;           /* [n_conn][8] NonCorrectedSim3                          */
+  float*   tiw_corrected;                /* [n_conn][12] the pose SetPose takes                   */
+  float*   ow_corrected;                 /* [n_conn][3] its camera centre                         */
+  float*   scw_f32;                      /* [n_conn][12] toCvMat(CorrectedSiw) = [sR | t]         */
+  float*   pos;                          /* [n_points][3]                                         */
+  int32_t* corrected_by;                 /* [n_points] the owner's rank in conn, or -1            */
+  float*   normal;                       /* [n_points][3]                                         */
+  float*   min_distance;                 /* [n_points]                                            */
+  float*   max_distance;                 /* [n_points]                                            */
+  uint8_t* updated;                      /* [n_points] bit 0 moved, bit 1 normal / depth          */
+} lld_loop_correct_out;
+int lld_loop_correct(lld_ctx* ctx, const lld_loop_correct_in* in, lld_loop_correct_out* out);
+typedef struct {
+  int32_t n_kf, reserved;
+  const double*   sim3_before;           /* [n_kf][8] vScw                                        */
+  const double*   sim3_after;            /* [n_kf][8] the optimised CorrectedSiw                  */
+  const int32_t*  corr_kf;               /* [n_points] mnCorrectedReference or pRefKF (:1631-1639) */
+  lld_mapcorr_points  points;
+} lld_essential_graph_apply_in;
+typedef struct {
+  float*   tiw;                          /* [n_kf][12]                                            */
+  float*   ow;                           /* [n_kf][3]                                             */
+  float*   pos;                          /* [n_points][3]                                         */
+  float*   normal;                       /* [n_points][3]                                         */
+  float*   min_distance;                 /* [n_points]                                            */
+  float*   max_distance;                 /* [n_points]                                            */
+  uint8_t* updated;                      /* [n_points] bit 0 moved, bit 1 normal / depth          */
+} lld_essential_graph_apply_out;
+int lld_essential_graph_apply(lld_ctx* ctx, const lld_essential_graph_apply_in* in, lld_essential_graph_apply_out* out);
+typedef struct {
+  int32_t n_kf, n_origins, n_points, reserved;
+  const float*    kf_tcw;                /* [n_kf][12] GetPose()                                  */
+  const uint8_t*  kf_in_gba;             /* [n_kf] mnBAGlobalForKF == nLoopKF on entry            */
+  const float*    kf_tcw_gba;            /* [n_kf][12] mTcwGBA, read where kf_in_gba is set       */
+  const int32_t*  parent;                /* [n_kf] slot of GetParent(), -1 for none               */
+  const int32_t*  origins;               /* [n_origins] Map::mvpKeyFrameOrigins                   */
+  const float*    pos;                   /* [n_points][3]                                         */
+  const uint8_t*  bad;                   /* [n_points]                                            */
+  const uint8_t*  in_gba;                /* [n_points] mnBAGlobalForKF == nLoopKF                 */
+  const float*    pos_gba;               /* [n_points][3] mPosGBA, read where in_gba is set       */
+  const int32_t*  ref_kf;                /* [n_points]                                            */
+} lld_global_ba_apply_in;
+typedef struct {
+  uint8_t* visited;                      /* [n_kf] always written                                 */
+  float*   tcw_new;                      /* [n_kf][12] mTcwGBA of a visited keyframe              */
+  float*   tcw_before;                   /* [n_kf][12] mTcwBefGBA of a visited keyframe           */
+  float*   ow_new;                       /* [n_kf][3]                                             */
+  float*   pos;                          /* [n_points][3]                                         */
+  uint8_t* moved;                        /* [n_points] 0 untouched, 1 pos_gba, 2 through ref_kf   */
+} lld_global_ba_apply_out;
+int lld_global_ba_apply(lld_ctx* ctx, const lld_global_ba_apply_in* in, lld_global_ba_apply_out* out);
 
 #if defined(__GNUC__)
 #pragma GCC visibility pop

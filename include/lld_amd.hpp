@@ -1238,5 +1238,106 @@ inline void Covisibility(const Context& ctx, const CovisibilityBatch& b, uint32_
   }
 }
 
+// ---- the loop-closing thread moves the map: LoopClosing::CorrectLoop :440-518, the write-back of Optimizer::OptimizeEssentialGraph
+// (Optimizer.cc:1601-1653) and the map update after a global bundle adjustment (LoopClosing.cc:678-739) over flat arrays.  Keyframe
+// tables in pointer order, observations in the CSR layout of MapPointBatch, a Sim3 as 8 doubles, a pose as the 12 floats of [R|t].
+// Point outputs are in / out: an entry the rule leaves alone keeps its value; vectors that are too short are grown with zeros.
+struct MapCorrPoints {
+  std::vector<float> pos;                // [3*n]
+  std::vector<uint8_t> bad;              // [n]
+  std::vector<int32_t> obs_start, obs_kf, ref_kf, ref_level;   // [n+1], [n_obs], [n], [n]
+  std::vector<float> level_scale;        // [n_levels]
+  lld_mapcorr_points view() const {
+    lld_mapcorr_points p = lld_mapcorr_points();
+    p.n_points = (int32_t)bad.size(); p.n_obs = (int32_t)obs_kf.size(); p.n_levels = (int32_t)level_scale.size();
+    p.pos = pos.data(); p.bad = bad.data(); p.obs_start = obs_start.data(); p.obs_kf = obs_kf.data(); p.ref_kf = ref_kf.data();
+    p.ref_level = ref_level.data(); p.level_scale = level_scale.data();
+    return p;
+  }
+};
+struct LoopCorrectBatch {
+  int32_t cur;                           // the position of mpCurrentKF in conn
+  double scw[8];                         // mg2oScw
+  std::vector<float> kf_tcw;             // [12*n_kf]
+  std::vector<int32_t> conn;             // [n_conn] keyframe slots in CorrectedSim3's iteration order
+  std::vector<int32_t> kf_start, kf_point;   // [n_conn+1], [n_entries]
+  std::vector<uint8_t> already;          // [n] mnCorrectedByKF == mpCurrentKF->mnId
+  MapCorrPoints points;
+};
+struct LoopCorrectOutput {
+  std::vector<double> corrected_sim3, non_corrected_sim3;        // [8*n_conn]
+  std::vector<float> tiw_corrected, ow_corrected, scw_f32;       // [12*n_conn], [3*n_conn], [12*n_conn]
+  std::vector<float> pos, normal, min_distance, max_distance;    // [3*n], [3*n], [n], [n]
+  std::vector<int32_t> corrected_by;                             // [n] rank in conn, or -1
+  std::vector<uint8_t> updated;                                  // bit 0 (LLD_MAPCORR_MOVED), bit 1 (LLD_LANDMARK_NORMAL_DEPTH)
+};
+inline void CorrectLoop(const Context& ctx, const LoopCorrectBatch& b, LoopCorrectOutput& io) {
+  const size_t n = b.points.bad.size(), nc = b.conn.size();
+  lld_loop_correct_in in = lld_loop_correct_in();
+  in.n_kf = (int32_t)(b.kf_tcw.size() / 12); in.n_conn = (int32_t)nc; in.cur = b.cur; in.n_entries = (int32_t)b.kf_point.size();
+  in.kf_tcw = b.kf_tcw.data(); in.conn = b.conn.data(); in.scw = b.scw; in.kf_start = b.kf_start.data(); in.kf_point = b.kf_point.data();
+  in.already = b.already.data(); in.points = b.points.view();
+  io.corrected_sim3.resize(8 * nc); io.non_corrected_sim3.resize(8 * nc); io.tiw_corrected.resize(12 * nc); io.ow_corrected.resize(3 * nc);
+  io.scw_f32.resize(12 * nc); io.pos.resize(3 * n); io.normal.resize(3 * n); io.min_distance.resize(n); io.max_distance.resize(n);
+  io.corrected_by.resize(n); io.updated.resize(n);
+  lld_loop_correct_out out;
+  out.corrected_sim3 = io.corrected_sim3.data(); out.non_corrected_sim3 = io.non_corrected_sim3.data(); out.tiw_corrected = io.tiw_corrected.data();
+  out.ow_corrected = io.ow_corrected.data(); out.scw_f32 = io.scw_f32.data(); out.pos = io.pos.data(); out.corrected_by = io.corrected_by.data();
+  out.normal = io.normal.data(); out.min_distance = io.min_distance.data(); out.max_distance = io.max_distance.data(); out.updated = io.updated.data();
+  check(lld_loop_correct(ctx.get(), &in, &out), "lld_loop_correct");
+}
+
+struct EssentialGraphApplyBatch {
+  std::vector<double> sim3_before, sim3_after;   // [8*n_kf]: the sim3 array OptimizeEssentialGraph takes, and the one it returns
+  std::vector<int32_t> corr_kf;                  // [n] mnCorrectedReference or pRefKF (Optimizer.cc:1631-1639)
+  MapCorrPoints points;
+};
+struct EssentialGraphApplyOutput {
+  std::vector<float> tiw, ow;                                    // [12*n_kf], [3*n_kf]
+  std::vector<float> pos, normal, min_distance, max_distance;
+  std::vector<uint8_t> updated;
+};
+inline void ApplyEssentialGraph(const Context& ctx, const EssentialGraphApplyBatch& b, EssentialGraphApplyOutput& io) {
+  const size_t n = b.points.bad.size(), nk = b.sim3_before.size() / 8;
+  if (b.sim3_after.size() != b.sim3_before.size()) check(LLD_ERR_INVALID, "lld_essential_graph_apply");
+  lld_essential_graph_apply_in in = lld_essential_graph_apply_in();
+  in.n_kf = (int32_t)nk; in.sim3_before = b.sim3_before.data(); in.sim3_after = b.sim3_after.data(); in.corr_kf = b.corr_kf.data();
+  in.points = b.points.view();
+  io.tiw.resize(12 * nk); io.ow.resize(3 * nk); io.pos.resize(3 * n); io.normal.resize(3 * n); io.min_distance.resize(n);
+  io.max_distance.resize(n); io.updated.resize(n);
+  lld_essential_graph_apply_out out;
+  out.tiw = io.tiw.data(); out.ow = io.ow.data(); out.pos = io.pos.data(); out.normal = io.normal.data(); out.min_distance = io.min_distance.data();
+  out.max_distance = io.max_distance.data(); out.updated = io.updated.data();
+  check(lld_essential_graph_apply(ctx.get(), &in, &out), "lld_essential_graph_apply");
+}
+
+struct GlobalBAApplyBatch {
+  std::vector<float> kf_tcw, kf_tcw_gba;         // [12*n_kf]
+  std::vector<uint8_t> kf_in_gba;                // [n_kf]
+  std::vector<int32_t> parent, origins;          // [n_kf] (-1: none), [n_origins]
+  std::vector<float> pos, pos_gba;               // [3*n]
+  std::vector<uint8_t> bad, in_gba;              // [n]
+  std::vector<int32_t> ref_kf;                   // [n]
+};
+struct GlobalBAApplyOutput {
+  std::vector<uint8_t> visited;                  // [n_kf]
+  std::vector<float> tcw_new, tcw_before, ow_new;   // of the visited keyframes
+  std::vector<float> pos;                        // [3*n]
+  std::vector<uint8_t> moved;                    // 0 untouched, 1 from pos_gba, 2 through the reference keyframe
+};
+inline void ApplyGlobalBA(const Context& ctx, const GlobalBAApplyBatch& b, GlobalBAApplyOutput& io) {
+  const size_t n = b.bad.size(), nk = b.parent.size();
+  lld_global_ba_apply_in in = lld_global_ba_apply_in();
+  in.n_kf = (int32_t)nk; in.n_origins = (int32_t)b.origins.size(); in.n_points = (int32_t)n;
+  in.kf_tcw = b.kf_tcw.data(); in.kf_in_gba = b.kf_in_gba.data(); in.kf_tcw_gba = b.kf_tcw_gba.data(); in.parent = b.parent.data();
+  in.origins = b.origins.data(); in.pos = b.pos.data(); in.bad = b.bad.data(); in.in_gba = b.in_gba.data(); in.pos_gba = b.pos_gba.data();
+  in.ref_kf = b.ref_kf.data();
+  io.visited.resize(nk); io.tcw_new.resize(12 * nk); io.tcw_before.resize(12 * nk); io.ow_new.resize(3 * nk); io.pos.resize(3 * n); io.moved.resize(n);
+  lld_global_ba_apply_out out;
+  out.visited = io.visited.data(); out.tcw_new = io.tcw_new.data(); out.tcw_before = io.tcw_before.data(); out.ow_new = io.ow_new.data();
+  out.pos = io.pos.data(); out.moved = io.moved.data();
+  check(lld_global_ba_apply(ctx.get(), &in, &out), "lld_global_ba_apply");
+}
+
 }  // namespace lld_amd
 #endif

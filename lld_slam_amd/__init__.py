@@ -12,10 +12,12 @@ from .initializer import Initializer, InitializerError, problem_from_scene  # no
 from .landmarks import LandmarkError, distinctive_line_descriptors, refresh_map_points  # noqa: F401
 from .new_points import NewPointsError, triangulate_new_points  # noqa: F401
 from .covisibility import CovisibilityError, keyframe_culling, update_connections  # noqa: F401
+from .loop_correction import LoopCorrectionError, apply_essential_graph, apply_global_ba, correct_loop  # noqa: F401
 from .host import (BABatch, Context, Optimizer, ORBmatcher, PoseBatch, PoseFrame, Tracking, TwoFrameLineMatcher,  # noqa: F401
                    Window)
 
 __all__ = ["abi", "Context", "Optimizer", "ORBmatcher", "TwoFrameLineMatcher", "Tracking", "BABatch", "PoseBatch", "Window",
            "PoseFrame", "PnPsolver", "PnPsolverBatch", "Sim3Solver", "Sim3SolverBatch", "Initializer", "InitializerError",
            "problem_from_scene", "refresh_map_points", "distinctive_line_descriptors", "LandmarkError",
-           "triangulate_new_points", "NewPointsError", "update_connections", "keyframe_culling", "CovisibilityError"]
+           "triangulate_new_points", "NewPointsError", "update_connections", "keyframe_culling", "CovisibilityError",
+           "correct_loop", "apply_essential_graph", "apply_global_ba", "LoopCorrectionError"]

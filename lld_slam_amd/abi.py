@@ -277,6 +277,45 @@ class CovisibilityOut(C.Structure):
                 ("phase_ms", c_float_p)]
 
 
+class MapCorrPoints(C.Structure):
+    _fields_ = [("n_points", C.c_int32), ("n_obs", C.c_int32), ("n_levels", C.c_int32), ("reserved", C.c_int32), ("pos", c_float_p),
+                ("bad", c_uint8_p), ("obs_start", c_int32_p), ("obs_kf", c_int32_p), ("ref_kf", c_int32_p), ("ref_level", c_int32_p),
+                ("level_scale", c_float_p)]
+
+
+class LoopCorrectIn(C.Structure):
+    _fields_ = [("n_kf", C.c_int32), ("n_conn", C.c_int32), ("cur", C.c_int32), ("n_entries", C.c_int32), ("kf_tcw", c_float_p),
+                ("conn", c_int32_p), ("scw", c_double_p), ("kf_start", c_int32_p), ("kf_point", c_int32_p), ("already", c_uint8_p),
+                ("points", MapCorrPoints)]
+
+
+class LoopCorrectOut(C.Structure):
+    _fields_ = [("corrected_sim3", c_double_p), ("non_corrected_sim3", c_double_p), ("tiw_corrected", c_float_p),
+                ("ow_corrected", c_float_p), ("scw_f32", c_float_p), ("pos", c_float_p), ("corrected_by", c_int32_p), ("normal", c_float_p),
+                ("min_distance", c_float_p), ("max_distance", c_float_p), ("updated", c_uint8_p)]
+
+
+class EssentialGraphApplyIn(C.Structure):
+    _fields_ = [("n_kf", C.c_int32), ("reserved", C.c_int32), ("sim3_before", c_double_p), ("sim3_after", c_double_p),
+                ("corr_kf", c_int32_p), ("points", MapCorrPoints)]
+
+
+class EssentialGraphApplyOut(C.Structure):
+    _fields_ = [("tiw", c_float_p), ("ow", c_float_p), ("pos", c_float_p), ("normal", c_float_p), ("min_distance", c_float_p),
+                ("max_distance", c_float_p), ("updated", c_uint8_p)]
+
+
+class GlobalBAApplyIn(C.Structure):
+    _fields_ = [("n_kf", C.c_int32), ("n_origins", C.c_int32), ("n_points", C.c_int32), ("reserved", C.c_int32), ("kf_tcw", c_float_p),
+                ("kf_in_gba", c_uint8_p), ("kf_tcw_gba", c_float_p), ("parent", c_int32_p), ("origins", c_int32_p), ("pos", c_float_p),
+                ("bad", c_uint8_p), ("in_gba", c_uint8_p), ("pos_gba", c_float_p), ("ref_kf", c_int32_p)]
+
+
+class GlobalBAApplyOut(C.Structure):
+    _fields_ = [("visited", c_uint8_p), ("tcw_new", c_float_p), ("tcw_before", c_float_p), ("ow_new", c_float_p), ("pos", c_float_p),
+                ("moved", c_uint8_p)]
+
+
 class PoseGraph(C.Structure):
     _fields_ = [("n_vertices", C.c_int32), ("n_edges", C.c_int32), ("sim3", c_double_p), ("fixed", c_uint8_p), ("edge_i", c_int32_p),
                 ("edge_j", c_int32_p), ("edge_sji", c_double_p)]
@@ -418,6 +457,7 @@ PRODUCT_SYMBOLS = [
     "lld_mappoint_refresh", "lld_mapline_distinctive",
     "lld_new_points_triangulate",
     "lld_covisibility_params_default", "lld_covisibility",
+    "lld_loop_correct", "lld_essential_graph_apply", "lld_global_ba_apply",
     "lld_frame_build_stereo_keypoints", "lld_frame_build_stereo", "lld_frame_stereo_download",
     "lld_frame_build_mono_keypoints", "lld_frame_build_mono", "lld_frame_keypoints_download", "lld_frame_image_bounds",
 ]
@@ -562,6 +602,11 @@ class Lib:
             f("covisibility_params_default").restype = None
             f("covisibility").argtypes = [vp, C.POINTER(CovisibilityIn), C.POINTER(CovisibilityOut)]
             f("covisibility").restype = C.c_int
+            f("loop_correct").argtypes = [vp, C.POINTER(LoopCorrectIn), C.POINTER(LoopCorrectOut)]; f("loop_correct").restype = C.c_int
+            f("essential_graph_apply").argtypes = [vp, C.POINTER(EssentialGraphApplyIn), C.POINTER(EssentialGraphApplyOut)]
+            f("essential_graph_apply").restype = C.c_int
+            f("global_ba_apply").argtypes = [vp, C.POINTER(GlobalBAApplyIn), C.POINTER(GlobalBAApplyOut)]
+            f("global_ba_apply").restype = C.c_int
             # (frame, vocabulary, levelsup, lld_bow_result* or NULL); (frame, lld_track_params*, lld_frame_view*, pose_qt, lld_ref_keyframe*):
             # the structs of vocabulary.py / tracking.py / orb_search.py pass by reference
             f("frame_compute_bow").argtypes = [vp, vp, C.c_int, vp]; f("frame_compute_bow").restype = C.c_int

@@ -14,7 +14,8 @@
 //   lm_point_block  one workgroup of 256 per MapPoint with 65 .. LLD_LANDMARK_MAX_OBS kept observations: descriptors in LDS, rows
 //                   strided over the lanes, the same bisection with the distances recomputed from LDS (broadcast reads).
 //   lm_normal_wave  one wavefront per MapPoint: 64 terms (pos - Ow_i)/|pos - Ow_i| formed at once, then every lane adds them in
-//                   observation order through lane broadcasts, so the float sum has the reference's order.
+//                   observation order through lane broadcasts, so the float sum has the reference's order.  The term, the centre it
+//                   reads and the final write are lld_normal_depth.h's, shared with the whole-map kernels of lld_map_correct.hip.
 //   lm_line_wave    one wavefront per MapLine: rows in LDS (odd stride), float distances in LDS, sorted[idx] by rank count, the
 //                   truncation to int, a wavefront min on (median, i).
 // Every landmark is handled by one workgroup that reads nothing another workgroup writes: the result cannot depend on the batch.
@@ -24,6 +25,7 @@
 #include <vector>
 
 #include "lld_common.h"
+#include "lld_normal_depth.h"
 #include "lld_wave.h"
 
 namespace {
@@ -155,14 +157,6 @@ __global__ __launch_bounds__(kBlock) void lm_point_block(PointArgs A) {
   if (tid == 0) { A.best_obs[p] = w; A.best_median[p] = key >> 16; A.upd[p] = 1; }
 }
 
-// cv::norm of a 3-vector of floats: the squares summed in double in index order, the square root in double
-__device__ __forceinline__ double norm3(float x, float y, float z) {
-  double s = (double)x * (double)x;
-  s += (double)y * (double)y;
-  s += (double)z * (double)z;
-  return __dsqrt_rn(s);
-}
-
 // grid: n_points, block 64
 __global__ __launch_bounds__(kWave) void lm_normal_wave(NormalArgs A) {
   const int lane = threadIdx.x;
@@ -173,29 +167,20 @@ __global__ __launch_bounds__(kWave) void lm_normal_wave(NormalArgs A) {
     return;
   }
   const float px = A.pos[3 * (size_t)p], py = A.pos[3 * (size_t)p + 1], pz = A.pos[3 * (size_t)p + 2];
+  const lld_nd::Centres C{A.kf_ow, A.kf_ow, nullptr};
   float nx = 0.f, ny = 0.f, nz = 0.f;
   for (int c = s; c < e; c += kWave) {
     const int o = c + lane;
     float tx = 0.f, ty = 0.f, tz = 0.f;
-    if (o < e) {
-      const float* ow = A.kf_ow + 3 * (size_t)A.obs_kf[o];
-      const float dx = px - ow[0], dy = py - ow[1], dz = pz - ow[2];            // normali = mWorldPos - Owi (:354)
-      const float inv = (float)(1.0 / norm3(dx, dy, dz));                       // normali/cv::norm(normali): Mat / double (:355)
-      tx = dx * inv; ty = dy * inv; tz = dz * inv;
-    }
+    if (o < e) lld_nd::term(px, py, pz, lld_nd::centre(C, A.obs_kf[o], 0), tx, ty, tz);
     const int cnt = e - c < kWave ? e - c : kWave;
     for (int l = 0; l < cnt; ++l) {          // normal = normal + ... in observation order, the same sum in every lane
       nx = nx + bcastf(tx, l); ny = ny + bcastf(ty, l); nz = nz + bcastf(tz, l);
     }
   }
   if (lane == 0) {
-    const float invn = (float)(1.0 / (double)(e - s));                          // normal/n (:369)
-    A.normal[3 * (size_t)p] = nx * invn; A.normal[3 * (size_t)p + 1] = ny * invn; A.normal[3 * (size_t)p + 2] = nz * invn;
-    const float* owr = A.kf_ow + 3 * (size_t)A.ref_kf[p];
-    const float dist = (float)norm3(px - owr[0], py - owr[1], pz - owr[2]);    // PC = Pos - pRefKF->GetCameraCenter() (:359-360)
-    const float mx = dist * A.level_scale[A.ref_level[p]];                      // (:367)
-    A.max_distance[p] = mx;
-    A.min_distance[p] = __fdiv_rn(mx, A.level_scale[A.n_levels - 1]);           // (:368)
+    lld_nd::finish(lld_nd::Out{A.normal, A.min_distance, A.max_distance}, p, px, py, pz, nx, ny, nz, e - s,
+                   lld_nd::centre(C, A.ref_kf[p], 0), A.level_scale, A.ref_level[p], A.n_levels);
     A.upd[p] = 2;
   }
 }

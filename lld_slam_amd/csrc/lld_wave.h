@@ -67,6 +67,12 @@ __device__ __forceinline__ T max(T x) {
   return x;
 }
 
+// x of lane l (0 <= l < W) of the caller's own aligned group of W lanes; l may differ from lane to lane.  The source lane must be active.
+// For in-order sums over a sub-group: `for l: acc = acc + group_bcast<W>(x, l)` is the same sequence of additions in every lane of the group.
+// (A move, no arithmetic: held by the packing test of tests/test_gpu_map_correct.py through mc_normal<8>.)
+template <int W, class T>
+__device__ __forceinline__ T group_bcast(T x, int l) { return __shfl(x, l, W); }
+
 // Sum of x over the workgroup (double or int); every lane returns it.  All blockDim.x lanes (a multiple of 64) call it; lds holds
 // blockDim.x / 64 values.  Barriers: one before the wavefront totals are written (lds may still be read from an earlier call) and one after,
 // none at the end.  Additions: sum<64>() inside each wavefront, then 0 + total[0] + total[1] + ... in ascending wavefront order.
