@@ -1,12 +1,13 @@
 // C++ caller of lld_amd::KeyFrameDatabase (include/lld_amd.hpp): runs a binary script of database operations, the calls
 // LoopClosing, KeyFrame::SetBadFlag and Tracking::Relocalization make.
-//   kfdb_harness <vocabulary.txt> <script.bin> <out.bin>
+//   kfdb_harness <vocabulary.txt> <script.bin> <out.bin> [max_keyframes [max_words]]      (default 1024 and 2^20)
 //   script.bin: a sequence of int32 op codes, each followed by its arguments; a BowVector is int32 n, {int32 word, f64 value} x n
 //     1 add     u64 id, BowVector            2 erase   u64 id            3 clear
 //     4 covis   u64 id, int32 m, u64 x m     5 reloc   u64 query id, BowVector
 //     6 loop    u64 query id, BowVector, int32 nc, u64 x nc (connected), f32 minScore          0 end
 //   out.bin: per query: int32 n, u64 ids x n, f32 accScore x n, int32 n_sharing, max_common_words, min_common_words, n_scored
 #include <cstdio>
+#include <cstdlib>
 #include <set>
 #include <vector>
 
@@ -41,7 +42,9 @@ void put_result(FILE* out, const lld_amd::KeyFrameDatabase& db, const std::vecto
 }  // namespace
 
 int main(int argc, char** argv) {
-  if (argc != 4) { std::fprintf(stderr, "usage: %s vocabulary.txt script.bin out.bin\n", argv[0]); return 2; }
+  if (argc < 4 || argc > 6) { std::fprintf(stderr, "usage: %s vocabulary.txt script.bin out.bin [max_keyframes [max_words]]\n", argv[0]); return 2; }
+  const int max_keyframes = argc > 4 ? std::atoi(argv[4]) : 1024;
+  const long long max_words = argc > 5 ? std::atoll(argv[5]) : 1 << 20;
   FILE* in = std::fopen(argv[2], "rb");
   FILE* out = std::fopen(argv[3], "wb");
   if (!in || !out) return 2;
@@ -50,7 +53,7 @@ int main(int argc, char** argv) {
     lld_amd::Context ctx(0);
     lld_amd::ORBVocabulary voc(ctx);
     if (!voc.loadFromTextFile(argv[1])) { std::fprintf(stderr, "loadFromTextFile failed\n"); return 3; }
-    lld_amd::KeyFrameDatabase db(voc, 1024, 1 << 20);
+    lld_amd::KeyFrameDatabase db(voc, max_keyframes, (int64_t)max_words);
     int32_t op = 0;
     while (get(in, &op) && op != 0) {
       uint64_t id = 0;

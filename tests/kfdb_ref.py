@@ -44,6 +44,8 @@ class KeyFrameDatabase:
         self.kfs = {}                           # id -> KeyFrame: every id the database has met (slots are never released)
         self.in_db = set()
         self.live_words = 0
+        self.last_detail = dict(n_kept=0, n_retained=0, n_out=0)   # sizes of the last query's retention; not part of stats
+        self.last_listed = []                                      # ids of the last query's lKFsSharingWords, in list order
 
     # ---------------------------------------------------------------------------------------------------------- helpers
     def kf(self, kf_id):
@@ -124,6 +126,8 @@ class KeyFrameDatabase:
                         lKFsSharingWords.append(pKFi)
                 pKFi.mnLoopWords += 1
         stats = dict(n_sharing=len(lKFsSharingWords), max_common_words=0, min_common_words=0, n_scored=0)
+        self.last_detail = dict(n_kept=0, n_retained=0, n_out=0)
+        self.last_listed = [k.mnId for k in lKFsSharingWords]
         if not lKFsSharingWords:
             return [], [], stats
         maxCommonWords = 0
@@ -172,6 +176,8 @@ class KeyFrameDatabase:
                     lKFsSharingWords.append(pKFi)
                 pKFi.mnRelocWords += 1
         stats = dict(n_sharing=len(lKFsSharingWords), max_common_words=0, min_common_words=0, n_scored=0)
+        self.last_detail = dict(n_kept=0, n_retained=0, n_out=0)
+        self.last_listed = [k.mnId for k in lKFsSharingWords]
         if not lKFsSharingWords:
             return [], [], stats
         maxCommonWords = 0
@@ -208,16 +214,19 @@ class KeyFrameDatabase:
                 bestAccScore = accScore
         return self._retain(lAccScoreAndMatch, bestAccScore, stats)
 
-    @staticmethod
-    def _retain(lAccScoreAndMatch, bestAccScore, stats):
+    def _retain(self, lAccScoreAndMatch, bestAccScore, stats):
         minScoreToRetain = F32(F32(0.75) * bestAccScore)
         spAlreadyAddedKF = set()
         ids, accs = [], []
+        n_retained = 0
         for acc, pKFi in lAccScoreAndMatch:
+            if acc > minScoreToRetain:
+                n_retained += 1
             if acc > minScoreToRetain and pKFi not in spAlreadyAddedKF:
                 ids.append(pKFi.mnId)
                 accs.append(F32(acc))
                 spAlreadyAddedKF.add(pKFi)
+        self.last_detail = dict(n_kept=len(lAccScoreAndMatch), n_retained=n_retained, n_out=len(ids))
         return ids, accs, stats
 
 

@@ -6,6 +6,7 @@ import pytest
 
 import bow_ref as B
 import kfdb_ref as K
+from kfdb_scenes import apply, check
 from lld_slam_amd import abi
 from lld_slam_amd import vocabulary as voc
 from lld_slam_amd.keyframe_database import KeyFrameDatabase
@@ -18,32 +19,6 @@ def vocab(gpu_ctx):
     V = B.make_vocab(41, k=10, L=4, p_full=1.0)             # 10^4 words
     with voc.ORBVocabulary.from_arrays(gpu_ctx, V["parent"], V["is_leaf"], V["desc"], V["weight"], V["k"], V["L"]) as v:
         yield v
-
-
-def check(got, exp, what=""):
-    ids, acc, stats = exp
-    assert list(got.kf_id) == ids, f"{what}: ids {list(got.kf_id)[:10]} vs {ids[:10]}"
-    assert np.array_equal(np.asarray(got.acc_score, np.float32).view(np.uint32), np.asarray(acc, np.float32).view(np.uint32)), what
-    assert dict(n_sharing=got.n_sharing, max_common_words=got.max_common_words, min_common_words=got.min_common_words,
-                n_scored=got.n_scored) == stats, what
-
-
-def apply(dev, ref, op):
-    """One scenario operation on both; returns (device Candidates, restatement result) for a query, else None."""
-    k = op[0]
-    if k == "add":
-        dev.add(op[1], op[2]); ref.add(op[1], op[2])
-    elif k == "erase":
-        dev.erase(op[1]); ref.erase(op[1])
-    elif k == "clear":
-        dev.clear(); ref.clear()
-    elif k == "cov":
-        dev.set_covisibles(op[1], op[2]); ref.set_covisibles(op[1], op[2])
-    elif k == "reloc":
-        return dev.detect_relocalization_candidates(op[1], op[2]), ref.detect_relocalization_candidates(op[1], op[2])
-    elif k == "loop":
-        return dev.detect_loop_candidates(op[1], op[2], op[3], op[4]), ref.detect_loop_candidates(op[1], op[2], op[3], op[4])
-    return None
 
 
 @pytest.mark.parametrize("name", sorted(K.SCENARIOS))

@@ -9,6 +9,7 @@ import pytest
 
 import bow_ref as B
 import kfdb_ref as K
+import kfdb_scenes as S
 
 pytestmark = pytest.mark.gpu
 
@@ -61,11 +62,17 @@ def test_kfdb_harness_matches_the_restatement(tmp_path):
             j = int(rng.integers(0, i + 1))
             ops.append(("reloc", 5000 + i, vecs[j]))
             ops.append(("loop", ids[j] + 100, vecs[j], [n + 100 for n in cov[ids[j]][:3]], 0.02))
+    exp = K.run_ops(K.KeyFrameDatabase(n_words), ops)
+    run_and_compare(tmp_path, ops, exp)
+    assert len(exp) > 50
+
+
+def run_and_compare(tmp_path, ops, exp, *limits):
+    """Runs the harness on the script of ops (vocabulary in tmp_path/voc.txt); every query must equal exp's (ids, accs, stats)."""
     (tmp_path / "script.bin").write_bytes(script(ops))
-    r = subprocess.run([HARNESS, str(tmp_path / "voc.txt"), str(tmp_path / "script.bin"), str(tmp_path / "out.bin")],
+    r = subprocess.run([HARNESS, str(tmp_path / "voc.txt"), str(tmp_path / "script.bin"), str(tmp_path / "out.bin"), *map(str, limits)],
                        capture_output=True, text=True, timeout=300)
     assert r.returncode == 0, r.stdout + r.stderr
-    exp = K.run_ops(K.KeyFrameDatabase(n_words), ops)
     data = (tmp_path / "out.bin").read_bytes()
     pos = 0
     for q, (eids, eacc, stats) in enumerate(exp):
@@ -76,4 +83,16 @@ def test_kfdb_harness_matches_the_restatement(tmp_path):
         assert got_ids == eids, q
         assert np.array_equal(got_acc.view(np.uint32), np.asarray(eacc, np.float32).view(np.uint32)), q
         assert s == (stats["n_sharing"], stats["max_common_words"], stats["min_common_words"], stats["n_scored"]), q
-    assert pos == len(data) and len(exp) > 50
+    assert pos == len(data)
+
+
+@pytest.mark.parametrize("name", ["groups", "all_retained[1025]"])
+def test_kfdb_harness_on_a_scene(tmp_path, name):
+    """Scenes of tests/kfdb_scenes.py through the C++ wrapper, which sizes its own result buffers: 2200 entries de-duplicated to 200,
+    and 1025 candidates, one more than a pass of the finish kernel."""
+    subprocess.run(["make", "-C", os.path.join(ROOT, "examples"), "kfdb_harness"], check=True, capture_output=True)
+    sc = S.scene(name)
+    V = B.make_vocab(41, k=10, L=4, p_full=1.0)
+    assert int(V["is_leaf"].sum()) == sc.n_words
+    B.write_text(V, tmp_path / "voc.txt")
+    run_and_compare(tmp_path, sc.ops, [(a.ids, a.acc, a.stats) for a in S.reference(name)], sc.max_keyframes, sc.max_words)
