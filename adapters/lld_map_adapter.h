@@ -1,0 +1,56 @@
+// lld_map_adapter.h — host adapter that keeps a live Map of SLAM objects mirrored in an lld_map (include/lld_amd.h, "the resident map"), so that
+// Tracking::UpdateLocalMap (src/Tracking.cc:1667-1835) and TrackLocalMap run on the device between the tracking stages
+// (FrameOnDevice::TrackLocalMap(.., MapOnDevice&, ..) in lld_tracking_adapter.h).
+//   Upload(Map*)        after Map::clear() or at start-up: every keyframe, MapPoint and MapLine of the map.
+//   UpdatePoints(..)    what LocalMapping, a BA or a loop correction changed about MapPoints: position, normal, distances, descriptor, bad flag,
+//                       observations (the whole row of each listed point travels).
+//   UpdateKeyFrames(..) a new keyframe, or one whose matches, best covisibles, children, parent or bad flag changed (all four lists travel).
+//   UpdateLines(..)     MapLines likewise.
+// Slots: the slot of a KeyFrame, MapPoint or MapLine is its mnId - the ids lld_tracking_adapter already names MapPoints and MapLines by on the
+// device, so every stage-1 routine of FrameOnDevice is followed unchanged.  order_key of a keyframe is its pointer value: the device visits
+// the voted keyframes and the children in the order std::map<KeyFrame*,int> / std::set<KeyFrame*> iterate.  An object that is referenced by a
+// row but was never sent stays "never set" on the device: a temporal MapPoint votes for nothing, a keyframe or line counts as bad.
+// The caller holds Map::mMutexMapUpdate as the reference does around the same changes.  One context, one host thread.
+#ifndef LLD_MAP_ADAPTER_H
+#define LLD_MAP_ADAPTER_H
+
+#include <vector>
+
+#include "../include/lld_amd.h"
+
+#ifndef LLD_ADAPTER_OBJECTS_HEADER
+#define LLD_ADAPTER_OBJECTS_HEADER "lld_slam_objects.h"
+#endif
+#include LLD_ADAPTER_OBJECTS_HEADER
+
+namespace lld_adapter {
+
+class MapOnDevice {
+ public:
+  MapOnDevice(lld_ctx* ctx, const lld_map_limits& limits);
+  ~MapOnDevice();
+  MapOnDevice(const MapOnDevice&) = delete;
+  MapOnDevice& operator=(const MapOnDevice&) = delete;
+
+  void Upload(lld_slam::Map* pMap);
+  void UpdatePoints(const std::vector<lld_slam::MapPoint*>& points);
+  void UpdateKeyFrames(const std::vector<lld_slam::KeyFrame*>& keyframes);
+  void UpdateLines(const std::vector<lld_slam::MapLine*>& lines);
+
+  // slot -> object (NULL: never sent)
+  lld_slam::KeyFrame* KeyFrameOf(int slot) const { return slot >= 0 && slot < (int)kf_.size() ? kf_[slot] : nullptr; }
+  lld_slam::MapPoint* PointOf(int slot) const { return slot >= 0 && slot < (int)pt_.size() ? pt_[slot] : nullptr; }
+  lld_slam::MapLine* LineOf(int slot) const { return slot >= 0 && slot < (int)ln_.size() ? ln_[slot] : nullptr; }
+  const lld_map_limits& limits() const { return limits_; }
+  lld_map* get() const { return m_; }
+
+ private:
+  lld_map* m_ = nullptr;
+  lld_map_limits limits_;
+  std::vector<lld_slam::KeyFrame*> kf_;
+  std::vector<lld_slam::MapPoint*> pt_;
+  std::vector<lld_slam::MapLine*> ln_;
+};
+
+}  // namespace lld_adapter
+#endif

@@ -95,6 +95,7 @@ class KeyFrame {
  public:
   unsigned long mnId = 0;
   unsigned long mnBALocalForKF = 0, mnBAFixedForKF = 0;            // KeyFrame.h: visit marks of LocalBundleAdjustment
+  unsigned long mnTrackReferenceForFrame = 0;                      // KeyFrame.h: the mark of Tracking::UpdateLocalKeyFrames (Tracking.cc:1773)
   float fx = 0, fy = 0, cx = 0, cy = 0, mbf = 0;
   Mat mK;                                                          // 3x3 CV_32F
   std::vector<KeyPoint> mvKeysUn;
@@ -255,6 +256,7 @@ class MapPoint {
   bool mbTrackInView = false;
   int mnTrackScaleLevel = 0;
   unsigned long mnLastFrameSeen = 0;
+  unsigned long mnTrackReferenceForFrame = 0;                      // the mark of Tracking::UpdateLocalPoints (Tracking.cc:1700)
 
   // variables used by loop closing (MapPoint.h:103-107)
   unsigned long mnCorrectedByKF = 0, mnCorrectedReference = 0;
@@ -322,6 +324,8 @@ class MapLine {
   void GetMinimalPos(Vector3d* X0, Vector3d* dir) const { *X0 = mX0; *dir = mDir; }
   void GetMainPoints3D(Vector3d* X1, Vector3d* X2) const { *X1 = mX1; *X2 = mX2; }   // the 3D end points the depth test of Tracking::AddLinesFrom maps (:1064-1072)
   Vector3d mX1, mX2;
+  long mnTrackReferenceForFrame = -1;                              // MapLine.h: the mark of Tracking::UpdateLocalPoints (Tracking.cc:1720)
+  void GetDescriptor(Mat* d) const { *d = mDescriptor.clone(); }   // MapLine.cc
   long tracked_last_id = -1;                                       // MapLine.h: the frame that last took this line (Tracking.cc:1019, :1118)
   void SetMinimalPos(const Vector3d& X0, const Vector3d& dir) { mX0 = X0; mDir = dir; n_set_pos++; }
   std::map<KeyFrame*, size_t> GetObservations() const { return mObservations; }
@@ -350,6 +354,7 @@ class Frame {                                                      // what PoseO
   std::vector<int> line_matches;
   std::vector<MapLine*> mvpMapLines;
   std::vector<bool> mvbOutlierLines;
+  KeyFrame* mpReferenceKF = nullptr;                               // Frame.h: set with Tracking::mpReferenceKF (Tracking.cc:1833)
   Mat mDescriptorsLines;                                           // one LBD descriptor (CV_32F row) per left line
   Mat mDescriptorsLinesRight;                                      // ... per right line (Frame.h; read by the Frame constructor's MatchLines, src/Frame.cc:122)
   void SetPose(const Mat& T) { mTcw = T.clone(); n_set_pose++; UpdatePoseMatrices(); }
@@ -390,6 +395,7 @@ class Map {
   void AddKeyFrame(KeyFrame* pKF) { mspKeyFrames.insert(pKF); }
   std::set<KeyFrame*> mspKeyFrames;
   std::vector<KeyFrame*> GetAllKeyFrames() const { return std::vector<KeyFrame*>(mspKeyFrames.begin(), mspKeyFrames.end()); }
+  std::vector<MapLine*> GetAllMapLines() const { return std::vector<MapLine*>(mspMapLines.begin(), mspMapLines.end()); }
   std::vector<MapPoint*> GetAllMapPoints() const { return std::vector<MapPoint*>(mspMapPoints.begin(), mspMapPoints.end()); }
   std::vector<KeyFrame*> mvpKeyFrameOrigins;
 };

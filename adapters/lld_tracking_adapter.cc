@@ -141,6 +141,32 @@ lld_frame_view view_of_matrix(const Frame& Cur, const float* T) {
   return view;
 }
 
+// Matches, PoseOptimization's flags, the statistics loop (src/Tracking.cc:1155-1187) and SetPose from a stage-2 record
+void stage2_to_frame(const TrackingMembers& tr, Frame& Cur, const Outputs& out, std::unordered_map<int32_t, MapPoint*>& point_of, std::unordered_map<int32_t, MapLine*>& line_of,
+                     int nt, int nl, int* mnMatchesInliers) {
+  int inliers = 0;
+  for (int k = 0; k < nt; k++) {
+    Cur.mvpMapPoints[k] = static_cast<MapPoint*>(NULL);
+    if (out.kp_id[k] < 0) { continue; }
+    MapPoint* pMP = point_of[out.kp_id[k]];
+    Cur.mvbOutlier[k] = out.kp_out[k] != 0;
+    if (!out.kp_out[k]) {
+      Cur.mvpMapPoints[k] = pMP;
+      pMP->IncreaseFound();
+      if (!tr.mbOnlyTracking) { if (pMP->Observations() > 0) inliers++; } else inliers++;
+    }                                                                          // else: STEREO -> mvpMapPoints[k] = NULL, the flag stays (:1170-1171)
+  }
+  for (int i = 0; i < nl; i++) {
+    if (out.ln_id[i] < 0) { Cur.mvpMapLines[i] = static_cast<MapLine*>(NULL); continue; }
+    MapLine* pML = line_of[out.ln_id[i]];
+    pML->tracked_last_id = (long)Cur.mnId;
+    Cur.mvbOutlierLines[i] = out.ln_out[i] != 0;
+    Cur.mvpMapLines[i] = out.ln_out[i] ? static_cast<MapLine*>(NULL) : pML;
+  }
+  set_pose(Cur, out.r);
+  if (mnMatchesInliers) *mnMatchesInliers = inliers;
+}
+
 }  // namespace
 
 void FrameOnDevice::create(const Frame& F) {
@@ -543,28 +569,61 @@ void FrameOnDevice::TrackLocalMap(const TrackingMembers& tr, Frame& Cur, const s
     pMP->mbTrackInView = out.in_view[i] != 0;
     if (out.in_view[i]) pMP->IncreaseVisible();
   }
-  // ---- matches, PoseOptimization's flags, the statistics loop (:1155-1187)
-  int inliers = 0;
+  stage2_to_frame(tr, Cur, out, point_of, line_of, nt_, nl_, mnMatchesInliers);
+}
+
+void FrameOnDevice::TrackLocalMap(const TrackingMembers& tr, Frame& Cur, MapOnDevice& map, LocalMapMembers& lm, int* mnMatchesInliers, TrackTrace* trace,
+                                  lld_local_map_result* rec) {
+  params_.pose.gamma = tr.gamma; params_.line_md_thr = tr.mdThr;
+  params_.th_local = tr.just_relocalised ? 5.f : 1.f;
+  const lld_map_limits& L = map.limits();
+  // ---- UpdateLocalKeyFrames' side effect on the frame (:1741-1744): the device takes the same MapPoints out of its copy
+  for (int k = 0; k < nt_; k++) if (Cur.mvpMapPoints[k] && Cur.mvpMapPoints[k]->isBad()) Cur.mvpMapPoints[k] = static_cast<MapPoint*>(NULL);
+  // ---- the three calls
+  check(lld_frame_track_update_local_map(f_, map.get()), "lld_frame_track_update_local_map");
+  check(lld_frame_track_local_map_resident(f_, &params_, map.get()), "lld_frame_track_local_map_resident");
+  const int n_max = L.max_local_points;
+  Outputs out(nt_, nl_, n_max);
+  std::vector<int32_t> kfs(LLD_MAP_MAX_LOCAL_KEYFRAMES, -1), pts(n_max + 1, -1), lns(L.max_local_lines + 1, -1);
+  lld_local_map_result R; std::memset(&R, 0, sizeof R);
+  R.local_keyframes = kfs.data(); R.local_points = pts.data(); R.local_lines = lns.data(); R.mp_in_view = out.in_view.data(); R.stage2 = &out.r;
+  check(lld_frame_local_map_download(f_, map.get(), &R), "lld_frame_local_map_download");
+  if (rec) { *rec = R; rec->local_keyframes = nullptr; rec->local_points = nullptr; rec->local_lines = nullptr; rec->mp_in_view = nullptr; rec->stage1 = nullptr; rec->stage2 = nullptr; }
+  if (R.status != 0) throw std::runtime_error("FrameOnDevice::TrackLocalMap: the local map exceeds the resident map's limits (lld_local_map_result.status " + std::to_string(R.status) + ")");
+  // ---- what UpdateLocalMap leaves on Tracking and in the objects (:1684-1722, :1758-1834)
+  lm.mvpLocalKeyFrames.clear(); lm.mvpLocalMapPoints.clear(); lm.local_lines.clear(); lm.local_line_descs.clear();
+  for (int i = 0; i < R.n_local_keyframes; i++) {
+    KeyFrame* pKF = map.KeyFrameOf(kfs[i]);
+    lm.mvpLocalKeyFrames.push_back(pKF);
+    if (!R.vote_empty) pKF->mnTrackReferenceForFrame = Cur.mnId;              // (after an empty vote the routine returned before it marked anything, :1748)
+  }
+  if (R.ref_keyframe >= 0) { lm.mpReferenceKF = map.KeyFrameOf(R.ref_keyframe); Cur.mpReferenceKF = lm.mpReferenceKF; }
+  for (int i = 0; i < R.n_local_points; i++) { MapPoint* pMP = map.PointOf(pts[i]); lm.mvpLocalMapPoints.push_back(pMP); pMP->mnTrackReferenceForFrame = Cur.mnId; }
+  for (int i = 0; i < R.n_local_lines; i++) {
+    MapLine* pML = map.LineOf(lns[i]);
+    lm.local_lines.push_back(pML); pML->mnTrackReferenceForFrame = (long)Cur.mnId;
+    lld_slam::Mat ml_desc; pML->GetDescriptor(&ml_desc); lm.local_line_descs.push_back(ml_desc);
+  }
+  // ---- SearchLocalPoints' bookkeeping (:1616-1650), in the order of the TrackLocalMap above
+  std::unordered_map<int32_t, MapPoint*> point_of;
   for (int k = 0; k < nt_; k++) {
-    Cur.mvpMapPoints[k] = static_cast<MapPoint*>(NULL);
-    if (out.kp_id[k] < 0) { continue; }
-    MapPoint* pMP = point_of[out.kp_id[k]];
-    Cur.mvbOutlier[k] = out.kp_out[k] != 0;
-    if (!out.kp_out[k]) {
-      Cur.mvpMapPoints[k] = pMP;
-      pMP->IncreaseFound();
-      if (!tr.mbOnlyTracking) { if (pMP->Observations() > 0) inliers++; } else inliers++;
-    }                                                                          // else: STEREO -> mvpMapPoints[k] = NULL, the flag stays (:1170-1171)
+    MapPoint* pMP = Cur.mvpMapPoints[k];
+    if (!pMP) continue;
+    pMP->IncreaseVisible(); pMP->mnLastFrameSeen = Cur.mnId; pMP->mbTrackInView = false;
+    point_of[(int32_t)pMP->mnId] = pMP;
   }
-  for (int i = 0; i < nl_; i++) {
-    if (out.ln_id[i] < 0) { Cur.mvpMapLines[i] = static_cast<MapLine*>(NULL); continue; }
-    MapLine* pML = line_of[out.ln_id[i]];
-    pML->tracked_last_id = (long)Cur.mnId;
-    Cur.mvbOutlierLines[i] = out.ln_out[i] != 0;
-    Cur.mvpMapLines[i] = out.ln_out[i] ? static_cast<MapLine*>(NULL) : pML;
+  for (int i = 0; i < R.n_local_points; i++) {
+    MapPoint* pMP = lm.mvpLocalMapPoints[i];
+    point_of[pts[i]] = pMP;
+    if (pMP->isBad() || pMP->mnLastFrameSeen == Cur.mnId) continue;
+    pMP->mbTrackInView = out.in_view[i] != 0;
+    if (out.in_view[i]) pMP->IncreaseVisible();
   }
-  set_pose(Cur, out.r);
-  if (mnMatchesInliers) *mnMatchesInliers = inliers;
+  std::unordered_map<int32_t, MapLine*> line_of;
+  for (int i = 0; i < nl_; i++) if (Cur.mvpMapLines[i]) line_of[(int32_t)Cur.mvpMapLines[i]->mnId] = Cur.mvpMapLines[i];
+  for (int i = 0; i < R.n_local_lines; i++) line_of[lns[i]] = lm.local_lines[i];
+  out.to(trace, nt_, nl_, R.n_local_points);
+  stage2_to_frame(tr, Cur, out, point_of, line_of, nt_, nl_, mnMatchesInliers);
 }
 
 }  // namespace lld_adapter

@@ -20,6 +20,7 @@
 #define LLD_ADAPTER_OBJECTS_HEADER "lld_slam_objects.h"
 #endif
 #include LLD_ADAPTER_OBJECTS_HEADER
+#include "lld_map_adapter.h"
 
 namespace lld_adapter {
 
@@ -33,6 +34,15 @@ struct TrackingMembers {          // what the two routines read off `this` (incl
   double mdThr = 0.9;             // yaml mdThr
   bool mbOnlyTracking = false;
   bool just_relocalised = false;  // mCurrentFrame.mnId < mnLastRelocFrameId + 2: SearchLocalPoints uses th = 5 (:1656-1658)
+};
+
+// What Tracking::UpdateLocalMap writes on `this` (include/Tracking.h): the local map, and the reference keyframe
+struct LocalMapMembers {
+  std::vector<KeyFrame*> mvpLocalKeyFrames;
+  std::vector<MapPoint*> mvpLocalMapPoints;
+  std::vector<MapLine*> local_lines;
+  std::vector<lld_slam::Mat> local_line_descs;
+  KeyFrame* mpReferenceKF = nullptr;
 };
 
 // What one stage got back (optional; the tests read it, a live system passes nullptr).
@@ -105,6 +115,15 @@ class FrameOnDevice {
   // Returns mnMatchesInliers through the pointer; the two final tests of the reference (:1212-1219) stay with the caller.
   void TrackLocalMap(const TrackingMembers& tr, Frame& mCurrentFrame, const std::vector<MapPoint*>& mvpLocalMapPoints, const std::vector<MapLine*>& local_lines,
                      const std::vector<lld_slam::Mat>& local_line_descs, int* mnMatchesInliers, TrackTrace* trace = nullptr);
+  // bool Tracking::TrackLocalMap() WITH its UpdateLocalMap() (src/Tracking.cc:1126-1220, :1667-1835) on a map that is resident on the device
+  // (MapOnDevice, lld_map_adapter.h): lld_frame_track_update_local_map + lld_frame_track_local_map_resident + one download.  Nothing is gathered:
+  // the vote, the local keyframes, points and lines and stage 2's inputs are read from the map's tables.  Written back, as the host routine and
+  // the TrackLocalMap above leave them: lm.mvpLocalKeyFrames / mvpLocalMapPoints / local_lines / local_line_descs / mpReferenceKF (kept when no
+  // keyframe qualified), mCurrentFrame.mpReferenceKF, the mnTrackReferenceForFrame marks, a bad MapPoint taken out of mvpMapPoints (:1743), and
+  // everything the TrackLocalMap above writes.  `map` must hold what the objects hold now (MapOnDevice::Update*).  A local map beyond the
+  // map's limits (lld_local_map_result.status) throws, the objects untouched but for the bad MapPoints taken out; rec: the call's record, optional.
+  void TrackLocalMap(const TrackingMembers& tr, Frame& mCurrentFrame, MapOnDevice& map, LocalMapMembers& lm, int* mnMatchesInliers, TrackTrace* trace = nullptr,
+                     lld_local_map_result* rec = nullptr);
   // int Tracking::MatchLinesLastKF(bool do_skip_addnew, KeyFrame* pKF) (src/Tracking.cc:1449-1611) with mLastFrame on the device too (lld_frame_new_map_lines):
   // no gather - lines, partners, descriptors, poses, what the frames hold and what this frame tracked are read where the chain left them - then the
   // object bookkeeping of :1597-1604 from the call's result, as lld_line_adapter's MatchLinesLastKF does it from host arrays.  New MapLines take

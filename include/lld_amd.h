@@ -795,8 +795,10 @@ void lld_frame_destroy(lld_frame* frame);
  * PoseOptimization are gathered from the match tables by a kernel (what Optimizer.cc:683-804 does from mvpMapPoints / mvpMapLines), and
  * NOTHING travels to the host between the stages.  Both calls only upload their map-side inputs (one copy), queue their kernels on the
  * context's stream and return; lld_frame_track_download fetches both stages' records in one copy and is the only synchronisation.
- * (The reference's host needs the MapPoints of stage 1 for UpdateLocalMap before it can name the local map of stage 2: such a caller
- * downloads between the two calls - 10 KB - and still has no search -> PoseOptimization hand-over through the host.)
+ * (The reference's host needs the MapPoints of stage 1 for UpdateLocalMap before it can name the local map of stage 2.  A caller that keeps
+ * its map on the host downloads between the two calls - 10 KB - and gathers the local map into arrays; a caller that keeps it in an lld_map
+ * queues lld_frame_track_update_local_map and lld_frame_track_local_map_resident instead and downloads once, after stage 2: see "the resident
+ * map" at the end of this header.)
  *
  * MapPoints / MapLines are named by caller-chosen ids >= 0 (MapPoint::mnId / MapLine ids, or indices into the caller's own tables):
  *   - "pMP->mnLastFrameSeen == mCurrentFrame.mnId" (:1640), which makes SearchLocalPoints skip the points the frame already holds (:1629)
@@ -2503,6 +2505,106 @@ typedef struct {
   uint8_t* moved;                        /* [n_points] 0 untouched, 1 pos_gba, 2 through ref_kf   */
 } lld_global_ba_apply_out;
 int lld_global_ba_apply(lld_ctx* ctx, const lld_global_ba_apply_in* in, lld_global_ba_apply_out* out);
+
+/* ------------------------------------------------------------------ the resident map: Tracking::UpdateLocalMap between the tracking stages
+ * Between its stage 1 (TrackWithMotionModel / TrackReferenceKeyFrame / Relocalization) and TrackLocalMap the reference runs
+ * Tracking::UpdateLocalMap (src/Tracking.cc:1667-1835): the MapPoints stage 1 matched vote for the keyframes that observe them, the voted
+ * keyframes and some of their neighbours, children and parents become mvpLocalKeyFrames, and the MapPoints / MapLines of those keyframes
+ * become stage 2's input.  With the map on the host that is a download, a walk over std::maps, a gather of thousands of objects into arrays
+ * and an upload, every frame.  An lld_map keeps what that walk reads as flat tables in HBM, so that the routine is a handful of kernels queued
+ * between the two stages and stage 2 gathers its input from the tables by slot: one upload (stage 1's inputs) and one download per frame.
+ *
+ * Slots are caller-chosen dense integers, 0 <= slot < max_*.  On this route the ids the frame chain carries (last_point_id, kp_point_id,
+ * the ids of lld_map_lines, what lld_frame_track_finish numbers) ARE point / line slots.  A point id outside [0, max_points), or a slot
+ * lld_map_set_points never set, names a MapPoint the map does not hold - a temporal point of UpdateLastFrame (:840-883): it votes for
+ * nothing and is not bad.  A keyframe or line slot never set counts as bad.
+ * The handle belongs to one context and one host thread, like lld_frame. */
+typedef struct lld_map lld_map;
+typedef struct {
+  int32_t max_keyframes;            /* <= 262144                                                                                                       */
+  int32_t max_points, max_lines;
+  int32_t line_dim;                 /* <= 128; a frame with lines must have the same dim                                                             */
+  /* the most LIVE list entries, summed over all rows (the library reserves twice as much, so that rows can be replaced in any order) */
+  int32_t max_observations;         /* MapPoint::mObservations                                                                                        */
+  int32_t max_kf_points;            /* KeyFrame::mvpMapPoints (one entry per keypoint, -1 included)                                                  */
+  int32_t max_kf_lines;             /* KeyFrame::mvpMapLines                                                                                          */
+  int32_t max_children;             /* KeyFrame::mspChildrens                                                                                         */
+  int32_t max_local_points;         /* mvpLocalMapPoints: also the number of queries stage 2 is sized for                                             */
+  int32_t max_local_lines;          /* local_lines                                                                                                    */
+} lld_map_limits;
+int  lld_map_create(lld_ctx* ctx, const lld_map_limits* limits, lld_map** out);
+void lld_map_destroy(lld_map* map);   /* waits for the context's stream */
+int  lld_map_clear(lld_map* map);     /* Map::clear(): every slot never set, every list empty, no local map */
+/* Updates.  Each replaces whole rows by slot from flat host arrays: one upload, queued on the context's stream, ordered before any later
+ * track call; a row may be replaced any number of times, and no replacement fails while the live totals stay inside the limits.
+ * Refused before anything is queued, the map unchanged: LLD_ERR_INVALID for a NULL map or required array, n < 0, a slot out of range or
+ * named twice in one call, a referenced slot out of range, a start array that does not ascend from 0, order_key = UINT64_MAX;
+ * LLD_ERR_UNSUPPORTED for a live total beyond its limit.  n = 0 is LLD_OK.  Uniqueness of order_key among live keyframes is NOT checked: with
+ * two equal keys the order of those keyframes, and so the lists, are undefined (nothing is refused, nothing is read out of bounds).
+ * A HIP failure (LLD_ERR_HIP / LLD_ERR_ALLOC) may arrive after a call's host bookkeeping moved: the map is then unusable - every later
+ * lld_map_set_* and track call on it returns LLD_ERR_HIP - until lld_map_clear, after which it is filled again.
+ *   lld_map_set_points        GetWorldPos, GetNormal, GetMinDistanceInvariance / GetMaxDistanceInvariance AS lld_map_points takes them, GetDescriptor, isBad
+ *   lld_map_set_observations  mObservations of point slot[i] = kf_slot[start[i] .. start[i+1]); Observations() > 0 is "list not empty"
+ *   lld_map_set_keyframes     order_key: the keyframe's position in std::map<KeyFrame*,int> / std::set<KeyFrame*> iteration - the pointer value,
+ *                             or mnId for runs that repeat; unique among live keyframes.  parent: GetParent() or -1.  CSR lists per keyframe:
+ *                             cov = GetBestCovisibilityKeyFrames(10) in its order (entries beyond 10 are ignored), child = GetChilds() in any order,
+ *                             point = GetMapPointMatches() per keypoint (slot or -1), line = GetMapLineMatches() (slot or -1)
+ *   lld_map_set_lines         GetMinimalPos (x0, dir), GetMainPoints3D (x1, x2), GetDescriptor [line_dim], isBad */
+int  lld_map_set_points(lld_map* map, int32_t n, const int32_t* slot, const float* world_pos, const float* normal, const float* min_distance,
+                        const float* max_distance, const uint32_t* desc, const uint8_t* bad);
+int  lld_map_set_observations(lld_map* map, int32_t n, const int32_t* slot, const int32_t* start, const int32_t* kf_slot);
+int  lld_map_set_keyframes(lld_map* map, int32_t n, const int32_t* slot, const uint64_t* order_key, const uint8_t* bad, const int32_t* parent,
+                           const int32_t* cov_start, const int32_t* cov, const int32_t* child_start, const int32_t* child,
+                           const int32_t* point_start, const int32_t* point, const int32_t* line_start, const int32_t* line);
+int  lld_map_set_lines(lld_map* map, int32_t n, const int32_t* slot, const double* x0, const double* dir, const double* x1, const double* x2,
+                       const float* desc, const uint8_t* bad);
+/* Tracking::UpdateLocalMap on the frame's device state, queued behind whatever produced it (lld_frame_track_motion_model,
+ * _reference_keyframe, lld_frame_relocalize or lld_frame_track_set_state): no upload, no synchronisation.  :1726-1835 and :1677-1723, quirks included:
+ *   vote (:1730-1746)       a keypoint whose MapPoint is bad loses it (mvbOutlier stays); every observation of the others is one vote.
+ *   empty vote (:1748)      the routine returns: the list of the previous call (it lives in the lld_map) and the reference keyframe stay,
+ *                           UpdateLocalPoints still runs on that list with today's bad flags.
+ *   voted (:1758-1774)      in ascending order_key; bad ones are neither listed nor marked nor candidates for pKFmax, which is the first
+ *                           keyframe in that order with the strictly greatest count.
+ *   extension (:1778-1828)  over the voted entries only; it stops before an entry when the list holds more than 80; per entry the first of its
+ *                           cov list that is neither bad nor marked, the child of smallest order_key that is neither bad nor marked, and
+ *                           the parent if unmarked (its bad flag is not read) - and appending a parent ends the WHOLE loop (:1824).
+ *   points, lines (:1684-1722)  list order, then keypoint order; every non-bad one once.
+ * Never a silently shortened local map: more than 1024 voted keyframes, more than max_local_points points or max_local_lines lines set the
+ * status bits below, and lld_frame_track_local_map_resident then leaves the frame as it found it. */
+#define LLD_LOCAL_MAP_KEYFRAME_OVERFLOW 1
+#define LLD_LOCAL_MAP_POINT_OVERFLOW    2
+#define LLD_LOCAL_MAP_LINE_OVERFLOW     4
+#define LLD_MAP_MAX_LOCAL_KEYFRAMES  1280   /* 1024 voted, or at most 81 visited entries x 3 behind at most 81 */
+int  lld_frame_track_update_local_map(lld_frame* frame, lld_map* map);
+/* Stage 2 (lld_frame_track_local_map) on the lists the last lld_frame_track_update_local_map left: a kernel copies the listed rows into the
+ * buffers lld_frame_track_local_map stages from the host (has_obs = observations not empty, id = slot), and the same kernels follow, sized
+ * by max_local_points / max_local_lines; the entries behind the device-side counts are skipped entries.  Only the search's problem record
+ * is uploaded.  After an overflow the decision is taken on the device: every entry is a skipped entry and the frame's MapPoint / MapLine
+ * tables are set aside while the stage's kernels run and put back behind them, so the frame is left as stage 1 and the vote left it; the
+ * stage-2 record then reads all zero and lld_local_map_result.stage2_ran is 0.  lld_frame_track_finish and lld_frame_new_map_lines follow as
+ * after lld_frame_track_local_map.  LLD_ERR_INVALID before anything is queued: a NULL argument, a map of another context, no stage 1 on the
+ * frame, no lld_frame_track_update_local_map on this frame and this map since that stage 1, or another
+ * frame's update on the map since (the lists in the map are the last update's: frames share a map one after the other), a frame with lines whose dim differs from the map's line_dim. */
+int  lld_frame_track_local_map_resident(lld_frame* frame, const lld_track_params* params, lld_map* map);
+typedef struct {
+  int32_t status;                   /* 0, or LLD_LOCAL_MAP_*_OVERFLOW bits                                                                            */
+  int32_t n_voted;                  /* keyframeCounter.size()                                                                                         */
+  int32_t n_local_keyframes, n_local_points, n_local_lines;   /* a count beyond its limit is the true count; its list was not written                */
+  int32_t n_bad_cleared;            /* keypoints that lost a bad MapPoint (:1743)                                                                    */
+  int32_t ref_keyframe;             /* slot of pKFmax -> mpReferenceKF, or -1: unchanged                                                              */
+  int32_t vote_empty;               /* 1: the routine returned at :1748                                                                               */
+  int32_t stage2_ran;               /* 1 after lld_frame_track_local_map_resident on a local map without overflow                                     */
+  int32_t reserved;
+  /* caller-allocated, any may be NULL */
+  int32_t* local_keyframes;         /* [LLD_MAP_MAX_LOCAL_KEYFRAMES] mvpLocalKeyFrames as slots                                                       */
+  int32_t* local_points;            /* [max_local_points] mvpLocalMapPoints                                                                           */
+  int32_t* local_lines;             /* [max_local_lines]                                                                                              */
+  uint8_t* mp_in_view;              /* [max_local_points] with stage2: lld_track_result.mp_in_view per local point (stage2->mp_in_view is not read); left
+                                       alone when the frame's last stage 2 was lld_frame_track_local_map on more points than that                        */
+  lld_track_result* stage1;         /* as lld_frame_track_download fills them, in the same synchronisation                                            */
+  lld_track_result* stage2;
+} lld_local_map_result;
+int  lld_frame_local_map_download(lld_frame* frame, lld_map* map, lld_local_map_result* out);
 
 #if defined(__GNUC__)
 #pragma GCC visibility pop

@@ -373,7 +373,56 @@ class Tracking {
   Context& ctx_;
   double K_[9]; double b_, sx_, sy_, mdThr_; bool mono_;
 };
-
+// The map as flat tables resident in HBM (lld_map_*, include/lld_amd.h "the resident map"): keyframes, MapPoints and MapLines by slot, rows
+// replaced whole by the Set* calls (one upload each, queued on the context's stream).  TrackedFrame::UpdateLocalMap / TrackLocalMapResident run
+// Tracking::UpdateLocalMap (src/Tracking.cc:1667-1835) and TrackLocalMap on it.  One context, one host thread.
+class DeviceMap {
+ public:
+  DeviceMap(Context& ctx, const lld_map_limits& limits) : limits_(limits) { check(lld_map_create(ctx.get(), &limits, &m_), "lld_map_create"); }
+  ~DeviceMap() { if (m_) lld_map_destroy(m_); }
+  DeviceMap(const DeviceMap&) = delete;
+  DeviceMap& operator=(const DeviceMap&) = delete;
+  void Clear() { check(lld_map_clear(m_), "lld_map_clear"); }                                  // Map::clear()
+  void SetPoints(const std::vector<int32_t>& slot, const float* world_pos, const float* normal, const float* min_distance, const float* max_distance,
+                 const uint32_t* desc, const uint8_t* bad) {
+    check(lld_map_set_points(m_, (int32_t)slot.size(), slot.data(), world_pos, normal, min_distance, max_distance, desc, bad), "lld_map_set_points");
+  }
+  // start [slot.size() + 1] / kf_slot: MapPoint::mObservations of every listed point as keyframe slots
+  void SetObservations(const std::vector<int32_t>& slot, const std::vector<int32_t>& start, const std::vector<int32_t>& kf_slot) {
+    if (start.size() != slot.size() + 1) check(LLD_ERR_INVALID, "lld_map_set_observations");
+    check(lld_map_set_observations(m_, (int32_t)slot.size(), slot.data(), start.data(), kf_slot.data()), "lld_map_set_observations");
+  }
+  struct KeyFrameRows {          // CSR per listed keyframe: GetBestCovisibilityKeyFrames(10), GetChilds(), GetMapPointMatches(), GetMapLineMatches()
+    std::vector<int32_t> slot, parent, cov_start, cov, child_start, child, point_start, point, line_start, line;
+    std::vector<uint64_t> order_key; std::vector<uint8_t> bad;
+  };
+  void SetKeyFrames(const KeyFrameRows& k) {
+    const size_t n = k.slot.size();
+    if (k.order_key.size() != n || k.bad.size() != n || k.parent.size() != n || k.cov_start.size() != n + 1 || k.child_start.size() != n + 1 ||
+        k.point_start.size() != n + 1 || k.line_start.size() != n + 1) check(LLD_ERR_INVALID, "lld_map_set_keyframes");
+    check(lld_map_set_keyframes(m_, (int32_t)n, k.slot.data(), k.order_key.data(), k.bad.data(), k.parent.data(), k.cov_start.data(), k.cov.data(), k.child_start.data(),
+                                k.child.data(), k.point_start.data(), k.point.data(), k.line_start.data(), k.line.data()), "lld_map_set_keyframes");
+  }
+  void SetLines(const std::vector<int32_t>& slot, const double* x0, const double* dir, const double* x1, const double* x2, const float* desc, const uint8_t* bad) {
+    check(lld_map_set_lines(m_, (int32_t)slot.size(), slot.data(), x0, dir, x1, x2, desc, bad), "lld_map_set_lines");
+  }
+  const lld_map_limits& limits() const { return limits_; }
+  lld_map* get() const { return m_; }
+ private:
+  lld_map* m_ = nullptr;
+  lld_map_limits limits_;
+};
+// UpdateLocalMap's record with its lists and stage 2's mp_in_view (TrackedFrame::DownloadLocalMap binds them)
+struct LocalMapRecord {
+  lld_local_map_result r{};
+  std::vector<int32_t> local_keyframes, local_points, local_lines;
+  std::vector<uint8_t> mp_in_view;
+  void bind(const lld_map_limits& L) {
+    local_keyframes.assign(LLD_MAP_MAX_LOCAL_KEYFRAMES, -1); local_points.assign(L.max_local_points, -1); local_lines.assign(L.max_local_lines > 0 ? L.max_local_lines : 1, -1);
+    mp_in_view.assign(L.max_local_points, 0);
+    r.local_keyframes = local_keyframes.data(); r.local_points = local_points.data(); r.local_lines = local_lines.data(); r.mp_in_view = mp_in_view.data();
+  }
+};
 // The Tracking thread's per-frame chain on ONE device-resident Frame (lld_frame_track_*, include/lld_amd.h): what Tracking::TrackWithMotionModel
 // (src/Tracking.cc:885-994) and Tracking::TrackLocalMap (:1126-1220) do to mCurrentFrame, with mvpMapPoints / mvbOutlier / mvpMapLines /
 // mvbOutlierLines / mTcw living in HBM between the calls.  Both Track* calls only queue work; Download() is the one synchronisation.
@@ -456,6 +505,17 @@ class TrackedFrame {
   }
   void TrackLocalMap(const lld_map_points& local_points, const int32_t* ids, const lld_map_lines* local_lines) {
     check(lld_frame_track_local_map(f_, &params, &local_points, ids, local_lines), "lld_frame_track_local_map");
+  }
+  // Tracking::UpdateLocalMap on the resident map, queued behind stage 1; then stage 2 from the lists it left; then the frame's one download:
+  // UpdateLocalMap's record and lists, both stage records and mp_in_view per local point.
+  void UpdateLocalMap(DeviceMap& map) { check(lld_frame_track_update_local_map(f_, map.get()), "lld_frame_track_update_local_map"); }
+  void TrackLocalMapResident(DeviceMap& map) { check(lld_frame_track_local_map_resident(f_, &params, map.get()), "lld_frame_track_local_map_resident"); }
+  void DownloadLocalMap(DeviceMap& map, LocalMapRecord& rec, TrackRecord* stage1, TrackRecord* stage2) {
+    rec.bind(map.limits());
+    if (stage1) stage1->bind(nt_, nl_);
+    if (stage2) stage2->bind(nt_, nl_);
+    rec.r.stage1 = stage1 ? &stage1->r : nullptr; rec.r.stage2 = stage2 ? &stage2->r : nullptr;
+    check(lld_frame_local_map_download(f_, map.get(), &rec.r), "lld_frame_local_map_download");
   }
   void Download(TrackRecord* stage1, TrackRecord* stage2) {
     if (stage1) stage1->bind(nt_, nl_);

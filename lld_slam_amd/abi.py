@@ -416,6 +416,23 @@ class FramePointsParams(C.Structure):
                 ("view", C.c_void_p), ("pose_qt", c_double_p), ("depth", c_float_p)]
 
 
+class MapLimits(C.Structure):
+    """lld_map_limits."""
+    _fields_ = [("max_keyframes", C.c_int32), ("max_points", C.c_int32), ("max_lines", C.c_int32), ("line_dim", C.c_int32), ("max_observations", C.c_int32),
+                ("max_kf_points", C.c_int32), ("max_kf_lines", C.c_int32), ("max_children", C.c_int32), ("max_local_points", C.c_int32),
+                ("max_local_lines", C.c_int32)]
+
+
+class LocalMapResult(C.Structure):
+    """lld_local_map_result: stage1 / stage2 are lld_track_result* (tracking.TrackResult by reference)."""
+    _fields_ = [("status", C.c_int32), ("n_voted", C.c_int32), ("n_local_keyframes", C.c_int32), ("n_local_points", C.c_int32), ("n_local_lines", C.c_int32),
+                ("n_bad_cleared", C.c_int32), ("ref_keyframe", C.c_int32), ("vote_empty", C.c_int32), ("stage2_ran", C.c_int32), ("reserved", C.c_int32),
+                ("local_keyframes", c_int32_p), ("local_points", c_int32_p), ("local_lines", c_int32_p), ("mp_in_view", c_uint8_p),
+                ("stage1", C.c_void_p), ("stage2", C.c_void_p)]
+
+
+LOCAL_MAP_KEYFRAME_OVERFLOW, LOCAL_MAP_POINT_OVERFLOW, LOCAL_MAP_LINE_OVERFLOW = 1, 2, 4
+MAP_MAX_LOCAL_KEYFRAMES = 1280
 POINTS_LAST_FRAME, POINTS_INITIALIZATION = 0, 1
 RELOC_RUNG_POSE1, RELOC_RUNG_SEARCH1, RELOC_RUNG_POSE2, RELOC_RUNG_SEARCH2, RELOC_RUNG_POSE3 = 1, 2, 4, 8, 16
 
@@ -460,6 +477,8 @@ PRODUCT_SYMBOLS = [
     "lld_loop_correct", "lld_essential_graph_apply", "lld_global_ba_apply",
     "lld_frame_build_stereo_keypoints", "lld_frame_build_stereo", "lld_frame_stereo_download",
     "lld_frame_build_mono_keypoints", "lld_frame_build_mono", "lld_frame_keypoints_download", "lld_frame_image_bounds",
+    "lld_map_create", "lld_map_destroy", "lld_map_clear", "lld_map_set_points", "lld_map_set_observations", "lld_map_set_keyframes", "lld_map_set_lines",
+    "lld_frame_track_update_local_map", "lld_frame_track_local_map_resident", "lld_frame_local_map_download",
 ]
 
 

@@ -220,7 +220,7 @@ int run_finish(lld_frame* f, int mode, float th_depth, int32_t first_id, const D
   }
   if (mode == FIN_INITIALIZATION) {                                    // a new frame's state with the pose handed in (SetPose(eye), :526)
     st = track_reset_launch(sm, S, B, H); if (st) return st;
-    S->stage1_queued = true; S->n_in_view = 0; S->finish_ready = false; S->stage2_queued = false;
+    S->stage1_queued = true; S->local_map_of = nullptr; S->n_in_view = 0; S->finish_ready = false; S->stage2_queued = false;
   }
   FinishDev A{};
   A.nt = nt; A.n_keys = 2; while (A.n_keys < nt) A.n_keys <<= 1;

@@ -340,7 +340,7 @@ extern "C" int lld_frame_relocalize(lld_frame* f, const lld_track_params* P, con
   // ---- the frame enters the routine holding nothing; SearchByBoW against every candidate
   s = track_reset_launch(st, S, B, H); if (s) return s;
   { const int nmax = std::max(std::max(nt, S->nl), 1); hipLaunchKernelGGL(reloc_record_clear_kernel, dim3((nmax + 255) / 256), dim3(256), 0, st, S->D); }
-  S->stage1_queued = true; S->n_in_view = 0; S->finish_ready = false; S->stage2_queued = false;
+  S->stage1_queued = true; S->local_map_of = nullptr; S->n_in_view = 0; S->finish_ready = false; S->stage2_queued = false;
   LLD_HIP_TRY(hipMemsetAsync(B.d + o_zero, 0, zero_bytes, st));
   if (kn) LLD_HIP_TRY(hipMemsetAsync(B.dev(taken), 0xff, kn * 4, st));
   if (nt > 0 && nn_max > 0)

@@ -22,6 +22,7 @@
 #include "lld_common.h"
 #include "lld_device_math.h"
 #include "lld_frame_track_state.h"
+#include "lld_map_internal.h"
 #include "lld_track_internal.h"
 #include "lld_wave.h"
 
@@ -428,6 +429,66 @@ int check_lines(const lld_map_lines* ML) {
   return (ML->n < 0 || !ML->x0 || !ML->dir || !ML->x1 || !ML->x2 || !ML->desc || !ML->id) ? LLD_ERR_INVALID : LLD_OK;
 }
 
+// Stage 2 on nq local MapPoints and n_map local MapLines.  From the host (`map` null): the arrays travel in the stage's one upload.  From the
+// resident map: only the search's problem record travels, a kernel of lld_map.hip fills the same buffers from the tables, and the entries
+// behind the device-side counts are skipped entries.
+// After an overflow of UpdateLocalMap the resident route must leave the frame as it found it, and it does so WITHOUT a predicate in the
+// kernels below: the gather empties kp_has / ln_has and skips every entry, restore_launch puts the two tables back and blanks the record.
+// That rests on every kernel between the two being a no-op on a frame that holds nothing and a local map of skipped entries:
+//   track_mark_seen_kernel    writes only its own skip2 scratch;
+//   the projection and orb_search_kernel   no query survives: nothing is applied to kp_has / kp_id / kp_world / kp_obs;
+//   the line kernels          every map line is skipped: no assignment, n_tracked unchanged;
+//   pose_track_launch         no edge: no flag is written, pose_out reports fewer than three point edges;
+//   track_after_pose_kernel   nothing held: no discard; fewer than three edges: view, line camera and pose_qt stay.
+// A kernel added to this stage that writes frame state regardless of what is held breaks that: give it the status word instead.
+int local_map_stage(lld_frame* f, const lld_track_params* P, int nq, int n_map, const lld_map_points* mp, const int32_t* point_id, const lld_map_lines* local_lines,
+                    const lld_map* map) {
+  lld_frame_track_state* S = f->track; lld_ctx* ctx = f->ctx;
+  const int nt = f->nt;
+  // stage 2 reuses the work block from its start: stage 1's kernels are queued before this upload on the same stream, and stage_begin
+  // synchronises the stream before it grows the block
+  UploadBlock B; LocalPointsUp MPU; LinesUp U; SearchScratch sc;
+  const auto prob = B.take<char>(orbs_problem_bytes());
+  if (map) B.end_upload();
+  MPU.reserve(B, nq); U.reserve(B, n_map, S->dim);
+  if (!map) B.end_upload();
+  U.reserve_scratch(B); MPU.reserve_scratch(B);
+  const auto lskip2 = B.take<uint8_t>(std::max(n_map, 1)), inview = B.take<uint8_t>(std::max(nq, 1));
+  sc.reserve(B, nq, nt);
+  const auto lwork = B.take<char>(line_track_work_bytes(n_map, S->nl)), pwork = B.take<char>(pose_track_work_bytes(nt, S->nl));
+  const auto bk_kp = B.take<uint8_t>(map ? nt : 0), bk_ln = B.take<uint8_t>(map ? S->nl : 0);
+  int s = stage_begin(S, ctx, 1, B); if (s) return s;
+  if (!map) { MPU.stage(B, mp, point_id); U.stage(B, local_lines); }
+  const MapPointsDev MP = MPU.dev(B);
+  const ApplyDev ap{S->D.kp_has, S->D.kp_world, S->D.kp_id, S->D.kp_obs, MP.pos, B.dev(MPU.id), MP.has_obs, S->D.rec_h[1]->i + RI_SEARCH1, 0, 0};
+  orbs_fill_problem(f, 1, nq, S->D.kp_has, B.dev(sc.qrec), B.dev(MPU.desc), sc.out(B), B.dev(sc.cache), P->nnratio_local, 0, RunIf{}, ap, B.host(prob));
+  hipStream_t st = ctx->stream;
+  s = stage_submit(S, st, 1, B); if (s) return s;
+  // ---- kernels
+  lld_map_dev::GatherDst G{};
+  if (map) {
+    G.nt = nt; G.nl = S->nl;
+    G.pos = B.dev(MPU.pos); G.nrm = B.dev(MPU.nrm); G.maxd = B.dev(MPU.maxd); G.mind = B.dev(MPU.mind); G.obs = B.dev(MPU.obs); G.skip = B.dev(MPU.skip);
+    G.desc = B.dev(MPU.desc); G.id = B.dev(MPU.id);
+    if (n_map > 0) { G.x0 = B.dev(U.x0); G.dir = B.dev(U.dir); G.x1 = B.dev(U.x1); G.x2 = B.dev(U.x2); G.lskip = B.dev(U.skip); G.ldesc = B.dev(U.desc); G.lid = B.dev(U.id); }
+    G.kp_has = S->D.kp_has; G.ln_has = S->D.ln_has; G.bk_kp = B.dev(bk_kp); G.bk_ln = B.dev(bk_ln);
+    G.rec2 = reinterpret_cast<int32_t*>(S->D.rec_h[1]); G.n_rec2 = (int)(sizeof(RecHeader) / 4);
+    s = lld_map_dev::gather_launch(st, map, G); if (s) return s;
+  }
+  if (nq + n_map > 0)                                                          // (tables sized by state_build)
+    hipLaunchKernelGGL(track_mark_seen_kernel, dim3(1), dim3(kSeenThreads), S->seen_lds, st, S->D, nq, B.dev(MPU.id), B.dev(MPU.skip), B.dev(MPU.skip2), n_map, B.dev(U.id),
+                       B.dev(U.skip), B.dev(lskip2), S->seen_psize - 1, S->seen_lsize - 1);
+  S->in_view_off = inview.off; S->n_in_view = nq;
+  s = orbs_project_local_points(st, f->consts, nullptr, S->D.view, MP, P->viewing_cos_limit, P->th_local, B.dev(sc.qrec),
+                                FrustumOut{B.dev(inview), nullptr, nullptr, nullptr, S->D.rec_h[1]->i + RI_IN_VIEW}); if (s) return s;
+  s = orbs_launch_n(ctx, st, f, B.dev(prob), 1); if (s) return s;
+  s = run_lines(f, st, P, B, U, B.dev(lskip2), B.dev(lwork)); if (s) return s;
+  s = run_pose(f, st, P, B.dev(pwork), 1); if (s) return s;
+  if (map) { s = lld_map_dev::restore_launch(st, map, G); if (s) return s; }
+  S->finish_ready = true; S->stage2_queued = true;
+  return LLD_OK;
+}
+
 }  // namespace
 
 namespace lld_track {
@@ -537,7 +598,7 @@ int lld_frame_track_motion_model(lld_frame* f, const lld_track_params* P, const 
   }
   s = run_lines(f, st, P, B, U, B.dev(U.skip), B.dev(lwork)); if (s) return s;
   s = run_pose(f, st, P, B.dev(pwork), 0); if (s) return s;
-  S->stage1_queued = true; S->n_in_view = 0; S->finish_ready = false; S->stage2_queued = false;
+  S->stage1_queued = true; S->local_map_of = nullptr; S->n_in_view = 0; S->finish_ready = false; S->stage2_queued = false;
   return LLD_OK;
 }
 
@@ -576,7 +637,7 @@ int lld_frame_track_reference_keyframe(lld_frame* f, const lld_track_params* P, 
   const ApplyDev ap{S->D.kp_has, S->D.kp_world, S->D.kp_id, S->D.kp_obs, q.pos, q.id, q.obs, S->D.rec_h[0]->i + RI_SEARCH1, 0, 0};
   s = bow_search_launch(st, Bs, ap); if (s) return s;
   s = run_pose(f, st, P, B.dev(pwork), 0); if (s) return s;                    // (no AddLinesFrom: track_reset_launch left the line tables empty)
-  S->stage1_queued = true; S->n_in_view = 0; S->finish_ready = false; S->stage2_queued = false;
+  S->stage1_queued = true; S->local_map_of = nullptr; S->n_in_view = 0; S->finish_ready = false; S->stage2_queued = false;
   return LLD_OK;
 }
 
@@ -610,7 +671,7 @@ int lld_frame_track_set_state(lld_frame* f, const lld_track_params* P, const lld
   const int nmax = std::max(std::max(std::max(nt, nl), n_trk), 64);
   hipLaunchKernelGGL(track_load_kernel, dim3((nmax + 255) / 256), dim3(256), 0, st, S->D, U.dev(B), B.dev(H.pose), B.dev(H.view), B.dev(H.lp));
   LLD_HIP_TRY(hipGetLastError());
-  S->stage1_queued = true; S->n_in_view = 0; S->finish_ready = true; S->stage2_queued = false;
+  S->stage1_queued = true; S->local_map_of = nullptr; S->n_in_view = 0; S->finish_ready = true; S->stage2_queued = false;
   return LLD_OK;
 }
 
@@ -618,41 +679,24 @@ int lld_frame_track_local_map(lld_frame* f, const lld_track_params* P, const lld
   if (!f || !P || !mp) return LLD_ERR_INVALID;
   lld_frame_track_state* S = f->track;
   if (!S || !S->stage1_queued) return LLD_ERR_INVALID;                        // the frame's pose and MapPoints come from lld_frame_track_motion_model
-  const int nq = mp->n, nt = f->nt;
+  const int nq = mp->n;
   if (nq < 0 || (nq > 0 && (!mp->world_pos || !mp->normal || !mp->max_distance || !mp->min_distance || !mp->desc || !point_id))) return LLD_ERR_INVALID;
-  lld_ctx* ctx = f->ctx;
-  LLD_HIP_TRY(hipSetDevice(ctx->device));
+  LLD_HIP_TRY(hipSetDevice(f->ctx->device));
   int s = check_lines(local_lines); if (s) return s;
   const int n_map = (local_lines && S->nl > 0) ? local_lines->n : 0;
-  // stage 2 reuses the work block from its start: stage 1's kernels are queued before this upload on the same stream, and stage_begin
-  // synchronises the stream before it grows the block
-  UploadBlock B; LocalPointsUp MPU; LinesUp U; SearchScratch sc;
-  const auto prob = B.take<char>(orbs_problem_bytes());
-  MPU.reserve(B, nq); U.reserve(B, n_map, S->dim);
-  B.end_upload();
-  U.reserve_scratch(B); MPU.reserve_scratch(B);
-  const auto lskip2 = B.take<uint8_t>(std::max(n_map, 1)), inview = B.take<uint8_t>(std::max(nq, 1));
-  sc.reserve(B, nq, nt);
-  const auto lwork = B.take<char>(line_track_work_bytes(n_map, S->nl)), pwork = B.take<char>(pose_track_work_bytes(nt, S->nl));
-  s = stage_begin(S, ctx, 1, B); if (s) return s;
-  MPU.stage(B, mp, point_id); U.stage(B, local_lines);
-  const MapPointsDev MP = MPU.dev(B);
-  const ApplyDev ap{S->D.kp_has, S->D.kp_world, S->D.kp_id, S->D.kp_obs, MP.pos, B.dev(MPU.id), MP.has_obs, S->D.rec_h[1]->i + RI_SEARCH1, 0, 0};
-  orbs_fill_problem(f, 1, nq, S->D.kp_has, B.dev(sc.qrec), B.dev(MPU.desc), sc.out(B), B.dev(sc.cache), P->nnratio_local, 0, RunIf{}, ap, B.host(prob));
-  hipStream_t st = ctx->stream;
-  s = stage_submit(S, st, 1, B); if (s) return s;
-  // ---- kernels
-  if (nq + n_map > 0)                                                          // (tables sized by state_build)
-    hipLaunchKernelGGL(track_mark_seen_kernel, dim3(1), dim3(kSeenThreads), S->seen_lds, st, S->D, nq, B.dev(MPU.id), B.dev(MPU.skip), B.dev(MPU.skip2), n_map, B.dev(U.id),
-                       B.dev(U.skip), B.dev(lskip2), S->seen_psize - 1, S->seen_lsize - 1);
-  S->in_view_off = inview.off; S->n_in_view = nq;
-  s = orbs_project_local_points(st, f->consts, nullptr, S->D.view, MP, P->viewing_cos_limit, P->th_local, B.dev(sc.qrec),
-                                FrustumOut{B.dev(inview), nullptr, nullptr, nullptr, S->D.rec_h[1]->i + RI_IN_VIEW}); if (s) return s;
-  s = orbs_launch_n(ctx, st, f, B.dev(prob), 1); if (s) return s;
-  s = run_lines(f, st, P, B, U, B.dev(lskip2), B.dev(lwork)); if (s) return s;
-  s = run_pose(f, st, P, B.dev(pwork), 1); if (s) return s;
-  S->finish_ready = true; S->stage2_queued = true;
-  return LLD_OK;
+  return local_map_stage(f, P, nq, n_map, mp, point_id, local_lines, nullptr);
+}
+
+int lld_frame_track_local_map_resident(lld_frame* f, const lld_track_params* P, lld_map* map) {
+  if (!f || !P || !map) return LLD_ERR_INVALID;
+  lld_frame_track_state* S = f->track;
+  if (!S || !S->stage1_queued) return LLD_ERR_INVALID;
+  const lld_map_dev::Limits L = lld_map_dev::limits(map);
+  if (L.ctx != f->ctx || (S->nl > 0 && S->dim != L.line_dim)) return LLD_ERR_INVALID;
+  if (L.poisoned) return LLD_ERR_HIP;
+  if (S->local_map_of != map || S->local_map_serial != L.serial) return LLD_ERR_INVALID;                         // the lists must be this frame's: UpdateLocalMap comes first (src/Tracking.cc:1131)
+  LLD_HIP_TRY(hipSetDevice(f->ctx->device));
+  return local_map_stage(f, P, L.max_local_points, S->nl > 0 ? L.max_local_lines : 0, nullptr, nullptr, nullptr, map);
 }
 
 int lld_frame_track_download(lld_frame* f, lld_track_result* r1, lld_track_result* r2) {

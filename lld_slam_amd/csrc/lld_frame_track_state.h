@@ -134,6 +134,8 @@ struct lld_frame_track_state {
   char* h_rec = nullptr; size_t h_rec_bytes = 0;
   lld_track::ViewConsts consts{};
   bool stage1_queued = false;
+  unsigned long long local_map_serial = 0;     // ... and that call's number on the map: another frame's update since replaces the lists
+  const lld_map* local_map_of = nullptr;       // the map lld_frame_track_update_local_map ran on after the last stage 1 (every stage 1 clears it)
   bool stage2_queued = false;                  // lld_frame_track_local_map ran after the last stage 1: the stage-2 record is this frame's
   bool finish_ready = false;                   // the last chain call was lld_frame_track_local_map or lld_frame_track_set_state (lld_frame_track_finish)
   size_t in_view_off = 0; int n_in_view = 0;   // Frame::isInFrustum flags of stage 2's local MapPoints, inside d_work

@@ -137,6 +137,21 @@ __device__ __forceinline__ void bitonic_sort(unsigned long long* keys, int npad)
     }
 }
 
+// The same network on (key, value) pairs: vals[i] travels with keys[i].  For keys that fill all 64 bits (a pointer, an id), where no value
+// can be packed into the key.  Equal keys keep no particular order.  Lanes, npad and barriers as bitonic_sort.
+template <int kThreads>
+__device__ __forceinline__ void bitonic_sort_pairs(unsigned long long* keys, int* vals, int npad) {
+  for (int k = 2; k <= npad; k <<= 1)
+    for (int j = k >> 1; j > 0; j >>= 1) {
+      for (int t = threadIdx.x; t < (npad >> 1); t += kThreads) {
+        const int lo = ((t & ~(j - 1)) << 1) | (t & (j - 1)), hi = lo | j;
+        const unsigned long long a = keys[lo], b = keys[hi];
+        if ((a > b) == ((lo & k) == 0)) { keys[lo] = b; keys[hi] = a; const int v = vals[lo]; vals[lo] = vals[hi]; vals[hi] = v; }
+      }
+      __syncthreads();
+    }
+}
+
 // ---------------------------------------------------------------------------------------------------------------- Hamming distance
 // DescriptorDistance of two 256-bit descriptors: plain popcounts of the eight word pairs, summed from the first word.  Any lane, no LDS.
 

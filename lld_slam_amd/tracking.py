@@ -470,6 +470,58 @@ class DeviceTrackedFrame:
         self._check(self.lib.fn("frame_track_local_map")(self.res.handle, C.byref(self.params), C.byref(m), ids.ctypes.data_as(c_int32_p),
                                                           C.byref(ml) if local_lines is not None else None), "lld_frame_track_local_map")
 
+    def update_local_map(self, dmap):
+        """Tracking::UpdateLocalMap on the device (lld_frame_track_update_local_map), queued behind stage 1.  dmap: device_map.DeviceMap."""
+        fn = self.lib.fn("frame_track_update_local_map")
+        fn.argtypes = [C.c_void_p, C.c_void_p]; fn.restype = C.c_int
+        self._check(fn(self.res.handle, dmap.handle), "lld_frame_track_update_local_map")
+
+    def track_local_map_resident(self, dmap):
+        """Stage 2 on the lists update_local_map left in dmap (lld_frame_track_local_map_resident)."""
+        fn = self.lib.fn("frame_track_local_map_resident")
+        fn.argtypes = [C.c_void_p, C.POINTER(TrackParams), C.c_void_p]; fn.restype = C.c_int
+        self._check(fn(self.res.handle, C.byref(self.params), dmap.handle), "lld_frame_track_local_map_resident")
+        self.n_local_points = int(dmap.limits.max_local_points)
+
+    def local_map_download(self, dmap, lists=True, stage2=True):
+        """lld_frame_local_map_download: UpdateLocalMap's record as a dict (with the three lists when `lists`), plus 'stages': the records of
+        download() fetched in the same synchronisation (stage 2 with mp_in_view per local point when it was queued)."""
+        fn = self.lib.fn("frame_local_map_download")
+        fn.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(abi.LocalMapResult)]; fn.restype = C.c_int
+        nt, nl, L = self.F.n, self.n_lines, dmap.limits
+        R = abi.LocalMapResult()
+        a = dict(local_keyframes=np.zeros(abi.MAP_MAX_LOCAL_KEYFRAMES, np.int32), local_points=np.zeros(max(L.max_local_points, 1), np.int32),
+                 local_lines=np.zeros(max(L.max_local_lines, 1), np.int32))
+        if lists:
+            for k_, v in a.items(): setattr(R, k_, v.ctypes.data_as(c_int32_p))
+        outs = []
+        for st_ in range(2 if stage2 else 1):
+            r = TrackResult()
+            b = dict(kp_point_id=np.empty(nt, np.int32), kp_outlier=np.empty(nt, np.uint8), ln_line_id=np.empty(nl, np.int32), ln_outlier=np.empty(nl, np.uint8))
+            r.kp_point_id = b["kp_point_id"].ctypes.data_as(c_int32_p); r.kp_outlier = b["kp_outlier"].ctypes.data_as(c_uint8_p)
+            r.ln_line_id = b["ln_line_id"].ctypes.data_as(c_int32_p); r.ln_outlier = b["ln_outlier"].ctypes.data_as(c_uint8_p)
+            outs.append((r, b))
+        in_view = np.zeros(max(L.max_local_points, 1), np.uint8)
+        R.mp_in_view = in_view.ctypes.data_as(c_uint8_p)
+        R.stage1 = C.cast(C.pointer(outs[0][0]), C.c_void_p)
+        if stage2: R.stage2 = C.cast(C.pointer(outs[1][0]), C.c_void_p)
+        self._check(fn(self.res.handle, dmap.handle, C.byref(R)), "lld_frame_local_map_download")
+        d = {k_: int(getattr(R, k_)) for k_ in ("status", "n_voted", "n_local_keyframes", "n_local_points", "n_local_lines", "n_bad_cleared", "ref_keyframe",
+                                                "vote_empty", "stage2_ran")}
+        if lists:
+            d["local_keyframes"] = a["local_keyframes"][:min(d["n_local_keyframes"], abi.MAP_MAX_LOCAL_KEYFRAMES)].copy()
+            ok = not (d["status"] & abi.LOCAL_MAP_KEYFRAME_OVERFLOW)
+            d["local_points"] = a["local_points"][:d["n_local_points"]].copy() if ok and d["n_local_points"] <= L.max_local_points else None
+            d["local_lines"] = a["local_lines"][:d["n_local_lines"]].copy() if ok and d["n_local_lines"] <= L.max_local_lines else None
+        stages = []
+        for r, b in outs:
+            s_ = dict(b, pose_qt=np.array(list(r.pose_qt)), chi2=float(r.chi2))
+            for c in _COUNTERS: s_[c] = int(getattr(r, c))
+            stages.append(s_)
+        if stage2: stages[1]["mp_in_view"] = in_view
+        d["stages"] = stages
+        return d
+
     def download(self, stage2=True):
         """One copy, one synchronisation: the records of stage 1 and (if queued) stage 2 as dicts."""
         nt, nl = self.F.n, self.n_lines
