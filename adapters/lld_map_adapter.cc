@@ -46,7 +46,7 @@ void MapOnDevice::Upload(lld_slam::Map* pMap) {
 void MapOnDevice::UpdatePoints(const std::vector<MapPoint*>& points) {
   const size_t n = points.size();
   if (!n) return;
-  std::vector<int32_t> slot(n), start(1, 0), obs; std::vector<float> pos(3 * n), nrm(3 * n), mind(n), maxd(n); std::vector<uint32_t> desc(8 * n, 0u); std::vector<uint8_t> bad(n);
+  std::vector<int32_t> slot(n), start(1, 0), obs, idx, nobs(n); std::vector<float> pos(3 * n), nrm(3 * n), mind(n), maxd(n); std::vector<uint32_t> desc(8 * n, 0u); std::vector<uint8_t> bad(n);
   for (size_t i = 0; i < n; i++) {
     MapPoint* pMP = points[i];
     remember(pt_, pMP, limits_.max_points, "MapOnDevice::UpdatePoints");
@@ -59,13 +59,15 @@ void MapOnDevice::UpdatePoints(const std::vector<MapPoint*>& points) {
     const std::map<KeyFrame*, size_t> observations = pMP->GetObservations();
     for (std::map<KeyFrame*, size_t>::const_iterator it = observations.begin(); it != observations.end(); ++it) {
       const int32_t s = slot_of(it->first, limits_.max_keyframes);
-      if (s >= 0) obs.push_back(s);
+      if (s >= 0) { obs.push_back(s); idx.push_back((int32_t)it->second); }
     }
     start.push_back((int32_t)obs.size());
+    nobs[i] = pMP->Observations();
   }
-  obs.push_back(0);                                                            // (never read: a non-null pointer for an empty list)
+  obs.push_back(0); idx.push_back(0);                                          // (never read: a non-null pointer for an empty list)
   check(lld_map_set_points(m_, (int32_t)n, slot.data(), pos.data(), nrm.data(), mind.data(), maxd.data(), desc.data(), bad.data()), "lld_map_set_points");
-  check(lld_map_set_observations(m_, (int32_t)n, slot.data(), start.data(), obs.data()), "lld_map_set_observations");
+  if (covis_) check(lld_map_set_observations_indexed(m_, (int32_t)n, slot.data(), start.data(), obs.data(), idx.data(), nobs.data()), "lld_map_set_observations_indexed");
+  else check(lld_map_set_observations(m_, (int32_t)n, slot.data(), start.data(), obs.data()), "lld_map_set_observations");
 }
 
 void MapOnDevice::UpdateKeyFrames(const std::vector<KeyFrame*>& keyframes) {
@@ -93,6 +95,162 @@ void MapOnDevice::UpdateKeyFrames(const std::vector<KeyFrame*>& keyframes) {
   cv.push_back(0); hv.push_back(0); pv.push_back(-1); lv.push_back(-1);       // (never read: non-null pointers for empty lists)
   check(lld_map_set_keyframes(m_, (int32_t)n, slot.data(), key.data(), bad.data(), parent.data(), cs.data(), cv.data(), hs.data(), hv.data(), ps.data(), pv.data(),
                               ls.data(), lv.data()), "lld_map_set_keyframes");
+  if (!covis_) return;
+  // one octave and one depth per entry of the point row just sent
+  std::vector<int32_t> oct; std::vector<float> dep, thd(n);
+  for (size_t i = 0; i < n; i++) {
+    const KeyFrame* pKF = keyframes[i];
+    for (int32_t j = 0; j < ps[i + 1] - ps[i]; j++) {
+      oct.push_back((size_t)j < pKF->mvKeysUn.size() ? pKF->mvKeysUn[j].octave : 0);
+      dep.push_back((size_t)j < pKF->mvDepth.size() ? pKF->mvDepth[j] : -1.f);
+    }
+    thd[i] = pKF->mThDepth;
+  }
+  oct.push_back(0); dep.push_back(0.f);
+  check(lld_map_set_keyframe_keypoints(m_, (int32_t)n, slot.data(), ps.data(), oct.data(), dep.data(), thd.data()), "lld_map_set_keyframe_keypoints");
+}
+
+void MapOnDevice::SetCovisibles(const std::vector<KeyFrame*>& keyframes) {
+  const size_t n = keyframes.size();
+  if (!n) return;
+  std::vector<int32_t> slot(n), cs(1, 0), cv;
+  for (size_t i = 0; i < n; i++) {
+    slot[i] = (int32_t)keyframes[i]->mnId;
+    const std::vector<KeyFrame*> vNeighs = keyframes[i]->GetBestCovisibilityKeyFrames(10);
+    for (size_t j = 0; j < vNeighs.size(); j++) { const int32_t s = slot_of(vNeighs[j], limits_.max_keyframes); if (s >= 0) cv.push_back(s); }
+    cs.push_back((int32_t)cv.size());
+  }
+  cv.push_back(0);
+  check(lld_map_set_covisibles(m_, (int32_t)n, slot.data(), cs.data(), cv.data()), "lld_map_set_covisibles");
+}
+
+namespace {
+// One lld_map_covisibility call with lists that hold the totals: a guess first, then what the library reports.
+struct CovisResult {
+  std::vector<int32_t> conn_start, conn_kf, conn_weight, ordered_start, ordered_kf, ordered_weight, n_max, kf_max, n_mps, n_redundant;
+  std::vector<uint8_t> updated, redundant, status;
+};
+void covisibility(lld_map* m, const std::vector<int32_t>& slots, uint32_t flags, bool monocular, CovisResult& r) {
+  const size_t nq = slots.size();
+  lld_map_covisibility_in in; std::memset(&in, 0, sizeof in);
+  in.n_queries = (int32_t)nq; in.monocular = monocular ? 1 : 0; in.flags = flags; in.kf_slot = slots.data();
+  lld_covisibility_params_default(&in.params);
+  r.conn_start.assign(nq + 1, 0); r.ordered_start.assign(nq + 1, 0); r.n_max.assign(nq, 0); r.kf_max.assign(nq, -1); r.updated.assign(nq, 0);
+  r.n_mps.assign(nq, 0); r.n_redundant.assign(nq, 0); r.redundant.assign(nq, 0); r.status.assign(nq, 0);
+  size_t cap_c = 64 * nq, cap_o = 64 * nq;
+  for (int attempt = 0;; attempt++) {
+    r.conn_kf.assign(cap_c + 1, 0); r.conn_weight.assign(cap_c + 1, 0); r.ordered_kf.assign(cap_o + 1, 0); r.ordered_weight.assign(cap_o + 1, 0);
+    lld_map_covisibility_out out; std::memset(&out, 0, sizeof out);
+    lld_covisibility_out& L = out.lists;
+    L.conn_capacity = (int32_t)cap_c; L.ordered_capacity = (int32_t)cap_o; L.n_conn = L.n_ordered = -1;
+    L.conn_start = r.conn_start.data(); L.conn_kf = r.conn_kf.data(); L.conn_weight = r.conn_weight.data(); L.ordered_start = r.ordered_start.data();
+    L.ordered_kf = r.ordered_kf.data(); L.ordered_weight = r.ordered_weight.data(); L.n_max = r.n_max.data(); L.kf_max = r.kf_max.data(); L.updated = r.updated.data();
+    L.n_mps = r.n_mps.data(); L.n_redundant = r.n_redundant.data(); L.redundant = r.redundant.data();
+    out.status = r.status.data();
+    const int st = lld_map_covisibility(m, &in, &out);
+    if (st == LLD_ERR_INVALID && attempt == 0 && L.n_conn >= 0 && ((size_t)L.n_conn > cap_c || (size_t)L.n_ordered > cap_o)) { cap_c = L.n_conn; cap_o = L.n_ordered; continue; }
+    check(st, "lld_map_covisibility");
+    return;
+  }
+}
+}  // namespace
+
+int MapOnDevice::UpdateConnections(const std::vector<KeyFrame*>& vpKFs, std::vector<KeyFrame*>* overflowed) {
+  std::vector<KeyFrame*> queries; std::vector<int32_t> slots;
+  for (size_t i = 0; i < vpKFs.size(); i++) {
+    if (!vpKFs[i]) continue;
+    if (KeyFrameOf(slot_of(vpKFs[i], limits_.max_keyframes)) != vpKFs[i]) throw std::runtime_error("MapOnDevice::UpdateConnections: a keyframe the map does not hold");
+    queries.push_back(vpKFs[i]); slots.push_back((int32_t)vpKFs[i]->mnId);
+  }
+  if (queries.empty()) return 0;
+  CovisResult o;
+  covisibility(m_, slots, LLD_COVIS_CONNECTIONS | LLD_MAP_COVIS_WRITE_COV, false, o);
+  std::set<KeyFrame*> touched, tree;                                   // received AddConnection; parent or children changed
+  std::vector<KeyFrame*> over;
+  int written = 0;
+  for (size_t q = 0; q < queries.size(); q++) {
+    // more covisible keyframes than the device answers for: nothing was written for this one, neither here nor in the map
+    if (o.status[q]) { over.push_back(queries[q]); continue; }
+    if (!o.updated[q]) continue;                                       // if(KFcounter.empty()) return;   (:346-347)
+    KeyFrame* pKF = queries[q];
+    written++;
+    const int32_t s = o.ordered_start[q], e = o.ordered_start[q + 1];
+    // (mit->first)->AddConnection(this, mit->second) for the counters >= th, or for pKFmax (:364-375): the ordered list holds exactly these
+    for (int32_t j = s; j < e; j++) { KeyFrame* pN = kf_[o.ordered_kf[j]]; if (!pN) continue; pN->AddConnection(pKF, o.ordered_weight[j]); touched.insert(pN); }
+    std::map<KeyFrame*, int> KFcounter;
+    for (int32_t j = o.conn_start[q]; j < o.conn_start[q + 1]; j++) if (kf_[o.conn_kf[j]]) KFcounter[kf_[o.conn_kf[j]]] = o.conn_weight[j];
+    pKF->mConnectedKeyFrameWeights = KFcounter;                        // :390-392
+    pKF->mvpOrderedConnectedKeyFrames.clear(); pKF->mvOrderedWeights.clear();
+    for (int32_t j = s; j < e; j++) if (kf_[o.ordered_kf[j]]) { pKF->mvpOrderedConnectedKeyFrames.push_back(kf_[o.ordered_kf[j]]); pKF->mvOrderedWeights.push_back(o.ordered_weight[j]); }
+    if (pKF->mbFirstConnection && pKF->mnId != 0 && !pKF->mvpOrderedConnectedKeyFrames.empty()) {      // :394-399
+      pKF->mpParent = pKF->mvpOrderedConnectedKeyFrames.front();
+      pKF->mpParent->AddChild(pKF);
+      pKF->mbFirstConnection = false;
+      tree.insert(pKF); tree.insert(pKF->mpParent);
+    }
+  }
+  // the map: the queries' own cov rows are written already (a query that is also a neighbour is sent again: the objects hold the final lists)
+  std::vector<KeyFrame*> rows, cov;
+  for (std::set<KeyFrame*>::const_iterator it = tree.begin(); it != tree.end(); ++it) rows.push_back(*it);
+  for (std::set<KeyFrame*>::const_iterator it = touched.begin(); it != touched.end(); ++it) if (!tree.count(*it)) cov.push_back(*it);
+  UpdateKeyFrames(rows);
+  SetCovisibles(cov);
+  // objects and map agree about every keyframe that was applied; the others are the caller's (pKF->UpdateConnections(), then UpdateKeyFrames)
+  if (overflowed) *overflowed = over;
+  else if (!over.empty()) throw std::runtime_error("MapOnDevice::UpdateConnections: more covisible keyframes than LLD_MAP_COVIS_MAX_CONNECTED");
+  return written;
+}
+
+std::vector<KeyFrame*> MapOnDevice::KeyFrameCulling(KeyFrame* pCurrentKF, bool bMonocular, int* n_calls) {
+  const std::vector<KeyFrame*> vpLocalKeyFrames = pCurrentKF->GetVectorCovisibleKeyFrames();
+  std::vector<KeyFrame*> flagged;
+  int calls = 0;
+  size_t at = 0;
+  while (at < vpLocalKeyFrames.size()) {
+    std::vector<size_t> where; std::vector<int32_t> slots;             // position in vpLocalKeyFrames of each query
+    for (size_t i = at; i < vpLocalKeyFrames.size(); i++) {
+      KeyFrame* pKF = vpLocalKeyFrames[i];
+      if (pKF->mnId == 0) continue;                                    // :644-645
+      if (KeyFrameOf(slot_of(pKF, limits_.max_keyframes)) != pKF) throw std::runtime_error("MapOnDevice::KeyFrameCulling: a keyframe the map does not hold");
+      where.push_back(i); slots.push_back((int32_t)pKF->mnId);
+    }
+    if (slots.empty()) break;
+    CovisResult o;
+    covisibility(m_, slots, LLD_COVIS_CULLING, bMonocular, o);
+    calls++;
+    for (size_t q = 0; q < slots.size(); q++) if (o.status[q]) throw std::runtime_error("MapOnDevice::KeyFrameCulling: the map lacks keypoint data (EnableCovisibility before Upload)");
+    at = vpLocalKeyFrames.size();
+    for (size_t q = 0; q < slots.size(); q++) {
+      if (!o.redundant[q]) continue;                                   // if(nRedundantObservations>0.9*nMPs)   (:694)
+      KeyFrame* pKF = vpLocalKeyFrames[where[q]];
+      // what SetBadFlag is about to change: its MapPoints lose an observation, its neighbours a connection
+      std::set<MapPoint*> pts; std::vector<KeyFrame*> neighbours;
+      const std::vector<MapPoint*> vpMPs = pKF->GetMapPointMatches();
+      for (size_t j = 0; j < vpMPs.size(); j++) if (vpMPs[j] && PointOf(slot_of(vpMPs[j], limits_.max_points)) == vpMPs[j]) pts.insert(vpMPs[j]);
+      for (std::map<KeyFrame*, int>::const_iterator it = pKF->mConnectedKeyFrameWeights.begin(); it != pKF->mConnectedKeyFrameWeights.end(); ++it)
+        if (KeyFrameOf(slot_of(it->first, limits_.max_keyframes)) == it->first) neighbours.push_back(it->first);
+      // ... and the spanning tree is repaired (KeyFrame.cc:505-560): its children get new parents, those parents new children, its own
+      // parent loses a child
+      const std::set<KeyFrame*> spChilds = pKF->GetChilds();
+      KeyFrame* pOldParent = pKF->GetParent();
+      pKF->SetBadFlag();                                               // :695: observations are erased, the later counts are stale
+      flagged.push_back(pKF);
+      std::set<KeyFrame*> rows;                                        // whole rows: bad flag, parent, children (and the cov row with them)
+      rows.insert(pKF);
+      if (pOldParent) rows.insert(pOldParent);
+      for (std::set<KeyFrame*>::const_iterator it = spChilds.begin(); it != spChilds.end(); ++it) { rows.insert(*it); if ((*it)->GetParent()) rows.insert((*it)->GetParent()); }
+      std::vector<KeyFrame*> vRows, vCov;
+      for (std::set<KeyFrame*>::const_iterator it = rows.begin(); it != rows.end(); ++it) if (KeyFrameOf(slot_of(*it, limits_.max_keyframes)) == *it) vRows.push_back(*it);
+      for (size_t j = 0; j < neighbours.size(); j++) if (!rows.count(neighbours[j])) vCov.push_back(neighbours[j]);
+      UpdatePoints(std::vector<MapPoint*>(pts.begin(), pts.end()));
+      UpdateKeyFrames(vRows);
+      SetCovisibles(vCov);
+      at = where[q] + 1;
+      break;
+    }
+  }
+  if (n_calls) *n_calls = calls;
+  return flagged;
 }
 
 void MapOnDevice::UpdateLines(const std::vector<MapLine*>& lines) {

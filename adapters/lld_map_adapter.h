@@ -37,6 +37,26 @@ class MapOnDevice {
   void UpdateKeyFrames(const std::vector<lld_slam::KeyFrame*>& keyframes);
   void UpdateLines(const std::vector<lld_slam::MapLine*>& lines);
 
+  // ---- covisibility on the mirrored map (lld_map_covisibility): no gather, no upload of the map
+  // From here on Upload / UpdatePoints / UpdateKeyFrames also send what KeyFrameCulling reads: the keypoint index of every observation and
+  // MapPoint::Observations() with the points, mvKeysUn[i].octave / mvDepth[i] / mThDepth with the keyframes.  Call it before the first Upload
+  // (rows sent earlier carry none of it and KeyFrameCulling then throws).  Without it the three calls behave exactly as before.
+  void EnableCovisibility() { covis_ = true; }
+  // pKF->UpdateConnections() for every keyframe of the list, in list order, with one device call on the resident tables: what
+  // lld_adapter::UpdateConnections (lld_covisibility_adapter.h) applies - members, AddConnection on the neighbours, first-connection parent and
+  // AddChild - and then the map is brought up to date: the device wrote the queries' own cov rows, the neighbours' go through
+  // lld_map_set_covisibles, a keyframe with a new parent or child through UpdateKeyFrames.  The listed keyframes and their MapPoints must be
+  // current in the map.  Returns the number of keyframes the rule wrote.  A keyframe with more than LLD_MAP_COVIS_MAX_CONNECTED covisible
+  // keyframes gets nothing written, neither its members nor its cov row in the map; all the others are applied and pushed first, so objects
+  // and map agree.  Then such keyframes are returned in `overflowed` for the caller's pKF->UpdateConnections() + UpdateKeyFrames, or, when
+  // `overflowed` is NULL, the call throws.
+  int UpdateConnections(const std::vector<lld_slam::KeyFrame*>& vpKFs, std::vector<lld_slam::KeyFrame*>* overflowed = nullptr);
+  // LocalMapping::KeyFrameCulling for pCurrentKF, walked as lld_adapter::KeyFrameCulling walks it: one device call for the keyframes that
+  // remain, SetBadFlag on the first redundant one, then what that changed is pushed and the rest is counted again: its MapPoints' rows, its
+  // own row, its former neighbours' cov rows, and for the spanning-tree repair of KeyFrame::SetBadFlag (KeyFrame.cc:505-560) the whole rows of
+  // its former parent, of its children and of the parents they have afterwards.  Returns the flagged keyframes in order.
+  std::vector<lld_slam::KeyFrame*> KeyFrameCulling(lld_slam::KeyFrame* pCurrentKF, bool bMonocular, int* n_calls = nullptr);
+
   // slot -> object (NULL: never sent)
   lld_slam::KeyFrame* KeyFrameOf(int slot) const { return slot >= 0 && slot < (int)kf_.size() ? kf_[slot] : nullptr; }
   lld_slam::MapPoint* PointOf(int slot) const { return slot >= 0 && slot < (int)pt_.size() ? pt_[slot] : nullptr; }
@@ -50,6 +70,8 @@ class MapOnDevice {
   std::vector<lld_slam::KeyFrame*> kf_;
   std::vector<lld_slam::MapPoint*> pt_;
   std::vector<lld_slam::MapLine*> ln_;
+  bool covis_ = false;
+  void SetCovisibles(const std::vector<lld_slam::KeyFrame*>& keyframes);
 };
 
 }  // namespace lld_adapter

@@ -2606,6 +2606,98 @@ typedef struct {
 } lld_local_map_result;
 int  lld_frame_local_map_download(lld_frame* frame, lld_map* map, lld_local_map_result* out);
 
+/* ------------------------------------------------------------------ covisibility on the resident map (lld_map.hip)
+ * KeyFrame::UpdateConnections (src/KeyFrame.cc:312-402) and the redundancy count of LocalMapping::KeyFrameCulling (src/LocalMapping.cc:646-694)
+ * for a batch of keyframes, counted on the tables the map already holds: nothing of the map is gathered or uploaded, only the list of
+ * query slots travels.  The rules are those of lld_covisibility above, restated on the map's tables; every result is an integer.
+ *
+ * Tables the culling part needs beyond lld_map_set_*.  They live in pools of their own (sized from max_observations and max_kf_points, twice
+ * the limit like the others) that are allocated by the first call of one of the first two setters below - a map on which they are never
+ * called allocates what it allocated before.  The setters follow the contract of lld_map_set_*: everything is validated first, a refusal
+ * changes nothing, one block and one copy, a HIP failure behind the host bookkeeping poisons the map, lld_map_clear empties the new pools too.
+ *   lld_map_set_observations_indexed  lld_map_set_observations, and with each observation kp_index = mObservations[pKF], the keypoint index
+ *                             in the observing keyframe (>= 0), and per point n_obs[i] = MapPoint::Observations(), the stereo-weighted nObs
+ *                             (>= 0), which is not the list length.  A row set through lld_map_set_observations carries no indices (an
+ *                             earlier index row of that point is dropped) and keeps its n_obs.
+ *   lld_map_set_keyframe_keypoints    per keyframe slot[i]: octave[start[i] .. start[i+1]) = mvKeysUn[k].octave, depth[..] = mvDepth[k] (a float
+ *                             travels as its bit pattern), th_depth[i] = mThDepth.  LLD_ERR_INVALID also for a keyframe lld_map_set_keyframes
+ *                             never set and for a row whose length differs from the keyframe's point row.  A point row replaced later by one
+ *                             of another length leaves the keypoint row stale: the culling part says so (below) until the keypoints follow.
+ *   lld_map_set_covisibles    replaces only the cov row (GetBestCovisibilityKeyFrames(10), entries beyond 10 are ignored) of keyframes that are
+ *                             already set - for the neighbours on which UpdateConnections calls AddConnection (KeyFrame.cc:367, :374); key,
+ *                             bad flag, parent and the point, line and child rows stay.  LLD_ERR_INVALID also for a keyframe never set.  It
+ *                             allocates nothing. */
+int  lld_map_set_observations_indexed(lld_map* map, int32_t n, const int32_t* slot, const int32_t* start, const int32_t* kf_slot,
+                                      const int32_t* kp_index, const int32_t* n_obs);
+int  lld_map_set_keyframe_keypoints(lld_map* map, int32_t n, const int32_t* slot, const int32_t* start, const int32_t* octave, const float* depth,
+                                    const float* th_depth);
+int  lld_map_set_covisibles(lld_map* map, int32_t n, const int32_t* slot, const int32_t* cov_start, const int32_t* cov);
+/* What Tracking::UpdateLocalMap reads of a keyframe besides its points, read back from the device tables - for a caller that audits its
+ * mirror (examples/map_covis_harness.cpp) and for the tests: parent[i] (slot or -1), n_cov[i] and cov[10 i ..] (the row as the device holds
+ * it, written by lld_map_set_keyframes, lld_map_set_covisibles or LLD_MAP_COVIS_WRITE_COV; entries behind n_cov[i] are -1), and the child
+ * rows as CSR: child_start [n + 1] is always written, child [child_capacity] only if the total fits - otherwise the call returns
+ * LLD_ERR_INVALID with child_start alone written (child may be NULL with a capacity of 0).  One small upload, one kernel, one download, one
+ * wait; cost follows n.  LLD_ERR_INVALID also for a NULL argument, n < 0, a slot out of range or never set; n = 0 is LLD_OK. */
+int  lld_map_download_links(lld_map* map, int32_t n, const int32_t* slot, int32_t* parent, int32_t* n_cov, int32_t* cov, int32_t* child_start,
+                            int32_t child_capacity, int32_t* child);
+/* The call.  One upload (the query slots), kernels queued on the context's stream with no host trip between them, one download, one wait.
+ * Every keyframe in the outputs is a SLOT.  "Map order" is ascending order_key, NOT slot order: order_key decides every tie.
+ * Connections (LLD_COVIS_CONNECTIONS), per query kf_slot[q] (a slot may repeat; each listing is counted on its own):
+ *   :329-333 the query walks its own point row (lld_map_set_keyframes); an entry -1, a bad point and a point slot lld_map_set_points never
+ *            set (its row is empty) are skipped.
+ *   :335-342 every observation of the others whose keyframe slot differs from the query's is one count for that slot; a point listed twice
+ *            counts twice.  The observers' bad flags are not read (the reference does not read them).
+ *   :346-347 an empty counter: updated[q] = 0, no entries of either list, n_max[q] = 0, kf_max[q] = -1.
+ *   :390     conn_kf / conn_weight: every counted keyframe in ascending order_key.
+ *   :359-363 kf_max[q]: the first keyframe in that order with the strictly greatest count, n_max[q] its count.
+ *   :364-375 the counts >= th, or if there is none the single pair (n_max, kf_max).
+ *   :377-384 ordered_kf / ordered_weight: by descending weight, equal weights by descending order_key.
+ *   AddConnection on the neighbours and the first-connection parent belong to the caller (adapters/lld_map_adapter.cc).
+ *   With LLD_MAP_COVIS_WRITE_COV (valid only together with LLD_COVIS_CONNECTIONS) a query with updated = 1 and status 0 also gets the first
+ *   min(10, n) entries of its ordered list written into its cov row - GetBestCovisibilityKeyFrames(10) - on the stream, before any later
+ *   lld_frame_track_update_local_map; every other query's row is left alone.
+ * Culling (LLD_COVIS_CULLING), per query, over the same point row with the keyframe's keypoint row beside it:
+ *   :655-657 an entry -1 and a bad point are skipped.  A point slot never set is not bad and has Observations() == 0.
+ *   :659-663 unless `monocular`, an entry with depth > th_depth || depth < 0 is skipped (float compares; depth == th_depth is kept).
+ *   :665     n_mps++.
+ *   :666-688 only if the point's n_obs > th_obs: count its observations whose slot differs from the query's and whose octave - the observing
+ *            keyframe's keypoint row at the stored index - is <= the entry's octave + 1; count >= th_obs: n_redundant++.
+ *   :694     redundant[q] = (n_redundant > redundant_ratio * n_mps), the int against the double product.
+ *   The mnId == 0 skip and SetBadFlag stay with the caller, who updates the rows a flagged keyframe changed and calls again for the rest.
+ * Never a silently wrong answer - status[q], per query, and a bit of one query changes nothing for the others in the call:
+ *   LLD_MAP_COVIS_CONN_OVERFLOW      more than LLD_MAP_COVIS_MAX_CONNECTED distinct covisible keyframes: the query's connection outputs are
+ *                                    empty (no entries, n_max 0, kf_max -1), updated = 0, its cov row untouched.
+ *   LLD_MAP_COVIS_NO_KEYPOINT_DATA   culling only: the query keyframe has no keypoint row of its point row's length, or the observation row
+ *                                    of a point counted in n_mps has no index row of its length (it came through lld_map_set_observations,
+ *                                    so its n_obs is not known either), or an index falls outside the observing keyframe's keypoint row.
+ *                                    n_mps, n_redundant and redundant of the query are 0.  The device decides this from the row lengths
+ *                                    before it reads; no read leaves a row.
+ * Capacities as lld_covisibility: the totals needed are always written to lists.n_conn / lists.n_ordered; if either capacity is short the call
+ * returns LLD_ERR_INVALID with only those two written (n_queries * LLD_MAP_COVIS_MAX_CONNECTED always suffices; the cov rows of
+ * LLD_MAP_COVIS_WRITE_COV are written by that call all the same, and the repeated call writes the same rows again).  Arrays of a part not
+ * selected are neither read nor written and may be NULL; status is always required; lists.phase_ms may be NULL, otherwise it receives the
+ * HIP-event times of the upload of the query list, the kernels and the download.
+ * LLD_ERR_INVALID before anything is queued: a NULL map, in, out, kf_slot, status or required output; n_queries < 0; a negative capacity;
+ * flags zero, with unknown bits, or LLD_MAP_COVIS_WRITE_COV without LLD_COVIS_CONNECTIONS; a query slot out of range or never set.
+ * LLD_ERR_HIP for a poisoned map, like every other call on it.  n_queries = 0 is LLD_OK and touches nothing. */
+#define LLD_MAP_COVIS_MAX_CONNECTED    4096   /* distinct covisible keyframes of one query: half the 8192 cells of the counting table in LDS */
+#define LLD_MAP_COVIS_WRITE_COV        4u     /* flags bit 2, beside LLD_COVIS_CONNECTIONS / LLD_COVIS_CULLING                              */
+#define LLD_MAP_COVIS_CONN_OVERFLOW    1      /* status bits                                                                                */
+#define LLD_MAP_COVIS_NO_KEYPOINT_DATA 2
+typedef struct {
+  int32_t n_queries;
+  int32_t monocular;                /* mbMonocular: no depth test in the culling part */
+  uint32_t flags;
+  int32_t reserved;
+  lld_covisibility_params params;
+  const int32_t* kf_slot;           /* [n_queries] */
+} lld_map_covisibility_in;
+typedef struct {
+  lld_covisibility_out lists;       /* the arrays and the capacity protocol of lld_covisibility; keyframes are slots */
+  uint8_t* status;                  /* [n_queries] 0, or LLD_MAP_COVIS_CONN_OVERFLOW / LLD_MAP_COVIS_NO_KEYPOINT_DATA bits */
+} lld_map_covisibility_out;
+int  lld_map_covisibility(lld_map* map, const lld_map_covisibility_in* in, lld_map_covisibility_out* out);
+
 #if defined(__GNUC__)
 #pragma GCC visibility pop
 #endif

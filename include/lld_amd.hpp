@@ -406,6 +406,82 @@ class DeviceMap {
   void SetLines(const std::vector<int32_t>& slot, const double* x0, const double* dir, const double* x1, const double* x2, const float* desc, const uint8_t* bad) {
     check(lld_map_set_lines(m_, (int32_t)slot.size(), slot.data(), x0, dir, x1, x2, desc, bad), "lld_map_set_lines");
   }
+  // ---- covisibility on the resident map (lld_map_covisibility): the tables of its culling part, then the call
+  // start [slot.size() + 1]; kf_slot / kp_index: mObservations as (keyframe slot, keypoint index in it); n_obs: MapPoint::Observations()
+  void SetObservationsIndexed(const std::vector<int32_t>& slot, const std::vector<int32_t>& start, const std::vector<int32_t>& kf_slot,
+                              const std::vector<int32_t>& kp_index, const std::vector<int32_t>& n_obs) {
+    if (start.size() != slot.size() + 1 || kp_index.size() != kf_slot.size() || n_obs.size() != slot.size()) check(LLD_ERR_INVALID, "lld_map_set_observations_indexed");
+    check(lld_map_set_observations_indexed(m_, (int32_t)slot.size(), slot.data(), start.data(), kf_slot.data(), kp_index.data(), n_obs.data()),
+          "lld_map_set_observations_indexed");
+  }
+  // per listed keyframe one octave and one depth per keypoint (start [slot.size() + 1]) and mThDepth
+  void SetKeyFrameKeypoints(const std::vector<int32_t>& slot, const std::vector<int32_t>& start, const std::vector<int32_t>& octave, const std::vector<float>& depth,
+                            const std::vector<float>& th_depth) {
+    if (start.size() != slot.size() + 1 || depth.size() != octave.size() || th_depth.size() != slot.size()) check(LLD_ERR_INVALID, "lld_map_set_keyframe_keypoints");
+    check(lld_map_set_keyframe_keypoints(m_, (int32_t)slot.size(), slot.data(), start.data(), octave.data(), depth.data(), th_depth.data()), "lld_map_set_keyframe_keypoints");
+  }
+  // only the cov rows (GetBestCovisibilityKeyFrames(10)) of keyframes that are set
+  void SetCovisibles(const std::vector<int32_t>& slot, const std::vector<int32_t>& cov_start, const std::vector<int32_t>& cov) {
+    if (cov_start.size() != slot.size() + 1) check(LLD_ERR_INVALID, "lld_map_set_covisibles");
+    check(lld_map_set_covisibles(m_, (int32_t)slot.size(), slot.data(), cov_start.data(), cov.data()), "lld_map_set_covisibles");
+  }
+  // lld_map_download_links: parent, cov row and child row of the listed keyframes as the device holds them (CSR for the two lists)
+  struct Links { std::vector<int32_t> parent, cov_start, cov, child_start, child; };
+  Links DownloadLinks(const std::vector<int32_t>& kf_slot) const { return DownloadLinksOn(m_, kf_slot); }
+  static Links DownloadLinksOn(lld_map* m, const std::vector<int32_t>& kf_slot) {
+    Links r;
+    const size_t n = kf_slot.size();
+    std::vector<int32_t> ncov(n + 1, 0), cov(10 * n + 1, -1);
+    r.parent.assign(n + 1, -1); r.child_start.assign(n + 1, 0); r.child.assign(1, 0);
+    int st = lld_map_download_links(m, (int32_t)n, kf_slot.data(), r.parent.data(), ncov.data(), cov.data(), r.child_start.data(), 0, nullptr);
+    if (st == LLD_ERR_INVALID && n && r.child_start[n] > 0) {
+      r.child.assign(r.child_start[n], 0);
+      st = lld_map_download_links(m, (int32_t)n, kf_slot.data(), r.parent.data(), ncov.data(), cov.data(), r.child_start.data(), r.child_start[n], r.child.data());
+    }
+    check(st, "lld_map_download_links");
+    r.parent.resize(n); r.child.resize(n ? r.child_start[n] : 0);
+    r.cov_start.assign(1, 0);
+    for (size_t i = 0; i < n; i++) { for (int j = 0; j < ncov[i]; j++) r.cov.push_back(cov[10 * i + j]); r.cov_start.push_back((int32_t)r.cov.size()); }
+    return r;
+  }
+  struct CovisibilityResult {    // the outputs of lld_map_covisibility; every keyframe is a slot
+    std::vector<int32_t> conn_start, conn_kf, conn_weight, ordered_start, ordered_kf, ordered_weight, n_max, kf_max, n_mps, n_redundant;
+    std::vector<uint8_t> updated, redundant, status;
+    float phase_ms[3] = {0.f, 0.f, 0.f};
+  };
+  // flags: LLD_COVIS_CONNECTIONS, LLD_COVIS_CULLING, LLD_MAP_COVIS_WRITE_COV.  The lists are sized by a guess and, if the library reports a
+  // greater total, by that total in a second call.
+  CovisibilityResult Covisibility(const std::vector<int32_t>& kf_slot, uint32_t flags, bool monocular, const lld_covisibility_params* params = nullptr, bool timed = false) {
+    return CovisibilityOn(m_, kf_slot, flags, monocular, params, timed);
+  }
+  // ... on a handle somebody else owns (adapters/lld_map_adapter.h's MapOnDevice::get())
+  static CovisibilityResult CovisibilityOn(lld_map* m_, const std::vector<int32_t>& kf_slot, uint32_t flags, bool monocular, const lld_covisibility_params* params = nullptr,
+                                           bool timed = false) {
+    CovisibilityResult r;
+    const size_t nq = kf_slot.size();
+    lld_map_covisibility_in in{};
+    in.n_queries = (int32_t)nq; in.monocular = monocular ? 1 : 0; in.flags = flags; in.kf_slot = kf_slot.data();
+    if (params) in.params = *params; else lld_covisibility_params_default(&in.params);
+    r.conn_start.assign(nq + 1, 0); r.ordered_start.assign(nq + 1, 0); r.n_max.assign(nq, 0); r.kf_max.assign(nq, -1); r.updated.assign(nq, 0);
+    r.n_mps.assign(nq, 0); r.n_redundant.assign(nq, 0); r.redundant.assign(nq, 0); r.status.assign(nq, 0);
+    size_t cap_c = 64 * nq, cap_o = 64 * nq;
+    for (int attempt = 0;; attempt++) {
+      r.conn_kf.assign(cap_c + 1, 0); r.conn_weight.assign(cap_c + 1, 0); r.ordered_kf.assign(cap_o + 1, 0); r.ordered_weight.assign(cap_o + 1, 0);
+      lld_map_covisibility_out out{};
+      lld_covisibility_out& L = out.lists;
+      L.conn_capacity = (int32_t)cap_c; L.ordered_capacity = (int32_t)cap_o; L.n_conn = L.n_ordered = -1;
+      L.conn_start = r.conn_start.data(); L.conn_kf = r.conn_kf.data(); L.conn_weight = r.conn_weight.data(); L.ordered_start = r.ordered_start.data();
+      L.ordered_kf = r.ordered_kf.data(); L.ordered_weight = r.ordered_weight.data(); L.n_max = r.n_max.data(); L.kf_max = r.kf_max.data(); L.updated = r.updated.data();
+      L.n_mps = r.n_mps.data(); L.n_redundant = r.n_redundant.data(); L.redundant = r.redundant.data(); L.phase_ms = timed ? r.phase_ms : nullptr;
+      out.status = r.status.data();
+      const int st = lld_map_covisibility(m_, &in, &out);
+      if (st == LLD_ERR_INVALID && attempt == 0 && L.n_conn >= 0 && ((size_t)L.n_conn > cap_c || (size_t)L.n_ordered > cap_o)) { cap_c = L.n_conn; cap_o = L.n_ordered; continue; }
+      check(st, "lld_map_covisibility");
+      const bool conn = (flags & LLD_COVIS_CONNECTIONS) && nq;
+      r.conn_kf.resize(conn ? L.n_conn : 0); r.conn_weight.resize(conn ? L.n_conn : 0); r.ordered_kf.resize(conn ? L.n_ordered : 0); r.ordered_weight.resize(conn ? L.n_ordered : 0);
+      return r;
+    }
+  }
   const lld_map_limits& limits() const { return limits_; }
   lld_map* get() const { return m_; }
  private:

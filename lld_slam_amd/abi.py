@@ -431,6 +431,20 @@ class LocalMapResult(C.Structure):
                 ("stage1", C.c_void_p), ("stage2", C.c_void_p)]
 
 
+class MapCovisibilityIn(C.Structure):
+    """lld_map_covisibility_in."""
+    _fields_ = [("n_queries", C.c_int32), ("monocular", C.c_int32), ("flags", C.c_uint32), ("reserved", C.c_int32), ("params", CovisibilityParams),
+                ("kf_slot", c_int32_p)]
+
+
+class MapCovisibilityOut(C.Structure):
+    """lld_map_covisibility_out."""
+    _fields_ = [("lists", CovisibilityOut), ("status", c_uint8_p)]
+
+
+MAP_COVIS_MAX_CONNECTED = 4096
+MAP_COVIS_WRITE_COV = 4
+MAP_COVIS_CONN_OVERFLOW, MAP_COVIS_NO_KEYPOINT_DATA = 1, 2
 LOCAL_MAP_KEYFRAME_OVERFLOW, LOCAL_MAP_POINT_OVERFLOW, LOCAL_MAP_LINE_OVERFLOW = 1, 2, 4
 MAP_MAX_LOCAL_KEYFRAMES = 1280
 POINTS_LAST_FRAME, POINTS_INITIALIZATION = 0, 1
@@ -479,6 +493,7 @@ PRODUCT_SYMBOLS = [
     "lld_frame_build_mono_keypoints", "lld_frame_build_mono", "lld_frame_keypoints_download", "lld_frame_image_bounds",
     "lld_map_create", "lld_map_destroy", "lld_map_clear", "lld_map_set_points", "lld_map_set_observations", "lld_map_set_keyframes", "lld_map_set_lines",
     "lld_frame_track_update_local_map", "lld_frame_track_local_map_resident", "lld_frame_local_map_download",
+    "lld_map_set_observations_indexed", "lld_map_set_keyframe_keypoints", "lld_map_set_covisibles", "lld_map_covisibility", "lld_map_download_links",
 ]
 
 

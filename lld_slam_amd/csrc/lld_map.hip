@@ -20,6 +20,11 @@
 // Kernels of UpdateLocalMap: map_vote_kernel (one lane per keypoint), map_local_keyframes_kernel (one workgroup: sort, maximum, prefetch,
 // one wavefront for the order-dependent extension loop out of LDS), map_first_kernel / map_count_kernel / map_write_kernel (first occurrences
 // by 64-bit atomicMin, per-keyframe counts, ordered compaction), and map_gather_kernel for stage 2 (lld_frame_track_local_map_resident).
+//
+// Covisibility on the same tables (lld_map_covisibility: KeyFrame::UpdateConnections, src/KeyFrame.cc:312-402, and the redundancy count of
+// LocalMapping::KeyFrameCulling, src/LocalMapping.cc:646-694): map_covis_query_kernel, one workgroup per query, and map_covis_pack_kernel.
+// The culling part reads four members more (MapExt: keypoint index per observation, nObs per point, octave / depth / mThDepth per keyframe);
+// their tables and pools are allocated by the first lld_map_set_observations_indexed / lld_map_set_keyframe_keypoints, never by lld_map_create.
 #include "lld_common.h"
 #include "lld_frame_track_state.h"
 #include "lld_map_internal.h"
@@ -52,7 +57,22 @@ struct MapDev {
   int32_t* lkf; int32_t* lkf_np; int32_t* lkf_nl; int32_t* lpts; int32_t* llns; int32_t* st;
 };
 
+// The culling tables.  All null until the first lld_map_set_observations_indexed / lld_map_set_keyframe_keypoints.
+//   point slot s     p_nobs = MapPoint::Observations(), p_idx = (offset, length) in idx_pool of the keypoint indices, parallel to the p_obs row
+//   keyframe slot s  k_oct / k_dep = (offset, length) in oct_pool / dep_pool of mvKeysUn[i].octave / the bits of mvDepth[i], k_thd = mThDepth
+struct MapExt {
+  int32_t* p_nobs; int2* p_idx; int32_t* idx_pool; int2* k_oct; int2* k_dep; int32_t* oct_pool; int32_t* dep_pool; float* k_thd;
+};
+
 // ------------------------------------------------------------------------------------------------ scatter kernels of lld_map_set_*
+__global__ void map_scatter_kernel(int n, const int32_t* slot, const int32_t* v, int32_t* dst) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i < n) dst[slot[i]] = v[i];
+}
+__global__ void map_drop_rows_kernel(int n, const int32_t* slot, int2* d_row) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i < n) d_row[slot[i]] = make_int2(0, 0);
+}
 __global__ void map_rows_kernel(int n, const int32_t* slot, const int2* row, const int32_t* src, const int32_t* data, int2* d_row, int32_t* pool) {
   for (int r = blockIdx.x; r < n; r += gridDim.x) {
     const int2 w = row[r]; const int32_t from = src[r];
@@ -92,6 +112,24 @@ __global__ void map_set_keyframes_kernel(MapDev M, int n, const int32_t* slot, c
   const int c0 = cov_start[i], nc = min(cov_start[i + 1] - c0, 10);          // GetBestCovisibilityKeyFrames(10)
   M.k_ncov[s] = nc;
   for (int j = 0; j < nc; j++) M.k_cov[10 * s + j] = cov[c0 + j];
+}
+__global__ void map_set_cov_kernel(MapDev M, int n, const int32_t* slot, const int32_t* cov_start, const int32_t* cov) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  const int s = slot[i], c0 = cov_start[i], nc = min(cov_start[i + 1] - c0, 10);
+  M.k_ncov[s] = nc;
+  for (int j = 0; j < nc; j++) M.k_cov[10 * s + j] = cov[c0 + j];
+}
+// lld_map_download_links: what Tracking::UpdateLocalMap reads of a keyframe besides its points - parent, cov row, child row - back to the host
+__global__ void map_links_kernel(MapDev M, int n, const int32_t* slot, const int32_t* out_start, int32_t* parent, int32_t* ncov, int32_t* cov, int32_t* nchild, int32_t* child) {
+  const int i = blockIdx.x;
+  if (i >= n) return;
+  const int s = slot[i];
+  const int2 row = M.k_child[s];
+  const int room = out_start[i + 1] - out_start[i];
+  if (threadIdx.x == 0) { parent[i] = M.k_parent[s]; ncov[i] = M.k_ncov[s]; nchild[i] = row.y; }
+  if (threadIdx.x < 10) cov[10 * i + threadIdx.x] = (int)threadIdx.x < M.k_ncov[s] ? M.k_cov[10 * s + threadIdx.x] : -1;
+  for (int j = threadIdx.x; j < min(row.y, room); j += blockDim.x) child[out_start[i] + j] = M.child_pool[row.x + j];
 }
 
 // ------------------------------------------------------------------------------------------------ UpdateLocalKeyFrames: the vote (:1730-1746)
@@ -361,6 +399,224 @@ __global__ void map_restore_kernel(MapDev M, lld_map_dev::GatherDst G) {
   if (i < G.n_rec2) G.rec2[i] = 0;
 }
 
+// ------------------------------------------------------------------------------------------------ covisibility on the tables
+// map_covis_query_kernel, one workgroup of 256 per query.  A group of 16 lanes walks the observation row of one entry of the query
+// keyframe's point row, so sixteen entries are in flight.
+//   Connections: a map has up to 2^18 keyframe slots and a query meets a few hundred of them, so the counts live in an open-addressing table
+//     in LDS keyed by slot (8192 cells: int key[], int count[], 64 KB; home cell = slot mod 8192, linear probing).  A lane claims an empty
+//     cell by atomicCAS and then adds to the cell's count; integer adds commute, so the counts do not depend on the order.  Claims are counted:
+//     beyond LLD_MAP_COVIS_MAX_CONNECTED the query is an overflow and nothing more is inserted (at most one claim per lane goes through
+//     behind the limit, so the table is never full and every probe ends).
+//   Finishing: the cells in use are compacted to the query's staging range in HBM (the table is dead from here), their order_key fetched,
+//     and (key, position) sorted in the LDS the table held (lld_wave::bitonic_sort_pairs): the rank in that order is map order, conn_* go
+//     out by rank, the maximum is reduced on (weight, ~rank) so that the lowest rank wins, and the counts >= th are sorted once more as
+//     weight << 32 | rank; read from the top that is descending weight, then descending order_key.
+//   Culling: the qualifying observations of an entry are summed over its group by lane shuffles, the two per-query sums over the wavefront,
+//     then one LDS atomic per wavefront.  Two dependent loads more per observation than on flat tables: the keypoint index, then the octave
+//     in the observing keyframe's row - each behind a comparison of the index with that row's length.
+// map_covis_pack_kernel: one workgroup per query, exclusive sums of the per-query counts, then the staged lists to their packed places.
+// No workgroup reads what another workgroup of the same kernel writes, so a query's result cannot depend on the batch.
+constexpr int kCovThreads = 256, kCovGroup = 16, kCovGroups = kCovThreads / kCovGroup;
+constexpr int kCovMax = LLD_MAP_COVIS_MAX_CONNECTED, kCovCells = 2 * kCovMax;
+static_assert((kCovCells & (kCovCells - 1)) == 0 && kCovMax + 2 * kCovThreads < kCovCells, "the table keeps empty cells behind an overflow");
+constexpr size_t kCovLds = (size_t)kCovCells * 8;
+enum { CS_CLAIMED = 0, CS_NO_KP, CS_MPS, CS_RED, CS_WORDS };
+
+struct CovArgs {
+  const int32_t* query; const int32_t* stage_off;
+  int32_t n_queries, monocular, th, th_obs, has_ext; uint32_t flags; double ratio;
+  int32_t* st_slot; int32_t* st_cnt;         // staging: the table's cells in use, in cell order
+  int32_t* st_kf; int32_t* st_w; u64* st_key;     // ... the same in map order; the ordered list as weight << 32 | rank
+  int32_t* cnt_conn; int32_t* cnt_ord;
+  int32_t* n_max; int32_t* kf_max; uint8_t* updated; uint8_t* status; int32_t* n_mps; int32_t* n_red; uint8_t* redundant;
+  int32_t cap_conn, cap_ord;
+  int32_t* conn_start; int32_t* ord_start; int32_t* totals; int32_t* conn_kf; int32_t* conn_w; int32_t* ord_kf; int32_t* ord_w;
+};
+
+__device__ __forceinline__ void cov_count(int* tkey, int* tcnt, int* s_st, int kf) {
+  if (*(volatile int*)&s_st[CS_CLAIMED] > kCovMax) return;
+  int h = kf & (kCovCells - 1);
+  for (;;) {
+    int k = *(volatile int*)&tkey[h];
+    if (k == -1) {
+      k = atomicCAS(&tkey[h], -1, kf);
+      if (k == -1) { atomicAdd(&s_st[CS_CLAIMED], 1); k = kf; }
+    }
+    if (k == kf) break;
+    h = (h + 1) & (kCovCells - 1);
+  }
+  atomicAdd(&tcnt[h], 1);
+}
+
+__global__ __launch_bounds__(kCovThreads) void map_covis_query_kernel(MapDev M, MapExt X, CovArgs A) {
+  extern __shared__ __align__(16) unsigned char cov_lds[];
+  int* tkey = reinterpret_cast<int*>(cov_lds);
+  int* tcnt = tkey + kCovCells;
+  u64* keys = reinterpret_cast<u64*>(cov_lds);                         // behind the compaction: 32 KB of sort keys, 16 KB of values
+  int* vals = reinterpret_cast<int*>(keys + kCovMax);
+  __shared__ int s_st[CS_WORDS];
+  __shared__ int s_scan[kCovThreads / 64];
+  __shared__ u64 s_best[kCovThreads / 64];
+  const int q = blockIdx.x, t = threadIdx.x, lane = t & 63, wv = t >> 6;
+  const bool conn = (A.flags & LLD_COVIS_CONNECTIONS) != 0, cull = (A.flags & LLD_COVIS_CULLING) != 0;
+  const int own = A.query[q];
+  const int2 rp = M.k_pt[own];
+  if (conn) for (int i = t; i < kCovCells; i += kCovThreads) { tkey[i] = -1; tcnt[i] = 0; }
+  if (t < CS_WORDS) s_st[t] = 0;
+  // culling reads the keyframe's keypoint row beside its point row: only a row of the same length is read at all
+  int2 ro = make_int2(0, 0), rd = make_int2(0, 0);
+  float th_depth = 0.f;
+  bool kp_ok = false;
+  if (cull && A.has_ext) { ro = X.k_oct[own]; rd = X.k_dep[own]; th_depth = X.k_thd[own]; kp_ok = ro.y == rp.y && rd.y == rp.y; }
+  const bool cull_run = cull && kp_ok;
+  __syncthreads();
+
+  const int g = t / kCovGroup, gl = t % kCovGroup;
+  int my_mps = 0, my_red = 0;                                          // kept by the first lane of each group
+  const int n_row = (conn || cull_run) ? rp.y : 0;
+  for (int base = 0; base < n_row; base += kCovGroups) {               // uniform over the workgroup: the shuffles below are safe
+    const int j = base + g;
+    int s = 0, f = 0, lvl = 0, to_idx = 0;
+    bool count_cull = false;
+    if (j < n_row) {
+      const int p = M.kpt_pool[rp.x + j];
+      const int state = p >= 0 ? M.p_state[p] : 2;                     // NULL entries and bad points are skipped by both routines
+      if (state != 2) {
+        bool walk = conn && state == 1;                                // a point never set has an empty row
+        if (cull_run) {
+          const float depth = __int_as_float(X.dep_pool[rd.x + j]);
+          if (A.monocular || !(depth > th_depth || depth < 0.f)) {
+            if (gl == 0) my_mps++;
+            if (state == 1) {                                          // never set: Observations() == 0
+              // a row without an index row of its length came through lld_map_set_observations: its n_obs is not known either
+              const int2 row = M.p_obs[p], ir = X.p_idx[p];
+              if (ir.y != row.y) s_st[CS_NO_KP] = 1;
+              else if (X.p_nobs[p] > A.th_obs) { count_cull = true; lvl = X.oct_pool[ro.x + j] + 1; to_idx = ir.x - row.x; }
+            }
+          }
+        }
+        if (walk || count_cull) { const int2 row = M.p_obs[p]; s = row.x; f = row.x + row.y; }
+      }
+    }
+    int c = 0;
+    for (int o = s + gl; o < f; o += kCovGroup) {
+      const int kf = M.obs_pool[o];
+      if (kf == own) continue;
+      if (conn) cov_count(tkey, tcnt, s_st, kf);
+      if (count_cull) {
+        const int idx = X.idx_pool[o + to_idx];
+        const int2 orow = X.k_oct[kf];
+        if (idx < 0 || idx >= orow.y) s_st[CS_NO_KP] = 1;              // an index outside the observer's keypoint row
+        else if (X.oct_pool[orow.x + idx] <= lvl) c++;
+      }
+    }
+    if (cull_run) {
+      c = lld_wave::sum<kCovGroup>(c);
+      if (gl == 0 && count_cull && c >= A.th_obs) my_red++;
+    }
+  }
+  if (cull_run) {
+    lld_wave::sum_each(my_mps, my_red);
+    if (lane == 0) { atomicAdd(&s_st[CS_MPS], my_mps); atomicAdd(&s_st[CS_RED], my_red); }
+  }
+  __syncthreads();
+  int status = 0;
+  if (cull) {
+    const bool no_kp = !kp_ok || s_st[CS_NO_KP] != 0;
+    if (no_kp) status |= LLD_MAP_COVIS_NO_KEYPOINT_DATA;
+    if (t == 0) {
+      const int nm = no_kp ? 0 : s_st[CS_MPS], nr = no_kp ? 0 : s_st[CS_RED];
+      A.n_mps[q] = nm; A.n_red[q] = nr;
+      A.redundant[q] = ((double)nr > A.ratio * (double)nm) ? 1 : 0;    // nRedundantObservations > 0.9*nMPs: int against double
+    }
+  }
+  if (!conn) { if (t == 0) A.status[q] = (uint8_t)status; return; }
+  const int claimed = s_st[CS_CLAIMED];
+  if (claimed == 0 || claimed > kCovMax) {
+    // keyframeCounter.empty() (:346-347), or more keyframes than the table answers for: no entries, the cov row stays
+    if (t == 0) {
+      A.cnt_conn[q] = 0; A.cnt_ord[q] = 0; A.n_max[q] = 0; A.kf_max[q] = -1; A.updated[q] = 0;
+      A.status[q] = (uint8_t)(status | (claimed ? LLD_MAP_COVIS_CONN_OVERFLOW : 0));
+    }
+    return;
+  }
+  // ---- the cells in use, to the staging
+  const size_t off = (size_t)A.stage_off[q];
+  int n = 0;
+  for (int c0 = 0; c0 < kCovCells && n < claimed; c0 += kCovThreads) {
+    const int k = tkey[c0 + t], w = tcnt[c0 + t];
+    int tot;
+    const int r = lld_wave::block_excl_scan<kCovThreads>(k >= 0 ? 1 : 0, s_scan, tot);
+    if (k >= 0) { A.st_slot[off + n + r] = k; A.st_cnt[off + n + r] = w; }
+    n += tot;
+  }
+  __syncthreads();                                                     // the table is dead; the staged cells are visible to the workgroup
+  // ---- map order: ascending order_key
+  int npad = 2;
+  while (npad < n) npad <<= 1;
+  for (int i = t; i < npad; i += kCovThreads) { keys[i] = i < n ? M.k_key[A.st_slot[off + i]] : ~0ull; vals[i] = i < n ? i : -1; }
+  __syncthreads();
+  lld_wave::bitonic_sort_pairs<kCovThreads>(keys, vals, npad);
+  u64 best = 0;
+  int n_sel = 0;
+  for (int r = t; r < npad; r += kCovThreads) {
+    u64 k2 = 0;                                                        // a selected key is above 0: its weight is >= 1
+    if (r < n) {
+      const int i = vals[r], slot = A.st_slot[off + i], w = A.st_cnt[off + i];
+      A.st_kf[off + r] = slot; A.st_w[off + r] = w;
+      const u64 b = ((u64)(uint32_t)w << 32) | (uint32_t)(0xffffffffu - (uint32_t)r);     // it->second > nmax: the first of the greatest
+      if (b > best) best = b;
+      if (w >= A.th) { k2 = ((u64)(uint32_t)w << 32) | (uint32_t)r; n_sel++; }
+    }
+    keys[r] = k2;                                                      // rank r's key was this lane's to read
+  }
+  best = lld_wave::max(best);
+  if (lane == 0) s_best[wv] = best;
+  n_sel = lld_wave::block_sum(n_sel, s_scan);                          // (its barriers also publish s_best and the keys)
+  best = s_best[0];
+#pragma unroll
+  for (int k = 1; k < kCovThreads / 64; ++k) if (s_best[k] > best) best = s_best[k];
+  const int nmax = (int)(best >> 32), rmax = (int)(0xffffffffu - (uint32_t)best);
+  const int n_ord = n_sel ? n_sel : 1;                                 // none reaches th: the single pair (nmax, pKFmax) (:371-375)
+  lld_wave::bitonic_sort<kCovThreads>(keys, npad);                     // descending (weight, order_key) from the top
+  for (int i = t; i < n_sel; i += kCovThreads) A.st_key[off + i] = keys[npad - 1 - i];
+  if (t == 0) {
+    if (!n_sel) A.st_key[off] = ((u64)(uint32_t)nmax << 32) | (uint32_t)rmax;
+    A.cnt_conn[q] = n; A.cnt_ord[q] = n_ord; A.n_max[q] = nmax; A.kf_max[q] = A.st_kf[off + rmax]; A.updated[q] = 1;
+    A.status[q] = (uint8_t)status;
+  }
+  if ((A.flags & LLD_MAP_COVIS_WRITE_COV) && status == 0) {
+    // mvpOrderedConnectedKeyFrames' first ten: what Tracking::UpdateLocalMap reads as GetBestCovisibilityKeyFrames(10)
+    const int nc = min(n_ord, 10);
+    if (t < nc) M.k_cov[10 * own + t] = A.st_kf[off + (n_sel ? (uint32_t)keys[npad - 1 - t] : (uint32_t)rmax)];
+    if (t == 0) M.k_ncov[own] = nc;
+  }
+}
+
+__global__ __launch_bounds__(kCovThreads) void map_covis_pack_kernel(CovArgs A) {
+  __shared__ int s_sum[4];
+  const int q = blockIdx.x, t = threadIdx.x;
+  int a = 0, b = 0, ta = 0, tb = 0;                                    // conn before q, ordered before q, the totals
+  for (int j = t; j < A.n_queries; j += kCovThreads) {
+    const int c = A.cnt_conn[j], d = A.cnt_ord[j];
+    if (j < q) { a += c; b += d; }
+    ta += c; tb += d;
+  }
+  a = lld_wave::block_sum(a, s_sum); b = lld_wave::block_sum(b, s_sum); ta = lld_wave::block_sum(ta, s_sum); tb = lld_wave::block_sum(tb, s_sum);
+  if (t == 0) {
+    A.conn_start[q] = a; A.ord_start[q] = b;
+    if (q == A.n_queries - 1) { A.conn_start[A.n_queries] = ta; A.ord_start[A.n_queries] = tb; A.totals[0] = ta; A.totals[1] = tb; }
+  }
+  if (ta > A.cap_conn || tb > A.cap_ord) return;                       // a short capacity: only the totals go back
+  const size_t off = (size_t)A.stage_off[q];
+  const int nc = A.cnt_conn[q], no = A.cnt_ord[q];
+  for (int i = t; i < nc; i += kCovThreads) { A.conn_kf[a + i] = A.st_kf[off + i]; A.conn_w[a + i] = A.st_w[off + i]; }
+  for (int i = t; i < no; i += kCovThreads) {
+    const u64 key = A.st_key[off + i];
+    A.ord_kf[b + i] = A.st_kf[off + (uint32_t)key]; A.ord_w[b + i] = (int32_t)(key >> 32);
+  }
+}
+
 // ------------------------------------------------------------------------------------------------ host: the pools
 struct PoolPlan { bool repack = false; int n_up = 0; size_t n_data = 0; int64_t live_after = 0; Span<int32_t> slot, src, data; Span<int2> row; };
 
@@ -445,6 +701,10 @@ struct lld_map {
   char* d_tables = nullptr; size_t first_off = 0, first_bytes = 0, down_off = 0, down_bytes = 0, tables_bytes = 0;
   size_t o_lkf = 0, o_lpts = 0, o_llns = 0;                         // inside the downloaded span, which starts with st
   RowPool obs, child, kpt, kln;
+  // the culling tables (MapExt): allocated by the first setter that fills them
+  MapExt X{}; char* d_ext = nullptr; size_t ext_bytes = 0; RowPool idx, koct, kdep;
+  std::vector<uint8_t> kf_set;              // lld_map_set_keyframes named the slot since the last clear
+  bool cov_lds_set = false;                 // map_covis_query_kernel was granted its 64 KB of dynamic LDS
   std::vector<uint32_t> stamp_pt, stamp_kf, stamp_ln; uint32_t epoch = 0;
   // the staging of lld_map_set_*: pinned block, device block, the event of the last copy
   char* h_up = nullptr; size_t h_up_bytes = 0; char* d_up = nullptr; size_t d_up_bytes = 0; hipEvent_t uploaded = nullptr; bool upload_pending = false;
@@ -501,6 +761,32 @@ int tables_reset(lld_map* m) {
   LLD_HIP_TRY(hipMemsetAsync(m->D.k_parent, 0xff, (size_t)m->lim.max_keyframes * 4, st));
   LLD_HIP_TRY(hipMemsetAsync(m->D.st + ST_REF, 0xff, 4, st));
   m->obs.reset(); m->child.reset(); m->kpt.reset(); m->kln.reset();
+  std::fill(m->kf_set.begin(), m->kf_set.end(), (uint8_t)0);
+  if (m->d_ext) {
+    LLD_HIP_TRY(hipMemsetAsync(m->d_ext, 0, m->ext_bytes, st));
+    m->idx.reset(); m->koct.reset(); m->kdep.reset();
+  }
+  return LLD_OK;
+}
+
+// The culling tables and their pools, on the first call that fills them.  A failure leaves the map as it was.
+int ext_ensure(lld_map* m) {
+  if (m->d_ext) return LLD_OK;
+  const size_t nk = m->lim.max_keyframes, np = m->lim.max_points;
+  m->idx.init((int)np, m->lim.max_observations); m->koct.init((int)nk, m->lim.max_kf_points); m->kdep.init((int)nk, m->lim.max_kf_points);
+  UploadBlock B;
+  const auto pnobs = B.take<int32_t>(np); const auto pidx = B.take<int2>(np); const auto ipool = B.take<int32_t>(m->idx.mirror.size());
+  const auto koct = B.take<int2>(nk), kdep = B.take<int2>(nk); const auto opool = B.take<int32_t>(m->koct.mirror.size()), dpool = B.take<int32_t>(m->kdep.mirror.size());
+  const auto kthd = B.take<float>(nk);
+  char* d = nullptr;
+  if (hipMalloc(reinterpret_cast<void**>(&d), B.size) != hipSuccess) return LLD_ERR_ALLOC;
+  if (hipMemsetAsync(d, 0, B.size, m->ctx->stream) != hipSuccess) { (void)hipFree(d); return LLD_ERR_HIP; }
+  m->d_ext = d; m->ext_bytes = B.size;
+  B.bind(nullptr, d);
+  MapExt& X = m->X;
+  X.p_nobs = B.dev(pnobs); X.p_idx = B.dev(pidx); X.idx_pool = B.dev(ipool); X.k_oct = B.dev(koct); X.k_dep = B.dev(kdep); X.oct_pool = B.dev(opool);
+  X.dep_pool = B.dev(dpool); X.k_thd = B.dev(kthd);
+  m->idx.d_row = X.p_idx; m->idx.d_pool = X.idx_pool; m->koct.d_row = X.k_oct; m->koct.d_pool = X.oct_pool; m->kdep.d_row = X.k_dep; m->kdep.d_pool = X.dep_pool;
   return LLD_OK;
 }
 
@@ -538,7 +824,7 @@ int lld_map_create(lld_ctx* ctx, const lld_map_limits* L, lld_map** out) {
   m->ctx = ctx; m->lim = *L;
   const size_t nk = L->max_keyframes, np = L->max_points, nl = std::max(L->max_lines, 1), dim = L->line_dim, nlp = L->max_local_points, nll = std::max(L->max_local_lines, 1);
   m->obs.init((int)np, L->max_observations); m->child.init((int)nk, L->max_children); m->kpt.init((int)nk, L->max_kf_points); m->kln.init((int)nk, L->max_kf_lines);
-  m->stamp_pt.assign(np, 0); m->stamp_kf.assign(nk, 0); m->stamp_ln.assign(L->max_lines, 0);
+  m->stamp_pt.assign(np, 0); m->stamp_kf.assign(nk, 0); m->stamp_ln.assign(L->max_lines, 0); m->kf_set.assign(nk, 0);
   UploadBlock B;
   const auto ppos = B.take<float>(np, 3), pnrm = B.take<float>(np, 3), pmind = B.take<float>(np), pmaxd = B.take<float>(np); const auto pdesc = B.take<uint32_t>(np, 8);
   const auto pstate = B.take<uint8_t>(np); const auto pobs = B.take<int2>(np); const auto opool = B.take<int32_t>(m->obs.mirror.size());
@@ -587,6 +873,7 @@ void lld_map_destroy(lld_map* m) {
   (void)hipSetDevice(m->ctx->device);
   (void)hipStreamSynchronize(m->ctx->stream);
   if (m->d_tables) (void)hipFree(m->d_tables);
+  if (m->d_ext) (void)hipFree(m->d_ext);
   if (m->d_up) (void)hipFree(m->d_up);
   if (m->h_up) (void)hipHostFree(m->h_up);
   if (m->h_down) (void)hipHostFree(m->h_down);
@@ -632,12 +919,107 @@ int lld_map_set_observations(lld_map* m, int32_t n, const int32_t* slot, const i
   LLD_HIP_TRY(hipSetDevice(m->ctx->device));
   UploadBlock B;
   m->obs.reserve(B, P);
+  const auto drop = B.take<int32_t>(m->d_ext ? n : 0);              // with the culling tables: these rows carry no keypoint indices any more
   int st = up_begin(m, B); if (st) return st;
   m->obs.commit(B, P, n, slot, start, kf_slot);
+  if (m->d_ext) {
+    B.stage(drop, slot);
+    for (int i = 0; i < n; i++) { m->idx.live -= m->idx.len[slot[i]]; m->idx.len[slot[i]] = 0; }
+  }
   st = up_submit(m, B);
   if (!st) st = m->obs.launch(m->ctx->stream, B, P);
+  if (!st && m->d_ext) {
+    hipLaunchKernelGGL(map_drop_rows_kernel, dim3((n + 255) / 256), dim3(256), 0, m->ctx->stream, n, B.dev(drop), m->X.p_idx);
+    if (hipGetLastError() != hipSuccess) st = LLD_ERR_HIP;
+  }
   if (st) m->poisoned = true;                                        // the host's rows are ahead of the device's
   return st;
+}
+
+int lld_map_set_observations_indexed(lld_map* m, int32_t n, const int32_t* slot, const int32_t* start, const int32_t* kf_slot, const int32_t* kp_index,
+                                     const int32_t* n_obs) {
+  if (!m || n < 0) return LLD_ERR_INVALID;
+  if (m->poisoned) return LLD_ERR_HIP;
+  if (n == 0) return LLD_OK;
+  if (!slot || !n_obs || !starts_ok(n, start) || (start[n] > 0 && (!kf_slot || !kp_index))) return LLD_ERR_INVALID;
+  if (!slots_ok(m->stamp_pt, m->epoch, n, slot) || !entries_in(kf_slot, start[n], 0, m->lim.max_keyframes)) return LLD_ERR_INVALID;
+  for (int i = 0; i < start[n]; i++) if (kp_index[i] < 0) return LLD_ERR_INVALID;
+  for (int i = 0; i < n; i++) if (n_obs[i] < 0) return LLD_ERR_INVALID;
+  PoolPlan P, Pi;
+  if (!m->obs.plan(n, slot, start, P)) return LLD_ERR_UNSUPPORTED;
+  // every limit is held before anything is allocated: a fresh index pool is empty, so the call's own entries are its live total
+  if (m->d_ext ? !m->idx.plan(n, slot, start, Pi) : start[n] > m->lim.max_observations) return LLD_ERR_UNSUPPORTED;
+  LLD_HIP_TRY(hipSetDevice(m->ctx->device));
+  const bool fresh = !m->d_ext;
+  int st = ext_ensure(m); if (st) return st;
+  if (fresh && !m->idx.plan(n, slot, start, Pi)) return LLD_ERR_UNSUPPORTED;     // (cannot happen: checked above)
+  UploadBlock B;
+  m->obs.reserve(B, P); m->idx.reserve(B, Pi);
+  const auto s = B.take<int32_t>(n), no = B.take<int32_t>(n);
+  st = up_begin(m, B); if (st) return st;
+  m->obs.commit(B, P, n, slot, start, kf_slot); m->idx.commit(B, Pi, n, slot, start, kp_index);
+  B.stage(s, slot); B.stage(no, n_obs);
+  st = up_submit(m, B);
+  hipStream_t stream = m->ctx->stream;
+  if (!st) st = m->obs.launch(stream, B, P);
+  if (!st) st = m->idx.launch(stream, B, Pi);
+  if (!st) {
+    hipLaunchKernelGGL(map_scatter_kernel, dim3((n + 255) / 256), dim3(256), 0, stream, n, B.dev(s), B.dev(no), m->X.p_nobs);
+    if (hipGetLastError() != hipSuccess) st = LLD_ERR_HIP;
+  }
+  if (st) m->poisoned = true;                                        // the host's rows are ahead of the device's
+  return st;
+}
+
+int lld_map_set_keyframe_keypoints(lld_map* m, int32_t n, const int32_t* slot, const int32_t* start, const int32_t* octave, const float* depth, const float* th_depth) {
+  if (!m || n < 0) return LLD_ERR_INVALID;
+  if (m->poisoned) return LLD_ERR_HIP;
+  if (n == 0) return LLD_OK;
+  if (!slot || !th_depth || !starts_ok(n, start) || (start[n] > 0 && (!octave || !depth))) return LLD_ERR_INVALID;
+  if (!slots_ok(m->stamp_kf, m->epoch, n, slot)) return LLD_ERR_INVALID;
+  for (int i = 0; i < n; i++) if (!m->kf_set[slot[i]] || start[i + 1] - start[i] != m->kpt.len[slot[i]]) return LLD_ERR_INVALID;   // one entry per keypoint of a keyframe the map holds
+  PoolPlan Po, Pd;
+  // as above: the limits first, the allocation behind them
+  if (m->d_ext ? (!m->koct.plan(n, slot, start, Po) || !m->kdep.plan(n, slot, start, Pd)) : start[n] > m->lim.max_kf_points) return LLD_ERR_UNSUPPORTED;
+  LLD_HIP_TRY(hipSetDevice(m->ctx->device));
+  const bool fresh = !m->d_ext;
+  int st = ext_ensure(m); if (st) return st;
+  if (fresh && (!m->koct.plan(n, slot, start, Po) || !m->kdep.plan(n, slot, start, Pd))) return LLD_ERR_UNSUPPORTED;      // (cannot happen: checked above)
+  UploadBlock B;
+  m->koct.reserve(B, Po); m->kdep.reserve(B, Pd);
+  const auto s = B.take<int32_t>(n); const auto thd = B.take<float>(n);
+  st = up_begin(m, B); if (st) return st;
+  m->koct.commit(B, Po, n, slot, start, octave); m->kdep.commit(B, Pd, n, slot, start, reinterpret_cast<const int32_t*>(depth));    // a float travels as its bit pattern
+  B.stage(s, slot); B.stage(thd, th_depth);
+  st = up_submit(m, B);
+  hipStream_t stream = m->ctx->stream;
+  if (!st) st = m->koct.launch(stream, B, Po);
+  if (!st) st = m->kdep.launch(stream, B, Pd);
+  if (!st) {
+    hipLaunchKernelGGL(map_scatter_kernel, dim3((n + 255) / 256), dim3(256), 0, stream, n, B.dev(s), reinterpret_cast<const int32_t*>(B.dev(thd)),
+                       reinterpret_cast<int32_t*>(m->X.k_thd));
+    if (hipGetLastError() != hipSuccess) st = LLD_ERR_HIP;
+  }
+  if (st) m->poisoned = true;
+  return st;
+}
+
+int lld_map_set_covisibles(lld_map* m, int32_t n, const int32_t* slot, const int32_t* cov_start, const int32_t* cov) {
+  if (!m || n < 0) return LLD_ERR_INVALID;
+  if (m->poisoned) return LLD_ERR_HIP;
+  if (n == 0) return LLD_OK;
+  if (!slot || !starts_ok(n, cov_start) || (cov_start[n] > 0 && !cov)) return LLD_ERR_INVALID;
+  if (!slots_ok(m->stamp_kf, m->epoch, n, slot) || !entries_in(cov, cov_start[n], 0, m->lim.max_keyframes)) return LLD_ERR_INVALID;
+  for (int i = 0; i < n; i++) if (!m->kf_set[slot[i]]) return LLD_ERR_INVALID;
+  LLD_HIP_TRY(hipSetDevice(m->ctx->device));
+  UploadBlock B;
+  const auto s = B.take<int32_t>(n), cs = B.take<int32_t>((size_t)n + 1), cv = B.take<int32_t>(cov_start[n]);
+  int st = up_begin(m, B); if (st) return st;
+  B.stage(s, slot); B.stage(cs, cov_start); B.stage(cv, cov);
+  st = up_submit(m, B); if (st) return st;
+  hipLaunchKernelGGL(map_set_cov_kernel, dim3((n + 255) / 256), dim3(256), 0, m->ctx->stream, m->D, n, B.dev(s), B.dev(cs), B.dev(cv));
+  LLD_HIP_TRY(hipGetLastError());
+  return LLD_OK;
 }
 
 int lld_map_set_keyframes(lld_map* m, int32_t n, const int32_t* slot, const uint64_t* order_key, const uint8_t* bad, const int32_t* parent, const int32_t* cov_start,
@@ -664,6 +1046,7 @@ int lld_map_set_keyframes(lld_map* m, int32_t n, const int32_t* slot, const uint
   int st = up_begin(m, B); if (st) return st;
   B.stage(s, slot); B.stage(key, reinterpret_cast<const u64*>(order_key)); B.stage(b, bad); B.stage(par, parent); B.stage(cs, cov_start); B.stage(cv, cov);
   m->child.commit(B, Pc, n, slot, child_start, child); m->kpt.commit(B, Pp, n, slot, point_start, point); m->kln.commit(B, Pl, n, slot, line_start, line);
+  for (int i = 0; i < n; i++) m->kf_set[slot[i]] = 1;
   st = up_submit(m, B);
   hipStream_t stream = m->ctx->stream;
   if (!st) {
@@ -741,6 +1124,159 @@ int lld_frame_local_map_download(lld_frame* f, lld_map* m, lld_local_map_result*
   if (r->local_keyframes) std::memcpy(r->local_keyframes, m->h_down + m->o_lkf, (size_t)std::min(std::max(r->n_local_keyframes, 0), kLkfCap) * 4);
   if (r->local_points && kf_ok && r->n_local_points <= m->lim.max_local_points) std::memcpy(r->local_points, m->h_down + m->o_lpts, (size_t)r->n_local_points * 4);
   if (r->local_lines && kf_ok && r->n_local_lines <= m->lim.max_local_lines) std::memcpy(r->local_lines, m->h_down + m->o_llns, (size_t)r->n_local_lines * 4);
+  return LLD_OK;
+}
+
+int lld_map_download_links(lld_map* m, int32_t n, const int32_t* slot, int32_t* parent, int32_t* n_cov, int32_t* cov, int32_t* child_start, int32_t child_capacity,
+                           int32_t* child) {
+  if (!m || n < 0 || child_capacity < 0) return LLD_ERR_INVALID;
+  if (m->poisoned) return LLD_ERR_HIP;
+  if (n == 0) return LLD_OK;
+  if (!slot || !parent || !n_cov || !cov || !child_start || (child_capacity > 0 && !child)) return LLD_ERR_INVALID;
+  for (int i = 0; i < n; i++) if (slot[i] < 0 || slot[i] >= m->lim.max_keyframes || !m->kf_set[slot[i]]) return LLD_ERR_INVALID;
+  // the child rows' lengths are the host's (every update before this call is queued before its kernel); the contents come from the device
+  std::vector<int32_t> start((size_t)n + 1, 0);
+  for (int i = 0; i < n; i++) start[i + 1] = start[i] + m->child.len[slot[i]];
+  std::memcpy(child_start, start.data(), ((size_t)n + 1) * 4);
+  if (start[n] > child_capacity) return LLD_ERR_INVALID;              // only child_start is written
+  lld_ctx* ctx = m->ctx;
+  LLD_HIP_TRY(hipSetDevice(ctx->device));
+  UploadBlock B;
+  const auto i_s = B.take<int32_t>(n), i_st = B.take<int32_t>((size_t)n + 1);
+  B.end_upload();
+  const size_t out_off = B.size;
+  const auto r_par = B.take<int32_t>(n), r_nc = B.take<int32_t>(n), r_cov = B.take<int32_t>(n, 10), r_nch = B.take<int32_t>(n), r_ch = B.take<int32_t>((size_t)start[n]);
+  int st;
+  void* hb; st = lld_ctx_pinned(ctx, B.size, &hb); if (st) return st;
+  void* db; st = lld_ctx_scratch(ctx, B.size + 256, &db); if (st) return st;
+  B.bind((char*)hb, (char*)db);
+  B.stage(i_s, slot); B.stage(i_st, start.data());
+  hipStream_t sm = ctx->stream;
+  LLD_HIP_TRY(hipMemcpyAsync(B.d, B.h, B.up_bytes, hipMemcpyHostToDevice, sm));
+  hipLaunchKernelGGL(map_links_kernel, dim3(n), dim3(64), 0, sm, m->D, n, B.dev(i_s), B.dev(i_st), B.dev(r_par), B.dev(r_nc), B.dev(r_cov), B.dev(r_nch), B.dev(r_ch));
+  LLD_HIP_TRY(hipGetLastError());
+  LLD_HIP_TRY(hipMemcpyAsync(B.h + out_off, B.d + out_off, B.size - out_off, hipMemcpyDeviceToHost, sm));
+  LLD_HIP_TRY(hipStreamSynchronize(sm));
+  const int32_t* nch = B.host(r_nch);
+  for (int i = 0; i < n; i++) if (nch[i] != start[i + 1] - start[i]) return LLD_ERR_HIP;       // the device's rows are not the host's: never with a sound map
+  std::memcpy(parent, B.host(r_par), (size_t)n * 4); std::memcpy(n_cov, B.host(r_nc), (size_t)n * 4); std::memcpy(cov, B.host(r_cov), (size_t)n * 40);
+  if (start[n]) std::memcpy(child, B.host(r_ch), (size_t)start[n] * 4);
+  return LLD_OK;
+}
+
+int lld_map_covisibility(lld_map* m, const lld_map_covisibility_in* in, lld_map_covisibility_out* out) {
+  if (!m || !in || !out) return LLD_ERR_INVALID;
+  lld_covisibility_out* L = &out->lists;
+  const int32_t nq = in->n_queries;
+  const bool conn = (in->flags & LLD_COVIS_CONNECTIONS) != 0, cull = (in->flags & LLD_COVIS_CULLING) != 0;
+  if (nq < 0) return LLD_ERR_INVALID;
+  if ((in->flags & ~(uint32_t)(LLD_COVIS_CONNECTIONS | LLD_COVIS_CULLING | LLD_MAP_COVIS_WRITE_COV)) || !(conn || cull)) return LLD_ERR_INVALID;
+  if ((in->flags & LLD_MAP_COVIS_WRITE_COV) && !conn) return LLD_ERR_INVALID;
+  if (m->poisoned) return LLD_ERR_HIP;
+  if (nq == 0) return LLD_OK;
+  if (!in->kf_slot || !out->status) return LLD_ERR_INVALID;
+  if (cull && (!L->n_mps || !L->n_redundant || !L->redundant)) return LLD_ERR_INVALID;
+  if (conn) {
+    if (L->conn_capacity < 0 || L->ordered_capacity < 0) return LLD_ERR_INVALID;
+    if (!L->conn_start || !L->ordered_start || !L->n_max || !L->kf_max || !L->updated) return LLD_ERR_INVALID;
+    if (L->conn_capacity > 0 && (!L->conn_kf || !L->conn_weight)) return LLD_ERR_INVALID;
+    if (L->ordered_capacity > 0 && (!L->ordered_kf || !L->ordered_weight)) return LLD_ERR_INVALID;
+  }
+  for (int q = 0; q < nq; q++) if (in->kf_slot[q] < 0 || in->kf_slot[q] >= m->lim.max_keyframes || !m->kf_set[in->kf_slot[q]]) return LLD_ERR_INVALID;
+  lld_ctx* ctx = m->ctx;
+  LLD_HIP_TRY(hipSetDevice(ctx->device));
+
+  // the staging range of a query: it cannot meet more keyframes than its points hold observations, nor more than the table answers for
+  // (the host's rows are the device's: every update before this call is queued before its kernels)
+  std::vector<int32_t> stage_off;
+  long long stage_total = 0;
+  if (conn) {
+    stage_off.resize((size_t)nq + 1);
+    for (int q = 0; q < nq; q++) {
+      const int s = in->kf_slot[q];
+      const int32_t* row = m->kpt.mirror.data() + m->kpt.off[s];
+      long long b = 0;
+      for (int j = 0; j < m->kpt.len[s] && b < kCovMax; j++) if (row[j] >= 0) b += m->obs.len[row[j]];
+      stage_off[q] = (int32_t)stage_total;
+      stage_total += std::min<long long>(b, kCovMax);
+    }
+    if (stage_total > 0x7fffffffLL) return LLD_ERR_UNSUPPORTED;
+    stage_off[nq] = (int32_t)stage_total;
+  }
+  const int32_t cap_conn = conn ? (int32_t)std::min<long long>(L->conn_capacity, stage_total) : 0;
+  const int32_t cap_ord = conn ? (int32_t)std::min<long long>(L->ordered_capacity, stage_total) : 0;
+
+  UploadBlock B;
+  const auto i_q = B.take<int32_t>(nq), i_so = B.take<int32_t>(conn ? (size_t)nq + 1 : 0);
+  B.end_upload();
+  const size_t out_off = B.size;
+  const auto r_cs = B.take<int32_t>(conn ? (size_t)nq + 1 : 0), r_rs = B.take<int32_t>(conn ? (size_t)nq + 1 : 0), r_tot = B.take<int32_t>(conn ? 2 : 0);
+  const auto r_nm = B.take<int32_t>(conn ? nq : 0), r_km = B.take<int32_t>(conn ? nq : 0); const auto r_up = B.take<uint8_t>(conn ? nq : 0), r_st = B.take<uint8_t>(nq);
+  const auto r_mp = B.take<int32_t>(cull ? nq : 0), r_rd = B.take<int32_t>(cull ? nq : 0); const auto r_rf = B.take<uint8_t>(cull ? nq : 0);
+  const auto r_ck = B.take<int32_t>(cap_conn), r_cw = B.take<int32_t>(cap_conn), r_rk = B.take<int32_t>(cap_ord), r_rw = B.take<int32_t>(cap_ord);
+  const size_t out_bytes = B.size - out_off;
+  const auto t_cc = B.take<int32_t>(conn ? nq : 0), t_co = B.take<int32_t>(conn ? nq : 0);
+  const auto t_sl = B.take<int32_t>((size_t)stage_total), t_sc = B.take<int32_t>((size_t)stage_total), t_kf = B.take<int32_t>((size_t)stage_total),
+             t_w = B.take<int32_t>((size_t)stage_total);
+  const auto t_key = B.take<u64>((size_t)stage_total);
+  int st;
+  void* hb; st = lld_ctx_pinned(ctx, out_off + out_bytes, &hb); if (st) return st;
+  void* db; st = lld_ctx_scratch(ctx, B.size + 256, &db); if (st) return st;
+  B.bind((char*)hb, (char*)db);
+  B.stage(i_q, in->kf_slot);
+  if (conn) B.stage(i_so, stage_off.data());
+
+  CovArgs A;
+  A.query = B.dev(i_q); A.stage_off = B.dev(i_so);
+  A.n_queries = nq; A.monocular = in->monocular ? 1 : 0; A.th = in->params.th; A.th_obs = in->params.th_obs; A.has_ext = m->d_ext ? 1 : 0;
+  A.flags = in->flags; A.ratio = in->params.redundant_ratio;
+  A.st_slot = B.dev(t_sl); A.st_cnt = B.dev(t_sc); A.st_kf = B.dev(t_kf); A.st_w = B.dev(t_w); A.st_key = B.dev(t_key);
+  A.cnt_conn = B.dev(t_cc); A.cnt_ord = B.dev(t_co);
+  A.n_max = B.dev(r_nm); A.kf_max = B.dev(r_km); A.updated = B.dev(r_up); A.status = B.dev(r_st);
+  A.n_mps = B.dev(r_mp); A.n_red = B.dev(r_rd); A.redundant = B.dev(r_rf);
+  A.cap_conn = cap_conn; A.cap_ord = cap_ord;
+  A.conn_start = B.dev(r_cs); A.ord_start = B.dev(r_rs); A.totals = B.dev(r_tot);
+  A.conn_kf = B.dev(r_ck); A.conn_w = B.dev(r_cw); A.ord_kf = B.dev(r_rk); A.ord_w = B.dev(r_rw);
+
+  if (conn && !m->cov_lds_set) {
+    LLD_HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(&map_covis_query_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)kCovLds));
+    m->cov_lds_set = true;
+  }
+  hipStream_t sm = ctx->stream;
+  struct Events {                                                      // destroyed on every way out
+    hipEvent_t e[4] = {nullptr, nullptr, nullptr, nullptr};
+    ~Events() { for (int k = 0; k < 4; ++k) if (e[k]) (void)hipEventDestroy(e[k]); }
+  } events;
+  hipEvent_t* ev = events.e;
+  const bool timed = L->phase_ms != nullptr;
+  if (timed) for (int k = 0; k < 4; ++k) LLD_HIP_TRY(hipEventCreate(&ev[k]));
+  if (timed) LLD_HIP_TRY(hipEventRecord(ev[0], sm));
+  LLD_HIP_TRY(hipMemcpyAsync(B.d, B.h, B.up_bytes, hipMemcpyHostToDevice, sm));
+  if (timed) LLD_HIP_TRY(hipEventRecord(ev[1], sm));
+  hipLaunchKernelGGL(map_covis_query_kernel, dim3(nq), dim3(kCovThreads), conn ? kCovLds : 0, sm, m->D, m->X, A);
+  if (conn) hipLaunchKernelGGL(map_covis_pack_kernel, dim3(nq), dim3(kCovThreads), 0, sm, A);
+  LLD_HIP_TRY(hipGetLastError());
+  if (timed) LLD_HIP_TRY(hipEventRecord(ev[2], sm));
+  LLD_HIP_TRY(hipMemcpyAsync(B.h + out_off, B.d + out_off, out_bytes, hipMemcpyDeviceToHost, sm));
+  if (timed) LLD_HIP_TRY(hipEventRecord(ev[3], sm));
+  LLD_HIP_TRY(hipStreamSynchronize(sm));
+  if (timed) {
+    for (int k = 0; k < 3; ++k) LLD_HIP_TRY(hipEventElapsedTime(&L->phase_ms[k], ev[k], ev[k + 1]));
+  }
+
+  if (conn) {
+    const int32_t* tot = B.host(r_tot);
+    L->n_conn = tot[0]; L->n_ordered = tot[1];
+    if (tot[0] > L->conn_capacity || tot[1] > L->ordered_capacity) return LLD_ERR_INVALID;
+    std::memcpy(L->conn_start, B.host(r_cs), (size_t)(nq + 1) * 4); std::memcpy(L->ordered_start, B.host(r_rs), (size_t)(nq + 1) * 4);
+    std::memcpy(L->n_max, B.host(r_nm), (size_t)nq * 4); std::memcpy(L->kf_max, B.host(r_km), (size_t)nq * 4); std::memcpy(L->updated, B.host(r_up), (size_t)nq);
+    if (tot[0]) { std::memcpy(L->conn_kf, B.host(r_ck), (size_t)tot[0] * 4); std::memcpy(L->conn_weight, B.host(r_cw), (size_t)tot[0] * 4); }
+    if (tot[1]) { std::memcpy(L->ordered_kf, B.host(r_rk), (size_t)tot[1] * 4); std::memcpy(L->ordered_weight, B.host(r_rw), (size_t)tot[1] * 4); }
+  }
+  if (cull) {
+    std::memcpy(L->n_mps, B.host(r_mp), (size_t)nq * 4); std::memcpy(L->n_redundant, B.host(r_rd), (size_t)nq * 4); std::memcpy(L->redundant, B.host(r_rf), (size_t)nq);
+  }
+  std::memcpy(out->status, B.host(r_st), (size_t)nq);
   return LLD_OK;
 }
 

@@ -39,6 +39,13 @@ class DeviceMap:
         f("map_set_keyframes").restype = C.c_int
         f("map_set_lines").argtypes = [C.c_void_p, C.c_int32, c_int32_p, c_double_p, c_double_p, c_double_p, c_double_p, c_float_p, c_uint8_p]
         f("map_set_lines").restype = C.c_int
+        f("map_set_observations_indexed").argtypes = [C.c_void_p, C.c_int32] + [c_int32_p] * 5; f("map_set_observations_indexed").restype = C.c_int
+        f("map_set_keyframe_keypoints").argtypes = [C.c_void_p, C.c_int32, c_int32_p, c_int32_p, c_int32_p, c_float_p, c_float_p]
+        f("map_set_keyframe_keypoints").restype = C.c_int
+        f("map_set_covisibles").argtypes = [C.c_void_p, C.c_int32, c_int32_p, c_int32_p, c_int32_p]; f("map_set_covisibles").restype = C.c_int
+        f("map_covisibility").argtypes = [C.c_void_p, C.POINTER(abi.MapCovisibilityIn), C.POINTER(abi.MapCovisibilityOut)]
+        f("map_covisibility").restype = C.c_int
+        f("map_download_links").argtypes = [C.c_void_p, C.c_int32] + [c_int32_p] * 5 + [C.c_int32, c_int32_p]; f("map_download_links").restype = C.c_int
         h = C.c_void_p()
         self.handle = None
         self._check(f("map_create")(ctx.handle, C.byref(self.limits), C.byref(h)), "lld_map_create")
@@ -87,6 +94,99 @@ class DeviceMap:
         for st, fl in lists:
             k.append(self._p(st, np.int32, c_int32_p)); k.append(self._p(fl, np.int32, c_int32_p))
         self._check(self.lib.fn("map_set_keyframes")(self.handle, len(k[0][0]), *[p for _, p in k]), "lld_map_set_keyframes")
+
+    def set_observations_indexed(self, slot, rows=None, n_obs=None, start=None, kf_slot=None, kp_index=None):
+        """rows: per entry of `slot` one list of (keyframe slot, keypoint index in that keyframe); or the CSR arrays themselves.
+        n_obs: MapPoint::Observations() per point (the stereo-weighted count)."""
+        if rows is not None:
+            start, kf_slot = csr([[o[0] for o in r] for r in rows])
+            _, kp_index = csr([[o[1] for o in r] for r in rows])
+        k = [self._p(slot, np.int32, c_int32_p), self._p(start, np.int32, c_int32_p), self._p(kf_slot, np.int32, c_int32_p),
+             self._p(kp_index, np.int32, c_int32_p), self._p(n_obs, np.int32, c_int32_p)]
+        self._check(self.lib.fn("map_set_observations_indexed")(self.handle, len(k[0][0]), *[p for _, p in k]), "lld_map_set_observations_indexed")
+
+    def set_keyframe_keypoints(self, slot, octave, depth, th_depth):
+        """octave / depth: one list per keyframe with one entry per keypoint, or (start, flat) pairs with the same start; th_depth per keyframe."""
+        st, oc = octave if isinstance(octave, tuple) else csr(octave)
+        _, dp = depth if isinstance(depth, tuple) else csr(depth, np.float32)
+        k = [self._p(slot, np.int32, c_int32_p), self._p(st, np.int32, c_int32_p), self._p(oc, np.int32, c_int32_p), self._p(dp, np.float32, c_float_p),
+             self._p(th_depth, np.float32, c_float_p)]
+        self._check(self.lib.fn("map_set_keyframe_keypoints")(self.handle, len(k[0][0]), *[p for _, p in k]), "lld_map_set_keyframe_keypoints")
+
+    def set_covisibles(self, slot, cov):
+        """cov: one list per keyframe (GetBestCovisibilityKeyFrames(10) in its order), or a (start, flat) pair.  Only the cov rows change."""
+        st, fl = cov if isinstance(cov, tuple) else csr(cov)
+        k = [self._p(slot, np.int32, c_int32_p), self._p(st, np.int32, c_int32_p), self._p(fl, np.int32, c_int32_p)]
+        self._check(self.lib.fn("map_set_covisibles")(self.handle, len(k[0][0]), *[p for _, p in k]), "lld_map_set_covisibles")
+
+    def links(self, kf_slots):
+        """lld_map_download_links: (parent [n], cov: one list per keyframe as the device holds it, child: one list per keyframe in the row's order)."""
+        s = np.ascontiguousarray(kf_slots, np.int32); n = len(s)
+        parent = np.zeros(n, np.int32); ncov = np.zeros(n, np.int32); cov = np.zeros((n, 10), np.int32); start = np.zeros(n + 1, np.int32)
+        p = lambda a: a.ctypes.data_as(c_int32_p)
+        fn = self.lib.fn("map_download_links")
+        st = fn(self.handle, n, p(s), p(parent), p(ncov), p(cov), p(start), 0, None)
+        child = np.zeros(max(int(start[-1]), 1), np.int32)
+        if st == abi.LLD_ERR_INVALID and start[-1] > 0:
+            st = fn(self.handle, n, p(s), p(parent), p(ncov), p(cov), p(start), int(start[-1]), p(child))
+        self._check(st, "lld_map_download_links")
+        return parent, [cov[i, :ncov[i]].tolist() for i in range(n)], [child[start[i]:start[i + 1]].tolist() for i in range(n)]
+
+    def covisibility(self, kf_slots, connections=True, culling=False, write_cov=False, monocular=False, th=None, th_obs=None, redundant_ratio=None,
+                     conn_capacity=None, ordered_capacity=None, phase_ms=None, flags=None):
+        """lld_map_covisibility for the keyframes kf_slots.  Returns a dict of arrays: conn_start, conn_kf, conn_weight, ordered_start, ordered_kf,
+        ordered_weight, n_max, kf_max, updated (connections); n_mps, n_redundant, redundant (culling); status.  Every keyframe is a slot.
+        Without capacities the call is made with a guess and repeated once with the totals the library reports; with them a short one raises
+        (the error carries status, n_conn and n_ordered).  flags overrides the three booleans."""
+        kf_slots = np.ascontiguousarray(kf_slots, np.int32)
+        nq = len(kf_slots)
+        if flags is None:
+            flags = (1 if connections else 0) | (2 if culling else 0) | (abi.MAP_COVIS_WRITE_COV if write_cov else 0)
+        a = abi.MapCovisibilityIn()
+        a.n_queries, a.monocular, a.flags = nq, 1 if monocular else 0, int(flags)
+        self.lib.fn("covisibility_params_default")(C.byref(a.params))
+        if th is not None: a.params.th = int(th)
+        if th_obs is not None: a.params.th_obs = int(th_obs)
+        if redundant_ratio is not None: a.params.redundant_ratio = float(redundant_ratio)
+        a.kf_slot = kf_slots.ctypes.data_as(c_int32_p)
+        retry = conn_capacity is None and ordered_capacity is None
+        caps = [64 * nq if conn_capacity is None else int(conn_capacity), 64 * nq if ordered_capacity is None else int(ordered_capacity)]
+        while True:
+            r = dict(conn_start=np.zeros(nq + 1, np.int32), conn_kf=np.zeros(max(caps[0], 1), np.int32), conn_weight=np.zeros(max(caps[0], 1), np.int32),
+                     ordered_start=np.zeros(nq + 1, np.int32), ordered_kf=np.zeros(max(caps[1], 1), np.int32), ordered_weight=np.zeros(max(caps[1], 1), np.int32),
+                     n_max=np.zeros(nq, np.int32), kf_max=np.zeros(nq, np.int32), updated=np.zeros(nq, np.uint8),
+                     n_mps=np.zeros(nq, np.int32), n_redundant=np.zeros(nq, np.int32), redundant=np.zeros(nq, np.uint8), status=np.zeros(nq, np.uint8))
+            o = abi.MapCovisibilityOut()
+            o.lists.conn_capacity, o.lists.ordered_capacity = caps
+            for name in ("conn_start", "conn_kf", "conn_weight", "ordered_start", "ordered_kf", "ordered_weight", "n_max", "kf_max", "n_mps", "n_redundant"):
+                setattr(o.lists, name, r[name].ctypes.data_as(c_int32_p))
+            o.lists.updated = r["updated"].ctypes.data_as(c_uint8_p); o.lists.redundant = r["redundant"].ctypes.data_as(c_uint8_p)
+            o.status = r["status"].ctypes.data_as(c_uint8_p)
+            if phase_ms is not None:
+                assert phase_ms.dtype == np.float32 and phase_ms.size >= 3 and phase_ms.flags.c_contiguous
+                o.lists.phase_ms = phase_ms.ctypes.data_as(c_float_p)
+            o.lists.n_conn = o.lists.n_ordered = -1
+            st = self.lib.fn("map_covisibility")(self.handle, C.byref(a), C.byref(o))
+            short = st == abi.LLD_ERR_INVALID and o.lists.n_conn >= 0
+            if short and retry:
+                caps, retry = [o.lists.n_conn, o.lists.n_ordered], False
+                continue
+            if st != abi.LLD_OK:
+                err = RuntimeError(f"lld_map_covisibility failed: {self.lib.fn('status_string')(st).decode()}")
+                err.status, err.n_conn, err.n_ordered = st, (o.lists.n_conn if short else None), (o.lists.n_ordered if short else None)
+                raise err
+            break
+        if flags & 1:
+            nc, no = (o.lists.n_conn, o.lists.n_ordered) if nq else (0, 0)
+            r["conn_kf"] = r["conn_kf"][:nc]; r["conn_weight"] = r["conn_weight"][:nc]
+            r["ordered_kf"] = r["ordered_kf"][:no]; r["ordered_weight"] = r["ordered_weight"][:no]
+        else:
+            for name in ("conn_start", "conn_kf", "conn_weight", "ordered_start", "ordered_kf", "ordered_weight", "n_max", "kf_max", "updated"):
+                del r[name]
+        if not flags & 2:
+            for name in ("n_mps", "n_redundant", "redundant"):
+                del r[name]
+        return r
 
     def set_lines(self, slot, x0, dir, x1, x2, desc, bad):
         k = [self._p(slot, np.int32, c_int32_p), self._p(x0, np.float64, c_double_p), self._p(dir, np.float64, c_double_p), self._p(x1, np.float64, c_double_p),
