@@ -2606,7 +2606,7 @@ typedef struct {
 } lld_local_map_result;
 int  lld_frame_local_map_download(lld_frame* frame, lld_map* map, lld_local_map_result* out);
 
-/* ------------------------------------------------------------------ covisibility on the resident map (lld_map.hip)
+/* ------------------------------------------------------------------ covisibility on the resident map (lld_map_covis.hip)
  * KeyFrame::UpdateConnections (src/KeyFrame.cc:312-402) and the redundancy count of LocalMapping::KeyFrameCulling (src/LocalMapping.cc:646-694)
  * for a batch of keyframes, counted on the tables the map already holds: nothing of the map is gathered or uploaded, only the list of
  * query slots travels.  The rules are those of lld_covisibility above, restated on the map's tables; every result is an integer.

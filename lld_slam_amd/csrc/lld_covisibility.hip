@@ -7,17 +7,20 @@
 //                depend on the order).  Culling: the qualifying observations of an entry are summed over its group by lane
 //                shuffles, the two per-query sums over the wavefront, then one LDS atomic per wavefront.
 //                Finishing pass: the non-zero counters are compacted in slot order (ballot + prefix over the four wavefronts),
-//                the maximum is reduced on the key (weight, ~slot) so that the lowest slot wins, the counters >= th go out as
-//                64-bit keys (weight << 32 | slot), come back into the LDS the counters occupied, and a bitonic sort orders
-//                them; they are written in descending order.  Both lists go to a per-query staging range whose size the host
-//                bounds by min(n_kf, observations of the query's entries).
-//   covis_pack   one workgroup per query: the exclusive sums of the per-query counts give conn_start / ordered_start and the
-//                totals; if both totals fit the capacities the staged lists are copied to their packed places.
+//                which gives every connected keyframe its rank; rank rises with slot.  The maximum is reduced on the key
+//                (weight, ~rank) so that the lowest slot wins, the counters >= th go out as 64-bit keys (weight << 32 | rank), come
+//                back into the LDS the counters occupied, and a bitonic sort orders them; they are written in descending order.
+//                Both lists go to a per-query staging range whose size the host bounds by min(n_kf, observations of the query's entries).
+//   covis_pack   the library's one pack kernel, for this call and for lld_map_covisibility (lld_covis::pack_launch).  One workgroup per
+//                query: the exclusive sums of the per-query counts give conn_start / ordered_start and the totals; if both totals
+//                fit the capacities the staged lists are copied to their packed places, the ordered keyframes through their ranks.
 // No workgroup reads what another workgroup of the same kernel writes, so a query's result cannot depend on the batch.
+// From the staged lists onward the two calls share everything (lld_covis_lists.h); the host half of that is defined at the end of this file.
 #include <cmath>
 #include <vector>
 
 #include "lld_common.h"
+#include "lld_covis_lists.h"
 #include "lld_wave.h"
 
 namespace {
@@ -29,19 +32,15 @@ constexpr int kGroup = 16;                   // lanes per query entry
 constexpr int kGroups = kThreads / kGroup;
 
 typedef unsigned long long u64;
+using lld_covis::Lists;
+using lld_track::UploadBlock;
 
 struct CovisArgs {
   const int32_t* obs_start; const int32_t* obs_kf; const int32_t* obs_octave; const uint8_t* point_bad; const int32_t* point_nobs;
   const int32_t* query_kf; const int32_t* q_start; const int32_t* q_point; const int32_t* q_octave; const float* q_depth;
   const float* q_th_depth;
-  const int32_t* stage_off;                  // [n_queries+1] the staging range of each query
-  int32_t n_kf, n_queries, monocular, th, th_obs; uint32_t flags; double ratio;
-  int32_t* st_kf; int32_t* st_w; u64* st_key;                               // staging
-  int32_t* cnt_conn; int32_t* cnt_ord; int32_t* n_max; int32_t* kf_max; uint8_t* updated;
-  int32_t* n_mps; int32_t* n_red; uint8_t* redundant;
-  int32_t cap_conn, cap_ord;
-  int32_t* conn_start; int32_t* ord_start; int32_t* totals;                 // packed outputs
-  int32_t* conn_kf; int32_t* conn_w; int32_t* ord_kf; int32_t* ord_w;
+  int32_t n_kf, monocular, th, th_obs; uint32_t flags; double ratio;
+  Lists L;
 };
 
 __global__ __launch_bounds__(kThreads) void covis_query(CovisArgs A) {
@@ -70,7 +69,7 @@ __global__ __launch_bounds__(kThreads) void covis_query(CovisArgs A) {
         bool walk = conn;
         if (cull) {
           const float depth = A.q_depth[e];
-          if (A.monocular || !(depth > th_depth || depth < 0.f)) {
+          if (lld_covis::depth_counts(A.monocular, depth, th_depth)) {
             if (gl == 0) my_mps++;
             if (A.point_nobs[p] > A.th_obs) { count_cull = true; walk = true; lvl = A.q_octave[e] + 1; }
           }
@@ -94,17 +93,14 @@ __global__ __launch_bounds__(kThreads) void covis_query(CovisArgs A) {
     lld_wave::sum_each(my_mps, my_red);
     if (lane == 0) { atomicAdd(&s_cull[0], my_mps); atomicAdd(&s_cull[1], my_red); }
     __syncthreads();
-    if (t == 0) {
-      const int nm = s_cull[0], nr = s_cull[1];
-      A.n_mps[q] = nm; A.n_red[q] = nr;
-      A.redundant[q] = ((double)nr > A.ratio * (double)nm) ? 1 : 0;          // nRedundantObservations > 0.9*nMPs: int against double
-    }
+    if (t == 0) lld_covis::publish_cull(A.L, q, s_cull[0], s_cull[1], A.ratio);
   }
   if (!conn) return;
   __syncthreads();
 
-  // ---- the non-zero counters in slot order, the maximum with its lowest slot, the counters >= th as keys
-  const size_t off = (size_t)A.stage_off[q];
+  // ---- the non-zero counters in slot order (their rank), the maximum with its lowest rank, the counters >= th as keys
+  const Lists& L = A.L;
+  const size_t off = (size_t)L.stage_off[q];
   const u64 below = lane == 0 ? 0ull : (~0ull >> (kWave - lane));
   int n_conn = 0, n_sel = 0;
   u64 best = 0;
@@ -123,14 +119,14 @@ __global__ __launch_bounds__(kThreads) void covis_query(CovisArgs A) {
       tz += a; ts += b;
     }
     if (nz) {
-      const size_t i = off + n_conn + wz + __popcll(bz & below);
-      A.st_kf[i] = slot; A.st_w[i] = w;
-      const u64 key = ((u64)(uint32_t)w << 32) | (uint32_t)(0xffffffffu - (uint32_t)slot);
+      const uint32_t rank = (uint32_t)(n_conn + wz + __popcll(bz & below));
+      L.st_kf[off + rank] = slot; L.st_w[off + rank] = w;
+      const u64 key = ((u64)(uint32_t)w << 32) | (0xffffffffu - rank);
       if (key > best) best = key;
+      if (sel) L.st_key[off + n_sel + ws + __popcll(bs & below)] = ((u64)(uint32_t)w << 32) | rank;
     }
-    if (sel) A.st_key[off + n_sel + ws + __popcll(bs & below)] = ((u64)(uint32_t)w << 32) | (uint32_t)slot;
     n_conn += tz; n_sel += ts;
-    __syncthreads();
+    __syncthreads();                         // (the last one also stands between the st_kf writes and lane 0's read of st_kf[off + rmax] below)
   }
   best = lld_wave::max(best);
   if (lane == 0) s_best[wv] = best;
@@ -139,23 +135,23 @@ __global__ __launch_bounds__(kThreads) void covis_query(CovisArgs A) {
 #pragma unroll
   for (int k = 1; k < kWaves; ++k) if (s_best[k] > best) best = s_best[k];
   const int nmax = n_conn ? (int)(best >> 32) : 0;
-  const int kfmax = n_conn ? (int)(0xffffffffu - (uint32_t)best) : -1;
+  const uint32_t rmax = 0xffffffffu - (uint32_t)best;
   const int n_ord = n_sel ? n_sel : (n_conn ? 1 : 0);
   if (t == 0) {
-    A.cnt_conn[q] = n_conn; A.cnt_ord[q] = n_ord; A.n_max[q] = nmax; A.kf_max[q] = kfmax; A.updated[q] = n_conn ? 1 : 0;
-    if (n_conn && !n_sel) A.st_key[off] = ((u64)(uint32_t)nmax << 32) | (uint32_t)kfmax;   // the fallback pair (nmax, pKFmax)
+    L.cnt_conn[q] = n_conn; L.cnt_ord[q] = n_ord; L.n_max[q] = nmax; L.kf_max[q] = n_conn ? L.st_kf[off + rmax] : -1; L.updated[q] = n_conn ? 1 : 0;
+    if (n_conn && !n_sel) L.st_key[off] = ((u64)(uint32_t)nmax << 32) | rmax;              // the fallback pair (nmax, pKFmax)
   }
   if (n_sel < 2) return;
-  // ---- descending (weight, slot): the staged keys come back into the LDS the counters held
+  // ---- descending (weight, rank), which is descending (weight, slot): the staged keys come back into the LDS the counters held
   int npad = 1;
   while (npad < n_sel) npad <<= 1;
-  for (int i = t; i < npad; i += kThreads) dyn[i] = i < n_sel ? A.st_key[off + i] : 0ull;   // a real key is above 0: its weight is >= 1
+  for (int i = t; i < npad; i += kThreads) dyn[i] = i < n_sel ? L.st_key[off + i] : 0ull;   // a real key is above 0: its weight is >= 1
   __syncthreads();
   lld_wave::bitonic_sort<kThreads>(dyn, npad);
-  for (int i = t; i < n_sel; i += kThreads) A.st_key[off + i] = dyn[npad - 1 - i];
+  for (int i = t; i < n_sel; i += kThreads) L.st_key[off + i] = dyn[npad - 1 - i];
 }
 
-__global__ __launch_bounds__(kThreads) void covis_pack(CovisArgs A) {
+__global__ __launch_bounds__(kThreads) void covis_pack(Lists A) {
   __shared__ int s_sum[4][kWaves];
   const int q = blockIdx.x, t = threadIdx.x, lane = t & (kWave - 1), wv = t / kWave;
   int v[4] = {0, 0, 0, 0};                   // conn before q, ordered before q, conn total, ordered total
@@ -179,11 +175,9 @@ __global__ __launch_bounds__(kThreads) void covis_pack(CovisArgs A) {
   for (int i = t; i < nc; i += kThreads) { A.conn_kf[v[0] + i] = A.st_kf[off + i]; A.conn_w[v[0] + i] = A.st_w[off + i]; }
   for (int i = t; i < no; i += kThreads) {
     const u64 key = A.st_key[off + i];
-    A.ord_kf[v[1] + i] = (int32_t)(uint32_t)key; A.ord_w[v[1] + i] = (int32_t)(key >> 32);
+    A.ord_kf[v[1] + i] = A.st_kf[off + (uint32_t)key]; A.ord_w[v[1] + i] = (int32_t)(key >> 32);
   }
 }
-
-inline size_t al(size_t b) { return (b + 255) & ~size_t(255); }
 
 bool csr_ok(int32_t n, int32_t total, const int32_t* start) {
   if (start[0] != 0 || start[n] != total) return false;
@@ -210,14 +204,9 @@ int lld_covisibility(lld_ctx* ctx, const lld_covisibility_in* in, lld_covisibili
   if (!in->obs_start || !in->query_kf || !in->q_start || (n_obs > 0 && !in->obs_kf) || (np > 0 && !in->point_bad) || (ne > 0 && !in->q_point))
     return LLD_ERR_INVALID;
   if (cull && ((n_obs > 0 && !in->obs_octave) || (np > 0 && !in->point_nobs) || (ne > 0 && (!in->q_octave || !in->q_depth)) ||
-               !in->q_th_depth || !out->n_mps || !out->n_redundant || !out->redundant))
+               !in->q_th_depth))
     return LLD_ERR_INVALID;
-  if (conn) {
-    if (out->conn_capacity < 0 || out->ordered_capacity < 0) return LLD_ERR_INVALID;
-    if (!out->conn_start || !out->ordered_start || !out->n_max || !out->kf_max || !out->updated) return LLD_ERR_INVALID;
-    if (out->conn_capacity > 0 && (!out->conn_kf || !out->conn_weight)) return LLD_ERR_INVALID;
-    if (out->ordered_capacity > 0 && (!out->ordered_kf || !out->ordered_weight)) return LLD_ERR_INVALID;
-  }
+  if (lld_covis::check_out(out, conn, cull)) return LLD_ERR_INVALID;
   if (!csr_ok(np, n_obs, in->obs_start) || !csr_ok(nq, ne, in->q_start)) return LLD_ERR_INVALID;
   for (int o = 0; o < n_obs; ++o) if (in->obs_kf[o] < 0 || in->obs_kf[o] >= n_kf) return LLD_ERR_INVALID;
   for (int q = 0; q < nq; ++q) if (in->query_kf[q] < -1 || in->query_kf[q] >= n_kf) return LLD_ERR_INVALID;
@@ -241,60 +230,24 @@ int lld_covisibility(lld_ctx* ctx, const lld_covisibility_in* in, lld_covisibili
     if (stage_total > 0x7fffffffLL) return LLD_ERR_UNSUPPORTED;
     stage_off[nq] = (int32_t)stage_total;
   }
-  const int32_t cap_conn = conn ? (int32_t)std::min<long long>(out->conn_capacity, stage_total) : 0;
-  const int32_t cap_ord = conn ? (int32_t)std::min<long long>(out->ordered_capacity, stage_total) : 0;
 
-  size_t inb = 0, outb = 0, tmpb = 0;
-  auto add_in = [&](size_t b) { const size_t o = inb; inb += al(b); return o; };
-  auto add_out = [&](size_t b) { const size_t o = outb; outb += al(b); return o; };
-  auto add_tmp = [&](size_t b) { const size_t o = tmpb; tmpb += al(b); return o; };
-  const size_t o_os = add_in((size_t)(np + 1) * 4), o_ok = add_in((size_t)n_obs * 4), o_pb = add_in((size_t)np);
-  const size_t o_qk = add_in((size_t)nq * 4), o_qs = add_in((size_t)(nq + 1) * 4), o_qp = add_in((size_t)ne * 4);
-  const size_t o_oo = cull ? add_in((size_t)n_obs * 4) : 0, o_pn = cull ? add_in((size_t)np * 4) : 0;
-  const size_t o_qo = cull ? add_in((size_t)ne * 4) : 0, o_qd = cull ? add_in((size_t)ne * 4) : 0, o_qt = cull ? add_in((size_t)nq * 4) : 0;
-  const size_t o_so = conn ? add_in((size_t)(nq + 1) * 4) : 0;
-  const size_t r_cs = conn ? add_out((size_t)(nq + 1) * 4) : 0, r_rs = conn ? add_out((size_t)(nq + 1) * 4) : 0;
-  const size_t r_tot = conn ? add_out(8) : 0, r_nm = conn ? add_out((size_t)nq * 4) : 0, r_km = conn ? add_out((size_t)nq * 4) : 0;
-  const size_t r_up = conn ? add_out((size_t)nq) : 0;
-  const size_t r_ck = conn ? add_out((size_t)cap_conn * 4) : 0, r_cw = conn ? add_out((size_t)cap_conn * 4) : 0;
-  const size_t r_rk = conn ? add_out((size_t)cap_ord * 4) : 0, r_rw = conn ? add_out((size_t)cap_ord * 4) : 0;
-  const size_t r_mp = cull ? add_out((size_t)nq * 4) : 0, r_rd = cull ? add_out((size_t)nq * 4) : 0, r_rf = cull ? add_out((size_t)nq) : 0;
-  const size_t t_cc = conn ? add_tmp((size_t)nq * 4) : 0, t_co = conn ? add_tmp((size_t)nq * 4) : 0;
-  const size_t t_kf = conn ? add_tmp((size_t)stage_total * 4) : 0, t_w = conn ? add_tmp((size_t)stage_total * 4) : 0;
-  const size_t t_key = conn ? add_tmp((size_t)stage_total * 8) : 0;
-  int st;
-  void* hb; st = lld_ctx_pinned(ctx, inb + outb, &hb); if (st) return st;
-  void* db; st = lld_ctx_scratch(ctx, inb + outb + tmpb + 256, &db); if (st) return st;
-  char* h = (char*)hb; char* d = (char*)db; char* h_out = h + inb; char* d_out = d + inb; char* d_tmp = d_out + outb;
-  std::memcpy(h + o_os, in->obs_start, (size_t)(np + 1) * 4);
-  if (n_obs) std::memcpy(h + o_ok, in->obs_kf, (size_t)n_obs * 4);
-  if (np) std::memcpy(h + o_pb, in->point_bad, (size_t)np);
-  std::memcpy(h + o_qk, in->query_kf, (size_t)nq * 4);
-  std::memcpy(h + o_qs, in->q_start, (size_t)(nq + 1) * 4);
-  if (ne) std::memcpy(h + o_qp, in->q_point, (size_t)ne * 4);
-  if (cull) {
-    if (n_obs) std::memcpy(h + o_oo, in->obs_octave, (size_t)n_obs * 4);
-    if (np) std::memcpy(h + o_pn, in->point_nobs, (size_t)np * 4);
-    if (ne) { std::memcpy(h + o_qo, in->q_octave, (size_t)ne * 4); std::memcpy(h + o_qd, in->q_depth, (size_t)ne * 4); }
-    std::memcpy(h + o_qt, in->q_th_depth, (size_t)nq * 4);
-  }
-  if (conn) std::memcpy(h + o_so, stage_off.data(), (size_t)(nq + 1) * 4);
-
+  UploadBlock B;
+  const auto i_os = B.take<int32_t>((size_t)np + 1), i_ok = B.take<int32_t>(n_obs); const auto i_pb = B.take<uint8_t>(np);
+  const auto i_qk = B.take<int32_t>(nq), i_qs = B.take<int32_t>((size_t)nq + 1), i_qp = B.take<int32_t>(ne);
+  const auto i_oo = B.take<int32_t>(cull ? n_obs : 0), i_pn = B.take<int32_t>(cull ? np : 0), i_qo = B.take<int32_t>(cull ? ne : 0);
+  const auto i_qd = B.take<float>(cull ? ne : 0), i_qt = B.take<float>(cull ? nq : 0);
+  lld_covis::Plan P;
+  P.outputs(B, out, conn, cull, nq, stage_total);
+  P.scratch(B);
   CovisArgs A;
-  auto I32 = [](char* p) { return reinterpret_cast<int32_t*>(p); };
-  A.obs_start = I32(d + o_os); A.obs_kf = I32(d + o_ok); A.obs_octave = I32(d + o_oo); A.point_bad = reinterpret_cast<uint8_t*>(d + o_pb);
-  A.point_nobs = I32(d + o_pn); A.query_kf = I32(d + o_qk); A.q_start = I32(d + o_qs); A.q_point = I32(d + o_qp);
-  A.q_octave = I32(d + o_qo); A.q_depth = reinterpret_cast<float*>(d + o_qd); A.q_th_depth = reinterpret_cast<float*>(d + o_qt);
-  A.stage_off = I32(d + o_so);
-  A.n_kf = n_kf; A.n_queries = nq; A.monocular = in->monocular ? 1 : 0; A.th = in->params.th; A.th_obs = in->params.th_obs;
+  const int st = P.bind(ctx, B, stage_off.data(), A.L); if (st) return st;
+  B.stage(i_os, in->obs_start); B.stage(i_ok, in->obs_kf); B.stage(i_pb, in->point_bad);
+  B.stage(i_qk, in->query_kf); B.stage(i_qs, in->q_start); B.stage(i_qp, in->q_point);
+  B.stage(i_oo, in->obs_octave); B.stage(i_pn, in->point_nobs); B.stage(i_qo, in->q_octave); B.stage(i_qd, in->q_depth); B.stage(i_qt, in->q_th_depth);
+  A.obs_start = B.dev(i_os); A.obs_kf = B.dev(i_ok); A.obs_octave = B.dev(i_oo); A.point_bad = B.dev(i_pb); A.point_nobs = B.dev(i_pn);
+  A.query_kf = B.dev(i_qk); A.q_start = B.dev(i_qs); A.q_point = B.dev(i_qp); A.q_octave = B.dev(i_qo); A.q_depth = B.dev(i_qd); A.q_th_depth = B.dev(i_qt);
+  A.n_kf = n_kf; A.monocular = in->monocular ? 1 : 0; A.th = in->params.th; A.th_obs = in->params.th_obs;
   A.flags = in->flags; A.ratio = in->params.redundant_ratio;
-  A.st_kf = I32(d_tmp + t_kf); A.st_w = I32(d_tmp + t_w); A.st_key = reinterpret_cast<u64*>(d_tmp + t_key);
-  A.cnt_conn = I32(d_tmp + t_cc); A.cnt_ord = I32(d_tmp + t_co);
-  A.n_max = I32(d_out + r_nm); A.kf_max = I32(d_out + r_km); A.updated = reinterpret_cast<uint8_t*>(d_out + r_up);
-  A.n_mps = I32(d_out + r_mp); A.n_red = I32(d_out + r_rd); A.redundant = reinterpret_cast<uint8_t*>(d_out + r_rf);
-  A.cap_conn = cap_conn; A.cap_ord = cap_ord;
-  A.conn_start = I32(d_out + r_cs); A.ord_start = I32(d_out + r_rs); A.totals = I32(d_out + r_tot);
-  A.conn_kf = I32(d_out + r_ck); A.conn_w = I32(d_out + r_cw); A.ord_kf = I32(d_out + r_rk); A.ord_w = I32(d_out + r_rw);
 
   // LDS: the counters, then the sort keys of the longest list any query can select (a power of two of 8-byte keys)
   size_t lds = 0;
@@ -306,43 +259,79 @@ int lld_covisibility(lld_ctx* ctx, const lld_covisibility_in* in, lld_covisibili
     if (lds > 48 * 1024)
       LLD_HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(&covis_query), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
   }
-  hipStream_t sm = ctx->stream;
-  hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
-  const bool timed = out->phase_ms != nullptr;
-  if (timed) for (int k = 0; k < 4; ++k) LLD_HIP_TRY(hipEventCreate(&ev[k]));
-  if (timed) LLD_HIP_TRY(hipEventRecord(ev[0], sm));
-  LLD_HIP_TRY(hipMemcpyAsync(d, h, inb, hipMemcpyHostToDevice, sm));
-  if (timed) LLD_HIP_TRY(hipEventRecord(ev[1], sm));
-  hipLaunchKernelGGL(covis_query, dim3(nq), dim3(kThreads), lds, sm, A);
-  if (conn) hipLaunchKernelGGL(covis_pack, dim3(nq), dim3(kThreads), 0, sm, A);
-  LLD_HIP_TRY(hipGetLastError());
-  if (timed) LLD_HIP_TRY(hipEventRecord(ev[2], sm));
-  LLD_HIP_TRY(hipMemcpyAsync(h_out, d_out, outb, hipMemcpyDeviceToHost, sm));
-  if (timed) LLD_HIP_TRY(hipEventRecord(ev[3], sm));
-  LLD_HIP_TRY(hipStreamSynchronize(sm));
-  if (timed) {
-    for (int k = 0; k < 3; ++k) LLD_HIP_TRY(hipEventElapsedTime(&out->phase_ms[k], ev[k], ev[k + 1]));
-    for (int k = 0; k < 4; ++k) LLD_HIP_TRY(hipEventDestroy(ev[k]));
-  }
+  const int ran = lld_covis::run(ctx->stream, B, P, A.L, out->phase_ms,
+                                 [&](hipStream_t sm) { hipLaunchKernelGGL(covis_query, dim3(nq), dim3(kThreads), lds, sm, A); });
+  return ran ? ran : P.copy_back(B, out);
+}
 
+}  // extern "C"
+
+// ------------------------------------------------------------------------------------------------ lld_covis_lists.h, the host half
+namespace lld_covis {
+
+int check_out(const lld_covisibility_out* out, bool conn, bool cull) {
+  if (cull && (!out->n_mps || !out->n_redundant || !out->redundant)) return LLD_ERR_INVALID;
   if (conn) {
-    const int32_t* tot = reinterpret_cast<const int32_t*>(h_out + r_tot);
-    out->n_conn = tot[0]; out->n_ordered = tot[1];
-    if (tot[0] > out->conn_capacity || tot[1] > out->ordered_capacity) return LLD_ERR_INVALID;
-    std::memcpy(out->conn_start, h_out + r_cs, (size_t)(nq + 1) * 4);
-    std::memcpy(out->ordered_start, h_out + r_rs, (size_t)(nq + 1) * 4);
-    std::memcpy(out->n_max, h_out + r_nm, (size_t)nq * 4);
-    std::memcpy(out->kf_max, h_out + r_km, (size_t)nq * 4);
-    std::memcpy(out->updated, h_out + r_up, (size_t)nq);
-    if (tot[0]) { std::memcpy(out->conn_kf, h_out + r_ck, (size_t)tot[0] * 4); std::memcpy(out->conn_weight, h_out + r_cw, (size_t)tot[0] * 4); }
-    if (tot[1]) { std::memcpy(out->ordered_kf, h_out + r_rk, (size_t)tot[1] * 4); std::memcpy(out->ordered_weight, h_out + r_rw, (size_t)tot[1] * 4); }
-  }
-  if (cull) {
-    std::memcpy(out->n_mps, h_out + r_mp, (size_t)nq * 4);
-    std::memcpy(out->n_redundant, h_out + r_rd, (size_t)nq * 4);
-    std::memcpy(out->redundant, h_out + r_rf, (size_t)nq);
+    if (out->conn_capacity < 0 || out->ordered_capacity < 0) return LLD_ERR_INVALID;
+    if (!out->conn_start || !out->ordered_start || !out->n_max || !out->kf_max || !out->updated) return LLD_ERR_INVALID;
+    if (out->conn_capacity > 0 && (!out->conn_kf || !out->conn_weight)) return LLD_ERR_INVALID;
+    if (out->ordered_capacity > 0 && (!out->ordered_kf || !out->ordered_weight)) return LLD_ERR_INVALID;
   }
   return LLD_OK;
 }
 
-}  // extern "C"
+void pack_launch(hipStream_t st, const Lists& L) { hipLaunchKernelGGL(covis_pack, dim3(L.n_queries), dim3(kThreads), 0, st, L); }
+
+void Plan::outputs(UploadBlock& B, const lld_covisibility_out* out, bool conn_, bool cull_, int32_t nq_, long long stage_total_) {
+  conn = conn_; cull = cull_; nq = nq_; stage_total = (size_t)stage_total_;
+  cap_conn = conn ? (int32_t)std::min<long long>(out->conn_capacity, stage_total_) : 0;
+  cap_ord = conn ? (int32_t)std::min<long long>(out->ordered_capacity, stage_total_) : 0;
+  const size_t nc = conn ? nq : 0, nu = cull ? nq : 0;
+  stage_off = B.take<int32_t>(conn ? nc + 1 : 0);
+  B.end_upload();
+  out_off = B.size;
+  conn_start = B.take<int32_t>(conn ? nc + 1 : 0); ord_start = B.take<int32_t>(conn ? nc + 1 : 0); totals = B.take<int32_t>(conn ? 2 : 0);
+  n_max = B.take<int32_t>(nc); kf_max = B.take<int32_t>(nc); updated = B.take<uint8_t>(nc);
+  n_mps = B.take<int32_t>(nu); n_red = B.take<int32_t>(nu); redundant = B.take<uint8_t>(nu);
+  conn_kf = B.take<int32_t>(cap_conn); conn_w = B.take<int32_t>(cap_conn); ord_kf = B.take<int32_t>(cap_ord); ord_w = B.take<int32_t>(cap_ord);
+}
+
+void Plan::scratch(UploadBlock& B) {
+  out_bytes = B.size - out_off;
+  cnt_conn = B.take<int32_t>(conn ? nq : 0); cnt_ord = B.take<int32_t>(conn ? nq : 0);
+  st_kf = B.take<int32_t>(stage_total); st_w = B.take<int32_t>(stage_total); st_key = B.take<u64>(stage_total);
+}
+
+int Plan::bind(lld_ctx* ctx, UploadBlock& B, const int32_t* stage_off_host, Lists& L) const {
+  int st;
+  void* hb; st = lld_ctx_pinned(ctx, out_off + out_bytes, &hb); if (st) return st;
+  void* db; st = lld_ctx_scratch(ctx, B.size + 256, &db); if (st) return st;
+  B.bind((char*)hb, (char*)db);
+  if (conn) B.stage(stage_off, stage_off_host);
+  L.stage_off = B.dev(stage_off); L.n_queries = nq;
+  L.st_kf = B.dev(st_kf); L.st_w = B.dev(st_w); L.st_key = B.dev(st_key);
+  L.cnt_conn = B.dev(cnt_conn); L.cnt_ord = B.dev(cnt_ord); L.n_max = B.dev(n_max); L.kf_max = B.dev(kf_max); L.updated = B.dev(updated);
+  L.n_mps = B.dev(n_mps); L.n_red = B.dev(n_red); L.redundant = B.dev(redundant);
+  L.cap_conn = cap_conn; L.cap_ord = cap_ord;
+  L.conn_start = B.dev(conn_start); L.ord_start = B.dev(ord_start); L.totals = B.dev(totals);
+  L.conn_kf = B.dev(conn_kf); L.conn_w = B.dev(conn_w); L.ord_kf = B.dev(ord_kf); L.ord_w = B.dev(ord_w);
+  return LLD_OK;
+}
+
+int Plan::copy_back(const UploadBlock& B, lld_covisibility_out* out) const {
+  if (conn) {
+    const int32_t* tot = B.host(totals);
+    out->n_conn = tot[0]; out->n_ordered = tot[1];
+    if (tot[0] > out->conn_capacity || tot[1] > out->ordered_capacity) return LLD_ERR_INVALID;
+    std::memcpy(out->conn_start, B.host(conn_start), (size_t)(nq + 1) * 4); std::memcpy(out->ordered_start, B.host(ord_start), (size_t)(nq + 1) * 4);
+    std::memcpy(out->n_max, B.host(n_max), (size_t)nq * 4); std::memcpy(out->kf_max, B.host(kf_max), (size_t)nq * 4); std::memcpy(out->updated, B.host(updated), (size_t)nq);
+    if (tot[0]) { std::memcpy(out->conn_kf, B.host(conn_kf), (size_t)tot[0] * 4); std::memcpy(out->conn_weight, B.host(conn_w), (size_t)tot[0] * 4); }
+    if (tot[1]) { std::memcpy(out->ordered_kf, B.host(ord_kf), (size_t)tot[1] * 4); std::memcpy(out->ordered_weight, B.host(ord_w), (size_t)tot[1] * 4); }
+  }
+  if (cull) {
+    std::memcpy(out->n_mps, B.host(n_mps), (size_t)nq * 4); std::memcpy(out->n_redundant, B.host(n_red), (size_t)nq * 4); std::memcpy(out->redundant, B.host(redundant), (size_t)nq);
+  }
+  return LLD_OK;
+}
+
+}  // namespace lld_covis

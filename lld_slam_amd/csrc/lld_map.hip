@@ -21,23 +21,24 @@
 // one wavefront for the order-dependent extension loop out of LDS), map_first_kernel / map_count_kernel / map_write_kernel (first occurrences
 // by 64-bit atomicMin, per-keyframe counts, ordered compaction), and map_gather_kernel for stage 2 (lld_frame_track_local_map_resident).
 //
-// Covisibility on the same tables (lld_map_covisibility: KeyFrame::UpdateConnections, src/KeyFrame.cc:312-402, and the redundancy count of
-// LocalMapping::KeyFrameCulling, src/LocalMapping.cc:646-694): map_covis_query_kernel, one workgroup per query, and map_covis_pack_kernel.
-// The culling part reads four members more (MapExt: keypoint index per observation, nObs per point, octave / depth / mThDepth per keyframe);
-// their tables and pools are allocated by the first lld_map_set_observations_indexed / lld_map_set_keyframe_keypoints, never by lld_map_create.
+// The tables' declarations are in lld_map_tables.h; covisibility on the same tables (lld_map_covisibility) is in lld_map_covis.hip.
 #include "lld_common.h"
 #include "lld_frame_track_state.h"
 #include "lld_map_internal.h"
+#include "lld_map_tables.h"
 #include "lld_track_internal.h"
-#include "lld_upload_block.h"
 #include "lld_wave.h"
 
 namespace {
 
+using lld_map_dev::MapDev;
+using lld_map_dev::MapExt;
+using lld_map_dev::PoolPlan;
+using lld_map_dev::RowPool;
+using lld_map_dev::u64;
 using lld_track::Span;
 using lld_track::TrackDev;
 using lld_track::UploadBlock;
-typedef unsigned long long u64;
 
 constexpr int kMaxVoted = 1024;                    // voted keyframes one workgroup sorts in LDS
 constexpr int kLkfCap = LLD_MAP_MAX_LOCAL_KEYFRAMES;
@@ -45,24 +46,6 @@ static_assert(kLkfCap >= kMaxVoted + 3 * 81, "list capacity");    // the list: t
 constexpr int kMaxKeyframes = 1 << 18;             // the marks are a bit set in LDS: 32 KB at this size
 enum { ST_STATUS = 0, ST_VOTED, ST_NKF, ST_NPTS, ST_NLNS, ST_CLEARED, ST_REF, ST_EMPTY, ST_STAGE2, ST_WORDS = 16 };
 enum { FC_TOUCHED = 0, FC_CLEARED, FC_WORDS = 4 };
-
-struct MapDev {
-  int max_kf, max_pt, max_ln, dim, max_lp, max_ll;
-  float* p_pos; float* p_nrm; float* p_mind; float* p_maxd; uint32_t* p_desc; uint8_t* p_state; int2* p_obs; int32_t* obs_pool;
-  double* l_x0; double* l_dir; double* l_x1; double* l_x2; float* l_desc; uint8_t* l_bad;
-  u64* k_key; uint8_t* k_bad; int32_t* k_parent; int32_t* k_cov; int32_t* k_ncov; int2* k_child; int2* k_pt; int2* k_ln;
-  int32_t* child_pool; int32_t* kpt_pool; int32_t* kln_pool;
-  // per call: vote counters (zero between calls), the slots that got a first vote, first occurrences, the lists
-  int32_t* cnt; int32_t* touched; int32_t* fc; u64* p_first; u64* l_first;
-  int32_t* lkf; int32_t* lkf_np; int32_t* lkf_nl; int32_t* lpts; int32_t* llns; int32_t* st;
-};
-
-// The culling tables.  All null until the first lld_map_set_observations_indexed / lld_map_set_keyframe_keypoints.
-//   point slot s     p_nobs = MapPoint::Observations(), p_idx = (offset, length) in idx_pool of the keypoint indices, parallel to the p_obs row
-//   keyframe slot s  k_oct / k_dep = (offset, length) in oct_pool / dep_pool of mvKeysUn[i].octave / the bits of mvDepth[i], k_thd = mThDepth
-struct MapExt {
-  int32_t* p_nobs; int2* p_idx; int32_t* idx_pool; int2* k_oct; int2* k_dep; int32_t* oct_pool; int32_t* dep_pool; float* k_thd;
-};
 
 // ------------------------------------------------------------------------------------------------ scatter kernels of lld_map_set_*
 __global__ void map_scatter_kernel(int n, const int32_t* slot, const int32_t* v, int32_t* dst) {
@@ -399,289 +382,6 @@ __global__ void map_restore_kernel(MapDev M, lld_map_dev::GatherDst G) {
   if (i < G.n_rec2) G.rec2[i] = 0;
 }
 
-// ------------------------------------------------------------------------------------------------ covisibility on the tables
-// map_covis_query_kernel, one workgroup of 256 per query.  A group of 16 lanes walks the observation row of one entry of the query
-// keyframe's point row, so sixteen entries are in flight.
-//   Connections: a map has up to 2^18 keyframe slots and a query meets a few hundred of them, so the counts live in an open-addressing table
-//     in LDS keyed by slot (8192 cells: int key[], int count[], 64 KB; home cell = slot mod 8192, linear probing).  A lane claims an empty
-//     cell by atomicCAS and then adds to the cell's count; integer adds commute, so the counts do not depend on the order.  Claims are counted:
-//     beyond LLD_MAP_COVIS_MAX_CONNECTED the query is an overflow and nothing more is inserted (at most one claim per lane goes through
-//     behind the limit, so the table is never full and every probe ends).
-//   Finishing: the cells in use are compacted to the query's staging range in HBM (the table is dead from here), their order_key fetched,
-//     and (key, position) sorted in the LDS the table held (lld_wave::bitonic_sort_pairs): the rank in that order is map order, conn_* go
-//     out by rank, the maximum is reduced on (weight, ~rank) so that the lowest rank wins, and the counts >= th are sorted once more as
-//     weight << 32 | rank; read from the top that is descending weight, then descending order_key.
-//   Culling: the qualifying observations of an entry are summed over its group by lane shuffles, the two per-query sums over the wavefront,
-//     then one LDS atomic per wavefront.  Two dependent loads more per observation than on flat tables: the keypoint index, then the octave
-//     in the observing keyframe's row - each behind a comparison of the index with that row's length.
-// map_covis_pack_kernel: one workgroup per query, exclusive sums of the per-query counts, then the staged lists to their packed places.
-// No workgroup reads what another workgroup of the same kernel writes, so a query's result cannot depend on the batch.
-constexpr int kCovThreads = 256, kCovGroup = 16, kCovGroups = kCovThreads / kCovGroup;
-constexpr int kCovMax = LLD_MAP_COVIS_MAX_CONNECTED, kCovCells = 2 * kCovMax;
-static_assert((kCovCells & (kCovCells - 1)) == 0 && kCovMax + 2 * kCovThreads < kCovCells, "the table keeps empty cells behind an overflow");
-constexpr size_t kCovLds = (size_t)kCovCells * 8;
-enum { CS_CLAIMED = 0, CS_NO_KP, CS_MPS, CS_RED, CS_WORDS };
-
-struct CovArgs {
-  const int32_t* query; const int32_t* stage_off;
-  int32_t n_queries, monocular, th, th_obs, has_ext; uint32_t flags; double ratio;
-  int32_t* st_slot; int32_t* st_cnt;         // staging: the table's cells in use, in cell order
-  int32_t* st_kf; int32_t* st_w; u64* st_key;     // ... the same in map order; the ordered list as weight << 32 | rank
-  int32_t* cnt_conn; int32_t* cnt_ord;
-  int32_t* n_max; int32_t* kf_max; uint8_t* updated; uint8_t* status; int32_t* n_mps; int32_t* n_red; uint8_t* redundant;
-  int32_t cap_conn, cap_ord;
-  int32_t* conn_start; int32_t* ord_start; int32_t* totals; int32_t* conn_kf; int32_t* conn_w; int32_t* ord_kf; int32_t* ord_w;
-};
-
-__device__ __forceinline__ void cov_count(int* tkey, int* tcnt, int* s_st, int kf) {
-  if (*(volatile int*)&s_st[CS_CLAIMED] > kCovMax) return;
-  int h = kf & (kCovCells - 1);
-  for (;;) {
-    int k = *(volatile int*)&tkey[h];
-    if (k == -1) {
-      k = atomicCAS(&tkey[h], -1, kf);
-      if (k == -1) { atomicAdd(&s_st[CS_CLAIMED], 1); k = kf; }
-    }
-    if (k == kf) break;
-    h = (h + 1) & (kCovCells - 1);
-  }
-  atomicAdd(&tcnt[h], 1);
-}
-
-__global__ __launch_bounds__(kCovThreads) void map_covis_query_kernel(MapDev M, MapExt X, CovArgs A) {
-  extern __shared__ __align__(16) unsigned char cov_lds[];
-  int* tkey = reinterpret_cast<int*>(cov_lds);
-  int* tcnt = tkey + kCovCells;
-  u64* keys = reinterpret_cast<u64*>(cov_lds);                         // behind the compaction: 32 KB of sort keys, 16 KB of values
-  int* vals = reinterpret_cast<int*>(keys + kCovMax);
-  __shared__ int s_st[CS_WORDS];
-  __shared__ int s_scan[kCovThreads / 64];
-  __shared__ u64 s_best[kCovThreads / 64];
-  const int q = blockIdx.x, t = threadIdx.x, lane = t & 63, wv = t >> 6;
-  const bool conn = (A.flags & LLD_COVIS_CONNECTIONS) != 0, cull = (A.flags & LLD_COVIS_CULLING) != 0;
-  const int own = A.query[q];
-  const int2 rp = M.k_pt[own];
-  if (conn) for (int i = t; i < kCovCells; i += kCovThreads) { tkey[i] = -1; tcnt[i] = 0; }
-  if (t < CS_WORDS) s_st[t] = 0;
-  // culling reads the keyframe's keypoint row beside its point row: only a row of the same length is read at all
-  int2 ro = make_int2(0, 0), rd = make_int2(0, 0);
-  float th_depth = 0.f;
-  bool kp_ok = false;
-  if (cull && A.has_ext) { ro = X.k_oct[own]; rd = X.k_dep[own]; th_depth = X.k_thd[own]; kp_ok = ro.y == rp.y && rd.y == rp.y; }
-  const bool cull_run = cull && kp_ok;
-  __syncthreads();
-
-  const int g = t / kCovGroup, gl = t % kCovGroup;
-  int my_mps = 0, my_red = 0;                                          // kept by the first lane of each group
-  const int n_row = (conn || cull_run) ? rp.y : 0;
-  for (int base = 0; base < n_row; base += kCovGroups) {               // uniform over the workgroup: the shuffles below are safe
-    const int j = base + g;
-    int s = 0, f = 0, lvl = 0, to_idx = 0;
-    bool count_cull = false;
-    if (j < n_row) {
-      const int p = M.kpt_pool[rp.x + j];
-      const int state = p >= 0 ? M.p_state[p] : 2;                     // NULL entries and bad points are skipped by both routines
-      if (state != 2) {
-        bool walk = conn && state == 1;                                // a point never set has an empty row
-        if (cull_run) {
-          const float depth = __int_as_float(X.dep_pool[rd.x + j]);
-          if (A.monocular || !(depth > th_depth || depth < 0.f)) {
-            if (gl == 0) my_mps++;
-            if (state == 1) {                                          // never set: Observations() == 0
-              // a row without an index row of its length came through lld_map_set_observations: its n_obs is not known either
-              const int2 row = M.p_obs[p], ir = X.p_idx[p];
-              if (ir.y != row.y) s_st[CS_NO_KP] = 1;
-              else if (X.p_nobs[p] > A.th_obs) { count_cull = true; lvl = X.oct_pool[ro.x + j] + 1; to_idx = ir.x - row.x; }
-            }
-          }
-        }
-        if (walk || count_cull) { const int2 row = M.p_obs[p]; s = row.x; f = row.x + row.y; }
-      }
-    }
-    int c = 0;
-    for (int o = s + gl; o < f; o += kCovGroup) {
-      const int kf = M.obs_pool[o];
-      if (kf == own) continue;
-      if (conn) cov_count(tkey, tcnt, s_st, kf);
-      if (count_cull) {
-        const int idx = X.idx_pool[o + to_idx];
-        const int2 orow = X.k_oct[kf];
-        if (idx < 0 || idx >= orow.y) s_st[CS_NO_KP] = 1;              // an index outside the observer's keypoint row
-        else if (X.oct_pool[orow.x + idx] <= lvl) c++;
-      }
-    }
-    if (cull_run) {
-      c = lld_wave::sum<kCovGroup>(c);
-      if (gl == 0 && count_cull && c >= A.th_obs) my_red++;
-    }
-  }
-  if (cull_run) {
-    lld_wave::sum_each(my_mps, my_red);
-    if (lane == 0) { atomicAdd(&s_st[CS_MPS], my_mps); atomicAdd(&s_st[CS_RED], my_red); }
-  }
-  __syncthreads();
-  int status = 0;
-  if (cull) {
-    const bool no_kp = !kp_ok || s_st[CS_NO_KP] != 0;
-    if (no_kp) status |= LLD_MAP_COVIS_NO_KEYPOINT_DATA;
-    if (t == 0) {
-      const int nm = no_kp ? 0 : s_st[CS_MPS], nr = no_kp ? 0 : s_st[CS_RED];
-      A.n_mps[q] = nm; A.n_red[q] = nr;
-      A.redundant[q] = ((double)nr > A.ratio * (double)nm) ? 1 : 0;    // nRedundantObservations > 0.9*nMPs: int against double
-    }
-  }
-  if (!conn) { if (t == 0) A.status[q] = (uint8_t)status; return; }
-  const int claimed = s_st[CS_CLAIMED];
-  if (claimed == 0 || claimed > kCovMax) {
-    // keyframeCounter.empty() (:346-347), or more keyframes than the table answers for: no entries, the cov row stays
-    if (t == 0) {
-      A.cnt_conn[q] = 0; A.cnt_ord[q] = 0; A.n_max[q] = 0; A.kf_max[q] = -1; A.updated[q] = 0;
-      A.status[q] = (uint8_t)(status | (claimed ? LLD_MAP_COVIS_CONN_OVERFLOW : 0));
-    }
-    return;
-  }
-  // ---- the cells in use, to the staging
-  const size_t off = (size_t)A.stage_off[q];
-  int n = 0;
-  for (int c0 = 0; c0 < kCovCells && n < claimed; c0 += kCovThreads) {
-    const int k = tkey[c0 + t], w = tcnt[c0 + t];
-    int tot;
-    const int r = lld_wave::block_excl_scan<kCovThreads>(k >= 0 ? 1 : 0, s_scan, tot);
-    if (k >= 0) { A.st_slot[off + n + r] = k; A.st_cnt[off + n + r] = w; }
-    n += tot;
-  }
-  __syncthreads();                                                     // the table is dead; the staged cells are visible to the workgroup
-  // ---- map order: ascending order_key
-  int npad = 2;
-  while (npad < n) npad <<= 1;
-  for (int i = t; i < npad; i += kCovThreads) { keys[i] = i < n ? M.k_key[A.st_slot[off + i]] : ~0ull; vals[i] = i < n ? i : -1; }
-  __syncthreads();
-  lld_wave::bitonic_sort_pairs<kCovThreads>(keys, vals, npad);
-  u64 best = 0;
-  int n_sel = 0;
-  for (int r = t; r < npad; r += kCovThreads) {
-    u64 k2 = 0;                                                        // a selected key is above 0: its weight is >= 1
-    if (r < n) {
-      const int i = vals[r], slot = A.st_slot[off + i], w = A.st_cnt[off + i];
-      A.st_kf[off + r] = slot; A.st_w[off + r] = w;
-      const u64 b = ((u64)(uint32_t)w << 32) | (uint32_t)(0xffffffffu - (uint32_t)r);     // it->second > nmax: the first of the greatest
-      if (b > best) best = b;
-      if (w >= A.th) { k2 = ((u64)(uint32_t)w << 32) | (uint32_t)r; n_sel++; }
-    }
-    keys[r] = k2;                                                      // rank r's key was this lane's to read
-  }
-  best = lld_wave::max(best);
-  if (lane == 0) s_best[wv] = best;
-  n_sel = lld_wave::block_sum(n_sel, s_scan);                          // (its barriers also publish s_best and the keys)
-  best = s_best[0];
-#pragma unroll
-  for (int k = 1; k < kCovThreads / 64; ++k) if (s_best[k] > best) best = s_best[k];
-  const int nmax = (int)(best >> 32), rmax = (int)(0xffffffffu - (uint32_t)best);
-  const int n_ord = n_sel ? n_sel : 1;                                 // none reaches th: the single pair (nmax, pKFmax) (:371-375)
-  lld_wave::bitonic_sort<kCovThreads>(keys, npad);                     // descending (weight, order_key) from the top
-  for (int i = t; i < n_sel; i += kCovThreads) A.st_key[off + i] = keys[npad - 1 - i];
-  if (t == 0) {
-    if (!n_sel) A.st_key[off] = ((u64)(uint32_t)nmax << 32) | (uint32_t)rmax;
-    A.cnt_conn[q] = n; A.cnt_ord[q] = n_ord; A.n_max[q] = nmax; A.kf_max[q] = A.st_kf[off + rmax]; A.updated[q] = 1;
-    A.status[q] = (uint8_t)status;
-  }
-  if ((A.flags & LLD_MAP_COVIS_WRITE_COV) && status == 0) {
-    // mvpOrderedConnectedKeyFrames' first ten: what Tracking::UpdateLocalMap reads as GetBestCovisibilityKeyFrames(10)
-    const int nc = min(n_ord, 10);
-    if (t < nc) M.k_cov[10 * own + t] = A.st_kf[off + (n_sel ? (uint32_t)keys[npad - 1 - t] : (uint32_t)rmax)];
-    if (t == 0) M.k_ncov[own] = nc;
-  }
-}
-
-__global__ __launch_bounds__(kCovThreads) void map_covis_pack_kernel(CovArgs A) {
-  __shared__ int s_sum[4];
-  const int q = blockIdx.x, t = threadIdx.x;
-  int a = 0, b = 0, ta = 0, tb = 0;                                    // conn before q, ordered before q, the totals
-  for (int j = t; j < A.n_queries; j += kCovThreads) {
-    const int c = A.cnt_conn[j], d = A.cnt_ord[j];
-    if (j < q) { a += c; b += d; }
-    ta += c; tb += d;
-  }
-  a = lld_wave::block_sum(a, s_sum); b = lld_wave::block_sum(b, s_sum); ta = lld_wave::block_sum(ta, s_sum); tb = lld_wave::block_sum(tb, s_sum);
-  if (t == 0) {
-    A.conn_start[q] = a; A.ord_start[q] = b;
-    if (q == A.n_queries - 1) { A.conn_start[A.n_queries] = ta; A.ord_start[A.n_queries] = tb; A.totals[0] = ta; A.totals[1] = tb; }
-  }
-  if (ta > A.cap_conn || tb > A.cap_ord) return;                       // a short capacity: only the totals go back
-  const size_t off = (size_t)A.stage_off[q];
-  const int nc = A.cnt_conn[q], no = A.cnt_ord[q];
-  for (int i = t; i < nc; i += kCovThreads) { A.conn_kf[a + i] = A.st_kf[off + i]; A.conn_w[a + i] = A.st_w[off + i]; }
-  for (int i = t; i < no; i += kCovThreads) {
-    const u64 key = A.st_key[off + i];
-    A.ord_kf[b + i] = A.st_kf[off + (uint32_t)key]; A.ord_w[b + i] = (int32_t)(key >> 32);
-  }
-}
-
-// ------------------------------------------------------------------------------------------------ host: the pools
-struct PoolPlan { bool repack = false; int n_up = 0; size_t n_data = 0; int64_t live_after = 0; Span<int32_t> slot, src, data; Span<int2> row; };
-
-struct RowPool {
-  int rows = 0; int64_t limit = 0, cap = 0, tail = 0, live = 0;
-  std::vector<int32_t> off, len, rcap, mirror;
-  int2* d_row = nullptr; int32_t* d_pool = nullptr;
-  void init(int rows_, int64_t limit_) {
-    rows = rows_; limit = limit_; cap = 2 * limit_; tail = live = 0;
-    off.assign(rows, 0); len.assign(rows, 0); rcap.assign(rows, 0); mirror.assign((size_t)std::max<int64_t>(cap, 1), 0);
-  }
-  void reset() { tail = live = 0; std::fill(off.begin(), off.end(), 0); std::fill(len.begin(), len.end(), 0); std::fill(rcap.begin(), rcap.end(), 0); }
-  // false: the live total would pass the limit.  Nothing is changed.
-  bool plan(int n, const int32_t* slot, const int32_t* start, PoolPlan& P) const {
-    int64_t lv = live, t = tail; size_t nd = 0;
-    for (int i = 0; i < n; i++) {
-      const int nl = start[i + 1] - start[i], s = slot[i];
-      lv += nl - len[s]; nd += nl;
-      if (nl > rcap[s]) t += nl;
-    }
-    if (lv > limit) return false;
-    P.live_after = lv; P.repack = t > cap;
-    P.n_up = P.repack ? rows : n; P.n_data = P.repack ? (size_t)lv : nd;
-    return true;
-  }
-  void reserve(UploadBlock& B, PoolPlan& P) const {
-    P.slot = B.take<int32_t>(P.n_up); P.src = B.take<int32_t>(P.n_up); P.row = B.take<int2>(P.n_up); P.data = B.take<int32_t>(P.n_data);
-  }
-  void commit(const UploadBlock& B, const PoolPlan& P, int n, const int32_t* slot, const int32_t* start, const int32_t* data) {
-    int32_t* hs = B.host(P.slot); int32_t* hsrc = B.host(P.src); int2* hrow = B.host(P.row); int32_t* hd = B.host(P.data);
-    if (!P.repack) {
-      int32_t run = 0;
-      for (int i = 0; i < n; i++) {
-        const int nl = start[i + 1] - start[i], s = slot[i];
-        if (nl > rcap[s]) { off[s] = (int32_t)tail; rcap[s] = nl; tail += nl; }
-        len[s] = nl;
-        if (nl) { std::memcpy(&mirror[off[s]], data + start[i], (size_t)nl * 4); std::memcpy(hd + run, data + start[i], (size_t)nl * 4); }
-        hs[i] = s; hsrc[i] = run; hrow[i] = make_int2(off[s], nl); run += nl;
-      }
-    } else {
-      // every row, packed tightly in slot order: the rows of this call from the caller's arrays, the others from the host copy
-      std::vector<int32_t> upd(rows, -1), packed((size_t)std::max<int64_t>(cap, 1));
-      for (int i = 0; i < n; i++) upd[slot[i]] = i;
-      int32_t run = 0;
-      for (int r = 0; r < rows; r++) {
-        const int i = upd[r];
-        const int nl = i >= 0 ? start[i + 1] - start[i] : len[r];
-        const int32_t* from = i >= 0 ? data + start[i] : mirror.data() + off[r];
-        if (nl) std::memcpy(&packed[run], from, (size_t)nl * 4);
-        off[r] = run; len[r] = nl; rcap[r] = nl;
-        hs[r] = r; hsrc[r] = run; hrow[r] = make_int2(run, nl); run += nl;
-      }
-      mirror.swap(packed); tail = run;
-      if (run) std::memcpy(hd, mirror.data(), (size_t)run * 4);
-    }
-    live = P.live_after;
-  }
-  int launch(hipStream_t st, const UploadBlock& B, const PoolPlan& P) const {
-    if (P.n_up <= 0) return LLD_OK;
-    hipLaunchKernelGGL(map_rows_kernel, dim3(std::min(P.n_up, 4096)), dim3(64), 0, st, P.n_up, B.dev(P.slot), B.dev(P.row), B.dev(P.src), B.dev(P.data), d_row, d_pool);
-    LLD_HIP_TRY(hipGetLastError());
-    return LLD_OK;
-  }
-};
-
 bool starts_ok(int n, const int32_t* start) {
   if (!start || start[0] != 0) return false;
   for (int i = 0; i < n; i++) if (start[i + 1] < start[i]) return false;
@@ -694,25 +394,12 @@ bool entries_in(const int32_t* v, int n, int lo, int hi) {        // lo <= v < h
 
 }  // namespace
 
-struct lld_map {
-  lld_ctx* ctx = nullptr;
-  lld_map_limits lim{};
-  MapDev D{};
-  char* d_tables = nullptr; size_t first_off = 0, first_bytes = 0, down_off = 0, down_bytes = 0, tables_bytes = 0;
-  size_t o_lkf = 0, o_lpts = 0, o_llns = 0;                         // inside the downloaded span, which starts with st
-  RowPool obs, child, kpt, kln;
-  // the culling tables (MapExt): allocated by the first setter that fills them
-  MapExt X{}; char* d_ext = nullptr; size_t ext_bytes = 0; RowPool idx, koct, kdep;
-  std::vector<uint8_t> kf_set;              // lld_map_set_keyframes named the slot since the last clear
-  bool cov_lds_set = false;                 // map_covis_query_kernel was granted its 64 KB of dynamic LDS
-  std::vector<uint32_t> stamp_pt, stamp_kf, stamp_ln; uint32_t epoch = 0;
-  // the staging of lld_map_set_*: pinned block, device block, the event of the last copy
-  char* h_up = nullptr; size_t h_up_bytes = 0; char* d_up = nullptr; size_t d_up_bytes = 0; hipEvent_t uploaded = nullptr; bool upload_pending = false;
-  char* h_down = nullptr;
-  unsigned long long serial = 0;            // counts lld_frame_track_update_local_map calls: the lists in the tables are the last one's
-  bool poisoned = false;                    // a HIP failure after the host bookkeeping of a set call moved: host copy and device tables may differ
-  size_t lkf_lds = 0;
-};
+int lld_map_dev::RowPool::launch(hipStream_t st, const UploadBlock& B, const PoolPlan& P) const {
+  if (P.n_up <= 0) return LLD_OK;
+  hipLaunchKernelGGL(map_rows_kernel, dim3(std::min(P.n_up, 4096)), dim3(64), 0, st, P.n_up, B.dev(P.slot), B.dev(P.row), B.dev(P.src), B.dev(P.data), d_row, d_pool);
+  LLD_HIP_TRY(hipGetLastError());
+  return LLD_OK;
+}
 
 namespace {
 
@@ -1161,122 +848,6 @@ int lld_map_download_links(lld_map* m, int32_t n, const int32_t* slot, int32_t* 
   for (int i = 0; i < n; i++) if (nch[i] != start[i + 1] - start[i]) return LLD_ERR_HIP;       // the device's rows are not the host's: never with a sound map
   std::memcpy(parent, B.host(r_par), (size_t)n * 4); std::memcpy(n_cov, B.host(r_nc), (size_t)n * 4); std::memcpy(cov, B.host(r_cov), (size_t)n * 40);
   if (start[n]) std::memcpy(child, B.host(r_ch), (size_t)start[n] * 4);
-  return LLD_OK;
-}
-
-int lld_map_covisibility(lld_map* m, const lld_map_covisibility_in* in, lld_map_covisibility_out* out) {
-  if (!m || !in || !out) return LLD_ERR_INVALID;
-  lld_covisibility_out* L = &out->lists;
-  const int32_t nq = in->n_queries;
-  const bool conn = (in->flags & LLD_COVIS_CONNECTIONS) != 0, cull = (in->flags & LLD_COVIS_CULLING) != 0;
-  if (nq < 0) return LLD_ERR_INVALID;
-  if ((in->flags & ~(uint32_t)(LLD_COVIS_CONNECTIONS | LLD_COVIS_CULLING | LLD_MAP_COVIS_WRITE_COV)) || !(conn || cull)) return LLD_ERR_INVALID;
-  if ((in->flags & LLD_MAP_COVIS_WRITE_COV) && !conn) return LLD_ERR_INVALID;
-  if (m->poisoned) return LLD_ERR_HIP;
-  if (nq == 0) return LLD_OK;
-  if (!in->kf_slot || !out->status) return LLD_ERR_INVALID;
-  if (cull && (!L->n_mps || !L->n_redundant || !L->redundant)) return LLD_ERR_INVALID;
-  if (conn) {
-    if (L->conn_capacity < 0 || L->ordered_capacity < 0) return LLD_ERR_INVALID;
-    if (!L->conn_start || !L->ordered_start || !L->n_max || !L->kf_max || !L->updated) return LLD_ERR_INVALID;
-    if (L->conn_capacity > 0 && (!L->conn_kf || !L->conn_weight)) return LLD_ERR_INVALID;
-    if (L->ordered_capacity > 0 && (!L->ordered_kf || !L->ordered_weight)) return LLD_ERR_INVALID;
-  }
-  for (int q = 0; q < nq; q++) if (in->kf_slot[q] < 0 || in->kf_slot[q] >= m->lim.max_keyframes || !m->kf_set[in->kf_slot[q]]) return LLD_ERR_INVALID;
-  lld_ctx* ctx = m->ctx;
-  LLD_HIP_TRY(hipSetDevice(ctx->device));
-
-  // the staging range of a query: it cannot meet more keyframes than its points hold observations, nor more than the table answers for
-  // (the host's rows are the device's: every update before this call is queued before its kernels)
-  std::vector<int32_t> stage_off;
-  long long stage_total = 0;
-  if (conn) {
-    stage_off.resize((size_t)nq + 1);
-    for (int q = 0; q < nq; q++) {
-      const int s = in->kf_slot[q];
-      const int32_t* row = m->kpt.mirror.data() + m->kpt.off[s];
-      long long b = 0;
-      for (int j = 0; j < m->kpt.len[s] && b < kCovMax; j++) if (row[j] >= 0) b += m->obs.len[row[j]];
-      stage_off[q] = (int32_t)stage_total;
-      stage_total += std::min<long long>(b, kCovMax);
-    }
-    if (stage_total > 0x7fffffffLL) return LLD_ERR_UNSUPPORTED;
-    stage_off[nq] = (int32_t)stage_total;
-  }
-  const int32_t cap_conn = conn ? (int32_t)std::min<long long>(L->conn_capacity, stage_total) : 0;
-  const int32_t cap_ord = conn ? (int32_t)std::min<long long>(L->ordered_capacity, stage_total) : 0;
-
-  UploadBlock B;
-  const auto i_q = B.take<int32_t>(nq), i_so = B.take<int32_t>(conn ? (size_t)nq + 1 : 0);
-  B.end_upload();
-  const size_t out_off = B.size;
-  const auto r_cs = B.take<int32_t>(conn ? (size_t)nq + 1 : 0), r_rs = B.take<int32_t>(conn ? (size_t)nq + 1 : 0), r_tot = B.take<int32_t>(conn ? 2 : 0);
-  const auto r_nm = B.take<int32_t>(conn ? nq : 0), r_km = B.take<int32_t>(conn ? nq : 0); const auto r_up = B.take<uint8_t>(conn ? nq : 0), r_st = B.take<uint8_t>(nq);
-  const auto r_mp = B.take<int32_t>(cull ? nq : 0), r_rd = B.take<int32_t>(cull ? nq : 0); const auto r_rf = B.take<uint8_t>(cull ? nq : 0);
-  const auto r_ck = B.take<int32_t>(cap_conn), r_cw = B.take<int32_t>(cap_conn), r_rk = B.take<int32_t>(cap_ord), r_rw = B.take<int32_t>(cap_ord);
-  const size_t out_bytes = B.size - out_off;
-  const auto t_cc = B.take<int32_t>(conn ? nq : 0), t_co = B.take<int32_t>(conn ? nq : 0);
-  const auto t_sl = B.take<int32_t>((size_t)stage_total), t_sc = B.take<int32_t>((size_t)stage_total), t_kf = B.take<int32_t>((size_t)stage_total),
-             t_w = B.take<int32_t>((size_t)stage_total);
-  const auto t_key = B.take<u64>((size_t)stage_total);
-  int st;
-  void* hb; st = lld_ctx_pinned(ctx, out_off + out_bytes, &hb); if (st) return st;
-  void* db; st = lld_ctx_scratch(ctx, B.size + 256, &db); if (st) return st;
-  B.bind((char*)hb, (char*)db);
-  B.stage(i_q, in->kf_slot);
-  if (conn) B.stage(i_so, stage_off.data());
-
-  CovArgs A;
-  A.query = B.dev(i_q); A.stage_off = B.dev(i_so);
-  A.n_queries = nq; A.monocular = in->monocular ? 1 : 0; A.th = in->params.th; A.th_obs = in->params.th_obs; A.has_ext = m->d_ext ? 1 : 0;
-  A.flags = in->flags; A.ratio = in->params.redundant_ratio;
-  A.st_slot = B.dev(t_sl); A.st_cnt = B.dev(t_sc); A.st_kf = B.dev(t_kf); A.st_w = B.dev(t_w); A.st_key = B.dev(t_key);
-  A.cnt_conn = B.dev(t_cc); A.cnt_ord = B.dev(t_co);
-  A.n_max = B.dev(r_nm); A.kf_max = B.dev(r_km); A.updated = B.dev(r_up); A.status = B.dev(r_st);
-  A.n_mps = B.dev(r_mp); A.n_red = B.dev(r_rd); A.redundant = B.dev(r_rf);
-  A.cap_conn = cap_conn; A.cap_ord = cap_ord;
-  A.conn_start = B.dev(r_cs); A.ord_start = B.dev(r_rs); A.totals = B.dev(r_tot);
-  A.conn_kf = B.dev(r_ck); A.conn_w = B.dev(r_cw); A.ord_kf = B.dev(r_rk); A.ord_w = B.dev(r_rw);
-
-  if (conn && !m->cov_lds_set) {
-    LLD_HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(&map_covis_query_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)kCovLds));
-    m->cov_lds_set = true;
-  }
-  hipStream_t sm = ctx->stream;
-  struct Events {                                                      // destroyed on every way out
-    hipEvent_t e[4] = {nullptr, nullptr, nullptr, nullptr};
-    ~Events() { for (int k = 0; k < 4; ++k) if (e[k]) (void)hipEventDestroy(e[k]); }
-  } events;
-  hipEvent_t* ev = events.e;
-  const bool timed = L->phase_ms != nullptr;
-  if (timed) for (int k = 0; k < 4; ++k) LLD_HIP_TRY(hipEventCreate(&ev[k]));
-  if (timed) LLD_HIP_TRY(hipEventRecord(ev[0], sm));
-  LLD_HIP_TRY(hipMemcpyAsync(B.d, B.h, B.up_bytes, hipMemcpyHostToDevice, sm));
-  if (timed) LLD_HIP_TRY(hipEventRecord(ev[1], sm));
-  hipLaunchKernelGGL(map_covis_query_kernel, dim3(nq), dim3(kCovThreads), conn ? kCovLds : 0, sm, m->D, m->X, A);
-  if (conn) hipLaunchKernelGGL(map_covis_pack_kernel, dim3(nq), dim3(kCovThreads), 0, sm, A);
-  LLD_HIP_TRY(hipGetLastError());
-  if (timed) LLD_HIP_TRY(hipEventRecord(ev[2], sm));
-  LLD_HIP_TRY(hipMemcpyAsync(B.h + out_off, B.d + out_off, out_bytes, hipMemcpyDeviceToHost, sm));
-  if (timed) LLD_HIP_TRY(hipEventRecord(ev[3], sm));
-  LLD_HIP_TRY(hipStreamSynchronize(sm));
-  if (timed) {
-    for (int k = 0; k < 3; ++k) LLD_HIP_TRY(hipEventElapsedTime(&L->phase_ms[k], ev[k], ev[k + 1]));
-  }
-
-  if (conn) {
-    const int32_t* tot = B.host(r_tot);
-    L->n_conn = tot[0]; L->n_ordered = tot[1];
-    if (tot[0] > L->conn_capacity || tot[1] > L->ordered_capacity) return LLD_ERR_INVALID;
-    std::memcpy(L->conn_start, B.host(r_cs), (size_t)(nq + 1) * 4); std::memcpy(L->ordered_start, B.host(r_rs), (size_t)(nq + 1) * 4);
-    std::memcpy(L->n_max, B.host(r_nm), (size_t)nq * 4); std::memcpy(L->kf_max, B.host(r_km), (size_t)nq * 4); std::memcpy(L->updated, B.host(r_up), (size_t)nq);
-    if (tot[0]) { std::memcpy(L->conn_kf, B.host(r_ck), (size_t)tot[0] * 4); std::memcpy(L->conn_weight, B.host(r_cw), (size_t)tot[0] * 4); }
-    if (tot[1]) { std::memcpy(L->ordered_kf, B.host(r_rk), (size_t)tot[1] * 4); std::memcpy(L->ordered_weight, B.host(r_rw), (size_t)tot[1] * 4); }
-  }
-  if (cull) {
-    std::memcpy(L->n_mps, B.host(r_mp), (size_t)nq * 4); std::memcpy(L->n_redundant, B.host(r_rd), (size_t)nq * 4); std::memcpy(L->redundant, B.host(r_rf), (size_t)nq);
-  }
-  std::memcpy(out->status, B.host(r_st), (size_t)nq);
   return LLD_OK;
 }
 

@@ -1,0 +1,117 @@
+// lld_map_tables.h — the resident map's tables as the files that run on them see them: the device pointers (MapDev, MapExt), the host's
+// bookkeeping of the variable-length rows (RowPool) and the handle that owns both (struct lld_map).  lld_map.hip creates, fills and frees
+// them; lld_map_covis.hip walks them.  lld_map_internal.h stays the narrow face lld_frame_track.hip sees.  Nothing here is exported.
+#ifndef LLD_MAP_TABLES_H
+#define LLD_MAP_TABLES_H
+
+#include "lld_common.h"
+#include "lld_upload_block.h"
+
+namespace lld_map_dev {
+
+using lld_track::Span;
+using lld_track::UploadBlock;
+typedef unsigned long long u64;
+
+// The layout of a slot's rows is described at the top of lld_map.hip.
+struct MapDev {
+  int max_kf, max_pt, max_ln, dim, max_lp, max_ll;
+  float* p_pos; float* p_nrm; float* p_mind; float* p_maxd; uint32_t* p_desc; uint8_t* p_state; int2* p_obs; int32_t* obs_pool;
+  double* l_x0; double* l_dir; double* l_x1; double* l_x2; float* l_desc; uint8_t* l_bad;
+  u64* k_key; uint8_t* k_bad; int32_t* k_parent; int32_t* k_cov; int32_t* k_ncov; int2* k_child; int2* k_pt; int2* k_ln;
+  int32_t* child_pool; int32_t* kpt_pool; int32_t* kln_pool;
+  // per call: vote counters (zero between calls), the slots that got a first vote, first occurrences, the lists
+  int32_t* cnt; int32_t* touched; int32_t* fc; u64* p_first; u64* l_first;
+  int32_t* lkf; int32_t* lkf_np; int32_t* lkf_nl; int32_t* lpts; int32_t* llns; int32_t* st;
+};
+
+// The culling tables.  All null until the first lld_map_set_observations_indexed / lld_map_set_keyframe_keypoints.
+//   point slot s     p_nobs = MapPoint::Observations(), p_idx = (offset, length) in idx_pool of the keypoint indices, parallel to the p_obs row
+//   keyframe slot s  k_oct / k_dep = (offset, length) in oct_pool / dep_pool of mvKeysUn[i].octave / the bits of mvDepth[i], k_thd = mThDepth
+struct MapExt {
+  int32_t* p_nobs; int2* p_idx; int32_t* idx_pool; int2* k_oct; int2* k_dep; int32_t* oct_pool; int32_t* dep_pool; float* k_thd;
+};
+
+// ------------------------------------------------------------------------------------------------ host: the pools
+struct PoolPlan { bool repack = false; int n_up = 0; size_t n_data = 0; int64_t live_after = 0; Span<int32_t> slot, src, data; Span<int2> row; };
+
+struct RowPool {
+  int rows = 0; int64_t limit = 0, cap = 0, tail = 0, live = 0;
+  std::vector<int32_t> off, len, rcap, mirror;
+  int2* d_row = nullptr; int32_t* d_pool = nullptr;
+  void init(int rows_, int64_t limit_) {
+    rows = rows_; limit = limit_; cap = 2 * limit_; tail = live = 0;
+    off.assign(rows, 0); len.assign(rows, 0); rcap.assign(rows, 0); mirror.assign((size_t)std::max<int64_t>(cap, 1), 0);
+  }
+  void reset() { tail = live = 0; std::fill(off.begin(), off.end(), 0); std::fill(len.begin(), len.end(), 0); std::fill(rcap.begin(), rcap.end(), 0); }
+  // false: the live total would pass the limit.  Nothing is changed.
+  bool plan(int n, const int32_t* slot, const int32_t* start, PoolPlan& P) const {
+    int64_t lv = live, t = tail; size_t nd = 0;
+    for (int i = 0; i < n; i++) {
+      const int nl = start[i + 1] - start[i], s = slot[i];
+      lv += nl - len[s]; nd += nl;
+      if (nl > rcap[s]) t += nl;
+    }
+    if (lv > limit) return false;
+    P.live_after = lv; P.repack = t > cap;
+    P.n_up = P.repack ? rows : n; P.n_data = P.repack ? (size_t)lv : nd;
+    return true;
+  }
+  void reserve(UploadBlock& B, PoolPlan& P) const {
+    P.slot = B.take<int32_t>(P.n_up); P.src = B.take<int32_t>(P.n_up); P.row = B.take<int2>(P.n_up); P.data = B.take<int32_t>(P.n_data);
+  }
+  void commit(const UploadBlock& B, const PoolPlan& P, int n, const int32_t* slot, const int32_t* start, const int32_t* data) {
+    int32_t* hs = B.host(P.slot); int32_t* hsrc = B.host(P.src); int2* hrow = B.host(P.row); int32_t* hd = B.host(P.data);
+    if (!P.repack) {
+      int32_t run = 0;
+      for (int i = 0; i < n; i++) {
+        const int nl = start[i + 1] - start[i], s = slot[i];
+        if (nl > rcap[s]) { off[s] = (int32_t)tail; rcap[s] = nl; tail += nl; }
+        len[s] = nl;
+        if (nl) { std::memcpy(&mirror[off[s]], data + start[i], (size_t)nl * 4); std::memcpy(hd + run, data + start[i], (size_t)nl * 4); }
+        hs[i] = s; hsrc[i] = run; hrow[i] = make_int2(off[s], nl); run += nl;
+      }
+    } else {
+      // every row, packed tightly in slot order: the rows of this call from the caller's arrays, the others from the host copy
+      std::vector<int32_t> upd(rows, -1), packed((size_t)std::max<int64_t>(cap, 1));
+      for (int i = 0; i < n; i++) upd[slot[i]] = i;
+      int32_t run = 0;
+      for (int r = 0; r < rows; r++) {
+        const int i = upd[r];
+        const int nl = i >= 0 ? start[i + 1] - start[i] : len[r];
+        const int32_t* from = i >= 0 ? data + start[i] : mirror.data() + off[r];
+        if (nl) std::memcpy(&packed[run], from, (size_t)nl * 4);
+        off[r] = run; len[r] = nl; rcap[r] = nl;
+        hs[r] = r; hsrc[r] = run; hrow[r] = make_int2(run, nl); run += nl;
+      }
+      mirror.swap(packed); tail = run;
+      if (run) std::memcpy(hd, mirror.data(), (size_t)run * 4);
+    }
+    live = P.live_after;
+  }
+  int launch(hipStream_t st, const UploadBlock& B, const PoolPlan& P) const;      // defined in lld_map.hip: it names map_rows_kernel
+};
+
+}  // namespace lld_map_dev
+
+struct lld_map {
+  lld_ctx* ctx = nullptr;
+  lld_map_limits lim{};
+  lld_map_dev::MapDev D{};
+  char* d_tables = nullptr; size_t first_off = 0, first_bytes = 0, down_off = 0, down_bytes = 0, tables_bytes = 0;
+  size_t o_lkf = 0, o_lpts = 0, o_llns = 0;                         // inside the downloaded span, which starts with st
+  lld_map_dev::RowPool obs, child, kpt, kln;
+  // the culling tables (MapExt): allocated by the first setter that fills them
+  lld_map_dev::MapExt X{}; char* d_ext = nullptr; size_t ext_bytes = 0; lld_map_dev::RowPool idx, koct, kdep;
+  std::vector<uint8_t> kf_set;              // lld_map_set_keyframes named the slot since the last clear
+  bool cov_lds_set = false;                 // map_covis_query_kernel was granted its 64 KB of dynamic LDS
+  std::vector<uint32_t> stamp_pt, stamp_kf, stamp_ln; uint32_t epoch = 0;
+  // the staging of lld_map_set_*: pinned block, device block, the event of the last copy
+  char* h_up = nullptr; size_t h_up_bytes = 0; char* d_up = nullptr; size_t d_up_bytes = 0; hipEvent_t uploaded = nullptr; bool upload_pending = false;
+  char* h_down = nullptr;
+  unsigned long long serial = 0;            // counts lld_frame_track_update_local_map calls: the lists in the tables are the last one's
+  bool poisoned = false;                    // a HIP failure after the host bookkeeping of a set call moved: host copy and device tables may differ
+  size_t lkf_lds = 0;
+};
+
+#endif

@@ -71,6 +71,25 @@ def test_observation_counts_at_the_lane_and_wavefront_boundaries(gpu_ctx):
     assert conn.n_max[0] >= 16 and conn.ordered_start[1] > 200 and conn.ordered_start[2] - conn.ordered_start[1] == 1
 
 
+@pytest.mark.parametrize("th", [1000, 15, 4])
+def test_sparse_slots_over_three_passes_give_slots_not_ranks(gpu_ctx, th):
+    """The staged keys carry a keyframe's rank among the connected ones, the outputs its slot: connected slots that are sparse over more
+    than one 256-lane pass of the table, in a second query whose staging range starts behind the first's.  The lists are written out by
+    hand (the lower slot of the tied maxima wins, and its rank, 3, is not its slot; equal weights come out in descending slot order)."""
+    b = S.Builder(600); own = 7
+    pts = S._shared(b, own, {5: 3, 255: 2, 256: 4, 300: 6, 599: 6})
+    b.query(own, pts); b.query(599, pts[:3])
+    sc = b.scene()
+    got = run(gpu_ctx, sc, CV.CONNECTIONS, th=th)[0]
+    same_conn(got, R.update_connections_ref(sc, th))
+    assert got.conn_start.tolist() == [0, 5, 7] and got.conn_kf.tolist() == [5, 255, 256, 300, 599, 5, 7]
+    assert got.conn_weight.tolist() == [3, 2, 4, 6, 6, 3, 3] and got.n_max.tolist() == [6, 3] and got.kf_max.tolist() == [300, 5]
+    if th == 4:
+        assert got.ordered_start.tolist() == [0, 3, 4] and got.ordered_kf.tolist() == [599, 300, 256, 5] and got.ordered_weight.tolist() == [6, 6, 4, 3]
+    else:
+        assert got.ordered_kf.tolist() == [300, 5] and got.ordered_weight.tolist() == [6, 3]
+
+
 @pytest.mark.parametrize("n_kf", [1, 64, 65, 16384])
 def test_keyframe_table_sizes(gpu_ctx, n_kf):
     rng = np.random.default_rng(n_kf)
