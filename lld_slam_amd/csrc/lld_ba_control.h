@@ -1,4 +1,4 @@
-// lld_ba_control.h - LM control of the batched bundle adjustment: ba_control, ba_backsub_ctl, classification between the rounds, final classification + read-back.
+// lld_ba_control.h - LM control of the batched bundle adjustment: ba_control, ba_backsub_ctl, per-edge chi2 where it is read, classification between the rounds, final classification + read-back.
 // Part of lld_ba_kernels.h (split by kernel family in round 6; no behaviour change): included from there INSIDE namespace lldba, after the shared types and helpers.
 // Not a stand-alone header.
 
@@ -28,6 +28,7 @@ __device__ __forceinline__ void ba_control_body(const BAArrays& A, const BAWin& 
     double rho = (S.currentChi - tempChi);
     scale += 1e-3;
     rho /= scale;
+    S.ev = S.cur ^ 1;                              // the errors of every active edge now belong to the trial buffer, whatever becomes of the trial
     if (rho > 0 && isfinite(tempChi)) {
       double alpha = 1. - (2 * rho - 1) * (2 * rho - 1) * (2 * rho - 1);
       alpha = fmin(alpha, 2. / 3.);
@@ -152,6 +153,29 @@ __global__ __launch_bounds__(kLmThreads) void ba_backsub_ctl_kernel(BAArrays A, 
   }
 }
 
+// ================================================================== e->chi2() where it is read
+// The chi2 of one edge on state buffer `buf`, with the functions and in the order of the trial evaluations of ba_backsub_pt / ba_backsub_ln
+// (point_edge_trial, line_obs_trial), which do not store it: the classification and the read-back compute it from BAState::ev.
+__device__ __forceinline__ double point_edge_chi2_at(const BAArrays& A, const BAWin& W, int buf, int e) {
+  const Vec3 Xn = load_pt(A, buf, W.pt_off + A.pe_pt[e]);
+  const Pose T = load_cam(A, buf, W.cam_off + pt_cam_of<kPkRuntime>(A, e));
+  const Vec3 Xc = pose_map(T, Xn);
+  const PtObs ob = pt_obs_of<kPkRuntime>(A, e);
+  const bool stereo = !(ob.ur < 0);
+  double r[3];
+  point_residual_iz(W.cam, Xc, rcp_nr(Xc.z), ob.u, ob.v, ob.ur, stereo, true, r);
+  return chi2_of(r, stereo ? 3 : 2, ob.s);
+}
+__device__ __forceinline__ double line_edge_chi2_at(const BAArrays& A, const BAWin& W, int buf, int e) {   // e: a VALID edge slot
+  const LineGeom G = line_geom(load_ln(A, buf, W.ln_off + ln_line_of<kPkRuntime>(A, e >> 1)));
+  const Pose T = load_cam(A, buf, W.cam_off + ln_cam_of<kPkRuntime>(A, e >> 1));
+  const Vec3 X1m = pose_map(T, G.X1), X2m = pose_map(T, G.X2);
+  const LnSeg sg = ln_seg_of<kPkRuntime>(A, e);
+  double r[2];
+  line_residual_t<true>(W.cam, (e & 1) ? W.cam.bx_right : 0.0, X1m, X2m, sg.xs, sg.ys, sg.xe, sg.ye, r, nullptr);
+  return chi2_of(r, 2, ln_info_of<kPkRuntime>(A, e));
+}
+
 // ================================================================== classification between the rounds
 // grid (nb_pt + nb_ln, nW), windows in PH_TRANSITION only.
 __global__ __launch_bounds__(kLmThreads) void ba_classify_kernel(BAArrays A, const BAWin* __restrict__ wins, BAState* __restrict__ st) {
@@ -162,7 +186,7 @@ __global__ __launch_bounds__(kLmThreads) void ba_classify_kernel(BAArrays A, con
   BAState& S = st[wrow];
   if (S.phase != PH_TRANSITION) return;
   if ((int)blockIdx.x >= W.nb_pt + W.nb_ln) return;
-  const int cur = S.cur;
+  const int cur = S.cur, ev = S.ev;
   const CamK cam = W.cam;
   double n_active = 0.0;
   // Two phases per workgroup: the edges of the workgroup's landmarks (a contiguous range) are classified by EDGE lanes - coalesced reads,
@@ -176,9 +200,12 @@ __global__ __launch_bounds__(kLmThreads) void ba_classify_kernel(BAArrays A, con
       const Pose T = load_cam(A, cur, W.cam_off + pt_cam_of<kPkRuntime>(A, e));
       const bool depth_pos = pose_map(T, X).z > 0.0;
       const bool stereo = pt_obs_stereo<kPkRuntime>(A, e);
-      if (A.pe_chi2[e] > (stereo ? 7.815 : 5.991) || !depth_pos) fl |= EF_LEVEL1;      // Optimizer.cc:1246,1260
+      const double c2 = point_edge_chi2_at(A, W, ev, e);                               // (round 1 evaluates every point edge)
+      A.pe_chi2[e] = c2;                                                               // the snapshot for the edges round 2 leaves out
+      if (c2 > (stereo ? 7.815 : 5.991) || !depth_pos) fl |= EF_LEVEL1;                // Optimizer.cc:1246,1260
       fl &= (uint8_t)~EF_ROBUST;                                                       // e->setRobustKernel(0)
       A.pe_flags[e] = fl;
+      if (fl & EF_LEVEL1) A.pe_ws[e] = 0.0;                                            // (the linearisations of round 2 skip the edge; the Schur staging reads its weight)
     }
     __syncthreads();
     const int p = p0 + threadIdx.x;
@@ -202,7 +229,9 @@ __global__ __launch_bounds__(kLmThreads) void ba_classify_kernel(BAArrays A, con
       const Pose T = load_cam(A, cur, W.cam_off + ln_cam_of<kPkRuntime>(A, e >> 1));
       const LnSeg sg = ln_seg_of<kPkRuntime>(A, e);
       const bool depth_pos = line_depth_positive(cam, (e & 1) ? cam.bx_right : 0.0, T, c0, c1, L.alpha, sg.xs, sg.ys, sg.xe, sg.ye);
-      if (A.le_chi2[e] > th * th || !depth_pos) fl |= EF_LEVEL1;                       // LineOptimizer.cc:141-153
+      const double c2 = line_edge_chi2_at(A, W, ev, e);                                // (round 1 evaluates every valid line edge)
+      A.le_chi2[e] = c2;
+      if (c2 > th * th || !depth_pos) fl |= EF_LEVEL1;                                 // LineOptimizer.cc:141-153
       fl &= (uint8_t)~EF_ROBUST;
       A.le_flags[e] = fl;
     }
@@ -265,7 +294,7 @@ __global__ __launch_bounds__(kLmThreads) void ba_finalize_kernel(BAArrays A, con
   const BAState& S = st[blockIdx.y];
   if (S.phase != PH_FINALIZE) return;
   if ((int)blockIdx.x >= W.nb_pt + W.nb_ln + 1) return;
-  const int cur = S.cur;
+  const int cur = S.cur, ev = S.ev;
   const CamK cam = W.cam;
   // Optimizer.cc:1220-1222: a stop request before the first optimize() returns without classifying or writing anything
   const bool global = W.protocol == 1;                     // Optimizer::BundleAdjustment erases nothing: all flags stay 0
@@ -304,7 +333,10 @@ __global__ __launch_bounds__(kLmThreads) void ba_finalize_kernel(BAArrays A, con
       const Pose T = load_cam(A, cur, W.cam_off + pt_cam_of<kPkRuntime>(A, e));
       const bool depth_pos = pose_map(T, X).z > 0.0;
       const bool stereo = pt_obs_stereo<kPkRuntime>(A, e);
-      o_pe[e - W.pe_off] = (!untouched && !global && (A.pe_chi2[e] > (stereo ? 7.815 : 5.991) || !depth_pos)) ? 1 : 0;      // Optimizer.cc:1290,1305
+      // e->chi2() is the error of the edge's last evaluation: the window's last trial if its last round had the edge in (level 0 - a landmark
+      // is inactive only when all its edges are level 1), else what the classification between the rounds saw (0.0 if none ran)
+      const double c2 = (untouched || global) ? 0.0 : (A.pe_flags[e] & EF_LEVEL1) ? A.pe_chi2[e] : point_edge_chi2_at(A, W, ev, e);
+      o_pe[e - W.pe_off] = (!untouched && !global && (c2 > (stereo ? 7.815 : 5.991) || !depth_pos)) ? 1 : 0;      // Optimizer.cc:1290,1305
     }
   } else {
     const int l = (blockIdx.x - W.nb_pt) * kLmThreads + threadIdx.x;
@@ -338,7 +370,6 @@ __global__ __launch_bounds__(kLmThreads) void ba_finalize_kernel(BAArrays A, con
       double r[2];
       line_residual(cam, bx, pose_map(T, X1), pose_map(T, X2), sg.xs, sg.ys, sg.xe, sg.ye, r, nullptr);
       const double c2 = chi2_of(r, 2, ln_info_of<kPkRuntime>(A, e));
-      A.le_chi2[e] = c2;
       const double th = (fl & EF_PAIRSTEREO) ? W.th_ln_stereo : W.th_ln_mono;
       o_le[e - W.le_off] = (!global && (c2 > th * th || !depth_pos)) ? 1 : 0;                    // LineOptimizer.cc:185-196
     }

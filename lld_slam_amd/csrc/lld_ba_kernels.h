@@ -108,7 +108,9 @@ struct BAState {               // mutable per-window LM state
   unsigned long long maxdiag_bits;
   double chi2_round1, chi2_final;
   int lm_iterations[2], lm_trials[2];
-  int pcg_iterations, aborted, n_active_edges, pad;
+  int pcg_iterations, aborted, n_active_edges;
+  int ev;                      // the state buffer the window's last LM trial evaluated its errors on (set by ba_control_body: cur after an accepted trial, cur ^ 1 after a
+                               // rejected one - g2o's pop() restores estimates, not errors); ba_classify / ba_finalize compute e->chi2() from it
   int ticket_lin, ticket_bs, ticket_cls, pad2;   // "last workgroup of the window" tickets of ba_hpp_reduce / ba_backsub_ctl / ba_classify (zero between launches)
 };
 
@@ -168,8 +170,10 @@ struct BAArrays {
   const double *le_xs, *le_ys, *le_xe, *le_ye, *le_s;      // (b_x of a slot is 0 for the left and CamK::bx_right for the right image; its validity follows from startPointX of the right segment)
   // per-edge mutable
   uint8_t *pe_flags, *le_flags;
-  double *pe_chi2, *le_chi2;
-  double *pe_ws;               // [NPE] rho' * invSigma2 of the edge at the linearisation point (0 for level-1 edges), NEGATED for a stereo edge (the weight is >= 0: its sign
+  double *pe_chi2, *le_chi2;   // e->chi2() as the classification between the rounds saw it: written ONCE per solve, by ba_classify_kernel for every edge (0.0 from ba_init until then).
+                               //       No linearisation or trial stores chi2: ba_classify / ba_finalize recompute it from BAState::ev.  The read-back reads pe_chi2 for the
+                               //       point edges round 2 left out (they keep the error of their last evaluation); le_chi2 has no reader
+  double *pe_ws;               // [NPE] rho' * invSigma2 of the edge at the linearisation point (0 for level-1 edges: written by ba_init and, where the flag is set, by ba_classify_kernel), NEGATED for a stereo edge (the weight is >= 0: its sign
                                //       bit carries the one flag the Schur staging needs, which spares it a gather of the flag byte - round 5): the 6x3 Hpl
                                //       block of a point edge is recomputed from it (point_hpl) instead of being stored
   double *lo_W;                // [NLO*24]  Hpl block 6x4 per (line, KF) observation: left + right edge summed

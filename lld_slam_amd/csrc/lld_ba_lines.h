@@ -1,6 +1,8 @@
 // lld_ba_lines.h - Line landmark kernels of the batched bundle adjustment: linearisation (ba_linearize_ln_*, ba_linearize_both) and back-substitution + trial errors (ba_backsub_ln_*), one lane per (line, KF) OBSERVATION.
 // Part of lld_ba_kernels.h (split by kernel family in round 6; no behaviour change): included from there INSIDE namespace lldba, after the shared types and helpers.
 // Not a stand-alone header.
+// e->chi2(): summed here, stored nowhere (see lld_ba_points.h).  ba_classify_kernel computes it with line_geom + line_residual_t<true> + chi2_of as
+// line_obs_trial does, on BAState::ev, and keeps it in BAArrays::le_chi2 (no reader: ba_finalize_kernel evaluates every line edge again at the final state).
 
 // ================================================================== line landmarks: one lane per (line, KF) OBSERVATION
 // Same scheme as the point kernels with the observation as the unit: a lane linearises the left and (if present) right image
@@ -41,14 +43,12 @@ __device__ __forceinline__ double line_obs_linearize(const BAArrays& A, const BA
   const Vec3 X1m = pose_map(T, G.X1), X2m = pose_map(T, G.X2);
 #pragma unroll
   for (int side = 0; side < 2; side++) {
-    const int e = 2 * o + side;
     const uint8_t fl = I.fl[side];
     if (!(fl & EF_VALID) || (fl & EF_LEVEL1)) continue;
     double r[2]; LineAdj adj;
     line_residual_t<true>(W.cam, side == 1 ? W.cam.bx_right : 0.0, X1m, X2m, I.xs[side], I.ys[side], I.xe[side], I.ye[side], r, &adj);
     const double s = I.s[side];
     const double c2 = chi2_of(r, 2, s);
-    A.le_chi2[e] = c2;
     double w = 1.0, rho0 = c2;
     if (fl & EF_ROBUST) rho0 = huber_nr(c2, (fl & EF_PAIRSTEREO) ? W.th_ln_stereo : W.th_ln_mono, &w);
     chi += rho0;
@@ -216,13 +216,11 @@ __device__ __forceinline__ double line_obs_trial(const BAArrays& A, const BAWin&
   const Vec3 X1m = pose_map(T, G.X1), X2m = pose_map(T, G.X2);
 #pragma unroll
   for (int side = 0; side < 2; side++) {
-    const int e = 2 * o + side;
     const uint8_t fl = I.fl[side];
     if (!(fl & EF_VALID) || (fl & EF_LEVEL1)) continue;
     double r[2];
     line_residual_t<true>(W.cam, side == 1 ? W.cam.bx_right : 0.0, X1m, X2m, I.xs[side], I.ys[side], I.xe[side], I.ye[side], r, nullptr);
     const double c2 = chi2_of(r, 2, I.s[side]);
-    A.le_chi2[e] = c2;
     double w, rho0 = c2;
     if (fl & EF_ROBUST) rho0 = huber_nr(c2, (fl & EF_PAIRSTEREO) ? W.th_ln_stereo : W.th_ln_mono, &w);
     chi += rho0;

@@ -1,6 +1,11 @@
 // lld_ba_points.h - Point landmark kernels of the batched bundle adjustment: linearisation (ba_linearize_pt_*) and back-substitution + trial errors (ba_backsub_pt_*), one lane per EDGE.
 // Part of lld_ba_kernels.h (split by kernel family in round 6; no behaviour change): included from there INSIDE namespace lldba, after the shared types and helpers.
 // Not a stand-alone header.
+// e->chi2(): these kernels SUM the (robust) chi2 of the edges they evaluate and store none of it.  The two readers of a per-edge chi2 - ba_classify_kernel
+// between the rounds and ba_finalize_kernel at the read-back (lld_ba_control.h) - compute it themselves, with point_residual_iz + chi2_of as
+// point_edge_trial does, on the buffer the window's last trial evaluated (BAState::ev); BAArrays::pe_chi2 is written once per solve, by the
+// classification.  (Until round 6 every linearisation and every trial stored it: 8 B per edge and launch, two thirds of what ba_backsub_pt wrote.)
+// BAArrays::pe_ws: written by the linearisation for the edges it evaluates; the 0.0 of a level-1 edge by ba_init and by the classification that sets the flag.
 
 // ================================================================== point landmarks: one lane per EDGE
 // Edge SoA arrays are read fully coalesced (lane i <-> edge e0 + i); what belongs to a landmark (Hll, b_l, the back-substituted
@@ -62,7 +67,7 @@ __device__ __forceinline__ void wave_sum_n(double* v) {
 
 struct PtEdgeLin { double r[3], Jp[9], Jc[18], ws, rho0; bool stereo; };
 
-// residual, chi2 (stored), Huber weight, Jacobians of one active point edge at the linearisation point
+// residual, chi2, Huber weight, Jacobians of one active point edge at the linearisation point
 template <int kPk>
 __device__ __forceinline__ void point_edge_linearize(const BAArrays& A, const BAWin& W, int cur, int e, uint8_t fl, int c, const Vec3& X, PtEdgeLin& L) {
   const Pose T = load_cam(A, cur, W.cam_off + c);
@@ -72,7 +77,6 @@ __device__ __forceinline__ void point_edge_linearize(const BAArrays& A, const BA
   point_residual_iz(W.cam, Xc, rcp_nr(Xc.z), ob.u, ob.v, ob.ur, L.stereo, true, L.r);
   const double s = ob.s;
   const double c2 = chi2_of(L.r, L.stereo ? 3 : 2, s);
-  A.pe_chi2[e] = c2;
   double w = 1.0;
   L.rho0 = c2;
   if (fl & EF_ROBUST) L.rho0 = huber_nr(c2, L.stereo ? W.th_stereo : W.th_mono, &w);
@@ -227,10 +231,9 @@ __device__ __forceinline__ void ba_linearize_pt_body(const BAArrays& A, const BA
       double hb[9];
 #pragma unroll
       for (int i = 0; i < 9; i++) hb[i] = 0.0;
-      if (has && (fl & EF_LEVEL1)) A.pe_ws[e] = 0.0;
       if (lm_act && !(fl & EF_LEVEL1)) {
         double hp[27], ws_e, rho0_e;
-        A.pe_chi2[e] = point_edge_blocks_closed(W, pose_load(cams + c * 7), X, ob, fl, ws_e, rho0_e, hb, hp);
+        point_edge_blocks_closed(W, pose_load(cams + c * 7), X, ob, fl, ws_e, rho0_e, hb, hp);
         A.pe_ws[e] = (fl & EF_STEREO) ? -ws_e : ws_e;
         chi += rho0_e;
         if (c < W.n_free) {
@@ -257,7 +260,7 @@ __device__ __forceinline__ void ba_linearize_pt_body(const BAArrays& A, const BA
         for (int sidx = lane; sidx < T.ne; sidx += 64) {
           const int e = T.e0 + sidx;
           const uint8_t fl = A.pe_flags[e];
-          if (fl & EF_LEVEL1) { A.pe_ws[e] = 0.0; continue; }
+          if (fl & EF_LEVEL1) continue;                    // (its weight is 0 since the classification set the flag)
           const int c = pt_cam_of<kPk>(A, e);
           PtEdgeLin L;
           point_edge_linearize<kPk>(A, W, cur, e, fl, c, X, L);
@@ -318,7 +321,7 @@ __device__ __forceinline__ void point_edge_wtx(const BAArrays& A, const BAWin& W
 #pragma unroll
   for (int k = 0; k < 3; k++) t[k] = Jp[k] * uu[0] + Jp[3 + k] * uu[1] + Jp[6 + k] * uu[2];
 }
-// trial-state residual of one active point edge: stores chi2, returns its (robust) cost
+// trial-state residual of one active point edge: returns its (robust) cost
 template <int kPk>
 __device__ __forceinline__ double point_edge_trial(const BAArrays& A, const BAWin& W, int nxt, int e, uint8_t fl, int c, const Vec3& Xn) {
   const Pose T = load_cam(A, nxt, W.cam_off + c);
@@ -328,7 +331,6 @@ __device__ __forceinline__ double point_edge_trial(const BAArrays& A, const BAWi
   double r[3];
   point_residual_iz(W.cam, Xc, rcp_nr(Xc.z), ob.u, ob.v, ob.ur, stereo, true, r);
   const double c2 = chi2_of(r, stereo ? 3 : 2, ob.s);
-  A.pe_chi2[e] = c2;
   double w, rho0 = c2;
   if (fl & EF_ROBUST) rho0 = huber_nr(c2, stereo ? W.th_stereo : W.th_mono, &w);
   return rho0;
@@ -442,7 +444,6 @@ __device__ __forceinline__ void ba_backsub_pt_body(const BAArrays& A, const BAWi
         double r[3];
         point_residual_iz(W.cam, Xc, rcp_nr(Xc.z), ob.u, ob.v, ob.ur, stereo, true, r);
         const double c2 = chi2_of(r, stereo ? 3 : 2, ob.s);
-        A.pe_chi2[e] = c2;
         double w, rho0 = c2;
         if (fl & EF_ROBUST) rho0 = huber_nr(c2, stereo ? W.th_stereo : W.th_mono, &w);
         chi += rho0;
