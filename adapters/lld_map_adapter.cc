@@ -6,6 +6,7 @@
 #include <cstdint>
 #include <cstring>
 #include <map>
+#include <mutex>
 #include <set>
 #include <stdexcept>
 #include <string>
@@ -108,6 +109,138 @@ void MapOnDevice::UpdateKeyFrames(const std::vector<KeyFrame*>& keyframes) {
   }
   oct.push_back(0); dep.push_back(0.f);
   check(lld_map_set_keyframe_keypoints(m_, (int32_t)n, slot.data(), ps.data(), oct.data(), dep.data(), thd.data()), "lld_map_set_keyframe_keypoints");
+  if (!ba_) return;
+  // mnId, pose, and one (u, v, uR) per entry of the point row, one keyline with its stereo partner per entry of the line row
+  std::vector<uint64_t> id(n); std::vector<float> Tcw(16 * n), uvr, left, right; std::vector<int32_t> loct;
+  for (size_t i = 0; i < n; i++) {
+    const KeyFrame* pKF = keyframes[i];
+    id[i] = pKF->mnId;
+    const lld_slam::Mat T = pKF->GetPose();
+    std::memcpy(&Tcw[16 * i], T.ptr<float>(), 64);
+    for (int32_t j = 0; j < ps[i + 1] - ps[i]; j++) {
+      const bool has = (size_t)j < pKF->mvKeysUn.size();
+      uvr.push_back(has ? pKF->mvKeysUn[j].pt.x : 0.f); uvr.push_back(has ? pKF->mvKeysUn[j].pt.y : 0.f);
+      uvr.push_back((size_t)j < pKF->mvuRight.size() ? pKF->mvuRight[j] : -1.f);
+    }
+    for (int32_t j = 0; j < ls[i + 1] - ls[i]; j++) {
+      const bool has = (size_t)j < pKF->mvLinesLeft.size();
+      const lld_slam::KeyLine kl = has ? pKF->mvLinesLeft[j] : lld_slam::KeyLine();
+      left.push_back(kl.startPointX); left.push_back(kl.startPointY); left.push_back(kl.endPointX); left.push_back(kl.endPointY);
+      const int match = has && (size_t)j < pKF->line_matches.size() ? pKF->line_matches[j] : -1;
+      if (match >= 0) {
+        const lld_slam::KeyLine& kr = pKF->mvLinesRight[match];
+        right.push_back(kr.startPointX); right.push_back(kr.startPointY); right.push_back(kr.endPointX); right.push_back(kr.endPointY);
+        loct.push_back(kl.octave); loct.push_back(kr.octave);
+      } else {
+        for (int k = 0; k < 4; k++) right.push_back(-1.f);                      // kl_empty (Optimizer.cc:1203-1209)
+        loct.push_back(kl.octave); loct.push_back(0);
+      }
+    }
+  }
+  uvr.push_back(0.f); left.push_back(0.f); right.push_back(0.f); loct.push_back(0);
+  check(lld_map_set_keyframe_features(m_, (int32_t)n, slot.data(), id.data(), Tcw.data(), ps.data(), uvr.data(), ls.data(), left.data(), right.data(), loct.data()),
+        "lld_map_set_keyframe_features");
+}
+
+void MapOnDevice::LocalBundleAdjustment(KeyFrame* pKF, bool* pbStopFlag, lld_slam::Map* pMap, double gamma, LbaTrace* trace) {
+  LbaTrace local_trace;
+  LbaTrace& tr = trace ? *trace : local_trace;
+  tr = LbaTrace();
+  if (!ba_) throw std::runtime_error("MapOnDevice::LocalBundleAdjustment: EnableBundleAdjustment before Upload");
+  // ---- :938-950  the list that travels: pKF, then its covisible keyframes in their order
+  const std::vector<KeyFrame*> vNeighKFs = pKF->GetVectorCovisibleKeyFrames();
+  std::vector<int32_t> slots(1, slot_of(pKF, limits_.max_keyframes));
+  pKF->mnBALocalForKF = pKF->mnId;
+  for (size_t i = 0; i < vNeighKFs.size(); i++) { vNeighKFs[i]->mnBALocalForKF = pKF->mnId; slots.push_back(slot_of(vNeighKFs[i], limits_.max_keyframes)); }
+  for (size_t i = 0; i < slots.size(); i++)
+    if (KeyFrameOf(slots[i]) != (i ? vNeighKFs[i - 1] : pKF)) throw std::runtime_error("MapOnDevice::LocalBundleAdjustment: a keyframe the map does not hold");
+  lld_ba_params p; lld_ba_params_default(&p); p.gamma = gamma;
+  // ---- :953-1329  window, graph, optimize(5), classification, optimize(15): one call
+  const lld_amd::DeviceMap::LocalBaResult solved = lld_amd::DeviceMap::LocalBaOn(m_, slots, lld_camera{pKF->fx, pKF->fy, pKF->cx, pKF->cy, pKF->mbf}, pKF->mvInvLevelSigma2, &p, pbStopFlag);
+  const lld_ba_result& res = solved.result; const lld_map_ba_ids& ids = solved.ids;
+  if (ids.status) throw std::runtime_error("MapOnDevice::LocalBundleAdjustment: the map lacks feature data (EnableBundleAdjustment before Upload)");
+  const lld_ba_window& w = ids.window;
+  std::vector<KeyFrame*>& cams = tr.cams;
+  for (int32_t c = 0; c < w.n_cams; c++) cams.push_back(kf_[ids.cam_slot[c]]);
+  for (int32_t k = 0; k < w.n_points; k++) { tr.points.push_back(pt_[ids.point_slot[k]]); tr.points.back()->mnBALocalForKF = pKF->mnId; }
+  for (int32_t k = 0; k < w.n_lines; k++) { tr.lines.push_back(ln_[ids.line_slot[k]]); tr.lines.back()->mnBALocalForKF = pKF->mnId; }
+  for (int32_t c = ids.n_local_cams; c < w.n_cams; c++) cams[c]->mnBAFixedForKF = pKF->mnId;
+  for (int32_t k = 0; k < ids.n_marked_bad; k++) if (KeyFrame* kf = KeyFrameOf(ids.marked_bad_slot[k])) kf->mnBAFixedForKF = pKF->mnId;   // marked, never a camera
+  for (int32_t k = 0; k < w.n_points; k++)
+    for (int32_t e = w.pt_obs_start[k]; e < w.pt_obs_start[k + 1]; e++) tr.pt_obs_owner.push_back(std::make_pair(cams[w.pt_obs_cam[e]], tr.points[k]));
+  for (int32_t k = 0; k < w.n_lines; k++)
+    for (int32_t e = w.ln_obs_start[k]; e < w.ln_obs_start[k + 1]; e++) tr.ln_obs_owner.push_back(std::make_pair(cams[w.ln_obs_cam[e]], tr.lines[k]));
+  if (trace) {
+    lld_amd::BAWindow& g = tr.window; lld_amd::BAOutput& o = tr.output;
+    const size_t nc = w.n_cams, np = w.n_points, npo = w.n_pt_obs, nl = w.n_lines, nlo = w.n_ln_obs;
+    g.cam = w.cam; g.n_free_cams = w.n_free_cams;
+    g.cam_qt.assign(w.cam_qt, w.cam_qt + 7 * nc); g.pt_xyz.assign(w.pt_xyz, w.pt_xyz + 3 * np); g.pt_obs_start.assign(w.pt_obs_start, w.pt_obs_start + np + 1);
+    g.pt_obs_cam.assign(w.pt_obs_cam, w.pt_obs_cam + npo); g.pt_obs_uvr.assign(w.pt_obs_uvr, w.pt_obs_uvr + 3 * npo);
+    g.pt_obs_inv_sigma2.assign(w.pt_obs_inv_sigma2, w.pt_obs_inv_sigma2 + npo);
+    g.line_x0.assign(w.line_x0, w.line_x0 + 3 * nl); g.line_dir.assign(w.line_dir, w.line_dir + 3 * nl); g.ln_obs_start.assign(w.ln_obs_start, w.ln_obs_start + nl + 1);
+    g.ln_obs_cam.assign(w.ln_obs_cam, w.ln_obs_cam + nlo); g.ln_obs_left.assign(w.ln_obs_left, w.ln_obs_left + 4 * nlo);
+    g.ln_obs_right.assign(w.ln_obs_right, w.ln_obs_right + 4 * nlo); g.ln_obs_octave.assign(w.ln_obs_octave, w.ln_obs_octave + 2 * nlo);
+    o.cam_qt.assign(res.cam_qt, res.cam_qt + 7 * nc); o.pt_xyz.assign(res.pt_xyz, res.pt_xyz + 3 * np); o.line_x0.assign(res.line_x0, res.line_x0 + 3 * nl);
+    o.line_dir.assign(res.line_dir, res.line_dir + 3 * nl); o.pt_obs_outlier.assign(res.pt_obs_outlier, res.pt_obs_outlier + npo);
+    o.ln_edge_outlier.assign(res.ln_edge_outlier, res.ln_edge_outlier + 2 * nlo); o.line_removed.assign(res.line_removed, res.line_removed + nl);
+  }
+  tr.output.stats = res.stats;
+  tr.solved = true;
+  if (res.stats.aborted && res.stats.lm_iterations[0] == 0 && res.stats.lm_trials[0] == 0) {      // :1220-1222 return before optimising: the map is not touched
+    tr.returned_before_optimising = true;
+    return;
+  }
+  // ---- :1278-1329  erase lists
+  for (size_t k = 0; k < tr.pt_obs_owner.size(); k++) if (res.pt_obs_outlier[k]) tr.vToErase.push_back(tr.pt_obs_owner[k]);
+  for (size_t k = 0; k < tr.ln_obs_owner.size(); k++)
+    for (int si = 0; si < 2; si++) if (res.ln_edge_outlier[2 * k + si]) tr.vToEraseLines.push_back(tr.ln_obs_owner[k]);   // once per outlier edge
+  std::set<KeyFrame*> lost;                                             // keyframes whose match rows change
+  {
+    // ---- :1334-1386  write-back under the map mutex
+    std::unique_lock<std::mutex> lock(pMap->mMutexMapUpdate);
+    for (size_t i = 0; i < tr.vToErase.size(); i++) {
+      KeyFrame* pKFi = tr.vToErase[i].first; MapPoint* pMPi = tr.vToErase[i].second;
+      pKFi->EraseMapPointMatch(pMPi);
+      pMPi->EraseObservation(pKFi);
+      lost.insert(pKFi);
+    }
+    for (size_t i = 0; i < tr.vToEraseLines.size(); i++) {
+      KeyFrame* pKFi = tr.vToEraseLines[i].first; MapLine* pMLi = tr.vToEraseLines[i].second;
+      pKFi->EraseMapLineMatch(pMLi);
+      pMLi->EraseObservation(pKFi);
+      lost.insert(pKFi);
+    }
+    for (int32_t c = 0; c < ids.n_local_cams; c++) {                   // every local keyframe, the fixed mnId == 0 one included
+      float T[16];
+      lld_se3_to_tcw_f32(res.cam_qt + 7 * (size_t)c, T);
+      cams[c]->SetPose(lld_slam::Mat(4, 4, T));
+    }
+    for (size_t k = 0; k < tr.points.size(); k++) {
+      lld_slam::Mat X(3, 1);
+      for (int c = 0; c < 3; c++) X.at<float>(c) = (float)res.pt_xyz[3 * k + c];
+      tr.points[k]->SetWorldPos(X);
+      tr.points[k]->UpdateNormalAndDepth();
+    }
+    for (size_t k = 0; k < tr.lines.size(); k++) {
+      if (res.line_removed[k]) continue;
+      tr.lines[k]->SetMinimalPos(lld_slam::Vector3d(res.line_x0[3 * k], res.line_x0[3 * k + 1], res.line_x0[3 * k + 2]),
+                                 lld_slam::Vector3d(res.line_dir[3 * k], res.line_dir[3 * k + 1], res.line_dir[3 * k + 2]));
+    }
+  }
+  // ---- the map follows the objects (res and ids are not read beyond this point: the setters do not touch them, but nothing needs them)
+  const int32_t n_local = ids.n_local_cams;
+  std::vector<KeyFrame*> rows(lost.begin(), lost.end());
+  std::vector<int32_t> pose_slot; std::vector<float> pose;
+  for (int32_t c = 0; c < n_local; c++) {
+    if (lost.count(cams[c])) continue;                                  // its whole row travels below, the pose with it
+    pose_slot.push_back((int32_t)cams[c]->mnId);
+    const lld_slam::Mat T = cams[c]->GetPose();
+    pose.insert(pose.end(), T.ptr<float>(), T.ptr<float>() + 16);
+  }
+  UpdateKeyFrames(rows);
+  if (!pose_slot.empty()) check(lld_map_set_keyframe_poses(m_, (int32_t)pose_slot.size(), pose_slot.data(), pose.data()), "lld_map_set_keyframe_poses");
+  UpdatePoints(tr.points);
+  UpdateLines(tr.lines);
 }
 
 void MapOnDevice::SetCovisibles(const std::vector<KeyFrame*>& keyframes) {
@@ -272,6 +405,19 @@ void MapOnDevice::UpdateLines(const std::vector<MapLine*>& lines) {
     }
   }
   check(lld_map_set_lines(m_, (int32_t)n, slot.data(), x0.data(), dir.data(), x1.data(), x2.data(), desc.data(), bad.data()), "lld_map_set_lines");
+  if (!ba_) return;
+  std::vector<int32_t> start(1, 0), obs, idx, nobs(n);
+  for (size_t i = 0; i < n; i++) {
+    const std::map<KeyFrame*, size_t> observations = lines[i]->GetObservations();
+    for (std::map<KeyFrame*, size_t>::const_iterator it = observations.begin(); it != observations.end(); ++it) {
+      const int32_t s = slot_of(it->first, limits_.max_keyframes);
+      if (s >= 0) { obs.push_back(s); idx.push_back((int32_t)it->second); }
+    }
+    start.push_back((int32_t)obs.size());
+    nobs[i] = lines[i]->Observations();
+  }
+  obs.push_back(0); idx.push_back(0);
+  check(lld_map_set_line_observations(m_, (int32_t)n, slot.data(), start.data(), obs.data(), idx.data(), nobs.data()), "lld_map_set_line_observations");
 }
 
 }  // namespace lld_adapter

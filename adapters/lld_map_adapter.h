@@ -17,11 +17,7 @@
 #include <vector>
 
 #include "../include/lld_amd.h"
-
-#ifndef LLD_ADAPTER_OBJECTS_HEADER
-#define LLD_ADAPTER_OBJECTS_HEADER "lld_slam_objects.h"
-#endif
-#include LLD_ADAPTER_OBJECTS_HEADER
+#include "lld_optimizer_adapter.h"      // LbaTrace (and the object model: LLD_ADAPTER_OBJECTS_HEADER)
 
 namespace lld_adapter {
 
@@ -57,6 +53,20 @@ class MapOnDevice {
   // its former parent, of its children and of the parents they have afterwards.  Returns the flagged keyframes in order.
   std::vector<lld_slam::KeyFrame*> KeyFrameCulling(lld_slam::KeyFrame* pCurrentKF, bool bMonocular, int* n_calls = nullptr);
 
+  // ---- local bundle adjustment on the mirrored map (lld_map_local_ba): the window is assembled on the device's tables
+  // From here on Upload / UpdateKeyFrames / UpdateLines also send what the window reads beyond the covisibility tables (which this enables
+  // too): mnId, pose, mvKeysUn[i].pt / mvuRight[i] and the keylines with their stereo partners per keyframe, the observation rows and
+  // Observations() per MapLine.  Call it before the first Upload (LocalBundleAdjustment throws on a map whose rows carry none of it).
+  void EnableBundleAdjustment() { covis_ = true; ba_ = true; }
+  // Optimizer::LocalBundleAdjustment(pKF, pbStopFlag, pMap, gamma) as lld_adapter::LocalBundleAdjustment (lld_optimizer_adapter.h) makes it,
+  // with the window of src/Optimizer.cc:938-1218 assembled by the device instead of walked on the objects: one call, then the same erase
+  // lists and write-back under the map mutex, then the rows that changed are pushed - the local keyframes' poses (lld_map_set_keyframe_poses),
+  // the local points and lines (UpdatePoints / UpdateLines: positions and the rows an erased observation shortened) and the keyframes that
+  // lost a match (UpdateKeyFrames).  pKF, its covisible keyframes and everything they see must be current in the map.  The visit marks
+  // (mnBALocalForKF / mnBAFixedForKF) are set on the objects as the reference sets them.  mvInvLevelSigma2 is read from pKF: one table for
+  // all keyframes, as ORBextractor makes it.  The trace's window and output are filled only when a trace is asked for.
+  void LocalBundleAdjustment(lld_slam::KeyFrame* pKF, bool* pbStopFlag, lld_slam::Map* pMap, double gamma = 1.0, LbaTrace* trace = nullptr);
+
   // slot -> object (NULL: never sent)
   lld_slam::KeyFrame* KeyFrameOf(int slot) const { return slot >= 0 && slot < (int)kf_.size() ? kf_[slot] : nullptr; }
   lld_slam::MapPoint* PointOf(int slot) const { return slot >= 0 && slot < (int)pt_.size() ? pt_[slot] : nullptr; }
@@ -70,7 +80,7 @@ class MapOnDevice {
   std::vector<lld_slam::KeyFrame*> kf_;
   std::vector<lld_slam::MapPoint*> pt_;
   std::vector<lld_slam::MapLine*> ln_;
-  bool covis_ = false;
+  bool covis_ = false, ba_ = false;
   void SetCovisibles(const std::vector<lld_slam::KeyFrame*>& keyframes);
 };
 

@@ -6,10 +6,9 @@
 //   adapter_harness ba   <in> <out> [seed]    Optimizer::LocalBundleAdjustment(pKF, &mbAbortBA, pMap, gamma)
 //   adapter_harness pose <in> <out> [seed]    Optimizer::PoseOptimization(&mCurrentFrame, gamma)
 //
-// The object graph is deliberately awkward: keyframes are allocated in shuffled order (std::map<KeyFrame*, ...> iterates by ADDRESS),
-// their mnIds are a permutation of the input's camera order, one covisible keyframe has mnId 0 (fixed although local), and there are
-// objects the reference skips (a bad MapPoint, a MapLine with two observations, a bad observing KeyFrame, keypoints / lines without
-// a landmark).  Input files are the ones examples/harness.cpp reads (`ba` / `pose` modes).
+// The object graph of `ba` is deliberately awkward (lba_graph.h: keyframes at shuffled addresses - std::map<KeyFrame*, ...> iterates by
+// ADDRESS -, mnIds a permutation of the input's camera order, one covisible keyframe with mnId 0, and the objects the reference skips).
+// Input files are the ones examples/harness.cpp reads (`ba` / `pose` modes).
 #include <algorithm>
 #include <cmath>
 #include <cstdio>
@@ -25,6 +24,7 @@
 #include "../adapters/lld_matcher_adapter.h"
 #include "../adapters/lld_line_adapter.h"
 #include "../adapters/lld_tracking_adapter.h"
+#include "lba_graph.h"
 
 std::mutex lld_slam::MapPoint::mGlobalMutex;        // the doubles' static member (the real class defines its own, MapPoint.cc:30)
 
@@ -69,103 +69,14 @@ int run_ba(const char* in, const char* out, unsigned seed) {
   r.get(w.line_x0, 3 * (size_t)h[4]); r.get(w.line_dir, 3 * (size_t)h[4]); r.get(w.ln_obs_start, (size_t)h[4] + 1);
   r.get(w.ln_obs_cam, h[5]); r.get(w.ln_obs_left, 4 * (size_t)h[5]); r.get(w.ln_obs_right, 4 * (size_t)h[5]);
   r.get(w.ln_obs_octave, 2 * (size_t)h[5]);
-  const int n_cams = h[0], n_free = h[1], n_pts = h[2], n_lns = h[4];
-  if (n_free < 1) throw std::runtime_error("adapter-ba needs a free camera (pKF)");
+  // ---- the object graph (lba_graph.h): shuffled addresses, permuted mnIds, a local mnId 0, and the objects the reference skips
   std::mt19937 rng(seed);
-  const std::vector<float> table = level_table();
-
-  // ---- keyframes: allocated in shuffled order, mnIds a permutation of the input order; the first fixed camera becomes mnId 0 and local
-  std::vector<int> alloc_order(n_cams + 1);
-  for (int i = 0; i <= n_cams; i++) alloc_order[i] = i;
-  std::shuffle(alloc_order.begin(), alloc_order.end(), rng);
-  std::vector<std::unique_ptr<KeyFrame> > kf_store(n_cams + 1);
-  for (int i : alloc_order) kf_store[i].reset(new KeyFrame());
-  std::vector<KeyFrame*> kf(n_cams);
-  for (int c = 0; c < n_cams; c++) kf[c] = kf_store[c].get();
-  KeyFrame* bad_kf = kf_store[n_cams].get();                                   // an observer the reference skips
-  std::vector<int> perm(n_free);
-  for (int i = 0; i < n_free; i++) perm[i] = i;
-  std::shuffle(perm.begin(), perm.end(), rng);
-  std::map<const KeyFrame*, int> kf_orig;
-  for (int c = 0; c < n_cams; c++) {
-    KeyFrame& K = *kf[c];
-    K.mnId = c < n_free ? (unsigned long)(5 + 2 * perm[c]) : (c == n_free ? 0ul : (unsigned long)(1000 + c));
-    K.fx = (float)camg[0]; K.fy = (float)camg[1]; K.cx = (float)camg[2]; K.cy = (float)camg[3]; K.mbf = (float)camg[4];
-    K.mK = k_mat(K.fx, K.fy, K.cx, K.cy);
-    K.mvInvLevelSigma2 = table;
-    K.Tcw = pose_mat(&w.cam_qt[7 * (size_t)c]);
-    kf_orig[&K] = c;
-  }
-  bad_kf->mnId = 777; bad_kf->mbBad = true; bad_kf->mvInvLevelSigma2 = table; bad_kf->Tcw = pose_mat(&w.cam_qt[0]);
-  bad_kf->fx = (float)camg[0]; bad_kf->mK = k_mat((float)camg[0], (float)camg[1], (float)camg[2], (float)camg[3]);
-  // pKF = the free camera with the largest mnId; every other free camera and the mnId-0 one are covisible (in shuffled order)
-  KeyFrame* pKF = kf[0];
-  for (int c = 1; c < n_free; c++) if (kf[c]->mnId > pKF->mnId) pKF = kf[c];
-  for (int c = 0; c < n_cams; c++) if (kf[c] != pKF && (c < n_free || c == n_free)) pKF->mvpOrderedConnectedKeyFrames.push_back(kf[c]);
-  std::shuffle(pKF->mvpOrderedConnectedKeyFrames.begin(), pKF->mvpOrderedConnectedKeyFrames.end(), rng);
-  pKF->mvpOrderedConnectedKeyFrames.push_back(bad_kf);                         // a bad covisible keyframe: marked local, never a camera
-
-  // ---- map points and their observations
-  std::vector<std::unique_ptr<MapPoint> > mp_store(n_pts + 1);
-  std::map<const MapPoint*, int> mp_orig;
-  std::map<std::pair<const KeyFrame*, const MapPoint*>, int> ptobs_orig;
-  for (int p = 0; p < n_pts; p++) {
-    mp_store[p].reset(new MapPoint());
-    MapPoint& M = *mp_store[p];
-    M.mnId = (unsigned long)(3 * p + 1);
-    M.mWorldPos = Mat(3, 1);
-    for (int k = 0; k < 3; k++) M.mWorldPos.at<float>(k) = (float)w.pt_xyz[3 * (size_t)p + k];
-    mp_orig[&M] = p;
-    for (int o = w.pt_obs_start[p]; o < w.pt_obs_start[p + 1]; o++) {
-      KeyFrame& K = *kf[w.pt_obs_cam[o]];
-      KeyPoint kp; kp.pt.x = (float)w.pt_obs_uvr[3 * (size_t)o]; kp.pt.y = (float)w.pt_obs_uvr[3 * (size_t)o + 1]; kp.octave = octave_of(table, w.pt_obs_inv_sigma2[o]);
-      if (K.mvKeysUn.size() % 5 == 2) { K.mvKeysUn.push_back(kp); K.mvuRight.push_back(-1.f); K.mvpMapPoints.push_back(nullptr); }   // a keypoint without a MapPoint in between
-      M.mObservations[&K] = K.mvKeysUn.size();
-      K.mvKeysUn.push_back(kp); K.mvuRight.push_back((float)w.pt_obs_uvr[3 * (size_t)o + 2]); K.mvpMapPoints.push_back(&M);
-      ptobs_orig[std::make_pair((const KeyFrame*)&K, (const MapPoint*)&M)] = o;
-    }
-    if (p % 7 == 3) {                                                           // the bad keyframe also observes this point: skipped by the reference
-      KeyPoint kp; kp.pt.x = 10.f; kp.pt.y = 10.f; kp.octave = 0;
-      M.mObservations[bad_kf] = bad_kf->mvKeysUn.size();
-      bad_kf->mvKeysUn.push_back(kp); bad_kf->mvuRight.push_back(5.f); bad_kf->mvpMapPoints.push_back(&M);
-    }
-  }
-  mp_store[n_pts].reset(new MapPoint());                                         // a bad MapPoint among pKF's matches: never enters the window
-  MapPoint& bad_mp = *mp_store[n_pts];
-  bad_mp.mnId = 999999; bad_mp.mbBad = true; bad_mp.mWorldPos = Mat(3, 1);
-  { KeyPoint kp; kp.pt.x = 1.f; kp.pt.y = 2.f; kp.octave = 0; bad_mp.mObservations[pKF] = pKF->mvKeysUn.size(); pKF->mvKeysUn.push_back(kp); pKF->mvuRight.push_back(1.f); pKF->mvpMapPoints.push_back(&bad_mp); }
-
-  // ---- map lines
-  std::vector<std::unique_ptr<MapLine> > ml_store(n_lns + 1);
-  std::map<const MapLine*, int> ml_orig;
-  std::map<std::pair<const KeyFrame*, const MapLine*>, int> lnobs_orig;
-  for (int l = 0; l < n_lns; l++) {
-    ml_store[l].reset(new MapLine());
-    MapLine& L = *ml_store[l];
-    L.mnId = (unsigned long)(2 * l + 7);
-    L.mX0 = Vector3d(w.line_x0[3 * (size_t)l], w.line_x0[3 * (size_t)l + 1], w.line_x0[3 * (size_t)l + 2]);
-    L.mDir = Vector3d(w.line_dir[3 * (size_t)l], w.line_dir[3 * (size_t)l + 1], w.line_dir[3 * (size_t)l + 2]);
-    ml_orig[&L] = l;
-    for (int o = w.ln_obs_start[l]; o < w.ln_obs_start[l + 1]; o++) {
-      KeyFrame& K = *kf[w.ln_obs_cam[o]];
-      const bool has_right = !(w.ln_obs_right[4 * (size_t)o] < 0);
-      L.mObservations[&K] = K.mvLinesLeft.size();
-      K.mvLinesLeft.push_back(key_line(&w.ln_obs_left[4 * (size_t)o], w.ln_obs_octave[2 * (size_t)o]));
-      if (has_right) { K.line_matches.push_back((int)K.mvLinesRight.size()); K.mvLinesRight.push_back(key_line(&w.ln_obs_right[4 * (size_t)o], w.ln_obs_octave[2 * (size_t)o + 1])); }
-      else K.line_matches.push_back(-1);
-      K.mvpMapLines.push_back(&L);
-      lnobs_orig[std::make_pair((const KeyFrame*)&K, (const MapLine*)&L)] = o;
-    }
-  }
-  ml_store[n_lns].reset(new MapLine());                                          // a MapLine with two observations: below the `Observations() < 4` bar (:972)
-  MapLine& short_ml = *ml_store[n_lns];
-  short_ml.mnId = 888888; short_ml.mX0 = Vector3d(1, 2, 3); short_ml.mDir = Vector3d(1, 0, 0);
-  for (int c = 0; c < std::min(2, n_free); c++) {
-    KeyFrame& K = *kf[c];
-    short_ml.mObservations[&K] = K.mvLinesLeft.size();
-    const double seg[4] = {10, 10, 50, 50};
-    K.mvLinesLeft.push_back(key_line(seg, 0)); K.line_matches.push_back(-1); K.mvpMapLines.push_back(&short_ml);
-  }
+  lba_graph::Graph G;
+  G.build(w, camg, rng);
+  KeyFrame* pKF = G.pKF; KeyFrame* bad_kf = G.bad_kf; MapPoint& bad_mp = *G.bad_mp; MapLine& short_ml = *G.short_ml;
+  std::map<const KeyFrame*, int>& kf_orig = G.kf_orig; std::map<const MapPoint*, int>& mp_orig = G.mp_orig; std::map<const MapLine*, int>& ml_orig = G.ml_orig;
+  std::map<std::pair<const KeyFrame*, const MapPoint*>, int>& ptobs_orig = G.ptobs_orig;
+  std::map<std::pair<const KeyFrame*, const MapLine*>, int>& lnobs_orig = G.lnobs_orig;
 
   // ---- the call, as LocalMapping::Run makes it (LocalMapping.cc:76-82)
   Map map;

@@ -2698,6 +2698,107 @@ typedef struct {
 } lld_map_covisibility_out;
 int  lld_map_covisibility(lld_map* map, const lld_map_covisibility_in* in, lld_map_covisibility_out* out);
 
+/* ------------------------------------------------------------------ the local BA window from the resident map (lld_map_ba.hip)
+ * The first third of Optimizer::LocalBundleAdjustment (src/Optimizer.cc:938-1018 and the edge loops :1093-1218): local keyframes, local
+ * points and lines, fixed cameras, and every observation flattened into a lld_ba_window - assembled on the map's tables.  Only the list
+ * of local keyframe slots travels up; the window arrives in the layout lld_local_ba takes.
+ *
+ * Tables beyond the ones above, in pools of their own that the first of these three setters allocates (a map on which they are never
+ * called allocates what it allocated before).  The contract is that of the other setters: everything is validated first, a refusal
+ * changes nothing, one block and one copy per call, a HIP failure behind the host bookkeeping poisons the map, lld_map_clear empties them.
+ *   lld_map_set_keyframe_features  per keyframe slot[i] (lld_map_set_keyframes must have set it): mn_id[i] = KeyFrame::mnId; Tcw [16 i ..] =
+ *                             GetPose() row-major, stored as lld_se3_from_tcw_f32 of it (7 doubles, computed on the host); per keypoint
+ *                             kp_uvr [3 k ..] = mvKeysUn[k].pt.x, .pt.y, mvuRight[k] - kp_start[i + 1] - kp_start[i] must equal the length
+ *                             of the keyframe's point row; per left keyline kl_left [4 k ..] = startPointX, startPointY, endPointX,
+ *                             endPointY, kl_right [4 k ..] the same of mvLinesRight[line_matches[k]] or four times -1.0f when
+ *                             line_matches[k] < 0, kl_octave [2 k ..] = left octave, right octave (0 without a partner) - kl_start[i + 1] -
+ *                             kl_start[i] must equal the length of the keyframe's line row.  Floats stay floats and are widened on the
+ *                             device.  Keypoint octaves are those of lld_map_set_keyframe_keypoints.
+ *   lld_map_set_keyframe_poses     Tcw alone, for keyframes that already have features (LLD_ERR_INVALID otherwise).
+ *   lld_map_set_line_observations  per line slot[i]: kf_slot / line_index [start[i] .. start[i+1]) = MapLine::mObservations in
+ *                             std::map<KeyFrame*, size_t> iteration order, n_obs[i] = MapLine::Observations() (stereo-weighted, not the
+ *                             row length).  The live total of line observations is bounded by max_kf_lines (an observation is an entry of
+ *                             a keyframe's line row).
+ * LLD_ERR_UNSUPPORTED from the first setter when max_kf_points > 2^28 or max_kf_lines > 2^26 (the pools' offsets are int32). */
+int  lld_map_set_keyframe_features(lld_map* map, int32_t n, const int32_t* slot, const uint64_t* mn_id, const float* Tcw, const int32_t* kp_start,
+                                   const float* kp_uvr, const int32_t* kl_start, const float* kl_left, const float* kl_right, const int32_t* kl_octave);
+int  lld_map_set_keyframe_poses(lld_map* map, int32_t n, const int32_t* slot, const float* Tcw);
+int  lld_map_set_line_observations(lld_map* map, int32_t n, const int32_t* slot, const int32_t* start, const int32_t* kf_slot,
+                                   const int32_t* line_index, const int32_t* n_obs);
+/* The call.  One upload (the slot list and the level table), kernels on the context's stream with no host trip between them, one download,
+ * one wait.  kf_slot[0] = pKF, kf_slot[1 .. n) = pKF->GetVectorCovisibleKeyFrames() in its order.  Rules, quirks included:
+ *   :940-950   kf_slot[0] is a local keyframe whatever its bad flag; a bad neighbour is marked local but not listed (so it is never a fixed
+ *              camera either).
+ *   :955-984   local points in list order, then keypoint order: entries -1, bad points and point slots never set are skipped, the first
+ *              occurrence counts.  Local lines likewise; a line slot never set is bad, and a line with n_obs < 4 is skipped without being marked.
+ *   :990-1018  fixed cameras: the local points in list order, each observation row in stored order, then the lines the same way; an observer
+ *              that is neither marked local nor marked fixed yet is marked fixed, and listed if it is not bad.
+ *   cameras    the listed local keyframes with mn_id != 0 by ascending mn_id (n_free_cams of them), the listed local keyframes with
+ *              mn_id == 0, then the fixed cameras in first-marked order.  [0, n_local_cams) are the local ones.  Uniqueness of mn_id is not
+ *              checked: with equal ids the order of those is undefined, nothing is read out of bounds.
+ *   :1093-1178 a point's run: its observations in stored order without the bad observers; u, v, uR widened from the observer's keypoint row
+ *              at the stored index, inv_sigma2 = (double)inv_level_sigma2[octave of that keypoint].  A point whose run is empty stays.
+ *   :1185-1218 a line's run: its non-bad observers in ascending mn_id, left and right end points widened, both octaves.
+ *   pt_xyz is the widened float position; line_x0 / line_dir are the stored doubles.
+ * Capacities: the seven counts are always written; if any capacity is short the call returns LLD_ERR_INVALID with only the counts (and
+ * status = 0) written.  Arrays whose capacity is 0 may be NULL, except pt_obs_start and ln_obs_start (capacity + 1 entries each).
+ * Never a silently wrong window - status, LLD_OK returned: LLD_MAP_BA_NO_FEATURE_DATA when a camera of the window has no feature rows
+ * (lld_map_set_keyframe_features, lld_map_set_keyframe_keypoints) of its point and line rows' lengths, a local point's observation row has
+ * no index row of its length, a local line that is not bad has no observation row, or a stored index falls outside the observer's row - or
+ * an octave outside [0, n_levels).  The device decides this from the row lengths before it reads.  The counts are then 0 and no array is
+ * written.
+ * LLD_ERR_INVALID before anything is queued: a NULL argument; n_keyframes < 1 or > LLD_MAP_BA_MAX_LOCAL; a slot out of range, never set or
+ * named twice; n_levels < 1 or a NULL level table; a negative capacity; a NULL array with a capacity above 0.  LLD_ERR_HIP for a poisoned map. */
+#define LLD_MAP_BA_MAX_LOCAL        1024
+#define LLD_MAP_BA_NO_FEATURE_DATA  1
+typedef struct {
+  int32_t n_keyframes;
+  int32_t n_levels;
+  const int32_t* kf_slot;           /* [n_keyframes]                                   */
+  const float* inv_level_sigma2;    /* [n_levels] mvInvLevelSigma2                     */
+  lld_camera cam;                   /* copied into the window: pKF's fx, fy, cx, cy, mbf */
+} lld_map_ba_in;
+typedef struct {
+  int32_t cam_capacity, point_capacity, pt_obs_capacity, line_capacity, ln_obs_capacity;
+  int32_t n_cams, n_free_cams, n_local_cams, n_points, n_pt_obs, n_lines, n_ln_obs;      /* always written */
+  int32_t status;
+  int32_t*  cam_slot;               /* [n_cams]                                         */
+  double*   cam_qt;                 /* [n_cams][7]                                      */
+  int32_t*  point_slot;             /* [n_points]                                       */
+  double*   pt_xyz;                 /* [n_points][3]                                    */
+  int32_t*  pt_obs_start;           /* [n_points + 1] (capacity + 1 entries are needed) */
+  int32_t*  pt_obs_cam;             /* [n_pt_obs]                                       */
+  double*   pt_obs_uvr;             /* [n_pt_obs][3]                                    */
+  double*   pt_obs_inv_sigma2;      /* [n_pt_obs]                                       */
+  int32_t*  line_slot;              /* [n_lines]                                        */
+  double*   line_x0;                /* [n_lines][3]                                     */
+  double*   line_dir;               /* [n_lines][3]                                     */
+  int32_t*  ln_obs_start;           /* [n_lines + 1]                                    */
+  int32_t*  ln_obs_cam;             /* [n_ln_obs]                                       */
+  double*   ln_obs_left;            /* [n_ln_obs][4]                                    */
+  double*   ln_obs_right;           /* [n_ln_obs][4]                                    */
+  int32_t*  ln_obs_octave;          /* [n_ln_obs][2]                                    */
+  float*    phase_ms;               /* NULL, or [3]: HIP-event times of upload, kernels, download */
+} lld_map_ba_window_out;
+int  lld_map_ba_window(lld_map* map, const lld_map_ba_in* in, lld_map_ba_window_out* out);
+/* lld_map_ba_window into pinned buffers the map owns (grown on demand: a call that finds them short repeats the assembly once), then
+ * lld_local_ba_stopflag on that window.  The map's tables are not changed.  Every pointer of `result` and `ids` is SET by the call and
+ * points into memory of the map, valid until the next lld_map_local_ba or lld_map_destroy on it; ids->window is the window that was solved.
+ * With ids->status != 0 nothing was solved and the counts are 0.  params = NULL: lld_ba_params_default; stop_flag may be NULL. */
+typedef struct {
+  int32_t status;                   /* 0 or LLD_MAP_BA_NO_FEATURE_DATA                  */
+  int32_t n_local_cams;             /* cameras [0, n_local_cams) are the local keyframes: the adapter writes a pose back for each */
+  const int32_t* cam_slot;          /* [window.n_cams]                                  */
+  const int32_t* point_slot;        /* [window.n_points]                                */
+  const int32_t* line_slot;         /* [window.n_lines]                                 */
+  int32_t n_marked_bad;             /* keyframe slots the walk marks fixed (mnBAFixedForKF) although they are bad or were never set: */
+  int32_t reserved;                 /* no cameras, in no order - for a caller that mirrors the reference's visit marks               */
+  const int32_t* marked_bad_slot;   /* [n_marked_bad]                                   */
+  lld_ba_window window;
+} lld_map_ba_ids;
+int  lld_map_local_ba(lld_map* map, const lld_map_ba_in* in, const lld_ba_params* params, volatile const unsigned char* stop_flag,
+                      lld_ba_result* result, lld_map_ba_ids* ids);
+
 #if defined(__GNUC__)
 #pragma GCC visibility pop
 #endif

@@ -482,6 +482,92 @@ class DeviceMap {
       return r;
     }
   }
+  // ---- the local BA window from the resident map (lld_map_ba_window, lld_map_local_ba): its tables, then the calls
+  struct KeyFrameFeatures {      // the arguments of lld_map_set_keyframe_features
+    std::vector<int32_t> slot; std::vector<uint64_t> mn_id; std::vector<float> Tcw;
+    std::vector<int32_t> kp_start{0}; std::vector<float> kp_uvr;
+    std::vector<int32_t> kl_start{0}; std::vector<float> kl_left, kl_right; std::vector<int32_t> kl_octave;
+  };
+  void SetKeyFrameFeatures(const KeyFrameFeatures& f) { SetKeyFrameFeaturesOn(m_, f); }
+  static void SetKeyFrameFeaturesOn(lld_map* m, const KeyFrameFeatures& f) {
+    const size_t n = f.slot.size();
+    if (f.mn_id.size() != n || f.Tcw.size() != 16 * n || f.kp_start.size() != n + 1 || f.kl_start.size() != n + 1 || f.kp_uvr.size() != 3 * (size_t)f.kp_start[n] ||
+        f.kl_left.size() != 4 * (size_t)f.kl_start[n] || f.kl_right.size() != f.kl_left.size() || f.kl_octave.size() != 2 * (size_t)f.kl_start[n])
+      check(LLD_ERR_INVALID, "lld_map_set_keyframe_features");
+    check(lld_map_set_keyframe_features(m, (int32_t)n, f.slot.data(), f.mn_id.data(), f.Tcw.data(), f.kp_start.data(), f.kp_uvr.data(), f.kl_start.data(), f.kl_left.data(),
+                                        f.kl_right.data(), f.kl_octave.data()), "lld_map_set_keyframe_features");
+  }
+  void SetKeyFramePoses(const std::vector<int32_t>& slot, const std::vector<float>& Tcw) {
+    if (Tcw.size() != 16 * slot.size()) check(LLD_ERR_INVALID, "lld_map_set_keyframe_poses");
+    check(lld_map_set_keyframe_poses(m_, (int32_t)slot.size(), slot.data(), Tcw.data()), "lld_map_set_keyframe_poses");
+  }
+  void SetLineObservations(const std::vector<int32_t>& slot, const std::vector<int32_t>& start, const std::vector<int32_t>& kf_slot, const std::vector<int32_t>& line_index,
+                           const std::vector<int32_t>& n_obs) {
+    if (start.size() != slot.size() + 1 || line_index.size() != kf_slot.size() || n_obs.size() != slot.size()) check(LLD_ERR_INVALID, "lld_map_set_line_observations");
+    check(lld_map_set_line_observations(m_, (int32_t)slot.size(), slot.data(), start.data(), kf_slot.data(), line_index.data(), n_obs.data()), "lld_map_set_line_observations");
+  }
+  struct BaWindowResult {        // the outputs of lld_map_ba_window: with status != 0 everything else is empty
+    int status = 0, n_local_cams = 0;
+    BAWindow window;
+    std::vector<int32_t> cam_slot, point_slot, line_slot;
+    float phase_ms[3] = {0.f, 0.f, 0.f};
+  };
+  // kf_slot[0] = pKF, the others its covisible keyframes in their order.  The arrays are sized by a guess and, if the library reports greater
+  // counts, by those counts in a second call.
+  BaWindowResult BaWindow(const std::vector<int32_t>& kf_slot, const lld_camera& cam, const std::vector<float>& inv_level_sigma2, bool timed = false) {
+    return BaWindowOn(m_, kf_slot, cam, inv_level_sigma2, timed);
+  }
+  static BaWindowResult BaWindowOn(lld_map* m, const std::vector<int32_t>& kf_slot, const lld_camera& cam, const std::vector<float>& inv_level_sigma2, bool timed = false) {
+    BaWindowResult r;
+    BAWindow& w = r.window;
+    lld_map_ba_in in{};
+    in.n_keyframes = (int32_t)kf_slot.size(); in.n_levels = (int32_t)inv_level_sigma2.size(); in.kf_slot = kf_slot.data(); in.inv_level_sigma2 = inv_level_sigma2.data(); in.cam = cam;
+    size_t cap[5] = {256, 16384, 65536, 2048, 8192};
+    for (int attempt = 0;; attempt++) {
+      r.cam_slot.assign(cap[0] + 1, 0); w.cam_qt.assign(7 * cap[0] + 1, 0.0);
+      r.point_slot.assign(cap[1] + 1, 0); w.pt_xyz.assign(3 * cap[1] + 1, 0.0); w.pt_obs_start.assign(cap[1] + 1, 0);
+      w.pt_obs_cam.assign(cap[2] + 1, 0); w.pt_obs_uvr.assign(3 * cap[2] + 1, 0.0); w.pt_obs_inv_sigma2.assign(cap[2] + 1, 0.0);
+      r.line_slot.assign(cap[3] + 1, 0); w.line_x0.assign(3 * cap[3] + 1, 0.0); w.line_dir.assign(3 * cap[3] + 1, 0.0); w.ln_obs_start.assign(cap[3] + 1, 0);
+      w.ln_obs_cam.assign(cap[4] + 1, 0); w.ln_obs_left.assign(4 * cap[4] + 1, 0.0); w.ln_obs_right.assign(4 * cap[4] + 1, 0.0); w.ln_obs_octave.assign(2 * cap[4] + 1, 0);
+      lld_map_ba_window_out o{};
+      o.cam_capacity = (int32_t)cap[0]; o.point_capacity = (int32_t)cap[1]; o.pt_obs_capacity = (int32_t)cap[2]; o.line_capacity = (int32_t)cap[3]; o.ln_obs_capacity = (int32_t)cap[4];
+      o.cam_slot = r.cam_slot.data(); o.cam_qt = w.cam_qt.data(); o.point_slot = r.point_slot.data(); o.pt_xyz = w.pt_xyz.data(); o.pt_obs_start = w.pt_obs_start.data();
+      o.pt_obs_cam = w.pt_obs_cam.data(); o.pt_obs_uvr = w.pt_obs_uvr.data(); o.pt_obs_inv_sigma2 = w.pt_obs_inv_sigma2.data();
+      o.line_slot = r.line_slot.data(); o.line_x0 = w.line_x0.data(); o.line_dir = w.line_dir.data(); o.ln_obs_start = w.ln_obs_start.data();
+      o.ln_obs_cam = w.ln_obs_cam.data(); o.ln_obs_left = w.ln_obs_left.data(); o.ln_obs_right = w.ln_obs_right.data(); o.ln_obs_octave = w.ln_obs_octave.data();
+      o.phase_ms = timed ? r.phase_ms : nullptr;
+      o.n_cams = -1;
+      const int st = lld_map_ba_window(m, &in, &o);
+      if (st == LLD_ERR_INVALID && attempt == 0 && o.n_cams >= 0) {
+        cap[0] = o.n_cams; cap[1] = o.n_points; cap[2] = o.n_pt_obs; cap[3] = o.n_lines; cap[4] = o.n_ln_obs;
+        continue;
+      }
+      check(st, "lld_map_ba_window");
+      r.status = o.status; r.n_local_cams = o.n_local_cams;
+      w.cam = cam; w.n_free_cams = o.n_free_cams;
+      const size_t nc = o.n_cams, np = o.n_points, npo = o.n_pt_obs, nl = o.n_lines, nlo = o.n_ln_obs;
+      r.cam_slot.resize(nc); w.cam_qt.resize(7 * nc); r.point_slot.resize(np); w.pt_xyz.resize(3 * np); w.pt_obs_start.resize(np + 1);
+      w.pt_obs_cam.resize(npo); w.pt_obs_uvr.resize(3 * npo); w.pt_obs_inv_sigma2.resize(npo);
+      r.line_slot.resize(nl); w.line_x0.resize(3 * nl); w.line_dir.resize(3 * nl); w.ln_obs_start.resize(nl + 1);
+      w.ln_obs_cam.resize(nlo); w.ln_obs_left.resize(4 * nlo); w.ln_obs_right.resize(4 * nlo); w.ln_obs_octave.resize(2 * nlo);
+      return r;
+    }
+  }
+  // lld_map_local_ba: the window assembled on the tables and solved.  `result` and `ids` point into memory of the map, valid until the next
+  // call of this on it; ids.status != 0: feature data is missing, nothing was solved.  params = NULL: lld_ba_params_default.
+  struct LocalBaResult { lld_ba_result result; lld_map_ba_ids ids; };
+  LocalBaResult LocalBa(const std::vector<int32_t>& kf_slot, const lld_camera& cam, const std::vector<float>& inv_level_sigma2, const lld_ba_params* params = nullptr,
+                        const bool* pbStopFlag = nullptr) {
+    return LocalBaOn(m_, kf_slot, cam, inv_level_sigma2, params, pbStopFlag);
+  }
+  static LocalBaResult LocalBaOn(lld_map* m, const std::vector<int32_t>& kf_slot, const lld_camera& cam, const std::vector<float>& inv_level_sigma2,
+                                 const lld_ba_params* params = nullptr, const bool* pbStopFlag = nullptr) {
+    lld_map_ba_in in{};
+    in.n_keyframes = (int32_t)kf_slot.size(); in.n_levels = (int32_t)inv_level_sigma2.size(); in.kf_slot = kf_slot.data(); in.inv_level_sigma2 = inv_level_sigma2.data(); in.cam = cam;
+    LocalBaResult r;
+    check(lld_map_local_ba(m, &in, params, reinterpret_cast<volatile const unsigned char*>(pbStopFlag), &r.result, &r.ids), "lld_map_local_ba");
+    return r;
+  }
   const lld_map_limits& limits() const { return limits_; }
   lld_map* get() const { return m_; }
  private:

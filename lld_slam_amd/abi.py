@@ -442,6 +442,31 @@ class MapCovisibilityOut(C.Structure):
     _fields_ = [("lists", CovisibilityOut), ("status", c_uint8_p)]
 
 
+class MapBaIn(C.Structure):
+    """lld_map_ba_in."""
+    _fields_ = [("n_keyframes", C.c_int32), ("n_levels", C.c_int32), ("kf_slot", c_int32_p), ("inv_level_sigma2", c_float_p), ("cam", Camera)]
+
+
+class MapBaWindowOut(C.Structure):
+    """lld_map_ba_window_out."""
+    _fields_ = [("cam_capacity", C.c_int32), ("point_capacity", C.c_int32), ("pt_obs_capacity", C.c_int32), ("line_capacity", C.c_int32),
+                ("ln_obs_capacity", C.c_int32),
+                ("n_cams", C.c_int32), ("n_free_cams", C.c_int32), ("n_local_cams", C.c_int32), ("n_points", C.c_int32), ("n_pt_obs", C.c_int32),
+                ("n_lines", C.c_int32), ("n_ln_obs", C.c_int32), ("status", C.c_int32),
+                ("cam_slot", c_int32_p), ("cam_qt", c_double_p), ("point_slot", c_int32_p), ("pt_xyz", c_double_p), ("pt_obs_start", c_int32_p),
+                ("pt_obs_cam", c_int32_p), ("pt_obs_uvr", c_double_p), ("pt_obs_inv_sigma2", c_double_p),
+                ("line_slot", c_int32_p), ("line_x0", c_double_p), ("line_dir", c_double_p), ("ln_obs_start", c_int32_p), ("ln_obs_cam", c_int32_p),
+                ("ln_obs_left", c_double_p), ("ln_obs_right", c_double_p), ("ln_obs_octave", c_int32_p), ("phase_ms", c_float_p)]
+
+
+class MapBaIds(C.Structure):
+    """lld_map_ba_ids."""
+    _fields_ = [("status", C.c_int32), ("n_local_cams", C.c_int32), ("cam_slot", c_int32_p), ("point_slot", c_int32_p), ("line_slot", c_int32_p),
+                ("n_marked_bad", C.c_int32), ("reserved", C.c_int32), ("marked_bad_slot", c_int32_p), ("window", BAWindow)]
+
+
+MAP_BA_MAX_LOCAL = 1024
+MAP_BA_NO_FEATURE_DATA = 1
 MAP_COVIS_MAX_CONNECTED = 4096
 MAP_COVIS_WRITE_COV = 4
 MAP_COVIS_CONN_OVERFLOW, MAP_COVIS_NO_KEYPOINT_DATA = 1, 2
@@ -494,6 +519,7 @@ PRODUCT_SYMBOLS = [
     "lld_map_create", "lld_map_destroy", "lld_map_clear", "lld_map_set_points", "lld_map_set_observations", "lld_map_set_keyframes", "lld_map_set_lines",
     "lld_frame_track_update_local_map", "lld_frame_track_local_map_resident", "lld_frame_local_map_download",
     "lld_map_set_observations_indexed", "lld_map_set_keyframe_keypoints", "lld_map_set_covisibles", "lld_map_covisibility", "lld_map_download_links",
+    "lld_map_set_keyframe_features", "lld_map_set_keyframe_poses", "lld_map_set_line_observations", "lld_map_ba_window", "lld_map_local_ba",
 ]
 
 

@@ -32,6 +32,7 @@
 namespace {
 
 using lld_map_dev::MapDev;
+using lld_map_dev::MapBa;
 using lld_map_dev::MapExt;
 using lld_map_dev::PoolPlan;
 using lld_map_dev::RowPool;
@@ -102,6 +103,14 @@ __global__ void map_set_cov_kernel(MapDev M, int n, const int32_t* slot, const i
   const int s = slot[i], c0 = cov_start[i], nc = min(cov_start[i + 1] - c0, 10);
   M.k_ncov[s] = nc;
   for (int j = 0; j < nc; j++) M.k_cov[10 * s + j] = cov[c0 + j];
+}
+// lld_map_set_keyframe_features / _poses: mnId (id null: poses only), the pose as SE3Quat, "has features"
+__global__ void map_set_kf_pose_kernel(MapBa Y, int n, const int32_t* slot, const u64* id, const double* qt) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  const int s = slot[i];
+  for (int c = 0; c < 7; c++) Y.k_qt[7 * (size_t)s + c] = qt[7 * (size_t)i + c];
+  if (id) { Y.k_id[s] = id[i]; Y.k_feat[s] = 1; }
 }
 // lld_map_download_links: what Tracking::UpdateLocalMap reads of a keyframe besides its points - parent, cov row, child row - back to the host
 __global__ void map_links_kernel(MapDev M, int n, const int32_t* slot, const int32_t* out_start, int32_t* parent, int32_t* ncov, int32_t* cov, int32_t* nchild, int32_t* child) {
@@ -453,6 +462,12 @@ int tables_reset(lld_map* m) {
     LLD_HIP_TRY(hipMemsetAsync(m->d_ext, 0, m->ext_bytes, st));
     m->idx.reset(); m->koct.reset(); m->kdep.reset();
   }
+  if (m->d_ba) {
+    LLD_HIP_TRY(hipMemsetAsync(m->d_ba, 0, m->ba_bytes, st));
+    LLD_HIP_TRY(hipMemsetAsync(m->Y.l_nobs, 0xff, (size_t)std::max(m->lim.max_lines, 1) * 4, st));     // no observation row
+    m->kuvr.reset(); m->kkl.reset(); m->lobs.reset(); m->lidx.reset();
+    std::fill(m->kf_feat.begin(), m->kf_feat.end(), (uint8_t)0);
+  }
   return LLD_OK;
 }
 
@@ -474,6 +489,34 @@ int ext_ensure(lld_map* m) {
   X.p_nobs = B.dev(pnobs); X.p_idx = B.dev(pidx); X.idx_pool = B.dev(ipool); X.k_oct = B.dev(koct); X.k_dep = B.dev(kdep); X.oct_pool = B.dev(opool);
   X.dep_pool = B.dev(dpool); X.k_thd = B.dev(kthd);
   m->idx.d_row = X.p_idx; m->idx.d_pool = X.idx_pool; m->koct.d_row = X.k_oct; m->koct.d_pool = X.oct_pool; m->kdep.d_row = X.k_dep; m->kdep.d_pool = X.dep_pool;
+  return LLD_OK;
+}
+
+// The bundle-adjustment tables and their pools, on the first call that fills them.  A failure leaves the map as it was.
+int ba_ensure(lld_map* m) {
+  if (m->d_ba) return LLD_OK;
+  if (m->lim.max_kf_points > (1 << 28) || m->lim.max_kf_lines > (1 << 26)) return LLD_ERR_UNSUPPORTED;      // twice the pools' totals stay int32 offsets
+  const size_t nk = m->lim.max_keyframes, nl = std::max(m->lim.max_lines, 1);
+  m->kuvr.init((int)nk, 3 * (int64_t)m->lim.max_kf_points); m->kkl.init((int)nk, 10 * (int64_t)m->lim.max_kf_lines);
+  m->lobs.init((int)nl, m->lim.max_kf_lines); m->lidx.init((int)nl, m->lim.max_kf_lines);
+  m->kf_feat.assign(nk, 0);
+  UploadBlock B;
+  const auto kid = B.take<u64>(nk); const auto kqt = B.take<double>(nk, 7); const auto kfeat = B.take<uint8_t>(nk); const auto kuvr = B.take<int2>(nk), kkl = B.take<int2>(nk);
+  const auto upool = B.take<int32_t>(m->kuvr.mirror.size()), kpool = B.take<int32_t>(m->kkl.mirror.size());
+  const auto lobs = B.take<int2>(nl), lidx = B.take<int2>(nl); const auto opool = B.take<int32_t>(m->lobs.mirror.size()), ipool = B.take<int32_t>(m->lidx.mirror.size());
+  const auto lnobs = B.take<int32_t>(nl);
+  const auto kmark = B.take<u64>(nk); const auto kcam = B.take<int32_t>(nk), fixed = B.take<int32_t>(nk), fixed_bad = B.take<int32_t>(nk);
+  char* d = nullptr;
+  if (hipMalloc(reinterpret_cast<void**>(&d), B.size) != hipSuccess) return LLD_ERR_ALLOC;
+  B.bind(nullptr, d);
+  if (hipMemsetAsync(d, 0, B.size, m->ctx->stream) != hipSuccess || hipMemsetAsync(B.dev(lnobs), 0xff, nl * 4, m->ctx->stream) != hipSuccess) { (void)hipFree(d); return LLD_ERR_HIP; }
+  m->d_ba = d; m->ba_bytes = B.size; m->mark_off = kmark.off; m->mark_bytes = nk * sizeof(u64);
+  MapBa& Y = m->Y;
+  Y.k_id = B.dev(kid); Y.k_qt = B.dev(kqt); Y.k_feat = B.dev(kfeat); Y.k_uvr = B.dev(kuvr); Y.k_kl = B.dev(kkl); Y.uvr_pool = B.dev(upool); Y.kl_pool = B.dev(kpool);
+  Y.l_obs = B.dev(lobs); Y.l_idx = B.dev(lidx); Y.lobs_pool = B.dev(opool); Y.lidx_pool = B.dev(ipool); Y.l_nobs = B.dev(lnobs);
+  Y.k_mark = B.dev(kmark); Y.k_cam = B.dev(kcam); Y.fixed = B.dev(fixed); Y.fixed_bad = B.dev(fixed_bad);
+  m->kuvr.d_row = Y.k_uvr; m->kuvr.d_pool = Y.uvr_pool; m->kkl.d_row = Y.k_kl; m->kkl.d_pool = Y.kl_pool;
+  m->lobs.d_row = Y.l_obs; m->lobs.d_pool = Y.lobs_pool; m->lidx.d_row = Y.l_idx; m->lidx.d_pool = Y.lidx_pool;
   return LLD_OK;
 }
 
@@ -561,6 +604,9 @@ void lld_map_destroy(lld_map* m) {
   (void)hipStreamSynchronize(m->ctx->stream);
   if (m->d_tables) (void)hipFree(m->d_tables);
   if (m->d_ext) (void)hipFree(m->d_ext);
+  if (m->d_ba) (void)hipFree(m->d_ba);
+  if (m->d_run) (void)hipFree(m->d_run);
+  if (m->h_ba) (void)hipHostFree(m->h_ba);
   if (m->d_up) (void)hipFree(m->d_up);
   if (m->h_up) (void)hipHostFree(m->h_up);
   if (m->h_down) (void)hipHostFree(m->h_down);
@@ -766,6 +812,102 @@ int lld_map_set_lines(lld_map* m, int32_t n, const int32_t* slot, const double* 
                      B.dev(d), B.dev(b));
   LLD_HIP_TRY(hipGetLastError());
   return LLD_OK;
+}
+
+int lld_map_set_keyframe_features(lld_map* m, int32_t n, const int32_t* slot, const uint64_t* mn_id, const float* Tcw, const int32_t* kp_start, const float* kp_uvr,
+                                  const int32_t* kl_start, const float* kl_left, const float* kl_right, const int32_t* kl_octave) {
+  if (!m || n < 0) return LLD_ERR_INVALID;
+  if (m->poisoned) return LLD_ERR_HIP;
+  if (n == 0) return LLD_OK;
+  if (!slot || !mn_id || !Tcw || !starts_ok(n, kp_start) || !starts_ok(n, kl_start)) return LLD_ERR_INVALID;
+  if ((kp_start[n] > 0 && !kp_uvr) || (kl_start[n] > 0 && (!kl_left || !kl_right || !kl_octave))) return LLD_ERR_INVALID;
+  if (!slots_ok(m->stamp_kf, m->epoch, n, slot)) return LLD_ERR_INVALID;
+  for (int i = 0; i < n; i++)                                         // one entry per keypoint and per keyline of a keyframe the map holds
+    if (!m->kf_set[slot[i]] || kp_start[i + 1] - kp_start[i] != m->kpt.len[slot[i]] || kl_start[i + 1] - kl_start[i] != m->kln.len[slot[i]]) return LLD_ERR_INVALID;
+  // the rows as the pools hold them: three words per keypoint, ten per keyline (the totals are the point and line rows', so they fit)
+  std::vector<int32_t> us((size_t)n + 1), ks((size_t)n + 1), kl((size_t)kl_start[n] * 10);
+  for (int i = 0; i <= n; i++) { us[i] = 3 * kp_start[i]; ks[i] = 10 * kl_start[i]; }
+  for (int k = 0; k < kl_start[n]; k++) {
+    std::memcpy(&kl[10 * (size_t)k], kl_left + 4 * (size_t)k, 16); std::memcpy(&kl[10 * (size_t)k + 4], kl_right + 4 * (size_t)k, 16);
+    kl[10 * (size_t)k + 8] = kl_octave[2 * (size_t)k]; kl[10 * (size_t)k + 9] = kl_octave[2 * (size_t)k + 1];
+  }
+  PoolPlan Pu, Pk;
+  // the limits first, the allocation behind them: fresh pools are empty, and the rows' totals are bounded by the point and line rows' limits
+  if (m->d_ba && (!m->kuvr.plan(n, slot, us.data(), Pu) || !m->kkl.plan(n, slot, ks.data(), Pk))) return LLD_ERR_UNSUPPORTED;
+  LLD_HIP_TRY(hipSetDevice(m->ctx->device));
+  const bool fresh = !m->d_ba;
+  int st = ba_ensure(m); if (st) return st;
+  if (fresh && (!m->kuvr.plan(n, slot, us.data(), Pu) || !m->kkl.plan(n, slot, ks.data(), Pk))) return LLD_ERR_UNSUPPORTED;      // (cannot happen)
+  UploadBlock B;
+  m->kuvr.reserve(B, Pu); m->kkl.reserve(B, Pk);
+  const auto s = B.take<int32_t>(n); const auto id = B.take<u64>(n); const auto qt = B.take<double>(n, 7);
+  st = up_begin(m, B); if (st) return st;
+  m->kuvr.commit(B, Pu, n, slot, us.data(), reinterpret_cast<const int32_t*>(kp_uvr));          // a float travels as its bit pattern
+  m->kkl.commit(B, Pk, n, slot, ks.data(), kl.data());
+  B.stage(s, slot); B.stage(id, reinterpret_cast<const u64*>(mn_id));
+  for (int i = 0; i < n; i++) { lld_se3_from_tcw_f32(Tcw + 16 * (size_t)i, B.host(qt) + 7 * (size_t)i); m->kf_feat[slot[i]] = 1; }
+  st = up_submit(m, B);
+  hipStream_t stream = m->ctx->stream;
+  if (!st) st = m->kuvr.launch(stream, B, Pu);
+  if (!st) st = m->kkl.launch(stream, B, Pk);
+  if (!st) {
+    hipLaunchKernelGGL(map_set_kf_pose_kernel, dim3((n + 255) / 256), dim3(256), 0, stream, m->Y, n, B.dev(s), B.dev(id), B.dev(qt));
+    if (hipGetLastError() != hipSuccess) st = LLD_ERR_HIP;
+  }
+  if (st) m->poisoned = true;                                        // the host's rows are ahead of the device's
+  return st;
+}
+
+int lld_map_set_keyframe_poses(lld_map* m, int32_t n, const int32_t* slot, const float* Tcw) {
+  if (!m || n < 0) return LLD_ERR_INVALID;
+  if (m->poisoned) return LLD_ERR_HIP;
+  if (n == 0) return LLD_OK;
+  if (!slot || !Tcw) return LLD_ERR_INVALID;
+  if (!slots_ok(m->stamp_kf, m->epoch, n, slot)) return LLD_ERR_INVALID;
+  for (int i = 0; i < n; i++) if (!m->d_ba || !m->kf_feat[slot[i]]) return LLD_ERR_INVALID;
+  LLD_HIP_TRY(hipSetDevice(m->ctx->device));
+  UploadBlock B;
+  const auto s = B.take<int32_t>(n); const auto qt = B.take<double>(n, 7);
+  int st = up_begin(m, B); if (st) return st;
+  B.stage(s, slot);
+  for (int i = 0; i < n; i++) lld_se3_from_tcw_f32(Tcw + 16 * (size_t)i, B.host(qt) + 7 * (size_t)i);
+  st = up_submit(m, B); if (st) return st;
+  hipLaunchKernelGGL(map_set_kf_pose_kernel, dim3((n + 255) / 256), dim3(256), 0, m->ctx->stream, m->Y, n, B.dev(s), (const u64*)nullptr, B.dev(qt));
+  LLD_HIP_TRY(hipGetLastError());
+  return LLD_OK;
+}
+
+int lld_map_set_line_observations(lld_map* m, int32_t n, const int32_t* slot, const int32_t* start, const int32_t* kf_slot, const int32_t* line_index,
+                                  const int32_t* n_obs) {
+  if (!m || n < 0) return LLD_ERR_INVALID;
+  if (m->poisoned) return LLD_ERR_HIP;
+  if (n == 0) return LLD_OK;
+  if (!slot || !n_obs || !starts_ok(n, start) || (start[n] > 0 && (!kf_slot || !line_index))) return LLD_ERR_INVALID;
+  if (!slots_ok(m->stamp_ln, m->epoch, n, slot) || !entries_in(kf_slot, start[n], 0, m->lim.max_keyframes)) return LLD_ERR_INVALID;
+  for (int i = 0; i < start[n]; i++) if (line_index[i] < 0) return LLD_ERR_INVALID;
+  for (int i = 0; i < n; i++) if (n_obs[i] < 0) return LLD_ERR_INVALID;
+  PoolPlan Po, Pi;
+  if (m->d_ba ? (!m->lobs.plan(n, slot, start, Po) || !m->lidx.plan(n, slot, start, Pi)) : start[n] > m->lim.max_kf_lines) return LLD_ERR_UNSUPPORTED;
+  LLD_HIP_TRY(hipSetDevice(m->ctx->device));
+  const bool fresh = !m->d_ba;
+  int st = ba_ensure(m); if (st) return st;
+  if (fresh && (!m->lobs.plan(n, slot, start, Po) || !m->lidx.plan(n, slot, start, Pi))) return LLD_ERR_UNSUPPORTED;      // (cannot happen: checked above)
+  UploadBlock B;
+  m->lobs.reserve(B, Po); m->lidx.reserve(B, Pi);
+  const auto s = B.take<int32_t>(n), no = B.take<int32_t>(n);
+  st = up_begin(m, B); if (st) return st;
+  m->lobs.commit(B, Po, n, slot, start, kf_slot); m->lidx.commit(B, Pi, n, slot, start, line_index);
+  B.stage(s, slot); B.stage(no, n_obs);
+  st = up_submit(m, B);
+  hipStream_t stream = m->ctx->stream;
+  if (!st) st = m->lobs.launch(stream, B, Po);
+  if (!st) st = m->lidx.launch(stream, B, Pi);
+  if (!st) {
+    hipLaunchKernelGGL(map_scatter_kernel, dim3((n + 255) / 256), dim3(256), 0, stream, n, B.dev(s), B.dev(no), m->Y.l_nobs);
+    if (hipGetLastError() != hipSuccess) st = LLD_ERR_HIP;
+  }
+  if (st) m->poisoned = true;                                        // the host's rows are ahead of the device's
+  return st;
 }
 
 int lld_frame_track_update_local_map(lld_frame* f, lld_map* m) {

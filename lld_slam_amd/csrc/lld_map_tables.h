@@ -32,6 +32,20 @@ struct MapExt {
   int32_t* p_nobs; int2* p_idx; int32_t* idx_pool; int2* k_oct; int2* k_dep; int32_t* oct_pool; int32_t* dep_pool; float* k_thd;
 };
 
+// The bundle-adjustment tables (lld_map_ba.hip).  All null until the first lld_map_set_keyframe_features / _poses / lld_map_set_line_observations.
+//   keyframe slot s  k_id = mnId, k_qt[7] = the pose as SE3Quat, k_feat (1: features were set), k_uvr = (offset, length) in uvr_pool of the
+//                    keypoints' (u, v, uR) float bits, three words per keypoint, k_kl = (offset, length) in kl_pool of the keylines, ten words
+//                    each: left[4], right[4] float bits, octave[2]
+//   line slot s      l_obs / l_idx = (offset, length) in lobs_pool / lidx_pool of mObservations: keyframe slot, keyline index; l_nobs =
+//                    MapLine::Observations(), -1: no observation row was ever set
+//   per call         k_mark (~0 unmarked, 0 local, 1 + (landmark ordinal << 32 | row position) of the first visit: fixed), k_cam = the
+//                    keyframe's camera index in the window, fixed / fixed_bad = the non-bad / bad keyframes marked fixed, in no order
+struct MapBa {
+  u64* k_id; double* k_qt; uint8_t* k_feat; int2* k_uvr; int2* k_kl; int32_t* uvr_pool; int32_t* kl_pool;
+  int2* l_obs; int2* l_idx; int32_t* lobs_pool; int32_t* lidx_pool; int32_t* l_nobs;
+  u64* k_mark; int32_t* k_cam; int32_t* fixed; int32_t* fixed_bad;
+};
+
 // ------------------------------------------------------------------------------------------------ host: the pools
 struct PoolPlan { bool repack = false; int n_up = 0; size_t n_data = 0; int64_t live_after = 0; Span<int32_t> slot, src, data; Span<int2> row; };
 
@@ -103,6 +117,12 @@ struct lld_map {
   lld_map_dev::RowPool obs, child, kpt, kln;
   // the culling tables (MapExt): allocated by the first setter that fills them
   lld_map_dev::MapExt X{}; char* d_ext = nullptr; size_t ext_bytes = 0; lld_map_dev::RowPool idx, koct, kdep;
+  // the bundle-adjustment tables (MapBa): allocated by the first setter that fills them; mark_off / mark_bytes: k_mark inside d_ba
+  lld_map_dev::MapBa Y{}; char* d_ba = nullptr; size_t ba_bytes = 0, mark_off = 0, mark_bytes = 0; lld_map_dev::RowPool kuvr, kkl, lobs, lidx;
+  std::vector<uint8_t> kf_feat;             // lld_map_set_keyframe_features named the slot since the last clear
+  // lld_map_ba_window's staging (pinned, device), grow-only; lld_map_local_ba's result arrays and the capacities of its last call
+  char* h_ba = nullptr; size_t h_ba_bytes = 0; char* d_run = nullptr; size_t d_run_bytes = 0;
+  std::vector<double> ba_res_f; std::vector<uint8_t> ba_res_b; int32_t ba_cap[6] = {0, 0, 0, 0, 0, 0};
   std::vector<uint8_t> kf_set;              // lld_map_set_keyframes named the slot since the last clear
   bool cov_lds_set = false;                 // map_covis_query_kernel was granted its 64 KB of dynamic LDS
   std::vector<uint32_t> stamp_pt, stamp_kf, stamp_ln; uint32_t epoch = 0;

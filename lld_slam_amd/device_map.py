@@ -46,6 +46,7 @@ class DeviceMap:
         f("map_covisibility").argtypes = [C.c_void_p, C.POINTER(abi.MapCovisibilityIn), C.POINTER(abi.MapCovisibilityOut)]
         f("map_covisibility").restype = C.c_int
         f("map_download_links").argtypes = [C.c_void_p, C.c_int32] + [c_int32_p] * 5 + [C.c_int32, c_int32_p]; f("map_download_links").restype = C.c_int
+        self._bind_ba()
         h = C.c_void_p()
         self.handle = None
         self._check(f("map_create")(ctx.handle, C.byref(self.limits), C.byref(h)), "lld_map_create")
@@ -187,6 +188,125 @@ class DeviceMap:
             for name in ("n_mps", "n_redundant", "redundant"):
                 del r[name]
         return r
+
+    # ------------------------------------------------------------------ the local BA window (lld_map_ba.hip)
+    def _bind_ba(self):
+        f = self.lib.fn
+        f("map_set_keyframe_features").argtypes = [C.c_void_p, C.c_int32, c_int32_p, c_uint64_p, c_float_p, c_int32_p, c_float_p, c_int32_p, c_float_p, c_float_p,
+                                                   c_int32_p]
+        f("map_set_keyframe_features").restype = C.c_int
+        f("map_set_keyframe_poses").argtypes = [C.c_void_p, C.c_int32, c_int32_p, c_float_p]; f("map_set_keyframe_poses").restype = C.c_int
+        f("map_set_line_observations").argtypes = [C.c_void_p, C.c_int32] + [c_int32_p] * 5; f("map_set_line_observations").restype = C.c_int
+        f("map_ba_window").argtypes = [C.c_void_p, C.POINTER(abi.MapBaIn), C.POINTER(abi.MapBaWindowOut)]; f("map_ba_window").restype = C.c_int
+        f("map_local_ba").argtypes = [C.c_void_p, C.POINTER(abi.MapBaIn), C.c_void_p, C.c_void_p, C.POINTER(abi.BAResult), C.POINTER(abi.MapBaIds)]
+        f("map_local_ba").restype = C.c_int
+
+    def set_keyframe_features(self, slot, mn_id, Tcw, kp_uvr, kl_left, kl_right, kl_octave):
+        """Per keyframe: mn_id, Tcw (4x4 float), and one array per keyframe in the lists kp_uvr [(n_kp, 3)], kl_left / kl_right [(n_kl, 4)],
+        kl_octave [(n_kl, 2)]; kl_right = -1 and right octave 0 for a keyline without a partner."""
+        cat = lambda rows, w, dt: (np.concatenate([np.asarray(r, dt).reshape(-1, w) for r in rows]) if len(rows) else np.zeros((0, w), dt))
+        kp_start = np.concatenate([[0], np.cumsum([np.asarray(r).reshape(-1, 3).shape[0] for r in kp_uvr])]).astype(np.int32)
+        kl_start = np.concatenate([[0], np.cumsum([np.asarray(r).reshape(-1, 4).shape[0] for r in kl_left])]).astype(np.int32)
+        k = [self._p(slot, np.int32, c_int32_p), self._p(mn_id, np.uint64, c_uint64_p), self._p(np.asarray(Tcw, np.float32).reshape(-1, 16), np.float32, c_float_p),
+             self._p(kp_start, np.int32, c_int32_p), self._p(cat(kp_uvr, 3, np.float32), np.float32, c_float_p), self._p(kl_start, np.int32, c_int32_p),
+             self._p(cat(kl_left, 4, np.float32), np.float32, c_float_p), self._p(cat(kl_right, 4, np.float32), np.float32, c_float_p),
+             self._p(cat(kl_octave, 2, np.int32), np.int32, c_int32_p)]
+        self._check(self.lib.fn("map_set_keyframe_features")(self.handle, len(k[0][0]), *[p for _, p in k]), "lld_map_set_keyframe_features")
+
+    def set_keyframe_poses(self, slot, Tcw):
+        k = [self._p(slot, np.int32, c_int32_p), self._p(np.asarray(Tcw, np.float32).reshape(-1, 16), np.float32, c_float_p)]
+        self._check(self.lib.fn("map_set_keyframe_poses")(self.handle, len(k[0][0]), *[p for _, p in k]), "lld_map_set_keyframe_poses")
+
+    def set_line_observations(self, slot, rows, n_obs):
+        """rows: per line one list of (keyframe slot, keyline index) in std::map iteration order; n_obs: MapLine::Observations() per line."""
+        start, kf_slot = csr([[o[0] for o in r] for r in rows])
+        _, index = csr([[o[1] for o in r] for r in rows])
+        k = [self._p(slot, np.int32, c_int32_p), self._p(start, np.int32, c_int32_p), self._p(kf_slot, np.int32, c_int32_p), self._p(index, np.int32, c_int32_p),
+             self._p(n_obs, np.int32, c_int32_p)]
+        self._check(self.lib.fn("map_set_line_observations")(self.handle, len(k[0][0]), *[p for _, p in k]), "lld_map_set_line_observations")
+
+    def _ba_in(self, kf_slots, cam, inv_level_sigma2):
+        s = np.ascontiguousarray(kf_slots, np.int32); sig = np.ascontiguousarray(inv_level_sigma2, np.float32)
+        a = abi.MapBaIn()
+        a.n_keyframes, a.n_levels = len(s), len(sig)
+        a.kf_slot = s.ctypes.data_as(c_int32_p); a.inv_level_sigma2 = sig.ctypes.data_as(c_float_p)
+        a.cam = abi.Camera(*[float(v) for v in cam])
+        return a, (s, sig)
+
+    BA_ARRAYS = (("cam_slot", np.int32, 0, 1), ("cam_qt", np.float64, 0, 7), ("point_slot", np.int32, 1, 1), ("pt_xyz", np.float64, 1, 3),
+                 ("pt_obs_start", np.int32, 1, -1), ("pt_obs_cam", np.int32, 2, 1), ("pt_obs_uvr", np.float64, 2, 3), ("pt_obs_inv_sigma2", np.float64, 2, 1),
+                 ("line_slot", np.int32, 3, 1), ("line_x0", np.float64, 3, 3), ("line_dir", np.float64, 3, 3), ("ln_obs_start", np.int32, 3, -1),
+                 ("ln_obs_cam", np.int32, 4, 1), ("ln_obs_left", np.float64, 4, 4), ("ln_obs_right", np.float64, 4, 4), ("ln_obs_octave", np.int32, 4, 2))
+    BA_COUNTS = ("n_cams", "n_points", "n_pt_obs", "n_lines", "n_ln_obs")
+
+    def ba_window(self, kf_slots, cam, inv_level_sigma2, capacities=None, phase_ms=None, fill=0):
+        """lld_map_ba_window.  Returns a dict: the seven counts, status, and - when the status is 0 - the arrays of the window and the three slot
+        lists, cut to their counts.  Without capacities (cameras, points, point observations, lines, line observations) the call is made with a
+        guess and repeated once with the counts the library reports; with them a short one raises (the error carries status and counts).
+        fill: the byte the arrays hold before the call (for tests that look at what a call leaves untouched; see raw)."""
+        a, keep = self._ba_in(kf_slots, cam, inv_level_sigma2)
+        retry = capacities is None
+        caps = [64, 1024, 4096, 64, 256] if capacities is None else [int(c) for c in capacities]
+        while True:
+            o = abi.MapBaWindowOut()
+            o.cam_capacity, o.point_capacity, o.pt_obs_capacity, o.line_capacity, o.ln_obs_capacity = caps
+            raw = {}
+            for name, dt, which, w in self.BA_ARRAYS:
+                arr = np.full(caps[which] + 1 if w < 0 else max(caps[which], 1) * w, fill, np.uint8).repeat(np.dtype(dt).itemsize).view(dt)
+                raw[name] = arr
+                setattr(o, name, arr.ctypes.data_as(c_int32_p if dt == np.int32 else c_double_p))
+            if phase_ms is not None:
+                assert phase_ms.dtype == np.float32 and phase_ms.size >= 3 and phase_ms.flags.c_contiguous
+                o.phase_ms = phase_ms.ctypes.data_as(c_float_p)
+            o.n_cams = -1
+            st = self.lib.fn("map_ba_window")(self.handle, C.byref(a), C.byref(o))
+            counts = dict(n_cams=o.n_cams, n_free_cams=o.n_free_cams, n_local_cams=o.n_local_cams, n_points=o.n_points, n_pt_obs=o.n_pt_obs,
+                          n_lines=o.n_lines, n_ln_obs=o.n_ln_obs)
+            short = st == abi.LLD_ERR_INVALID and o.n_cams >= 0
+            if short and retry:
+                caps, retry = [counts[k] for k in self.BA_COUNTS], False
+                continue
+            if st != abi.LLD_OK:
+                err = RuntimeError(f"lld_map_ba_window failed: {self.lib.fn('status_string')(st).decode()}")
+                err.status, err.counts, err.raw = st, (counts if short else None), raw
+                raise err
+            break
+        r = dict(counts, status=o.status, raw=raw)
+        if o.status == 0:
+            for name, dt, which, w in self.BA_ARRAYS:
+                n = counts[self.BA_COUNTS[which]]
+                r[name] = raw[name][:n + 1] if w < 0 else raw[name][:n * w].reshape((n, w) if w > 1 else (n,))
+        return r
+
+    def local_ba(self, kf_slots, cam, inv_level_sigma2, stop=False, params=None):
+        """lld_map_local_ba.  Returns (BAOutput or None, ids): ids holds status, n_local_cams, cam_slot, point_slot, line_slot and window (a
+        host.Window copy of what was solved); None when the status is not 0."""
+        from . import host
+        a, keep = self._ba_in(kf_slots, cam, inv_level_sigma2)
+        res, ids = abi.BAResult(), abi.MapBaIds()
+        flag = C.c_ubyte(1 if stop else 0)
+        if params is None:
+            params = host.ba_params(self.lib)
+        self._check(self.lib.fn("map_local_ba")(self.handle, C.byref(a), C.byref(params), C.byref(flag), C.byref(res), C.byref(ids)), "lld_map_local_ba")
+        out = dict(status=ids.status, n_local_cams=ids.n_local_cams)
+        if ids.status:
+            return None, out
+        w = ids.window
+        cp = lambda p, n, dt: np.ctypeslib.as_array(p, shape=(max(n, 1),))[:n].astype(dt, copy=True) if n else np.zeros(0, dt)
+        nc, npt, npo, nl, nlo = w.n_cams, w.n_points, w.n_pt_obs, w.n_lines, w.n_ln_obs
+        out.update(cam_slot=cp(ids.cam_slot, nc, np.int32), point_slot=cp(ids.point_slot, npt, np.int32), line_slot=cp(ids.line_slot, nl, np.int32),
+                   marked_bad_slot=cp(ids.marked_bad_slot, ids.n_marked_bad, np.int32))
+        out["window"] = host.Window(tuple(getattr(w.cam, k) for k in ("fx", "fy", "cx", "cy", "bf")), w.n_free_cams, cp(w.cam_qt, 7 * nc, np.float64).reshape(-1, 7),
+                                    cp(w.pt_xyz, 3 * npt, np.float64).reshape(-1, 3), cp(w.pt_obs_start, npt + 1, np.int32), cp(w.pt_obs_cam, npo, np.int32),
+                                    cp(w.pt_obs_uvr, 3 * npo, np.float64).reshape(-1, 3), cp(w.pt_obs_inv_sigma2, npo, np.float64),
+                                    cp(w.line_x0, 3 * nl, np.float64).reshape(-1, 3), cp(w.line_dir, 3 * nl, np.float64).reshape(-1, 3),
+                                    cp(w.ln_obs_start, nl + 1, np.int32), cp(w.ln_obs_cam, nlo, np.int32), cp(w.ln_obs_left, 4 * nlo, np.float64).reshape(-1, 4),
+                                    cp(w.ln_obs_right, 4 * nlo, np.float64).reshape(-1, 4), cp(w.ln_obs_octave, 2 * nlo, np.int32).reshape(-1, 2))
+        bo = host.BAOutput(cp(res.cam_qt, 7 * nc, np.float64).reshape(-1, 7), cp(res.pt_xyz, 3 * npt, np.float64).reshape(-1, 3),
+                           cp(res.line_x0, 3 * nl, np.float64).reshape(-1, 3), cp(res.line_dir, 3 * nl, np.float64).reshape(-1, 3),
+                           cp(res.pt_obs_outlier, npo, np.uint8), cp(res.ln_edge_outlier, 2 * nlo, np.uint8).reshape(-1, 2), cp(res.line_removed, nl, np.uint8),
+                           host.stats_dict(res.stats))
+        return bo, out
 
     def set_lines(self, slot, x0, dir, x1, x2, desc, bad):
         k = [self._p(slot, np.int32, c_int32_p), self._p(x0, np.float64, c_double_p), self._p(dir, np.float64, c_double_p), self._p(x1, np.float64, c_double_p),
