@@ -211,11 +211,156 @@ def point_details():
     return scene("point_details", b, [{"frame": [5, 9, 64, 1000, 3, 11, -1, 10, 7]}], max_points=64)
 
 
+# ---------------------------------------------------------------------------------------------------------------- past the kernels' widths
+# (lld_map.hip: kChildLds = 32 children of a visited entry in LDS and 64 per trip behind them, rows and prefix sums in tiles of 256, one
+# lane per keypoint in blocks of 256, the marks a bit set of (max_keyframes + 31) / 32 words, the extension loop's limit of 80)
+CHILD_LDS, WAVE, TILE = 32, 64, 256
+CHILD0 = 10                                        # children_long: the children's first slot
+
+
+def children_winner_positions(n):
+    """where children_long(n) puts the winner of its first four voted keyframes: among the LDS-resident ones, at the first position walked
+    in HBM, at the row's last position (for n = 97 and 161 a trip of its own), and inside the first HBM trip behind a bad LDS child"""
+    return [5, CHILD_LDS, n - 1, 40 if n > 41 else CHILD_LDS]
+
+
+def children_long(n):
+    """Six voted keyframes (slots 0..5, listed in slot order), each with a child row of the same n children in an order of its own; 0 and 1
+    share one row.  The children that are neither bad nor marked, by key: 150, 160, 170, 2^63 + 5, then 2^63 + 1000 + j.  The smallest key of
+    all (1) belongs to a bad child at position 3 of every row; two voted keyframes (marked from the start, keys 100 and 101) are children too."""
+    rng = np.random.default_rng(0xC41D + n)
+    b = Builder()
+    ids = chain_of(b, 6)
+    kids = list(range(CHILD0, CHILD0 + n - 2))
+    perm = rng.permutation(len(kids)).tolist()
+    bad_small, winners, rest = kids[perm[0]], [kids[j] for j in perm[1:5]], [kids[j] for j in perm[5:]]
+    b.kf(bad_small, 1, bad=1)
+    for w, k in zip(winners, (150, 160, 170, 2 ** 63 + 5)): b.kf(w, k)
+    for j, s in enumerate(rest):
+        if j % 4 == 0: b.kf(s, 2 ** 63 + 1000 + j)                        # live, behind every winner
+        else: b.kf(s, int(rng.integers(2, 2 ** 64 - 2, dtype=np.uint64)) if j % 4 != 1 else 2 + j, bad=1)
+    pos = children_winner_positions(n)
+
+    def row(places):                                                    # {child: position}; the bad smallest key at 3
+        places = dict(places); places[bad_small] = 3
+        others = [c for c in [0, 1] + kids if c not in places]
+        others = [others[j] for j in rng.permutation(len(others))]
+        r = [None] * n
+        for c, p in places.items(): r[p] = c
+        it = iter(others)
+        return [c if c is not None else next(it) for c in r]
+    shared = row({winners[0]: pos[0], winners[1]: pos[1]})
+    rows = [shared, list(shared), row({winners[2]: pos[2]}), row({winners[3]: pos[3]}), row({}), row({})]
+    for i in range(6): b.m["keyframes"][i]["child"] = rows[i]
+    return scene("children_%d" % n, b, [{"frame": ids}])
+
+
+def long_row(n, over=False):
+    """Keyframe 1 (listed second) has a point row and a line row of n entries: -1 at every 17th, a bad slot at every 19th, a slot never set at
+    every 23rd.  Entry 256, the first of the second tile, repeats entry 200 - but for the point row of 257 entries, where it is a slot of
+    its own, so that the second tile has something to write behind the first one's; a last entry beyond 256 repeats entry 10.  Keyframe 0
+    (listed first) already holds entries 2, 255 and n - 2.  The limits are the lists' lengths; over: one less."""
+    b = Builder()
+    row, bad, unset = [], set(), set()
+    for j in range(n):
+        if j % 17 == 3: row.append(-1)
+        elif j % 19 == 5: row.append(j); bad.add(j)
+        elif j % 23 == 7: row.append(j); unset.add(j)
+        else: row.append(j)
+    lrow = list(row)
+    lrow[TILE] = lrow[200]
+    if n - 1 > TILE: row[TILE] = row[200]; row[n - 1] = lrow[n - 1] = row[10]
+    first = [row[2], row[TILE - 1], row[n - 2]]
+    assert all(s >= 0 and s not in bad and s not in unset for s in first + [row[200], row[10], row[TILE]])
+    b.kf(0, 10, points=[n + 1] + first, lines=first[::-1]); b.kf(1, 20, points=row, lines=lrow)
+    for s in sorted(set(row + [n + 1, n + 40]) - {-1} - unset):          # n + 40: a set slot beyond every slot never set
+        b.pt(s, obs=[k for k in (0, 1) if s in b.m["keyframes"][k]["points"]], bad=s in bad)
+        if s != n + 1: b.ln(s, bad=s in bad)
+    n_pts = len(set(row + [n + 1]) - {-1} - unset - bad); n_lns = len(set(lrow) - {-1} - unset - bad)
+    return scene("row_%d%s" % (n, "_over" if over else ""), b, [{"frame": [n + 1, row[0]]}], max_local_points=n_pts - over, max_local_lines=n_lns - over)
+
+
+def prefix_600():
+    """600 voted, listed keyframes (one MapPoint votes for all of them), key order scrambled against slot order; each has two or three
+    points of its own, every fifth one of another keyframe's, every seventh a line of its own, every 21st another one's."""
+    n = 600
+    b = Builder()
+    for i in range(n):
+        pts = [3 * i, 3 * i + 1] + ([3 * i + 2] if i % 2 else []) + ([3 * ((i * 7 + 1) % n)] if i % 5 == 0 else [])
+        lns = ([i // 7] if i % 7 == 0 else []) + ([(i // 7 + 40) % 86] if i % 21 == 0 else [])
+        b.kf(i, 7 * ((i * 389) % n) + 1, points=pts, lines=lns)
+        for p in pts[:3 if i % 2 else 2]: b.pt(p, obs=[i])
+    for l in range(86): b.ln(l)
+    b.pt(3 * n, obs=list(range(n)))
+    return scene("prefix_600", b, [{"frame": [3 * n]}], max_local_points=2048, max_local_lines=128)
+
+
+def voted_n(n):
+    """n voted keyframes, each with one unmarked covisible neighbour of its own.  The loop visits an entry while the list holds at most 80:
+    with 40 voted it visits every entry and ends at 80, with 80 voted it visits the first entry (81 listed), with 81 none (81 listed)."""
+    b = Builder()
+    ids = chain_of(b, n)
+    for i in range(n): b.m["keyframes"][i]["cov"] = [n + i]
+    for i in range(n, 2 * n): b.kf(i, 1000 + i)
+    return scene("voted_%d" % n, b, [{"frame": ids}])
+
+
+FRAME_1000_KP = (255, 256, 257, 511, 512, 999)
+
+
+def frame_1000():
+    """A frame of 1 000 keypoints that holds MapPoints at the last keypoint of the first block of 256 and at keypoints of the three blocks
+    behind it only; in the second frame the live and the bad ones have changed places."""
+    b = Builder()
+    for k in range(6): b.kf(k, 60 - k, points=[k])
+    for p, obs in enumerate(([0], [1], [1, 2], [3], [3, 4], [5])): b.pt(p, obs=obs)
+    for p in (6, 7, 8): b.pt(p, obs=[0, 5], bad=1)
+    steps = []
+    for at in (dict(zip(FRAME_1000_KP, (0, 6, 2, 7, 4, 5))), dict(zip(FRAME_1000_KP, (6, 1, 7, 3, 8, 8)))):
+        steps.append({"frame": [at.get(k, -1) for k in range(1000)]})
+    return scene("frame_1000", b, steps)
+
+
+def slot_roles(nk):
+    """the keyframe slots of slots_scene(nk): the bits 0 and 31 of the first word, bit 0 of the second and the bits of the last word"""
+    if nk == 1 << 18:
+        return dict(V1=nk - 1, V2=0, V3=32, N=nk - 32, C=31, N2=33, C3=30, P=nk - 31)
+    assert nk == 33
+    return dict(V1=32, V2=0, V3=1, N=31, C=30, N2=2, C3=3, P=29)
+
+
+def slots_scene(nk):
+    """max_keyframes = nk.  Voted V1, V2, V3 in key order.  V1: cov [V2 (marked), N], children [V3 (marked), C], parent V2 (marked).
+    V2: cov [N, C, V1 (all marked by then), N2], children [N, C].  V3: children [C3, V1], parent P: pushed, and the loop is left."""
+    r = slot_roles(nk)
+    V1, V2, V3, N, C, N2, C3, P = (r[k] for k in ("V1", "V2", "V3", "N", "C", "N2", "C3", "P"))
+    b = Builder()
+    b.kf(V1, 10, parent=V2, cov=[V2, N], child=[V3, C], points=[5, 1]); b.kf(V2, 20, cov=[N, C, V1, N2], child=[N, C], points=[1, 2], lines=[0])
+    b.kf(V3, 30, parent=P, child=[C3, V1], points=[3]); b.kf(N, 40, points=[4]); b.kf(C, 50, points=[2, 0]); b.kf(N2, 60); b.kf(C3, 70, points=[6])
+    b.kf(P, 80, points=[7, 5])
+    for p, obs in ((5, [V1]), (1, [V1, V2]), (3, [V3]), (0, []), (2, []), (4, []), (6, []), (7, [])): b.pt(p, obs=obs)
+    b.ln(0)
+    return scene("slots_%d" % nk, b, [{"frame": [5, 1, 3]}], max_keyframes=nk)
+
+
+def slots_expected(nk):
+    """slots_scene(nk)'s answer, written out by hand"""
+    r = slot_roles(nk)
+    return dict(local_keyframes=[r[k] for k in ("V1", "V2", "V3", "N", "C", "N2", "C3", "P")], local_points=[5, 1, 2, 3, 4, 0, 6, 7], local_lines=[0],
+                ref_keyframe=r["V1"], n_voted=3, n_bad_cleared=0, status=0, vote_empty=0)
+
+
+def width_scenes():
+    return [children_long(n) for n in (33, 96, 97, 161)] + [long_row(257), long_row(513), long_row(257, over=True), prefix_600(), voted_n(40), voted_n(80), voted_n(81),
+                                                            slots_scene(33)]
+
+
 def all_scenes():
+    """every scene a frame of 256 keypoints can hold and whose dense text file is small"""
     s = [random_map(i) for i in range(10)]
     s += [empty_vote(), bad_voted(), tie(), parent_break(0), parent_break(2), parent_break(None), parent_break(2, bad_parent=True), neighbours(), children()]
     s += limit_80() + [voted_overflow(1024), voted_overflow(1025)] + list_overflow() + [point_details()]
-    return s
+    return s + width_scenes()
 
 
 # ---------------------------------------------------------------------------------------------------------------- a scene as a text file

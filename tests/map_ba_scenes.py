@@ -326,9 +326,83 @@ def no_lines():
     return sc.link(), [0, 1]
 
 
-def wide(n_points=None, n_observers=None, n_line_observers=None, n_local=None):
+def trip(n_points, n_lines):
+    """n_points local points and n_lines local lines in the row of keyframe 0 (slot 4), past the 8 192 landmarks one trip of the grid-stride
+    kernels covers.  Observers, written out (link() would search every row for every landmark): keyframe 0 all of them, local keyframe 1
+    (slot 2) every 1 000th point, the last three points and every line, fixed keyframe 2 (slot 0) the last two points and the odd lines,
+    bad keyframe 3 (slot 1) the last point and the last line."""
+    sc = Scene()
+    P, Ls = list(range(n_points)), list(range(n_lines))
+    rows = {4: P, 2: sorted(set(P[::1000] + P[-3:])), 0: P[-2:], 1: P[-1:]}
+    lrows = {4: Ls, 2: Ls[::-1], 0: Ls[1::2], 1: Ls[-1:]}
+    for s, mn, key, bad in ((4, 7, 40, 0), (2, 3, 10, 0), (0, 9, 30, 0), (1, 5, 20, 1)):
+        sc.kf(s, mn, rows[s], lrows[s], bad=bad, key=key, mono=[1], no_partner=[0])
+    order = (2, 1, 0, 4)                                                   # ascending order_key
+    at = {s: {p: i for i, p in enumerate(rows[s])} for s in rows}; lat = {s: {l: i for i, l in enumerate(lrows[s])} for s in lrows}
+    for p in P: sc.pt(p, obs=[(s, at[s][p]) for s in order if p in at[s]])
+    for l in Ls: sc.ln(l, obs=[(s, lat[s][l]) for s in order if l in lat[s]], n_obs=4)
+    return sc.link(), [4, 2]
+
+
+def line_rows(n):
+    """n local lines in the row of keyframe 0, between them a -1 at every 16th entry, a bad line at every 21st, one with three observations
+    at every 25th and, at entry 256, entry 200 again; fixed keyframe 1 observes all of them, local keyframe 2 every third (and lists five
+    of them before its own)."""
+    sc = Scene()
+    row, live, j = [], [], 0
+    while len(live) < n:
+        k = len(row)
+        if k == 256: row.append(row[200])
+        elif k % 16 == 5: row.append(-1)
+        else:
+            row.append(j)
+            if k % 21 != 9 and k % 25 != 13: live.append(j)
+            j += 1
+    others = [l for l in row if l >= 0 and l not in set(live)]
+    assert row[200] in live and len(set(live)) == n
+    row1 = [l for l in dict.fromkeys(row) if l >= 0][::-1]
+    row2 = live[7:40:8] + [j, j + 1] + live[::3]
+    sc.kf(0, 3, [0], row); sc.kf(1, 1, [0], row1, key=5, no_partner=range(0, len(row1), 4)); sc.kf(2, 2, [1, 0], row2, key=2000)
+    sc.pt(0); sc.pt(1)
+    for k, l in enumerate(others): sc.ln(l, bad=k % 2 == 0, n_obs=4 if k % 2 == 0 else 3)
+    for l in live + [j, j + 1]: sc.ln(l, n_obs=4 + l % 3)
+    return sc.link(), [0, 2]
+
+
+def local_spread(n):
+    """n listed keyframes, mn_id and order_key each scrambled against slot order, every eleventh bad; each has two points and a line of its
+    own, every fourth one of an earlier keyframe's points and every sixth an earlier one's line."""
+    sc = Scene()
+    for s in range(n):
+        pts = [2 * s, 2 * s + 1] + ([2 * ((s * 5) % max(s, 1))] if s % 4 == 0 else [])
+        lns = [s] + ([(s * 7) % max(s, 1)] if s % 6 == 0 else [])
+        sc.kf(s, 1 + (s * 389) % n, pts, lns, bad=(s % 11 == 5), key=5000 + (s * 77) % n)
+    for p in range(2 * n): sc.pt(p)
+    for l in range(n): sc.ln(l, n_obs=4)
+    return sc.link(), list(range(n))
+
+
+def fixed_cameras(n):
+    """three local keyframes with 40 points and two lines each; n other keyframes (every thirteenth bad) observe one to three of the points
+    and every tenth a line, order_key scrambled against slot order: first visits spread over the landmarks and over the rows' positions"""
+    sc = Scene()
+    for s in range(3): sc.kf(s, s + 1, list(range(40 * s, 40 * s + 40)), [2 * s, 2 * s + 1], key=10 ** 6 + s)
+    for f in range(n):
+        pts = sorted({(f * 37) % 120, (f * 53 + 7) % 120} | ({(f * 11) % 120} if f % 3 == 0 else set()))
+        sc.kf(3 + f, 10 + f, pts, [f % 6] if f % 10 == 0 else [], bad=(f % 13 == 6), key=1000 + 3 * ((f * 389) % n))
+    for p in range(120): sc.pt(p)
+    for l in range(6): sc.ln(l, n_obs=4)
+    return sc.link(), [0, 1, 2]
+
+
+def wide(n_points=None, n_observers=None, n_line_observers=None, n_local=None, n_lines=None, n_local_spread=None, n_fixed=None):
     """14: one past a width.  n_points local points in one keyframe; a point with n_observers observers; a line with n_line_observers
-    observers (mn_id descending along the row); n_local listed keyframes."""
+    observers (mn_id descending along the row); n_local listed keyframes.  Past 8 192 landmarks: trip(n_points, n_lines or 0).
+    n_lines alone: line_rows; n_local_spread: local_spread; n_fixed: fixed_cameras."""
+    if n_points and n_points > 8000: return trip(n_points, n_lines or 0)
+    if n_lines: return line_rows(n_lines)
+    if n_local_spread: return local_spread(n_local_spread)
+    if n_fixed: return fixed_cameras(n_fixed)
     sc = Scene()
     if n_points:
         sc.kf(0, 1, list(range(n_points))); sc.kf(1, 2, [3, 1])

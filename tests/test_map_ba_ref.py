@@ -128,10 +128,24 @@ def test_restatement_equals_the_walk_on_the_named_scenes(name):
     same(R.ba_window(m, q, S.SIGMA2, se3), walk(m, q, S.SIGMA2))
 
 
-@pytest.mark.parametrize("kw", [dict(n_points=257), dict(n_observers=65), dict(n_line_observers=65), dict(n_local=40)], ids=lambda k: "%s%d" % next(iter(k.items())))
+WIDE = [dict(n_points=257), dict(n_observers=65), dict(n_line_observers=65), dict(n_local=40), dict(n_points=8193), dict(n_points=8190, n_lines=5), dict(n_lines=257),
+        dict(n_lines=513), dict(n_local_spread=600), dict(n_fixed=300)]
+
+
+@pytest.mark.parametrize("kw", WIDE, ids=lambda k: "-".join("%s%d" % i for i in k.items()))
 def test_restatement_equals_the_walk_on_the_wide_scenes(kw):
     m, q = S.wide(**kw)
-    same(R.ba_window(m, q, S.SIGMA2, se3), walk(m, q, S.SIGMA2))
+    ref = R.ba_window(m, q, S.SIGMA2, se3)
+    same(ref, walk(m, q, S.SIGMA2))
+    # the scenes past the kernels' widths are as wide as they were made to be
+    if kw.get("n_points", 0) > 8000: assert ref["n_points"] == kw["n_points"] and ref["n_lines"] == kw.get("n_lines", 0) and ref["marked_bad"] == [1]
+    if "n_lines" in kw and "n_points" not in kw:
+        assert ref["n_lines"] == kw["n_lines"] + 2 and len(m["keyframes"][0]["lines"]) > kw["n_lines"]
+        local = set(ref["line_slot"].tolist())                       # every tile of 256 row entries adds local lines behind the tiles before it
+        row = m["keyframes"][0]["lines"]
+        assert all(len(local & set(row[t:t + 256]) - set(row[:t])) > 0 for t in range(0, len(row), 256)) and len(row) > 256 * (kw["n_lines"] // 256)
+    if "n_local_spread" in kw: assert ref["n_local_cams"] > 512 and ref["n_points"] == 2 * ref["n_local_cams"] and ref["n_lines"] == ref["n_local_cams"]
+    if "n_fixed" in kw: assert ref["n_cams"] - ref["n_local_cams"] > 256 and len(ref["marked_bad"]) > 16
 
 
 @pytest.mark.parametrize("name", sorted(S.HAND))
