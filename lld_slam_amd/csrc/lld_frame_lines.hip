@@ -2,7 +2,7 @@
 // on the frame, its result written where the chain reads Frame::line_matches), lld_frame_lines_download, and lld_frame_new_map_lines
 // (Tracking::MatchLinesLastKF, src/Tracking.cc:1449-1611, between two resident frames).
 //
-// The matching kernels are lld_match.hip's (line_candidates_kernel, line_resolve_kernel, line_cells_kernel, line_lastkf_kernel), reached
+// The matching kernels are lld_line_match.hip's (line_candidates_kernel, line_resolve_kernel, line_cells_kernel, line_lastkf_kernel), reached
 // through lld_track_internal.h; the state is lld_frame_track.hip's (frame_state_build_lines).  The device code of this file is what the
 // reference does around MatchLinesLastKF's loop: "was this line of the last frame tracked by the current one" (:1518) as an id look-up, and
 // the numbering of the created MapLines in creation order (:1597-1606) with their entry into mCurrentFrame.mvpMapLines (:1602).
@@ -91,7 +91,7 @@ int lld_frame_build_lines(lld_frame* f, const lld_frame_lines_build* L) {
     if (L->n_right > 0 && (!L->right || !L->right_octave || !L->desc_right)) return LLD_ERR_INVALID;
     if (!octaves_ok(L->left_octave, L->n_left) || !octaves_ok(L->right_octave, L->n_right)) return LLD_ERR_INVALID;
     if (L->n_left > frame_max_lines(f->nt)) return LLD_ERR_UNSUPPORTED;
-    if (const int st = line_stereo_check(L->n_left, L->n_right, L->dim)) return st;
+    if (const int st = line_limits_check(L->n_left, L->n_right, L->dim)) return st;
   }
   LLD_HIP_TRY(hipSetDevice(f->ctx->device));
   if (f->track) LLD_HIP_TRY(hipStreamSynchronize(f->ctx->stream));          // kernels of the state this call replaces may still run

@@ -15,7 +15,7 @@
 //                ids of the MapPoints the outlier discard marked (mnLastFrameSeen = mnId, :949) and of the MapLines this frame already
 //                tracked (tracked_last_id = mnId, :1117): SearchLocalPoints / AddLinesFrom skip them by id.
 //
-// Kernels of this file: the bookkeeping between the library's search / line / pose kernels (lld_orb_search.hip, lld_match.hip, lld_pose.hip),
+// Kernels of this file: the bookkeeping between the library's search / line / pose kernels (lld_orb_search.hip, lld_line_match.hip, lld_pose.hip),
 // i.e. what the reference does in the few lines of C++ between its calls.  Host half of a stage: one UploadBlock (lld_upload_block.h) declares the
 // uploaded arrays and the scratch behind them once, region structs (here and in lld_frame_track_state.h) lay out, pack and bind each group of
 // arrays, stage_begin / stage_submit size the buffers and queue the one copy.
@@ -291,7 +291,7 @@ int state_fill(lld_frame* f, const lld_frame_lines* L, const lld_frame_lines_bui
       }
     }
     void* d_match_work = nullptr;
-    if (nr > 0) { const int st = lld_ctx_scratch(ctx, line_stereo_work_bytes(nl, nr), &d_match_work); if (st) return st; }   // device scratch: ordered by the stream
+    if (nr > 0) { const int st = lld_ctx_scratch(ctx, line_work_bytes(nl, nr), &d_match_work); if (st) return st; }   // device scratch: ordered by the stream
     LB.bind(static_cast<char*>(f->h_lines), LB.d);
     std::memset(LB.h, 0, LB.up_bytes);
     LB.stage(ll, Bd->left); LB.stage(lo, Bd->left_octave); LB.stage(ld, Bd->desc_left);
@@ -403,7 +403,7 @@ int run_lines(lld_frame* f, hipStream_t st, const lld_track_params* P, const Upl
   if (U.n <= 0 || S->nl <= 0) return LLD_OK;
   LineFrameDev Cur{S->nl, S->ln_left, S->ln_loct, S->ln_right, S->ln_match, S->D.ln_has, S->ln_cell, S->ln_desc, S->dim};
   const LineApplyDev ap{S->D.ln_has, S->D.ln_x0, S->D.ln_dir, S->D.ln_id, S->D.tracked, S->D.n_tracked, S->D.tracked_cap, B.dev(U.id)};
-  return line_track_launch_dev(f->ctx, st, S->D.line_params, U.dev(B, d_skip), Cur, P->line_md_thr, d_line_work, B.dev(U.matches), ap);
+  return line_track_launch_dev(st, S->D.line_params, U.dev(B, d_skip), Cur, P->line_md_thr, d_line_work, B.dev(U.matches), ap);
 }
 
 int run_pose(lld_frame* f, hipStream_t st, const lld_track_params* P, void* d_pose_work, int stage) {
@@ -455,7 +455,7 @@ int local_map_stage(lld_frame* f, const lld_track_params* P, int nq, int n_map, 
   U.reserve_scratch(B); MPU.reserve_scratch(B);
   const auto lskip2 = B.take<uint8_t>(std::max(n_map, 1)), inview = B.take<uint8_t>(std::max(nq, 1));
   sc.reserve(B, nq, nt);
-  const auto lwork = B.take<char>(line_track_work_bytes(n_map, S->nl)), pwork = B.take<char>(pose_track_work_bytes(nt, S->nl));
+  const auto lwork = B.take<char>(line_work_bytes(n_map, S->nl)), pwork = B.take<char>(pose_track_work_bytes(nt, S->nl));
   const auto bk_kp = B.take<uint8_t>(map ? nt : 0), bk_ln = B.take<uint8_t>(map ? S->nl : 0);
   int s = stage_begin(S, ctx, 1, B); if (s) return s;
   if (!map) { MPU.stage(B, mp, point_id); U.stage(B, local_lines); }
@@ -572,7 +572,7 @@ int lld_frame_track_motion_model(lld_frame* f, const lld_track_params* P, const 
   B.end_upload();
   U.reserve_scratch(B);
   sc[0].reserve(B, nq, nt); sc[1].reserve(B, nq, nt, &sc[0]);
-  const auto lwork = B.take<char>(line_track_work_bytes(n_map, S->nl)), pwork = B.take<char>(pose_track_work_bytes(nt, S->nl));
+  const auto lwork = B.take<char>(line_work_bytes(n_map, S->nl)), pwork = B.take<char>(pose_track_work_bytes(nt, S->nl));
   s = stage_begin(S, ctx, 0, B); if (s) return s;
   // ---- pack
   LP.stage(B, last, last_point_id); U.stage(B, last_lines); H.stage(B, S->consts, view, pose_qt);

@@ -104,25 +104,28 @@ struct BowSearchDev {
 };
 int bow_search_launch(hipStream_t st, const BowSearchDev& in, const ApplyDev& ap);
 
-// ---------------------------------------------------------------- Tracking::AddLinesFrom on device arrays (lld_match.hip)
-struct LineTrackDevParams { double K[9]; double R[9]; double t[3]; double tr[3]; double thr_base, sx, sy; int monocular, use_grid; };   // = LineTrackParams of lld_match.hip
+// ---------------------------------------------------------------- the line matchers on device arrays (lld_line_match.hip)
+// The limits every line matcher with a resolve shares (include/lld_amd.h, lld_line_match_greedy): LLD_ERR_UNSUPPORTED for dim > LLD_LINE_DIM_MAX,
+// for a row of `cols` distances + the descriptor or the resolve's rows + cols words above LLD_LINE_LDS_CEILING; LLD_OK when either side is empty.
+// Decided from the counts alone, so every route asks before it allocates or queues anything.
+int line_limits_check(int rows, int cols, int dim);
+size_t line_work_bytes(int rows, int cols);          // the d_work of the launchers below: gate [rows][cols] | distances [rows][cols] | candidate lists [rows]
+
+// Tracking::AddLinesFrom.  The camera the gate kernel takes (by value, or from device memory where a pose kernel wrote it):
+struct LineTrackDevParams { double K[9]; double R[9]; double t[3]; double tr[3]; double thr_base, sx, sy; int monocular, use_grid; };
 struct LineMapDev { int n; const double* x0; const double* dir; const double* x1; const double* x2; const uint8_t* skip; const float* desc; };
 struct LineFrameDev { int n_cur; const float* left; const int32_t* loct; const float* right; const int32_t* lmatch; const uint8_t* occupied; const int32_t* cell;
                       const float* desc; int dim; };
 // mCurrentFrame.mvpMapLines[mi] = pML; pML->tracked_last_id = mnId (src/Tracking.cc:1116-1117), done by the assignment kernel itself
 struct LineApplyDev { uint8_t* ln_has; double* ln_x0; double* ln_dir; int32_t* ln_id; int32_t* tracked; int32_t* n_tracked; int tracked_cap; const int32_t* map_id; };
-size_t line_track_work_bytes(int n_map, int n_cur);
 int line_cells_dev(hipStream_t st, const float* d_left, int n, double sx, double sy, int32_t* d_cell);
 // params_d: LineTrackDevParams in device memory (written by the tracker's pose kernel); matches_d [n_map]
-int line_track_launch_dev(lld_ctx* ctx, hipStream_t st, const LineTrackDevParams* params_d, const LineMapDev& map, const LineFrameDev& cur, double md_thr,
+int line_track_launch_dev(hipStream_t st, const LineTrackDevParams* params_d, const LineMapDev& map, const LineFrameDev& cur, double md_thr,
                           void* d_work, int32_t* matches_d, const LineApplyDev& apply);
 
 // TwoFrameLineMatcher::MatchLines of the frame's stereo pair (the kernels of lld_line_match_stereo) on device arrays: matches_d [nl] is the
-// frame's line_matches, match_dist_d [nl] the accepted distances (DBL_MAX where none).  check: the limits of lld_line_match_stereo
-// (LLD_ERR_UNSUPPORTED), decided from the counts alone; nothing is launched when either side is empty.
+// frame's line_matches, match_dist_d [nl] the accepted distances (DBL_MAX where none).  Nothing is launched when either side is empty.
 struct LineStereoDev { int nl, nr, dim; const float* left; const int32_t* loct; const float* right; const int32_t* roct; const float* dl; const float* dr; };
-int line_stereo_check(int nl, int nr, int dim);
-size_t line_stereo_work_bytes(int nl, int nr);
 int line_stereo_launch_dev(hipStream_t st, const lld_line_stereo_params& prm, const LineStereoDev& in, void* d_work, int32_t* matches_d, double* match_dist_d);
 // Tracking::MatchLinesLastKF (the kernel of lld_line_match_last_frame) between two resident frames: `last` is a LineFrameDev whose n_cur counts
 // the last frame's lines; the cameras are the frames' own LineTrackDevParams in device memory (K, sx, sy from cur_cam).

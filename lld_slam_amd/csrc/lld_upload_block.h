@@ -17,9 +17,13 @@ template <class T> struct Span { size_t off = 0, n = 0; };   // n T's at byte of
 
 struct UploadBlock {
   size_t size = 0, up_bytes = 0;             // bytes declared so far; the prefix that travels (end_upload)
-  char* h = nullptr; char* d = nullptr;      // pinned host base (the uploaded prefix only), device base (the whole block)
+  char* h = nullptr; char* d = nullptr;      // pinned host base (the prefix that travels), device base (the whole block)
   template <class T> Span<T> take(size_t n, size_t per = 1) { const Span<T> s{size, n * per}; size += al(s.n * sizeof(T)); return s; }
   void end_upload() { up_bytes = size; }     // what was declared so far is uploaded, what follows is device-only scratch
+  // a call that also fetches results declares them right behind the upload and ends them here: the pinned base then spans travel_bytes()
+  size_t down_bytes = 0;
+  void end_download() { down_bytes = size - up_bytes; }
+  size_t travel_bytes() const { return up_bytes + down_bytes; }
   void bind(char* host, char* dev) { h = host; d = dev; }
   template <class T> T* host(const Span<T>& s) const { return reinterpret_cast<T*>(h + s.off); }
   template <class T> T* dev(const Span<T>& s) const { return reinterpret_cast<T*>(d + s.off); }

@@ -11,7 +11,7 @@
 //                                             (xor 32, 16, 8, 7, 2, 1) and so their own addition order
 //   the segmented __shfl_down sums (lld_ba_points.h, lld_ba_schur.h)                      runs of lanes of varying length, not aligned groups
 //   the partial `xor 16, xor 32` column sums (lld_ba_solve.h, lld_ba_chol_sparse.h, lld_posegraph.hip pg dense solve)   two steps, not a full group
-//   every (value, index) and best/second merge (lld_match.hip, lld_landmark.hip lm_line_*, lld_bow_merge.h bow_match_node, the top-2 merge of
+//   every (value, index) and best/second merge (lld_match.hip, lld_line_match.hip, lld_landmark.hip lm_line_*, lld_bow_merge.h bow_match_node, the top-2 merge of
 //                                             orb_search_kernel)   two coupled values per step
 //   the ballot rankings and counts (lld_frame_finish.hip, lld_frame_lines.hip, lld_new_points.hip np_compact, lld_covisibility.hip,
 //                                             lld_landmark.hip compact_kept, lld_orb_extract.hip, lld_ba_control.h)   order-preserving ranks from lane masks
