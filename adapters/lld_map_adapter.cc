@@ -228,6 +228,10 @@ void MapOnDevice::LocalBundleAdjustment(KeyFrame* pKF, bool* pbStopFlag, lld_sla
     }
   }
   // ---- the map follows the objects (res and ids are not read beyond this point: the setters do not touch them, but nothing needs them)
+  // This push-back re-sends every window point's whole row although only a position and a normal moved.  lld_map_ba_apply does the loops
+  // above on the device's tables and needs no push-back, but this adapter stays on the setters: the object doubles of lld_slam_objects.h
+  // do not model nObs, SetBadFlag's cascade or UpdateNormalAndDepth, so the objects could not follow what the device decides.  Making
+  // them do so changes what the doubles compute and belongs in a change of its own.
   const int32_t n_local = ids.n_local_cams;
   std::vector<KeyFrame*> rows(lost.begin(), lost.end());
   std::vector<int32_t> pose_slot; std::vector<float> pose;

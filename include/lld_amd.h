@@ -2782,7 +2782,7 @@ typedef struct {
 } lld_map_ba_window_out;
 int  lld_map_ba_window(lld_map* map, const lld_map_ba_in* in, lld_map_ba_window_out* out);
 /* lld_map_ba_window into pinned buffers the map owns (grown on demand: a call that finds them short repeats the assembly once), then
- * lld_local_ba_stopflag on that window.  The map's tables are not changed.  Every pointer of `result` and `ids` is SET by the call and
+ * lld_local_ba_stopflag on that window.  The map's tables are not changed (lld_map_ba_apply, below, does that).  Every pointer of `result` and `ids` is SET by the call and
  * points into memory of the map, valid until the next lld_map_local_ba or lld_map_destroy on it; ids->window is the window that was solved.
  * With ids->status != 0 nothing was solved and the counts are 0.  params = NULL: lld_ba_params_default; stop_flag may be NULL. */
 typedef struct {
@@ -2798,6 +2798,115 @@ typedef struct {
 } lld_map_ba_ids;
 int  lld_map_local_ba(lld_map* map, const lld_map_ba_in* in, const lld_ba_params* params, volatile const unsigned char* stop_flag,
                       lld_ba_result* result, lld_map_ba_ids* ids);
+
+/* ------------------------------------------------------------------ a local BA's result applied to the resident map (lld_map_apply.hip)
+ * The last third of Optimizer::LocalBundleAdjustment, the part under mMutexMapUpdate (src/Optimizer.cc:1334-1386): the outlier
+ * observations are erased, the local keyframes get their poses, every local point its position and UpdateNormalAndDepth, every line its
+ * minimal position - on the map's tables, by the device.  It is the first call that lets the device change rows of the map; the host's
+ * bookkeeping of the rows (lengths, live totals, the copy a repack is made from) follows every change, so the setters, the limits and
+ * lld_map_covisibility go on as if the caller had sent the changed rows itself.
+ *
+ * Two tables beyond the ones above:
+ *   lld_map_set_point_refs    MapPoint::mpRefKF of point slot[i] as a keyframe slot, or -1: unknown.  A pool of its own that the first call
+ *                             allocates (every slot then -1).  The contract is that of the other setters: everything is validated first
+ *                             (LLD_ERR_INVALID for a NULL array, n < 0, a slot out of range or named twice, a ref_kf outside
+ *                             [-1, max_keyframes)), a refusal changes nothing, one block and one copy per call, lld_map_clear sets every
+ *                             slot to -1 again.
+ *   the camera centre         lld_map_set_keyframe_features and lld_map_set_keyframe_poses also store KeyFrame::SetPose's Ow of the float
+ *                             Tcw they are given (float[3] per keyframe, computed on the host: -Rcw^T tcw, each entry one three-term sum in
+ *                             double rounded once - the arithmetic of lld_loop_correct's centres).
+ *
+ * lld_map_ba_apply applies a result to THE WINDOW THIS MAP ASSEMBLED LAST (lld_map_ba_window or lld_map_local_ba): that window's index
+ * arrays (point_slot, pt_obs_start, pt_obs_cam, cam_slot and the line twins) are still in the map's device staging, only the result
+ * travels up.  The result is the caller's to pass (the arrays of lld_ba_result); the "returned before optimising" exit (:1220-1222) is the
+ * caller's too - it does not call.  The map counts its mutations (every lld_map_set_* that is not refused, lld_map_clear,
+ * LLD_MAP_COVIS_WRITE_COV and an apply itself).  LLD_ERR_INVALID before anything is queued, nothing changed: a NULL argument or array
+ * (phase_ms may be NULL; arrays of a count of 0 may be NULL); n_levels < 1; no complete window is staged (the last assembly had a status
+ * other than 0 or a short capacity, or there was none); the map changed since that window was assembled - so a second apply of one
+ * window is refused too; n_cams, n_points, n_pt_obs, n_lines or n_ln_obs differ from that window's.  LLD_ERR_HIP for a poisoned map.
+ * One upload, kernels on the context's stream with no host trip between them, one download, one wait; no allocation per call (the
+ * staging grows only).  A HIP failure behind the first launch poisons the map.
+ *
+ * Cameras  [0, n_local_cams) of the window, the mn_id == 0 one included: T = lld_se3_to_tcw_f32(cam_qt[c]) on the host (out->tcw), the
+ *          stored pose lld_se3_from_tcw_f32(T), the centre of T (out->ow is read back from the table).
+ * Points   Every window point on its own.  Its erase list: its window observations with pt_obs_outlier = 1, the ones at a keypoint with
+ *          uR < 0 (the mono edges) first, then the others, each in window order - the reference's order (:1282-1310).
+ *          One erasure (MapPoint.cc:111-137, KeyFrame::EraseMapPointMatch before it): the observer cam_slot[pt_obs_cam[e]] is looked up in the
+ *          stored row; the observer's point-row entry at the stored keypoint index is set to -1 whatever it holds; n_obs drops by 2 if
+ *          uR >= 0 at that keypoint (a float compare on the stored bits), else by 1; the entry leaves the observation row and the index row
+ *          (the order of the rest and the row's place are kept).  n_obs <= 2 after an erasure: the point goes bad (SetBadFlag, :151-168) -
+ *          state isBad, EVERY remaining observer's point-row entry at its stored index set to -1 (by index, the observer is not looked
+ *          at), both rows empty; the erasures behind that one do nothing, so n_obs stays where it went bad.
+ *          A stored index outside the observer's point row (a bad or never-set observer met by the cascade; never a window camera) is
+ *          not written: counted in n_index_skipped, flagged on the point.
+ *          mpRefKF: of a surviving point whose reference keyframe was erased, the first entry of the final row (mObservations.begin()).
+ *          Of a point that went bad the table gets -1; the reference leaves whatever begin() was at the erasure that took mpRefKF,
+ *          a value that depends on its erase order.  Without lld_map_set_point_refs every reference is -1 and none is written.
+ *          Position: p_pos = (float)pt_xyz for every window point, bad ones included (SetWorldPos does not look).
+ *          UpdateNormalAndDepth (:330-371) for every window point that is not bad and whose row is not empty, with the numerics of
+ *          lld_mappoint_refresh: the terms in row order, the centres from the table (the local cameras' are the new ones), the level =
+ *          the octave of the reference keyframe's keypoint at the point's stored index there - keypoint 0 when the reference keyframe is
+ *          no observer (observations[pRefKF] default-inserts 0); the reference keyframe's bad flag is not read.  Nothing is refreshed
+ *          (normal and distances stay, LLD_MAP_APPLY_NO_REFERENCE) when the reference is -1, has no keypoint row reaching that index or
+ *          no centre, when an observer has no centre, or when the octave is outside [0, n_levels).
+ * Lines    A line with line_removed = 1 is skipped whole (:1320-1323).  Of the others an observation is erased when either of its two
+ *          ln_edge_outlier flags is set, in window order (ascending mn_id).  One erasure (MapLine.cc:77-104): the observer's line-row
+ *          entry at the stored keyline index set to -1; n_obs drops by 2 if that keyline's stored right end points are not four times
+ *          -1.0f, else by 1; the entry leaves l_obs / l_idx.  n_obs <= 4: the line goes bad - and MapLine::SetBadFlag clears
+ *          mObservations BEFORE it calls EraseMapLineMatch(this), which then finds no index: the remaining observers' line-row entries
+ *          are NOT cleared, only the row is emptied and the line marked bad; later erasures of that line do nothing.  l_x0 / l_dir take
+ *          the result for every line that was not removed; l_x1 / l_x2 stay.
+ * Outputs  are read from the tables behind the writes, per window point and per window line, in window order. */
+#define LLD_MAP_APPLY_WENT_BAD       1   /* pt_flags bits */
+#define LLD_MAP_APPLY_REFRESHED      2   /* normal, min and max distance were recomputed */
+#define LLD_MAP_APPLY_NO_REFERENCE   4
+#define LLD_MAP_APPLY_INDEX_SKIPPED  8
+typedef struct {
+  int32_t n_cams, n_points, n_pt_obs, n_lines, n_ln_obs;   /* the counts of the window the result belongs to */
+  int32_t n_levels;
+  const double*  cam_qt;            /* [n_cams][7]; the local cameras' are read       */
+  const double*  pt_xyz;            /* [n_points][3]                                  */
+  const double*  line_x0;           /* [n_lines][3]                                   */
+  const double*  line_dir;          /* [n_lines][3]                                   */
+  const uint8_t* pt_obs_outlier;    /* [n_pt_obs]                                     */
+  const uint8_t* ln_edge_outlier;   /* [n_ln_obs][2]                                  */
+  const uint8_t* line_removed;      /* [n_lines]                                      */
+  const float*   level_scale;       /* [n_levels] mvScaleFactors                      */
+} lld_map_ba_apply_in;
+typedef struct {
+  int32_t n_local_cams;             /* written: the window's                          */
+  int32_t n_pt_obs_erased, n_ln_obs_erased;   /* erasures that took effect            */
+  int32_t n_points_bad, n_lines_bad;          /* went bad in this call                */
+  int32_t n_index_skipped;
+  float*   tcw;                     /* [n_local_cams][16] the poses as the keyframes get them (SetPose) */
+  float*   ow;                      /* [n_local_cams][3]                              */
+  float*   pt_pos;                  /* [n_points][3]                                  */
+  float*   pt_normal;               /* [n_points][3]                                  */
+  float*   pt_min_distance;         /* [n_points]                                     */
+  float*   pt_max_distance;         /* [n_points]                                     */
+  int32_t* pt_n_obs;                /* [n_points]                                     */
+  int32_t* pt_ref_kf;               /* [n_points] -1 without lld_map_set_point_refs   */
+  int32_t* pt_row_len;              /* [n_points]                                     */
+  uint8_t* pt_flags;                /* [n_points] LLD_MAP_APPLY_* bits                */
+  uint8_t* ln_bad;                  /* [n_lines]                                      */
+  int32_t* ln_n_obs;                /* [n_lines]                                      */
+  int32_t* ln_row_len;              /* [n_lines]                                      */
+  float*   phase_ms;                /* NULL, or [3]: HIP-event times of upload, kernels, download */
+} lld_map_ba_apply_out;
+int  lld_map_set_point_refs(lld_map* map, int32_t n, const int32_t* slot, const int32_t* ref_kf);
+int  lld_map_ba_apply(lld_map* map, const lld_map_ba_apply_in* in, lld_map_ba_apply_out* out);
+/* The rows of one pool as the DEVICE holds them, for a caller that audits its mirror and for the tests: CSR with the capacity protocol of
+ * lld_map_download_links - start [n + 1] is always written (from the host's lengths), data [capacity] only if the total fits, otherwise
+ * LLD_ERR_INVALID with start alone written (data may be NULL with a capacity of 0).  LLD_ERR_HIP when a device row's length is not the
+ * host's: never with a sound map.  A pool that was never allocated has empty rows.  One small upload, one kernel, one download, one wait.
+ * LLD_ERR_INVALID also for a NULL argument, an unknown kind, n < 0, a slot out of the pool's range; n = 0 is LLD_OK. */
+#define LLD_MAP_ROWS_POINT_OBS   0   /* per point slot: the observing keyframe slots                */
+#define LLD_MAP_ROWS_POINT_IDX   1   /* per point slot: the keypoint indices, parallel to them      */
+#define LLD_MAP_ROWS_KF_POINTS   2   /* per keyframe slot: the point slot per keypoint, or -1       */
+#define LLD_MAP_ROWS_KF_LINES    3   /* per keyframe slot: the line slot per keyline, or -1         */
+#define LLD_MAP_ROWS_LINE_OBS    4   /* per line slot: the observing keyframe slots                 */
+#define LLD_MAP_ROWS_LINE_IDX    5   /* per line slot: the keyline indices                          */
+int  lld_map_download_rows(lld_map* map, int32_t kind, int32_t n, const int32_t* slot, int32_t* start, int32_t capacity, int32_t* data);
 
 #if defined(__GNUC__)
 #pragma GCC visibility pop

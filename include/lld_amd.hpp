@@ -568,6 +568,66 @@ class DeviceMap {
     check(lld_map_local_ba(m, &in, params, reinterpret_cast<volatile const unsigned char*>(pbStopFlag), &r.result, &r.ids), "lld_map_local_ba");
     return r;
   }
+  // ---- a local BA's result applied to the map's tables (lld_map_ba_apply): the last third of LocalBundleAdjustment, under mMutexMapUpdate
+  // MapPoint::mpRefKF per point slot as a keyframe slot, -1: unknown
+  void SetPointRefs(const std::vector<int32_t>& slot, const std::vector<int32_t>& ref_kf) {
+    if (ref_kf.size() != slot.size()) check(LLD_ERR_INVALID, "lld_map_set_point_refs");
+    check(lld_map_set_point_refs(m_, (int32_t)slot.size(), slot.data(), ref_kf.data()), "lld_map_set_point_refs");
+  }
+  struct ApplyResult {           // the outputs of lld_map_ba_apply, per local camera, per window point and per window line
+    int n_local_cams = 0, n_pt_obs_erased = 0, n_ln_obs_erased = 0, n_points_bad = 0, n_lines_bad = 0, n_index_skipped = 0;
+    std::vector<float> tcw, ow, pt_pos, pt_normal, pt_min_distance, pt_max_distance;
+    std::vector<int32_t> pt_n_obs, pt_ref_kf, pt_row_len, ln_n_obs, ln_row_len;
+    std::vector<uint8_t> pt_flags, ln_bad;
+    float phase_ms[3] = {0.f, 0.f, 0.f};
+  };
+  // `result` (of LocalBa on this map, or any solve of the window this map assembled last) applied to that window; n_cams .. n_ln_obs are the
+  // window's counts, level_scale = mvScaleFactors.  The caller skips the call when the solve returned before optimising.
+  ApplyResult ApplyLocalBa(const lld_ba_result& result, int n_cams, int n_points, int n_pt_obs, int n_lines, int n_ln_obs, const std::vector<float>& level_scale,
+                           bool timed = false) {
+    return ApplyLocalBaOn(m_, result, n_cams, n_points, n_pt_obs, n_lines, n_ln_obs, level_scale, timed);
+  }
+  static ApplyResult ApplyLocalBaOn(lld_map* m, const lld_ba_result& result, int n_cams, int n_points, int n_pt_obs, int n_lines, int n_ln_obs,
+                                    const std::vector<float>& level_scale, bool timed = false) {
+    lld_map_ba_apply_in in{};
+    in.n_cams = n_cams; in.n_points = n_points; in.n_pt_obs = n_pt_obs; in.n_lines = n_lines; in.n_ln_obs = n_ln_obs; in.n_levels = (int32_t)level_scale.size();
+    in.cam_qt = result.cam_qt; in.pt_xyz = result.pt_xyz; in.line_x0 = result.line_x0; in.line_dir = result.line_dir;
+    in.pt_obs_outlier = result.pt_obs_outlier; in.ln_edge_outlier = result.ln_edge_outlier; in.line_removed = result.line_removed; in.level_scale = level_scale.data();
+    ApplyResult r;
+    const size_t nc = n_cams > 0 ? n_cams : 0, np = n_points > 0 ? n_points : 0, nl = n_lines > 0 ? n_lines : 0;
+    r.tcw.assign(16 * nc + 1, 0.f); r.ow.assign(3 * nc + 1, 0.f);
+    r.pt_pos.assign(3 * np + 1, 0.f); r.pt_normal.assign(3 * np + 1, 0.f); r.pt_min_distance.assign(np + 1, 0.f); r.pt_max_distance.assign(np + 1, 0.f);
+    r.pt_n_obs.assign(np + 1, 0); r.pt_ref_kf.assign(np + 1, -1); r.pt_row_len.assign(np + 1, 0); r.pt_flags.assign(np + 1, 0);
+    r.ln_bad.assign(nl + 1, 0); r.ln_n_obs.assign(nl + 1, 0); r.ln_row_len.assign(nl + 1, 0);
+    lld_map_ba_apply_out o{};
+    o.tcw = r.tcw.data(); o.ow = r.ow.data(); o.pt_pos = r.pt_pos.data(); o.pt_normal = r.pt_normal.data(); o.pt_min_distance = r.pt_min_distance.data();
+    o.pt_max_distance = r.pt_max_distance.data(); o.pt_n_obs = r.pt_n_obs.data(); o.pt_ref_kf = r.pt_ref_kf.data(); o.pt_row_len = r.pt_row_len.data();
+    o.pt_flags = r.pt_flags.data(); o.ln_bad = r.ln_bad.data(); o.ln_n_obs = r.ln_n_obs.data(); o.ln_row_len = r.ln_row_len.data();
+    o.phase_ms = timed ? r.phase_ms : nullptr;
+    check(lld_map_ba_apply(m, &in, &o), "lld_map_ba_apply");
+    r.n_local_cams = o.n_local_cams; r.n_pt_obs_erased = o.n_pt_obs_erased; r.n_ln_obs_erased = o.n_ln_obs_erased; r.n_points_bad = o.n_points_bad;
+    r.n_lines_bad = o.n_lines_bad; r.n_index_skipped = o.n_index_skipped;
+    r.tcw.resize(16 * (size_t)o.n_local_cams); r.ow.resize(3 * (size_t)o.n_local_cams);
+    r.pt_pos.resize(3 * np); r.pt_normal.resize(3 * np); r.pt_min_distance.resize(np); r.pt_max_distance.resize(np);
+    r.pt_n_obs.resize(np); r.pt_ref_kf.resize(np); r.pt_row_len.resize(np); r.pt_flags.resize(np); r.ln_bad.resize(nl); r.ln_n_obs.resize(nl); r.ln_row_len.resize(nl);
+    return r;
+  }
+  // lld_map_download_rows: the rows of one pool (LLD_MAP_ROWS_*) as the device holds them, CSR
+  struct Rows { std::vector<int32_t> start, data; };
+  Rows DownloadRows(int kind, const std::vector<int32_t>& slot) const { return DownloadRowsOn(m_, kind, slot); }
+  static Rows DownloadRowsOn(lld_map* m, int kind, const std::vector<int32_t>& slot) {
+    Rows r;
+    const size_t n = slot.size();
+    r.start.assign(n + 1, 0); r.data.assign(1, 0);
+    int st = lld_map_download_rows(m, kind, (int32_t)n, slot.data(), r.start.data(), 0, nullptr);
+    if (st == LLD_ERR_INVALID && n && r.start[n] > 0) {
+      r.data.assign(r.start[n], 0);
+      st = lld_map_download_rows(m, kind, (int32_t)n, slot.data(), r.start.data(), r.start[n], r.data.data());
+    }
+    check(st, "lld_map_download_rows");
+    r.data.resize(n ? r.start[n] : 0);
+    return r;
+  }
   const lld_map_limits& limits() const { return limits_; }
   lld_map* get() const { return m_; }
  private:

@@ -465,8 +465,26 @@ class MapBaIds(C.Structure):
                 ("n_marked_bad", C.c_int32), ("reserved", C.c_int32), ("marked_bad_slot", c_int32_p), ("window", BAWindow)]
 
 
+class MapBaApplyIn(C.Structure):
+    """lld_map_ba_apply_in."""
+    _fields_ = [("n_cams", C.c_int32), ("n_points", C.c_int32), ("n_pt_obs", C.c_int32), ("n_lines", C.c_int32), ("n_ln_obs", C.c_int32), ("n_levels", C.c_int32),
+                ("cam_qt", c_double_p), ("pt_xyz", c_double_p), ("line_x0", c_double_p), ("line_dir", c_double_p),
+                ("pt_obs_outlier", c_uint8_p), ("ln_edge_outlier", c_uint8_p), ("line_removed", c_uint8_p), ("level_scale", c_float_p)]
+
+
+class MapBaApplyOut(C.Structure):
+    """lld_map_ba_apply_out."""
+    _fields_ = [("n_local_cams", C.c_int32), ("n_pt_obs_erased", C.c_int32), ("n_ln_obs_erased", C.c_int32), ("n_points_bad", C.c_int32),
+                ("n_lines_bad", C.c_int32), ("n_index_skipped", C.c_int32),
+                ("tcw", c_float_p), ("ow", c_float_p), ("pt_pos", c_float_p), ("pt_normal", c_float_p), ("pt_min_distance", c_float_p),
+                ("pt_max_distance", c_float_p), ("pt_n_obs", c_int32_p), ("pt_ref_kf", c_int32_p), ("pt_row_len", c_int32_p), ("pt_flags", c_uint8_p),
+                ("ln_bad", c_uint8_p), ("ln_n_obs", c_int32_p), ("ln_row_len", c_int32_p), ("phase_ms", c_float_p)]
+
+
 MAP_BA_MAX_LOCAL = 1024
 MAP_BA_NO_FEATURE_DATA = 1
+MAP_APPLY_WENT_BAD, MAP_APPLY_REFRESHED, MAP_APPLY_NO_REFERENCE, MAP_APPLY_INDEX_SKIPPED = 1, 2, 4, 8
+MAP_ROWS = dict(point_obs=0, point_idx=1, kf_points=2, kf_lines=3, line_obs=4, line_idx=5)
 MAP_COVIS_MAX_CONNECTED = 4096
 MAP_COVIS_WRITE_COV = 4
 MAP_COVIS_CONN_OVERFLOW, MAP_COVIS_NO_KEYPOINT_DATA = 1, 2
@@ -520,6 +538,7 @@ PRODUCT_SYMBOLS = [
     "lld_frame_track_update_local_map", "lld_frame_track_local_map_resident", "lld_frame_local_map_download",
     "lld_map_set_observations_indexed", "lld_map_set_keyframe_keypoints", "lld_map_set_covisibles", "lld_map_covisibility", "lld_map_download_links",
     "lld_map_set_keyframe_features", "lld_map_set_keyframe_poses", "lld_map_set_line_observations", "lld_map_ba_window", "lld_map_local_ba",
+    "lld_map_set_point_refs", "lld_map_ba_apply", "lld_map_download_rows",
 ]
 
 

@@ -37,6 +37,17 @@ LLD_HD void rwc_mul(const float* Rcw, const float* v, float* o) {
   }
 }
 
+// KeyFrame::SetPose's camera centre (src/KeyFrame.cc:82-85) of a float pose given as the rows of [R|t] (Tcw[12], or the first three rows of
+// a row-major 4x4): Ow = -Rwc*tcw with Rwc = Rcw.t() - one product with double accumulation, one rounding, then the sign.  The resident
+// map's host setters and the kernels of lld_map_correct.hip share it.
+LLD_HD void camera_centre(const float* T, float* ow) {
+  const float R[9] = {T[0], T[1], T[2], T[4], T[5], T[6], T[8], T[9], T[10]};
+  const float t[3] = {T[3], T[7], T[11]};
+  rwc_mul(R, t, ow);
+#pragma unroll
+  for (int i = 0; i < 3; ++i) ow[i] = -ow[i];
+}
+
 // Eigen::Quaterniond(Matrix3d) — trace branch / largest-diagonal branch (Eigen Quaternion.h).
 LLD_HD Quat quat_from_rotation(const Mat3& R) {
   Quat q;

@@ -23,6 +23,7 @@
 //
 // The tables' declarations are in lld_map_tables.h; covisibility on the same tables (lld_map_covisibility) is in lld_map_covis.hip.
 #include "lld_common.h"
+#include "lld_device_math.h"
 #include "lld_frame_track_state.h"
 #include "lld_map_internal.h"
 #include "lld_map_tables.h"
@@ -104,12 +105,13 @@ __global__ void map_set_cov_kernel(MapDev M, int n, const int32_t* slot, const i
   M.k_ncov[s] = nc;
   for (int j = 0; j < nc; j++) M.k_cov[10 * s + j] = cov[c0 + j];
 }
-// lld_map_set_keyframe_features / _poses: mnId (id null: poses only), the pose as SE3Quat, "has features"
-__global__ void map_set_kf_pose_kernel(MapBa Y, int n, const int32_t* slot, const u64* id, const double* qt) {
+// lld_map_set_keyframe_features / _poses: mnId (id null: poses only), the pose as SE3Quat and its camera centre, "has features"
+__global__ void map_set_kf_pose_kernel(MapBa Y, int n, const int32_t* slot, const u64* id, const double* qt, const float* ow) {
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n) return;
   const int s = slot[i];
   for (int c = 0; c < 7; c++) Y.k_qt[7 * (size_t)s + c] = qt[7 * (size_t)i + c];
+  for (int c = 0; c < 3; c++) Y.k_ow[3 * (size_t)s + c] = ow[3 * (size_t)i + c];
   if (id) { Y.k_id[s] = id[i]; Y.k_feat[s] = 1; }
 }
 // lld_map_download_links: what Tracking::UpdateLocalMap reads of a keyframe besides its points - parent, cov row, child row - back to the host
@@ -457,6 +459,8 @@ int tables_reset(lld_map* m) {
   LLD_HIP_TRY(hipMemsetAsync(m->D.k_parent, 0xff, (size_t)m->lim.max_keyframes * 4, st));
   LLD_HIP_TRY(hipMemsetAsync(m->D.st + ST_REF, 0xff, 4, st));
   m->obs.reset(); m->child.reset(); m->kpt.reset(); m->kln.reset();
+  m->mutations++; m->win.valid = false;
+  if (m->d_ref) LLD_HIP_TRY(hipMemsetAsync(m->d_ref, 0xff, (size_t)m->lim.max_points * 4, st));
   std::fill(m->kf_set.begin(), m->kf_set.end(), (uint8_t)0);
   if (m->d_ext) {
     LLD_HIP_TRY(hipMemsetAsync(m->d_ext, 0, m->ext_bytes, st));
@@ -501,7 +505,7 @@ int ba_ensure(lld_map* m) {
   m->lobs.init((int)nl, m->lim.max_kf_lines); m->lidx.init((int)nl, m->lim.max_kf_lines);
   m->kf_feat.assign(nk, 0);
   UploadBlock B;
-  const auto kid = B.take<u64>(nk); const auto kqt = B.take<double>(nk, 7); const auto kfeat = B.take<uint8_t>(nk); const auto kuvr = B.take<int2>(nk), kkl = B.take<int2>(nk);
+  const auto kid = B.take<u64>(nk); const auto kqt = B.take<double>(nk, 7); const auto kow = B.take<float>(nk, 3); const auto kfeat = B.take<uint8_t>(nk); const auto kuvr = B.take<int2>(nk), kkl = B.take<int2>(nk);
   const auto upool = B.take<int32_t>(m->kuvr.mirror.size()), kpool = B.take<int32_t>(m->kkl.mirror.size());
   const auto lobs = B.take<int2>(nl), lidx = B.take<int2>(nl); const auto opool = B.take<int32_t>(m->lobs.mirror.size()), ipool = B.take<int32_t>(m->lidx.mirror.size());
   const auto lnobs = B.take<int32_t>(nl);
@@ -512,7 +516,7 @@ int ba_ensure(lld_map* m) {
   if (hipMemsetAsync(d, 0, B.size, m->ctx->stream) != hipSuccess || hipMemsetAsync(B.dev(lnobs), 0xff, nl * 4, m->ctx->stream) != hipSuccess) { (void)hipFree(d); return LLD_ERR_HIP; }
   m->d_ba = d; m->ba_bytes = B.size; m->mark_off = kmark.off; m->mark_bytes = nk * sizeof(u64);
   MapBa& Y = m->Y;
-  Y.k_id = B.dev(kid); Y.k_qt = B.dev(kqt); Y.k_feat = B.dev(kfeat); Y.k_uvr = B.dev(kuvr); Y.k_kl = B.dev(kkl); Y.uvr_pool = B.dev(upool); Y.kl_pool = B.dev(kpool);
+  Y.k_id = B.dev(kid); Y.k_qt = B.dev(kqt); Y.k_ow = B.dev(kow); Y.k_feat = B.dev(kfeat); Y.k_uvr = B.dev(kuvr); Y.k_kl = B.dev(kkl); Y.uvr_pool = B.dev(upool); Y.kl_pool = B.dev(kpool);
   Y.l_obs = B.dev(lobs); Y.l_idx = B.dev(lidx); Y.lobs_pool = B.dev(opool); Y.lidx_pool = B.dev(ipool); Y.l_nobs = B.dev(lnobs);
   Y.k_mark = B.dev(kmark); Y.k_cam = B.dev(kcam); Y.fixed = B.dev(fixed); Y.fixed_bad = B.dev(fixed_bad);
   m->kuvr.d_row = Y.k_uvr; m->kuvr.d_pool = Y.uvr_pool; m->kkl.d_row = Y.k_kl; m->kkl.d_pool = Y.kl_pool;
@@ -606,6 +610,9 @@ void lld_map_destroy(lld_map* m) {
   if (m->d_ext) (void)hipFree(m->d_ext);
   if (m->d_ba) (void)hipFree(m->d_ba);
   if (m->d_run) (void)hipFree(m->d_run);
+  if (m->d_ref) (void)hipFree(m->d_ref);
+  if (m->d_ap) (void)hipFree(m->d_ap);
+  if (m->h_ap) (void)hipHostFree(m->h_ap);
   if (m->h_ba) (void)hipHostFree(m->h_ba);
   if (m->d_up) (void)hipFree(m->d_up);
   if (m->h_up) (void)hipHostFree(m->h_up);
@@ -634,6 +641,7 @@ int lld_map_set_points(lld_map* m, int32_t n, const int32_t* slot, const float* 
   const auto s = B.take<int32_t>(n); const auto pos = B.take<float>(n, 3), nrm = B.take<float>(n, 3), mind = B.take<float>(n), maxd = B.take<float>(n);
   const auto d = B.take<uint32_t>(n, 8); const auto b = B.take<uint8_t>(n);
   int st = up_begin(m, B); if (st) return st;
+  m->mutations++;
   B.stage(s, slot); B.stage(pos, world_pos); B.stage(nrm, normal); B.stage(mind, min_distance); B.stage(maxd, max_distance); B.stage(d, desc); B.stage(b, bad);
   st = up_submit(m, B); if (st) return st;
   hipLaunchKernelGGL(map_set_points_kernel, dim3((n + 255) / 256), dim3(256), 0, m->ctx->stream, m->D, n, B.dev(s), B.dev(pos), B.dev(nrm), B.dev(mind), B.dev(maxd), B.dev(d), B.dev(b));
@@ -654,6 +662,7 @@ int lld_map_set_observations(lld_map* m, int32_t n, const int32_t* slot, const i
   m->obs.reserve(B, P);
   const auto drop = B.take<int32_t>(m->d_ext ? n : 0);              // with the culling tables: these rows carry no keypoint indices any more
   int st = up_begin(m, B); if (st) return st;
+  m->mutations++;
   m->obs.commit(B, P, n, slot, start, kf_slot);
   if (m->d_ext) {
     B.stage(drop, slot);
@@ -690,6 +699,7 @@ int lld_map_set_observations_indexed(lld_map* m, int32_t n, const int32_t* slot,
   m->obs.reserve(B, P); m->idx.reserve(B, Pi);
   const auto s = B.take<int32_t>(n), no = B.take<int32_t>(n);
   st = up_begin(m, B); if (st) return st;
+  m->mutations++;
   m->obs.commit(B, P, n, slot, start, kf_slot); m->idx.commit(B, Pi, n, slot, start, kp_index);
   B.stage(s, slot); B.stage(no, n_obs);
   st = up_submit(m, B);
@@ -722,6 +732,7 @@ int lld_map_set_keyframe_keypoints(lld_map* m, int32_t n, const int32_t* slot, c
   m->koct.reserve(B, Po); m->kdep.reserve(B, Pd);
   const auto s = B.take<int32_t>(n); const auto thd = B.take<float>(n);
   st = up_begin(m, B); if (st) return st;
+  m->mutations++;
   m->koct.commit(B, Po, n, slot, start, octave); m->kdep.commit(B, Pd, n, slot, start, reinterpret_cast<const int32_t*>(depth));    // a float travels as its bit pattern
   B.stage(s, slot); B.stage(thd, th_depth);
   st = up_submit(m, B);
@@ -748,6 +759,7 @@ int lld_map_set_covisibles(lld_map* m, int32_t n, const int32_t* slot, const int
   UploadBlock B;
   const auto s = B.take<int32_t>(n), cs = B.take<int32_t>((size_t)n + 1), cv = B.take<int32_t>(cov_start[n]);
   int st = up_begin(m, B); if (st) return st;
+  m->mutations++;
   B.stage(s, slot); B.stage(cs, cov_start); B.stage(cv, cov);
   st = up_submit(m, B); if (st) return st;
   hipLaunchKernelGGL(map_set_cov_kernel, dim3((n + 255) / 256), dim3(256), 0, m->ctx->stream, m->D, n, B.dev(s), B.dev(cs), B.dev(cv));
@@ -777,6 +789,7 @@ int lld_map_set_keyframes(lld_map* m, int32_t n, const int32_t* slot, const uint
              cv = B.take<int32_t>(cov_start[n]);
   m->child.reserve(B, Pc); m->kpt.reserve(B, Pp); m->kln.reserve(B, Pl);
   int st = up_begin(m, B); if (st) return st;
+  m->mutations++;
   B.stage(s, slot); B.stage(key, reinterpret_cast<const u64*>(order_key)); B.stage(b, bad); B.stage(par, parent); B.stage(cs, cov_start); B.stage(cv, cov);
   m->child.commit(B, Pc, n, slot, child_start, child); m->kpt.commit(B, Pp, n, slot, point_start, point); m->kln.commit(B, Pl, n, slot, line_start, line);
   for (int i = 0; i < n; i++) m->kf_set[slot[i]] = 1;
@@ -805,6 +818,7 @@ int lld_map_set_lines(lld_map* m, int32_t n, const int32_t* slot, const double* 
   const auto s = B.take<int32_t>(n); const auto a0 = B.take<double>(n, 3), ad = B.take<double>(n, 3), a1 = B.take<double>(n, 3), a2 = B.take<double>(n, 3);
   const auto d = B.take<float>(n, dim); const auto b = B.take<uint8_t>(n);
   int st = up_begin(m, B); if (st) return st;
+  m->mutations++;
   B.stage(s, slot); B.stage(a0, x0); B.stage(ad, dir); B.stage(a1, x1); B.stage(a2, x2); B.stage(d, desc); B.stage(b, bad);
   st = up_submit(m, B); if (st) return st;
   const long long total = (long long)n * W;
@@ -840,18 +854,22 @@ int lld_map_set_keyframe_features(lld_map* m, int32_t n, const int32_t* slot, co
   if (fresh && (!m->kuvr.plan(n, slot, us.data(), Pu) || !m->kkl.plan(n, slot, ks.data(), Pk))) return LLD_ERR_UNSUPPORTED;      // (cannot happen)
   UploadBlock B;
   m->kuvr.reserve(B, Pu); m->kkl.reserve(B, Pk);
-  const auto s = B.take<int32_t>(n); const auto id = B.take<u64>(n); const auto qt = B.take<double>(n, 7);
+  const auto s = B.take<int32_t>(n); const auto id = B.take<u64>(n); const auto qt = B.take<double>(n, 7); const auto ow = B.take<float>(n, 3);
   st = up_begin(m, B); if (st) return st;
+  m->mutations++;
   m->kuvr.commit(B, Pu, n, slot, us.data(), reinterpret_cast<const int32_t*>(kp_uvr));          // a float travels as its bit pattern
   m->kkl.commit(B, Pk, n, slot, ks.data(), kl.data());
   B.stage(s, slot); B.stage(id, reinterpret_cast<const u64*>(mn_id));
-  for (int i = 0; i < n; i++) { lld_se3_from_tcw_f32(Tcw + 16 * (size_t)i, B.host(qt) + 7 * (size_t)i); m->kf_feat[slot[i]] = 1; }
+  for (int i = 0; i < n; i++) {
+    lld_se3_from_tcw_f32(Tcw + 16 * (size_t)i, B.host(qt) + 7 * (size_t)i); lld::camera_centre(Tcw + 16 * (size_t)i, B.host(ow) + 3 * (size_t)i);
+    m->kf_feat[slot[i]] = 1;
+  }
   st = up_submit(m, B);
   hipStream_t stream = m->ctx->stream;
   if (!st) st = m->kuvr.launch(stream, B, Pu);
   if (!st) st = m->kkl.launch(stream, B, Pk);
   if (!st) {
-    hipLaunchKernelGGL(map_set_kf_pose_kernel, dim3((n + 255) / 256), dim3(256), 0, stream, m->Y, n, B.dev(s), B.dev(id), B.dev(qt));
+    hipLaunchKernelGGL(map_set_kf_pose_kernel, dim3((n + 255) / 256), dim3(256), 0, stream, m->Y, n, B.dev(s), B.dev(id), B.dev(qt), B.dev(ow));
     if (hipGetLastError() != hipSuccess) st = LLD_ERR_HIP;
   }
   if (st) m->poisoned = true;                                        // the host's rows are ahead of the device's
@@ -867,12 +885,13 @@ int lld_map_set_keyframe_poses(lld_map* m, int32_t n, const int32_t* slot, const
   for (int i = 0; i < n; i++) if (!m->d_ba || !m->kf_feat[slot[i]]) return LLD_ERR_INVALID;
   LLD_HIP_TRY(hipSetDevice(m->ctx->device));
   UploadBlock B;
-  const auto s = B.take<int32_t>(n); const auto qt = B.take<double>(n, 7);
+  const auto s = B.take<int32_t>(n); const auto qt = B.take<double>(n, 7); const auto ow = B.take<float>(n, 3);
   int st = up_begin(m, B); if (st) return st;
+  m->mutations++;
   B.stage(s, slot);
-  for (int i = 0; i < n; i++) lld_se3_from_tcw_f32(Tcw + 16 * (size_t)i, B.host(qt) + 7 * (size_t)i);
+  for (int i = 0; i < n; i++) { lld_se3_from_tcw_f32(Tcw + 16 * (size_t)i, B.host(qt) + 7 * (size_t)i); lld::camera_centre(Tcw + 16 * (size_t)i, B.host(ow) + 3 * (size_t)i); }
   st = up_submit(m, B); if (st) return st;
-  hipLaunchKernelGGL(map_set_kf_pose_kernel, dim3((n + 255) / 256), dim3(256), 0, m->ctx->stream, m->Y, n, B.dev(s), (const u64*)nullptr, B.dev(qt));
+  hipLaunchKernelGGL(map_set_kf_pose_kernel, dim3((n + 255) / 256), dim3(256), 0, m->ctx->stream, m->Y, n, B.dev(s), (const u64*)nullptr, B.dev(qt), B.dev(ow));
   LLD_HIP_TRY(hipGetLastError());
   return LLD_OK;
 }
@@ -896,6 +915,7 @@ int lld_map_set_line_observations(lld_map* m, int32_t n, const int32_t* slot, co
   m->lobs.reserve(B, Po); m->lidx.reserve(B, Pi);
   const auto s = B.take<int32_t>(n), no = B.take<int32_t>(n);
   st = up_begin(m, B); if (st) return st;
+  m->mutations++;
   m->lobs.commit(B, Po, n, slot, start, kf_slot); m->lidx.commit(B, Pi, n, slot, start, line_index);
   B.stage(s, slot); B.stage(no, n_obs);
   st = up_submit(m, B);
@@ -908,6 +928,30 @@ int lld_map_set_line_observations(lld_map* m, int32_t n, const int32_t* slot, co
   }
   if (st) m->poisoned = true;                                        // the host's rows are ahead of the device's
   return st;
+}
+
+int lld_map_set_point_refs(lld_map* m, int32_t n, const int32_t* slot, const int32_t* ref_kf) {
+  if (!m || n < 0) return LLD_ERR_INVALID;
+  if (m->poisoned) return LLD_ERR_HIP;
+  if (n == 0) return LLD_OK;
+  if (!slot || !ref_kf) return LLD_ERR_INVALID;
+  if (!slots_ok(m->stamp_pt, m->epoch, n, slot) || !entries_in(ref_kf, n, -1, m->lim.max_keyframes)) return LLD_ERR_INVALID;
+  LLD_HIP_TRY(hipSetDevice(m->ctx->device));
+  if (!m->d_ref) {                                                    // the first call: every slot unknown.  A failure leaves the map as it was.
+    int32_t* d = nullptr;
+    if (hipMalloc(reinterpret_cast<void**>(&d), (size_t)m->lim.max_points * 4) != hipSuccess) return LLD_ERR_ALLOC;
+    if (hipMemsetAsync(d, 0xff, (size_t)m->lim.max_points * 4, m->ctx->stream) != hipSuccess) { (void)hipFree(d); return LLD_ERR_HIP; }
+    m->d_ref = d;
+  }
+  UploadBlock B;
+  const auto s = B.take<int32_t>(n), r = B.take<int32_t>(n);
+  int st = up_begin(m, B); if (st) return st;
+  m->mutations++;
+  B.stage(s, slot); B.stage(r, ref_kf);
+  st = up_submit(m, B); if (st) return st;
+  hipLaunchKernelGGL(map_scatter_kernel, dim3((n + 255) / 256), dim3(256), 0, m->ctx->stream, n, B.dev(s), B.dev(r), m->d_ref);
+  LLD_HIP_TRY(hipGetLastError());
+  return LLD_OK;
 }
 
 int lld_frame_track_update_local_map(lld_frame* f, lld_map* m) {

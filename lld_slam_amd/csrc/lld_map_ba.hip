@@ -378,6 +378,7 @@ int run_window(lld_map* m, const lld_map_ba_in* in, const int32_t* cap, UploadBl
   L.pt_cam = B.take<int32_t>(cpo); L.pt_uvr = B.take<double>(cpo, 3); L.pt_sig = B.take<double>(cpo);
   L.line_slot = B.take<int32_t>(cl); L.ln_x0 = B.take<double>(cl, 3); L.ln_dir = B.take<double>(cl, 3); L.ln_start = B.take<int32_t>(cl + 1);
   L.ln_cam = B.take<int32_t>(clo); L.ln_left = B.take<double>(clo, 4); L.ln_right = B.take<double>(clo, 4); L.ln_oct = B.take<int32_t>(clo, 2);
+  m->win.valid = false;                                                // the staging is about to be overwritten
   int st = grow_staging(m, B.size); if (st) return st;
   B.bind(m->h_ba, m->d_run);
   B.stage(i_slot, in->kf_slot); B.stage(i_sig, in->inv_level_sigma2);
@@ -429,6 +430,15 @@ bool fits(const int32_t* h, const int32_t* cap, bool with_bad = false) {
   return h[H_NCAMS] <= cap[0] && h[H_NPTS] <= cap[1] && h[H_NPTOBS] <= cap[2] && h[H_NLNS] <= cap[3] && h[H_NLNOBS] <= cap[4] && (!with_bad || h[H_NBAD] <= cap[5]);
 }
 
+// A complete window (status 0, every capacity held) stays in the staging: lld_map_ba_apply scatters a result through its index arrays.
+void keep_for_apply(lld_map* m, const Layout& L, const int32_t* h) {
+  lld_map::BaStaged& W = m->win;
+  W.valid = true; W.at = m->mutations;
+  W.n_cams = h[H_NCAMS]; W.n_local = h[H_NLOCAL]; W.n_pts = h[H_NPTS]; W.n_ptobs = h[H_NPTOBS]; W.n_lns = h[H_NLNS]; W.n_lnobs = h[H_NLNOBS];
+  W.cam_slot = L.cam_slot.off; W.point_slot = L.point_slot.off; W.pt_start = L.pt_start.off; W.pt_cam = L.pt_cam.off;
+  W.line_slot = L.line_slot.off; W.ln_start = L.ln_start.off; W.ln_cam = L.ln_cam.off;
+}
+
 template <class T> void copy_out(T* dst, const UploadBlock& B, const Span<T>& s, size_t n) { if (n) std::memcpy(dst, B.host(s), n * sizeof(T)); }
 
 }  // namespace
@@ -465,6 +475,7 @@ int lld_map_ba_window(lld_map* m, const lld_map_ba_in* in, lld_map_ba_window_out
   out->n_cams = h[H_NCAMS]; out->n_free_cams = h[H_NFREE]; out->n_local_cams = h[H_NLOCAL]; out->n_points = h[H_NPTS]; out->n_pt_obs = h[H_NPTOBS];
   out->n_lines = h[H_NLNS]; out->n_ln_obs = h[H_NLNOBS];
   if (!fits(h, cap)) return LLD_ERR_INVALID;                           // only the counts are written
+  keep_for_apply(m, L, h);
   const size_t nc = h[H_NCAMS], np = h[H_NPTS], npo = h[H_NPTOBS], nl = h[H_NLNS], nlo = h[H_NLNOBS];
   copy_out(out->cam_slot, B, L.cam_slot, nc); copy_out(out->cam_qt, B, L.cam_qt, 7 * nc);
   copy_out(out->point_slot, B, L.point_slot, np); copy_out(out->pt_xyz, B, L.pt_xyz, 3 * np); copy_out(out->pt_obs_start, B, L.pt_start, np + 1);
@@ -501,6 +512,7 @@ int lld_map_local_ba(lld_map* m, const lld_map_ba_in* in, const lld_ba_params* p
     const int32_t need[6] = {h[H_NCAMS], h[H_NPTS], h[H_NPTOBS], h[H_NLNS], h[H_NLNOBS], h[H_NBAD]};
     for (int k = 0; k < 6; k++) if (need[k] > m->ba_cap[k]) m->ba_cap[k] = need[k] + need[k] / 4 + 16;
   }
+  keep_for_apply(m, L, h);
   lld_ba_window& w = ids->window;
   w.cam = in->cam;
   w.n_cams = h[H_NCAMS]; w.n_free_cams = h[H_NFREE]; w.cam_qt = B.host(L.cam_qt);

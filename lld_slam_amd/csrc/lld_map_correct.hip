@@ -46,13 +46,7 @@ constexpr int kNoOwner = 0x7f7f7f7f;         // the staged fill of the owner wor
 // A pose is Tcw[12], the rows of [R|t]; the fourth row of the cv::Mat is (0, 0, 0, 1).
 
 // Ow = -Rwc*tcw with Rwc = Rcw.t() (KeyFrame.cc:84-85): one gemm, double accumulation, one rounding
-__device__ __forceinline__ void centre_of(const float* T, float* ow) {
-  const float R[9] = {T[0], T[1], T[2], T[4], T[5], T[6], T[8], T[9], T[10]};
-  const float t[3] = {T[3], T[7], T[11]};
-  lld::rwc_mul(R, t, ow);
-#pragma unroll
-  for (int i = 0; i < 3; ++i) ow[i] = -ow[i];
-}
+__device__ __forceinline__ void centre_of(const float* T, float* ow) { lld::camera_centre(T, ow); }
 // Twc = [Rcw^T | Ow] (KeyFrame.cc:87-89)
 __device__ __forceinline__ void inverse_of(const float* T, float* Twc) {
   float ow[3];

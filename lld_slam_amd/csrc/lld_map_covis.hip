@@ -256,6 +256,7 @@ int lld_map_covisibility(lld_map* m, const lld_map_covisibility_in* in, lld_map_
   A.flags = in->flags; A.ratio = in->params.redundant_ratio;
   A.st_slot = B.dev(t_sl); A.st_cnt = B.dev(t_sc); A.status = B.dev(r_st);
 
+  if (in->flags & LLD_MAP_COVIS_WRITE_COV) m->mutations++;             // cov rows change: a staged BA window is no longer this map's
   if (conn && !m->cov_lds_set) {
     LLD_HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(&map_covis_query_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)kCovLds));
     m->cov_lds_set = true;

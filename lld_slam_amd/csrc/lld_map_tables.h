@@ -1,6 +1,7 @@
 // lld_map_tables.h — the resident map's tables as the files that run on them see them: the device pointers (MapDev, MapExt), the host's
 // bookkeeping of the variable-length rows (RowPool) and the handle that owns both (struct lld_map).  lld_map.hip creates, fills and frees
-// them; lld_map_covis.hip walks them.  lld_map_internal.h stays the narrow face lld_frame_track.hip sees.  Nothing here is exported.
+// them; lld_map_covis.hip and lld_map_ba.hip walk them; lld_map_apply.hip changes rows on the device and makes the RowPools follow.
+// lld_map_internal.h stays the narrow face lld_frame_track.hip sees.  Nothing here is exported.
 #ifndef LLD_MAP_TABLES_H
 #define LLD_MAP_TABLES_H
 
@@ -33,7 +34,8 @@ struct MapExt {
 };
 
 // The bundle-adjustment tables (lld_map_ba.hip).  All null until the first lld_map_set_keyframe_features / _poses / lld_map_set_line_observations.
-//   keyframe slot s  k_id = mnId, k_qt[7] = the pose as SE3Quat, k_feat (1: features were set), k_uvr = (offset, length) in uvr_pool of the
+//   keyframe slot s  k_id = mnId, k_qt[7] = the pose as SE3Quat, k_ow[3] = the camera centre of that pose (KeyFrame::SetPose, float),
+//                    k_feat (1: features were set), k_uvr = (offset, length) in uvr_pool of the
 //                    keypoints' (u, v, uR) float bits, three words per keypoint, k_kl = (offset, length) in kl_pool of the keylines, ten words
 //                    each: left[4], right[4] float bits, octave[2]
 //   line slot s      l_obs / l_idx = (offset, length) in lobs_pool / lidx_pool of mObservations: keyframe slot, keyline index; l_nobs =
@@ -41,7 +43,7 @@ struct MapExt {
 //   per call         k_mark (~0 unmarked, 0 local, 1 + (landmark ordinal << 32 | row position) of the first visit: fixed), k_cam = the
 //                    keyframe's camera index in the window, fixed / fixed_bad = the non-bad / bad keyframes marked fixed, in no order
 struct MapBa {
-  u64* k_id; double* k_qt; uint8_t* k_feat; int2* k_uvr; int2* k_kl; int32_t* uvr_pool; int32_t* kl_pool;
+  u64* k_id; double* k_qt; float* k_ow; uint8_t* k_feat; int2* k_uvr; int2* k_kl; int32_t* uvr_pool; int32_t* kl_pool;
   int2* l_obs; int2* l_idx; int32_t* lobs_pool; int32_t* lidx_pool; int32_t* l_nobs;
   u64* k_mark; int32_t* k_cam; int32_t* fixed; int32_t* fixed_bad;
 };
@@ -124,6 +126,18 @@ struct lld_map {
   char* h_ba = nullptr; size_t h_ba_bytes = 0; char* d_run = nullptr; size_t d_run_bytes = 0;
   std::vector<double> ba_res_f; std::vector<uint8_t> ba_res_b; int32_t ba_cap[6] = {0, 0, 0, 0, 0, 0};
   std::vector<uint8_t> kf_set;              // lld_map_set_keyframes named the slot since the last clear
+  // MapPoint::mpRefKF per point slot (lld_map_set_point_refs), -1 unknown: a pool of its own, allocated by the first call
+  int32_t* d_ref = nullptr;
+  // The window lld_map_ba_window / lld_map_local_ba assembled last, for lld_map_ba_apply: its index arrays are still in h_ba / d_run at these
+  // byte offsets.  valid: the status was 0 and every capacity held; at: `mutations` when it was assembled.  mutations counts every call that
+  // changes a table: lld_map_set_*, lld_map_clear, LLD_MAP_COVIS_WRITE_COV, lld_map_ba_apply.
+  struct BaStaged {
+    bool valid = false; unsigned long long at = 0;
+    int32_t n_cams = 0, n_local = 0, n_pts = 0, n_ptobs = 0, n_lns = 0, n_lnobs = 0;
+    size_t cam_slot = 0, point_slot = 0, pt_start = 0, pt_cam = 0, line_slot = 0, ln_start = 0, ln_cam = 0;
+  } win;
+  unsigned long long mutations = 0;
+  char* h_ap = nullptr; size_t h_ap_bytes = 0; char* d_ap = nullptr; size_t d_ap_bytes = 0;      // lld_map_ba_apply's staging, grow-only
   bool cov_lds_set = false;                 // map_covis_query_kernel was granted its 64 KB of dynamic LDS
   std::vector<uint32_t> stamp_pt, stamp_kf, stamp_ln; uint32_t epoch = 0;
   // the staging of lld_map_set_*: pinned block, device block, the event of the last copy

@@ -47,6 +47,7 @@ class DeviceMap:
         f("map_covisibility").restype = C.c_int
         f("map_download_links").argtypes = [C.c_void_p, C.c_int32] + [c_int32_p] * 5 + [C.c_int32, c_int32_p]; f("map_download_links").restype = C.c_int
         self._bind_ba()
+        self._bind_apply()
         h = C.c_void_p()
         self.handle = None
         self._check(f("map_create")(ctx.handle, C.byref(self.limits), C.byref(h)), "lld_map_create")
@@ -307,6 +308,76 @@ class DeviceMap:
                            cp(res.pt_obs_outlier, npo, np.uint8), cp(res.ln_edge_outlier, 2 * nlo, np.uint8).reshape(-1, 2), cp(res.line_removed, nl, np.uint8),
                            host.stats_dict(res.stats))
         return bo, out
+
+    # ------------------------------------------------------------------ a local BA's result applied to the map (lld_map_apply.hip)
+    def _bind_apply(self):
+        f = self.lib.fn
+        f("map_set_point_refs").argtypes = [C.c_void_p, C.c_int32, c_int32_p, c_int32_p]; f("map_set_point_refs").restype = C.c_int
+        f("map_ba_apply").argtypes = [C.c_void_p, C.POINTER(abi.MapBaApplyIn), C.POINTER(abi.MapBaApplyOut)]; f("map_ba_apply").restype = C.c_int
+        f("map_download_rows").argtypes = [C.c_void_p, C.c_int32, C.c_int32, c_int32_p, c_int32_p, C.c_int32, c_int32_p]; f("map_download_rows").restype = C.c_int
+
+    def set_point_refs(self, slot, ref_kf):
+        """MapPoint::mpRefKF per point slot as a keyframe slot, -1: unknown."""
+        k = [self._p(slot, np.int32, c_int32_p), self._p(ref_kf, np.int32, c_int32_p)]
+        self._check(self.lib.fn("map_set_point_refs")(self.handle, len(k[0][0]), *[p for _, p in k]), "lld_map_set_point_refs")
+
+    APPLY_POINT = (("pt_pos", np.float32, 3), ("pt_normal", np.float32, 3), ("pt_min_distance", np.float32, 1), ("pt_max_distance", np.float32, 1),
+                   ("pt_n_obs", np.int32, 1), ("pt_ref_kf", np.int32, 1), ("pt_row_len", np.int32, 1), ("pt_flags", np.uint8, 1))
+    APPLY_LINE = (("ln_bad", np.uint8, 1), ("ln_n_obs", np.int32, 1), ("ln_row_len", np.int32, 1))
+    APPLY_COUNTS = ("n_local_cams", "n_pt_obs_erased", "n_ln_obs_erased", "n_points_bad", "n_lines_bad", "n_index_skipped")
+
+    def ba_apply(self, result, level_scale, n_local_cams=None, phase_ms=None, counts=None):
+        """lld_map_ba_apply: `result` (a host.BAOutput, or anything with cam_qt, pt_xyz, line_x0, line_dir, pt_obs_outlier, ln_edge_outlier and
+        line_removed) applied to the window this map assembled last.  n_local_cams sizes tcw / ow (default: every camera of the result).
+        counts overrides the five counts sent (for tests of the refusals).  Returns a dict: the six counts, tcw, ow, and the per-point and
+        per-line arrays of lld_map_ba_apply_out."""
+        g = (lambda k: result[k]) if isinstance(result, dict) else (lambda k: getattr(result, k))
+        cam_qt = np.ascontiguousarray(g("cam_qt"), np.float64).reshape(-1, 7); pt_xyz = np.ascontiguousarray(g("pt_xyz"), np.float64).reshape(-1, 3)
+        x0 = np.ascontiguousarray(g("line_x0"), np.float64).reshape(-1, 3); d = np.ascontiguousarray(g("line_dir"), np.float64).reshape(-1, 3)
+        po = np.ascontiguousarray(g("pt_obs_outlier"), np.uint8).reshape(-1); lo = np.ascontiguousarray(g("ln_edge_outlier"), np.uint8).reshape(-1, 2)
+        rm = np.ascontiguousarray(g("line_removed"), np.uint8).reshape(-1); ls = np.ascontiguousarray(level_scale, np.float32)
+        a = abi.MapBaApplyIn()
+        a.n_cams, a.n_points, a.n_pt_obs, a.n_lines, a.n_ln_obs = (len(cam_qt), len(pt_xyz), len(po), len(x0), len(lo)) if counts is None else counts
+        a.n_levels = len(ls)
+        a.cam_qt = cam_qt.ctypes.data_as(c_double_p); a.pt_xyz = pt_xyz.ctypes.data_as(c_double_p); a.line_x0 = x0.ctypes.data_as(c_double_p)
+        a.line_dir = d.ctypes.data_as(c_double_p); a.pt_obs_outlier = po.ctypes.data_as(c_uint8_p); a.ln_edge_outlier = lo.ctypes.data_as(c_uint8_p)
+        a.line_removed = rm.ctypes.data_as(c_uint8_p); a.level_scale = ls.ctypes.data_as(c_float_p)
+        nloc = len(cam_qt) if n_local_cams is None else int(n_local_cams)
+        r = dict(tcw=np.zeros((max(nloc, 1), 16), np.float32), ow=np.zeros((max(nloc, 1), 3), np.float32))
+        for name, dt, w in self.APPLY_POINT:
+            r[name] = np.zeros((max(len(pt_xyz), 1), w) if w > 1 else max(len(pt_xyz), 1), dt)
+        for name, dt, w in self.APPLY_LINE:
+            r[name] = np.zeros(max(len(x0), 1), dt)
+        o = abi.MapBaApplyOut()
+        ptr = {np.float32: c_float_p, np.int32: c_int32_p, np.uint8: c_uint8_p}
+        for name, arr in r.items():
+            setattr(o, name, arr.ctypes.data_as(ptr[arr.dtype.type]))
+        if phase_ms is not None:
+            assert phase_ms.dtype == np.float32 and phase_ms.size >= 3 and phase_ms.flags.c_contiguous
+            o.phase_ms = phase_ms.ctypes.data_as(c_float_p)
+        self._check(self.lib.fn("map_ba_apply")(self.handle, C.byref(a), C.byref(o)), "lld_map_ba_apply")
+        nloc = o.n_local_cams
+        r["tcw"] = r["tcw"][:nloc].reshape(-1, 4, 4); r["ow"] = r["ow"][:nloc]
+        for name, _, _ in self.APPLY_POINT:
+            r[name] = r[name][:len(pt_xyz)]
+        for name, _, _ in self.APPLY_LINE:
+            r[name] = r[name][:len(x0)]
+        r.update({k: getattr(o, k) for k in self.APPLY_COUNTS})
+        return r
+
+    def rows(self, kind, slots):
+        """lld_map_download_rows: the rows of one pool as the device holds them, one list per slot.  kind: a key of abi.MAP_ROWS or its value."""
+        kind = abi.MAP_ROWS[kind] if isinstance(kind, str) else int(kind)
+        s = np.ascontiguousarray(slots, np.int32); n = len(s)
+        start = np.zeros(n + 1, np.int32)
+        p = lambda a: a.ctypes.data_as(c_int32_p)
+        fn = self.lib.fn("map_download_rows")
+        st = fn(self.handle, kind, n, p(s), p(start), 0, None)
+        data = np.zeros(max(int(start[-1]), 1), np.int32)
+        if st == abi.LLD_ERR_INVALID and start[-1] > 0:
+            st = fn(self.handle, kind, n, p(s), p(start), int(start[-1]), p(data))
+        self._check(st, "lld_map_download_rows")
+        return [data[start[i]:start[i + 1]].tolist() for i in range(n)]
 
     def set_lines(self, slot, x0, dir, x1, x2, desc, bad):
         k = [self._p(slot, np.int32, c_int32_p), self._p(x0, np.float64, c_double_p), self._p(dir, np.float64, c_double_p), self._p(x1, np.float64, c_double_p),
