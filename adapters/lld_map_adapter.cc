@@ -69,6 +69,74 @@ void MapOnDevice::UpdatePoints(const std::vector<MapPoint*>& points) {
   check(lld_map_set_points(m_, (int32_t)n, slot.data(), pos.data(), nrm.data(), mind.data(), maxd.data(), desc.data(), bad.data()), "lld_map_set_points");
   if (covis_) check(lld_map_set_observations_indexed(m_, (int32_t)n, slot.data(), start.data(), obs.data(), idx.data(), nobs.data()), "lld_map_set_observations_indexed");
   else check(lld_map_set_observations(m_, (int32_t)n, slot.data(), start.data(), obs.data()), "lld_map_set_observations");
+  if (!refresh_) return;
+  std::vector<int32_t> ref(n);
+  for (size_t i = 0; i < n; i++) ref[i] = slot_of(points[i]->mpRefKF, limits_.max_keyframes);       // -1: none, or one the table cannot hold
+  check(lld_map_set_point_refs(m_, (int32_t)n, slot.data(), ref.data()), "lld_map_set_point_refs");
+}
+
+int MapOnDevice::RefreshMapPoints(const std::vector<MapPoint*>& vpMapPoints, unsigned flags) {
+  if (!refresh_) throw std::runtime_error("MapOnDevice::RefreshMapPoints: EnableRefresh before Upload");
+  std::vector<MapPoint*> pts; std::vector<int32_t> slots;
+  const KeyFrame* scales = nullptr;
+  for (size_t i = 0; i < vpMapPoints.size(); i++) {
+    MapPoint* pMP = vpMapPoints[i];
+    if (!pMP) continue;
+    if (PointOf(slot_of(pMP, limits_.max_points)) != pMP) throw std::runtime_error("MapOnDevice::RefreshMapPoints: a point the map does not hold");
+    pts.push_back(pMP); slots.push_back((int32_t)pMP->mnId);
+    if (!scales && !pMP->isBad() && pMP->mpRefKF) scales = pMP->mpRefKF;
+  }
+  const size_t n = pts.size();
+  if (!n) return 0;
+  std::vector<float> level_scale(1, 1.f);                               // (read only when some point has a reference keyframe)
+  if (scales) level_scale.assign(scales->mvScaleFactors.begin(), scales->mvScaleFactors.begin() + scales->mnScaleLevels);
+  lld_map_refresh_points_in in; std::memset(&in, 0, sizeof in);
+  in.n = (int32_t)n; in.flags = flags; in.n_levels = (int32_t)level_scale.size(); in.slot = slots.data(); in.level_scale = level_scale.data();
+  std::vector<uint32_t> desc(8 * n); std::vector<float> nrm(3 * n), mind(n), maxd(n); std::vector<uint8_t> upd(n);
+  lld_map_refresh_points_out out; std::memset(&out, 0, sizeof out);
+  out.desc = desc.data(); out.normal = nrm.data(); out.min_distance = mind.data(); out.max_distance = maxd.data(); out.updated = upd.data();
+  check(lld_map_refresh_points(m_, &in, &out), "lld_map_refresh_points");
+  int written = 0;
+  for (size_t i = 0; i < n; i++) {
+    if (!(upd[i] & (LLD_LANDMARK_DESCRIPTOR | LLD_LANDMARK_NORMAL_DEPTH))) continue;
+    written++;
+    if (upd[i] & LLD_LANDMARK_DESCRIPTOR) {                             // mDescriptor = vDescriptors[BestIdx].clone() (MapPoint.cc:305)
+      lld_slam::MatU8 d(1, 32);
+      std::memcpy(d.ptr<unsigned char>(), &desc[8 * i], 32);
+      pts[i]->mDescriptor = d;
+    }
+    if (upd[i] & LLD_LANDMARK_NORMAL_DEPTH) {                           // :367-369
+      pts[i]->mfMaxDistance = maxd[i]; pts[i]->mfMinDistance = mind[i];
+      pts[i]->mNormalVector = lld_slam::Mat(3, 1, &nrm[3 * i]);
+    }
+  }
+  return written;
+}
+
+int MapOnDevice::ComputeDistinctiveDescriptors(const std::vector<MapLine*>& vpMapLines) {
+  if (!refresh_) throw std::runtime_error("MapOnDevice::ComputeDistinctiveDescriptors: EnableRefresh before Upload");
+  std::vector<MapLine*> lns; std::vector<int32_t> slots;
+  for (size_t i = 0; i < vpMapLines.size(); i++) {
+    MapLine* pML = vpMapLines[i];
+    if (!pML) continue;
+    if (LineOf(slot_of(pML, limits_.max_lines)) != pML) throw std::runtime_error("MapOnDevice::ComputeDistinctiveDescriptors: a line the map does not hold");
+    lns.push_back(pML); slots.push_back((int32_t)pML->mnId);
+  }
+  const size_t n = lns.size(), dim = limits_.line_dim;
+  if (!n) return 0;
+  lld_map_refresh_lines_in in; std::memset(&in, 0, sizeof in);
+  in.n = (int32_t)n; in.slot = slots.data();
+  std::vector<float> desc(dim * n); std::vector<uint8_t> upd(n);
+  lld_map_refresh_lines_out out; std::memset(&out, 0, sizeof out);
+  out.desc = desc.data(); out.updated = upd.data();
+  check(lld_map_refresh_lines(m_, &in, &out), "lld_map_refresh_lines");
+  int written = 0;
+  for (size_t i = 0; i < n; i++) {
+    if (!(upd[i] & LLD_LANDMARK_DESCRIPTOR)) continue;
+    written++;
+    lns[i]->mDescriptor = lld_slam::Mat(1, (int)dim, &desc[dim * i]);   // mDescriptor = vDescriptors[BestIdx].clone() (MapLine.cc:199)
+  }
+  return written;
 }
 
 void MapOnDevice::UpdateKeyFrames(const std::vector<KeyFrame*>& keyframes) {
@@ -140,6 +208,19 @@ void MapOnDevice::UpdateKeyFrames(const std::vector<KeyFrame*>& keyframes) {
   uvr.push_back(0.f); left.push_back(0.f); right.push_back(0.f); loct.push_back(0);
   check(lld_map_set_keyframe_features(m_, (int32_t)n, slot.data(), id.data(), Tcw.data(), ps.data(), uvr.data(), ls.data(), left.data(), right.data(), loct.data()),
         "lld_map_set_keyframe_features");
+  if (!refresh_) return;
+  // mDescriptors.row(j) per entry of the point row, mDescriptorsLines.row(j) per entry of the line row (zeros where the keyframe has no such row)
+  const size_t dim = limits_.line_dim;
+  std::vector<uint32_t> kd(8 * (size_t)ps[n] + 1, 0u); std::vector<float> kl(dim * (size_t)ls[n] + 1, 0.f);
+  for (size_t i = 0; i < n; i++) {
+    const KeyFrame* pKF = keyframes[i];
+    for (int32_t j = 0; j < ps[i + 1] - ps[i] && j < pKF->mDescriptors.rows; j++) std::memcpy(&kd[8 * (size_t)(ps[i] + j)], pKF->mDescriptors.ptr<unsigned char>(j), 32);
+    if (pKF->mDescriptorsLines.rows > 0 && (size_t)pKF->mDescriptorsLines.cols != dim)
+      throw std::runtime_error("MapOnDevice::UpdateKeyFrames: line descriptors of another length than line_dim");
+    for (int32_t j = 0; j < ls[i + 1] - ls[i] && j < pKF->mDescriptorsLines.rows; j++) std::memcpy(&kl[dim * (size_t)(ls[i] + j)], pKF->mDescriptorsLines.ptr<float>(j), dim * 4);
+  }
+  check(lld_map_set_keyframe_descriptors(m_, (int32_t)n, slot.data(), ps.data(), kd.data()), "lld_map_set_keyframe_descriptors");
+  check(lld_map_set_keyframe_line_descriptors(m_, (int32_t)n, slot.data(), ls.data(), kl.data()), "lld_map_set_keyframe_line_descriptors");
 }
 
 void MapOnDevice::LocalBundleAdjustment(KeyFrame* pKF, bool* pbStopFlag, lld_slam::Map* pMap, double gamma, LbaTrace* trace) {

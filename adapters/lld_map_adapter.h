@@ -67,6 +67,22 @@ class MapOnDevice {
   // all keyframes, as ORBextractor makes it.  The trace's window and output are filled only when a trace is asked for.
   void LocalBundleAdjustment(lld_slam::KeyFrame* pKF, bool* pbStopFlag, lld_slam::Map* pMap, double gamma = 1.0, LbaTrace* trace = nullptr);
 
+  // ---- the per-landmark refresh on the mirrored map (lld_map_refresh_points / _lines): no gather, nothing pushed back
+  // From here on Upload / UpdateKeyFrames also send mDescriptors and mDescriptorsLines (one row per entry of the point and line rows) and
+  // Upload / UpdatePoints the points' mpRefKF.  It implies the covisibility and bundle-adjustment tables: the normal part reads the camera
+  // centres, the octaves and the index rows.  Call it before the first Upload.
+  void EnableRefresh() { covis_ = true; ba_ = true; refresh_ = true; }
+  // MapPoint::ComputeDistinctiveDescriptors / UpdateNormalAndDepth for the listed points (flags: LLD_LANDMARK_DESCRIPTOR, LLD_LANDMARK_NORMAL_DEPTH
+  // or both) as lld_adapter::RefreshMapPoints (lld_landmark_adapter.h) makes them, in ONE device call on the resident tables, then
+  // mDescriptor / mNormalVector / mfMinDistance / mfMaxDistance of exactly the objects the call updated are written.  The map already holds
+  // the result.  The points, their observers and their reference keyframes must be current in the map; NULL entries are skipped, a point
+  // may be listed once.  mvScaleFactors is read from the first listed point's mpRefKF: one table for all keyframes.  Returns the number of
+  // points written, as lld_adapter::RefreshMapPoints does.  A point the device flags (LLD_MAP_REFRESH_*: no mpRefKF, or the map lacks a
+  // row it needs) is left alone, as lld_adapter::RefreshMapPoints leaves a point without mpRefKF alone.
+  int RefreshMapPoints(const std::vector<lld_slam::MapPoint*>& vpMapPoints, unsigned flags);
+  // MapLine::ComputeDistinctiveDescriptors for the listed lines, likewise; returns the number of lines written.
+  int ComputeDistinctiveDescriptors(const std::vector<lld_slam::MapLine*>& vpMapLines);
+
   // slot -> object (NULL: never sent)
   lld_slam::KeyFrame* KeyFrameOf(int slot) const { return slot >= 0 && slot < (int)kf_.size() ? kf_[slot] : nullptr; }
   lld_slam::MapPoint* PointOf(int slot) const { return slot >= 0 && slot < (int)pt_.size() ? pt_[slot] : nullptr; }
@@ -80,7 +96,7 @@ class MapOnDevice {
   std::vector<lld_slam::KeyFrame*> kf_;
   std::vector<lld_slam::MapPoint*> pt_;
   std::vector<lld_slam::MapLine*> ln_;
-  bool covis_ = false, ba_ = false;
+  bool covis_ = false, ba_ = false, refresh_ = false;
   void SetCovisibles(const std::vector<lld_slam::KeyFrame*>& keyframes);
 };
 

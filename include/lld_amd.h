@@ -2908,6 +2908,91 @@ int  lld_map_ba_apply(lld_map* map, const lld_map_ba_apply_in* in, lld_map_ba_ap
 #define LLD_MAP_ROWS_LINE_IDX    5   /* per line slot: the keyline indices                          */
 int  lld_map_download_rows(lld_map* map, int32_t kind, int32_t n, const int32_t* slot, int32_t* start, int32_t capacity, int32_t* data);
 
+/* ------------------------------------------------------------------ landmark refresh on the resident map (lld_map_refresh.hip)
+ * MapPoint::ComputeDistinctiveDescriptors + UpdateNormalAndDepth and MapLine::ComputeDistinctiveDescriptors - the rules of
+ * lld_mappoint_refresh / lld_mapline_distinctive above, bit for bit - for the landmarks a list of slots names, read from and written to the
+ * map's tables.  LocalMapping runs them in ProcessNewKeyFrame, after CreateNewMapPoints and twice in SearchInNeighbors; with the map
+ * resident only the slot list (and the level table) travels up, and nothing has to be sent back into the map afterwards.
+ *
+ * Two row pools beyond the ones above, allocated by the first of these two setters (a map that never calls them allocates what it
+ * allocated before).  The contract is that of the other setters: everything is validated first, a refusal changes nothing, one block and
+ * one copy per call, the mutation count increments, a HIP failure behind the host bookkeeping poisons the map, lld_map_clear empties them.
+ *   lld_map_set_keyframe_descriptors       desc[8 k ..] = mDescriptors.row(k) as eight uint32, for keypoints start[i] .. start[i+1] of keyframe
+ *                                          slot[i].  LLD_ERR_INVALID also for a keyframe lld_map_set_keyframes never set or a row of another
+ *                                          length than its point row.  The live total is bounded by 8 * max_kf_points words:
+ *                                          LLD_ERR_UNSUPPORTED, nothing changed, when the call's rows would take it past that bound, and
+ *                                          when twice that bound (or twice the line pool's) passes an int32 offset.
+ *   lld_map_set_keyframe_line_descriptors  desc[dim k ..] = mDescriptorsLines.row(k), dim = the map's line_dim floats (they travel as bit
+ *                                          patterns); the row length must be the keyframe's line row's; the bound is line_dim * max_kf_lines,
+ *                                          with the same LLD_ERR_UNSUPPORTED past it.
+ *
+ * lld_map_refresh_points / lld_map_refresh_lines: n landmark slots, each at most once.  One small upload (the slots, the level table),
+ * kernels on the context's stream with no host trip between them, one download, one wait; no allocation per call (the staging only grows).
+ * Early return: a point whose state is isBad or never set, or whose observation row is empty, and a line that is bad, never set or without
+ *   an observation row, is left alone: updated = 0, best_obs = best_median = -1.
+ * Descriptor part (points with LLD_LANDMARK_DESCRIPTOR, every line): the stored row is in std::map order; observers whose keyframe is bad or
+ *   never set are skipped; observer j contributes the row of its keyframe's descriptor pool at the index the landmark's index row stores
+ *   for it; selection, median index and first-of-equal-medians are lld_mappoint_refresh's (for lines: lld_mapline_distinctive's float L2,
+ *   rank count and `int median`).  The winner goes to the landmark's descriptor row; best_obs is its position in the stored row.
+ * Normal part (points with LLD_LANDMARK_NORMAL_DEPTH): every stored observer counts, the centres are the keyframe table's, the reference is
+ *   lld_map_set_point_refs', the level is the octave of the reference keyframe's keypoint at the point's stored index there (keypoint 0 when
+ *   the reference is no observer) - the rules lld_map_ba_apply applies to a window's points, with the numerics of lld_mappoint_refresh.
+ * No index is followed before it is held to the row it points into.  A landmark that fails one of these checks is NOT WRITTEN AT ALL (neither
+ * part) and carries the bit in its updated byte; the call still returns LLD_OK:
+ *   LLD_MAP_REFRESH_NO_INDEX       its index row is missing or of another length than its observation row
+ *   LLD_MAP_REFRESH_NO_DESCRIPTOR  descriptor part: an observer that is not bad has no descriptor row reaching the stored index
+ *   LLD_MAP_REFRESH_NO_REFERENCE   normal part: the conditions of LLD_MAP_APPLY_NO_REFERENCE
+ * Refused before anything is queued, nothing changed.  LLD_ERR_INVALID: a NULL argument, slot or updated array; n < 0; a slot out of range or
+ * named twice; flags zero or with unknown bits; with the normal part a NULL level_scale or n_levels outside [1, LLD_ORB_MAX_LEVELS].
+ * LLD_ERR_UNSUPPORTED: a named point whose observation row is longer than LLD_LANDMARK_MAX_OBS, a named line whose row is longer than
+ * LLD_LANDMARK_MAX_LINE_OBS.  LLD_ERR_HIP for a poisoned map.  n = 0 is LLD_OK and touches nothing.
+ * A call that wrote a landmark counts as a mutation of the map: a BA window staged before it is stale, and lld_map_ba_apply refuses it, as
+ * after any setter.  No row length changes.  A HIP failure behind the first launch poisons the map.
+ * Outputs are per query, read from the tables behind the writes (so a landmark that was not written shows what the map holds); every
+ * output array but updated may be NULL. */
+#define LLD_MAP_REFRESH_NO_INDEX       4   /* updated bits, beside LLD_LANDMARK_DESCRIPTOR / LLD_LANDMARK_NORMAL_DEPTH */
+#define LLD_MAP_REFRESH_NO_DESCRIPTOR  8
+#define LLD_MAP_REFRESH_NO_REFERENCE   16
+typedef struct {
+  int32_t n;                        /* point slots named                                */
+  uint32_t flags;                   /* LLD_LANDMARK_DESCRIPTOR | LLD_LANDMARK_NORMAL_DEPTH */
+  int32_t n_levels, reserved;
+  const int32_t* slot;              /* [n]                                              */
+  const float*   level_scale;       /* [n_levels] mvScaleFactors; normal part only      */
+} lld_map_refresh_points_in;
+typedef struct {
+  uint32_t* desc;                   /* [n][8] p_desc behind the call                    */
+  int32_t*  best_obs;               /* [n] position in the stored row, or -1            */
+  int32_t*  best_median;            /* [n] or -1                                        */
+  float*    normal;                 /* [n][3]                                           */
+  float*    min_distance;           /* [n]                                              */
+  float*    max_distance;           /* [n]                                              */
+  uint8_t*  updated;                /* [n] required                                     */
+  float*    phase_ms;               /* NULL, or [3]: HIP-event times of upload, kernels, download */
+} lld_map_refresh_points_out;
+typedef struct {
+  int32_t n, reserved;
+  const int32_t* slot;              /* [n] line slots                                   */
+} lld_map_refresh_lines_in;
+typedef struct {
+  float*   desc;                    /* [n][line_dim] l_desc behind the call             */
+  int32_t* best_obs;                /* [n] or -1                                        */
+  int32_t* best_median;             /* [n] the int of the QUIRK, or -1                  */
+  uint8_t* updated;                 /* [n] required: LLD_LANDMARK_DESCRIPTOR, or LLD_MAP_REFRESH_* bits */
+  float*   phase_ms;
+} lld_map_refresh_lines_out;
+int  lld_map_set_keyframe_descriptors(lld_map* map, int32_t n, const int32_t* slot, const int32_t* start, const uint32_t* desc);
+int  lld_map_set_keyframe_line_descriptors(lld_map* map, int32_t n, const int32_t* slot, const int32_t* start, const float* desc);
+int  lld_map_refresh_points(lld_map* map, const lld_map_refresh_points_in* in, lld_map_refresh_points_out* out);
+int  lld_map_refresh_lines(lld_map* map, const lld_map_refresh_lines_in* in, lld_map_refresh_lines_out* out);
+/* The fixed rows of point / line slots as the DEVICE holds them - the twins of lld_map_download_rows for an audit and for the tests.  One
+ * small upload, one kernel, one download, one wait; any output array may be NULL; a slot may be named more than once.  state: 0 never set,
+ * 1 live, 2 isBad; bad: 1 isBad or never set.  LLD_ERR_INVALID for a NULL map or slot array, n < 0, a slot out of range; LLD_ERR_HIP for a
+ * poisoned map; n = 0 is LLD_OK. */
+int  lld_map_download_points(lld_map* map, int32_t n, const int32_t* slot, float* pos, float* normal, float* min_distance, float* max_distance,
+                             uint32_t* desc, uint8_t* state);
+int  lld_map_download_lines(lld_map* map, int32_t n, const int32_t* slot, float* desc, uint8_t* bad);
+
 #if defined(__GNUC__)
 #pragma GCC visibility pop
 #endif

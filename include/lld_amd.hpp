@@ -628,6 +628,68 @@ class DeviceMap {
     r.data.resize(n ? r.start[n] : 0);
     return r;
   }
+  // ---- landmark refresh on the map's tables (lld_map_refresh_points / _lines): ComputeDistinctiveDescriptors, UpdateNormalAndDepth
+  // mDescriptors per keyframe slot: start [n + 1] in keypoints, desc eight words per keypoint; one row per entry of the keyframe's point row
+  void SetKeyFrameDescriptors(const std::vector<int32_t>& slot, const std::vector<int32_t>& start, const std::vector<uint32_t>& desc) {
+    if (start.size() != slot.size() + 1 || desc.size() != 8 * (size_t)start.back()) check(LLD_ERR_INVALID, "lld_map_set_keyframe_descriptors");
+    check(lld_map_set_keyframe_descriptors(m_, (int32_t)slot.size(), slot.data(), start.data(), desc.data()), "lld_map_set_keyframe_descriptors");
+  }
+  // mDescriptorsLines per keyframe slot: line_dim floats per keyline; one row per entry of the keyframe's line row
+  void SetKeyFrameLineDescriptors(const std::vector<int32_t>& slot, const std::vector<int32_t>& start, const std::vector<float>& desc) {
+    if (start.size() != slot.size() + 1 || desc.size() != (size_t)limits_.line_dim * start.back()) check(LLD_ERR_INVALID, "lld_map_set_keyframe_line_descriptors");
+    check(lld_map_set_keyframe_line_descriptors(m_, (int32_t)slot.size(), slot.data(), start.data(), desc.data()), "lld_map_set_keyframe_line_descriptors");
+  }
+  struct RefreshedPoints {       // per query, what the map holds behind the call; updated: LLD_LANDMARK_* and LLD_MAP_REFRESH_* bits
+    std::vector<uint32_t> desc; std::vector<int32_t> best_obs, best_median; std::vector<float> normal, min_distance, max_distance; std::vector<uint8_t> updated;
+    float phase_ms[3] = {0.f, 0.f, 0.f};
+  };
+  RefreshedPoints RefreshPoints(const std::vector<int32_t>& slot, unsigned flags, const std::vector<float>& level_scale, bool timed = false) {
+    lld_map_refresh_points_in in{};
+    in.n = (int32_t)slot.size(); in.flags = flags; in.n_levels = (int32_t)level_scale.size(); in.slot = slot.data(); in.level_scale = level_scale.empty() ? nullptr : level_scale.data();
+    RefreshedPoints r;
+    const size_t n = slot.size();
+    r.desc.assign(8 * n + 1, 0); r.best_obs.assign(n + 1, -1); r.best_median.assign(n + 1, -1); r.normal.assign(3 * n + 1, 0.f); r.min_distance.assign(n + 1, 0.f);
+    r.max_distance.assign(n + 1, 0.f); r.updated.assign(n + 1, 0);
+    lld_map_refresh_points_out o{};
+    o.desc = r.desc.data(); o.best_obs = r.best_obs.data(); o.best_median = r.best_median.data(); o.normal = r.normal.data(); o.min_distance = r.min_distance.data();
+    o.max_distance = r.max_distance.data(); o.updated = r.updated.data(); o.phase_ms = timed ? r.phase_ms : nullptr;
+    check(lld_map_refresh_points(m_, &in, &o), "lld_map_refresh_points");
+    r.desc.resize(8 * n); r.best_obs.resize(n); r.best_median.resize(n); r.normal.resize(3 * n); r.min_distance.resize(n); r.max_distance.resize(n); r.updated.resize(n);
+    return r;
+  }
+  struct RefreshedLines { std::vector<float> desc; std::vector<int32_t> best_obs, best_median; std::vector<uint8_t> updated; float phase_ms[3] = {0.f, 0.f, 0.f}; };
+  RefreshedLines RefreshLines(const std::vector<int32_t>& slot, bool timed = false) {
+    lld_map_refresh_lines_in in{};
+    in.n = (int32_t)slot.size(); in.slot = slot.data();
+    RefreshedLines r;
+    const size_t n = slot.size(), dim = (size_t)limits_.line_dim;
+    r.desc.assign(dim * n + 1, 0.f); r.best_obs.assign(n + 1, -1); r.best_median.assign(n + 1, -1); r.updated.assign(n + 1, 0);
+    lld_map_refresh_lines_out o{};
+    o.desc = r.desc.data(); o.best_obs = r.best_obs.data(); o.best_median = r.best_median.data(); o.updated = r.updated.data(); o.phase_ms = timed ? r.phase_ms : nullptr;
+    check(lld_map_refresh_lines(m_, &in, &o), "lld_map_refresh_lines");
+    r.desc.resize(dim * n); r.best_obs.resize(n); r.best_median.resize(n); r.updated.resize(n);
+    return r;
+  }
+  // lld_map_download_points / _lines: the fixed rows of the slots as the device holds them
+  struct PointRows { std::vector<float> pos, normal, min_distance, max_distance; std::vector<uint32_t> desc; std::vector<uint8_t> state; };
+  PointRows DownloadPoints(const std::vector<int32_t>& slot) const {
+    const size_t n = slot.size();
+    PointRows r;
+    r.pos.assign(3 * n + 1, 0.f); r.normal.assign(3 * n + 1, 0.f); r.min_distance.assign(n + 1, 0.f); r.max_distance.assign(n + 1, 0.f); r.desc.assign(8 * n + 1, 0); r.state.assign(n + 1, 0);
+    check(lld_map_download_points(m_, (int32_t)n, slot.data(), r.pos.data(), r.normal.data(), r.min_distance.data(), r.max_distance.data(), r.desc.data(), r.state.data()),
+          "lld_map_download_points");
+    r.pos.resize(3 * n); r.normal.resize(3 * n); r.min_distance.resize(n); r.max_distance.resize(n); r.desc.resize(8 * n); r.state.resize(n);
+    return r;
+  }
+  struct LineRows { std::vector<float> desc; std::vector<uint8_t> bad; };
+  LineRows DownloadLines(const std::vector<int32_t>& slot) const {
+    const size_t n = slot.size(), dim = (size_t)limits_.line_dim;
+    LineRows r;
+    r.desc.assign(dim * n + 1, 0.f); r.bad.assign(n + 1, 0);
+    check(lld_map_download_lines(m_, (int32_t)n, slot.data(), r.desc.data(), r.bad.data()), "lld_map_download_lines");
+    r.desc.resize(dim * n); r.bad.resize(n);
+    return r;
+  }
   const lld_map_limits& limits() const { return limits_; }
   lld_map* get() const { return m_; }
  private:

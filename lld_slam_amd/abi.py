@@ -481,6 +481,31 @@ class MapBaApplyOut(C.Structure):
                 ("ln_bad", c_uint8_p), ("ln_n_obs", c_int32_p), ("ln_row_len", c_int32_p), ("phase_ms", c_float_p)]
 
 
+class MapRefreshPointsIn(C.Structure):
+    """lld_map_refresh_points_in."""
+    _fields_ = [("n", C.c_int32), ("flags", C.c_uint32), ("n_levels", C.c_int32), ("reserved", C.c_int32), ("slot", c_int32_p), ("level_scale", c_float_p)]
+
+
+class MapRefreshPointsOut(C.Structure):
+    """lld_map_refresh_points_out."""
+    _fields_ = [("desc", c_uint32_p), ("best_obs", c_int32_p), ("best_median", c_int32_p), ("normal", c_float_p), ("min_distance", c_float_p),
+                ("max_distance", c_float_p), ("updated", c_uint8_p), ("phase_ms", c_float_p)]
+
+
+class MapRefreshLinesIn(C.Structure):
+    """lld_map_refresh_lines_in."""
+    _fields_ = [("n", C.c_int32), ("reserved", C.c_int32), ("slot", c_int32_p)]
+
+
+class MapRefreshLinesOut(C.Structure):
+    """lld_map_refresh_lines_out."""
+    _fields_ = [("desc", c_float_p), ("best_obs", c_int32_p), ("best_median", c_int32_p), ("updated", c_uint8_p), ("phase_ms", c_float_p)]
+
+
+LANDMARK_DESCRIPTOR, LANDMARK_NORMAL_DEPTH = 1, 2
+LANDMARK_MAX_OBS, LANDMARK_MAX_LINE_OBS = 1024, 64
+ORB_MAX_LEVELS = 16
+MAP_REFRESH_NO_INDEX, MAP_REFRESH_NO_DESCRIPTOR, MAP_REFRESH_NO_REFERENCE = 4, 8, 16
 MAP_BA_MAX_LOCAL = 1024
 MAP_BA_NO_FEATURE_DATA = 1
 MAP_APPLY_WENT_BAD, MAP_APPLY_REFRESHED, MAP_APPLY_NO_REFERENCE, MAP_APPLY_INDEX_SKIPPED = 1, 2, 4, 8
@@ -539,6 +564,8 @@ PRODUCT_SYMBOLS = [
     "lld_map_set_observations_indexed", "lld_map_set_keyframe_keypoints", "lld_map_set_covisibles", "lld_map_covisibility", "lld_map_download_links",
     "lld_map_set_keyframe_features", "lld_map_set_keyframe_poses", "lld_map_set_line_observations", "lld_map_ba_window", "lld_map_local_ba",
     "lld_map_set_point_refs", "lld_map_ba_apply", "lld_map_download_rows",
+    "lld_map_set_keyframe_descriptors", "lld_map_set_keyframe_line_descriptors", "lld_map_refresh_points", "lld_map_refresh_lines",
+    "lld_map_download_points", "lld_map_download_lines",
 ]
 
 

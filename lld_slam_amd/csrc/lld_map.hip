@@ -414,15 +414,7 @@ int lld_map_dev::RowPool::launch(hipStream_t st, const UploadBlock& B, const Poo
 
 namespace {
 
-// slots in range and no slot twice in one call
-bool slots_ok(std::vector<uint32_t>& stamp, uint32_t& epoch, int n, const int32_t* slot) {
-  if (++epoch == 0) { std::fill(stamp.begin(), stamp.end(), 0u); epoch = 1; }
-  for (int i = 0; i < n; i++) {
-    if (slot[i] < 0 || (size_t)slot[i] >= stamp.size() || stamp[slot[i]] == epoch) return false;
-    stamp[slot[i]] = epoch;
-  }
-  return true;
-}
+using lld_map_dev::slots_ok;
 
 int up_begin(lld_map* m, UploadBlock& B) {
   B.end_upload();
@@ -471,6 +463,10 @@ int tables_reset(lld_map* m) {
     LLD_HIP_TRY(hipMemsetAsync(m->Y.l_nobs, 0xff, (size_t)std::max(m->lim.max_lines, 1) * 4, st));     // no observation row
     m->kuvr.reset(); m->kkl.reset(); m->lobs.reset(); m->lidx.reset();
     std::fill(m->kf_feat.begin(), m->kf_feat.end(), (uint8_t)0);
+  }
+  if (m->d_desc) {
+    LLD_HIP_TRY(hipMemsetAsync(m->d_desc, 0, m->desc_bytes, st));
+    m->kdesc.reset(); m->kldesc.reset();
   }
   return LLD_OK;
 }
@@ -522,6 +518,57 @@ int ba_ensure(lld_map* m) {
   m->kuvr.d_row = Y.k_uvr; m->kuvr.d_pool = Y.uvr_pool; m->kkl.d_row = Y.k_kl; m->kkl.d_pool = Y.kl_pool;
   m->lobs.d_row = Y.l_obs; m->lobs.d_pool = Y.lobs_pool; m->lidx.d_row = Y.l_idx; m->lidx.d_pool = Y.lidx_pool;
   return LLD_OK;
+}
+
+// The keyframes' descriptor rows and their two pools, on the first call that fills one of them.  A failure leaves the map as it was.
+int desc_ensure(lld_map* m) {
+  if (m->d_desc) return LLD_OK;
+  const int64_t lim_p = 8 * (int64_t)m->lim.max_kf_points, lim_l = (int64_t)m->lim.line_dim * m->lim.max_kf_lines;
+  if (2 * lim_p > INT32_MAX || 2 * lim_l > INT32_MAX) return LLD_ERR_UNSUPPORTED;                    // twice the pools' totals stay int32 offsets
+  const size_t nk = m->lim.max_keyframes;
+  m->kdesc.init((int)nk, lim_p); m->kldesc.init((int)nk, lim_l);
+  UploadBlock B;
+  const auto kd = B.take<int2>(nk), kl = B.take<int2>(nk); const auto dpool = B.take<int32_t>(m->kdesc.mirror.size()), lpool = B.take<int32_t>(m->kldesc.mirror.size());
+  char* d = nullptr;
+  if (hipMalloc(reinterpret_cast<void**>(&d), B.size) != hipSuccess) return LLD_ERR_ALLOC;
+  if (hipMemsetAsync(d, 0, B.size, m->ctx->stream) != hipSuccess) { (void)hipFree(d); return LLD_ERR_HIP; }
+  m->d_desc = d; m->desc_bytes = B.size;
+  B.bind(nullptr, d);
+  lld_map_dev::MapDesc& Z = m->Z;
+  Z.k_desc = B.dev(kd); Z.kdesc_pool = B.dev(dpool); Z.k_ldesc = B.dev(kl); Z.kldesc_pool = B.dev(lpool);
+  m->kdesc.d_row = Z.k_desc; m->kdesc.d_pool = Z.kdesc_pool; m->kldesc.d_row = Z.k_ldesc; m->kldesc.d_pool = Z.kldesc_pool;
+  return LLD_OK;
+}
+
+// lld_map_set_keyframe_descriptors / _line_descriptors: `per` words per feature of the keyframe's row `feat` (its point or line row), into `pool`
+int set_kf_desc_rows(lld_map* m, RowPool lld_map::*pool, const RowPool& feat, int per, int32_t n, const int32_t* slot, const int32_t* start, const int32_t* desc) {
+  if (!m || n < 0) return LLD_ERR_INVALID;
+  if (m->poisoned) return LLD_ERR_HIP;
+  if (n == 0) return LLD_OK;
+  if (!slot || !starts_ok(n, start) || (start[n] > 0 && !desc)) return LLD_ERR_INVALID;
+  if (!slots_ok(m->stamp_kf, m->epoch, n, slot)) return LLD_ERR_INVALID;
+  for (int i = 0; i < n; i++) if (!m->kf_set[slot[i]] || start[i + 1] - start[i] != feat.len[slot[i]]) return LLD_ERR_INVALID;   // one row per feature of a keyframe the map holds
+  const int64_t limit = pool == &lld_map::kdesc ? 8 * (int64_t)m->lim.max_kf_points : (int64_t)m->lim.line_dim * m->lim.max_kf_lines;
+  if (2 * limit > INT32_MAX || (int64_t)per * start[n] > limit) return LLD_ERR_UNSUPPORTED;           // (what desc_ensure refuses, before the scaled starts are formed)
+  std::vector<int32_t> ws((size_t)n + 1);
+  for (int i = 0; i <= n; i++) ws[i] = per * start[i];
+  PoolPlan P;
+  // the limits first, the allocation behind them: a fresh pool is empty, so the call's own words are its live total
+  if (m->d_desc && !(m->*pool).plan(n, slot, ws.data(), P)) return LLD_ERR_UNSUPPORTED;
+  LLD_HIP_TRY(hipSetDevice(m->ctx->device));
+  const bool fresh = !m->d_desc;
+  int st = desc_ensure(m); if (st) return st;
+  RowPool& R = m->*pool;
+  if (fresh && !R.plan(n, slot, ws.data(), P)) return LLD_ERR_UNSUPPORTED;                            // (cannot happen: checked above)
+  UploadBlock B;
+  R.reserve(B, P);
+  st = up_begin(m, B); if (st) return st;
+  m->mutations++;
+  R.commit(B, P, n, slot, ws.data(), desc);
+  st = up_submit(m, B);
+  if (!st) st = R.launch(m->ctx->stream, B, P);
+  if (st) m->poisoned = true;                                          // the host's rows are ahead of the device's
+  return st;
 }
 
 }  // namespace
@@ -613,6 +660,9 @@ void lld_map_destroy(lld_map* m) {
   if (m->d_ref) (void)hipFree(m->d_ref);
   if (m->d_ap) (void)hipFree(m->d_ap);
   if (m->h_ap) (void)hipHostFree(m->h_ap);
+  if (m->d_desc) (void)hipFree(m->d_desc);
+  if (m->d_rf) (void)hipFree(m->d_rf);
+  if (m->h_rf) (void)hipHostFree(m->h_rf);
   if (m->h_ba) (void)hipHostFree(m->h_ba);
   if (m->d_up) (void)hipFree(m->d_up);
   if (m->h_up) (void)hipHostFree(m->h_up);
@@ -952,6 +1002,16 @@ int lld_map_set_point_refs(lld_map* m, int32_t n, const int32_t* slot, const int
   hipLaunchKernelGGL(map_scatter_kernel, dim3((n + 255) / 256), dim3(256), 0, m->ctx->stream, n, B.dev(s), B.dev(r), m->d_ref);
   LLD_HIP_TRY(hipGetLastError());
   return LLD_OK;
+}
+
+int lld_map_set_keyframe_descriptors(lld_map* m, int32_t n, const int32_t* slot, const int32_t* start, const uint32_t* desc) {
+  if (!m) return LLD_ERR_INVALID;
+  return set_kf_desc_rows(m, &lld_map::kdesc, m->kpt, 8, n, slot, start, reinterpret_cast<const int32_t*>(desc));
+}
+
+int lld_map_set_keyframe_line_descriptors(lld_map* m, int32_t n, const int32_t* slot, const int32_t* start, const float* desc) {
+  if (!m) return LLD_ERR_INVALID;
+  return set_kf_desc_rows(m, &lld_map::kldesc, m->kln, m->lim.line_dim, n, slot, start, reinterpret_cast<const int32_t*>(desc));    // a float travels as its bit pattern
 }
 
 int lld_frame_track_update_local_map(lld_frame* f, lld_map* m) {

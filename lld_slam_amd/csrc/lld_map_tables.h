@@ -1,6 +1,7 @@
 // lld_map_tables.h — the resident map's tables as the files that run on them see them: the device pointers (MapDev, MapExt), the host's
 // bookkeeping of the variable-length rows (RowPool) and the handle that owns both (struct lld_map).  lld_map.hip creates, fills and frees
-// them; lld_map_covis.hip and lld_map_ba.hip walk them; lld_map_apply.hip changes rows on the device and makes the RowPools follow.
+// them; lld_map_covis.hip and lld_map_ba.hip walk them; lld_map_apply.hip changes rows on the device and makes the RowPools follow;
+// lld_map_refresh.hip rewrites the landmarks' descriptor, normal and distance rows from them.
 // lld_map_internal.h stays the narrow face lld_frame_track.hip sees.  Nothing here is exported.
 #ifndef LLD_MAP_TABLES_H
 #define LLD_MAP_TABLES_H
@@ -47,6 +48,12 @@ struct MapBa {
   int2* l_obs; int2* l_idx; int32_t* lobs_pool; int32_t* lidx_pool; int32_t* l_nobs;
   u64* k_mark; int32_t* k_cam; int32_t* fixed; int32_t* fixed_bad;
 };
+
+// The keyframes' descriptor rows (lld_map_refresh.hip reads them).  All null until the first lld_map_set_keyframe_descriptors /
+// lld_map_set_keyframe_line_descriptors.
+//   keyframe slot s  k_desc = (offset, length) in kdesc_pool of mDescriptors, eight words per keypoint; k_ldesc = (offset, length) in
+//                    kldesc_pool of mDescriptorsLines, `dim` float bit patterns per keyline
+struct MapDesc { int2* k_desc; int32_t* kdesc_pool; int2* k_ldesc; int32_t* kldesc_pool; };
 
 // ------------------------------------------------------------------------------------------------ host: the pools
 struct PoolPlan { bool repack = false; int n_up = 0; size_t n_data = 0; int64_t live_after = 0; Span<int32_t> slot, src, data; Span<int2> row; };
@@ -108,6 +115,16 @@ struct RowPool {
   int launch(hipStream_t st, const UploadBlock& B, const PoolPlan& P) const;      // defined in lld_map.hip: it names map_rows_kernel
 };
 
+// slots in range and no slot twice in one call (stamp / epoch: lld_map::stamp_* and lld_map::epoch)
+inline bool slots_ok(std::vector<uint32_t>& stamp, uint32_t& epoch, int n, const int32_t* slot) {
+  if (++epoch == 0) { std::fill(stamp.begin(), stamp.end(), 0u); epoch = 1; }
+  for (int i = 0; i < n; i++) {
+    if (slot[i] < 0 || (size_t)slot[i] >= stamp.size() || stamp[slot[i]] == epoch) return false;
+    stamp[slot[i]] = epoch;
+  }
+  return true;
+}
+
 }  // namespace lld_map_dev
 
 struct lld_map {
@@ -138,6 +155,9 @@ struct lld_map {
   } win;
   unsigned long long mutations = 0;
   char* h_ap = nullptr; size_t h_ap_bytes = 0; char* d_ap = nullptr; size_t d_ap_bytes = 0;      // lld_map_ba_apply's staging, grow-only
+  // the keyframes' descriptor rows (MapDesc): allocated by the first setter that fills them; lld_map_refresh_*'s staging, grow-only
+  lld_map_dev::MapDesc Z{}; char* d_desc = nullptr; size_t desc_bytes = 0; lld_map_dev::RowPool kdesc, kldesc;
+  char* h_rf = nullptr; size_t h_rf_bytes = 0; char* d_rf = nullptr; size_t d_rf_bytes = 0;
   bool cov_lds_set = false;                 // map_covis_query_kernel was granted its 64 KB of dynamic LDS
   std::vector<uint32_t> stamp_pt, stamp_kf, stamp_ln; uint32_t epoch = 0;
   // the staging of lld_map_set_*: pinned block, device block, the event of the last copy

@@ -48,6 +48,7 @@ class DeviceMap:
         f("map_download_links").argtypes = [C.c_void_p, C.c_int32] + [c_int32_p] * 5 + [C.c_int32, c_int32_p]; f("map_download_links").restype = C.c_int
         self._bind_ba()
         self._bind_apply()
+        self._bind_refresh()
         h = C.c_void_p()
         self.handle = None
         self._check(f("map_create")(ctx.handle, C.byref(self.limits), C.byref(h)), "lld_map_create")
@@ -378,6 +379,95 @@ class DeviceMap:
             st = fn(self.handle, kind, n, p(s), p(start), int(start[-1]), p(data))
         self._check(st, "lld_map_download_rows")
         return [data[start[i]:start[i + 1]].tolist() for i in range(n)]
+
+    # ------------------------------------------------------------------ landmark refresh on the map's tables (lld_map_refresh.hip)
+    def _bind_refresh(self):
+        f = self.lib.fn
+        f("map_set_keyframe_descriptors").argtypes = [C.c_void_p, C.c_int32, c_int32_p, c_int32_p, c_uint32_p]; f("map_set_keyframe_descriptors").restype = C.c_int
+        f("map_set_keyframe_line_descriptors").argtypes = [C.c_void_p, C.c_int32, c_int32_p, c_int32_p, c_float_p]
+        f("map_set_keyframe_line_descriptors").restype = C.c_int
+        f("map_refresh_points").argtypes = [C.c_void_p, C.POINTER(abi.MapRefreshPointsIn), C.POINTER(abi.MapRefreshPointsOut)]; f("map_refresh_points").restype = C.c_int
+        f("map_refresh_lines").argtypes = [C.c_void_p, C.POINTER(abi.MapRefreshLinesIn), C.POINTER(abi.MapRefreshLinesOut)]; f("map_refresh_lines").restype = C.c_int
+        f("map_download_points").argtypes = [C.c_void_p, C.c_int32, c_int32_p, c_float_p, c_float_p, c_float_p, c_float_p, c_uint32_p, c_uint8_p]
+        f("map_download_points").restype = C.c_int
+        f("map_download_lines").argtypes = [C.c_void_p, C.c_int32, c_int32_p, c_float_p, c_uint8_p]; f("map_download_lines").restype = C.c_int
+
+    def _set_kf_desc(self, name, slot, desc, dtype, ptr, width):
+        rows = [np.ascontiguousarray(d, dtype).reshape(-1, width) for d in desc]
+        start = np.concatenate([[0], np.cumsum([len(r) for r in rows])]).astype(np.int32)
+        flat = np.concatenate(rows) if rows else np.zeros((0, width), dtype)
+        k = [self._p(slot, np.int32, c_int32_p), self._p(start, np.int32, c_int32_p), self._p(flat, dtype, ptr)]
+        self._check(self.lib.fn(name)(self.handle, len(k[0][0]), *[p for _, p in k]), "lld_" + name)
+
+    def set_keyframe_descriptors(self, slot, desc):
+        """desc: per keyframe mDescriptors as an (n_keypoints, 8) uint32 array, one row per entry of its point row."""
+        self._set_kf_desc("map_set_keyframe_descriptors", slot, desc, np.uint32, c_uint32_p, 8)
+
+    def set_keyframe_line_descriptors(self, slot, desc):
+        """desc: per keyframe mDescriptorsLines as an (n_keylines, line_dim) float32 array, one row per entry of its line row."""
+        self._set_kf_desc("map_set_keyframe_line_descriptors", slot, desc, np.float32, c_float_p, self.limits.line_dim)
+
+    REFRESH_POINT = (("desc", np.uint32, 8), ("best_obs", np.int32, 1), ("best_median", np.int32, 1), ("normal", np.float32, 3), ("min_distance", np.float32, 1),
+                     ("max_distance", np.float32, 1), ("updated", np.uint8, 1))
+    REFRESH_LINE = (("desc", np.float32, 0), ("best_obs", np.int32, 1), ("best_median", np.int32, 1), ("updated", np.uint8, 1))
+    _PTR = {np.float32: c_float_p, np.int32: c_int32_p, np.uint8: c_uint8_p, np.uint32: c_uint32_p}
+
+    def refresh_points(self, slots, flags=abi.LANDMARK_DESCRIPTOR | abi.LANDMARK_NORMAL_DEPTH, level_scale=None, phase_ms=None, omit=()):
+        """lld_map_refresh_points for the point slots `slots`.  Returns a dict of per-query arrays: desc, best_obs, best_median, normal,
+        min_distance, max_distance (what the map holds behind the call) and updated.  omit: names of output arrays passed as NULL."""
+        s = np.ascontiguousarray(slots, np.int32); n = len(s)
+        a = abi.MapRefreshPointsIn()
+        a.n, a.flags = n, int(flags)
+        a.slot = s.ctypes.data_as(c_int32_p)
+        ls = None
+        if level_scale is not None:
+            ls = np.ascontiguousarray(level_scale, np.float32)
+            a.n_levels = len(ls); a.level_scale = ls.ctypes.data_as(c_float_p)
+        r, o = {}, abi.MapRefreshPointsOut()
+        for name, dt, w in self.REFRESH_POINT:
+            if name in omit:
+                continue
+            r[name] = np.zeros((max(n, 1), w) if w > 1 else max(n, 1), dt)
+            setattr(o, name, r[name].ctypes.data_as(self._PTR[dt]))
+        if phase_ms is not None:
+            assert phase_ms.dtype == np.float32 and phase_ms.size >= 3 and phase_ms.flags.c_contiguous
+            o.phase_ms = phase_ms.ctypes.data_as(c_float_p)
+        self._check(self.lib.fn("map_refresh_points")(self.handle, C.byref(a), C.byref(o)), "lld_map_refresh_points")
+        return {k: v[:n] for k, v in r.items()}
+
+    def refresh_lines(self, slots, phase_ms=None, omit=()):
+        """lld_map_refresh_lines for the line slots `slots`: desc (n x line_dim), best_obs, best_median, updated."""
+        s = np.ascontiguousarray(slots, np.int32); n = len(s)
+        a = abi.MapRefreshLinesIn()
+        a.n = n; a.slot = s.ctypes.data_as(c_int32_p)
+        r, o = {}, abi.MapRefreshLinesOut()
+        for name, dt, w in self.REFRESH_LINE:
+            if name in omit:
+                continue
+            r[name] = np.zeros((max(n, 1), self.limits.line_dim) if w == 0 else max(n, 1), dt)
+            setattr(o, name, r[name].ctypes.data_as(self._PTR[dt]))
+        if phase_ms is not None:
+            assert phase_ms.dtype == np.float32 and phase_ms.size >= 3 and phase_ms.flags.c_contiguous
+            o.phase_ms = phase_ms.ctypes.data_as(c_float_p)
+        self._check(self.lib.fn("map_refresh_lines")(self.handle, C.byref(a), C.byref(o)), "lld_map_refresh_lines")
+        return {k: v[:n] for k, v in r.items()}
+
+    def download_points(self, slots):
+        """lld_map_download_points: pos, normal, min_distance, max_distance, desc and state of the point slots as the device holds them."""
+        s = np.ascontiguousarray(slots, np.int32); n = len(s)
+        r = dict(pos=np.zeros((max(n, 1), 3), np.float32), normal=np.zeros((max(n, 1), 3), np.float32), min_distance=np.zeros(max(n, 1), np.float32),
+                 max_distance=np.zeros(max(n, 1), np.float32), desc=np.zeros((max(n, 1), 8), np.uint32), state=np.zeros(max(n, 1), np.uint8))
+        self._check(self.lib.fn("map_download_points")(self.handle, n, s.ctypes.data_as(c_int32_p), *[v.ctypes.data_as(self._PTR[v.dtype.type]) for v in r.values()]),
+                    "lld_map_download_points")
+        return {k: v[:n] for k, v in r.items()}
+
+    def download_lines(self, slots):
+        """lld_map_download_lines: desc (n x line_dim) and bad of the line slots as the device holds them."""
+        s = np.ascontiguousarray(slots, np.int32); n = len(s)
+        r = dict(desc=np.zeros((max(n, 1), self.limits.line_dim), np.float32), bad=np.zeros(max(n, 1), np.uint8))
+        self._check(self.lib.fn("map_download_lines")(self.handle, n, s.ctypes.data_as(c_int32_p), r["desc"].ctypes.data_as(c_float_p), r["bad"].ctypes.data_as(c_uint8_p)),
+                    "lld_map_download_lines")
+        return {k: v[:n] for k, v in r.items()}
 
     def set_lines(self, slot, x0, dir, x1, x2, desc, bad):
         k = [self._p(slot, np.int32, c_int32_p), self._p(x0, np.float64, c_double_p), self._p(dir, np.float64, c_double_p), self._p(x1, np.float64, c_double_p),
