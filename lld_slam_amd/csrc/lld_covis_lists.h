@@ -1,8 +1,9 @@
 // lld_covis_lists.h — what the two covisibility calls share from "the connected keyframes of query q with their weights are known" onward
 // (lld_covisibility on flat tables, lld_covisibility.hip; lld_map_covisibility on the resident map, lld_map_covis.hip): the staged and packed
 // lists as one device argument block (Lists), the culling tally's gate and verdict, the pack kernel behind pack_launch, and on the host the
-// validation of a lld_covisibility_out, the layout of outputs and scratch on an UploadBlock, the timed upload / launches / download and the
-// copy-back.  Everything that is not inline here is defined once, in lld_covisibility.hip.  Nothing here is exported.
+// validation of a lld_covisibility_out, the layout of outputs and scratch on an UploadBlock, the timed upload / launches / download
+// (lld_round_trip.h's, with the pack kernel behind the query kernel) and the copy-back.  Everything that is not inline here is defined
+// once, in lld_covisibility.hip.  Nothing here is exported.
 //
 // A query kernel owes the pack kernel, per query q with off = stage_off[q]: cnt_conn[q] connected keyframes in list order in st_kf / st_w
 // [off, off + cnt_conn), and cnt_ord[q] keys weight << 32 | rank in st_key [off, ...) in the order they go out, rank being the position in
@@ -11,6 +12,7 @@
 #define LLD_COVIS_LISTS_H
 
 #include "lld_common.h"
+#include "lld_round_trip.h"
 #include "lld_upload_block.h"
 
 namespace lld_covis {
@@ -61,31 +63,15 @@ struct Plan {
   int copy_back(const UploadBlock& B, lld_covisibility_out* out) const;
 };
 
-struct Events {                              // destroyed on every way out
-  hipEvent_t e[4] = {nullptr, nullptr, nullptr, nullptr};
-  ~Events() { for (int k = 0; k < 4; ++k) if (e[k]) (void)hipEventDestroy(e[k]); }
-};
-
-// One upload, launch_query(stream), the pack kernel (conn), one download, then the stream is waited for.  phase_ms, when given, receives the
-// HIP-event times of upload, kernels and download.
+// One upload, launch_query(stream), the pack kernel (conn), one download, then the stream is waited for (lld_round_trip.h).  phase_ms, when
+// given, receives the HIP-event times of upload, kernels and download.
 template <class LaunchQuery>
 int run(hipStream_t sm, const UploadBlock& B, const Plan& P, const Lists& L, float* phase_ms, LaunchQuery launch_query) {
-  Events events;
-  hipEvent_t* ev = events.e;
-  const bool timed = phase_ms != nullptr;
-  if (timed) for (int k = 0; k < 4; ++k) LLD_HIP_TRY(hipEventCreate(&ev[k]));
-  if (timed) LLD_HIP_TRY(hipEventRecord(ev[0], sm));
-  LLD_HIP_TRY(hipMemcpyAsync(B.d, B.h, B.up_bytes, hipMemcpyHostToDevice, sm));
-  if (timed) LLD_HIP_TRY(hipEventRecord(ev[1], sm));
-  launch_query(sm);
-  if (P.conn) pack_launch(sm, L);
-  LLD_HIP_TRY(hipGetLastError());
-  if (timed) LLD_HIP_TRY(hipEventRecord(ev[2], sm));
-  LLD_HIP_TRY(hipMemcpyAsync(B.h + P.out_off, B.d + P.out_off, P.out_bytes, hipMemcpyDeviceToHost, sm));
-  if (timed) LLD_HIP_TRY(hipEventRecord(ev[3], sm));
-  LLD_HIP_TRY(hipStreamSynchronize(sm));
-  if (timed) for (int k = 0; k < 3; ++k) LLD_HIP_TRY(hipEventElapsedTime(&phase_ms[k], ev[k], ev[k + 1]));
-  return LLD_OK;
+  return lld_rt::round_trip(sm, B, P.out_off, P.out_bytes, phase_ms, [&](hipStream_t s) {
+    launch_query(s);
+    if (P.conn) pack_launch(s, L);
+    return LLD_OK;
+  });
 }
 
 }  // namespace lld_covis

@@ -4,6 +4,9 @@
 // and the deviations are written out in include/lld_amd.h; tests/landmark_ref.py restates them independently in numpy.
 //
 // The whole file is compiled without FMA contraction: every float operation is the one IEEE operation the restatement performs.
+// The selection of the distinctive descriptor (distances, sorted[idx], the first strictly smallest median) is lld_distinctive.h's, shared
+// with lld_map_refresh.hip; the kernels here keep the compaction of the kept observations, the early return and where the winner goes.
+// The host side declares its arrays on an UploadBlock (lld_upload_block.h) and travels through lld_round_trip.h.
 //
 // Kernels (one call = one upload, the kernels its flags select, one download; no atomics, no scratch):
 //   lm_point_wave   one wavefront (a workgroup of 64) per MapPoint with at most 64 kept observations.  The kept observations are
@@ -25,13 +28,16 @@
 #include <vector>
 
 #include "lld_common.h"
+#include "lld_distinctive.h"
 #include "lld_normal_depth.h"
+#include "lld_round_trip.h"
 #include "lld_wave.h"
 
 namespace {
 
 constexpr int kWave = 64;
 constexpr int kBlock = 256;
+static_assert(kWave == lld_dd::kWave && kBlock == lld_dd::kBlock, "lld_distinctive.h is written for these");
 
 struct PointArgs {
   const int32_t* obs_start; const int32_t* obs_kf; const uint32_t* obs_desc; const uint8_t* kf_bad; const uint8_t* bad;
@@ -50,8 +56,9 @@ struct LineArgs {
   float* desc; int32_t* best_obs; int32_t* best_median; uint8_t* upd;
 };
 
-__device__ __forceinline__ uint32_t bcast(uint32_t v, int l) { return (uint32_t)__builtin_amdgcn_readlane((int)v, l); }
-__device__ __forceinline__ float bcastf(float v, int l) { return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), l)); }
+using lld_rt::round_trip;
+using lld_track::UploadBlock;
+using lld_wave::bcastf;
 
 // The observations of [s, e) whose keyframe is not bad, in list order: kept[r] = position in the landmark's own list.  Called by
 // one whole wavefront; returns the count (the same in every lane).  Positions past `cap` are counted but not stored.
@@ -91,20 +98,7 @@ __global__ __launch_bounds__(kWave) void lm_point_wave(PointArgs A) {
     const uint4* src = reinterpret_cast<const uint4*>(A.obs_desc + (size_t)(s + kept[lane]) * 8);
     d0 = src[0]; d1 = src[1];
   }
-  for (int j = 0; j < N; ++j) {
-    const uint4 b0 = make_uint4(bcast(d0.x, j), bcast(d0.y, j), bcast(d0.z, j), bcast(d0.w, j));
-    const uint4 b1 = make_uint4(bcast(d1.x, j), bcast(d1.y, j), bcast(d1.z, j), bcast(d1.w, j));
-    dist[j * kWave + lane] = (uint16_t)lld_wave::hamming256(d0, d1, b0, b1);
-  }
-  const int idx = (int)(0.5 * (N - 1));      // vDists[0.5*(N-1)] (:294)
-  int lo = 0, hi = 256;                      // sorted[idx] = the smallest v with count(d <= v) >= idx + 1
-  while (lo < hi) {
-    const int mid = (lo + hi) >> 1;
-    int cnt = 0;
-    for (int j = 0; j < N; ++j) cnt += dist[j * kWave + lane] <= mid ? 1 : 0;
-    if (cnt > idx) hi = mid; else lo = mid + 1;
-  }
-  const int key = lld_wave::min(lane < N ? ((lo << 16) | lane) : 0x7fffffff);   // median < BestMedian in row order (:296-300)
+  const int key = lld_dd::point_wave(d0, d1, N, lane, dist);
   const int w = kept[key & 0xffff];
   if (lane < 8) A.desc[(size_t)p * 8 + lane] = A.obs_desc[(size_t)(s + w) * 8 + lane];
   if (lane == 0) { A.best_obs[p] = w; A.best_median[p] = key >> 16; A.upd[p] = 1; }
@@ -133,25 +127,7 @@ __global__ __launch_bounds__(kBlock) void lm_point_block(PointArgs A) {
   for (int q = tid; q < 2 * N; q += kBlock)
     rows[q] = reinterpret_cast<const uint4*>(A.obs_desc + (size_t)(s + kept[q >> 1]) * 8)[q & 1];
   __syncthreads();
-  const int idx = (int)(0.5 * (N - 1));
-  int key = 0x7fffffff;
-  for (int i = tid; i < N; i += kBlock) {    // ascending i per lane: the packed key keeps the first of equal medians
-    const uint4 a0 = rows[2 * i], a1 = rows[2 * i + 1];
-    int lo = 0, hi = 256;
-    while (lo < hi) {
-      const int mid = (lo + hi) >> 1;
-      int cnt = 0;
-      for (int j = 0; j < N; ++j) cnt += lld_wave::hamming256(a0, a1, rows[2 * j], rows[2 * j + 1]) <= mid ? 1 : 0;
-      if (cnt > idx) hi = mid; else lo = mid + 1;
-    }
-    const int k = (lo << 16) | i;
-    key = k < key ? k : key;
-  }
-  key = lld_wave::min(key);
-  if ((tid & (kWave - 1)) == 0) red[tid / kWave] = key;
-  __syncthreads();
-#pragma unroll
-  for (int q = 0; q < kBlock / kWave; ++q) key = red[q] < key ? red[q] : key;
+  const int key = lld_dd::point_block(rows, N, tid, red);
   const int w = kept[key & 0xffff];
   if (tid < 8) A.desc[(size_t)p * 8 + tid] = A.obs_desc[(size_t)(s + w) * 8 + tid];
   if (tid == 0) { A.best_obs[p] = w; A.best_median[p] = key >> 16; A.upd[p] = 1; }
@@ -208,33 +184,11 @@ __global__ __launch_bounds__(kWave) void lm_line_wave(LineArgs A) {
     for (int k = lane; k < dim; k += kWave) rows[r * stride + k] = src[k];
   }
   __syncthreads();
-  const float* mine = rows + (lane < N ? lane : 0) * stride;
-  for (int j = 0; j < N; ++j) {
-    const float* other = rows + j * stride;
-    double acc = 0.0;
-    for (int k = 0; k < dim; ++k) { const float df = mine[k] - other[k]; acc = fma((double)df, (double)df, acc); }   // the product is exact in double
-    dist[j * kWave + lane] = (float)__dsqrt_rn(acc);
-  }
-  const int idx = (int)(0.5 * (N - 1));
-  float med = 0.f;                           // sorted[idx]: the value with rank_below <= idx < rank_below_or_equal
-  for (int j = 0; j < N; ++j) {
-    const float v = dist[j * kWave + lane];
-    int lt = 0, le = 0;
-    for (int k = 0; k < N; ++k) { const float u = dist[k * kWave + lane]; lt += u < v ? 1 : 0; le += u <= v ? 1 : 0; }
-    if (lt <= idx && idx < le) med = v;
-  }
-  int m = lane < N ? (int)med : 0x7fffffff;   // int median = vDists[...]: the float is truncated before the `<` test (:188)
-  int bi = lane;
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) {
-    const int om = __shfl_xor(m, off), oi = __shfl_xor(bi, off);
-    if (om < m || (om == m && oi < bi)) { m = om; bi = oi; }
-  }
+  const int2 best = lld_dd::line(rows, dist, N, dim, stride, lane);
+  const int m = best.x, bi = best.y;
   for (int k = lane; k < dim; k += kWave) A.desc[(size_t)p * dim + k] = rows[bi * stride + k];
   if (lane == 0) { A.best_obs[p] = kept[bi]; A.best_median[p] = m; A.upd[p] = 1; }
 }
-
-inline size_t al(size_t b) { return (b + 255) & ~size_t(255); }
 
 // CSR checks shared by both entry points: INVALID for a malformed list, UNSUPPORTED above `max_obs` per landmark.
 int check_csr(int32_t n, int32_t n_obs, int32_t n_kf, const int32_t* obs_start, const int32_t* obs_kf, int max_obs) {
@@ -272,11 +226,27 @@ int lld_mappoint_refresh(lld_ctx* ctx, const lld_mappoint_refresh_in* in, lld_ma
   if (st) return st;
   LLD_HIP_TRY(hipSetDevice(ctx->device));
 
+  const size_t nn = (size_t)n, no = (size_t)n_obs, nk = (size_t)n_kf, nd = want_desc ? 1 : 0, nv = want_norm ? 1 : 0;   // an array of a part not asked for is empty
+  UploadBlock B;
+  const auto u_start = B.take<int32_t>(nn + 1), u_kf = B.take<int32_t>(no); const auto u_bad = B.take<uint8_t>(nn);
+  const auto u_desc = B.take<uint32_t>(nd * no, 8); const auto u_kfbad = B.take<uint8_t>(nd * nk); const auto u_list = B.take<int32_t>(nd * nn);
+  const auto u_ow = B.take<float>(nv * nk, 3), u_pos = B.take<float>(nv * nn, 3); const auto u_rkf = B.take<int32_t>(nv * nn), u_rlv = B.take<int32_t>(nv * nn);
+  const auto u_scale = B.take<float>(want_norm ? (size_t)in->n_levels : 0);
+  B.end_upload();
+  const auto r_desc = B.take<uint32_t>(nd * nn, 8); const auto r_bo = B.take<int32_t>(nd * nn), r_bm = B.take<int32_t>(nd * nn); const auto r_ud = B.take<uint8_t>(nd * nn);
+  const auto r_nrm = B.take<float>(nv * nn, 3), r_min = B.take<float>(nv * nn), r_max = B.take<float>(nv * nn); const auto r_un = B.take<uint8_t>(nv * nn);
+  B.end_download();
+  void* hb; st = lld_ctx_pinned(ctx, B.size, &hb); if (st) return st;
+  void* db; st = lld_ctx_scratch(ctx, B.size + 256, &db); if (st) return st;
+  B.bind((char*)hb, (char*)db);
+  B.stage(u_start, in->obs_start); B.stage(u_kf, in->obs_kf); B.stage(u_bad, in->bad);
+  B.stage(u_desc, in->obs_desc); B.stage(u_kfbad, in->kf_bad);
+  B.stage(u_ow, in->kf_ow); B.stage(u_pos, in->pos); B.stage(u_rkf, in->ref_kf); B.stage(u_rlv, in->ref_level); B.stage(u_scale, in->level_scale);
+
   // the two launch lists of the descriptor part, by kept observations
-  std::vector<int32_t> list;
   int n_wave = 0;
   if (want_desc) {
-    list.resize((size_t)n);
+    int32_t* list = B.host(u_list);
     std::vector<int32_t> big;
     for (int i = 0; i < n; ++i) {
       int kept = 0;
@@ -287,75 +257,38 @@ int lld_mappoint_refresh(lld_ctx* ctx, const lld_mappoint_refresh_in* in, lld_ma
   }
   const int n_block = want_desc ? n - n_wave : 0;
 
-  size_t inb = 0, outb = 0;
-  auto add_in = [&](size_t b) { const size_t o = inb; inb += al(b); return o; };
-  auto add_out = [&](size_t b) { const size_t o = outb; outb += al(b); return o; };
-  const size_t o_start = add_in((size_t)(n + 1) * 4), o_kf = add_in((size_t)n_obs * 4), o_bad = add_in((size_t)n);
-  const size_t o_desc = want_desc ? add_in((size_t)n_obs * 32) : 0, o_kfbad = want_desc ? add_in((size_t)n_kf) : 0;
-  const size_t o_list = want_desc ? add_in((size_t)n * 4) : 0;
-  const size_t o_ow = want_norm ? add_in((size_t)n_kf * 12) : 0, o_pos = want_norm ? add_in((size_t)n * 12) : 0;
-  const size_t o_rkf = want_norm ? add_in((size_t)n * 4) : 0, o_rlv = want_norm ? add_in((size_t)n * 4) : 0;
-  const size_t o_scale = want_norm ? add_in((size_t)LLD_ORB_MAX_LEVELS * 4) : 0;
-  const size_t r_desc = want_desc ? add_out((size_t)n * 32) : 0, r_bo = want_desc ? add_out((size_t)n * 4) : 0;
-  const size_t r_bm = want_desc ? add_out((size_t)n * 4) : 0, r_ud = want_desc ? add_out((size_t)n) : 0;
-  const size_t r_nrm = want_norm ? add_out((size_t)n * 12) : 0, r_min = want_norm ? add_out((size_t)n * 4) : 0;
-  const size_t r_max = want_norm ? add_out((size_t)n * 4) : 0, r_un = want_norm ? add_out((size_t)n) : 0;
-  void* hb; st = lld_ctx_pinned(ctx, inb + outb, &hb); if (st) return st;
-  void* db; st = lld_ctx_scratch(ctx, inb + outb + 256, &db); if (st) return st;
-  char* h = (char*)hb; char* d = (char*)db; char* h_out = h + inb; char* d_out = d + inb;
-  std::memcpy(h + o_start, in->obs_start, (size_t)(n + 1) * 4);
-  if (n_obs) std::memcpy(h + o_kf, in->obs_kf, (size_t)n_obs * 4);
-  std::memcpy(h + o_bad, in->bad, (size_t)n);
-  if (want_desc) {
-    if (n_obs) std::memcpy(h + o_desc, in->obs_desc, (size_t)n_obs * 32);
-    if (n_kf && in->kf_bad) std::memcpy(h + o_kfbad, in->kf_bad, (size_t)n_kf);
-    std::memcpy(h + o_list, list.data(), (size_t)n * 4);
-  }
-  if (want_norm) {
-    if (n_kf && in->kf_ow) std::memcpy(h + o_ow, in->kf_ow, (size_t)n_kf * 12);
-    std::memcpy(h + o_pos, in->pos, (size_t)n * 12);
-    std::memcpy(h + o_rkf, in->ref_kf, (size_t)n * 4); std::memcpy(h + o_rlv, in->ref_level, (size_t)n * 4);
-    std::memcpy(h + o_scale, in->level_scale, (size_t)in->n_levels * 4);
-  }
-  hipStream_t sm = ctx->stream;
-  LLD_HIP_TRY(hipMemcpyAsync(d, h, inb, hipMemcpyHostToDevice, sm));
-  if (want_desc) {
-    PointArgs A;
-    A.obs_start = reinterpret_cast<const int32_t*>(d + o_start); A.obs_kf = reinterpret_cast<const int32_t*>(d + o_kf);
-    A.obs_desc = reinterpret_cast<const uint32_t*>(d + o_desc); A.kf_bad = reinterpret_cast<const uint8_t*>(d + o_kfbad);
-    A.bad = reinterpret_cast<const uint8_t*>(d + o_bad); A.list = reinterpret_cast<const int32_t*>(d + o_list);
-    A.desc = reinterpret_cast<uint32_t*>(d_out + r_desc); A.best_obs = reinterpret_cast<int32_t*>(d_out + r_bo);
-    A.best_median = reinterpret_cast<int32_t*>(d_out + r_bm); A.upd = reinterpret_cast<uint8_t*>(d_out + r_ud);
-    if (n_wave) hipLaunchKernelGGL(lm_point_wave, dim3(n_wave), dim3(kWave), 0, sm, A);
-    if (n_block) { A.list += n_wave; hipLaunchKernelGGL(lm_point_block, dim3(n_block), dim3(kBlock), 0, sm, A); }
-  }
-  if (want_norm) {
-    NormalArgs B;
-    B.obs_start = reinterpret_cast<const int32_t*>(d + o_start); B.obs_kf = reinterpret_cast<const int32_t*>(d + o_kf);
-    B.kf_ow = reinterpret_cast<const float*>(d + o_ow); B.pos = reinterpret_cast<const float*>(d + o_pos);
-    B.bad = reinterpret_cast<const uint8_t*>(d + o_bad); B.ref_kf = reinterpret_cast<const int32_t*>(d + o_rkf);
-    B.ref_level = reinterpret_cast<const int32_t*>(d + o_rlv); B.level_scale = reinterpret_cast<const float*>(d + o_scale);
-    B.n_levels = in->n_levels;
-    B.normal = reinterpret_cast<float*>(d_out + r_nrm); B.min_distance = reinterpret_cast<float*>(d_out + r_min);
-    B.max_distance = reinterpret_cast<float*>(d_out + r_max); B.upd = reinterpret_cast<uint8_t*>(d_out + r_un);
-    hipLaunchKernelGGL(lm_normal_wave, dim3(n), dim3(kWave), 0, sm, B);
-  }
-  LLD_HIP_TRY(hipGetLastError());
-  LLD_HIP_TRY(hipMemcpyAsync(h_out, d_out, outb, hipMemcpyDeviceToHost, sm));
-  LLD_HIP_TRY(hipStreamSynchronize(sm));
-  // scatter: a landmark the rule left alone keeps what the caller passed in
-  const uint8_t* ud = reinterpret_cast<const uint8_t*>(h_out + r_ud); const uint8_t* un = reinterpret_cast<const uint8_t*>(h_out + r_un);
-  for (int i = 0; i < n; ++i) {
-    uint8_t u = 0;
+  st = round_trip(ctx->stream, B, nullptr, [&](hipStream_t sm) {
     if (want_desc) {
-      out->best_obs[i] = reinterpret_cast<const int32_t*>(h_out + r_bo)[i];
-      out->best_median[i] = reinterpret_cast<const int32_t*>(h_out + r_bm)[i];
-      if (ud[i]) { std::memcpy(out->desc + (size_t)i * 8, h_out + r_desc + (size_t)i * 32, 32); u |= LLD_LANDMARK_DESCRIPTOR; }
+      PointArgs A{B.dev(u_start), B.dev(u_kf), B.dev(u_desc), B.dev(u_kfbad), B.dev(u_bad), B.dev(u_list), B.dev(r_desc), B.dev(r_bo), B.dev(r_bm), B.dev(r_ud)};
+      if (n_wave) hipLaunchKernelGGL(lm_point_wave, dim3(n_wave), dim3(kWave), 0, sm, A);
+      if (n_block) { A.list += n_wave; hipLaunchKernelGGL(lm_point_block, dim3(n_block), dim3(kBlock), 0, sm, A); }
     }
-    if (want_norm && un[i]) {
-      std::memcpy(out->normal + (size_t)i * 3, h_out + r_nrm + (size_t)i * 12, 12);
-      out->min_distance[i] = reinterpret_cast<const float*>(h_out + r_min)[i];
-      out->max_distance[i] = reinterpret_cast<const float*>(h_out + r_max)[i];
+    if (want_norm) {
+      const NormalArgs N{B.dev(u_start), B.dev(u_kf), B.dev(u_ow), B.dev(u_pos), B.dev(u_bad), B.dev(u_rkf), B.dev(u_rlv), B.dev(u_scale), in->n_levels,
+                         B.dev(r_nrm), B.dev(r_min), B.dev(r_max), B.dev(r_un)};
+      hipLaunchKernelGGL(lm_normal_wave, dim3(n), dim3(kWave), 0, sm, N);
+    }
+    return LLD_OK;
+  });
+  if (st) return st;
+  // scatter: a landmark the rule left alone keeps what the caller passed in
+  // (typed pointers as locals: B and the spans are captured by the launch above, and a byte store into `out` would make each one be read again)
+  const uint8_t* ud = B.host(r_ud); const uint8_t* un = B.host(r_un);
+  const int32_t* h_bo = B.host(r_bo); const int32_t* h_bm = B.host(r_bm); const uint32_t* h_desc = B.host(r_desc);
+  const float* h_nrm = B.host(r_nrm); const float* h_min = B.host(r_min); const float* h_max = B.host(r_max);
+  const bool desc_part = want_desc, norm_part = want_norm;
+  const int count = n;
+  for (int i = 0; i < count; ++i) {
+    uint8_t u = 0;
+    if (desc_part) {
+      out->best_obs[i] = h_bo[i];
+      out->best_median[i] = h_bm[i];
+      if (ud[i]) { std::memcpy(out->desc + (size_t)i * 8, h_desc + (size_t)i * 8, 32); u |= LLD_LANDMARK_DESCRIPTOR; }
+    }
+    if (norm_part && un[i]) {
+      std::memcpy(out->normal + (size_t)i * 3, h_nrm + (size_t)i * 3, 12);
+      out->min_distance[i] = h_min[i];
+      out->max_distance[i] = h_max[i];
       u |= LLD_LANDMARK_NORMAL_DEPTH;
     }
     out->updated[i] = u;
@@ -378,40 +311,31 @@ int lld_mapline_distinctive(lld_ctx* ctx, const lld_mapline_distinctive_in* in, 
   if (st) return st;
   LLD_HIP_TRY(hipSetDevice(ctx->device));
 
-  size_t inb = 0, outb = 0;
-  auto add_in = [&](size_t b) { const size_t o = inb; inb += al(b); return o; };
-  auto add_out = [&](size_t b) { const size_t o = outb; outb += al(b); return o; };
-  const size_t o_start = add_in((size_t)(n + 1) * 4), o_kf = add_in((size_t)n_obs * 4), o_bad = add_in((size_t)n);
-  const size_t o_desc = add_in((size_t)n_obs * dim * 4), o_kfbad = add_in((size_t)n_kf);
-  const size_t r_desc = add_out((size_t)n * dim * 4), r_bo = add_out((size_t)n * 4), r_bm = add_out((size_t)n * 4), r_u = add_out((size_t)n);
-  void* hb; st = lld_ctx_pinned(ctx, inb + outb, &hb); if (st) return st;
-  void* db; st = lld_ctx_scratch(ctx, inb + outb + 256, &db); if (st) return st;
-  char* h = (char*)hb; char* d = (char*)db; char* h_out = h + inb; char* d_out = d + inb;
-  std::memcpy(h + o_start, in->obs_start, (size_t)(n + 1) * 4);
-  std::memcpy(h + o_bad, in->bad, (size_t)n);
-  if (n_obs) {
-    std::memcpy(h + o_kf, in->obs_kf, (size_t)n_obs * 4);
-    std::memcpy(h + o_desc, in->obs_desc, (size_t)n_obs * dim * 4);
-  }
-  if (n_kf && in->kf_bad) std::memcpy(h + o_kfbad, in->kf_bad, (size_t)n_kf);
-  LineArgs A;
-  A.obs_start = reinterpret_cast<const int32_t*>(d + o_start); A.obs_kf = reinterpret_cast<const int32_t*>(d + o_kf);
-  A.obs_desc = reinterpret_cast<const float*>(d + o_desc); A.kf_bad = reinterpret_cast<const uint8_t*>(d + o_kfbad);
-  A.bad = reinterpret_cast<const uint8_t*>(d + o_bad); A.dim = dim;
-  A.desc = reinterpret_cast<float*>(d_out + r_desc); A.best_obs = reinterpret_cast<int32_t*>(d_out + r_bo);
-  A.best_median = reinterpret_cast<int32_t*>(d_out + r_bm); A.upd = reinterpret_cast<uint8_t*>(d_out + r_u);
-  hipStream_t sm = ctx->stream;
-  LLD_HIP_TRY(hipMemcpyAsync(d, h, inb, hipMemcpyHostToDevice, sm));
+  const size_t nn = (size_t)n, no = (size_t)n_obs;
+  UploadBlock B;
+  const auto u_start = B.take<int32_t>(nn + 1), u_kf = B.take<int32_t>(no); const auto u_bad = B.take<uint8_t>(nn);
+  const auto u_desc = B.take<float>(no, (size_t)dim); const auto u_kfbad = B.take<uint8_t>((size_t)n_kf);
+  B.end_upload();
+  const auto r_desc = B.take<float>(nn, (size_t)dim); const auto r_bo = B.take<int32_t>(nn), r_bm = B.take<int32_t>(nn); const auto r_u = B.take<uint8_t>(nn);
+  B.end_download();
+  void* hb; st = lld_ctx_pinned(ctx, B.size, &hb); if (st) return st;
+  void* db; st = lld_ctx_scratch(ctx, B.size + 256, &db); if (st) return st;
+  B.bind((char*)hb, (char*)db);
+  B.stage(u_start, in->obs_start); B.stage(u_kf, in->obs_kf); B.stage(u_bad, in->bad); B.stage(u_desc, in->obs_desc); B.stage(u_kfbad, in->kf_bad);
+  const LineArgs A{B.dev(u_start), B.dev(u_kf), B.dev(u_desc), B.dev(u_kfbad), B.dev(u_bad), dim, B.dev(r_desc), B.dev(r_bo), B.dev(r_bm), B.dev(r_u)};
   const size_t lds = ((size_t)kWave * (dim | 1) + (size_t)kWave * kWave) * sizeof(float);
-  hipLaunchKernelGGL(lm_line_wave, dim3(n), dim3(kWave), lds, sm, A);
-  LLD_HIP_TRY(hipGetLastError());
-  LLD_HIP_TRY(hipMemcpyAsync(h_out, d_out, outb, hipMemcpyDeviceToHost, sm));
-  LLD_HIP_TRY(hipStreamSynchronize(sm));
-  const uint8_t* u = reinterpret_cast<const uint8_t*>(h_out + r_u);
-  for (int i = 0; i < n; ++i) {
-    out->best_obs[i] = reinterpret_cast<const int32_t*>(h_out + r_bo)[i];
-    out->best_median[i] = reinterpret_cast<const int32_t*>(h_out + r_bm)[i];
-    if (u[i]) std::memcpy(out->desc + (size_t)i * dim, h_out + r_desc + (size_t)i * dim * 4, (size_t)dim * 4);
+  st = round_trip(ctx->stream, B, nullptr, [&](hipStream_t sm) {
+    hipLaunchKernelGGL(lm_line_wave, dim3(n), dim3(kWave), lds, sm, A);
+    return LLD_OK;
+  });
+  if (st) return st;
+  const uint8_t* u = B.host(r_u);
+  const int32_t* h_bo = B.host(r_bo); const int32_t* h_bm = B.host(r_bm); const float* h_desc = B.host(r_desc);
+  const int count = n; const size_t width = (size_t)dim;
+  for (int i = 0; i < count; ++i) {
+    out->best_obs[i] = h_bo[i];
+    out->best_median[i] = h_bm[i];
+    if (u[i]) std::memcpy(out->desc + (size_t)i * width, h_desc + (size_t)i * width, width * 4);
     out->updated[i] = u[i] ? LLD_LANDMARK_DESCRIPTOR : 0;
   }
   return LLD_OK;

@@ -21,7 +21,8 @@
 // one wavefront for the order-dependent extension loop out of LDS), map_first_kernel / map_count_kernel / map_write_kernel (first occurrences
 // by 64-bit atomicMin, per-keyframe counts, ordered compaction), and map_gather_kernel for stage 2 (lld_frame_track_local_map_resident).
 //
-// The tables' declarations are in lld_map_tables.h; covisibility on the same tables (lld_map_covisibility) is in lld_map_covis.hip.
+// The tables' declarations are in lld_map_tables.h, and so is Staging, the grow-only pinned and device pair the setters (up_begin) and the
+// other call families on the handle stage through; covisibility on the same tables (lld_map_covisibility) is in lld_map_covis.hip.
 #include "lld_common.h"
 #include "lld_device_math.h"
 #include "lld_frame_track_state.h"
@@ -419,22 +420,8 @@ using lld_map_dev::slots_ok;
 int up_begin(lld_map* m, UploadBlock& B) {
   B.end_upload();
   if (m->upload_pending) { LLD_HIP_TRY(hipEventSynchronize(m->uploaded)); m->upload_pending = false; }
-  if (B.size > m->h_up_bytes) {
-    if (m->h_up) LLD_HIP_TRY(hipHostFree(m->h_up));
-    m->h_up = nullptr; m->h_up_bytes = 0;
-    const size_t want = B.size + (B.size >> 2) + 4096;
-    if (hipHostMalloc(reinterpret_cast<void**>(&m->h_up), want, hipHostMallocDefault) != hipSuccess) { m->h_up = nullptr; return LLD_ERR_ALLOC; }
-    m->h_up_bytes = want;
-  }
-  if (B.size > m->d_up_bytes) {
-    LLD_HIP_TRY(hipStreamSynchronize(m->ctx->stream));                // the scatter kernels of an earlier call may still read the old block
-    if (m->d_up) LLD_HIP_TRY(hipFree(m->d_up));
-    m->d_up = nullptr; m->d_up_bytes = 0;
-    const size_t want = B.size + (B.size >> 2) + 4096;
-    if (hipMalloc(reinterpret_cast<void**>(&m->d_up), want) != hipSuccess) { m->d_up = nullptr; return LLD_ERR_ALLOC; }
-    m->d_up_bytes = want;
-  }
-  B.bind(m->h_up, m->d_up);
+  const int st = m->up.grow(m->ctx->stream, B.size, B.size); if (st) return st;
+  B.bind(m->up.h, m->up.d);
   return LLD_OK;
 }
 int up_submit(lld_map* m, const UploadBlock& B) {
@@ -656,16 +643,9 @@ void lld_map_destroy(lld_map* m) {
   if (m->d_tables) (void)hipFree(m->d_tables);
   if (m->d_ext) (void)hipFree(m->d_ext);
   if (m->d_ba) (void)hipFree(m->d_ba);
-  if (m->d_run) (void)hipFree(m->d_run);
   if (m->d_ref) (void)hipFree(m->d_ref);
-  if (m->d_ap) (void)hipFree(m->d_ap);
-  if (m->h_ap) (void)hipHostFree(m->h_ap);
   if (m->d_desc) (void)hipFree(m->d_desc);
-  if (m->d_rf) (void)hipFree(m->d_rf);
-  if (m->h_rf) (void)hipHostFree(m->h_rf);
-  if (m->h_ba) (void)hipHostFree(m->h_ba);
-  if (m->d_up) (void)hipFree(m->d_up);
-  if (m->h_up) (void)hipHostFree(m->h_up);
+  m->ba.release(); m->ap.release(); m->rf.release(); m->up.release();
   if (m->h_down) (void)hipHostFree(m->h_down);
   if (m->uploaded) (void)hipEventDestroy(m->uploaded);
   delete m;

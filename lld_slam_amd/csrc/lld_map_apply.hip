@@ -11,19 +11,20 @@
 //   ap_lines_kernel    one lane per window line: its erasures one after the other (their order decides which entries a line that goes
 //                      bad still clears), the minimal position, and the line's outputs
 //   ap_refresh_kernel  sixteen lanes per window point: mpRefKF, the position, UpdateNormalAndDepth on the entries that stay - each lane
-//                      forms terms, every lane adds them in row order (lld_normal_depth.h)
+//                      forms terms, every lane adds them in row order; the sum and the level lookup are lld_normal_depth.h's
 //   ap_rows_kernel     one lane per window point: the kept entries moved to the front of both rows (or both rows emptied), then the
 //                      point's outputs read back from the tables
 // The kernels follow each other on the stream, so none reads a row while another kernel rewrites it.  No index is followed before it is
 // held to the row it points into.  The host then repeats the removals on its copies of the rows (RowPool), from the flags it sent and the
-// verdicts it got back, and holds the lengths it arrives at to the device's.
+// verdicts it got back, and holds the lengths it arrives at to the device's.  The staging pair is lld_map_tables.h's Staging, the timed
+// upload / launches / download lld_round_trip.h's.
 #pragma clang fp contract(off)
 
 #include "lld_common.h"
-#include "lld_covis_lists.h"
 #include "lld_device_math.h"
 #include "lld_map_tables.h"
 #include "lld_normal_depth.h"
+#include "lld_round_trip.h"
 #include "lld_wave.h"
 
 namespace {
@@ -32,6 +33,8 @@ using lld_map_dev::MapBa;
 using lld_map_dev::MapDev;
 using lld_map_dev::MapExt;
 using lld_map_dev::RowPool;
+using lld_rt::blocks;
+using lld_rt::copy_out;
 using lld_track::Span;
 using lld_track::UploadBlock;
 
@@ -194,25 +197,15 @@ __global__ __launch_bounds__(kThreads) void ap_refresh_kernel(MapDev M, MapExt X
       if (gl == 0) A.p_ref[s] = ref;
     }
     if (!kept) continue;                                               // bad, or observations.empty(): the routine returns  (group-uniform)
-    // the level: pRefKF->mvKeysUn[observations[pRefKF]].octave; operator[] inserts 0 for a keyframe that is no observer
-    int level = -1; bool ok = ref >= 0 && !no_centre && A.has_ext;
-    if (ok) {
-      const int idx = ref_at < len ? X.idx_pool[ir.x + ref_at] : 0;
-      const int2 orow = X.k_oct[ref];
-      ok = Y.k_feat[ref] && idx < orow.y;
-      if (ok) { level = X.oct_pool[orow.x + idx]; ok = level >= 0 && level < A.n_levels; }
-    }
-    if (!ok) { if (gl == 0) A.o_flags[q] |= kNoRef; continue; }       // (group-uniform)
+    int level = -1;                                                    // of the reference keyframe's own observation
+    if (ref >= 0 && !no_centre && A.has_ext) level = lld_nd::ref_level(ref, ref_at, len, X.idx_pool + ir.x, X.k_oct, X.oct_pool, Y.k_feat, A.n_levels);
+    if (level < 0) { if (gl == 0) A.o_flags[q] |= kNoRef; continue; }       // (group-uniform)
     float nx = 0.f, ny = 0.f, nz = 0.f;
     for (int j0 = 0; j0 < len; j0 += kGroup) {
       const int j = j0 + gl;
       float tx = 0.f, ty = 0.f, tz = 0.f; int keep = 0;
       if (j < len && !A.era[at + j]) { keep = 1; lld_nd::term(px, py, pz, Y.k_ow + 3 * (size_t)M.obs_pool[row.x + j], tx, ty, tz); }
-      for (int l = 0; l < kGroup; l++) {                               // normal = normal + normali/cv::norm(normali), in row order, in every lane
-        const int k = lld_wave::group_bcast<kGroup>(keep, l);
-        const float ax = lld_wave::group_bcast<kGroup>(tx, l), ay = lld_wave::group_bcast<kGroup>(ty, l), az = lld_wave::group_bcast<kGroup>(tz, l);
-        if (k) { nx = nx + ax; ny = ny + ay; nz = nz + az; }
-      }
+      lld_nd::add_in_order<kGroup>(keep, tx, ty, tz, nx, ny, nz);
     }
     if (gl == 0) {
       lld_nd::finish(lld_nd::Out{M.p_nrm, M.p_mind, M.p_maxd}, s, px, py, pz, nx, ny, nz, kept, Y.k_ow + 3 * (size_t)ref, A.level_scale, level, A.n_levels);
@@ -250,25 +243,6 @@ __global__ void ap_download_rows_kernel(int n, const int32_t* slot, const int32_
   }
 }
 
-int grow_staging(lld_map* m, size_t pinned, size_t device) {
-  if (pinned > m->h_ap_bytes) {
-    if (m->h_ap) LLD_HIP_TRY(hipHostFree(m->h_ap));
-    m->h_ap = nullptr; m->h_ap_bytes = 0;
-    const size_t want = pinned + (pinned >> 2) + 4096;
-    if (hipHostMalloc(reinterpret_cast<void**>(&m->h_ap), want, hipHostMallocDefault) != hipSuccess) { m->h_ap = nullptr; return LLD_ERR_ALLOC; }
-    m->h_ap_bytes = want;
-  }
-  if (device > m->d_ap_bytes) {
-    LLD_HIP_TRY(hipStreamSynchronize(m->ctx->stream));
-    if (m->d_ap) LLD_HIP_TRY(hipFree(m->d_ap));
-    m->d_ap = nullptr; m->d_ap_bytes = 0;
-    const size_t want = device + (device >> 2) + 4096;
-    if (hipMalloc(reinterpret_cast<void**>(&m->d_ap), want) != hipSuccess) { m->d_ap = nullptr; return LLD_ERR_ALLOC; }
-    m->d_ap_bytes = want;
-  }
-  return LLD_OK;
-}
-
 // entry `at` leaves rows a and b (parallel rows of one landmark): the entries behind it move up, the rows' places stay
 void drop_entry(RowPool& a, RowPool& b, int s, int at) {
   int32_t* ra = a.mirror.data() + a.off[s]; int32_t* rb = b.mirror.data() + b.off[s];
@@ -278,8 +252,6 @@ void drop_entry(RowPool& a, RowPool& b, int s, int at) {
 }
 void drop_row(RowPool& a, RowPool& b, int s) { a.live -= a.len[s]; b.live -= b.len[s]; a.len[s] = b.len[s] = 0; }
 void clear_match(RowPool& rows, int kf, int idx) { if (idx < rows.len[kf]) rows.mirror[rows.off[kf] + idx] = -1; }
-
-template <class T> void copy_out(T* dst, const UploadBlock& B, const Span<T>& s, size_t n) { if (n) std::memcpy(dst, B.host(s), n * sizeof(T)); }
 
 RowPool* pool_of(lld_map* m, int kind, bool& allocated) {
   allocated = true;
@@ -311,13 +283,13 @@ int lld_map_ba_apply(lld_map* m, const lld_map_ba_apply_in* in, lld_map_ba_apply
   if ((nloc && (!out->tcw || !out->ow)) || (np && (!out->pt_pos || !out->pt_normal || !out->pt_min_distance || !out->pt_max_distance || !out->pt_n_obs || !out->pt_ref_kf ||
                                                   !out->pt_row_len || !out->pt_flags)) || (nl && (!out->ln_bad || !out->ln_n_obs || !out->ln_row_len))) return LLD_ERR_INVALID;
   // the window as the host received it; the rows of its points as the host keeps them (they are the device's: the map has not changed)
-  const int32_t* w_cam_slot = reinterpret_cast<const int32_t*>(m->h_ba + W.cam_slot);
-  const int32_t* w_point = reinterpret_cast<const int32_t*>(m->h_ba + W.point_slot);
-  const int32_t* w_pt_start = reinterpret_cast<const int32_t*>(m->h_ba + W.pt_start);
-  const int32_t* w_pt_cam = reinterpret_cast<const int32_t*>(m->h_ba + W.pt_cam);
-  const int32_t* w_line = reinterpret_cast<const int32_t*>(m->h_ba + W.line_slot);
-  const int32_t* w_ln_start = reinterpret_cast<const int32_t*>(m->h_ba + W.ln_start);
-  const int32_t* w_ln_cam = reinterpret_cast<const int32_t*>(m->h_ba + W.ln_cam);
+  const int32_t* w_cam_slot = reinterpret_cast<const int32_t*>(m->ba.h + W.cam_slot);
+  const int32_t* w_point = reinterpret_cast<const int32_t*>(m->ba.h + W.point_slot);
+  const int32_t* w_pt_start = reinterpret_cast<const int32_t*>(m->ba.h + W.pt_start);
+  const int32_t* w_pt_cam = reinterpret_cast<const int32_t*>(m->ba.h + W.pt_cam);
+  const int32_t* w_line = reinterpret_cast<const int32_t*>(m->ba.h + W.line_slot);
+  const int32_t* w_ln_start = reinterpret_cast<const int32_t*>(m->ba.h + W.ln_start);
+  const int32_t* w_ln_cam = reinterpret_cast<const int32_t*>(m->ba.h + W.ln_cam);
   long long era_total = 0;
   for (size_t q = 0; q < np; q++) {
     const int s = w_point[q];
@@ -338,8 +310,8 @@ int lld_map_ba_apply(lld_map* m, const lld_map_ba_apply_in* in, lld_map_ba_apply
   const auto r_lnobs = B.take<int32_t>(nl), r_llen = B.take<int32_t>(nl), r_lapp = B.take<int32_t>(nl);
   B.end_download();
   const auto t_era = B.take<uint8_t>((size_t)era_total);
-  int st = grow_staging(m, B.travel_bytes(), B.size); if (st) return st;
-  B.bind(m->h_ap, m->d_ap);
+  int st = m->ap.grow(ctx->stream, B.travel_bytes(), B.size); if (st) return st;
+  B.bind(m->ap.h, m->ap.d);
 
   float* tcw = out->tcw;
   for (size_t c = 0; c < nloc; c++) {                                  // SetPose(Converter::toCvMat(SE3quat)) (:1369): the float matrix is what the keyframe keeps
@@ -354,7 +326,7 @@ int lld_map_ba_apply(lld_map* m, const lld_map_ba_apply_in* in, lld_map_ba_apply
 
   ApArgs A{};
   A.n_local = W.n_local; A.n_pts = W.n_pts; A.n_lns = W.n_lns; A.n_levels = in->n_levels; A.has_ext = 1;
-  const char* dw = m->d_run;
+  const char* dw = m->ba.d;
   A.cam_slot = reinterpret_cast<const int32_t*>(dw + W.cam_slot); A.point_slot = reinterpret_cast<const int32_t*>(dw + W.point_slot);
   A.pt_start = reinterpret_cast<const int32_t*>(dw + W.pt_start); A.pt_cam = reinterpret_cast<const int32_t*>(dw + W.pt_cam);
   A.line_slot = reinterpret_cast<const int32_t*>(dw + W.line_slot); A.ln_start = reinterpret_cast<const int32_t*>(dw + W.ln_start);
@@ -368,17 +340,8 @@ int lld_map_ba_apply(lld_map* m, const lld_map_ba_apply_in* in, lld_map_ba_apply
 
   // from here on the tables move: the window is spent, and a HIP failure leaves host rows and device rows apart
   m->mutations++; m->win.valid = false;
-  hipStream_t sm = ctx->stream;
-  lld_covis::Events events;
-  hipEvent_t* ev = events.e;
-  const bool timed = out->phase_ms != nullptr;
-  const auto queue = [&]() -> int {
-    if (timed) for (int k = 0; k < 4; ++k) LLD_HIP_TRY(hipEventCreate(&ev[k]));
-    if (timed) LLD_HIP_TRY(hipEventRecord(ev[0], sm));
-    LLD_HIP_TRY(hipMemcpyAsync(B.d, B.h, B.up_bytes, hipMemcpyHostToDevice, sm));
-    if (timed) LLD_HIP_TRY(hipEventRecord(ev[1], sm));
+  st = lld_rt::round_trip(ctx->stream, B, out->phase_ms, [&](hipStream_t sm) {
     LLD_HIP_TRY(hipMemsetAsync(B.dev(r_cnt), 0, C_WORDS * 4, sm));
-    const auto blocks = [](size_t n, int per) { return dim3((unsigned)std::max<size_t>((n + per - 1) / per, 1)); };
     const dim3 grouped((unsigned)std::min<size_t>(std::max<size_t>((np + kGroups - 1) / kGroups, 1), 2048));
     if (nloc) hipLaunchKernelGGL(ap_cams_kernel, blocks(nloc, kThreads), dim3(kThreads), 0, sm, m->Y, A);
     if (np) hipLaunchKernelGGL(ap_mark_kernel, grouped, dim3(kThreads), 0, sm, m->D, m->X, m->Y, A);
@@ -386,15 +349,8 @@ int lld_map_ba_apply(lld_map* m, const lld_map_ba_apply_in* in, lld_map_ba_apply
     if (np) hipLaunchKernelGGL(ap_refresh_kernel, grouped, dim3(kThreads), 0, sm, m->D, m->X, m->Y, A);
     if (np) hipLaunchKernelGGL(ap_rows_kernel, blocks(np, 64), dim3(64), 0, sm, m->D, m->X, A);
     if (nloc) hipLaunchKernelGGL(ap_cams_out_kernel, blocks(nloc, kThreads), dim3(kThreads), 0, sm, m->Y, A);
-    LLD_HIP_TRY(hipGetLastError());
-    if (timed) LLD_HIP_TRY(hipEventRecord(ev[2], sm));
-    LLD_HIP_TRY(hipMemcpyAsync(B.h + B.up_bytes, B.d + B.up_bytes, B.down_bytes, hipMemcpyDeviceToHost, sm));
-    if (timed) LLD_HIP_TRY(hipEventRecord(ev[3], sm));
-    LLD_HIP_TRY(hipStreamSynchronize(sm));
-    if (timed) for (int k = 0; k < 3; ++k) LLD_HIP_TRY(hipEventElapsedTime(&out->phase_ms[k], ev[k], ev[k + 1]));
     return LLD_OK;
-  };
-  st = queue();
+  });
   if (st) { m->poisoned = true; return st; }
 
   // The host's rows follow: the same removals, from the flags that went up and the verdicts that came down.
@@ -474,17 +430,17 @@ int lld_map_download_rows(lld_map* m, int32_t kind, int32_t n, const int32_t* sl
   const auto i_s = B.take<int32_t>(n), i_st = B.take<int32_t>((size_t)n + 1);
   B.end_upload();
   const auto r_len = B.take<int32_t>(n), r_data = B.take<int32_t>((size_t)st[n]);
+  B.end_download();
   int rc;
   void* hb; rc = lld_ctx_pinned(ctx, B.size, &hb); if (rc) return rc;
   void* db; rc = lld_ctx_scratch(ctx, B.size + 256, &db); if (rc) return rc;
   B.bind((char*)hb, (char*)db);
   B.stage(i_s, slot); B.stage(i_st, st.data());
-  hipStream_t sm = ctx->stream;
-  LLD_HIP_TRY(hipMemcpyAsync(B.d, B.h, B.up_bytes, hipMemcpyHostToDevice, sm));
-  hipLaunchKernelGGL(ap_download_rows_kernel, dim3(std::min(n, 4096)), dim3(64), 0, sm, n, B.dev(i_s), B.dev(i_st), P->d_row, P->d_pool, B.dev(r_len), B.dev(r_data));
-  LLD_HIP_TRY(hipGetLastError());
-  LLD_HIP_TRY(hipMemcpyAsync(B.h + B.up_bytes, B.d + B.up_bytes, B.size - B.up_bytes, hipMemcpyDeviceToHost, sm));
-  LLD_HIP_TRY(hipStreamSynchronize(sm));
+  rc = lld_rt::round_trip(ctx->stream, B, nullptr, [&](hipStream_t sm) {
+    hipLaunchKernelGGL(ap_download_rows_kernel, dim3(std::min(n, 4096)), dim3(64), 0, sm, n, B.dev(i_s), B.dev(i_st), P->d_row, P->d_pool, B.dev(r_len), B.dev(r_data));
+    return LLD_OK;
+  });
+  if (rc) return rc;
   const int32_t* len = B.host(r_len);
   for (int i = 0; i < n; i++) if (len[i] != st[i + 1] - st[i]) return LLD_ERR_HIP;         // the device's rows are not the host's: never with a sound map
   if (st[n]) std::memcpy(data, B.host(r_data), (size_t)st[n] * 4);

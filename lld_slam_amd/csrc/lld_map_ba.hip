@@ -17,10 +17,12 @@
 //   ba_fill_kernel        sixteen lanes per landmark: a point's run in stored order, a line's run by ascending mn_id, widened
 // A row's order inside a run is a rank by counting (how many kept entries come before this one), not a sort in LDS: rows are short, and no
 // row length is a limit.  Nothing is written to the window unless the status is 0 and every count is inside its capacity; both are decided
-// on the device before ba_fill_kernel, from row lengths alone.  Plain vector loads and stores only.
+// on the device before ba_fill_kernel, from row lengths alone.  Plain vector loads and stores only.  On the host the window is laid out on an
+// UploadBlock in the map's staging pair (lld_map_tables.h's Staging) and travels through lld_round_trip.h; the downloaded range starts behind
+// the scratch, at the header.
 #include "lld_common.h"
-#include "lld_covis_lists.h"
 #include "lld_map_tables.h"
+#include "lld_round_trip.h"
 #include "lld_wave.h"
 
 namespace {
@@ -29,6 +31,7 @@ using lld_map_dev::MapBa;
 using lld_map_dev::MapDev;
 using lld_map_dev::MapExt;
 using lld_map_dev::u64;
+using lld_rt::copy_out;
 using lld_track::Span;
 using lld_track::UploadBlock;
 
@@ -320,25 +323,6 @@ struct Layout {                                  // the downloaded span of one c
   Span<double> cam_qt, pt_xyz, pt_uvr, pt_sig, ln_x0, ln_dir, ln_left, ln_right;
 };
 
-int grow_staging(lld_map* m, size_t bytes) {
-  if (bytes > m->h_ba_bytes) {
-    if (m->h_ba) LLD_HIP_TRY(hipHostFree(m->h_ba));
-    m->h_ba = nullptr; m->h_ba_bytes = 0;
-    const size_t want = bytes + (bytes >> 2) + 4096;
-    if (hipHostMalloc(reinterpret_cast<void**>(&m->h_ba), want, hipHostMallocDefault) != hipSuccess) { m->h_ba = nullptr; return LLD_ERR_ALLOC; }
-    m->h_ba_bytes = want;
-  }
-  if (bytes > m->d_run_bytes) {
-    LLD_HIP_TRY(hipStreamSynchronize(m->ctx->stream));
-    if (m->d_run) LLD_HIP_TRY(hipFree(m->d_run));
-    m->d_run = nullptr; m->d_run_bytes = 0;
-    const size_t want = bytes + (bytes >> 2) + 4096;
-    if (hipMalloc(reinterpret_cast<void**>(&m->d_run), want) != hipSuccess) { m->d_run = nullptr; return LLD_ERR_ALLOC; }
-    m->d_run_bytes = want;
-  }
-  return LLD_OK;
-}
-
 int check_in(const lld_map* m, const lld_map_ba_in* in) {
   if (!m || !in) return LLD_ERR_INVALID;
   if (in->n_keyframes < 1 || in->n_keyframes > kMaxLocal || !in->kf_slot || in->n_levels < 1 || !in->inv_level_sigma2) return LLD_ERR_INVALID;
@@ -379,8 +363,8 @@ int run_window(lld_map* m, const lld_map_ba_in* in, const int32_t* cap, UploadBl
   L.line_slot = B.take<int32_t>(cl); L.ln_x0 = B.take<double>(cl, 3); L.ln_dir = B.take<double>(cl, 3); L.ln_start = B.take<int32_t>(cl + 1);
   L.ln_cam = B.take<int32_t>(clo); L.ln_left = B.take<double>(clo, 4); L.ln_right = B.take<double>(clo, 4); L.ln_oct = B.take<int32_t>(clo, 2);
   m->win.valid = false;                                                // the staging is about to be overwritten
-  int st = grow_staging(m, B.size); if (st) return st;
-  B.bind(m->h_ba, m->d_run);
+  int st = m->ba.grow(ctx->stream, B.size, B.size); if (st) return st;
+  B.bind(m->ba.h, m->ba.d);
   B.stage(i_slot, in->kf_slot); B.stage(i_sig, in->inv_level_sigma2);
   std::memset(B.host(L.hdr), 0, H_WORDS * 4);
 
@@ -395,35 +379,23 @@ int run_window(lld_map* m, const lld_map_ba_in* in, const int32_t* cap, UploadBl
   A.line_slot = B.dev(L.line_slot); A.ln_x0 = B.dev(L.ln_x0); A.ln_dir = B.dev(L.ln_dir); A.ln_start = B.dev(L.ln_start); A.ln_cam = B.dev(L.ln_cam);
   A.ln_left = B.dev(L.ln_left); A.ln_right = B.dev(L.ln_right); A.ln_oct = B.dev(L.ln_oct);
 
-  hipStream_t sm = ctx->stream;
-  lld_covis::Events events;
-  hipEvent_t* ev = events.e;
-  const bool timed = phase_ms != nullptr;
-  if (timed) for (int k = 0; k < 4; ++k) LLD_HIP_TRY(hipEventCreate(&ev[k]));
-  if (timed) LLD_HIP_TRY(hipEventRecord(ev[0], sm));
-  LLD_HIP_TRY(hipMemcpyAsync(B.d, B.h, B.up_bytes, hipMemcpyHostToDevice, sm));
-  if (timed) LLD_HIP_TRY(hipEventRecord(ev[1], sm));
-  const MapDev& M = m->D;
-  LLD_HIP_TRY(hipMemsetAsync(B.dev(L.hdr), 0, H_WORDS * 4, sm));
-  LLD_HIP_TRY(hipMemsetAsync(m->d_tables + m->first_off, 0xff, m->first_bytes, sm));       // p_first / l_first: scratch of a call, as in UpdateLocalMap
-  LLD_HIP_TRY(hipMemsetAsync(m->d_ba + m->mark_off, 0xff, m->mark_bytes, sm));
-  hipLaunchKernelGGL(ba_mark_kernel, dim3((n + kThreads - 1) / kThreads), dim3(kThreads), 0, sm, M, m->Y, A);
-  hipLaunchKernelGGL(ba_first_kernel, dim3(n), dim3(kThreads), 0, sm, M, m->Y, A);
-  hipLaunchKernelGGL(ba_count_kernel, dim3(n), dim3(kThreads), 0, sm, M, m->Y, A);
-  hipLaunchKernelGGL(ba_write_kernel, dim3(n), dim3(kThreads), 0, sm, M, m->Y, A);
-  hipLaunchKernelGGL(ba_visit_kernel, dim3(kGrid), dim3(kThreads), 0, sm, M, m->X, m->Y, A);
-  hipLaunchKernelGGL(ba_local_cams_kernel, dim3(1), dim3(kMaxLocal), 0, sm, m->Y, A);
-  hipLaunchKernelGGL(ba_fixed_rank_kernel, dim3(kGrid), dim3(kThreads), 0, sm, m->Y, A);
-  hipLaunchKernelGGL(ba_cams_kernel, dim3(kGrid), dim3(kThreads), 0, sm, M, m->X, m->Y, A);
-  hipLaunchKernelGGL(ba_scan_kernel, dim3(kGrid), dim3(kThreads), 0, sm, A);
-  hipLaunchKernelGGL(ba_fill_kernel, dim3(kGrid), dim3(kThreads), 0, sm, M, m->X, m->Y, A);
-  LLD_HIP_TRY(hipGetLastError());
-  if (timed) LLD_HIP_TRY(hipEventRecord(ev[2], sm));
-  LLD_HIP_TRY(hipMemcpyAsync(B.h + out_off, B.d + out_off, B.size - out_off, hipMemcpyDeviceToHost, sm));
-  if (timed) LLD_HIP_TRY(hipEventRecord(ev[3], sm));
-  LLD_HIP_TRY(hipStreamSynchronize(sm));
-  if (timed) for (int k = 0; k < 3; ++k) LLD_HIP_TRY(hipEventElapsedTime(&phase_ms[k], ev[k], ev[k + 1]));
-  return LLD_OK;
+  return lld_rt::round_trip(ctx->stream, B, out_off, B.size - out_off, phase_ms, [&](hipStream_t sm) {
+    const MapDev& M = m->D;
+    LLD_HIP_TRY(hipMemsetAsync(B.dev(L.hdr), 0, H_WORDS * 4, sm));
+    LLD_HIP_TRY(hipMemsetAsync(m->d_tables + m->first_off, 0xff, m->first_bytes, sm));       // p_first / l_first: scratch of a call, as in UpdateLocalMap
+    LLD_HIP_TRY(hipMemsetAsync(m->d_ba + m->mark_off, 0xff, m->mark_bytes, sm));
+    hipLaunchKernelGGL(ba_mark_kernel, dim3((n + kThreads - 1) / kThreads), dim3(kThreads), 0, sm, M, m->Y, A);
+    hipLaunchKernelGGL(ba_first_kernel, dim3(n), dim3(kThreads), 0, sm, M, m->Y, A);
+    hipLaunchKernelGGL(ba_count_kernel, dim3(n), dim3(kThreads), 0, sm, M, m->Y, A);
+    hipLaunchKernelGGL(ba_write_kernel, dim3(n), dim3(kThreads), 0, sm, M, m->Y, A);
+    hipLaunchKernelGGL(ba_visit_kernel, dim3(kGrid), dim3(kThreads), 0, sm, M, m->X, m->Y, A);
+    hipLaunchKernelGGL(ba_local_cams_kernel, dim3(1), dim3(kMaxLocal), 0, sm, m->Y, A);
+    hipLaunchKernelGGL(ba_fixed_rank_kernel, dim3(kGrid), dim3(kThreads), 0, sm, m->Y, A);
+    hipLaunchKernelGGL(ba_cams_kernel, dim3(kGrid), dim3(kThreads), 0, sm, M, m->X, m->Y, A);
+    hipLaunchKernelGGL(ba_scan_kernel, dim3(kGrid), dim3(kThreads), 0, sm, A);
+    hipLaunchKernelGGL(ba_fill_kernel, dim3(kGrid), dim3(kThreads), 0, sm, M, m->X, m->Y, A);
+    return LLD_OK;
+  });
 }
 
 bool fits(const int32_t* h, const int32_t* cap, bool with_bad = false) {
@@ -438,8 +410,6 @@ void keep_for_apply(lld_map* m, const Layout& L, const int32_t* h) {
   W.cam_slot = L.cam_slot.off; W.point_slot = L.point_slot.off; W.pt_start = L.pt_start.off; W.pt_cam = L.pt_cam.off;
   W.line_slot = L.line_slot.off; W.ln_start = L.ln_start.off; W.ln_cam = L.ln_cam.off;
 }
-
-template <class T> void copy_out(T* dst, const UploadBlock& B, const Span<T>& s, size_t n) { if (n) std::memcpy(dst, B.host(s), n * sizeof(T)); }
 
 }  // namespace
 

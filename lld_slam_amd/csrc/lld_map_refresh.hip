@@ -4,7 +4,9 @@
 // descriptor rows where the map keeps them, and write p_desc / p_nrm / p_mind / p_maxd / l_desc in place.  The rules and the numerics are
 // those of lld_mappoint_refresh / lld_mapline_distinctive (lld_landmark.hip), restated on how a descriptor row is fetched: through the
 // landmark's index row into the keyframe's descriptor pool, not from a gathered array.  lld_map_download_points / _lines read the fixed
-// rows back for an audit.
+// rows back for an audit.  Shared with lld_landmark.hip: the selection cores (lld_distinctive.h); with lld_map_apply.hip: the ordered sum and
+// the reference keyframe's level (lld_normal_depth.h); with every call on the map: the staging pair (lld_map_tables.h) and the timed upload /
+// launches / download (lld_round_trip.h).
 //
 //   rf_check_kernel    sixteen lanes per named point: the early return, and every index held to the row it points into before any other
 //                      kernel follows it - the verdict byte the kernels below obey, the reference keyframe and the level of the normal part
@@ -25,9 +27,10 @@
 #include <vector>
 
 #include "lld_common.h"
-#include "lld_covis_lists.h"
+#include "lld_distinctive.h"
 #include "lld_map_tables.h"
 #include "lld_normal_depth.h"
+#include "lld_round_trip.h"
 #include "lld_wave.h"
 
 namespace {
@@ -36,11 +39,15 @@ using lld_map_dev::MapBa;
 using lld_map_dev::MapDesc;
 using lld_map_dev::MapDev;
 using lld_map_dev::MapExt;
+using lld_rt::blocks;
+using lld_rt::copy_out;
+using lld_rt::round_trip;
 using lld_track::Span;
 using lld_track::UploadBlock;
 
 constexpr int kWave = 64;
 constexpr int kBlock = 256;
+static_assert(kWave == lld_dd::kWave && kBlock == lld_dd::kBlock, "lld_distinctive.h is written for these");
 constexpr int kGroup = 16, kGroups = kBlock / kGroup;
 constexpr uint8_t kDesc = LLD_LANDMARK_DESCRIPTOR, kNormal = LLD_LANDMARK_NORMAL_DEPTH;
 constexpr uint8_t kNoIndex = LLD_MAP_REFRESH_NO_INDEX, kNoDesc = LLD_MAP_REFRESH_NO_DESCRIPTOR, kNoRef = LLD_MAP_REFRESH_NO_REFERENCE;
@@ -59,8 +66,6 @@ struct RfLineArgs {
   const int32_t* slot;
   float* o_desc; int32_t* o_best; int32_t* o_med; uint8_t* o_upd;
 };
-
-__device__ __forceinline__ uint32_t bcast(uint32_t v, int l) { return (uint32_t)__builtin_amdgcn_readlane((int)v, l); }
 
 // ------------------------------------------------------------------------------------------------ points: what may be followed
 __global__ __launch_bounds__(kBlock) void rf_check_kernel(MapDev M, MapExt X, MapBa Y, MapDesc Z, RfArgs A) {
@@ -98,15 +103,9 @@ __global__ __launch_bounds__(kBlock) void rf_check_kernel(MapDev M, MapExt X, Ma
     if (len) {
       if (no_desc) v |= kNoDesc;
       if (A.want_norm) {
-        // the level: pRefKF->mvKeysUn[observations[pRefKF]].octave; operator[] inserts 0 for a keyframe that is no observer
-        bool ok = ref >= 0 && !no_centre && A.has_ext && A.has_ba;
-        if (ok) {
-          const int idx = ref_at < len ? X.idx_pool[ir.x + ref_at] : 0;
-          const int2 orow = X.k_oct[ref];
-          ok = Y.k_feat[ref] && idx < orow.y;
-          if (ok) { level = X.oct_pool[orow.x + idx]; ok = level >= 0 && level < A.n_levels; }
-        }
-        if (!ok) { v |= kNoRef; level = 0; }
+        level = -1;                                // of the reference keyframe's own observation
+        if (ref >= 0 && !no_centre && A.has_ext && A.has_ba) level = lld_nd::ref_level(ref, ref_at, len, X.idx_pool + ir.x, X.k_oct, X.oct_pool, Y.k_feat, A.n_levels);
+        if (level < 0) { v |= kNoRef; level = 0; }
       }
     }
     A.verdict[q] = v; A.t_ref[q] = ref; A.t_level[q] = level;
@@ -151,20 +150,7 @@ __global__ __launch_bounds__(kWave) void rf_point_wave(MapDev M, MapExt X, MapDe
     const uint4* from = reinterpret_cast<const uint4*>(Z.kdesc_pool + src[lane]);   // rows start at multiples of eight words
     d0 = from[0]; d1 = from[1];
   }
-  for (int j = 0; j < N; ++j) {
-    const uint4 b0 = make_uint4(bcast(d0.x, j), bcast(d0.y, j), bcast(d0.z, j), bcast(d0.w, j));
-    const uint4 b1 = make_uint4(bcast(d1.x, j), bcast(d1.y, j), bcast(d1.z, j), bcast(d1.w, j));
-    dist[j * kWave + lane] = (uint16_t)lld_wave::hamming256(d0, d1, b0, b1);
-  }
-  const int idx = (int)(0.5 * (N - 1));          // vDists[0.5*(N-1)] (:294)
-  int lo = 0, hi = 256;                          // sorted[idx] = the smallest v with count(d <= v) >= idx + 1
-  while (lo < hi) {
-    const int mid = (lo + hi) >> 1;
-    int cnt = 0;
-    for (int j = 0; j < N; ++j) cnt += dist[j * kWave + lane] <= mid ? 1 : 0;
-    if (cnt > idx) hi = mid; else lo = mid + 1;
-  }
-  const int key = lld_wave::min(lane < N ? ((lo << 16) | lane) : 0x7fffffff);   // median < BestMedian in row order (:296-300)
+  const int key = lld_dd::point_wave(d0, d1, N, lane, dist);
   const int w = key & 0xffff;
   if (lane < 8) M.p_desc[8 * (size_t)s + lane] = (uint32_t)Z.kdesc_pool[src[w] + lane];
   if (lane == 0) { A.o_best[q] = kept[w]; A.o_med[q] = key >> 16; A.o_upd[q] |= kDesc; }
@@ -191,25 +177,7 @@ __global__ __launch_bounds__(kBlock) void rf_point_block(MapDev M, MapExt X, Map
   if (N == 0) return;
   for (int k = tid; k < 2 * N; k += kBlock) rows[k] = reinterpret_cast<const uint4*>(Z.kdesc_pool + src[k >> 1])[k & 1];
   __syncthreads();
-  const int idx = (int)(0.5 * (N - 1));
-  int key = 0x7fffffff;
-  for (int i = tid; i < N; i += kBlock) {        // ascending i per lane: the packed key keeps the first of equal medians
-    const uint4 a0 = rows[2 * i], a1 = rows[2 * i + 1];
-    int lo = 0, hi = 256;
-    while (lo < hi) {
-      const int mid = (lo + hi) >> 1;
-      int cnt = 0;
-      for (int j = 0; j < N; ++j) cnt += lld_wave::hamming256(a0, a1, rows[2 * j], rows[2 * j + 1]) <= mid ? 1 : 0;
-      if (cnt > idx) hi = mid; else lo = mid + 1;
-    }
-    const int k = (lo << 16) | i;
-    key = k < key ? k : key;
-  }
-  key = lld_wave::min(key);
-  if ((tid & (kWave - 1)) == 0) red[tid / kWave] = key;
-  __syncthreads();
-#pragma unroll
-  for (int k = 0; k < kBlock / kWave; ++k) key = red[k] < key ? red[k] : key;
+  const int key = lld_dd::point_block(rows, N, tid, red);
   const int w = key & 0xffff;
   if (tid < 8) M.p_desc[8 * (size_t)s + tid] = reinterpret_cast<const uint32_t*>(rows + 2 * w)[tid];
   if (tid == 0) { A.o_best[q] = kept[w]; A.o_med[q] = key >> 16; A.o_upd[q] |= kDesc; }
@@ -230,11 +198,7 @@ __global__ __launch_bounds__(kBlock) void rf_normal_kernel(MapDev M, MapBa Y, Rf
       const int j = j0 + gl;
       float tx = 0.f, ty = 0.f, tz = 0.f; int keep = 0;
       if (j < len) { keep = 1; lld_nd::term(px, py, pz, Y.k_ow + 3 * (size_t)M.obs_pool[row.x + j], tx, ty, tz); }
-      for (int l = 0; l < kGroup; l++) {         // normal = normal + normali/cv::norm(normali), in row order, in every lane
-        const int k = lld_wave::group_bcast<kGroup>(keep, l);
-        const float ax = lld_wave::group_bcast<kGroup>(tx, l), ay = lld_wave::group_bcast<kGroup>(ty, l), az = lld_wave::group_bcast<kGroup>(tz, l);
-        if (k) { nx = nx + ax; ny = ny + ay; nz = nz + az; }
-      }
+      lld_nd::add_in_order<kGroup>(keep, tx, ty, tz, nx, ny, nz);
     }
     if (on && gl == 0) {
       lld_nd::finish(lld_nd::Out{M.p_nrm, M.p_mind, M.p_maxd}, s, px, py, pz, nx, ny, nz, len, Y.k_ow + 3 * (size_t)A.t_ref[q], A.level_scale, A.t_level[q],
@@ -299,28 +263,8 @@ __global__ __launch_bounds__(kWave) void rf_line_wave(MapDev M, MapBa Y, MapDesc
     for (int k = lane; k < dim; k += kWave) rows[r * stride + k] = __int_as_float(from[k]);
   }
   __syncthreads();
-  const float* mine = rows + (lane < N ? lane : 0) * stride;
-  for (int j = 0; j < N; ++j) {
-    const float* other = rows + j * stride;
-    double acc = 0.0;
-    for (int k = 0; k < dim; ++k) { const float df = mine[k] - other[k]; acc = fma((double)df, (double)df, acc); }   // the product is exact in double
-    dist[j * kWave + lane] = (float)__dsqrt_rn(acc);
-  }
-  const int idx = (int)(0.5 * (N - 1));
-  float med = 0.f;                               // sorted[idx]: the value with rank_below <= idx < rank_below_or_equal
-  for (int j = 0; j < N; ++j) {
-    const float v = dist[j * kWave + lane];
-    int lt = 0, le = 0;
-    for (int k = 0; k < N; ++k) { const float u = dist[k * kWave + lane]; lt += u < v ? 1 : 0; le += u <= v ? 1 : 0; }
-    if (lt <= idx && idx < le) med = v;
-  }
-  int mi = lane < N ? (int)med : 0x7fffffff;     // int median = vDists[...]: the float is truncated before the `<` test (:188)
-  int bi = lane;
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) {
-    const int om = __shfl_xor(mi, o), oi = __shfl_xor(bi, o);
-    if (om < mi || (om == mi && oi < bi)) { mi = om; bi = oi; }
-  }
+  const int2 best = lld_dd::line(rows, dist, N, dim, stride, lane);
+  const int mi = best.x, bi = best.y;
   for (int k = lane; k < dim; k += kWave) M.l_desc[(size_t)s * dim + k] = rows[bi * stride + k];
   if (lane == 0) { A.o_best[q] = kept[bi]; A.o_med[q] = mi; A.o_upd[q] = kDesc; }
 }
@@ -354,50 +298,7 @@ __global__ void rf_download_lines_kernel(MapDev M, int n, const int32_t* slot, f
 }
 
 // ------------------------------------------------------------------------------------------------ host
-int grow_staging(lld_map* m, size_t pinned, size_t device) {
-  if (pinned > m->h_rf_bytes) {
-    if (m->h_rf) LLD_HIP_TRY(hipHostFree(m->h_rf));
-    m->h_rf = nullptr; m->h_rf_bytes = 0;
-    const size_t want = pinned + (pinned >> 2) + 4096;
-    if (hipHostMalloc(reinterpret_cast<void**>(&m->h_rf), want, hipHostMallocDefault) != hipSuccess) { m->h_rf = nullptr; return LLD_ERR_ALLOC; }
-    m->h_rf_bytes = want;
-  }
-  if (device > m->d_rf_bytes) {
-    LLD_HIP_TRY(hipStreamSynchronize(m->ctx->stream));
-    if (m->d_rf) LLD_HIP_TRY(hipFree(m->d_rf));
-    m->d_rf = nullptr; m->d_rf_bytes = 0;
-    const size_t want = device + (device >> 2) + 4096;
-    if (hipMalloc(reinterpret_cast<void**>(&m->d_rf), want) != hipSuccess) { m->d_rf = nullptr; return LLD_ERR_ALLOC; }
-    m->d_rf_bytes = want;
-  }
-  return LLD_OK;
-}
-
 using lld_map_dev::slots_ok;
-
-template <class T> void copy_out(T* dst, const UploadBlock& B, const Span<T>& s, size_t n) { if (dst && n) std::memcpy(dst, B.host(s), n * sizeof(T)); }
-
-// upload, launch(stream), download, wait; phase_ms, when given, receives the HIP-event times of the three
-template <class Launch>
-int run(hipStream_t sm, const UploadBlock& B, float* phase_ms, Launch launch) {
-  lld_covis::Events events;
-  hipEvent_t* ev = events.e;
-  const bool timed = phase_ms != nullptr;
-  if (timed) for (int k = 0; k < 4; ++k) LLD_HIP_TRY(hipEventCreate(&ev[k]));
-  if (timed) LLD_HIP_TRY(hipEventRecord(ev[0], sm));
-  LLD_HIP_TRY(hipMemcpyAsync(B.d, B.h, B.up_bytes, hipMemcpyHostToDevice, sm));
-  if (timed) LLD_HIP_TRY(hipEventRecord(ev[1], sm));
-  launch(sm);
-  LLD_HIP_TRY(hipGetLastError());
-  if (timed) LLD_HIP_TRY(hipEventRecord(ev[2], sm));
-  LLD_HIP_TRY(hipMemcpyAsync(B.h + B.up_bytes, B.d + B.up_bytes, B.down_bytes, hipMemcpyDeviceToHost, sm));
-  if (timed) LLD_HIP_TRY(hipEventRecord(ev[3], sm));
-  LLD_HIP_TRY(hipStreamSynchronize(sm));
-  if (timed) for (int k = 0; k < 3; ++k) LLD_HIP_TRY(hipEventElapsedTime(&phase_ms[k], ev[k], ev[k + 1]));
-  return LLD_OK;
-}
-
-dim3 blocks(size_t n, int per) { return dim3((unsigned)std::max<size_t>((n + per - 1) / per, 1)); }
 
 }  // namespace
 
@@ -426,8 +327,8 @@ int lld_map_refresh_points(lld_map* m, const lld_map_refresh_points_in* in, lld_
   const auto r_nrm = B.take<float>(nn, 3), r_min = B.take<float>(nn), r_max = B.take<float>(nn); const auto r_upd = B.take<uint8_t>(nn);
   B.end_download();
   const auto t_v = B.take<uint8_t>(nn); const auto t_ref = B.take<int32_t>(nn), t_lv = B.take<int32_t>(nn);
-  int st = grow_staging(m, B.travel_bytes(), B.size); if (st) return st;
-  B.bind(m->h_rf, m->d_rf);
+  int st = m->rf.grow(ctx->stream, B.travel_bytes(), B.size); if (st) return st;
+  B.bind(m->rf.h, m->rf.d);
 
   // the two launch lists of the descriptor part, by the stored row's length (the host's lengths are the device's)
   B.stage(u_slot, in->slot);
@@ -447,13 +348,14 @@ int lld_map_refresh_points(lld_map* m, const lld_map_refresh_points_in* in, lld_
   A.o_desc = B.dev(r_desc); A.o_best = B.dev(r_best); A.o_med = B.dev(r_med); A.o_nrm = B.dev(r_nrm); A.o_mind = B.dev(r_min); A.o_maxd = B.dev(r_max);
   A.o_upd = B.dev(r_upd);
 
-  st = run(ctx->stream, B, out->phase_ms, [&](hipStream_t sm) {
+  st = round_trip(ctx->stream, B, out->phase_ms, [&](hipStream_t sm) {
     const dim3 grouped((unsigned)std::min<size_t>(std::max<size_t>((nn + kGroups - 1) / kGroups, 1), 2048));
     hipLaunchKernelGGL(rf_check_kernel, grouped, dim3(kBlock), 0, sm, m->D, m->X, m->Y, m->Z, A);
     if (want_desc && n_wave) hipLaunchKernelGGL(rf_point_wave, dim3(n_wave), dim3(kWave), 0, sm, m->D, m->X, m->Z, A, 0);
     if (want_desc && n_block) hipLaunchKernelGGL(rf_point_block, dim3(n_block), dim3(kBlock), 0, sm, m->D, m->X, m->Z, A, n_wave);
     if (want_norm) hipLaunchKernelGGL(rf_normal_kernel, grouped, dim3(kBlock), 0, sm, m->D, m->Y, A);
     hipLaunchKernelGGL(rf_points_out_kernel, blocks(nn * 8, kBlock), dim3(kBlock), 0, sm, m->D, A);
+    return LLD_OK;
   });
   if (st) { m->poisoned = true; return st; }                           // what the tables hold is not known
   const uint8_t* upd = B.host(r_upd);
@@ -484,8 +386,8 @@ int lld_map_refresh_lines(lld_map* m, const lld_map_refresh_lines_in* in, lld_ma
   B.end_upload();
   const auto r_desc = B.take<float>(nn, dim); const auto r_best = B.take<int32_t>(nn), r_med = B.take<int32_t>(nn); const auto r_upd = B.take<uint8_t>(nn);
   B.end_download();
-  int st = grow_staging(m, B.travel_bytes(), B.size); if (st) return st;
-  B.bind(m->h_rf, m->d_rf);
+  int st = m->rf.grow(ctx->stream, B.travel_bytes(), B.size); if (st) return st;
+  B.bind(m->rf.h, m->rf.d);
   B.stage(u_slot, in->slot);
 
   RfLineArgs A{};
@@ -493,9 +395,10 @@ int lld_map_refresh_lines(lld_map* m, const lld_map_refresh_lines_in* in, lld_ma
   A.o_desc = B.dev(r_desc); A.o_best = B.dev(r_best); A.o_med = B.dev(r_med); A.o_upd = B.dev(r_upd);
   const size_t lds = ((size_t)kWave * (dim | 1) + (size_t)kWave * kWave + 2 * kWave) * sizeof(float);     // at most 49.9 KB: line_dim <= 128
 
-  st = run(ctx->stream, B, out->phase_ms, [&](hipStream_t sm) {
+  st = round_trip(ctx->stream, B, out->phase_ms, [&](hipStream_t sm) {
     hipLaunchKernelGGL(rf_line_wave, dim3(n), dim3(kWave), lds, sm, m->D, m->Y, m->Z, A);
     hipLaunchKernelGGL(rf_lines_out_kernel, blocks(nn * dim, kBlock), dim3(kBlock), 0, sm, m->D, A);
+    return LLD_OK;
   });
   if (st) { m->poisoned = true; return st; }
   const uint8_t* upd = B.host(r_upd);
@@ -528,7 +431,10 @@ int lld_map_download_points(lld_map* m, int32_t n, const int32_t* slot, float* p
   B.bind((char*)hb, (char*)db);
   B.stage(u_slot, slot);
   const DlArgs A{n, B.dev(u_slot), B.dev(r_pos), B.dev(r_nrm), B.dev(r_min), B.dev(r_max), B.dev(r_desc), B.dev(r_state)};
-  st = run(ctx->stream, B, nullptr, [&](hipStream_t sm) { hipLaunchKernelGGL(rf_download_points_kernel, blocks(nn * 8, kBlock), dim3(kBlock), 0, sm, m->D, A); });
+  st = round_trip(ctx->stream, B, nullptr, [&](hipStream_t sm) {
+    hipLaunchKernelGGL(rf_download_points_kernel, blocks(nn * 8, kBlock), dim3(kBlock), 0, sm, m->D, A);
+    return LLD_OK;
+  });
   if (st) return st;
   copy_out(pos, B, r_pos, nn * 3); copy_out(normal, B, r_nrm, nn * 3); copy_out(min_distance, B, r_min, nn); copy_out(max_distance, B, r_max, nn);
   copy_out(desc, B, r_desc, nn * 8); copy_out(state, B, r_state, nn);
@@ -554,8 +460,9 @@ int lld_map_download_lines(lld_map* m, int32_t n, const int32_t* slot, float* de
   void* db; st = lld_ctx_scratch(ctx, B.size + 256, &db); if (st) return st;
   B.bind((char*)hb, (char*)db);
   B.stage(u_slot, slot);
-  st = run(ctx->stream, B, nullptr, [&](hipStream_t sm) {
+  st = round_trip(ctx->stream, B, nullptr, [&](hipStream_t sm) {
     hipLaunchKernelGGL(rf_download_lines_kernel, blocks(nn * dim, kBlock), dim3(kBlock), 0, sm, m->D, n, B.dev(u_slot), B.dev(r_desc), B.dev(r_bad));
+    return LLD_OK;
   });
   if (st) return st;
   copy_out(desc, B, r_desc, nn * dim); copy_out(bad, B, r_bad, nn);

@@ -1,7 +1,8 @@
 // lld_map_tables.h — the resident map's tables as the files that run on them see them: the device pointers (MapDev, MapExt), the host's
 // bookkeeping of the variable-length rows (RowPool) and the handle that owns both (struct lld_map).  lld_map.hip creates, fills and frees
 // them; lld_map_covis.hip and lld_map_ba.hip walk them; lld_map_apply.hip changes rows on the device and makes the RowPools follow;
-// lld_map_refresh.hip rewrites the landmarks' descriptor, normal and distance rows from them.
+// lld_map_refresh.hip rewrites the landmarks' descriptor, normal and distance rows from them.  The grow-only staging pair each of these
+// call families keeps on the handle is one struct (Staging); how a call travels through it is lld_round_trip.h's.
 // lld_map_internal.h stays the narrow face lld_frame_track.hip sees.  Nothing here is exported.
 #ifndef LLD_MAP_TABLES_H
 #define LLD_MAP_TABLES_H
@@ -115,6 +116,37 @@ struct RowPool {
   int launch(hipStream_t st, const UploadBlock& B, const PoolPlan& P) const;      // defined in lld_map.hip: it names map_rows_kernel
 };
 
+// A pinned block and a device block that a call family reuses from call to call and that only grow: a quarter and a page more than asked
+// for, so a slowly growing map does not allocate on every call.
+struct Staging {
+  char* h = nullptr; size_t h_bytes = 0; char* d = nullptr; size_t d_bytes = 0;
+  // LLD_ERR_ALLOC leaves the block that could not grow null.  `stream` is waited for before the device block is freed: the kernels of an
+  // earlier call may still read it.
+  int grow(hipStream_t stream, size_t pinned, size_t device) {
+    if (pinned > h_bytes) {
+      if (h) LLD_HIP_TRY(hipHostFree(h));
+      h = nullptr; h_bytes = 0;
+      const size_t want = pinned + (pinned >> 2) + 4096;
+      if (hipHostMalloc(reinterpret_cast<void**>(&h), want, hipHostMallocDefault) != hipSuccess) { h = nullptr; return LLD_ERR_ALLOC; }
+      h_bytes = want;
+    }
+    if (device > d_bytes) {
+      LLD_HIP_TRY(hipStreamSynchronize(stream));
+      if (d) LLD_HIP_TRY(hipFree(d));
+      d = nullptr; d_bytes = 0;
+      const size_t want = device + (device >> 2) + 4096;
+      if (hipMalloc(reinterpret_cast<void**>(&d), want) != hipSuccess) { d = nullptr; return LLD_ERR_ALLOC; }
+      d_bytes = want;
+    }
+    return LLD_OK;
+  }
+  void release() {
+    if (d) (void)hipFree(d);
+    if (h) (void)hipHostFree(h);
+    h = d = nullptr; h_bytes = d_bytes = 0;
+  }
+};
+
 // slots in range and no slot twice in one call (stamp / epoch: lld_map::stamp_* and lld_map::epoch)
 inline bool slots_ok(std::vector<uint32_t>& stamp, uint32_t& epoch, int n, const int32_t* slot) {
   if (++epoch == 0) { std::fill(stamp.begin(), stamp.end(), 0u); epoch = 1; }
@@ -139,13 +171,13 @@ struct lld_map {
   // the bundle-adjustment tables (MapBa): allocated by the first setter that fills them; mark_off / mark_bytes: k_mark inside d_ba
   lld_map_dev::MapBa Y{}; char* d_ba = nullptr; size_t ba_bytes = 0, mark_off = 0, mark_bytes = 0; lld_map_dev::RowPool kuvr, kkl, lobs, lidx;
   std::vector<uint8_t> kf_feat;             // lld_map_set_keyframe_features named the slot since the last clear
-  // lld_map_ba_window's staging (pinned, device), grow-only; lld_map_local_ba's result arrays and the capacities of its last call
-  char* h_ba = nullptr; size_t h_ba_bytes = 0; char* d_run = nullptr; size_t d_run_bytes = 0;
+  // lld_map_ba_window's staging; lld_map_local_ba's result arrays and the capacities of its last call
+  lld_map_dev::Staging ba;
   std::vector<double> ba_res_f; std::vector<uint8_t> ba_res_b; int32_t ba_cap[6] = {0, 0, 0, 0, 0, 0};
   std::vector<uint8_t> kf_set;              // lld_map_set_keyframes named the slot since the last clear
   // MapPoint::mpRefKF per point slot (lld_map_set_point_refs), -1 unknown: a pool of its own, allocated by the first call
   int32_t* d_ref = nullptr;
-  // The window lld_map_ba_window / lld_map_local_ba assembled last, for lld_map_ba_apply: its index arrays are still in h_ba / d_run at these
+  // The window lld_map_ba_window / lld_map_local_ba assembled last, for lld_map_ba_apply: its index arrays are still in ba.h / ba.d at these
   // byte offsets.  valid: the status was 0 and every capacity held; at: `mutations` when it was assembled.  mutations counts every call that
   // changes a table: lld_map_set_*, lld_map_clear, LLD_MAP_COVIS_WRITE_COV, lld_map_ba_apply.
   struct BaStaged {
@@ -154,14 +186,14 @@ struct lld_map {
     size_t cam_slot = 0, point_slot = 0, pt_start = 0, pt_cam = 0, line_slot = 0, ln_start = 0, ln_cam = 0;
   } win;
   unsigned long long mutations = 0;
-  char* h_ap = nullptr; size_t h_ap_bytes = 0; char* d_ap = nullptr; size_t d_ap_bytes = 0;      // lld_map_ba_apply's staging, grow-only
-  // the keyframes' descriptor rows (MapDesc): allocated by the first setter that fills them; lld_map_refresh_*'s staging, grow-only
+  lld_map_dev::Staging ap;                  // lld_map_ba_apply's staging
+  // the keyframes' descriptor rows (MapDesc): allocated by the first setter that fills them; lld_map_refresh_*'s staging
   lld_map_dev::MapDesc Z{}; char* d_desc = nullptr; size_t desc_bytes = 0; lld_map_dev::RowPool kdesc, kldesc;
-  char* h_rf = nullptr; size_t h_rf_bytes = 0; char* d_rf = nullptr; size_t d_rf_bytes = 0;
+  lld_map_dev::Staging rf;
   bool cov_lds_set = false;                 // map_covis_query_kernel was granted its 64 KB of dynamic LDS
   std::vector<uint32_t> stamp_pt, stamp_kf, stamp_ln; uint32_t epoch = 0;
-  // the staging of lld_map_set_*: pinned block, device block, the event of the last copy
-  char* h_up = nullptr; size_t h_up_bytes = 0; char* d_up = nullptr; size_t d_up_bytes = 0; hipEvent_t uploaded = nullptr; bool upload_pending = false;
+  // the staging of lld_map_set_*, the event of the last copy out of its pinned block
+  lld_map_dev::Staging up; hipEvent_t uploaded = nullptr; bool upload_pending = false;
   char* h_down = nullptr;
   unsigned long long serial = 0;            // counts lld_frame_track_update_local_map calls: the lists in the tables are the last one's
   bool poisoned = false;                    // a HIP failure after the host bookkeeping of a set call moved: host copy and device tables may differ

@@ -1,7 +1,9 @@
 // lld_normal_depth.h — MapPoint::UpdateNormalAndDepth (src/MapPoint.cc:330-371) for the kernels that run it: the term of one observation, the
 // camera centre it reads and the final write, once.  lm_normal_wave (lld_landmark.hip: a wavefront per point) and the packed kernels of
 // lld_map_correct.hip (several points per wavefront) differ only in how the terms reach the lane that sums them; the sum itself is
-// `normal = normal + term` in observation order in all of them.  The numerics are those include/lld_amd.h states for lld_mappoint_refresh.
+// `normal = normal + term` in observation order in all of them.  The kernels on the resident map (ap_refresh_kernel of lld_map_apply.hip,
+// rf_check_kernel / rf_normal_kernel of lld_map_refresh.hip) sum rows in which some entries do not count (add_in_order) and look the
+// reference keyframe's level up in the map's own rows (ref_level).  The numerics are those include/lld_amd.h states for lld_mappoint_refresh.
 // Device only.  The including file is compiled under `#pragma clang fp contract(off)`: every operation here is one IEEE operation.
 #ifndef LLD_NORMAL_DEPTH_H
 #define LLD_NORMAL_DEPTH_H
@@ -9,6 +11,8 @@
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
+
+#include "lld_wave.h"
 
 namespace lld_nd {
 
@@ -35,6 +39,30 @@ __device__ __forceinline__ void term(float px, float py, float pz, const float* 
   const float dx = px - ow[0], dy = py - ow[1], dz = pz - ow[2];
   const float inv = (float)(1.0 / norm3(dx, dy, dz));
   tx = dx * inv; ty = dy * inv; tz = dz * inv;
+}
+
+// One step of the sum over a row that aligned groups of W lanes walk W entries at a time: lane l of the group holds the term of entry
+// j0 + l and keep = 1, or keep = 0 for an entry that does not count (erased, or past the row's end).  Every lane of the group adds the kept
+// terms in lane order: normal = normal + normali/cv::norm(normali), the same sequence of additions in every lane.
+template <int W>
+__device__ __forceinline__ void add_in_order(int keep, float tx, float ty, float tz, float& nx, float& ny, float& nz) {
+  for (int l = 0; l < W; l++) {
+    const int k = lld_wave::group_bcast<W>(keep, l);
+    const float ax = lld_wave::group_bcast<W>(tx, l), ay = lld_wave::group_bcast<W>(ty, l), az = lld_wave::group_bcast<W>(tz, l);
+    if (k) { nx = nx + ax; ny = ny + ay; nz = nz + az; }
+  }
+}
+
+// The level of the final write: pRefKF->mvKeysUn[observations[pRefKF]].octave (:361), or -1 when the tables do not hold it.  ref is the
+// reference keyframe's slot, ref_at its position in the point's row of `len` entries (>= len: it is no observer, and operator[] inserts 0),
+// idx_row the keypoint indices parallel to that row.  k_oct / oct_pool: the keyframes' octave rows; k_feat: the keyframe's features were set.
+__device__ __forceinline__ int ref_level(int ref, int ref_at, int len, const int32_t* idx_row, const int2* k_oct, const int32_t* oct_pool,
+                                         const uint8_t* k_feat, int n_levels) {
+  const int idx = ref_at < len ? idx_row[ref_at] : 0;
+  const int2 orow = k_oct[ref];
+  if (!k_feat[ref] || idx >= orow.y) return -1;
+  const int level = oct_pool[orow.x + idx];
+  return level >= 0 && level < n_levels ? level : -1;
 }
 
 struct Out { float* normal; float* min_distance; float* max_distance; };

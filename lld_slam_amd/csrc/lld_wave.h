@@ -11,7 +11,7 @@
 //                                             (xor 32, 16, 8, 7, 2, 1) and so their own addition order
 //   the segmented __shfl_down sums (lld_ba_points.h, lld_ba_schur.h)                      runs of lanes of varying length, not aligned groups
 //   the partial `xor 16, xor 32` column sums (lld_ba_solve.h, lld_ba_chol_sparse.h, lld_posegraph.hip pg dense solve)   two steps, not a full group
-//   every (value, index) and best/second merge (lld_match.hip, lld_line_match.hip, lld_landmark.hip lm_line_*, lld_bow_merge.h bow_match_node, the top-2 merge of
+//   every (value, index) and best/second merge (lld_match.hip, lld_line_match.hip, lld_distinctive.h line, lld_bow_merge.h bow_match_node, the top-2 merge of
 //                                             orb_search_kernel)   two coupled values per step
 //   the ballot rankings and counts (lld_frame_finish.hip, lld_frame_lines.hip, lld_new_points.hip np_compact, lld_covisibility.hip,
 //                                             lld_landmark.hip compact_kept, lld_orb_extract.hip, lld_ba_control.h)   order-preserving ranks from lane masks
@@ -72,6 +72,10 @@ __device__ __forceinline__ T max(T x) {
 // (A move, no arithmetic: held by the packing test of tests/test_gpu_map_correct.py through mc_normal<8>.)
 template <int W, class T>
 __device__ __forceinline__ T group_bcast(T x, int l) { return __shfl(x, l, W); }
+
+// v of lane l of the wavefront, l the same in every lane (it goes through a scalar register): a v_readlane, not a shuffle
+__device__ __forceinline__ uint32_t bcast(uint32_t v, int l) { return (uint32_t)__builtin_amdgcn_readlane((int)v, l); }
+__device__ __forceinline__ float bcastf(float v, int l) { return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), l)); }
 
 // Sum of x over the workgroup (double or int); every lane returns it.  All blockDim.x lanes (a multiple of 64) call it; lds holds
 // blockDim.x / 64 values.  Barriers: one before the wavefront totals are written (lds may still be read from an earlier call) and one after,

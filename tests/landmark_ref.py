@@ -236,6 +236,38 @@ def make_line_scene(seed, n_lines=100, n_kf=20, dim=72, scaled=False, counts=Non
                 bad=(rng.random(n_lines) < p_bad).astype(np.uint8), dim=dim)
 
 
+def tie_rows(N, t, seed=0, dim=None):
+    """N descriptor rows whose winner is row t by the tie rule alone: rows t .. N-1 are identical (more than N / 2 of them, so each has the
+    median 0) and rows 0 .. t-1 are distinct from each other and far from the cluster.  An outlier is at distance 0 from itself alone and the
+    cluster is more than half of the rows, so its median is its distance to the cluster: positive.  The first of the equal medians wins.
+    dim = None: 8 uint32 words; row s < t is the cluster's complement with s xor-ed into word 0, so it lies 256 - popcount(s) bits from
+    the cluster and only popcount(s ^ s') bits from another outlier s'.  Else dim floats; row s < t is the cluster with 1000 (s + 1) added
+    to coordinate s % dim, at least 1000 from the cluster and from every other outlier."""
+    assert 0 <= t and 2 * (N - t) > N
+    rng = np.random.default_rng(seed)
+    if dim is None:
+        cluster = rng.integers(0, 2 ** 32, 8, dtype=np.uint64).astype(np.uint32)
+        rows = np.tile(cluster, (N, 1))
+        rows[:t] = ~cluster
+        rows[:t, 0] ^= np.arange(t, dtype=np.uint32)
+    else:
+        rows = np.tile(rng.normal(0, 40, dim).astype(f32), (N, 1))
+        for s in range(t):
+            rows[s, s % dim] += f32(1000 * (s + 1))
+    return rows
+
+
+def tie_scene(cases, first_bad, dim=None):
+    """One landmark per (N, t) of `cases`, its N observers keyframes 0 .. N-1 in that order with the rows of tie_rows(N, t).  first_bad:
+    keyframe 0 is bad, so the first kept position of every list is 1.  Only the descriptor part's inputs."""
+    n_kf = max(N for N, _ in cases)
+    kf_bad = np.zeros(n_kf, np.uint8); kf_bad[0] = 1 if first_bad else 0
+    return dict(obs_start=np.concatenate([[0], np.cumsum([N for N, _ in cases])]).astype(np.int32),
+                obs_kf=np.concatenate([np.arange(N) for N, _ in cases]).astype(np.int32),
+                obs_desc=np.concatenate([tie_rows(N, t, 100 + i, dim) for i, (N, t) in enumerate(cases)]), kf_bad=kf_bad,
+                bad=np.zeros(len(cases), np.uint8), **({} if dim is None else dict(dim=dim)))
+
+
 def subset(sc, order, lines=False):
     """The same landmarks in another batch order (the keyframe table unchanged)."""
     order = np.asarray(order)

@@ -173,6 +173,53 @@ def test_one_line_and_the_largest_dim(gpu_ctx):
     check_lines(run_lines(gpu_ctx, sc), L.distinctive_lines_ref(sc))
 
 
+# Which row wins among equal medians, and at which lane: random 256-bit rows rarely tie, so these scenes make every candidate tie.
+def run_descriptors(ctx, sc):
+    return refresh_map_points(ctx, sc["obs_start"], sc["obs_kf"], sc["bad"], obs_desc=sc["obs_desc"], kf_bad=sc["kf_bad"], flags=DESCRIPTOR)
+
+
+def check_descriptors(got, exp):
+    assert np.array_equal(got.updated, exp["updated"]) and np.array_equal(got.desc, exp["desc"])
+    assert np.array_equal(got.best_obs, exp["best_obs"]) and np.array_equal(got.best_median, exp["best_median"])
+
+
+def test_identical_rows_elect_the_first_kept(gpu_ctx):
+    # lists of N observers whose first keyframe is bad and whose rows are all the same: every median is 0, list position 1 wins
+    sizes = [2, 3, 64, 65, 66, 257, MAX_OBS]              # kept: one less - both paths at their ends, a lane's second row, the limit
+    sc = L.tie_scene([(N, 0) for N in sizes], first_bad=True)
+    assert kept_counts(sc) == [N - 1 for N in sizes]
+    exp = L.refresh_map_points_ref(sc, DESCRIPTOR)
+    assert np.all(exp["best_obs"] == 1) and np.all(exp["best_median"] == 0) and np.all(exp["updated"] == DESCRIPTOR)
+    check_descriptors(run_descriptors(gpu_ctx, sc), exp)
+
+
+# (N, t): the wavefront path; the workgroup path at its first size, then at the limit: the first lane of the second wavefront, the last lane,
+# a lane's second row, and a row inside the second trip
+TIE_POINTS = [(64, 31), (65, 32), (MAX_OBS, 64), (MAX_OBS, 255), (MAX_OBS, 256), (MAX_OBS, 300)]
+
+
+@pytest.mark.parametrize("N,t", TIE_POINTS)
+def test_the_first_of_equal_medians_wins_at_row(gpu_ctx, N, t):
+    sc = L.tie_scene([(N, t)], first_bad=False)
+    exp = L.refresh_map_points_ref(sc, DESCRIPTOR)
+    assert exp["best_obs"].tolist() == [t] and exp["best_median"].tolist() == [0]          # the scene does what it claims
+    assert L.select_from_table(L.hamming_table(sc["obs_desc"]), False)[2][:t].min() > 0    # ... and every outlier's median is positive
+    check_descriptors(run_descriptors(gpu_ctx, sc), exp)
+
+
+@pytest.mark.parametrize("dim", [33, MAX_LINE_DIM])
+def test_line_ties(gpu_ctx, dim):
+    sc = L.tie_scene([(2, 0), (MAX_LINE_OBS, 0)], first_bad=True, dim=dim)
+    exp = L.distinctive_lines_ref(sc)
+    assert np.all(exp["best_obs"] == 1) and np.all(exp["best_median"] == 0) and np.all(exp["updated"] == DESCRIPTOR)
+    check_lines(run_lines(gpu_ctx, sc), exp, "identical rows")
+    sc = L.tie_scene([(MAX_LINE_OBS, 31)], first_bad=False, dim=dim)
+    exp = L.distinctive_lines_ref(sc)
+    assert exp["best_obs"].tolist() == [31] and exp["best_median"].tolist() == [0]
+    assert L.select_from_table(L.l2_table(sc["obs_desc"]), True)[2][:31].min() > 0
+    check_lines(run_lines(gpu_ctx, sc), exp, "row 31")
+
+
 def status_of(fn):
     with pytest.raises(LandmarkError) as e:
         fn()

@@ -173,6 +173,61 @@ def test_query_list_lengths(gpu_ctx, n):
         refresh_points_checked(gpu_ctx, dm, m, slots, BOTH, "%d queries" % n)
 
 
+# ---------------------------------------------------------------------------------------------------------------- 2b. ties
+def tie_map(point_cases, line_cases, first_bad, dim=S.LINE_DIM):
+    """Point slot i / line slot i has the observers keyframes 0 .. N-1 in slot order, for (N, t) = the i-th case, and their descriptor rows are
+    landmark_ref.tie_rows(N, t): row t wins by the tie rule alone.  first_bad: keyframe 0 is bad, so every first kept position is 1."""
+    sc = S.Scene()
+    for s in range(max(N for N, _ in list(point_cases) + list(line_cases))):
+        sc.kf(s, s + 1, [i for i, (N, _) in enumerate(point_cases) if s < N], [i for i, (N, _) in enumerate(line_cases) if s < N], bad=int(first_bad and s == 0))
+    for i in range(len(point_cases)): sc.pt(i)
+    for i in range(len(line_cases)): sc.ln(i)
+    m = sc.link()
+    rows = [R.LM.tie_rows(N, t, i) for i, (N, t) in enumerate(point_cases)], [R.LM.tie_rows(N, t, i, dim) for i, (N, t) in enumerate(line_cases)]
+    for s, k in m["keyframes"].items():
+        k["desc"] = np.array([rows[0][i][s] for i in k["points"]], np.uint32).reshape(-1, 8)
+        k["ldesc"] = np.array([rows[1][i][s] for i in k["lines"]], np.float32).reshape(-1, dim)
+    return m
+
+
+def test_identical_rows_elect_the_first_kept(gpu_ctx):
+    sizes = [2, 3, 64, 65, 66, 257, RS.MAX_OBS]          # stored rows; kept: one less - both kernels at their ends, a lane's second row, the limit
+    m = tie_map([(N, 0) for N in sizes], [], first_bad=True)
+    slots = list(range(len(sizes)))
+    exp = R.refresh_points(m, slots, R.DESCRIPTOR)
+    assert np.all(exp["best_obs"] == 1) and np.all(exp["best_median"] == 0) and np.all(exp["updated"] == R.DESCRIPTOR)
+    with fresh(gpu_ctx, m) as dm:
+        refresh_points_checked(gpu_ctx, dm, m, slots, R.DESCRIPTOR, "identical rows")
+
+
+# (N, t): rf_point_wave; rf_point_block at its first size, then at the limit: the first lane of the second wavefront, the last lane, a lane's
+# second row, and a row inside the second trip
+@pytest.mark.parametrize("N,t", [(64, 31), (65, 32), (RS.MAX_OBS, 64), (RS.MAX_OBS, 255), (RS.MAX_OBS, 256), (RS.MAX_OBS, 300)])
+def test_the_first_of_equal_medians_wins_at_row(gpu_ctx, N, t):
+    m = tie_map([(N, t)], [], first_bad=False)
+    exp = R.refresh_points(m, [0], R.DESCRIPTOR)
+    assert exp["best_obs"].tolist() == [t] and exp["best_median"].tolist() == [0]                          # the scene does what it claims
+    sc, _, _ = R.gather_points(m, [0], R.DESCRIPTOR, None)
+    assert R.LM.select_from_table(R.LM.hamming_table(sc["obs_desc"]), False)[2][:t].min() > 0              # ... and every outlier's median is positive
+    with fresh(gpu_ctx, m) as dm:
+        refresh_points_checked(gpu_ctx, dm, m, [0], R.DESCRIPTOR, "row %d of %d" % (t, N))
+
+
+@pytest.mark.parametrize("dim", [33, 128])
+def test_line_ties(gpu_ctx, dim):
+    m = tie_map([], [(2, 0), (RS.MAX_LINE_OBS, 0)], first_bad=True, dim=dim)
+    exp = R.refresh_lines(m, [0, 1], dim)
+    assert np.all(exp["best_obs"] == 1) and np.all(exp["best_median"] == 0) and np.all(exp["updated"] == R.DESCRIPTOR)
+    with fresh(gpu_ctx, m, dim) as dm:
+        refresh_lines_checked(gpu_ctx, dm, m, [0, 1], dim, "identical line rows, dim %d" % dim)
+    m = tie_map([], [(RS.MAX_LINE_OBS, 31)], first_bad=False, dim=dim)
+    exp = R.refresh_lines(m, [0], dim)
+    assert exp["best_obs"].tolist() == [31] and exp["best_median"].tolist() == [0]
+    assert R.LM.select_from_table(R.LM.l2_table(R.LM.tie_rows(RS.MAX_LINE_OBS, 31, 0, dim)), True)[2][:31].min() > 0
+    with fresh(gpu_ctx, m, dim) as dm:
+        refresh_lines_checked(gpu_ctx, dm, m, [0], dim, "line row 31, dim %d" % dim)
+
+
 # ---------------------------------------------------------------------------------------------------------------- 3. guards
 def guard_scene():
     sc = S.Scene()
