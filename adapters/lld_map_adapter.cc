@@ -139,6 +139,96 @@ int MapOnDevice::ComputeDistinctiveDescriptors(const std::vector<MapLine*>& vpMa
   return written;
 }
 
+int MapOnDevice::Fuse(KeyFrame* pKF, const std::vector<MapPoint*>& vpMapPoints, float th, KeyFrame* pSourceKF) {
+  if (!refresh_) throw std::runtime_error("MapOnDevice::Fuse: EnableRefresh before Upload");
+  if (KeyFrameOf(slot_of(pKF, limits_.max_keyframes)) != pKF) throw std::runtime_error("MapOnDevice::Fuse: a keyframe the map does not hold");
+  const size_t n = vpMapPoints.size();
+  if (!n) return 0;
+  std::vector<int32_t> slots(n, -1);
+  for (size_t i = 0; i < n; i++) {
+    MapPoint* pMP = vpMapPoints[i];
+    if (!pMP) continue;
+    if (PointOf(slot_of(pMP, limits_.max_points)) != pMP) throw std::runtime_error("MapOnDevice::Fuse: a point the map does not hold");
+    slots[i] = (int32_t)pMP->mnId;
+  }
+  lld_map_fuse_in in; std::memset(&in, 0, sizeof in);
+  in.target = (int32_t)pKF->mnId; in.n_points = (int32_t)n; in.th = th;
+  in.point_slot = pSourceKF ? nullptr : slots.data(); in.source_keyframe = pSourceKF ? slot_of(pSourceKF, limits_.max_keyframes) : -1;
+  const lld_slam::Mat Rcw = pKF->GetRotation(), tcw = pKF->GetTranslation(), Ow = pKF->GetCameraCenter();
+  for (int r = 0; r < 3; r++) {
+    for (int c = 0; c < 3; c++) in.view.Rcw[3 * r + c] = Rcw.at<float>(r, c);
+    in.view.tcw[r] = tcw.at<float>(r); in.view.Ow[r] = Ow.at<float>(r);
+  }
+  in.view.fx = pKF->fx; in.view.fy = pKF->fy; in.view.cx = pKF->cx; in.view.cy = pKF->cy; in.view.bf = pKF->mbf;
+  in.view.min_x = (float)pKF->mnMinX; in.view.max_x = (float)pKF->mnMaxX; in.view.min_y = (float)pKF->mnMinY; in.view.max_y = (float)pKF->mnMaxY;
+  in.view.log_scale_factor = pKF->mfLogScaleFactor; in.view.n_levels = pKF->mnScaleLevels;
+  in.grid_min_x = (float)pKF->mnMinX; in.grid_min_y = (float)pKF->mnMinY; in.grid_width_inv = pKF->mfGridElementWidthInv; in.grid_height_inv = pKF->mfGridElementHeightInv;
+  in.grid_cols = 64; in.grid_rows = 48;                                  // FRAME_GRID_COLS, FRAME_GRID_ROWS (Frame.h:43-44)
+  in.n_levels = pKF->mnScaleLevels; in.level_scale = pKF->mvScaleFactors.data(); in.level_inv_sigma2 = pKF->mvInvLevelSigma2.data();
+  std::vector<int32_t> match(n), other(n), surv(n); std::vector<uint8_t> action(n);
+  lld_map_fuse_out out; std::memset(&out, 0, sizeof out);
+  out.match = match.data(); out.action = action.data(); out.other = other.data(); out.survivor = surv.data(); out.survivor_capacity = (int32_t)n;
+  check(lld_map_fuse(m_, &in, &out), "lld_map_fuse");
+  // the objects follow, in list order (src/ORBmatcher.cc:934-954)
+  for (size_t i = 0; i < n; i++) {
+    MapPoint* pMP = vpMapPoints[i];
+    switch (action[i]) {
+      case LLD_MAP_FUSE_ADDED: pMP->AddObservation(pKF, (size_t)match[i]); pKF->AddMapPoint(pMP, (size_t)match[i]); break;
+      case LLD_MAP_FUSE_CANDIDATE_REPLACED: pMP->Replace(PointOf(other[i])); break;
+      case LLD_MAP_FUSE_HOLDER_REPLACED: PointOf(other[i])->Replace(pMP); break;
+      default: break;
+    }
+  }
+  if (out.n_survivors > 0) {                                             // ComputeDistinctiveDescriptors of MapPoint::Replace (MapPoint.cc:212): the map holds it
+    std::vector<uint32_t> desc(8 * (size_t)out.n_survivors);
+    check(lld_map_download_points(m_, out.n_survivors, surv.data(), nullptr, nullptr, nullptr, nullptr, desc.data(), nullptr), "lld_map_download_points");
+    for (int32_t k = 0; k < out.n_survivors; k++) {
+      lld_slam::MatU8 d(1, 32);
+      std::memcpy(d.ptr<unsigned char>(), &desc[8 * (size_t)k], 32);
+      PointOf(surv[k])->mDescriptor = d;
+    }
+  }
+  return out.n_fused;
+}
+
+int MapOnDevice::SearchInNeighbors(KeyFrame* pKF) {
+  const std::vector<KeyFrame*> vpNeighKFs = pKF->GetBestCovisibilityKeyFrames(10);
+  std::vector<KeyFrame*> vpTargetKFs;
+  for (size_t i = 0; i < vpNeighKFs.size(); i++) {                        // :463-480
+    KeyFrame* pKFi = vpNeighKFs[i];
+    if (pKFi->isBad() || pKFi->mnFuseTargetForKF == pKF->mnId) continue;
+    vpTargetKFs.push_back(pKFi);
+    pKFi->mnFuseTargetForKF = pKF->mnId;
+    const std::vector<KeyFrame*> vpSecondNeighKFs = pKFi->GetBestCovisibilityKeyFrames(5);
+    for (size_t j = 0; j < vpSecondNeighKFs.size(); j++) {
+      KeyFrame* pKFi2 = vpSecondNeighKFs[j];
+      if (pKFi2->isBad() || pKFi2->mnFuseTargetForKF == pKF->mnId || pKFi2->mnId == pKF->mnId) continue;
+      vpTargetKFs.push_back(pKFi2);
+    }
+  }
+  int n = 0;
+  std::vector<MapPoint*> vpMapPointMatches = pKF->GetMapPointMatches();
+  for (size_t i = 0; i < vpTargetKFs.size(); i++) n += Fuse(vpTargetKFs[i], vpMapPointMatches, 3.0f, i == 0 ? pKF : nullptr);      // :486-491
+  std::vector<MapPoint*> vpFuseCandidates;                               // :494-513
+  for (size_t i = 0; i < vpTargetKFs.size(); i++) {
+    const std::vector<MapPoint*> vpMapPointsKFi = vpTargetKFs[i]->GetMapPointMatches();
+    for (size_t j = 0; j < vpMapPointsKFi.size(); j++) {
+      MapPoint* pMP = vpMapPointsKFi[j];
+      if (!pMP || pMP->isBad() || pMP->mnFuseCandidateForKF == pKF->mnId) continue;
+      pMP->mnFuseCandidateForKF = pKF->mnId;
+      vpFuseCandidates.push_back(pMP);
+    }
+  }
+  n += Fuse(pKF, vpFuseCandidates, 3.0f);                                // :515
+  vpMapPointMatches = pKF->GetMapPointMatches();                         // :519-531
+  std::vector<MapPoint*> live;
+  for (size_t i = 0; i < vpMapPointMatches.size(); i++)
+    if (vpMapPointMatches[i] && !vpMapPointMatches[i]->isBad() && std::find(live.begin(), live.end(), vpMapPointMatches[i]) == live.end()) live.push_back(vpMapPointMatches[i]);
+  RefreshMapPoints(live, LLD_LANDMARK_DESCRIPTOR | LLD_LANDMARK_NORMAL_DEPTH);
+  UpdateConnections(std::vector<KeyFrame*>(1, pKF));                     // :534
+  return n;
+}
+
 void MapOnDevice::UpdateKeyFrames(const std::vector<KeyFrame*>& keyframes) {
   const size_t n = keyframes.size();
   if (!n) return;

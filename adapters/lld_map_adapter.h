@@ -83,6 +83,22 @@ class MapOnDevice {
   // MapLine::ComputeDistinctiveDescriptors for the listed lines, likewise; returns the number of lines written.
   int ComputeDistinctiveDescriptors(const std::vector<lld_slam::MapLine*>& vpMapLines);
 
+  // ---- ORBmatcher::Fuse and LocalMapping::SearchInNeighbors on the mirrored map (lld_map_fuse): no gather, nothing pushed back
+  // (EnableRefresh before the first Upload: the search reads the keyframes' keypoints, octaves and descriptors.)
+  // int ORBmatcher::Fuse(KeyFrame *pKF, const vector<MapPoint *> &vpMapPoints, const float th) as lld_adapter::ORBmatcher::Fuse
+  // (lld_matcher_adapter.h) makes it, in ONE device call: the search on the map's rows, the add / Replace bookkeeping on the map's rows, the
+  // survivors' descriptors.  The objects then follow from the call's action / other, in list order: AddObservation + AddMapPoint, or
+  // MapPoint::Replace in the direction the call took (mnFound / mnVisible travel inside Replace), and the survivors' mDescriptor is read
+  // back from the map.  pKF, the listed points and the points pKF holds must be current in the map; a NULL entry is a NULL entry.  With
+  // pSourceKF the candidates are that keyframe's point row as the MAP holds it - vpMapPoints must be its GetMapPointMatches() - and no
+  // list travels.  Returns nFused.
+  int Fuse(lld_slam::KeyFrame* pKF, const std::vector<lld_slam::MapPoint*>& vpMapPoints, float th = 3.0f, lld_slam::KeyFrame* pSourceKF = nullptr);
+  // LocalMapping::SearchInNeighbors (src/LocalMapping.cc:455-535, nn = 10) for pKF: the target list with the mnFuseTargetForKF marks, one
+  // Fuse per target with pKF's matches (the first as pKF's row in the map, the later ones as the list copied before the first, as the
+  // reference holds it: a Replace may have changed the row meanwhile), the candidate list with the mnFuseCandidateForKF marks, one Fuse into
+  // pKF, then RefreshMapPoints over pKF's matches and UpdateConnections({pKF}).  Returns the sum of the Fuse calls' return values.
+  int SearchInNeighbors(lld_slam::KeyFrame* pKF);
+
   // slot -> object (NULL: never sent)
   lld_slam::KeyFrame* KeyFrameOf(int slot) const { return slot >= 0 && slot < (int)kf_.size() ? kf_[slot] : nullptr; }
   lld_slam::MapPoint* PointOf(int slot) const { return slot >= 0 && slot < (int)pt_.size() ? pt_[slot] : nullptr; }

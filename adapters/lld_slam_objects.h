@@ -96,6 +96,7 @@ class KeyFrame {
   unsigned long mnId = 0;
   unsigned long mnBALocalForKF = 0, mnBAFixedForKF = 0;            // KeyFrame.h: visit marks of LocalBundleAdjustment
   unsigned long mnTrackReferenceForFrame = 0;                      // KeyFrame.h: the mark of Tracking::UpdateLocalKeyFrames (Tracking.cc:1773)
+  unsigned long mnFuseTargetForKF = 0;                             // KeyFrame.h: the mark of LocalMapping::SearchInNeighbors (LocalMapping.cc:469)
   float fx = 0, fy = 0, cx = 0, cy = 0, mbf = 0;
   Mat mK;                                                          // 3x3 CV_32F
   std::vector<KeyPoint> mvKeysUn;
@@ -257,6 +258,7 @@ class MapPoint {
   int mnTrackScaleLevel = 0;
   unsigned long mnLastFrameSeen = 0;
   unsigned long mnTrackReferenceForFrame = 0;                      // the mark of Tracking::UpdateLocalPoints (Tracking.cc:1700)
+  unsigned long mnFuseCandidateForKF = 0;                          // MapPoint.h: the mark of LocalMapping::SearchInNeighbors (LocalMapping.cc:510)
 
   // variables used by loop closing (MapPoint.h:103-107)
   unsigned long mnCorrectedByKF = 0, mnCorrectedReference = 0;

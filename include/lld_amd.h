@@ -2993,6 +2993,89 @@ int  lld_map_download_points(lld_map* map, int32_t n, const int32_t* slot, float
                              uint32_t* desc, uint8_t* state);
 int  lld_map_download_lines(lld_map* map, int32_t n, const int32_t* slot, float* desc, uint8_t* bad);
 
+/* ------------------------------------------------------------------ duplicate map points fused on the resident map
+ * lld_map_fuse: one ORBmatcher::Fuse(pKF, vpMapPoints, th) (src/ORBmatcher.cc:825-958) on the map's tables, as LocalMapping::SearchInNeighbors
+ * (src/LocalMapping.cc:455-535) calls it 10-30 times per keyframe.  Nothing is gathered: the target keyframe's keypoints, octaves and
+ * descriptors are its rows of lld_map_set_keyframe_features / _keypoints / _descriptors, the candidates' positions, normals, distances,
+ * descriptors, flags and observation rows are the points' rows, and the holders are the target's point row.  Two phases.
+ *
+ * Search (device).  Candidate i is skipped (:846-850) when its slot is -1, was never set, is bad, or holds the target in its observation
+ * row.  Otherwise it is projected with the float operations of lld_orb_fuse_search (the pose, centre, intrinsics and bounds travel in
+ * `view` and are NOT rebuilt from the map's stored pose, so that both routes see the same floats), and every keypoint k of the target is a
+ * candidate match under the rules of LLD_ORB_CAND_GRID with the gates LEVEL | CHI2 above: |dx| < r && |dy| < r with r = th *
+ * level_scale[level]; the keypoint's PosInGrid cell (rounded) lies inside the grid and inside GetFeaturesInArea's cell range of the window;
+ * octave in [level - 1, level] (and inside the level tables); the 7.8 / 5.99 chi2 gate on level_inv_sigma2; DescriptorDistance against
+ * the point's descriptor row.  match[i] = the FIRST minimum in GetFeaturesInArea's order (column outer, row inner, index within the cell)
+ * if its distance is <= 50, else -1: what lld_orb_fuse_search returns for the same inputs, bit for bit.
+ *
+ * Walk (host, on the copies of the rows the map keeps, in list order over the matched candidates; :934-956 as adapters/
+ * lld_matcher_adapter.cc restates it behind a finished search).  The candidate is tested again: bad by now, or attached to the target by an
+ * earlier step -> action 5.  The holder is the target's point row at match[i]:
+ *   none              AddObservation + AddMapPoint: the candidate's observation and index rows grow by (target, match[i]), its
+ *                     Observations() by 2 if the keypoint's uR >= 0, else by 1, the target's entry is set.  action 1.
+ *   bad or never set  counted, nothing done.  action 4.
+ *   else              Observations(holder) > Observations(candidate): the candidate is replaced by the holder (action 2), else the holder by
+ *                     the candidate (action 3; a tie replaces the holder).  MapPoint::Replace (src/MapPoint.cc:176-220) row-wise: the same slot
+ *                     returns; the loser's entries in stored order - the survivor absent from that keyframe: its entry there becomes the
+ *                     survivor, the survivor gains the observation (+2 / +1 by that keyframe's uR at that index); present: the entry is
+ *                     cleared by index; the loser becomes bad with empty rows, its Observations() stays what it was; mpRefKF untouched.
+ * A new observation enters a row in front of the first stored observer whose order key (lld_map_set_keyframes) is greater than the new
+ * keyframe's: a row stored in std::map order stays in it.  An index beyond a keyframe's rows writes nothing there and counts as monocular.
+ * mnFound / mnVisible are no tables of the map: the caller adds the loser's to the survivor's from action / other (MapPoint.cc:210-211).
+ * Then one upload carries every changed row (through the pools' one placement machinery: in place, to the tail, or a repack) and the
+ * changed counts and flags, and behind it on the stream ComputeDistinctiveDescriptors (MapPoint.cc:212) runs for every survivor, once, on
+ * the rows the call leaves, with lld_map_refresh_points' kernels and guards.  QUIRK kept apart from the reference: a survivor that a later
+ * step of the same call makes bad keeps the descriptor it had (the reference recomputed it before; a bad point's descriptor is never read).
+ * survivor[]: the distinct survivors in walk order, n_survivors of them.
+ *
+ * Refused before anything is queued, map unchanged.  LLD_ERR_INVALID: a NULL argument or output array; a target out of range, never set, or
+ * without feature, keypoint and descriptor rows of its point row's length; n_points < 0; both or neither of point_slot / source_keyframe
+ * (with source_keyframe >= 0: a keyframe never set, or n_points other than its point row's length); a slot outside [-1, max_points);
+ * th, fx or fy not > 0; n_levels outside [1, LLD_ORB_MAX_LEVELS] or other than view.n_levels; a NULL level table; grid_cols / grid_rows < 1;
+ * a candidate or holder of the walk whose index row is not of its observation row's length; more survivors than survivor_capacity (then
+ * n_survivors holds the number needed; the search has run by then, so a caller that retries pays for it twice - a capacity of n_points
+ * never meets this).  LLD_ERR_UNSUPPORTED: a live total of a pool beyond its limit, a survivor row longer than
+ * LLD_LANDMARK_MAX_OBS, a target of more than 2^24 keypoints or a grid of more than 2^24 cells.  LLD_ERR_HIP: a poisoned map.
+ * n_points = 0 is LLD_OK and touches nothing.  A slot may be named twice: the second occurrence meets the re-test.
+ * A call that changed anything counts as one mutation: a staged BA window is stale.  A HIP failure behind the first queued change, or a
+ * row length on the device that is not the host's, poisons the map.  phase_ms (NULL or [4]): HIP-event times of the search's upload and
+ * kernels, the host clock over walk + row upload + refresh, the HIP-event time of the search's download. */
+typedef struct {
+  int32_t target;                   /* keyframe slot of pKF                             */
+  int32_t n_points;                 /* candidates, in vpMapPoints order                 */
+  const int32_t* point_slot;        /* [n_points], -1 = a NULL entry; NULL with source_keyframe >= 0 */
+  int32_t source_keyframe;          /* -1, or: the candidates are this keyframe's point row as the map holds it */
+  float th;                         /* 3.0 in SearchInNeighbors                         */
+  lld_frame_view view;              /* pKF's pose, Ow, intrinsics, bounds, log scale factor, levels */
+  float grid_min_x, grid_min_y, grid_width_inv, grid_height_inv;
+  int32_t grid_cols, grid_rows;
+  int32_t n_levels, reserved;
+  const float* level_scale;         /* [n_levels] mvScaleFactors                        */
+  const float* level_inv_sigma2;    /* [n_levels] mvInvLevelSigma2                      */
+} lld_map_fuse_in;
+typedef struct {
+  int32_t n_fused;                  /* nFused (:956)                                    */
+  int32_t n_added, n_replaced;      /* actions 1; actions 2 and 3                       */
+  int32_t reserved;
+  int32_t* match;                   /* [n_points] bestIdx or -1: the search alone       */
+  uint8_t* action;                  /* [n_points] 0 none, 1 added, 2 candidate replaced by holder, 3 holder replaced by candidate,
+                                       4 holder bad, 5 skipped by the walk's re-test    */
+  int32_t* other;                   /* [n_points] the holder's slot for 2 / 3 / 4, else -1 */
+  int32_t survivor_capacity, n_survivors;
+  int32_t* survivor;                /* [survivor_capacity]                              */
+  float*   phase_ms;                /* NULL or [4]                                      */
+} lld_map_fuse_out;
+#define LLD_MAP_FUSE_NONE 0
+#define LLD_MAP_FUSE_ADDED 1
+#define LLD_MAP_FUSE_CANDIDATE_REPLACED 2
+#define LLD_MAP_FUSE_HOLDER_REPLACED 3
+#define LLD_MAP_FUSE_HOLDER_BAD 4
+#define LLD_MAP_FUSE_SKIPPED 5
+int  lld_map_fuse(lld_map* map, const lld_map_fuse_in* in, lld_map_fuse_out* out);
+/* MapPoint::Observations() of point slots as the DEVICE holds it (0 before the first lld_map_set_observations_indexed): the twin of
+ * lld_map_download_points for the one fixed value it does not carry.  Refusals as there. */
+int  lld_map_download_point_counts(lld_map* map, int32_t n, const int32_t* slot, int32_t* n_obs);
+
 #if defined(__GNUC__)
 #pragma GCC visibility pop
 #endif

@@ -690,6 +690,35 @@ class DeviceMap {
     r.desc.resize(dim * n); r.bad.resize(n);
     return r;
   }
+  // ---- duplicate map points fused on the map's tables (lld_map_fuse): one ORBmatcher::Fuse(pKF, vpMapPoints, th)
+  struct Fused {                 // per candidate: match, action (LLD_MAP_FUSE_*), other; the distinct survivors in walk order
+    int32_t n_fused = 0, n_added = 0, n_replaced = 0;
+    std::vector<int32_t> match, other, survivor; std::vector<uint8_t> action; float phase_ms[4] = {0.f, 0.f, 0.f, 0.f};
+  };
+  // `in` carries the target, th, the view, the grid constants and the level tables; the candidates are point_slot (-1: a NULL entry) or, when
+  // source_keyframe >= 0, that keyframe's point row as the map holds it (n_points: its length)
+  Fused Fuse(lld_map_fuse_in in, const std::vector<int32_t>* point_slot, int32_t source_keyframe = -1, int32_t n_points = 0, bool timed = false) {
+    in.source_keyframe = source_keyframe;
+    in.point_slot = point_slot ? point_slot->data() : nullptr;
+    in.n_points = point_slot ? (int32_t)point_slot->size() : n_points;
+    const size_t n = in.n_points > 0 ? (size_t)in.n_points : 0;
+    Fused r;
+    r.match.assign(n + 1, -1); r.other.assign(n + 1, -1); r.action.assign(n + 1, 0); r.survivor.assign(n + 1, -1);
+    lld_map_fuse_out o{};
+    o.match = r.match.data(); o.action = r.action.data(); o.other = r.other.data(); o.survivor = r.survivor.data(); o.survivor_capacity = (int32_t)n;
+    o.phase_ms = timed ? r.phase_ms : nullptr;
+    check(lld_map_fuse(m_, &in, &o), "lld_map_fuse");
+    r.n_fused = o.n_fused; r.n_added = o.n_added; r.n_replaced = o.n_replaced;
+    r.match.resize(n); r.other.resize(n); r.action.resize(n); r.survivor.resize((size_t)o.n_survivors);
+    return r;
+  }
+  // lld_map_download_point_counts: MapPoint::Observations() of the slots as the device holds it
+  std::vector<int32_t> PointCounts(const std::vector<int32_t>& slot) const {
+    std::vector<int32_t> n(slot.size() + 1, 0);
+    check(lld_map_download_point_counts(m_, (int32_t)slot.size(), slot.data(), n.data()), "lld_map_download_point_counts");
+    n.resize(slot.size());
+    return n;
+  }
   const lld_map_limits& limits() const { return limits_; }
   lld_map* get() const { return m_; }
  private:

@@ -502,6 +502,29 @@ class MapRefreshLinesOut(C.Structure):
     _fields_ = [("desc", c_float_p), ("best_obs", c_int32_p), ("best_median", c_int32_p), ("updated", c_uint8_p), ("phase_ms", c_float_p)]
 
 
+class FrameViewStruct(C.Structure):
+    """lld_frame_view (orb_search.FrameView has the same layout; orb_search imports this module, so lld_map_fuse_in embeds this one)."""
+    _fields_ = [("Rcw", C.c_float * 9), ("tcw", C.c_float * 3), ("Ow", C.c_float * 3), ("fx", C.c_float), ("fy", C.c_float),
+                ("cx", C.c_float), ("cy", C.c_float), ("bf", C.c_float), ("min_x", C.c_float), ("max_x", C.c_float), ("min_y", C.c_float),
+                ("max_y", C.c_float), ("log_scale_factor", C.c_float), ("n_levels", C.c_int32)]
+
+
+class MapFuseIn(C.Structure):
+    """lld_map_fuse_in."""
+    _fields_ = [("target", C.c_int32), ("n_points", C.c_int32), ("point_slot", c_int32_p), ("source_keyframe", C.c_int32), ("th", C.c_float),
+                ("view", FrameViewStruct), ("grid_min_x", C.c_float), ("grid_min_y", C.c_float), ("grid_width_inv", C.c_float), ("grid_height_inv", C.c_float),
+                ("grid_cols", C.c_int32), ("grid_rows", C.c_int32), ("n_levels", C.c_int32), ("reserved", C.c_int32),
+                ("level_scale", c_float_p), ("level_inv_sigma2", c_float_p)]
+
+
+class MapFuseOut(C.Structure):
+    """lld_map_fuse_out."""
+    _fields_ = [("n_fused", C.c_int32), ("n_added", C.c_int32), ("n_replaced", C.c_int32), ("reserved", C.c_int32),
+                ("match", c_int32_p), ("action", c_uint8_p), ("other", c_int32_p), ("survivor_capacity", C.c_int32), ("n_survivors", C.c_int32),
+                ("survivor", c_int32_p), ("phase_ms", c_float_p)]
+
+
+MAP_FUSE_NONE, MAP_FUSE_ADDED, MAP_FUSE_CANDIDATE_REPLACED, MAP_FUSE_HOLDER_REPLACED, MAP_FUSE_HOLDER_BAD, MAP_FUSE_SKIPPED = 0, 1, 2, 3, 4, 5
 LANDMARK_DESCRIPTOR, LANDMARK_NORMAL_DEPTH = 1, 2
 LANDMARK_MAX_OBS, LANDMARK_MAX_LINE_OBS = 1024, 64
 ORB_MAX_LEVELS = 16
@@ -566,6 +589,7 @@ PRODUCT_SYMBOLS = [
     "lld_map_set_point_refs", "lld_map_ba_apply", "lld_map_download_rows",
     "lld_map_set_keyframe_descriptors", "lld_map_set_keyframe_line_descriptors", "lld_map_refresh_points", "lld_map_refresh_lines",
     "lld_map_download_points", "lld_map_download_lines",
+    "lld_map_fuse", "lld_map_download_point_counts",
 ]
 
 

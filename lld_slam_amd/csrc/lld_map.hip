@@ -440,7 +440,7 @@ int tables_reset(lld_map* m) {
   m->obs.reset(); m->child.reset(); m->kpt.reset(); m->kln.reset();
   m->mutations++; m->win.valid = false;
   if (m->d_ref) LLD_HIP_TRY(hipMemsetAsync(m->d_ref, 0xff, (size_t)m->lim.max_points * 4, st));
-  std::fill(m->kf_set.begin(), m->kf_set.end(), (uint8_t)0);
+  std::fill(m->kf_set.begin(), m->kf_set.end(), (uint8_t)0); std::fill(m->kf_key.begin(), m->kf_key.end(), 0ull);
   if (m->d_ext) {
     LLD_HIP_TRY(hipMemsetAsync(m->d_ext, 0, m->ext_bytes, st));
     m->idx.reset(); m->koct.reset(); m->kdep.reset();
@@ -592,7 +592,7 @@ int lld_map_create(lld_ctx* ctx, const lld_map_limits* L, lld_map** out) {
   m->ctx = ctx; m->lim = *L;
   const size_t nk = L->max_keyframes, np = L->max_points, nl = std::max(L->max_lines, 1), dim = L->line_dim, nlp = L->max_local_points, nll = std::max(L->max_local_lines, 1);
   m->obs.init((int)np, L->max_observations); m->child.init((int)nk, L->max_children); m->kpt.init((int)nk, L->max_kf_points); m->kln.init((int)nk, L->max_kf_lines);
-  m->stamp_pt.assign(np, 0); m->stamp_kf.assign(nk, 0); m->stamp_ln.assign(L->max_lines, 0); m->kf_set.assign(nk, 0);
+  m->stamp_pt.assign(np, 0); m->stamp_kf.assign(nk, 0); m->stamp_ln.assign(L->max_lines, 0); m->kf_set.assign(nk, 0); m->kf_key.assign(nk, 0);
   UploadBlock B;
   const auto ppos = B.take<float>(np, 3), pnrm = B.take<float>(np, 3), pmind = B.take<float>(np), pmaxd = B.take<float>(np); const auto pdesc = B.take<uint32_t>(np, 8);
   const auto pstate = B.take<uint8_t>(np); const auto pobs = B.take<int2>(np); const auto opool = B.take<int32_t>(m->obs.mirror.size());
@@ -645,7 +645,7 @@ void lld_map_destroy(lld_map* m) {
   if (m->d_ba) (void)hipFree(m->d_ba);
   if (m->d_ref) (void)hipFree(m->d_ref);
   if (m->d_desc) (void)hipFree(m->d_desc);
-  m->ba.release(); m->ap.release(); m->rf.release(); m->up.release();
+  m->ba.release(); m->ap.release(); m->rf.release(); m->fu.release(); m->up.release();
   if (m->h_down) (void)hipHostFree(m->h_down);
   if (m->uploaded) (void)hipEventDestroy(m->uploaded);
   delete m;
@@ -822,7 +822,7 @@ int lld_map_set_keyframes(lld_map* m, int32_t n, const int32_t* slot, const uint
   m->mutations++;
   B.stage(s, slot); B.stage(key, reinterpret_cast<const u64*>(order_key)); B.stage(b, bad); B.stage(par, parent); B.stage(cs, cov_start); B.stage(cv, cov);
   m->child.commit(B, Pc, n, slot, child_start, child); m->kpt.commit(B, Pp, n, slot, point_start, point); m->kln.commit(B, Pl, n, slot, line_start, line);
-  for (int i = 0; i < n; i++) m->kf_set[slot[i]] = 1;
+  for (int i = 0; i < n; i++) { m->kf_set[slot[i]] = 1; m->kf_key[slot[i]] = order_key[i]; }
   st = up_submit(m, B);
   hipStream_t stream = m->ctx->stream;
   if (!st) {

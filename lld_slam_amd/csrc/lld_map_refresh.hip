@@ -302,6 +302,20 @@ using lld_map_dev::slots_ok;
 
 }  // namespace
 
+int lld_map_dev::refresh_descriptors_queue(hipStream_t sm, const lld_map* m, const DescRefresh& R) {
+  if (R.n <= 0) return LLD_OK;
+  RfArgs A{};
+  A.n = R.n; A.want_desc = 1; A.has_ext = m->d_ext != nullptr; A.has_ba = m->d_ba != nullptr; A.has_desc = m->d_desc != nullptr;
+  A.slot = R.slot; A.list = R.list; A.p_ref = m->d_ref;
+  A.verdict = R.verdict; A.t_ref = R.t_ref; A.t_level = R.t_level; A.o_best = R.o_best; A.o_med = R.o_med; A.o_upd = R.o_upd;
+  const dim3 grouped((unsigned)std::min<size_t>(std::max<size_t>(((size_t)R.n + kGroups - 1) / kGroups, 1), 2048));
+  hipLaunchKernelGGL(rf_check_kernel, grouped, dim3(kBlock), 0, sm, m->D, m->X, m->Y, m->Z, A);
+  if (R.n_wave) hipLaunchKernelGGL(rf_point_wave, dim3(R.n_wave), dim3(kWave), 0, sm, m->D, m->X, m->Z, A, 0);
+  if (R.n - R.n_wave) hipLaunchKernelGGL(rf_point_block, dim3(R.n - R.n_wave), dim3(kBlock), 0, sm, m->D, m->X, m->Z, A, R.n_wave);
+  LLD_HIP_TRY(hipGetLastError());
+  return LLD_OK;
+}
+
 extern "C" {
 
 int lld_map_refresh_points(lld_map* m, const lld_map_refresh_points_in* in, lld_map_refresh_points_out* out) {

@@ -1,7 +1,8 @@
 // lld_map_tables.h — the resident map's tables as the files that run on them see them: the device pointers (MapDev, MapExt), the host's
 // bookkeeping of the variable-length rows (RowPool) and the handle that owns both (struct lld_map).  lld_map.hip creates, fills and frees
 // them; lld_map_covis.hip and lld_map_ba.hip walk them; lld_map_apply.hip changes rows on the device and makes the RowPools follow;
-// lld_map_refresh.hip rewrites the landmarks' descriptor, normal and distance rows from them.  The grow-only staging pair each of these
+// lld_map_refresh.hip rewrites the landmarks' descriptor, normal and distance rows from them; lld_map_fuse.hip searches a keyframe's rows for
+// duplicates of listed points and moves observation rows between the landmarks it fuses.  The grow-only staging pair each of these
 // call families keeps on the handle is one struct (Staging); how a call travels through it is lld_round_trip.h's.
 // lld_map_internal.h stays the narrow face lld_frame_track.hip sees.  Nothing here is exported.
 #ifndef LLD_MAP_TABLES_H
@@ -157,6 +158,11 @@ inline bool slots_ok(std::vector<uint32_t>& stamp, uint32_t& epoch, int n, const
   return true;
 }
 
+// ComputeDistinctiveDescriptors of n point slots, queued on `sm` behind whatever changed their rows (lld_map_refresh.hip: rf_check_kernel,
+// rf_point_wave, rf_point_block).  slot [n] and list [n] (the queries with a stored row of at most 64 first, n_wave of them) are device
+// arrays the caller uploaded; the others are device scratch of n elements each.  A slot is named at most once.
+struct DescRefresh { int32_t n, n_wave; const int32_t* slot; const int32_t* list; uint8_t* verdict; int32_t* t_ref; int32_t* t_level; int32_t* o_best; int32_t* o_med; uint8_t* o_upd; };
+
 }  // namespace lld_map_dev
 
 struct lld_map {
@@ -175,11 +181,12 @@ struct lld_map {
   lld_map_dev::Staging ba;
   std::vector<double> ba_res_f; std::vector<uint8_t> ba_res_b; int32_t ba_cap[6] = {0, 0, 0, 0, 0, 0};
   std::vector<uint8_t> kf_set;              // lld_map_set_keyframes named the slot since the last clear
+  std::vector<unsigned long long> kf_key;   // ... and the order key it gave it (0: never set): where lld_map_fuse puts a new observation in a row
   // MapPoint::mpRefKF per point slot (lld_map_set_point_refs), -1 unknown: a pool of its own, allocated by the first call
   int32_t* d_ref = nullptr;
   // The window lld_map_ba_window / lld_map_local_ba assembled last, for lld_map_ba_apply: its index arrays are still in ba.h / ba.d at these
   // byte offsets.  valid: the status was 0 and every capacity held; at: `mutations` when it was assembled.  mutations counts every call that
-  // changes a table: lld_map_set_*, lld_map_clear, LLD_MAP_COVIS_WRITE_COV, lld_map_ba_apply.
+  // changes a table: lld_map_set_*, lld_map_clear, LLD_MAP_COVIS_WRITE_COV, lld_map_ba_apply, lld_map_refresh_* and lld_map_fuse when they wrote.
   struct BaStaged {
     bool valid = false; unsigned long long at = 0;
     int32_t n_cams = 0, n_local = 0, n_pts = 0, n_ptobs = 0, n_lns = 0, n_lnobs = 0;
@@ -190,6 +197,7 @@ struct lld_map {
   // the keyframes' descriptor rows (MapDesc): allocated by the first setter that fills them; lld_map_refresh_*'s staging
   lld_map_dev::MapDesc Z{}; char* d_desc = nullptr; size_t desc_bytes = 0; lld_map_dev::RowPool kdesc, kldesc;
   lld_map_dev::Staging rf;
+  lld_map_dev::Staging fu;                  // lld_map_fuse's staging
   bool cov_lds_set = false;                 // map_covis_query_kernel was granted its 64 KB of dynamic LDS
   std::vector<uint32_t> stamp_pt, stamp_kf, stamp_ln; uint32_t epoch = 0;
   // the staging of lld_map_set_*, the event of the last copy out of its pinned block
@@ -199,5 +207,9 @@ struct lld_map {
   bool poisoned = false;                    // a HIP failure after the host bookkeeping of a set call moved: host copy and device tables may differ
   size_t lkf_lds = 0;
 };
+
+namespace lld_map_dev {
+int refresh_descriptors_queue(hipStream_t sm, const lld_map* m, const DescRefresh& R);      // lld_map_refresh.hip
+}
 
 #endif

@@ -49,6 +49,7 @@ class DeviceMap:
         self._bind_ba()
         self._bind_apply()
         self._bind_refresh()
+        self._bind_fuse()
         h = C.c_void_p()
         self.handle = None
         self._check(f("map_create")(ctx.handle, C.byref(self.limits), C.byref(h)), "lld_map_create")
@@ -468,6 +469,55 @@ class DeviceMap:
         self._check(self.lib.fn("map_download_lines")(self.handle, n, s.ctypes.data_as(c_int32_p), r["desc"].ctypes.data_as(c_float_p), r["bad"].ctypes.data_as(c_uint8_p)),
                     "lld_map_download_lines")
         return {k: v[:n] for k, v in r.items()}
+
+    # ------------------------------------------------------------------ duplicate map points fused on the map's tables (lld_map_fuse.hip)
+    def _bind_fuse(self):
+        f = self.lib.fn
+        f("map_fuse").argtypes = [C.c_void_p, C.POINTER(abi.MapFuseIn), C.POINTER(abi.MapFuseOut)]; f("map_fuse").restype = C.c_int
+        f("map_download_point_counts").argtypes = [C.c_void_p, C.c_int32, c_int32_p, c_int32_p]; f("map_download_point_counts").restype = C.c_int
+
+    def fuse(self, target, view, grid, level_scale, level_inv_sigma2, point_slot=None, source_keyframe=-1, th=3.0, n_points=None, survivor_capacity=None,
+             phase_ms=None):
+        """lld_map_fuse: one ORBmatcher::Fuse(pKF, vpMapPoints, th) into keyframe slot `target`.  view: pKF's lld_frame_view (orb_search.FrameView,
+        as orb_search.frame_view builds it); grid: (min_x, min_y, width_inv, height_inv, cols, rows) as lld_orb_search carries them; the candidates
+        are point_slot (-1 = a NULL entry) or, with source_keyframe >= 0, that keyframe's point row as the map holds it.  Returns a dict:
+        n_fused, n_added, n_replaced, match, action, other (per candidate) and survivor.  A refusal raises; the error carries status and
+        n_survivors."""
+        ls = np.ascontiguousarray(level_scale, np.float32); sig = np.ascontiguousarray(level_inv_sigma2, np.float32)
+        a = abi.MapFuseIn()
+        ps = None
+        if point_slot is not None:
+            ps = np.ascontiguousarray(point_slot, np.int32)
+            a.point_slot = ps.ctypes.data_as(c_int32_p)
+        n = (len(ps) if ps is not None else len(self.rows("kf_points", [source_keyframe])[0])) if n_points is None else int(n_points)
+        a.target, a.n_points, a.source_keyframe, a.th = int(target), n, int(source_keyframe), float(np.float32(th))
+        C.memmove(C.byref(a.view), C.byref(view), C.sizeof(abi.FrameViewStruct))
+        a.grid_min_x, a.grid_min_y, a.grid_width_inv, a.grid_height_inv = [float(np.float32(v)) for v in grid[:4]]
+        a.grid_cols, a.grid_rows = int(grid[4]), int(grid[5])
+        a.n_levels = len(ls); a.level_scale = ls.ctypes.data_as(c_float_p); a.level_inv_sigma2 = sig.ctypes.data_as(c_float_p)
+        cap = max(n, 0) if survivor_capacity is None else int(survivor_capacity)
+        r = dict(match=np.full(max(n, 1), -1, np.int32), action=np.zeros(max(n, 1), np.uint8), other=np.full(max(n, 1), -1, np.int32), survivor=np.zeros(max(cap, 1), np.int32))
+        o = abi.MapFuseOut()
+        o.match = r["match"].ctypes.data_as(c_int32_p); o.action = r["action"].ctypes.data_as(c_uint8_p); o.other = r["other"].ctypes.data_as(c_int32_p)
+        o.survivor = r["survivor"].ctypes.data_as(c_int32_p); o.survivor_capacity = cap
+        if phase_ms is not None:
+            assert phase_ms.dtype == np.float32 and phase_ms.size >= 4 and phase_ms.flags.c_contiguous
+            o.phase_ms = phase_ms.ctypes.data_as(c_float_p)
+        st = self.lib.fn("map_fuse")(self.handle, C.byref(a), C.byref(o))
+        if st != abi.LLD_OK:
+            err = RuntimeError(f"lld_map_fuse failed: {self.lib.fn('status_string')(st).decode()}")
+            err.status, err.n_survivors = st, o.n_survivors
+            raise err
+        n = max(n, 0)
+        return dict(n_fused=o.n_fused, n_added=o.n_added, n_replaced=o.n_replaced, match=r["match"][:n], action=r["action"][:n], other=r["other"][:n],
+                    survivor=r["survivor"][:o.n_survivors].copy())
+
+    def point_counts(self, slots):
+        """lld_map_download_point_counts: MapPoint::Observations() of the point slots as the device holds it."""
+        s = np.ascontiguousarray(slots, np.int32); n = len(s)
+        out = np.zeros(max(n, 1), np.int32)
+        self._check(self.lib.fn("map_download_point_counts")(self.handle, n, s.ctypes.data_as(c_int32_p), out.ctypes.data_as(c_int32_p)), "lld_map_download_point_counts")
+        return out[:n]
 
     def set_lines(self, slot, x0, dir, x1, x2, desc, bad):
         k = [self._p(slot, np.int32, c_int32_p), self._p(x0, np.float64, c_double_p), self._p(dir, np.float64, c_double_p), self._p(x1, np.float64, c_double_p),
